@@ -8,11 +8,15 @@ A step = one forward of the whole graph (scann_model.py:329-453) over one batch 
 molecules (configs/model_qm9.yaml: 7 local-attention layers, d=128, 8 heads, g_update) whose packed inputs are
 already resident in HBM.  The packed layout has no per-batch padding, so the engine runs the K steps as
 ceil(K/16) launch sequences over groups of at most 16 concatenated batches (equal sizes +-1): EXACTLY K batches
-of 128 molecules per timed region.  The timed region is bracketed by device sync + rank barrier on both sides and is
-REPEATED until >= 1 s has been measured (after an untimed pre-warm that does not depend on --warmup: the chip needs
-a few hundred ms under load to reach its sustained clock); the reported time is the median over repeats of the
-max-over-ranks region time.  value = molecules of all ranks / that time.  Inference shards by structure with no
+of 128 molecules in the ONE timed region, which is bracketed by device sync + rank barrier on both sides (after --warmup
+steps and an untimed pre-warm that does not depend on --warmup: the chip needs a few hundred ms under load to reach its
+sustained clock); the reported time is the max-over-ranks region time, ms_per_step = that time / K.
+value = molecules of all ranks / that time.  Inference shards by structure with no
 data-path collective ("weak" scaling: per-GPU work fixed); ranks meet through a loopback TCP rendezvous (no torch).
+
+--dump-outputs DIR writes what the last launch sequence of the timed region returned (its y and GlobalAttention scores, the
+arrays Engine.download gives a caller) as DIR/<name>.npy; the inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line with `roofline` (dominant kernel = the fused edge kernel: both bounds are reported,
 `bound` names the tighter one), `one_batch_per_launch`, the host-inclusive `end_to_end` rate and `cpu_baseline`
@@ -21,7 +25,6 @@ Rank 0 prints ONE JSON line with `roofline` (dominant kernel = the fused edge ke
 import argparse
 import importlib.util
 import json
-import math
 import os
 import sys
 import time
@@ -190,6 +193,23 @@ def group_sizes(steps, target=16):
     return [base + 1] * rem + [base] * (n - rem)
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: every rank's files together
+
+
+def dump_outputs(out_dir, arrays, suffix="", world=1):
+    """`arrays` -> out_dir/<name><suffix>.npy as float32.  An array larger than its share of DUMP_BYTES is replaced by a fixed, seeded
+    sample of its elements (same indices in every run with the same shapes), so that two runs stay comparable element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // (len(arrays) * world)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def scaling_fields(world, units_per_rank_region, rank_region_s, solo_region_s=None, rccl_ranks=None):
     """What a SCALE record can be checked against, from one N-rank run: `rccl_ranks` = the size RCCL itself reports for the
     communicator (ncclCommCount after scann_comm_init; None on the collective-free inference path), `rank_values` = every rank's OWN
@@ -258,7 +278,7 @@ def train_bench(args, eng, rdzv):
             inflight[0] -= 1
         eng.sync()
 
-    steps, warm = min(args.steps, 400), max(min(args.warmup, 20), 5)
+    steps, warm = args.steps, max(min(args.warmup, 20), 5)
     for i in range(warm):
         step(i)
     drain()
@@ -590,7 +610,6 @@ def main():
     ap.add_argument("--config", default="qm9", choices=["qm9", "qm9_std", "mp2018"],
                     help="qm9 = BASELINE configs[1] (the metric); qm9_std = configs[4] (SCANN+ L=8, QM9 shapes), mp2018 = configs[3] "
                          "shapes (crystals, L=9, batch 64): extras")
-    ap.add_argument("--min-time", type=float, default=1.0, help="seconds of timed regions to collect (median over repeats)")
     ap.add_argument("--prewarm", type=float, default=0.6, help="seconds of untimed load before the first timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
@@ -605,8 +624,14 @@ def main():
                     help="rehearsal only: allow more ranks than visible devices (rank r runs on device r %% n_devices); the line "
                          "is then marked \"oversubscribed\" and is not a scaling measurement")
     ap.add_argument("--profile-reps", type=int, default=12)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the timed region's last launch sequence as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument("--leg", default=None, choices=sorted(LEGS), help="internal: run one extra leg in this process and print its dict")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.train:
+        ap.error("--dump-outputs dumps the forward benchmark's outputs; it does not apply to --train")
     if args.leg:
         return run_leg_here(args.leg, args.batch, args.config)
 
@@ -673,41 +698,34 @@ def main():
     while time.perf_counter() - t_pw < args.prewarm:
         run(sizes_t)
         eng.sync()
+    if rank == 0:  # HIP events around the edge-kernel launches of sampled forwards: the first, then every n-th -- at most one in 16
+        eng.edge_timing(max(16, len(sizes_t) // 64))  # (the event records cost a sampled forward a little), ~64 of a long region
+    eng.sync()
+    rdzv.barrier()
     t0 = time.perf_counter()
     run(sizes_t)
+    t_issue = time.perf_counter() - t0  # host time to enqueue every launch (diagnostic: host- vs device-bound)
     eng.sync()
-    est = rdzv.allreduce_max(time.perf_counter() - t0)
-    repeats = int(min(4000, max(3, math.ceil(args.min_time / max(est, 1e-6))))) | 1  # odd: the median is a measured region
-    if rank == 0:  # HIP events around the edge-kernel launches of sampled forwards, on their own streams (<= ~64 forwards)
-        eng.edge_timing(max(1, repeats * len(sizes_t) // 64))
-    times, t_issue = [], 0.0
-    for _ in range(repeats):
-        eng.sync()
-        rdzv.barrier()
-        t0 = time.perf_counter()
-        run(sizes_t)
-        t1 = time.perf_counter()
-        eng.sync()
-        times.append(time.perf_counter() - t0)
-        t_issue += t1 - t0  # host time to enqueue every launch (diagnostic: host- vs device-bound)
-        rdzv.barrier()
-    all_times = rdzv.gather(times)
+    t_region = time.perf_counter() - t0
+    rdzv.barrier()
+    all_times = rdzv.gather([t_region])
+    if args.dump_outputs:
+        last = resident[sizes_t[-1]][(len(sizes_t) - 1) % len(resident[sizes_t[-1]])]
+        y, ga = eng.download(last)
+        dump_outputs(args.dump_outputs, {"y": y, "ga": ga}, "" if world == 1 else "_rank%d" % rank, world)
     solo = None
-    if world > 1:  # N = 1 inside this run: rank 0 repeats the timed region alone while the other ranks wait at the barrier
+    if world > 1:  # N = 1 inside this run: rank 0 runs the timed region again alone while the other ranks wait at the barrier
         if rank == 0:
-            ts = []
-            for _ in range(min(repeats, 101)):
-                eng.sync()
-                t0 = time.perf_counter()
-                run(sizes_t)
-                eng.sync()
-                ts.append(time.perf_counter() - t0)
-            solo = float(np.median(ts))
+            eng.sync()
+            t0 = time.perf_counter()
+            run(sizes_t)
+            eng.sync()
+            solo = time.perf_counter() - t0
         rdzv.barrier()
 
     if rank == 0:
-        per_repeat = np.max(np.asarray(all_times, dtype=np.float64), axis=0)  # max over ranks of every timed region
-        elapsed = float(np.median(per_repeat))
+        rank_times = [float(t[0]) for t in all_times]
+        elapsed = max(rank_times)  # the job's time: the slowest rank's
         live_us, live_n, live_edges = eng.edge_timing_read()
         eng.edge_timing(0)
         # sequential per-kernel durations of one forward (scann_forward_profile), largest timed group
@@ -787,14 +805,12 @@ def main():
                        "batch": args.batch, "atoms_per_batch": A, "edges_per_batch": E,
                        "streams": nstream, "batches_fused_per_launch": G_eff, "launch_groups": sorted(set(sizes_t)),
                        "parallelism": "dp%d (independent shards, no collective)" % world},
-            "timing": {"repeats": repeats, "timed_region_ms_median": elapsed * 1e3, "timed_region_ms_min": float(per_repeat.min()) * 1e3,
-                       "timed_region_ms_max": float(per_repeat.max()) * 1e3, "prewarm_s": args.prewarm,
-                       "rank_median_ms": [float(np.median(t)) * 1e3 for t in all_times],
-                       "rule": "each repeat = EXACTLY --steps batches between sync+barrier pairs; value from the median repeat (max over ranks)"},
-            "host_issue_ms_per_step": t_issue / repeats / args.steps * 1e3,
+            "timing": {"timed_region_ms": elapsed * 1e3, "prewarm_s": args.prewarm, "rank_region_ms": [t * 1e3 for t in rank_times],
+                       "rule": "ONE timed region = EXACTLY --steps batches between sync+barrier pairs; its time = the slowest rank's"},
+            "host_issue_ms_per_step": t_issue / args.steps * 1e3,
             "whole_path_tflops_min": world * args.steps * total_flops_min(A, E, L_cfg, emb_cfg) / elapsed / 1e12,
             "roofline": roof,
-            **scaling_fields(world, args.steps * args.batch, [float(np.median(t)) for t in all_times], solo, None),
+            **scaling_fields(world, args.steps * args.batch, rank_times, solo, None),
         }
         if world > ndev:
             out["oversubscribed"] = True

@@ -114,13 +114,22 @@ _lib = None
 _pinned = False  # the process has pinned itself to its device's cores (Engine.__init__, multi-rank runs)
 
 
+def _hw_queue_advice(n, fix):
+    """The warning _check_hw_queues gives for ``n`` hardware queues per process (None: nothing to say); ``fix``: SCANN_FIX_HW_QUEUES=1."""
+    if n <= 4:
+        return None
+    return ("GPU_MAX_HW_QUEUES=%d: with more than 4 hardware queues a stream waiting on a later-created stream stalls ~2 ms "
+            "per wait (trainer.fit: 3x slower, profiles/r03_notes.md); %s" % (n, "SCANN_FIX_HW_QUEUES=1: unset, ROCm's default applies to "
+            "this process (effective only if HIP has not started yet)" if fix else "left as set -- SCANN_FIX_HW_QUEUES=1 unsets it"))
+
+
 def _check_hw_queues():
     """``GPU_MAX_HW_QUEUES`` above ROCm's default of 4 makes a stream that waits for an event of a later-created stream (the upload
     copy stream, the basis-gradient stream of the training step) stall ~2 ms per wait: two queues time-sliced on one hardware pipe,
-    the waiter holding it.  Measured (profiles/r03_notes.md, tools/queue_matrix.sh): ``trainer.fit`` 0.93 -> 2.85 ms per step with
+    the waiter holding it.  Measured (profiles/r03_notes.md): ``trainer.fit`` 0.93 -> 2.85 ms per step with
     6-16 queues and 2-3 streams per handle; inference is unaffected.  The variable is the PROCESS's (torch and RCCL in the same process
-    read it too), so importing this package only SAYS so; ``SCANN_FIX_HW_QUEUES=1`` asks for the value to be put back to 4 -- which works
-    only because the HIP runtime reads it at its first call, i.e. if nothing in the process has touched HIP yet."""
+    read it too), so importing this package only SAYS so; ``SCANN_FIX_HW_QUEUES=1`` asks for the variable to be removed, i.e. ROCm's
+    default -- which works only because the HIP runtime reads it at its first call, i.e. if nothing in the process has touched HIP yet."""
     v = os.environ.get("GPU_MAX_HW_QUEUES")
     if not v:
         return
@@ -128,16 +137,14 @@ def _check_hw_queues():
         n = int(v)
     except ValueError:
         return
-    if n > 4:
+    fix = os.environ.get("SCANN_FIX_HW_QUEUES") == "1"
+    msg = _hw_queue_advice(n, fix)
+    if msg:
         import warnings
 
-        fix = os.environ.get("SCANN_FIX_HW_QUEUES") == "1"
-        warnings.warn("GPU_MAX_HW_QUEUES=%d: with more than 4 hardware queues a stream waiting on a later-created stream stalls ~2 ms "
-                      "per wait (trainer.fit: 3x slower, profiles/r03_notes.md); %s" % (n, "SCANN_FIX_HW_QUEUES=1: using 4 for this process "
-                      "(effective only if HIP has not started yet)" if fix else "left as set -- SCANN_FIX_HW_QUEUES=1 puts it back to 4"),
-                      RuntimeWarning, stacklevel=3)
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
         if fix:
-            os.environ["GPU_MAX_HW_QUEUES"] = "4"
+            del os.environ["GPU_MAX_HW_QUEUES"]
 
 
 def _check_runtime_env():

@@ -696,7 +696,7 @@ def test_bench_two_ranks_through_the_self_spawning_launcher(hip_lib):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ndev = hip_lib.scann_device_count()
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-extras",
-           "--min-time", "0.2", "--prewarm", "0.1", "--pool", "32"] + (["--oversubscribe"] if ndev < 2 else [])
+           "--prewarm", "0.1", "--pool", "32"] + (["--oversubscribe"] if ndev < 2 else [])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -35,7 +35,7 @@ SHAPES = {"g10": (20, 10), "g16": (64, 16)}  # bench --steps / --warmup: the dri
 def one_pass(name, counters, steps, warm):
     d = os.path.join(OUT, name)
     cmd = ["rocprofv3", "--pmc"] + counters + ["--output-format", "csv", "-d", d, "--", "python3", os.path.join(ROOT, "bench.py"), "--no-extras",
-           "--steps", str(steps), "--warmup", str(warm), "--min-time", "0.3", "--prewarm", "0.3"]
+           "--steps", str(steps), "--warmup", str(warm), "--prewarm", "0.3"]
     with open(d + ".log", "w") as log:
         rc = subprocess.run(cmd, stdout=log, stderr=subprocess.STDOUT, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp")).returncode
     ok = bool(glob.glob(os.path.join(d, "*", "*counter_collection.csv")))

@@ -9,7 +9,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 warm=$(( steps < 32 ? steps / 2 : 16 ))   # warm-up launches of the same group size as the measured ones
-args="$root/bench.py --no-extras --steps $steps --warmup $warm --min-time 0.3 --prewarm 0.3"
+args="$root/bench.py --no-extras --steps $steps --warmup $warm --prewarm 0.3"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -- python3 $root/bench.py --no-extras --steps 400 > $out/prof_$tag.log 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_${tag}_sq -- python3 $args > $out/pmc_${tag}_sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_ANY --output-format csv -d $out/pmc_${tag}_sq2 -- python3 $args > $out/pmc_${tag}_sq2.log 2>&1

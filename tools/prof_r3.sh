@@ -5,11 +5,11 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r3_g16 -- python3 $R/bench.py --no-extras --steps 400 > $O/prof_r3_g16.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r3_g10 -- python3 $R/bench.py --no-extras --steps 20 --warmup 5 > $O/prof_r3_g10.log 2>&1
 for tag in g16:64 g10:20; do t=${tag%%:*}; st=${tag##*:}; warm=$(( st < 32 ? st / 2 : 16 ))
- args="$R/bench.py --no-extras --steps $st --warmup $warm --min-time 0.3 --prewarm 0.3"
+ args="$R/bench.py --no-extras --steps $st --warmup $warm --prewarm 0.3"
  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_r3${t}_fetch -- python3 $args > $O/pmc_r3${t}_fetch.log 2>&1
  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_r3${t}_write -- python3 $args > $O/pmc_r3${t}_write.log 2>&1
 done
-args="$R/bench.py --no-extras --steps 64 --warmup 16 --min-time 0.3 --prewarm 0.3"
+args="$R/bench.py --no-extras --steps 64 --warmup 16 --prewarm 0.3"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_r3g16_sq -- python3 $args > $O/pmc_r3g16_sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc_r3g16_sq2 -- python3 $args > $O/pmc_r3g16_sq2.log 2>&1
 rocprofv3 --pmc TA_TA_BUSY_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TA_BUSY_avr --output-format csv -d $O/pmc_r3g16_ta -- python3 $args > $O/pmc_r3g16_ta.log 2>&1

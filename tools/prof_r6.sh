@@ -17,7 +17,7 @@ head -8 $O/r06_kernel_stats_g16.csv; head -8 $O/r06_kernel_stats_g10.csv
 cd $R
 for tag in g10:20 g16:64; do t=${tag%%:*}; st=${tag##*:}; warm=$(( st < 32 ? st / 2 : 16 ))
   python3 tools/pmc_r6.py r06f $t 2>&1 | tee -a $O/r06f_pmc.log
-  args="$R/bench.py --no-extras --steps $st --warmup $warm --min-time 0.3 --prewarm 0.3"
+  args="$R/bench.py --no-extras --steps $st --warmup $warm --prewarm 0.3"
   ( cd /tmp && rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_r06f${t}_fetch -- python3 $args > $O/pmc_r06f${t}_fetch.log 2>&1
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_r06f${t}_write -- python3 $args > $O/pmc_r06f${t}_write.log 2>&1 )
   python3 tools/pmc_report.py r06f$t --traffic qm9_$t > /dev/null
