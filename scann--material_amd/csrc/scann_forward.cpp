@@ -1,0 +1,495 @@
+// Forward launch schedules -- run_forward (the split-fp16 MFMA kernels and their exact-fp32 instantiations), run_forward_generic
+// (the plain-fp32 kernels of other widths) -- and the entry points that run, time or inspect one forward.
+#include "scann_runtime.h"
+
+namespace {
+
+// Events that only time kernels on one stream: no system-scope cache write-back / invalidate when they fire (the HIP headers' own
+// advice for timing events), so that a sampled launch is not lengthened by its own measurement.
+constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
+
+int ensure_debug(scann_handle* h, scann_dbatch* db) {
+  const int L = h->cfg.n_attention;
+  if (db->dbg_layers == L) return SCANN_OK;
+  HIPCHK(h, cached_malloc((void**)&db->dbg_c, (size_t)(L + 1) * db->n_atom * D * 4));
+  HIPCHK(h, cached_malloc((void**)&db->dbg_ctx, (size_t)std::max(L, 1) * db->n_atom * D * 4));
+  if (h->cfg.g_update) HIPCHK(h, cached_malloc((void**)&db->dbg_g, (size_t)(L + 1) * std::max(db->n_edge, 1) * D * 4));
+  db->dbg_layers = L;
+  return SCANN_OK;
+}
+
+// create_model (scann_model.py:362-447) for a handle whose widths are not 128 / 8: one plain-fp32 kernel per formula
+// (scann_generic.hip) on the same packed batch.  kp non-null: the training forward -- Dropout layers active (kp->drop_p, kp->attn_p,
+// kp->seed), every intermediate kept in kp, the property head as dense launches.
+int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKeep* kp = nullptr) {
+  const scann_config_t& c = h->cfg;
+  const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
+  const int d = c.local_dim, dg = c.global_dim, dout = c.dense_out, H = c.num_head, emb = c.embedding_dim;
+  const int cin = emb + (c.use_ring ? 10 : 0);
+  if (kp) kp->dbg.clear();  // (scann_train_debug_read: the tensors it names belong to the backward of THIS forward's arena)
+  if ((size_t)std::max(1, db->max_degree) * H * 4 * (kp ? 3 : 1) > 60000 || ((size_t)db->max_atoms * (kp ? 3 : 1) + dg + dout + 4) * 4 > 60000 ||
+      (size_t)4 * 3 * d * 4 > 60000)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "forward (generic widths): an atom's neighbours x heads, or a structure's atoms, exceed one workgroup's LDS");
+  auto W = [&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
+  // workspace: atom rows, edge rows, Gaussian bases
+  const size_t fA = (size_t)A, fE = (size_t)std::max(E, 1), fB = (size_t)B, Ls = (size_t)L;
+  float* p = nullptr;
+  char* p_end = nullptr;
+  if (!kp) {
+    const size_t need = 4 * (fA * (5 * (size_t)d + (size_t)cin + (size_t)emb + 10 + 3 * (size_t)dg) + fE * (3 * (size_t)d + 2 * NG)) + 4096;
+    if (db->gen_ws_bytes < need) {
+      HIPCHK(h, hipStreamSynchronize(s));
+      cached_free(db->gen_ws);
+      db->gen_ws = nullptr;
+      db->gen_ws_bytes = 0;
+      HIPCHK(h, cached_malloc((void**)&db->gen_ws, need));
+      db->gen_ws_bytes = need;
+    }
+    p = reinterpret_cast<float*>(db->gen_ws);
+    p_end = db->gen_ws + db->gen_ws_bytes;
+  } else {
+    const size_t need = 4 * (fA * ((size_t)emb + 10 + (2 + 7 * Ls) * (size_t)d + 4 * (size_t)dg) + fE * (2 * NG + (5 + 4 * Ls) * (size_t)d) +
+                             fB * ((size_t)dg + 2 * (size_t)dout + 1)) + 256 * (32 + 12 * Ls);
+    if (kp->bytes < need) {
+      HIPCHK(h, hipStreamSynchronize(s));
+      cached_free(kp->arena);
+      kp->arena = nullptr;
+      kp->bytes = 0;
+      HIPCHK(h, cached_malloc((void**)&kp->arena, need));
+      kp->bytes = need;
+    }
+    p = reinterpret_cast<float*>(kp->arena);
+    p_end = kp->arena + kp->bytes;
+    kp->layer.assign((size_t)L, GenLayerKeep{});
+  }
+  auto take = [&](size_t n) { float* q = p; p += (n + 63) & ~(size_t)63; return q; };
+  float *cc = take(fA * d), *ctx = nullptr, *t1 = nullptr, *t2 = nullptr, *q = nullptr;
+  if (!kp) { ctx = take(fA * d); t1 = take(fA * d); t2 = take(fA * d); q = take(fA * d); }
+  float *embE = take(fA * emb), *ring10 = take(fA * 10);
+  float *z = take(fA * dg), *gq = take(fA * dg), *gk = take(fA * dg);
+  float *G = take(fE * d), *T = nullptr, *K = nullptr, *gd = take(fE * NG), *gw = take(fE * NG);
+  if (!kp) { T = take(fE * d); K = take(fE * d); }
+  const float tp = kp ? kp->drop_p : 0.f;
+  const unsigned long long seed = kp ? kp->seed : 0;
+  auto dense = [&](GenSeg s0, GenSeg s1, GenSeg s2, int n_seg, int prod, const std::string& name, int K_, int N_, int rows, int act,
+                   const float* res, const float* row_scale, float* Y, float* pre = nullptr, float drop_p = 0.f, unsigned drop_tag = 0) {
+    GenDenseArgs a{};
+    a.seg[0] = s0; a.seg[1] = s1; a.seg[2] = s2; a.n_seg = n_seg; a.prod = prod;
+    a.W = W(name + "/kernel"); a.b = W(name + "/bias"); a.K = K_; a.N = N_; a.rows = rows; a.act = act;
+    a.res = res; a.res_idx = nullptr; a.row_scale = row_scale; a.Y = Y;
+    a.pre = pre; a.drop_p = drop_p; a.drop_tag = drop_tag; a.drop_seed = seed;
+    launch_gen_dense(a, s);
+  };
+  const GenSeg none{nullptr, nullptr, 0};
+  // ---- embedding (scann_model.py:362-374; Dropout(0.1) on the centres in training, :374) ----
+  float* pre_e = kp ? take(fA * d) : nullptr;
+  GenSeg e0;
+  if (c.feature_cgcnn) {
+    dense(GenSeg{db->cgcnn, nullptr, 92}, none, none, 1, 0, "embed_atom", 92, emb, A, 0, nullptr, nullptr, embE);
+    e0 = GenSeg{embE, nullptr, emb};
+  } else {
+    e0 = GenSeg{W("embed_atom/embeddings"), db->atomic, emb};
+  }
+  if (c.use_ring) {
+    dense(GenSeg{db->ring, nullptr, 2}, none, none, 1, 0, "extra_embed", 2, 10, A, 0, nullptr, nullptr, ring10);
+    dense(e0, GenSeg{ring10, nullptr, 10}, none, 2, 0, "dense_embed", emb + 10, d, A, 1, nullptr, nullptr, cc, pre_e, tp, DROP_TAG_EMBED);
+  } else {
+    dense(e0, none, none, 1, 0, "dense_embed", emb, d, A, 1, nullptr, nullptr, cc, pre_e, tp, DROP_TAG_EMBED);
+  }
+  if (kp) { kp->embE = embE; kp->ring10 = ring10; kp->pre_e = pre_e; kp->cc0 = cc; kp->gd = gd; kp->gw = gw; }
+  // ---- Gaussian bases and the initial geometry (scann_model.py:376-391) ----
+  launch_gen_gauss(db->dist, h->g_centres, E, gd, s);
+  if (c.g_update) {
+    launch_gen_gauss(db->weight, h->g_centres + NG, E, gw, s);
+    float *Td = kp ? take(fE * d) : T, *Tw = kp ? take(fE * d) : K;
+    float *pre_d = kp ? take(fE * d) : nullptr, *pre_w = kp ? take(fE * d) : nullptr;
+    dense(GenSeg{gd, nullptr, NG}, none, none, 1, 0, "neighbor_d", NG, d, E, 1, nullptr, nullptr, Td, pre_d);
+    dense(GenSeg{gw, nullptr, NG}, none, none, 1, 0, "neighbor_w", NG, d, E, 1, nullptr, nullptr, Tw, pre_w);
+    launch_gen_mul(Td, Tw, (size_t)E * d, G, s);
+    if (kp) { kp->Td = Td; kp->Tw = Tw; kp->pre_d = pre_d; kp->pre_w = pre_w; kp->G0 = G; }
+  }
+  // ---- LocalAttention iterations (scann_model.py:413-421; attention.py:118-216, :37-40) ----
+  for (int l = 0; l < L; ++l) {
+    const std::string la = "local_attention_" + std::to_string(l), rn = "residual_norm_" + std::to_string(l);
+    GenLayerKeep b;
+    b.cc_in = cc; b.G_in = G;
+    if (kp) {
+      b.Z = take(fE * d); b.Gn = take(fE * d); b.K = take(fE * d);
+      if (c.g_update) b.T = take(fE * d);
+      b.q = take(fA * d); b.t1 = take(fA * d); b.ctx = take(fA * d);
+      if (c.use_attn_norm) { b.pre1 = take(fA * d); b.h1 = take(fA * d); b.t2 = take(fA * d); b.cc_out = take(fA * d); }
+      else b.cc_out = b.ctx;
+    } else {
+      b.T = T; b.Gn = c.g_update ? G : T; b.K = K; b.q = q; b.t1 = t1; b.ctx = ctx; b.h1 = t1; b.t2 = t2;
+      b.cc_out = c.use_attn_norm ? cc : ctx;
+    }
+    if (c.g_update) {
+      dense(GenSeg{cc, db->edge_row, d}, GenSeg{G, nullptr, d}, GenSeg{cc, db->edge_col, d}, 3, 0, la + "/filter_geo", 3 * d, d, E, 1, G, nullptr, b.T, b.Z);
+      launch_gen_layernorm(b.T, nullptr, W(la + "/layer_norm_g/gamma"), W(la + "/layer_norm_g/beta"), E, d, b.Gn, s);
+    } else {
+      dense(GenSeg{gd, nullptr, NG}, none, none, 1, 0, la + "/filter_geo", NG, d, E, 1, nullptr, db->weight, b.Gn, b.Z);
+    }
+    dense(GenSeg{cc, db->edge_col, d}, GenSeg{b.Gn, nullptr, d}, none, 2, 1, la + "/key", d, d, E, 0, nullptr, nullptr, b.K);
+    dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, la + "/query", d, d, A, 0, nullptr, nullptr, b.q);
+    launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed);
+    launch_gen_layernorm(b.t1, nullptr, W(la + "/layer_norm/gamma"), W(la + "/layer_norm/beta"), A, d, b.ctx, s);
+    if (c.use_attn_norm) {  // ResidualNorm (attention.py:37-40): LayerNorm(x + Dropout(dense_2(swish(dense_1 x))))
+      dense(GenSeg{b.ctx, nullptr, d}, none, none, 1, 0, rn + "/dense_1", d, d, A, 1, nullptr, nullptr, b.h1, b.pre1);
+      dense(GenSeg{b.h1, nullptr, d}, none, none, 1, 0, rn + "/dense_2", d, d, A, 0, nullptr, nullptr, b.t2, nullptr, tp, (unsigned)l);
+      launch_gen_layernorm(b.ctx, b.t2, W(rn + "/layer_norm/gamma"), W(rn + "/layer_norm/beta"), A, d, b.cc_out, s);
+    }
+    if (kp) {
+      kp->layer[(size_t)l] = b;
+      cc = b.cc_out;
+      if (c.g_update) G = b.Gn;
+    } else if (!c.use_attn_norm) {
+      std::swap(cc, ctx);
+    }
+  }
+  // ---- readout (scann_model.py:424-447; attention.py:267-318) ----
+  float* z_pre = kp ? take(fA * dg) : nullptr;
+  dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, "after_Lc", d, dg, A, 1, nullptr, nullptr, z, z_pre);
+  dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/query", dg, dg, A, 0, nullptr, nullptr, gq);
+  dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/key", dg, dg, A, 0, nullptr, nullptr, gk);
+  float* rep = kp ? take(fB * dg) : nullptr;
+  launch_gen_readout(db->mol_offset, B, db->max_atoms, gq, gk, dg, dout, c.use_ga_norm, c.relu_out, W("bf_property/kernel"), W("bf_property/bias"),
+                     W("predict_property/kernel"), W("predict_property/bias"), db->ga, db->y, s, rep);
+  if (kp) {
+    float *hid_pre = take(fB * dout), *hid = take(fB * dout);
+    dense(GenSeg{rep, nullptr, dg}, none, none, 1, 0, "bf_property", dg, dout, B, 1, nullptr, nullptr, hid, hid_pre);
+    dense(GenSeg{hid, nullptr, dout}, none, none, 1, 0, "predict_property", dout, 1, B, 0, nullptr, nullptr, db->y);
+    if (c.relu_out) launch_gen_relu(db->y, B, s);  // mrelu forward (custom_layers.py:15); its gradient is the identity
+    kp->cc_L = cc; kp->z_pre = z_pre; kp->z = z; kp->gq = gq; kp->gk = gk; kp->rep = rep; kp->hid_pre = hid_pre; kp->hid = hid;
+  }
+  if (reinterpret_cast<char*>(p) > p_end) return fail(h, SCANN_ERR_HIP, "forward (generic widths): workspace overrun");
+  HIPCHK(h, hipGetLastError());
+  return SCANN_OK;
+}
+
+}  // namespace
+
+namespace scann {
+
+struct Timer {
+  hipStream_t s;
+  bool on;
+  std::vector<hipEvent_t> ev;
+  std::vector<int> kind;
+  void mark(int k) {
+    if (!on) return;
+    hipEvent_t e;
+    (void)hipEventCreateWithFlags(&e, kTimingEventFlags);
+    (void)hipEventRecord(e, s);
+    ev.push_back(e);
+    kind.push_back(k);
+  }
+};
+
+// The forward graph of create_model (scann_model.py:362-447) as a launch schedule on one stream.
+// kind codes for the timer: 0 basis, 1 atom, 2 edge, 3 readout.
+int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, bool exact) {
+  if ((h->force_exact || h->weights_exact) && !h->debug && !h->in_train_forward) exact = true;
+  db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
+  HIPCHK(h, wait_upload(db, s));  // the inputs' copy (scann_batch_upload returned when it was enqueued)
+  if (h->generic) {
+    if (tm) { tm->mark(-1); }
+    const int r = run_forward_generic(h, db, s, h->in_train_forward ? h->gen_keep : nullptr);
+    if (tm) tm->mark(3);
+    return r;
+  }
+  const scann_config_t& c = h->cfg;
+  const int L = c.n_attention;
+  if (h->debug) {
+    const int r = ensure_debug(h, db);
+    if (r) return r;
+  }
+  // keep-mode (training / scann_set_debug): every layer writes its centres, context and geometry straight into its slice of
+  // the per-layer buffers (base branch: no geometry to thread)
+  const size_t nA_ = (size_t)db->n_atom * D, nE_ = (size_t)db->n_edge * D;
+  auto c_of = [&](int l) { return h->debug ? db->dbg_c + (size_t)l * nA_ : db->c; };
+  auto ctx_of = [&](int l) { return h->debug ? db->dbg_ctx + (size_t)l * nA_ : db->ctx; };
+  auto g_of = [&](int l) { return h->debug && c.g_update ? db->dbg_g + (size_t)l * nE_ : db->geom; };
+  int32_t* const rflag = h->range_flag ? h->range_flag + db->last_slot : nullptr;  // this stream's range-guard word
+  if (tm) tm->mark(-1);
+  // exact: the forward's range guard fired (an operand outside the split-fp16 range): the same launches on the EX instantiations of
+  // the atom / edge kernels -- exact-fp32 projections -- with the plain first layer (basis_kernel, no per-species tables)
+  // inference: the first layer's edge kernel computes its geometry rows from (dist, weight) itself -- geom0 is never written by a
+  // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
+  const bool fuse_basis = !exact && h->fuse_basis && c.g_update && L > 0 && !h->debug && !h->in_train_forward && db->n_edge > 0;
+  if (!fuse_basis) {
+    if (c.g_update) launch_basis(h->basis, db->dist, db->weight, db->n_edge, g_of(0), s);
+    else launch_basis_raw(h->cd, db->dist, db->n_edge, db->gd, s);
+  }
+  if (tm) tm->mark(0);
+
+  const bool general_embed = c.use_ring || c.feature_cgcnn;
+  if (general_embed) {
+    EmbedArgs e = h->embed;
+    e.n_atom = db->n_atom; e.atomic = db->atomic; e.c0 = db->c0;
+    e.ring = c.use_ring ? db->ring : nullptr;
+    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+    launch_embed(e, s);
+    if (tm) tm->mark(0);
+  }
+  // first layer from per-species tables: no atom launch at all (see EdgeArgs::species)
+  // (not with chunked atoms: edge_merge_kernel reads the query rows per atom)
+  const bool species0 = fuse_basis && h->species_tables && !general_embed && h->train_drop_p == 0.f && h->sp_c && db->n_big == 0;
+  if (species0 && h->sp_dirty) {
+    AtomArgs a{};
+    a.n_atom = c.n_atoms; a.x = h->lut; a.ffn = 0; a.c = h->sp_c;
+    a.range_flag = rflag; a.layer = 0;
+    const LayerParams& p = h->layers[0];
+    a.mode = 0;
+    a.WAh = p.W1h; a.bA = p.bg; a.WBh = p.W3h; a.WCh = p.Wqh; a.bC = p.bq;
+    a.oA = h->sp_P1; a.oB = h->sp_P3; a.oC = h->sp_q;
+    launch_atom(a, s);
+    HIPCHK(h, hipStreamSynchronize(s));  // once per weight change: forwards on the handle's other streams read the tables too
+    h->sp_dirty = false;
+  }
+  for (int l = 0; l <= L; ++l) {
+    // training forward through edge_kernel_lean: q, V, T, ang, K of every layer are kept for the backward
+    const bool keep = h->debug && h->in_train_forward && db->keep_K && l < L;
+    // atom kernel at the head of layer l: ResidualNorm of layer l-1, centres, projections of layer l
+    AtomArgs a{};
+    a.n_atom = db->n_atom;
+    if (l == 0) {
+      a.x = general_embed ? db->c0 : h->lut;
+      a.x_index = general_embed ? nullptr : db->atomic;
+      a.ffn = 0;
+    } else {
+      a.x = ctx_of(l - 1);
+      a.x_index = nullptr;
+      a.ffn = c.use_attn_norm ? 1 : 0;
+      const LayerParams& pp = h->layers[l - 1];
+      a.Wf1h = pp.Wf1h; a.bf1 = pp.bf1; a.Wf2h = pp.Wf2h; a.bf2 = pp.bf2; a.lnr_g = pp.lnr_g; a.lnr_b = pp.lnr_b;
+      if (a.ffn && h->debug && h->in_train_forward && db->keep_T2) {
+        a.keep_pre1 = db->keep_pre1 + (size_t)(l - 1) * nA_; a.keep_H1 = db->keep_H1 + (size_t)(l - 1) * nA_;
+        a.keep_T2 = db->keep_T2 + (size_t)(l - 1) * nA_;
+      }
+    }
+    a.c = c_of(l);
+    a.range_flag = rflag; a.layer = l;
+    if (h->train_drop_p > 0.f) {  // training-mode Dropout(0.1) layers (scann_model.py:374, attention.py:29)
+      a.drop_p = (l == 0 || c.use_attn_norm) ? h->train_drop_p : 0.f;
+      a.drop_seed = h->train_seed;
+      a.drop_tag = l == 0 ? DROP_TAG_EMBED : (unsigned)(l - 1);
+    }
+    if (l < L) {
+      const LayerParams& p = h->layers[l];
+      a.mode = c.g_update ? 0 : 1;
+      a.WAh = p.W1h; a.bA = p.bg; a.WBh = p.W3h; a.WCh = p.Wqh; a.bC = p.bq;
+      a.oA = db->P1; a.oB = db->P3; a.oC = keep ? db->keep_q + (size_t)l * nA_ : db->q;
+    } else {
+      a.mode = 2;
+      a.WAh = h->head.Wah; a.bA = h->head.ba; a.WCh = h->head.Wgqh; a.bC = h->head.bgq; a.WDh = h->head.Wgkh; a.bD = h->head.bgk;
+      a.oB = db->gk; a.oC = db->gq;
+      if (h->debug && h->in_train_forward && db->keep_preA) { a.keep_preA = db->keep_preA; a.keep_z = db->keep_z; }
+    }
+#ifdef SCANN_STAMPS
+    if (getenv("SCANN_STAMP_ATOM") && l >= 1 && l < L) {  // phase clocks of atom_kernel<true, 0> (the last such launch wins)
+      const int nt = (db->n_atom + 31) / 32;  // 32- or 64-row tiles (launch_atom): room for either
+      if (!db->stamps) HIPCHK(h, hipMalloc((void**)&db->stamps, (size_t)nt * 16 * sizeof(unsigned long long)));
+      a.stamps = db->stamps;
+      db->n_stamp = nt;
+    }
+#endif
+    if (exact) {  // fp32 fragment-order images in place of the split-fp16 ones
+      a.exact = 1;
+      if (l > 0 && a.ffn) {
+        const LayerParams& pp = h->layers[l - 1];
+        a.Wf1h = reinterpret_cast<const _Float16*>(pp.Wf1p); a.Wf2h = reinterpret_cast<const _Float16*>(pp.Wf2p);
+      }
+      if (l < L) {
+        const LayerParams& p = h->layers[l];
+        a.WAh = reinterpret_cast<const _Float16*>(p.W1p); a.WBh = reinterpret_cast<const _Float16*>(p.W3p);
+        a.WCh = reinterpret_cast<const _Float16*>(p.Wqp);
+      } else {
+        a.WAh = reinterpret_cast<const _Float16*>(h->head.Wap); a.WCh = reinterpret_cast<const _Float16*>(h->head.Wgqp);
+        a.WDh = reinterpret_cast<const _Float16*>(h->head.Wgkp);
+      }
+    }
+    if (!(species0 && l == 0)) launch_atom(a, s);
+    if (tm) tm->mark(l < L ? 1 : 3);
+    if (l == L) break;
+    EdgeArgs ea{};
+    ea.tiles = db->tiles; ea.n_tile = db->n_tile; ea.g_update = c.g_update; ea.tile_rows = db->tile_rows;
+    ea.edge_offset = db->edge_offset; ea.edge_col = db->edge_col; ea.edge_row = db->edge_row;
+    ea.geom = g_of(l); ea.geom_out = h->debug && c.g_update ? g_of(l + 1) : nullptr; ea.gd = db->gd; ea.edge_weight = db->weight;
+    if (fuse_basis && l == 0) { ea.fuse_basis = 1; ea.dist = db->dist; ea.basis = h->basis; }
+    ea.n_edge = db->n_edge;
+    ea.geom_rows = fuse_basis ? 0 : 1;  // piece-major tiles only when the first layer computed its own geometry rows (plain inference)
+    ea.geom_dead = (l == L - 1 && !h->debug) ? 1 : 0;  // the geometry leaving the last layer is never consumed (141 MB of writes per 16-batch launch)
+    ea.c = c_of(l); ea.P1 = db->P1; ea.P3 = db->P3; ea.q = keep ? db->keep_q + (size_t)l * nA_ : db->q; ea.ctx = ctx_of(l);
+    if (species0 && l == 0) { ea.species = db->atomic; ea.c = h->sp_c; ea.P1 = h->sp_P1; ea.P3 = h->sp_P3; ea.q = h->sp_q; }
+    if (keep) {
+      ea.keep_V = db->keep_V + (size_t)l * nE_; ea.keep_K = db->keep_K + (size_t)l * nE_;
+      // T = swish(V) + G and ang = c[j] * G' are formed again where the fused backward needs them (edge_bwd_kernel, the key weight
+      // gradient's operand load): two of the six [n_edge,128] streams of the training forward's edge launch
+      if (db->keep_T) ea.keep_T = db->keep_T + (size_t)l * nE_;
+      if (db->keep_ang) ea.keep_ang = db->keep_ang + (size_t)l * nE_;
+      db->kept = true;
+    }
+    ea.p = h->layers[l];
+    if (exact) {
+      ea.exact = 1;
+      ea.p.W2h = reinterpret_cast<const _Float16*>(ea.p.W2p); ea.p.Wkh = reinterpret_cast<const _Float16*>(ea.p.Wkp);
+    }
+    ea.range_flag = rflag; ea.layer = l;
+    // (the first layer's launch with the basis MLP fused in is a different kernel: not part of edge_kernel's sampled average)
+    // (... nor is the last layer's, whose geometry is not stored -- the DEAD instantiation, ~10 % shorter: the sampled average is the
+    //  kernel rocprofv3 lists as edge_kernel<true, RT, false, false, false, false>, and its algorithmic bytes include that store)
+    const bool sample = !tm && h->time_every > 0 && (h->time_count % h->time_every) == 0 && !(fuse_basis && l == 0) && !(ea.geom_dead && L > 2);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (sample) {
+      (void)hipEventCreateWithFlags(&ev0, kTimingEventFlags);
+      (void)hipEventCreateWithFlags(&ev1, kTimingEventFlags);
+      (void)hipEventRecord(ev0, s);
+    }
+    ea.tile_part = db->tile_part; ea.part_buf = db->part_buf;
+    ea.xcd_remap = h->xcd_remap;
+    if (h->in_train_forward && h->attn_drop_p > 0.f) {  // validation passes run with scann_set_attention_dropout(h, 0): trainer.fit
+      ea.attn_drop_p = h->attn_drop_p;
+      ea.attn_drop_seed = h->train_seed;
+      ea.attn_drop_tag = DROP_TAG_ATTN + (unsigned)l;
+    }
+#ifdef SCANN_STAMPS
+    if (!getenv("SCANN_STAMP_ATOM") && l == (getenv("SCANN_STAMP_LAYER") ? atoi(getenv("SCANN_STAMP_LAYER")) : L - 1)) {  // one launch's picture
+      if (!db->stamps) HIPCHK(h, hipMalloc((void**)&db->stamps, (size_t)db->n_tile * 16 * sizeof(unsigned long long)));
+      ea.stamps = db->stamps;
+      db->n_stamp = db->n_tile;
+    }
+#endif
+    launch_edge(ea, s);
+    launch_edge_merge(db->big_tab, db->n_big, db->part_buf, ea.q, ea.p.ln_g, ea.p.ln_b, ea.ctx, rflag, l, s);
+    if (sample) {
+      (void)hipEventRecord(ev1, s);
+      h->time_ev.push_back(ev0);
+      h->time_ev.push_back(ev1);
+      h->time_edges.push_back(db->n_edge);
+    }
+    if (tm) tm->mark(2);
+  }
+  if (!tm) h->time_count++;
+  ReadoutArgs r{};
+  r.mol_offset = db->mol_offset; r.n_struct = db->n_struct; r.max_atoms = db->max_atoms;
+  r.gq = db->gq; r.gk = db->gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = c.relu_out;
+  r.p = h->head; r.ga_attn = db->ga; r.y = db->y;
+  launch_readout(r, s);
+  if (tm) tm->mark(3);
+  HIPCHK(h, hipGetLastError());
+  return SCANN_OK;
+}
+
+}  // namespace scann
+
+extern "C" {
+
+int scann_forward_resident(scann_handle_t* h, scann_dbatch_t* db, int stream_slot) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_forward_resident: null argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int slot = ((stream_slot % h->nstream) + h->nstream) % h->nstream;
+  db->last_slot = slot;
+  return run_forward(h, db, h->streams[slot], nullptr);
+}
+
+int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t* prof) {
+  if (!h || !db || !prof) return fail(h, SCANN_ERR_INVALID, "scann_forward_profile: null argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  memset(prof, 0, sizeof(*prof));
+  Timer tm{h->streams[0], true, {}, {}};
+  db->last_slot = 0;
+  const int r = run_forward(h, db, h->streams[0], &tm);
+  if (r) return r;
+  HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  if (const int rp = check_pack_flag(h, db, "scann_forward_profile")) return rp;
+  for (size_t i = 1; i < tm.ev.size(); ++i) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, tm.ev[i - 1], tm.ev[i]);
+    switch (tm.kind[i]) {
+      case 0: prof->ms_basis += ms; break;
+      case 1: prof->ms_atom += ms; prof->n_atom_launch++; break;
+      case 2: prof->ms_edge += ms; prof->n_edge_launch++; break;
+      default: prof->ms_readout += ms; break;
+    }
+  }
+  if (tm.ev.size() >= 2) (void)hipEventElapsedTime(&prof->ms_total, tm.ev.front(), tm.ev.back());
+  for (hipEvent_t e : tm.ev) (void)hipEventDestroy(e);
+  return SCANN_OK;
+}
+
+int scann_edge_timing(scann_handle_t* h, int every) {
+  if (!h) return SCANN_ERR_INVALID;
+  h->time_every = every > 0 ? every : 0;
+  h->time_count = 0;
+  return SCANN_OK;
+}
+
+int scann_edge_timing_read(scann_handle_t* h, double* avg_us, int64_t* n_launches, double* avg_edges) {
+  if (!h || !avg_us || !n_launches) return SCANN_ERR_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  double tot = 0, edges = 0;
+  int64_t n = 0;
+  for (size_t i = 0; i + 1 < h->time_ev.size(); i += 2) {
+    float ms = 0.f;
+    if (hipEventSynchronize(h->time_ev[i + 1]) == hipSuccess && hipEventElapsedTime(&ms, h->time_ev[i], h->time_ev[i + 1]) == hipSuccess) {
+      tot += ms * 1e3;
+      edges += h->time_edges[i / 2];
+      ++n;
+    }
+    (void)hipEventDestroy(h->time_ev[i]);
+    (void)hipEventDestroy(h->time_ev[i + 1]);
+  }
+  h->time_ev.clear();
+  h->time_edges.clear();
+  *avg_us = n ? tot / n : 0.0;
+  *n_launches = n;
+  if (avg_edges) *avg_edges = n ? edges / n : 0.0;
+  return SCANN_OK;
+}
+
+int scann_debug_stamps(scann_handle_t* h, scann_dbatch_t* db, uint64_t* out, int max_tiles) {
+  if (!h || !db || !out) return fail(h, SCANN_ERR_INVALID, "scann_debug_stamps: null argument");
+#ifdef SCANN_STAMPS
+  if (!db->stamps) return fail(h, SCANN_ERR_INVALID, "scann_debug_stamps: no forward has run");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipDeviceSynchronize());
+  const int n = std::min(max_tiles, db->n_stamp);
+  HIPCHK(h, hipMemcpy(out, db->stamps, (size_t)n * 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return n;
+#else
+  (void)max_tiles;
+  return fail(h, SCANN_ERR_UNSUPPORTED, "scann_debug_stamps: library was not built with -DSCANN_STAMPS");
+#endif
+}
+
+int scann_debug_read(scann_handle_t* h, scann_dbatch_t* db, int what, int layer, float* out) {
+  if (!h || !db || !out) return fail(h, SCANN_ERR_INVALID, "scann_debug_read: null argument");
+  const int L = h->cfg.n_attention;
+  if (db->dbg_layers != L) return fail(h, SCANN_ERR_INVALID, "scann_debug_read: forward was not run with debug on");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->streams[db->last_slot]));
+  if (const int rp = check_pack_flag(h, db, "scann_debug_read")) return rp;
+  const size_t rowA = (size_t)db->n_atom * D, rowE = (size_t)db->n_edge * D;
+  const float* src = nullptr;
+  size_t n = 0;
+  if (what == 0 && layer >= 0 && layer <= L) { src = db->dbg_c + layer * rowA; n = rowA; }
+  else if (what == 1 && h->cfg.g_update && layer >= 0 && layer <= L) { src = db->dbg_g + layer * rowE; n = rowE; }
+  else if (what == 2 && layer >= 1 && layer <= L) { src = db->dbg_ctx + (layer - 1) * rowA; n = rowA; }
+  else if (what >= 3 && what <= 7 && db->kept && layer >= 1 && layer <= L) {
+    // per-layer tensors kept by the last TRAINING forward (scann_train_forward): 3 = K, 4 = ang, 5 = V, 6 = T [n_edge,128]; 7 = q [n_atom,128]
+    const float* base = what == 3 ? db->keep_K : what == 4 ? db->keep_ang : what == 5 ? db->keep_V : what == 6 ? db->keep_T : db->keep_q;
+    if (!base)  // the fused backward forms T and the gated rows again instead of reading them: the training forward does not store them
+      return fail(h, SCANN_ERR_UNSUPPORTED, "scann_debug_read: this tensor is not kept by the training forward (selectors 4 = ang and 6 = T exist with the "
+                                            "modular backward only: SCANN_TRAIN_FUSED=0; the base branch keeps no T)");
+    n = what == 7 ? rowA : rowE;
+    src = base + (size_t)(layer - 1) * n;
+  }
+  else return fail(h, SCANN_ERR_INVALID, "scann_debug_read: bad selector");
+  if (n) HIPCHK(h, hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
+  return SCANN_OK;
+}
+
+int64_t scann_exact_reruns(const scann_handle_t* h) { return h ? h->exact_reruns : -1; }
+
+}  // extern "C"

@@ -1,0 +1,901 @@
+// Training path: the per-batch training workspace, training-mode forward, hand-written backward, Adam
+// and the one-call step.  The all-reduces between ranks are in scann_comm.cpp.
+#include "scann_runtime.h"
+
+namespace {
+
+int ensure_train_ws(scann_handle* h, scann_dbatch* db, scann_train_ws** out) {
+  if (!db->train) db->train = std::make_unique<scann_train_ws>();
+  scann_train_ws& w = *db->train;
+  *out = &w;
+  if (w.arena) return SCANN_OK;
+  if (h->generic) {  // loss statistics, targets, d loss / d y; the tensors live in w.gen (run_forward_generic, gen_backward)
+    const size_t nb = align_up((size_t)db->n_struct * 4);
+    HIPCHK(h, cached_malloc((void**)&w.arena, 256 + 2 * nb));
+    w.sse = (double*)w.arena;
+    w.dy = (float*)(w.arena + 256);
+    w.targets = (float*)(w.arena + 256 + nb);
+    return SCANN_OK;
+  }
+  const size_t rowA = align_up((size_t)db->n_atom * D * 4), rowE = align_up((size_t)std::max(db->n_edge, 1) * D * 4);
+  const size_t rowB = align_up((size_t)db->n_struct * D * 4);
+  // per-layer tensors kept by the training forward (edge_kernel_lean on 64-edge tiles): q [A,128]; V, T, ang, K [E,128]
+  // (base branch: geomL in the V slices, T unused)
+  const size_t Lk = (size_t)h->cfg.n_attention;
+  // weight-gradient partial slots: per layer <= 2 gradients over the edge rows (key, filter_geo geometry third; base: key) and
+  // <= 5 over the atom rows (filter_geo centre / neighbour thirds, query, ResidualNorm dense_1 / dense_2), readout 3 over atoms
+  // and 1 over structures; each with a bias row per slab
+  const size_t Lc = (size_t)h->cfg.n_attention;
+  w.wpart_floats = (size_t)(D * D + D) * (Lc * (2 * (size_t)wgrad_slabs(std::max(db->n_edge, 1)) + 5 * (size_t)wgrad_slabs(db->n_atom)) +
+                                           3 * (size_t)wgrad_slabs(db->n_atom) + (size_t)wgrad_slabs(db->n_struct)) +
+                   // LayerNorm gamma / beta partials: per layer ln_bwd over edges and atoms, attention backward over atoms
+                   (size_t)2 * D * Lc * ((size_t)std::max(ln_bwd_slots(std::max(db->n_edge, 1)), tile_slots(std::max(db->n_edge, 1))) +
+                                         (size_t)std::max(ln_bwd_slots(db->n_atom), tile_slots(db->n_atom)) +
+                                         (size_t)attn_bwd_slots(db->n_atom, db->max_degree)) +
+                   (size_t)D * db->n_struct +  // predict_property/kernel: one slot per structure (readout_bwd_kernel)
+                   (size_t)4 * D * Lc * (size_t)db->n_tile;  // attention + edge backward in one launch: four vectors, one slot per tile
+  // the operands of a layer's weight gradients live until the end of the step (sets of their own per layer): the gradient launches on
+  // the side stream never have to be waited for before a buffer is reused
+  // the modular backward (SCANN_TRAIN_FUSED=0) reads T and ang as tensors; the fused chains form them again
+  const bool keep_all = !h->train_fused;
+  const size_t n_keepE = keep_all ? 4 : h->cfg.g_update ? 2 : 3;
+  const size_t nTA = 5 + 5 * (Lc + 1), nTE = 4 + 2 * (Lc + 1);
+  const size_t total = nTA * rowA + nTE * rowE + 2 * rowB + 2 * align_up((size_t)db->n_struct * 4) +
+                       align_up((size_t)h->cfg.n_atoms * D * 4) + 256 + Lk * (4 * rowA + n_keepE * rowE) + 2 * rowA + align_up(w.wpart_floats * 4);
+  HIPCHK(h, cached_malloc((void**)&w.arena, total));
+  char* p = w.arena;
+  w.tA.assign(nTA, nullptr);
+  w.tE.assign(nTE, nullptr);
+  for (size_t i = 0; i < nTA; ++i) { w.tA[i] = (float*)p; p += rowA; }
+  for (size_t i = 0; i < nTE; ++i) { w.tE[i] = (float*)p; p += rowE; }
+  w.rep = (float*)p; p += rowB;
+  w.dpre = (float*)p; p += rowB;
+  w.dy = (float*)p; p += align_up((size_t)db->n_struct * 4);
+  w.targets = (float*)p; p += align_up((size_t)db->n_struct * 4);
+  w.dlut = (float*)p; p += align_up((size_t)h->cfg.n_atoms * D * 4);
+  // (zero from here on between steps: embed_bwd_kernel clears every row it consumes -- one memset command per step less on the
+  //  main stream; this one is the workspace's first and only, on the stream every training launch of the handle goes to)
+  HIPCHK(h, hipMemsetAsync(w.dlut, 0, (size_t)h->cfg.n_atoms * D * 4, h->streams[0]));
+  w.sse = (double*)p; p += 256;
+  w.wpart = (float*)p; p += align_up(w.wpart_floats * 4);
+  if (Lk) {  // slices are [rows,128] without padding between layers: size them from the un-aligned row counts
+    w.keep_q = (float*)p; p += Lk * rowA;
+    w.keep_V = (float*)p; p += Lk * rowE;
+    if (keep_all) {
+      w.keep_T = (float*)p; p += Lk * rowE;
+      w.keep_ang = (float*)p; p += Lk * rowE;
+    } else if (!h->cfg.g_update) {  // base branch: the gated rows feed edge_dang_kernel as they are
+      w.keep_ang = (float*)p; p += Lk * rowE;
+    }
+    w.keep_K = (float*)p; p += Lk * rowE;
+    w.keep_pre1 = (float*)p; p += Lk * rowA;
+    w.keep_H1 = (float*)p; p += Lk * rowA;
+    w.keep_preA = (float*)p; p += rowA;
+    w.keep_z = (float*)p; p += rowA;
+    w.keep_T2 = (float*)p; p += Lk * rowA;
+  }
+  return SCANN_OK;
+}
+
+int64_t spec_offset(const scann_handle* h, const std::string& name) {
+  for (size_t i = 0; i < h->specs.size(); ++i)
+    if (h->specs[i].name == name) return h->spec_off[i];
+  return -1;
+}
+
+}  // namespace
+
+// the training forward (activations kept for the backward) and the batch's sum of squared errors + count -> w->sse[0..1]; no sync
+static int train_forward_impl(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, uint64_t seed, scann_train_ws** wout,
+                              int slot) {  // slot 0 / 1: a scann_train_step in that slot; 2: the synchronous scann_train_forward
+  const bool fused_step = slot < 2;
+  scann_train_ws* w = nullptr;
+  int r = ensure_train_ws(h, db, &w);
+  if (r) return r;
+  hipStream_t s = h->streams[0];
+  db->last_slot = 0;
+  w->drop_p = dropout;
+  w->seed = seed;
+  db->keep_q = w->keep_q; db->keep_V = w->keep_V; db->keep_T = w->keep_T; db->keep_ang = w->keep_ang; db->keep_K = w->keep_K;
+  db->keep_pre1 = w->keep_pre1; db->keep_H1 = w->keep_H1; db->keep_T2 = w->keep_T2;
+  db->keep_preA = w->keep_preA; db->keep_z = w->keep_z;
+  db->kept = false;
+  const bool dbg = h->debug;
+  if (h->generic) {  // run_forward_generic keeps its tensors in w->gen
+    w->gen.drop_p = dropout;
+    w->gen.attn_p = h->attn_drop_p;
+    w->gen.seed = seed;
+    h->gen_keep = &w->gen;
+  }
+  h->debug = !h->generic;  // keep centres / geometry / context of every layer (and, with edge_kernel_lean, q / V / T / ang / K)
+  h->train_drop_p = dropout;
+  h->train_seed = seed;
+  h->in_train_forward = true;
+  w->attn_p = h->attn_drop_p;
+  db->last_slot = 0;  // training runs on stream 0 (its range-guard word is slot 0's)
+  r = run_forward(h, db, s, nullptr);
+  h->in_train_forward = false;
+  h->train_drop_p = 0.f;
+  h->debug = dbg;
+  h->gen_keep = nullptr;
+  if (r) return r;
+  if (h->generic) {
+    db->kept = true;
+    db->dbg_layers = h->cfg.n_attention;
+  }
+  // targets: staged in pinned memory that the loss kernel reads directly (it leaves the device copy the backward uses): no copy operation
+  if (h->h_targets_cap[slot] < (size_t)db->n_struct) {
+    if (h->h_targets[slot]) {
+      HIPCHK(h, hipStreamSynchronize(s));  // an earlier step may still be reading the buffer that is about to be replaced
+      (void)hipHostFree(h->h_targets[slot]);
+    }
+    h->h_targets[slot] = nullptr;
+    h->h_targets_cap[slot] = 0;
+    HIPCHK(h, hipHostMalloc((void**)&h->h_targets[slot], (size_t)db->n_struct * 4));
+    h->h_targets_cap[slot] = (size_t)db->n_struct;
+  }
+  memcpy(h->h_targets[slot], targets, (size_t)db->n_struct * 4);
+  const bool single = !(h->comm && h->comm_world > 1);
+  if (fused_step && !h->h_stat) HIPCHK(h, hipHostMalloc((void**)&h->h_stat, 2 * 4 * sizeof(double)));
+  // single-rank fused step: the loss kernel also forms d rmse / d y and posts {sse, count, sum |y - t|} to the slot's pinned triple
+  launch_sse(db->y, h->h_targets[slot], db->n_struct, w->sse, w->targets, fused_step && single ? w->dy : nullptr,
+             fused_step && single ? h->h_stat + 4 * slot : nullptr, s);
+  *wout = w;
+  return SCANN_OK;
+}
+
+// Reverse adjacency of a batch that was uploaded while the handle was not in training mode (scann_batch_upload skips it then):
+// the neighbour indices come back from the device, the counting sort runs on the host as in upload_impl.  Synchronous; once per batch.
+static int ensure_reverse(scann_handle_t* h, scann_dbatch_t* db) {
+  if (db->has_rev) return SCANN_OK;
+  const int A = db->n_atom, E = db->n_edge;
+  hipStream_t s = h->streams[0];
+  HIPCHK(h, wait_upload(db, s));
+  std::vector<int32_t> col((size_t)std::max(E, 1)), in_off((size_t)A + 1, 0), in_edge((size_t)std::max(E, 1));
+  if (E > 0) HIPCHK(h, hipMemcpyAsync(col.data(), db->edge_col, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  for (int e = 0; e < E; ++e) ++in_off[(size_t)col[(size_t)e] + 1];
+  for (int a = 0; a < A; ++a) in_off[(size_t)a + 1] += in_off[(size_t)a];
+  std::vector<int32_t> fill(in_off.begin(), in_off.begin() + A);
+  for (int e = 0; e < E; ++e) in_edge[(size_t)fill[(size_t)col[(size_t)e]]++] = e;
+  HIPCHK(h, hipMemcpyAsync(db->in_off, in_off.data(), (size_t)(A + 1) * 4, hipMemcpyHostToDevice, s));
+  if (E > 0) HIPCHK(h, hipMemcpyAsync(db->in_edge, in_edge.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  db->has_rev = true;
+  return SCANN_OK;
+}
+
+// The backward pass of create_model (scann_model.py:362-447) for a generic-width handle: the formulas of backward_impl below, one plain
+// kernel each (scann_generic_train.hip), on the tensors the training forward kept (GenKeep).  One stream; gradients are ACCUMULATED
+// into the flat gradient vector (two backward calls give the gradient of the sum, as on the 128-wide path).
+static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done) {
+  hipStream_t s = h->streams[0];
+  const scann_config_t& c = h->cfg;
+  GenKeep& kp = w.gen;
+  const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
+  const int d = c.local_dim, dg = c.global_dim, dout = c.dense_out, H = c.num_head, emb = c.embedding_dim;
+  const int cin = emb + (c.use_ring ? 10 : 0);
+  if (!kp.arena || (int)kp.layer.size() != L) return fail(h, SCANN_ERR_INVALID, "scann_train_backward: run scann_train_forward on this batch first");
+  if ((size_t)std::max(std::max(dg, dout), std::max(3 * d, std::max(cin, 92))) * 4 * 4 > 60000)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "backward (generic widths): a layer's rows exceed one workgroup's LDS");
+  // launch limits of two kernels, checked BEFORE anything is launched (a refused launch would otherwise surface as a bare hipGetLastError at
+  // the end, after earlier kernels have added into the gradient vector): gen_table_part_kernel's grid.y = 64-atom chunks,
+  // gen_attn_bwd_kernel's dynamic LDS = 3 x max_degree x heads floats
+  if (!c.feature_cgcnn && (A + 63) / 64 > 65535)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "backward (generic widths): more than 4,194,240 atoms in one batch (Embedding gradient: 65,535 chunks of 64 atoms)");
+  if ((size_t)3 * std::max(1, db->max_degree) * H * sizeof(float) > 65536)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "backward (generic widths): an atom's neighbours x heads exceed one workgroup's LDS (3 x max_degree x num_head floats <= 64 KiB)");
+  if (((size_t)3 * db->max_atoms + 4) * sizeof(double) > 65536)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "backward (generic widths): a structure's atoms exceed one workgroup's LDS (GlobalAttention pooling: 3 x atoms doubles <= 64 KiB)");
+  // ---- temporaries ----
+  const size_t fA = (size_t)A, fE = (size_t)std::max(E, 1), fB = (size_t)B;
+  const size_t dmax = (size_t)std::max(d, std::max(dg, dout));
+  const size_t need0 = 4 * (fA * (8 * (size_t)d + 4 * (size_t)dg + (size_t)emb + 10) + fE * 9 * (size_t)d + fB * (2 * (size_t)dout + (size_t)dg) +
+                           2 * std::max(fA, fE) + 2 * 512 * dmax) + 256 * 48;
+  // per-slab partial tiles of a weight gradient (gen_dense_dw_kernel): slabs x tiles <= 1024 + tiles (gen_dw_slabs), 1024 floats a tile
+  const size_t Kmax = (size_t)std::max(std::max(3 * d, dg), std::max(std::max(dout, cin), 92));
+  const size_t wpart = (1024 + ((Kmax + 31) / 32) * ((dmax + 31) / 32)) * 1024 + 64 * dmax;
+  const size_t tpart = c.feature_cgcnn ? 0 : ((fA + 63) / 64) * (size_t)c.n_atoms * (size_t)emb;  // Embedding gradient: per-chunk sums
+  const size_t need = need0 + 4 * (wpart + tpart);
+  if (kp.bbytes < need) {
+    HIPCHK(h, hipStreamSynchronize(s));
+    cached_free(kp.barena);
+    kp.barena = nullptr;
+    kp.bbytes = 0;
+    HIPCHK(h, cached_malloc((void**)&kp.barena, need));
+    kp.bbytes = need;
+  }
+  float* p = reinterpret_cast<float*>(kp.barena);
+  auto take = [&](size_t n) { float* q = p; p += (n + 63) & ~(size_t)63; return q; };
+  float *dCa = take(fA * d), *dCb = take(fA * d), *dXr = take(fA * d), *tA1 = take(fA * d), *tA2 = take(fA * d), *dT1 = take(fA * d), *dQ = take(fA * d);
+  float *dz = take(fA * dg), *dgq = take(fA * dg), *dgk = take(fA * dg), *dv = take(fA * (emb + 10));
+  float *dK = take(fE * d), *dang = take(fE * d), *dGt = take(fE * d), *dT = take(fE * d), *dZ = take(fE * d), *dXi = take(fE * d), *dXj = take(fE * d);
+  float *dGa = take(fE * d), *dGb = take(fE * d);
+  float *dhid = take(fB * dout), *drep = take(fB * dg);
+  float *stats = take(2 * std::max(fA, fE)), *part = take(2 * 512 * dmax), *wp = take(wpart), *tp_ = take(tpart);
+  if (reinterpret_cast<char*>(p) > kp.barena + kp.bbytes) return fail(h, SCANN_ERR_HIP, "backward (generic widths): workspace overrun");
+  // ---- helpers ----
+  launch_gen_transpose(h->d_gt_descs, (int)h->gt_descs.size(), h->gt_max, h->g_weights, h->g_WT, s);
+  auto Wp = [&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
+  auto WT = [&](const std::string& name, int blk = 0) -> const float* { return h->g_WT + h->gt_off.at(name + "/kernel#" + std::to_string(blk)); };
+  auto G = [&](const std::string& name) -> float* { return h->t_grad + h->g_off.at(name); };
+  const GenSeg none{nullptr, nullptr, 0};
+  // d x [rows, n_in] = d z [rows, n_out] . W^T (+ res)
+  auto dx = [&](const float* dZ_, int rows, int n_out, int n_in, const float* wt, const float* res, float* out) {
+    GenDenseArgs a{};
+    a.seg[0] = GenSeg{dZ_, nullptr, n_out}; a.seg[1] = none; a.seg[2] = none; a.n_seg = 1;
+    a.W = wt; a.b = nullptr; a.K = n_out; a.N = n_in; a.rows = rows; a.res = res; a.Y = out;
+    launch_gen_dense(a, s);
+  };
+  bool part_overrun = false;
+  auto dw = [&](GenSeg s0, GenSeg s1, GenSeg s2, int n_seg, int prod, const float* dZ_, int K_, int N_, int rows, const std::string& name) {
+    GenDwArgs a{};
+    a.seg[0] = s0; a.seg[1] = s1; a.seg[2] = s2; a.n_seg = n_seg; a.prod = prod;
+    a.dZ = dZ_; a.K = K_; a.N = N_; a.rows = rows; a.dW = G(name + "/kernel"); a.db = G(name + "/bias"); a.part = wp;
+    if (rows > 0 && gen_dw_part_floats(rows, K_, N_) > wpart) { part_overrun = true; return; }
+    launch_gen_dense_dw(a, s);
+  };
+  auto lnb = [&](const float* X, const float* res, const std::string& name, const float* dY, int rows, float* dX) {
+    launch_gen_layernorm_bwd(X, res, Wp(name + "/gamma"), dY, rows, d, dX, stats, part, G(name + "/gamma"), G(name + "/beta"), s);
+  };
+  if (!dy_done) launch_dy(db->y, w.targets, B, scale, d_stat, w.dy, s);
+  // ---- property head (scann_model.py:437-447; mrelu's gradient is the identity, custom_layers.py:6-15) ----
+  dw(GenSeg{kp.hid, nullptr, dout}, none, none, 1, 0, w.dy, dout, 1, B, "predict_property");
+  dx(w.dy, B, 1, dout, WT("predict_property"), nullptr, dhid);
+  launch_gen_act_bwd(dhid, kp.hid_pre, nullptr, B, dout, 0.f, 0, 0, dhid, s);
+  dw(GenSeg{kp.rep, nullptr, dg}, none, none, 1, 0, dhid, dg, dout, B, "bf_property");
+  dx(dhid, B, dout, dg, WT("bf_property"), nullptr, drep);
+  // ---- GlobalAttention pooling, its projections, after_Lc (attention.py:279-316; scann_model.py:424-434) ----
+  launch_gen_pool_bwd(db->mol_offset, B, db->max_atoms, kp.gq, kp.gk, dg, c.use_ga_norm, drep, dgq, dgk, s);
+  kp.dbg = {{"gq", {kp.gq, fA * dg}}, {"gk", {kp.gk, fA * dg}}, {"z", {kp.z, fA * dg}}, {"rep", {kp.rep, fB * dg}}, {"drep", {drep, fB * dg}},
+            {"dgq", {dgq, fA * dg}}, {"dgk", {dgk, fA * dg}}, {"dz", {dz, fA * dg}}};
+  dw(GenSeg{kp.z, nullptr, dg}, none, none, 1, 0, dgq, dg, dg, A, "global_attention/query");
+  dw(GenSeg{kp.z, nullptr, dg}, none, none, 1, 0, dgk, dg, dg, A, "global_attention/key");
+  dx(dgq, A, dg, dg, WT("global_attention/query"), nullptr, dz);
+  dx(dgk, A, dg, dg, WT("global_attention/key"), dz, dz);
+  launch_gen_act_bwd(dz, kp.z_pre, nullptr, A, dg, 0.f, 0, 0, dz, s);
+  dw(GenSeg{kp.cc_L, nullptr, d}, none, none, 1, 0, dz, d, dg, A, "after_Lc");
+  float *dC = dCa, *dC_other = dCb;
+  dx(dz, A, dg, d, WT("after_Lc"), nullptr, dC);
+  const float* dGn = nullptr;  // gradient of the geometry leaving layer l (nothing reads the last layer's)
+  float *dG_next = dGa, *dG_spare = dGb;
+  // ---- LocalAttention + ResidualNorm iterations, last to first (attention.py:118-216, :37-40) ----
+  for (int l = L - 1; l >= 0; --l) {
+    const GenLayerKeep& b = kp.layer[(size_t)l];
+    const std::string la = "local_attention_" + std::to_string(l), rn = "residual_norm_" + std::to_string(l);
+    const float* dCtx = dC;
+    if (c.use_attn_norm) {  // c' = LayerNorm(ctx + Dropout(dense_2(swish(dense_1 ctx))))
+      lnb(b.ctx, b.t2, rn + "/layer_norm", dC, A, dXr);
+      launch_gen_act_bwd(dXr, nullptr, nullptr, A, d, kp.drop_p, (unsigned)l, kp.seed, tA1, s);  // through the Dropout mask
+      dw(GenSeg{b.h1, nullptr, d}, none, none, 1, 0, tA1, d, d, A, rn + "/dense_2");
+      dx(tA1, A, d, d, WT(rn + "/dense_2"), nullptr, tA2);
+      launch_gen_act_bwd(tA2, b.pre1, nullptr, A, d, 0.f, 0, 0, tA2, s);
+      dw(GenSeg{b.ctx, nullptr, d}, none, none, 1, 0, tA2, d, d, A, rn + "/dense_1");
+      dx(tA2, A, d, d, WT(rn + "/dense_1"), dXr, dXr);  // + the residual branch
+      dCtx = dXr;
+    }
+    lnb(b.t1, nullptr, la + "/layer_norm", dCtx, A, dT1);
+    launch_gen_attn_bwd(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, dT1, kp.attn_p, DROP_TAG_ATTN + (unsigned)l, kp.seed, dQ, dK, s);
+    dw(GenSeg{b.cc_in, nullptr, d}, none, none, 1, 0, dQ, d, d, A, la + "/query");
+    dw(GenSeg{b.cc_in, db->edge_col, d}, GenSeg{b.Gn, nullptr, d}, none, 2, 1, dK, d, d, E, la + "/key");
+    dx(dQ, A, d, d, WT(la + "/query"), nullptr, dC_other);
+    dx(dK, E, d, d, WT(la + "/key"), nullptr, dang);  // gradient of the gated rows c[j] * g (attention.py:157)
+    if (c.g_update) {
+      launch_gen_mul_gather(dang, b.cc_in, db->edge_col, dGn, E, d, dGt, s);  // d g' = dang * c[j] + what the layer above left
+      lnb(b.T, nullptr, la + "/layer_norm_g", dGt, E, dT);
+      launch_gen_act_bwd(dT, b.Z, nullptr, E, d, 0.f, 0, 0, dZ, s);
+      dw(GenSeg{b.cc_in, db->edge_row, d}, GenSeg{b.G_in, nullptr, d}, GenSeg{b.cc_in, db->edge_col, d}, 3, 0, dZ, 3 * d, d, E, la + "/filter_geo");
+      dx(dZ, E, d, d, WT(la + "/filter_geo", 0), nullptr, dXi);
+      dx(dZ, E, d, d, WT(la + "/filter_geo", 1), dT, dG_next);  // + the residual geometry (attention.py:152)
+      dx(dZ, E, d, d, WT(la + "/filter_geo", 2), nullptr, dXj);
+      launch_gen_edge_to_atom(db->edge_offset, db->in_off, db->in_edge, dXi, dXj, dang, b.Gn, dC_other, A, d, dC_other, s);
+      dGn = dG_next;
+      std::swap(dG_next, dG_spare);
+    } else {  // g = swish(basis . Wf + bf) * Voronoi weight (attention.py:159-163)
+      launch_gen_mul_gather(dang, b.cc_in, db->edge_col, nullptr, E, d, dGt, s);
+      launch_gen_act_bwd(dGt, b.Z, db->weight, E, d, 0.f, 0, 0, dZ, s);
+      dw(GenSeg{kp.gd, nullptr, NG}, none, none, 1, 0, dZ, NG, d, E, la + "/filter_geo");
+      launch_gen_edge_to_atom(db->edge_offset, db->in_off, db->in_edge, nullptr, nullptr, dang, b.Gn, dC_other, A, d, dC_other, s);
+    }
+    std::swap(dC, dC_other);
+  }
+  // ---- basis MLP of the initial geometry (scann_model.py:386-391) ----
+  if (c.g_update && dGn) {
+    launch_gen_mul_gather(dGn, kp.Tw, nullptr, nullptr, E, d, dT, s);
+    launch_gen_act_bwd(dT, kp.pre_d, nullptr, E, d, 0.f, 0, 0, dT, s);
+    dw(GenSeg{kp.gd, nullptr, NG}, none, none, 1, 0, dT, NG, d, E, "neighbor_d");
+    launch_gen_mul_gather(dGn, kp.Td, nullptr, nullptr, E, d, dZ, s);
+    launch_gen_act_bwd(dZ, kp.pre_w, nullptr, E, d, 0.f, 0, 0, dZ, s);
+    dw(GenSeg{kp.gw, nullptr, NG}, none, none, 1, 0, dZ, NG, d, E, "neighbor_w");
+  }
+  // ---- embedding (scann_model.py:362-374) ----
+  launch_gen_act_bwd(dC, kp.pre_e, nullptr, A, d, kp.drop_p, DROP_TAG_EMBED, kp.seed, tA1, s);
+  const GenSeg e0 = c.feature_cgcnn ? GenSeg{kp.embE, nullptr, emb} : GenSeg{Wp("embed_atom/embeddings"), db->atomic, emb};
+  if (c.use_ring) dw(e0, GenSeg{kp.ring10, nullptr, 10}, none, 2, 0, tA1, cin, d, A, "dense_embed");
+  else dw(e0, none, none, 1, 0, tA1, emb, d, A, "dense_embed");
+  dx(tA1, A, d, emb, WT("dense_embed", 0), nullptr, dv);
+  if (c.feature_cgcnn) dw(GenSeg{db->cgcnn, nullptr, 92}, none, none, 1, 0, dv, 92, emb, A, "embed_atom");
+  else launch_gen_table_grad(db->atomic, A, dv, emb, c.n_atoms, tp_, G("embed_atom/embeddings"), s);
+  if (c.use_ring) {
+    dx(tA1, A, d, 10, WT("dense_embed", 1), nullptr, dv);
+    dw(GenSeg{db->ring, nullptr, 2}, none, none, 1, 0, dv, 2, 10, A, "extra_embed");
+  }
+  if (part_overrun) return fail(h, SCANN_ERR_HIP, "backward (generic widths): a weight gradient's partial tiles exceed their scratch");
+  HIPCHK(h, hipGetLastError());
+  return SCANN_OK;
+}
+
+// d_stat (device, {global sse, global count}) non-null: the loss scale is formed on the device (scann_train_step: no host round trip)
+static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done) {
+  if (const int r = ensure_reverse(h, db)) return r;
+  if (h->generic) return gen_backward(h, db, w, scale, d_stat, dy_done);
+  hipStream_t s = h->streams[0];
+  const scann_config_t& c = h->cfg;
+  const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
+  const size_t nA = (size_t)A * D, nE = (size_t)E * D;
+  float* const G = h->t_grad;
+  auto g = [&](const std::string& name) { return G + spec_offset(h, name); };
+  if (!dy_done) launch_dy(db->y, w.targets, B, scale, d_stat, w.dy, s);
+  // Weight-gradient GEMMs are off the critical path (only the final reduce needs them): with the kept-activation forward
+  // their operands are never overwritten inside a layer, so they run on a side stream beside the data-gradient chain, which
+  // alone does not fill the chip at batch 128.  fork(): side stream waits for everything enqueued so far; join(): main waits
+  // for the side stream (start of every layer: the previous layer's temporaries are about to be overwritten).
+  hipStream_t aux = h->train_aux;
+  const bool side = aux != nullptr;
+  size_t ev_i = 0;
+  auto fork = [&]() -> hipStream_t {
+    if (!side) return s;
+    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
+    (void)hipEventRecord(e, s);
+    (void)hipStreamWaitEvent(aux, e, 0);
+    return aux;
+  };
+  // a fork whose producer was launched with the event as its own completion signal (launch_atom_gather3 / launch_attn_edge_bwd, `done`):
+  // the side stream only has to wait -- no marker packet on the main stream (4.0 instead of 6.7 us per fork, tools/fork_probe.hip)
+  auto next_ev = [&]() -> hipEvent_t { return side ? h->train_ev[ev_i++ % h->train_ev.size()] : nullptr; };
+  auto fork_after = [&](hipEvent_t e) -> hipStream_t {
+    if (!side) return s;
+    (void)hipStreamWaitEvent(aux, e, 0);
+    return aux;
+  };
+  auto join = [&]() {
+    if (!side) return;
+    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
+    (void)hipEventRecord(e, aux);
+    (void)hipStreamWaitEvent(s, e, 0);
+  };
+  // The side stream's chain per layer is a gradient launch (~32 us) and two reductions of its partial slots (~34 us): as long as the
+  // main stream's chain per layer (~70 us), so the step ended when the SIDE stream did, ~65 us after the main one.  The reductions
+  // go to the second side stream (idle but for the basis leaf): gradient launch of layer l - 1 beside the reductions of layer l.
+  bool aux2_used = false;
+  auto flush_side = [&](hipStream_t ws, WgradCtx& ctx, bool last) {
+    if (!side) return;
+    hipStream_t fs = ws;
+    // (the LAST layer's reductions stay behind their gradient launch: the second side stream is busy with the basis leaf, 46 us, by then)
+    if (h->train_aux2 && !last) {
+      hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
+      (void)hipEventRecord(e, ws);
+      (void)hipStreamWaitEvent(h->train_aux2, e, 0);
+      fs = h->train_aux2;
+      aux2_used = true;
+    }
+    wgrad_flush(ctx, fs);
+  };
+  WgradCtx wg;
+  wg.arena = w.wpart;
+  // a fork costs the main stream ~7 us (tools/fork_probe.hip): the layers' gradient launches may share one (their operand sets live
+  // to the end of the step)
+  const int fork_every = 1;  // (2 / 3 / 4 / 7 layers per fork measured slower: profiles/r04_notes.md)
+
+  // named temporaries
+  float *dC = w.tA[0], *dCtx = w.tA[1], *t0 = w.tA[2], *t1 = w.tA[3], *t2 = w.tA[4];
+  float *edAng = w.tE[0], *eT = w.tE[1], *edGa = w.tE[2], *edGb = w.tE[3];
+  // The operands of a layer's weight gradients (t3, t4, dQ, dP1, dP3, edK, eU) exist once per layer (set L = the readout): the
+  // gradient launch of layer l runs on the side stream beside the data-gradient chains of the layers below and nothing it reads
+  // is overwritten before the end of the step.
+  auto setA = [&](int l, int k) { return w.tA[5 + 5 * (size_t)l + k]; };
+  auto setE = [&](int l, int k) { return w.tE[4 + 2 * (size_t)l + k]; };
+  float *t3 = setA(L, 0), *t4 = setA(L, 1), *dQ = setA(L, 2), *dP1 = setA(L, 3), *dP3 = setA(L, 4), *edK = setE(L, 0), *eU = setE(L, 1);
+  const float* cL = db->dbg_c + (size_t)L * nA;  // centres entering after_Lc
+
+  // ---- readout (scann_model.py:424-447, attention.py:267-318) ----
+  float* const rdgk = t3;  // the readout is "layer L" of the operand-set scheme
+  // the training forward kept preA = cL.Wa + ba and z = swish(preA); gq, gk, ga, y are still in the batch workspace
+  t0 = db->keep_preA;
+  t1 = db->keep_z;
+  ReadoutBwdArgs ra{};
+  ra.mol_offset = db->mol_offset; ra.n_struct = B; ra.max_atoms = db->max_atoms; ra.use_ga_norm = c.use_ga_norm;
+  ra.gq = db->gq; ra.gk = db->gk; ra.ga = db->ga; ra.dy = w.dy;
+  ra.Wb = h->head.Wb; ra.bb = h->head.bb; ra.wo = h->head.wo;
+  ra.dgq = t2; ra.dgk = rdgk; ra.rep_out = w.rep; ra.dpre_out = w.dpre;
+  // (one slot per structure, summed in structure order with the layer's other vectors: 128 workgroups adding to the same 128
+  // addresses was a queue of 16 k atomics)
+  ra.dwo = reserve_vec(wg, g("predict_property/kernel"), B); ra.dbo = g("predict_property/bias");
+  launch_readout_bwd(ra, s);
+  // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z = t1,
+  // dgq = t2, dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no fork of their own,
+  // each of which costs the main stream ~7 us (tools/fork_probe.hip)
+  wgrad_add(wg, w.rep, w.dpre, g("bf_property/kernel"), g("bf_property/bias"), B);
+  wgrad_add(wg, t1, t2, g("global_attention/query/kernel"), g("global_attention/query/bias"), A);
+  wgrad_add(wg, t1, rdgk, g("global_attention/key/kernel"), g("global_attention/key/bias"), A);
+  float* const dpreA = dQ;
+  launch_linear_sum(t2, h->WgqT, rdgk, h->WgkT, nullptr, nullptr, dpreA, A, 0, s, t0);  // dpreA = (dgq.Wgq^T + dgk.Wgk^T) * swish'(preA)
+  wgrad_add(wg, cL, dpreA, g("after_Lc/kernel"), g("after_Lc/bias"), A);
+
+  const float* dG_in = nullptr;  // gradient w.r.t. the geometry leaving layer l (none for the last layer)
+  // fused chains (scann_train_fused.hip); SCANN_TRAIN_FUSED=0 selects the modular one-kernel-per-operation backward
+  const bool fused = h->train_fused;
+  struct Pend {  // projections of layer l + 1 that still have to be added to dC (d loss / d centres_{l+1})
+    int n = 0;
+    const float* X[3];
+    const _Float16* Wh[3];
+    const float* W[3];
+    bool fresh = false;  // dC holds nothing yet: the terms ARE d loss / d centres (first use: dpreA.Wa^T of the readout)
+  } pend;
+  hipStream_t tail_s = s;  // where the embedding chain goes (below)
+  auto flush_pend = [&]() {
+    if (pend.n)
+      launch_linear_sum(pend.X[0], pend.W[0], pend.n > 1 ? pend.X[1] : nullptr, pend.n > 1 ? pend.W[1] : nullptr,
+                        pend.n > 2 ? pend.X[2] : nullptr, pend.n > 2 ? pend.W[2] : nullptr, dC, A, pend.fresh ? 0 : 1, tail_s);
+    pend.n = 0;
+    pend.fresh = false;
+  };
+  // d loss / d centres_L = dpreA.Wa^T: folded into the first rn_bwd_kernel (or launched by flush_pend)
+  pend.n = 1;
+  pend.X[0] = dpreA; pend.Wh[0] = h->WaTh; pend.W[0] = h->WaT;
+  pend.fresh = true;
+  // basis MLP (scann_model.py:378-389): a leaf (parameter gradients only) on a stream of its own, started as soon as the geometry
+  // gradient entering layer 0 exists -- at 45 us it is the longest thing between there and the optimiser
+  hipEvent_t ev_basis = nullptr;
+  bool basis_done = false;
+  auto basis_leaf = [&](const float* dG, hipEvent_t produced) {  // `produced`: completion event of the kernel that wrote dG, or null
+    hipStream_t bs = s;
+    if (side && h->train_aux2) {
+      hipEvent_t e = produced;
+      if (!e) {
+        e = h->train_ev[ev_i++ % h->train_ev.size()];
+        (void)hipEventRecord(e, s);
+      }
+      (void)hipStreamWaitEvent(h->train_aux2, e, 0);
+      bs = h->train_aux2;
+    }
+    launch_basis_bwd(h->basis, db->dist, db->weight, dG, E, g("neighbor_d/kernel"), g("neighbor_d/bias"),
+                     g("neighbor_w/kernel"), g("neighbor_w/bias"), bs);
+    if (bs != s) {
+      ev_basis = h->train_ev[ev_i++ % h->train_ev.size()];
+      (void)hipEventRecord(ev_basis, bs);
+    }
+    basis_done = true;
+  };
+  for (int l = L - 1; l >= 0; --l) {
+    t3 = setA(l, 0); t4 = setA(l, 1); dQ = setA(l, 2); dP1 = setA(l, 3); dP3 = setA(l, 4);
+    edK = setE(l, 0); eU = setE(l, 1);
+    const LayerParams& p = h->layers[l];
+    const scann_handle::LayerT& pt = h->layersT[l];
+    const std::string la = "local_attention_" + std::to_string(l) + "/", rn = "residual_norm_" + std::to_string(l) + "/";
+    const float* c_in = db->dbg_c + (size_t)l * nA;        // centres entering LocalAttention l
+    const float* ctx = db->dbg_ctx + (size_t)l * nA;       // LocalAttention output (after layer_norm)
+    const float* Gin = c.g_update ? db->dbg_g + (size_t)l * nE : nullptr;         // geometry entering layer l
+    const float* Gout = c.g_update ? db->dbg_g + (size_t)(l + 1) * nE : nullptr;  // geometry leaving layer l (= layer_norm_g output)
+    // tensors the training forward kept (nothing is recomputed): q [A,128]; K, ang, V (base branch: geomL), T [E,128]
+    const float* qL = db->keep_q + (size_t)l * nA;
+    const float* angL = db->keep_ang ? db->keep_ang + (size_t)l * nE : nullptr;  // null: formed again from c[j] and G
+    const float* KL = db->keep_K + (size_t)l * nE;
+    const float* VL = db->keep_V + (size_t)l * nE;
+    const float* TL = db->keep_T ? db->keep_T + (size_t)l * nE : nullptr;        // null: formed again from V and G
+
+    if (pend.n && !(fused && c.use_attn_norm)) flush_pend();  // nobody below folds the projections of the layer above in
+    // ---- ResidualNorm backward (attention.py:37-40): c_{l+1} = LN(x + drop(W2 swish(W1 x + b1) + b2)), x = ctx ----
+    if (c.use_attn_norm) {
+      const float* pre1 = db->keep_pre1 + (size_t)l * nA;
+      const float* H1 = db->keep_H1 + (size_t)l * nA;
+      const float* T2 = db->keep_T2 + (size_t)l * nA;
+      if (fused) {
+        // one kernel: [dC += the projections of the layer above] -> LayerNorm backward -> Dropout mask -> dense_2^T, swish' -> dense_1^T
+        RnBwdArgs ra{};
+        ra.dC = pend.fresh ? nullptr : dC; ra.T2 = T2; ra.pre1 = pre1; ra.gamma = p.lnr_g; ra.Wf2Th = pt.Wf2Th; ra.Wf1Th = pt.Wf1Th;
+        ra.dY = t3; ra.dpre1 = t4; ra.dCtx = dCtx; ra.n_atom = A;
+        ra.drop_p = w.drop_p; ra.drop_seed = w.seed; ra.drop_tag = (unsigned)l;
+        ra.n_pre = pend.n;
+        for (int t = 0; t < pend.n; ++t) { ra.X[t] = pend.X[t]; ra.Wh[t] = pend.Wh[t]; }
+        pend.n = 0;
+        pend.fresh = false;
+        launch_rn_bwd(wg, ra, g(rn + "layer_norm/gamma"), g(rn + "layer_norm/beta"), s);
+      } else {
+        launch_ln_bwd(wg, T2, p.lnr_g, dC, dCtx, g(rn + "layer_norm/gamma"), g(rn + "layer_norm/beta"), A, 0, s);  // dT2 -> dCtx
+        // gradient of the Dense_2 output = dT2 through the Dropout mask, in a buffer of its own: dT2 (dCtx) is the residual path and
+        // is accumulated into below, while the queued weight gradient reads its operand at the end of the layer
+        if (w.drop_p > 0.f) launch_dropout_copy(t3, dCtx, nA, w.seed, (unsigned)l, w.drop_p, s);
+        else HIPCHK(h, hipMemcpyAsync(t3, dCtx, nA * 4, hipMemcpyDeviceToDevice, s));
+        launch_linear(t3, pt.Wf2T, nullptr, t4, const_cast<float*>(pre1), A, 4, s);  // dpre1 = (dY.W2^T) * swish'(pre1)
+        launch_linear(t4, pt.Wf1T, nullptr, dCtx, nullptr, A, 1, s);                 // dctx = dT2 + dpre1.W1^T
+      }
+      wgrad_add(wg, H1, t3, g(rn + "dense_2/kernel"), g(rn + "dense_2/bias"), A);
+      wgrad_add(wg, ctx, t4, g(rn + "dense_1/kernel"), g(rn + "dense_1/bias"), A);
+    } else {
+      HIPCHK(h, hipMemcpyAsync(dCtx, dC, nA * 4, hipMemcpyDeviceToDevice, s));
+    }
+
+    // ---- LocalAttention backward (attention.py:118-216) ----
+    // On the forward's 32-row tile plan (whole atoms per tile, every degree <= 16) the softmax / LayerNorm backward of a tile's atoms
+    // runs at the head of the tile's edge_bwd workgroup: one launch less per layer.
+    const bool fuse_attn = fused && c.g_update && db->tile_rows == 32 && db->n_big == 0 && db->max_degree <= 16 && E > 0;
+    if (!fuse_attn)
+      launch_attn_bwd(wg, qL, KL, db->edge_offset, dCtx, p.ln_g, dQ, edK, g(la + "layer_norm/gamma"), g(la + "layer_norm/beta"), A,
+                      db->max_degree, w.attn_p, DROP_TAG_ATTN + (unsigned)l, w.seed, s);
+    if (angL) wgrad_add(wg, angL, edK, g(la + "key/kernel"), g(la + "key/bias"), E);
+    else wgrad_add(wg, c_in, edK, g(la + "key/kernel"), g(la + "key/bias"), E, db->edge_col, Gout);  // ang = c[j] * G'
+    wgrad_add(wg, c_in, dQ, g(la + "query/kernel"), g(la + "query/bias"), A);
+    if (!c.g_update) {
+      // base SCANN (attention.py:155): geomL = swish(gd.Wf + bf) * weight from the raw basis (kept in the V slices), no geometry threading
+      launch_linear(edK, pt.WkT, nullptr, edAng, nullptr, E, 0, s);            // dang
+      launch_edge_dang(c_in, db->edge_col, VL, edAng, nullptr, eT, eU, E, s);  // eT = dang * geomL ; eU = dgeomL = dang * c[j]
+      launch_gather_sum(eT, db->in_off, db->in_edge, dC, A, 0, s);             // dC[j] = sum over the edges that point at j
+      // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
+      hipStream_t ws = fork();
+      wgrad_launch(wg, ws);
+      flush_side(ws, wg, l == 0);
+      launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws);
+      pend.n = 1;  // dC += dq.Wq^T: folded into the next rn_bwd_kernel (or launched by flush_pend)
+      pend.X[0] = dQ; pend.Wh[0] = pt.WqTh; pend.W[0] = pt.WqT;
+      continue;
+    }
+    // geometry update: G' = LN_g(swish(V) + G), V = G.W2 + P1[i] + P3[j]; gate ang = c[j] * G'
+    float* dGnext = (dG_in == edGa) ? edGb : edGa;  // d loss / d geometry entering layer l
+    hipEvent_t ev_sums = nullptr;
+    if (fused) {
+      // one kernel: dang = dK.Wk^T -> dG'tot = dang * c[j] + dG'(next layer) -> LayerNorm_g backward -> dV = dT * swish'(V) -> dG = dT + dV.W2^T
+      EdgeBwdArgs ea{};
+      ea.dK = edK; ea.c = c_in; ea.dG_in = dG_in; ea.T = TL; ea.G = Gin; ea.V = VL; ea.gamma = p.lng_g; ea.nb = db->edge_col;
+      ea.WkTh = pt.WkTh; ea.W2Th = pt.W2Th; ea.dang = edAng; ea.dV = eU; ea.dG = dGnext; ea.n_edge = E;
+      hipEvent_t ev_dg = nullptr;  // layer 0: the basis leaf waits for the geometry gradient this launch leaves
+      if (fuse_attn) {
+        AttnPart ab{};
+        ab.q = qL; ab.K = KL; ab.dctx = dCtx; ab.gamma = p.ln_g; ab.edge_offset = db->edge_offset; ab.tiles = db->tiles;
+        ab.dq = dQ; ab.dK = edK; ab.drop_p = w.attn_p; ab.drop_tag = DROP_TAG_ATTN + (unsigned)l; ab.drop_seed = w.seed;
+        if (l == 0 && h->train_aux2) ev_dg = next_ev();
+        launch_attn_edge_bwd(wg, ea, ab, db->n_tile, g(la + "layer_norm_g/gamma"), g(la + "layer_norm_g/beta"), g(la + "layer_norm/gamma"),
+                             g(la + "layer_norm/beta"), s, ev_dg);
+      } else {
+        launch_edge_bwd(wg, ea, g(la + "layer_norm_g/gamma"), g(la + "layer_norm_g/beta"), s);
+      }
+      if (l == 0) basis_leaf(dGnext, ev_dg);  // (before the atom sums below: they do not touch the geometry gradient)
+      // dC[j] = sum over the edges that point at j of dang * G' (gate), dP3[j] = the same sum of dV, dP1[i] = sum of dV over i's own edges
+      ev_sums = next_ev();  // ... and this launch's completion is what the layer's weight-gradient launch on the side stream waits for
+      launch_atom_gather3(edAng, Gout, eU, db->edge_offset, db->in_off, db->in_edge, dC, dP1, dP3, A, s, ev_sums);
+    } else {
+      launch_linear(edK, pt.WkT, nullptr, edAng, nullptr, E, 0, s);  // dang
+      launch_gather_prod_sum(edAng, Gout, db->in_off, db->in_edge, dC, A, 0, s);
+      // LayerNorm_g backward with its neighbours fused: in  dG'tot = dang * c[j] + dG'(next layer), out  dT (residual path, -> dGnext)
+      // and dV = dT * swish'(V) (-> eU)
+      launch_ln_bwd_edge(wg, TL, p.lng_g, edAng, c_in, db->edge_col, dG_in, VL, dGnext, eU, g(la + "layer_norm_g/gamma"),
+                         g(la + "layer_norm_g/beta"), E, s);
+      launch_atom_sums(eU, db->edge_offset, db->in_off, db->in_edge, dP1, dP3, A, s);  // dP1[i]: the atom's own edges; dP3[j]: the edges that point at j
+      launch_linear(eU, pt.W2T, nullptr, dGnext, nullptr, E, 1, s);                    // dG += dV.W2^T
+    }
+    float* fgk = g(la + "filter_geo/kernel");
+    wgrad_add(wg, Gin, eU, fgk + (size_t)D * D, nullptr, E);  // dW2
+    wgrad_add(wg, c_in, dP1, fgk, g(la + "filter_geo/bias"), A);
+    wgrad_add(wg, c_in, dP3, fgk + (size_t)2 * D * D, nullptr, A);
+    if (l == 0 && side && ev_sums) {
+      // The FIRST layer's gradient launch and its reductions are the longest thing left (the main stream only has the embedding chain,
+      // ~40 us): they stay on the main stream, with no hand-over in front of them, and the embedding chain goes to the side stream
+      // instead (0.830 -> 0.819 ms per step, eight alternations on one box: profiles/r05_notes.md)
+      wgrad_launch(wg, s);
+      wgrad_flush(wg, s);
+      tail_s = fork_after(ev_sums);
+    } else if ((L - 1 - l) % fork_every == fork_every - 1 || l == 0) {
+      // every weight gradient of this layer (ResidualNorm 2, key, query, filter_geo 3) in ONE launch, then the fixed-order sum of its
+      // partial slots (and of the layer's LayerNorm gamma / beta slots): both beside the chains of the layers below
+      hipStream_t ws = ev_sums ? fork_after(ev_sums) : fork();
+      wgrad_launch(wg, ws);
+      flush_side(ws, wg, l == 0);
+    }
+    // dC += dP1.W1^T + dP3.W3^T + dq.Wq^T: folded into the next layer's rn_bwd_kernel (or launched by flush_pend)
+    pend.n = 3;
+    pend.X[0] = dP1; pend.X[1] = dP3; pend.X[2] = dQ;
+    pend.Wh[0] = pt.W1Th; pend.Wh[1] = pt.W3Th; pend.Wh[2] = pt.WqTh;
+    pend.W[0] = pt.W1T; pend.W[1] = pt.W3T; pend.W[2] = pt.WqT;
+    dG_in = dGnext;
+  }
+  // ---- basis MLP and embedding (scann_model.py:362-389) ----
+  // (the basis leaf first: it needs only the geometry gradient the last edge_bwd_kernel left, and at 43 us on its own stream it is
+  // the longest thing between here and the optimiser -- started behind the embedding chain it ended 30 us after it)
+  if (dG_in && !basis_done) basis_leaf(dG_in, nullptr);
+  flush_pend();
+  if (c.use_ring || c.feature_cgcnn) {
+    launch_dropout(dC, nA, w.seed, DROP_TAG_EMBED, w.drop_p, tail_s);
+    EmbedArgs e = h->embed;
+    e.n_atom = A; e.atomic = db->atomic; e.c0 = db->c0;
+    e.ring = c.use_ring ? db->ring : nullptr;
+    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+    launch_embed_general_bwd(e, dC, c.feature_cgcnn ? nullptr : g("embed_atom/embeddings"),
+                             c.feature_cgcnn ? g("embed_atom/kernel") : nullptr, c.feature_cgcnn ? g("embed_atom/bias") : nullptr,
+                             c.use_ring ? g("extra_embed/kernel") : nullptr, c.use_ring ? g("extra_embed/bias") : nullptr,
+                             g("dense_embed/kernel"), g("dense_embed/bias"), tail_s);
+  } else {
+    launch_embed_bwd(dC, db->atomic, A, h->d_weights + h->o_emb, h->d_weights + h->o_Wde, h->d_weights + h->o_bde, w.dlut,
+                     c.n_atoms, c.embedding_dim, g("embed_atom/embeddings"), g("dense_embed/kernel"), g("dense_embed/bias"), w.seed,
+                     DROP_TAG_EMBED, w.drop_p, tail_s);
+  }
+  if (wg.off > w.wpart_floats)
+    return fail(h, SCANN_ERR_HIP, "scann_train_backward: weight-gradient partial arena overrun");
+  if (!wg.jobs.empty()) wgrad_launch(wg, s);  // a model without LocalAttention layers: the readout's gradients were never launched
+  join();
+  if (aux2_used) {  // everything the second side stream was given (the basis leaf included)
+    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
+    (void)hipEventRecord(e, h->train_aux2);
+    (void)hipStreamWaitEvent(s, e, 0);
+  } else if (ev_basis) {
+    (void)hipStreamWaitEvent(s, ev_basis, 0);
+  }
+  wgrad_flush(wg, s);  // ONE launch adds the per-slab partials of every weight gradient, in slab order
+  HIPCHK(h, hipGetLastError());
+  return SCANN_OK;
+}
+
+static int adam_impl(scann_handle_t* h, float lr_t, float beta1, float beta2, float eps, float l2, int zero_g) {
+  hipStream_t s = h->streams[0];
+  h->t_step += 1;
+  const double t = (double)h->t_step;
+  const float lr_hat = (float)((double)lr_t * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
+  const size_t n = h->host_master.size();
+  // t_l2 holds a 0/1 mask; fold the coefficient in by scaling through the kernel argument
+  launch_adam(h->t_master, h->t_grad, h->t_m, h->t_v, h->t_l2, n, lr_hat, beta1, beta2, eps, l2, zero_g, s);
+  if (h->generic) {  // the plain kernels read the Keras tensors as they are: the forward's copy is the master vector
+    HIPCHK(h, hipMemcpyAsync(h->g_weights, h->t_master, n * 4, hipMemcpyDeviceToDevice, s));
+    return SCANN_OK;
+  }
+  launch_repack(h->t_descs, (int)h->descs.size(), h->t_master, h->d_weights, h->range_flag, s);
+  h->sp_dirty = true;
+  if (!h->cfg.use_ring && !h->cfg.feature_cgcnn)
+    launch_embed_lut(h->d_weights + h->o_emb, h->d_weights + h->o_Wde, h->d_weights + h->o_bde, h->cfg.n_atoms,
+                     h->cfg.embedding_dim, h->d_weights + h->o_lut, s);
+  HIPCHK(h, hipGetLastError());
+  return SCANN_OK;
+}
+
+extern "C" {
+
+int scann_train_begin(scann_handle_t* h) {
+  if (!h) return SCANN_ERR_INVALID;
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_train_begin: weights not loaded");
+  if (h->weights_exact)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_train_begin: a 128x128 kernel has |w| >= 255.9; the training kernels multiply in split-fp16 "
+                                          "form only (inference of such a checkpoint runs on the exact-fp32 kernels)");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = h->host_master.size();
+  if (!h->t_master) {
+    HIPCHK(h, hipMalloc((void**)&h->t_master, n * 4));
+    HIPCHK(h, hipMalloc((void**)&h->t_grad, n * 4));
+    HIPCHK(h, hipMalloc((void**)&h->t_m, n * 4));
+    HIPCHK(h, hipMalloc((void**)&h->t_v, n * 4));
+    HIPCHK(h, hipMalloc((void**)&h->t_l2, n * 4));
+    if (!h->generic) HIPCHK(h, hipMalloc((void**)&h->t_descs, h->descs.size() * sizeof(RepackDesc)));
+  }
+  HIPCHK(h, hipMemcpy(h->t_master, h->host_master.data(), n * 4, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemset(h->t_grad, 0, n * 4));
+  HIPCHK(h, hipMemset(h->t_m, 0, n * 4));
+  HIPCHK(h, hipMemset(h->t_v, 0, n * 4));
+  if (!h->generic) HIPCHK(h, hipMemcpy(h->t_descs, h->descs.data(), h->descs.size() * sizeof(RepackDesc), hipMemcpyHostToDevice));
+  // kernel_regularizer=l2(1e-4) mask: LocalAttention query/key/filter_geo, ResidualNorm dense_1/2, GlobalAttention
+  // query/key, after_Lc, bf_property (attention.py:27-28,95-109,260-265; scann_model.py:428,441)
+  std::vector<float> l2(n, 0.f);
+  for (size_t i = 0; i < h->specs.size(); ++i) {
+    const std::string& nm = h->specs[i].name;
+    const bool is_kernel = nm.size() > 7 && nm.compare(nm.size() - 7, 7, "/kernel") == 0;
+    const bool reg = is_kernel && (nm.find("local_attention_") == 0 || nm.find("residual_norm_") == 0 ||
+                                   nm.find("global_attention/") == 0 || nm.find("after_Lc/") == 0 || nm.find("bf_property/") == 0);
+    if (reg) std::fill(l2.begin() + h->spec_off[i], l2.begin() + h->spec_off[i] + h->specs[i].numel(), 1.0f);
+  }
+  HIPCHK(h, hipMemcpy(h->t_l2, l2.data(), n * 4, hipMemcpyHostToDevice));
+  if (h->generic) {
+    // the backward's d x = d z . W^T runs through gen_dense_kernel on transposed images of the kernels: one block per kernel, except
+    // that filter_geo of the g_update branch is cut into its centre / geometry / neighbour thirds (attention.py:142-150) and
+    // dense_embed with the ring input into its embedding / ring rows (scann_model.py:367-373) -- each third's d x is a tensor of its own
+    h->gt_descs.clear();
+    h->gt_off.clear();
+    int64_t off = 0;
+    h->gt_max = 0;
+    const int d = h->cfg.local_dim, emb = h->cfg.embedding_dim;
+    for (size_t i = 0; i < h->specs.size(); ++i) {
+      const WeightSpec& sp = h->specs[i];
+      const std::string& nm = sp.name;
+      if (!(sp.cols > 0 && nm.size() > 7 && nm.compare(nm.size() - 7, 7, "/kernel") == 0)) continue;
+      std::vector<int> cuts{0, (int)sp.rows};
+      if (h->cfg.g_update && nm.find("/filter_geo/") != std::string::npos && sp.rows == 3 * d) cuts = {0, d, 2 * d, 3 * d};
+      if (nm == "dense_embed/kernel" && h->cfg.use_ring) cuts = {0, emb, emb + 10};
+      for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+        const int kn = cuts[b + 1] - cuts[b];
+        h->gt_descs.push_back(GenTransDesc{h->spec_off[i], off, cuts[b], kn, (int32_t)sp.cols});
+        h->gt_off[nm + "#" + std::to_string(b)] = off;
+        off += (int64_t)kn * sp.cols;
+        h->gt_max = std::max(h->gt_max, kn * (int)sp.cols);
+      }
+    }
+    if (h->g_WT) (void)hipFree(h->g_WT);
+    if (h->d_gt_descs) (void)hipFree(h->d_gt_descs);
+    h->g_WT = nullptr;
+    h->d_gt_descs = nullptr;
+    HIPCHK(h, hipMalloc((void**)&h->g_WT, (size_t)std::max<int64_t>(off, 1) * 4));
+    HIPCHK(h, hipMalloc((void**)&h->d_gt_descs, h->gt_descs.size() * sizeof(GenTransDesc)));
+    HIPCHK(h, hipMemcpy(h->d_gt_descs, h->gt_descs.data(), h->gt_descs.size() * sizeof(GenTransDesc), hipMemcpyHostToDevice));
+  } else if (!h->train_aux) {
+    // (side streams created with the lowest priority changed nothing: 0.895 vs 0.895 ms per step, profiles/r04_notes.md)
+    // (and so did confining them to half / a quarter of the CUs with hipExtStreamCreateWithCUMask: 0.89-0.93 ms either way)
+    // A handle with a second forward stream lends it to the backward pass as its side stream instead of creating a fifth stream: HIP
+    // deals a process's streams onto 4 hardware queues, and the fifth shares one (training step 0.91-0.92 -> 0.88-0.89 ms with the
+    // default two forward streams; validation forwards on that stream never overlap a step).
+    if (h->nstream >= 2) {
+      h->train_aux = h->streams[1];
+      h->train_aux_borrowed = true;
+    } else {
+      HIPCHK(h, hipStreamCreateWithFlags(&h->train_aux, hipStreamNonBlocking));
+    }
+    HIPCHK(h, hipStreamCreateWithFlags(&h->train_aux2, hipStreamNonBlocking));
+    h->train_ev.resize(128);
+    // fork / join events between streams of ONE device: no system-scope fence (the kernels' own end-of-kernel release already makes
+    // their results visible device-wide, and nothing the host or a DMA engine wrote is ordered by them)
+    const unsigned ev_flags = hipEventDisableTiming | hipEventDisableSystemFence;
+    for (hipEvent_t& e : h->train_ev) HIPCHK(h, hipEventCreateWithFlags(&e, ev_flags));
+  }
+  h->grads_zeroed = false;  // (re)allocated gradient vector: contents unknown
+  h->step_begun = h->step_ended = 0;
+  {
+    const char* e = getenv("SCANN_TRAIN_FUSED");
+    h->train_fused = !(e && e[0] == '0');
+  }
+  h->t_step = 0;
+  return SCANN_OK;
+}
+
+int scann_set_attention_dropout(scann_handle_t* h, float p) {
+  if (!h || !(p >= 0.f && p < 1.f)) return fail(h, SCANN_ERR_INVALID, "scann_set_attention_dropout: rate must be in [0, 1)");
+  h->attn_drop_p = p;
+  return SCANN_OK;
+}
+
+int scann_zero_grads(scann_handle_t* h) {
+  if (!h || !h->t_grad) return fail(h, SCANN_ERR_INVALID, "scann_zero_grads: call scann_train_begin first");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemsetAsync(h->t_grad, 0, h->host_master.size() * 4, h->streams[0]));
+  h->grads_zeroed = true;
+  return SCANN_OK;
+}
+
+int scann_get_grads(scann_handle_t* h, float* out) {
+  if (!h || !h->t_grad || !out) return fail(h, SCANN_ERR_INVALID, "scann_get_grads: no training state");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  HIPCHK(h, hipMemcpy(out, h->t_grad, h->host_master.size() * 4, hipMemcpyDeviceToHost));
+  return SCANN_OK;
+}
+
+int scann_get_weights(scann_handle_t* h, float* out) {
+  if (!h || !out) return SCANN_ERR_INVALID;
+  if (!h->t_master) {
+    memcpy(out, h->host_master.data(), h->host_master.size() * 4);
+    return SCANN_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  HIPCHK(h, hipMemcpy(out, h->t_master, h->host_master.size() * 4, hipMemcpyDeviceToHost));
+  memcpy(h->host_master.data(), out, h->host_master.size() * 4);
+  return SCANN_OK;
+}
+
+int scann_train_forward(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, uint64_t seed, double* sse_out) {
+  if (!h || !db || !targets || !sse_out) return fail(h, SCANN_ERR_INVALID, "scann_train_forward: null argument");
+  if (!h->t_master) return fail(h, SCANN_ERR_INVALID, "scann_train_forward: call scann_train_begin first");
+  HIPCHK(h, hipSetDevice(h->device));
+  scann_train_ws* w = nullptr;
+  const int r = train_forward_impl(h, db, targets, dropout, seed, &w, 2);
+  if (r) return r;
+  hipStream_t s = h->streams[0];
+  HIPCHK(h, hipMemcpyAsync(sse_out, w->sse, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return check_range(h, "scann_train_forward");
+}
+
+int scann_train_backward(scann_handle_t* h, scann_dbatch_t* db, double sse_global, int64_t count_global) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_train_backward: null argument");
+  if (!h->t_grad || !db->train || db->dbg_layers != h->cfg.n_attention || !db->kept)
+    return fail(h, SCANN_ERR_INVALID, "scann_train_backward: run scann_train_forward on this batch first");
+  HIPCHK(h, hipSetDevice(h->device));
+  const double rmse = std::sqrt(sse_global / (double)count_global);
+  const float scale = rmse > 0 ? (float)(1.0 / ((double)count_global * rmse)) : 0.f;
+  h->grads_zeroed = false;
+  return backward_impl(h, db, *db->train, scale, nullptr, false);
+}
+
+int64_t scann_train_debug_read(scann_handle_t* h, scann_dbatch_t* db, const char* name, float* out, int64_t cap) {
+  if (!h || !db || !name || !out) return fail(h, SCANN_ERR_INVALID, "scann_train_debug_read: null argument");
+  if (!h->generic) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_train_debug_read: plain-fp32 (generic-width) training handles only");
+  const scann_train_ws* w = db->train.get();
+  if (!w || w->gen.dbg.empty()) return fail(h, SCANN_ERR_INVALID, "scann_train_debug_read: run scann_train_backward on this batch first");
+  auto it = w->gen.dbg.find(name);
+  if (it == w->gen.dbg.end()) return fail(h, SCANN_ERR_INVALID, std::string("scann_train_debug_read: no tensor named ") + name);
+  if ((int64_t)it->second.second > cap) return fail(h, SCANN_ERR_INVALID, "scann_train_debug_read: output buffer too small");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  HIPCHK(h, hipMemcpy(out, it->second.first, it->second.second * 4, hipMemcpyDeviceToHost));
+  return (int64_t)it->second.second;
+}
+
+int scann_adam_step(scann_handle_t* h, float lr_t, float beta1, float beta2, float eps, float l2) {
+  if (!h || !h->t_master) return fail(h, SCANN_ERR_INVALID, "scann_adam_step: call scann_train_begin first");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int r = adam_impl(h, lr_t, beta1, beta2, eps, l2, 0);
+  if (r) return r;
+  HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  return check_range(h, "scann_adam_step");
+}
+
+// One optimisation step without a host round trip in the middle: forward, [all-reduce of {sse, count}], backward with the loss scale
+// formed on the device, [all-reduce of the gradients], Adam + weight-image refresh; ONE synchronisation at the end.  Same results as
+// scann_train_forward / scann_allreduce_sse / scann_zero_grads / scann_train_backward / scann_allreduce_grads / scann_adam_step.
+int scann_train_step_begin(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, uint64_t seed, float lr_t, float beta1,
+                           float beta2, float eps, float l2) {
+  if (!h || !db || !targets) return fail(h, SCANN_ERR_INVALID, "scann_train_step: null argument");
+  if (h->step_begun - h->step_ended >= 2) return fail(h, SCANN_ERR_INVALID, "scann_train_step_begin: two steps are already in flight; end one first");
+  const int slot = (int)(h->step_begun & 1);
+  if (!h->t_master) return fail(h, SCANN_ERR_INVALID, "scann_train_step: call scann_train_begin first");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  scann_train_ws* w = nullptr;
+  int r = train_forward_impl(h, db, targets, dropout, seed, &w, slot);
+  if (r) return r;
+  // From here on kernels of this step are queued: a failure below must not leave the slot's pinned buffers (targets, statistics)
+  // looking free while that work is still running -- drain the stream before the error goes back (the step is not counted).
+  auto drained = [&](int code) {
+    (void)hipStreamSynchronize(s);
+    if (h->train_aux) (void)hipStreamSynchronize(h->train_aux);
+    if (h->train_aux2) (void)hipStreamSynchronize(h->train_aux2);
+    h->grads_zeroed = false;
+    return code;
+  };
+  const bool single = !(h->comm && h->comm_world > 1);
+  if (!single) {  // losses.py:5-6 is the RMSE of the GLOBAL batch
+    const ncclResult_t nr = ncclAllReduce(w->sse, w->sse, 3, ncclDouble, ncclSum, h->comm, s);
+    if (nr != ncclSuccess) return drained(fail(h, SCANN_ERR_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(nr)));
+    if (hipMemcpyAsync(h->h_stat + 4 * slot, w->sse, 3 * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+      return drained(fail(h, SCANN_ERR_HIP, "scann_train_step_begin: hipMemcpyAsync(statistics) failed"));
+  }
+  if (!h->grads_zeroed && hipMemsetAsync(h->t_grad, 0, h->host_master.size() * 4, s) != hipSuccess)
+    return drained(fail(h, SCANN_ERR_HIP, "scann_train_step_begin: hipMemsetAsync(gradients) failed"));
+  h->grads_zeroed = false;
+  r = backward_impl(h, db, *w, 0.f, w->sse, /*dy_done=*/single);
+  if (r) return drained(r);
+  r = scann_allreduce_grads(h);
+  if (r) return drained(r);
+  r = adam_impl(h, lr_t, beta1, beta2, eps, l2, /*zero_g=*/1);  // leaves the gradient vector zeroed for the next step
+  if (r) return drained(r);
+  h->grads_zeroed = true;
+  if (!h->step_ev[slot]) HIPCHK(h, hipEventCreateWithFlags(&h->step_ev[slot], hipEventDisableTiming));
+  HIPCHK(h, hipEventRecord(h->step_ev[slot], s));
+  db->busy_ev = h->step_ev[slot];
+  h->step_begun += 1;
+  return SCANN_OK;
+}
+
+int scann_train_step_end(scann_handle_t* h, double* sse_out, int64_t* count_out, double* abs_err_out) {
+  if (!h || !sse_out || !count_out) return fail(h, SCANN_ERR_INVALID, "scann_train_step_end: null argument");
+  if (h->step_begun == h->step_ended) return fail(h, SCANN_ERR_INVALID, "scann_train_step_end: no step in flight");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int slot = (int)(h->step_ended & 1);  // the OLDEST step in flight
+  HIPCHK(h, hipEventSynchronize(h->step_ev[slot]));
+  h->step_ended += 1;  // only now: after a failed wait the slot still counts as in flight (its buffers are not reused)
+  *sse_out = h->h_stat[4 * slot];
+  *count_out = (int64_t)(h->h_stat[4 * slot + 1] + 0.5);
+  if (abs_err_out) *abs_err_out = h->h_stat[4 * slot + 2];
+  return check_range(h, "scann_train_step_end");
+}
+
+int scann_train_step(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, uint64_t seed, float lr_t, float beta1,
+                     float beta2, float eps, float l2, double* sse_out, int64_t* count_out) {
+  if (!sse_out || !count_out) return fail(h, SCANN_ERR_INVALID, "scann_train_step: null argument");
+  const int r = scann_train_step_begin(h, db, targets, dropout, seed, lr_t, beta1, beta2, eps, l2);
+  return r ? r : scann_train_step_end(h, sse_out, count_out, nullptr);
+}
+
+}  // extern "C"
