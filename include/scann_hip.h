@@ -168,6 +168,27 @@ int scann_device_memory(scann_handle_t* h, int64_t* free_bytes, int64_t* total_b
 int64_t scann_exact_reruns(const scann_handle_t* h);
 int scann_num_streams(const scann_handle_t* h);
 
+/* ---- outputs beyond y and the GlobalAttention scores (what a user of the reference reads through a Keras sub-model, as
+ * load_model_infer does for the GlobalAttention scores, scann_model.py:86-91) ----
+ * scann_set_outputs selects what the handle's later INFERENCE forwards also write into each batch's own workspace: bit k of
+ * attn_layers = the attention weights of LocalAttention layer k ("local_attention_<k>", attention.py:189); flags = SCANN_OUT_AFTER_LC
+ * (the representation of each local structure, scann_model.py:423-429) | SCANN_OUT_BF_PROPERTY (the structure vector fed to the
+ * head, :437-442).  A layer >= n_attention or an unknown flag is SCANN_ERR_INVALID.  (0, 0) -- the default -- selects nothing: a
+ * forward then launches exactly the kernels it launches without outputs.  Training forwards ignore the selection.  The buffers are
+ * allocated on the first forward of a batch that needs them and freed with the batch.  On the 128-wide kernels, attention weights
+ * of a g_update model need the fused first layer: a forward with scann_set_debug on or SCANN_FUSE_BASIS=0 is SCANN_ERR_UNSUPPORTED.
+ * scann_output_read copies one output of the batch's last forward to host, once that forward has finished (it waits for it; a forward
+ * whose range guard fired is re-run on the exact-fp32 kernels first, as scann_batch_download does): what = SCANN_OUT_LOCAL_ATTENTION
+ * (layer k) -> [n_edge, num_head] in packed edge order, every atom's weights summing to 1 per head; SCANN_OUT_AFTER_LC ->
+ * [n_atom, global_dim]; SCANN_OUT_BF_PROPERTY -> [n_struct, dense_out].  `cap` = floats `out` holds; returns the number of floats
+ * copied (out == NULL: the number it would copy) or a negative status -- SCANN_ERR_INVALID if the output was not selected for the
+ * batch's last forward or does not fit. */
+#define SCANN_OUT_LOCAL_ATTENTION 0
+#define SCANN_OUT_AFTER_LC 1
+#define SCANN_OUT_BF_PROPERTY 2
+int scann_set_outputs(scann_handle_t* h, uint64_t attn_layers, int32_t flags);
+int64_t scann_output_read(scann_handle_t* h, scann_dbatch_t* db, int32_t what, int32_t layer, float* out, int64_t cap);
+
 /* Timed forward of a resident batch: HIP events around every kernel on its stream. */
 int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t* prof);
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CLI with the reference's interface (predict_model.py:95-100): load ``<trained_model>/config.yaml`` and
 ``<trained_model>/models/model_<target>.h5`` in infer mode, predict the whole dataset, pickle GA scores and
-predictions next to the model."""
+predictions next to the model.  ``--outputs after_Lc,local_attention_2,bf_property`` also pickles each named output as
+``<name>_<target>.pickle``: one array per structure, laid out as the padded predict of its batch returns it."""
 import argparse
 import os
 import pickle
@@ -25,7 +26,11 @@ def main(args):
     # the reference loops predict_data over the batches (predict_model.py:49-62); the same per-batch results come out of the
     # pipelined dataset path (batches fused per launch sequence, uploads / launches / downloads overlapped over the streams)
     data = scann.dataIter
-    yp, ga, yt = scann.model.predict_dataset(data, want_ga=True)
+    names = [n for n in (args.outputs or "").split(",") if n]
+    if names:
+        yp, ga, yt, extra = scann.model.predict_dataset(data, want_ga=True, outputs=names)
+    else:
+        yp, ga, yt = scann.model.predict_dataset(data, want_ga=True)
     struct_energy = list(np.asarray(yp) * scann.std + scann.mean)   # predict_data's de-normalisation (scann_model.py:315-319)
     y = list(yt)
     # GA scores in the reference's shape: one [M, 1] array per structure, M = largest structure of ITS batch (zeros behind the
@@ -45,9 +50,13 @@ def main(args):
     print("Save prediction and GA score")
     pickle.dump(ga_scores, open(os.path.join(args.trained_model, "ga_scores_{}.pickle".format(target)), "wb"))
     pickle.dump([y, struct_energy], open(os.path.join(args.trained_model, "energy_pre_{}.pickle".format(target)), "wb"))
+    for n in names:
+        pickle.dump(extra[n], open(os.path.join(args.trained_model, "{}_{}.pickle".format(n, target)), "wb"))
 
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("trained_model", type=str, help="Target trained model path for loading")
+    p.add_argument("--outputs", type=str, default="",
+                   help="comma-separated outputs to pickle as well: local_attention_<k>, after_Lc, bf_property")
     main(p.parse_args())

@@ -1,6 +1,7 @@
-// The body of atom_kernel<FFN, MODE, RT, EX, KEEP> (scann_kernels.hip) as text (a file of its own like scann_edge_body.inc; round 4's
+// The body of atom_kernel<FFN, MODE, RT, EX, KEEP, ZOUT> (scann_kernels.hip) as text (a file of its own like scann_edge_body.inc; round 4's
 // layer launches included both).
-// Expects in scope: FFN, MODE, RT, EX, KEEP (training forward: Dropout and the keep_* stores exist), TAR; `a` (AtomArgs); LDS sTile [2 TAR PLANE_STRIDE halfs], sRed [TAR 8], sPar [7 D];
+// Expects in scope: FFN, MODE, RT, EX, KEEP (training forward: Dropout and the keep_* stores exist), ZOUT (mode 2, inference outputs:
+// after_Lc is stored), TAR; `a` (AtomArgs); LDS sTile [2 TAR PLANE_STRIDE halfs], sRed [TAR 8], sPar [7 D];
 // SCANN_ATOM_BIX = the atom tile of this workgroup.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 31, lh = lane >> 5, cbase = 32 * wave + 4 * lh;
@@ -223,6 +224,7 @@
           st4(a.keep_preA, ooff[rt] + 32 * j, pre);
           st4(a.keep_z, ooff[rt] + 32 * j, z);
         }
+        if constexpr (ZOUT) st4(a.out_z, ooff[rt] + 32 * j, z);  // inference outputs: after_Lc, stored the way keep_z is
         if constexpr (KEEP) tile_store<EX, TAR>(sTile, row, cbase + 8 * j, z);
         else {
           pair2[j & 1] = z;

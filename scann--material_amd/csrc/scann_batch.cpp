@@ -89,8 +89,11 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     if (db->stamps) (void)hipFree(db->stamps);
     char* const gen_ws = db->gen_ws;  // (the generic-width forward's workspace is kept across calls, like the arena below)
     const size_t gen_ws_bytes = db->gen_ws_bytes;
+    char* const out_block = db->out_block;  // (... and so is the block of the inference outputs)
+    const size_t out_cap = db->out_cap;
     *db = scann_dbatch();
     db->gen_ws = gen_ws; db->gen_ws_bytes = gen_ws_bytes;
+    db->out_block = out_block; db->out_cap = out_cap;
     db->owns_arena = false;
   } else {
     db = new scann_dbatch();
@@ -294,6 +297,7 @@ namespace scann {
 void free_batch(scann_dbatch* db) {
   if (db->arena && db->owns_arena) cached_free(db->arena);
   cached_free(db->gen_ws);
+  cached_free(db->out_block);
   cached_free(db->dbg_c);
   cached_free(db->dbg_g);
   cached_free(db->dbg_ctx);
@@ -312,6 +316,21 @@ int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who) {
   HIPCHK(h, hipMemcpy(&bad, db->pack_flag, 4, hipMemcpyDeviceToHost));
   if (bad & 1) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": an unmasked neighbour slot points at a padded atom (or outside the structure)");
   if (bad & 2) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": atomic number outside the embedding table (n_atoms)");
+  return SCANN_OK;
+}
+
+int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, bool* rerun) {
+  *rerun = false;
+  if (!h->range_flag || h->strict_range || db->kept) return SCANN_OK;
+  const int32_t code = *reinterpret_cast<volatile int32_t*>(h->range_flag + db->last_slot);
+  const int site = code >> 8;
+  if (!code || site < 1 || site > 4) return SCANN_OK;
+  h->range_flag[db->last_slot] = 0;
+  const int r = run_forward(h, db, s, nullptr, true);
+  if (r) return r;
+  h->exact_reruns++;
+  *rerun = true;
+  HIPCHK(h, hipStreamSynchronize(s));
   return SCANN_OK;
 }
 
@@ -380,17 +399,11 @@ int scann_batch_download(scann_handle_t* h, scann_dbatch_t* db, float* y_out, fl
   // The forward's range guard fired: an activation left the range of the split-fp16 projections (sites 1-4).  The reference runs any
   // fp32 values (attention.py:95-113), so the forward is run again on the exact-fp32 instantiations (1/16 of the matrix rate, this
   // batch only) instead of handing an error back -- unless SCANN_STRICT_RANGE=1 asks for the error.
-  if (h->range_flag && !h->strict_range && !db->kept) {
-    const int32_t code = *reinterpret_cast<volatile int32_t*>(h->range_flag + db->last_slot);
-    const int site = code >> 8;
-    if (code && site >= 1 && site <= 4) {
-      h->range_flag[db->last_slot] = 0;
-      const int r = run_forward(h, db, s, nullptr, true);
-      if (r) return r;
-      h->exact_reruns++;
-      const int rf3 = fetch_results(h, db, s, y_out, ga_attn_out);
-      if (rf3) return rf3;
-    }
+  bool rerun = false;
+  if (const int r = rerun_if_out_of_range(h, db, s, &rerun)) return r;
+  if (rerun) {
+    const int rf3 = fetch_results(h, db, s, y_out, ga_attn_out);
+    if (rf3) return rf3;
   }
   db->idle = true;
   return check_range(h, "scann_batch_download", db->last_slot);

@@ -1,7 +1,8 @@
-// The body of edge_kernel<GUPD, RT, FB, EX, KEEP, DEAD> (scann_kernels.hip) as text, in a file of its own (round 4's layer launches included
+// The body of edge_kernel<GUPD, RT, FB, EX, KEEP, DEAD, ATTN> (scann_kernels.hip) as text, in a file of its own (round 4's layer launches included
 // it a second time; as an inlined device function the same body moved hipcc's register allocation of the 168-VGPR kernel: +3.7 %).
 // Expects in scope: GUPD, RT, FB, EX, KEEP (training forward: the keep_* stores and the attention
-// dropout exist), DEAD (geom' is not stored), BLK (piece-major geometry tiles), TEK; `a` (EdgeArgs); LDS sTile [2 TEK PLANE_STRIDE halfs],
+// dropout exist), DEAD (geom' is not stored), ATTN (inference outputs: the attention weights are stored), BLK (piece-major geometry
+// tiles), TEK; `a` (EdgeArgs); LDS sTile [2 TEK PLANE_STRIDE halfs],
 // sQ [TQ LDS_STRIDE], sE [NHEAD (TEK + 1)] with the index maps SE_STAT(wave, row) / SE_LOGIT(row, head), sPar [5 D], sOff [TQ + 1];
 // SCANN_EDGE_TIX = the edge tile of this workgroup.
   _Float16* const sH = reinterpret_cast<_Float16*>(sTile);
@@ -465,6 +466,12 @@
         cx.y = fmaf(pa, ka.y, fmaf(pb, kb.y, cx.y));
         cx.z = fmaf(pa, ka.z, fmaf(pb, kb.z, cx.z));
         cx.w = fmaf(pa, ka.w, fmaf(pb, kb.w, cx.w));
+      }
+      if (ATTN) {  // inference outputs: the weights of the context sum (attention.py:189), a second pass over the logits still in sE --
+                   // the head's four lanes take every fourth edge: one writer per (edge, head), 4 edges x 8 heads = 128 contiguous bytes
+                   // per 32 lanes.  A chunk tile knows its own chunk's maximum and sum only: exp(e - m_chunk), finished by attn_merge_kernel
+        const float rn = part >= 0 ? 1.f : __builtin_amdgcn_rcpf(ssum);
+        for (int n = e0 + (c4 & 3); n < e1; n += 4) a.attn_out[(size_t)(eb + n) * NHEAD + h] = fast_exp(sE[SE_LOGIT(n, h)] - m) * rn;
       }
       if (part >= 0) {  // chunk tile: leave the softmax state of this chunk for edge_merge_kernel
         float* pb = a.part_buf + (size_t)part * 3 * D + 4 * c4;

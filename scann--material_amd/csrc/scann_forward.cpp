@@ -18,6 +18,44 @@ int ensure_debug(scann_handle* h, scann_dbatch* db) {
   return SCANN_OK;
 }
 
+// The inference outputs the handle selected (scann_set_outputs) for this forward of `db` (a training forward: none): the batch's output
+// block is sized for them -- allocated by the first forward that needs it, grown when a selection or batch needs more -- and db->out_*
+// record what this forward writes.  With nothing selected nothing happens.
+int ensure_outputs(scann_handle* h, scann_dbatch* db) {
+  const bool infer = !h->in_train_forward;
+  db->out_layers = infer ? h->out_layers : 0;
+  db->out_flags = infer ? h->out_flags : 0;
+  db->out_attn = db->out_z = db->out_bf = nullptr;
+  if (!db->out_layers && !db->out_flags) return SCANN_OK;
+  const scann_config_t& c = h->cfg;
+  const size_t n_attn = (size_t)__builtin_popcountll(db->out_layers) * db->n_edge * c.num_head;
+  const size_t n_z = db->out_flags & SCANN_OUT_AFTER_LC ? (size_t)db->n_atom * c.global_dim : 0;
+  const size_t n_bf = db->out_flags & SCANN_OUT_BF_PROPERTY ? (size_t)db->n_struct * c.dense_out : 0;
+  const size_t need = align_up(n_attn * 4) + align_up(n_z * 4) + align_up(n_bf * 4) + 256;
+  if (db->out_cap < need) {
+    HIPCHK(h, hipDeviceSynchronize());  // (an earlier forward of the batch, on any stream, may still write the old block)
+    cached_free(db->out_block);
+    db->out_block = nullptr;
+    db->out_cap = 0;
+    HIPCHK(h, cached_malloc((void**)&db->out_block, need));
+    db->out_cap = need;
+  }
+  char* p = db->out_block;
+  if (n_attn) db->out_attn = reinterpret_cast<float*>(p);
+  p += align_up(n_attn * 4);
+  if (n_z) db->out_z = reinterpret_cast<float*>(p);
+  p += align_up(n_z * 4);
+  if (n_bf) db->out_bf = reinterpret_cast<float*>(p);
+  return SCANN_OK;
+}
+
+// where layer l's attention weights go in this forward (null: not selected, or a batch without edges)
+float* attn_out_of(const scann_handle* h, const scann_dbatch* db, int l) {
+  if (!db->out_attn || !((db->out_layers >> l) & 1) || db->n_edge <= 0) return nullptr;
+  const uint64_t below = db->out_layers & ((uint64_t(1) << l) - 1);
+  return db->out_attn + (size_t)__builtin_popcountll(below) * db->n_edge * h->cfg.num_head;
+}
+
 // create_model (scann_model.py:362-447) for a handle whose widths are not 128 / 8: one plain-fp32 kernel per formula
 // (scann_generic.hip) on the same packed batch.  kp non-null: the training forward -- Dropout layers active (kp->drop_p, kp->attn_p,
 // kp->seed), every intermediate kept in kp, the property head as dense launches.
@@ -131,7 +169,8 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
     }
     dense(GenSeg{cc, db->edge_col, d}, GenSeg{b.Gn, nullptr, d}, none, 2, 1, la + "/key", d, d, E, 0, nullptr, nullptr, b.K);
     dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, la + "/query", d, d, A, 0, nullptr, nullptr, b.q);
-    launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed);
+    launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed,
+                    kp ? nullptr : attn_out_of(h, db, l));
     launch_gen_layernorm(b.t1, nullptr, W(la + "/layer_norm/gamma"), W(la + "/layer_norm/beta"), A, d, b.ctx, s);
     if (c.use_attn_norm) {  // ResidualNorm (attention.py:37-40): LayerNorm(x + Dropout(dense_2(swish(dense_1 x))))
       dense(GenSeg{b.ctx, nullptr, d}, none, none, 1, 0, rn + "/dense_1", d, d, A, 1, nullptr, nullptr, b.h1, b.pre1);
@@ -148,12 +187,13 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   }
   // ---- readout (scann_model.py:424-447; attention.py:267-318) ----
   float* z_pre = kp ? take(fA * dg) : nullptr;
+  if (!kp && db->out_z) z = db->out_z;  // inference outputs: after_Lc straight into the batch's output block
   dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, "after_Lc", d, dg, A, 1, nullptr, nullptr, z, z_pre);
   dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/query", dg, dg, A, 0, nullptr, nullptr, gq);
   dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/key", dg, dg, A, 0, nullptr, nullptr, gk);
   float* rep = kp ? take(fB * dg) : nullptr;
   launch_gen_readout(db->mol_offset, B, db->max_atoms, gq, gk, dg, dout, c.use_ga_norm, c.relu_out, W("bf_property/kernel"), W("bf_property/bias"),
-                     W("predict_property/kernel"), W("predict_property/bias"), db->ga, db->y, s, rep);
+                     W("predict_property/kernel"), W("predict_property/bias"), db->ga, db->y, s, rep, kp ? nullptr : db->out_bf);
   if (kp) {
     float *hid_pre = take(fB * dout), *hid = take(fB * dout);
     dense(GenSeg{rep, nullptr, dg}, none, none, 1, 0, "bf_property", dg, dout, B, 1, nullptr, nullptr, hid, hid_pre);
@@ -192,6 +232,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
   HIPCHK(h, wait_upload(db, s));  // the inputs' copy (scann_batch_upload returned when it was enqueued)
+  if (const int r = ensure_outputs(h, db)) return r;
   if (h->generic) {
     if (tm) { tm->mark(-1); }
     const int r = run_forward_generic(h, db, s, h->in_train_forward ? h->gen_keep : nullptr);
@@ -217,6 +258,11 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   // inference: the first layer's edge kernel computes its geometry rows from (dist, weight) itself -- geom0 is never written by a
   // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
   const bool fuse_basis = !exact && h->fuse_basis && c.g_update && L > 0 && !h->debug && !h->in_train_forward && db->n_edge > 0;
+  // the attention-weight stores exist in the piece-major g_update kernels (and the row-major base / exact ones) only
+  if (db->out_layers && c.g_update && !exact && !fuse_basis && db->n_edge > 0) {
+    db->out_layers = db->out_flags = 0;
+    return fail(h, SCANN_ERR_UNSUPPORTED, "forward: local-attention outputs need the fused first layer (not with scann_set_debug or SCANN_FUSE_BASIS=0)");
+  }
   if (!fuse_basis) {
     if (c.g_update) launch_basis(h->basis, db->dist, db->weight, db->n_edge, g_of(0), s);
     else launch_basis_raw(h->cd, db->dist, db->n_edge, db->gd, s);
@@ -285,6 +331,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
       a.WAh = h->head.Wah; a.bA = h->head.ba; a.WCh = h->head.Wgqh; a.bC = h->head.bgq; a.WDh = h->head.Wgkh; a.bD = h->head.bgk;
       a.oB = db->gk; a.oC = db->gq;
       if (h->debug && h->in_train_forward && db->keep_preA) { a.keep_preA = db->keep_preA; a.keep_z = db->keep_z; }
+      a.out_z = db->out_z;
     }
 #ifdef SCANN_STAMPS
     if (getenv("SCANN_STAMP_ATOM") && l >= 1 && l < L) {  // phase clocks of atom_kernel<true, 0> (the last such launch wins)
@@ -348,6 +395,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     }
     ea.tile_part = db->tile_part; ea.part_buf = db->part_buf;
     ea.xcd_remap = h->xcd_remap;
+    ea.attn_out = attn_out_of(h, db, l);
     if (h->in_train_forward && h->attn_drop_p > 0.f) {  // validation passes run with scann_set_attention_dropout(h, 0): trainer.fit
       ea.attn_drop_p = h->attn_drop_p;
       ea.attn_drop_seed = h->train_seed;
@@ -362,6 +410,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
 #endif
     launch_edge(ea, s);
     launch_edge_merge(db->big_tab, db->n_big, db->part_buf, ea.q, ea.p.ln_g, ea.p.ln_b, ea.ctx, rflag, l, s);
+    if (ea.attn_out) launch_attn_merge(db->big_tab, db->n_big, db->part_buf, db->edge_offset, db->tile_rows, ea.attn_out, s);
     if (sample) {
       (void)hipEventRecord(ev1, s);
       h->time_ev.push_back(ev0);
@@ -374,7 +423,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   ReadoutArgs r{};
   r.mol_offset = db->mol_offset; r.n_struct = db->n_struct; r.max_atoms = db->max_atoms;
   r.gq = db->gq; r.gk = db->gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = c.relu_out;
-  r.p = h->head; r.ga_attn = db->ga; r.y = db->y;
+  r.p = h->head; r.ga_attn = db->ga; r.y = db->y; r.bf_out = db->out_bf;
   launch_readout(r, s);
   if (tm) tm->mark(3);
   HIPCHK(h, hipGetLastError());
@@ -491,5 +540,46 @@ int scann_debug_read(scann_handle_t* h, scann_dbatch_t* db, int what, int layer,
 }
 
 int64_t scann_exact_reruns(const scann_handle_t* h) { return h ? h->exact_reruns : -1; }
+
+int scann_set_outputs(scann_handle_t* h, uint64_t attn_layers, int32_t flags) {
+  if (!h) return SCANN_ERR_INVALID;
+  const int L = h->cfg.n_attention;
+  if (L < 64 && (attn_layers >> L) != 0)
+    return fail(h, SCANN_ERR_INVALID, "scann_set_outputs: local_attention layer >= n_attention (" + std::to_string(L) + ")");
+  if (flags & ~(SCANN_OUT_AFTER_LC | SCANN_OUT_BF_PROPERTY)) return fail(h, SCANN_ERR_INVALID, "scann_set_outputs: unknown output flag");
+  h->out_layers = attn_layers;
+  h->out_flags = flags;
+  return SCANN_OK;
+}
+
+int64_t scann_output_read(scann_handle_t* h, scann_dbatch_t* db, int32_t what, int32_t layer, float* out, int64_t cap) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_output_read: null argument");
+  const scann_config_t& c = h->cfg;
+  int64_t n = 0;
+  if (what == SCANN_OUT_LOCAL_ATTENTION) {
+    if (layer < 0 || layer >= c.n_attention || layer >= 64 || !((db->out_layers >> layer) & 1))
+      return fail(h, SCANN_ERR_INVALID, "scann_output_read: local_attention_" + std::to_string(layer) + " was not selected for the batch's last forward");
+    n = (int64_t)db->n_edge * c.num_head;
+  } else if (what == SCANN_OUT_AFTER_LC || what == SCANN_OUT_BF_PROPERTY) {
+    if (!(db->out_flags & what))
+      return fail(h, SCANN_ERR_INVALID, std::string("scann_output_read: ") + (what == SCANN_OUT_AFTER_LC ? "after_Lc" : "bf_property") +
+                                            " was not selected for the batch's last forward");
+    n = what == SCANN_OUT_AFTER_LC ? (int64_t)db->n_atom * c.global_dim : (int64_t)db->n_struct * c.dense_out;
+  } else {
+    return fail(h, SCANN_ERR_INVALID, "scann_output_read: unknown output");
+  }
+  if (!out) return n;  // the size, without waiting for the forward
+  if (cap < n) return fail(h, SCANN_ERR_INVALID, "scann_output_read: " + std::to_string(n) + " floats do not fit a buffer of " + std::to_string(cap));
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[db->last_slot];
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (const int rp = check_pack_flag(h, db, "scann_output_read")) return rp;
+  bool rerun = false;  // (the forward's range guard fired: the outputs come from the exact-fp32 re-run, as y does from scann_batch_download)
+  if (const int r = rerun_if_out_of_range(h, db, s, &rerun)) return r;
+  if (const int r = check_range(h, "scann_output_read", db->last_slot)) return r;
+  const float* src = what == SCANN_OUT_LOCAL_ATTENTION ? attn_out_of(h, db, layer) : what == SCANN_OUT_AFTER_LC ? db->out_z : db->out_bf;
+  if (n && src) HIPCHK(h, hipMemcpy(out, src, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return n;
+}
 
 }  // extern "C"

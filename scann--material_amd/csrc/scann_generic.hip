@@ -171,7 +171,7 @@ __global__ void gen_mul_kernel(const float* __restrict__ a, const float* __restr
 // sum_n attn[n][head(o)] K[n][o] + q[o] (the residual is the UNSCALED query, attention.py:198-212).  No edges: context = q.
 __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__ q, const float* __restrict__ K, const int32_t* __restrict__ edge_offset,
                                                        int n_atom, int d, int H, float* __restrict__ ctx, float drop_p, unsigned drop_tag,
-                                                       unsigned long long drop_seed) {
+                                                       unsigned long long drop_seed, float* __restrict__ attn_out) {
 #pragma clang fp contract(off)
   extern __shared__ float sL[];  // [deg][H] logits -> attention
   const int at = blockIdx.x, tid = threadIdx.x;
@@ -197,6 +197,7 @@ __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__
     }
     for (int n = 0; n < deg; ++n) {
       float at = sL[n * H + h] / ss;
+      if (attn_out) attn_out[(size_t)(e0 + n) * H + h] = at;  // inference outputs: the attention weights (attention.py:189)
       if (drop_p > 0.f) at = at * drop_scale(drop_seed, drop_tag, (size_t)(e0 + n) * H + h, drop_p);  // Dropout(0.05), attention.py:191 (training)
       sL[n * H + h] = at;
     }
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void gen_readout_kernel(const int32_t* __restrict__ mol_offset, const float* __restrict__ gq, const float* __restrict__ gk, int dg,
                                                           int dout, int use_ga_norm, int relu_out, const float* __restrict__ Wb, const float* __restrict__ bb,
                                                           const float* __restrict__ wo, const float* __restrict__ bo, float* __restrict__ ga_attn,
-                                                          float* __restrict__ y, float* __restrict__ rep_out) {
+                                                          float* __restrict__ y, float* __restrict__ rep_out, float* __restrict__ bf_out) {
 #pragma clang fp contract(off)
   extern __shared__ float sm[];  // [n] scores -> attention, [dg] pooled rows, [dout] hidden, [4] reductions
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -280,7 +281,9 @@ __global__ __launch_bounds__(256) void gen_readout_kernel(const int32_t* __restr
   for (int o = tid; o < dout; o += 256) {
     float s = 0.f;
     for (int k = 0; k < dg; ++k) s = fmaf(sRep[k], Wb[(size_t)k * dout + o], s);
-    part += swish_exact(s + bb[o]) * wo[o];
+    const float hb = swish_exact(s + bb[o]);
+    if (bf_out) bf_out[(size_t)blockIdx.x * dout + o] = hb;  // inference outputs: bf_property
+    part += hb * wo[o];
   }
   part = block_sum(part);
   if (tid == 0) {
@@ -325,18 +328,18 @@ void launch_gen_mul(const float* a, const float* b, size_t n, float* out, hipStr
   hipLaunchKernelGGL(gen_mul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, b, n, out);
 }
 void launch_gen_attn(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
-                     float drop_p, unsigned drop_tag, unsigned long long drop_seed) {
+                     float drop_p, unsigned drop_tag, unsigned long long drop_seed, float* attn_out) {
   if (n_atom <= 0) return;
   hipLaunchKernelGGL(gen_attn_kernel, dim3(n_atom), dim3(256), (size_t)std::max(1, max_degree) * H * sizeof(float), s, q, K, edge_offset, n_atom, d, H, ctx,
-                     drop_p, drop_tag, drop_seed);
+                     drop_p, drop_tag, drop_seed, attn_out);
 }
 void launch_gen_readout(const int32_t* mol_offset, int n_struct, int max_atoms, const float* gq, const float* gk, int dg, int dout, int use_ga_norm,
                         int relu_out, const float* Wb, const float* bb, const float* wo, const float* bo, float* ga_attn, float* y, hipStream_t s,
-                        float* rep_out) {
+                        float* rep_out, float* bf_out) {
   if (n_struct <= 0) return;
   const size_t lds = ((size_t)max_atoms + dg + dout + 4) * sizeof(float);
   hipLaunchKernelGGL(gen_readout_kernel, dim3(n_struct), dim3(256), lds, s, mol_offset, gq, gk, dg, dout, use_ga_norm, relu_out, Wb, bb, wo, bo, ga_attn, y,
-                     rep_out);
+                     rep_out, bf_out);
 }
 
 }  // namespace scann

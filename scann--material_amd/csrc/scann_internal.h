@@ -167,6 +167,8 @@ struct AtomArgs {
   int32_t layer;               // layer whose projections this launch computes (for the range-guard message)
   // exact-fp32 projections (EX instantiation): Wf1h, Wf2h, WAh .. WDh then point at fp32 fragment-order images (pack_weight)
   int32_t exact;
+  // mode 2, inference outputs (scann_set_outputs): after_Lc = swish(c Wa + ba) [n_atom,128] is stored here (the ZOUT instantiation), or null
+  float* out_z;
 };
 void launch_atom(const AtomArgs& a, hipStream_t s);
 
@@ -214,9 +216,15 @@ struct EdgeArgs {
   int32_t layer;
   int32_t exact;               // exact-fp32 projections (EX instantiation): p.W2h, p.Wkh then point at fp32 fragment-order images
   LayerParams p;
+  // inference outputs (scann_set_outputs): the layer's attention weights (attention.py:189) per (edge, head), [n_edge, NHEAD] (the ATTN
+  // instantiation), or null.  A chunk tile stores exp(e - m_chunk) unnormalised; launch_attn_merge finishes those rows
+  float* attn_out;
 };
 void launch_edge(const EdgeArgs& a, hipStream_t s);
 // softmax merge of the chunk tiles of every big atom (+ unscaled-query residual + LayerNorm, attention.py:189-214)
+// inference outputs: the attention weights of the chunk tiles of atoms with more than `chunk` neighbours, exp(e - m_chunk) as the
+// chunk tiles stored them, scaled by exp(m_chunk - M) / S (the merged softmax state of edge_merge_kernel) in place
+void launch_attn_merge(const int32_t* big_tab, int n_big, const float* part_buf, const int32_t* edge_offset, int chunk, float* attn, hipStream_t s);
 void launch_edge_merge(const int32_t* big_tab, int n_big, const float* part_buf, const float* q, const float* ln_g,
                        const float* ln_b, float* ctx, int32_t* range_flag, int layer, hipStream_t s);
 
@@ -249,11 +257,13 @@ void launch_gen_layernorm(const float* X, const float* res, const float* gamma, 
 void launch_gen_gauss(const float* x, const float* centres, int n, float* out, hipStream_t s);
 void launch_gen_mul(const float* a, const float* b, size_t n, float* out, hipStream_t s);
 void launch_gen_attn(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
-                     float drop_p = 0.f, unsigned drop_tag = 0, unsigned long long drop_seed = 0);
-// rep_out non-null (training forward): the pooled rows [n_struct, dg] are stored and the property head is NOT evaluated
+                     float drop_p = 0.f, unsigned drop_tag = 0, unsigned long long drop_seed = 0, float* attn_out = nullptr);  // attn_out non-null
+                     // (inference outputs): the normalised attention weights are stored, [n_edge, H]
+// rep_out non-null (training forward): the pooled rows [n_struct, dg] are stored and the property head is NOT evaluated;
+// bf_out non-null (inference outputs): bf_property [n_struct, dout] is stored
 void launch_gen_readout(const int32_t* mol_offset, int n_struct, int max_atoms, const float* gq, const float* gk, int dg, int dout, int use_ga_norm,
                         int relu_out, const float* Wb, const float* bb, const float* wo, const float* bo, float* ga_attn, float* y, hipStream_t s,
-                        float* rep_out = nullptr);
+                        float* rep_out = nullptr, float* bf_out = nullptr);
 
 // ---- generic-width training (scann_generic_train.hip) ----
 struct GenTransDesc {  // WT[dst + o * kn + kk] = W[src + (k0 + kk) * N + o]: rows [k0, k0 + kn) of a row-major [*, N] kernel, transposed
@@ -298,6 +308,7 @@ struct ReadoutArgs {
   HeadParams p;
   float* ga_attn;             // [n_atom]
   float* y;                   // [n_struct]
+  float* bf_out;              // [n_struct,128] bf_property = swish(rep Wb + bb) (scann_model.py:437-442), or null (inference outputs)
 };
 void launch_readout(const ReadoutArgs& a, hipStream_t s);
 

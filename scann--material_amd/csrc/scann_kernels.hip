@@ -42,10 +42,13 @@ namespace scann {
 // (workgroups per CU: three at 64 rows, four at 32 -- except where the register allocator could not be kept below the limit without
 // spilling and occupancy is not what bounds the launch: the exact-fp32 re-run at 64 rows (1/16 of the matrix rate), the base branch's
 // query-only kernel at 32 rows; tests/test_host.py reads scratch sizes and register counts from the built library)
-template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false>
+// ZOUT: mode 2 of an inference forward that returns after_Lc (scann_set_outputs): z is stored to out_z as the training forward stores
+// keep_z (a compile-time flag: a branch around a store in these kernels has cost a spill before, tests/test_host.py)
+template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false, bool ZOUT = false>
 __global__ __launch_bounds__(256, RT == 2 ? (EX ? 2 : 3) : (MODE == 1 ? 3 : 4)) void atom_kernel(AtomArgs a) {
 #pragma clang fp contract(off)  // fusions are written out: both row-tile copies of a formula round alike (see edge_kernel)
   static_assert(!(EX && KEEP), "the training forward runs the split-fp16 kernels");
+  static_assert(!ZOUT || (MODE == 2 && !KEEP), "after_Lc is an output of the readout launch of inference forwards");
   constexpr int TAR = 32 * RT;  // atom rows per tile
   __shared__ __attribute__((aligned(16))) unsigned char sTile[2 * TAR * PLANE_STRIDE * 2];  // hi / lo planes of the current GEMM input
   __shared__ __attribute__((aligned(16))) float sRed[TAR * 8];  // LayerNorm partial statistics [wave][row][mean, m2]
@@ -71,6 +74,20 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
   const int rows = a.n_atom <= 32 * 1024 ? 32 : 64;
   const dim3 grid((a.n_atom + rows - 1) / rows), block(256);
   const bool keep = !a.exact && (a.drop_p > 0.f || a.keep_pre1 || a.keep_T2 || a.keep_preA);  // training forward
+  if (a.mode == 2 && a.out_z) {  // inference forward that returns after_Lc (never a training forward: run_forward)
+#define SCANN_ATOM_Z(F)                                                                                        \
+  do {                                                                                                         \
+    if (a.exact) {                                                                                             \
+      if (rows == 32) hipLaunchKernelGGL((atom_kernel<F, 2, 1, true, false, true>), grid, block, 0, s, a);     \
+      else hipLaunchKernelGGL((atom_kernel<F, 2, 2, true, false, true>), grid, block, 0, s, a);                \
+    } else if (rows == 32) hipLaunchKernelGGL((atom_kernel<F, 2, 1, false, false, true>), grid, block, 0, s, a); \
+    else hipLaunchKernelGGL((atom_kernel<F, 2, 2, false, false, true>), grid, block, 0, s, a);                 \
+  } while (0)
+    if (a.ffn) SCANN_ATOM_Z(true);
+    else SCANN_ATOM_Z(false);
+#undef SCANN_ATOM_Z
+    return;
+  }
 #define SCANN_ATOM_CASE(F, M)                                                                               \
   do {                                                                                                      \
     if (a.exact) {                                                                                          \
@@ -125,7 +142,9 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
 // KEEP: the training forward's instantiation -- the keep_* stores and the attention dropout exist only there (as uniform branches in
 // the inference kernels they cut every epilogue into basic blocks of one LDS read -> wait -> arithmetic -> store each).
 // DEAD: the last layer of an inference forward -- nobody reads geom' (scann_model.py:415-421 threads it to the NEXT layer only).
-template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false>
+// ATTN: an inference forward that returns this layer's attention weights (scann_set_outputs) -- the softmax stores them per (edge,
+// head).  A template flag like KEEP: with it off every instantiation is the code it was.
+template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false, bool ATTN = false>
 __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) {
 #pragma clang fp contract(off)  // fusions are written out (fmaf): both unrolled row-tile copies of a formula must round alike,
                                 // so that a row's result does not depend on where in a tile it lands (batch-composition invariance)
@@ -133,6 +152,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
   static_assert(!(FB && EX), "the exact fallback runs the plain first layer");
   static_assert(!KEEP || (!FB && !EX && !DEAD), "the training forward runs the plain split-fp16 kernel and keeps every layer's geometry");
   static_assert(!DEAD || GUPD, "the base branch stores no geometry");
+  static_assert(!(ATTN && KEEP), "the training forward returns no attention weights");
   constexpr int TEK = 32 * RT;  // edge rows per tile: 64 (three workgroups per CU) or, for launches of one round, 32 (four)
   // piece-major geometry tiles (scann_edge_body.inc): the inference kernels, whose geometry nobody else reads.  The training / debug
   // forward (KEEP) and the exact re-run (EX: its first layer reads basis_kernel's row-major geom0) keep [n_edge,128] rows.
@@ -210,6 +230,30 @@ void launch_edge_merge(const int32_t* big_tab, int n_big, const float* part_buf,
     hipLaunchKernelGGL(edge_merge_kernel, dim3(n_big), dim3(128), 0, s, big_tab, part_buf, q, ln_g, ln_b, ctx, range_flag, layer);
 }
 
+// Attention weights of the atoms with more than 64 neighbours (inference outputs): chunk i's tile stored exp(e - m_i) per (edge, head);
+// the weight is that times exp(m_i - M) / S, with M = max m_i and S = sum s_i exp(m_i - M) formed in edge_merge_kernel's order
+// (column 16 h of part_buf holds head h's m_i, s_i).  One workgroup per such atom, one thread per (edge, head).
+__global__ __launch_bounds__(256) void attn_merge_kernel(const int32_t* __restrict__ big_tab, const float* __restrict__ part_buf,
+                                                         const int32_t* __restrict__ edge_offset, int chunk, float* __restrict__ attn) {
+  const int atom = big_tab[3 * blockIdx.x], s0 = big_tab[3 * blockIdx.x + 1], ns = big_tab[3 * blockIdx.x + 2];
+  const int e0 = edge_offset[atom], deg = edge_offset[atom + 1] - e0;
+  for (int i = threadIdx.x; i < deg * NHEAD; i += blockDim.x) {
+    const int n = i / NHEAD, h = i - n * NHEAD;
+    const float* pb = part_buf + (size_t)s0 * 3 * D + HDIM * h;
+    float M = -INFINITY;
+    for (int k = 0; k < ns; ++k) M = fmaxf(M, pb[(size_t)k * 3 * D]);
+    float S = 0.f;
+    for (int k = 0; k < ns; ++k) S += pb[(size_t)k * 3 * D + D] * fast_exp(pb[(size_t)k * 3 * D] - M);
+    const float mi = pb[(size_t)(n / chunk) * 3 * D];
+    float* const w = attn + (size_t)(e0 + n) * NHEAD + h;
+    *w = *w * fast_exp(mi - M) * __builtin_amdgcn_rcpf(S);
+  }
+}
+
+void launch_attn_merge(const int32_t* big_tab, int n_big, const float* part_buf, const int32_t* edge_offset, int chunk, float* attn, hipStream_t s) {
+  if (n_big > 0 && attn) hipLaunchKernelGGL(attn_merge_kernel, dim3(n_big), dim3(256), 0, s, big_tab, part_buf, edge_offset, chunk, attn);
+}
+
 // centre atom of every edge: one thread per atom writes its CSR row's entries (a batch has ~8 edges per atom)
 // (zero_word: a device word this launch clears on its way -- the flag of the pack_padded_kernel launch behind it)
 __global__ void edge_row_kernel(const int32_t* __restrict__ edge_offset, int n_atom, int32_t* __restrict__ edge_row, int32_t* __restrict__ zero_word) {
@@ -271,10 +315,20 @@ void launch_edge(const EdgeArgs& a, hipStream_t s) {
     if (a.tile_rows == 32) SCANN_EDGE_GO(G, 1, __VA_ARGS__);                \
     else SCANN_EDGE_GO(G, 2, __VA_ARGS__);                                  \
   } while (0)
-  if (a.exact) {  // never with the fused first layer (run_forward launches basis_kernel for it)
+  if (a.exact && a.attn_out) {  // (the exact re-run of a forward that returns attention weights returns the re-run's)
+    if (!a.g_update) SCANN_EDGE_ROWS(false, false, true, false, false, true);
+    else if (dead) SCANN_EDGE_ROWS(true, false, true, false, true, true);
+    else SCANN_EDGE_ROWS(true, false, true, false, false, true);
+  } else if (a.exact) {  // never with the fused first layer (run_forward launches basis_kernel for it)
     if (!a.g_update) SCANN_EDGE_ROWS(false, false, true, false, false);
     else if (dead) SCANN_EDGE_ROWS(true, false, true, false, true);
     else SCANN_EDGE_ROWS(true, false, true, false, false);
+  } else if (a.attn_out) {  // inference kernels that store the attention weights: the base branch's row-major kernel (its KEEP twin differs
+                            // only by the training stores), the piece-major g_update family (run_forward refuses row-major g_update forwards)
+    if (!a.g_update) SCANN_EDGE_ROWS(false, false, false, false, false, true);
+    else if (a.fuse_basis) SCANN_EDGE_ROWS(true, true, false, false, false, true);
+    else if (a.geom_dead) SCANN_EDGE_ROWS(true, false, false, false, true, true);
+    else SCANN_EDGE_ROWS(true, false, false, false, false, true);
   } else if (keep) {
     if (a.g_update) SCANN_EDGE_ROWS(true, false, false, true, false);
     else SCANN_EDGE_ROWS(false, false, false, true, false);
@@ -583,7 +637,11 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
     const float hs = (h0 + h1) + (h2 + h3);
     if (half == 1) sHead[f] = hs;
     __syncthreads();
-    if (half == 0) part = swish_exact((hs + sHead[f]) + a.p.bb[f]) * a.p.wo[f];
+    if (half == 0) {
+      const float hb = swish_exact((hs + sHead[f]) + a.p.bb[f]);
+      if (a.bf_out) a.bf_out[(size_t)blockIdx.x * D + f] = hb;  // inference outputs: bf_property (uniform per workgroup)
+      part = hb * a.p.wo[f];
+    }
   }
   part = wave_sum(part);
   if (lane == 0) sRed[wave] = part;

@@ -95,6 +95,10 @@ struct scann_handle {
   std::vector<WeightSpec> specs;
   bool loaded = false;
   bool debug = false;
+  // scann_set_outputs: what later inference forwards also write -- bit k: local_attention_k's weights; out_flags: SCANN_OUT_AFTER_LC |
+  // SCANN_OUT_BF_PROPERTY.  Zero: the forward launches exactly the plain schedule
+  uint64_t out_layers = 0;
+  int32_t out_flags = 0;
   int tile_atoms = TQ;     // atoms per edge tile the tile builder allows (edge_kernel's query-row buffer)
   int n_cu = 256;      // compute units of the device
   int time_every = 0;  // > 0: sample edge-kernel launch durations on every n-th forward (scann_edge_timing)
@@ -227,6 +231,14 @@ struct scann_dbatch {
   int dbg_layers = -1;
   int last_slot = 0;
   bool owns_arena = true;  // false: the arena belongs to the handle's scratch (scann_forward)
+  // inference outputs of the last forward (scann_set_outputs, scann_output_read): one block of the device cache, allocated by the first
+  // forward that needs it, grown when a selection needs more, freed with the batch
+  char* out_block = nullptr;
+  size_t out_cap = 0;
+  float* out_attn = nullptr;  // [selected layers, in layer order][n_edge][num_head]
+  float *out_z = nullptr, *out_bf = nullptr;  // after_Lc [n_atom, global_dim], bf_property [n_struct, dense_out]
+  uint64_t out_layers = 0;  // what the last forward wrote (a training forward: nothing)
+  int32_t out_flags = 0;
 };
 
 namespace scann {
@@ -258,10 +270,14 @@ int check_range(scann_handle* h, const char* where, int slot = 0);
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // scann_forward.cpp: the forward graph as a launch schedule on one stream; exact: on the exact-fp32 instantiations
+// (an inference forward also writes the outputs the handle selected, scann_set_outputs)
 int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, bool exact = false);
 
 // scann_batch.cpp
 int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who);
+// after the batch's stream has been synchronised: the forward's range guard fired -> run it again on the exact-fp32 instantiations
+// (*rerun = true) unless SCANN_STRICT_RANGE asks for the error (check_range reports it)
+int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, bool* rerun);
 void free_batch(scann_dbatch* db);  // everything the batch holds, and the batch; no work on it may still be running
 
 }  // namespace scann

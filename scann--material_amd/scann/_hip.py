@@ -108,7 +108,12 @@ SYMBOLS = [
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("scann_batch_read_csr", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     ("scann_host_copy", C.c_int, [_P, _P, C.c_int64]),
+    ("scann_set_outputs", C.c_int, [_P, C.c_uint64, C.c_int32]),
+    ("scann_output_read", C.c_int64, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64]),
 ]
+
+# scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
+OUT_LOCAL_ATTENTION, OUT_AFTER_LC, OUT_BF_PROPERTY = 0, 1, 2
 
 _lib = None
 _pinned = False  # the process has pinned itself to its device's cores (Engine.__init__, multi-rank runs)
@@ -351,6 +356,34 @@ def slice_dataset(ds_mol_offset, ds_edge_offset, ds_atomic, ds_ring, ds_edge_loc
     return PackedBatch(o_atomic, o_mol, o_eoff, o_col, o_dist, o_wgt, ring=o_ring)
 
 
+def repad_local_attention(attn, atom_mask, neighbor_mask):
+    """Packed attention weights [n_edge, H] of one layer -> the reference's ``attn`` [B, H, M, N] (attention.py:189): edge e is slot
+    ``np.nonzero(neighbor_mask & atom_mask)[e]`` (packed edges are the unmasked slots of real atoms in (structure, atom, slot) order).
+    The padded slots hold what the reference's fp32 softmax gives them: 0 on a masked slot of an atom that has a real neighbour
+    (exp(-1e9 - max)), 1/N in every slot of a row without one -- a padded or an isolated atom -- whose logits all round to -1e9."""
+    amask = np.asarray(atom_mask).reshape(np.shape(neighbor_mask)[:2]) != 0
+    em = (np.asarray(neighbor_mask) != 0) & amask[:, :, None]
+    B, M, N = em.shape
+    attn = np.asarray(attn, dtype=np.float32)
+    H = attn.shape[1]
+    if attn.shape[0] != int(em.sum()):
+        raise ValueError("%d attention rows for %d real neighbour slots" % (attn.shape[0], int(em.sum())))
+    out = np.zeros((B, M, N, H), dtype=np.float32)
+    if N:
+        out[~em.any(-1)] = np.float32(1.0) / np.float32(N)
+    out[em] = attn
+    return np.ascontiguousarray(out.transpose(0, 3, 1, 2))
+
+
+def repad_atoms(x, atom_mask):
+    """Packed per-atom rows [n_atom, F] -> [B, M, F] with zero rows for padded atoms."""
+    amask = np.asarray(atom_mask)
+    amask = amask.reshape(amask.shape[:2]) != 0
+    out = np.zeros(amask.shape + (np.shape(x)[1],), dtype=np.float32)
+    out[amask] = x
+    return out
+
+
 def _mask_arg(m):
     """A mask of the Keras input dict as the C ABI takes it: (contiguous array, element size 1 | 4).  ONE truth rule on every path --
     NumPy's `m != 0` (what the reference's bool(...) / cast-to-float32 masks mean, datagenerator.py:123-133): bool / uint8 / int8 and
@@ -556,6 +589,31 @@ class Engine:
 
     def sync(self):
         self._check(self.lib.scann_sync(self._h))
+
+    def set_outputs(self, attn_layers=(), after_lc=False, bf_property=False):
+        """Select what later inference forwards also write (scann_set_outputs): the attention weights of LocalAttention layers
+        ``attn_layers``, after_Lc, bf_property.  ``set_outputs()`` selects nothing again."""
+        bits = 0
+        for k in attn_layers:
+            k = int(k)
+            if not 0 <= k < 64:
+                raise ValueError("local_attention layer %d out of range" % k)
+            bits |= 1 << k
+        flags = (OUT_AFTER_LC if after_lc else 0) | (OUT_BF_PROPERTY if bf_property else 0)
+        self._check(self.lib.scann_set_outputs(self._h, bits, flags))
+
+    def read_output(self, rb, what, layer=0):
+        """One output of the batch's last forward (scann_output_read): ``what`` = OUT_LOCAL_ATTENTION (``layer``) -> [n_edge, num_head],
+        OUT_AFTER_LC -> [n_atom, global_dim], OUT_BF_PROPERTY -> [n_struct, dense_out]."""
+        p = rb.packed
+        rows, cols = {OUT_LOCAL_ATTENTION: (p.n_edge, self.cfg.num_head), OUT_AFTER_LC: (p.n_atom, self.cfg.global_dim),
+                      OUT_BF_PROPERTY: (p.n_struct, self.cfg.dense_out)}[what]
+        out = np.empty((rows, cols), dtype=np.float32)
+        n = self.lib.scann_output_read(self._h, rb._h, int(what), int(layer), _ptr(out), out.size)
+        if n < 0:
+            self._check(int(n))
+        assert n == out.size, (n, out.shape)
+        return out
 
     def exact_reruns(self):
         """forwards this handle has re-run on the exact-fp32 kernels because an activation left the split-fp16 range"""

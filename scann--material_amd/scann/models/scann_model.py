@@ -90,11 +90,39 @@ def save_container(path, config, weights):
             os.unlink(tmp)
 
 
+OUTPUT_NAMES = ("predict_property", "global_attention", "after_Lc", "bf_property")  # + local_attention_<k>
+
+
+def _output_selection(names, n_attention):
+    """Validate a list of output names (the reference's Keras layer names): ``predict_property``, ``global_attention``,
+    ``local_attention_<k>`` (k < n_attention), ``after_Lc``, ``bf_property``.  -> (names, attention layers, after_Lc?, bf_property?);
+    ValueError before anything runs."""
+    if isinstance(names, str):
+        names = [names]
+    names = list(names)
+    layers = []
+    for n in names:
+        if not isinstance(n, str):
+            raise ValueError("output names are strings, got %r" % (n,))
+        if n.startswith("local_attention_"):
+            k = n[len("local_attention_"):]
+            if not k.isdigit() or str(int(k)) != k:
+                raise ValueError("unknown output %r" % n)
+            if int(k) >= n_attention:
+                raise ValueError("%s: the model has %d local-attention layers (local_attention_0 .. local_attention_%d)" % (
+                    n, n_attention, n_attention - 1))
+            layers.append(int(k))
+        elif n not in OUTPUT_NAMES:
+            raise ValueError("unknown output %r (known: %s, local_attention_<k>)" % (n, ", ".join(OUTPUT_NAMES)))
+    return names, sorted(set(layers)), "after_Lc" in names, "bf_property" in names
+
+
+
 class HipModel:
     """Stand-in for the ``tf.keras.Model`` that ``create_model`` returns (scann_model.py:449):
     ``predict`` runs the whole forward graph on the GPU."""
 
-    def __init__(self, config, weights=None, device=None, infer=False, seed=None):
+    def __init__(self, config, weights=None, device=None, infer=False, seed=None, outputs=None):
         self.config = normalize_config(config)
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0")) if os.environ.get("SCANN_DEVICE") is None \
@@ -103,6 +131,10 @@ class HipModel:
         self.infer = infer  # True: outputs [y, global_attention scores] (scann_model.py:81-83)
         self.input_names = list(INPUT_NAMES) + (["ring_aromatic"] if self.config["model"]["use_ring"] else [])
         self.output_names = ["predict_property"] + (["global_attention"] if infer else [])
+        self.outputs = None  # a list of output names: what predict returns when its call names none (load_model_infer(path, outputs))
+        if outputs is not None:
+            self.outputs = _output_selection(outputs, int(self.config["model"]["n_attention"]))[0]
+            self.output_names = list(self.outputs)
         self._weights = None
         self.set_weights(weights if weights is not None else keras_default_init(self.engine.weight_specs(), seed))
 
@@ -123,15 +155,26 @@ class HipModel:
         save_container(path, self.config, self._weights)
 
     # -- inference ---------------------------------------------------------------------------------
-    def predict(self, inputs, batch_size=None, verbose=0, **_):
+    def predict(self, inputs, batch_size=None, verbose=0, outputs=None, **_):
         """``model.predict(inputs)`` (scann_model.py:266,316): ``[B,1]`` or, in infer mode,
-        ``[[B,1], [B,M,1]]``."""
+        ``[[B,1], [B,M,1]]``.
+
+        ``outputs`` (a list of the reference's layer names; what a Keras sub-model of the graph would return): a list in that order.
+        ``predict_property`` [B,1] and ``global_attention`` [B,M,1] as above; ``local_attention_<k>`` -- layer k's attention weights
+        (attention.py:189) -- [B, num_head, M, N]; ``after_Lc`` [B, M, global_dim] (zero rows for padded atoms); ``bf_property``
+        [B, dense_out].  For a ``PackedBatch`` the per-edge / per-atom outputs stay packed: [n_edge, num_head], [n_atom, global_dim].
+        Unknown names and layers >= n_attention raise ValueError before anything runs."""
         m = self.config["model"]
+        if outputs is None and self.outputs is not None:
+            outputs = self.outputs
+        sel = None if outputs is None else _output_selection(outputs, int(m["n_attention"]))
         if not isinstance(inputs, _hip.PackedBatch):
             nb = np.shape(inputs["neighbors"])
             slots = int(nb[0]) * int(nb[1]) * max(1, int(nb[2]))  # padded neighbour slots >= edges; >= atoms
             if nb[0] >= self.BIG_PREDICT or (slots > self.BIG_SLOTS and nb[0] > 1):
-                return self._predict_chunked(inputs)
+                return self._predict_chunked(inputs, sel)
+        if sel is not None:
+            return self._predict_outputs(inputs, sel)
         if not isinstance(inputs, _hip.PackedBatch) and m["feature"] == "atomic" and not m["use_ring"]:
             y, ga = self.engine.forward_padded(inputs, want_ga=self.infer)  # native CSR packing
             return [y.reshape(-1, 1), ga] if self.infer else y.reshape(-1, 1)
@@ -148,7 +191,69 @@ class HipModel:
     PREDICT_CHUNK = 2048  # structures per chunk: one launch sequence each (16 batches of the reference's 128)
     BIG_SLOTS = 6_000_000  # ... or padded neighbour slots (a launch sequence takes < 8,388,608 atoms / edges: few but large crystals)
 
-    def _predict_chunked(self, inputs):
+    def _select(self, sel):
+        """scann_set_outputs for a selection made by _output_selection (None: nothing)"""
+        if sel is None:
+            self.engine.set_outputs()
+        else:
+            self.engine.set_outputs(sel[1], after_lc=sel[2], bf_property=sel[3])
+
+    def _read_outputs(self, rb, sel):
+        """the packed outputs of a downloaded batch: {name: array} for the names beyond y and the GlobalAttention scores"""
+        eng, out = self.engine, {}
+        for k in sel[1]:
+            out["local_attention_%d" % k] = eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, k)
+        if sel[2]:
+            out["after_Lc"] = eng.read_output(rb, _hip.OUT_AFTER_LC)
+        if sel[3]:
+            out["bf_property"] = eng.read_output(rb, _hip.OUT_BF_PROPERTY)
+        return out
+
+    def _assemble(self, sel, y, ga_pad, packed, atom_mask=None, neighbor_mask=None):
+        """the list predict(outputs=...) returns; atom_mask / neighbor_mask None: per-edge / per-atom outputs stay packed"""
+        res = []
+        for n in sel[0]:
+            if n == "predict_property":
+                res.append(y.reshape(-1, 1))
+            elif n == "global_attention":
+                res.append(ga_pad)
+            elif n.startswith("local_attention_"):
+                a = packed["local_attention_%d" % int(n[16:])]
+                res.append(a if atom_mask is None else _hip.repad_local_attention(a, atom_mask, neighbor_mask))
+            elif n == "after_Lc":
+                res.append(packed[n] if atom_mask is None else _hip.repad_atoms(packed[n], atom_mask))
+            else:
+                res.append(packed[n])
+        return res
+
+    def _predict_outputs(self, inputs, sel):
+        """one batch through the resident path with the selected outputs on (the handle's selection is cleared afterwards)"""
+        eng = self.engine
+        m = self.config["model"]
+        is_packed = isinstance(inputs, _hip.PackedBatch)
+        if is_packed:
+            rb = eng.upload(inputs)
+        elif m["feature"] == "atomic" and not m["use_ring"] and not eng.training:
+            rb = eng.upload_padded(inputs)  # native CSR packing on the device, as forward_padded does
+        else:
+            rb = eng.upload(_hip.pack_inputs(inputs))
+        try:
+            self._select(sel)
+            try:
+                eng.forward_resident(rb, 0)
+                y, ga = eng.download(rb, want_ga=True)
+                packed = self._read_outputs(rb, sel)
+            finally:
+                self._select(None)
+        except BaseException:
+            rb.free()
+            raise
+        rb.release()
+        if is_packed:
+            return self._assemble(sel, y, inputs.repad_ga(ga), packed)
+        return self._assemble(sel, y, rb.packed.repad_ga(ga), packed, inputs["atom_mask"], inputs["neighbor_mask"])
+
+    def _predict_chunked(self, inputs, sel=None):
         """`model.predict(x)` on a WHOLE padded dataset (what the reference's evaluate / predict scripts do with Keras, which batches
         internally: scann_model.py:266,316): rows are cut into chunks -- views, nothing is copied -- and software-pipelined on this
         thread: chunk k + 1 is packed and uploaded (host, native code) while the device runs chunk k (launches are asynchronous),
@@ -157,6 +262,8 @@ class HipModel:
         eng = self.engine
         B = len(inputs["atom_mask"])
         nb = np.shape(inputs["neighbors"])
+        want_ga = self.infer if sel is None else "global_attention" in sel[0]
+        outs = []  # per chunk: {name: packed array}
         # at least four chunks (the first chunk's packing is the only host work the device waits for), at most PREDICT_CHUNK
         # structures and BIG_SLOTS * 2 / 3 padded slots each
         C = min(self.PREDICT_CHUNK, max(512, -(-B // 4 // 128) * 128))
@@ -168,7 +275,9 @@ class HipModel:
         def fetch_oldest():
             rb, first = pending.pop(0)
             try:
-                y, ga = eng.download(rb, want_ga=self.infer)
+                y, ga = eng.download(rb, want_ga=want_ga)
+                if sel is not None:
+                    outs.append(self._read_outputs(rb, sel))
             except _hip.ScannHipError as e:
                 rb.free()
                 # (a device-packed chunk reports bad input only here, up to `window` chunks after it was uploaded: say WHICH chunk)
@@ -177,7 +286,7 @@ class HipModel:
                 rb.free()
                 raise
             ys.append(y)
-            if self.infer:
+            if want_ga:
                 gas.append(ga)
             rb.release()
 
@@ -185,6 +294,8 @@ class HipModel:
         m = self.config["model"]
         device_pack = m["feature"] == "atomic" and not m["use_ring"] and not eng.training
         k = 0
+        if sel is not None:
+            self._select(sel)
         try:
             for i in range(0, B, C):
                 chunk = {key: v[i:i + C] for key, v in inputs.items()}
@@ -201,15 +312,24 @@ class HipModel:
             while pending:
                 fetch_oldest()
         finally:
+            if sel is not None:
+                self._select(None)
             for rb, _ in pending:
                 rb.free()
         y = np.concatenate(ys).reshape(-1, 1)
-        if not self.infer:
+        if not want_ga and sel is None:
             return y
         amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
-        ga_pad = np.zeros(amask.shape, dtype=np.float32)  # softmax of -1e9 -> 0 on padded atoms
-        ga_pad[amask] = np.concatenate(gas)  # packed rows are the real atoms in (structure, atom) order
-        return [y, ga_pad[..., None]]
+        ga_pad = None
+        if want_ga:
+            ga_pad = np.zeros(amask.shape, dtype=np.float32)  # softmax of -1e9 -> 0 on padded atoms
+            ga_pad[amask] = np.concatenate(gas)  # packed rows are the real atoms in (structure, atom) order
+            ga_pad = ga_pad[..., None]
+        if sel is None:
+            return [y, ga_pad]
+        # chunks are consecutive structures: their packed outputs, concatenated, are the whole batch's packed outputs
+        packed = {n: np.concatenate([o[n] for o in outs]) for n in (outs[0] if outs else {})}
+        return self._assemble(sel, y, ga_pad, packed, amask, inputs["neighbor_mask"])
 
     @staticmethod
     def default_group(dataset):
@@ -218,11 +338,16 @@ class HipModel:
         bs = int(getattr(dataset, "batch_size", 0) or 0)
         return max(1, 1024 // bs) if bs > 0 else 8
 
-    def predict_dataset(self, dataset, group=None, want_ga=False):
+    def predict_dataset(self, dataset, group=None, want_ga=False, outputs=None):
         """Pipelined inference over a whole ``PackedDataset`` (or any sequence of ``(PackedBatch | inputs dict, target)``):
         batches are fused ``group`` at a time into one launch sequence, spread over the handle's streams, and fetched at
         the end -- the throughput path behind ``SCANN.evaluate`` / ``predict_model.py``.  Returns ``(y [N], ga list | None,
         targets [N])`` in dataset order.
+
+        ``outputs`` (names ``local_attention_<k>``, ``after_Lc``, ``bf_property``): a fourth element, ``{name: [one array per
+        structure]}`` in dataset order, each as ``predict(batch, outputs=...)`` returns it for that structure's own batch of the
+        dataset (fused groups are split back into batches): [num_head, M, N] / [M, global_dim] / [dense_out], M and N the
+        batch's largest structure and neighbour count.
 
         A software pipeline on the calling thread: group k + 1 is sliced and uploaded (native calls; the upload returns when its copy
         is enqueued) right after group k's launches are enqueued, a rolling window of 2 x streams groups stays in flight, results are
@@ -235,6 +360,13 @@ class HipModel:
         ns = eng.num_streams()
         pending, ys, gas, ts = [], [], [], []
         group = int(group) if group else self.default_group(dataset)
+        sel = None
+        if outputs is not None:
+            sel = _output_selection(outputs, int(self.config["model"]["n_attention"]))
+            if "predict_property" in sel[0] or "global_attention" in sel[0]:
+                raise ValueError("predict_dataset returns predict_property and global_attention as y and ga (want_ga=True)")
+        per_struct = {n: [] for n in sel[0]} if sel is not None else None
+        layout = []  # per group in flight: (PackedBatch, structures per dataset batch)
 
         def fetch_oldest():
             # a rolling window of `ns` groups in flight (one per stream): only the OLDEST is waited for, and its batch is released
@@ -242,6 +374,8 @@ class HipModel:
             rb = pending.pop(0)
             try:
                 y, ga = eng.download(rb, want_ga=want_ga)
+                if sel is not None:
+                    self._split_outputs(self._read_outputs(rb, sel), *layout.pop(0), per_struct)
             except BaseException:
                 rb.free()
                 raise
@@ -256,19 +390,27 @@ class HipModel:
         def make(g0):
             if grouped is not None:
                 pk, tgt = grouped(g0, min(n, g0 + group))
+                if sel is not None:  # (a dataset batch holds batch_size structures, the last one the rest)
+                    bs = int(dataset.batch_size)
+                    layout.append((pk, [min(bs, pk.n_struct - j) for j in range(0, pk.n_struct, bs)]))
                 return pk, [np.asarray(tgt, dtype=np.float32)]
             parts, tg = [], []
             for i in range(g0, min(n, g0 + group)):
                 item, tgt = dataset[i]
                 parts.append(item if isinstance(item, _hip.PackedBatch) else _hip.pack_inputs(item))
                 tg.append(np.asarray(tgt, dtype=np.float32))
-            return (_hip.concat_packed(parts) if len(parts) > 1 else parts[0]), tg
+            pk = _hip.concat_packed(parts) if len(parts) > 1 else parts[0]
+            if sel is not None:
+                layout.append((pk, [p.n_struct for p in parts]))
+            return pk, tg
 
         # One thread is enough, and faster: launches and uploads are asynchronous, so slicing + uploading group k + 1 right after
         # enqueueing group k overlaps host and device by itself; the producer thread of rounds 3-4 (below, SCANN_DATASET_THREAD=1)
         # cost more in Python thread hand-offs than it hid (bench.py end_to_end: 1.70-1.72 M -> 1.81 M molecules/s, one box).
-        if os.environ.get("SCANN_DATASET_THREAD", "0") != "1":
+        if os.environ.get("SCANN_DATASET_THREAD", "0") != "1" or sel is not None:
             k = 0
+            if sel is not None:
+                self._select(sel)
             try:
                 for g0 in range(0, n, group):
                     pk, tg = make(g0)
@@ -286,11 +428,15 @@ class HipModel:
                 while pending:
                     fetch_oldest()
             finally:
+                if sel is not None:
+                    self._select(None)
                 for rb in pending:
                     rb.free()
             if not ys:
-                return np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
-            return np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
+                res = np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
+            else:
+                res = np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
+            return res if sel is None else res + (per_struct,)
         ready = queue.Queue(maxsize=max(2, ns))  # uploaded groups waiting for their launches
         stop = threading.Event()
 
@@ -356,6 +502,35 @@ class HipModel:
             return np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
         return np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
 
+    def _split_outputs(self, packed, pk, counts, per_struct):
+        """Packed outputs of one fused group (PackedBatch ``pk``, ``counts`` structures per dataset batch) -> one array per structure,
+        appended to ``per_struct``: what the padded predict of that structure's own batch returns for it (each dataset batch is
+        repadded as a whole; its structures are views of that array)."""
+        mol = np.asarray(pk.mol_offset, dtype=np.int64)
+        eoff = np.asarray(pk.edge_offset, dtype=np.int64)
+        deg = np.diff(eoff)
+        s0 = 0
+        for cnt in counts:
+            a0, a1 = int(mol[s0]), int(mol[s0 + cnt])
+            sizes = np.diff(mol[s0:s0 + cnt + 1])
+            M = int(sizes.max()) if cnt else 0
+            N = int(deg[a0:a1].max()) if a1 > a0 else 0
+            st = np.repeat(np.arange(cnt), sizes)  # structure of each atom of the batch, and its slot in the structure
+            slot = np.arange(a1 - a0) - np.repeat(mol[s0:s0 + cnt] - a0, sizes)
+            amask = np.zeros((cnt, M), dtype=bool)
+            amask[st, slot] = True
+            em = np.zeros((cnt, M, N), dtype=bool)  # the batch's neighbour mask
+            em[st, slot] = np.arange(N)[None, :] < deg[a0:a1, None]
+            for name, arr in packed.items():
+                if name.startswith("local_attention_"):
+                    v = _hip.repad_local_attention(arr[eoff[a0]:eoff[a1]], amask, em)
+                elif name == "after_Lc":
+                    v = _hip.repad_atoms(arr[a0:a1], amask)
+                else:
+                    v = arr[s0:s0 + cnt]
+                per_struct[name].extend(list(v))
+            s0 += cnt
+
     def summary(self):
         print("SCANN HIP model: %d parameters, %d local-attention layers, g_update=%s" % (
             self.count_params(), self.config["model"]["n_attention"], self.config["model"]["g_update"]))
@@ -373,14 +548,14 @@ def _read_container(path, config=None):
     return cfg, {k: z[k] for k in z.files if k != "__config__"}
 
 
-def load_model(path, custom_objects=None, infer=False, config=None):
+def load_model(path, custom_objects=None, infer=False, config=None, outputs=None):
     """``tf.keras.models.load_model`` counterpart (scann_model.py:79,87,323): this package's weight container, or a Keras
     HDF5 checkpoint written by the reference (imported by ``keras_import``; pass the run's ``config`` for the keys the file
     does not determine)."""
     cfg, weights = _read_container(path, config)
     if config is not None:  # the caller's yaml wins for everything but the architecture (hyper.target selects the mrelu head)
         cfg["hyper"].update({k: v for k, v in config.get("hyper", {}).items() if k != "target" or "target" not in cfg["hyper"]})
-    return HipModel(cfg, weights, infer=infer)
+    return HipModel(cfg, weights, infer=infer, outputs=outputs)
 
 
 def create_model_pretrained(pretrained):
@@ -417,8 +592,11 @@ class SCANN:
             self.model = load_model(pretrained, infer=True, config=self.config)
 
     @classmethod
-    def load_model_infer(cls, path):
-        return load_model(path, infer=True)
+    def load_model_infer(cls, path, outputs=None):
+        """scann_model.py:86-91 builds a Keras sub-model that returns [prediction, GlobalAttention scores]; ``outputs`` (layer
+        names: predict_property, global_attention, local_attention_<k>, after_Lc, bf_property) builds the sub-model that returns
+        those, in that order."""
+        return load_model(path, infer=True, outputs=outputs)
 
     @classmethod
     def load_model(cls, path):
