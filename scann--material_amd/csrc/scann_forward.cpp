@@ -68,7 +68,11 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   if ((size_t)std::max(1, db->max_degree) * H * 4 * (kp ? 3 : 1) > 60000 || ((size_t)db->max_atoms * (kp ? 3 : 1) + dg + dout + 4) * 4 > 60000 ||
       (size_t)4 * 3 * d * 4 > 60000)
     return fail(h, SCANN_ERR_UNSUPPORTED, "forward (generic widths): an atom's neighbours x heads, or a structure's atoms, exceed one workgroup's LDS");
-  auto W = [&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
+  // the training forward also admits only what its backward can run (gen_backward's GlobalAttention pooling: 3 x atoms + 4 doubles of LDS),
+  // so that a step is refused here, before it has touched anything, and not halfway through
+  if (kp && ((size_t)3 * db->max_atoms + 4) * sizeof(double) > 65536)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "training forward (generic widths): a structure's atoms exceed one workgroup's LDS in the backward (GlobalAttention pooling: 3 x atoms doubles <= 64 KiB)");
+  auto W =[&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
   // workspace: atom rows, edge rows, Gaussian bases
   const size_t fA = (size_t)A, fE = (size_t)std::max(E, 1), fB = (size_t)B, Ls = (size_t)L;
   float* p = nullptr;

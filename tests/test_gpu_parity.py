@@ -800,15 +800,19 @@ def test_activation_outside_the_split_fp16_range_is_rerun_in_exact_fp32(hip_lib,
 
 @pytest.mark.parametrize("name,kind,n,over", [
     ("qm9", "qm9", 40, {}), ("qm9", "qm9", 12, dict(g_update=False)), ("qm9", "qm9", 12, dict(use_attn_norm=False)),
-    ("mp2018", "mp2018", 6, {}), ("qm9", "worst", 4, {}),
-], ids=["qm9", "base", "no_attn_norm", "mp2018", "worst"])
+    ("mp2018", "mp2018", 6, {}), ("qm9", "worst", 4, {}), ("qm9", "qm9", 260, {}),
+], ids=["qm9", "base", "no_attn_norm", "mp2018", "worst", "qm9_b260"])
 def test_exact_fp32_kernels_match_the_oracle(hip_lib, monkeypatch, name, kind, n, over):
     """SCANN_EXACT=1 runs every inference forward on the EX instantiations of the atom / edge kernels (exact-fp32 MFMA: the re-run
     path of a forward whose split-fp16 range guard fired), here on ordinary models: the oracle's numbers on every branch, 32- and
-    64-row tiles, and the fast path's to the split scheme's accuracy."""
+    64-row edge tiles (260 molecules: 35 k edges), and the fast path's to the split scheme's accuracy."""
+    from scann import _hip
     from scann.models.scann_model import HipModel
 
     cfg, w, inputs, fast = make(name, n=n, seed=9, kind=kind, model=dict(over))
+    rb = fast.engine.upload(_hip.pack_inputs(inputs))
+    assert fast.engine.batch_info(rb)["tile_rows"] == (64 if n == 260 else 32)
+    rb.free()
     y_fast, ga_fast = fast.predict(inputs)
     monkeypatch.setenv("SCANN_EXACT", "1")
     y, ga = HipModel(cfg, w, device=0, infer=True).predict(inputs)

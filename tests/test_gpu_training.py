@@ -28,12 +28,8 @@ def setup(n=6, L=2, seed=1, **model_over):
 GRAD_FLOOR, GRAD_SLACK, GRAD_CAP = 2e-5, 4.0, 2e-4
 
 
-def check_grads(got, cfg, w, pk, targets, attn_scale=None, cap=None, drop=None):
-    """Gradient parity rule.  Reference: fp64 autograd of the independent torch graph.  A single-precision step cannot be closer
-    to it than the SAME graph run by torch in fp32 is, so every tensor is held to max(GRAD_FLOOR, GRAD_SLACK x that fp32
-    error), and to GRAD_CAP overall.  (Measured, tests/manual/grad_floor.py: HIP errors 4e-7 ... 1.5e-5 of the tensor scale,
-    1 - 2.2 x the torch-fp32 floor; the 2e-3 bound of round 1 was three orders looser than the implementation needs.)
-    Returns (rmse of the fp64 graph, errors)."""
+def grad_reference(cfg, w, pk, targets, attn_scale=None, drop=None):
+    """(rmse of the fp64 graph, fp64 autograd gradients, the same graph's fp32 gradients), without the l2 term: check_grads' reference"""
     import torch_ref
 
     _, rmse, ref, _ = torch_ref.loss_and_grads(cfg, w, pk, targets, attn_scale=attn_scale, drop=drop)
@@ -42,6 +38,17 @@ def check_grads(got, cfg, w, pk, targets, attn_scale=None, cap=None, drop=None):
         if k.endswith(torch_ref.REGULARIZED):
             ref[k] = ref[k] - 2e-4 * w[k].astype(np.float64)
             g32[k] = g32[k] - 2e-4 * w[k].astype(np.float64)
+    return rmse, ref, g32
+
+
+def check_grads(got, cfg, w, pk, targets, attn_scale=None, cap=None, drop=None, refs=None):
+    """Gradient parity rule.  Reference: fp64 autograd of the independent torch graph.  A single-precision step cannot be closer
+    to it than the SAME graph run by torch in fp32 is, so every tensor is held to max(GRAD_FLOOR, GRAD_SLACK x that fp32
+    error), and to GRAD_CAP overall.  (Measured, tests/manual/grad_floor.py: HIP errors 4e-7 ... 1.5e-5 of the tensor scale,
+    1 - 2.2 x the torch-fp32 floor; the 2e-3 bound of round 1 was three orders looser than the implementation needs.)
+    refs: grad_reference(...) of the same arguments, computed once for several checks.
+    Returns (rmse of the fp64 graph, errors)."""
+    rmse, ref, g32 = refs if refs is not None else grad_reference(cfg, w, pk, targets, attn_scale=attn_scale, drop=drop)
     e_gpu, e_32 = grad_errors(got, ref), grad_errors(g32, ref)
     bad = {k: (e_gpu[k], e_32[k]) for k in ref if not e_gpu[k] <= min(cap or GRAD_CAP, max(GRAD_FLOOR, GRAD_SLACK * e_32[k]))}
     assert not bad, bad
