@@ -235,6 +235,14 @@ int scann_train_backward(scann_handle_t* h, scann_dbatch_t* db, double sse_globa
 /* model.use_drop (train.py --use_drop): Dropout(0.05) on the local-attention weights during training forwards
  * (attention.py:116,191); 0 disables.  Both branches (g_update on / off), MFMA and plain-fp32 kernels alike. */
 int scann_set_attention_dropout(scann_handle_t* h, float p);
+/* on != 0: deterministic training mode, from the next scann_train_backward / scann_train_step[_begin] on (it may be switched
+ * between steps).  The six small gradient reductions of the 128-wide backward that otherwise end in float atomics (readout bias,
+ * basis MLP, base-branch filter_geo, embedding table, dense_embed, ring / cgcnn embedding) store per-workgroup partial sums and
+ * add them in a fixed order over a partition that depends on the batch shape only: a step's gradients, and so its weights, are
+ * then bitwise the same on every run.  Their slots live in the batch's training workspace (allocated on the batch's first
+ * deterministic backward, freed with the batch).  Plain-fp32 handles (other widths) are deterministic already and ignore it, as do
+ * inference forwards.  Across ranks the gradient all-reduce keeps RCCL's order. */
+int scann_set_deterministic(scann_handle_t* h, int on);
 int scann_zero_grads(scann_handle_t* h);
 int scann_allreduce_grads(scann_handle_t* h);                 /* RCCL sum over the communicator; no-op without one */
 int scann_allreduce_sse(scann_handle_t* h, double* sse, int64_t* count); /* in-place sum over ranks */

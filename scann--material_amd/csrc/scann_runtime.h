@@ -69,12 +69,15 @@ struct scann_train_ws {  // per resident batch (scann_dbatch::train), allocated 
   float *rep = nullptr, *dpre = nullptr, *dy = nullptr, *targets = nullptr, *dlut = nullptr;
   float* wpart = nullptr;  // per-slab partial sums of every weight gradient of a step (WgradCtx::arena)
   size_t wpart_floats = 0;
+  float* det_part = nullptr;  // deterministic mode: the slots of the otherwise atomic reductions (first deterministic backward)
+  size_t det_floats = 0;
   double* sse = nullptr;
   float drop_p = 0.f, attn_p = 0.f;
   unsigned long long seed = 0;
   GenKeep gen;  // generic widths: the training forward's tensors and the backward's temporaries
   ~scann_train_ws() {  // freed with its batch (free_batch): the arenas go back to the block cache
     cached_free(arena);
+    cached_free(det_part);
     cached_free(gen.arena);
     cached_free(gen.barena);
   }
@@ -152,6 +155,7 @@ struct scann_handle {
   int64_t t_step = 0;
   float train_drop_p = 0.f;            // > 0 only inside scann_train_forward
   float attn_drop_p = 0.f;             // use_drop: Dropout(0.05) on attention weights (scann_set_attention_dropout)
+  bool deterministic = false;          // scann_set_deterministic: the backward's small reductions in a fixed order, no float atomics
   bool in_train_forward = false;
   unsigned long long train_seed = 0;
   ncclComm_t comm = nullptr;

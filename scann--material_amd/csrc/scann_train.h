@@ -14,7 +14,7 @@ struct ReadoutBwdArgs {
   const float *Wb, *bb, *wo;   // bf_property (row-major), predict_property
   float *dgq, *dgk;            // [n_atom,128] out
   float *rep_out, *dpre_out;   // [n_struct,128] out (inputs of the bf_property weight gradient)
-  float *dwo, *dbo;            // dwo: [n_struct,128] slots (reserve_vec); dbo: the scalar bias gradient (atomic)
+  float *dwo, *dbo;            // dwo: [n_struct,128] slots (reserve_vec); dbo: the scalar bias gradient (atomic; none when det)
 };
 
 // One region of the device weight arena, regenerated from the flat master parameters after each optimiser step.
@@ -128,16 +128,27 @@ void launch_attn_edge_bwd(WgradCtx& ctx, EdgeBwdArgs a, AttnPart b, int n_tile, 
 // (`done`: an event recorded by the kernel's own completion signal, for a side stream to wait on -- see launch_attn_edge_bwd)
 void launch_atom_gather3(const float* dang, const float* G, const float* dV, const int* edge_offset, const int* in_off, const int* in_edge,
                          float* dC, float* dP1, float* dP3, int n_atom, hipStream_t s, hipEvent_t done = nullptr);
-void launch_readout_bwd(const ReadoutBwdArgs& a, hipStream_t s);
+// Deterministic mode (scann_set_deterministic): the six small reductions that otherwise end in float atomics -- the readout's bias,
+// the basis MLP, the base branch's filter_geo, the species table, dense_embed and the general embedding -- store per-workgroup (per
+// species) partial sums into slots of `det->arena` instead, over a partition that is a function of the batch shape only, and each
+// launcher adds its slots to the destinations in slot order on its own stream (det_flush) before it returns.  det == null / false:
+// the atomic kernels, unchanged.  The readout's bias: launch_scalar_sum of d loss / d y.
+void launch_readout_bwd(const ReadoutBwdArgs& a, hipStream_t s, bool det = false);
 void launch_basis_bwd(const BasisParams& p, const float* dist, const float* weight, const float* dgeom, int n_edge, float* dWd,
-                      float* dbd, float* dWw, float* dbw, hipStream_t s);
+                      float* dbd, float* dWw, float* dbw, hipStream_t s, WgradCtx* det = nullptr);
 void launch_base_geom_bwd(const float* gd, const float* Wf, const float* bf, const float* wgt, const float* dgeomL, int n_edge,
-                          float* dWf, float* dbf, hipStream_t s);
+                          float* dWf, float* dbf, hipStream_t s, WgradCtx* det = nullptr);
 void launch_embed_bwd(const float* dc0, const int* atomic, int n_atom, const float* emb, const float* W, const float* b,
                       float* dlut, int n_species, int emb_dim, float* dEmb, float* dW, float* db, unsigned long long drop_seed,
-                      unsigned drop_tag, float drop_p, hipStream_t s);
+                      unsigned drop_tag, float drop_p, hipStream_t s, WgradCtx* det = nullptr);
 void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb, float* dWe, float* dbe, float* dWr, float* dbr,
-                              float* dWde, float* dbde, hipStream_t s);
+                              float* dWde, float* dbde, hipStream_t s, WgradCtx* det = nullptr, int n_species = 0);
+float* reserve_slots(WgradCtx& ctx, float* dst, int n_slot, int numel);  // records (dst, n_slot slots of numel floats)
+void det_flush(WgradCtx& ctx, hipStream_t s);                            // adds every recorded slot set in slot order
+void launch_scalar_sum(const float* x, int n, float* dst, hipStream_t s);  // *dst += x[0] + ... + x[n - 1], fixed order
+// floats of det slots one backward over this batch shape reserves at most
+size_t det_slot_floats(int n_atom, int n_edge, int n_layer, int n_species, int emb_dim, bool g_update, bool general, bool cgcnn,
+                       bool ring);
 void launch_sse(const float* y, const float* t, int n, double* out, float* t_dev, float* dy, double* host_stat, hipStream_t s);
 void launch_dy(const float* y, const float* t, int n, float scale, const double* stat, float* dy, hipStream_t s);
 void launch_adam(float* w, float* g, float* m, float* v, const float* l2mask, size_t n, float lr_hat, float b1, float b2,

@@ -1085,7 +1085,10 @@ void launch_attn_bwd(WgradCtx& ctx, const float* q, const float* K, const int* e
 // ---- readout backward: one workgroup per structure ------------------------------------------------------------------
 // forward (attention.py:279-316, scann_model.py:437-447): a_i = sum_{j!=i} gk_i.gq_j ; an = a/|a| ; at = softmax(an);
 // rep = sum_i at_i gk_i ; pre = rep.Wb + bb ; h = swish(pre) ; y = h.wo + bo (mrelu has an identity gradient).
-__global__ __launch_bounds__(128) void readout_bwd_kernel(ReadoutBwdArgs a) {
+// DET (deterministic mode, scann_set_deterministic): no bias atomic -- dbo = sum of dy over the structures, which
+// launch_scalar_sum adds in a fixed order
+template <bool DET>
+__device__ __forceinline__ void readout_bwd_body(const ReadoutBwdArgs& a) {
   extern __shared__ float sd[];  // [n] attn, [n] agg, [n] da
   __shared__ float sRep[D], sV[D], sS[D], sW[D], sRed[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1133,7 +1136,7 @@ __global__ __launch_bounds__(128) void readout_bwd_kernel(ReadoutBwdArgs a) {
   const float dh = dy * a.wo[tid];
   const float dpre = dh * dswish_(pre);
   a.dwo[(size_t)mol * D + tid] = dy * hj;  // this structure's slot (vec_reduce_kernel adds the slots in order)
-  if (tid == 0) atomicAdd(a.dbo, dy);
+  if (!DET && tid == 0) atomicAdd(a.dbo, dy);
   a.rep_out[(size_t)mol * D + tid] = rep;
   a.dpre_out[(size_t)mol * D + tid] = dpre;
   sV[tid] = dpre;
@@ -1220,9 +1223,12 @@ __global__ __launch_bounds__(128) void readout_bwd_kernel(ReadoutBwdArgs a) {
       }
   }
 }
-void launch_readout_bwd(const ReadoutBwdArgs& a, hipStream_t s) {
+__global__ __launch_bounds__(128) void readout_bwd_kernel(ReadoutBwdArgs a) { readout_bwd_body<false>(a); }
+__global__ __launch_bounds__(128) void readout_bwd_det_kernel(ReadoutBwdArgs a) { readout_bwd_body<true>(a); }
+void launch_readout_bwd(const ReadoutBwdArgs& a, hipStream_t s, bool det) {
   if (a.n_struct <= 0) return;
-  hipLaunchKernelGGL(readout_bwd_kernel, dim3(a.n_struct), dim3(128), (size_t)3 * a.max_atoms * sizeof(float), s, a);
+  hipLaunchKernelGGL(det ? readout_bwd_det_kernel : readout_bwd_kernel, dim3(a.n_struct), dim3(128),
+                     (size_t)3 * a.max_atoms * sizeof(float), s, a);
 }
 
 // ---- basis backward: geom0 = swish(gd.Wd + bd) * swish(gw.Ww + bw)  (scann_model.py:378-389) ---------------------------
@@ -1230,9 +1236,11 @@ __device__ __forceinline__ float gauss_(float x, float c) {
   const float d = x - c;
   return expf(-(d * d) / 0.25f);
 }
-__global__ __launch_bounds__(128) void basis_bwd_kernel(BasisParams p, const float* __restrict__ dist,
-                                                        const float* __restrict__ weight, const float* __restrict__ dgeom,
-                                                        int n_edge, int chunks, float* dWd, float* dbd, float* dWw, float* dbw) {
+// DET: the workgroup's sums go to slot blockIdx.x of each of the 2 NG + 2 gradient rows (row r's slots at part + r * gridDim.x * 128)
+template <bool DET>
+__device__ __forceinline__ void basis_bwd_body(const BasisParams& p, const float* __restrict__ dist, const float* __restrict__ weight,
+                                               const float* __restrict__ dgeom, int n_edge, int chunks, float* dWd, float* dbd,
+                                               float* dWw, float* dbw, float* part) {
   // `chunks` blocks of 32 edges per workgroup, gradients accumulated in registers: the 42 x 128 atomics at the end go to the
   // same addresses for every workgroup of the launch, so their number is what this kernel's time scales with
   __shared__ float sG[32][2 * NG];
@@ -1277,6 +1285,18 @@ __global__ __launch_bounds__(128) void basis_bwd_kernel(BasisParams p, const flo
     }
   }
   }
+  if (DET) {
+    const size_t rs = (size_t)gridDim.x * D;
+    float* q = part + (size_t)blockIdx.x * D + tid;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+      q[k * rs] = gdw[k];
+      q[(NG + k) * rs] = gww[k];
+    }
+    q[2 * NG * rs] = gbd;
+    q[(2 * NG + 1) * rs] = gbw;
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < NG; ++k) {
     atomicAdd(&dWd[k * D + tid], gdw[k]);
@@ -1285,21 +1305,47 @@ __global__ __launch_bounds__(128) void basis_bwd_kernel(BasisParams p, const flo
   atomicAdd(&dbd[tid], gbd);
   atomicAdd(&dbw[tid], gbw);
 }
+__global__ __launch_bounds__(128) void basis_bwd_kernel(BasisParams p, const float* __restrict__ dist,
+                                                        const float* __restrict__ weight, const float* __restrict__ dgeom,
+                                                        int n_edge, int chunks, float* dWd, float* dbd, float* dWw, float* dbw) {
+  basis_bwd_body<false>(p, dist, weight, dgeom, n_edge, chunks, dWd, dbd, dWw, dbw, nullptr);
+}
+__global__ __launch_bounds__(128) void basis_bwd_det_kernel(BasisParams p, const float* __restrict__ dist,
+                                                            const float* __restrict__ weight, const float* __restrict__ dgeom,
+                                                            int n_edge, int chunks, float* part) {
+  basis_bwd_body<true>(p, dist, weight, dgeom, n_edge, chunks, nullptr, nullptr, nullptr, nullptr, part);
+}
 void launch_basis_bwd(const BasisParams& p, const float* dist, const float* weight, const float* dgeom, int n_edge, float* dWd,
-                      float* dbd, float* dWw, float* dbw, hipStream_t s) {
+                      float* dbd, float* dWw, float* dbw, hipStream_t s, WgradCtx* det) {
   if (n_edge > 0)
   {
     const int chunks = n_edge >= (1 << 20) ? 4 : 1;  // the per-edge arithmetic, not the final atomics, bounds this kernel: 4 x fewer workgroups measured 105 vs 37 us at 18 k edges
-    hipLaunchKernelGGL(basis_bwd_kernel, dim3((n_edge + 32 * chunks - 1) / (32 * chunks)), dim3(128), 0, s, p, dist, weight, dgeom,
+    const int n_wg = (n_edge + 32 * chunks - 1) / (32 * chunks);
+    if (det) {  // the same partition (a function of n_edge only), one slot per workgroup and gradient row, summed in workgroup order
+      float* part = nullptr;
+      for (int k = 0; k < NG; ++k) {
+        float* q = reserve_vec(*det, dWd + k * D, n_wg);
+        if (k == 0) part = q;
+      }
+      for (int k = 0; k < NG; ++k) reserve_vec(*det, dWw + k * D, n_wg);
+      reserve_vec(*det, dbd, n_wg);
+      reserve_vec(*det, dbw, n_wg);
+      hipLaunchKernelGGL(basis_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, p, dist, weight, dgeom, n_edge, chunks, part);
+      det_flush(*det, s);
+      return;
+    }
+    hipLaunchKernelGGL(basis_bwd_kernel, dim3(n_wg), dim3(128), 0, s, p, dist, weight, dgeom,
                        n_edge, chunks, dWd, dbd, dWw, dbw);
   }
 }
 
 // ---- base SCANN branch: geomL = swish(gd.Wf + bf) * weight  (attention.py:155; gd = raw Gaussian basis [E,20]) -------------
 // backward: dpre = dgeomL * weight * swish'(pre); dWf[k][col] += gd[e][k] dpre; dbf[col] += dpre   (32 edges per workgroup)
-__global__ __launch_bounds__(128) void base_geom_bwd_kernel(const float* __restrict__ gd, const float* __restrict__ Wf,
-                                                            const float* __restrict__ bf, const float* __restrict__ wgt,
-                                                            const float* __restrict__ dgeomL, int n_edge, float* dWf, float* dbf) {
+// DET: slot blockIdx.x of each of the NG + 1 gradient rows (row r's slots at part + r * gridDim.x * 128)
+template <bool DET>
+__device__ __forceinline__ void base_geom_bwd_body(const float* __restrict__ gd, const float* __restrict__ Wf,
+                                                   const float* __restrict__ bf, const float* __restrict__ wgt,
+                                                   const float* __restrict__ dgeomL, int n_edge, float* dWf, float* dbf, float* part) {
   __shared__ float sG[32][NG];
   const int tid = threadIdx.x;
   const int e0 = blockIdx.x * 32;
@@ -1323,14 +1369,41 @@ __global__ __launch_bounds__(128) void base_geom_bwd_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < NG; ++k) gw[k] += sG[e][k] * dp;
   }
+  if (DET) {
+    const size_t rs = (size_t)gridDim.x * D;
+    float* q = part + (size_t)blockIdx.x * D + tid;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) q[k * rs] = gw[k];
+    q[NG * rs] = gb;
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < NG; ++k) atomicAdd(&dWf[k * D + tid], gw[k]);
   atomicAdd(&dbf[tid], gb);
 }
+__global__ __launch_bounds__(128) void base_geom_bwd_kernel(const float* __restrict__ gd, const float* __restrict__ Wf,
+                                                            const float* __restrict__ bf, const float* __restrict__ wgt,
+                                                            const float* __restrict__ dgeomL, int n_edge, float* dWf, float* dbf) {
+  base_geom_bwd_body<false>(gd, Wf, bf, wgt, dgeomL, n_edge, dWf, dbf, nullptr);
+}
+__global__ __launch_bounds__(128) void base_geom_bwd_det_kernel(const float* __restrict__ gd, const float* __restrict__ Wf,
+                                                                const float* __restrict__ bf, const float* __restrict__ wgt,
+                                                                const float* __restrict__ dgeomL, int n_edge, float* part) {
+  base_geom_bwd_body<true>(gd, Wf, bf, wgt, dgeomL, n_edge, nullptr, nullptr, part);
+}
 void launch_base_geom_bwd(const float* gd, const float* Wf, const float* bf, const float* wgt, const float* dgeomL, int n_edge,
-                          float* dWf, float* dbf, hipStream_t s) {
-  if (n_edge > 0)
-    hipLaunchKernelGGL(base_geom_bwd_kernel, dim3((n_edge + 31) / 32), dim3(128), 0, s, gd, Wf, bf, wgt, dgeomL, n_edge, dWf, dbf);
+                          float* dWf, float* dbf, hipStream_t s, WgradCtx* det) {
+  if (n_edge <= 0) return;
+  const int n_wg = (n_edge + 31) / 32;
+  if (det) {
+    float* part = reserve_vec(*det, dWf, n_wg);
+    for (int k = 1; k < NG; ++k) reserve_vec(*det, dWf + k * D, n_wg);
+    reserve_vec(*det, dbf, n_wg);
+    hipLaunchKernelGGL(base_geom_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, gd, Wf, bf, wgt, dgeomL, n_edge, part);
+    det_flush(*det, s);
+    return;
+  }
+  hipLaunchKernelGGL(base_geom_bwd_kernel, dim3(n_wg), dim3(128), 0, s, gd, Wf, bf, wgt, dgeomL, n_edge, dWf, dbf);
 }
 
 // ---- embedding backward (Embedding + dense_embed, scann_model.py:362,373) -------------------------------------------------
@@ -1338,9 +1411,11 @@ void launch_base_geom_bwd(const float* gd, const float* Wf, const float* bf, con
 // One workgroup (128 threads = columns) per run of `run` atoms, with a private [n_species][128] table in LDS (thread `col` is
 // the only writer of column `col`): the global table has only n_species x 128 addresses and every atomic on them is serialised
 // behind all the others of the launch, so each workgroup adds its totals once.
-__global__ __launch_bounds__(128) void embed_scatter_kernel(const float* __restrict__ dc0, const int* __restrict__ atomic,
-                                                            float* __restrict__ dlut, int n_atom, int run, int n_species,
-                                                            unsigned long long drop_seed, unsigned drop_tag, float drop_p) {
+// DET: the private table is stored whole to slot blockIdx.x (dlut points at the slots, n_species x 128 floats each)
+template <bool DET>
+__device__ __forceinline__ void embed_scatter_body(const float* __restrict__ dc0, const int* __restrict__ atomic,
+                                                   float* __restrict__ dlut, int n_atom, int run, int n_species,
+                                                   unsigned long long drop_seed, unsigned drop_tag, float drop_p) {
   extern __shared__ float sTab[];  // [n_species][D]
   const int col = threadIdx.x, a0 = blockIdx.x * run, a1 = min(n_atom, a0 + run);
   for (int sp = 0; sp < n_species; ++sp) sTab[sp * D + col] = 0.f;
@@ -1362,14 +1437,32 @@ __global__ __launch_bounds__(128) void embed_scatter_kernel(const float* __restr
         sTab[z[u] * D + col] += drop_p > 0.f ? v[u] * drop_scale(drop_seed, drop_tag, i, drop_p) : v[u];
       }
   }
+  if (DET) {
+    float* q = dlut + (size_t)blockIdx.x * n_species * D;
+    for (int sp = 0; sp < n_species; ++sp) q[sp * D + col] = sTab[sp * D + col];
+    return;
+  }
   for (int sp = 0; sp < n_species; ++sp) {
     const float v = sTab[sp * D + col];
     if (v != 0.f) atomicAdd(&dlut[(size_t)sp * D + col], v);
   }
 }
-__global__ __launch_bounds__(128) void embed_bwd_kernel(const float* __restrict__ emb, const float* __restrict__ W,
-                                                        const float* __restrict__ b, float* __restrict__ dlut,
-                                                        int n_species, int emb_dim, float* dEmb, float* dW, float* db) {
+__global__ __launch_bounds__(128) void embed_scatter_kernel(const float* __restrict__ dc0, const int* __restrict__ atomic,
+                                                            float* __restrict__ dlut, int n_atom, int run, int n_species,
+                                                            unsigned long long drop_seed, unsigned drop_tag, float drop_p) {
+  embed_scatter_body<false>(dc0, atomic, dlut, n_atom, run, n_species, drop_seed, drop_tag, drop_p);
+}
+__global__ __launch_bounds__(128) void embed_scatter_det_kernel(const float* __restrict__ dc0, const int* __restrict__ atomic,
+                                                                float* __restrict__ part, int n_atom, int run, int n_species,
+                                                                unsigned long long drop_seed, unsigned drop_tag, float drop_p) {
+  embed_scatter_body<true>(dc0, atomic, part, n_atom, run, n_species, drop_seed, drop_tag, drop_p);
+}
+// DET: species sp's dense_embed kernel / bias terms go to slot sp of part (emb_dim x 128 floats per slot, then n_species slots of
+// 128 for the bias), absent species store zeros
+template <bool DET>
+__device__ __forceinline__ void embed_bwd_body(const float* __restrict__ emb, const float* __restrict__ W, const float* __restrict__ b,
+                                               float* __restrict__ dlut, int n_species, int emb_dim, float* dEmb, float* dW, float* db,
+                                               float* part) {
   // one workgroup per species; thread = output column
   extern __shared__ float sdp[];  // [128] dpre
   const int sp = blockIdx.x, col = threadIdx.x;
@@ -1377,7 +1470,15 @@ __global__ __launch_bounds__(128) void embed_bwd_kernel(const float* __restrict_
   dlut[sp * D + col] = 0.f;  // consumed: the table is zero again for the next step's embed_scatter_kernel (no memset per step)
   // a species absent from the batch has a zero row: nothing to add anywhere (QM9: 5 of the table's species occur; their workgroups'
   // atomics on the shared dW / db addresses were queueing behind ~20 x as many adds of zero)
-  if (!__syncthreads_or(dl != 0.f)) return;
+  float* const pW = DET ? part + (size_t)sp * emb_dim * D + col : nullptr;
+  float* const pB = DET ? part + (size_t)n_species * emb_dim * D + (size_t)sp * D + col : nullptr;
+  if (!__syncthreads_or(dl != 0.f)) {
+    if (DET) {
+      *pB = 0.f;
+      for (int k = 0; k < emb_dim; ++k) pW[(size_t)k * D] = 0.f;
+    }
+    return;
+  }
   float pre = b[col];
   for (int k0 = 0; k0 < emb_dim; k0 += 16) {  // the same sum in the same order, operands requested sixteen at a time
     float e[16], w[16];
@@ -1393,7 +1494,10 @@ __global__ __launch_bounds__(128) void embed_bwd_kernel(const float* __restrict_
   }
   const float dpre = dl * dswish_(pre);
   sdp[col] = dpre;
-  if (dpre != 0.f) {
+  if (DET) {
+    *pB = dpre;
+    for (int k = 0; k < emb_dim; ++k) pW[(size_t)k * D] = emb[sp * emb_dim + k] * dpre;
+  } else if (dpre != 0.f) {
     atomicAdd(&db[col], dpre);
     for (int k = 0; k < emb_dim; ++k) atomicAdd(&dW[k * D + col], emb[sp * emb_dim + k] * dpre);
   }
@@ -1415,12 +1519,37 @@ __global__ __launch_bounds__(128) void embed_bwd_kernel(const float* __restrict_
     dEmb[sp * emb_dim + k] += acc;  // accumulate; each species row is touched by exactly one workgroup
   }
 }
+__global__ __launch_bounds__(128) void embed_bwd_kernel(const float* __restrict__ emb, const float* __restrict__ W,
+                                                        const float* __restrict__ b, float* __restrict__ dlut,
+                                                        int n_species, int emb_dim, float* dEmb, float* dW, float* db) {
+  embed_bwd_body<false>(emb, W, b, dlut, n_species, emb_dim, dEmb, dW, db, nullptr);
+}
+__global__ __launch_bounds__(128) void embed_bwd_det_kernel(const float* __restrict__ emb, const float* __restrict__ W,
+                                                            const float* __restrict__ b, float* __restrict__ dlut,
+                                                            int n_species, int emb_dim, float* dEmb, float* part) {
+  embed_bwd_body<true>(emb, W, b, dlut, n_species, emb_dim, dEmb, nullptr, nullptr, part);
+}
 void launch_embed_bwd(const float* dc0, const int* atomic, int n_atom, const float* emb, const float* W, const float* b,
                       float* dlut, int n_species, int emb_dim, float* dEmb, float* dW, float* db, unsigned long long drop_seed,
-                      unsigned drop_tag, float drop_p, hipStream_t s) {
+                      unsigned drop_tag, float drop_p, hipStream_t s, WgradCtx* det) {
   if (n_atom <= 0) return;
   const int run = std::max(32, (n_atom + 127) / 128);  // <= 128 workgroups
-  hipLaunchKernelGGL(embed_scatter_kernel, dim3((n_atom + run - 1) / run), dim3(128), (size_t)n_species * D * sizeof(float), s, dc0,
+  const int n_wg = (n_atom + run - 1) / run;
+  if (det) {
+    // the species table: one slot per workgroup of the same partition (a function of n_atom), added into dlut in workgroup order
+    // before the per-species launch reads it; then that launch's kernel / bias terms, one slot per species, in species order
+    float* tab = reserve_slots(*det, dlut, n_wg, n_species * D);
+    hipLaunchKernelGGL(embed_scatter_det_kernel, dim3(n_wg), dim3(128), (size_t)n_species * D * sizeof(float), s, dc0, atomic, tab,
+                       n_atom, run, n_species, drop_seed, drop_tag, drop_p);
+    det_flush(*det, s);
+    float* part = reserve_slots(*det, dW, n_species, emb_dim * D);
+    reserve_vec(*det, db, n_species);
+    hipLaunchKernelGGL(embed_bwd_det_kernel, dim3(n_species), dim3(128), D * sizeof(float), s, emb, W, b, dlut, n_species, emb_dim,
+                       dEmb, part);
+    det_flush(*det, s);
+    return;
+  }
+  hipLaunchKernelGGL(embed_scatter_kernel, dim3(n_wg), dim3(128), (size_t)n_species * D * sizeof(float), s, dc0,
                      atomic, dlut, n_atom, run, n_species, drop_seed, drop_tag, drop_p);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(n_species), dim3(128), D * sizeof(float), s, emb, W, b, dlut, n_species, emb_dim,
                      dEmb, dW, db);
@@ -1497,10 +1626,208 @@ __global__ __launch_bounds__(128) void embed_general_bwd_kernel(EmbedArgs a, con
     }
   }
 }
+// Deterministic-mode sibling: a run of `run` atoms (a multiple of 8) per workgroup, taken eight at a time through the same per-atom
+// arithmetic.  Every gradient is summed on chip in atom order into the workgroup's own slot -- each element has one owning thread
+// (dense_embed: thread = column; the cin-wide ones: thread = k, k + 128), so plain loads and stores suffice -- and det_flush adds the
+// slots in workgroup order.  Slot regions (n_wg slots each): dbde [128]; dWde row k [128] (k < cin); atomic: dEmb [n_species * emb];
+// cgcnn: dbe [emb], dWe [92 * emb]; ring: dbr [10], dWr [20].
+struct EmbedDetSlots {
+  float *bde, *Wde, *emb, *be, *We, *br, *Wr;
+  int32_t run, n_species;
+};
+__global__ __launch_bounds__(128) void embed_general_bwd_det_kernel(EmbedArgs a, const float* __restrict__ dc0, EmbedDetSlots o) {
+  __shared__ float sV[8][160], sDp[8][D], sDv[8][160];
+  const int tid = threadIdx.x, b = blockIdx.x, n_wg = gridDim.x;
+  const int cin = a.emb_dim + (a.ring ? 10 : 0);
+  const int r0 = b * o.run, r1 = min(a.n_atom, r0 + o.run);
+  const size_t sWde = (size_t)n_wg * D;
+  float* const pWde = o.Wde + (size_t)b * D + tid;  // + k * sWde: row k
+  float* const pEmb = a.cgcnn ? nullptr : o.emb + (size_t)b * o.n_species * a.emb_dim;
+  float* const pWe = a.cgcnn ? o.We + (size_t)b * 92 * a.emb_dim : nullptr;
+  for (int k = 0; k < cin; ++k) pWde[k * sWde] = 0.f;
+  for (int k = tid; k < a.emb_dim; k += 128) {
+    if (a.cgcnn)
+      for (int j = 0; j < 92; ++j) pWe[j * a.emb_dim + k] = 0.f;
+    else
+      for (int sp = 0; sp < o.n_species; ++sp) pEmb[sp * a.emb_dim + k] = 0.f;
+  }
+  float gb = 0.f;                                 // dbde[tid]
+  float gk[2] = {0.f, 0.f}, gr0[2] = {0.f, 0.f}, gr1[2] = {0.f, 0.f};  // per owned k = tid, tid + 128: dbe[k] or dbr[r], dWr[r], dWr[10 + r]
+  for (int a0 = r0; a0 < r1; a0 += 8) {
+    const int na = min(8, r1 - a0);
+    __syncthreads();  // the previous group's sV / sDp / sDv are consumed
+    for (int i = tid; i < na * cin; i += 128) {
+      const int la = i / cin, k = i % cin, at = a0 + la;
+      float v;
+      if (k < a.emb_dim) {
+        if (a.cgcnn) {
+          float acc = 0.f;
+          for (int j = 0; j < 92; ++j) acc += a.cgcnn[(size_t)at * 92 + j] * a.We[j * a.emb_dim + k];
+          v = acc + a.be[k];
+        } else {
+          v = a.emb[(size_t)a.atomic[at] * a.emb_dim + k];
+        }
+      } else {
+        const int r = k - a.emb_dim;
+        v = (a.ring[(size_t)at * 2] * a.Wr[r] + a.ring[(size_t)at * 2 + 1] * a.Wr[10 + r]) + a.br[r];
+      }
+      sV[la][k] = v;
+    }
+    __syncthreads();
+    for (int la = 0; la < na; ++la) {  // thread = output column
+      float pre = a.bde[tid];
+      for (int k = 0; k < cin; ++k) pre += sV[la][k] * a.Wde[k * D + tid];
+      const float dp = dc0[(size_t)(a0 + la) * D + tid] * dswish_(pre);
+      sDp[la][tid] = dp;
+      gb += dp;
+    }
+    __syncthreads();
+    for (int k = 0; k < cin; ++k) {  // dWde[k][col] += sum_la v[la][k] dpre[la][col]
+      float g = 0.f;
+      for (int la = 0; la < na; ++la) g += sV[la][k] * sDp[la][tid];
+      pWde[k * sWde] += g;
+    }
+    for (int i = tid; i < na * cin; i += 128) {  // dv[la][k] = sum_col dpre[la][col] Wde[k][col]
+      const int la = i / cin, k = i % cin;
+      float acc = 0.f;
+      for (int c = 0; c < D; ++c) acc += sDp[la][c] * a.Wde[k * D + c];
+      sDv[la][k] = acc;
+    }
+    __syncthreads();
+    for (int u = 0; u < 2; ++u) {
+      const int k = tid + 128 * u;
+      if (k >= cin) break;
+      for (int la = 0; la < na; ++la) {
+        const int at = a0 + la;
+        const float dv = sDv[la][k];
+        if (k < a.emb_dim) {
+          gk[u] += dv;
+          if (a.cgcnn) {
+            for (int j = 0; j < 92; ++j) pWe[j * a.emb_dim + k] += a.cgcnn[(size_t)at * 92 + j] * dv;
+          } else {
+            pEmb[(size_t)a.atomic[at] * a.emb_dim + k] += dv;
+          }
+        } else {
+          gk[u] += dv;
+          gr0[u] += a.ring[(size_t)at * 2] * dv;
+          gr1[u] += a.ring[(size_t)at * 2 + 1] * dv;
+        }
+      }
+    }
+  }
+  o.bde[(size_t)b * D + tid] = gb;
+  for (int u = 0; u < 2; ++u) {
+    const int k = tid + 128 * u;
+    if (k >= cin) break;
+    if (k < a.emb_dim) {
+      if (a.cgcnn) o.be[(size_t)b * a.emb_dim + k] = gk[u];
+    } else {
+      const int r = k - a.emb_dim;
+      o.br[(size_t)b * 10 + r] = gk[u];
+      o.Wr[(size_t)b * 20 + r] = gr0[u];
+      o.Wr[(size_t)b * 20 + 10 + r] = gr1[u];
+    }
+  }
+}
+int embed_general_det_run(int n_atom) { return std::max(32, ((n_atom + 127) / 128 + 7) / 8 * 8); }  // <= 128 workgroups
 void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb, float* dWe, float* dbe, float* dWr, float* dbr,
-                              float* dWde, float* dbde, hipStream_t s) {
-  if (a.n_atom > 0)
-    hipLaunchKernelGGL(embed_general_bwd_kernel, dim3((a.n_atom + 7) / 8), dim3(128), 0, s, a, dc0, dEmb, dWe, dbe, dWr, dbr, dWde, dbde);
+                              float* dWde, float* dbde, hipStream_t s, WgradCtx* det, int n_species) {
+  if (a.n_atom <= 0) return;
+  if (det) {
+    const int run = embed_general_det_run(a.n_atom), n_wg = (a.n_atom + run - 1) / run;
+    const int cin = a.emb_dim + (a.ring ? 10 : 0);
+    EmbedDetSlots o{};
+    o.run = run;
+    o.n_species = n_species;
+    o.bde = reserve_vec(*det, dbde, n_wg);
+    for (int k = 0; k < cin; ++k) {
+      float* q = reserve_vec(*det, dWde + (size_t)k * D, n_wg);
+      if (k == 0) o.Wde = q;
+    }
+    if (a.cgcnn) {
+      o.be = reserve_slots(*det, dbe, n_wg, a.emb_dim);
+      o.We = reserve_slots(*det, dWe, n_wg, 92 * a.emb_dim);
+    } else {
+      o.emb = reserve_slots(*det, dEmb, n_wg, n_species * a.emb_dim);
+    }
+    if (a.ring) {
+      o.br = reserve_slots(*det, dbr, n_wg, 10);
+      o.Wr = reserve_slots(*det, dWr, n_wg, 20);
+    }
+    hipLaunchKernelGGL(embed_general_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, a, dc0, o);
+    det_flush(*det, s);
+    return;
+  }
+  hipLaunchKernelGGL(embed_general_bwd_kernel, dim3((a.n_atom + 7) / 8), dim3(128), 0, s, a, dc0, dEmb, dWe, dbe, dWr, dbr, dWde, dbde);
+}
+
+// ---- deterministic mode: slot records and their fixed-order sums --------------------------------------------------------------
+float* reserve_slots(WgradCtx& ctx, float* dst, int n_slot, int numel) {
+  float* part = ctx.arena + ctx.off;
+  ctx.entries.push_back(WgradReduceEntry{dst, part, n_slot, numel});
+  ctx.off += (size_t)n_slot * numel;
+  return part;
+}
+void det_flush(WgradCtx& ctx, hipStream_t s) {
+  // 128-wide rows: vec_reduce_kernel (eight groups of slots per column, group sums in group order); other sizes: wgrad_reduce_kernel
+  // (a thread per element, the slots in order) -- the same sums as wgrad_flush's, with the grid sized to the largest record
+  std::vector<WgradReduceEntry> mats, vecs;
+  for (const WgradReduceEntry& e : ctx.entries)
+    if (e.n_slab > 0 && e.numel > 0) (e.numel == D ? vecs : mats).push_back(e);
+  ctx.entries.clear();
+  for (size_t e0 = 0; e0 < vecs.size(); e0 += WGRAD_REDUCE_MAX) {
+    const int n = (int)std::min<size_t>(WGRAD_REDUCE_MAX, vecs.size() - e0);
+    WgradReduceSet set{};
+    for (int k = 0; k < n; ++k) set.e[k] = vecs[e0 + k];
+    hipLaunchKernelGGL(vec_reduce_kernel, dim3(n), dim3(1024), 0, s, set);
+  }
+  for (size_t e0 = 0; e0 < mats.size(); e0 += WGRAD_REDUCE_MAX) {
+    const int n = (int)std::min<size_t>(WGRAD_REDUCE_MAX, mats.size() - e0);
+    WgradReduceSet set{};
+    int numel = 0;
+    for (int k = 0; k < n; ++k) {
+      set.e[k] = mats[e0 + k];
+      numel = std::max(numel, set.e[k].numel);
+    }
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((numel + 255) / 256, n), dim3(256), 0, s, set);
+  }
+}
+// dst += x[0] + x[1] + ... + x[n - 1] in a fixed association: thread t sums x[t], x[t + 256], ... in order, then the 256 sums are
+// added pairwise in LDS (the predict_property bias gradient = the sum of d loss / d y over the structures)
+__global__ __launch_bounds__(256) void scalar_sum_kernel(const float* __restrict__ x, int n, float* dst) {
+  __shared__ float sr[256];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += x[i];
+  sr[threadIdx.x] = acc;
+  for (int w = 128; w > 0; w >>= 1) {
+    __syncthreads();
+    if (threadIdx.x < w) sr[threadIdx.x] += sr[threadIdx.x + w];
+  }
+  if (threadIdx.x == 0) *dst += sr[0];
+}
+void launch_scalar_sum(const float* x, int n, float* dst, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(scalar_sum_kernel, dim3(1), dim3(256), 0, s, x, n, dst);
+}
+size_t det_slot_floats(int n_atom, int n_edge, int n_layer, int n_species, int emb_dim, bool g_update, bool general, bool cgcnn,
+                       bool ring) {
+  // upper bound of what one backward's det launches reserve (bump allocated, never reused within the step)
+  size_t f = 0;
+  if (n_edge > 0) {
+    const int chunks = n_edge >= (1 << 20) ? 4 : 1;
+    if (g_update) f += (size_t)(2 * NG + 2) * D * ((n_edge + 32 * chunks - 1) / (32 * chunks));
+    else f += (size_t)n_layer * (NG + 1) * D * ((n_edge + 31) / 32);
+  }
+  if (n_atom > 0) {
+    if (general) {
+      const int run = embed_general_det_run(n_atom), n_wg = (n_atom + run - 1) / run;
+      const int cin = emb_dim + (ring ? 10 : 0);
+      f += (size_t)n_wg * ((size_t)(1 + cin) * D + (cgcnn ? (size_t)93 * emb_dim : (size_t)n_species * emb_dim) + (ring ? 30 : 0));
+    } else {
+      const int run = std::max(32, (n_atom + 127) / 128), n_wg = (n_atom + run - 1) / run;
+      f += (size_t)n_wg * n_species * D + (size_t)n_species * (emb_dim + 1) * D;
+    }
+  }
+  return f;
 }
 
 // ---- loss ------------------------------------------------------------------------------------------------------------------

@@ -383,6 +383,27 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   };
   WgradCtx wg;
   wg.arena = w.wpart;
+  // deterministic mode: slots of the six reductions that otherwise end in float atomics (scann_train.h), allocated with the batch's
+  // workspace on the first such backward and sized from the batch shape alone
+  WgradCtx dct;
+  WgradCtx* const det = h->deterministic ? &dct : nullptr;
+  if (det) {
+    const bool general = c.use_ring || c.feature_cgcnn;
+    const size_t need = det_slot_floats(A, E, L, c.n_atoms, c.embedding_dim, c.g_update, general, c.feature_cgcnn, c.use_ring);
+    if (need > w.det_floats) {
+      // (the slots of a previous step on this batch may still be read by its reductions: the stream order of the main stream
+      //  alone does not cover the side streams, so wait for the device before the block goes back to the cache)
+      if (w.det_part) {
+        HIPCHK(h, hipDeviceSynchronize());
+        cached_free(w.det_part);
+        w.det_part = nullptr;
+        w.det_floats = 0;
+      }
+      HIPCHK(h, cached_malloc((void**)&w.det_part, need * 4));
+      w.det_floats = need;
+    }
+    dct.arena = w.det_part;
+  }
   // a fork costs the main stream ~7 us (tools/fork_probe.hip): the layers' gradient launches may share one (their operand sets live
   // to the end of the step)
   const int fork_every = 1;  // (2 / 3 / 4 / 7 layers per fork measured slower: profiles/r04_notes.md)
@@ -411,7 +432,7 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   // (one slot per structure, summed in structure order with the layer's other vectors: 128 workgroups adding to the same 128
   // addresses was a queue of 16 k atomics)
   ra.dwo = reserve_vec(wg, g("predict_property/kernel"), B); ra.dbo = g("predict_property/bias");
-  launch_readout_bwd(ra, s);
+  launch_readout_bwd(ra, s, det != nullptr);
   // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z = t1,
   // dgq = t2, dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no fork of their own,
   // each of which costs the main stream ~7 us (tools/fork_probe.hip)
@@ -460,7 +481,7 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
       bs = h->train_aux2;
     }
     launch_basis_bwd(h->basis, db->dist, db->weight, dG, E, g("neighbor_d/kernel"), g("neighbor_d/bias"),
-                     g("neighbor_w/kernel"), g("neighbor_w/bias"), bs);
+                     g("neighbor_w/kernel"), g("neighbor_w/bias"), bs, det);
     if (bs != s) {
       ev_basis = h->train_ev[ev_i++ % h->train_ev.size()];
       (void)hipEventRecord(ev_basis, bs);
@@ -535,7 +556,7 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
       hipStream_t ws = fork();
       wgrad_launch(wg, ws);
       flush_side(ws, wg, l == 0);
-      launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws);
+      launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws, det);
       pend.n = 1;  // dC += dq.Wq^T: folded into the next rn_bwd_kernel (or launched by flush_pend)
       pend.X[0] = dQ; pend.Wh[0] = pt.WqTh; pend.W[0] = pt.WqT;
       continue;
@@ -603,6 +624,8 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   // the longest thing between here and the optimiser -- started behind the embedding chain it ended 30 us after it)
   if (dG_in && !basis_done) basis_leaf(dG_in, nullptr);
   flush_pend();
+  // deterministic mode: the readout's bias gradient = the sum of d loss / d y, in structure order, beside the embedding chain
+  if (det) launch_scalar_sum(w.dy, B, g("predict_property/bias"), tail_s);
   if (c.use_ring || c.feature_cgcnn) {
     launch_dropout(dC, nA, w.seed, DROP_TAG_EMBED, w.drop_p, tail_s);
     EmbedArgs e = h->embed;
@@ -612,12 +635,14 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
     launch_embed_general_bwd(e, dC, c.feature_cgcnn ? nullptr : g("embed_atom/embeddings"),
                              c.feature_cgcnn ? g("embed_atom/kernel") : nullptr, c.feature_cgcnn ? g("embed_atom/bias") : nullptr,
                              c.use_ring ? g("extra_embed/kernel") : nullptr, c.use_ring ? g("extra_embed/bias") : nullptr,
-                             g("dense_embed/kernel"), g("dense_embed/bias"), tail_s);
+                             g("dense_embed/kernel"), g("dense_embed/bias"), tail_s, det, c.n_atoms);
   } else {
     launch_embed_bwd(dC, db->atomic, A, h->d_weights + h->o_emb, h->d_weights + h->o_Wde, h->d_weights + h->o_bde, w.dlut,
                      c.n_atoms, c.embedding_dim, g("embed_atom/embeddings"), g("dense_embed/kernel"), g("dense_embed/bias"), w.seed,
-                     DROP_TAG_EMBED, w.drop_p, tail_s);
+                     DROP_TAG_EMBED, w.drop_p, tail_s, det);
   }
+  if (det && dct.off > w.det_floats)
+    return fail(h, SCANN_ERR_HIP, "scann_train_backward: deterministic partial arena overrun");
   if (wg.off > w.wpart_floats)
     return fail(h, SCANN_ERR_HIP, "scann_train_backward: weight-gradient partial arena overrun");
   if (!wg.jobs.empty()) wgrad_launch(wg, s);  // a model without LocalAttention layers: the readout's gradients were never launched
@@ -752,6 +777,12 @@ int scann_train_begin(scann_handle_t* h) {
 int scann_set_attention_dropout(scann_handle_t* h, float p) {
   if (!h || !(p >= 0.f && p < 1.f)) return fail(h, SCANN_ERR_INVALID, "scann_set_attention_dropout: rate must be in [0, 1)");
   h->attn_drop_p = p;
+  return SCANN_OK;
+}
+
+int scann_set_deterministic(scann_handle_t* h, int on) {
+  if (!h) return SCANN_ERR_INVALID;
+  h->deterministic = on != 0;  // read by each backward as it is enqueued (plain-fp32 handles: every sum is fixed-order already)
   return SCANN_OK;
 }
 

@@ -82,6 +82,7 @@ SYMBOLS = [
     ("scann_train_forward", C.c_int, [_P, _P, _P, C.c_float, C.c_uint64, C.POINTER(C.c_double)]),
     ("scann_train_backward", C.c_int, [_P, _P, C.c_double, C.c_int64]),
     ("scann_set_attention_dropout", C.c_int, [_P, C.c_float]),
+    ("scann_set_deterministic", C.c_int, [_P, C.c_int]),
     ("scann_zero_grads", C.c_int, [_P]),
     ("scann_allreduce_grads", C.c_int, [_P]),
     ("scann_allreduce_sse", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -666,6 +667,11 @@ class Engine:
 
     def set_attention_dropout(self, p):
         self._check(self.lib.scann_set_attention_dropout(self._h, float(p)))
+
+    def set_deterministic(self, on):
+        """Deterministic training mode (scann_set_deterministic): later backward passes sum every gradient in a fixed order, so
+        a training step is bit-reproducible; off restores the default reductions.  Takes effect from the next backward."""
+        self._check(self.lib.scann_set_deterministic(self._h, int(bool(on))))
 
     def zero_grads(self):
         self._check(self.lib.scann_zero_grads(self._h))

@@ -20,7 +20,8 @@ INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_we
 # keys some shipped yaml files omit (model_qm9_std.yaml / model_ptgp.yaml; train.py:37-43 injects the CLI ones)
 _MODEL_DEFAULTS = dict(feature="atomic", use_ring=False, use_drop=False, g_update=False, gaussian_d=4.0,
                        use_attn_norm=True, use_ga_norm=True)
-_HYPER_DEFAULTS = dict(scaler=False, scheduler="cosine", use_ref=False, target="", pretrained="")
+# deterministic (extension, train.py --deterministic): bit-reproducible training steps and initial weights drawn from hyper.seed
+_HYPER_DEFAULTS = dict(scaler=False, scheduler="cosine", use_ref=False, target="", pretrained="", deterministic=False)
 
 
 def normalize_config(config):
@@ -122,7 +123,7 @@ class HipModel:
     """Stand-in for the ``tf.keras.Model`` that ``create_model`` returns (scann_model.py:449):
     ``predict`` runs the whole forward graph on the GPU."""
 
-    def __init__(self, config, weights=None, device=None, infer=False, seed=None, outputs=None):
+    def __init__(self, config, weights=None, device=None, infer=False, seed=None, outputs=None, deterministic=None):
         self.config = normalize_config(config)
         if device is None:
             device = int(os.environ.get("LOCAL_RANK", "0")) if os.environ.get("SCANN_DEVICE") is None \
@@ -137,6 +138,10 @@ class HipModel:
             self.output_names = list(self.outputs)
         self._weights = None
         self.set_weights(weights if weights is not None else keras_default_init(self.engine.weight_specs(), seed))
+        # deterministic training mode (scann_set_deterministic): every gradient of a step summed in a fixed order
+        self.deterministic = bool(self.config["hyper"]["deterministic"] if deterministic is None else deterministic)
+        if self.deterministic:
+            self.engine.set_deterministic(True)
 
     # -- weights ---------------------------------------------------------------------------------
     def set_weights(self, weights):
@@ -586,6 +591,9 @@ class SCANN:
                 print("load pretrained model from ", pretrained, "\n")
                 self.model = create_model_pretrained(pretrained)
                 self.config["hyper"]["pretrained"] = pretrained
+            elif self.config["hyper"]["deterministic"]:
+                # reproducible run: the initial weights come from hyper.seed as well, not from fresh OS entropy
+                self.model = create_model(self.config, seed=int(self.config["hyper"].get("seed", 0)))
             else:
                 self.model = create_model(self.config)
         else:

@@ -4,7 +4,8 @@
 kept because downstream scripts grep them.
 
 Extensions: ``--epochs`` (the reference hard-codes 1000, train.py:53), ``--packed`` (flat-CSR ``PackedDataset`` iterators instead
-of the nested-list ``DataIterator``), ``--gpus N`` (test-set prediction spread over N devices), ``--seed``.
+of the nested-list ``DataIterator``), ``--gpus N`` (test-set prediction spread over N devices), ``--seed``, ``--deterministic``
+(bit-reproducible training: fixed-order gradient sums on the GPU and initial weights drawn from ``--seed``).
 
 Data-parallel training is one process per GPU: ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 train.py ...`` or ``scann.parallel.spawn_ranks(["train.py", ...], N)``; every rank runs this file, rank 0 reports."""
@@ -37,11 +38,13 @@ FLAGS = (
     ("feature", str, "atomic", "atom input: 'atomic' (embedding of Z) or 'cgcnn' (92-d element descriptors)"),
     ("pretrained", str, "", "checkpoint to start from / to evaluate (container or the reference's Keras .h5)"),
     ("mode", str, "train", "'train' (train, then evaluate the best checkpoint) or anything else (evaluate only)"),
+    ("deterministic", bool, False, "bit-reproducible training: fixed-order gradient sums, initial weights drawn from --seed"),
 )
 
 
 def seed_everything(seed):
-    """Python / NumPy generators (dataset split and shuffling, weight initialisation of the package draw from NumPy)."""
+    """Python / NumPy global generators: the dataset split and the shuffling draw from them.  The initial weights do not (they
+    come from a generator of their own); with --deterministic they are drawn from the same seed (hyper.seed)."""
     random.seed(seed)
     np.random.seed(seed)
     os.environ["PYTHONHASHSEED"] = str(seed)
@@ -53,6 +56,9 @@ def configured(args):
         config[section][key] = getattr(args, flag)
     if args.gpus:
         config["hyper"]["gpus"] = args.gpus
+    if args.deterministic:
+        config["hyper"]["deterministic"] = True
+        config["hyper"]["seed"] = args.seed
     return config
 
 
