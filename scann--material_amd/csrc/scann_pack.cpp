@@ -23,6 +23,37 @@ int pack_fail(const char* msg) {
   t_pack_error = msg;
   return SCANN_ERR_INVALID;
 }
+
+// fn(t) for t in [0, n): t = 0 on the calling thread, the others on threads of their own, all joined before the return.  A thread that
+// cannot be started leaves its range, and every later one, to the calling thread: no exception reaches the C ABI.
+template <class Fn>
+void fan_out(int n, Fn&& fn) {
+  std::vector<std::thread> th;
+  int t = 1;
+  try {
+    th.reserve((size_t)std::max(0, n - 1));
+    for (; t < n; ++t) th.emplace_back(fn, t);
+  } catch (const std::exception&) {
+  }
+  fn(0);
+  for (int u = t; u < n; ++u) fn(u);
+  for (std::thread& x : th) x.join();
+}
+
+// Threads of a packer pass over B structures: one below 2,048 (below ~1,000 structures per thread the threads' start-up costs what they
+// save: measured at 256 per thread), else min(cores, 8, B / 1024) or SCANN_PACK_THREADS (read on every call), at most B.
+int pack_threads(int32_t B) {
+  if (B < 2048) return 1;
+  const unsigned hw = std::thread::hardware_concurrency();
+  int n = (int)std::min<int64_t>(std::min<unsigned>(hw ? hw : 1u, 8u), B / 1024);
+  if (const char* e = getenv("SCANN_PACK_THREADS")) n = std::max(1, std::min(64, atoi(e)));
+  return std::max(1, std::min<int>(n, B));
+}
+
+// structures [b0, b1) of range t of n
+std::pair<int32_t, int32_t> pack_range(int32_t B, int t, int n) {
+  return {(int32_t)((int64_t)B * t / n), (int32_t)((int64_t)B * (t + 1) / n)};
+}
 }  // namespace
 
 namespace scann {
@@ -136,27 +167,12 @@ int scann_pack_padded(int32_t B, int32_t M, int32_t N, const int32_t* atomic, co
   // are turned into each range's first atom row / first edge, and the ranges are filled (pass 2) -- by one thread for a batch, by up
   // to 8 for the reference's `model.predict(whole padded dataset)` (130 k structures: 100 ms -> 15-20 ms of host time).  The output
   // does not depend on the number of threads.
-  const int64_t BM = (int64_t)B * M;
-  int n_thr = 1;
-  if (B >= 2048) {  // (below ~1,000 structures per thread the threads' start-up costs what they save: measured at 256 per thread)
-    const unsigned hw = std::thread::hardware_concurrency();
-    n_thr = (int)std::min<int64_t>(std::min<unsigned>(hw ? hw : 1u, 8u), B / 1024);
-    if (const char* e = getenv("SCANN_PACK_THREADS")) n_thr = std::max(1, std::min(64, atoi(e)));
-    n_thr = std::max(1, std::min<int>(n_thr, B));
-  }
+  const int n_thr = pack_threads(B);
   std::vector<int64_t> cnt_a((size_t)n_thr + 1, 0), cnt_e((size_t)n_thr + 1, 0);
   std::vector<const char*> err((size_t)n_thr, nullptr);
-  auto range = [&](int t) { return std::make_pair((int32_t)((int64_t)B * t / n_thr), (int32_t)((int64_t)B * (t + 1) / n_thr)); };
-  auto run = [&](auto&& fn) {
-    if (n_thr == 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 1; t < n_thr; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (std::thread& x : th) x.join();
-  };
   // pass 1: counts per range
-  run([&](int t) {
-    const auto [b0, b1] = range(t);
+  fan_out(n_thr, [&](int t) {
+    const auto [b0, b1] = pack_range(B, t, n_thr);
     int64_t na_t = 0, ne_t = 0;
     for (int32_t b = b0; b < b1; ++b) {
       const uint8_t* am = atom_mask + (int64_t)b * M;
@@ -181,13 +197,12 @@ int scann_pack_padded(int32_t B, int32_t M, int32_t N, const int32_t* atomic, co
   const int64_t na = cnt_a[n_thr], ne = cnt_e[n_thr];
   if (na > INT32_MAX) return pack_fail("batch too large for int32 atom rows");
   if (ne > INT32_MAX) return pack_fail("batch too large for int32 edge rows");
-  (void)BM;
   // pass 2: packed row of every real atom (the job of gather_shape, custom_layers.py:18-28, moved to the host), then the unmasked
   // neighbour slots of real atoms, in slot order
   out_mol_offset[0] = 0;
   out_edge_offset[0] = 0;
-  run([&](int t) {
-    const auto [b0, b1] = range(t);
+  fan_out(n_thr, [&](int t) {
+    const auto [b0, b1] = pack_range(B, t, n_thr);
     int64_t row = cnt_a[t], e = cnt_e[t];
     for (int32_t b = b0; b < b1; ++b) {
       const uint8_t* am = atom_mask + (int64_t)b * M;
@@ -243,13 +258,10 @@ int scann_host_copy(void* dst, const void* src, int64_t bytes_) {
   size_t n_thr = std::min<size_t>(std::min<unsigned>(hw ? hw : 1u, 8u), bytes >> 22);  // >= 4 MiB per thread
   if (const char* e = getenv("SCANN_COPY_THREADS")) n_thr = (size_t)std::max(1, std::min(64, atoi(e)));  // (tests: threads on a small block)
   if (n_thr <= 1 || bytes < 64 * n_thr) { memcpy(dst, src, bytes); return SCANN_OK; }
-  std::vector<std::thread> th;
-  for (size_t t = 1; t < n_thr; ++t) {
-    const size_t o0 = (bytes * t / n_thr) & ~(size_t)63, o1 = t + 1 == n_thr ? bytes : (bytes * (t + 1) / n_thr) & ~(size_t)63;
-    th.emplace_back([=] { memcpy(static_cast<char*>(dst) + o0, static_cast<const char*>(src) + o0, o1 - o0); });
-  }
-  memcpy(dst, src, (bytes / n_thr) & ~(size_t)63);
-  for (std::thread& x : th) x.join();
+  fan_out((int)n_thr, [&](int t) {
+    const size_t o0 = (bytes * t / n_thr) & ~(size_t)63, o1 = t + 1 == (int)n_thr ? bytes : (bytes * (t + 1) / n_thr) & ~(size_t)63;
+    memcpy(static_cast<char*>(dst) + o0, static_cast<const char*>(src) + o0, o1 - o0);
+  });
   return SCANN_OK;
 }
 
@@ -260,23 +272,9 @@ int scann_count_padded(int32_t B, int32_t M, int32_t N, const void* atom_mask, i
     return pack_fail("scann_count_padded: null argument or negative shape");
   if ((atom_mask_size != 1 && atom_mask_size != 4) || (neighbor_mask_size != 1 && neighbor_mask_size != 4))
     return pack_fail("scann_count_padded: masks must have 1-byte or 4-byte elements");
-  int n_thr = 1;
-  if (B >= 2048) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    n_thr = (int)std::min<int64_t>(std::min<unsigned>(hw ? hw : 1u, 8u), B / 1024);
-    if (const char* e = getenv("SCANN_PACK_THREADS")) n_thr = std::max(1, std::min(64, atoi(e)));
-    n_thr = std::max(1, std::min<int>(n_thr, B));
-  }
+  const int n_thr = pack_threads(B);
   std::vector<int64_t> cnt_a((size_t)n_thr + 1, 0), cnt_e((size_t)n_thr + 1, 0);
   std::vector<const char*> err((size_t)n_thr, nullptr);
-  auto range = [&](int t) { return std::make_pair((int32_t)((int64_t)B * t / n_thr), (int32_t)((int64_t)B * (t + 1) / n_thr)); };
-  auto run = [&](auto&& fn) {
-    if (n_thr == 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 1; t < n_thr; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (std::thread& x : th) x.join();
-  };
   // degree of every padded atom slot (0 for a padded atom), kept in out_row_of until the second pass turns it into the row
   auto degree = [&](int64_t bm) {
     int32_t d = 0;
@@ -289,8 +287,8 @@ int scann_count_padded(int32_t B, int32_t M, int32_t N, const void* atom_mask, i
     }
     return d;
   };
-  run([&](int t) {
-    const auto [b0, b1] = range(t);
+  fan_out(n_thr, [&](int t) {
+    const auto [b0, b1] = pack_range(B, t, n_thr);
     int64_t na_t = 0, ne_t = 0;
     for (int32_t b = b0; b < b1; ++b) {
       int64_t here = 0;
@@ -317,8 +315,8 @@ int scann_count_padded(int32_t B, int32_t M, int32_t N, const void* atom_mask, i
   if (cnt_e[n_thr] > INT32_MAX) return pack_fail("batch too large for int32 edge rows");
   out_mol_offset[0] = 0;
   out_edge_offset[0] = 0;
-  run([&](int t) {
-    const auto [b0, b1] = range(t);
+  fan_out(n_thr, [&](int t) {
+    const auto [b0, b1] = pack_range(B, t, n_thr);
     int64_t row = cnt_a[t], e = cnt_e[t];
     for (int32_t b = b0; b < b1; ++b) {
       for (int32_t a = 0; a < M; ++a) {

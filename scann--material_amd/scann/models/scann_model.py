@@ -7,6 +7,7 @@ pretrained, mode)``, ``.model.predict(inputs)``, ``.prepare_dataset``, ``.evalua
 """
 from __future__ import annotations
 
+import functools
 import io
 import json
 import os
@@ -203,6 +204,52 @@ class HipModel:
         else:
             self.engine.set_outputs(sel[1], after_lc=sel[2], bf_property=sel[3])
 
+    def _pipeline(self, jobs, finish, sel=None):
+        """The software pipeline behind every batched inference path, on the calling thread.  ``jobs`` yields ``(upload, tag)``;
+        ``upload()`` -> ResidentBatch.  Job k + 1 is taken (sliced / packed) and uploaded right after job k's launches are enqueued:
+        launches and uploads are asynchronous, so this order alone overlaps host and device.  Up to 2 x streams batches stay in
+        flight, batch k on stream k % streams; ``finish(rb, tag)`` collects the OLDEST (download, outputs), in job order, and the
+        batch is then released without a device-wide synchronisation, so the device keeps running the younger ones.  ``sel``: the
+        output selection, set before the first launch and cleared on every exit.  On any error every batch uploaded and not yet
+        released is freed, once, and the error propagates.  (A producer thread for slicing + upload, rounds 3-4, cost more in
+        Python thread hand-offs than it hid: bench.py end_to_end 1.70-1.72 M -> 1.81 M molecules/s without it.)"""
+        eng = self.engine
+        ns = eng.num_streams()
+        pending = []  # (batch, tag) in flight, oldest first
+        rb = None  # uploaded, not yet in flight
+
+        def fetch_oldest():
+            finish(*pending[0])
+            pending.pop(0)[0].release()
+
+        try:
+            if sel is not None:
+                self._select(sel)
+            for k, (upload, tag) in enumerate(jobs):
+                rb = upload()
+                if len(pending) >= 2 * ns:
+                    fetch_oldest()
+                eng.forward_resident(rb, k % ns)
+                pending.append((rb, tag))
+                rb = None
+            while pending:
+                fetch_oldest()
+        finally:
+            if rb is not None:
+                rb.free()
+            for b, _ in pending:
+                b.free()
+            if sel is not None:
+                self._select(None)
+
+    def _upload_padded(self, inputs):
+        """A padded input dict (or row views of one) -> resident batch: feature = "atomic" without ring on an inference handle is
+        packed to CSR on the DEVICE (the host reads its masks only, as forward_padded does), anything else by the native host packer."""
+        m, eng = self.config["model"], self.engine
+        if m["feature"] == "atomic" and not m["use_ring"] and not eng.training:
+            return eng.upload_padded(inputs)
+        return eng.upload(_hip.pack_inputs(inputs))
+
     def _read_outputs(self, rb, sel):
         """the packed outputs of a downloaded batch: {name: array} for the names beyond y and the GlobalAttention scores"""
         eng, out = self.engine, {}
@@ -232,31 +279,19 @@ class HipModel:
         return res
 
     def _predict_outputs(self, inputs, sel):
-        """one batch through the resident path with the selected outputs on (the handle's selection is cleared afterwards)"""
-        eng = self.engine
-        m = self.config["model"]
+        """one batch through the resident pipeline with the selected outputs on (the handle's selection is cleared afterwards)"""
+        eng, got = self.engine, []
         is_packed = isinstance(inputs, _hip.PackedBatch)
+
+        def finish(rb, _):
+            y, ga = eng.download(rb, want_ga=True)
+            got.extend((y, rb.packed.repad_ga(ga), self._read_outputs(rb, sel)))
+
+        upload = functools.partial(eng.upload if is_packed else self._upload_padded, inputs)
+        self._pipeline([(upload, None)], finish, sel)
         if is_packed:
-            rb = eng.upload(inputs)
-        elif m["feature"] == "atomic" and not m["use_ring"] and not eng.training:
-            rb = eng.upload_padded(inputs)  # native CSR packing on the device, as forward_padded does
-        else:
-            rb = eng.upload(_hip.pack_inputs(inputs))
-        try:
-            self._select(sel)
-            try:
-                eng.forward_resident(rb, 0)
-                y, ga = eng.download(rb, want_ga=True)
-                packed = self._read_outputs(rb, sel)
-            finally:
-                self._select(None)
-        except BaseException:
-            rb.free()
-            raise
-        rb.release()
-        if is_packed:
-            return self._assemble(sel, y, inputs.repad_ga(ga), packed)
-        return self._assemble(sel, y, rb.packed.repad_ga(ga), packed, inputs["atom_mask"], inputs["neighbor_mask"])
+            return self._assemble(sel, *got)
+        return self._assemble(sel, *got, inputs["atom_mask"], inputs["neighbor_mask"])
 
     def _predict_chunked(self, inputs, sel=None):
         """`model.predict(x)` on a WHOLE padded dataset (what the reference's evaluate / predict scripts do with Keras, which batches
@@ -273,54 +308,23 @@ class HipModel:
         # structures and BIG_SLOTS * 2 / 3 padded slots each
         C = min(self.PREDICT_CHUNK, max(512, -(-B // 4 // 128) * 128))
         C = max(1, min(C, (self.BIG_SLOTS * 2 // 3) // max(1, int(nb[1]) * max(1, int(nb[2])))))
-        ns = eng.num_streams()
-        window = 2 * ns
-        pending, ys, gas = [], [], []
+        ys, gas = [], []
 
-        def fetch_oldest():
-            rb, first = pending.pop(0)
+        def finish(rb, first):
             try:
                 y, ga = eng.download(rb, want_ga=want_ga)
                 if sel is not None:
                     outs.append(self._read_outputs(rb, sel))
             except _hip.ScannHipError as e:
-                rb.free()
-                # (a device-packed chunk reports bad input only here, up to `window` chunks after it was uploaded: say WHICH chunk)
+                # (a device-packed chunk reports bad input only here, up to a window of chunks after it was uploaded: say WHICH chunk)
                 raise _hip.ScannHipError(e.code, "%s [structures %d..%d of this call]" % (e.detail, first, min(first + C, B) - 1)) from e
-            except BaseException:
-                rb.free()
-                raise
             ys.append(y)
             if want_ga:
                 gas.append(ga)
-            rb.release()
 
-        # feature = "atomic" without ring: the chunk is packed to CSR on the DEVICE (the host reads its masks only); else the native host packer
-        m = self.config["model"]
-        device_pack = m["feature"] == "atomic" and not m["use_ring"] and not eng.training
-        k = 0
-        if sel is not None:
-            self._select(sel)
-        try:
-            for i in range(0, B, C):
-                chunk = {key: v[i:i + C] for key, v in inputs.items()}
-                rb = eng.upload_padded(chunk) if device_pack else eng.upload(_hip.pack_inputs(chunk))
-                try:
-                    if len(pending) >= window:
-                        fetch_oldest()
-                    eng.forward_resident(rb, k % ns)
-                except BaseException:
-                    rb.free()
-                    raise
-                k += 1
-                pending.append((rb, i))
-            while pending:
-                fetch_oldest()
-        finally:
-            if sel is not None:
-                self._select(None)
-            for rb, _ in pending:
-                rb.free()
+        # one job per chunk of rows (views), tagged with its first structure
+        self._pipeline(((functools.partial(self._upload_padded, {key: v[i:i + C] for key, v in inputs.items()}), i)
+                        for i in range(0, B, C)), finish, sel)
         y = np.concatenate(ys).reshape(-1, 1)
         if not want_ga and sel is None:
             return y
@@ -354,16 +358,10 @@ class HipModel:
         dataset (fused groups are split back into batches): [num_head, M, N] / [M, global_dim] / [dense_out], M and N the
         batch's largest structure and neighbour count.
 
-        A software pipeline on the calling thread: group k + 1 is sliced and uploaded (native calls; the upload returns when its copy
-        is enqueued) right after group k's launches are enqueued, a rolling window of 2 x streams groups stays in flight, results are
-        fetched oldest first.  (Rounds 3-4 used a producer thread for slicing + upload; it is still there behind
-        SCANN_DATASET_THREAD=1.)"""
-        import queue
-        import threading
-
+        One group is one job of ``_pipeline``: group k + 1 is sliced and uploaded on the calling thread right after group k's
+        launches are enqueued, a rolling window of 2 x streams groups stays in flight, results are fetched oldest first."""
         eng = self.engine
-        ns = eng.num_streams()
-        pending, ys, gas, ts = [], [], [], []
+        ys, gas, ts = [], [], []
         group = int(group) if group else self.default_group(dataset)
         sel = None
         if outputs is not None:
@@ -371,141 +369,43 @@ class HipModel:
             if "predict_property" in sel[0] or "global_attention" in sel[0]:
                 raise ValueError("predict_dataset returns predict_property and global_attention as y and ga (want_ga=True)")
         per_struct = {n: [] for n in sel[0]} if sel is not None else None
-        layout = []  # per group in flight: (PackedBatch, structures per dataset batch)
-
-        def fetch_oldest():
-            # a rolling window of `ns` groups in flight (one per stream): only the OLDEST is waited for, and its batch is released
-            # without a device-wide synchronisation, so the device keeps running the younger groups
-            rb = pending.pop(0)
-            try:
-                y, ga = eng.download(rb, want_ga=want_ga)
-                if sel is not None:
-                    self._split_outputs(self._read_outputs(rb, sel), *layout.pop(0), per_struct)
-            except BaseException:
-                rb.free()
-                raise
-            ys.append(y)
-            if want_ga:
-                gas.append(ga)
-            rb.release()
-
         n = len(dataset)
         grouped = getattr(dataset, "batches", None)  # PackedDataset: a whole group with one native slice call
 
-        def make(g0):
-            if grouped is not None:
-                pk, tgt = grouped(g0, min(n, g0 + group))
-                if sel is not None:  # (a dataset batch holds batch_size structures, the last one the rest)
-                    bs = int(dataset.batch_size)
-                    layout.append((pk, [min(bs, pk.n_struct - j) for j in range(0, pk.n_struct, bs)]))
-                return pk, [np.asarray(tgt, dtype=np.float32)]
-            parts, tg = [], []
-            for i in range(g0, min(n, g0 + group)):
-                item, tgt = dataset[i]
-                parts.append(item if isinstance(item, _hip.PackedBatch) else _hip.pack_inputs(item))
-                tg.append(np.asarray(tgt, dtype=np.float32))
-            pk = _hip.concat_packed(parts) if len(parts) > 1 else parts[0]
+        def jobs():  # tag: (targets, the group's PackedBatch, structures per dataset batch)
+            for g0 in range(0, n, group):
+                if grouped is not None:
+                    pk, tgt = grouped(g0, min(n, g0 + group))
+                    tg, counts = [np.asarray(tgt, dtype=np.float32)], None
+                    if sel is not None:  # (a dataset batch holds batch_size structures, the last one the rest)
+                        bs = int(dataset.batch_size)
+                        counts = [min(bs, pk.n_struct - j) for j in range(0, pk.n_struct, bs)]
+                else:
+                    parts, tg = [], []
+                    for i in range(g0, min(n, g0 + group)):
+                        item, tgt = dataset[i]
+                        parts.append(item if isinstance(item, _hip.PackedBatch) else _hip.pack_inputs(item))
+                        tg.append(np.asarray(tgt, dtype=np.float32))
+                    pk = _hip.concat_packed(parts) if len(parts) > 1 else parts[0]
+                    counts = [p.n_struct for p in parts]
+                yield functools.partial(eng.upload, pk), (tg, pk, counts)
+
+        def finish(rb, tag):
+            tg, pk, counts = tag
+            y, ga = eng.download(rb, want_ga=want_ga)
             if sel is not None:
-                layout.append((pk, [p.n_struct for p in parts]))
-            return pk, tg
+                self._split_outputs(self._read_outputs(rb, sel), pk, counts, per_struct)
+            ys.append(y)
+            if want_ga:
+                gas.append(ga)
+            ts.extend(tg)
 
-        # One thread is enough, and faster: launches and uploads are asynchronous, so slicing + uploading group k + 1 right after
-        # enqueueing group k overlaps host and device by itself; the producer thread of rounds 3-4 (below, SCANN_DATASET_THREAD=1)
-        # cost more in Python thread hand-offs than it hid (bench.py end_to_end: 1.70-1.72 M -> 1.81 M molecules/s, one box).
-        if os.environ.get("SCANN_DATASET_THREAD", "0") != "1" or sel is not None:
-            k = 0
-            if sel is not None:
-                self._select(sel)
-            try:
-                for g0 in range(0, n, group):
-                    pk, tg = make(g0)
-                    rb = eng.upload(pk)
-                    ts.extend(tg)
-                    try:
-                        if len(pending) >= 2 * ns:
-                            fetch_oldest()
-                        eng.forward_resident(rb, k % ns)
-                    except BaseException:
-                        rb.free()
-                        raise
-                    k += 1
-                    pending.append(rb)
-                while pending:
-                    fetch_oldest()
-            finally:
-                if sel is not None:
-                    self._select(None)
-                for rb in pending:
-                    rb.free()
-            if not ys:
-                res = np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
-            else:
-                res = np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
-            return res if sel is None else res + (per_struct,)
-        ready = queue.Queue(maxsize=max(2, ns))  # uploaded groups waiting for their launches
-        stop = threading.Event()
-
-        def put(item):
-            while not stop.is_set():
-                try:
-                    ready.put(item, timeout=0.05)
-                    return True
-                except queue.Full:
-                    pass
-            return False
-
-        def producer():
-            try:
-                for g0 in range(0, n, group):
-                    if stop.is_set():
-                        return
-                    pk, tg = make(g0)
-                    rb = eng.upload(pk)
-                    if not put((rb, tg)):
-                        rb.free()
-                        return
-                put(None)
-            except BaseException as e:  # noqa: BLE001 -- handed to the consumer, which re-raises it
-                put(e)
-
-        worker = threading.Thread(target=producer, name="scann-upload", daemon=True)
-        worker.start()
-        k = 0
-        taken = None  # a group taken off the queue and not yet in flight
-        try:
-            while True:
-                item = ready.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                taken, tg = item
-                ts.extend(tg)
-                if len(pending) >= ns:
-                    fetch_oldest()  # frees the stream slot the new group is about to use
-                eng.forward_resident(taken, k)
-                k += 1
-                pending.append(taken)
-                taken = None
-            while pending:
-                fetch_oldest()
-        finally:
-            stop.set()
-            worker.join()
-            if taken is not None:
-                taken.free()
-            while True:  # groups uploaded but never launched (an error on either side)
-                try:
-                    item = ready.get_nowait()
-                except queue.Empty:
-                    break
-                if isinstance(item, tuple):
-                    item[0].free()
-            for rb in pending:
-                rb.free()
+        self._pipeline(jobs(), finish, sel)
         if not ys:
-            return np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
-        return np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
+            res = np.zeros(0, np.float32), (np.zeros(0, np.float32) if want_ga else None), np.zeros(0, np.float32)
+        else:
+            res = np.concatenate(ys), (np.concatenate(gas) if want_ga else None), np.concatenate(ts)
+        return res if sel is None else res + (per_struct,)
 
     def _split_outputs(self, packed, pk, counts, per_struct):
         """Packed outputs of one fused group (PackedBatch ``pk``, ``counts`` structures per dataset batch) -> one array per structure,

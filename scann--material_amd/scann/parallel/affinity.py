@@ -1,6 +1,6 @@
 """CPU affinity of a rank: the cores of its GPU's NUMA node.
 
-Eight ranks of one node each run a main thread and a producer thread (``HipModel.predict_dataset``, ``trainer.fit``); left to
+Eight ranks of one node each run a main thread and, in training, a loader thread (``trainer.fit``); left to
 float over all cores they share caches with seven strangers and cross the socket to reach their GPU's PCIe root.  A rank
 therefore pins itself -- before its first GPU call -- to the cores of the NUMA node its device hangs off
 (``/sys/class/drm/card*/device/numa_node``), and the ranks whose devices share a node split that node's cores between them.

@@ -1509,17 +1509,106 @@ def test_train_cli_flags_and_overrides(tmp_path, monkeypatch):
     assert np.random.rand() == x
 
 
-@pytest.mark.parametrize("threaded", [False, True])
-def test_predict_dataset_pipeline_with_a_stub_engine(monkeypatch, threaded):
-    """HipModel.predict_dataset's pipeline without a GPU, in both forms: the default software pipeline on the calling thread (group
-    k + 1 uploaded right after group k's launches) and the producer-thread form of rounds 3-4 (SCANN_DATASET_THREAD=1: uploads on a
-    second thread).  Results come back in dataset order, an error raised by the engine in upload or download reaches the caller, and
-    every uploaded batch is freed or released exactly once."""
-    monkeypatch.setenv("SCANN_DATASET_THREAD", "1" if threaded else "0")
+class _StubBatch:
+    """ResidentBatch stand-in: ends exactly once, freed or released"""
+
+    def __init__(self, eng, packed, y):
+        self.eng, self.packed, self.y, self.state = eng, packed, y, "uploaded"
+        eng.live.add(self)
+
+    def _end(self, how):
+        assert self.state != "gone", "freed twice"
+        self.state = "gone"
+        self.eng.live.discard(self)
+        self.eng.ended.append(how)
+
+    def free(self):
+        self._end("free")
+
+    def release(self):
+        self._end("release")
+
+
+class _StubEngine:
+    """Engine stand-in for HipModel's resident pipeline: the n-th upload / launch / download fails on request (ScannHipError), and
+    every launch records its stream slot and the output selection in force.  The "prediction" of a structure is a number the test
+    can check order by: its atom count (PackedBatch) or its first atomic number (padded rows); its GlobalAttention scores repeat it."""
+    training = False
+
+    def __init__(self, streams=2, fail_upload_at=None, fail_forward_at=None, fail_download_at=None):
+        self.streams, self.fail = streams, dict(upload=fail_upload_at, forward=fail_forward_at, download=fail_download_at)
+        self.calls = dict(upload=0, forward=0, download=0)
+        self.live, self.ended, self.upload_threads, self.slots, self.launch_sel = set(), [], set(), [], []
+        self.selected, self.in_flight, self.max_in_flight = None, 0, 0
+
+    def _call(self, what):
+        from scann import _hip
+
+        self.calls[what] += 1
+        if self.calls[what] == self.fail[what]:
+            raise _hip.ScannHipError(-1, what + " failed")
+
+    def num_streams(self):
+        return self.streams
+
+    def upload(self, pk):
+        import threading
+
+        self.upload_threads.add(threading.get_ident())
+        self._call("upload")
+        return _StubBatch(self, pk, np.diff(pk.mol_offset).astype(np.float32))
+
+    def upload_padded(self, inputs):
+        from scann import _hip
+
+        amask = np.asarray(inputs["atom_mask"]) != 0
+        self._call("upload")
+        return _StubBatch(self, _hip.PaddedInfo(len(amask), int(amask.sum()), 0, amask), inputs["atomic"][:, 0].astype(np.float32))
+
+    def set_outputs(self, attn_layers=(), after_lc=False, bf_property=False):
+        self.selected = (tuple(attn_layers), after_lc, bf_property) if (len(attn_layers) or after_lc or bf_property) else None
+
+    def forward_resident(self, rb, slot):
+        assert rb.state == "uploaded"
+        self._call("forward")
+        rb.state = "launched"
+        self.slots.append(slot)
+        self.launch_sel.append(self.selected)
+        self.in_flight += 1
+        self.max_in_flight = max(self.max_in_flight, self.in_flight)
+
+    def download(self, rb, want_ga=True):
+        assert rb.state == "launched"
+        self._call("download")
+        self.in_flight -= 1
+        p = rb.packed
+        sizes = np.diff(p.mol_offset) if hasattr(p, "mol_offset") else p.atom_mask.sum(1)
+        return rb.y, (np.repeat(rb.y, sizes) if want_ga else None)
+
+    def read_output(self, rb, what, layer=0):
+        from scann import _hip
+
+        assert what == _hip.OUT_BF_PROPERTY and rb.state == "launched"
+        return np.stack([rb.y, -rb.y], 1)
+
+
+def _stub_model(eng, **attrs):
+    from scann.models.scann_model import HipModel
+
+    m = HipModel.__new__(HipModel)
+    m.engine = eng
+    m.__dict__.update(attrs)
+    return m
+
+
+def test_predict_dataset_pipeline_with_a_stub_engine():
+    """HipModel.predict_dataset's pipeline without a GPU: group k + 1 is uploaded on the calling thread right after group k's
+    launches, at most 2 x streams groups are in flight, group k runs on stream k % streams.  Results come back in dataset order, an
+    error raised by the engine in upload, launch or download reaches the caller unchanged, and every uploaded batch is freed or
+    released exactly once."""
     import threading
 
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     rng = np.random.default_rng(3)
 
@@ -1531,74 +1620,66 @@ def test_predict_dataset_pipeline_with_a_stub_engine(monkeypatch, threaded):
         return _hip.PackedBatch(rng.integers(1, 9, mol[-1]).astype(np.int32), mol, eoff, base.astype(np.int32),
                                 rng.random(eoff[-1]).astype(np.float32), rng.random(eoff[-1]).astype(np.float32))
 
-    class Rb:
-        def __init__(self, eng, pk):
-            self.eng, self.packed, self.state = eng, pk, "uploaded"
-            eng.live.add(self)
-
-        def _end(self, how):
-            assert self.state != "gone", "freed twice"
-            self.state = "gone"
-            self.eng.live.discard(self)
-            self.eng.ended.append(how)
-
-        def free(self):
-            self._end("free")
-
-        def release(self):
-            self._end("release")
-
-    class Eng:
-        def __init__(self, fail_upload_at=None, fail_download_at=None):
-            self.live, self.ended, self.n_up, self.n_down = set(), [], 0, 0
-            self.fail_upload_at, self.fail_download_at = fail_upload_at, fail_download_at
-            self.upload_threads = set()
-
-        def num_streams(self):
-            return 2
-
-        def upload(self, pk):
-            self.upload_threads.add(threading.get_ident())
-            self.n_up += 1
-            if self.n_up == self.fail_upload_at:
-                raise RuntimeError("upload failed")
-            return Rb(self, pk)
-
-        def forward_resident(self, rb, slot):
-            assert rb.state == "uploaded"
-            rb.state = "launched"
-
-        def download(self, rb, want_ga=True):
-            assert rb.state == "launched"
-            self.n_down += 1
-            if self.n_down == self.fail_download_at:
-                raise RuntimeError("download failed")
-            y = np.diff(rb.packed.mol_offset).astype(np.float32)           # "prediction" = atoms per structure: order is checkable
-            return y, (np.arange(rb.packed.n_atom, dtype=np.float32) if want_ga else None)
-
     data = [(batch(int(rng.integers(1, 6))), rng.random(1)) for _ in range(23)]
     data = [(pk, np.full(pk.n_struct, i, np.float32)) for i, (pk, _) in enumerate(data)]
     expect_y = np.concatenate([np.diff(pk.mol_offset) for pk, _ in data]).astype(np.float32)
     expect_t = np.concatenate([t for _, t in data])
-
-    def model(eng):
-        m = HipModel.__new__(HipModel)
-        m.engine = eng
-        return m
+    expect_ga = np.concatenate([np.repeat(np.diff(pk.mol_offset), np.diff(pk.mol_offset)) for pk, _ in data]).astype(np.float32)
 
     for group in (1, 4, 50):
-        eng = Eng()
-        y, ga, t = model(eng).predict_dataset(data, group=group, want_ga=True)
+        eng = _StubEngine()
+        y, ga, t = _stub_model(eng).predict_dataset(data, group=group, want_ga=True)
         assert np.array_equal(y, expect_y) and np.array_equal(t, expect_t) and len(ga) == sum(pk.n_atom for pk, _ in data)
-        assert not eng.live and eng.ended.count("release") == eng.n_up
-        assert (threading.get_ident() not in eng.upload_threads) == threaded
-    for kw in (dict(fail_upload_at=3), dict(fail_download_at=2)):
-        eng = Eng(**kw)
-        with pytest.raises(RuntimeError):
-            model(eng).predict_dataset(data, group=2)
+        assert np.array_equal(ga, expect_ga)
+        assert not eng.live and eng.ended.count("release") == eng.calls["upload"]
+        assert eng.upload_threads == {threading.get_ident()}
+        n_groups = -(-len(data) // group)
+        assert eng.slots == [k % 2 for k in range(n_groups)] and eng.max_in_flight == min(4, n_groups)
+    # a failing launch: the second group (one in flight), the sixth (just uploaded, four in flight)
+    for kw in (dict(fail_upload_at=3), dict(fail_forward_at=2), dict(fail_forward_at=6), dict(fail_download_at=2)):
+        eng = _StubEngine(**kw)
+        with pytest.raises(_hip.ScannHipError) as e:
+            _stub_model(eng).predict_dataset(data, group=2)
+        assert str(e.value).endswith(" failed")
         assert not eng.live  # nothing uploaded is left behind, launched or not
-    y, ga, t = model(Eng()).predict_dataset([], group=4)
+    y, ga, t = _stub_model(_StubEngine()).predict_dataset([], group=4)
     assert len(y) == 0 and ga is None and len(t) == 0
+
+
+def test_predict_chunked_pipeline_with_a_stub_engine():
+    """model.predict on a whole padded dataset (HipModel._predict_chunked) without a GPU: chunks of rows in order through the resident
+    pipeline (at most 2 x streams in flight, chunk k on stream k % streams), every batch released or freed exactly once, a failing
+    download names the structures of its chunk, and the output selection is on for every launch and cleared on every exit."""
+    from scann import _hip
+
+    B, M, N = 3000, 3, 2  # chunks of 768 structures: 0..767, 768..1535, 1536..2303, 2304..2999
+    rng = np.random.default_rng(4)
+    amask = np.ones((B, M), dtype=bool)
+    amask[:, 2] = rng.random(B) < 0.5
+    inputs = dict(atomic=np.where(amask, np.arange(B)[:, None], 0).astype(np.int32), atom_mask=amask,
+                  neighbors=np.zeros((B, M, N), np.int32), neighbor_mask=np.ones((B, M, N), bool),
+                  neighbor_weight=np.ones((B, M, N), np.float32), neighbor_distance=np.ones((B, M, N), np.float32))
+    cfg = {"model": {"feature": "atomic", "use_ring": False, "n_attention": 2}}
+    expect_y = np.arange(B, dtype=np.float32).reshape(-1, 1)
+
+    for streams in (1, 2):
+        eng = _StubEngine(streams=streams)
+        y, ga = _stub_model(eng, config=cfg, infer=True, outputs=None).predict(inputs)
+        assert np.array_equal(y, expect_y) and ga.shape == (B, M, 1)
+        assert np.array_equal(ga[amask, 0], np.repeat(np.arange(B), amask.sum(1))) and not ga[~amask].any()
+        assert eng.slots == [k % streams for k in range(4)] and eng.max_in_flight == min(4, 2 * streams)
+        assert not eng.live and eng.ended == ["release"] * 4 and eng.launch_sel == [None] * 4
+    eng = _StubEngine(streams=1)
+    bf, yy = _stub_model(eng, config=cfg, infer=False, outputs=None).predict(inputs, outputs=["bf_property", "predict_property"])
+    assert np.array_equal(yy, expect_y) and np.array_equal(bf, np.concatenate([expect_y, -expect_y], 1))
+    assert eng.launch_sel == [((), False, True)] * 4 and eng.selected is None and eng.ended == ["release"] * 4
+    for kw, msg in ((dict(fail_download_at=2), r"download failed \[structures 768\.\.1535 of this call\]$"),
+                    (dict(fail_upload_at=4), r"upload failed$"), (dict(fail_forward_at=3), r"forward failed$")):
+        for outputs in (None, ["bf_property"]):
+            eng = _StubEngine(streams=1, **kw)
+            with pytest.raises(_hip.ScannHipError, match=msg):
+                _stub_model(eng, config=cfg, infer=True, outputs=None).predict(inputs, outputs=outputs)
+            assert not eng.live and eng.selected is None
 
 
 def test_mask_counting_matches_the_host_packer(hip_lib):
