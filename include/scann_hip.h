@@ -267,6 +267,17 @@ int scann_train_step_begin(scann_handle_t* h, scann_dbatch_t* db, const float* t
 int scann_train_step_end(scann_handle_t* h, double* sse_out, int64_t* count_out, double* abs_err_out /* sum |y - target|, or NULL */);
 int scann_get_grads(scann_handle_t* h, float* out);           /* [scann_param_count] */
 int scann_get_weights(scann_handle_t* h, float* out);         /* current master parameters, same order */
+
+/* ---- gradients of the prediction with respect to the inputs (inference semantics) ----
+ * d y_s / d input for every structure of a resident batch (inference semantics, dy_s = 1 per structure); synchronous.
+ * y is the raw output (predict_property, before any target de-normalisation); mrelu (target e_b) passes the gradient through as the
+ * identity, as in training.  Writes nothing into the training state (gradients, Adam moments, master weights, step counter); on a
+ * training handle it uses the current weights.  SCANN_ERR_UNSUPPORTED for a checkpoint with |w| >= 255.9 in a 128x128 kernel,
+ * SCANN_ERR_RANGE when the forward's range guard fires; either is returned before any output is written.
+ * Any output pointer may be NULL (that leaf is not computed): y[n_struct], d_distance[n_edge], d_weight[n_edge],
+ * d_ring[n_atom*2] (use_ring), d_cgcnn[n_atom*92] (feature cgcnn; otherwise SCANN_ERR_INVALID if non-NULL). */
+int scann_input_grads(scann_handle_t* h, scann_dbatch_t* db, float* y, float* d_distance, float* d_weight,
+                      float* d_ring, float* d_cgcnn);
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -72,12 +72,15 @@ struct scann_train_ws {  // per resident batch (scann_dbatch::train), allocated 
   float* det_part = nullptr;  // deterministic mode: the slots of the otherwise atomic reductions (first deterministic backward)
   size_t det_floats = 0;
   double* sse = nullptr;
+  char* ig = nullptr;  // scann_input_grads: the device copies of its outputs (first such call on the batch)
+  size_t ig_bytes = 0;
   float drop_p = 0.f, attn_p = 0.f;
   unsigned long long seed = 0;
   GenKeep gen;  // generic widths: the training forward's tensors and the backward's temporaries
   ~scann_train_ws() {  // freed with its batch (free_batch): the arenas go back to the block cache
     cached_free(arena);
     cached_free(det_part);
+    cached_free(ig);
     cached_free(gen.arena);
     cached_free(gen.barena);
   }
@@ -152,6 +155,8 @@ struct scann_handle {
   // training state (scann_train_begin)
   float *t_master = nullptr, *t_grad = nullptr, *t_m = nullptr, *t_v = nullptr, *t_l2 = nullptr;
   RepackDesc* t_descs = nullptr;
+  // scann_input_grads: where its backward's parameter-gradient side products go (never the training state above), allocated by its first call
+  float* ig_grad = nullptr;
   int64_t t_step = 0;
   float train_drop_p = 0.f;            // > 0 only inside scann_train_forward
   float attn_drop_p = 0.f;             // use_drop: Dropout(0.05) on attention weights (scann_set_attention_dropout)

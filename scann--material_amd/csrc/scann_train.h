@@ -155,4 +155,27 @@ void launch_adam(float* w, float* g, float* m, float* v, const float* l2mask, si
                  float eps, float l2, int zero_g, hipStream_t s);
 void launch_repack(const RepackDesc* descs, int n, const float* master, float* arena, int32_t* range_flag, hipStream_t s);
 
+// ---- leaves of the data-gradient backward (scann_input_grad.hip; scann_input_grads) ----
+// d y / d (dist, weight) per edge from the gradient of the first geometry features dG0 [n_edge,width] (g_update); null outputs: skipped
+void launch_basis_input_grad(const float* dist, const float* weight, const float* dG0, const float* Wd, const float* bd, const float* Ww,
+                             const float* bw, const float* cd, const float* cw, int n_edge, int width, float* d_dist, float* d_weight,
+                             hipStream_t s);
+// base branch: ADDS one layer's share from d y / d geomL [n_edge,width]
+void launch_base_input_grad(const float* dist, const float* weight, const float* dgeomL, const float* Wf, const float* bf, const float* cd,
+                            int n_edge, int width, float* d_dist, float* d_weight, hipStream_t s);
+struct InputGradEmbed {
+  int32_t width, emb_dim;
+  const float* dC;          // [n_atom,width] d y / d centres after dense_embed
+  const int32_t* atomic;    // [n_atom] (feature "atomic")
+  const float* cgcnn;       // [n_atom,92] or null
+  const float* ring;        // [n_atom,2] or null (no ring input)
+  const float* emb;         // embed_atom/embeddings [n_atoms,emb]
+  const float *We, *be;     // embed_atom/kernel [92,emb], bias (cgcnn)
+  const float *Wr, *br;     // extra_embed [2,10], [10]
+  const float *Wde, *bde;   // dense_embed [emb(+10),width], [width]
+  float *d_ring, *d_cgcnn;  // out [n_atom,2], [n_atom,92] or null
+};
+size_t embed_input_grad_lds(int emb_dim, bool ring, int width);
+void launch_embed_input_grad(const InputGradEmbed& a, int n_atom, hipStream_t s);
+
 }  // namespace scann

@@ -77,6 +77,47 @@ int ensure_train_ws(scann_handle* h, scann_dbatch* db, scann_train_ws** out) {
   return SCANN_OK;
 }
 
+// Data-gradient mode of the backward (scann_input_grads): device outputs of its leaves, null where not asked for.  In this mode the
+// backward seeds nothing itself (dy = 1 is in place), enqueues no weight-gradient work and leaves the training state alone.
+struct InGrad {
+  float *d_dist, *d_weight, *d_ring, *d_cgcnn;
+};
+
+// generic widths: the backward's d x = d z . W^T runs through gen_dense_kernel on transposed images of the kernels: one block per kernel,
+// except that filter_geo of the g_update branch is cut into its centre / geometry / neighbour thirds (attention.py:142-150) and
+// dense_embed with the ring input into its embedding / ring rows (scann_model.py:367-373) -- each third's d x is a tensor of its own.
+// The descriptors depend on the configuration only; gen_backward refreshes the images from the current weights.
+int build_gen_transposes(scann_handle* h) {
+  h->gt_descs.clear();
+  h->gt_off.clear();
+  int64_t off = 0;
+  h->gt_max = 0;
+  const int d = h->cfg.local_dim, emb = h->cfg.embedding_dim;
+  for (size_t i = 0; i < h->specs.size(); ++i) {
+    const WeightSpec& sp = h->specs[i];
+    const std::string& nm = sp.name;
+    if (!(sp.cols > 0 && nm.size() > 7 && nm.compare(nm.size() - 7, 7, "/kernel") == 0)) continue;
+    std::vector<int> cuts{0, (int)sp.rows};
+    if (h->cfg.g_update && nm.find("/filter_geo/") != std::string::npos && sp.rows == 3 * d) cuts = {0, d, 2 * d, 3 * d};
+    if (nm == "dense_embed/kernel" && h->cfg.use_ring) cuts = {0, emb, emb + 10};
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+      const int kn = cuts[b + 1] - cuts[b];
+      h->gt_descs.push_back(GenTransDesc{h->spec_off[i], off, cuts[b], kn, (int32_t)sp.cols});
+      h->gt_off[nm + "#" + std::to_string(b)] = off;
+      off += (int64_t)kn * sp.cols;
+      h->gt_max = std::max(h->gt_max, kn * (int)sp.cols);
+    }
+  }
+  if (h->g_WT) (void)hipFree(h->g_WT);
+  if (h->d_gt_descs) (void)hipFree(h->d_gt_descs);
+  h->g_WT = nullptr;
+  h->d_gt_descs = nullptr;
+  HIPCHK(h, hipMalloc((void**)&h->g_WT, (size_t)std::max<int64_t>(off, 1) * 4));
+  HIPCHK(h, hipMalloc((void**)&h->d_gt_descs, h->gt_descs.size() * sizeof(GenTransDesc)));
+  HIPCHK(h, hipMemcpy(h->d_gt_descs, h->gt_descs.data(), h->gt_descs.size() * sizeof(GenTransDesc), hipMemcpyHostToDevice));
+  return SCANN_OK;
+}
+
 int64_t spec_offset(const scann_handle* h, const std::string& name) {
   for (size_t i = 0; i < h->specs.size(); ++i)
     if (h->specs[i].name == name) return h->spec_off[i];
@@ -123,6 +164,10 @@ static int train_forward_impl(scann_handle_t* h, scann_dbatch_t* db, const float
     db->kept = true;
     db->dbg_layers = h->cfg.n_attention;
   }
+  if (!targets) {  // scann_input_grads: no loss
+    *wout = w;
+    return SCANN_OK;
+  }
   // targets: staged in pinned memory that the loss kernel reads directly (it leaves the device copy the backward uses): no copy operation
   if (h->h_targets_cap[slot] < (size_t)db->n_struct) {
     if (h->h_targets[slot]) {
@@ -168,7 +213,10 @@ static int ensure_reverse(scann_handle_t* h, scann_dbatch_t* db) {
 // The backward pass of create_model (scann_model.py:362-447) for a generic-width handle: the formulas of backward_impl below, one plain
 // kernel each (scann_generic_train.hip), on the tensors the training forward kept (GenKeep).  One stream; gradients are ACCUMULATED
 // into the flat gradient vector (two backward calls give the gradient of the sum, as on the 128-wide path).
-static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done) {
+// ig non-null: the data-gradient mode (InGrad): no weight gradients, the parameter-gradient side products of the LayerNorm backward go to
+// h->ig_grad, and the input leaves are called where the weight-gradient leaves would be.
+static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done,
+                        const InGrad* ig) {
   hipStream_t s = h->streams[0];
   const scann_config_t& c = h->cfg;
   GenKeep& kp = w.gen;
@@ -218,7 +266,7 @@ static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w
   launch_gen_transpose(h->d_gt_descs, (int)h->gt_descs.size(), h->gt_max, h->g_weights, h->g_WT, s);
   auto Wp = [&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
   auto WT = [&](const std::string& name, int blk = 0) -> const float* { return h->g_WT + h->gt_off.at(name + "/kernel#" + std::to_string(blk)); };
-  auto G = [&](const std::string& name) -> float* { return h->t_grad + h->g_off.at(name); };
+  auto G = [&](const std::string& name) -> float* { return (ig ? h->ig_grad : h->t_grad) + h->g_off.at(name); };
   const GenSeg none{nullptr, nullptr, 0};
   // d x [rows, n_in] = d z [rows, n_out] . W^T (+ res)
   auto dx = [&](const float* dZ_, int rows, int n_out, int n_in, const float* wt, const float* res, float* out) {
@@ -229,6 +277,7 @@ static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w
   };
   bool part_overrun = false;
   auto dw = [&](GenSeg s0, GenSeg s1, GenSeg s2, int n_seg, int prod, const float* dZ_, int K_, int N_, int rows, const std::string& name) {
+    if (ig) return;
     GenDwArgs a{};
     a.seg[0] = s0; a.seg[1] = s1; a.seg[2] = s2; a.n_seg = n_seg; a.prod = prod;
     a.dZ = dZ_; a.K = K_; a.N = N_; a.rows = rows; a.dW = G(name + "/kernel"); a.db = G(name + "/bias"); a.part = wp;
@@ -293,11 +342,35 @@ static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w
       std::swap(dG_next, dG_spare);
     } else {  // g = swish(basis . Wf + bf) * Voronoi weight (attention.py:159-163)
       launch_gen_mul_gather(dang, b.cc_in, db->edge_col, nullptr, E, d, dGt, s);
-      launch_gen_act_bwd(dGt, b.Z, db->weight, E, d, 0.f, 0, 0, dZ, s);
-      dw(GenSeg{kp.gd, nullptr, NG}, none, none, 1, 0, dZ, NG, d, E, la + "/filter_geo");
+      if (ig) {
+        launch_base_input_grad(db->dist, db->weight, dGt, Wp(la + "/filter_geo/kernel"), Wp(la + "/filter_geo/bias"), h->g_centres, E, d,
+                               ig->d_dist, ig->d_weight, s);
+      } else {
+        launch_gen_act_bwd(dGt, b.Z, db->weight, E, d, 0.f, 0, 0, dZ, s);
+        dw(GenSeg{kp.gd, nullptr, NG}, none, none, 1, 0, dZ, NG, d, E, la + "/filter_geo");
+      }
       launch_gen_edge_to_atom(db->edge_offset, db->in_off, db->in_edge, nullptr, nullptr, dang, b.Gn, dC_other, A, d, dC_other, s);
     }
     std::swap(dC, dC_other);
+  }
+  if (ig) {  // the input leaves (scann_input_grad.hip) in place of the basis-MLP and embedding weight gradients
+    if (c.g_update && dGn)
+      launch_basis_input_grad(db->dist, db->weight, dGn, Wp("neighbor_d/kernel"), Wp("neighbor_d/bias"), Wp("neighbor_w/kernel"),
+                              Wp("neighbor_w/bias"), h->g_centres, h->g_centres + NG, E, d, ig->d_dist, ig->d_weight, s);
+    if (ig->d_ring || ig->d_cgcnn) {
+      InputGradEmbed e{};
+      e.width = d; e.emb_dim = emb; e.dC = dC; e.atomic = db->atomic;
+      e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+      e.ring = c.use_ring ? db->ring : nullptr;
+      if (c.feature_cgcnn) { e.We = Wp("embed_atom/kernel"); e.be = Wp("embed_atom/bias"); }
+      else e.emb = Wp("embed_atom/embeddings");
+      if (c.use_ring) { e.Wr = Wp("extra_embed/kernel"); e.br = Wp("extra_embed/bias"); }
+      e.Wde = Wp("dense_embed/kernel"); e.bde = Wp("dense_embed/bias");
+      e.d_ring = ig->d_ring; e.d_cgcnn = ig->d_cgcnn;
+      launch_embed_input_grad(e, A, s);
+    }
+    HIPCHK(h, hipGetLastError());
+    return SCANN_OK;
   }
   // ---- basis MLP of the initial geometry (scann_model.py:386-391) ----
   if (c.g_update && dGn) {
@@ -326,14 +399,18 @@ static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w
 }
 
 // d_stat (device, {global sse, global count}) non-null: the loss scale is formed on the device (scann_train_step: no host round trip)
-static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done) {
+// ig non-null: the data-gradient mode (InGrad; scann_input_grads): one stream, no weight-gradient launch or reduction, no deterministic
+// slots; what the fused kernels store per workgroup for the LayerNorm gradients stays in the partial arena, the readout's bias
+// gradient goes to h->ig_grad, and the input leaves replace the basis / filter_geo / embedding weight-gradient leaves.
+static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done,
+                         const InGrad* ig = nullptr) {
   if (const int r = ensure_reverse(h, db)) return r;
-  if (h->generic) return gen_backward(h, db, w, scale, d_stat, dy_done);
+  if (h->generic) return gen_backward(h, db, w, scale, d_stat, dy_done, ig);
   hipStream_t s = h->streams[0];
   const scann_config_t& c = h->cfg;
   const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
   const size_t nA = (size_t)A * D, nE = (size_t)E * D;
-  float* const G = h->t_grad;
+  float* const G = ig ? h->ig_grad : h->t_grad;
   auto g = [&](const std::string& name) { return G + spec_offset(h, name); };
   if (!dy_done) launch_dy(db->y, w.targets, B, scale, d_stat, w.dy, s);
   // Weight-gradient GEMMs are off the critical path (only the final reduce needs them): with the kept-activation forward
@@ -341,7 +418,7 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   // alone does not fill the chip at batch 128.  fork(): side stream waits for everything enqueued so far; join(): main waits
   // for the side stream (start of every layer: the previous layer's temporaries are about to be overwritten).
   hipStream_t aux = h->train_aux;
-  const bool side = aux != nullptr;
+  const bool side = aux != nullptr && !ig;
   size_t ev_i = 0;
   auto fork = [&]() -> hipStream_t {
     if (!side) return s;
@@ -383,10 +460,13 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   };
   WgradCtx wg;
   wg.arena = w.wpart;
+  auto wadd = [&](auto&&... a) {  // a weight gradient's GEMM job (none in the data-gradient mode)
+    if (!ig) wgrad_add(wg, a...);
+  };
   // deterministic mode: slots of the six reductions that otherwise end in float atomics (scann_train.h), allocated with the batch's
   // workspace on the first such backward and sized from the batch shape alone
   WgradCtx dct;
-  WgradCtx* const det = h->deterministic ? &dct : nullptr;
+  WgradCtx* const det = h->deterministic && !ig ? &dct : nullptr;
   if (det) {
     const bool general = c.use_ring || c.feature_cgcnn;
     const size_t need = det_slot_floats(A, E, L, c.n_atoms, c.embedding_dim, c.g_update, general, c.feature_cgcnn, c.use_ring);
@@ -436,12 +516,12 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z = t1,
   // dgq = t2, dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no fork of their own,
   // each of which costs the main stream ~7 us (tools/fork_probe.hip)
-  wgrad_add(wg, w.rep, w.dpre, g("bf_property/kernel"), g("bf_property/bias"), B);
-  wgrad_add(wg, t1, t2, g("global_attention/query/kernel"), g("global_attention/query/bias"), A);
-  wgrad_add(wg, t1, rdgk, g("global_attention/key/kernel"), g("global_attention/key/bias"), A);
+  wadd(w.rep, w.dpre, g("bf_property/kernel"), g("bf_property/bias"), B);
+  wadd(t1, t2, g("global_attention/query/kernel"), g("global_attention/query/bias"), A);
+  wadd(t1, rdgk, g("global_attention/key/kernel"), g("global_attention/key/bias"), A);
   float* const dpreA = dQ;
   launch_linear_sum(t2, h->WgqT, rdgk, h->WgkT, nullptr, nullptr, dpreA, A, 0, s, t0);  // dpreA = (dgq.Wgq^T + dgk.Wgk^T) * swish'(preA)
-  wgrad_add(wg, cL, dpreA, g("after_Lc/kernel"), g("after_Lc/bias"), A);
+  wadd(cL, dpreA, g("after_Lc/kernel"), g("after_Lc/bias"), A);
 
   const float* dG_in = nullptr;  // gradient w.r.t. the geometry leaving layer l (none for the last layer)
   // fused chains (scann_train_fused.hip); SCANN_TRAIN_FUSED=0 selects the modular one-kernel-per-operation backward
@@ -480,8 +560,12 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
       (void)hipStreamWaitEvent(h->train_aux2, e, 0);
       bs = h->train_aux2;
     }
-    launch_basis_bwd(h->basis, db->dist, db->weight, dG, E, g("neighbor_d/kernel"), g("neighbor_d/bias"),
-                     g("neighbor_w/kernel"), g("neighbor_w/bias"), bs, det);
+    if (ig)
+      launch_basis_input_grad(db->dist, db->weight, dG, h->basis.Wd, h->basis.bd, h->basis.Ww, h->basis.bw, h->basis.cd, h->basis.cw, E, D,
+                              ig->d_dist, ig->d_weight, bs);
+    else
+      launch_basis_bwd(h->basis, db->dist, db->weight, dG, E, g("neighbor_d/kernel"), g("neighbor_d/bias"),
+                       g("neighbor_w/kernel"), g("neighbor_w/bias"), bs, det);
     if (bs != s) {
       ev_basis = h->train_ev[ev_i++ % h->train_ev.size()];
       (void)hipEventRecord(ev_basis, bs);
@@ -531,8 +615,8 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
         launch_linear(t3, pt.Wf2T, nullptr, t4, const_cast<float*>(pre1), A, 4, s);  // dpre1 = (dY.W2^T) * swish'(pre1)
         launch_linear(t4, pt.Wf1T, nullptr, dCtx, nullptr, A, 1, s);                 // dctx = dT2 + dpre1.W1^T
       }
-      wgrad_add(wg, H1, t3, g(rn + "dense_2/kernel"), g(rn + "dense_2/bias"), A);
-      wgrad_add(wg, ctx, t4, g(rn + "dense_1/kernel"), g(rn + "dense_1/bias"), A);
+      wadd(H1, t3, g(rn + "dense_2/kernel"), g(rn + "dense_2/bias"), A);
+      wadd(ctx, t4, g(rn + "dense_1/kernel"), g(rn + "dense_1/bias"), A);
     } else {
       HIPCHK(h, hipMemcpyAsync(dCtx, dC, nA * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -544,19 +628,23 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
     if (!fuse_attn)
       launch_attn_bwd(wg, qL, KL, db->edge_offset, dCtx, p.ln_g, dQ, edK, g(la + "layer_norm/gamma"), g(la + "layer_norm/beta"), A,
                       db->max_degree, w.attn_p, DROP_TAG_ATTN + (unsigned)l, w.seed, s);
-    if (angL) wgrad_add(wg, angL, edK, g(la + "key/kernel"), g(la + "key/bias"), E);
-    else wgrad_add(wg, c_in, edK, g(la + "key/kernel"), g(la + "key/bias"), E, db->edge_col, Gout);  // ang = c[j] * G'
-    wgrad_add(wg, c_in, dQ, g(la + "query/kernel"), g(la + "query/bias"), A);
+    if (angL) wadd(angL, edK, g(la + "key/kernel"), g(la + "key/bias"), E);
+    else wadd(c_in, edK, g(la + "key/kernel"), g(la + "key/bias"), E, db->edge_col, Gout);  // ang = c[j] * G'
+    wadd(c_in, dQ, g(la + "query/kernel"), g(la + "query/bias"), A);
     if (!c.g_update) {
       // base SCANN (attention.py:155): geomL = swish(gd.Wf + bf) * weight from the raw basis (kept in the V slices), no geometry threading
       launch_linear(edK, pt.WkT, nullptr, edAng, nullptr, E, 0, s);            // dang
       launch_edge_dang(c_in, db->edge_col, VL, edAng, nullptr, eT, eU, E, s);  // eT = dang * geomL ; eU = dgeomL = dang * c[j]
       launch_gather_sum(eT, db->in_off, db->in_edge, dC, A, 0, s);             // dC[j] = sum over the edges that point at j
-      // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
-      hipStream_t ws = fork();
-      wgrad_launch(wg, ws);
-      flush_side(ws, wg, l == 0);
-      launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws, det);
+      if (ig) {
+        launch_base_input_grad(db->dist, db->weight, eU, p.Wfg, p.bfg, h->cd, E, D, ig->d_dist, ig->d_weight, s);
+      } else {
+        // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
+        hipStream_t ws = fork();
+        wgrad_launch(wg, ws);
+        flush_side(ws, wg, l == 0);
+        launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws, det);
+      }
       pend.n = 1;  // dC += dq.Wq^T: folded into the next rn_bwd_kernel (or launched by flush_pend)
       pend.X[0] = dQ; pend.Wh[0] = pt.WqTh; pend.W[0] = pt.WqT;
       continue;
@@ -595,10 +683,12 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
       launch_linear(eU, pt.W2T, nullptr, dGnext, nullptr, E, 1, s);                    // dG += dV.W2^T
     }
     float* fgk = g(la + "filter_geo/kernel");
-    wgrad_add(wg, Gin, eU, fgk + (size_t)D * D, nullptr, E);  // dW2
-    wgrad_add(wg, c_in, dP1, fgk, g(la + "filter_geo/bias"), A);
-    wgrad_add(wg, c_in, dP3, fgk + (size_t)2 * D * D, nullptr, A);
-    if (l == 0 && side && ev_sums) {
+    wadd(Gin, eU, fgk + (size_t)D * D, nullptr, E);  // dW2
+    wadd(c_in, dP1, fgk, g(la + "filter_geo/bias"), A);
+    wadd(c_in, dP3, fgk + (size_t)2 * D * D, nullptr, A);
+    if (ig) {
+      // (no weight gradients)
+    } else if (l == 0 && side && ev_sums) {
       // The FIRST layer's gradient launch and its reductions are the longest thing left (the main stream only has the embedding chain,
       // ~40 us): they stay on the main stream, with no hand-over in front of them, and the embedding chain goes to the side stream
       // instead (0.830 -> 0.819 ms per step, eight alternations on one box: profiles/r05_notes.md)
@@ -624,6 +714,20 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   // the longest thing between here and the optimiser -- started behind the embedding chain it ended 30 us after it)
   if (dG_in && !basis_done) basis_leaf(dG_in, nullptr);
   flush_pend();
+  if (ig) {  // d y / d (ring, cgcnn) from d y / d centres after dense_embed (no Dropout: inference semantics)
+    if (ig->d_ring || ig->d_cgcnn) {
+      InputGradEmbed e{};
+      const EmbedArgs& ea = h->embed;
+      e.width = D; e.emb_dim = c.embedding_dim; e.dC = dC; e.atomic = db->atomic;
+      e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+      e.ring = c.use_ring ? db->ring : nullptr;
+      e.emb = ea.emb; e.We = ea.We; e.be = ea.be; e.Wr = ea.Wr; e.br = ea.br; e.Wde = ea.Wde; e.bde = ea.bde;
+      e.d_ring = ig->d_ring; e.d_cgcnn = ig->d_cgcnn;
+      launch_embed_input_grad(e, A, s);
+    }
+    HIPCHK(h, hipGetLastError());
+    return SCANN_OK;
+  }
   // deterministic mode: the readout's bias gradient = the sum of d loss / d y, in structure order, beside the embedding chain
   if (det) launch_scalar_sum(w.dy, B, g("predict_property/bias"), tail_s);
   if (c.use_ring || c.feature_cgcnn) {
@@ -715,36 +819,7 @@ int scann_train_begin(scann_handle_t* h) {
   }
   HIPCHK(h, hipMemcpy(h->t_l2, l2.data(), n * 4, hipMemcpyHostToDevice));
   if (h->generic) {
-    // the backward's d x = d z . W^T runs through gen_dense_kernel on transposed images of the kernels: one block per kernel, except
-    // that filter_geo of the g_update branch is cut into its centre / geometry / neighbour thirds (attention.py:142-150) and
-    // dense_embed with the ring input into its embedding / ring rows (scann_model.py:367-373) -- each third's d x is a tensor of its own
-    h->gt_descs.clear();
-    h->gt_off.clear();
-    int64_t off = 0;
-    h->gt_max = 0;
-    const int d = h->cfg.local_dim, emb = h->cfg.embedding_dim;
-    for (size_t i = 0; i < h->specs.size(); ++i) {
-      const WeightSpec& sp = h->specs[i];
-      const std::string& nm = sp.name;
-      if (!(sp.cols > 0 && nm.size() > 7 && nm.compare(nm.size() - 7, 7, "/kernel") == 0)) continue;
-      std::vector<int> cuts{0, (int)sp.rows};
-      if (h->cfg.g_update && nm.find("/filter_geo/") != std::string::npos && sp.rows == 3 * d) cuts = {0, d, 2 * d, 3 * d};
-      if (nm == "dense_embed/kernel" && h->cfg.use_ring) cuts = {0, emb, emb + 10};
-      for (size_t b = 0; b + 1 < cuts.size(); ++b) {
-        const int kn = cuts[b + 1] - cuts[b];
-        h->gt_descs.push_back(GenTransDesc{h->spec_off[i], off, cuts[b], kn, (int32_t)sp.cols});
-        h->gt_off[nm + "#" + std::to_string(b)] = off;
-        off += (int64_t)kn * sp.cols;
-        h->gt_max = std::max(h->gt_max, kn * (int)sp.cols);
-      }
-    }
-    if (h->g_WT) (void)hipFree(h->g_WT);
-    if (h->d_gt_descs) (void)hipFree(h->d_gt_descs);
-    h->g_WT = nullptr;
-    h->d_gt_descs = nullptr;
-    HIPCHK(h, hipMalloc((void**)&h->g_WT, (size_t)std::max<int64_t>(off, 1) * 4));
-    HIPCHK(h, hipMalloc((void**)&h->d_gt_descs, h->gt_descs.size() * sizeof(GenTransDesc)));
-    HIPCHK(h, hipMemcpy(h->d_gt_descs, h->gt_descs.data(), h->gt_descs.size() * sizeof(GenTransDesc), hipMemcpyHostToDevice));
+    if (const int r = build_gen_transposes(h)) return r;
   } else if (!h->train_aux) {
     // (side streams created with the lowest priority changed nothing: 0.895 vs 0.895 ms per step, profiles/r04_notes.md)
     // (and so did confining them to half / a quarter of the CUs with hipExtStreamCreateWithCUMask: 0.89-0.93 ms either way)
@@ -927,6 +1002,66 @@ int scann_train_step(scann_handle_t* h, scann_dbatch_t* db, const float* targets
   if (!sse_out || !count_out) return fail(h, SCANN_ERR_INVALID, "scann_train_step: null argument");
   const int r = scann_train_step_begin(h, db, targets, dropout, seed, lr_t, beta1, beta2, eps, l2);
   return r ? r : scann_train_step_end(h, sse_out, count_out, nullptr);
+}
+
+// d y_s / d input for every structure of a resident batch: the training forward with inference semantics (no Dropout, no attention
+// dropout) and the backward in its data-gradient mode, seeded with d y_s = 1 for every structure (structures are independent, so one
+// pass gives each structure's own gradients).  Touches none of the training state: on a training handle it reads the current weights,
+// on an inference handle it allocates what the training forward needs privately.  Synchronous.
+int scann_input_grads(scann_handle_t* h, scann_dbatch_t* db, float* y, float* d_distance, float* d_weight, float* d_ring, float* d_cgcnn) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_input_grads: null argument");
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_input_grads: weights not loaded");
+  const scann_config_t& c = h->cfg;
+  if (d_ring && !c.use_ring) return fail(h, SCANN_ERR_INVALID, "scann_input_grads: the model has no ring_aromatic input (use_ring off)");
+  if (d_cgcnn && !c.feature_cgcnn) return fail(h, SCANN_ERR_INVALID, "scann_input_grads: the model has no cgcnn input (feature is not cgcnn)");
+  if (h->weights_exact)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_input_grads: a 128x128 kernel has |w| >= 255.9; the backward kernels multiply in split-fp16 "
+                                          "form only (inference of such a checkpoint runs on the exact-fp32 kernels)");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->generic && !h->g_WT)
+    if (const int r = build_gen_transposes(h)) return r;
+  if (!h->ig_grad) HIPCHK(h, hipMalloc((void**)&h->ig_grad, h->host_master.size() * 4));
+  hipStream_t s = h->streams[0];
+  const float attn_p = h->attn_drop_p;
+  h->attn_drop_p = 0.f;
+  scann_train_ws* w = nullptr;
+  int r = train_forward_impl(h, db, nullptr, 0.f, 0, &w, 2);
+  h->attn_drop_p = attn_p;
+  if (r) {
+    db->kept = false;
+    return r;
+  }
+  const int A = db->n_atom, E = db->n_edge, B = db->n_struct;
+  const size_t bE = align_up((size_t)std::max(E, 1) * 4), bR = c.use_ring ? align_up((size_t)A * 2 * 4) : 0,
+               bC = c.feature_cgcnn ? align_up((size_t)A * 92 * 4) : 0, need = 2 * bE + bR + bC;
+  if (w->ig_bytes < need) {
+    HIPCHK(h, hipStreamSynchronize(s));
+    cached_free(w->ig);
+    w->ig = nullptr;
+    w->ig_bytes = 0;
+    HIPCHK(h, cached_malloc((void**)&w->ig, need));
+    w->ig_bytes = need;
+  }
+  InGrad ig{};
+  ig.d_dist = d_distance ? reinterpret_cast<float*>(w->ig) : nullptr;
+  ig.d_weight = d_weight ? reinterpret_cast<float*>(w->ig + bE) : nullptr;
+  ig.d_ring = d_ring ? reinterpret_cast<float*>(w->ig + 2 * bE) : nullptr;
+  ig.d_cgcnn = d_cgcnn ? reinterpret_cast<float*>(w->ig + 2 * bE + bR) : nullptr;
+  HIPCHK(h, hipMemsetAsync(w->ig, 0, need, s));  // (the base branch's leaf adds per layer; a model without layers leaves zeros)
+  HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w->dy), 0x3f800000, (size_t)B, s));  // d y_s = 1.0f
+  r = backward_impl(h, db, *w, 0.f, nullptr, /*dy_done=*/true, &ig);
+  db->kept = false;  // the kept tensors are this call's, not a training forward's (scann_train_backward asks for a new one)
+  const hipError_t se = hipStreamSynchronize(s);
+  if (r) return r;
+  HIPCHK(h, se);
+  if ((r = check_range(h, "scann_input_grads", 0))) return r;
+  if ((r = check_pack_flag(h, db, "scann_input_grads"))) return r;
+  if (y) HIPCHK(h, hipMemcpy(y, db->y, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (E > 0 && d_distance) HIPCHK(h, hipMemcpy(d_distance, ig.d_dist, (size_t)E * 4, hipMemcpyDeviceToHost));
+  if (E > 0 && d_weight) HIPCHK(h, hipMemcpy(d_weight, ig.d_weight, (size_t)E * 4, hipMemcpyDeviceToHost));
+  if (A > 0 && d_ring) HIPCHK(h, hipMemcpy(d_ring, ig.d_ring, (size_t)A * 2 * 4, hipMemcpyDeviceToHost));
+  if (A > 0 && d_cgcnn) HIPCHK(h, hipMemcpy(d_cgcnn, ig.d_cgcnn, (size_t)A * 92 * 4, hipMemcpyDeviceToHost));
+  return SCANN_OK;
 }
 
 }  // extern "C"

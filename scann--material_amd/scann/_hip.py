@@ -111,6 +111,7 @@ SYMBOLS = [
     ("scann_host_copy", C.c_int, [_P, _P, C.c_int64]),
     ("scann_set_outputs", C.c_int, [_P, C.c_uint64, C.c_int32]),
     ("scann_output_read", C.c_int64, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    ("scann_input_grads", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
 ]
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
@@ -275,6 +276,15 @@ def concat_packed(parts):
         ring=cat([p.ring for p in parts]), cgcnn=cat([p.cgcnn for p in parts]))
 
 
+def slice_packed(pk, s0, s1):
+    """Structures [s0, s1) of a PackedBatch as a PackedBatch of their own (offsets rebased; no padding information)."""
+    a0, a1 = int(pk.mol_offset[s0]), int(pk.mol_offset[s1])
+    e0, e1 = int(pk.edge_offset[a0]), int(pk.edge_offset[a1])
+    part = lambda x: x[a0:a1] if x is not None else None  # noqa: E731
+    return PackedBatch(part(pk.atomic), pk.mol_offset[s0:s1 + 1] - a0, pk.edge_offset[a0:a1 + 1] - e0, pk.edge_col[e0:e1] - a0,
+                       pk.edge_dist[e0:e1], pk.edge_weight[e0:e1], ring=part(pk.ring), cgcnn=part(pk.cgcnn))
+
+
 def pack_inputs(inputs):
     """Keras input dict (scann_model.py:338-357; DataIterator.__getitem__, datagenerator.py:123-133)
     -> PackedBatch.  Real atoms are those with atom_mask set; real edges the unmasked neighbour
@@ -374,6 +384,19 @@ def repad_local_attention(attn, atom_mask, neighbor_mask):
         out[~em.any(-1)] = np.float32(1.0) / np.float32(N)
     out[em] = attn
     return np.ascontiguousarray(out.transpose(0, 3, 1, 2))
+
+
+def repad_edges(x, atom_mask, neighbor_mask):
+    """Packed per-edge values [n_edge] -> [B, M, N] (edge e is slot ``np.nonzero(neighbor_mask & atom_mask)[e]``, as in
+    repad_local_attention) with 0 in every masked slot and every slot of a padded atom."""
+    em = np.asarray(neighbor_mask) != 0
+    em = em & (np.asarray(atom_mask).reshape(em.shape[:2]) != 0)[:, :, None]
+    x = np.asarray(x, dtype=np.float32)
+    if x.shape[0] != int(em.sum()):
+        raise ValueError("%d edge values for %d real neighbour slots" % (x.shape[0], int(em.sum())))
+    out = np.zeros(em.shape, dtype=np.float32)
+    out[em] = x
+    return out
 
 
 def repad_atoms(x, atom_mask):
@@ -639,6 +662,22 @@ class Engine:
         p = Profile()
         self._check(self.lib.scann_forward_profile(self._h, rb._h, C.byref(p)))
         return {k: getattr(p, k) for k, _ in Profile._fields_ if k != "reserved"}
+
+    def input_grads(self, rb, distance=True, weight=True, ring=False, cgcnn=False):
+        """d y_s / d input for every structure of a resident batch (scann_input_grads; inference semantics, raw y): a dict with
+        ``y`` [n_struct] and the gradients asked for -- ``neighbor_distance`` / ``neighbor_weight`` [n_edge] in packed edge order,
+        ``ring_aromatic`` [n_atom, 2], ``atomic`` [n_atom, 92] (feature cgcnn).  Leaves the handle's training state alone."""
+        p = rb.packed
+        y = np.empty(p.n_struct, dtype=np.float32)
+        out = {"neighbor_distance": np.empty(p.n_edge, np.float32) if distance else None,
+               "neighbor_weight": np.empty(p.n_edge, np.float32) if weight else None,
+               "ring_aromatic": np.empty((p.n_atom, 2), np.float32) if ring else None,
+               "atomic": np.empty((p.n_atom, 92), np.float32) if cgcnn else None}
+        self._check(self.lib.scann_input_grads(self._h, rb._h, _ptr(y), _ptr(out["neighbor_distance"]), _ptr(out["neighbor_weight"]),
+                                               _ptr(out["ring_aromatic"]), _ptr(out["atomic"])))
+        res = {k: v for k, v in out.items() if v is not None}
+        res["y"] = y
+        return res
 
     # -- training (scann_model.py:199-241) --------------------------------------------------------------------
     def _unflatten(self, flat):

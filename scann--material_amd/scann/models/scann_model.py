@@ -193,6 +193,60 @@ class HipModel:
 
     __call__ = predict
 
+    GRAD_INPUTS = ("neighbor_distance", "neighbor_weight", "ring_aromatic", "atomic")
+
+    def input_gradients(self, inputs, wrt=("neighbor_distance", "neighbor_weight"), batch_size=None):
+        """Gradients of each structure's own raw prediction y_s (``predict_property`` before any target de-normalisation) with
+        respect to its inputs, under inference semantics (no Dropout) -- what ``tf.GradientTape`` over ``model(inputs)`` gives for the
+        reference's graph, per structure.  ``wrt``: any of ``neighbor_distance``, ``neighbor_weight``, ``ring_aromatic`` (use_ring) and
+        ``atomic`` (feature cgcnn: the [.., 92] features).  Returns {name: gradient} plus ``predict_property`` [B, 1].  A padded dict
+        gives [B, M, N] / [B, M, 2] / [B, M, 92], 0 in masked slots and padded atoms; a ``PackedBatch`` gives packed [n_edge] /
+        [n_atom, 2] / [n_atom, 92].  Inputs are run ``batch_size`` structures at a time (default: hyper.batch_size) and the results
+        concatenated.  Unknown names, or names the configuration has no such input for, raise ValueError before anything runs."""
+        m = self.config["model"]
+        wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+        for n in wrt:
+            if n not in self.GRAD_INPUTS:
+                raise ValueError("no gradient with respect to %r (one of %s)" % (n, ", ".join(self.GRAD_INPUTS)))
+            if n == "ring_aromatic" and not m["use_ring"]:
+                raise ValueError("ring_aromatic: the model has no ring input (use_ring is off)")
+            if n == "atomic" and m["feature"] != "cgcnn":
+                raise ValueError("atomic: gradients exist for the cgcnn features only (the atomic numbers are integers)")
+        bs = int(batch_size or self.config["hyper"]["batch_size"])
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        flags = dict(distance="neighbor_distance" in wrt, weight="neighbor_weight" in wrt, ring="ring_aromatic" in wrt,
+                     cgcnn="atomic" in wrt)
+        eng = self.engine
+        parts = []
+        if isinstance(inputs, _hip.PackedBatch):
+            for s0 in range(0, inputs.n_struct, bs):
+                rb = eng.upload(_hip.slice_packed(inputs, s0, min(s0 + bs, inputs.n_struct)))
+                try:
+                    parts.append(eng.input_grads(rb, **flags))
+                finally:
+                    rb.free()
+        else:
+            B = int(np.shape(inputs["neighbors"])[0])
+            for s0 in range(0, B, bs):
+                sl = {k: np.asarray(v)[s0:s0 + bs] for k, v in inputs.items() if k in self.input_names}
+                rb = eng.upload(_hip.pack_inputs(sl))
+                try:
+                    g = eng.input_grads(rb, **flags)
+                finally:
+                    rb.free()
+                amask, nmask = sl["atom_mask"], sl["neighbor_mask"]
+                for n in ("neighbor_distance", "neighbor_weight"):
+                    if n in g:
+                        g[n] = _hip.repad_edges(g[n], amask, nmask)
+                for n in ("ring_aromatic", "atomic"):
+                    if n in g:
+                        g[n] = _hip.repad_atoms(g[n], amask)
+                parts.append(g)
+        out = {n: np.concatenate([p[n] for p in parts]) for n in wrt}
+        out["predict_property"] = np.concatenate([p["y"] for p in parts]).reshape(-1, 1)
+        return out
+
     BIG_PREDICT = 1024   # structures from which `predict(padded arrays)` runs as a pipeline of chunks
     PREDICT_CHUNK = 2048  # structures per chunk: one launch sequence each (16 batches of the reference's 128)
     BIG_SLOTS = 6_000_000  # ... or padded neighbour slots (a launch sequence takes < 8,388,608 atoms / edges: few but large crystals)
@@ -612,6 +666,15 @@ class SCANN:
             np.save("{}/hist_data.npy".format(self._out_dir()), np.array([y_predict, y, self.hist.history], dtype=object))
             print("Saved model record for dataset")
         return mae, r2
+
+    def input_gradients(self, ip, wrt=("neighbor_distance", "neighbor_weight"), batch_size=None):
+        """HipModel.input_gradients in the units of the target: gradients scaled by the target's std and the prediction
+        de-normalised, as predict_data does."""
+        out = self.model.input_gradients(ip, wrt=wrt, batch_size=batch_size)
+        y = out.pop("predict_property")
+        res = {k: v * self.std for k, v in out.items()}
+        res["predict_property"] = y * self.std + self.mean
+        return res
 
     def predict_data(self, ip):
         out = self.model.predict(ip)
