@@ -278,6 +278,23 @@ int scann_get_weights(scann_handle_t* h, float* out);         /* current master 
  * d_ring[n_atom*2] (use_ring), d_cgcnn[n_atom*92] (feature cgcnn; otherwise SCANN_ERR_INVALID if non-NULL). */
 int scann_input_grads(scann_handle_t* h, scann_dbatch_t* db, float* y, float* d_distance, float* d_weight,
                       float* d_ring, float* d_cgcnn);
+
+/* ---- Monte Carlo dropout ----
+ * n_samples forwards of a resident batch with the model's Dropout layers active -- Keras' model(x, training=True) -- reduced on the
+ * device to the mean and the unbiased standard deviation (divided by T - 1; fp64 sums over the samples in order) of y and, if asked
+ * for, of the GlobalAttention scores.  The masks of sample t of structure s are drop_scale(mc_seed(seed, t, key_s), tag, i, p) with the
+ * training forward's tags and a structure-local element index (scann_mc_drop_scale), so a structure's samples do not depend on its
+ * batch: two identical structures with the same key get identical samples.  keys: [n_struct] or NULL (all 0).  p_drop: the two
+ * Dropout(0.1) layers (< 0: 0.1); p_attn: the attention-weight Dropout of use_drop models (< 0: the rate of scann_set_attention_dropout,
+ * 0 unless set); a rate outside [0, 1) or n_samples < 2 is SCANN_ERR_INVALID.  Both rates 0: every sample is the plain forward's y.
+ * Outputs: y_mean, y_std [n_struct]; ga_mean, ga_std [n_atom] (NULL: not computed); y_samples [n_samples * n_struct] (NULL: not copied).
+ * Works on inference and training handles and changes neither (weights, gradients, Adam state, step counter, selected outputs, the
+ * batch's last y).  SCANN_ERR_UNSUPPORTED on a handle whose forwards run on the exact-fp32 kernels (|w| >= 255.9, SCANN_EXACT=1), and
+ * SCANN_ERR_RANGE when a sample trips the split-fp16 range guard; either before any output is written.  Synchronous. */
+int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, uint64_t seed, const uint64_t* keys, float p_drop, float p_attn,
+                     float* y_mean, float* y_std, float* ga_mean, float* ga_std, float* y_samples);
+/* the Monte Carlo dropout factor of one element: 0 or 1 / (1 - p) (host; the kernels' definition) */
+double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag, uint64_t idx, float p);
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -2,7 +2,10 @@
 """CLI with the reference's interface (predict_model.py:95-100): load ``<trained_model>/config.yaml`` and
 ``<trained_model>/models/model_<target>.h5`` in infer mode, predict the whole dataset, pickle GA scores and
 predictions next to the model.  ``--outputs after_Lc,local_attention_2,bf_property`` also pickles each named output as
-``<name>_<target>.pickle``: one array per structure, laid out as the padded predict of its batch returns it."""
+``<name>_<target>.pickle``: one array per structure, laid out as the padded predict of its batch returns it.
+``--mc-samples T [--mc-seed S]`` also pickles Monte Carlo dropout estimates as ``mc_<target>.pickle``: a dict with the de-normalised
+mean and standard deviation of the prediction per structure and the mean and standard deviation of its GA scores (one [M, 1] array
+per structure, as ga_scores), each structure keyed by its index in the dataset."""
 import argparse
 import os
 import pickle
@@ -52,11 +55,30 @@ def main(args):
     pickle.dump([y, struct_energy], open(os.path.join(args.trained_model, "energy_pre_{}.pickle".format(target)), "wb"))
     for n in names:
         pickle.dump(extra[n], open(os.path.join(args.trained_model, "{}_{}.pickle".format(n, target)), "wb"))
+    if args.mc_samples:
+        print("Monte Carlo dropout: %d samples per structure" % args.mc_samples)
+        mc = {"mean": [], "std": [], "ga_mean": [], "ga_std": []}
+        for b in range(len(data)):
+            inputs, _ = data[b]
+            sel = data.indexes[b * data.batch_size:(b + 1) * data.batch_size]
+            r = scann.predict_uncertainty(inputs, samples=args.mc_samples, seed=args.mc_seed, keys=sel)
+            mc["mean"] += list(r["predict_property"][:, 0])
+            mc["std"] += list(r["predict_property_std"][:, 0])
+            mc["ga_mean"] += list(r["global_attention"])
+            mc["ga_std"] += list(r["global_attention_std"])
+        pickle.dump(mc, open(os.path.join(args.trained_model, "mc_{}.pickle".format(target)), "wb"))
 
 
-if __name__ == "__main__":
+def parser():
     p = argparse.ArgumentParser()
     p.add_argument("trained_model", type=str, help="Target trained model path for loading")
     p.add_argument("--outputs", type=str, default="",
                    help="comma-separated outputs to pickle as well: local_attention_<k>, after_Lc, bf_property")
-    main(p.parse_args())
+    p.add_argument("--mc-samples", type=int, default=0,
+                   help="Monte Carlo dropout samples per structure (>= 2; 0: none): pickles mc_<target>.pickle")
+    p.add_argument("--mc-seed", type=int, default=0, help="seed of the Monte Carlo dropout masks")
+    return p
+
+
+if __name__ == "__main__":
+    main(parser().parse_args())

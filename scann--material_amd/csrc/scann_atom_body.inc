@@ -1,7 +1,7 @@
-// The body of atom_kernel<FFN, MODE, RT, EX, KEEP, ZOUT> (scann_kernels.hip) as text (a file of its own like scann_edge_body.inc; round 4's
+// The body of atom_kernel<FFN, MODE, RT, EX, KEEP, ZOUT, MC> (scann_kernels.hip) as text (a file of its own like scann_edge_body.inc; round 4's
 // layer launches included both).
 // Expects in scope: FFN, MODE, RT, EX, KEEP (training forward: Dropout and the keep_* stores exist), ZOUT (mode 2, inference outputs:
-// after_Lc is stored), TAR; `a` (AtomArgs); LDS sTile [2 TAR PLANE_STRIDE halfs], sRed [TAR 8], sPar [7 D];
+// after_Lc is stored), MC (Monte Carlo dropout: the Dropout layers with structure-local masks, scann_predict_mc), TAR; `a` (AtomArgs); LDS sTile [2 TAR PLANE_STRIDE halfs], sRed [TAR 8], sPar [7 D];
 // SCANN_ATOM_BIX = the atom tile of this workgroup.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 31, lh = lane >> 5, cbase = 32 * wave + 4 * lh;
@@ -43,10 +43,14 @@
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int row = lrow + 32 * rt;
+    unsigned long long mcs = 0;  // MC: this row's structure seed and the structure-local index of its first element
+    size_t mce = 0;
+    if constexpr (MC && !FFN) mc_row_key(a, row0 + min(row, nrows - 1), mcs, mce);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float4 v = xr[rt][j];
       if (!FFN) {
+        if constexpr (MC) v = mc_drop4(mcs, a.drop_tag, mce + cbase + 8 * j, a.drop_p, v);  // Monte Carlo dropout after dense_embed
         if (KEEP && a.drop_p > 0.f) {  // training: Dropout after dense_embed (scann_model.py:374)
           const size_t e = (size_t)(row0 + min(row, nrows - 1)) * D + cbase + 8 * j;
           v.x *= drop_scale(a.drop_seed, a.drop_tag, e, a.drop_p);
@@ -59,6 +63,22 @@
       xr[rt][j] = v;
       if constexpr (KEEP) tile_store<EX, TAR>(sTile, row, cbase + 8 * j, v);  // (training instantiations: round 5's stores -- at their register limit the paired form spills)
       else if (j & 1) tile_store2<EX, TAR>(sTile, row, cbase + 8 * (j - 1), xr[rt][j - 1], v);
+    }
+  }
+  // MC with a ResidualNorm: this lane's 16 keep bits per row, hashed here -- beside the accumulators and x of the dropout site the hash's
+  // 64-bit temporaries spill
+  uint32_t mcm[RT] = {};
+  if constexpr (MC && FFN) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      unsigned long long sd;
+      size_t e;
+      mc_row_key(a, row0 + min(lrow + 32 * rt, nrows - 1), sd, e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (drop_scale(sd, a.drop_tag, e + cbase + 8 * j + k, a.drop_p) != 0.f) mcm[rt] |= 1u << (4 * j + k);
     }
   }
   __syncthreads();
@@ -106,6 +126,7 @@
         const float4 bv = *reinterpret_cast<const float4*>(&sPar[D + cbase + 8 * j]);
         float4 y = make_float4(fmaf(acc[rt][4 * j], WINV, bv.x), fmaf(acc[rt][4 * j + 1], WINV, bv.y),
                                fmaf(acc[rt][4 * j + 2], WINV, bv.z), fmaf(acc[rt][4 * j + 3], WINV, bv.w));
+        if constexpr (MC) y = mc_keep4(mcm[rt] >> (4 * j), a.drop_p, y);  // Monte Carlo dropout, attention.py:29
         if (KEEP && a.drop_p > 0.f) {  // attention.py:29 (training)
           const size_t e = (size_t)(row0 + min(row, nrows - 1)) * D + cbase + 8 * j;
           y.x *= drop_scale(a.drop_seed, a.drop_tag, e, a.drop_p);

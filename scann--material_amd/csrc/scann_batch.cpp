@@ -91,9 +91,12 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     const size_t gen_ws_bytes = db->gen_ws_bytes;
     char* const out_block = db->out_block;  // (... and so is the block of the inference outputs)
     const size_t out_cap = db->out_cap;
+    char* const mc_ws = db->mc_ws;  // (... and scann_predict_mc's)
+    const size_t mc_bytes = db->mc_bytes;
     *db = scann_dbatch();
     db->gen_ws = gen_ws; db->gen_ws_bytes = gen_ws_bytes;
     db->out_block = out_block; db->out_cap = out_cap;
+    db->mc_ws = mc_ws; db->mc_bytes = mc_bytes;
     db->owns_arena = false;
   } else {
     db = new scann_dbatch();
@@ -298,6 +301,7 @@ void free_batch(scann_dbatch* db) {
   if (db->arena && db->owns_arena) cached_free(db->arena);
   cached_free(db->gen_ws);
   cached_free(db->out_block);
+  cached_free(db->mc_ws);
   cached_free(db->dbg_c);
   cached_free(db->dbg_g);
   cached_free(db->dbg_ctx);

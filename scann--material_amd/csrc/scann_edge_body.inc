@@ -1,7 +1,8 @@
-// The body of edge_kernel<GUPD, RT, FB, EX, KEEP, DEAD, ATTN> (scann_kernels.hip) as text, in a file of its own (round 4's layer launches included
+// The body of edge_kernel<GUPD, RT, FB, EX, KEEP, DEAD, ATTN, MC> (scann_kernels.hip) as text, in a file of its own (round 4's layer launches included
 // it a second time; as an inlined device function the same body moved hipcc's register allocation of the 168-VGPR kernel: +3.7 %).
 // Expects in scope: GUPD, RT, FB, EX, KEEP (training forward: the keep_* stores and the attention
-// dropout exist), DEAD (geom' is not stored), ATTN (inference outputs: the attention weights are stored), BLK (piece-major geometry
+// dropout exist), DEAD (geom' is not stored), ATTN (inference outputs: the attention weights are stored), MC (Monte Carlo dropout on the
+// attention weights with structure-local masks, scann_predict_mc), BLK (piece-major geometry
 // tiles), TEK; `a` (EdgeArgs); LDS sTile [2 TEK PLANE_STRIDE halfs],
 // sQ [TQ LDS_STRIDE], sE [NHEAD (TEK + 1)] with the index maps SE_STAT(wave, row) / SE_LOGIT(row, head), sPar [5 D], sOff [TQ + 1];
 // SCANN_EDGE_TIX = the edge tile of this workgroup.
@@ -442,6 +443,13 @@
     const int lgp = tid >> 5, c4 = tid & 31, h = c4 >> 2;
     for (int la = lgp; la < natom; la += 8) {
       const int e0 = sOff[la], e1 = sOff[la + 1];
+      unsigned long long mcs = 0;  // MC: the atom's structure seed, and its first edge's structure-local index minus the tile's first edge
+      size_t mce = 0;
+      if constexpr (MC) {
+        const McRow mr = a.mc_rows[tile.atom_begin + la];
+        mcs = mc_seed(a.attn_drop_seed, a.mc_t, mr.key);
+        mce = (size_t)(eb - mr.e0);
+      }
       // row maximum first (logits only), then one exp per edge: no running-maximum rescaling in the accumulation loop
       float m = -INFINITY;
       for (int n = e0; n < e1; n += 4) {
@@ -461,6 +469,10 @@
         if (KEEP && a.attn_drop_p > 0.f) {  // training with use_drop: Dropout(0.05) on the attention weights (attention.py:116,191)
           pa *= drop_scale(a.attn_drop_seed, a.attn_drop_tag, (size_t)(eb + n) * NHEAD + h, a.attn_drop_p);
           pb *= drop_scale(a.attn_drop_seed, a.attn_drop_tag, (size_t)(eb + n1) * NHEAD + h, a.attn_drop_p);
+        }
+        if constexpr (MC) {  // Monte Carlo dropout on the attention weights, structure-local edge index
+          pa *= drop_scale(mcs, a.attn_drop_tag, (mce + n) * NHEAD + h, a.attn_drop_p);
+          pb *= drop_scale(mcs, a.attn_drop_tag, (mce + n1) * NHEAD + h, a.attn_drop_p);
         }
         cx.x = fmaf(pa, ka.x, fmaf(pb, kb.x, cx.x));
         cx.y = fmaf(pa, ka.y, fmaf(pb, kb.y, cx.y));

@@ -111,8 +111,9 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   float *z = take(fA * dg), *gq = take(fA * dg), *gk = take(fA * dg);
   float *G = take(fE * d), *T = nullptr, *K = nullptr, *gd = take(fE * NG), *gw = take(fE * NG);
   if (!kp) { T = take(fE * d); K = take(fE * d); }
-  const float tp = kp ? kp->drop_p : 0.f;
-  const unsigned long long seed = kp ? kp->seed : 0;
+  const McState* mc = kp ? nullptr : h->mc;  // Monte Carlo dropout (scann_predict_mc): structure-local masks
+  const float tp = kp ? kp->drop_p : mc ? mc->p_drop : 0.f;
+  const unsigned long long seed = kp ? kp->seed : mc ? mc->seed : 0;
   auto dense = [&](GenSeg s0, GenSeg s1, GenSeg s2, int n_seg, int prod, const std::string& name, int K_, int N_, int rows, int act,
                    const float* res, const float* row_scale, float* Y, float* pre = nullptr, float drop_p = 0.f, unsigned drop_tag = 0) {
     GenDenseArgs a{};
@@ -120,6 +121,7 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
     a.W = W(name + "/kernel"); a.b = W(name + "/bias"); a.K = K_; a.N = N_; a.rows = rows; a.act = act;
     a.res = res; a.res_idx = nullptr; a.row_scale = row_scale; a.Y = Y;
     a.pre = pre; a.drop_p = drop_p; a.drop_tag = drop_tag; a.drop_seed = seed;
+    if (mc) { a.mc_rows = mc->rows; a.mc_t = mc->t; }
     launch_gen_dense(a, s);
   };
   const GenSeg none{nullptr, nullptr, 0};
@@ -173,8 +175,11 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
     }
     dense(GenSeg{cc, db->edge_col, d}, GenSeg{b.Gn, nullptr, d}, none, 2, 1, la + "/key", d, d, E, 0, nullptr, nullptr, b.K);
     dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, la + "/query", d, d, A, 0, nullptr, nullptr, b.q);
-    launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed,
-                    kp ? nullptr : attn_out_of(h, db, l));
+    if (mc && mc->p_attn > 0.f)
+      launch_gen_attn_mc(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, mc->p_attn, DROP_TAG_ATTN + (unsigned)l, seed, mc->rows, mc->t);
+    else
+      launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed,
+                      kp ? nullptr : attn_out_of(h, db, l));
     launch_gen_layernorm(b.t1, nullptr, W(la + "/layer_norm/gamma"), W(la + "/layer_norm/beta"), A, d, b.ctx, s);
     if (c.use_attn_norm) {  // ResidualNorm (attention.py:37-40): LayerNorm(x + Dropout(dense_2(swish(dense_1 x))))
       dense(GenSeg{b.ctx, nullptr, d}, none, none, 1, 0, rn + "/dense_1", d, d, A, 1, nullptr, nullptr, b.h1, b.pre1);
@@ -261,7 +266,10 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   // the atom / edge kernels -- exact-fp32 projections -- with the plain first layer (basis_kernel, no per-species tables)
   // inference: the first layer's edge kernel computes its geometry rows from (dist, weight) itself -- geom0 is never written by a
   // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
-  const bool fuse_basis = !exact && h->fuse_basis && c.g_update && L > 0 && !h->debug && !h->in_train_forward && db->n_edge > 0;
+  // Monte Carlo dropout (scann_predict_mc, never exact): the sample's masks at the training forward's Dropout sites, on the MC instantiations
+  // (the piece-major family: the fused first layer whatever SCANN_FUSE_BASIS says)
+  const McState* mc = h->in_train_forward ? nullptr : h->mc;
+  const bool fuse_basis = !exact && (h->fuse_basis || mc) && c.g_update && L > 0 && !h->debug && !h->in_train_forward && db->n_edge > 0;
   // the attention-weight stores exist in the piece-major g_update kernels (and the row-major base / exact ones) only
   if (db->out_layers && c.g_update && !exact && !fuse_basis && db->n_edge > 0) {
     db->out_layers = db->out_flags = 0;
@@ -284,7 +292,8 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   }
   // first layer from per-species tables: no atom launch at all (see EdgeArgs::species)
   // (not with chunked atoms: edge_merge_kernel reads the query rows per atom)
-  const bool species0 = fuse_basis && h->species_tables && !general_embed && h->train_drop_p == 0.f && h->sp_c && db->n_big == 0;
+  const bool species0 = fuse_basis && h->species_tables && !general_embed && h->train_drop_p == 0.f && !(mc && mc->p_drop > 0.f) && h->sp_c &&
+                        db->n_big == 0;
   if (species0 && h->sp_dirty) {
     AtomArgs a{};
     a.n_atom = c.n_atoms; a.x = h->lut; a.ffn = 0; a.c = h->sp_c;
@@ -324,6 +333,13 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
       a.drop_p = (l == 0 || c.use_attn_norm) ? h->train_drop_p : 0.f;
       a.drop_seed = h->train_seed;
       a.drop_tag = l == 0 ? DROP_TAG_EMBED : (unsigned)(l - 1);
+    }
+    if (mc && mc->p_drop > 0.f && (l == 0 || c.use_attn_norm)) {  // the same sites and tags, structure-local masks
+      a.drop_p = mc->p_drop;
+      a.drop_seed = mc->seed;
+      a.drop_tag = l == 0 ? DROP_TAG_EMBED : (unsigned)(l - 1);
+      a.mc_rows = mc->rows;
+      a.mc_t = mc->t;
     }
     if (l < L) {
       const LayerParams& p = h->layers[l];
@@ -390,7 +406,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     // (the first layer's launch with the basis MLP fused in is a different kernel: not part of edge_kernel's sampled average)
     // (... nor is the last layer's, whose geometry is not stored -- the DEAD instantiation, ~10 % shorter: the sampled average is the
     //  kernel rocprofv3 lists as edge_kernel<true, RT, false, false, false, false>, and its algorithmic bytes include that store)
-    const bool sample = !tm && h->time_every > 0 && (h->time_count % h->time_every) == 0 && !(fuse_basis && l == 0) && !(ea.geom_dead && L > 2);
+    const bool sample = !tm && !mc && h->time_every > 0 && (h->time_count % h->time_every) == 0 && !(fuse_basis && l == 0) && !(ea.geom_dead && L > 2);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (sample) {
       (void)hipEventCreateWithFlags(&ev0, kTimingEventFlags);
@@ -404,6 +420,13 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
       ea.attn_drop_p = h->attn_drop_p;
       ea.attn_drop_seed = h->train_seed;
       ea.attn_drop_tag = DROP_TAG_ATTN + (unsigned)l;
+    }
+    if (mc && mc->p_attn > 0.f && db->n_edge > 0) {
+      ea.attn_drop_p = mc->p_attn;
+      ea.attn_drop_seed = mc->seed;
+      ea.attn_drop_tag = DROP_TAG_ATTN + (unsigned)l;
+      ea.mc_rows = mc->rows;
+      ea.mc_t = mc->t;
     }
 #ifdef SCANN_STAMPS
     if (!getenv("SCANN_STAMP_ATOM") && l == (getenv("SCANN_STAMP_LAYER") ? atoi(getenv("SCANN_STAMP_LAYER")) : L - 1)) {  // one launch's picture
@@ -423,7 +446,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     }
     if (tm) tm->mark(2);
   }
-  if (!tm) h->time_count++;
+  if (!tm && !mc) h->time_count++;
   ReadoutArgs r{};
   r.mol_offset = db->mol_offset; r.n_struct = db->n_struct; r.max_atoms = db->max_atoms;
   r.gq = db->gq; r.gk = db->gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = c.relu_out;
@@ -584,6 +607,98 @@ int64_t scann_output_read(scann_handle_t* h, scann_dbatch_t* db, int32_t what, i
   const float* src = what == SCANN_OUT_LOCAL_ATTENTION ? attn_out_of(h, db, layer) : what == SCANN_OUT_AFTER_LC ? db->out_z : db->out_bf;
   if (n && src) HIPCHK(h, hipMemcpy(out, src, (size_t)n * 4, hipMemcpyDeviceToHost));
   return n;
+}
+
+double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag, uint64_t idx, float p) {
+  return drop_scale(mc_seed(seed, (unsigned)t, key), tag, (size_t)idx, p);
+}
+
+// Monte Carlo dropout: n_samples inference forwards of the resident batch, each with the Dropout layers of the training graph active under
+// structure-local masks (scann_internal.h: mc_seed), y and the GlobalAttention scores of sample t written to row t of [T, B] / [T, n_atom]
+// buffers in the batch's workspace, and one reduction per output.  Saves and restores whatever of the handle and the batch a forward
+// touches (selected outputs, debug mode, edge timing, y / ga), so that later forwards and downloads see what they would have seen.
+int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, uint64_t seed, const uint64_t* keys, float p_drop, float p_attn,
+                     float* y_mean, float* y_std, float* ga_mean, float* ga_std, float* y_samples) {
+  if (!h || !db || !y_mean || !y_std) return fail(h, SCANN_ERR_INVALID, "scann_predict_mc: null argument");
+  if (n_samples < 2) return fail(h, SCANN_ERR_INVALID, "scann_predict_mc: n_samples must be >= 2 (the standard deviation divides by T - 1)");
+  if (p_drop < 0.f) p_drop = 0.1f;  // Dropout(0.1), scann_model.py:374 and attention.py:29
+  if (p_attn < 0.f) p_attn = h->attn_drop_p;
+  if (!(p_drop < 1.f) || !(p_attn < 1.f)) return fail(h, SCANN_ERR_INVALID, "scann_predict_mc: dropout rates must lie in [0, 1)");
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_predict_mc: weights not loaded");
+  if (!h->generic && (h->weights_exact || h->force_exact))
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_predict_mc: this handle's forwards run on the exact-fp32 kernels (a 128x128 kernel with |w| >= 255.9, "
+                                          "or SCANN_EXACT=1), which have no dropout instantiations");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int T = n_samples, A = db->n_atom, B = db->n_struct;
+  const int slot = db->last_slot;  // behind whatever was last enqueued on the batch
+  hipStream_t s = h->streams[slot];
+  // workspace: rows [A], keys [B], y samples [T, B], ga samples [T, A], means / stds [2 B + 2 A]
+  const size_t bR = align_up((size_t)std::max(A, 1) * sizeof(McRow)), bK = align_up((size_t)std::max(B, 1) * 8),
+               bY = align_up((size_t)T * B * 4), bG = align_up((size_t)T * A * 4), bO = align_up((size_t)(2 * B + 2 * A + 1) * 4);
+  const size_t need = bR + bK + bY + bG + bO;
+  if (db->mc_bytes < need) {
+    HIPCHK(h, hipStreamSynchronize(s));
+    cached_free(db->mc_ws);
+    db->mc_ws = nullptr;
+    db->mc_bytes = 0;
+    HIPCHK(h, cached_malloc((void**)&db->mc_ws, need));
+    db->mc_bytes = need;
+  }
+  char* p = db->mc_ws;
+  McRow* rows = reinterpret_cast<McRow*>(p);
+  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(p + bR);
+  float* ys = reinterpret_cast<float*>(p + bR + bK);
+  float* gs = reinterpret_cast<float*>(p + bR + bK + bY);
+  float* outs = reinterpret_cast<float*>(p + bR + bK + bY + bG);
+  float *o_ym = outs, *o_ys = outs + B, *o_gm = outs + 2 * B, *o_gs = outs + 2 * B + A;
+  HIPCHK(h, wait_upload(db, s));
+  if (keys && B > 0) HIPCHK(h, hipMemcpyAsync(d_keys, keys, (size_t)B * 8, hipMemcpyHostToDevice, s));
+  launch_mc_rows(db->mol_offset, db->edge_offset, keys ? d_keys : nullptr, B, A, rows, s);
+  // what a forward of this call would otherwise change
+  const uint64_t h_out_layers = h->out_layers, d_out_layers = db->out_layers;
+  const int32_t h_out_flags = h->out_flags, d_out_flags = db->out_flags;
+  float *const d_out_attn = db->out_attn, *const d_out_z = db->out_z, *const d_out_bf = db->out_bf;
+  const bool debug = h->debug;
+  float *const y0 = db->y, *const ga0 = db->ga;
+  h->out_layers = 0;
+  h->out_flags = 0;
+  h->debug = false;
+  McState mc{rows, (unsigned long long)seed, 0u, p_drop, p_attn};
+  h->mc = &mc;
+  int r = SCANN_OK;
+  for (int t = 0; t < T && r == SCANN_OK; ++t) {
+    mc.t = (uint32_t)t;
+    db->y = ys + (size_t)t * B;
+    db->ga = gs + (size_t)t * A;
+    r = run_forward(h, db, s, nullptr);
+  }
+  h->mc = nullptr;
+  db->y = y0;
+  db->ga = ga0;
+  h->out_layers = h_out_layers;
+  h->out_flags = h_out_flags;
+  db->out_layers = d_out_layers;
+  db->out_flags = d_out_flags;
+  db->out_attn = d_out_attn; db->out_z = d_out_z; db->out_bf = d_out_bf;
+  h->debug = debug;
+  if (r == SCANN_OK) {
+    launch_mc_reduce(ys, T, B, o_ym, o_ys, s);
+    if (ga_mean || ga_std) launch_mc_reduce(gs, T, A, o_gm, o_gs, s);
+  }
+  const hipError_t se = hipStreamSynchronize(s);
+  if (r) return r;
+  HIPCHK(h, se);
+  HIPCHK(h, hipGetLastError());
+  if ((r = check_range(h, "scann_predict_mc", slot))) return r;
+  if ((r = check_pack_flag(h, db, "scann_predict_mc"))) return r;
+  if (B > 0) {
+    HIPCHK(h, hipMemcpy(y_mean, o_ym, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(y_std, o_ys, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (y_samples) HIPCHK(h, hipMemcpy(y_samples, ys, (size_t)T * B * 4, hipMemcpyDeviceToHost));
+  }
+  if (A > 0 && ga_mean) HIPCHK(h, hipMemcpy(ga_mean, o_gm, (size_t)A * 4, hipMemcpyDeviceToHost));
+  if (A > 0 && ga_std) HIPCHK(h, hipMemcpy(ga_std, o_gs, (size_t)A * 4, hipMemcpyDeviceToHost));
+  return SCANN_OK;
 }
 
 }  // extern "C"

@@ -23,7 +23,8 @@ namespace {
 // GR rows per workgroup: every weight element fetched serves GR rows (8 while the staged rows fit 48 KB of LDS, else 4).  A thread
 // owns RPT of them for one output column at a time, so that narrow layers (N <= 128, <= 64) still use all 256 threads: the workgroup
 // covers 256 / (GR / RPT) columns per pass.  A row's sum over k is the same sequence in every shape (four interleaved partial sums).
-template <int GR, int RPT>
+// MC: Monte Carlo dropout on the layer's output with structure-local masks (scann_predict_mc: rows are atoms, a.mc_rows their structures)
+template <int GR, int RPT, bool MC = false>
 __global__ __launch_bounds__(256) void gen_dense_kernel(GenDenseArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ float sX[];  // [GR][Ks], Ks = K rounded up to 4: 16-byte fragment reads
@@ -114,7 +115,11 @@ __global__ __launch_bounds__(256) void gen_dense_kernel(GenDenseArgs a) {
       float y = (float)(acc[rr] + bias);
       if (a.pre) a.pre[(size_t)r * a.N + o] = y;  // training forward: the pre-activation the backward differentiates swish at
       if (a.act) y = swish_exact(y);
-      if (a.drop_p > 0.f) y = y * drop_scale(a.drop_seed, a.drop_tag, (size_t)r * a.N + o, a.drop_p);  // Dropout on the layer's OUTPUT
+      if (!MC && a.drop_p > 0.f) y = y * drop_scale(a.drop_seed, a.drop_tag, (size_t)r * a.N + o, a.drop_p);  // Dropout on the layer's OUTPUT
+      if constexpr (MC) {
+        const McRow m = a.mc_rows[r];
+        y = y * drop_scale(mc_seed(a.drop_seed, a.mc_t, m.key), a.drop_tag, (size_t)(r - m.a0) * a.N + o, a.drop_p);
+      }
       if (a.res) y = y + a.res[(size_t)(a.res_idx ? a.res_idx[r] : r) * a.N + o];
       if (a.row_scale) y = y * a.row_scale[r];
       a.Y[(size_t)r * a.N + o] = y;
@@ -169,9 +174,12 @@ __global__ void gen_mul_kernel(const float* __restrict__ a, const float* __restr
 
 // one workgroup per atom.  logits[n][h] = (q[h] * hd^-0.5) . K[n][h] over the atom's CSR row, softmax over n per head, context[o] =
 // sum_n attn[n][head(o)] K[n][o] + q[o] (the residual is the UNSCALED query, attention.py:198-212).  No edges: context = q.
+// MC: Monte Carlo dropout on the attention weights with structure-local masks (scann_predict_mc)
+template <bool MC = false>
 __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__ q, const float* __restrict__ K, const int32_t* __restrict__ edge_offset,
                                                        int n_atom, int d, int H, float* __restrict__ ctx, float drop_p, unsigned drop_tag,
-                                                       unsigned long long drop_seed, float* __restrict__ attn_out) {
+                                                       unsigned long long drop_seed, float* __restrict__ attn_out, const McRow* __restrict__ mc_rows,
+                                                       uint32_t mc_t) {
 #pragma clang fp contract(off)
   extern __shared__ float sL[];  // [deg][H] logits -> attention
   const int at = blockIdx.x, tid = threadIdx.x;
@@ -186,6 +194,12 @@ __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__
     sL[i] = s;
   }
   __syncthreads();
+  McRow mrow{};
+  unsigned long long mseed = 0;
+  if constexpr (MC) {
+    mrow = mc_rows[at];
+    mseed = mc_seed(drop_seed, mc_t, mrow.key);
+  }
   for (int h = tid; h < H; h += 256) {
     float m = -INFINITY;
     for (int n = 0; n < deg; ++n) m = fmaxf(m, sL[n * H + h]);
@@ -198,7 +212,8 @@ __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__
     for (int n = 0; n < deg; ++n) {
       float at = sL[n * H + h] / ss;
       if (attn_out) attn_out[(size_t)(e0 + n) * H + h] = at;  // inference outputs: the attention weights (attention.py:189)
-      if (drop_p > 0.f) at = at * drop_scale(drop_seed, drop_tag, (size_t)(e0 + n) * H + h, drop_p);  // Dropout(0.05), attention.py:191 (training)
+      if (!MC && drop_p > 0.f) at = at * drop_scale(drop_seed, drop_tag, (size_t)(e0 + n) * H + h, drop_p);  // Dropout(0.05), attention.py:191 (training)
+      if constexpr (MC) at = at * drop_scale(mseed, drop_tag, (size_t)(e0 + n - mrow.e0) * H + h, drop_p);
       sL[n * H + h] = at;
     }
   }
@@ -305,14 +320,17 @@ void launch_gen_dense(const GenDenseArgs& a, hipStream_t s) {
   const int ngrp = a.N <= 64 ? 4 : a.N <= 128 ? 2 : 1;  // row groups side by side: 256 / ngrp columns per pass
   const dim3 grid((a.rows + gr - 1) / gr), block(256);
   const size_t lds = gr * Ks * sizeof(float);
-#define SCANN_GEN_CASE(GR_)                                                                     \
-  do {                                                                                          \
-    if (ngrp == 4) hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_ / 4>), grid, block, lds, s, a);  \
-    else if (ngrp == 2) hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_ / 2>), grid, block, lds, s, a); \
-    else hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_>), grid, block, lds, s, a);               \
+#define SCANN_GEN_CASE(GR_, MC_)                                                                         \
+  do {                                                                                                    \
+    if (ngrp == 4) hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_ / 4, MC_>), grid, block, lds, s, a);     \
+    else if (ngrp == 2) hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_ / 2, MC_>), grid, block, lds, s, a); \
+    else hipLaunchKernelGGL((gen_dense_kernel<GR_, GR_, MC_>), grid, block, lds, s, a);                  \
   } while (0)
-  if (gr == 8) SCANN_GEN_CASE(8);
-  else SCANN_GEN_CASE(4);
+  if (a.mc_rows && a.drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc)
+    if (gr == 8) SCANN_GEN_CASE(8, true);
+    else SCANN_GEN_CASE(4, true);
+  } else if (gr == 8) SCANN_GEN_CASE(8, false);
+  else SCANN_GEN_CASE(4, false);
 #undef SCANN_GEN_CASE
 }
 void launch_gen_layernorm(const float* X, const float* res, const float* gamma, const float* beta, int rows, int N, float* Y, hipStream_t s) {
@@ -330,8 +348,14 @@ void launch_gen_mul(const float* a, const float* b, size_t n, float* out, hipStr
 void launch_gen_attn(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
                      float drop_p, unsigned drop_tag, unsigned long long drop_seed, float* attn_out) {
   if (n_atom <= 0) return;
-  hipLaunchKernelGGL(gen_attn_kernel, dim3(n_atom), dim3(256), (size_t)std::max(1, max_degree) * H * sizeof(float), s, q, K, edge_offset, n_atom, d, H, ctx,
-                     drop_p, drop_tag, drop_seed, attn_out);
+  hipLaunchKernelGGL(gen_attn_kernel<false>, dim3(n_atom), dim3(256), (size_t)std::max(1, max_degree) * H * sizeof(float), s, q, K, edge_offset, n_atom, d, H, ctx,
+                     drop_p, drop_tag, drop_seed, attn_out, nullptr, 0u);
+}
+void launch_gen_attn_mc(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
+                        float drop_p, unsigned drop_tag, unsigned long long drop_seed, const McRow* mc_rows, uint32_t mc_t) {
+  if (n_atom <= 0) return;
+  hipLaunchKernelGGL(gen_attn_kernel<true>, dim3(n_atom), dim3(256), (size_t)std::max(1, max_degree) * H * sizeof(float), s, q, K, edge_offset, n_atom, d, H, ctx,
+                     drop_p, drop_tag, drop_seed, nullptr, mc_rows, mc_t);
 }
 void launch_gen_readout(const int32_t* mol_offset, int n_struct, int max_atoms, const float* gq, const float* gk, int dg, int dout, int use_ga_norm,
                         int relu_out, const float* Wb, const float* bb, const float* wo, const float* bo, float* ga_attn, float* y, hipStream_t s,

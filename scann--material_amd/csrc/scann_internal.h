@@ -31,6 +31,23 @@ __host__ __device__ inline float drop_scale(unsigned long long seed, unsigned ta
   const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
   return u < p ? 0.f : 1.0f / (1.0f - p);
 }
+// Monte Carlo dropout (scann_predict_mc): the masks of sample t of structure s are drop_scale(mc_seed(seed, t, key_s), tag, i, p) with the
+// training forward's tags and an element index i LOCAL to the structure -- (atom - first atom) * local_dim + column for the two Dropout(0.1)
+// layers, (edge - first edge) * num_head + head for the attention weights -- so that a structure's samples do not depend on its batch.
+__host__ __device__ inline unsigned long long mc_mix(unsigned long long z) {  // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline unsigned long long mc_seed(unsigned long long seed, unsigned t, unsigned long long key) {
+  return mc_mix(mc_mix(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)t + 1)) + 0x9E3779B97F4A7C15ull * (key + 1));
+}
+// per atom of an MC batch (launch_mc_rows): the first atom and the first edge of its structure, the structure's key
+struct McRow {
+  int32_t a0, e0;
+  unsigned long long key;
+};
+
 #ifdef __HIPCC__
 // GlobalAttention score of atom i of a structure (attention.py:279-292): sum over j != i of gk_i . gq_j, exact products, fp64 sums, four
 // interleaved partial sums per dot product (shared by the forward and by the pooling backward, which must see the SAME scores)
@@ -169,6 +186,10 @@ struct AtomArgs {
   int32_t exact;
   // mode 2, inference outputs (scann_set_outputs): after_Lc = swish(c Wa + ba) [n_atom,128] is stored here (the ZOUT instantiation), or null
   float* out_z;
+  // Monte Carlo dropout (the MC instantiation, scann_predict_mc): per-atom structure table; the masks are keyed by mc_seed(drop_seed, mc_t,
+  // key) and the structure-local element index.  Null otherwise
+  const McRow* mc_rows;
+  uint32_t mc_t;
 };
 void launch_atom(const AtomArgs& a, hipStream_t s);
 
@@ -219,6 +240,9 @@ struct EdgeArgs {
   // inference outputs (scann_set_outputs): the layer's attention weights (attention.py:189) per (edge, head), [n_edge, NHEAD] (the ATTN
   // instantiation), or null.  A chunk tile stores exp(e - m_chunk) unnormalised; launch_attn_merge finishes those rows
   float* attn_out;
+  // Monte Carlo dropout on the attention weights (the MC instantiation, scann_predict_mc; attn_drop_p > 0): as AtomArgs::mc_rows / mc_t
+  const McRow* mc_rows;
+  uint32_t mc_t;
 };
 void launch_edge(const EdgeArgs& a, hipStream_t s);
 // softmax merge of the chunk tiles of every big atom (+ unscaled-query residual + LayerNorm, attention.py:189-214)
@@ -251,6 +275,9 @@ struct GenDenseArgs {
   float drop_p;
   uint32_t drop_tag;
   unsigned long long drop_seed;
+  // Monte Carlo dropout (scann_predict_mc): structure-local masks keyed by mc_seed(drop_seed, mc_t, key) of the row's atom, null otherwise
+  const McRow* mc_rows;
+  uint32_t mc_t;
 };
 void launch_gen_dense(const GenDenseArgs& a, hipStream_t s);
 void launch_gen_layernorm(const float* X, const float* res, const float* gamma, const float* beta, int rows, int N, float* Y, hipStream_t s);
@@ -259,6 +286,14 @@ void launch_gen_mul(const float* a, const float* b, size_t n, float* out, hipStr
 void launch_gen_attn(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
                      float drop_p = 0.f, unsigned drop_tag = 0, unsigned long long drop_seed = 0, float* attn_out = nullptr);  // attn_out non-null
                      // (inference outputs): the normalised attention weights are stored, [n_edge, H]
+// Monte Carlo dropout on the attention weights (scann_predict_mc): structure-local masks (McRow), drop_p > 0
+void launch_gen_attn_mc(const float* q, const float* K, const int32_t* edge_offset, int n_atom, int d, int H, int max_degree, float* ctx, hipStream_t s,
+                        float drop_p, unsigned drop_tag, unsigned long long drop_seed, const McRow* mc_rows, uint32_t mc_t);
+// scann_predict_mc: rows[a] for every atom from the structure offsets and the per-structure keys (null: all 0)
+void launch_mc_rows(const int32_t* mol_offset, const int32_t* edge_offset, const unsigned long long* keys, int n_struct, int n_atom, McRow* rows,
+                    hipStream_t s);
+// scann_predict_mc: per column j of a [T, n] sample matrix, the mean and the unbiased standard deviation (fp64, samples summed in order)
+void launch_mc_reduce(const float* samples, int T, int n, float* mean, float* std_out, hipStream_t s);
 // rep_out non-null (training forward): the pooled rows [n_struct, dg] are stored and the property head is NOT evaluated;
 // bf_out non-null (inference outputs): bf_property [n_struct, dout] is stored
 void launch_gen_readout(const int32_t* mol_offset, int n_struct, int max_atoms, const float* gq, const float* gk, int dg, int dout, int use_ga_norm,

@@ -44,11 +44,37 @@ namespace scann {
 // query-only kernel at 32 rows; tests/test_host.py reads scratch sizes and register counts from the built library)
 // ZOUT: mode 2 of an inference forward that returns after_Lc (scann_set_outputs): z is stored to out_z as the training forward stores
 // keep_z (a compile-time flag: a branch around a store in these kernels has cost a spill before, tests/test_host.py)
-template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false, bool ZOUT = false>
+// MC: Monte Carlo dropout of an inference forward (scann_predict_mc) -- the Dropout(0.1) of the staged rows (!FFN: after dense_embed) or of
+// the ResidualNorm branch (FFN) applied unconditionally, with structure-local masks (scann_internal.h: mc_seed); no keep_* stores
+//
+// MC: the row's structure seed and the structure-local index of its element 0 (McRow of the atom)
+__device__ __forceinline__ void mc_row_key(const AtomArgs& a, int atom, unsigned long long& seed, size_t& e) {
+  const McRow m = a.mc_rows[atom];
+  seed = mc_seed(a.drop_seed, a.mc_t, m.key);
+  e = (size_t)(atom - m.a0) * D;
+}
+__device__ __forceinline__ float4 mc_drop4(unsigned long long seed, unsigned tag, size_t e, float p, float4 v) {
+  v.x *= drop_scale(seed, tag, e, p);
+  v.y *= drop_scale(seed, tag, e + 1, p);
+  v.z *= drop_scale(seed, tag, e + 2, p);
+  v.w *= drop_scale(seed, tag, e + 3, p);
+  return v;
+}
+// MC: the factors of four elements from their keep bits (bit k: element k kept) -- drop_scale's values, 0 or 1 / (1 - p)
+__device__ __forceinline__ float4 mc_keep4(uint32_t bits, float p, float4 v) {
+  const float sc = 1.0f / (1.0f - p);
+  v.x *= (bits & 1u) ? sc : 0.f;
+  v.y *= (bits & 2u) ? sc : 0.f;
+  v.z *= (bits & 4u) ? sc : 0.f;
+  v.w *= (bits & 8u) ? sc : 0.f;
+  return v;
+}
+template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false, bool ZOUT = false, bool MC = false>
 __global__ __launch_bounds__(256, RT == 2 ? (EX ? 2 : 3) : (MODE == 1 ? 3 : 4)) void atom_kernel(AtomArgs a) {
 #pragma clang fp contract(off)  // fusions are written out: both row-tile copies of a formula round alike (see edge_kernel)
   static_assert(!(EX && KEEP), "the training forward runs the split-fp16 kernels");
   static_assert(!ZOUT || (MODE == 2 && !KEEP), "after_Lc is an output of the readout launch of inference forwards");
+  static_assert(!MC || (!EX && !KEEP && !ZOUT), "Monte Carlo dropout runs on the plain split-fp16 inference kernels");
   constexpr int TAR = 32 * RT;  // atom rows per tile
   __shared__ __attribute__((aligned(16))) unsigned char sTile[2 * TAR * PLANE_STRIDE * 2];  // hi / lo planes of the current GEMM input
   __shared__ __attribute__((aligned(16))) float sRed[TAR * 8];  // LayerNorm partial statistics [wave][row][mean, m2]
@@ -73,6 +99,24 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
   //  of atom launches per forward against 0.152-0.157 ms for the 720 32-row tiles: the threshold stays)
   const int rows = a.n_atom <= 32 * 1024 ? 32 : 64;
   const dim3 grid((a.n_atom + rows - 1) / rows), block(256);
+  if (a.mc_rows && a.drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc: never exact, no keep_* tensors, no outputs)
+#define SCANN_ATOM_MC(F, M)                                                                                   \
+  do {                                                                                                        \
+    if (rows == 32) hipLaunchKernelGGL((atom_kernel<F, M, 1, false, false, false, true>), grid, block, 0, s, a); \
+    else hipLaunchKernelGGL((atom_kernel<F, M, 2, false, false, false, true>), grid, block, 0, s, a);           \
+  } while (0)
+    if (a.ffn) {
+      if (a.mode == 0) SCANN_ATOM_MC(true, 0);
+      else if (a.mode == 1) SCANN_ATOM_MC(true, 1);
+      else SCANN_ATOM_MC(true, 2);
+    } else {
+      if (a.mode == 0) SCANN_ATOM_MC(false, 0);
+      else if (a.mode == 1) SCANN_ATOM_MC(false, 1);
+      else SCANN_ATOM_MC(false, 2);
+    }
+#undef SCANN_ATOM_MC
+    return;
+  }
   const bool keep = !a.exact && (a.drop_p > 0.f || a.keep_pre1 || a.keep_T2 || a.keep_preA);  // training forward
   if (a.mode == 2 && a.out_z) {  // inference forward that returns after_Lc (never a training forward: run_forward)
 #define SCANN_ATOM_Z(F)                                                                                        \
@@ -144,7 +188,9 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
 // DEAD: the last layer of an inference forward -- nobody reads geom' (scann_model.py:415-421 threads it to the NEXT layer only).
 // ATTN: an inference forward that returns this layer's attention weights (scann_set_outputs) -- the softmax stores them per (edge,
 // head).  A template flag like KEEP: with it off every instantiation is the code it was.
-template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false, bool ATTN = false>
+// MC: Monte Carlo dropout on the attention weights of an inference forward (scann_predict_mc): Dropout(0.05) applied unconditionally with
+// structure-local masks; the piece-major family (FB, plain, DEAD) and the base branch's row-major kernel, no keep_* stores
+template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false, bool ATTN = false, bool MC = false>
 __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) {
 #pragma clang fp contract(off)  // fusions are written out (fmaf): both unrolled row-tile copies of a formula must round alike,
                                 // so that a row's result does not depend on where in a tile it lands (batch-composition invariance)
@@ -153,6 +199,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
   static_assert(!KEEP || (!FB && !EX && !DEAD), "the training forward runs the plain split-fp16 kernel and keeps every layer's geometry");
   static_assert(!DEAD || GUPD, "the base branch stores no geometry");
   static_assert(!(ATTN && KEEP), "the training forward returns no attention weights");
+  static_assert(!MC || (!EX && !KEEP && !ATTN), "Monte Carlo dropout runs on the split-fp16 inference kernels and returns no attention weights");
   constexpr int TEK = 32 * RT;  // edge rows per tile: 64 (three workgroups per CU) or, for launches of one round, 32 (four)
   // piece-major geometry tiles (scann_edge_body.inc): the inference kernels, whose geometry nobody else reads.  The training / debug
   // forward (KEEP) and the exact re-run (EX: its first layer reads basis_kernel's row-major geom0) keep [n_edge,128] rows.
@@ -315,7 +362,12 @@ void launch_edge(const EdgeArgs& a, hipStream_t s) {
     if (a.tile_rows == 32) SCANN_EDGE_GO(G, 1, __VA_ARGS__);                \
     else SCANN_EDGE_GO(G, 2, __VA_ARGS__);                                  \
   } while (0)
-  if (a.exact && a.attn_out) {  // (the exact re-run of a forward that returns attention weights returns the re-run's)
+  if (a.mc_rows && a.attn_drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc; g_update: the piece-major family, run_forward)
+    if (!a.g_update) SCANN_EDGE_ROWS(false, false, false, false, false, false, true);
+    else if (a.fuse_basis) SCANN_EDGE_ROWS(true, true, false, false, false, false, true);
+    else if (a.geom_dead) SCANN_EDGE_ROWS(true, false, false, false, true, false, true);
+    else SCANN_EDGE_ROWS(true, false, false, false, false, false, true);
+  } else if (a.exact && a.attn_out) {  // (the exact re-run of a forward that returns attention weights returns the re-run's)
     if (!a.g_update) SCANN_EDGE_ROWS(false, false, true, false, false, true);
     else if (dead) SCANN_EDGE_ROWS(true, false, true, false, true, true);
     else SCANN_EDGE_ROWS(true, false, true, false, false, true);

@@ -88,6 +88,14 @@ struct scann_train_ws {  // per resident batch (scann_dbatch::train), allocated 
 
 struct Timer;  // scann_forward_profile's launch timer (scann_forward.cpp)
 
+// scann_predict_mc: the sample run_forward is computing (scann_handle::mc, set for the duration of the call)
+struct McState {
+  const McRow* rows;        // [n_atom] of the batch (launch_mc_rows)
+  unsigned long long seed;  // the call's seed
+  uint32_t t;               // sample index
+  float p_drop, p_attn;     // Dropout(0.1) layers / attention-weight rates (0: the site is off)
+};
+
 }  // namespace scann
 
 struct scann_handle {
@@ -163,6 +171,7 @@ struct scann_handle {
   bool deterministic = false;          // scann_set_deterministic: the backward's small reductions in a fixed order, no float atomics
   bool in_train_forward = false;
   unsigned long long train_seed = 0;
+  const McState* mc = nullptr;         // inside scann_predict_mc: the inference forwards apply that sample's dropout masks
   ncclComm_t comm = nullptr;
   // scann_train_step_begin / _end: up to two steps may be enqueued before the first is ended (the host prepares step k + 1 while the
   // device runs step k); slot = step number & 1.  Slot 2 of the targets belongs to the synchronous scann_train_forward.
@@ -248,6 +257,9 @@ struct scann_dbatch {
   float *out_z = nullptr, *out_bf = nullptr;  // after_Lc [n_atom, global_dim], bf_property [n_struct, dense_out]
   uint64_t out_layers = 0;  // what the last forward wrote (a training forward: nothing)
   int32_t out_flags = 0;
+  // scann_predict_mc: per-atom structure table, keys, the [T, B] / [T, n_atom] samples and the reduced outputs (one block, grow-only)
+  char* mc_ws = nullptr;
+  size_t mc_bytes = 0;
 };
 
 namespace scann {

@@ -112,6 +112,8 @@ SYMBOLS = [
     ("scann_set_outputs", C.c_int, [_P, C.c_uint64, C.c_int32]),
     ("scann_output_read", C.c_int64, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64]),
     ("scann_input_grads", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("scann_predict_mc", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    ("scann_mc_drop_scale", C.c_double, [C.c_uint64, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float]),
 ]
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
@@ -210,6 +212,12 @@ def comm_unique_id():
     if rc != SCANN_OK:
         raise ScannHipError(rc, "scann_comm_unique_id failed")
     return buf.raw
+
+
+def mc_drop_scale(seed, t, key, tag, idx, p):
+    """The Monte Carlo dropout factor of one element as the kernels form it (scann_mc_drop_scale): 0 or 1 / (1 - p)."""
+    return float(load_library().scann_mc_drop_scale(int(seed) & 0xFFFFFFFFFFFFFFFF, int(t), int(key) & 0xFFFFFFFFFFFFFFFF, int(tag), int(idx),
+                                                    float(p)))
 
 
 def _ptr(a):
@@ -678,6 +686,30 @@ class Engine:
         res = {k: v for k, v in out.items() if v is not None}
         res["y"] = y
         return res
+
+    def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):
+        """Monte Carlo dropout over a resident batch (scann_predict_mc; raw y): ``samples`` forwards with the Dropout layers active under
+        structure-local masks, reduced on the device.  Returns {"y_mean", "y_std"} [n_struct], with ``want_ga`` {"ga_mean", "ga_std"}
+        [n_atom], with ``want_samples`` "y_samples" [samples, n_struct].  ``keys``: one uint64 per structure (None: all 0).
+        ``p_drop`` None: 0.1; ``p_attn`` None: the handle's attention-dropout rate."""
+        p = rb.packed
+        B, A, T = p.n_struct, p.n_atom, int(samples)
+        k = None
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys).astype(np.uint64).reshape(-1))
+            if k.shape[0] != B:
+                raise ValueError("keys: %d values for %d structures" % (k.shape[0], B))
+        out = {"y_mean": np.empty(B, np.float32), "y_std": np.empty(B, np.float32)}
+        if want_ga:
+            out["ga_mean"] = np.empty(A, np.float32)
+            out["ga_std"] = np.empty(A, np.float32)
+        if want_samples:
+            out["y_samples"] = np.empty((T, B), np.float32)
+        self._check(self.lib.scann_predict_mc(self._h, rb._h, T, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(k),
+                                              -1.0 if p_drop is None else float(p_drop), -1.0 if p_attn is None else float(p_attn),
+                                              _ptr(out["y_mean"]), _ptr(out["y_std"]), _ptr(out.get("ga_mean")), _ptr(out.get("ga_std")),
+                                              _ptr(out.get("y_samples"))))
+        return out
 
     # -- training (scann_model.py:199-241) --------------------------------------------------------------------
     def _unflatten(self, flat):

@@ -247,6 +247,68 @@ class HipModel:
         out["predict_property"] = np.concatenate([p["y"] for p in parts]).reshape(-1, 1)
         return out
 
+    def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
+                            return_samples=False):
+        """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
+        times -- reduced to their mean and unbiased standard deviation (fp64 sums on the device).  ``rate``: the two Dropout(0.1) layers
+        (None: 0.1); ``attention_rate``: the attention-weight Dropout (None: 0.05 with use_drop, else 0).  The masks of a structure depend
+        on the structure, ``seed``, the sample number and its key only (``keys``: one integer per structure, default 0), so slicing into
+        ``batch_size`` chunks or reordering changes no bit -- and two identical structures with the same key get identical samples.
+        Returns {"predict_property": [B, 1], "predict_property_std": [B, 1], "global_attention": [B, M, 1], "global_attention_std":
+        [B, M, 1]} (raw y; padded atoms 0; a ``PackedBatch`` without padding gives [n_atom, 1]) and, with ``return_samples``,
+        "samples" [T, B, 1].  Bad arguments raise ValueError before anything is uploaded."""
+        T = int(samples)
+        if T < 2:
+            raise ValueError("samples must be >= 2 (the standard deviation divides by samples - 1)")
+        p_drop = 0.1 if rate is None else float(rate)
+        p_attn = (0.05 if self.config["model"].get("use_drop") else 0.0) if attention_rate is None else float(attention_rate)
+        for name, v in (("rate", p_drop), ("attention_rate", p_attn)):
+            if not (0.0 <= v < 1.0):
+                raise ValueError("%s must lie in [0, 1), got %r" % (name, v))
+        packed_in = isinstance(inputs, _hip.PackedBatch)
+        B = inputs.n_struct if packed_in else int(np.shape(inputs["neighbors"])[0])
+        if keys is not None:
+            keys = np.asarray(keys).reshape(-1)
+            if keys.shape[0] != B:
+                raise ValueError("keys: %d values for %d structures" % (keys.shape[0], B))
+            keys = keys.astype(np.uint64)
+        bs = int(batch_size or self.config["hyper"]["batch_size"])
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        eng = self.engine
+        parts = []
+        for s0 in range(0, B, bs):
+            s1 = min(s0 + bs, B)
+            if packed_in:
+                sl, pk = None, _hip.slice_packed(inputs, s0, s1)
+            else:
+                sl = {k: np.asarray(v)[s0:s1] for k, v in inputs.items() if k in self.input_names}
+                pk = _hip.pack_inputs(sl)
+            rb = eng.upload(pk)
+            try:
+                r = eng.predict_mc(rb, T, seed=seed, keys=None if keys is None else keys[s0:s1], p_drop=p_drop, p_attn=p_attn,
+                                   want_ga=True, want_samples=return_samples)
+            finally:
+                rb.free()
+            if sl is not None:
+                for k in ("ga_mean", "ga_std"):
+                    r[k] = _hip.repad_atoms(r[k].reshape(-1, 1), sl["atom_mask"])
+            else:
+                for k in ("ga_mean", "ga_std"):
+                    r[k] = r[k].reshape(-1, 1)
+            parts.append(r)
+        out = {"predict_property": np.concatenate([p["y_mean"] for p in parts]).reshape(-1, 1),
+               "predict_property_std": np.concatenate([p["y_std"] for p in parts]).reshape(-1, 1)}
+        if packed_in and inputs.pad_shape is not None:
+            out["global_attention"] = inputs.repad_ga(np.concatenate([p["ga_mean"][:, 0] for p in parts]))
+            out["global_attention_std"] = inputs.repad_ga(np.concatenate([p["ga_std"][:, 0] for p in parts]))
+        else:
+            out["global_attention"] = np.concatenate([p["ga_mean"] for p in parts])
+            out["global_attention_std"] = np.concatenate([p["ga_std"] for p in parts])
+        if return_samples:
+            out["samples"] = np.concatenate([p["y_samples"] for p in parts], axis=1)[:, :, None]
+        return out
+
     BIG_PREDICT = 1024   # structures from which `predict(padded arrays)` runs as a pipeline of chunks
     PREDICT_CHUNK = 2048  # structures per chunk: one launch sequence each (16 batches of the reference's 128)
     BIG_SLOTS = 6_000_000  # ... or padded neighbour slots (a launch sequence takes < 8,388,608 atoms / edges: few but large crystals)
@@ -675,6 +737,17 @@ class SCANN:
         res = {k: v * self.std for k, v in out.items()}
         res["predict_property"] = y * self.std + self.mean
         return res
+
+    def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
+        """HipModel.predict_uncertainty in the units of the target, as predict_data de-normalises: the mean times std plus mean, the
+        standard deviation and the samples times |std|; the GlobalAttention scores as they are."""
+        out = self.model.predict_uncertainty(ip, samples=samples, seed=seed, keys=keys, rate=rate, attention_rate=attention_rate,
+                                             batch_size=batch_size, return_samples=return_samples)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        out["predict_property_std"] = out["predict_property_std"] * abs(self.std)
+        if "samples" in out:
+            out["samples"] = out["samples"] * self.std + self.mean
+        return out
 
     def predict_data(self, ip):
         out = self.model.predict(ip)
