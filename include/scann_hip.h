@@ -306,6 +306,34 @@ int scann_comm_ranks(scann_handle_t* h);
  * Needs scann_train_begin. */
 int scann_broadcast_weights(scann_handle_t* h, int root);
 
+/* ---- model sets: several weight sets of one architecture in one forward ------------------------------------------------------------
+ * A model set is K (1..16) weight sets of the handle's scann_config_t -- K targets of one dataset, or K seeds of one target (a deep
+ * ensemble) -- run over one resident batch by the same launches: every atom, edge, merge and readout launch of scann_forward_models
+ * covers all K members (grids of K x the tiles of one member).  Member m's y and GlobalAttention scores are bitwise what a handle holding
+ * only member m's weights (and its relu_out) gives through scann_forward_resident + scann_batch_download for the same batch.
+ * Generic widths run the members one after another on the plain-fp32 kernels; a member with |w| >= 255.9 in a 128x128 kernel runs alone
+ * on the exact-fp32 kernels (the others still share their launches).  The set leaves the handle's own weights, predictions, selected
+ * outputs (a set forward writes none), training state and the batch's last single-model y untouched.
+ *
+ * scann_models_load replaces the handle's set, atomically: on any error the previous set stays.  Member m is validated exactly like
+ * scann_load_weights (blobs[m], manifests[m], n_tensors[m] as its blob / manifest / n); relu_out[m] is its mrelu flag (target e_b), or
+ * relu_out NULL: all cfg.relu_out.  scann_models_count: the members of the handle's set (0: none). */
+int scann_models_load(scann_handle_t* h, int32_t n_models, const float* const* blobs, const scann_tensor_desc_t* const* manifests,
+                      const int32_t* n_tensors, const int32_t* relu_out);
+int scann_models_count(const scann_handle_t* h);
+/* Enqueue one forward of every member over a resident batch on stream slot `stream_slot` (asynchronous; SCANN_ERR_WEIGHTS without a
+ * set).  The batch keeps one workspace block for the members, allocated by its first set forward and freed with it.  A batch's set forwards
+ * are tracked apart from its single-model forwards: scann_batch_download waits for the batch's last single forward only, a set forward
+ * queues behind an earlier set forward of the batch on another stream, and scann_batch_release synchronises the device while a set forward
+ * has not been waited for by scann_models_download. */
+int scann_forward_models(scann_handle_t* h, scann_dbatch_t* db, int stream_slot);
+/* Wait for the batch's last set forward and copy its results, member-major: y[K * n_struct], ga[K * n_atom] (or NULL).  If that
+ * forward's range guard fired, every member is run again on the exact-fp32 kernels first (one count of scann_exact_reruns; each member
+ * then equals its single handle under SCANN_EXACT=1); with SCANN_STRICT_RANGE=1 the result is SCANN_ERR_RANGE.  A device-packing error
+ * of a scann_upload_padded batch is reported here.  SCANN_ERR_INVALID if no forward of the handle's current set (the last
+ * scann_models_load) ran on the batch. */
+int scann_models_download(scann_handle_t* h, scann_dbatch_t* db, float* y, float* ga);
+
 /* ---- host batch packers (no GPU work) --------------------------------------------------------------
  * Replace DataIterator.__getitem__ + pad_sequence / pad_nested_sequences (datagenerator.py:69-135, general.py:14-50).
  * All arrays are caller-allocated; on error the return is SCANN_ERR_INVALID and scann_pack_last_error() has the text

@@ -5,7 +5,10 @@ predictions next to the model.  ``--outputs after_Lc,local_attention_2,bf_proper
 ``<name>_<target>.pickle``: one array per structure, laid out as the padded predict of its batch returns it.
 ``--mc-samples T [--mc-seed S]`` also pickles Monte Carlo dropout estimates as ``mc_<target>.pickle``: a dict with the de-normalised
 mean and standard deviation of the prediction per structure and the mean and standard deviation of its GA scores (one [M, 1] array
-per structure, as ga_scores), each structure keyed by its index in the dataset."""
+per structure, as ga_scores), each structure keyed by its index in the dataset.
+``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
+writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
+``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
 import argparse
 import os
 import pickle
@@ -19,7 +22,56 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "sca
 from scann.models import SCANN  # noqa: E402
 
 
+def main_with(args, make_set=None):
+    """--with: the models of one architecture over the first model's dataset, every batch through one model set.  Each member's ground
+    truth and de-normalisation are its own run's: its dataset is prepared from its own config.yaml (its target's values, normalised with
+    its own statistics when hyper.scaler is set), so its pickles are the ones ``predict_model.py <its dir>`` writes.  ``make_set(dirs)``:
+    the model set (default ``ModelSet(dirs)``)."""
+    from scann.models import ModelSet
+
+    dirs = [args.trained_model] + [d for d in args.with_models.split(",") if d]
+    configs = [yaml.safe_load(open(os.path.join(d, "config.yaml"))) for d in dirs]
+    for d, c in zip(dirs[1:], configs[1:]):  # one dataset, batched alike (the GA scores are padded per batch)
+        for k in ("data_energy_path", "data_nei_path", "batch_size"):
+            if c["hyper"].get(k) != configs[0]["hyper"].get(k):
+                raise SystemExit("--with: %s has hyper.%s = %r, %s has %r; the models of a set run over one dataset"
+                                 % (d, k, c["hyper"].get(k), dirs[0], configs[0]["hyper"].get(k)))
+    runs = []
+    for c in configs:
+        run = SCANN(c, mode="data")
+        run.prepare_dataset(split=False)
+        runs.append(run)
+    data = runs[0].dataIter
+    ms = make_set(dirs) if make_set is not None else ModelSet(dirs)
+    K = len(dirs)
+    raw, gas = [[] for _ in range(K)], [[] for _ in range(K)]
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = ms.predict(inputs)
+        for m in range(K):
+            raw[m].append(r["predict_property"][m][:, 0])
+            gas[m] += list(r["global_attention"][m])
+    preds = []
+    for m, (d, run) in enumerate(zip(dirs, runs)):
+        t, dm = run.config["hyper"]["target"], run.dataIter
+        # main()'s arithmetic: the member's float32 targets as its dataset batches them, its predictions de-normalised with its own mean / std
+        y = list(np.array([float(dm.data_energy[i][1]) * dm.converter for i in dm.indexes], "float32"))
+        struct_energy = list(np.concatenate(raw[m]) * run.std + run.mean)
+        preds.append(struct_energy)
+        print("%s (%s): R2 %s, MAE %s" % (d, t, r2_score(struct_energy, y), mean_absolute_error(struct_energy, y)))
+        print("Save prediction and GA score to", d)
+        pickle.dump(gas[m], open(os.path.join(d, "ga_scores_{}.pickle".format(t)), "wb"))
+        pickle.dump([y, struct_energy], open(os.path.join(d, "energy_pre_{}.pickle".format(t)), "wb"))
+    targets = [run.config["hyper"]["target"] for run in runs]
+    if K >= 2 and len(set(targets)) == 1:
+        p = np.asarray(preds, dtype=np.float64)
+        pickle.dump({"mean": list(p.mean(axis=0)), "std": list(p.std(axis=0, ddof=1))},
+                    open(os.path.join(args.trained_model, "ensemble_{}.pickle".format(targets[0])), "wb"))
+
+
 def main(args):
+    if args.with_models:
+        return main_with(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     target = config["hyper"]["target"]
     print("Load pretrained weight for target ", target)
@@ -77,6 +129,8 @@ def parser():
     p.add_argument("--mc-samples", type=int, default=0,
                    help="Monte Carlo dropout samples per structure (>= 2; 0: none): pickles mc_<target>.pickle")
     p.add_argument("--mc-seed", type=int, default=0, help="seed of the Monte Carlo dropout masks")
+    p.add_argument("--with", dest="with_models", type=str, default="",
+                   help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p
 
 

@@ -93,7 +93,10 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     const size_t out_cap = db->out_cap;
     char* const mc_ws = db->mc_ws;  // (... and scann_predict_mc's)
     const size_t mc_bytes = db->mc_bytes;
+    char* const set_ws = db->set_ws;  // (... and scann_forward_models')
+    const size_t set_bytes = db->set_bytes;
     *db = scann_dbatch();
+    db->set_ws = set_ws; db->set_bytes = set_bytes;
     db->gen_ws = gen_ws; db->gen_ws_bytes = gen_ws_bytes;
     db->out_block = out_block; db->out_cap = out_cap;
     db->mc_ws = mc_ws; db->mc_bytes = mc_bytes;
@@ -302,6 +305,7 @@ void free_batch(scann_dbatch* db) {
   cached_free(db->gen_ws);
   cached_free(db->out_block);
   cached_free(db->mc_ws);
+  cached_free(db->set_ws);
   cached_free(db->dbg_c);
   cached_free(db->dbg_g);
   cached_free(db->dbg_ctx);
@@ -379,7 +383,7 @@ void scann_batch_free(scann_handle_t* h, scann_dbatch_t* db) {
 void scann_batch_release(scann_handle_t* h, scann_dbatch_t* db) {
   if (!db) return;
   const bool step_done = db->busy_ev && hipEventQuery(db->busy_ev) == hipSuccess;
-  if (!h || !(step_done || db->idle)) {
+  if (!h || !(step_done || (db->idle && db->set_busy < 0))) {  // (a set forward not yet downloaded: scann_models_download)
     scann_batch_free(h, db);
     return;
   }
@@ -410,6 +414,7 @@ int scann_batch_download(scann_handle_t* h, scann_dbatch_t* db, float* y_out, fl
     if (rf3) return rf3;
   }
   db->idle = true;
+  db->fwd_pending = false;
   return check_range(h, "scann_batch_download", db->last_slot);
 }
 

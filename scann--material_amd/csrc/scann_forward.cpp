@@ -239,6 +239,7 @@ struct Timer {
 int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, bool exact) {
   if ((h->force_exact || h->weights_exact) && !h->debug && !h->in_train_forward) exact = true;
   db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
+  db->fwd_pending = true;
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
   HIPCHK(h, wait_upload(db, s));  // the inputs' copy (scann_batch_upload returned when it was enqueued)
   if (const int r = ensure_outputs(h, db)) return r;

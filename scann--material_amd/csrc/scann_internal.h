@@ -190,6 +190,11 @@ struct AtomArgs {
   // key) and the structure-local element index.  Null otherwise
   const McRow* mc_rows;
   uint32_t mc_t;
+  // model set (the SET instantiation, scann_forward_models): n_member members' launches in one grid of n_member x the tiles of one, member m
+  // of workgroup b = b / tiles; its pointers are member 0's plus m times a byte stride -- m_w for the weight images (Wf*, bf*, lnr_*,
+  // W*h, b*), m_x for x, m_o for c, oA, oB, oC.  x_index is shared.  n_member == 0: not a set launch
+  int32_t n_member;
+  int64_t m_w, m_x, m_o;
 };
 void launch_atom(const AtomArgs& a, hipStream_t s);
 
@@ -243,6 +248,11 @@ struct EdgeArgs {
   // Monte Carlo dropout on the attention weights (the MC instantiation, scann_predict_mc; attn_drop_p > 0): as AtomArgs::mc_rows / mc_t
   const McRow* mc_rows;
   uint32_t mc_t;
+  // model set (the SET instantiation): n_member x n_tile workgroups, linear (XCD-remapped) index t -> member t / n_tile, tile t % n_tile;
+  // byte strides between members: m_w for p and basis, m_r for c, P1, P3, q (per-species tables: the weight block's stride), m_a for geom,
+  // ctx and part_buf.  tiles, CSR, dist, edge_weight, gd (model-independent Gaussians), species are shared.  n_member == 0: not a set launch
+  int32_t n_member;
+  int64_t m_w, m_r, m_a;
 };
 void launch_edge(const EdgeArgs& a, hipStream_t s);
 // softmax merge of the chunk tiles of every big atom (+ unscaled-query residual + LayerNorm, attention.py:189-214)
@@ -251,6 +261,9 @@ void launch_edge(const EdgeArgs& a, hipStream_t s);
 void launch_attn_merge(const int32_t* big_tab, int n_big, const float* part_buf, const int32_t* edge_offset, int chunk, float* attn, hipStream_t s);
 void launch_edge_merge(const int32_t* big_tab, int n_big, const float* part_buf, const float* q, const float* ln_g,
                        const float* ln_b, float* ctx, int32_t* range_flag, int layer, hipStream_t s);
+// ... for n_member members of a model set at once: member m's part_buf, q, ctx lie m_a bytes, its ln_g / ln_b m_w bytes behind member 0's
+void launch_edge_merge_set(const int32_t* big_tab, int n_big, const float* part_buf, const float* q, const float* ln_g, const float* ln_b,
+                           float* ctx, int32_t* range_flag, int layer, int n_member, int64_t m_a, int64_t m_w, hipStream_t s);
 
 // ---- generic-width forward (scann_generic.hip): plain fp32 kernels for local_dim / num_head / global_dim / dense_out other than 128 / 8 ----
 struct GenSeg {
@@ -344,6 +357,10 @@ struct ReadoutArgs {
   float* ga_attn;             // [n_atom]
   float* y;                   // [n_struct]
   float* bf_out;              // [n_struct,128] bf_property = swish(rep Wb + bb) (scann_model.py:437-442), or null (inference outputs)
+  // model set: n_member x n_struct workgroups, member m = b / n_struct; byte strides between members: m_w (p), m_a (gq, gk), m_g (ga_attn),
+  // m_y (y); relu_out is then a bit mask (bit m: member m's mrelu).  bf_out null.  n_member == 0: not a set launch
+  int32_t n_member;
+  int64_t m_w, m_a, m_g, m_y;
 };
 void launch_readout(const ReadoutArgs& a, hipStream_t s);
 

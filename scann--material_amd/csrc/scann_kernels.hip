@@ -20,6 +20,7 @@
 //                   scann_model.py:378-389)
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "scann_internal.h"
 #include "scann_mma.h"
 
@@ -69,13 +70,32 @@ __device__ __forceinline__ float4 mc_keep4(uint32_t bits, float p, float4 v) {
   v.w *= (bits & 8u) ? sc : 0.f;
   return v;
 }
-template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false, bool ZOUT = false, bool MC = false>
+// SET: a model set's launch (scann_forward_models) -- K members of one architecture in one grid of K x the tiles of one; the workgroup's
+// member shifts every per-member pointer once, in scalar registers (set_member), and the body is the plain inference kernel's
+template <class T>
+__device__ __forceinline__ T* set_member(T* p, int64_t bytes) {
+  return reinterpret_cast<T*>(reinterpret_cast<typename std::conditional<std::is_const<T>::value, const char, char>::type*>(p) + bytes);
+}
+template <bool FFN, int MODE, int RT, bool EX = false, bool KEEP = false, bool ZOUT = false, bool MC = false, bool SET = false>
 __global__ __launch_bounds__(256, RT == 2 ? (EX ? 2 : 3) : (MODE == 1 ? 3 : 4)) void atom_kernel(AtomArgs a) {
 #pragma clang fp contract(off)  // fusions are written out: both row-tile copies of a formula round alike (see edge_kernel)
   static_assert(!(EX && KEEP), "the training forward runs the split-fp16 kernels");
   static_assert(!ZOUT || (MODE == 2 && !KEEP), "after_Lc is an output of the readout launch of inference forwards");
   static_assert(!MC || (!EX && !KEEP && !ZOUT), "Monte Carlo dropout runs on the plain split-fp16 inference kernels");
+  static_assert(!SET || (!EX && !KEEP && !ZOUT && !MC), "a model set runs the plain split-fp16 inference kernels");
   constexpr int TAR = 32 * RT;  // atom rows per tile
+  unsigned set_bix = blockIdx.x;
+  if constexpr (SET) {
+    const unsigned nt = ((unsigned)a.n_atom + TAR - 1) / TAR, m = blockIdx.x / nt;
+    set_bix = blockIdx.x - m * nt;
+    const int64_t w = (int64_t)m * a.m_w, o = (int64_t)m * a.m_o;
+    a.x = set_member(a.x, (int64_t)m * a.m_x);
+    a.Wf1h = set_member(a.Wf1h, w); a.Wf2h = set_member(a.Wf2h, w);
+    a.bf1 = set_member(a.bf1, w); a.bf2 = set_member(a.bf2, w); a.lnr_g = set_member(a.lnr_g, w); a.lnr_b = set_member(a.lnr_b, w);
+    a.WAh = set_member(a.WAh, w); a.WBh = set_member(a.WBh, w); a.WCh = set_member(a.WCh, w); a.WDh = set_member(a.WDh, w);
+    a.bA = set_member(a.bA, w); a.bC = set_member(a.bC, w); a.bD = set_member(a.bD, w);
+    a.c = set_member(a.c, o); a.oA = set_member(a.oA, o); a.oB = set_member(a.oB, o); a.oC = set_member(a.oC, o);
+  }
   __shared__ __attribute__((aligned(16))) unsigned char sTile[2 * TAR * PLANE_STRIDE * 2];  // hi / lo planes of the current GEMM input
   __shared__ __attribute__((aligned(16))) float sRed[TAR * 8];  // LayerNorm partial statistics [wave][row][mean, m2]
 #ifdef SCANN_DIAG_SE_ROWMAJOR  // A/B build: round 5's [row][wave][2]
@@ -84,7 +104,7 @@ __global__ __launch_bounds__(256, RT == 2 ? (EX ? 2 : 3) : (MODE == 1 ? 3 : 4)) 
 #define SR_STAT(w, r) (((w) * TAR + (r)) * 2)
 #endif
   __shared__ __attribute__((aligned(16))) float sPar[7 * D];   // bf1 | bf2 | lnr_g | lnr_b | bA | bC | bD
-#define SCANN_ATOM_BIX blockIdx.x
+#define SCANN_ATOM_BIX set_bix
 #include "scann_atom_body.inc"
 #undef SR_STAT
 #undef SCANN_ATOM_BIX
@@ -98,6 +118,25 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
   // (re-measured in round 5 at the driver's 10-batch shape, 23 k atoms: 64-row tiles -- half the weight traffic, 360 tiles -- 0.159-0.170 ms
   //  of atom launches per forward against 0.152-0.157 ms for the 720 32-row tiles: the threshold stays)
   const int rows = a.n_atom <= 32 * 1024 ? 32 : 64;
+  if (a.n_member > 0) {  // model set: the plain inference kernels (scann_forward_models), the same row height as one member's launch
+    const dim3 grid(((a.n_atom + rows - 1) / rows) * a.n_member), block(256);
+#define SCANN_ATOM_SET(F, M)                                                                                          \
+  do {                                                                                                                \
+    if (rows == 32) hipLaunchKernelGGL((atom_kernel<F, M, 1, false, false, false, false, true>), grid, block, 0, s, a); \
+    else hipLaunchKernelGGL((atom_kernel<F, M, 2, false, false, false, false, true>), grid, block, 0, s, a);           \
+  } while (0)
+    if (a.ffn) {
+      if (a.mode == 0) SCANN_ATOM_SET(true, 0);
+      else if (a.mode == 1) SCANN_ATOM_SET(true, 1);
+      else SCANN_ATOM_SET(true, 2);
+    } else {
+      if (a.mode == 0) SCANN_ATOM_SET(false, 0);
+      else if (a.mode == 1) SCANN_ATOM_SET(false, 1);
+      else SCANN_ATOM_SET(false, 2);
+    }
+#undef SCANN_ATOM_SET
+    return;
+  }
   const dim3 grid((a.n_atom + rows - 1) / rows), block(256);
   if (a.mc_rows && a.drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc: never exact, no keep_* tensors, no outputs)
 #define SCANN_ATOM_MC(F, M)                                                                                   \
@@ -190,7 +229,10 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
 // head).  A template flag like KEEP: with it off every instantiation is the code it was.
 // MC: Monte Carlo dropout on the attention weights of an inference forward (scann_predict_mc): Dropout(0.05) applied unconditionally with
 // structure-local masks; the piece-major family (FB, plain, DEAD) and the base branch's row-major kernel, no keep_* stores
-template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false, bool ATTN = false, bool MC = false>
+// SET: a model set's launch (scann_forward_models): the linear workgroup index -- XCD-remapped over the whole K x n_tile grid -- is
+// member * n_tile + tile; the member's pointers are shifted once per workgroup (set_member), the body is the plain inference kernel's
+template <bool GUPD, int RT, bool FB = false, bool EX = false, bool KEEP = false, bool DEAD = false, bool ATTN = false, bool MC = false,
+          bool SET = false>
 __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) {
 #pragma clang fp contract(off)  // fusions are written out (fmaf): both unrolled row-tile copies of a formula must round alike,
                                 // so that a row's result does not depend on where in a tile it lands (batch-composition invariance)
@@ -200,6 +242,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
   static_assert(!DEAD || GUPD, "the base branch stores no geometry");
   static_assert(!(ATTN && KEEP), "the training forward returns no attention weights");
   static_assert(!MC || (!EX && !KEEP && !ATTN), "Monte Carlo dropout runs on the split-fp16 inference kernels and returns no attention weights");
+  static_assert(!SET || (!EX && !KEEP && !ATTN && !MC), "a model set runs the split-fp16 inference kernels and returns no attention weights");
   constexpr int TEK = 32 * RT;  // edge rows per tile: 64 (three workgroups per CU) or, for launches of one round, 32 (four)
   // piece-major geometry tiles (scann_edge_body.inc): the inference kernels, whose geometry nobody else reads.  The training / debug
   // forward (KEEP) and the exact re-run (EX: its first layer reads basis_kernel's row-major geom0) keep [n_edge,128] rows.
@@ -224,7 +267,20 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
   if (a.n_tile < 0) sDummy[threadIdx.x] = 1.f;
 #endif
   static_assert(2 * TEK * PLANE_STRIDE * 2 >= TEK * LDS_STRIDE * (int)sizeof(float), "K tile must fit the plane buffer");
-#define SCANN_EDGE_TIX (a.xcd_remap ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x)
+  int set_tix = 0;
+  if constexpr (SET) {
+    const int t = a.xcd_remap ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x, m = t / a.n_tile;
+    set_tix = t - m * a.n_tile;
+    const int64_t w = (int64_t)m * a.m_w, r = (int64_t)m * a.m_r, x = (int64_t)m * a.m_a;
+    a.p.W2h = set_member(a.p.W2h, w); a.p.Wkh = set_member(a.p.Wkh, w); a.p.Wfh = set_member(a.p.Wfh, w);
+    a.p.bfg = set_member(a.p.bfg, w); a.p.bk = set_member(a.p.bk, w);
+    a.p.lng_g = set_member(a.p.lng_g, w); a.p.lng_b = set_member(a.p.lng_b, w); a.p.ln_g = set_member(a.p.ln_g, w); a.p.ln_b = set_member(a.p.ln_b, w);
+    a.basis.Wdh = set_member(a.basis.Wdh, w); a.basis.Wwh = set_member(a.basis.Wwh, w); a.basis.bd = set_member(a.basis.bd, w);
+    a.basis.bw = set_member(a.basis.bw, w); a.basis.cd = set_member(a.basis.cd, w); a.basis.cw = set_member(a.basis.cw, w);
+    a.c = set_member(a.c, r); a.P1 = set_member(a.P1, r); a.P3 = set_member(a.P3, r); a.q = set_member(a.q, r);
+    a.geom = set_member(a.geom, x); a.ctx = set_member(a.ctx, x); a.part_buf = set_member(a.part_buf, x);
+  }
+#define SCANN_EDGE_TIX (SET ? set_tix : a.xcd_remap ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x)
 #include "scann_edge_body.inc"
 #undef SCANN_EDGE_TIX
 #undef SE_STAT
@@ -238,12 +294,22 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
 // Atoms with more than 64 neighbours: combine the per-chunk softmax states (running max m, sum s, unnormalised context x per
 // column) exactly as the online softmax combines edges -- M = max m_i, s = sum s_i e^(m_i - M), x = sum x_i e^(m_i - M) -- then
 // add the unscaled query and apply the LayerNorm (attention.py:189-214).  One workgroup of 128 threads per such atom.
+// SET: a model set's launch -- n_member x n_big workgroups, member m = b / n_big (the big-atom table is the batch's, shared); member m's
+// part_buf, q, ctx lie m * m_a bytes, its ln_g / ln_b m * m_w bytes behind member 0's.  The trailing arguments are unused otherwise
+template <bool SET = false>
 __global__ __launch_bounds__(128) void edge_merge_kernel(const int32_t* __restrict__ big_tab, const float* __restrict__ part_buf,
                                                          const float* __restrict__ q, const float* __restrict__ ln_g,
                                                          const float* __restrict__ ln_b, float* __restrict__ ctx,
-                                                         int32_t* __restrict__ range_flag, int layer) {
+                                                         int32_t* __restrict__ range_flag, int layer, int n_big, int64_t m_a, int64_t m_w) {
   __shared__ float sRed[2][2];
-  const int c = threadIdx.x, atom = big_tab[3 * blockIdx.x], s0 = big_tab[3 * blockIdx.x + 1], ns = big_tab[3 * blockIdx.x + 2];
+  unsigned bix = blockIdx.x;
+  if constexpr (SET) {
+    const unsigned m = blockIdx.x / (unsigned)n_big;
+    bix = blockIdx.x - m * (unsigned)n_big;
+    part_buf = set_member(part_buf, (int64_t)m * m_a); q = set_member(q, (int64_t)m * m_a); ctx = set_member(ctx, (int64_t)m * m_a);
+    ln_g = set_member(ln_g, (int64_t)m * m_w); ln_b = set_member(ln_b, (int64_t)m * m_w);
+  }
+  const int c = threadIdx.x, atom = big_tab[3 * bix], s0 = big_tab[3 * bix + 1], ns = big_tab[3 * bix + 2];
   const float* pb = part_buf + (size_t)s0 * 3 * D + c;
   float M = -INFINITY;
   for (int i = 0; i < ns; ++i) M = fmaxf(M, pb[(size_t)i * 3 * D]);
@@ -274,7 +340,14 @@ __global__ __launch_bounds__(128) void edge_merge_kernel(const int32_t* __restri
 void launch_edge_merge(const int32_t* big_tab, int n_big, const float* part_buf, const float* q, const float* ln_g,
                        const float* ln_b, float* ctx, int32_t* range_flag, int layer, hipStream_t s) {
   if (n_big > 0)
-    hipLaunchKernelGGL(edge_merge_kernel, dim3(n_big), dim3(128), 0, s, big_tab, part_buf, q, ln_g, ln_b, ctx, range_flag, layer);
+    hipLaunchKernelGGL(edge_merge_kernel<false>, dim3(n_big), dim3(128), 0, s, big_tab, part_buf, q, ln_g, ln_b, ctx, range_flag, layer, n_big,
+                       (int64_t)0, (int64_t)0);
+}
+void launch_edge_merge_set(const int32_t* big_tab, int n_big, const float* part_buf, const float* q, const float* ln_g, const float* ln_b,
+                           float* ctx, int32_t* range_flag, int layer, int n_member, int64_t m_a, int64_t m_w, hipStream_t s) {
+  if (n_big > 0 && n_member > 0)
+    hipLaunchKernelGGL(edge_merge_kernel<true>, dim3(n_big * n_member), dim3(128), 0, s, big_tab, part_buf, q, ln_g, ln_b, ctx, range_flag, layer,
+                       n_big, m_a, m_w);
 }
 
 // Attention weights of the atoms with more than 64 neighbours (inference outputs): chunk i's tile stored exp(e - m_i) per (edge, head);
@@ -350,7 +423,7 @@ void launch_pack_padded(const PackPaddedArgs& a, hipStream_t s) {
 
 void launch_edge(const EdgeArgs& a, hipStream_t s) {
   if (a.n_tile <= 0) return;
-  const dim3 grid(a.n_tile), block(256);
+  const dim3 grid(a.n_tile * std::max(a.n_member, 1)), block(256);
   // tile_rows is the height the batch's tile plan was made for (scann_batch_upload: 32 for launches of one round of workgroups)
   // three families: EX (exact-fp32 re-run of an inference forward), KEEP (training / debug forwards: row-major geometry, keep_* stores,
   // attention dropout), and the inference kernels proper (piece-major geometry tiles; FB = the first layer, DEAD = the last)
@@ -362,7 +435,12 @@ void launch_edge(const EdgeArgs& a, hipStream_t s) {
     if (a.tile_rows == 32) SCANN_EDGE_GO(G, 1, __VA_ARGS__);                \
     else SCANN_EDGE_GO(G, 2, __VA_ARGS__);                                  \
   } while (0)
-  if (a.mc_rows && a.attn_drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc; g_update: the piece-major family, run_forward)
+  if (a.n_member > 0) {  // model set (scann_forward_models): the inference kernels proper -- g_update piece-major, base branch row-major
+    if (!a.g_update) SCANN_EDGE_ROWS(false, false, false, false, false, false, false, true);
+    else if (a.fuse_basis) SCANN_EDGE_ROWS(true, true, false, false, false, false, false, true);
+    else if (a.geom_dead) SCANN_EDGE_ROWS(true, false, false, false, true, false, false, true);
+    else SCANN_EDGE_ROWS(true, false, false, false, false, false, false, true);
+  } else if (a.mc_rows && a.attn_drop_p > 0.f) {  // Monte Carlo dropout (scann_predict_mc; g_update: the piece-major family, run_forward)
     if (!a.g_update) SCANN_EDGE_ROWS(false, false, false, false, false, false, true);
     else if (a.fuse_basis) SCANN_EDGE_ROWS(true, true, false, false, false, false, true);
     else if (a.geom_dead) SCANN_EDGE_ROWS(true, false, false, false, true, false, true);
@@ -561,14 +639,27 @@ __device__ __forceinline__ float wave_max(float v) { return wave_max64(v); }
 // tiles; wave w contracts features [32w, 32w+32) of every tile, masks the diagonal (:282-285) and rows/columns past
 // the structure, keeps per-lane partial row sums over all column tiles, reduces them across the 32 columns once
 // per row tile, and the four waves' partial sums are added in fixed order (deterministic).
+// SET: a model set's launch (n_member x n_struct workgroups, member m = b / n_struct): the member's pointers are shifted once and its mrelu
+// is bit m of relu_out; the body is the plain kernel's with `sid` for the workgroup's structure
+template <bool SET = false>
 __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
   extern __shared__ float sDyn[];  // [4][npad] partial row sums, then [npad] scores / attention
   __shared__ float sRep[D];
   __shared__ float sHead[D];
   __shared__ float sRed[4];
+  unsigned sid = blockIdx.x;
+  if constexpr (SET) {
+    const unsigned m = blockIdx.x / (unsigned)a.n_struct;
+    sid = blockIdx.x - m * (unsigned)a.n_struct;
+    a.relu_out = (a.relu_out >> m) & 1;
+    const int64_t w = (int64_t)m * a.m_w, x = (int64_t)m * a.m_a;
+    a.p.Wb = set_member(a.p.Wb, w); a.p.bb = set_member(a.p.bb, w); a.p.wo = set_member(a.p.wo, w); a.p.bo = set_member(a.p.bo, w);
+    a.gq = set_member(a.gq, x); a.gk = set_member(a.gk, x);
+    a.ga_attn = set_member(a.ga_attn, (int64_t)m * a.m_g); a.y = set_member(a.y, (int64_t)m * a.m_y);
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a0 = a.mol_offset[blockIdx.x];
-  const int n = a.mol_offset[blockIdx.x + 1] - a0;
+  const int a0 = a.mol_offset[sid];
+  const int n = a.mol_offset[sid + 1] - a0;
   const int T = (n + 31) >> 5, npad = T << 5;
   float* sPart = sDyn;            // [4][npad]
   float* sAgg = sDyn + 4 * npad;  // [npad]
@@ -691,7 +782,7 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
     __syncthreads();
     if (half == 0) {
       const float hb = swish_exact((hs + sHead[f]) + a.p.bb[f]);
-      if (a.bf_out) a.bf_out[(size_t)blockIdx.x * D + f] = hb;  // inference outputs: bf_property (uniform per workgroup)
+      if (a.bf_out) a.bf_out[(size_t)sid * D + f] = hb;  // inference outputs: bf_property (uniform per workgroup)
       part = hb * a.p.wo[f];
     }
   }
@@ -701,7 +792,7 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
   if (tid == 0) {
     float y = (sRed[0] + sRed[1]) + a.p.bo[0];
     if (a.relu_out) y = fmaxf(y, 0.f);  // mrelu forward (custom_layers.py:15)
-    a.y[blockIdx.x] = y;
+    a.y[sid] = y;
   }
 }
 
@@ -709,7 +800,8 @@ void launch_readout(const ReadoutArgs& a, hipStream_t s) {
   if (a.n_struct <= 0) return;
   const size_t npad = (size_t)((a.max_atoms + 31) / 32) * 32;
   const size_t lds = 5 * npad * sizeof(float);  // 4 partial-sum rows + the score row
-  hipLaunchKernelGGL(readout_kernel, dim3(a.n_struct), dim3(256), lds, s, a);
+  if (a.n_member > 0) hipLaunchKernelGGL(readout_kernel<true>, dim3(a.n_struct * a.n_member), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(readout_kernel<false>, dim3(a.n_struct), dim3(256), lds, s, a);
 }
 
 }  // namespace scann

@@ -342,6 +342,7 @@ void scann_destroy(scann_handle_t* h) {
   if (h->train_aux2) (void)hipStreamDestroy(h->train_aux2);
   for (hipEvent_t e : h->train_ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->time_ev) (void)hipEventDestroy(e);
+  free_models(h->models);
   if (h->sc_db) free_batch(h->sc_db);  // (its arena is the handle's scratch, freed below)
   if (h->sc_arena) (void)hipFree(h->sc_arena);
   if (h->pp_dev) (void)hipFree(h->pp_dev);
@@ -371,6 +372,14 @@ int64_t scann_param_count(const scann_handle_t* h) {
 }
 
 int scann_load_weights(scann_handle_t* h, const float* blob, const scann_tensor_desc_t* manifest, int n) {
+  return scann::load_weights(h, blob, manifest, n, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+namespace scann {
+
+int load_weights(scann_handle* h, const float* blob, const scann_tensor_desc_t* manifest, int n, float* at, size_t* need) {
   if (!h || !blob || !manifest || n <= 0) return fail(h, SCANN_ERR_INVALID, "scann_load_weights: null argument");
   HIPCHK(h, hipSetDevice(h->device));
   std::map<std::string, const scann_tensor_desc_t*> by_name;
@@ -596,14 +605,25 @@ int scann_load_weights(scann_handle_t* h, const float* blob, const scann_tensor_
   const size_t obe = put_raw(src["dense_embed/bias"], D);
   const size_t olut = img.size();
   img.resize(olut + (size_t)c.n_atoms * D, 0.f);
-
-  if (h->d_weights) {
+  // per-species tables of the first layer (c | P1 | P3 | q) behind the arena when it is placed (a model set's block)
+  const size_t sp_tab = (!general_embed && c.g_update) ? (size_t)c.n_atoms * D : 0, o_sp = (img.size() + 63) & ~(size_t)63;
+  if (need) {  // validated: the floats the arena and the tables take at a placement
+    *need = o_sp + 4 * sp_tab;
+    return SCANN_OK;
+  }
+  if (at) {
+    h->d_weights = at;
+    if (sp_tab) {
+      h->sp_c = at + o_sp;
+      h->sp_P1 = h->sp_c + sp_tab; h->sp_P3 = h->sp_c + 2 * sp_tab; h->sp_q = h->sp_c + 3 * sp_tab;
+    }
+  } else if (h->d_weights) {
     HIPCHK(h, hipDeviceSynchronize());
     HIPCHK(h, hipFree(h->d_weights));
     h->d_weights = nullptr;
     h->loaded = false;
   }
-  HIPCHK(h, hipMalloc((void**)&h->d_weights, img.size() * sizeof(float)));
+  if (!at) HIPCHK(h, hipMalloc((void**)&h->d_weights, img.size() * sizeof(float)));
   HIPCHK(h, hipMemcpy(h->d_weights, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
   const float* base = h->d_weights;
   auto P = [&](size_t off) -> const float* { return off == NONE ? nullptr : base + off; };
@@ -659,6 +679,10 @@ int scann_load_weights(scann_handle_t* h, const float* blob, const scann_tensor_
   h->loaded = true;
   return SCANN_OK;
 }
+
+}  // namespace scann
+
+extern "C" {
 
 int scann_set_debug(scann_handle_t* h, int on) {
   if (!h) return SCANN_ERR_INVALID;

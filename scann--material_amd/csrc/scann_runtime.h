@@ -87,6 +87,8 @@ struct scann_train_ws {  // per resident batch (scann_dbatch::train), allocated 
 };
 
 struct Timer;  // scann_forward_profile's launch timer (scann_forward.cpp)
+struct ModelSet;  // scann_models_load's members (scann_models.cpp)
+void free_models(ModelSet* ms);  // no work of the set may still be running
 
 // scann_predict_mc: the sample run_forward is computing (scann_handle::mc, set for the duration of the call)
 struct McState {
@@ -212,6 +214,8 @@ struct scann_handle {
   int comm_world = 1;
   int32_t* range_flag = nullptr;  // host-pinned [MAX_STREAM], one word per stream slot (training: slot 0), written by the kernels'
                                   // range guard (flag_range), read after that stream's synchronisation
+  ModelSet* models = nullptr;     // scann_models_load: K weight sets of this configuration, run by scann_forward_models (null: none)
+  uint64_t models_gen = 0;        // loads of a model set so far (ModelSet::gen)
 };
 
 struct scann_dbatch {
@@ -260,6 +264,13 @@ struct scann_dbatch {
   // scann_predict_mc: per-atom structure table, keys, the [T, B] / [T, n_atom] samples and the reduced outputs (one block, grow-only)
   char* mc_ws = nullptr;
   size_t mc_bytes = 0;
+  // scann_forward_models: every member's workspace at a fixed stride, then y [K, n_struct] and the scores [K, n_atom] (one block, grow-only)
+  char* set_ws = nullptr;
+  size_t set_bytes = 0;
+  int set_slot = -1;    // stream slot of the batch's last set forward (-1: none)
+  uint64_t set_gen = 0; // ... and the load (ModelSet::gen) whose members it ran
+  int set_busy = -1;    // slot of a set forward not yet waited for by scann_models_download (-1: none): scann_batch_release then synchronises
+  bool fwd_pending = false;  // a forward was enqueued (run_forward) since the batch's last scann_batch_download
 };
 
 namespace scann {
@@ -289,6 +300,10 @@ int check_range(scann_handle* h, const char* where, int slot = 0);
   } while (0)
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// scann_runtime.cpp: scann_load_weights; at non-null: the arena (and the first layer's per-species tables behind it) is placed there, not
+// allocated; need non-null: validation only, *need = the floats such a placement takes
+int load_weights(scann_handle* h, const float* blob, const scann_tensor_desc_t* manifest, int n, float* at, size_t* need);
 
 // scann_forward.cpp: the forward graph as a launch schedule on one stream; exact: on the exact-fp32 instantiations
 // (an inference forward also writes the outputs the handle selected, scann_set_outputs)

@@ -114,6 +114,10 @@ SYMBOLS = [
     ("scann_input_grads", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("scann_predict_mc", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     ("scann_mc_drop_scale", C.c_double, [C.c_uint64, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float]),
+    ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("scann_models_count", C.c_int, [_P]),
+    ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
+    ("scann_models_download", C.c_int, [_P, _P, _P, _P]),
 ]
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
@@ -535,7 +539,8 @@ class Engine:
             out.append((name.value.decode(), (r.value, c.value) if c.value else (r.value,)))
         return out
 
-    def load_weights(self, weights):
+    def _weight_blob(self, weights):
+        """(blob, TensorDesc array, n, names kept alive) of a weight dict in the handle's spec order (shapes checked here)"""
         specs = self.weight_specs()
         chunks, descs, off = [], [], 0
         names = []
@@ -551,7 +556,42 @@ class Engine:
             off += t.size
         blob = np.concatenate(chunks).astype(np.float32)
         arr = (TensorDesc * len(descs))(*[TensorDesc(n, o, s) for n, o, s in descs])
-        self._check(self.lib.scann_load_weights(self._h, _ptr(blob), arr, len(descs)))
+        return blob, arr, len(descs), names
+
+    def models_load(self, members, relu_out=None):
+        """A model set (scann_models_load): ``members`` = K (1..16) weight dicts of this handle's configuration; ``relu_out`` = K flags
+        (None: all the configuration's).  Replaces the handle's set; on any error the previous set stays."""
+        K = len(members)
+        if not 1 <= K <= 16:
+            raise ValueError("a model set holds 1 to 16 members, not %d" % K)
+        parts = [self._weight_blob(w) for w in members]
+        blobs = (_P * K)(*[b.ctypes.data for b, _, _, _ in parts])
+        mans = (_P * K)(*[C.cast(a, _P) for _, a, _, _ in parts])
+        ns = np.array([n for _, _, n, _ in parts], dtype=np.int32)
+        relu = None if relu_out is None else np.ascontiguousarray(np.asarray(relu_out, dtype=np.int32).reshape(-1))
+        if relu is not None and relu.shape[0] != K:
+            raise ValueError("relu_out: %d flags for %d members" % (relu.shape[0], K))
+        self._check(self.lib.scann_models_load(self._h, K, blobs, mans, _ptr(ns), _ptr(relu)))
+        self.n_models = K
+
+    def models_count(self):
+        return int(self.lib.scann_models_count(self._h))
+
+    def forward_models(self, rb, slot=0):
+        """Enqueue one forward of every member of the handle's set over a resident batch (scann_forward_models)."""
+        self._check(self.lib.scann_forward_models(self._h, rb._h, int(slot)))
+
+    def models_download(self, rb, want_ga=True):
+        """Raw y [K, n_struct] and the GlobalAttention scores [K, n_atom] (or None) of the batch's last set forward."""
+        K = self.models_count()
+        y = np.empty((K, rb.packed.n_struct), dtype=np.float32)
+        ga = np.empty((K, rb.packed.n_atom), dtype=np.float32) if want_ga else None
+        self._check(self.lib.scann_models_download(self._h, rb._h, _ptr(y), _ptr(ga)))
+        return y, ga
+
+    def load_weights(self, weights):
+        blob, arr, n, _names = self._weight_blob(weights)
+        self._check(self.lib.scann_load_weights(self._h, _ptr(blob), arr, n))
 
     def forward(self, packed, want_ga=True):
         y = np.empty(packed.n_struct, dtype=np.float32)

@@ -320,17 +320,18 @@ class HipModel:
         else:
             self.engine.set_outputs(sel[1], after_lc=sel[2], bf_property=sel[3])
 
-    def _pipeline(self, jobs, finish, sel=None):
+    def _pipeline(self, jobs, finish, sel=None, launch=None):
         """The software pipeline behind every batched inference path, on the calling thread.  ``jobs`` yields ``(upload, tag)``;
         ``upload()`` -> ResidentBatch.  Job k + 1 is taken (sliced / packed) and uploaded right after job k's launches are enqueued:
         launches and uploads are asynchronous, so this order alone overlaps host and device.  Up to 2 x streams batches stay in
         flight, batch k on stream k % streams; ``finish(rb, tag)`` collects the OLDEST (download, outputs), in job order, and the
         batch is then released without a device-wide synchronisation, so the device keeps running the younger ones.  ``sel``: the
-        output selection, set before the first launch and cleared on every exit.  On any error every batch uploaded and not yet
-        released is freed, once, and the error propagates.  (A producer thread for slicing + upload, rounds 3-4, cost more in
+        output selection, set before the first launch and cleared on every exit.  ``launch(rb, slot)``: what is enqueued per batch
+        (None: the handle's forward).  On any error every batch uploaded and not yet released is freed, once, and the error propagates.  (A producer thread for slicing + upload, rounds 3-4, cost more in
         Python thread hand-offs than it hid: bench.py end_to_end 1.70-1.72 M -> 1.81 M molecules/s without it.)"""
         eng = self.engine
         ns = eng.num_streams()
+        launch = launch or eng.forward_resident
         pending = []  # (batch, tag) in flight, oldest first
         rb = None  # uploaded, not yet in flight
 
@@ -345,7 +346,7 @@ class HipModel:
                 rb = upload()
                 if len(pending) >= 2 * ns:
                     fetch_oldest()
-                eng.forward_resident(rb, k % ns)
+                launch(rb, k % ns)
                 pending.append((rb, tag))
                 rb = None
             while pending:
@@ -612,6 +613,8 @@ class SCANN:
                 self.model = create_model(self.config, seed=int(self.config["hyper"].get("seed", 0)))
             else:
                 self.model = create_model(self.config)
+        elif mode == "data":  # the configuration and its dataset only (prepare_dataset), no model: predict_model.py --with
+            pass
         else:
             self.model = load_model(pretrained, infer=True, config=self.config)
 
@@ -748,6 +751,15 @@ class SCANN:
         if "samples" in out:
             out["samples"] = out["samples"] * self.std + self.mean
         return out
+
+    @classmethod
+    def load_ensemble(cls, model_dirs, device=None):
+        """Several trained models of one architecture -- K targets of one dataset, or K seeds of one target -- as one model set
+        (``scann.models.ModelSet``): ``model_dirs`` are training output folders (``config.yaml`` + ``models/model_<target>.h5``).
+        Returns an ``Ensemble`` whose ``predict(inputs)`` de-normalises each member with its own target mean / std."""
+        from .model_set import Ensemble
+
+        return Ensemble(model_dirs, device=device)
 
     def predict_data(self, ip):
         out = self.model.predict(ip)
