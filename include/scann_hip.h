@@ -295,6 +295,31 @@ int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, u
                      float* y_mean, float* y_std, float* ga_mean, float* ga_std, float* y_samples);
 /* the Monte Carlo dropout factor of one element: 0 or 1 / (1 - p) (host; the kernels' definition) */
 double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag, uint64_t idx, float p);
+
+/* ---- per-atom contributions: the prediction with atoms left out of the global pooling ----
+ * In the reference atom_mask feeds nothing but GlobalAttention (scann_model.py:329-447; the LocalAttention layers take neighbor_mask
+ * only), so model.predict with atom_mask = 1 on a kept set S of a structure's atoms and 0 elsewhere is "the prediction with the other
+ * atoms' local-structure representations left out of the pooling, everything upstream unchanged": e_i(S) = sum over j in S, j != i of
+ * k_i . q_j (attention.py:279-292), softmax over S of e / ||e|| (:295-302, the division with use_ga_norm only), rep = sum a_i k_i
+ * (:314-316), then the head (scann_model.py:437-447).  This call runs one forward of the resident batch and computes y(S) for all the
+ * kept sets of one mode from the forward's gq / gk, with atoms ranked by the forward's GlobalAttention scores, descending, ties by
+ * ascending atom index:
+ *   SCANN_ABLATE_LEAVE_ONE_OUT  entry r (atom r):  all atoms of the structure but r
+ *   SCANN_ABLATE_DELETION       entry k - 1, k = 1..n:  all but the k highest-ranked atoms (k = n: the empty pooling)
+ *   SCANN_ABLATE_INSERTION      entry k - 1, k = 1..n:  the k highest-ranked atoms only (k = n: the plain forward's y, up to summation order)
+ * Non-finite results are the reference's: with use_ga_norm a pooling over one atom or none is 0 / 0 = NaN; without it both are finite.
+ * Outputs, any of them NULL: y [n_struct] and ga [n_atom], bitwise those of scann_forward_resident + scann_batch_download;
+ * y_abl [n_atom], entry e of structure s at mol_offset[s] + e; order [n_atom], the structure-local atom index by rank at
+ * mol_offset[s] + rank.  Raw outputs (before any target de-normalisation).  Synchronous.  An unknown mode is SCANN_ERR_INVALID; a
+ * structure of more than SCANN_ABLATE_MAX_ATOMS atoms is SCANN_ERR_UNSUPPORTED, returned before anything is launched;
+ * SCANN_ERR_RANGE as from scann_batch_download (an inference handle re-runs the forward on the exact-fp32 kernels first).  Works on
+ * inference and training handles, at 128 / 8 and at generic widths, and changes neither weights, gradients, Adam state, step counter
+ * nor the selected outputs. */
+#define SCANN_ABLATE_LEAVE_ONE_OUT 0
+#define SCANN_ABLATE_DELETION 1
+#define SCANN_ABLATE_INSERTION 2
+#define SCANN_ABLATE_MAX_ATOMS 960 /* atoms per structure: 32 score rows of the structure live in one workgroup's 160 KiB of LDS */
+int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, float* y, float* ga, float* y_abl, int32_t* order);
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

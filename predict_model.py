@@ -119,6 +119,20 @@ def main(args):
             mc["ga_mean"] += list(r["global_attention"])
             mc["ga_std"] += list(r["global_attention_std"])
         pickle.dump(mc, open(os.path.join(args.trained_model, "mc_{}.pickle".format(target)), "wb"))
+    if args.contributions:
+        print("Per-atom contributions:", args.contributions)
+        per = []
+        for b in range(len(data)):
+            inputs, _ = data[b]
+            r = scann.atom_contributions(inputs, mode=args.contributions)
+            amask = np.asarray(inputs["atom_mask"]).reshape(r["order"].shape) != 0
+            for i in range(len(amask)):  # unpadded: one entry per real atom of the structure
+                d = {k: v[i][amask[i]] for k, v in r.items() if k != "y"}
+                d["y"] = float(r["y"][i, 0])
+                # order: indices into the structure's own atoms (the padded positions of real atoms, counted)
+                d["order"] = (np.cumsum(amask[i]) - 1)[d["order"]].astype(np.int32)
+                per.append(d)
+        pickle.dump(per, open(os.path.join(args.trained_model, "contributions_{}.pickle".format(target)), "wb"))
 
 
 def parser():
@@ -129,6 +143,9 @@ def parser():
     p.add_argument("--mc-samples", type=int, default=0,
                    help="Monte Carlo dropout samples per structure (>= 2; 0: none): pickles mc_<target>.pickle")
     p.add_argument("--mc-seed", type=int, default=0, help="seed of the Monte Carlo dropout masks")
+    p.add_argument("--contributions", type=str, default="", choices=["", "leave_one_out", "deletion", "insertion"],
+                   help="also pickle per-atom contributions (the prediction with atoms left out of the global pooling) as "
+                        "contributions_<target>.pickle: one dict per structure, unpadded, in the units of the target")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

@@ -109,6 +109,7 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   if (!kp) { ctx = take(fA * d); t1 = take(fA * d); t2 = take(fA * d); q = take(fA * d); }
   float *embE = take(fA * emb), *ring10 = take(fA * 10);
   float *z = take(fA * dg), *gq = take(fA * dg), *gk = take(fA * dg);
+  if (!kp) { db->gen_gq = gq; db->gen_gk = gk; }
   float *G = take(fE * d), *T = nullptr, *K = nullptr, *gd = take(fE * NG), *gw = take(fE * NG);
   if (!kp) { T = take(fE * d); K = take(fE * d); }
   const McState* mc = kp ? nullptr : h->mc;  // Monte Carlo dropout (scann_predict_mc): structure-local masks

@@ -364,6 +364,21 @@ struct ReadoutArgs {
 };
 void launch_readout(const ReadoutArgs& a, hipStream_t s);
 
+// scann_ablate.hip (scann_ablate_pooling): y(S) of the readout for the kept sets of one mode, one workgroup per structure
+struct AblateArgs {
+  const int32_t* mol_offset;  // [n_struct+1]
+  int32_t n_struct, max_atoms;
+  const float *gq, *gk;       // [n_atom, dg] of the batch's last forward
+  int32_t dg, dout;           // global_dim, dense_out (128 / 128 on the MFMA kernel)
+  int32_t use_ga_norm, relu_out, mode;  // mode: SCANN_ABLATE_*
+  const float *Wb, *bb, *wo, *bo;       // bf_property [dg, dout], [dout]; predict_property [dout], [1]
+  const float* ga_attn;       // [n_atom] the forward's GlobalAttention scores (the ranking)
+  float* y_abl;               // [n_atom] entry e of structure s at mol_offset[s] + e
+  int32_t* order;             // [n_atom] structure-local atom index by rank, or null
+};
+size_t ablate_lds_bytes(int max_atoms, int dg);  // dynamic LDS of a launch whose largest structure has max_atoms atoms
+hipError_t launch_ablate(const AblateArgs& a, bool mfma, hipStream_t s);
+
 // Host-side edge-tile plan of a packed batch (scann_pack.cpp): whole atoms per tile, <= tile_rows edges and <= tile_atoms
 // atoms; atoms with more than TE_MAX neighbours become chunk tiles when allow_chunks.  Validates the CSR arrays and, with
 // fill_edge_row, fills edge_row (centre atom of each edge).  Returns SCANN_OK or a negative status with `err` set.

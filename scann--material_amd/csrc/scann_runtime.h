@@ -243,6 +243,7 @@ struct scann_dbatch {
   int32_t* pack_flag = nullptr;  // device packing (scann_upload_padded): what pack_padded_kernel found wrong with the input, behind y
   size_t gen_ws_bytes = 0;
   char* gen_ws = nullptr;  // generic-width forward: its per-batch workspace (sized by the handle's widths; cached_malloc)
+  float *gen_gq = nullptr, *gen_gk = nullptr;  // ... and the readout's operands in it after an inference forward (scann_ablate_pooling)
   // workspace
   float *geom = nullptr, *gd = nullptr, *c = nullptr, *ctx = nullptr, *P1 = nullptr, *P3 = nullptr, *q = nullptr;
   float *gq = nullptr, *gk = nullptr, *ga = nullptr, *y = nullptr;

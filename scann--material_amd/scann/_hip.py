@@ -114,11 +114,16 @@ SYMBOLS = [
     ("scann_input_grads", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("scann_predict_mc", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     ("scann_mc_drop_scale", C.c_double, [C.c_uint64, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float]),
+    ("scann_ablate_pooling", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
     ("scann_models_download", C.c_int, [_P, _P, _P, _P]),
 ]
+
+# scann_ablate_pooling modes and its limit on atoms per structure (include/scann_hip.h: SCANN_ABLATE_*)
+ABLATE_MODES = {"leave_one_out": 0, "deletion": 1, "insertion": 2}
+ABLATE_MAX_ATOMS = 960
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
 OUT_LOCAL_ATTENTION, OUT_AFTER_LC, OUT_BF_PROPERTY = 0, 1, 2
@@ -726,6 +731,20 @@ class Engine:
         res = {k: v for k, v in out.items() if v is not None}
         res["y"] = y
         return res
+
+    def ablate_pooling(self, rb, mode="leave_one_out"):
+        """One forward of a resident batch and the prediction with atoms left out of the global pooling (scann_ablate_pooling; raw y):
+        {"y" [n_struct], "ga" [n_atom], "ablated" [n_atom], "order" [n_atom] int32}.  ``ablated``: entry e of a structure at its atom
+        offset + e -- atom r for ``leave_one_out``, rank position k - 1 for the ``deletion`` / ``insertion`` curves; ``order``: the
+        structure-local atom index by rank of the forward's GlobalAttention scores (descending, ties by ascending index)."""
+        if mode not in ABLATE_MODES:
+            raise ValueError("mode must be one of %s, got %r" % (", ".join(ABLATE_MODES), mode))
+        p = rb.packed
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "ablated": np.empty(p.n_atom, np.float32),
+               "order": np.empty(p.n_atom, np.int32)}
+        self._check(self.lib.scann_ablate_pooling(self._h, rb._h, ABLATE_MODES[mode], _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["ablated"]),
+                                                  _ptr(out["order"])))
+        return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):
         """Monte Carlo dropout over a resident batch (scann_predict_mc; raw y): ``samples`` forwards with the Dropout layers active under

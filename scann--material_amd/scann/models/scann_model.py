@@ -247,6 +247,44 @@ class HipModel:
         out["predict_property"] = np.concatenate([p["y"] for p in parts]).reshape(-1, 1)
         return out
 
+    def atom_contributions(self, inputs, mode="leave_one_out", batch_size=None):
+        """How much of each structure's raw prediction hangs on each atom's local-structure representation: the prediction with atoms
+        left out of the GlobalAttention pooling and everything upstream unchanged -- the reference's ``model.predict`` with ``atom_mask``
+        zeroed on those atoms, which feeds nothing but the pooling (scann_model.py:329-447) -- for all kept sets of one ``mode`` from one
+        forward.  Atoms are ranked by the GlobalAttention scores of the unablated forward, descending, ties by ascending index.
+        ``leave_one_out``: entry r = all atoms but r; ``deletion``: entry k - 1 = all but the k highest-ranked; ``insertion``: entry
+        k - 1 = the k highest-ranked only.  ``inputs``: a padded dict, run ``batch_size`` structures at a time (default:
+        hyper.batch_size).  Returns {"y": [B, 1], "global_attention": [B, M, 1], "ablated": [B, M, 1] (entry e at the padded position
+        of the structure's e-th real atom, 0 at padding), "order": [B, M] int32 (padded-array atom index by rank, -1 at padding)} and,
+        for ``leave_one_out``, "contribution": [B, M, 1] = y - ablated in fp32.  With use_ga_norm a pooling over one atom or none is the
+        reference's 0 / 0 = NaN.  A bad mode or batch_size raises ValueError before anything is uploaded."""
+        if mode not in _hip.ABLATE_MODES:
+            raise ValueError("mode must be one of %s, got %r" % (", ".join(_hip.ABLATE_MODES), mode))
+        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        eng = self.engine
+        B = int(np.shape(inputs["neighbors"])[0])
+        amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
+        parts = []
+        sliced = {k: np.asarray(v) for k, v in inputs.items() if k in self.input_names}
+        jobs = ((functools.partial(self._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), i) for i in range(0, B, bs))
+        # (scann_ablate_pooling runs its own forward and is synchronous: nothing to enqueue ahead; the pipeline still uploads chunk k + 1
+        #  before chunk k is computed and frees every batch on an error)
+        self._pipeline(jobs, lambda rb, tag: parts.append(eng.ablate_pooling(rb, mode)), launch=lambda rb, slot: None)
+        cat = {k: np.concatenate([p[k] for p in parts]) for k in ("y", "ga", "ablated", "order")}
+        y = cat["y"].reshape(-1, 1)
+        out = {"y": y, "global_attention": _hip.repad_atoms(cat["ga"][:, None], amask), "ablated": _hip.repad_atoms(cat["ablated"][:, None], amask)}
+        # rank -> padded position: the structure's e-th real atom sits at the e-th set position of its mask row
+        order = np.full(amask.shape, -1, dtype=np.int32)
+        rows, cols = np.nonzero(amask)
+        first = np.concatenate([[0], np.cumsum(amask.sum(1))])[rows]  # packed offset of each real atom's structure
+        order[rows, cols] = cols[first + cat["order"]]
+        out["order"] = order
+        if mode == "leave_one_out":
+            out["contribution"] = np.where(amask[..., None], y[:, None, :] - out["ablated"], np.float32(0)).astype(np.float32)
+        return out
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -740,6 +778,17 @@ class SCANN:
         res = {k: v * self.std for k, v in out.items()}
         res["predict_property"] = y * self.std + self.mean
         return res
+
+    def atom_contributions(self, ip, mode="leave_one_out", batch_size=None):
+        """HipModel.atom_contributions in the units of the target: ``y`` and ``ablated`` de-normalised as predict_data does (times std
+        plus mean, real atoms only), ``contribution`` -- a difference of two predictions -- times std only."""
+        out = self.model.atom_contributions(ip, mode=mode, batch_size=batch_size)
+        real = (np.asarray(ip["atom_mask"]).reshape(out["order"].shape) != 0)[..., None]
+        out["y"] = out["y"] * self.std + self.mean
+        out["ablated"] = np.where(real, out["ablated"] * self.std + self.mean, 0).astype(np.float32)
+        if "contribution" in out:
+            out["contribution"] = out["contribution"] * self.std
+        return out
 
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
         """HipModel.predict_uncertainty in the units of the target, as predict_data de-normalises: the mean times std plus mean, the
