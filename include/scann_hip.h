@@ -320,6 +320,37 @@ double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag,
 #define SCANN_ABLATE_INSERTION 2
 #define SCANN_ABLATE_MAX_ATOMS 960 /* atoms per structure: 32 score rows of the structure live in one workgroup's 160 KiB of LDS */
 int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, float* y, float* ga, float* y_abl, int32_t* order);
+
+/* ---- attention rollout: a prediction traced through the LocalAttention layers ----
+ * A GlobalAttention score belongs to an atom's local structure after n_attention rounds of message passing, not to the atom.  Attention
+ * rollout (Abnar & Zuidema 2020) composes the layers' attention maps: for one structure of n atoms, packed edges in CSR order, and the
+ * weights a[l][e][h] of layer l exactly as scann_output_read(.., SCANN_OUT_LOCAL_ATTENTION, l, ..) returns them for this forward,
+ *   abar[l][e] = (a[l][e][0] + ... + a[l][e][H-1]) * (1 / H), heads added in index order (head = -1), or a[l][e][k] (head = k);
+ *   (T_l R)[i, :] = residual * R[i, :] + (1 - residual) * sum over the edges e of atom i, in CSR order, of abar[l][e] * R[col(e), :]
+ *                   for an atom with at least one edge, R[i, :] for an atom without (its context is the LayerNorm of its own query);
+ *                   several edges to one neighbour add, an edge from an atom to itself is an ordinary edge;
+ *   R = T_{depth-1} ... T_1 T_0 I: R[i, j] = the share of atom i's representation after `depth` layers that traces back to atom j, every
+ *                   row sums to 1;  attribution[j] = sum over i, ascending, of ga[i] * R[i, j], which sums to 1 wherever ga does (a
+ *                   one-atom structure under use_ga_norm has ga = NaN, and so has its attribution).
+ * fp32 sums in the stated order, no atomics; a structure's results are bitwise the same in any batch and at any position.
+ * The call runs one forward of the resident batch -- for this forward the first `depth` attention maps are added to what
+ * scann_set_outputs selected, and the handle's selection is put back before the call returns, also when it fails -- downloads it as
+ * scann_batch_download does (range guard, exact-fp32 re-run, SCANN_STRICT_RANGE; SCANN_ERR_UNSUPPORTED for a g_update model whose forward
+ * does not run the fused first layer, as with selected attention maps), and rolls the maps up where the forward left them.  The batch's
+ * output block then belongs to that forward: scann_output_read on the batch returns the maps the rollout was made from, until the
+ * batch's next forward, which writes the handle's own selection again.  residual in [0, 1] (0.5: attention and skip connection weigh the
+ * same); head in -1 .. num_head - 1; depth <= 0: n_attention, depth > n_attention: SCANN_ERR_INVALID.  Outputs, any of them NULL:
+ * y [n_struct] and ga [n_atom], bitwise those of scann_forward_resident + scann_batch_download; attribution [n_atom];
+ * rollout [scann_rollout_floats]: the structures' n x n row-major blocks one after another (NULL: not formed).  Synchronous.  Errors
+ * before anything is launched: SCANN_ERR_INVALID (null handle or batch, residual, head, depth), SCANN_ERR_WEIGHTS, and
+ * SCANN_ERR_UNSUPPORTED for a structure of more than SCANN_ROLLOUT_MAX_ATOMS atoms.  An empty batch and a batch without edges (R = I,
+ * attribution = ga) are computed.  Works on inference and training handles, at 128 / 8 and at generic widths, and changes neither
+ * weights, gradients, Adam state, step counter nor the selected outputs.  scann_rollout_floats: the sum over the batch's structures of
+ * n^2 (it waits for the batch's upload), or a negative status. */
+#define SCANN_ROLLOUT_MAX_ATOMS 960 /* atoms per structure: two 16-column slabs [n][16] of the structure live in one workgroup's 160 KiB of LDS */
+int64_t scann_rollout_floats(scann_handle_t* h, const scann_dbatch_t* db);
+int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residual, int32_t head, int32_t depth, float* y, float* ga,
+                            float* attribution, float* rollout);
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

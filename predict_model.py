@@ -6,6 +6,8 @@ predictions next to the model.  ``--outputs after_Lc,local_attention_2,bf_proper
 ``--mc-samples T [--mc-seed S]`` also pickles Monte Carlo dropout estimates as ``mc_<target>.pickle``: a dict with the de-normalised
 mean and standard deviation of the prediction per structure and the mean and standard deviation of its GA scores (one [M, 1] array
 per structure, as ga_scores), each structure keyed by its index in the dataset.
+``--rollout [--rollout-residual R] [--rollout-head K]`` also pickles the attention rollout as ``rollout_<target>.pickle``: one unpadded dict
+per structure with ``attribution`` [n] (the GA scores traced back to the atoms through the local-attention layers) and ``rollout`` [n, n].
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -133,6 +135,16 @@ def main(args):
                 d["order"] = (np.cumsum(amask[i]) - 1)[d["order"]].astype(np.int32)
                 per.append(d)
         pickle.dump(per, open(os.path.join(args.trained_model, "contributions_{}.pickle".format(target)), "wb"))
+    if args.rollout:
+        print("Attention rollout: residual %g, %s" % (args.rollout_residual, "head mean" if args.rollout_head < 0 else "head %d" % args.rollout_head))
+        per = []
+        for b in range(len(data)):
+            inputs, _ = data[b]
+            r = scann.attention_rollout(inputs, residual=args.rollout_residual, head=None if args.rollout_head < 0 else args.rollout_head)
+            amask = np.asarray(inputs["atom_mask"]).reshape(r["rollout"].shape[:2]) != 0
+            for i in range(len(amask)):  # unpadded: the structure's own atoms
+                per.append({"attribution": r["atom_attribution"][i][amask[i], 0], "rollout": r["rollout"][i][np.ix_(amask[i], amask[i])]})
+        pickle.dump(per, open(os.path.join(args.trained_model, "rollout_{}.pickle".format(target)), "wb"))
 
 
 def parser():
@@ -146,6 +158,11 @@ def parser():
     p.add_argument("--contributions", type=str, default="", choices=["", "leave_one_out", "deletion", "insertion"],
                    help="also pickle per-atom contributions (the prediction with atoms left out of the global pooling) as "
                         "contributions_<target>.pickle: one dict per structure, unpadded, in the units of the target")
+    p.add_argument("--rollout", action="store_true",
+                   help="also pickle the attention rollout (the GA scores traced back to the atoms through the local-attention layers) "
+                        "as rollout_<target>.pickle: one dict per structure, unpadded (attribution [n], rollout [n, n])")
+    p.add_argument("--rollout-residual", type=float, default=0.5, help="weight of the skip connection in every layer of the rollout, 0 .. 1")
+    p.add_argument("--rollout-head", type=int, default=-1, help="one attention head instead of the mean over the heads (-1)")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

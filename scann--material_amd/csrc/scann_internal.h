@@ -379,6 +379,23 @@ struct AblateArgs {
 size_t ablate_lds_bytes(int max_atoms, int dg);  // dynamic LDS of a launch whose largest structure has max_atoms atoms
 hipError_t launch_ablate(const AblateArgs& a, bool mfma, hipStream_t s);
 
+// scann_rollout.hip (scann_attention_rollout): the first `depth` attention maps of one forward composed per structure
+struct RolloutArgs {
+  const int32_t *mol_offset, *edge_offset, *edge_col;  // [n_struct+1], [n_atom+1], [n_edge] (global atom rows)
+  int32_t n_struct, n_edge, max_atoms;
+  int32_t num_head, head, depth;  // head: -1 = the mean over the heads
+  float residual;
+  const float* attn;           // [depth][n_edge][num_head]: layers 0 .. depth-1 of the forward's output block (null: a batch without edges)
+  const float* ga;             // [n_atom] the forward's GlobalAttention scores
+  float* abar;                 // [depth][n_edge] scratch: the edge weights of every layer
+  float* attribution;          // [n_atom]
+  float* rollout;              // the structures' n x n row-major blocks one after another, or null
+  const int64_t* roll_offset;  // [n_struct] first float of each structure's block (with rollout)
+};
+int rollout_slab(int max_atoms);          // columns per workgroup for a launch whose largest structure has max_atoms atoms
+size_t rollout_lds_bytes(int max_atoms);  // dynamic LDS of such a launch
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s);
+
 // Host-side edge-tile plan of a packed batch (scann_pack.cpp): whole atoms per tile, <= tile_rows edges and <= tile_atoms
 // atoms; atoms with more than TE_MAX neighbours become chunk tiles when allow_chunks.  Validates the CSR arrays and, with
 // fill_edge_row, fills edge_row (centre atom of each edge).  Returns SCANN_OK or a negative status with `err` set.

@@ -115,6 +115,8 @@ SYMBOLS = [
     ("scann_predict_mc", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     ("scann_mc_drop_scale", C.c_double, [C.c_uint64, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float]),
     ("scann_ablate_pooling", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("scann_rollout_floats", C.c_int64, [_P, _P]),
+    ("scann_attention_rollout", C.c_int, [_P, _P, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -124,9 +126,30 @@ SYMBOLS = [
 # scann_ablate_pooling modes and its limit on atoms per structure (include/scann_hip.h: SCANN_ABLATE_*)
 ABLATE_MODES = {"leave_one_out": 0, "deletion": 1, "insertion": 2}
 ABLATE_MAX_ATOMS = 960
+# scann_attention_rollout's limit on atoms per structure (SCANN_ROLLOUT_MAX_ATOMS)
+ROLLOUT_MAX_ATOMS = 960
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
 OUT_LOCAL_ATTENTION, OUT_AFTER_LC, OUT_BF_PROPERTY = 0, 1, 2
+
+
+
+def check_rollout_args(residual, head, depth, num_head, n_attention):
+    """The arguments of an attention rollout as the C call takes them: (residual, head or -1, depth or 0); ValueError for a residual
+    outside [0, 1], a head outside 0 .. num_head - 1, a depth outside 1 .. n_attention."""
+    try:
+        residual = float(residual)
+    except (TypeError, ValueError):
+        raise ValueError("residual must be a number in [0, 1], got %r" % (residual,)) from None
+    if not 0.0 <= residual <= 1.0:
+        raise ValueError("residual must lie in [0, 1], got %r" % (residual,))
+    for name, v, lo, hi in (("head", head, 0, int(num_head) - 1), ("depth", depth, 1, int(n_attention))):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("%s must be None or an integer in %d .. %d, got %r" % (name, lo, hi, v))
+    return residual, -1 if head is None else int(head), 0 if depth is None else int(depth)
+
 
 _lib = None
 _pinned = False  # the process has pinned itself to its device's cores (Engine.__init__, multi-rank runs)
@@ -744,6 +767,22 @@ class Engine:
                "order": np.empty(p.n_atom, np.int32)}
         self._check(self.lib.scann_ablate_pooling(self._h, rb._h, ABLATE_MODES[mode], _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["ablated"]),
                                                   _ptr(out["order"])))
+        return out
+
+    def attention_rollout(self, rb, residual=0.5, head=None, depth=None, matrix=True):
+        """One forward of a resident batch and its attention rollout (scann_attention_rollout; raw y): the first ``depth`` layers' attention
+        maps (None: all), head-averaged (``head`` None) or of one head, mixed with ``residual`` of the identity and multiplied through.
+        {"y" [n_struct], "ga" [n_atom], "attribution" [n_atom], "rollout_offset" [n_struct + 1] int64} and, with ``matrix``, "rollout"
+        [sum n^2]: structure s's n x n row-major block at rollout_offset[s] (row i: where atom i's representation comes from)."""
+        residual, head, depth = check_rollout_args(residual, head, depth, self.cfg.num_head, self.cfg.n_attention)
+        p = rb.packed
+        cnt = np.diff(p.mol_offset).astype(np.int64) if hasattr(p, "mol_offset") else p.atom_mask.sum(1).astype(np.int64)
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "attribution": np.empty(p.n_atom, np.float32),
+               "rollout_offset": np.concatenate([[0], np.cumsum(cnt * cnt)]).astype(np.int64)}
+        if matrix:  # (scann_rollout_floats gives the same size from the device's copy of the offsets, at the price of a copy)
+            out["rollout"] = np.empty(int(out["rollout_offset"][-1]), np.float32)
+        self._check(self.lib.scann_attention_rollout(self._h, rb._h, residual, head, depth, _ptr(out["y"]), _ptr(out["ga"]),
+                                                     _ptr(out["attribution"]), _ptr(out.get("rollout"))))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

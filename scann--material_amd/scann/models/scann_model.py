@@ -285,6 +285,59 @@ class HipModel:
             out["contribution"] = np.where(amask[..., None], y[:, None, :] - out["ablated"], np.float32(0)).astype(np.float32)
         return out
 
+    def attention_rollout(self, inputs, residual=0.5, head=None, depth=None, matrix=True, batch_size=None):
+        """Which atoms a structure's prediction traces back to through the LocalAttention layers: attention rollout (Abnar & Zuidema
+        2020).  A GlobalAttention score belongs to an atom's local structure after n_attention rounds of message passing; the rollout
+        multiplies the layers' attention maps through -- per layer the head-averaged map (``head`` None; or head k alone) mixed with
+        ``residual`` of the identity for the skip connection, an atom without neighbours keeping its row -- for the first ``depth``
+        layers (None: all).  ``rollout[i, j]``: the share of atom i's final representation that comes from atom j (rows sum to 1);
+        ``atom_attribution[j] = sum_i global_attention[i] * rollout[i, j]`` sums to 1 over a structure.  All from one forward, composed
+        on the GPU.  A padded dict gives {"predict_property": [B, 1], "global_attention": [B, M, 1], "atom_attribution": [B, M, 1],
+        "rollout": [B, M, M]} (row / column at the padded position of the atom, 0 at padding; ``matrix=False``: no "rollout"); a
+        ``PackedBatch`` gives the packed [n_atom] arrays, "rollout" [sum n^2] (the structures' n x n row-major blocks) and
+        "rollout_offset" [n_struct + 1].  Raw y.  Inputs run ``batch_size`` structures at a time (default: hyper.batch_size).  At most
+        _hip.ROLLOUT_MAX_ATOMS atoms per structure.  Bad arguments raise ValueError before anything is uploaded."""
+        m = self.config["model"]
+        args = _hip.check_rollout_args(residual, head, depth, int(m["num_head"]), int(m["n_attention"]))
+        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        eng = self.engine
+        is_packed = isinstance(inputs, _hip.PackedBatch)
+        if is_packed:
+            B = inputs.n_struct
+            jobs = ((functools.partial(eng.upload, _hip.slice_packed(inputs, i, min(i + bs, B))), i) for i in range(0, B, bs))
+        else:
+            B = int(np.shape(inputs["neighbors"])[0])
+            sliced = {k: np.asarray(v) for k, v in inputs.items() if k in self.input_names}
+            jobs = ((functools.partial(self._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), i) for i in range(0, B, bs))
+        parts = []
+        # (scann_attention_rollout runs its own forward and is synchronous, as scann_ablate_pooling: see atom_contributions)
+        self._pipeline(jobs, lambda rb, tag: parts.append(eng.attention_rollout(rb, args[0], None if args[1] < 0 else args[1],
+                                                                                args[2] or None, matrix=bool(matrix))),
+                       launch=lambda rb, slot: None)
+        keys = ("y", "ga", "attribution") + (("rollout",) if matrix else ())
+        cat = {k: np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, np.float32) for k in keys}
+        sq = np.concatenate([np.diff(p["rollout_offset"]) for p in parts]) if parts else np.zeros(0, np.int64)  # n^2 per structure
+        offset = np.concatenate([[0], np.cumsum(sq)]).astype(np.int64)
+        y = cat["y"].reshape(-1, 1)
+        if is_packed:
+            out = {"predict_property": y, "global_attention": cat["ga"], "atom_attribution": cat["attribution"], "rollout_offset": offset}
+            if matrix:
+                out["rollout"] = cat["rollout"]
+            return out
+        amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
+        out = {"predict_property": y, "global_attention": _hip.repad_atoms(cat["ga"][:, None], amask),
+               "atom_attribution": _hip.repad_atoms(cat["attribution"][:, None], amask)}
+        if matrix:
+            M = amask.shape[1]
+            R = np.zeros((B, M, M), dtype=np.float32)
+            for b in range(B):
+                pos = np.nonzero(amask[b])[0]
+                R[b][np.ix_(pos, pos)] = cat["rollout"][offset[b]:offset[b + 1]].reshape(len(pos), len(pos))
+            out["rollout"] = R
+        return out
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -788,6 +841,13 @@ class SCANN:
         out["ablated"] = np.where(real, out["ablated"] * self.std + self.mean, 0).astype(np.float32)
         if "contribution" in out:
             out["contribution"] = out["contribution"] * self.std
+        return out
+
+    def attention_rollout(self, ip, residual=0.5, head=None, depth=None, matrix=True, batch_size=None):
+        """HipModel.attention_rollout with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
+        scores, the attribution and the rollout are unitless shares and stay as they are."""
+        out = self.model.attention_rollout(ip, residual=residual, head=head, depth=depth, matrix=matrix, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
         return out
 
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
