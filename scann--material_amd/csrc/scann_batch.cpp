@@ -334,7 +334,9 @@ int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, 
   const int site = code >> 8;
   if (!code || site < 1 || site > 4) return SCANN_OK;
   h->range_flag[db->last_slot] = 0;
-  const int r = run_forward(h, db, s, nullptr, true);
+  FwdOpts o;
+  o.exact = true;
+  const int r = run_forward(h, db, s, o);
   if (r) return r;
   h->exact_reruns++;
   *rerun = true;

@@ -1,5 +1,7 @@
 // Forward launch schedules -- run_forward (the split-fp16 MFMA kernels and their exact-fp32 instantiations), run_forward_generic
-// (the plain-fp32 kernels of other widths) -- and the entry points that run, time or inspect one forward.
+// (the plain-fp32 kernels of other widths) -- and the entry points that run, time or inspect one forward.  Every forward of the library
+// -- inference, training, a Monte Carlo dropout sample, a member or a run of members of a model set -- is run_forward with the FwdOpts
+// (scann_runtime.h) that describe it; no caller selects a mode by writing into the handle or the batch.
 #include "scann_runtime.h"
 
 namespace {
@@ -21,8 +23,7 @@ int ensure_debug(scann_handle* h, scann_dbatch* db) {
 // The inference outputs the handle selected (scann_set_outputs) for this forward of `db` (a training forward: none): the batch's output
 // block is sized for them -- allocated by the first forward that needs it, grown when a selection or batch needs more -- and db->out_*
 // record what this forward writes.  With nothing selected nothing happens.
-int ensure_outputs(scann_handle* h, scann_dbatch* db) {
-  const bool infer = !h->in_train_forward;
+int ensure_outputs(scann_handle* h, scann_dbatch* db, bool infer) {
   db->out_layers = infer ? h->out_layers : 0;
   db->out_flags = infer ? h->out_flags : 0;
   db->out_attn = db->out_z = db->out_bf = nullptr;
@@ -58,9 +59,11 @@ float* attn_out_of(const scann_handle* h, const scann_dbatch* db, int l) {
 
 // create_model (scann_model.py:362-447) for a handle whose widths are not 128 / 8: one plain-fp32 kernel per formula
 // (scann_generic.hip) on the same packed batch.  kp non-null: the training forward -- Dropout layers active (kp->drop_p, kp->attn_p,
-// kp->seed), every intermediate kept in kp, the property head as dense launches.
-int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKeep* kp = nullptr) {
+// kp->seed), every intermediate kept in kp, the property head as dense launches.  wh: whose weights; buf: where y and the scores go
+int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o, const scann_handle* wh, const FwdBufs& buf) {
   const scann_config_t& c = h->cfg;
+  GenKeep* const kp = o.train ? o.train->gen : nullptr;
+  const bool outs = o.outputs && !kp;  // (the selected outputs of an inference forward)
   const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
   const int d = c.local_dim, dg = c.global_dim, dout = c.dense_out, H = c.num_head, emb = c.embedding_dim;
   const int cin = emb + (c.use_ring ? 10 : 0);
@@ -72,7 +75,7 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   // so that a step is refused here, before it has touched anything, and not halfway through
   if (kp && ((size_t)3 * db->max_atoms + 4) * sizeof(double) > 65536)
     return fail(h, SCANN_ERR_UNSUPPORTED, "training forward (generic widths): a structure's atoms exceed one workgroup's LDS in the backward (GlobalAttention pooling: 3 x atoms doubles <= 64 KiB)");
-  auto W =[&](const std::string& name) -> const float* { return h->g_weights + h->g_off.at(name); };
+  auto W =[&](const std::string& name) -> const float* { return wh->g_weights + wh->g_off.at(name); };
   // workspace: atom rows, edge rows, Gaussian bases
   const size_t fA = (size_t)A, fE = (size_t)std::max(E, 1), fB = (size_t)B, Ls = (size_t)L;
   float* p = nullptr;
@@ -112,7 +115,7 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   if (!kp) { db->gen_gq = gq; db->gen_gk = gk; }
   float *G = take(fE * d), *T = nullptr, *K = nullptr, *gd = take(fE * NG), *gw = take(fE * NG);
   if (!kp) { T = take(fE * d); K = take(fE * d); }
-  const McState* mc = kp ? nullptr : h->mc;  // Monte Carlo dropout (scann_predict_mc): structure-local masks
+  const McState* mc = kp ? nullptr : o.mc;  // Monte Carlo dropout (scann_predict_mc): structure-local masks
   const float tp = kp ? kp->drop_p : mc ? mc->p_drop : 0.f;
   const unsigned long long seed = kp ? kp->seed : mc ? mc->seed : 0;
   auto dense = [&](GenSeg s0, GenSeg s1, GenSeg s2, int n_seg, int prod, const std::string& name, int K_, int N_, int rows, int act,
@@ -143,9 +146,9 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   }
   if (kp) { kp->embE = embE; kp->ring10 = ring10; kp->pre_e = pre_e; kp->cc0 = cc; kp->gd = gd; kp->gw = gw; }
   // ---- Gaussian bases and the initial geometry (scann_model.py:376-391) ----
-  launch_gen_gauss(db->dist, h->g_centres, E, gd, s);
+  launch_gen_gauss(db->dist, wh->g_centres, E, gd, s);
   if (c.g_update) {
-    launch_gen_gauss(db->weight, h->g_centres + NG, E, gw, s);
+    launch_gen_gauss(db->weight, wh->g_centres + NG, E, gw, s);
     float *Td = kp ? take(fE * d) : T, *Tw = kp ? take(fE * d) : K;
     float *pre_d = kp ? take(fE * d) : nullptr, *pre_w = kp ? take(fE * d) : nullptr;
     dense(GenSeg{gd, nullptr, NG}, none, none, 1, 0, "neighbor_d", NG, d, E, 1, nullptr, nullptr, Td, pre_d);
@@ -180,7 +183,7 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
       launch_gen_attn_mc(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, mc->p_attn, DROP_TAG_ATTN + (unsigned)l, seed, mc->rows, mc->t);
     else
       launch_gen_attn(b.q, b.K, db->edge_offset, A, d, H, db->max_degree, b.t1, s, kp ? kp->attn_p : 0.f, DROP_TAG_ATTN + (unsigned)l, seed,
-                      kp ? nullptr : attn_out_of(h, db, l));
+                      outs ? attn_out_of(h, db, l) : nullptr);
     launch_gen_layernorm(b.t1, nullptr, W(la + "/layer_norm/gamma"), W(la + "/layer_norm/beta"), A, d, b.ctx, s);
     if (c.use_attn_norm) {  // ResidualNorm (attention.py:37-40): LayerNorm(x + Dropout(dense_2(swish(dense_1 x))))
       dense(GenSeg{b.ctx, nullptr, d}, none, none, 1, 0, rn + "/dense_1", d, d, A, 1, nullptr, nullptr, b.h1, b.pre1);
@@ -197,18 +200,18 @@ int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, GenKee
   }
   // ---- readout (scann_model.py:424-447; attention.py:267-318) ----
   float* z_pre = kp ? take(fA * dg) : nullptr;
-  if (!kp && db->out_z) z = db->out_z;  // inference outputs: after_Lc straight into the batch's output block
+  if (outs && db->out_z) z = db->out_z;  // inference outputs: after_Lc straight into the batch's output block
   dense(GenSeg{cc, nullptr, d}, none, none, 1, 0, "after_Lc", d, dg, A, 1, nullptr, nullptr, z, z_pre);
   dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/query", dg, dg, A, 0, nullptr, nullptr, gq);
   dense(GenSeg{z, nullptr, dg}, none, none, 1, 0, "global_attention/key", dg, dg, A, 0, nullptr, nullptr, gk);
   float* rep = kp ? take(fB * dg) : nullptr;
-  launch_gen_readout(db->mol_offset, B, db->max_atoms, gq, gk, dg, dout, c.use_ga_norm, c.relu_out, W("bf_property/kernel"), W("bf_property/bias"),
-                     W("predict_property/kernel"), W("predict_property/bias"), db->ga, db->y, s, rep, kp ? nullptr : db->out_bf);
+  launch_gen_readout(db->mol_offset, B, db->max_atoms, gq, gk, dg, dout, c.use_ga_norm, wh->cfg.relu_out, W("bf_property/kernel"), W("bf_property/bias"),
+                     W("predict_property/kernel"), W("predict_property/bias"), buf.ga, buf.y, s, rep, outs ? db->out_bf : nullptr);
   if (kp) {
     float *hid_pre = take(fB * dout), *hid = take(fB * dout);
     dense(GenSeg{rep, nullptr, dg}, none, none, 1, 0, "bf_property", dg, dout, B, 1, nullptr, nullptr, hid, hid_pre);
-    dense(GenSeg{hid, nullptr, dout}, none, none, 1, 0, "predict_property", dout, 1, B, 0, nullptr, nullptr, db->y);
-    if (c.relu_out) launch_gen_relu(db->y, B, s);  // mrelu forward (custom_layers.py:15); its gradient is the identity
+    dense(GenSeg{hid, nullptr, dout}, none, none, 1, 0, "predict_property", dout, 1, B, 0, nullptr, nullptr, buf.y);
+    if (wh->cfg.relu_out) launch_gen_relu(buf.y, B, s);  // mrelu forward (custom_layers.py:15); its gradient is the identity
     kp->cc_L = cc; kp->z_pre = z_pre; kp->z = z; kp->gq = gq; kp->gk = gk; kp->rep = rep; kp->hid_pre = hid_pre; kp->hid = hid;
   }
   if (reinterpret_cast<char*>(p) > p_end) return fail(h, SCANN_ERR_HIP, "forward (generic widths): workspace overrun");
@@ -235,34 +238,46 @@ struct Timer {
   }
 };
 
-// The forward graph of create_model (scann_model.py:362-447) as a launch schedule on one stream.
+// The forward graph of create_model (scann_model.py:362-447) as a launch schedule on one stream: THE schedule of the 128 / 8 kernels -- what
+// kind of forward it enqueues, on whose weights, into which buffers, for how many members of a model set at once is all in `o`.
 // kind codes for the timer: 0 basis, 1 atom, 2 edge, 3 readout.
-int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, bool exact) {
-  if ((h->force_exact || h->weights_exact) && !h->debug && !h->in_train_forward) exact = true;
-  db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
-  db->fwd_pending = true;
-  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
+int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o) {
+  scann_handle* const W = o.n_member ? o.members[0] : o.weights ? o.weights : h;  // the weight holder (a set launch: member 0's, the others by stride)
+  const FwdTrain* const tr = o.train;
+  const McState* const mc = o.mc;
+  Timer* const tm = o.tm;
+  const bool debug = o.keep_layers < 0 ? h->debug : o.keep_layers != 0;
+  const bool exact = o.exact || ((h->force_exact || W->weights_exact) && !debug && !tr);
+  const int nm = o.n_member;
+  const int64_t wst = o.m_w, ast = o.m_a;  // byte strides between members' weight images / workspaces (0: not a set launch)
+  if (!o.of_set) {
+    db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
+    db->fwd_pending = true;
+  }
+  if (!W->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
   HIPCHK(h, wait_upload(db, s));  // the inputs' copy (scann_batch_upload returned when it was enqueued)
-  if (const int r = ensure_outputs(h, db)) return r;
+  if (o.outputs)
+    if (const int r = ensure_outputs(h, db, !tr)) return r;
+  const FwdBufs b = o.bufs ? *o.bufs : FwdBufs(db);
   if (h->generic) {
     if (tm) { tm->mark(-1); }
-    const int r = run_forward_generic(h, db, s, h->in_train_forward ? h->gen_keep : nullptr);
+    const int r = run_forward_generic(h, db, s, o, W, b);
     if (tm) tm->mark(3);
     return r;
   }
   const scann_config_t& c = h->cfg;
   const int L = c.n_attention;
-  if (h->debug) {
+  if (debug) {
     const int r = ensure_debug(h, db);
     if (r) return r;
   }
   // keep-mode (training / scann_set_debug): every layer writes its centres, context and geometry straight into its slice of
   // the per-layer buffers (base branch: no geometry to thread)
   const size_t nA_ = (size_t)db->n_atom * D, nE_ = (size_t)db->n_edge * D;
-  auto c_of = [&](int l) { return h->debug ? db->dbg_c + (size_t)l * nA_ : db->c; };
-  auto ctx_of = [&](int l) { return h->debug ? db->dbg_ctx + (size_t)l * nA_ : db->ctx; };
-  auto g_of = [&](int l) { return h->debug && c.g_update ? db->dbg_g + (size_t)l * nE_ : db->geom; };
-  int32_t* const rflag = h->range_flag ? h->range_flag + db->last_slot : nullptr;  // this stream's range-guard word
+  auto c_of = [&](int l) { return debug ? db->dbg_c + (size_t)l * nA_ : b.c; };
+  auto ctx_of = [&](int l) { return debug ? db->dbg_ctx + (size_t)l * nA_ : b.ctx; };
+  auto g_of = [&](int l) { return debug && c.g_update ? db->dbg_g + (size_t)l * nE_ : b.geom; };
+  int32_t* const rflag = h->range_flag ? h->range_flag + (o.slot >= 0 ? o.slot : db->last_slot) : nullptr;  // this stream's range-guard word
   if (tm) tm->mark(-1);
   // exact: the forward's range guard fired (an operand outside the split-fp16 range): the same launches on the EX instantiations of
   // the atom / edge kernels -- exact-fp32 projections -- with the plain first layer (basis_kernel, no per-species tables)
@@ -270,70 +285,78 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
   // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
   // Monte Carlo dropout (scann_predict_mc, never exact): the sample's masks at the training forward's Dropout sites, on the MC instantiations
   // (the piece-major family: the fused first layer whatever SCANN_FUSE_BASIS says)
-  const McState* mc = h->in_train_forward ? nullptr : h->mc;
-  const bool fuse_basis = !exact && (h->fuse_basis || mc) && c.g_update && L > 0 && !h->debug && !h->in_train_forward && db->n_edge > 0;
+  const bool fuse_basis = !exact && (h->fuse_basis || mc) && c.g_update && L > 0 && !debug && !tr && db->n_edge > 0;
   // the attention-weight stores exist in the piece-major g_update kernels (and the row-major base / exact ones) only
-  if (db->out_layers && c.g_update && !exact && !fuse_basis && db->n_edge > 0) {
+  if (o.outputs && db->out_layers && c.g_update && !exact && !fuse_basis && db->n_edge > 0) {
     db->out_layers = db->out_flags = 0;
     return fail(h, SCANN_ERR_UNSUPPORTED, "forward: local-attention outputs need the fused first layer (not with scann_set_debug or SCANN_FUSE_BASIS=0)");
   }
   if (!fuse_basis) {
-    if (c.g_update) launch_basis(h->basis, db->dist, db->weight, db->n_edge, g_of(0), s);
-    else launch_basis_raw(h->cd, db->dist, db->n_edge, db->gd, s);
+    if (c.g_update) launch_basis(W->basis, db->dist, db->weight, db->n_edge, g_of(0), s);
+    else launch_basis_raw(W->cd, db->dist, db->n_edge, b.gd, s);  // (the Gaussians of the distances: model independent, one launch per set run)
   }
   if (tm) tm->mark(0);
 
   const bool general_embed = c.use_ring || c.feature_cgcnn;
   if (general_embed) {
-    EmbedArgs e = h->embed;
-    e.n_atom = db->n_atom; e.atomic = db->atomic; e.c0 = db->c0;
-    e.ring = c.use_ring ? db->ring : nullptr;
-    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
-    launch_embed(e, s);
+    for (int m = 0; m < std::max(nm, 1); ++m) {  // (no SET instantiation: one launch per member)
+      EmbedArgs e = nm ? o.members[m]->embed : W->embed;
+      e.n_atom = db->n_atom; e.atomic = db->atomic;
+      e.c0 = reinterpret_cast<float*>(reinterpret_cast<char*>(b.c0) + m * ast);
+      e.ring = c.use_ring ? db->ring : nullptr;
+      e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+      launch_embed(e, s);
+    }
     if (tm) tm->mark(0);
   }
   // first layer from per-species tables: no atom launch at all (see EdgeArgs::species)
   // (not with chunked atoms: edge_merge_kernel reads the query rows per atom)
-  const bool species0 = fuse_basis && h->species_tables && !general_embed && h->train_drop_p == 0.f && !(mc && mc->p_drop > 0.f) && h->sp_c &&
-                        db->n_big == 0;
-  if (species0 && h->sp_dirty) {
+  const bool species0 = fuse_basis && h->species_tables && !general_embed && !(mc && mc->p_drop > 0.f) && W->sp_c && db->n_big == 0;
+  bool sp_dirty = W->sp_dirty;  // (a set launch: the whole run's tables again when any of its members' are to be computed)
+  for (int m = 1; m < nm; ++m) sp_dirty |= o.members[m]->sp_dirty;
+  if (species0 && sp_dirty) {
     AtomArgs a{};
-    a.n_atom = c.n_atoms; a.x = h->lut; a.ffn = 0; a.c = h->sp_c;
+    a.n_atom = c.n_atoms; a.x = W->lut; a.ffn = 0; a.c = W->sp_c;
     a.range_flag = rflag; a.layer = 0;
-    const LayerParams& p = h->layers[0];
+    const LayerParams& p = W->layers[0];
     a.mode = 0;
     a.WAh = p.W1h; a.bA = p.bg; a.WBh = p.W3h; a.WCh = p.Wqh; a.bC = p.bq;
-    a.oA = h->sp_P1; a.oB = h->sp_P3; a.oC = h->sp_q;
+    a.oA = W->sp_P1; a.oB = W->sp_P3; a.oC = W->sp_q;
+    a.n_member = nm; a.m_w = a.m_x = a.m_o = wst;
     launch_atom(a, s);
     HIPCHK(h, hipStreamSynchronize(s));  // once per weight change: forwards on the handle's other streams read the tables too
-    h->sp_dirty = false;
+    W->sp_dirty = false;
+    for (int m = 1; m < nm; ++m) o.members[m]->sp_dirty = false;
   }
+  const bool keep_bwd = tr && tr->keep_backward;
   for (int l = 0; l <= L; ++l) {
     // training forward through edge_kernel_lean: q, V, T, ang, K of every layer are kept for the backward
-    const bool keep = h->debug && h->in_train_forward && db->keep_K && l < L;
+    const bool keep = keep_bwd && db->keep_K && l < L;
     // atom kernel at the head of layer l: ResidualNorm of layer l-1, centres, projections of layer l
     AtomArgs a{};
     a.n_atom = db->n_atom;
+    a.n_member = nm; a.m_w = wst; a.m_x = a.m_o = ast;
     if (l == 0) {
-      a.x = general_embed ? db->c0 : h->lut;
+      a.x = general_embed ? b.c0 : W->lut;
       a.x_index = general_embed ? nullptr : db->atomic;
       a.ffn = 0;
+      if (!general_embed) a.m_x = wst;
     } else {
       a.x = ctx_of(l - 1);
       a.x_index = nullptr;
       a.ffn = c.use_attn_norm ? 1 : 0;
-      const LayerParams& pp = h->layers[l - 1];
+      const LayerParams& pp = W->layers[l - 1];
       a.Wf1h = pp.Wf1h; a.bf1 = pp.bf1; a.Wf2h = pp.Wf2h; a.bf2 = pp.bf2; a.lnr_g = pp.lnr_g; a.lnr_b = pp.lnr_b;
-      if (a.ffn && h->debug && h->in_train_forward && db->keep_T2) {
+      if (a.ffn && keep_bwd && db->keep_T2) {
         a.keep_pre1 = db->keep_pre1 + (size_t)(l - 1) * nA_; a.keep_H1 = db->keep_H1 + (size_t)(l - 1) * nA_;
         a.keep_T2 = db->keep_T2 + (size_t)(l - 1) * nA_;
       }
     }
     a.c = c_of(l);
     a.range_flag = rflag; a.layer = l;
-    if (h->train_drop_p > 0.f) {  // training-mode Dropout(0.1) layers (scann_model.py:374, attention.py:29)
-      a.drop_p = (l == 0 || c.use_attn_norm) ? h->train_drop_p : 0.f;
-      a.drop_seed = h->train_seed;
+    if (tr && tr->drop_p > 0.f) {  // training-mode Dropout(0.1) layers (scann_model.py:374, attention.py:29)
+      a.drop_p = (l == 0 || c.use_attn_norm) ? tr->drop_p : 0.f;
+      a.drop_seed = tr->seed;
       a.drop_tag = l == 0 ? DROP_TAG_EMBED : (unsigned)(l - 1);
     }
     if (mc && mc->p_drop > 0.f && (l == 0 || c.use_attn_norm)) {  // the same sites and tags, structure-local masks
@@ -344,16 +367,16 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
       a.mc_t = mc->t;
     }
     if (l < L) {
-      const LayerParams& p = h->layers[l];
+      const LayerParams& p = W->layers[l];
       a.mode = c.g_update ? 0 : 1;
       a.WAh = p.W1h; a.bA = p.bg; a.WBh = p.W3h; a.WCh = p.Wqh; a.bC = p.bq;
-      a.oA = db->P1; a.oB = db->P3; a.oC = keep ? db->keep_q + (size_t)l * nA_ : db->q;
+      a.oA = b.P1; a.oB = b.P3; a.oC = keep ? db->keep_q + (size_t)l * nA_ : b.q;
     } else {
       a.mode = 2;
-      a.WAh = h->head.Wah; a.bA = h->head.ba; a.WCh = h->head.Wgqh; a.bC = h->head.bgq; a.WDh = h->head.Wgkh; a.bD = h->head.bgk;
-      a.oB = db->gk; a.oC = db->gq;
-      if (h->debug && h->in_train_forward && db->keep_preA) { a.keep_preA = db->keep_preA; a.keep_z = db->keep_z; }
-      a.out_z = db->out_z;
+      a.WAh = W->head.Wah; a.bA = W->head.ba; a.WCh = W->head.Wgqh; a.bC = W->head.bgq; a.WDh = W->head.Wgkh; a.bD = W->head.bgk;
+      a.oB = b.gk; a.oC = b.gq;
+      if (keep_bwd && db->keep_preA) { a.keep_preA = db->keep_preA; a.keep_z = db->keep_z; }
+      a.out_z = o.outputs ? db->out_z : nullptr;
     }
 #ifdef SCANN_STAMPS
     if (getenv("SCANN_STAMP_ATOM") && l >= 1 && l < L) {  // phase clocks of atom_kernel<true, 0> (the last such launch wins)
@@ -366,16 +389,16 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     if (exact) {  // fp32 fragment-order images in place of the split-fp16 ones
       a.exact = 1;
       if (l > 0 && a.ffn) {
-        const LayerParams& pp = h->layers[l - 1];
+        const LayerParams& pp = W->layers[l - 1];
         a.Wf1h = reinterpret_cast<const _Float16*>(pp.Wf1p); a.Wf2h = reinterpret_cast<const _Float16*>(pp.Wf2p);
       }
       if (l < L) {
-        const LayerParams& p = h->layers[l];
+        const LayerParams& p = W->layers[l];
         a.WAh = reinterpret_cast<const _Float16*>(p.W1p); a.WBh = reinterpret_cast<const _Float16*>(p.W3p);
         a.WCh = reinterpret_cast<const _Float16*>(p.Wqp);
       } else {
-        a.WAh = reinterpret_cast<const _Float16*>(h->head.Wap); a.WCh = reinterpret_cast<const _Float16*>(h->head.Wgqp);
-        a.WDh = reinterpret_cast<const _Float16*>(h->head.Wgkp);
+        a.WAh = reinterpret_cast<const _Float16*>(W->head.Wap); a.WCh = reinterpret_cast<const _Float16*>(W->head.Wgqp);
+        a.WDh = reinterpret_cast<const _Float16*>(W->head.Wgkp);
       }
     }
     if (!(species0 && l == 0)) launch_atom(a, s);
@@ -384,13 +407,14 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     EdgeArgs ea{};
     ea.tiles = db->tiles; ea.n_tile = db->n_tile; ea.g_update = c.g_update; ea.tile_rows = db->tile_rows;
     ea.edge_offset = db->edge_offset; ea.edge_col = db->edge_col; ea.edge_row = db->edge_row;
-    ea.geom = g_of(l); ea.geom_out = h->debug && c.g_update ? g_of(l + 1) : nullptr; ea.gd = db->gd; ea.edge_weight = db->weight;
-    if (fuse_basis && l == 0) { ea.fuse_basis = 1; ea.dist = db->dist; ea.basis = h->basis; }
+    ea.geom = g_of(l); ea.geom_out = debug && c.g_update ? g_of(l + 1) : nullptr; ea.gd = b.gd; ea.edge_weight = db->weight;
+    if (fuse_basis && l == 0) { ea.fuse_basis = 1; ea.dist = db->dist; ea.basis = W->basis; }
     ea.n_edge = db->n_edge;
     ea.geom_rows = fuse_basis ? 0 : 1;  // piece-major tiles only when the first layer computed its own geometry rows (plain inference)
-    ea.geom_dead = (l == L - 1 && !h->debug) ? 1 : 0;  // the geometry leaving the last layer is never consumed (141 MB of writes per 16-batch launch)
-    ea.c = c_of(l); ea.P1 = db->P1; ea.P3 = db->P3; ea.q = keep ? db->keep_q + (size_t)l * nA_ : db->q; ea.ctx = ctx_of(l);
-    if (species0 && l == 0) { ea.species = db->atomic; ea.c = h->sp_c; ea.P1 = h->sp_P1; ea.P3 = h->sp_P3; ea.q = h->sp_q; }
+    ea.geom_dead = (l == L - 1 && !debug) ? 1 : 0;  // the geometry leaving the last layer is never consumed (141 MB of writes per 16-batch launch)
+    ea.c = c_of(l); ea.P1 = b.P1; ea.P3 = b.P3; ea.q = keep ? db->keep_q + (size_t)l * nA_ : b.q; ea.ctx = ctx_of(l);
+    ea.n_member = nm; ea.m_w = wst; ea.m_a = ea.m_r = ast;
+    if (species0 && l == 0) { ea.species = db->atomic; ea.c = W->sp_c; ea.P1 = W->sp_P1; ea.P3 = W->sp_P3; ea.q = W->sp_q; ea.m_r = wst; }
     if (keep) {
       ea.keep_V = db->keep_V + (size_t)l * nE_; ea.keep_K = db->keep_K + (size_t)l * nE_;
       // T = swish(V) + G and ang = c[j] * G' are formed again where the fused backward needs them (edge_bwd_kernel, the key weight
@@ -399,7 +423,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
       if (db->keep_ang) ea.keep_ang = db->keep_ang + (size_t)l * nE_;
       db->kept = true;
     }
-    ea.p = h->layers[l];
+    ea.p = W->layers[l];
     if (exact) {
       ea.exact = 1;
       ea.p.W2h = reinterpret_cast<const _Float16*>(ea.p.W2p); ea.p.Wkh = reinterpret_cast<const _Float16*>(ea.p.Wkp);
@@ -408,19 +432,20 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     // (the first layer's launch with the basis MLP fused in is a different kernel: not part of edge_kernel's sampled average)
     // (... nor is the last layer's, whose geometry is not stored -- the DEAD instantiation, ~10 % shorter: the sampled average is the
     //  kernel rocprofv3 lists as edge_kernel<true, RT, false, false, false, false>, and its algorithmic bytes include that store)
-    const bool sample = !tm && !mc && h->time_every > 0 && (h->time_count % h->time_every) == 0 && !(fuse_basis && l == 0) && !(ea.geom_dead && L > 2);
+    const bool sample = !tm && !mc && !o.of_set && h->time_every > 0 && (h->time_count % h->time_every) == 0 && !(fuse_basis && l == 0) &&
+                        !(ea.geom_dead && L > 2);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (sample) {
       (void)hipEventCreateWithFlags(&ev0, kTimingEventFlags);
       (void)hipEventCreateWithFlags(&ev1, kTimingEventFlags);
       (void)hipEventRecord(ev0, s);
     }
-    ea.tile_part = db->tile_part; ea.part_buf = db->part_buf;
+    ea.tile_part = db->tile_part; ea.part_buf = b.part_buf;
     ea.xcd_remap = h->xcd_remap;
-    ea.attn_out = attn_out_of(h, db, l);
-    if (h->in_train_forward && h->attn_drop_p > 0.f) {  // validation passes run with scann_set_attention_dropout(h, 0): trainer.fit
-      ea.attn_drop_p = h->attn_drop_p;
-      ea.attn_drop_seed = h->train_seed;
+    ea.attn_out = o.outputs ? attn_out_of(h, db, l) : nullptr;
+    if (tr && tr->attn_p > 0.f) {  // validation passes run with scann_set_attention_dropout(h, 0): trainer.fit
+      ea.attn_drop_p = tr->attn_p;
+      ea.attn_drop_seed = tr->seed;
       ea.attn_drop_tag = DROP_TAG_ATTN + (unsigned)l;
     }
     if (mc && mc->p_attn > 0.f && db->n_edge > 0) {
@@ -438,8 +463,9 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     }
 #endif
     launch_edge(ea, s);
-    launch_edge_merge(db->big_tab, db->n_big, db->part_buf, ea.q, ea.p.ln_g, ea.p.ln_b, ea.ctx, rflag, l, s);
-    if (ea.attn_out) launch_attn_merge(db->big_tab, db->n_big, db->part_buf, db->edge_offset, db->tile_rows, ea.attn_out, s);
+    if (nm) launch_edge_merge_set(db->big_tab, db->n_big, b.part_buf, ea.q, ea.p.ln_g, ea.p.ln_b, ea.ctx, rflag, l, nm, ast, wst, s);
+    else launch_edge_merge(db->big_tab, db->n_big, b.part_buf, ea.q, ea.p.ln_g, ea.p.ln_b, ea.ctx, rflag, l, s);
+    if (ea.attn_out) launch_attn_merge(db->big_tab, db->n_big, b.part_buf, db->edge_offset, db->tile_rows, ea.attn_out, s);
     if (sample) {
       (void)hipEventRecord(ev1, s);
       h->time_ev.push_back(ev0);
@@ -448,11 +474,13 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, boo
     }
     if (tm) tm->mark(2);
   }
-  if (!tm && !mc) h->time_count++;
+  if (!tm && !mc && !o.of_set) h->time_count++;
   ReadoutArgs r{};
   r.mol_offset = db->mol_offset; r.n_struct = db->n_struct; r.max_atoms = db->max_atoms;
-  r.gq = db->gq; r.gk = db->gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = c.relu_out;
-  r.p = h->head; r.ga_attn = db->ga; r.y = db->y; r.bf_out = db->out_bf;
+  r.gq = b.gq; r.gk = b.gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = W->cfg.relu_out;
+  for (int m = 1; m < nm; ++m) r.relu_out |= o.members[m]->cfg.relu_out << m;  // (a set launch: bit m is member m's mrelu)
+  r.p = W->head; r.ga_attn = b.ga; r.y = b.y; r.bf_out = o.outputs ? db->out_bf : nullptr;
+  r.n_member = nm; r.m_w = wst; r.m_a = ast; r.m_g = o.m_g; r.m_y = o.m_y;
   launch_readout(r, s);
   if (tm) tm->mark(3);
   HIPCHK(h, hipGetLastError());
@@ -468,7 +496,7 @@ int scann_forward_resident(scann_handle_t* h, scann_dbatch_t* db, int stream_slo
   HIPCHK(h, hipSetDevice(h->device));
   const int slot = ((stream_slot % h->nstream) + h->nstream) % h->nstream;
   db->last_slot = slot;
-  return run_forward(h, db, h->streams[slot], nullptr);
+  return run_forward(h, db, h->streams[slot]);
 }
 
 int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t* prof) {
@@ -477,7 +505,9 @@ int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t
   memset(prof, 0, sizeof(*prof));
   Timer tm{h->streams[0], true, {}, {}};
   db->last_slot = 0;
-  const int r = run_forward(h, db, h->streams[0], &tm);
+  FwdOpts o;
+  o.tm = &tm;
+  const int r = run_forward(h, db, h->streams[0], o);
   if (r) return r;
   HIPCHK(h, hipStreamSynchronize(h->streams[0]));
   if (const int rp = check_pack_flag(h, db, "scann_forward_profile")) return rp;
@@ -617,8 +647,8 @@ double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag,
 
 // Monte Carlo dropout: n_samples inference forwards of the resident batch, each with the Dropout layers of the training graph active under
 // structure-local masks (scann_internal.h: mc_seed), y and the GlobalAttention scores of sample t written to row t of [T, B] / [T, n_atom]
-// buffers in the batch's workspace, and one reduction per output.  Saves and restores whatever of the handle and the batch a forward
-// touches (selected outputs, debug mode, edge timing, y / ga), so that later forwards and downloads see what they would have seen.
+// buffers in the batch's workspace, and one reduction per output.  The samples' options ask for no selected outputs and no debug buffers and
+// send y / ga to those rows, so that later forwards and downloads see what they would have seen.
 int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, uint64_t seed, const uint64_t* keys, float p_drop, float p_attn,
                      float* y_mean, float* y_std, float* ga_mean, float* ga_std, float* y_samples) {
   if (!h || !db || !y_mean || !y_std) return fail(h, SCANN_ERR_INVALID, "scann_predict_mc: null argument");
@@ -656,33 +686,20 @@ int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, u
   HIPCHK(h, wait_upload(db, s));
   if (keys && B > 0) HIPCHK(h, hipMemcpyAsync(d_keys, keys, (size_t)B * 8, hipMemcpyHostToDevice, s));
   launch_mc_rows(db->mol_offset, db->edge_offset, keys ? d_keys : nullptr, B, A, rows, s);
-  // what a forward of this call would otherwise change
-  const uint64_t h_out_layers = h->out_layers, d_out_layers = db->out_layers;
-  const int32_t h_out_flags = h->out_flags, d_out_flags = db->out_flags;
-  float *const d_out_attn = db->out_attn, *const d_out_z = db->out_z, *const d_out_bf = db->out_bf;
-  const bool debug = h->debug;
-  float *const y0 = db->y, *const ga0 = db->ga;
-  h->out_layers = 0;
-  h->out_flags = 0;
-  h->debug = false;
   McState mc{rows, (unsigned long long)seed, 0u, p_drop, p_attn};
-  h->mc = &mc;
+  FwdBufs bufs(db);
+  FwdOpts o;
+  o.mc = &mc;
+  o.keep_layers = 0;
+  o.outputs = false;
+  o.bufs = &bufs;
   int r = SCANN_OK;
   for (int t = 0; t < T && r == SCANN_OK; ++t) {
     mc.t = (uint32_t)t;
-    db->y = ys + (size_t)t * B;
-    db->ga = gs + (size_t)t * A;
-    r = run_forward(h, db, s, nullptr);
+    bufs.y = ys + (size_t)t * B;
+    bufs.ga = gs + (size_t)t * A;
+    r = run_forward(h, db, s, o);
   }
-  h->mc = nullptr;
-  db->y = y0;
-  db->ga = ga0;
-  h->out_layers = h_out_layers;
-  h->out_flags = h_out_flags;
-  db->out_layers = d_out_layers;
-  db->out_flags = d_out_flags;
-  db->out_attn = d_out_attn; db->out_z = d_out_z; db->out_bf = d_out_bf;
-  h->debug = debug;
   if (r == SCANN_OK) {
     launch_mc_reduce(ys, T, B, o_ym, o_ys, s);
     if (ga_mean || ga_std) launch_mc_reduce(gs, T, A, o_gm, o_gs, s);

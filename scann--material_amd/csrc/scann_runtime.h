@@ -90,7 +90,7 @@ struct Timer;  // scann_forward_profile's launch timer (scann_forward.cpp)
 struct ModelSet;  // scann_models_load's members (scann_models.cpp)
 void free_models(ModelSet* ms);  // no work of the set may still be running
 
-// scann_predict_mc: the sample run_forward is computing (scann_handle::mc, set for the duration of the call)
+// scann_predict_mc: the sample a forward is to compute (FwdOpts::mc)
 struct McState {
   const McRow* rows;        // [n_atom] of the batch (launch_mc_rows)
   unsigned long long seed;  // the call's seed
@@ -134,7 +134,6 @@ struct scann_handle {
   std::map<std::string, int64_t> gt_off;  // "<tensor name>#<block>" -> offset in g_WT
   float* g_WT = nullptr;
   int gt_max = 0;                         // elements of the largest block
-  GenKeep* gen_keep = nullptr;            // inside a training forward: where run_forward_generic keeps its tensors
   bool weights_exact = false;  // a loaded 128x128 kernel has |w| >= 255.9: the split-fp16 images cannot hold it, inference runs exact
   bool force_exact = false;    // env SCANN_EXACT=1: every inference forward on the exact-fp32 kernels (test / diagnosis switch)
   bool strict_range = false;   // env SCANN_STRICT_RANGE=1: SCANN_ERR_RANGE instead of the exact-fp32 re-run of an inference forward
@@ -168,12 +167,8 @@ struct scann_handle {
   // scann_input_grads: where its backward's parameter-gradient side products go (never the training state above), allocated by its first call
   float* ig_grad = nullptr;
   int64_t t_step = 0;
-  float train_drop_p = 0.f;            // > 0 only inside scann_train_forward
   float attn_drop_p = 0.f;             // use_drop: Dropout(0.05) on attention weights (scann_set_attention_dropout)
   bool deterministic = false;          // scann_set_deterministic: the backward's small reductions in a fixed order, no float atomics
-  bool in_train_forward = false;
-  unsigned long long train_seed = 0;
-  const McState* mc = nullptr;         // inside scann_predict_mc: the inference forwards apply that sample's dropout masks
   ncclComm_t comm = nullptr;
   // scann_train_step_begin / _end: up to two steps may be enqueued before the first is ended (the host prepares step k + 1 while the
   // device runs step k); slot = step number & 1.  Slot 2 of the targets belongs to the synchronous scann_train_forward.
@@ -306,9 +301,49 @@ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // allocated; need non-null: validation only, *need = the floats such a placement takes
 int load_weights(scann_handle* h, const float* blob, const scann_tensor_desc_t* manifest, int n, float* at, size_t* need);
 
-// scann_forward.cpp: the forward graph as a launch schedule on one stream; exact: on the exact-fp32 instantiations
-// (an inference forward also writes the outputs the handle selected, scann_set_outputs)
-int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, Timer* tm, bool exact = false);
+// The workspace pointers a forward writes: the batch's own (FwdBufs(db)) unless the caller sends the activations or the results
+// elsewhere (scann_predict_mc: row t of its sample matrices as y / ga; a set forward: a member's slice of the set workspace)
+struct FwdBufs {
+  float *geom, *gd, *c0, *c, *ctx, *P1, *P3, *q, *gq, *gk, *part_buf, *y, *ga;
+  explicit FwdBufs(const scann_dbatch* db)
+      : geom(db->geom), gd(db->gd), c0(db->c0), c(db->c), ctx(db->ctx), P1(db->P1), P3(db->P3), q(db->q), gq(db->gq), gk(db->gk),
+        part_buf(db->part_buf), y(db->y), ga(db->ga) {}
+};
+
+// A training forward: the Dropout layers active, the tensors of the backward kept
+struct FwdTrain {
+  float drop_p, attn_p;     // Dropout(0.1) layers / attention-weight rates
+  unsigned long long seed;
+  bool keep_backward;       // 128 / 8 kernels: q, V, T, ang, K, the ResidualNorm and after_Lc intermediates go to the batch's keep_* buffers
+  GenKeep* gen;             // generic widths: where every intermediate is kept
+};
+
+// The forward run_forward is to enqueue.  The defaults mean: the plain inference forward of the batch on the handle's own weights.
+struct FwdOpts {
+  bool exact = false;               // on the exact-fp32 instantiations (forced by SCANN_EXACT=1 and by weights the split-fp16 images cannot hold)
+  Timer* tm = nullptr;              // scann_forward_profile
+  const FwdTrain* train = nullptr;  // kind of forward -- null, null: inference; a training forward; ...
+  const McState* mc = nullptr;      // ... a Monte Carlo dropout sample (an inference forward under that sample's masks)
+  int keep_layers = -1;             // every layer's centres / context / geometry into the debug buffers (scann_debug_read); -1: the handle's
+                                    // scann_set_debug switch
+  bool outputs = true;              // an inference forward writes the outputs the handle selected (scann_set_outputs) and db->out_* record
+                                    // them (a training forward: that it wrote none); false: no outputs, db->out_* untouched
+  const FwdBufs* bufs = nullptr;    // where activations and results go; null: the batch's own workspace
+  int slot = -1;                    // stream slot whose range-guard word the kernels write; -1: db->last_slot
+  // whose weight images (layers, head, basis, lut, sp_*, cd, embed, g_*, weights_exact, cfg.relu_out); null: the handle's own.  Streams,
+  // switches, range-guard words, timing state and the error text are always those of the handle the call is made on
+  scann_handle* weights = nullptr;
+  // one launch sequence for n_member members of a model set (the SET instantiations; never with exact, train, mc, keep_layers): their
+  // weight holders, whose images lie m_w bytes apart; bufs is the first one's, the others' m_a bytes (y: m_y, ga: m_g) further each
+  int n_member = 0;                 // 0: not a set launch
+  scann_handle* const* members = nullptr;
+  int64_t m_w = 0, m_a = 0, m_y = 0, m_g = 0;
+  // part of a set forward: not the batch's single-model work (db->idle / db->fwd_pending stay; set work is db->set_busy), no edge-timing samples
+  bool of_set = false;
+};
+
+// scann_forward.cpp: the forward graph as a launch schedule on stream s
+int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o = FwdOpts());
 
 // scann_batch.cpp
 int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who);

@@ -127,8 +127,9 @@ int64_t spec_offset(const scann_handle* h, const std::string& name) {
 }  // namespace
 
 // the training forward (activations kept for the backward) and the batch's sum of squared errors + count -> w->sse[0..1]; no sync
-static int train_forward_impl(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, uint64_t seed, scann_train_ws** wout,
-                              int slot) {  // slot 0 / 1: a scann_train_step in that slot; 2: the synchronous scann_train_forward
+// attn_p: the attention-dropout rate (training: the handle's scann_set_attention_dropout; scann_input_grads: 0)
+static int train_forward_impl(scann_handle_t* h, scann_dbatch_t* db, const float* targets, float dropout, float attn_p, uint64_t seed,
+                              scann_train_ws** wout, int slot) {  // slot 0 / 1: a scann_train_step in that slot; 2: the synchronous scann_train_forward
   const bool fused_step = slot < 2;
   scann_train_ws* w = nullptr;
   int r = ensure_train_ws(h, db, &w);
@@ -141,24 +142,18 @@ static int train_forward_impl(scann_handle_t* h, scann_dbatch_t* db, const float
   db->keep_pre1 = w->keep_pre1; db->keep_H1 = w->keep_H1; db->keep_T2 = w->keep_T2;
   db->keep_preA = w->keep_preA; db->keep_z = w->keep_z;
   db->kept = false;
-  const bool dbg = h->debug;
   if (h->generic) {  // run_forward_generic keeps its tensors in w->gen
     w->gen.drop_p = dropout;
-    w->gen.attn_p = h->attn_drop_p;
+    w->gen.attn_p = attn_p;
     w->gen.seed = seed;
-    h->gen_keep = &w->gen;
   }
-  h->debug = !h->generic;  // keep centres / geometry / context of every layer (and, with edge_kernel_lean, q / V / T / ang / K)
-  h->train_drop_p = dropout;
-  h->train_seed = seed;
-  h->in_train_forward = true;
-  w->attn_p = h->attn_drop_p;
+  w->attn_p = attn_p;
+  const FwdTrain tr{dropout, attn_p, (unsigned long long)seed, /*keep_backward=*/true, h->generic ? &w->gen : nullptr};
+  FwdOpts o;
+  o.train = &tr;
+  o.keep_layers = !h->generic;  // keep centres / geometry / context of every layer (and, with edge_kernel_lean, q / V / T / ang / K)
   db->last_slot = 0;  // training runs on stream 0 (its range-guard word is slot 0's)
-  r = run_forward(h, db, s, nullptr);
-  h->in_train_forward = false;
-  h->train_drop_p = 0.f;
-  h->debug = dbg;
-  h->gen_keep = nullptr;
+  r = run_forward(h, db, s, o);
   if (r) return r;
   if (h->generic) {
     db->kept = true;
@@ -895,7 +890,7 @@ int scann_train_forward(scann_handle_t* h, scann_dbatch_t* db, const float* targ
   if (!h->t_master) return fail(h, SCANN_ERR_INVALID, "scann_train_forward: call scann_train_begin first");
   HIPCHK(h, hipSetDevice(h->device));
   scann_train_ws* w = nullptr;
-  const int r = train_forward_impl(h, db, targets, dropout, seed, &w, 2);
+  const int r = train_forward_impl(h, db, targets, dropout, h->attn_drop_p, seed, &w, 2);
   if (r) return r;
   hipStream_t s = h->streams[0];
   HIPCHK(h, hipMemcpyAsync(sse_out, w->sse, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -949,7 +944,7 @@ int scann_train_step_begin(scann_handle_t* h, scann_dbatch_t* db, const float* t
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->streams[0];
   scann_train_ws* w = nullptr;
-  int r = train_forward_impl(h, db, targets, dropout, seed, &w, slot);
+  int r = train_forward_impl(h, db, targets, dropout, h->attn_drop_p, seed, &w, slot);
   if (r) return r;
   // From here on kernels of this step are queued: a failure below must not leave the slot's pinned buffers (targets, statistics)
   // looking free while that work is still running -- drain the stream before the error goes back (the step is not counted).
@@ -1022,11 +1017,8 @@ int scann_input_grads(scann_handle_t* h, scann_dbatch_t* db, float* y, float* d_
     if (const int r = build_gen_transposes(h)) return r;
   if (!h->ig_grad) HIPCHK(h, hipMalloc((void**)&h->ig_grad, h->host_master.size() * 4));
   hipStream_t s = h->streams[0];
-  const float attn_p = h->attn_drop_p;
-  h->attn_drop_p = 0.f;
   scann_train_ws* w = nullptr;
-  int r = train_forward_impl(h, db, nullptr, 0.f, 0, &w, 2);
-  h->attn_drop_p = attn_p;
+  int r = train_forward_impl(h, db, nullptr, 0.f, 0.f, 0, &w, 2);
   if (r) {
     db->kept = false;
     return r;
