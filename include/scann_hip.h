@@ -351,6 +351,52 @@ int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, fl
 int64_t scann_rollout_floats(scann_handle_t* h, const scann_dbatch_t* db);
 int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residual, int32_t head, int32_t depth, float* y, float* ga,
                             float* attribution, float* rollout);
+
+/* ---- latent-space index: the nearest training structures of a prediction, searched on the device ----
+ * An index holds N < 2^31 rows of `dim` fp32 values in insertion order (position 0 .. N-1); each row carries an int64 id and an int32
+ * atom (-1 for a structure-level row).  For a query vector q and a row r
+ *   dist2(q, r) = acc_dim,  acc_0 = 0,  acc_{j+1} = fmaf(q[j] - r[j], q[j] - r[j], acc_j)
+ * in fp32, the difference rounded once, columns ascending (scann_knn_distsq is this chain on the host: the kernel's bits), and the k
+ * nearest rows of q are the first k rows under the TOTAL order (dist2 ascending, then position ascending).  A query's result therefore
+ * depends on the query and the index contents only: not on the batch it is in, on how the rows are split over workgroups or on how many
+ * calls built the index.  With query ids, rows whose id equals the query's are skipped (leave-one-out distances of a set to itself).
+ * Places for which no row qualifies hold id -1, atom -1, position -1, dist2 +inf; a row whose distance is NaN never qualifies.  The
+ * distance is not the product form |q|^2 + |r|^2 - 2 q.r, which loses near-duplicates to cancellation; its error against exact
+ * arithmetic is at most (dim + 3) * 2^-24 relative.
+ *
+ * The rows live in device blocks of the handle's cache, allocated a chunk (about 64 MiB) at a time; rows already stored are never moved.
+ * EVERY call below is synchronous (it returns when the device has finished), so no query is in flight while rows are added.
+ * scann_index_add / scann_index_query take host vectors (rows [n * dim], q [nq * dim]); ids NULL: the row's position; atoms NULL: -1;
+ * query_ids NULL: nothing is skipped.  scann_index_read copies rows [first, first + n) back (any output NULL), for saving an index.
+ * Outputs of the queries: dist2, ids, atoms, pos [nq * k] (ids, atoms, pos may be NULL).
+ * level = SCANN_OUT_BF_PROPERTY (one row per structure of the batch) or SCANN_OUT_AFTER_LC (one row per atom in packed order, atom = its
+ * index within its structure).  scann_index_add_batch runs one inference forward of the resident batch -- with the level's output added
+ * to what scann_set_outputs selected for that forward only; the handle's selection is put back before the call returns, also when it
+ * fails -- and appends the level's rows device to device; ids [n_struct] (NULL: structure level the position, atom level the structure's
+ * index in the batch).  scann_index_query_batch runs the same forward and searches the level's rows: y [n_struct] and ga [n_atom] (or
+ * NULL) are bitwise those of scann_forward_resident + scann_batch_download (range guard, exact-fp32 re-run, SCANN_STRICT_RANGE as there);
+ * query_ids [n_struct] or NULL.  After either call the batch's output block belongs to that forward, as after scann_attention_rollout.
+ * SCANN_ERR_INVALID before anything is launched: a null argument, k outside 1 .. SCANN_KNN_MAX_K, a dim outside 1 .. 1024 or that is
+ * not the model's dense_out / global_dim for the level, an unknown level, an empty query, an index created on another handle.  An empty
+ * index answers with the +inf tail.  The calls work on inference and training handles, at 128 / 8 and at generic widths and on handles
+ * whose forwards run on the exact-fp32 kernels, and change neither weights, gradients, Adam state, step counter nor the selected
+ * outputs.  An index must be freed before its handle's device is reset; scann_index_free(h, idx) needs no live handle (h may be NULL). */
+#define SCANN_KNN_MAX_K 32
+typedef struct scann_index scann_index_t;
+int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out);
+void scann_index_free(scann_handle_t* h, scann_index_t* idx);
+int64_t scann_index_size(const scann_index_t* idx);
+int scann_index_add(scann_handle_t* h, scann_index_t* idx, const float* rows, int64_t n, const int64_t* ids, const int32_t* atoms);
+int scann_index_read(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, float* rows, int64_t* ids, int32_t* atoms);
+int scann_index_query(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, int32_t k, float* dist2,
+                      int64_t* ids, int32_t* atoms, int32_t* pos);
+int scann_index_add_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* ids);
+int scann_index_query_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, int32_t k, float* y,
+                            float* ga, float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos);
+/* the kernel's distance chain on the host (no GPU work), one pair and out[i * n + r] for every (query i, row r) */
+float scann_knn_distsq(const float* q, const float* r, int64_t d);
+void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -8,6 +8,10 @@ mean and standard deviation of the prediction per structure and the mean and sta
 per structure, as ga_scores), each structure keyed by its index in the dataset.
 ``--rollout [--rollout-residual R] [--rollout-head K]`` also pickles the attention rollout as ``rollout_<target>.pickle``: one unpadded dict
 per structure with ``attribution`` [n] (the GA scores traced back to the atoms through the local-attention layers) and ``rollout`` [n, n].
+``--nearest K [--nearest-level atom] [--nearest-index FILE]`` also pickles ``nearest_<target>.pickle``: one unpadded dict per structure
+with the K nearest structures of the dataset in the model's latent space (``neighbor_id``: dataset indices, the structure itself left
+out; ``distance``; ``latent_distance``: their mean, an uncertainty measure), or per atom at ``--nearest-level atom`` (``neighbor_atom``
+as well).  With ``--nearest-index FILE`` a saved ``LatentIndex``, for example of the training set, is searched and nothing is left out.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -74,6 +78,8 @@ def main_with(args, make_set=None):
 def main(args):
     if args.with_models:
         return main_with(args)
+    if args.nearest and not 1 <= args.nearest <= 32:
+        raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     target = config["hyper"]["target"]
     print("Load pretrained weight for target ", target)
@@ -145,6 +151,38 @@ def main(args):
             for i in range(len(amask)):  # unpadded: the structure's own atoms
                 per.append({"attribution": r["atom_attribution"][i][amask[i], 0], "rollout": r["rollout"][i][np.ix_(amask[i], amask[i])]})
         pickle.dump(per, open(os.path.join(args.trained_model, "rollout_{}.pickle".format(target)), "wb"))
+    if args.nearest:
+        from scann.models import LatentIndex
+
+        if args.nearest_index:
+            index = LatentIndex.load(scann.model, args.nearest_index)
+            print("Nearest %d rows of %s (%s level, %d rows)" % (args.nearest, args.nearest_index, index.level, len(index)))
+        else:  # the dataset itself, every structure queried with its own dataset index left out
+            index = scann.build_index(data, level=args.nearest_level, ids=data.indexes)
+            print("Nearest %d of the dataset's own %d rows (%s level), leave-one-out" % (args.nearest, len(index), index.level))
+        per = nearest_records(scann, data, index, args.nearest, exclude=not args.nearest_index)
+        index.free()
+        pickle.dump(per, open(os.path.join(args.trained_model, "nearest_{}.pickle".format(target)), "wb"))
+
+
+def nearest_records(scann, data, index, k, exclude):
+    """--nearest: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = index.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        sel = data.indexes[b * data.batch_size:(b + 1) * data.batch_size]
+        r = scann.nearest(inputs, index, k=k, exclude_ids=sel if exclude else None)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["predict_property"][i, 0])}
+            if atom:  # the structure's own atoms
+                d.update(distance=r["distance"][i][amask[i]], neighbor_id=r["neighbor_id"][i][amask[i]],
+                         neighbor_atom=r["neighbor_atom"][i][amask[i]], latent_distance=r["latent_distance"][i][amask[i], 0])
+            else:
+                d.update(distance=r["distance"][i], neighbor_id=r["neighbor_id"][i], latent_distance=float(r["latent_distance"][i, 0]))
+            per.append(d)
+    return per
 
 
 def parser():
@@ -163,6 +201,13 @@ def parser():
                         "as rollout_<target>.pickle: one dict per structure, unpadded (attribution [n], rollout [n, n])")
     p.add_argument("--rollout-residual", type=float, default=0.5, help="weight of the skip connection in every layer of the rollout, 0 .. 1")
     p.add_argument("--rollout-head", type=int, default=-1, help="one attention head instead of the mean over the heads (-1)")
+    p.add_argument("--nearest", type=int, default=0,
+                   help="also pickle the K (1 .. 32) nearest structures of the dataset in latent space, leave-one-out, and their mean "
+                        "distance as nearest_<target>.pickle: one dict per structure, unpadded, ids = dataset indices")
+    p.add_argument("--nearest-level", type=str, default="structure", choices=["structure", "atom"],
+                   help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
+    p.add_argument("--nearest-index", type=str, default="",
+                   help="a saved LatentIndex (.npz) to search instead of the dataset itself; nothing is left out")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

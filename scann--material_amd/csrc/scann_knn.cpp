@@ -1,0 +1,356 @@
+// Latent-space index (include/scann_hip.h: scann_index_*): the rows of bf_property / after_Lc kept on the device in chunks that never
+// move, the exact k-nearest-neighbour search over them (scann_knn.hip) and the host twin of the kernel's distance chain.  Every call is
+// synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The forwards of
+// scann_index_add_batch / scann_index_query_batch are the public ones with the level's output flag added for that one forward, as
+// scann_attention_rollout adds its attention maps: y, the scores, the range guard and the exact re-run behave exactly as they do there.
+#include "scann_knn.h"
+#include "scann_runtime.h"
+
+using namespace scann;
+
+struct scann_index {
+  scann_handle* h = nullptr;
+  int device = 0;
+  int32_t dim = 0, stride = 0;  // stride: dim rounded up to a multiple of 4, the rest zero
+  int32_t chunk_rows = 0;       // rows per chunk (a multiple of 64): about 64 MiB of rows
+  int64_t n = 0;
+  std::vector<char*> chunks;    // device blocks of the handle's cache: rows [chunk_rows][stride] fp32, then ids [chunk_rows] int64
+  std::vector<int64_t> ids;     // host copies: what the calls report by position
+  std::vector<int32_t> atoms;
+  float* rows_of(size_t c) const { return reinterpret_cast<float*>(chunks[c]); }
+  int64_t* ids_of(size_t c) const { return reinterpret_cast<int64_t*>(chunks[c] + (size_t)chunk_rows * stride * 4); }
+  size_t chunk_bytes() const { return (size_t)chunk_rows * stride * 4 + (size_t)chunk_rows * 8; }
+};
+
+namespace {
+
+constexpr int KNN_QGROUP = 1024;     // queries per pass over the index (bounds the partial lists)
+constexpr int KNN_RANGES = 1024;     // about as many row ranges, i.e. workgroups per 128 queries, as this
+constexpr int KNN_MAX_RANGES = 65536;
+
+inline float dist2_chain(const float* q, const float* r, int64_t d) {
+  float acc = 0.f;
+  for (int64_t j = 0; j < d; ++j) {
+    const float t = q[j] - r[j];
+    acc = fmaf(t, t, acc);
+  }
+  return acc;
+}
+void dist2_matrix_plain(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out) {
+  for (int64_t i = 0; i < nq; ++i)
+    for (int64_t r = 0; r < n; ++r) out[i * n + r] = dist2_chain(q + i * d, rows + r * d, d);
+}
+// the same loop where the host has a fused multiply-add instruction: fmaf is then one instruction instead of a libm call; it is correctly
+// rounded either way, so the bits are the same
+__attribute__((target("fma"))) void dist2_matrix_fma(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out) {
+  for (int64_t i = 0; i < nq; ++i)
+    for (int64_t r = 0; r < n; ++r) {
+      const float *a = q + i * d, *b = rows + r * d;
+      float acc = 0.f;
+      for (int64_t j = 0; j < d; ++j) {
+        const float t = a[j] - b[j];
+        acc = __builtin_fmaf(t, t, acc);
+      }
+      out[i * n + r] = acc;
+    }
+}
+
+int check_index(scann_handle* h, const scann_index* ix, const char* who) {
+  if (!h || !ix) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": null argument");
+  if (ix->h != h) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": the index belongs to another handle");
+  return SCANN_OK;
+}
+
+int check_k(scann_handle* h, int32_t k, const char* who) {
+  if (k < 1 || k > SCANN_KNN_MAX_K)
+    return fail(h, SCANN_ERR_INVALID, std::string(who) + ": k " + std::to_string(k) + " outside 1 .. " + std::to_string(SCANN_KNN_MAX_K));
+  return SCANN_OK;
+}
+
+// the level's width in this model, or 0 for an unknown level
+int level_dim(const scann_handle* h, int32_t level) {
+  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
+}
+int check_level(scann_handle* h, const scann_index* ix, int32_t level, const char* who) {
+  const int d = level_dim(h, level);
+  if (!d) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  if (d != ix->dim)
+    return fail(h, SCANN_ERR_INVALID, std::string(who) + ": the index holds rows of " + std::to_string(ix->dim) + " columns, the model's " +
+                                          (level == SCANN_OUT_BF_PROPERTY ? "dense_out" : "global_dim") + " is " + std::to_string(d));
+  return SCANN_OK;
+}
+
+// n rows of `dim` floats, `pitch` bytes apart at src (host or device, `kind`), appended behind the index's rows; ids / atoms: host, n each.
+// Rows already stored stay where they are: a chunk that is full is never touched again, a new one comes from the handle's cache.
+int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch, hipMemcpyKind kind, int64_t n, const int64_t* ids,
+                const int32_t* atoms, hipStream_t s) {
+  if (n <= 0) return SCANN_OK;
+  if (ix->n + n > (int64_t)0x7fffffff) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_add: an index holds fewer than 2^31 rows");
+  int64_t done = 0;
+  while (done < n) {
+    const int64_t at = ix->n + done;
+    const size_t c = (size_t)(at / ix->chunk_rows);
+    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
+    if (c == ix->chunks.size()) {
+      char* p = nullptr;
+      HIPCHK(h, cached_malloc((void**)&p, ix->chunk_bytes()));
+      ix->chunks.push_back(p);
+      HIPCHK(h, hipMemsetAsync(p, 0, ix->chunk_bytes(), s));  // the padding columns are zero: fmaf(0, 0, acc) == acc
+    }
+    HIPCHK(h, hipMemcpy2DAsync(ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4, static_cast<const char*>(src) + (size_t)done * pitch,
+                               pitch, (size_t)ix->dim * 4, (size_t)m, kind, s));
+    HIPCHK(h, hipMemcpyAsync(ix->ids_of(c) + r0, ids + done, (size_t)m * 8, hipMemcpyHostToDevice, s));
+    done += m;
+  }
+  HIPCHK(h, hipStreamSynchronize(s));
+  ix->ids.insert(ix->ids.end(), ids, ids + n);
+  ix->atoms.insert(ix->atoms.end(), atoms, atoms + n);
+  ix->n += n;
+  return SCANN_OK;
+}
+
+// nq queries on the device ([nq][stride], padded like the rows; qid: device [nq] or null) against the whole index
+int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
+           int32_t* atoms, int32_t* pos) {
+  const int64_t N = ix->n;
+  const int rpr = (int)std::max<int64_t>(KNN_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + KNN_TR - 1) / KNN_TR * KNN_TR);
+  // one launch over all chunks: every chunk is cut into the same number of ranges (those behind the last row stay empty)
+  const int n_chunk = (int)((N + ix->chunk_rows - 1) / ix->chunk_rows);
+  const int64_t n_range = (int64_t)n_chunk * ((std::min<int64_t>(N, ix->chunk_rows) + rpr - 1) / rpr);
+  if (n_range > KNN_MAX_RANGES || n_chunk > 65535) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_query: the index has too many chunks");
+  const int64_t g = std::min<int64_t>(nq, KNN_QGROUP);
+  const size_t bP = align_up((size_t)std::max<int64_t>(g * n_range * k, 1) * 4), bO = align_up((size_t)g * k * 4),
+               bT = align_up((size_t)std::max(n_chunk, 1) * 8);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, 2 * bP + 2 * bO + 2 * bT));
+  float* part_d = reinterpret_cast<float*>(ws);
+  int32_t* part_p = reinterpret_cast<int32_t*>(ws + bP);
+  float* out_d = reinterpret_cast<float*>(ws + 2 * bP);
+  int32_t* out_p = reinterpret_cast<int32_t*>(ws + 2 * bP + bO);
+  std::vector<const void*> tab((size_t)2 * std::max(n_chunk, 1), nullptr);  // the chunks' rows, then their ids
+  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = ix->rows_of((size_t)c), tab[(size_t)n_chunk + c] = ix->ids_of((size_t)c);
+  std::vector<int32_t> pos_h((size_t)nq * k);
+  hipError_t e = hipSuccess;
+  if (n_chunk > 0) {
+    e = hipMemcpyAsync(ws + 2 * bP + 2 * bO, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ws + 2 * bP + 2 * bO + bT, tab.data() + n_chunk, (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
+  }
+  for (int64_t q0 = 0; q0 < nq && e == hipSuccess; q0 += g) {
+    const int m = (int)std::min<int64_t>(g, nq - q0);
+    KnnArgs a{};
+    a.rows = reinterpret_cast<const float* const*>(ws + 2 * bP + 2 * bO);
+    a.ids = reinterpret_cast<const int64_t* const*>(ws + 2 * bP + 2 * bO + bT);
+    a.n_total = (int32_t)N; a.chunk_rows = ix->chunk_rows; a.n_chunk = n_chunk;
+    a.stride = ix->stride; a.q = dq + (size_t)q0 * ix->stride; a.qid = dqid ? dqid + q0 : nullptr; a.nq = m; a.k = k; a.rows_per_range = rpr;
+    a.part_d = part_d; a.part_p = part_p; a.n_range = (int)n_range;
+    e = launch_knn_tile(a, s);
+    if (e == hipSuccess) e = launch_knn_merge(part_d, part_p, m, (int)n_range, k, out_d, out_p, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dist2 + (size_t)q0 * k, out_d, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(pos_h.data() + (size_t)q0 * k, out_p, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) (void)hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  for (size_t i = 0; i < pos_h.size(); ++i) {
+    const int32_t p = pos_h[i];
+    if (pos) pos[i] = p;
+    if (ids) ids[i] = p < 0 ? -1 : ix->ids[(size_t)p];
+    if (atoms) atoms[i] = p < 0 ? -1 : ix->atoms[(size_t)p];
+  }
+  return SCANN_OK;
+}
+
+// one inference forward of the batch with the level's output added to the handle's selection, downloaded as scann_batch_download does;
+// the handle's selection is put back whatever happens.  Afterwards db->out_bf / db->out_z hold the level's rows.
+int forward_level(scann_handle* h, scann_dbatch* db, int32_t level, std::vector<float>& y, std::vector<float>& ga) {
+  y.assign((size_t)std::max(db->n_struct, 1), 0.f);
+  ga.assign((size_t)std::max(db->n_atom, 1), 0.f);
+  const int32_t selected = h->out_flags;
+  h->out_flags |= level;
+  int r = scann_forward_resident(h, db, db->last_slot);
+  if (!r) r = scann_batch_download(h, db, y.data(), ga.data());
+  h->out_flags = selected;
+  return r;
+}
+
+int read_mol(scann_handle* h, scann_dbatch* db, std::vector<int32_t>& mol) {
+  mol.assign((size_t)db->n_struct + 1, 0);
+  if (db->n_struct > 0) HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
+  return SCANN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+float scann_knn_distsq(const float* q, const float* r, int64_t d) { return q && r && d > 0 ? dist2_chain(q, r, d) : 0.f; }
+
+void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out) {
+  if (!q || !rows || !out || nq <= 0 || n <= 0) return;
+  if (d < 0) d = 0;
+  if (__builtin_cpu_supports("fma")) dist2_matrix_fma(q, nq, rows, n, d, out);
+  else dist2_matrix_plain(q, nq, rows, n, d, out);
+}
+
+int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out) {
+  if (!h || !out) return fail(h, SCANN_ERR_INVALID, "scann_index_create: null argument");
+  if (dim < 1 || dim > 1024) return fail(h, SCANN_ERR_INVALID, "scann_index_create: dim " + std::to_string(dim) + " outside 1 .. 1024");
+  scann_index* ix = new scann_index();
+  ix->h = h;
+  ix->device = h->device;
+  ix->dim = dim;
+  ix->stride = (dim + 3) / 4 * 4;
+  ix->chunk_rows = (int32_t)std::max<size_t>(4096, ((size_t)64 << 20) / ((size_t)ix->stride * 4) / KNN_TR * KNN_TR);
+  *out = ix;
+  return SCANN_OK;
+}
+
+void scann_index_free(scann_handle_t* h, scann_index_t* ix) {
+  if (!ix) return;
+  (void)h;  // (the chunks go back to the device's block cache, which outlives the handle)
+  if (hipSetDevice(ix->device) == hipSuccess) (void)hipDeviceSynchronize();
+  for (char* p : ix->chunks) cached_free(p);
+  delete ix;
+}
+
+int64_t scann_index_size(const scann_index_t* ix) { return ix ? ix->n : SCANN_ERR_INVALID; }
+
+int scann_index_add(scann_handle_t* h, scann_index_t* ix, const float* rows, int64_t n, const int64_t* ids, const int32_t* atoms) {
+  if (const int r = check_index(h, ix, "scann_index_add")) return r;
+  if (n < 0 || (n > 0 && !rows)) return fail(h, SCANN_ERR_INVALID, "scann_index_add: n rows need a rows pointer and n >= 0");
+  if (n == 0) return SCANN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<int64_t> id_v((size_t)n);
+  std::vector<int32_t> at_v((size_t)n, -1);
+  for (int64_t i = 0; i < n; ++i) id_v[(size_t)i] = ids ? ids[i] : ix->n + i;  // ids NULL: the position
+  if (atoms) std::copy(atoms, atoms + n, at_v.begin());
+  return append_rows(h, ix, rows, (size_t)ix->dim * 4, hipMemcpyHostToDevice, n, id_v.data(), at_v.data(), h->streams[0]);
+}
+
+int scann_index_read(scann_handle_t* h, scann_index_t* ix, int64_t first, int64_t n, float* rows, int64_t* ids, int32_t* atoms) {
+  if (const int r = check_index(h, ix, "scann_index_read")) return r;
+  if (first < 0 || n < 0 || first + n > ix->n)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_read: rows " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " + std::to_string(ix->n));
+  HIPCHK(h, hipSetDevice(h->device));
+  for (int64_t done = 0; rows && done < n;) {
+    const int64_t at = first + done;
+    const size_t c = (size_t)(at / ix->chunk_rows);
+    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
+    HIPCHK(h, hipMemcpy2D(rows + (size_t)done * ix->dim, (size_t)ix->dim * 4, ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4,
+                          (size_t)ix->dim * 4, (size_t)m, hipMemcpyDeviceToHost));
+    done += m;
+  }
+  if (ids) std::copy(ix->ids.begin() + first, ix->ids.begin() + first + n, ids);
+  if (atoms) std::copy(ix->atoms.begin() + first, ix->atoms.begin() + first + n, atoms);
+  return SCANN_OK;
+}
+
+int scann_index_query(scann_handle_t* h, scann_index_t* ix, const float* q, int64_t nq, const int64_t* query_ids, int32_t k, float* dist2,
+                      int64_t* ids, int32_t* atoms, int32_t* pos) {
+  if (const int r = check_index(h, ix, "scann_index_query")) return r;
+  if (const int r = check_k(h, k, "scann_index_query")) return r;
+  if (nq <= 0 || !q) return fail(h, SCANN_ERR_INVALID, "scann_index_query: an empty query");
+  if (nq > (int64_t)0x7fffffff / SCANN_KNN_MAX_K) return fail(h, SCANN_ERR_INVALID, "scann_index_query: too many queries in one call");
+  if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query: dist2 is null");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  const size_t bQ = align_up((size_t)nq * ix->stride * 4), bI = align_up((size_t)nq * 8);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bQ + bI));
+  hipError_t e = ix->stride != ix->dim ? hipMemsetAsync(ws, 0, bQ, s) : hipSuccess;
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)ix->stride * 4, q, (size_t)ix->dim * 4, (size_t)ix->dim * 4, (size_t)nq, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && query_ids) e = hipMemcpyAsync(ws + bQ, query_ids, (size_t)nq * 8, hipMemcpyHostToDevice, s);
+  int r = SCANN_OK;
+  if (e == hipSuccess)
+    r = search(h, ix, reinterpret_cast<const float*>(ws), query_ids ? reinterpret_cast<const int64_t*>(ws + bQ) : nullptr, nq, k, s, dist2, ids, atoms, pos);
+  else
+    (void)hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  return r;
+}
+
+int scann_index_add_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* db, int32_t level, const int64_t* ids) {
+  if (const int r = check_index(h, ix, "scann_index_add_batch")) return r;
+  if (!db) return fail(h, SCANN_ERR_INVALID, "scann_index_add_batch: null argument");
+  if (const int r = check_level(h, ix, level, "scann_index_add_batch")) return r;
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_add_batch: weights not loaded");
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<float> y, ga;
+  if (const int r = forward_level(h, db, level, y, ga)) return r;
+  const int B = db->n_struct, A = db->n_atom;
+  const bool atom = level == SCANN_OUT_AFTER_LC;
+  const int64_t n = atom ? A : B;
+  std::vector<int64_t> id_v((size_t)n);
+  std::vector<int32_t> at_v((size_t)n, -1);
+  if (atom) {
+    std::vector<int32_t> mol;
+    if (const int r = read_mol(h, db, mol)) return r;
+    for (int b = 0; b < B; ++b)
+      for (int i = mol[b]; i < mol[b + 1]; ++i) {
+        id_v[(size_t)i] = ids ? ids[b] : b;
+        at_v[(size_t)i] = i - mol[b];
+      }
+  } else {
+    for (int b = 0; b < B; ++b) id_v[(size_t)b] = ids ? ids[b] : ix->n + b;
+  }
+  return append_rows(h, ix, atom ? db->out_z : db->out_bf, (size_t)ix->dim * 4, hipMemcpyDeviceToDevice, n, id_v.data(), at_v.data(),
+                     h->streams[db->last_slot]);
+}
+
+int scann_index_query_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, int32_t k, float* y,
+                            float* ga, float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos) {
+  if (const int r = check_index(h, ix, "scann_index_query_batch")) return r;
+  if (!db) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: null argument");
+  if (const int r = check_k(h, k, "scann_index_query_batch")) return r;
+  if (const int r = check_level(h, ix, level, "scann_index_query_batch")) return r;
+  const bool atom = level == SCANN_OUT_AFTER_LC;
+  const int B = db->n_struct, A = db->n_atom;
+  const int64_t nq = atom ? A : B;
+  if (nq <= 0) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: an empty query");
+  if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: dist2 is null");
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_query_batch: weights not loaded");
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<float> y_h, ga_h;
+  if (const int r = forward_level(h, db, level, y_h, ga_h)) return r;
+  hipStream_t s = h->streams[db->last_slot];
+  std::vector<int64_t> qid;
+  if (query_ids) {
+    qid.assign(query_ids, query_ids + B);
+    if (atom) {
+      std::vector<int32_t> mol;
+      if (const int r = read_mol(h, db, mol)) return r;
+      qid.assign((size_t)A, 0);
+      for (int b = 0; b < B; ++b)
+        for (int i = mol[b]; i < mol[b + 1]; ++i) qid[(size_t)i] = query_ids[b];
+    }
+  }
+  // the level's rows are the queries where the forward left them; a width that is no multiple of 4 is copied to the padded stride first
+  const float* src = atom ? db->out_z : db->out_bf;
+  const bool pad = ix->stride != ix->dim;
+  const size_t bQ = pad ? align_up((size_t)nq * ix->stride * 4) : 0, bI = align_up((size_t)nq * 8);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bQ + bI));
+  hipError_t e = hipSuccess;
+  if (pad) {
+    e = hipMemsetAsync(ws, 0, bQ, s);
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(ws, (size_t)ix->stride * 4, src, (size_t)ix->dim * 4, (size_t)ix->dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
+  }
+  if (e == hipSuccess && query_ids) e = hipMemcpyAsync(ws + bQ, qid.data(), (size_t)nq * 8, hipMemcpyHostToDevice, s);
+  int r = SCANN_OK;
+  if (e == hipSuccess)
+    r = search(h, ix, pad ? reinterpret_cast<const float*>(ws) : src, query_ids ? reinterpret_cast<const int64_t*>(ws + bQ) : nullptr, nq, k, s, dist2, ids,
+               atoms, pos);
+  else
+    (void)hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  if (r) return r;
+  if (y && B > 0) memcpy(y, y_h.data(), (size_t)B * 4);
+  if (ga && A > 0) memcpy(ga, ga_h.data(), (size_t)A * 4);
+  return SCANN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,35 @@
+// Internal declarations of the latent-space nearest-neighbour search (scann_knn.hip, scann_knn.cpp); the C ABI is include/scann_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace scann {
+
+constexpr int KNN_TQ = 128;     // queries per workgroup
+constexpr int KNN_TR = 64;      // index rows per tile
+constexpr int KNN_SLAB = 32;    // columns per LDS slab
+constexpr int KNN_QS = KNN_TQ, KNN_RS = KNN_TR;  // floats per staged column of the query / row slab; column c lies (c / 4) * 4 floats further
+                                                 // (scann_knn.hip), so a slab takes 32 * stride + 32 floats
+constexpr int KNN_UNION = KNN_TR * KNN_TQ;               // floats the slabs and the distance tile share: max(32 * (128 + 64) + 64, 64 * 128)
+
+// One launch of knn_tile_kernel: `nq` queries against all `n_total` rows of an index, stored in chunks of `chunk_rows` rows.  Workgroup
+// (x, y, z) takes queries [128 y, 128 y + 128) and rows [x * rows_per_range, (x + 1) * rows_per_range) of chunk z and leaves the range's
+// k best under the order (dist2, position) in part_d / part_p [query][n_range][k], range = z * gridDim.x + x; unused places (and the
+// ranges behind the last row) hold (+inf, -1).
+struct KnnArgs {
+  const float* const* rows;    // [n_chunk] -> [chunk_rows][stride], columns dim .. stride-1 zero
+  const int64_t* const* ids;   // [n_chunk] -> [chunk_rows] (read with qid only)
+  int32_t n_total, chunk_rows, n_chunk, stride;
+  const float* q;       // [nq][stride], padded like the rows
+  const int64_t* qid;   // [nq] or null: rows with ids[r] == qid[query] are skipped
+  int32_t nq, k, rows_per_range;
+  float* part_d;
+  int32_t* part_p;
+  int32_t n_range;      // n_chunk * ranges per chunk
+};
+size_t knn_lds_bytes(int k);
+hipError_t launch_knn_tile(const KnnArgs& a, hipStream_t s);
+// per query: the k first of its n_range partial lists under (dist2, position) -> out_d / out_p [nq][k]; the tail is (+inf, -1)
+hipError_t launch_knn_merge(const float* part_d, const int32_t* part_p, int nq, int n_range, int k, float* out_d, int32_t* out_p, hipStream_t s);
+
+}  // namespace scann

@@ -117,6 +117,16 @@ SYMBOLS = [
     ("scann_ablate_pooling", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("scann_rollout_floats", C.c_int64, [_P, _P]),
     ("scann_attention_rollout", C.c_int, [_P, _P, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("scann_index_create", C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
+    ("scann_index_free", None, [_P, _P]),
+    ("scann_index_size", C.c_int64, [_P]),
+    ("scann_index_add", C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    ("scann_index_read", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("scann_index_query", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),
+    ("scann_index_add_batch", C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    ("scann_index_query_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("scann_knn_distsq", C.c_float, [_P, _P, C.c_int64]),
+    ("scann_knn_distsq_matrix", None, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -131,6 +141,37 @@ ROLLOUT_MAX_ATOMS = 960
 
 # scann_output_read selectors / scann_set_outputs flags (include/scann_hip.h)
 OUT_LOCAL_ATTENTION, OUT_AFTER_LC, OUT_BF_PROPERTY = 0, 1, 2
+# the latent-space index (scann_index_*): the largest k (SCANN_KNN_MAX_K), the widest row, the two levels by name
+KNN_MAX_K = 32
+KNN_MAX_DIM = 1024
+KNN_LEVELS = {"structure": OUT_BF_PROPERTY, "atom": OUT_AFTER_LC}
+
+
+def check_knn_k(k):
+    """k of a nearest-neighbour query as the C calls take it; ValueError outside 1 .. KNN_MAX_K."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError("k must be an integer in 1 .. %d, got %r" % (KNN_MAX_K, k))
+    return int(k)
+
+
+def knn_dist2(q, r):
+    """dist2 of one pair as the search kernel forms it (scann_knn_distsq): the fp32 chain acc = fmaf(q[j] - r[j], q[j] - r[j], acc)."""
+    q = np.ascontiguousarray(q, dtype=np.float32).ravel()
+    r = np.ascontiguousarray(r, dtype=np.float32).ravel()
+    if q.shape != r.shape:
+        raise ValueError("knn_dist2: %d and %d columns" % (q.size, r.size))
+    return np.float32(load_library().scann_knn_distsq(_ptr(q), _ptr(r), q.size))
+
+
+def knn_dist2_matrix(q, rows):
+    """[nq, n] fp32: knn_dist2 of every (query, row) pair (scann_knn_distsq_matrix)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if q.ndim != 2 or rows.ndim != 2 or q.shape[1] != rows.shape[1]:
+        raise ValueError("knn_dist2_matrix: shapes %s and %s" % (q.shape, rows.shape))
+    out = np.zeros((q.shape[0], rows.shape[0]), dtype=np.float32)
+    load_library().scann_knn_distsq_matrix(_ptr(q), q.shape[0], _ptr(rows), rows.shape[0], q.shape[1], _ptr(out))
+    return out
 
 
 
@@ -520,6 +561,27 @@ class ResidentBatch:
             pass
 
 
+class DeviceIndex:
+    """A latent-space index on the device (scann_index_t) of one Engine."""
+
+    def __init__(self, engine, dim, handle):
+        self.engine, self.dim, self._h = engine, int(dim), handle
+
+    def __len__(self):
+        return int(self.engine.lib.scann_index_size(self._h)) if self._h is not None else 0
+
+    def free(self):
+        if self._h is not None:
+            self.engine.lib.scann_index_free(self.engine._h, self._h)  # (the handle may be gone already: the call does not need it)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     """One scann_handle_t: the forward graph of create_model on one GPU."""
 
@@ -783,6 +845,71 @@ class Engine:
             out["rollout"] = np.empty(int(out["rollout_offset"][-1]), np.float32)
         self._check(self.lib.scann_attention_rollout(self._h, rb._h, residual, head, depth, _ptr(out["y"]), _ptr(out["ga"]),
                                                      _ptr(out["attribution"]), _ptr(out.get("rollout"))))
+        return out
+
+    # -- latent-space index (scann_index_*) --
+    def index_create(self, dim):
+        ix = _P()
+        self._check(self.lib.scann_index_create(self._h, int(dim), C.byref(ix)))
+        return DeviceIndex(self, dim, ix)
+
+    def index_add(self, ix, rows, ids=None, atoms=None):
+        """Append host rows [n, dim] (ids int64 [n], None: the positions; atoms int32 [n], None: -1)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != ix.dim:
+            raise ValueError("index_add: rows of shape %s for an index of %d columns" % (rows.shape, ix.dim))
+        n = rows.shape[0]
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        atoms = None if atoms is None else np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+        if (ids is not None and ids.shape[0] != n) or (atoms is not None and atoms.shape[0] != n):
+            raise ValueError("index_add: %d rows need %d ids / atoms" % (n, n))
+        self._check(self.lib.scann_index_add(self._h, ix._h, _ptr(rows), n, _ptr(ids), _ptr(atoms)))
+
+    def index_read(self, ix, first=0, n=None):
+        """(rows [n, dim], ids [n], atoms [n]) of positions first .. first + n - 1 (scann_index_read)."""
+        n = len(ix) - int(first) if n is None else int(n)
+        rows, ids, atoms = np.empty((max(n, 0), ix.dim), np.float32), np.empty(max(n, 0), np.int64), np.empty(max(n, 0), np.int32)
+        self._check(self.lib.scann_index_read(self._h, ix._h, int(first), n, _ptr(rows), _ptr(ids), _ptr(atoms)))
+        return rows, ids, atoms
+
+    @staticmethod
+    def _knn_out(nq, k):
+        return {"dist2": np.empty((nq, k), np.float32), "id": np.empty((nq, k), np.int64), "atom": np.empty((nq, k), np.int32),
+                "position": np.empty((nq, k), np.int32)}
+
+    def index_query(self, ix, q, k, query_ids=None):
+        """The k nearest rows of every host query vector (scann_index_query): {"dist2", "id", "atom", "position"} [nq, k]."""
+        k = check_knn_k(k)
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise ValueError("index_query: queries of shape %s for an index of %d columns" % (q.shape, ix.dim))
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != q.shape[0]:
+            raise ValueError("index_query: %d queries need %d query ids" % (q.shape[0], q.shape[0]))
+        out = self._knn_out(q.shape[0], k)
+        self._check(self.lib.scann_index_query(self._h, ix._h, _ptr(q), q.shape[0], _ptr(qid), k, _ptr(out["dist2"]), _ptr(out["id"]),
+                                               _ptr(out["atom"]), _ptr(out["position"])))
+        return out
+
+    def index_add_batch(self, ix, rb, level, ids=None):
+        """One forward of a resident batch; its ``level`` rows (OUT_BF_PROPERTY / OUT_AFTER_LC) are appended device to device."""
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids is not None and ids.shape[0] != rb.packed.n_struct:
+            raise ValueError("index_add_batch: %d structures need %d ids" % (rb.packed.n_struct, rb.packed.n_struct))
+        self._check(self.lib.scann_index_add_batch(self._h, ix._h, rb._h, int(level), _ptr(ids)))
+
+    def index_query_batch(self, ix, rb, level, k, query_ids=None):
+        """One forward of a resident batch and the k nearest rows of each of its ``level`` rows (scann_index_query_batch; raw y):
+        {"y" [n_struct], "ga" [n_atom], "dist2", "id", "atom", "position" [n_struct or n_atom, k]}."""
+        k = check_knn_k(k)
+        p = rb.packed
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != p.n_struct:
+            raise ValueError("index_query_batch: %d structures need %d query ids" % (p.n_struct, p.n_struct))
+        out = self._knn_out(p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct, k)
+        out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
+        self._check(self.lib.scann_index_query_batch(self._h, ix._h, rb._h, int(level), _ptr(qid), k, _ptr(out["y"]), _ptr(out["ga"]),
+                                                     _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["position"])))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

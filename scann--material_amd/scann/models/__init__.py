@@ -1,4 +1,5 @@
+from .latent_index import LatentIndex
 from .model_set import Ensemble, ModelSet
 from .scann_model import SCANN, HipModel, create_model, create_model_pretrained, load_model, normalize_config
 
-__all__ = ["SCANN", "HipModel", "create_model", "create_model_pretrained", "load_model", "normalize_config", "ModelSet", "Ensemble"]
+__all__ = ["SCANN", "HipModel", "create_model", "create_model_pretrained", "load_model", "normalize_config", "ModelSet", "Ensemble", "LatentIndex"]

@@ -1,0 +1,131 @@
+"""Latent-space index: the learned representations of a set of structures kept on the GPU, searched for the nearest ones of a query.
+
+The mean Euclidean distance of a structure's last hidden representation (``bf_property``) to its k nearest training structures is an
+uncertainty / applicability-domain measure that needs one forward and no retraining (Janet, Duan, Yang, Nandy, Kulik, Chem. Sci. 2019);
+at the atom level (``after_Lc``) the neighbours say which local structures of the training set an atom's environment resembles.  The rows
+stay on the device (scann_index_*, include/scann_hip.h); the search is exact, in the difference form, under the total order (distance,
+then position), so a query's answer depends on the query and the index contents only."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from .. import _hip
+
+LEVELS = ("structure", "atom")
+
+
+def level_dim(config, level):
+    """Width of the rows of ``level`` in a model configuration: dense_out (structure, ``bf_property``) or global_dim (atom, ``after_Lc``);
+    ValueError for another level."""
+    if level not in LEVELS:
+        raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+    return int(config["model"]["dense_out" if level == "structure" else "global_dim"])
+
+
+def batch_jobs(model, data, bs):
+    """(upload, n_struct) per chunk of ``data``: a padded dict or a ``PackedBatch`` cut ``bs`` structures at a time, or a dataset -- any
+    sequence of ``(PackedBatch | padded dict, target)`` -- batch by batch."""
+    eng = model.engine
+    if isinstance(data, _hip.PackedBatch):
+        B = data.n_struct
+        for i in range(0, B, bs):
+            yield functools.partial(eng.upload, _hip.slice_packed(data, i, min(i + bs, B))), min(i + bs, B) - i
+    elif isinstance(data, dict):
+        B = int(np.shape(data["neighbors"])[0])
+        sliced = {k: np.asarray(v) for k, v in data.items() if k in model.input_names}
+        for i in range(0, B, bs):
+            yield functools.partial(model._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), min(i + bs, B) - i
+    else:
+        for i in range(len(data)):
+            item, _ = data[i]
+            if isinstance(item, _hip.PackedBatch):
+                yield functools.partial(eng.upload, item), item.n_struct
+            else:
+                yield functools.partial(model._upload_padded, item), int(np.shape(item["neighbors"])[0])
+
+
+def count_structures(data):
+    if isinstance(data, _hip.PackedBatch):
+        return data.n_struct
+    if isinstance(data, dict):
+        return int(np.shape(data["neighbors"])[0])
+    n = 0
+    for i in range(len(data)):
+        item, _ = data[i]
+        n += item.n_struct if isinstance(item, _hip.PackedBatch) else int(np.shape(item["neighbors"])[0])
+    return n
+
+
+class LatentIndex:
+    """Rows of one level of one model on its GPU.  ``level``: "structure" (one ``bf_property`` row per structure) or "atom" (one
+    ``after_Lc`` row per real atom).  Every row carries the id of its structure and, at atom level, the atom's index within it."""
+
+    def __init__(self, model, level="structure"):
+        self.dim = level_dim(model.config, level)
+        self.level = level
+        self.model = model
+        self._ix = model.engine.index_create(self.dim)
+        self._n_struct = 0  # structures given so far: where the default ids of the next add start
+
+    def __len__(self):
+        return len(self._ix)
+
+    def add(self, data, ids=None, batch_size=None):
+        """Append the rows of ``data`` -- a padded dict, a ``PackedBatch`` or a dataset as ``predict_dataset`` takes it -- computed by one
+        forward per batch and copied device to device.  ``ids``: one per structure (default: continuing from the structures the index
+        was given so far, i.e. 0 .. n-1 for a fresh one).  Returns self."""
+        bs = int(self.model.config["hyper"]["batch_size"] if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        n = count_structures(data)
+        if ids is None:
+            ids = np.arange(n, dtype=np.int64) + self._n_struct
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.shape[0] != n:
+            raise ValueError("%d structures need %d ids, got %d" % (n, n, ids.shape[0]))
+        eng, lvl = self.model.engine, _hip.KNN_LEVELS[self.level]
+        state = {"at": 0}
+
+        def finish(rb, cnt):
+            eng.index_add_batch(self._ix, rb, lvl, ids[state["at"]:state["at"] + cnt])
+            state["at"] += cnt
+
+        # (scann_index_add_batch runs its own forward and is synchronous: the pipeline still uploads batch k + 1 before batch k is computed)
+        self.model._pipeline(batch_jobs(self.model, data, bs), finish, launch=lambda rb, slot: None)
+        self._n_struct += n
+        return self
+
+    def add_rows(self, rows, ids=None, atoms=None):
+        """Append host rows [n, dim] with their ids (default: their positions) and atoms (default: -1)."""
+        self.model.engine.index_add(self._ix, rows, ids, atoms)
+        return self
+
+    def rows(self):
+        """(rows [n, dim] fp32, ids [n] int64, atoms [n] int32) copied back from the device, in insertion order."""
+        return self.model.engine.index_read(self._ix)
+
+    def save(self, path):
+        """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``)."""
+        rows, ids, atoms = self.rows()
+        with open(path, "wb") as f:
+            np.savez(f, rows=rows, ids=ids, atoms=atoms, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved index uploaded to ``model``'s GPU; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            rows, ids, atoms = z["rows"], z["ids"], z["atoms"]
+        if level_dim(model.config, level) != dim or rows.ndim != 2 or rows.shape[1] != dim:
+            raise ValueError("%s: a %s-level index of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level)))
+        ix = cls(model, level)
+        if len(rows):
+            ix.add_rows(rows, ids, atoms)
+        ix._n_struct = int(ids.max()) + 1 if len(ids) else 0  # default ids of later adds do not collide
+        return ix
+
+    def free(self):
+        self._ix.free()

@@ -338,6 +338,73 @@ class HipModel:
             out["rollout"] = R
         return out
 
+    def build_index(self, data, level="structure", ids=None, batch_size=None):
+        """A ``LatentIndex`` of ``data`` on this model's GPU: one ``bf_property`` row per structure (``level`` "structure") or one
+        ``after_Lc`` row per real atom ("atom"), computed batch by batch and kept on the device.  ``data``: a padded dict, a
+        ``PackedBatch`` or a dataset as ``predict_dataset`` takes it; ``ids``: one per structure (default 0 .. n-1 in input order).  A bad
+        level or batch_size raises ValueError before anything is uploaded."""
+        from .latent_index import LatentIndex, level_dim
+
+        level_dim(self.config, level)
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        return LatentIndex(self, level).add(data, ids=ids, batch_size=batch_size)
+
+    def nearest(self, inputs, index, k=5, exclude_ids=None, batch_size=None):
+        """The ``k`` nearest rows of a ``LatentIndex`` for every structure (or, for an atom-level index, every atom) of ``inputs``, by
+        Euclidean distance between the learned representations, searched on the GPU right behind the forward.  Rows are ranked by
+        (distance, position in the index): the result depends on the query and the index only.  ``exclude_ids`` [B]: rows whose id
+        equals the structure's are skipped (leave-one-out).  A padded dict gives {"predict_property": [B, 1], "distance": [B, k] fp32,
+        "neighbor_id": [B, k] int64, "latent_distance": [B, 1]} -- the mean of the k distances, ``inf`` if fewer than k rows qualify
+        (those places: distance inf, id -1) -- and at atom level [B, M, k] / [B, M, 1] arrays plus "neighbor_atom" [B, M, k], with
+        0 / -1 at padded atoms; a ``PackedBatch`` gives packed [n_atom, k] arrays.  Raw y.  ``batch_size`` structures at a time (default:
+        hyper.batch_size).  A k outside 1 .. 32, an index of another model or width, or a bad batch_size raise ValueError before anything
+        is uploaded."""
+        from .latent_index import LatentIndex, batch_jobs, level_dim
+
+        k = _hip.check_knn_k(k)
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        if index.model is not self or level_dim(self.config, index.level) != index.dim:
+            raise ValueError("the index was built for another model: it lives on that model's GPU handle (%s level, %d columns)" % (
+                index.level, index.dim))
+        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        is_packed = isinstance(inputs, _hip.PackedBatch)
+        B = inputs.n_struct if is_packed else int(np.shape(inputs["neighbors"])[0])
+        qid = None
+        if exclude_ids is not None:
+            qid = np.ascontiguousarray(exclude_ids, dtype=np.int64).reshape(-1)
+            if qid.shape[0] != B:
+                raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
+        parts, state = [], {"at": 0}
+
+        def finish(rb, cnt):
+            parts.append(eng.index_query_batch(index._ix, rb, lvl, k, None if qid is None else qid[state["at"]:state["at"] + cnt]))
+            state["at"] += cnt
+
+        self._pipeline(batch_jobs(self, inputs, bs), finish, launch=lambda rb, slot: None)
+        empty = {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
+                 "atom": np.zeros((0, k), np.int32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        dist = np.sqrt(cat["dist2"])  # correctly rounded on the host: no device square root enters the definition
+        mean = np.zeros(dist.shape[0], dtype=np.float32)
+        for j in range(k):  # fp32, places in order
+            mean = mean + dist[:, j]
+        mean = (mean / np.float32(k)).astype(np.float32)[:, None]
+        out = {"predict_property": cat["y"].reshape(-1, 1), "distance": dist, "neighbor_id": cat["id"], "latent_distance": mean}
+        if atom:
+            out["neighbor_atom"] = cat["atom"]
+            if not is_packed:
+                amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
+                for n, fill in (("distance", 0), ("latent_distance", 0), ("neighbor_id", -1), ("neighbor_atom", -1)):
+                    full = np.full(amask.shape + out[n].shape[1:], fill, dtype=out[n].dtype)
+                    full[amask] = out[n]
+                    out[n] = full
+        return out
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -847,6 +914,17 @@ class SCANN:
         """HipModel.attention_rollout with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
         scores, the attribution and the rollout are unitless shares and stay as they are."""
         out = self.model.attention_rollout(ip, residual=residual, head=head, depth=depth, matrix=matrix, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
+
+    def build_index(self, data, level="structure", ids=None, batch_size=None):
+        """HipModel.build_index: a ``LatentIndex`` of ``data`` on the model's GPU."""
+        return self.model.build_index(data, level=level, ids=ids, batch_size=batch_size)
+
+    def nearest(self, ip, index, k=5, exclude_ids=None, batch_size=None):
+        """HipModel.nearest with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
+        live in latent space and stay as they are."""
+        out = self.model.nearest(ip, index, k=k, exclude_ids=exclude_ids, batch_size=batch_size)
         out["predict_property"] = out["predict_property"] * self.std + self.mean
         return out
 

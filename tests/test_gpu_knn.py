@@ -1,0 +1,607 @@
+"""GPU tests of the latent-space index (scann_index_* through Engine.index_*, LatentIndex, HipModel.build_index / nearest).
+
+1. Kernel, exact: dist2 of every returned pair is bitwise the host twin's chain (scann_knn_distsq), and the returned (position, id, atom)
+   lists equal the total-order selection (dist2 ascending, position ascending; tests/knn_ref.py) over the host twin's N distances -- no
+   tolerance, the order is total.  Planted: exact duplicates, the query itself, near-duplicates among far rows, k > N, every row excluded.
+2. Invariance, bitwise: batch size and position of a query, one add or many, add_batch from batches of 8 or of 64.
+3. End to end: the index holds what predict(outputs=...) returns; nearest == scann_index_query on those rows; y and the scores are the
+   plain forward's; self-distance 0 at rank 0; against the fp64 oracle's representations under the rule of tests/test_gpu_outputs.py.
+4. State: weights, selected outputs, training state untouched; generic widths, SCANN_GENERIC=1, SCANN_EXACT=1, a training handle; errors.
+5. The CLI."""
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":  # the child process of the environment-switch tests
+    for p in (os.path.join(ROOT, "scann--material_amd"), os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__file__))):
+        sys.path.insert(0, p)
+
+import knn_ref  # noqa: E402
+import scann_oracle as so  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def padded(kind, n, seed, cfg):
+    inputs, _ = so.pad_batch(*so.synth_dataset(n, seed, kind=kind), g_update=cfg["model"]["g_update"])
+    return {k: np.array(v) for k, v in inputs.items()}
+
+
+def setup(kind="qm9", n=24, seed=0, infer=True, **over):
+    """as tests/test_gpu_rollout.py::setup builds its model and batch"""
+    from scann.models.scann_model import HipModel
+
+    cfg = so.default_config(kind)
+    cfg["model"].update(over)
+    w = so.init_weights(cfg, 1234, perturb=True)
+    return cfg, w, padded(kind, n, seed, cfg), HipModel(cfg, w, device=0, infer=infer)
+
+
+@pytest.fixture(scope="module")
+def engine(hip_lib):
+    cfg, w, inputs, model = setup(n=4)
+    yield model.engine
+    model.engine.close()
+
+
+def amask_of(inputs):
+    return np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+
+
+def check_exact(eng, ix, rows, ids, atoms, q, k, label, query_ids=None):
+    """the GPU's answer against the host twin's distances and the total-order selection: everything equal, bit for bit"""
+    from scann import _hip
+
+    got = eng.index_query(ix, q, k, query_ids=query_ids)
+    d = _hip.knn_dist2_matrix(q, rows) if len(rows) else np.zeros((len(q), 0), np.float32)
+    od, op, oi, oa = knn_ref.select(d, k, ids=ids, atoms=atoms, query_ids=query_ids)
+    n_bad = int((got["position"] != op).sum())
+    print("%s: N %d, dim %d, Q %d, k %d: %d of %d places differ from the total-order selection" % (
+        label, len(rows), q.shape[1], len(q), k, n_bad, op.size))
+    assert np.array_equal(got["position"], op), label
+    assert np.array_equal(_bits(got["dist2"]), _bits(od)), label
+    assert np.array_equal(got["id"], oi) and np.array_equal(got["atom"], oa), label
+    return got
+
+
+# N, dim, k, Q: a covering subset of N in {1, 31, 32, 33, 1,000, 20,000} x dim in {128, 64, 130} x k in {1, 5, 32} x Q in {1, 7, 128, 300},
+# the largest N = 20,000 with Q = 128, Q = 300 at N <= 1,000; and one index of 1,024 columns that spans two storage chunks
+EXACT_CASES = [(1, 128, 1, 1), (1, 64, 5, 7), (31, 128, 5, 7), (31, 64, 32, 1), (32, 64, 32, 7), (32, 130, 1, 128), (33, 130, 5, 128),
+               (33, 128, 32, 300), (1000, 128, 5, 300), (1000, 64, 32, 128), (1000, 130, 1, 300), (1000, 130, 32, 7), (20000, 128, 5, 128),
+               (20000, 64, 1, 7), (20000, 130, 32, 1), (17000, 1024, 5, 7)]
+
+
+@pytest.mark.parametrize("N,dim,k,Q", EXACT_CASES, ids=["N%d_d%d_k%d_Q%d" % c for c in EXACT_CASES])
+def test_kernel_exact_on_random_indices(engine, N, dim, k, Q):
+    rng = np.random.default_rng(N * 7 + dim * 3 + k + Q)
+    rows = rng.standard_normal((N, dim)).astype(np.float32)
+    ids = rng.integers(0, 1 << 40, N).astype(np.int64)
+    atoms = rng.integers(-1, 30, N).astype(np.int32)
+    q = rng.standard_normal((Q, dim)).astype(np.float32)
+    ix = engine.index_create(dim)
+    try:
+        engine.index_add(ix, rows, ids, atoms)
+        assert len(ix) == N
+        check_exact(engine, ix, rows, ids, atoms, q, k, "random")
+        if N >= 32 and Q >= 7:  # leave-one-out against ids that occur in the index
+            check_exact(engine, ix, rows, ids, atoms, q, k, "random, exclude", query_ids=ids[rng.integers(0, N, Q)])
+    finally:
+        ix.free()
+
+
+def test_kernel_exact_on_planted_cases(engine):
+    rng = np.random.default_rng(5)
+    dim, N = 128, 1000
+    rows = (rng.standard_normal((N, dim)) * 3).astype(np.float32)
+    q = (rng.standard_normal((16, dim)) * 3).astype(np.float32)
+    # exact duplicates of one row near query 0 (ties resolved by position), out of position order in distance
+    rows[700] = q[0] + np.float32(0.25)
+    rows[[20, 350, 999]] = rows[700]
+    # query 1 itself, twice
+    rows[[640, 64]] = q[1]
+    # near-duplicates of queries 2 .. 9 among the far rows: the case the product form fails
+    near = 100 + 63 * np.arange(8)
+    rows[near] = q[2:10] + np.float32(1e-3) * rng.standard_normal((8, dim)).astype(np.float32)
+    ids = np.arange(N, dtype=np.int64) + 5000
+    atoms = (np.arange(N) % 17).astype(np.int32)
+    ix = engine.index_create(dim)
+    try:
+        engine.index_add(ix, rows, ids, atoms)
+        got = check_exact(engine, ix, rows, ids, atoms, q, 5, "planted")
+        assert np.array_equal(got["position"][0, :4], [20, 350, 700, 999]) and len(set(got["dist2"][0, :4])) == 1
+        assert np.array_equal(got["position"][1, :2], [64, 640]) and not got["dist2"][1, :2].any() and got["dist2"][1, 2] > 0
+        assert np.array_equal(got["position"][2:10, 0], near)
+        assert np.all(got["dist2"][2:10, 0] < 1e-3) and np.all(got["dist2"][2:10, 1] > 100)
+        # excluding the duplicates' ids one by one moves the others up
+        check_exact(engine, ix, rows, ids, atoms, q, 5, "planted, exclude", query_ids=np.array([5020, 5064] + [0] * 14, dtype=np.int64))
+    finally:
+        ix.free()
+    # k > N, and exclude_id removing every row: the +inf tail
+    ix = engine.index_create(dim)
+    try:
+        engine.index_add(ix, rows[:7], np.full(7, 3, np.int64), atoms[:7])
+        got = check_exact(engine, ix, rows[:7], np.full(7, 3, np.int64), atoms[:7], q, 32, "k > N")
+        assert np.all(got["position"][:, 7:] == -1) and np.all(np.isinf(got["dist2"][:, 7:])) and np.all(got["position"][:, :7] >= 0)
+        got = check_exact(engine, ix, rows[:7], np.full(7, 3, np.int64), atoms[:7], q, 5, "all excluded", query_ids=np.full(16, 3, np.int64))
+        assert np.all(got["position"] == -1) and np.all(got["id"] == -1) and np.all(got["atom"] == -1) and np.all(np.isinf(got["dist2"]))
+    finally:
+        ix.free()
+    # an empty index answers with the tail
+    ix = engine.index_create(dim)
+    try:
+        got = check_exact(engine, ix, rows[:0], ids[:0], atoms[:0], q, 3, "empty index")
+        assert np.all(got["position"] == -1) and np.all(np.isinf(got["dist2"]))
+    finally:
+        ix.free()
+
+
+def test_invariance_of_a_query_and_of_how_the_index_was_built(engine):
+    rng = np.random.default_rng(9)
+    dim, N = 130, 3000
+    rows = rng.standard_normal((N, dim)).astype(np.float32)
+    rows[1500:1510] = rows[3]  # ties
+    q = rng.standard_normal((128, dim)).astype(np.float32)
+    one, many = engine.index_create(dim), engine.index_create(dim)
+    try:
+        engine.index_add(one, rows)
+        at = 0
+        for step in [1, 63, 64, 65, 7, 1000, 3, 500]:
+            engine.index_add(many, rows[at:at + step])
+            at += step
+        while at < N:
+            engine.index_add(many, rows[at:at + 311])
+            at += 311
+        assert len(one) == len(many) == N
+        a, b = engine.index_read(one), engine.index_read(many)
+        assert np.array_equal(_bits(a[0]), _bits(rows)) and np.array_equal(_bits(b[0]), _bits(rows))
+        assert np.array_equal(a[1], np.arange(N)) and np.array_equal(b[1], np.arange(N)) and np.all(a[2] == -1) and np.all(b[2] == -1)
+        part = engine.index_read(many, 60, 10)
+        assert np.array_equal(_bits(part[0]), _bits(rows[60:70])) and np.array_equal(part[1], np.arange(60, 70))
+        full = engine.index_query(one, q, 7)
+        full2 = engine.index_query(many, q, 7)
+        for key in full:
+            assert np.array_equal(full[key], full2[key]) and np.array_equal(_bits(full["dist2"]), _bits(full2["dist2"])), key
+        alone = engine.index_query(one, q[17:18], 7)
+        moved = engine.index_query(one, np.concatenate([q[40:45], q[17:18], q[:3]]), 7)
+        for key in full:
+            assert np.array_equal(alone[key][0], full[key][17]) and np.array_equal(moved[key][5], full[key][17]), key
+        assert np.array_equal(_bits(alone["dist2"][0]), _bits(full["dist2"][17]))
+    finally:
+        one.free()
+        many.free()
+
+
+# ---- end to end ----
+
+E2E = {"qm9": (64, 24), "mp2018": (24, 8)}
+
+
+def reps_of(model, inputs, level):
+    """the level's rows as predict(outputs=...) returns them, packed: [n_struct, dense_out] or [n_atom, global_dim]"""
+    out = model.predict(inputs, outputs=["bf_property" if level == "structure" else "after_Lc"])[0]
+    return out if level == "structure" else out[amask_of(inputs)]
+
+
+@pytest.mark.parametrize("level", ["structure", "atom"])
+@pytest.mark.parametrize("kind", ["qm9", "mp2018"])
+def test_index_holds_the_models_rows_and_nearest_is_the_query_on_them(hip_lib, kind, level):
+    n_i, n_q = E2E[kind]
+    cfg, w, data, model = setup(kind=kind, n=n_i, seed=0)
+    queries = padded(kind, n_q, 1, cfg)
+    eng = model.engine
+    ix = model.build_index(data, level=level, batch_size=16)
+    rows, ids, atoms = ix.rows()
+    ref = reps_of(model, data, level)
+    cnt = amask_of(data).sum(1)
+    assert rows.shape == ref.shape and np.array_equal(_bits(rows), _bits(ref))
+    if level == "structure":
+        assert np.array_equal(ids, np.arange(n_i)) and np.all(atoms == -1)
+    else:
+        assert np.array_equal(ids, np.repeat(np.arange(n_i), cnt)) and np.array_equal(atoms, np.concatenate([np.arange(c) for c in cnt]))
+    # nearest == scann_index_query on the downloaded query rows, bitwise; y and the scores are the plain forward's
+    y, ga = model.predict(queries)
+    got = model.nearest(queries, ix, k=3, batch_size=5)
+    qrows = reps_of(model, queries, level)
+    direct = eng.index_query(ix._ix, qrows, 3)
+    qm = amask_of(queries)
+    assert np.array_equal(_bits(got["predict_property"]), _bits(y))
+    dist = got["distance"] if level == "structure" else got["distance"][qm]
+    nid = got["neighbor_id"] if level == "structure" else got["neighbor_id"][qm]
+    assert np.array_equal(_bits(dist), _bits(np.sqrt(direct["dist2"]))) and np.array_equal(nid, direct["id"])
+    if level == "atom":
+        assert np.array_equal(got["neighbor_atom"][qm], direct["atom"])
+        assert np.all(got["neighbor_id"][~qm] == -1) and np.all(got["neighbor_atom"][~qm] == -1) and not got["distance"][~qm].any()
+    from scann import _hip
+
+    rb = eng.upload(_hip.pack_inputs(queries))
+    r = eng.index_query_batch(ix._ix, rb, _hip.KNN_LEVELS[level], 3)
+    rb.free()
+    assert np.array_equal(_bits(r["y"]), _bits(y[:, 0])) and np.array_equal(_bits(r["ga"]), _bits(ga[qm][:, 0]))
+    assert np.array_equal(r["position"], direct["position"]) and np.array_equal(_bits(r["dist2"]), _bits(direct["dist2"]))
+    # the indexed structures themselves: distance 0 at rank 0, their own id; with exclude_ids not
+    me = model.nearest(data, ix, k=2)
+    loo = model.nearest(data, ix, k=2, exclude_ids=np.arange(n_i))
+    dm = amask_of(data)
+    own = np.arange(n_i) if level == "structure" else np.repeat(np.arange(n_i), cnt)
+    d0, i0 = (me["distance"], me["neighbor_id"]) if level == "structure" else (me["distance"][dm], me["neighbor_id"][dm])
+    d1, i1 = (loo["distance"], loo["neighbor_id"]) if level == "structure" else (loo["distance"][dm], loo["neighbor_id"][dm])
+    assert not d0[:, 0].any() and np.array_equal(i0[:, 0], own)
+    assert np.all(d1[:, 0] > 0) and not np.any(i1 == own[:, None])
+    ix.free()
+
+
+@pytest.mark.parametrize("level", ["structure", "atom"])
+@pytest.mark.parametrize("kind", ["qm9", "mp2018"])
+def test_against_the_fp64_oracle(hip_lib, kind, level):
+    """k = 3.  err = max(1e-4, 2 x the fp32 oracle's own distance error), relative to the RMS of the fp64 distances (the rule of
+    tests/test_gpu_outputs.py).  Every returned distance lies within err of the fp64 distance of the row it names; a query is decided
+    when the fp64 gaps between its first k + 1 candidates all exceed err, and on every decided query the returned neighbours are the
+    fp64 ones, in order.  At most 10 % of the queries may be undecided (asserted before the GPU's answer is looked at)."""
+    k = 3
+    n_i, n_q = E2E[kind]
+    cfg, w, data, model = setup(kind=kind, n=n_i, seed=0)
+    queries = padded(kind, n_q, 1, cfg)
+
+    def oracle_reps(inputs, dt):
+        inter = {}
+        so.forward(cfg, w, inputs, dt, intermediates=inter)
+        return np.asarray(inter["struc_rep"] if level == "structure" else inter["after_Lc"][amask_of(inputs)], dtype=np.float64)
+
+    def dists(a, b):
+        return np.sqrt(knn_ref.dist2_f64(a, b))
+
+    D64 = dists(oracle_reps(queries, np.float64), oracle_reps(data, np.float64))
+    D32 = dists(oracle_reps(queries, np.float32), oracle_reps(data, np.float32))
+    scale = float(np.sqrt(np.mean(D64 * D64)))
+    e32 = float(np.max(np.abs(D32 - D64))) / scale
+    err = max(1e-4, 2 * e32) * scale
+    order = np.argsort(D64, axis=1, kind="stable")
+    first = np.take_along_axis(D64, order[:, :k + 1], axis=1)
+    decided = np.all(np.diff(first, axis=1) > err, axis=1)
+    share = 1.0 - float(decided.mean())
+    print("%s %s: %d rows, %d queries, fp32 oracle error / scale %.2e, err / scale %.2e, undecided %.1f %%" % (
+        kind, level, D64.shape[1], D64.shape[0], e32, err / scale, 100 * share))
+    assert share <= 0.10, share
+    ix = model.build_index(data, level=level)
+    got = model.nearest(queries, ix, k=k)
+    ix.free()
+    qm = amask_of(queries)
+    if level == "structure":
+        pos, dist = got["neighbor_id"], got["distance"]
+    else:
+        first_atom = np.concatenate([[0], np.cumsum(amask_of(data).sum(1))])
+        pos, dist = first_atom[got["neighbor_id"][qm]] + got["neighbor_atom"][qm], got["distance"][qm]
+    assert pos.shape == (D64.shape[0], k) and np.all(pos >= 0)
+    e_gpu = float(np.max(np.abs(dist.astype(np.float64) - np.take_along_axis(D64, pos, axis=1))))
+    wrong = int((pos[decided] != order[decided, :k]).any(axis=1).sum())
+    print("   gpu distance error / scale %.2e (allowed %.2e); decided queries with other neighbours than fp64's: %d of %d" % (
+        e_gpu / scale, err / scale, wrong, int(decided.sum())))
+    assert e_gpu <= err
+    assert wrong == 0
+
+
+def test_add_batch_from_batches_of_8_against_one_batch_of_64(hip_lib):
+    cfg, w, data, model = setup(n=64, seed=0)
+    for level in ("structure", "atom"):
+        a = model.build_index(data, level=level, batch_size=8)
+        b = model.build_index(data, level=level, batch_size=64)
+        ra, rb_ = a.rows(), b.rows()
+        assert len(a) == len(b) and np.array_equal(_bits(ra[0]), _bits(rb_[0])) and np.array_equal(ra[1], rb_[1]) and np.array_equal(ra[2], rb_[2])
+        qa, qb = model.nearest(data, a, k=5, batch_size=64), model.nearest(data, b, k=5, batch_size=3)
+        for key in qa:
+            assert np.array_equal(qa[key], qb[key]), (level, key)
+        a.free()
+        b.free()
+
+
+# ---- state, handles, errors ----
+
+def test_selected_outputs_weights_and_the_batchs_y_survive(hip_lib):
+    from scann import _hip
+
+    cfg, w, data, model = setup(n=6, seed=1)
+    eng = model.engine
+    names = ["local_attention_1", "after_Lc"]
+    before = model.predict(data, outputs=names)
+    y0, ga0 = model.predict(data)
+    eng.set_outputs([1], after_lc=True)
+    try:
+        rb = eng.upload(_hip.pack_inputs(data))
+        eng.forward_resident(rb)
+        y_first, _ = eng.download(rb)
+        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
+        with pytest.raises(_hip.ScannHipError):
+            eng.read_output(rb, _hip.OUT_BF_PROPERTY)
+        ix = eng.index_create(128)
+        eng.index_add_batch(ix, rb, _hip.OUT_BF_PROPERTY, np.arange(6))
+        # right after the call the block belongs to the call's forward: the handle's selection plus bf_property
+        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_BF_PROPERTY)), _bits(eng.index_read(ix)[0]))
+        r = eng.index_query_batch(ix, rb, _hip.OUT_BF_PROPERTY, 2)
+        assert np.array_equal(_bits(r["y"]), _bits(y_first)) and not r["dist2"][:, 0].any()
+        y_again, _ = eng.download(rb)  # the batch's last y
+        assert np.array_equal(_bits(y_again), _bits(y_first))
+        # failing calls leave the selection alone as well
+        wrong = eng.index_create(64)
+        with pytest.raises(_hip.ScannHipError):
+            eng.index_add_batch(wrong, rb, _hip.OUT_BF_PROPERTY)
+        with pytest.raises(_hip.ScannHipError):
+            eng.index_query_batch(ix, rb, 0, 2)
+        eng.forward_resident(rb)
+        eng.download(rb)
+        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
+        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
+        with pytest.raises(_hip.ScannHipError):
+            eng.read_output(rb, _hip.OUT_BF_PROPERTY)
+        rb.free()
+        ix.free()
+        wrong.free()
+    finally:
+        eng.set_outputs()
+    after = model.predict(data, outputs=names)
+    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
+    y1, ga1 = model.predict(data)
+    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+
+
+def test_errors_name_what_is_wrong(hip_lib):
+    import ctypes as C
+
+    from scann import _hip
+
+    cfg, w, data, model = setup(n=4, seed=1)
+    eng = model.engine
+    rb = eng.upload(_hip.pack_inputs(data))
+    ix = eng.index_create(128)
+    eng.index_add(ix, np.zeros((3, 128), np.float32))
+    q = np.zeros((2, 128), np.float32)
+    out = eng._knn_out(2, 32)
+
+    def query(k, nq=2, index=ix, handle=eng):
+        return eng.lib.scann_index_query(handle._h, index._h, _hip._ptr(q), nq, None, k, _hip._ptr(out["dist2"]), None, None, None)
+
+    def message():
+        return (eng.lib.scann_last_error(eng._h) or b"").decode()
+
+    for k in (0, 33, -1):
+        assert query(k) == -1 and "k %d outside 1 .. 32" % k in message()
+        assert eng.lib.scann_index_query_batch(eng._h, ix._h, rb._h, _hip.OUT_BF_PROPERTY, None, k, None, None, _hip._ptr(out["dist2"]), None, None, None) == -1
+    assert query(5, nq=0) == -1 and "empty query" in message()
+    assert query(5) == 0
+    for dim in (0, 1025, -4):
+        h = C.c_void_p()
+        assert eng.lib.scann_index_create(eng._h, dim, C.byref(h)) == -1 and "1 .. 1024" in message()
+    narrow = eng.index_create(64)
+    assert eng.lib.scann_index_add_batch(eng._h, narrow._h, rb._h, _hip.OUT_BF_PROPERTY, None) == -1
+    assert "64 columns" in message() and "dense_out is 128" in message()
+    assert eng.lib.scann_index_query_batch(eng._h, narrow._h, rb._h, _hip.OUT_AFTER_LC, None, 3, None, None, _hip._ptr(out["dist2"]), None, None, None) == -1
+    assert "global_dim is 128" in message()
+    assert eng.lib.scann_index_add_batch(eng._h, ix._h, rb._h, 7, None) == -1 and "level" in message()
+    assert len(narrow) == 0 and len(ix) == 3
+    # an index of another handle
+    cfg2, w2, _, other = setup(n=4, seed=1)
+    assert eng.lib.scann_index_query(other.engine._h, ix._h, _hip._ptr(q), 2, None, 5, _hip._ptr(out["dist2"]), None, None, None) == -1
+    assert "another handle" in (eng.lib.scann_last_error(other.engine._h) or b"").decode()
+    assert eng.lib.scann_index_add(other.engine._h, ix._h, _hip._ptr(q), 2, None, None) == -1 and len(ix) == 3
+    assert eng.lib.scann_index_read(eng._h, ix._h, 2, 2, None, None, None) == -1
+    # the Python layer: ValueError before anything is uploaded
+    lat = model.build_index(data)
+    for kw in (dict(k=0), dict(k=33), dict(batch_size=0)):
+        with pytest.raises(ValueError):
+            model.nearest(data, lat, **kw)
+    with pytest.raises(ValueError):
+        other.nearest(data, lat)
+    with pytest.raises(ValueError):
+        model.build_index(data, level="bond")
+    lat.free()
+    rb.free()
+    ix.free()
+    narrow.free()
+
+
+def test_generic_widths(hip_lib):
+    """widths other than 128 / 8 (the plain-fp32 kernels): rows of 32 and 96 columns"""
+    cfg, w, data, model = setup(n=9, seed=41, local_dim=64, num_head=4, global_dim=96, dense_out=32)
+    for level, dim in (("structure", 32), ("atom", 96)):
+        ix = model.build_index(data, level=level, batch_size=4)
+        assert ix.dim == dim
+        rows, ids, atoms = ix.rows()
+        assert np.array_equal(_bits(rows), _bits(reps_of(model, data, level)))
+        got = model.nearest(data, ix, k=4, batch_size=5)
+        direct = model.engine.index_query(ix._ix, rows, 4)
+        dm = amask_of(data)
+        dist = got["distance"] if level == "structure" else got["distance"][dm]
+        assert np.array_equal(_bits(dist), _bits(np.sqrt(direct["dist2"]))) and not dist[:, 0].any()
+        check_exact(model.engine, ix._ix, rows, ids, atoms, rows[:7] + np.float32(0.01), 5, "generic " + level)
+        ix.free()
+
+
+def child_scenario():
+    """what the environment-switch children run: the index holds the model's rows, nearest is the query on them, y is the forward's"""
+    cfg, w, data, model = setup(n=10, seed=3)
+    queries = padded("qm9", 6, 4, cfg)
+    for level in ("structure", "atom"):
+        ix = model.build_index(data, level=level, batch_size=4)
+        rows, ids, atoms = ix.rows()
+        assert np.array_equal(_bits(rows), _bits(reps_of(model, data, level))), level
+        got = model.nearest(queries, ix, k=3, batch_size=4)
+        direct = model.engine.index_query(ix._ix, reps_of(model, queries, level), 3)
+        qm = amask_of(queries)
+        dist = got["distance"] if level == "structure" else got["distance"][qm]
+        assert np.array_equal(_bits(dist), _bits(np.sqrt(direct["dist2"]))), level
+        y, _ = model.predict(queries)
+        assert np.array_equal(_bits(got["predict_property"]), _bits(y)), level
+        check_exact(model.engine, ix._ix, rows, ids, atoms, reps_of(model, queries, level), 5, "child " + level)
+        ix.free()
+    return model.engine.exact_reruns()
+
+
+@pytest.mark.parametrize("switch", ["SCANN_GENERIC", "SCANN_EXACT"])
+def test_under_an_environment_switch(hip_lib, switch):
+    """a 128 / 8 handle forced onto the plain-fp32 kernels (SCANN_GENERIC=1), a handle whose forwards run exact-fp32 (SCANN_EXACT=1):
+    a fresh process each"""
+    e = dict(os.environ)
+    e[switch] = "1"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_training_handle(hip_lib):
+    """after two training steps: the index and the neighbours are an inference handle's with the same weights, and weights, gradients
+    and the following (deterministic) step are those of a twin that never made the calls"""
+    from scann import _hip
+    from scann.models.scann_model import HipModel
+
+    cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
+    pk = _hip.pack_inputs(data)
+    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
+    res = []
+    for i in range(2):
+        eng = HipModel(cfg, w, device=0, deterministic=True).engine
+        eng.train_begin()
+        rb = eng.upload(pk)
+        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
+        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
+        if i == 0:
+            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
+            rb2 = inf.upload(pk)
+            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
+                a, b = eng.index_create(128), inf.index_create(128)
+                eng.index_add_batch(a, rb, level, np.arange(8))
+                inf.index_add_batch(b, rb2, level, np.arange(8))
+                ra, rb_ = eng.index_read(a), inf.index_read(b)
+                assert np.array_equal(_bits(ra[0]), _bits(rb_[0])) and np.array_equal(ra[1], rb_[1]) and np.array_equal(ra[2], rb_[2])
+                qa, qb = eng.index_query_batch(a, rb, level, 3, np.arange(8)), inf.index_query_batch(b, rb2, level, 3, np.arange(8))
+                for key in qa:
+                    assert np.array_equal(qa[key], qb[key]) and qa[key].dtype == qb[key].dtype, key
+                a.free()
+                b.free()
+            rb2.free()
+        grads, weights = eng.get_grads(), eng.get_weights()
+        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
+        res.append((grads, weights, step, eng.get_weights()))
+        rb.free()
+    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
+    for key in ga:
+        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
+        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
+        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
+    assert sa == sb_
+
+
+def test_repeated_calls_do_not_eat_device_memory(hip_lib):
+    from scann import _hip
+
+    cfg, w, data, model = setup(n=40, seed=2)
+    eng = model.engine
+    rb = eng.upload(_hip.pack_inputs(data))
+    ix = eng.index_create(128)
+    eng.index_add_batch(ix, rb, _hip.OUT_AFTER_LC)
+    first = eng.index_query_batch(ix, rb, _hip.OUT_AFTER_LC, 5)
+    free0, _ = eng.device_memory()
+    for rep in range(30):
+        r = eng.index_query_batch(ix, rb, _hip.OUT_AFTER_LC, 5)
+        assert np.array_equal(r["position"], first["position"])
+        tmp = eng.index_create(128)
+        eng.index_add_batch(tmp, rb, _hip.OUT_BF_PROPERTY)
+        tmp.free()
+    free1, _ = eng.device_memory()
+    rb.free()
+    ix.free()
+    assert free0 - free1 <= 96 << 20, (free0, free1)  # (one 64 MiB chunk of the temporary index may rest in the block cache)
+
+
+def test_save_and_load_on_the_device(hip_lib, tmp_path):
+    from scann.models import LatentIndex
+
+    cfg, w, data, model = setup(n=12, seed=3)
+    for level in ("structure", "atom"):
+        ix = model.build_index(data, level=level, ids=np.arange(12) * 3 + 1)
+        path = str(tmp_path / ("%s.npz" % level))
+        ix.save(path)
+        back = LatentIndex.load(model, path)
+        for a, b in zip(ix.rows(), back.rows()):
+            assert np.array_equal(a, b) and a.dtype == b.dtype
+        qa, qb = model.nearest(data, ix, k=4, exclude_ids=np.arange(12) * 3 + 1), model.nearest(data, back, k=4, exclude_ids=np.arange(12) * 3 + 1)
+        for key in qa:
+            assert np.array_equal(qa[key], qb[key]), key
+        ix.free()
+        back.free()
+
+
+def test_cli_writes_the_nearest_neighbours(hip_lib, tmp_path):
+    """predict_model.py --nearest 3: nearest_<target>.pickle, one unpadded dict per structure, leave-one-out over the dataset itself; the
+    other files' bytes are those of a run without the flag; --nearest-index searches a saved index instead"""
+    import yaml
+
+    from scann.models import SCANN
+    from scann.models.scann_model import save_container
+
+    n = 20
+    de, dn = so.synth_dataset(n, 5)
+    full = np.empty(n, dtype=object)
+    for i in range(n):
+        full[i] = {"Atomic": de[i][0], "Properties": {"homo": float(i)}}
+    np.save(tmp_path / "data_energy.npy", full, allow_pickle=True)
+    np.save(tmp_path / "data_nei.npy", dn, allow_pickle=True)
+    cfg = so.default_config("qm9")
+    cfg["model"]["n_attention"] = 2
+    cfg["hyper"].update(batch_size=8, scaler=False, use_ref=False, target="homo", data_energy_path=str(tmp_path / "data_energy.npy"),
+                        data_nei_path=str(tmp_path / "data_nei.npy"), save_path=str(tmp_path / "run"))
+    out = tmp_path / "model"
+    os.makedirs(out / "models")
+    yaml.safe_dump(cfg, open(out / "config.yaml", "w"))
+    save_container(str(out / "models" / "model_homo.h5"), cfg, so.init_weights(cfg, 77, perturb=True))
+    cli = [sys.executable, os.path.join(ROOT, "predict_model.py"), str(out)]
+    r = subprocess.run(cli, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    plain = {f: open(out / f, "rb").read() for f in ("ga_scores_homo.pickle", "energy_pre_homo.pickle")}
+    assert not os.path.exists(out / "nearest_homo.pickle")
+    r = subprocess.run(cli + ["--nearest", "3"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    for f, b in plain.items():
+        assert open(out / f, "rb").read() == b, f
+    got = pickle.load(open(out / "nearest_homo.pickle", "rb"))
+    scann = SCANN(yaml.safe_load(open(out / "config.yaml")), str(out / "models" / "model_homo.h5"), mode="infer")
+    scann.prepare_dataset(split=False)
+    data = scann.dataIter
+    index = scann.build_index(data, ids=data.indexes)
+    i = 0
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        sel = np.asarray(data.indexes[b * 8:(b + 1) * 8])
+        ref = scann.nearest(inputs, index, k=3, exclude_ids=sel)
+        for s in range(len(sel)):
+            d = got[i]
+            assert sorted(d) == ["distance", "latent_distance", "neighbor_id", "predict_property"]
+            assert np.array_equal(d["distance"], ref["distance"][s]) and np.array_equal(d["neighbor_id"], ref["neighbor_id"][s])
+            assert d["latent_distance"] == float(ref["latent_distance"][s, 0]) and d["predict_property"] == float(ref["predict_property"][s, 0])
+            assert sel[s] not in d["neighbor_id"] and np.all(d["neighbor_id"] >= 0) and np.all(d["distance"] > 0)
+            i += 1
+    assert i == n == len(got)
+    # a saved atom-level index searched instead: nothing is left out, every atom finds itself
+    atom_ix = scann.build_index(data, level="atom", ids=data.indexes)
+    atom_ix.save(str(tmp_path / "atoms.npz"))
+    r = subprocess.run(cli + ["--nearest", "2", "--nearest-index", str(tmp_path / "atoms.npz")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    got = pickle.load(open(out / "nearest_homo.pickle", "rb"))
+    assert len(got) == n
+    for i, d in enumerate(got):
+        n_at = len(de[data.indexes[i]][0])
+        assert d["distance"].shape == (n_at, 2) and d["neighbor_atom"].shape == (n_at, 2) and d["latent_distance"].shape == (n_at,)
+        assert not d["distance"][:, 0].any()
+    for f, b in plain.items():
+        assert open(out / f, "rb").read() == b, f
+
+
+if __name__ == "__main__":
+    child_scenario()
+    print("child ok")
