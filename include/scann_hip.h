@@ -397,6 +397,39 @@ int scann_index_query_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_
 float scann_knn_distsq(const float* q, const float* r, int64_t d);
 void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out);
 
+/* ---- greedy k-center selection: the most diverse rows of an index, picked on the device ----
+ * Which m candidates should be labelled next, given what is labelled already?  Farthest-point selection in latent space (the core-set
+ * rule of Sener & Savarese, ICLR 2018): repeatedly take the candidate whose distance to everything labelled or already taken is
+ * largest.  Each pick comes with the covering radius at that moment.  Without a reference the same call thins a redundant set to m
+ * representative rows.
+ * Inputs: a pool index P with N rows; an optional reference index R (NULL or empty: none; otherwise of the same dim, of the same handle
+ * and a different object from P); a count m >= 1; a threshold stop_dist2 (<= 0: none).
+ * Distance: dist2 is exactly the chain of scann_knn_distsq above: fp32, acc = fmaf(q[j] - r[j], q[j] - r[j], acc), columns ascending.
+ * It is symmetric bit for bit, because fl(a - b) = -fl(b - a).
+ * Eligibility: a pool row is eligible if and only if all its dim components are finite.  Ineligible rows are never picked; this includes
+ * a row picked as a centre already.  Between eligible rows no distance is NaN; overflow gives +inf, which is ordered.
+ * Initial distances: mind[p] is the least dist2(P[p], R[r]) over the rows r of R, with the rule of scann_index_query: a NaN distance
+ * never counts.  With no such row it is +inf.  (It is the k = 1 query of the pool's own rows against R, run device to device.)
+ * Each pick i = 0, 1, ...: (1) among the eligible rows not yet picked, take the first under the TOTAL order (mind descending, position
+ * ascending); (2) report its position, id, atom and radius2[i] = mind at that moment; (3) mark it picked; (4) update
+ * mind[p] = min(mind[p], dist2(P[p], P[pick])) for every p.
+ * Selection ends when m picks are made, or no eligible unpicked row is left, or stop_dist2 > 0 and the next pick's mind < stop_dist2
+ * (that pick is not made).
+ * Consequences: radius2 is non-increasing.  Without a reference the first pick is the lowest-positioned eligible row, with radius +inf.
+ * An exact duplicate of a picked row has mind 0 and is picked only after every row at a positive distance.  The result depends on the
+ * contents of P and R alone: not on chunking, on how many add calls built the indices or on the launch geometry.
+ * Return: the number of picks made (>= 0) or a negative status.  Places behind that count hold position -1, id -1, atom -1, radius2 +inf.
+ * SCANN_ERR_INVALID before anything is launched: a null handle or pool, an index of another handle, P == R, different dim, m < 1, a NaN
+ * stop_dist2, a null pos.  An empty pool returns 0.
+ * The call is synchronous.  It changes nothing in P, R, the handle's weights, training state or selected outputs; it works on inference
+ * and training handles at any width and runs no forward.  All m picks are enqueued on one stream and the host waits once: the picked
+ * position and the end of the selection travel from pick to pick through device memory. */
+int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t* reference /* or NULL */, int64_t m, float stop_dist2,
+                           int32_t* pos, int64_t* ids, int32_t* atoms, float* radius2);   /* [m] each; ids, atoms, radius2 may be NULL */
+/* the definition on the host, no GPU work: rows [n * dim], ref [nr * dim] (nr may be 0); the kernel's bits */
+int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, float stop_dist2,
+                           int32_t* pos, float* radius2);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -12,6 +12,10 @@ per structure with ``attribution`` [n] (the GA scores traced back to the atoms t
 with the K nearest structures of the dataset in the model's latent space (``neighbor_id``: dataset indices, the structure itself left
 out; ``distance``; ``latent_distance``: their mean, an uncertainty measure), or per atom at ``--nearest-level atom`` (``neighbor_atom``
 as well).  With ``--nearest-index FILE`` a saved ``LatentIndex``, for example of the training set, is searched and nothing is left out.
+``--select M [--select-level atom] [--select-reference FILE]`` also pickles ``selected_<target>.pickle``: one dict with the M most
+diverse structures of the dataset (or atoms, at ``--select-level atom``) by greedy k-center selection in the model's latent space, in
+pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering radius at each pick; ``position``; ``count``).  With
+``--select-reference FILE``, a saved ``LatentIndex`` of what is labelled already, they are the dataset's structures farthest from it.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -80,6 +84,8 @@ def main(args):
         return main_with(args)
     if args.nearest and not 1 <= args.nearest <= 32:
         raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
+    if args.select < 0:
+        raise SystemExit("--select: M must be >= 1, got %d" % args.select)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     target = config["hyper"]["target"]
     print("Load pretrained weight for target ", target)
@@ -163,6 +169,19 @@ def main(args):
         per = nearest_records(scann, data, index, args.nearest, exclude=not args.nearest_index)
         index.free()
         pickle.dump(per, open(os.path.join(args.trained_model, "nearest_{}.pickle".format(target)), "wb"))
+    if args.select:
+        from scann.models import LatentIndex
+
+        reference = LatentIndex.load(scann.model, args.select_reference) if args.select_reference else None
+        level = reference.level if reference is not None else args.select_level
+        pool = scann.build_index(data, level=level, ids=data.indexes)
+        print("Select %d of the dataset's %d rows (%s level)%s" % (args.select, len(pool), level, ", farthest from the %d rows of %s" % (
+            len(reference), args.select_reference) if reference is not None else ""))
+        sel = scann.select_diverse(pool, args.select, reference=reference)
+        pool.free()
+        if reference is not None:
+            reference.free()
+        pickle.dump(sel, open(os.path.join(args.trained_model, "selected_{}.pickle".format(target)), "wb"))
 
 
 def nearest_records(scann, data, index, k, exclude):
@@ -208,6 +227,13 @@ def parser():
                    help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
     p.add_argument("--nearest-index", type=str, default="",
                    help="a saved LatentIndex (.npz) to search instead of the dataset itself; nothing is left out")
+    p.add_argument("--select", type=int, default=0,
+                   help="also pickle the M most diverse structures of the dataset (greedy k-center selection in latent space) as "
+                        "selected_<target>.pickle: one dict with ids (dataset indices), atoms and radii in pick order")
+    p.add_argument("--select-level", type=str, default="structure", choices=["structure", "atom"],
+                   help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
+    p.add_argument("--select-reference", type=str, default="",
+                   help="a saved LatentIndex (.npz) of what is labelled already: the picks are the dataset's rows farthest from it")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

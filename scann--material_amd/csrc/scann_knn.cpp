@@ -5,6 +5,7 @@
 // scann_attention_rollout adds its attention maps: y, the scores, the range guard and the exact re-run behave exactly as they do there.
 #include "scann_knn.h"
 #include "scann_runtime.h"
+#include "scann_select.h"
 
 using namespace scann;
 
@@ -109,9 +110,11 @@ int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch,
   return SCANN_OK;
 }
 
-// nq queries on the device ([nq][stride], padded like the rows; qid: device [nq] or null) against the whole index
+// nq queries on the device ([nq][stride], padded like the rows; qid: device [nq] or null) against the whole index.  dev_d non-null: the
+// distances [nq][k] are left there, on the device, and nothing comes back to the host (scann_index_select: the pool's rows against the
+// reference, k = 1)
 int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
-           int32_t* atoms, int32_t* pos) {
+           int32_t* atoms, int32_t* pos, float* dev_d = nullptr) {
   const int64_t N = ix->n;
   const int rpr = (int)std::max<int64_t>(KNN_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + KNN_TR - 1) / KNN_TR * KNN_TR);
   // one launch over all chunks: every chunk is cut into the same number of ranges (those behind the last row stay empty)
@@ -129,7 +132,7 @@ int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqi
   int32_t* out_p = reinterpret_cast<int32_t*>(ws + 2 * bP + bO);
   std::vector<const void*> tab((size_t)2 * std::max(n_chunk, 1), nullptr);  // the chunks' rows, then their ids
   for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = ix->rows_of((size_t)c), tab[(size_t)n_chunk + c] = ix->ids_of((size_t)c);
-  std::vector<int32_t> pos_h((size_t)nq * k);
+  std::vector<int32_t> pos_h(dev_d ? 0 : (size_t)nq * k);
   hipError_t e = hipSuccess;
   if (n_chunk > 0) {
     e = hipMemcpyAsync(ws + 2 * bP + 2 * bO, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
@@ -144,12 +147,14 @@ int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqi
     a.stride = ix->stride; a.q = dq + (size_t)q0 * ix->stride; a.qid = dqid ? dqid + q0 : nullptr; a.nq = m; a.k = k; a.rows_per_range = rpr;
     a.part_d = part_d; a.part_p = part_p; a.n_range = (int)n_range;
     e = launch_knn_tile(a, s);
-    if (e == hipSuccess) e = launch_knn_merge(part_d, part_p, m, (int)n_range, k, out_d, out_p, s);
+    if (e == hipSuccess) e = launch_knn_merge(part_d, part_p, m, (int)n_range, k, dev_d ? dev_d + (size_t)q0 * k : out_d, out_p, s);
+    if (dev_d) continue;  // (the stream orders the next group's use of the partial lists)
     if (e == hipSuccess) e = hipMemcpyAsync(dist2 + (size_t)q0 * k, out_d, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(pos_h.data() + (size_t)q0 * k, out_p, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
   }
-  if (e != hipSuccess) (void)hipStreamSynchronize(s);
+  if (dev_d && e == hipSuccess) e = hipStreamSynchronize(s);
+  else if (e != hipSuccess) (void)hipStreamSynchronize(s);
   cached_free(ws);
   HIPCHK(h, e);
   for (size_t i = 0; i < pos_h.size(); ++i) {
@@ -178,6 +183,22 @@ int read_mol(scann_handle* h, scann_dbatch* db, std::vector<int32_t>& mol) {
   mol.assign((size_t)db->n_struct + 1, 0);
   if (db->n_struct > 0) HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
   return SCANN_OK;
+}
+
+// dist2 of one vector to n rows, the chain above (with the host's fused multiply-add where it has one: the same bits)
+void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out) {
+  if (__builtin_cpu_supports("fma")) dist2_matrix_fma(q, 1, rows, n, d, out);
+  else dist2_matrix_plain(q, 1, rows, n, d, out);
+}
+
+// the places of a selection's outputs from `from` on: no pick
+void select_tail(int64_t from, int64_t m, int32_t* pos, int64_t* ids, int32_t* atoms, float* radius2) {
+  for (int64_t i = from; i < m; ++i) {
+    pos[i] = -1;
+    if (ids) ids[i] = -1;
+    if (atoms) atoms[i] = -1;
+    if (radius2) radius2[i] = __builtin_inff();
+  }
 }
 
 }  // namespace
@@ -351,6 +372,113 @@ int scann_index_query_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t
   if (y && B > 0) memcpy(y, y_h.data(), (size_t)B * 4);
   if (ga && A > 0) memcpy(ga, ga_h.data(), (size_t)A * 4);
   return SCANN_OK;
+}
+
+int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, float stop_dist2, int32_t* pos,
+                           float* radius2) {
+  if (n < 0 || nr < 0 || dim < 1 || m < 1 || stop_dist2 != stop_dist2 || !pos || (n > 0 && !rows) || (nr > 0 && !ref) || n > (int64_t)0x7fffffff)
+    return SCANN_ERR_INVALID;
+  select_tail(0, m, pos, nullptr, nullptr, radius2);
+  if (n == 0) return 0;
+  std::vector<float> mind((size_t)n, __builtin_inff()), tmp((size_t)std::max(n, nr));
+  std::vector<char> live((size_t)n, 1);
+  for (int64_t p = 0; p < n; ++p)
+    for (int64_t j = 0; j < dim; ++j)
+      if (!std::isfinite(rows[p * dim + j])) live[(size_t)p] = 0;
+  for (int64_t p = 0; p < n && nr > 0; ++p) {
+    if (!live[(size_t)p]) continue;
+    dist2_to_rows(rows + p * dim, ref, nr, dim, tmp.data());
+    for (int64_t r = 0; r < nr; ++r)  // a NaN distance never counts
+      if (tmp[(size_t)r] < mind[(size_t)p]) mind[(size_t)p] = tmp[(size_t)r];
+  }
+  int64_t cnt = 0;
+  while (cnt < m) {
+    int64_t best = -1;
+    for (int64_t p = 0; p < n; ++p)  // mind descending, position ascending
+      if (live[(size_t)p] && (best < 0 || mind[(size_t)p] > mind[(size_t)best])) best = p;
+    if (best < 0 || (stop_dist2 > 0.f && mind[(size_t)best] < stop_dist2)) break;
+    pos[cnt] = (int32_t)best;
+    if (radius2) radius2[cnt] = mind[(size_t)best];
+    live[(size_t)best] = 0;
+    if (++cnt == m) break;
+    dist2_to_rows(rows + best * dim, rows, n, dim, tmp.data());
+    for (int64_t p = 0; p < n; ++p)
+      if (live[(size_t)p] && tmp[(size_t)p] < mind[(size_t)p]) mind[(size_t)p] = tmp[(size_t)p];
+  }
+  return cnt;
+}
+
+int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t* reference, int64_t m, float stop_dist2, int32_t* pos, int64_t* ids,
+                           int32_t* atoms, float* radius2) {
+  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_select: null handle or pool");
+  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_select: the pool belongs to another handle");
+  if (reference == pool) return fail(h, SCANN_ERR_INVALID, "scann_index_select: the reference is the pool itself");
+  if (reference && reference->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_select: the reference belongs to another handle");
+  if (reference && reference->dim != pool->dim)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_select: the pool holds rows of " + std::to_string(pool->dim) + " columns, the reference of " +
+                                          std::to_string(reference->dim));
+  if (m < 1) return fail(h, SCANN_ERR_INVALID, "scann_index_select: m " + std::to_string(m) + " is not >= 1");
+  if (stop_dist2 != stop_dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_select: stop_dist2 is NaN");
+  if (!pos) return fail(h, SCANN_ERR_INVALID, "scann_index_select: pos is null");
+  const int64_t N = pool->n;
+  if (N > (int64_t)0x7fffffff - 2 * KC_LANES) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_select: the pool has too many rows");
+  select_tail(0, m, pos, ids, atoms, radius2);
+  if (N == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  KcArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = pool->stride;
+  a.n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
+  a.tiles_per_chunk = (pool->chunk_rows + KC_LANES - 1) / KC_LANES;
+  a.n_tile = a.n_chunk * a.tiles_per_chunk;
+  a.n_pick = (int32_t)std::min<int64_t>(m, N);
+  a.stop = stop_dist2;
+  const int groups = std::min(a.n_tile, KC_MAX_GROUPS);
+  // one workspace for the call: the state (first: it is what the memset clears), mind, the picks, the candidates, the chunk table, live
+  const size_t bS = 256, bM = align_up((size_t)N * 4), bO = align_up((size_t)a.n_pick * 4), bP = align_up((size_t)groups * 8),
+               bT = align_up((size_t)a.n_chunk * 8), bL = align_up((size_t)N);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bS + bM + 2 * bO + bP + bT + bL));
+  a.st = reinterpret_cast<KcState*>(ws);
+  a.mind = reinterpret_cast<float*>(ws + bS);
+  a.out_pos = reinterpret_cast<int32_t*>(ws + bS + bM);
+  a.out_r2 = reinterpret_cast<float*>(ws + bS + bM + bO);
+  a.part = reinterpret_cast<unsigned long long*>(ws + bS + bM + 2 * bO);
+  a.rows = reinterpret_cast<const float* const*>(ws + bS + bM + 2 * bO + bP);
+  a.live = reinterpret_cast<uint8_t*>(ws + bS + bM + 2 * bO + bP + bT);
+  std::vector<const void*> tab((size_t)a.n_chunk);
+  for (int c = 0; c < a.n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  const bool has_ref = reference && reference->n > 0;
+  int r = SCANN_OK;
+  hipError_t e = hipMemsetAsync(ws, 0, sizeof(KcState), s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + bS + bM + 2 * bO + bP, tab.data(), (size_t)a.n_chunk * 8, hipMemcpyHostToDevice, s);
+  // the initial mind: the k = 1 query of the pool's own rows, chunk by chunk where they lie, against the reference
+  for (int c = 0; c < a.n_chunk && has_ref && e == hipSuccess && !r; ++c)
+    r = search(h, reference, pool->rows_of((size_t)c), nullptr, std::min<int64_t>(pool->chunk_rows, N - (int64_t)c * pool->chunk_rows), 1, s, nullptr,
+               nullptr, nullptr, nullptr, a.mind + (size_t)c * pool->chunk_rows);
+  if (e == hipSuccess && !r) e = launch_kcenter_prepare(a, has_ref, s);
+  // every pick is enqueued at once: a pick reads its predecessor's position, and whether the selection has ended, from device memory
+  for (int i = 0; i < a.n_pick && e == hipSuccess && !r; ++i) e = launch_kcenter_step(a, groups, s);
+  KcState st{};
+  std::vector<int32_t> pos_h((size_t)a.n_pick);
+  std::vector<float> r2_h((size_t)a.n_pick);
+  if (e == hipSuccess && !r) e = hipMemcpyAsync(pos_h.data(), a.out_pos, (size_t)a.n_pick * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && !r) e = hipMemcpyAsync(r2_h.data(), a.out_r2, (size_t)a.n_pick * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && !r) e = hipMemcpyAsync(&st, a.st, sizeof(KcState), hipMemcpyDeviceToHost, s);
+  const hipError_t e_sync = hipStreamSynchronize(s);
+  cached_free(ws);
+  if (r) return r;
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  const int64_t cnt = std::min<int64_t>(std::max<int32_t>(st.count, 0), a.n_pick);
+  for (int64_t i = 0; i < cnt; ++i) {
+    const int32_t p = pos_h[(size_t)i];
+    pos[i] = p;
+    if (ids) ids[i] = pool->ids[(size_t)p];
+    if (atoms) atoms[i] = pool->atoms[(size_t)p];
+    if (radius2) radius2[i] = r2_h[(size_t)i];
+  }
+  return cnt;
 }
 
 }  // extern "C"

@@ -127,6 +127,8 @@ SYMBOLS = [
     ("scann_index_query_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("scann_knn_distsq", C.c_float, [_P, _P, C.c_int64]),
     ("scann_knn_distsq_matrix", None, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
+    ("scann_index_select", C.c_int64, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
+    ("scann_kcenter_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -172,6 +174,38 @@ def knn_dist2_matrix(q, rows):
     out = np.zeros((q.shape[0], rows.shape[0]), dtype=np.float32)
     load_library().scann_knn_distsq_matrix(_ptr(q), q.shape[0], _ptr(rows), rows.shape[0], q.shape[1], _ptr(out))
     return out
+
+
+def check_select_args(m, stop_dist2):
+    """(m, stop_dist2) of a k-center selection as the C calls take them; ValueError for an m that is no integer >= 1 and for a NaN
+    threshold (<= 0 means none)."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+        raise ValueError("m must be an integer >= 1, got %r" % (m,))
+    try:
+        stop_dist2 = float(stop_dist2)
+    except (TypeError, ValueError):
+        raise ValueError("stop_dist2 must be a number, got %r" % (stop_dist2,)) from None
+    if stop_dist2 != stop_dist2:
+        raise ValueError("stop_dist2 must not be NaN")
+    return int(m), stop_dist2
+
+
+def kcenter_host(rows, ref, m, stop_dist2=0.0):
+    """Greedy k-center selection on the host with the kernel's bits (scann_kcenter_host, the definition in include/scann_hip.h):
+    ``rows`` [n, dim] the pool, ``ref`` [nr, dim] the reference or None.  {"position" [m] int32, "radius2" [m] fp32, "count"}: the
+    places behind ``count`` hold -1 / +inf."""
+    m, stop_dist2 = check_select_args(m, stop_dist2)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("kcenter_host: rows of shape %s" % (rows.shape,))
+    ref = np.zeros((0, rows.shape[1]), np.float32) if ref is None else np.ascontiguousarray(ref, dtype=np.float32)
+    if ref.ndim != 2 or ref.shape[1] != rows.shape[1]:
+        raise ValueError("kcenter_host: shapes %s and %s" % (rows.shape, ref.shape))
+    pos, r2 = np.empty(m, np.int32), np.empty(m, np.float32)
+    cnt = int(load_library().scann_kcenter_host(_ptr(rows), rows.shape[0], _ptr(ref), ref.shape[0], rows.shape[1], m, stop_dist2, _ptr(pos), _ptr(r2)))
+    if cnt < 0:
+        raise ValueError("kcenter_host: invalid arguments (%d)" % cnt)
+    return {"position": pos, "radius2": r2, "count": cnt}
 
 
 
@@ -910,6 +944,20 @@ class Engine:
         out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
         self._check(self.lib.scann_index_query_batch(self._h, ix._h, rb._h, int(level), _ptr(qid), k, _ptr(out["y"]), _ptr(out["ga"]),
                                                      _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["position"])))
+        return out
+
+    def index_select(self, pool_ix, ref_ix, m, stop_dist2=0.0):
+        """Greedy k-center selection of ``m`` rows of ``pool_ix``, farthest first from the rows of ``ref_ix`` (None: no reference) and
+        from each other (scann_index_select): {"position", "id", "atom", "radius2"} [m], "count"; behind ``count``: -1 / +inf."""
+        m, stop_dist2 = check_select_args(m, stop_dist2)
+        if ref_ix is not None and (ref_ix is pool_ix or ref_ix.dim != pool_ix.dim):
+            raise ValueError("index_select: the reference must be another index of %d columns" % pool_ix.dim)
+        out = {"position": np.empty(m, np.int32), "id": np.empty(m, np.int64), "atom": np.empty(m, np.int32), "radius2": np.empty(m, np.float32)}
+        cnt = int(self.lib.scann_index_select(self._h, pool_ix._h, None if ref_ix is None else ref_ix._h, m, stop_dist2, _ptr(out["position"]),
+                                              _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["radius2"])))
+        if cnt < 0:
+            self._check(cnt)
+        out["count"] = cnt
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

@@ -58,6 +58,20 @@ def count_structures(data):
     return n
 
 
+def stop_dist2_of(stop_distance):
+    """``stop_distance`` of a selection as the squared fp32 threshold the C call takes (None: 0, no threshold); ValueError for a
+    negative or NaN one."""
+    if stop_distance is None:
+        return 0.0
+    try:
+        stop = float(stop_distance)
+    except (TypeError, ValueError):
+        raise ValueError("stop_distance must be None or a number >= 0, got %r" % (stop_distance,)) from None
+    if not stop >= 0.0:
+        raise ValueError("stop_distance must be None or a number >= 0, got %r" % (stop_distance,))
+    return float(np.float32(stop) * np.float32(stop))
+
+
 class LatentIndex:
     """Rows of one level of one model on its GPU.  ``level``: "structure" (one ``bf_property`` row per structure) or "atom" (one
     ``after_Lc`` row per real atom).  Every row carries the id of its structure and, at atom level, the atom's index within it."""
@@ -126,6 +140,29 @@ class LatentIndex:
             ix.add_rows(rows, ids, atoms)
         ix._n_struct = int(ids.max()) + 1 if len(ids) else 0  # default ids of later adds do not collide
         return ix
+
+    def select(self, m, reference=None, stop_distance=None):
+        """The ``m`` most diverse rows of this index by greedy k-center (farthest-point) selection on the GPU: repeatedly the row whose
+        distance to every row of ``reference`` (a ``LatentIndex`` of the same model, level and width; None: nothing is labelled yet) and
+        to every row already taken is largest, ties to the earlier position; rows with a non-finite component are never taken.
+        ``stop_distance``: selection ends before the first pick nearer than this to what is covered already (None: no threshold).
+        Returns {"position" int32, "neighbor_id" int64 (the structure ids), "atom" int32, "radius" fp32 -- the covering radius at each
+        pick, non-increasing, ``inf`` for a first pick without a reference --, "count"}, every array cut to the picks made.  A bad ``m``,
+        a negative or NaN ``stop_distance`` or an unfit reference raise ValueError before any device call."""
+        m, _ = _hip.check_select_args(m, 0.0)
+        stop2 = stop_dist2_of(stop_distance)
+        if reference is not None:
+            if reference is self:
+                raise ValueError("the reference is the pool itself: every row would be at distance 0")
+            if not isinstance(reference, LatentIndex):
+                raise ValueError("reference must be a LatentIndex or None, got %r" % (type(reference).__name__,))
+            if reference.model is not self.model or reference.level != self.level or reference.dim != self.dim:
+                raise ValueError("the reference is a %s-level index of %d columns%s, the pool a %s-level index of %d" % (
+                    reference.level, reference.dim, "" if reference.model is self.model else " of another model", self.level, self.dim))
+        r = self.model.engine.index_select(self._ix, None if reference is None else reference._ix, m, stop2)
+        n = int(r["count"])
+        return {"position": r["position"][:n], "neighbor_id": r["id"][:n], "atom": r["atom"][:n],
+                "radius": np.sqrt(r["radius2"][:n]), "count": n}  # (correctly rounded on the host, as nearest reports distances)
 
     def free(self):
         self._ix.free()

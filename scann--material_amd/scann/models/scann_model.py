@@ -405,6 +405,43 @@ class HipModel:
                     out[n] = full
         return out
 
+    def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
+        """Which ``m`` structures (or atoms, ``level`` "atom") of ``pool`` to label next: greedy k-center selection in the model's latent
+        space (``LatentIndex.select``; the core-set rule of Sener & Savarese, ICLR 2018), farthest first from everything in ``reference``
+        -- what is labelled already -- and from the picks so far.  Without a reference the call thins ``pool`` to ``m`` representative
+        rows.  ``pool`` and ``reference`` are each a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes
+        it, which is indexed for the call and freed afterwards (ids: 0 .. n-1 in input order).  Returns ``LatentIndex.select``'s dict.
+        Bad arguments raise ValueError before anything is uploaded."""
+        from .latent_index import LatentIndex, level_dim, stop_dist2_of
+
+        level_dim(self.config, level)
+        m, _ = _hip.check_select_args(m, 0.0)
+        stop_dist2_of(stop_distance)
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        if reference is not None and reference is pool:
+            raise ValueError("the reference is the pool itself: every row would be at distance 0")
+        for ix in (pool, reference):
+            if isinstance(ix, LatentIndex) and (ix.model is not self or level_dim(self.config, ix.level) != ix.dim):
+                raise ValueError("the index was built for another model: it lives on that model's GPU handle (%s level, %d columns)" % (
+                    ix.level, ix.dim))
+        if isinstance(pool, LatentIndex):
+            level = pool.level
+        if isinstance(reference, LatentIndex) and reference.level != level:
+            raise ValueError("the reference is a %s-level index, the pool's level is %s" % (reference.level, level))
+        own = []
+        try:
+            if not isinstance(pool, LatentIndex):
+                pool = self.build_index(pool, level=level, batch_size=batch_size)
+                own.append(pool)
+            if reference is not None and not isinstance(reference, LatentIndex):
+                reference = self.build_index(reference, level=level, batch_size=batch_size)
+                own.append(reference)
+            return pool.select(m, reference=reference, stop_distance=stop_distance)
+        finally:
+            for ix in own:
+                ix.free()
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -927,6 +964,10 @@ class SCANN:
         out = self.model.nearest(ip, index, k=k, exclude_ids=exclude_ids, batch_size=batch_size)
         out["predict_property"] = out["predict_property"] * self.std + self.mean
         return out
+
+    def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
+        """HipModel.select_diverse as it is: the distances live in latent space."""
+        return self.model.select_diverse(pool, m, reference=reference, level=level, stop_distance=stop_distance, batch_size=batch_size)
 
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
         """HipModel.predict_uncertainty in the units of the target, as predict_data de-normalises: the mean times std plus mean, the
