@@ -1,6 +1,6 @@
 // scann_ablate_pooling (include/scann_hip.h): one forward of the resident batch, then every ablated pooling of one mode from the readout's
-// operands gq / gk that the forward left on the device (scann_ablate.hip).  The forward and the download are the public ones, so y, the
-// GlobalAttention scores, the range guard and the exact re-run behave exactly as they do there.
+// operands gq / gk that the forward left on the device (scann_ablate.hip).  The forward and its download are forward_and_download
+// (scann_batch.cpp): y, the GlobalAttention scores, the range guard and the exact re-run behave as in scann_batch_download.
 #include "scann_runtime.h"
 
 using namespace scann;
@@ -18,10 +18,7 @@ int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, fl
     return fail(h, SCANN_ERR_UNSUPPORTED, "scann_ablate_pooling: a structure of " + std::to_string(db->max_atoms) + " atoms exceeds the limit of " +
                                               std::to_string(SCANN_ABLATE_MAX_ATOMS) + " atoms per structure (32 score rows of one structure in 160 KiB of LDS)");
   const int A = db->n_atom, B = db->n_struct;
-  std::vector<float> y_h((size_t)std::max(B, 1)), ga_h((size_t)std::max(A, 1));
-  int r = scann_forward_resident(h, db, db->last_slot);
-  if (r) return r;
-  if ((r = scann_batch_download(h, db, y_h.data(), ga_h.data()))) return r;
+  if (const int r = forward_and_download(h, db, 0, 0, y, ga)) return r;
   hipStream_t s = h->streams[db->last_slot];
   const size_t bY = align_up((size_t)std::max(A, 1) * 4);
   char* ws = nullptr;
@@ -46,8 +43,6 @@ int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, fl
   if (e == hipSuccess && A > 0 && order) e = hipMemcpy(order, a.order, (size_t)A * 4, hipMemcpyDeviceToHost);
   cached_free(ws);
   HIPCHK(h, e);
-  if (y && B > 0) memcpy(y, y_h.data(), (size_t)B * 4);
-  if (ga && A > 0) memcpy(ga, ga_h.data(), (size_t)A * 4);
   return SCANN_OK;
 }
 

@@ -293,7 +293,7 @@ static int fetch_results(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, f
     if (bad & 1) return fail(h, SCANN_ERR_INVALID, "scann_batch_download: an unmasked neighbour slot points at a padded atom (or outside the structure)");
     if (bad & 2) return fail(h, SCANN_ERR_INVALID, "scann_batch_download: atomic number outside the embedding table (n_atoms)");
   }
-  memcpy(y_out, st.p + y_off, (size_t)db->n_struct * 4);
+  if (y_out) memcpy(y_out, st.p + y_off, (size_t)db->n_struct * 4);
   if (ga_attn_out) memcpy(ga_attn_out, st.p, (size_t)db->n_atom * 4);
   return SCANN_OK;
 }
@@ -334,13 +334,47 @@ int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, 
   const int site = code >> 8;
   if (!code || site < 1 || site > 4) return SCANN_OK;
   h->range_flag[db->last_slot] = 0;
-  FwdOpts o;
+  FwdOpts o;  // (what the batch recorded for the forward that is run again, not what the handle selects by now)
   o.exact = true;
+  o.out_layers = db->out_layers;
+  o.out_flags = db->out_flags;
   const int r = run_forward(h, db, s, o);
   if (r) return r;
   h->exact_reruns++;
   *rerun = true;
   HIPCHK(h, hipStreamSynchronize(s));
+  return SCANN_OK;
+}
+
+// scann_batch_download behind its argument checks
+static int download(scann_handle_t* h, scann_dbatch_t* db, float* y_out, float* ga_attn_out) {
+  hipStream_t s = h->streams[db->last_slot];
+  const int rf = fetch_results(h, db, s, y_out, ga_attn_out);
+  if (rf) return rf;
+  // The forward's range guard fired: an activation left the range of the split-fp16 projections (sites 1-4).  The reference runs any
+  // fp32 values (attention.py:95-113), so the forward is run again on the exact-fp32 instantiations (1/16 of the matrix rate, this
+  // batch only) instead of handing an error back -- unless SCANN_STRICT_RANGE=1 asks for the error.
+  bool rerun = false;
+  if (const int r = rerun_if_out_of_range(h, db, s, &rerun)) return r;
+  if (rerun) {
+    const int rf3 = fetch_results(h, db, s, y_out, ga_attn_out);
+    if (rf3) return rf3;
+  }
+  db->idle = true;
+  db->fwd_pending = false;
+  return check_range(h, "scann_batch_download", db->last_slot);
+}
+
+int forward_and_download(scann_handle_t* h, scann_dbatch_t* db, uint64_t layers, int32_t flags, float* y, float* ga) {
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const int r = run_forward(h, db, h->streams[db->last_slot], selected_opts(h, layers, flags))) return r;
+  return download(h, db, y, ga);
+}
+
+int read_mol_offset(scann_handle_t* h, const scann_dbatch_t* db, std::vector<int32_t>& mol) {
+  mol.assign((size_t)db->n_struct + 1, 0);
+  if (db->upload_ev && !db->upload_done) HIPCHK(h, hipEventSynchronize(db->upload_ev));
+  if (db->n_struct > 0) HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
   return SCANN_OK;
 }
 
@@ -403,21 +437,7 @@ int scann_batch_info(scann_handle_t* h, const scann_dbatch_t* db, int32_t* out8)
 int scann_batch_download(scann_handle_t* h, scann_dbatch_t* db, float* y_out, float* ga_attn_out) {
   if (!h || !db || !y_out) return fail(h, SCANN_ERR_INVALID, "scann_batch_download: null argument");
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->streams[db->last_slot];
-  const int rf = fetch_results(h, db, s, y_out, ga_attn_out);
-  if (rf) return rf;
-  // The forward's range guard fired: an activation left the range of the split-fp16 projections (sites 1-4).  The reference runs any
-  // fp32 values (attention.py:95-113), so the forward is run again on the exact-fp32 instantiations (1/16 of the matrix rate, this
-  // batch only) instead of handing an error back -- unless SCANN_STRICT_RANGE=1 asks for the error.
-  bool rerun = false;
-  if (const int r = rerun_if_out_of_range(h, db, s, &rerun)) return r;
-  if (rerun) {
-    const int rf3 = fetch_results(h, db, s, y_out, ga_attn_out);
-    if (rf3) return rf3;
-  }
-  db->idle = true;
-  db->fwd_pending = false;
-  return check_range(h, "scann_batch_download", db->last_slot);
+  return download(h, db, y_out, ga_attn_out);
 }
 
 int scann_device_memory(scann_handle_t* h, int64_t* free_bytes, int64_t* total_bytes) {

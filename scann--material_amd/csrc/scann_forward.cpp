@@ -20,12 +20,12 @@ int ensure_debug(scann_handle* h, scann_dbatch* db) {
   return SCANN_OK;
 }
 
-// The inference outputs the handle selected (scann_set_outputs) for this forward of `db` (a training forward: none): the batch's output
-// block is sized for them -- allocated by the first forward that needs it, grown when a selection or batch needs more -- and db->out_*
-// record what this forward writes.  With nothing selected nothing happens.
-int ensure_outputs(scann_handle* h, scann_dbatch* db, bool infer) {
-  db->out_layers = infer ? h->out_layers : 0;
-  db->out_flags = infer ? h->out_flags : 0;
+// The inference outputs this forward of `db` is to write (o.out_*; a training forward: none): the batch's output block is sized for them
+// -- allocated by the first forward that needs it, grown when a selection or batch needs more -- and db->out_* record what this forward
+// writes.  With nothing selected nothing happens.
+int ensure_outputs(scann_handle* h, scann_dbatch* db, const FwdOpts& o) {
+  db->out_layers = o.train ? 0 : o.out_layers;
+  db->out_flags = o.train ? 0 : o.out_flags;
   db->out_attn = db->out_z = db->out_bf = nullptr;
   if (!db->out_layers && !db->out_flags) return SCANN_OK;
   const scann_config_t& c = h->cfg;
@@ -63,7 +63,7 @@ float* attn_out_of(const scann_handle* h, const scann_dbatch* db, int l) {
 int run_forward_generic(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o, const scann_handle* wh, const FwdBufs& buf) {
   const scann_config_t& c = h->cfg;
   GenKeep* const kp = o.train ? o.train->gen : nullptr;
-  const bool outs = o.outputs && !kp;  // (the selected outputs of an inference forward)
+  const bool outs = o.out_flags != FWD_OUT_UNTOUCHED && !kp;  // (the selected outputs of an inference forward)
   const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
   const int d = c.local_dim, dg = c.global_dim, dout = c.dense_out, H = c.num_head, emb = c.embedding_dim;
   const int cin = emb + (c.use_ring ? 10 : 0);
@@ -255,9 +255,23 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
     db->fwd_pending = true;
   }
   if (!W->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
+  const scann_config_t& c = h->cfg;
+  const int L = c.n_attention;
+  const bool outs = o.out_flags != FWD_OUT_UNTOUCHED;  // this forward writes the batch's output block and db->out_* record what
+  // exact: the forward's range guard fired (an operand outside the split-fp16 range): the same launches on the EX instantiations of
+  // the atom / edge kernels -- exact-fp32 projections -- with the plain first layer (basis_kernel, no per-species tables)
+  // inference: the first layer's edge kernel computes its geometry rows from (dist, weight) itself -- geom0 is never written by a
+  // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
+  // Monte Carlo dropout (scann_predict_mc, never exact): the sample's masks at the training forward's Dropout sites, on the MC instantiations
+  // (the piece-major family: the fused first layer whatever SCANN_FUSE_BASIS says)
+  const bool fuse_basis = !exact && (h->fuse_basis || mc) && c.g_update && L > 0 && !debug && !tr && db->n_edge > 0;
+  // the attention-weight stores exist in the piece-major g_update kernels (and the row-major base / exact ones) only.  Refused before the
+  // output block is touched: db->out_* go on describing what it holds
+  if (outs && !tr && o.out_layers && !h->generic && c.g_update && !exact && !fuse_basis && db->n_edge > 0)
+    return fail(h, SCANN_ERR_UNSUPPORTED, "forward: local-attention outputs need the fused first layer (not with scann_set_debug or SCANN_FUSE_BASIS=0)");
   HIPCHK(h, wait_upload(db, s));  // the inputs' copy (scann_batch_upload returned when it was enqueued)
-  if (o.outputs)
-    if (const int r = ensure_outputs(h, db, !tr)) return r;
+  if (outs)
+    if (const int r = ensure_outputs(h, db, o)) return r;
   const FwdBufs b = o.bufs ? *o.bufs : FwdBufs(db);
   if (h->generic) {
     if (tm) { tm->mark(-1); }
@@ -265,8 +279,6 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
     if (tm) tm->mark(3);
     return r;
   }
-  const scann_config_t& c = h->cfg;
-  const int L = c.n_attention;
   if (debug) {
     const int r = ensure_debug(h, db);
     if (r) return r;
@@ -279,18 +291,6 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
   auto g_of = [&](int l) { return debug && c.g_update ? db->dbg_g + (size_t)l * nE_ : b.geom; };
   int32_t* const rflag = h->range_flag ? h->range_flag + (o.slot >= 0 ? o.slot : db->last_slot) : nullptr;  // this stream's range-guard word
   if (tm) tm->mark(-1);
-  // exact: the forward's range guard fired (an operand outside the split-fp16 range): the same launches on the EX instantiations of
-  // the atom / edge kernels -- exact-fp32 projections -- with the plain first layer (basis_kernel, no per-species tables)
-  // inference: the first layer's edge kernel computes its geometry rows from (dist, weight) itself -- geom0 is never written by a
-  // basis launch and read back (282 MB of the 16-batch forward's traffic and one launch)
-  // Monte Carlo dropout (scann_predict_mc, never exact): the sample's masks at the training forward's Dropout sites, on the MC instantiations
-  // (the piece-major family: the fused first layer whatever SCANN_FUSE_BASIS says)
-  const bool fuse_basis = !exact && (h->fuse_basis || mc) && c.g_update && L > 0 && !debug && !tr && db->n_edge > 0;
-  // the attention-weight stores exist in the piece-major g_update kernels (and the row-major base / exact ones) only
-  if (o.outputs && db->out_layers && c.g_update && !exact && !fuse_basis && db->n_edge > 0) {
-    db->out_layers = db->out_flags = 0;
-    return fail(h, SCANN_ERR_UNSUPPORTED, "forward: local-attention outputs need the fused first layer (not with scann_set_debug or SCANN_FUSE_BASIS=0)");
-  }
   if (!fuse_basis) {
     if (c.g_update) launch_basis(W->basis, db->dist, db->weight, db->n_edge, g_of(0), s);
     else launch_basis_raw(W->cd, db->dist, db->n_edge, b.gd, s);  // (the Gaussians of the distances: model independent, one launch per set run)
@@ -376,7 +376,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
       a.WAh = W->head.Wah; a.bA = W->head.ba; a.WCh = W->head.Wgqh; a.bC = W->head.bgq; a.WDh = W->head.Wgkh; a.bD = W->head.bgk;
       a.oB = b.gk; a.oC = b.gq;
       if (keep_bwd && db->keep_preA) { a.keep_preA = db->keep_preA; a.keep_z = db->keep_z; }
-      a.out_z = o.outputs ? db->out_z : nullptr;
+      a.out_z = outs ? db->out_z : nullptr;
     }
 #ifdef SCANN_STAMPS
     if (getenv("SCANN_STAMP_ATOM") && l >= 1 && l < L) {  // phase clocks of atom_kernel<true, 0> (the last such launch wins)
@@ -442,7 +442,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
     }
     ea.tile_part = db->tile_part; ea.part_buf = b.part_buf;
     ea.xcd_remap = h->xcd_remap;
-    ea.attn_out = o.outputs ? attn_out_of(h, db, l) : nullptr;
+    ea.attn_out = outs ? attn_out_of(h, db, l) : nullptr;
     if (tr && tr->attn_p > 0.f) {  // validation passes run with scann_set_attention_dropout(h, 0): trainer.fit
       ea.attn_drop_p = tr->attn_p;
       ea.attn_drop_seed = tr->seed;
@@ -479,7 +479,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
   r.mol_offset = db->mol_offset; r.n_struct = db->n_struct; r.max_atoms = db->max_atoms;
   r.gq = b.gq; r.gk = b.gk; r.use_ga_norm = c.use_ga_norm; r.relu_out = W->cfg.relu_out;
   for (int m = 1; m < nm; ++m) r.relu_out |= o.members[m]->cfg.relu_out << m;  // (a set launch: bit m is member m's mrelu)
-  r.p = W->head; r.ga_attn = b.ga; r.y = b.y; r.bf_out = o.outputs ? db->out_bf : nullptr;
+  r.p = W->head; r.ga_attn = b.ga; r.y = b.y; r.bf_out = outs ? db->out_bf : nullptr;
   r.n_member = nm; r.m_w = wst; r.m_a = ast; r.m_g = o.m_g; r.m_y = o.m_y;
   launch_readout(r, s);
   if (tm) tm->mark(3);
@@ -496,7 +496,7 @@ int scann_forward_resident(scann_handle_t* h, scann_dbatch_t* db, int stream_slo
   HIPCHK(h, hipSetDevice(h->device));
   const int slot = ((stream_slot % h->nstream) + h->nstream) % h->nstream;
   db->last_slot = slot;
-  return run_forward(h, db, h->streams[slot]);
+  return run_forward(h, db, h->streams[slot], selected_opts(h));
 }
 
 int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t* prof) {
@@ -505,7 +505,7 @@ int scann_forward_profile(scann_handle_t* h, scann_dbatch_t* db, scann_profile_t
   memset(prof, 0, sizeof(*prof));
   Timer tm{h->streams[0], true, {}, {}};
   db->last_slot = 0;
-  FwdOpts o;
+  FwdOpts o = selected_opts(h);
   o.tm = &tm;
   const int r = run_forward(h, db, h->streams[0], o);
   if (r) return r;
@@ -691,7 +691,7 @@ int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, u
   FwdOpts o;
   o.mc = &mc;
   o.keep_layers = 0;
-  o.outputs = false;
+  o.out_flags = FWD_OUT_UNTOUCHED;
   o.bufs = &bufs;
   int r = SCANN_OK;
   for (int t = 0; t < T && r == SCANN_OK; ++t) {

@@ -1,8 +1,8 @@
 // Latent-space index (include/scann_hip.h: scann_index_*): the rows of bf_property / after_Lc kept on the device in chunks that never
 // move, the exact k-nearest-neighbour search over them (scann_knn.hip) and the host twin of the kernel's distance chain.  Every call is
-// synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The forwards of
-// scann_index_add_batch / scann_index_query_batch are the public ones with the level's output flag added for that one forward, as
-// scann_attention_rollout adds its attention maps: y, the scores, the range guard and the exact re-run behave exactly as they do there.
+// synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The forward of
+// scann_index_add_batch / scann_index_query_batch is forward_and_download (scann_batch.cpp) with the level's output flag in that one
+// forward's options: y, the scores, the range guard and the exact re-run behave as in scann_batch_download, and the handle is not written.
 #include "scann_knn.h"
 #include "scann_runtime.h"
 #include "scann_select.h"
@@ -166,22 +166,47 @@ int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqi
   return SCANN_OK;
 }
 
-// one inference forward of the batch with the level's output added to the handle's selection, downloaded as scann_batch_download does;
-// the handle's selection is put back whatever happens.  Afterwards db->out_bf / db->out_z hold the level's rows.
-int forward_level(scann_handle* h, scann_dbatch* db, int32_t level, std::vector<float>& y, std::vector<float>& ga) {
-  y.assign((size_t)std::max(db->n_struct, 1), 0.f);
-  ga.assign((size_t)std::max(db->n_atom, 1), 0.f);
-  const int32_t selected = h->out_flags;
-  h->out_flags |= level;
-  int r = scann_forward_resident(h, db, db->last_slot);
-  if (!r) r = scann_batch_download(h, db, y.data(), ga.data());
-  h->out_flags = selected;
+// nq queries of the index's width at q -- host rows (kind = hipMemcpyHostToDevice) or device rows -- and their ids (host [nq], or null) staged
+// in one block of the cache and searched: the rows padded to the stride, then the ids.  Device rows whose width is the stride are searched
+// where they lie.
+int search_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int64_t* qid, int64_t nq, int k, hipStream_t s,
+                  float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos) {
+  const bool pad = ix->stride != ix->dim, copy = pad || kind == hipMemcpyHostToDevice;
+  const size_t bQ = copy ? align_up((size_t)nq * ix->stride * 4) : 0, bI = align_up((size_t)nq * 8);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bQ + bI));
+  hipError_t e = pad ? hipMemsetAsync(ws, 0, bQ, s) : hipSuccess;
+  if (e == hipSuccess && copy) e = hipMemcpy2DAsync(ws, (size_t)ix->stride * 4, q, (size_t)ix->dim * 4, (size_t)ix->dim * 4, (size_t)nq, kind, s);
+  if (e == hipSuccess && qid) e = hipMemcpyAsync(ws + bQ, qid, (size_t)nq * 8, hipMemcpyHostToDevice, s);
+  int r = SCANN_OK;
+  if (e == hipSuccess)
+    r = search(h, ix, copy ? reinterpret_cast<const float*>(ws) : q, qid ? reinterpret_cast<const int64_t*>(ws + bQ) : nullptr, nq, k, s, dist2, ids, atoms, pos);
+  else
+    (void)hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
   return r;
 }
 
-int read_mol(scann_handle* h, scann_dbatch* db, std::vector<int32_t>& mol) {
-  mol.assign((size_t)db->n_struct + 1, 0);
-  if (db->n_struct > 0) HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
+// The rows a batch has at a level -- one per structure, or (atom) one per atom in packed order -- named: id_v = the structure's id
+// (ids[b]; ids null: first + b), at_v (if asked for) = the atom's index in its structure, -1 for a structure row
+int expand_ids(scann_handle* h, const scann_dbatch* db, bool atom, const int64_t* ids, int64_t first, std::vector<int64_t>& id_v,
+               std::vector<int32_t>* at_v) {
+  const int B = db->n_struct;
+  id_v.assign((size_t)(atom ? db->n_atom : B), 0);
+  if (at_v) at_v->assign(id_v.size(), -1);
+  std::vector<int32_t> mol;
+  if (atom)
+    if (const int r = read_mol_offset(h, db, mol)) return r;
+  for (int b = 0; b < B; ++b) {
+    const int64_t id = ids ? ids[b] : first + b;
+    if (!atom) id_v[(size_t)b] = id;
+    else
+      for (int i = mol[b]; i < mol[b + 1]; ++i) {
+        id_v[(size_t)i] = id;
+        if (at_v) (*at_v)[(size_t)i] = i - mol[b];
+      }
+  }
   return SCANN_OK;
 }
 
@@ -275,21 +300,7 @@ int scann_index_query(scann_handle_t* h, scann_index_t* ix, const float* q, int6
   if (nq > (int64_t)0x7fffffff / SCANN_KNN_MAX_K) return fail(h, SCANN_ERR_INVALID, "scann_index_query: too many queries in one call");
   if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query: dist2 is null");
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->streams[0];
-  const size_t bQ = align_up((size_t)nq * ix->stride * 4), bI = align_up((size_t)nq * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bQ + bI));
-  hipError_t e = ix->stride != ix->dim ? hipMemsetAsync(ws, 0, bQ, s) : hipSuccess;
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)ix->stride * 4, q, (size_t)ix->dim * 4, (size_t)ix->dim * 4, (size_t)nq, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && query_ids) e = hipMemcpyAsync(ws + bQ, query_ids, (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  int r = SCANN_OK;
-  if (e == hipSuccess)
-    r = search(h, ix, reinterpret_cast<const float*>(ws), query_ids ? reinterpret_cast<const int64_t*>(ws + bQ) : nullptr, nq, k, s, dist2, ids, atoms, pos);
-  else
-    (void)hipStreamSynchronize(s);
-  cached_free(ws);
-  HIPCHK(h, e);
-  return r;
+  return search_staged(h, ix, q, hipMemcpyHostToDevice, query_ids, nq, k, h->streams[0], dist2, ids, atoms, pos);
 }
 
 int scann_index_add_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* db, int32_t level, const int64_t* ids) {
@@ -298,26 +309,13 @@ int scann_index_add_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* 
   if (const int r = check_level(h, ix, level, "scann_index_add_batch")) return r;
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_add_batch: weights not loaded");
   HIPCHK(h, hipSetDevice(h->device));
-  std::vector<float> y, ga;
-  if (const int r = forward_level(h, db, level, y, ga)) return r;
-  const int B = db->n_struct, A = db->n_atom;
+  if (const int r = forward_and_download(h, db, 0, level, nullptr, nullptr)) return r;
   const bool atom = level == SCANN_OUT_AFTER_LC;
-  const int64_t n = atom ? A : B;
-  std::vector<int64_t> id_v((size_t)n);
-  std::vector<int32_t> at_v((size_t)n, -1);
-  if (atom) {
-    std::vector<int32_t> mol;
-    if (const int r = read_mol(h, db, mol)) return r;
-    for (int b = 0; b < B; ++b)
-      for (int i = mol[b]; i < mol[b + 1]; ++i) {
-        id_v[(size_t)i] = ids ? ids[b] : b;
-        at_v[(size_t)i] = i - mol[b];
-      }
-  } else {
-    for (int b = 0; b < B; ++b) id_v[(size_t)b] = ids ? ids[b] : ix->n + b;
-  }
-  return append_rows(h, ix, atom ? db->out_z : db->out_bf, (size_t)ix->dim * 4, hipMemcpyDeviceToDevice, n, id_v.data(), at_v.data(),
-                     h->streams[db->last_slot]);
+  std::vector<int64_t> id_v;
+  std::vector<int32_t> at_v;
+  if (const int r = expand_ids(h, db, atom, ids, atom ? 0 : ix->n, id_v, &at_v)) return r;  // (ids null: the structure's place in the batch / the row's position)
+  return append_rows(h, ix, atom ? db->out_z : db->out_bf, (size_t)ix->dim * 4, hipMemcpyDeviceToDevice, (int64_t)id_v.size(), id_v.data(),
+                     at_v.data(), h->streams[db->last_slot]);
 }
 
 int scann_index_query_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, int32_t k, float* y,
@@ -333,45 +331,13 @@ int scann_index_query_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t
   if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: dist2 is null");
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_query_batch: weights not loaded");
   HIPCHK(h, hipSetDevice(h->device));
-  std::vector<float> y_h, ga_h;
-  if (const int r = forward_level(h, db, level, y_h, ga_h)) return r;
-  hipStream_t s = h->streams[db->last_slot];
+  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
   std::vector<int64_t> qid;
-  if (query_ids) {
-    qid.assign(query_ids, query_ids + B);
-    if (atom) {
-      std::vector<int32_t> mol;
-      if (const int r = read_mol(h, db, mol)) return r;
-      qid.assign((size_t)A, 0);
-      for (int b = 0; b < B; ++b)
-        for (int i = mol[b]; i < mol[b + 1]; ++i) qid[(size_t)i] = query_ids[b];
-    }
-  }
-  // the level's rows are the queries where the forward left them; a width that is no multiple of 4 is copied to the padded stride first
-  const float* src = atom ? db->out_z : db->out_bf;
-  const bool pad = ix->stride != ix->dim;
-  const size_t bQ = pad ? align_up((size_t)nq * ix->stride * 4) : 0, bI = align_up((size_t)nq * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bQ + bI));
-  hipError_t e = hipSuccess;
-  if (pad) {
-    e = hipMemsetAsync(ws, 0, bQ, s);
-    if (e == hipSuccess)
-      e = hipMemcpy2DAsync(ws, (size_t)ix->stride * 4, src, (size_t)ix->dim * 4, (size_t)ix->dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
-  }
-  if (e == hipSuccess && query_ids) e = hipMemcpyAsync(ws + bQ, qid.data(), (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  int r = SCANN_OK;
-  if (e == hipSuccess)
-    r = search(h, ix, pad ? reinterpret_cast<const float*>(ws) : src, query_ids ? reinterpret_cast<const int64_t*>(ws + bQ) : nullptr, nq, k, s, dist2, ids,
-               atoms, pos);
-  else
-    (void)hipStreamSynchronize(s);
-  cached_free(ws);
-  HIPCHK(h, e);
-  if (r) return r;
-  if (y && B > 0) memcpy(y, y_h.data(), (size_t)B * 4);
-  if (ga && A > 0) memcpy(ga, ga_h.data(), (size_t)A * 4);
-  return SCANN_OK;
+  if (query_ids)
+    if (const int r = expand_ids(h, db, atom, query_ids, 0, qid, nullptr)) return r;
+  // the level's rows are the queries where the forward left them
+  return search_staged(h, ix, atom ? db->out_z : db->out_bf, hipMemcpyDeviceToDevice, query_ids ? qid.data() : nullptr, nq, k, h->streams[db->last_slot],
+                       dist2, ids, atoms, pos);
 }
 
 int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, float stop_dist2, int32_t* pos,

@@ -112,7 +112,7 @@ int forward_all(scann_handle* h, ModelSet* ms, scann_dbatch* db, hipStream_t s, 
   FwdOpts o;
   o.exact = exact;
   o.keep_layers = 0;
-  o.outputs = false;
+  o.out_flags = FWD_OUT_UNTOUCHED;
   o.slot = slot;
   o.of_set = true;
   const bool shared = !exact && !h->generic && !h->force_exact && c.n_attention > 0 && db->n_edge > 0 && (!c.g_update || h->fuse_basis);

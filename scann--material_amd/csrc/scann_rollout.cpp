@@ -1,21 +1,10 @@
-// scann_attention_rollout (include/scann_hip.h): one forward of the resident batch with the first `depth` attention maps added to the
-// handle's selected outputs, then the maps composed per structure where the forward left them (scann_rollout.hip).  The forward and the
-// download are the public ones, so y, the GlobalAttention scores, the range guard and the exact re-run behave exactly as they do there.
+// scann_attention_rollout (include/scann_hip.h): one forward of the resident batch that writes the first `depth` attention maps besides
+// the handle's selected outputs -- its own options say so, the handle is not written -- then the maps composed per structure where the
+// forward left them (scann_rollout.hip).  The forward and its download are forward_and_download (scann_batch.cpp): y, the GlobalAttention
+// scores, the range guard and the exact re-run behave as in scann_batch_download.
 #include "scann_runtime.h"
 
 using namespace scann;
-
-namespace {
-
-// atoms per structure of a resident batch, from its device copy of mol_offset (the host keeps none)
-int read_mol_offset(scann_handle* h, scann_dbatch* db, std::vector<int32_t>& mol) {
-  mol.assign((size_t)db->n_struct + 1, 0);
-  if (db->upload_ev && !db->upload_done) HIPCHK(h, hipEventSynchronize(db->upload_ev));
-  if (db->n_struct > 0) HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
-  return SCANN_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -23,7 +12,7 @@ int64_t scann_rollout_floats(scann_handle_t* h, const scann_dbatch_t* db) {
   if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_rollout_floats: null argument");
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<int32_t> mol;
-  if (const int r = read_mol_offset(h, const_cast<scann_dbatch_t*>(db), mol)) return r;
+  if (const int r = read_mol_offset(h, db, mol)) return r;
   int64_t n = 0;
   for (int s = 0; s < db->n_struct; ++s) n += (int64_t)(mol[s + 1] - mol[s]) * (mol[s + 1] - mol[s]);
   return n;
@@ -48,14 +37,9 @@ int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residua
     return fail(h, SCANN_ERR_UNSUPPORTED, "scann_attention_rollout: a structure of " + std::to_string(db->max_atoms) + " atoms exceeds the limit of " +
                                               std::to_string(SCANN_ROLLOUT_MAX_ATOMS) + " atoms per structure (two 16-column slabs of one structure in 160 KiB of LDS)");
   const int A = db->n_atom, B = db->n_struct, E = db->n_edge;
-  std::vector<float> y_h((size_t)std::max(B, 1)), ga_h((size_t)std::max(A, 1));
   // this one forward also writes layers 0 .. depth-1: the lowest selected layers, so they lie first in the batch's output block.  The
-  // re-run of a forward whose range guard fired happens inside the download, under the same selection
-  const uint64_t selected = h->out_layers;
-  h->out_layers |= (uint64_t(1) << depth) - 1;
-  int r = scann_forward_resident(h, db, db->last_slot);
-  if (!r) r = scann_batch_download(h, db, y_h.data(), ga_h.data());
-  h->out_layers = selected;
+  // re-run of a forward whose range guard fired happens inside the download, under the selection the batch recorded
+  int r = forward_and_download(h, db, (uint64_t(1) << depth) - 1, 0, y, ga);
   if (r) return r;
   hipStream_t s = h->streams[db->last_slot];
   std::vector<int64_t> off;
@@ -91,8 +75,6 @@ int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residua
   if (e == hipSuccess && total > 0) e = hipMemcpy(rollout, a.rollout, (size_t)total * 4, hipMemcpyDeviceToHost);
   cached_free(ws);
   HIPCHK(h, e);
-  if (y && B > 0) memcpy(y, y_h.data(), (size_t)B * 4);
-  if (ga && A > 0) memcpy(ga, ga_h.data(), (size_t)A * 4);
   return SCANN_OK;
 }
 

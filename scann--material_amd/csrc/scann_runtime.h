@@ -112,7 +112,8 @@ struct scann_handle {
   bool loaded = false;
   bool debug = false;
   // scann_set_outputs: what later inference forwards also write -- bit k: local_attention_k's weights; out_flags: SCANN_OUT_AFTER_LC |
-  // SCANN_OUT_BF_PROPERTY.  Zero: the forward launches exactly the plain schedule
+  // SCANN_OUT_BF_PROPERTY.  Zero: the forward launches exactly the plain schedule.  Written there and read by selected_opts only: a
+  // forward runs under the selection in its FwdOpts
   uint64_t out_layers = 0;
   int32_t out_flags = 0;
   int tile_atoms = TQ;     // atoms per edge tile the tile builder allows (edge_kernel's query-row buffer)
@@ -318,7 +319,10 @@ struct FwdTrain {
   GenKeep* gen;             // generic widths: where every intermediate is kept
 };
 
-// The forward run_forward is to enqueue.  The defaults mean: the plain inference forward of the batch on the handle's own weights.
+constexpr int32_t FWD_OUT_UNTOUCHED = -1;  // FwdOpts::out_flags: the forward writes no outputs and leaves the batch's output block and db->out_* alone
+
+// The forward run_forward is to enqueue: everything that distinguishes one forward from another is here, nothing is looked up in the
+// handle or the batch at launch time.  The defaults mean: the plain inference forward of the batch on the handle's own weights, no outputs.
 struct FwdOpts {
   bool exact = false;               // on the exact-fp32 instantiations (forced by SCANN_EXACT=1 and by weights the split-fp16 images cannot hold)
   Timer* tm = nullptr;              // scann_forward_profile
@@ -326,8 +330,11 @@ struct FwdOpts {
   const McState* mc = nullptr;      // ... a Monte Carlo dropout sample (an inference forward under that sample's masks)
   int keep_layers = -1;             // every layer's centres / context / geometry into the debug buffers (scann_debug_read); -1: the handle's
                                     // scann_set_debug switch
-  bool outputs = true;              // an inference forward writes the outputs the handle selected (scann_set_outputs) and db->out_* record
-                                    // them (a training forward: that it wrote none); false: no outputs, db->out_* untouched
+  // the outputs this forward also writes into the batch's output block -- bit k: local_attention_k's weights; out_flags: SCANN_OUT_AFTER_LC
+  // | SCANN_OUT_BF_PROPERTY -- and db->out_* record (a training forward: none, whatever is asked for).  out_flags = FWD_OUT_UNTOUCHED: a
+  // forward beside the batch's own (a Monte Carlo sample, the members of a model set), which leaves the block and db->out_* as they are
+  uint64_t out_layers = 0;
+  int32_t out_flags = 0;
   const FwdBufs* bufs = nullptr;    // where activations and results go; null: the batch's own workspace
   int slot = -1;                    // stream slot whose range-guard word the kernels write; -1: db->last_slot
   // whose weight images (layers, head, basis, lut, sp_*, cd, embed, g_*, weights_exact, cfg.relu_out); null: the handle's own.  Streams,
@@ -342,14 +349,28 @@ struct FwdOpts {
   bool of_set = false;
 };
 
+// The options of a public inference forward: the outputs scann_set_outputs selected, plus `layers` / `flags` for this one forward.  The
+// one place that reads the handle's selection
+inline FwdOpts selected_opts(const scann_handle* h, uint64_t layers = 0, int32_t flags = 0) {
+  FwdOpts o;
+  o.out_layers = h->out_layers | layers;
+  o.out_flags = h->out_flags | flags;
+  return o;
+}
+
 // scann_forward.cpp: the forward graph as a launch schedule on stream s
-int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o = FwdOpts());
+int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts& o);
 
 // scann_batch.cpp
 int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who);
-// after the batch's stream has been synchronised: the forward's range guard fired -> run it again on the exact-fp32 instantiations
-// (*rerun = true) unless SCANN_STRICT_RANGE asks for the error (check_range reports it)
+// after the batch's stream has been synchronised: the forward's range guard fired -> run it again on the exact-fp32 instantiations,
+// writing the outputs the batch recorded for it (*rerun = true), unless SCANN_STRICT_RANGE asks for the error (check_range reports it)
 int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, bool* rerun);
+// One inference forward of a resident batch on its last_slot stream, writing `layers` / `flags` besides the handle's selected outputs,
+// and its results fetched as scann_batch_download fetches them (pack flag, range guard, exact re-run, db->idle); y / ga: host, or null
+int forward_and_download(scann_handle_t* h, scann_dbatch_t* db, uint64_t layers, int32_t flags, float* y, float* ga);
+// atoms of a resident batch by structure: its device copy of mol_offset [n_struct + 1] (the host keeps none), once the upload has ended
+int read_mol_offset(scann_handle_t* h, const scann_dbatch_t* db, std::vector<int32_t>& mol);
 void free_batch(scann_dbatch* db);  // everything the batch holds, and the batch; no work on it may still be running
 
 }  // namespace scann

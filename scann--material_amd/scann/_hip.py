@@ -367,11 +367,7 @@ class PackedBatch:
     def repad_ga(self, ga_packed):
         """Packed GlobalAttention scores -> the reference's [B, M, 1] (padded atoms score exactly 0:
         softmax of -1e9, attention.py:299-302)."""
-        if self.pad_shape is None:
-            return ga_packed
-        out = np.zeros(self.pad_shape + (1,), dtype=np.float32)
-        out[self.atom_mask, 0] = ga_packed
-        return out
+        return ga_packed if self.pad_shape is None else repad_atoms(ga_packed, self.atom_mask)[..., None]
 
 
 def concat_packed(parts):
@@ -514,11 +510,13 @@ def repad_edges(x, atom_mask, neighbor_mask):
     return out
 
 
-def repad_atoms(x, atom_mask):
-    """Packed per-atom rows [n_atom, F] -> [B, M, F] with zero rows for padded atoms."""
+def repad_atoms(x, atom_mask, fill=0):
+    """Packed per-atom values [n_atom] or rows [n_atom, F] -> [B, M] / [B, M, F] with ``fill`` (default: zero) at padded atoms.
+    THE packed-to-padded routine of per-atom results; integers keep their dtype, everything else comes back as float32."""
     amask = np.asarray(atom_mask)
     amask = amask.reshape(amask.shape[:2]) != 0
-    out = np.zeros(amask.shape + (np.shape(x)[1],), dtype=np.float32)
+    x = np.asarray(x)
+    out = np.full(amask.shape + x.shape[1:], fill, dtype=x.dtype if x.dtype.kind in "iu" else np.float32)
     out[amask] = x
     return out
 
@@ -566,9 +564,7 @@ class PaddedInfo:
         self.pad_shape = atom_mask.shape
 
     def repad_ga(self, ga_packed):
-        out = np.zeros(self.pad_shape + (1,), dtype=np.float32)
-        out[self.atom_mask, 0] = ga_packed
-        return out
+        return repad_atoms(ga_packed, self.atom_mask)[..., None]
 
 
 class ResidentBatch:

@@ -24,10 +24,12 @@ def level_dim(config, level):
     return int(config["model"]["dense_out" if level == "structure" else "global_dim"])
 
 
-def batch_jobs(model, data, bs):
+def batch_jobs(model, data, bs, upload_padded=None):
     """(upload, n_struct) per chunk of ``data``: a padded dict or a ``PackedBatch`` cut ``bs`` structures at a time, or a dataset -- any
-    sequence of ``(PackedBatch | padded dict, target)`` -- batch by batch."""
+    sequence of ``(PackedBatch | padded dict, target)`` -- batch by batch.  THE chunker of every batched call (HipModel._run_chunks).
+    ``upload_padded``: what uploads a padded chunk (default: the model's own choice of packer, HipModel._upload_padded)."""
     eng = model.engine
+    upload_padded = upload_padded or model._upload_padded
     if isinstance(data, _hip.PackedBatch):
         B = data.n_struct
         for i in range(0, B, bs):
@@ -36,14 +38,14 @@ def batch_jobs(model, data, bs):
         B = int(np.shape(data["neighbors"])[0])
         sliced = {k: np.asarray(v) for k, v in data.items() if k in model.input_names}
         for i in range(0, B, bs):
-            yield functools.partial(model._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), min(i + bs, B) - i
+            yield functools.partial(upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), min(i + bs, B) - i
     else:
         for i in range(len(data)):
             item, _ = data[i]
             if isinstance(item, _hip.PackedBatch):
                 yield functools.partial(eng.upload, item), item.n_struct
             else:
-                yield functools.partial(model._upload_padded, item), int(np.shape(item["neighbors"])[0])
+                yield functools.partial(upload_padded, item), int(np.shape(item["neighbors"])[0])
 
 
 def count_structures(data):
@@ -83,6 +85,12 @@ class LatentIndex:
         self._ix = model.engine.index_create(self.dim)
         self._n_struct = 0  # structures given so far: where the default ids of the next add start
 
+    def check_model(self, model):
+        """ValueError unless the index lives on ``model``'s GPU handle and holds rows of its level's width"""
+        if self.model is not model or level_dim(model.config, self.level) != self.dim:
+            raise ValueError("the index was built for another model: it lives on that model's GPU handle (%s level, %d columns)" % (
+                self.level, self.dim))
+
     def __len__(self):
         return len(self._ix)
 
@@ -90,9 +98,6 @@ class LatentIndex:
         """Append the rows of ``data`` -- a padded dict, a ``PackedBatch`` or a dataset as ``predict_dataset`` takes it -- computed by one
         forward per batch and copied device to device.  ``ids``: one per structure (default: continuing from the structures the index
         was given so far, i.e. 0 .. n-1 for a fresh one).  Returns self."""
-        bs = int(self.model.config["hyper"]["batch_size"] if batch_size is None else batch_size)
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
         n = count_structures(data)
         if ids is None:
             ids = np.arange(n, dtype=np.int64) + self._n_struct
@@ -100,14 +105,7 @@ class LatentIndex:
         if ids.shape[0] != n:
             raise ValueError("%d structures need %d ids, got %d" % (n, n, ids.shape[0]))
         eng, lvl = self.model.engine, _hip.KNN_LEVELS[self.level]
-        state = {"at": 0}
-
-        def finish(rb, cnt):
-            eng.index_add_batch(self._ix, rb, lvl, ids[state["at"]:state["at"] + cnt])
-            state["at"] += cnt
-
-        # (scann_index_add_batch runs its own forward and is synchronous: the pipeline still uploads batch k + 1 before batch k is computed)
-        self.model._pipeline(batch_jobs(self.model, data, bs), finish, launch=lambda rb, slot: None)
+        self.model._run_chunks(data, batch_size, lambda rb, s0, s1: eng.index_add_batch(self._ix, rb, lvl, ids[s0:s1]))
         self._n_struct += n
         return self
 

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
+from .latent_index import LatentIndex, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -212,38 +213,16 @@ class HipModel:
                 raise ValueError("ring_aromatic: the model has no ring input (use_ring is off)")
             if n == "atomic" and m["feature"] != "cgcnn":
                 raise ValueError("atomic: gradients exist for the cgcnn features only (the atomic numbers are integers)")
-        bs = int(batch_size or self.config["hyper"]["batch_size"])
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
         flags = dict(distance="neighbor_distance" in wrt, weight="neighbor_weight" in wrt, ring="ring_aromatic" in wrt,
                      cgcnn="atomic" in wrt)
         eng = self.engine
-        parts = []
-        if isinstance(inputs, _hip.PackedBatch):
-            for s0 in range(0, inputs.n_struct, bs):
-                rb = eng.upload(_hip.slice_packed(inputs, s0, min(s0 + bs, inputs.n_struct)))
-                try:
-                    parts.append(eng.input_grads(rb, **flags))
-                finally:
-                    rb.free()
-        else:
-            B = int(np.shape(inputs["neighbors"])[0])
-            for s0 in range(0, B, bs):
-                sl = {k: np.asarray(v)[s0:s0 + bs] for k, v in inputs.items() if k in self.input_names}
-                rb = eng.upload(_hip.pack_inputs(sl))
-                try:
-                    g = eng.input_grads(rb, **flags)
-                finally:
-                    rb.free()
-                amask, nmask = sl["atom_mask"], sl["neighbor_mask"]
-                for n in ("neighbor_distance", "neighbor_weight"):
-                    if n in g:
-                        g[n] = _hip.repad_edges(g[n], amask, nmask)
-                for n in ("ring_aromatic", "atomic"):
-                    if n in g:
-                        g[n] = _hip.repad_atoms(g[n], amask)
-                parts.append(g)
+        # (batch_size 0 has always meant the default here; padded chunks are packed on the host, whose packer names a bad input at once)
+        parts = self._run_chunks(inputs, batch_size or None, lambda rb, s0, s1: eng.input_grads(rb, **flags), host_pack=True)
         out = {n: np.concatenate([p[n] for p in parts]) for n in wrt}
+        if not isinstance(inputs, _hip.PackedBatch):  # (chunks are consecutive structures: their packed results, concatenated, are the input's)
+            amask, nmask = inputs["atom_mask"], inputs["neighbor_mask"]
+            for n in wrt:
+                out[n] = _hip.repad_atoms(out[n], amask) if n in ("ring_aromatic", "atomic") else _hip.repad_edges(out[n], amask, nmask)
         out["predict_property"] = np.concatenate([p["y"] for p in parts]).reshape(-1, 1)
         return out
 
@@ -260,21 +239,13 @@ class HipModel:
         reference's 0 / 0 = NaN.  A bad mode or batch_size raises ValueError before anything is uploaded."""
         if mode not in _hip.ABLATE_MODES:
             raise ValueError("mode must be one of %s, got %r" % (", ".join(_hip.ABLATE_MODES), mode))
-        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
         eng = self.engine
         B = int(np.shape(inputs["neighbors"])[0])
         amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
-        parts = []
-        sliced = {k: np.asarray(v) for k, v in inputs.items() if k in self.input_names}
-        jobs = ((functools.partial(self._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), i) for i in range(0, B, bs))
-        # (scann_ablate_pooling runs its own forward and is synchronous: nothing to enqueue ahead; the pipeline still uploads chunk k + 1
-        #  before chunk k is computed and frees every batch on an error)
-        self._pipeline(jobs, lambda rb, tag: parts.append(eng.ablate_pooling(rb, mode)), launch=lambda rb, slot: None)
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.ablate_pooling(rb, mode))
         cat = {k: np.concatenate([p[k] for p in parts]) for k in ("y", "ga", "ablated", "order")}
         y = cat["y"].reshape(-1, 1)
-        out = {"y": y, "global_attention": _hip.repad_atoms(cat["ga"][:, None], amask), "ablated": _hip.repad_atoms(cat["ablated"][:, None], amask)}
+        out = {"y": y, "global_attention": _hip.repad_atoms(cat["ga"], amask)[..., None], "ablated": _hip.repad_atoms(cat["ablated"], amask)[..., None]}
         # rank -> padded position: the structure's e-th real atom sits at the e-th set position of its mask row
         order = np.full(amask.shape, -1, dtype=np.int32)
         rows, cols = np.nonzero(amask)
@@ -299,38 +270,25 @@ class HipModel:
         _hip.ROLLOUT_MAX_ATOMS atoms per structure.  Bad arguments raise ValueError before anything is uploaded."""
         m = self.config["model"]
         args = _hip.check_rollout_args(residual, head, depth, int(m["num_head"]), int(m["n_attention"]))
-        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
         eng = self.engine
-        is_packed = isinstance(inputs, _hip.PackedBatch)
-        if is_packed:
-            B = inputs.n_struct
-            jobs = ((functools.partial(eng.upload, _hip.slice_packed(inputs, i, min(i + bs, B))), i) for i in range(0, B, bs))
-        else:
-            B = int(np.shape(inputs["neighbors"])[0])
-            sliced = {k: np.asarray(v) for k, v in inputs.items() if k in self.input_names}
-            jobs = ((functools.partial(self._upload_padded, {k: v[i:i + bs] for k, v in sliced.items()}), i) for i in range(0, B, bs))
-        parts = []
-        # (scann_attention_rollout runs its own forward and is synchronous, as scann_ablate_pooling: see atom_contributions)
-        self._pipeline(jobs, lambda rb, tag: parts.append(eng.attention_rollout(rb, args[0], None if args[1] < 0 else args[1],
-                                                                                args[2] or None, matrix=bool(matrix))),
-                       launch=lambda rb, slot: None)
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.attention_rollout(
+            rb, args[0], None if args[1] < 0 else args[1], args[2] or None, matrix=bool(matrix)))
         keys = ("y", "ga", "attribution") + (("rollout",) if matrix else ())
         cat = {k: np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, np.float32) for k in keys}
         sq = np.concatenate([np.diff(p["rollout_offset"]) for p in parts]) if parts else np.zeros(0, np.int64)  # n^2 per structure
         offset = np.concatenate([[0], np.cumsum(sq)]).astype(np.int64)
         y = cat["y"].reshape(-1, 1)
-        if is_packed:
+        if isinstance(inputs, _hip.PackedBatch):
             out = {"predict_property": y, "global_attention": cat["ga"], "atom_attribution": cat["attribution"], "rollout_offset": offset}
             if matrix:
                 out["rollout"] = cat["rollout"]
             return out
-        amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
-        out = {"predict_property": y, "global_attention": _hip.repad_atoms(cat["ga"][:, None], amask),
-               "atom_attribution": _hip.repad_atoms(cat["attribution"][:, None], amask)}
+        amask = np.asarray(inputs["atom_mask"])
+        amask = amask.reshape(amask.shape[:2]) != 0
+        out = {"predict_property": y, "global_attention": _hip.repad_atoms(cat["ga"], amask)[..., None],
+               "atom_attribution": _hip.repad_atoms(cat["attribution"], amask)[..., None]}
         if matrix:
-            M = amask.shape[1]
+            B, M = amask.shape
             R = np.zeros((B, M, M), dtype=np.float32)
             for b in range(B):
                 pos = np.nonzero(amask[b])[0]
@@ -343,11 +301,8 @@ class HipModel:
         ``after_Lc`` row per real atom ("atom"), computed batch by batch and kept on the device.  ``data``: a padded dict, a
         ``PackedBatch`` or a dataset as ``predict_dataset`` takes it; ``ids``: one per structure (default 0 .. n-1 in input order).  A bad
         level or batch_size raises ValueError before anything is uploaded."""
-        from .latent_index import LatentIndex, level_dim
-
         level_dim(self.config, level)
-        if batch_size is not None and int(batch_size) < 1:
-            raise ValueError("batch_size must be >= 1")
+        self._batch_size(batch_size)
         return LatentIndex(self, level).add(data, ids=ids, batch_size=batch_size)
 
     def nearest(self, inputs, index, k=5, exclude_ids=None, batch_size=None):
@@ -360,17 +315,10 @@ class HipModel:
         0 / -1 at padded atoms; a ``PackedBatch`` gives packed [n_atom, k] arrays.  Raw y.  ``batch_size`` structures at a time (default:
         hyper.batch_size).  A k outside 1 .. 32, an index of another model or width, or a bad batch_size raise ValueError before anything
         is uploaded."""
-        from .latent_index import LatentIndex, batch_jobs, level_dim
-
         k = _hip.check_knn_k(k)
         if not isinstance(index, LatentIndex):
             raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
-        if index.model is not self or level_dim(self.config, index.level) != index.dim:
-            raise ValueError("the index was built for another model: it lives on that model's GPU handle (%s level, %d columns)" % (
-                index.level, index.dim))
-        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
+        index.check_model(self)
         is_packed = isinstance(inputs, _hip.PackedBatch)
         B = inputs.n_struct if is_packed else int(np.shape(inputs["neighbors"])[0])
         qid = None
@@ -379,13 +327,8 @@ class HipModel:
             if qid.shape[0] != B:
                 raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
         eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
-        parts, state = [], {"at": 0}
-
-        def finish(rb, cnt):
-            parts.append(eng.index_query_batch(index._ix, rb, lvl, k, None if qid is None else qid[state["at"]:state["at"] + cnt]))
-            state["at"] += cnt
-
-        self._pipeline(batch_jobs(self, inputs, bs), finish, launch=lambda rb, slot: None)
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(
+            index._ix, rb, lvl, k, None if qid is None else qid[s0:s1]))
         empty = {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
                  "atom": np.zeros((0, k), np.int32)}
         cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
@@ -398,11 +341,8 @@ class HipModel:
         if atom:
             out["neighbor_atom"] = cat["atom"]
             if not is_packed:
-                amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
                 for n, fill in (("distance", 0), ("latent_distance", 0), ("neighbor_id", -1), ("neighbor_atom", -1)):
-                    full = np.full(amask.shape + out[n].shape[1:], fill, dtype=out[n].dtype)
-                    full[amask] = out[n]
-                    out[n] = full
+                    out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
         return out
 
     def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
@@ -412,19 +352,15 @@ class HipModel:
         rows.  ``pool`` and ``reference`` are each a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes
         it, which is indexed for the call and freed afterwards (ids: 0 .. n-1 in input order).  Returns ``LatentIndex.select``'s dict.
         Bad arguments raise ValueError before anything is uploaded."""
-        from .latent_index import LatentIndex, level_dim, stop_dist2_of
-
         level_dim(self.config, level)
         m, _ = _hip.check_select_args(m, 0.0)
         stop_dist2_of(stop_distance)
-        if batch_size is not None and int(batch_size) < 1:
-            raise ValueError("batch_size must be >= 1")
+        self._batch_size(batch_size)
         if reference is not None and reference is pool:
             raise ValueError("the reference is the pool itself: every row would be at distance 0")
         for ix in (pool, reference):
-            if isinstance(ix, LatentIndex) and (ix.model is not self or level_dim(self.config, ix.level) != ix.dim):
-                raise ValueError("the index was built for another model: it lives on that model's GPU handle (%s level, %d columns)" % (
-                    ix.level, ix.dim))
+            if isinstance(ix, LatentIndex):
+                ix.check_model(self)
         if isinstance(pool, LatentIndex):
             level = pool.level
         if isinstance(reference, LatentIndex) and reference.level != level:
@@ -467,39 +403,17 @@ class HipModel:
             if keys.shape[0] != B:
                 raise ValueError("keys: %d values for %d structures" % (keys.shape[0], B))
             keys = keys.astype(np.uint64)
-        bs = int(batch_size or self.config["hyper"]["batch_size"])
-        if bs < 1:
-            raise ValueError("batch_size must be >= 1")
         eng = self.engine
-        parts = []
-        for s0 in range(0, B, bs):
-            s1 = min(s0 + bs, B)
-            if packed_in:
-                sl, pk = None, _hip.slice_packed(inputs, s0, s1)
-            else:
-                sl = {k: np.asarray(v)[s0:s1] for k, v in inputs.items() if k in self.input_names}
-                pk = _hip.pack_inputs(sl)
-            rb = eng.upload(pk)
-            try:
-                r = eng.predict_mc(rb, T, seed=seed, keys=None if keys is None else keys[s0:s1], p_drop=p_drop, p_attn=p_attn,
-                                   want_ga=True, want_samples=return_samples)
-            finally:
-                rb.free()
-            if sl is not None:
-                for k in ("ga_mean", "ga_std"):
-                    r[k] = _hip.repad_atoms(r[k].reshape(-1, 1), sl["atom_mask"])
-            else:
-                for k in ("ga_mean", "ga_std"):
-                    r[k] = r[k].reshape(-1, 1)
-            parts.append(r)
+        # (batch_size 0 has always meant the default here; padded chunks are packed on the host, as in input_gradients)
+        parts = self._run_chunks(inputs, batch_size or None, lambda rb, s0, s1: eng.predict_mc(
+            rb, T, seed=seed, keys=None if keys is None else keys[s0:s1], p_drop=p_drop, p_attn=p_attn, want_ga=True,
+            want_samples=return_samples), host_pack=True)
         out = {"predict_property": np.concatenate([p["y_mean"] for p in parts]).reshape(-1, 1),
                "predict_property_std": np.concatenate([p["y_std"] for p in parts]).reshape(-1, 1)}
-        if packed_in and inputs.pad_shape is not None:
-            out["global_attention"] = inputs.repad_ga(np.concatenate([p["ga_mean"][:, 0] for p in parts]))
-            out["global_attention_std"] = inputs.repad_ga(np.concatenate([p["ga_std"][:, 0] for p in parts]))
-        else:
-            out["global_attention"] = np.concatenate([p["ga_mean"] for p in parts])
-            out["global_attention_std"] = np.concatenate([p["ga_std"] for p in parts])
+        amask = inputs.atom_mask if packed_in else inputs["atom_mask"]  # (a PackedBatch that was never padded has none: [n_atom, 1])
+        for name, key in (("global_attention", "ga_mean"), ("global_attention_std", "ga_std")):
+            ga = np.concatenate([p[key] for p in parts])
+            out[name] = ga.reshape(-1, 1) if amask is None else _hip.repad_atoms(ga, amask)[..., None]
         if return_samples:
             out["samples"] = np.concatenate([p["y_samples"] for p in parts], axis=1)[:, :, None]
         return out
@@ -553,6 +467,29 @@ class HipModel:
                 b.free()
             if sel is not None:
                 self._select(None)
+
+    def _batch_size(self, batch_size):
+        """The structures per chunk of a batched call -- None: hyper.batch_size; anything below 1 is a ValueError"""
+        bs = int(self.config["hyper"]["batch_size"] if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError("batch_size must be >= 1")
+        return bs
+
+    def _run_chunks(self, data, batch_size, call, host_pack=False):
+        """A synchronous per-batch engine call over ``data`` (what ``batch_jobs`` takes), ``batch_size`` structures at a time:
+        ``call(rb, s0, s1)`` for the resident batch of structures s0 .. s1 - 1, its results as a list in chunk order.  The calls run
+        their own forward, so nothing is enqueued ahead: the pipeline uploads chunk k + 1 before chunk k is computed and frees every
+        batch once, also on an error.  A bad batch_size raises ValueError before anything is uploaded.  ``host_pack``: padded chunks go
+        through the host packer whatever the model would choose."""
+        eng, parts, at = self.engine, [], [0]
+
+        def finish(rb, cnt):
+            parts.append(call(rb, at[0], at[0] + cnt))
+            at[0] += cnt
+
+        upload = (lambda chunk: eng.upload(_hip.pack_inputs(chunk))) if host_pack else None
+        self._pipeline(batch_jobs(self, data, self._batch_size(batch_size), upload), finish, launch=lambda rb, slot: None)
+        return parts
 
     def _upload_padded(self, inputs):
         """A padded input dict (or row views of one) -> resident batch: feature = "atomic" without ring on an inference handle is
@@ -643,9 +580,7 @@ class HipModel:
         amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
         ga_pad = None
         if want_ga:
-            ga_pad = np.zeros(amask.shape, dtype=np.float32)  # softmax of -1e9 -> 0 on padded atoms
-            ga_pad[amask] = np.concatenate(gas)  # packed rows are the real atoms in (structure, atom) order
-            ga_pad = ga_pad[..., None]
+            ga_pad = _hip.repad_atoms(np.concatenate(gas), amask)[..., None]  # softmax of -1e9 -> 0 on padded atoms
         if sel is None:
             return [y, ga_pad]
         # chunks are consecutive structures: their packed outputs, concatenated, are the whole batch's packed outputs

@@ -200,6 +200,40 @@ def test_outputs_come_from_the_exact_fp32_kernels_when_the_split_range_is_left(h
     rb.free()
 
 
+def test_the_exact_rerun_writes_what_the_batch_recorded_not_what_the_handle_selects_now(hip_lib):
+    """the selection belongs to the forward: cleared on the handle between the forward and its reads, the re-run of a forward whose
+    range guard fired still writes the outputs the batch recorded for it (the same after_Lc/bias + 1e5 weights as above)"""
+    from scann import _hip
+    from scann.models.scann_model import HipModel
+
+    cfg = so.default_config("qm9")
+    w = so.init_weights(cfg, 1234, perturb=True)
+    de, dn = so.synth_dataset(9, 3)
+    inputs, _ = so.pad_batch(de, dn, True)
+    bad = dict(w)
+    bad["after_Lc/bias"] = (w["after_Lc/bias"] + 1.0e5).astype(np.float32)
+    eng = HipModel(cfg, bad, device=0, infer=True).engine
+    pk = _hip.pack_inputs(inputs)
+    res = []
+    for clear in (False, True):
+        rb = eng.upload(pk)
+        eng.set_outputs([0], after_lc=True)
+        eng.forward_resident(rb, 1)
+        if clear:
+            eng.set_outputs()
+        before = eng.exact_reruns()
+        a = eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 0)
+        z = eng.read_output(rb, _hip.OUT_AFTER_LC)
+        assert eng.exact_reruns() == before + 1
+        y, ga = eng.download(rb, want_ga=True)
+        assert eng.exact_reruns() == before + 1
+        eng.set_outputs()
+        rb.free()
+        res.append((a, z, y, ga))
+    for on, off in zip(*res):
+        assert on.shape == off.shape and np.array_equal(on.view(np.int32), off.view(np.int32))
+
+
 @pytest.mark.parametrize("g_update", [True, False], ids=["scann_plus", "base"])
 def test_y_and_ga_are_bitwise_unchanged_by_outputs(hip_lib, g_update):
     from scann import _hip

@@ -94,9 +94,12 @@ class _StandIn:
     def __init__(self):
         self.uploads = 0
 
+    def num_streams(self):
+        return 2
+
     def upload(self, packed):
         self.uploads += 1
-        return types.SimpleNamespace(packed=packed, free=lambda: None)
+        return types.SimpleNamespace(packed=packed, free=lambda: None, release=lambda: None)
 
     def input_grads(self, rb, distance=True, weight=True, ring=False, cgcnn=False):
         p = rb.packed

@@ -52,9 +52,12 @@ class _StandIn:
         self.uploads = 0
         self.calls = []
 
+    def num_streams(self):
+        return 2
+
     def upload(self, packed):
         self.uploads += 1
-        return types.SimpleNamespace(packed=packed, free=lambda: None)
+        return types.SimpleNamespace(packed=packed, free=lambda: None, release=lambda: None)
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):
         p = rb.packed
