@@ -430,6 +430,48 @@ int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t
 int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, float stop_dist2,
                            int32_t* pos, float* radius2);
 
+/* ---- k-means over an index: which kinds of local structure the model distinguishes, clustered on the device ----
+ * Lloyd's iteration over the rows of an index, defined so that the labels and the centres depend on the index contents and the initial
+ * centres only, bit for bit: not on chunking, on how many add calls built the index, on the launch geometry or on the order of any sum.
+ * Inputs: a pool index P with N rows of dim columns; k initial centres C_0, 1 <= k <= SCANN_KMEANS_MAX_K; max_iter >= 0; stop_changed >= 0.
+ * Distance: dist2(P[p], C[c]) is exactly the chain of scann_knn_distsq(row, centre, dim): fp32, acc = fmaf(x[j] - c[j], x[j] - c[j], acc),
+ * columns ascending, the row as first argument.
+ * Eligibility: a row is eligible if and only if all its components are finite (the rule of scann_index_select).  Ineligible rows get
+ * label -1 and dist2 +inf, and count for nothing.
+ * Assignment A(C): for each eligible row, label[p] is the first centre under the TOTAL order (dist2 ascending, centre index ascending).  A
+ * NaN distance never qualifies; a row for which no centre qualifies gets -1 / +inf and counts for nothing.  For an eligible row this is
+ * the k = 1 answer of scann_index_query of that row against an index that holds the centres in order: label = that answer's position,
+ * dist2 = its dist2.
+ * Column scales, once per call: m_j is the largest |x[p][j]| over the eligible rows, e_j the frexp exponent of m_j (m_j < 2^e_j; e_j = 0
+ * if m_j = 0 or there is no eligible row), and q(x, j) = llrint(ldexp((double)x, 30 - e_j)), round to nearest even, so |q| <= 2^30.
+ * Update U(label, C): for centre c, n_c is the number of rows labelled c and S[c][j] the sum of q(P[p][j], j) over those rows as an int64
+ * (N < 2^31: it cannot overflow).  If n_c > 0 the new C[c][j] = (float) ldexp((double)S[c][j] / (double)n_c, e_j - 30), every conversion
+ * and the division rounded to nearest; if n_c = 0 the centre keeps its value.  The integer sum is what makes the result independent of
+ * the summation order; its error against the exact mean is at most 2^(e_j - 31) per component, 128 times finer than an fp32 ulp at the
+ * top of the column's range.
+ * Loop: label_{-1} is -1 everywhere.  For t = 0, 1, ...: (1) label_t, dist2_t = A(C_t); (2) changed_t = the number of rows with
+ * label_t[p] != label_{t-1}[p]; (3) if changed_t <= stop_changed or t == max_iter, stop with n_iter = t and
+ * converged = (changed_t <= stop_changed); (4) otherwise C_{t+1} = U(label_t, C_t).
+ * Consequences: the returned labels, distances and sizes (the bincount of the labels) always belong to the returned centres; at most
+ * max_iter updates are made; max_iter = 0 is a pure assignment to the given centres.
+ * Exactly one of init [k * dim] and init_pos [k] (positions in the pool, whose rows are copied device to device) is given.
+ * Return: n_iter (>= 0) or a negative status.  SCANN_ERR_INVALID, with a message that names the argument: a null handle, pool, labels or
+ * centres, an index of another handle, k outside 1 .. SCANN_KMEANS_MAX_K, both or neither of init and init_pos, a non-finite init value,
+ * an init_pos out of range, max_iter < 0, stop_changed < 0 -- all before anything is launched -- and an init_pos that names an ineligible
+ * row, found by the eligibility pass on the device before the first round; no output is written then.  An empty pool returns 0 with
+ * centres = init.
+ * The call is synchronous.  It changes nothing in the pool, the handle's weights, training state or selected outputs; it works on
+ * inference and training handles at any width and runs no forward.  All max_iter + 1 rounds are enqueued on one stream and the host
+ * waits once (once per 256 rounds of a longer run): the end of the loop travels from round to round through device memory. */
+#define SCANN_KMEANS_MAX_K 1024
+int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, const float* init /* [k * dim] or NULL */,
+                           const int32_t* init_pos /* [k] positions in pool, or NULL */, int32_t max_iter, int64_t stop_changed,
+                           int32_t* labels /* [N] */, float* dist2 /* [N] or NULL */, float* centres /* [k * dim] */,
+                           int64_t* sizes /* [k] or NULL */, int32_t* converged /* or NULL */);
+/* the definition on the host, no GPU work: rows [n * dim], init [k * dim]; the kernels' bits */
+int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, int64_t stop_changed,
+                          int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -16,6 +16,10 @@ as well).  With ``--nearest-index FILE`` a saved ``LatentIndex``, for example of
 diverse structures of the dataset (or atoms, at ``--select-level atom``) by greedy k-center selection in the model's latent space, in
 pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering radius at each pick; ``position``; ``count``).  With
 ``--select-reference FILE``, a saved ``LatentIndex`` of what is labelled already, they are the dataset's structures farthest from it.
+``--cluster K [--cluster-level atom|structure] [--cluster-iter N] [--cluster-out FILE]`` clusters the dataset's atoms (or structures)
+in the model's latent space by k-means on the GPU, prints the sizes, ``n_iter`` / ``converged`` / inertia and each cluster's medoid
+(dataset index and atom), pickles the result as ``clusters_<target>.pickle`` and, with ``--cluster-out``, saves the centres as a
+``LatentClustering`` (.npz) that ``SCANN.assign`` takes.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -86,6 +90,10 @@ def main(args):
         raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
     if args.select < 0:
         raise SystemExit("--select: M must be >= 1, got %d" % args.select)
+    if args.cluster and not 1 <= args.cluster <= 1024:
+        raise SystemExit("--cluster: K must lie in 1 .. 1024, got %d" % args.cluster)
+    if args.cluster_iter < 0:
+        raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     target = config["hyper"]["target"]
     print("Load pretrained weight for target ", target)
@@ -182,6 +190,18 @@ def main(args):
         if reference is not None:
             reference.free()
         pickle.dump(sel, open(os.path.join(args.trained_model, "selected_{}.pickle".format(target)), "wb"))
+    if args.cluster:
+        pool = scann.build_index(data, level=args.cluster_level, ids=data.indexes)
+        print("Cluster the dataset's %d rows (%s level) into %d clusters" % (len(pool), args.cluster_level, args.cluster))
+        res, clustering = scann.cluster(pool, args.cluster, max_iter=args.cluster_iter)
+        pool.free()
+        print("n_iter %d, converged %s, inertia %.6g" % (res["n_iter"], res["converged"], res["inertia"]))
+        for c in range(args.cluster):
+            print("cluster %4d: size %8d, medoid id %d atom %d" % (c, res["size"][c], res["medoid_id"][c], res["medoid_atom"][c]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "clusters_{}.pickle".format(target)), "wb"))
+        if args.cluster_out:
+            clustering.save(args.cluster_out)
+        clustering.free()
 
 
 def nearest_records(scann, data, index, k, exclude):
@@ -234,6 +254,13 @@ def parser():
                    help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
     p.add_argument("--select-reference", type=str, default="",
                    help="a saved LatentIndex (.npz) of what is labelled already: the picks are the dataset's rows farthest from it")
+    p.add_argument("--cluster", type=int, default=0,
+                   help="also cluster the dataset's rows in latent space into K clusters (k-means on the GPU, bit-reproducible) and pickle "
+                        "labels, distances, centres, sizes and medoids as clusters_<target>.pickle")
+    p.add_argument("--cluster-level", type=str, default="atom", choices=["atom", "structure"],
+                   help="atom: after_Lc rows, one per atom; structure: bf_property rows, one per structure")
+    p.add_argument("--cluster-iter", type=int, default=50, help="at most N updates of the centres")
+    p.add_argument("--cluster-out", type=str, default="", help="save the centres as a LatentClustering (.npz) for SCANN.assign")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

@@ -1,8 +1,10 @@
 // Latent-space index (include/scann_hip.h: scann_index_*): the rows of bf_property / after_Lc kept on the device in chunks that never
 // move, the exact k-nearest-neighbour search over them (scann_knn.hip) and the host twin of the kernel's distance chain.  Every call is
-// synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The forward of
+// synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The host halves of
+// the k-center selection (scann_select.hip) and of the k-means clustering (scann_kmeans.hip) and their host twins are here as well.  The forward of
 // scann_index_add_batch / scann_index_query_batch is forward_and_download (scann_batch.cpp) with the level's output flag in that one
 // forward's options: y, the scores, the range guard and the exact re-run behave as in scann_batch_download, and the handle is not written.
+#include "scann_kmeans.h"
 #include "scann_knn.h"
 #include "scann_runtime.h"
 #include "scann_select.h"
@@ -445,6 +447,171 @@ int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t
     if (radius2) radius2[i] = r2_h[(size_t)i];
   }
   return cnt;
+}
+
+// frexp's exponent of a column's largest |x| (0 for a column of zeros): the scale of the update's integer sums
+static int kmeans_exponent(float m) {
+  int e = 0;
+  if (m > 0.f) (void)std::frexp(m, &e);
+  return e;
+}
+
+int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, int64_t stop_changed,
+                          int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged) {
+  if (n < 0 || n > (int64_t)0x7fffffff || dim < 1 || k < 1 || k > SCANN_KMEANS_MAX_K || !init || max_iter < 0 || stop_changed < 0 || !centres ||
+      (n > 0 && (!rows || !labels)))
+    return SCANN_ERR_INVALID;
+  for (int64_t i = 0; i < (int64_t)k * dim; ++i)
+    if (!std::isfinite(init[i])) return SCANN_ERR_INVALID;
+  std::copy(init, init + (int64_t)k * dim, centres);
+  std::vector<char> elig((size_t)n, 1);
+  std::vector<int> ex((size_t)dim, 0);
+  {
+    std::vector<float> mx((size_t)dim, 0.f);
+    for (int64_t p = 0; p < n; ++p) {
+      for (int64_t j = 0; j < dim; ++j)
+        if (!std::isfinite(rows[p * dim + j])) elig[(size_t)p] = 0;
+      for (int64_t j = 0; j < dim && elig[(size_t)p]; ++j) mx[(size_t)j] = std::max(mx[(size_t)j], std::fabs(rows[p * dim + j]));
+    }
+    for (int64_t j = 0; j < dim; ++j) ex[(size_t)j] = kmeans_exponent(mx[(size_t)j]);
+  }
+  std::vector<int32_t> lab((size_t)n, -1);
+  std::vector<float> d2((size_t)n, __builtin_inff()), tmp((size_t)k);
+  std::vector<int64_t> sum((size_t)k * dim), cnt((size_t)k);
+  int32_t t = 0;
+  bool conv = false;
+  for (;; ++t) {
+    int64_t changed = 0;
+    for (int64_t p = 0; p < n; ++p) {
+      if (!elig[(size_t)p]) continue;
+      dist2_to_rows(rows + p * dim, centres, k, dim, tmp.data());  // the row first
+      int32_t best = -1;
+      for (int32_t c = 0; c < k; ++c)  // dist2 ascending, index ascending; a NaN distance never qualifies
+        if (tmp[(size_t)c] == tmp[(size_t)c] && (best < 0 || tmp[(size_t)c] < tmp[(size_t)best])) best = c;
+      changed += best != lab[(size_t)p];
+      lab[(size_t)p] = best;
+      d2[(size_t)p] = best < 0 ? __builtin_inff() : tmp[(size_t)best];
+    }
+    conv = changed <= stop_changed;
+    if (conv || t == max_iter) break;
+    std::fill(sum.begin(), sum.end(), 0);
+    std::fill(cnt.begin(), cnt.end(), 0);
+    for (int64_t p = 0; p < n; ++p) {
+      const int32_t c = lab[(size_t)p];
+      if (c < 0) continue;
+      ++cnt[(size_t)c];
+      for (int64_t j = 0; j < dim; ++j) sum[(size_t)c * dim + j] += std::llrint(std::ldexp((double)rows[p * dim + j], 30 - ex[(size_t)j]));
+    }
+    for (int32_t c = 0; c < k; ++c)
+      for (int64_t j = 0; j < dim && cnt[(size_t)c] > 0; ++j)
+        centres[(int64_t)c * dim + j] = (float)std::ldexp((double)sum[(size_t)c * dim + j] / (double)cnt[(size_t)c], ex[(size_t)j] - 30);
+  }
+  if (n > 0) std::copy(lab.begin(), lab.end(), labels);
+  if (dist2 && n > 0) std::copy(d2.begin(), d2.end(), dist2);
+  if (sizes) {
+    std::fill(sizes, sizes + k, 0);
+    for (int64_t p = 0; p < n; ++p)
+      if (lab[(size_t)p] >= 0) ++sizes[lab[(size_t)p]];
+  }
+  if (converged) *converged = conv ? 1 : 0;
+  return t;
+}
+
+int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, const float* init, const int32_t* init_pos, int32_t max_iter,
+                           int64_t stop_changed, int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged) {
+  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: null handle or pool");
+  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: the pool belongs to another handle");
+  if (k < 1 || k > SCANN_KMEANS_MAX_K)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: k " + std::to_string(k) + " outside 1 .. " + std::to_string(SCANN_KMEANS_MAX_K));
+  if ((init != nullptr) == (init_pos != nullptr))
+    return fail(h, SCANN_ERR_INVALID, std::string("scann_index_kmeans: exactly one of init and init_pos must be given, got ") + (init ? "both" : "neither"));
+  if (max_iter < 0) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: max_iter " + std::to_string(max_iter) + " is negative");
+  if (stop_changed < 0) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: stop_changed " + std::to_string(stop_changed) + " is negative");
+  if (!labels) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: labels is null");
+  if (!centres) return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: centres is null");
+  const int64_t N = pool->n;
+  const int32_t dim = pool->dim, stride = pool->stride;
+  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_kmeans: the pool has too many rows");
+  for (int64_t i = 0; init && i < (int64_t)k * dim; ++i)
+    if (!std::isfinite(init[i]))
+      return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: init holds a non-finite value (centre " + std::to_string(i / dim) + ", column " +
+                                            std::to_string(i % dim) + ")");
+  for (int32_t c = 0; init_pos && c < k; ++c)
+    if (init_pos[c] < 0 || init_pos[c] >= N)
+      return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: init_pos[" + std::to_string(c) + "] = " + std::to_string(init_pos[c]) + " outside the pool's " +
+                                            std::to_string(N) + " rows");
+  if (N == 0) {  // (init: init_pos has nothing to point at)
+    std::copy(init, init + (int64_t)k * dim, centres);
+    if (sizes) std::fill(sizes, sizes + k, 0);
+    if (converged) *converged = 1;
+    return 0;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  KmArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride; a.dim = dim; a.k = k;
+  a.n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
+  a.tiles_per_chunk = (pool->chunk_rows + KM_TP - 1) / KM_TP;
+  a.n_tile = a.n_chunk * a.tiles_per_chunk;
+  a.max_iter = max_iter; a.stop_changed = stop_changed;
+  // one workspace for the call.  First what the memset clears: the state, the column maxima, the counts, the sums; then the centres,
+  // the initial positions, the chunk table, labels, dist2 and the eligibility bytes
+  const size_t bS = align_up(sizeof(KmState)), bX = align_up((size_t)stride * 4), bN = align_up((size_t)k * 4), bU = align_up((size_t)k * stride * 8),
+               bC = align_up((size_t)k * stride * 4), bT = align_up((size_t)a.n_chunk * 8), bL = align_up((size_t)N * 4), bE = align_up((size_t)N);
+  const size_t zeroed = bS + bX + bN + bU + bC;  // (the centres' padding columns are zero)
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, zeroed + bN + bT + 2 * bL + bE));
+  a.st = reinterpret_cast<KmState*>(ws);
+  a.colmax = reinterpret_cast<uint32_t*>(ws + bS);
+  a.counts = reinterpret_cast<uint32_t*>(ws + bS + bX);
+  a.sums = reinterpret_cast<unsigned long long*>(ws + bS + bX + bN);
+  a.centres = reinterpret_cast<float*>(ws + bS + bX + bN + bU);
+  int32_t* d_pos = reinterpret_cast<int32_t*>(ws + zeroed);
+  a.init_pos = init_pos ? d_pos : nullptr;
+  a.rows = reinterpret_cast<const float* const*>(ws + zeroed + bN);
+  a.labels = reinterpret_cast<int32_t*>(ws + zeroed + bN + bT);
+  a.dist2 = reinterpret_cast<float*>(ws + zeroed + bN + bT + bL);
+  a.elig = reinterpret_cast<uint8_t*>(ws + zeroed + bN + bT + 2 * bL);
+  std::vector<const void*> tab((size_t)a.n_chunk);
+  for (int c = 0; c < a.n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + zeroed + bN, tab.data(), (size_t)a.n_chunk * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && init) e = hipMemcpy2DAsync(a.centres, (size_t)stride * 4, init, (size_t)dim * 4, (size_t)dim * 4, (size_t)k, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && init_pos) e = hipMemcpyAsync(d_pos, init_pos, (size_t)k * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_kmeans_prepare(a, s);
+  if (e == hipSuccess) e = launch_kmeans_gather(a, s);  // (init_pos: the centres never leave the device)
+  // every round is enqueued at once: whether the loop has ended travels from launch to launch through device memory.  (The state holds
+  // KM_ROUNDS counters: a longer run waits after that many rounds and clears them.)
+  KmState st{};
+  for (int64_t t0 = 0; t0 <= max_iter && e == hipSuccess; t0 += KM_ROUNDS) {
+    if (t0 > 0) e = hipMemsetAsync(reinterpret_cast<char*>(a.st) + offsetof(KmState, changed), 0, sizeof(st.changed), s);
+    for (int64_t t = t0; t <= max_iter && t < t0 + KM_ROUNDS && e == hipSuccess; ++t) e = launch_kmeans_round(a, (int)t, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&st, a.st, sizeof(KmState), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (st.done) break;
+  }
+  const bool ok = e == hipSuccess && st.done && !st.bad_init;
+  if (ok) e = hipMemcpyAsync(labels, a.labels, (size_t)N * 4, hipMemcpyDeviceToHost, s);
+  if (ok && e == hipSuccess && dist2) e = hipMemcpyAsync(dist2, a.dist2, (size_t)N * 4, hipMemcpyDeviceToHost, s);
+  if (ok && e == hipSuccess)
+    e = hipMemcpy2DAsync(centres, (size_t)dim * 4, a.centres, (size_t)stride * 4, (size_t)dim * 4, (size_t)k, hipMemcpyDeviceToHost, s);
+  const hipError_t e_sync = hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  if (st.bad_init) {
+    const int32_t c = k - st.bad_init;
+    return fail(h, SCANN_ERR_INVALID, "scann_index_kmeans: init_pos[" + std::to_string(c) + "] = " + std::to_string(init_pos[c]) +
+                                          " names a row with a non-finite component");
+  }
+  if (!st.done) return fail(h, SCANN_ERR_HIP, "scann_index_kmeans: the loop did not end");
+  if (sizes) {
+    std::fill(sizes, sizes + k, 0);
+    for (int64_t p = 0; p < N; ++p)
+      if (labels[p] >= 0) ++sizes[labels[p]];
+  }
+  if (converged) *converged = st.converged;
+  return st.n_iter;
 }
 
 }  // extern "C"

@@ -129,6 +129,8 @@ SYMBOLS = [
     ("scann_knn_distsq_matrix", None, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
     ("scann_index_select", C.c_int64, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
     ("scann_kcenter_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P]),
+    ("scann_index_kmeans", C.c_int64, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_kmeans_host", C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -147,6 +149,8 @@ OUT_LOCAL_ATTENTION, OUT_AFTER_LC, OUT_BF_PROPERTY = 0, 1, 2
 KNN_MAX_K = 32
 KNN_MAX_DIM = 1024
 KNN_LEVELS = {"structure": OUT_BF_PROPERTY, "atom": OUT_AFTER_LC}
+# scann_index_kmeans' largest k (SCANN_KMEANS_MAX_K)
+KMEANS_MAX_K = 1024
 
 
 def check_knn_k(k):
@@ -207,6 +211,56 @@ def kcenter_host(rows, ref, m, stop_dist2=0.0):
         raise ValueError("kcenter_host: invalid arguments (%d)" % cnt)
     return {"position": pos, "radius2": r2, "count": cnt}
 
+
+def check_kmeans_args(k, max_iter, stop_changed):
+    """(k, max_iter, stop_changed) of a k-means clustering as the C calls take them; ValueError for a k that is no integer in
+    1 .. KMEANS_MAX_K and for a max_iter or stop_changed that is no integer >= 0."""
+    def integer(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+    if not integer(k) or not 1 <= int(k) <= KMEANS_MAX_K:
+        raise ValueError("k must be an integer in 1 .. %d, got %r" % (KMEANS_MAX_K, k))
+    if not integer(max_iter) or not 0 <= int(max_iter) <= 0x7fffffff:
+        raise ValueError("max_iter must be an integer >= 0, got %r" % (max_iter,))
+    if not integer(stop_changed) or int(stop_changed) < 0:
+        raise ValueError("stop_changed must be an integer >= 0, got %r" % (stop_changed,))
+    return int(k), int(max_iter), min(int(stop_changed), (1 << 62))
+
+
+def check_kmeans_init(init, dim):
+    """The initial centres of a k-means clustering as a finite fp32 [k, dim] array; ValueError otherwise."""
+    try:
+        init = np.ascontiguousarray(init, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("init must be an array of k rows of %d columns" % dim) from None
+    if init.ndim != 2 or init.shape[1] != dim or not 1 <= init.shape[0] <= KMEANS_MAX_K:
+        raise ValueError("init must hold 1 .. %d centres of %d columns, got an array of shape %s" % (KMEANS_MAX_K, dim, init.shape))
+    if not np.isfinite(init).all():
+        raise ValueError("init holds a non-finite value")
+    return init
+
+
+def _kmeans_out(n, k, dim):
+    return {"label": np.full(n, -1, np.int32), "dist2": np.full(n, np.inf, np.float32), "centre": np.zeros((k, dim), np.float32),
+            "size": np.zeros(k, np.int64)}
+
+
+def kmeans_host(rows, init, max_iter, stop_changed=0):
+    """k-means on the host with the kernels' bits (scann_kmeans_host, the definition in include/scann_hip.h): ``rows`` [n, dim], ``init``
+    [k, dim] finite.  {"label" [n] int32, "dist2" [n] fp32, "centre" [k, dim] fp32, "size" [k] int64, "n_iter", "converged"}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("kmeans_host: rows of shape %s" % (rows.shape,))
+    init = check_kmeans_init(init, rows.shape[1])
+    k, max_iter, stop_changed = check_kmeans_args(init.shape[0], max_iter, stop_changed)
+    out = _kmeans_out(rows.shape[0], k, rows.shape[1])
+    conv = C.c_int32(0)
+    n_iter = int(load_library().scann_kmeans_host(_ptr(rows), rows.shape[0], rows.shape[1], k, _ptr(init), max_iter, stop_changed, _ptr(out["label"]),
+                                                  _ptr(out["dist2"]), _ptr(out["centre"]), _ptr(out["size"]), C.byref(conv)))
+    if n_iter < 0:
+        raise ValueError("kmeans_host: invalid arguments (%d)" % n_iter)
+    out["n_iter"], out["converged"] = n_iter, bool(conv.value)
+    return out
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -902,6 +956,13 @@ class Engine:
         self._check(self.lib.scann_index_read(self._h, ix._h, int(first), n, _ptr(rows), _ptr(ids), _ptr(atoms)))
         return rows, ids, atoms
 
+    def index_names(self, ix):
+        """(ids [n] int64, atoms [n] int32) of every row, from the host copies the index keeps: nothing is read from the device."""
+        n = len(ix)
+        ids, atoms = np.empty(n, np.int64), np.empty(n, np.int32)
+        self._check(self.lib.scann_index_read(self._h, ix._h, 0, n, None, _ptr(ids), _ptr(atoms)))
+        return ids, atoms
+
     @staticmethod
     def _knn_out(nq, k):
         return {"dist2": np.empty((nq, k), np.float32), "id": np.empty((nq, k), np.int64), "atom": np.empty((nq, k), np.int32),
@@ -954,6 +1015,31 @@ class Engine:
         if cnt < 0:
             self._check(cnt)
         out["count"] = cnt
+        return out
+
+    def index_kmeans(self, ix, init, max_iter=50, stop_changed=0):
+        """k-means over the rows of ``ix`` on the device (scann_index_kmeans).  ``init``: an integer array of k positions in the index
+        (their rows are the initial centres, copied on the device) or a finite float array [k, dim].  {"label" [N] int32, "dist2" [N]
+        fp32, "centre" [k, dim], "size" [k] int64, "n_iter", "converged"}."""
+        a = np.asarray(init)
+        by_pos = a.dtype.kind in "iu" and a.ndim == 1
+        if by_pos:
+            pos = np.ascontiguousarray(a, dtype=np.int64)
+            n = len(ix)
+            if pos.size and (pos.min() < 0 or pos.max() >= n):
+                raise ValueError("index_kmeans: an initial position outside the index's %d rows" % n)
+            pos, cen, k = pos.astype(np.int32), None, pos.shape[0]
+        else:
+            cen, pos = check_kmeans_init(init, ix.dim), None
+            k = cen.shape[0]
+        k, max_iter, stop_changed = check_kmeans_args(k, max_iter, stop_changed)
+        out = _kmeans_out(len(ix), k, ix.dim)
+        conv = C.c_int32(0)
+        n_iter = int(self.lib.scann_index_kmeans(self._h, ix._h, k, _ptr(cen), _ptr(pos), max_iter, stop_changed, _ptr(out["label"]), _ptr(out["dist2"]),
+                                                 _ptr(out["centre"]), _ptr(out["size"]), C.byref(conv)))
+        if n_iter < 0:
+            self._check(n_iter)
+        out["n_iter"], out["converged"] = n_iter, bool(conv.value)
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

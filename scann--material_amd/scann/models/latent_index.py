@@ -162,5 +162,106 @@ class LatentIndex:
         return {"position": r["position"][:n], "neighbor_id": r["id"][:n], "atom": r["atom"][:n],
                 "radius": np.sqrt(r["radius2"][:n]), "count": n}  # (correctly rounded on the host, as nearest reports distances)
 
+    def cluster(self, k, init="kcenter", max_iter=50, stop_changed=0):
+        """k-means over the rows of this index on the GPU (scann_index_kmeans): which kinds of row the model distinguishes, and which
+        kind each row is.  The result depends on the index contents and the initial centres only, bit for bit.  ``init``: "kcenter" --
+        the rows ``self.select(k)`` picks, a deterministic farthest-point seeding; ValueError if fewer than ``k`` rows are eligible --,
+        an integer array of ``k`` positions in the index, or a finite float array [k, dim].  The loop ends when at most ``stop_changed``
+        rows changed their label or after ``max_iter`` updates; rows with a non-finite component get label -1 and count for nothing.
+        Returns {"label" int32 [N], "distance" fp32 [N] (to the row's centre; inf for label -1), "centre" fp32 [k, dim], "size" int64
+        [k], "n_iter", "converged", "inertia" (the fp64 sum of the squared distances of the labelled rows), "medoid_position" int32,
+        "medoid_id" int64, "medoid_atom" int32 [k]: per cluster its member row nearest the centre, ties to the earlier position, -1 for
+        an empty cluster -- the cluster explained by an example}.  Bad arguments raise ValueError before any device call."""
+        k, max_iter, stop_changed = _hip.check_kmeans_args(k, max_iter, stop_changed)
+        eng = self.model.engine
+        if isinstance(init, str):
+            if init != "kcenter":
+                raise ValueError('init must be "kcenter", %d positions or an array [%d, %d], got %r' % (k, k, self.dim, init))
+            picks = eng.index_select(self._ix, None, k, 0.0)
+            if picks["count"] < k:
+                raise ValueError("k = %d clusters need %d rows without a non-finite component, the index has %d" % (k, k, picks["count"]))
+            init = picks["position"]
+        else:
+            a = np.asarray(init)
+            if a.dtype.kind in "iu" and a.ndim == 1:
+                if a.shape[0] != k or (k and (a.min() < 0 or a.max() >= len(self))):
+                    raise ValueError("init must name %d positions in 0 .. %d, got %d of them in %s .. %s" % (
+                        k, len(self) - 1, a.shape[0], a.min() if a.size else "-", a.max() if a.size else "-"))
+                init = a
+            else:
+                init = _hip.check_kmeans_init(init, self.dim)
+                if init.shape[0] != k:
+                    raise ValueError("init holds %d centres, k is %d" % (init.shape[0], k))
+        r = eng.index_kmeans(self._ix, init, max_iter, stop_changed)
+        label, d2 = r["label"], r["dist2"]
+        ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
+        medoid = np.full(k, -1, np.int32)
+        member = np.nonzero(label >= 0)[0]
+        least = np.full(k, np.inf, np.float32)
+        np.minimum.at(least, label[member], d2[member])
+        nearest = member[d2[member] == least[label[member]]]  # the members at their cluster's least dist2, positions ascending
+        cluster, first = np.unique(label[nearest], return_index=True)
+        medoid[cluster] = nearest[first]  # ... and of those the first position
+        has = medoid >= 0
+        return {"label": label, "distance": np.sqrt(d2),  # (correctly rounded on the host, as nearest reports distances)
+                "centre": r["centre"], "size": r["size"], "n_iter": int(r["n_iter"]), "converged": bool(r["converged"]),
+                "inertia": float(d2[member].astype(np.float64).sum()), "medoid_position": medoid,
+                "medoid_id": np.where(has, ids[np.maximum(medoid, 0)], -1).astype(np.int64),
+                "medoid_atom": np.where(has, atoms[np.maximum(medoid, 0)], -1).astype(np.int32)}
+
     def free(self):
         self._ix.free()
+
+
+class LatentClustering:
+    """The centres of a clustering of one level of one model: what ``HipModel.assign`` assigns new inputs to."""
+
+    def __init__(self, centres, level, dim=None):
+        centres = np.ascontiguousarray(centres, dtype=np.float32)
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        if centres.ndim != 2 or not 1 <= centres.shape[0] <= _hip.KMEANS_MAX_K or (dim is not None and centres.shape[1] != int(dim)):
+            raise ValueError("centres must be an array of 1 .. %d rows%s, got shape %s" % (
+                _hip.KMEANS_MAX_K, "" if dim is None else " of %d columns" % int(dim), centres.shape))
+        if not np.isfinite(centres).all():
+            raise ValueError("centres hold a non-finite value")
+        self.centres, self.level, self.dim = centres, level, int(centres.shape[1])
+        self._index = None  # the centres as an index on a model's GPU (index_on)
+
+    @property
+    def k(self):
+        return int(self.centres.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the centres have the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level clustering of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def index_on(self, model):
+        """The centres as a ``LatentIndex`` on ``model``'s GPU, centre c at position c with id c (built once per model and kept)."""
+        self.check_model(model)
+        if self._index is None or self._index.model is not model:
+            self.free()
+            self._index = LatentIndex(model, self.level).add_rows(self.centres)
+        return self._index
+
+    def save(self, path):
+        """An ``.npz`` of centres, level and dim (written to exactly ``path``)."""
+        with open(path, "wb") as f:
+            np.savez(f, centres=self.centres, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved clustering; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim, centres = str(z["level"]), int(z["dim"]), z["centres"]
+        if level not in LEVELS or level_dim(model.config, level) != dim or centres.ndim != 2 or centres.shape[1] != dim:
+            raise ValueError("%s: a %s-level clustering of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(centres, level, dim)
+
+    def free(self):
+        if self._index is not None:
+            self._index.free()
+        self._index = None

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentIndex, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import LatentClustering, LatentIndex, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -377,6 +377,47 @@ class HipModel:
         finally:
             for ix in own:
                 ix.free()
+
+    def cluster(self, data, k, level="atom", init="kcenter", max_iter=50, stop_changed=0, ids=None, batch_size=None):
+        """Which kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``) the
+        model distinguishes: k-means in its latent space, the whole loop on the GPU and bit-reproducible (``LatentIndex.cluster``).
+        ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for the
+        call (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(result, clustering)``: ``LatentIndex.cluster``'s
+        dict and the ``LatentClustering`` of its centres, which ``assign`` takes and which can be saved.  Bad arguments raise ValueError
+        before anything is uploaded."""
+        level_dim(self.config, level)
+        k, max_iter, stop_changed = _hip.check_kmeans_args(k, max_iter, stop_changed)
+        self._batch_size(batch_size)
+        if isinstance(init, str):
+            if init != "kcenter":
+                raise ValueError('init must be "kcenter", %d positions or an array of %d centres, got %r' % (k, k, init))
+        elif np.asarray(init).dtype.kind not in "iu":
+            _hip.check_kmeans_init(init, level_dim(self.config, data.level if isinstance(data, LatentIndex) else level))
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            result = index.cluster(k, init=init, max_iter=max_iter, stop_changed=stop_changed)
+            return result, LatentClustering(result["centre"], index.level, index.dim)
+        finally:
+            if own is not None:
+                own.free()
+
+    def assign(self, inputs, clustering, batch_size=None):
+        """The cluster of every structure (or, for an atom-level clustering, every atom) of new ``inputs``, right behind their forward:
+        ``nearest`` with k = 1 against an index that holds the centres in order, so bitwise the assignment of the clustering's
+        definition (first centre under (distance, index)).  A padded dict gives {"predict_property": [B, 1], "cluster": int32 [B],
+        "distance": fp32 [B]} and at atom level [B, M] arrays with -1 / 0 at padded atoms; a ``PackedBatch`` gives packed [n_atom]
+        arrays.  Raw y.  A clustering of another width or a bad batch_size raise ValueError before anything is uploaded."""
+        if not isinstance(clustering, LatentClustering):
+            raise ValueError("clustering must be a LatentClustering, got %r" % (type(clustering).__name__,))
+        clustering.check_model(self)
+        self._batch_size(batch_size)
+        r = self.nearest(inputs, clustering.index_on(self), k=1, batch_size=batch_size)
+        return {"predict_property": r["predict_property"], "cluster": r["neighbor_id"][..., 0].astype(np.int32), "distance": r["distance"][..., 0]}
 
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
@@ -903,6 +944,17 @@ class SCANN:
     def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
         """HipModel.select_diverse as it is: the distances live in latent space."""
         return self.model.select_diverse(pool, m, reference=reference, level=level, stop_distance=stop_distance, batch_size=batch_size)
+
+    def cluster(self, data, k, level="atom", init="kcenter", max_iter=50, stop_changed=0, ids=None, batch_size=None):
+        """HipModel.cluster as it is: ``(result, clustering)``; the distances live in latent space."""
+        return self.model.cluster(data, k, level=level, init=init, max_iter=max_iter, stop_changed=stop_changed, ids=ids, batch_size=batch_size)
+
+    def assign(self, ip, clustering, batch_size=None):
+        """HipModel.assign with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
+        live in latent space and stay as they are."""
+        out = self.model.assign(ip, clustering, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
 
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
         """HipModel.predict_uncertainty in the units of the target, as predict_data de-normalises: the mean times std plus mean, the
