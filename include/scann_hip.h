@@ -472,6 +472,67 @@ int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, co
 int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, int64_t stop_changed,
                           int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged);
 
+/* ---- principal-component map of an index: mean, covariance and projection on the device ----
+ * The low-dimensional map of a latent space, and the Mahalanobis distance to the indexed distribution (Lee et al., NeurIPS 2018) as an
+ * applicability-domain score beside the k-nearest-neighbour distance.  Mean and covariance are defined so that they depend on the index
+ * contents only, bit for bit: not on the order of any sum, on the launch geometry, on chunking or on how many add calls built the index.
+ * Eligibility: a row is eligible if and only if all its components are finite (the rule of scann_index_select).  n is the number of
+ * eligible rows; ineligible rows count for nothing.
+ * Mean: the k-means update with one cluster.  e_j is the frexp exponent of the largest |x[p][j]| over the eligible rows (0 if that is
+ * 0), q(x, j) = llrint(ldexp((double)x, 30 - e_j)), S_j the int64 sum of q over the eligible rows, and
+ *   mean_j = (float) ldexp((double)S_j / (double)n, e_j - 30).
+ * Centred values: y[p][j] = x[p][j] - mean_j in fp32, rounded once.  f_j is the frexp exponent of the largest |y[p][j]| over the
+ * eligible rows (0 if that is 0).  L is the bit length of n (n < 2^L) and b = min(24, (62 - L) / 2), integer division: 24 bits up to
+ * 16,383 rows, 20 at 2.4 M, 15 at 2^31 - 1 (scann_pca_bits).  u(y, j) = llrint(ldexp((double)y, b - f_j)), round to nearest even, so
+ * |u| <= 2^b.
+ * Scatter: T[i][j] is the int64 sum over the eligible rows of u_i * u_j, R_j the int64 sum of u_j.  Every partial sum of T is bounded by
+ * n * 2^(2b) < 2^62: no order of the adds can overflow, and the sum is the same in any order.
+ * Covariance, fp64:
+ *   cov[i][j] = ldexp(((double)T_ij - (double)R_i * (double)R_j / (double)n) / (double)(n - 1), f_i + f_j - 2b)
+ * as written, left to right, each operation rounded to nearest, none contracted; computed for i <= j and mirrored.
+ * Error against the exact covariance cov* of the fp32 rows: |cov_ij - cov*_ij| <= 2^(f_i + f_j - b + 2).  (|u - y 2^(b - f)| <= 1/2 gives
+ * n (2^b + 1/4) on T_ij; the remaining factor covers the fp32 centring, 2^-24 relative per factor, and the R term.)  The noise floor
+ * nu = dim * 2^(2 max_j f_j - b + 2): by Weyl's inequality an eigenvalue at or below nu cannot be told from 0.
+ * Eigen-decomposition (scann_sym_eig_host): on the host, fp64, cyclic Jacobi over the upper triangle of a [d * d], row-cyclic order
+ * (p, q), p < q ascending.  An a_pq with |a_pp| + |a_pq| == |a_pp| and |a_qq| + |a_pq| == |a_qq| in fp64 -- below half an ulp of both
+ * diagonal entries -- is set to exactly 0 without a rotation (between two equal eigenvalues theta is rounding noise, and rotating such
+ * entries would never leave them all exactly 0); otherwise a rotation is made if and only if a_pq != 0: theta = (a_qq - a_pp) / (2 a_pq);
+ * t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) with sign(0) = +1, or t = 1 / (2 theta) if theta^2 overflows; c = 1 / sqrt(t^2 + 1),
+ * s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0 exactly, and for every other r (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq); the
+ * vectors turn the same way.  Sweeps continue until one makes no rotation; *sweeps counts them, that last one included; 64 sweeps that
+ * all rotated are SCANN_ERR_UNSUPPORTED.  Order: eigenvalue descending, ties by original column ascending.  Sign: the entry of largest
+ * magnitude (first index among ties) of each vector is positive.  w [d]; v [d * d], vector c in v[c * d .. c * d + d - 1].
+ * Projection.  Inputs: mean [dim]; components W [m * dim], row c one vector, 1 <= m <= dim; scale s [m]; all fp32 and finite.  For a row x:
+ *   z_c    = acc_dim,  acc_0 = 0,  acc_{j+1} = fmaf(x[j] - mean[j], W[c][j], acc_j), fp32, columns ascending, the difference rounded once;
+ *   md2    = acc_m,  acc_0 = 0,  acc_{c+1} = fmaf(t_c, t_c, acc_c),  t_c = z_c * s_c rounded once, c ascending (with s_c = 1 / sqrt(lambda_c)
+ *            the squared Mahalanobis distance; s_c = 0 leaves a component out);
+ *   dist2  = the chain of scann_knn_distsq with the row as first and the mean as second argument.
+ * A row with a non-finite component gives what the chains give: a NaN stays a NaN (its sign and payload are not part of the definition).
+ *
+ * scann_index_moments: n_eligible, mean [dim], cov [dim * dim] fp64, col_exp [dim] = f_j (or NULL), bits = b (or NULL) of the pool's rows.
+ * Synchronous, one host wait.  Fewer than 2 eligible rows -- an empty pool among them -- are SCANN_ERR_INVALID with a message that says
+ * so; n_eligible is written then, the other outputs are not.  scann_index_project: rows [first, first + n) of the pool, device-resident;
+ * coords [n * m]; md2, dist2 [n] or NULL (scale may be NULL without md2).  scann_project_batch: one inference forward of the resident
+ * batch with the level's output added for that forward only (as scann_index_query_batch: y [n_struct] and ga [n_atom] or NULL are bitwise
+ * those of scann_forward_resident + scann_batch_download; range guard, exact-fp32 re-run and SCANN_STRICT_RANGE as there), and the level's
+ * rows -- one per structure, or per atom in packed order -- projected device to device.  SCANN_ERR_INVALID before anything is launched,
+ * with a message that names the argument: a null handle, pool, batch or output, an index of another handle, rows outside the pool, m
+ * outside 1 .. dim, an unknown level, a non-finite mean, component or scale.  The calls change nothing in the pool, the handle's
+ * weights, training state or selected outputs, and work on inference and training handles at any width.
+ * The twins need no GPU and give the kernels' bits: scann_moments_host (rows [n * dim]; threads over the rows of T, integer sums being
+ * order-free), scann_project_host. */
+int scann_index_moments(scann_handle_t* h, scann_index_t* pool, int64_t* n_eligible, float* mean /* [dim] */, double* cov /* [dim * dim] */,
+                        int32_t* col_exp /* [dim] or NULL */, int32_t* bits /* or NULL */);
+int scann_index_project(scann_handle_t* h, scann_index_t* pool, int64_t first, int64_t n, const float* mean, const float* components,
+                        const float* scale, int32_t m, float* coords /* [n * m] */, float* md2 /* [n] or NULL */, float* dist2 /* [n] or NULL */);
+int scann_project_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* components, const float* scale,
+                        int32_t m, float* y, float* ga, float* coords, float* md2, float* dist2);
+int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eligible, float* mean, double* cov, int32_t* col_exp, int32_t* bits);
+int scann_project_host(const float* rows, int64_t n, int64_t dim, const float* mean, const float* components, const float* scale, int32_t m,
+                       float* coords, float* md2, float* dist2);
+int scann_sym_eig_host(const double* a, int64_t d, double* w, double* v, int32_t* sweeps);
+int scann_pca_bits(int64_t n);  /* b for n eligible rows, 0 <= n < 2^31; SCANN_ERR_INVALID otherwise */
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

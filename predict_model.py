@@ -20,6 +20,11 @@ pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering
 in the model's latent space by k-means on the GPU, prints the sizes, ``n_iter`` / ``converged`` / inertia and each cluster's medoid
 (dataset index and atom), pickles the result as ``clusters_<target>.pickle`` and, with ``--cluster-out``, saves the centres as a
 ``LatentClustering`` (.npz) that ``SCANN.assign`` takes.
+``--project M [--project-level atom|structure] [--project-out FILE]`` maps the dataset's structures (or atoms) onto the M leading
+principal components of the model's latent space (mean and covariance on the GPU, bit-reproducible), prints the rank and the explained
+variance, pickles the result -- coordinates, Mahalanobis distance and distance to the mean per row, with the rows' dataset indices and
+atoms -- as ``projection_<target>.pickle`` and, with ``--project-out``, saves the map as a ``LatentProjection`` (.npz) that
+``SCANN.project`` takes.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -95,6 +100,10 @@ def main(args):
     if args.cluster_iter < 0:
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
+    if args.project:  # (0: the flag was not given)
+        width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
+        if not 1 <= args.project <= width:
+            raise SystemExit("--project: M must lie in 1 .. %d, the width of the %s level, got %d" % (width, args.project_level, args.project))
     target = config["hyper"]["target"]
     print("Load pretrained weight for target ", target)
     scann = SCANN(config, os.path.join(args.trained_model, "models", "model_{}.h5".format(target)), mode="infer")
@@ -202,6 +211,21 @@ def main(args):
         if args.cluster_out:
             clustering.save(args.cluster_out)
         clustering.free()
+    if args.project:
+        pool = scann.build_index(data, level=args.project_level, ids=data.indexes)
+        print("Map the dataset's %d rows (%s level) onto %d principal components" % (len(pool), args.project_level, args.project))
+        try:
+            res, projection = scann.fit_projection(pool, m=args.project)
+        except ValueError as e:  # (fewer than 2 usable rows)
+            pool.free()
+            raise SystemExit("--project: %s" % e) from None
+        res["id"], res["atom"] = pool.names()
+        print("n_rows %d, rank %d, total variance %.6g, explained variance ratio %s" % (
+            res["n_rows"], res["rank"], res["total_variance"], " ".join("%.4f" % r for r in res["explained_variance_ratio"])))
+        pickle.dump(res, open(os.path.join(args.trained_model, "projection_{}.pickle".format(target)), "wb"))
+        if args.project_out:
+            projection.save(args.project_out)
+        pool.free()
 
 
 def nearest_records(scann, data, index, k, exclude):
@@ -261,6 +285,12 @@ def parser():
                    help="atom: after_Lc rows, one per atom; structure: bf_property rows, one per structure")
     p.add_argument("--cluster-iter", type=int, default=50, help="at most N updates of the centres")
     p.add_argument("--cluster-out", type=str, default="", help="save the centres as a LatentClustering (.npz) for SCANN.assign")
+    p.add_argument("--project", type=int, default=0,
+                   help="also map the dataset's rows onto the M leading principal components of the latent space (moments on the GPU, "
+                        "bit-reproducible) and pickle coordinates and distances as projection_<target>.pickle")
+    p.add_argument("--project-level", type=str, default="structure", choices=["atom", "structure"],
+                   help="rows to map: one per structure (bf_property) or one per atom (after_Lc)")
+    p.add_argument("--project-out", type=str, default="", help="save the map as a LatentProjection (.npz) for SCANN.project")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

@@ -1,11 +1,13 @@
 // Latent-space index (include/scann_hip.h: scann_index_*): the rows of bf_property / after_Lc kept on the device in chunks that never
 // move, the exact k-nearest-neighbour search over them (scann_knn.hip) and the host twin of the kernel's distance chain.  Every call is
 // synchronous: it returns when the device has finished its work, so no query is ever in flight while an add runs.  The host halves of
-// the k-center selection (scann_select.hip) and of the k-means clustering (scann_kmeans.hip) and their host twins are here as well.  The forward of
-// scann_index_add_batch / scann_index_query_batch is forward_and_download (scann_batch.cpp) with the level's output flag in that one
+// the k-center selection (scann_select.hip) and of the k-means clustering (scann_kmeans.hip) and their host twins are here as well, and
+// the host half of the principal-component map (scann_pca.hip; its twins and the eigen-decomposition are in scann_pca.cpp).  The forward of
+// scann_index_add_batch / scann_index_query_batch / scann_project_batch is forward_and_download (scann_batch.cpp) with the level's output flag in that one
 // forward's options: y, the scores, the range guard and the exact re-run behave as in scann_batch_download, and the handle is not written.
 #include "scann_kmeans.h"
 #include "scann_knn.h"
+#include "scann_pca.h"
 #include "scann_runtime.h"
 #include "scann_select.h"
 
@@ -612,6 +614,187 @@ int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, co
   }
   if (converged) *converged = st.converged;
   return st.n_iter;
+}
+
+// ---- principal-component map (scann_pca.hip; the twins and the eigen-decomposition are in scann_pca.cpp) ----
+
+int scann_index_moments(scann_handle_t* h, scann_index_t* pool, int64_t* n_eligible, float* mean, double* cov, int32_t* col_exp, int32_t* bits) {
+  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: null handle or pool");
+  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: the pool belongs to another handle");
+  if (!n_eligible) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: n_eligible is null");
+  if (!mean) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: mean is null");
+  if (!cov) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: cov is null");
+  const int64_t N = pool->n;
+  const int32_t dim = pool->dim, stride = pool->stride;
+  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_moments: the pool has too many rows");
+  if (N == 0) {
+    *n_eligible = 0;
+    return fail(h, SCANN_ERR_INVALID, "scann_index_moments: a covariance needs at least 2 rows, the pool has 0");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  PcaArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride; a.dim = dim;
+  a.n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
+  // one workspace for the call.  First what the memset clears: the state, the two column maxima, S, R and T; then the mean, the
+  // covariance, f, the chunk table and the eligibility bytes
+  const size_t bS = align_up(sizeof(PcaState)), bX = align_up((size_t)stride * 4), bU = align_up((size_t)stride * 8),
+               bT = align_up((size_t)stride * stride * 8), bC = align_up((size_t)dim * dim * 8), bP = align_up((size_t)a.n_chunk * 8),
+               bE = align_up((size_t)N);
+  const size_t zeroed = bS + 2 * bX + 2 * bU + bT;
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, zeroed + 2 * bX + bC + bP + bE));
+  a.st = reinterpret_cast<PcaState*>(ws);
+  a.colmax = reinterpret_cast<uint32_t*>(ws + bS);
+  a.cenmax = reinterpret_cast<uint32_t*>(ws + bS + bX);
+  a.sums = reinterpret_cast<unsigned long long*>(ws + bS + 2 * bX);
+  a.R = reinterpret_cast<unsigned long long*>(ws + bS + 2 * bX + bU);
+  a.T = reinterpret_cast<unsigned long long*>(ws + bS + 2 * bX + 2 * bU);
+  a.mean = reinterpret_cast<float*>(ws + zeroed);
+  a.col_exp = reinterpret_cast<int32_t*>(ws + zeroed + bX);
+  a.cov = reinterpret_cast<double*>(ws + zeroed + 2 * bX);
+  a.rows = reinterpret_cast<const float* const*>(ws + zeroed + 2 * bX + bC);
+  a.elig = reinterpret_cast<uint8_t*>(ws + zeroed + 2 * bX + bC + bP);
+  std::vector<const void*> tab((size_t)a.n_chunk);
+  for (int c = 0; c < a.n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  PcaState st{};
+  std::vector<float> mean_h((size_t)dim);
+  std::vector<double> cov_h((size_t)dim * dim);
+  std::vector<int32_t> exp_h((size_t)dim);
+  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + zeroed + 2 * bX + bC, tab.data(), (size_t)a.n_chunk * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_pca_moments(a, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&st, a.st, sizeof(PcaState), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(mean_h.data(), a.mean, (size_t)dim * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(cov_h.data(), a.cov, (size_t)dim * dim * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(exp_h.data(), a.col_exp, (size_t)dim * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
+  cached_free(ws);
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  *n_eligible = st.n;
+  if (st.n < 2)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_moments: a covariance needs at least 2 rows without a non-finite component, the pool has " +
+                                          std::to_string(st.n) + " among its " + std::to_string(N));
+  std::copy(mean_h.begin(), mean_h.end(), mean);
+  std::copy(cov_h.begin(), cov_h.end(), cov);
+  if (col_exp) std::copy(exp_h.begin(), exp_h.end(), col_exp);
+  if (bits) *bits = scann_pca_bits(st.n);
+  return SCANN_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the arguments of a projection onto rows of `dim` columns
+int check_projection(scann_handle* h, const char* who, int64_t dim, const float* mean, const float* components, const float* scale, int32_t m,
+                     const float* coords, const float* md2) {
+  const std::string w(who);
+  if (m < 1 || m > dim) return fail(h, SCANN_ERR_INVALID, w + ": m " + std::to_string(m) + " outside 1 .. " + std::to_string(dim));
+  if (!mean) return fail(h, SCANN_ERR_INVALID, w + ": mean is null");
+  if (!components) return fail(h, SCANN_ERR_INVALID, w + ": components is null");
+  if (!coords) return fail(h, SCANN_ERR_INVALID, w + ": coords is null");
+  if (md2 && !scale) return fail(h, SCANN_ERR_INVALID, w + ": md2 needs scale, which is null");
+  for (int64_t j = 0; j < dim; ++j)
+    if (!std::isfinite(mean[j])) return fail(h, SCANN_ERR_INVALID, w + ": mean holds a non-finite value (column " + std::to_string(j) + ")");
+  for (int64_t i = 0; i < (int64_t)m * dim; ++i)
+    if (!std::isfinite(components[i]))
+      return fail(h, SCANN_ERR_INVALID, w + ": components hold a non-finite value (component " + std::to_string(i / dim) + ", column " +
+                                            std::to_string(i % dim) + ")");
+  for (int32_t c = 0; scale && c < m; ++c)
+    if (!std::isfinite(scale[c])) return fail(h, SCANN_ERR_INVALID, w + ": scale holds a non-finite value (component " + std::to_string(c) + ")");
+  return SCANN_OK;
+}
+
+// rows [first, first + n) of the chunks in `tab` ([chunk_rows][stride] each, the padding zero) projected; the outputs are host arrays.
+// The coordinates pass through a device block of at most 256 MiB, a group of rows at a time
+int project_rows(scann_handle* h, const std::vector<const void*>& tab, int32_t chunk_rows, int32_t stride, int32_t dim, int64_t first, int64_t n,
+                 const float* mean, const float* components, const float* scale, int32_t m, float* coords, float* md2, float* dist2, hipStream_t s) {
+  if (n <= 0) return SCANN_OK;
+  const int64_t g = std::min<int64_t>(n, std::max<int64_t>(PCA_TP, (((int64_t)256 << 20) / ((int64_t)m * 4)) / PCA_TP * PCA_TP));
+  const size_t bM = align_up((size_t)stride * 4), bW = align_up((size_t)m * stride * 4), bS = align_up((size_t)m * 4), bP = align_up(tab.size() * 8),
+               bZ = align_up((size_t)g * m * 4), bD = align_up((size_t)g * 4);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bM + bW + bS + bP + bZ + 2 * bD));
+  PcaProjArgs a{};
+  a.rows = reinterpret_cast<const float* const*>(ws + bM + bW + bS);
+  a.chunk_rows = chunk_rows; a.stride = stride; a.dim = dim; a.m = m;
+  a.mean = reinterpret_cast<const float*>(ws);
+  a.comp = reinterpret_cast<const float*>(ws + bM);
+  a.scale = reinterpret_cast<const float*>(ws + bM + bW);
+  a.coords = reinterpret_cast<float*>(ws + bM + bW + bS + bP);
+  a.md2 = md2 ? reinterpret_cast<float*>(ws + bM + bW + bS + bP + bZ) : nullptr;
+  a.dist2 = dist2 ? reinterpret_cast<float*>(ws + bM + bW + bS + bP + bZ + bD) : nullptr;
+  hipError_t e = hipMemsetAsync(ws, 0, bM + bW + bS, s);  // (the padding columns of the mean and of the components are zero)
+  if (e == hipSuccess) e = hipMemcpyAsync(ws, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + bM, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && scale) e = hipMemcpyAsync(ws + bM + bW, scale, (size_t)m * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + bM + bW + bS, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s);
+  for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += g) {
+    const int64_t cnt = std::min<int64_t>(g, n - r0);
+    a.first = (int32_t)(first + r0); a.n = (int32_t)cnt;
+    e = launch_pca_project(a, s);  // (the stream orders a group behind the copies of the one before)
+    if (e == hipSuccess) e = hipMemcpyAsync(coords + (size_t)r0 * m, a.coords, (size_t)cnt * m * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && md2) e = hipMemcpyAsync(md2 + r0, a.md2, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && dist2) e = hipMemcpyAsync(dist2 + r0, a.dist2, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t e_sync = hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  return SCANN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int scann_index_project(scann_handle_t* h, scann_index_t* pool, int64_t first, int64_t n, const float* mean, const float* components,
+                        const float* scale, int32_t m, float* coords, float* md2, float* dist2) {
+  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_project: null handle or pool");
+  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_project: the pool belongs to another handle");
+  if (first < 0 || n < 0 || first + n > pool->n)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_project: rows " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " + std::to_string(pool->n));
+  if (const int r = check_projection(h, "scann_index_project", pool->dim, mean, components, scale, m, coords, md2)) return r;
+  if (n == 0) return SCANN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<const void*> tab(pool->chunks.size());
+  for (size_t c = 0; c < tab.size(); ++c) tab[c] = pool->rows_of(c);
+  return project_rows(h, tab, pool->chunk_rows, pool->stride, pool->dim, first, n, mean, components, scale, m, coords, md2, dist2, h->streams[0]);
+}
+
+int scann_project_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* components, const float* scale,
+                        int32_t m, float* y, float* ga, float* coords, float* md2, float* dist2) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_project_batch: null handle or batch");
+  const int dim = level_dim(h, level);
+  if (!dim) return fail(h, SCANN_ERR_INVALID, "scann_project_batch: level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  if (const int r = check_projection(h, "scann_project_batch", dim, mean, components, scale, m, coords, md2)) return r;
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_project_batch: weights not loaded");
+  const bool atom = level == SCANN_OUT_AFTER_LC;
+  const int64_t nq = atom ? db->n_atom : db->n_struct;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
+  if (nq <= 0) return SCANN_OK;
+  hipStream_t s = h->streams[db->last_slot];
+  const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
+  const int stride = (dim + 3) / 4 * 4;
+  char* pad = nullptr;
+  if (stride != dim) {  // rows of the padded width, as an index keeps them
+    HIPCHK(h, cached_malloc((void**)&pad, align_up((size_t)nq * stride * 4)));
+    hipError_t e = hipMemsetAsync(pad, 0, (size_t)nq * stride * 4, s);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(pad, (size_t)stride * 4, src, (size_t)dim * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      cached_free(pad);
+      HIPCHK(h, e);
+    }
+    src = reinterpret_cast<const float*>(pad);
+  }
+  const std::vector<const void*> tab(1, src);
+  const int r = project_rows(h, tab, 0x7fffffff, stride, dim, 0, nq, mean, components, scale, m, coords, md2, dist2, s);
+  if (pad) cached_free(pad);
+  return r;
 }
 
 }  // extern "C"

@@ -131,6 +131,13 @@ SYMBOLS = [
     ("scann_kcenter_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P]),
     ("scann_index_kmeans", C.c_int64, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
     ("scann_kmeans_host", C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_index_moments", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_project", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("scann_project_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_moments_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_project_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("scann_sym_eig_host", C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    ("scann_pca_bits", C.c_int, [C.c_int64]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -261,6 +268,95 @@ def kmeans_host(rows, init, max_iter, stop_changed=0):
         raise ValueError("kmeans_host: invalid arguments (%d)" % n_iter)
     out["n_iter"], out["converged"] = n_iter, bool(conv.value)
     return out
+
+
+def pca_bits(n):
+    """b of the principal-component moments for ``n`` eligible rows (scann_pca_bits): min(24, (62 - bit_length(n)) // 2)."""
+    b = int(load_library().scann_pca_bits(int(n)))
+    if b < 0:
+        raise ValueError("pca_bits: n must lie in 0 .. 2^31 - 1, got %r" % (n,))
+    return b
+
+
+def moments_host(rows):
+    """Mean and covariance of the rows without a non-finite component on the host, with the kernels' bits (scann_moments_host, the
+    definition in include/scann_hip.h): ``rows`` [n, dim].  {"n" eligible rows, "mean" [dim] fp32, "cov" [dim, dim] fp64, "col_exp"
+    [dim] int32 (f_j), "bits" (b)}; ValueError for fewer than 2 eligible rows."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("moments_host: rows of shape %s" % (rows.shape,))
+    n, dim = rows.shape
+    out = {"mean": np.zeros(dim, np.float32), "cov": np.zeros((dim, dim), np.float64), "col_exp": np.zeros(dim, np.int32)}
+    ne, bits = C.c_int64(0), C.c_int32(0)
+    rc = int(load_library().scann_moments_host(_ptr(rows), n, dim, C.byref(ne), _ptr(out["mean"]), _ptr(out["cov"]), _ptr(out["col_exp"]),
+                                               C.byref(bits)))
+    if rc < 0:
+        raise ValueError("moments_host: a covariance needs at least 2 rows without a non-finite component, got %d among %d" % (ne.value, n))
+    out["n"], out["bits"] = int(ne.value), int(bits.value)
+    return out
+
+
+def check_pca_args(mean, components, scale, dim=None):
+    """(mean [dim], components [m, dim], scale [m] or None) of a projection as the C calls take them: finite fp32, 1 <= m <= dim;
+    ValueError otherwise, naming the argument."""
+    def array(x, name):
+        try:
+            return np.ascontiguousarray(x, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be an array of numbers" % name) from None
+
+    mean, components = array(mean, "mean"), array(components, "components")
+    if mean.ndim != 1 or mean.shape[0] < 1 or (dim is not None and mean.shape[0] != int(dim)):
+        raise ValueError("mean must be a vector%s, got shape %s" % ("" if dim is None else " of %d columns" % int(dim), mean.shape))
+    d = mean.shape[0]
+    if components.ndim != 2 or components.shape[1] != d or not 1 <= components.shape[0] <= d:
+        raise ValueError("components must hold m rows of %d columns, 1 <= m <= %d, got shape %s" % (d, d, components.shape))
+    if scale is not None:
+        scale = array(scale, "scale")
+        if scale.shape != (components.shape[0],):
+            raise ValueError("scale must hold one value per component (%d), got shape %s" % (components.shape[0], scale.shape))
+    for name, a in (("mean", mean), ("components", components), ("scale", scale)):
+        if a is not None and not np.isfinite(a).all():
+            raise ValueError("%s holds a non-finite value" % name)
+    return mean, components, scale
+
+
+def _project_out(n, m, scale):
+    out = {"coords": np.empty((n, m), np.float32), "dist2": np.empty(n, np.float32)}
+    if scale is not None:
+        out["md2"] = np.empty(n, np.float32)
+    return out
+
+
+def project_host(rows, mean, components, scale=None):
+    """The projection on the host with the kernel's bits (scann_project_host): {"coords" [n, m], "dist2" [n], with ``scale`` "md2" [n]}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("project_host: rows of shape %s" % (rows.shape,))
+    mean, components, scale = check_pca_args(mean, components, scale, rows.shape[1])
+    out = _project_out(rows.shape[0], components.shape[0], scale)
+    rc = int(load_library().scann_project_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(mean), _ptr(components), _ptr(scale),
+                                               components.shape[0], _ptr(out["coords"]), _ptr(out.get("md2")), _ptr(out["dist2"])))
+    if rc < 0:
+        raise ValueError("project_host: invalid arguments (%d)" % rc)
+    return out
+
+
+def sym_eig(a):
+    """Eigen-decomposition of a symmetric fp64 matrix (its upper triangle) by cyclic Jacobi on the host (scann_sym_eig_host): (w [d]
+    descending, v [d, d] with vector c in row c and its largest entry positive, sweeps).  ValueError for a matrix that is not square or
+    not finite; RuntimeError if 64 sweeps did not end the iteration."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1 or not np.isfinite(a).all():
+        raise ValueError("sym_eig: a finite square matrix is needed, got shape %s" % (a.shape,))
+    d = a.shape[0]
+    w, v, sweeps = np.zeros(d, np.float64), np.zeros((d, d), np.float64), C.c_int32(0)
+    rc = int(load_library().scann_sym_eig_host(_ptr(a), d, _ptr(w), _ptr(v), C.byref(sweeps)))
+    if rc == -2:
+        raise RuntimeError("sym_eig: no convergence in %d sweeps" % sweeps.value)
+    if rc < 0:
+        raise ValueError("sym_eig: invalid arguments (%d)" % rc)
+    return w, v, int(sweeps.value)
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -1040,6 +1136,41 @@ class Engine:
         if n_iter < 0:
             self._check(n_iter)
         out["n_iter"], out["converged"] = n_iter, bool(conv.value)
+        return out
+
+    def index_moments(self, ix):
+        """Mean and covariance of the rows of ``ix`` without a non-finite component, on the device (scann_index_moments): {"n", "mean"
+        [dim] fp32, "cov" [dim, dim] fp64, "col_exp" [dim] int32, "bits"}, bit for bit ``moments_host`` of the same rows."""
+        dim = ix.dim
+        out = {"mean": np.zeros(dim, np.float32), "cov": np.zeros((dim, dim), np.float64), "col_exp": np.zeros(dim, np.int32)}
+        ne, bits = C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.scann_index_moments(self._h, ix._h, C.byref(ne), _ptr(out["mean"]), _ptr(out["cov"]), _ptr(out["col_exp"]),
+                                                 C.byref(bits)))
+        out["n"], out["bits"] = int(ne.value), int(bits.value)
+        return out
+
+    def index_project(self, ix, mean, components, scale=None, first=0, n=None):
+        """Rows first .. first + n - 1 of ``ix`` (default: all) projected on the device (scann_index_project): {"coords" [n, m], "dist2"
+        [n], with ``scale`` "md2" [n]}."""
+        mean, components, scale = check_pca_args(mean, components, scale, ix.dim)
+        first = int(first)
+        n = len(ix) - first if n is None else int(n)
+        if first < 0 or n < 0 or first + n > len(ix):
+            raise ValueError("index_project: rows %d .. %d of %d" % (first, first + n, len(ix)))
+        out = _project_out(n, components.shape[0], scale)
+        self._check(self.lib.scann_index_project(self._h, ix._h, first, n, _ptr(mean), _ptr(components), _ptr(scale), components.shape[0],
+                                                 _ptr(out["coords"]), _ptr(out.get("md2")), _ptr(out["dist2"])))
+        return out
+
+    def project_batch(self, rb, level, mean, components, scale=None):
+        """One forward of a resident batch and the projection of each of its ``level`` rows (scann_project_batch; raw y): {"y"
+        [n_struct], "ga" [n_atom], "coords" [n_struct or n_atom, m], "dist2", with ``scale`` "md2"}."""
+        mean, components, scale = check_pca_args(mean, components, scale)
+        p = rb.packed
+        out = _project_out(p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct, components.shape[0], scale)
+        out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
+        self._check(self.lib.scann_project_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(components), _ptr(scale), components.shape[0],
+                                                 _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["coords"]), _ptr(out.get("md2")), _ptr(out["dist2"])))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

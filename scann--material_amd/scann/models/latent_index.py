@@ -74,6 +74,19 @@ def stop_dist2_of(stop_distance):
     return float(np.float32(stop) * np.float32(stop))
 
 
+def explained_ratio(w):
+    """The share of every eigenvalue in the total variance, fp64: negative eigenvalues (rounding noise of a rank-deficient covariance)
+    count as 0, and the divisor is the fp64 sum of the others times 1 + (d + 2) * 2^-52 = 1 + (2 d + 4) * 2^-53.  The d - 1 adds of that
+    sum, a quotient, and the d - 1 adds of a sum of the ratios each err by at most 2^-53 relative, fewer than 2 d roundings along any
+    path, so with that divisor the ratios, or any part of them, sum to at most 1 in fp64 whatever the order of the adds; dividing by
+    one number keeps them non-increasing.  All zeros if no eigenvalue is positive."""
+    w = np.maximum(np.asarray(w, dtype=np.float64), 0.0)
+    total = float(w.sum())
+    if not total > 0.0:
+        return np.zeros(len(w))
+    return w / (total * (1.0 + (len(w) + 2) * 2.0 ** -52))
+
+
 class LatentIndex:
     """Rows of one level of one model on its GPU.  ``level``: "structure" (one ``bf_property`` row per structure) or "atom" (one
     ``after_Lc`` row per real atom).  Every row carries the id of its structure and, at atom level, the atom's index within it."""
@@ -117,6 +130,10 @@ class LatentIndex:
     def rows(self):
         """(rows [n, dim] fp32, ids [n] int64, atoms [n] int32) copied back from the device, in insertion order."""
         return self.model.engine.index_read(self._ix)
+
+    def names(self):
+        """(ids [n] int64, atoms [n] int32) of every row, from the host copies the index keeps: nothing is read from the device."""
+        return self.model.engine.index_names(self._ix)
 
     def save(self, path):
         """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``)."""
@@ -209,8 +226,113 @@ class LatentIndex:
                 "medoid_id": np.where(has, ids[np.maximum(medoid, 0)], -1).astype(np.int64),
                 "medoid_atom": np.where(has, atoms[np.maximum(medoid, 0)], -1).astype(np.int32)}
 
+    def pca(self, m=None):
+        """The principal-component map of this index's rows, mean and covariance computed on the GPU (scann_index_moments) and
+        bit-reproducible: they depend on the index contents only.  Rows with a non-finite component count for nothing.  The covariance
+        is decomposed on the host (``_hip.sym_eig``: cyclic Jacobi, fp64) and the rows are projected on the device onto the ``m``
+        leading components (None: all ``dim``).  Returns ``(result, projection)``: {"mean" fp32 [dim], "components" fp32 [m, dim],
+        "variance" fp64 [m] (the eigenvalues, descending), "explained_variance_ratio" fp64 [m] (``explained_ratio``: each eigenvalue,
+        negative ones as 0, over the sum of them all, the divisor rounded up so that the ratios are non-increasing and their fp64 sum
+        never exceeds 1), "total_variance" (the trace), "rank" (eigenvalues above the noise floor of the integer moments), "noise_floor", "n_rows" (the
+        rows that counted), "coordinates" fp32 [N, m], "mahalanobis" fp32 [N] (over the ``m`` components; those at or below the noise
+        floor are left out), "distance_to_mean" fp32 [N]} -- NaN for every row whose distance to the mean is not finite, as it is for a
+        row with a non-finite component -- and the ``LatentProjection`` that ``HipModel.project`` takes.  A bad ``m`` raises ValueError
+        before any device call; so do fewer than 2 usable rows."""
+        m = self.dim if m is None else m
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= self.dim:
+            raise ValueError("m must be an integer in 1 .. %d, got %r" % (self.dim, m))
+        m = int(m)
+        if len(self) < 2:
+            raise ValueError("a covariance needs at least 2 rows, the index has %d" % len(self))
+        eng = self.model.engine
+        try:
+            mo = eng.index_moments(self._ix)
+        except _hip.ScannHipError as e:
+            if e.code == -1:
+                raise ValueError(str(e)) from None
+            raise
+        w, v, _ = _hip.sym_eig(mo["cov"])
+        noise = float(self.dim) * 2.0 ** (2 * int(mo["col_exp"].max()) - mo["bits"] + 2)
+        total = float(np.trace(mo["cov"]))
+        proj = LatentProjection(mo["mean"], v[:m].astype(np.float32), w[:m], noise, self.level, self.dim)
+        out = self.project(proj)
+        out.update({"mean": proj.mean, "components": proj.components, "variance": proj.variance, "total_variance": total,
+                    "explained_variance_ratio": explained_ratio(w)[:m], "rank": int((w > noise).sum()),
+                    "noise_floor": noise, "n_rows": mo["n"]})
+        return out, proj
+
+    def project(self, projection):
+        """This index's own rows through a ``LatentProjection``, on the device where they lie (scann_index_project): {"coordinates" fp32
+        [N, m], "mahalanobis" fp32 [N], "distance_to_mean" fp32 [N]}; NaN for every row whose distance to the mean is not finite."""
+        if not isinstance(projection, LatentProjection):
+            raise ValueError("projection must be a LatentProjection, got %r" % (type(projection).__name__,))
+        if projection.level != self.level or projection.dim != self.dim:
+            raise ValueError("a %s-level projection of %d columns does not fit a %s-level index of %d" % (
+                projection.level, projection.dim, self.level, self.dim))
+        r = self.model.engine.index_project(self._ix, projection.mean, projection.components, projection.scale)
+        return projection.finish(r)
+
     def free(self):
         self._ix.free()
+
+
+class LatentProjection:
+    """A principal-component map of one level of one model: mean [dim], components [m, dim] (fp32, rows), their variances (fp64) and the
+    noise floor below which a variance cannot be told from 0.  ``scale`` [m] fp32 is 1 / sqrt(variance) above the floor and 0 at or
+    below it, so such a component adds nothing to the Mahalanobis distance; ``rank`` counts the components above it."""
+
+    def __init__(self, mean, components, variance, noise_floor, level, dim=None):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        self.mean, self.components, _ = _hip.check_pca_args(mean, components, None, dim)
+        try:
+            self.variance = np.ascontiguousarray(variance, dtype=np.float64)
+            self.noise_floor = float(noise_floor)
+        except (TypeError, ValueError):
+            raise ValueError("variance must be an array of numbers and noise_floor a number") from None
+        if self.variance.shape != (self.components.shape[0],) or not np.isfinite(self.variance).all():
+            raise ValueError("variance must hold one finite value per component (%d), got shape %s" % (self.components.shape[0], self.variance.shape))
+        if not self.noise_floor >= 0.0 or not np.isfinite(self.noise_floor):
+            raise ValueError("noise_floor must be a finite number >= 0, got %r" % (noise_floor,))
+        self.level, self.dim = level, int(self.mean.shape[0])
+        above = self.variance > self.noise_floor
+        self.scale = np.where(above, 1.0 / np.sqrt(np.where(above, self.variance, 1.0)), 0.0).astype(np.float32)
+        self.rank = int(above.sum())
+
+    @property
+    def m(self):
+        return int(self.components.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the projection has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level projection of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def finish(self, r):
+        """the device's {"coords", "md2", "dist2"} as the rows the callers report: square roots taken on the host (correctly rounded, as
+        ``nearest`` reports distances), NaN where the distance to the mean is not finite"""
+        bad = ~np.isfinite(r["dist2"])
+        coords, md, dist = r["coords"].copy(), np.sqrt(r["md2"]), np.sqrt(r["dist2"])
+        coords[bad], md[bad], dist[bad] = np.nan, np.nan, np.nan
+        return {"coordinates": coords, "mahalanobis": md, "distance_to_mean": dist}
+
+    def save(self, path):
+        """An ``.npz`` of mean, components, variance, noise_floor, level and dim (written to exactly ``path``)."""
+        with open(path, "wb") as f:
+            np.savez(f, mean=self.mean, components=self.components, variance=self.variance, noise_floor=np.array(self.noise_floor),
+                     level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved projection; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            mean, components, variance, noise = z["mean"], z["components"], z["variance"], float(z["noise_floor"])
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level projection of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(mean, components, variance, noise, level, dim)
 
 
 class LatentClustering:

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentClustering, LatentIndex, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import LatentClustering, LatentIndex, LatentProjection, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -418,6 +418,53 @@ class HipModel:
         self._batch_size(batch_size)
         r = self.nearest(inputs, clustering.index_on(self), k=1, batch_size=batch_size)
         return {"predict_property": r["predict_property"], "cluster": r["neighbor_id"][..., 0].astype(np.int32), "distance": r["distance"][..., 0]}
+
+    def fit_projection(self, data, m=2, level="structure", ids=None, batch_size=None):
+        """The principal-component map of the model's latent space over ``data``: the ``m`` leading axes of the ``bf_property`` rows
+        (``level`` "structure") or of the ``after_Lc`` rows ("atom"), mean and covariance computed on the GPU and bit-reproducible
+        (``LatentIndex.pca``).  ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which
+        is indexed for the call (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(result, projection)``:
+        ``LatentIndex.pca``'s dict -- the map of ``data`` itself -- and the ``LatentProjection`` that ``project`` takes and that can be
+        saved.  Bad arguments raise ValueError before anything is uploaded."""
+        dim = level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= dim:
+            raise ValueError("m must be an integer in 1 .. %d, got %r" % (dim, m))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.pca(int(m))
+        finally:
+            if own is not None:
+                own.free()
+
+    def project(self, inputs, projection, batch_size=None):
+        """New ``inputs`` on a ``LatentProjection``'s map, right behind their forward (scann_project_batch): the coordinates, the
+        Mahalanobis distance to the distribution the projection was fitted on (an applicability-domain score beside ``nearest``'s
+        distances) and the Euclidean distance to its mean.  A padded dict gives {"predict_property": [B, 1], "coordinates": fp32 [B, m],
+        "mahalanobis": [B], "distance_to_mean": [B]} and at atom level [B, M, m] / [B, M] arrays with 0 at padded atoms; a
+        ``PackedBatch`` gives packed [n_atom, m] / [n_atom] arrays.  Raw y.  A projection of another width or a bad batch_size raise
+        ValueError before anything is uploaded."""
+        if not isinstance(projection, LatentProjection):
+            raise ValueError("projection must be a LatentProjection, got %r" % (type(projection).__name__,))
+        projection.check_model(self)
+        self._batch_size(batch_size)
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[projection.level], projection.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.project_batch(
+            rb, lvl, projection.mean, projection.components, projection.scale))
+        m = projection.m
+        empty = {"y": np.zeros(0, np.float32), "coords": np.zeros((0, m), np.float32), "md2": np.zeros(0, np.float32), "dist2": np.zeros(0, np.float32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = projection.finish(cat)
+        out["predict_property"] = cat["y"].reshape(-1, 1)
+        if atom and not isinstance(inputs, _hip.PackedBatch):
+            for n in ("coordinates", "mahalanobis", "distance_to_mean"):
+                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
+        return out
 
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
@@ -953,6 +1000,17 @@ class SCANN:
         """HipModel.assign with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
         live in latent space and stay as they are."""
         out = self.model.assign(ip, clustering, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
+
+    def fit_projection(self, data, m=2, level="structure", ids=None, batch_size=None):
+        """HipModel.fit_projection as it is: ``(result, projection)``; the map lives in latent space."""
+        return self.model.fit_projection(data, m=m, level=level, ids=ids, batch_size=batch_size)
+
+    def project(self, ip, projection, batch_size=None):
+        """HipModel.project with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
+        coordinates and the distances live in latent space and stay as they are."""
+        out = self.model.project(ip, projection, batch_size=batch_size)
         out["predict_property"] = out["predict_property"] * self.std + self.mean
         return out
 
