@@ -397,6 +397,61 @@ int scann_index_query_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_
 float scann_knn_distsq(const float* q, const float* r, int64_t d);
 void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out);
 
+/* ---- structure matching: the nearest structures of an atom-level index by their local structures ----
+ * Which indexed structures are made of the same local structures as this one?  A query structure and an indexed structure are compared
+ * as SETS of after_Lc rows (the best-match / average-kernel comparison of atomic environments), on the device right behind the forward.
+ *
+ * Segments.  The structures of an index are its segments: the maximal runs of consecutive positions whose rows carry the same id.
+ * Segment s is the rows [first_s, first_s + m_s); segments are numbered in position order.  scann_index_add_batch at atom level gives one
+ * segment per structure; an id that occurs in two separate runs gives two segments.  A segment may be of any length and may lie across
+ * a storage-chunk boundary.  scann_index_segments reads the table from the host copies the index keeps (any output NULL) and returns
+ * the number of segments.
+ *
+ * Pair quantities, for a query structure A = a_0 .. a_{n-1} (n >= 1) and a segment B = b_0 .. b_{m-1}:
+ *   D[i][j] = dist2(a_i, b_j), exactly the fp32 chain of scann_index_query (scann_knn_distsq: its bits);
+ *   f_i = min_j D[i][j] over the j whose D[i][j] is not NaN, +inf if there is none; its witness is the least position that attains it
+ *         (position -1 if there is none);
+ *   g_j = min_i D[i][j] likewise, the least query atom as witness;
+ *   F: fp64, acc = 0, acc += (double) f_i for i ascending, F = acc / n;    G: the same over j ascending, divided by m;
+ *   Fmax = max_i f_i, Gmax = max_j g_j (fp32);    parts = {(float) F, (float) G, Fmax, Gmax}.
+ * Score, by `measure`:
+ *   SCANN_MATCH_CHAMFER    (float)(F + G), the add in fp64 and rounded once;
+ *   SCANN_MATCH_HAUSDORFF  max(Fmax, Gmax);
+ *   SCANN_MATCH_COVER      (float) F, the directed form: does every local structure of the query occur in B?
+ * A score is never NaN; it is +inf if an atom has no finite partner.  Chamfer and Hausdorff are symmetric in (A, B) bit for bit: the
+ * difference is negated exactly, its square is the same, and the fp64 add commutes.
+ *
+ * Ranking.  The k nearest segments of A are the first k under the TOTAL order (score ascending, then segment number ascending), k in
+ * 1 .. SCANN_KNN_MAX_K, so the answer depends on the query and the index contents only, bit for bit: not on the batch the structure is
+ * in, on the launch geometry or on how many calls built the index.  With query ids, segments whose id equals the query's are skipped.
+ * Places without a segment hold segment -1, id -1, size 0, score and parts +inf, match positions -1, match dist2 +inf.
+ * Matches.  For every query atom i and every place p: the position of the witness of f_i in the place's segment, and f_i.
+ *
+ * scann_index_match takes host vectors: q [q_first[n_sets] * dim], the rows of set s being q_first[s] .. q_first[s + 1] - 1 (q_first[0]
+ * = 0).  Outputs: score, segment, ids, sizes [n_sets * k], parts [n_sets * k * 4], match_pos, match_dist2 [q_first[n_sets] * k]; all
+ * but score may be NULL.  scann_index_match_batch runs one inference forward of the resident batch with after_Lc added for that forward
+ * only and matches every structure of the batch; y, ga, the handle's selection, training state, generic widths and SCANN_EXACT are
+ * exactly as for scann_index_query_batch.  SCANN_ERR_INVALID before anything is launched: a null argument, a bad k or measure, an empty
+ * query or an empty query set, a q_first that does not start at 0 or decreases, an index of another handle or width.  A query structure
+ * of more than SCANN_MATCH_MAX_ATOMS atoms is SCANN_ERR_UNSUPPORTED, before anything is launched, and the message names it; segments
+ * have no length limit.  An empty index answers with the +inf tail.  Synchronous.
+ * scann_match_parts_host is the host twin (no GPU work, the scann_knn_distsq chain): parts [n_sets * n_seg * 4] of every (set,
+ * segment) pair of q [q_first[n_sets] * dim] and rows [seg_first[n_seg] * dim]; q_first [n_sets + 1], seg_first [n_seg + 1] increasing. */
+#define SCANN_MATCH_CHAMFER 0
+#define SCANN_MATCH_HAUSDORFF 1
+#define SCANN_MATCH_COVER 2
+#define SCANN_MATCH_MAX_ATOMS 128 /* atoms per query structure: a structure's atoms are the query rows of one workgroup, which holds the
+                                     128 x 64 distances of a tile in LDS (33 KiB) and an 8 x 4 register block of chains per lane */
+int64_t scann_index_segments(const scann_index_t* idx, int64_t* first, int32_t* count, int64_t* id);
+int scann_index_match(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets,
+                      const int64_t* query_ids, int32_t measure, int32_t k, float* score, int32_t* segment, int64_t* ids, int32_t* sizes,
+                      float* parts, int32_t* match_pos, float* match_dist2);
+int scann_index_match_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure, int32_t k,
+                            float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos,
+                            float* match_dist2);
+int scann_match_parts_host(const float* q, const int32_t* q_first, int64_t n_sets, const float* rows, const int32_t* seg_first, int64_t n_seg,
+                           int64_t dim, float* parts /* [n_sets * n_seg * 4] */);
+
 /* ---- greedy k-center selection: the most diverse rows of an index, picked on the device ----
  * Which m candidates should be labelled next, given what is labelled already?  Farthest-point selection in latent space (the core-set
  * rule of Sener & Savarese, ICLR 2018): repeatedly take the candidate whose distance to everything labelled or already taken is

@@ -12,6 +12,8 @@ per structure with ``attribution`` [n] (the GA scores traced back to the atoms t
 with the K nearest structures of the dataset in the model's latent space (``neighbor_id``: dataset indices, the structure itself left
 out; ``distance``; ``latent_distance``: their mean, an uncertainty measure), or per atom at ``--nearest-level atom`` (``neighbor_atom``
 as well).  With ``--nearest-index FILE`` a saved ``LatentIndex``, for example of the training set, is searched and nothing is left out.
+``--match K [--match-measure chamfer|hausdorff|cover] [--match-index FILE]`` pickles ``match_<target>.pickle``: per structure the K
+structures of the dataset (or of a saved atom-level index) made of the most similar local structures, and which atom matches which.
 ``--select M [--select-level atom] [--select-reference FILE]`` also pickles ``selected_<target>.pickle``: one dict with the M most
 diverse structures of the dataset (or atoms, at ``--select-level atom``) by greedy k-center selection in the model's latent space, in
 pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering radius at each pick; ``position``; ``count``).  With
@@ -93,6 +95,8 @@ def main(args):
         return main_with(args)
     if args.nearest and not 1 <= args.nearest <= 32:
         raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
+    if args.match and not 1 <= args.match <= 32:
+        raise SystemExit("--match: K must lie in 1 .. 32, got %d" % args.match)
     if args.select < 0:
         raise SystemExit("--select: M must be >= 1, got %d" % args.select)
     if args.cluster and not 1 <= args.cluster <= 1024:
@@ -186,6 +190,24 @@ def main(args):
         per = nearest_records(scann, data, index, args.nearest, exclude=not args.nearest_index)
         index.free()
         pickle.dump(per, open(os.path.join(args.trained_model, "nearest_{}.pickle".format(target)), "wb"))
+    if args.match:
+        from scann.models import LatentIndex
+
+        if args.match_index:
+            index = LatentIndex.load(scann.model, args.match_index)
+            if index.level != "atom":
+                raise SystemExit("--match-index: %s is a %s-level index, matching needs an atom-level one" % (args.match_index, index.level))
+            print("Match: %d nearest structures of %s (%d atom rows), %s" % (args.match, args.match_index, len(index), args.match_measure))
+        else:  # the dataset itself, every structure queried with its own dataset index left out
+            index = scann.build_index(data, level="atom", ids=data.indexes)
+            print("Match: %d nearest of the dataset's own structures (%d atom rows), %s, leave-one-out" % (args.match, len(index), args.match_measure))
+        try:
+            per = match_records(scann, data, index, args.match, args.match_measure, exclude=not args.match_index)
+        except ValueError as e:  # (a structure above the atom limit)
+            index.free()
+            raise SystemExit("--match: %s" % e) from None
+        index.free()
+        pickle.dump(per, open(os.path.join(args.trained_model, "match_{}.pickle".format(target)), "wb"))
     if args.select:
         from scann.models import LatentIndex
 
@@ -248,6 +270,21 @@ def nearest_records(scann, data, index, k, exclude):
     return per
 
 
+def match_records(scann, data, index, k, measure, exclude):
+    """--match: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        sel = data.indexes[b * data.batch_size:(b + 1) * data.batch_size]
+        r = scann.match_structures(inputs, index, k=k, measure=measure, exclude_ids=sel if exclude else None)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):  # matched_*: the structure's own atoms
+            per.append({"predict_property": float(r["predict_property"][i, 0]), "distance": r["distance"][i], "neighbor_id": r["neighbor_id"][i],
+                        "neighbor_size": r["neighbor_size"][i], "parts": r["parts"][i], "matched_atom": r["matched_atom"][i][amask[i]],
+                        "matched_distance": r["matched_distance"][i][amask[i]]})
+    return per
+
+
 def parser():
     p = argparse.ArgumentParser()
     p.add_argument("trained_model", type=str, help="Target trained model path for loading")
@@ -271,6 +308,14 @@ def parser():
                    help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
     p.add_argument("--nearest-index", type=str, default="",
                    help="a saved LatentIndex (.npz) to search instead of the dataset itself; nothing is left out")
+    p.add_argument("--match", type=int, default=0,
+                   help="also pickle the K (1 .. 32) structures of the dataset made of the most similar local structures (sets of after_Lc "
+                        "rows compared on the GPU), leave-one-out, with the atom-to-atom correspondence, as match_<target>.pickle: one dict "
+                        "per structure, unpadded, ids = dataset indices")
+    p.add_argument("--match-measure", type=str, default="chamfer", choices=["chamfer", "hausdorff", "cover"],
+                   help="chamfer: mean nearest-atom distance both ways; hausdorff: the worst one; cover: the query's atoms only")
+    p.add_argument("--match-index", type=str, default="",
+                   help="a saved atom-level LatentIndex (.npz) to match against instead of the dataset itself; nothing is left out")
     p.add_argument("--select", type=int, default=0,
                    help="also pickle the M most diverse structures of the dataset (greedy k-center selection in latent space) as "
                         "selected_<target>.pickle: one dict with ids (dataset indices), atoms and radii in pick order")

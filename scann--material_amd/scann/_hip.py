@@ -127,6 +127,10 @@ SYMBOLS = [
     ("scann_index_query_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("scann_knn_distsq", C.c_float, [_P, _P, C.c_int64]),
     ("scann_knn_distsq_matrix", None, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
+    ("scann_index_segments", C.c_int64, [_P, _P, _P, _P]),
+    ("scann_index_match", C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_match_batch", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_match_parts_host", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P]),
     ("scann_index_select", C.c_int64, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
     ("scann_kcenter_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P]),
     ("scann_index_kmeans", C.c_int64, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
@@ -158,6 +162,9 @@ KNN_MAX_DIM = 1024
 KNN_LEVELS = {"structure": OUT_BF_PROPERTY, "atom": OUT_AFTER_LC}
 # scann_index_kmeans' largest k (SCANN_KMEANS_MAX_K)
 KMEANS_MAX_K = 1024
+# scann_index_match: the measures by name (SCANN_MATCH_*) and the most atoms of one query structure (SCANN_MATCH_MAX_ATOMS)
+MATCH_MEASURES = {"chamfer": 0, "hausdorff": 1, "cover": 2}
+MATCH_MAX_ATOMS = 128
 
 
 def check_knn_k(k):
@@ -184,6 +191,42 @@ def knn_dist2_matrix(q, rows):
         raise ValueError("knn_dist2_matrix: shapes %s and %s" % (q.shape, rows.shape))
     out = np.zeros((q.shape[0], rows.shape[0]), dtype=np.float32)
     load_library().scann_knn_distsq_matrix(_ptr(q), q.shape[0], _ptr(rows), rows.shape[0], q.shape[1], _ptr(out))
+    return out
+
+
+def check_match_measure(measure):
+    """measure of a structure match as the C calls take it: a name of MATCH_MEASURES or its number; ValueError otherwise."""
+    if isinstance(measure, str) and measure in MATCH_MEASURES:
+        return MATCH_MEASURES[measure]
+    if not isinstance(measure, (bool, str)) and isinstance(measure, (int, np.integer)) and int(measure) in MATCH_MEASURES.values():
+        return int(measure)
+    raise ValueError("measure must be one of %s, got %r" % (", ".join(MATCH_MEASURES), measure))
+
+
+def check_match_sets(first, n_rows, what="q_first"):
+    """The offsets [n_sets + 1] of consecutive non-empty sets over ``n_rows`` rows as int32; ValueError otherwise."""
+    first = np.ascontiguousarray(first, dtype=np.int64).reshape(-1)
+    if first.shape[0] < 2 or first[0] != 0 or first[-1] != n_rows or (np.diff(first) < 1).any() or n_rows > 0x7fffffff:
+        raise ValueError("%s must be increasing offsets from 0 to the %d rows with no empty set, got %d offsets from %s to %s" % (
+            what, n_rows, first.shape[0], first[0] if first.size else "-", first[-1] if first.size else "-"))
+    return first.astype(np.int32)
+
+
+def match_parts_host(q, q_first, rows, seg_first):
+    """[n_sets, n_seg, 4] fp32: (float) F, (float) G, Fmax, Gmax of every (query set, segment) pair on the host with the kernel's bits
+    (scann_match_parts_host, the definition in include/scann_hip.h): ``q`` [nq, dim] cut by ``q_first`` [n_sets + 1], ``rows`` [n, dim]
+    cut by ``seg_first`` [n_seg + 1]."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if q.ndim != 2 or rows.ndim != 2 or q.shape[1] != rows.shape[1] or q.shape[1] < 1:
+        raise ValueError("match_parts_host: shapes %s and %s" % (q.shape, rows.shape))
+    q_first = check_match_sets(q_first, q.shape[0], "q_first")
+    seg_first = check_match_sets(seg_first, rows.shape[0], "seg_first")
+    out = np.zeros((q_first.shape[0] - 1, seg_first.shape[0] - 1, 4), dtype=np.float32)
+    r = load_library().scann_match_parts_host(_ptr(q), _ptr(q_first), q_first.shape[0] - 1, _ptr(rows), _ptr(seg_first), seg_first.shape[0] - 1,
+                                              q.shape[1], _ptr(out))
+    if r != 0:
+        raise ValueError("match_parts_host: bad arguments")
     return out
 
 
@@ -1097,6 +1140,62 @@ class Engine:
         out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
         self._check(self.lib.scann_index_query_batch(self._h, ix._h, rb._h, int(level), _ptr(qid), k, _ptr(out["y"]), _ptr(out["ga"]),
                                                      _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["position"])))
+        return out
+
+    def index_segments(self, ix):
+        """(first int64, count int32, id int64) [n_seg] of the segments of ``ix``: its maximal runs of rows with one id
+        (scann_index_segments; from the host copies the index keeps)."""
+        n = int(self.lib.scann_index_segments(ix._h, None, None, None))
+        if n < 0:
+            raise ScannHipError(n, "scann_index_segments: no index")
+        first, count, ids = np.empty(n, np.int64), np.empty(n, np.int32), np.empty(n, np.int64)
+        self.lib.scann_index_segments(ix._h, _ptr(first), _ptr(count), _ptr(ids))
+        return first, count, ids
+
+    @staticmethod
+    def _match_out(n_sets, n_rows, k):
+        return {"score": np.empty((n_sets, k), np.float32), "segment": np.empty((n_sets, k), np.int32), "id": np.empty((n_sets, k), np.int64),
+                "size": np.empty((n_sets, k), np.int32), "parts": np.empty((n_sets, k, 4), np.float32),
+                "match_position": np.empty((n_rows, k), np.int32), "match_dist2": np.empty((n_rows, k), np.float32)}
+
+    def index_match(self, ix, q, q_first, k, measure="chamfer", query_ids=None):
+        """The k nearest segments of ``ix`` for every set of host query rows -- ``q`` [nq, dim] cut by ``q_first`` [n_sets + 1] -- as
+        sets of rows (scann_index_match): {"score", "segment", "id", "size" [n_sets, k], "parts" [n_sets, k, 4], "match_position",
+        "match_dist2" [nq, k]}."""
+        k, measure = check_knn_k(k), check_match_measure(measure)
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise ValueError("index_match: queries of shape %s for an index of %d columns" % (q.shape, ix.dim))
+        if q.shape[0] < 1:
+            raise ValueError("index_match: an empty query")
+        q_first = check_match_sets(q_first, q.shape[0])
+        n_sets = q_first.shape[0] - 1
+        big = np.nonzero(np.diff(q_first) > MATCH_MAX_ATOMS)[0]
+        if big.size:
+            raise ValueError("index_match: query structure %d has %d atoms, more than %d" % (
+                big[0], int(np.diff(q_first)[big[0]]), MATCH_MAX_ATOMS))
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != n_sets:
+            raise ValueError("index_match: %d query structures need %d query ids" % (n_sets, n_sets))
+        out = self._match_out(n_sets, q.shape[0], k)
+        self._check(self.lib.scann_index_match(self._h, ix._h, _ptr(q), _ptr(q_first), n_sets, _ptr(qid), measure, k, _ptr(out["score"]),
+                                               _ptr(out["segment"]), _ptr(out["id"]), _ptr(out["size"]), _ptr(out["parts"]),
+                                               _ptr(out["match_position"]), _ptr(out["match_dist2"])))
+        return out
+
+    def index_match_batch(self, ix, rb, k, measure="chamfer", query_ids=None):
+        """One forward of a resident batch and the k nearest segments of ``ix`` for each of its structures, taken as sets of after_Lc
+        rows (scann_index_match_batch; raw y): index_match's dict over the batch's packed atoms plus "y" [n_struct], "ga" [n_atom]."""
+        k, measure = check_knn_k(k), check_match_measure(measure)
+        p = rb.packed
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != p.n_struct:
+            raise ValueError("index_match_batch: %d structures need %d query ids" % (p.n_struct, p.n_struct))
+        out = self._match_out(p.n_struct, p.n_atom, k)
+        out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
+        self._check(self.lib.scann_index_match_batch(self._h, ix._h, rb._h, _ptr(qid), measure, k, _ptr(out["y"]), _ptr(out["ga"]),
+                                                     _ptr(out["score"]), _ptr(out["segment"]), _ptr(out["id"]), _ptr(out["size"]),
+                                                     _ptr(out["parts"]), _ptr(out["match_position"]), _ptr(out["match_dist2"])))
         return out
 
     def index_select(self, pool_ix, ref_ix, m, stop_dist2=0.0):

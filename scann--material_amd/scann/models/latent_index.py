@@ -135,6 +135,11 @@ class LatentIndex:
         """(ids [n] int64, atoms [n] int32) of every row, from the host copies the index keeps: nothing is read from the device."""
         return self.model.engine.index_names(self._ix)
 
+    def segments(self):
+        """(first int64, count int32, id int64) of the index's segments -- its maximal runs of consecutive rows with one id, i.e. the
+        structures of an atom-level index, numbered in position order -- from the host copies the index keeps."""
+        return self.model.engine.index_segments(self._ix)
+
     def save(self, path):
         """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``)."""
         rows, ids, atoms = self.rows()

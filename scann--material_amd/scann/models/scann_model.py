@@ -345,6 +345,58 @@ class HipModel:
                     out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
         return out
 
+    def match_structures(self, inputs, index, k=5, measure="chamfer", exclude_ids=None, batch_size=None):
+        """The ``k`` structures of an atom-level ``LatentIndex`` that are made of the same local structures as each structure of
+        ``inputs``: the two are compared as sets of ``after_Lc`` rows on the GPU right behind the forward (scann_index_match_batch).
+        With f_i the squared distance of query atom i to its nearest atom of the indexed structure and g_j the same from the indexed
+        structure's atom j, ``measure`` "chamfer" scores mean f + mean g, "hausdorff" max(max f, max g), and "cover" mean f alone
+        (does every local structure of the query occur there?).  Structures are ranked by (score, position in the index): the result
+        depends on the query and the index only, bit for bit.  ``exclude_ids`` [B]: indexed structures whose id equals the
+        structure's are skipped (leave-one-out).  Returns {"predict_property": [B, 1], "distance": [B, k] fp32 -- the square root of
+        the score --, "neighbor_id": [B, k] int64, "neighbor_size": [B, k] int32 (atoms of the neighbour), "parts": [B, k, 4] (mean f,
+        mean g, max f, max g, squared), "matched_atom": [B, M, k] int32 -- the atom of the neighbour that query atom i matches, its index within that
+        structure -- and "matched_distance": [B, M, k] fp32 = sqrt(f_i)}, -1 / 0 at padded atoms; a ``PackedBatch`` gives packed
+        [n_atom, k] arrays.  Places without a neighbour hold distance inf, id -1, size 0, matched_atom -1.  Raw y.  ``batch_size``
+        structures at a time (default: hyper.batch_size).  A structure-level index, an index of another model, a bad k, measure,
+        batch_size or exclude_ids length, or a structure of more than _hip.MATCH_MAX_ATOMS atoms raise ValueError before anything is
+        uploaded."""
+        k, ms = _hip.check_knn_k(k), _hip.check_match_measure(measure)
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        index.check_model(self)
+        if index.level != "atom":
+            raise ValueError("match_structures compares structures atom by atom: it needs an atom-level index, got a %s-level one" % index.level)
+        self._batch_size(batch_size)
+        is_packed = isinstance(inputs, _hip.PackedBatch)
+        B = inputs.n_struct if is_packed else int(np.shape(inputs["neighbors"])[0])
+        n_at = np.diff(inputs.mol_offset) if is_packed else (np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0).sum(1)
+        big = np.nonzero(n_at > _hip.MATCH_MAX_ATOMS)[0]
+        if big.size:
+            raise ValueError("structure %d has %d atoms, more than the %d a query structure may have" % (
+                big[0], int(n_at[big[0]]), _hip.MATCH_MAX_ATOMS))
+        qid = None
+        if exclude_ids is not None:
+            qid = np.ascontiguousarray(exclude_ids, dtype=np.int64).reshape(-1)
+            if qid.shape[0] != B:
+                raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
+        eng = self.engine
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_match_batch(
+            index._ix, rb, k, ms, None if qid is None else qid[s0:s1]))
+        empty = {"y": np.zeros(0, np.float32), "score": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
+                 "size": np.zeros((0, k), np.int32), "parts": np.zeros((0, k, 4), np.float32),
+                 "match_position": np.zeros((0, k), np.int32), "match_dist2": np.zeros((0, k), np.float32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        _, atoms = eng.index_names(index._ix)  # (host copies: the rows stay on the device)
+        pos = cat["match_position"]
+        matched = np.where(pos >= 0, atoms[np.maximum(pos, 0)] if len(atoms) else -1, -1).astype(np.int32)
+        out = {"predict_property": cat["y"].reshape(-1, 1), "distance": np.sqrt(cat["score"]),  # (correctly rounded on the host, as nearest)
+               "neighbor_id": cat["id"], "neighbor_size": cat["size"], "parts": cat["parts"], "matched_atom": matched,
+               "matched_distance": np.sqrt(cat["match_dist2"])}
+        if not is_packed:
+            out["matched_atom"] = _hip.repad_atoms(out["matched_atom"], inputs["atom_mask"], -1)
+            out["matched_distance"] = _hip.repad_atoms(out["matched_distance"], inputs["atom_mask"], 0)
+        return out
+
     def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
         """Which ``m`` structures (or atoms, ``level`` "atom") of ``pool`` to label next: greedy k-center selection in the model's latent
         space (``LatentIndex.select``; the core-set rule of Sener & Savarese, ICLR 2018), farthest first from everything in ``reference``
@@ -985,6 +1037,13 @@ class SCANN:
         """HipModel.nearest with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
         live in latent space and stay as they are."""
         out = self.model.nearest(ip, index, k=k, exclude_ids=exclude_ids, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
+
+    def match_structures(self, ip, index, k=5, measure="chamfer", exclude_ids=None, batch_size=None):
+        """HipModel.match_structures with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
+        distances live in latent space and stay as they are."""
+        out = self.model.match_structures(ip, index, k=k, measure=measure, exclude_ids=exclude_ids, batch_size=batch_size)
         out["predict_property"] = out["predict_property"] * self.std + self.mean
         return out
 
