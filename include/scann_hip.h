@@ -321,6 +321,44 @@ double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag,
 #define SCANN_ABLATE_MAX_ATOMS 960 /* atoms per structure: 32 score rows of the structure live in one workgroup's 160 KiB of LDS */
 int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, float* y, float* ga, float* y_abl, int32_t* order);
 
+/* ---- Shapley values of the atoms for the global pooling, sampled ----
+ * The game: the players are the n real atoms of one structure, v(S) is the prediction with the atoms outside S left out of the
+ * GlobalAttention pooling and everything upstream unchanged -- for |S| >= 2 exactly scann_ablate_pooling's y(S).  With use_ga_norm the
+ * reference's pooling over one atom or none is 0 / 0, and every walk starts there, so for |S| <= 1 the game uses the arithmetic of
+ * use_ga_norm = false whatever the model's setting, the continuous extension: a softmax over one kept atom is 1 for any finite logit, so
+ * v({i}) = head(k_i), and the empty pooling has rep = 0, so v(empty) = head(0), the baseline.  (The full set keeps the forward's
+ * arithmetic: a ONE-atom structure under use_ga_norm has v(all) = y = NaN, and its Shapley value and stderr are NaN.  A NaN arising at
+ * |S| >= 2 propagates into that structure's outputs as it is.  scann_ablate_pooling keeps returning the reference's NaN.)
+ * This call runs one forward of the resident batch, then n_perm walks per structure from the forward's gq / gk.  Walk p of structure s adds
+ * the atoms in the order pi_p = scann_shapley_permutation(seed, keys[s], p, n) (keys NULL: all 0), or in the order of row p of perms_in
+ * ([n_perm * n_atom], structure-local atom indices at mol_offset[s] + position; every row a permutation of every structure, else
+ * SCANN_ERR_INVALID):
+ *   values[p][j] = v({pi_p(0..j)}) in fp32, j = 0 .. n - 1;  marginal of atom pi_p(j) = (double)values[p][j] - (double)(j ? values[p][j-1] : baseline)
+ *   shapley[i]   = the fp64 mean of atom i's marginals over p = 0 .. n_perm - 1, added in p order
+ *   stderr[i]    = sqrt(sum (m - mean)^2 / (n_perm - 1) / n_perm), two passes, same order; NaN when n_perm = 1
+ *   full         = the fp64 mean of values[p][n - 1];  sum_i shapley[i] = full - baseline up to fp64 rounding (efficiency)
+ * Outputs, any of them NULL: y [n_struct] and ga [n_atom], bitwise the forward's; shapley, stderr_out [n_atom]; baseline, full [n_struct];
+ * values [n_perm * n_atom] and perms_out [n_perm * n_atom] (entry j of walk p of structure s at p * n_atom + mol_offset[s] + j).  Raw
+ * outputs (before any target de-normalisation).  A structure's results depend on the structure, seed, its key and n_perm only -- not on
+ * its batch.  Synchronous.  n_perm < 1 is SCANN_ERR_INVALID; a structure of more than SCANN_ABLATE_MAX_ATOMS atoms, or scratch
+ * 2 * n_perm * n_atom * 4 bytes (or the batch's pair matrices, 4 * sum n^2 bytes) above 1 GiB, is SCANN_ERR_UNSUPPORTED; all returned
+ * before anything is launched.  SCANN_ERR_RANGE as from scann_batch_download.  Works on inference and training handles, at 128 / 8 and
+ * at generic widths, and changes neither weights, gradients, Adam state, step counter nor the selected outputs. */
+int scann_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, const int32_t* perms_in,
+                  float* y, float* ga, double* shapley, double* stderr_out, double* baseline, double* full, float* values, int32_t* perms_out);
+/* scann_shapley without outputs, timed between events: ms[0] the pair kernel, ms[1] the walks, ms[2] the reduction (milliseconds) */
+int scann_shapley_profile(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, float* ms);
+/* walk p of a structure of n atoms with key `key` (host; the kernels' definition): a Fisher-Yates shuffle, a function of (seed, key, p, n)
+ * only.  base = mix(mix(seed + G * (p + 1)) + G * (key + 1)), G = 0x9E3779B97F4A7C15, mix = the splitmix64 finaliser; out = 0 .. n - 1;
+ * for i = n - 1 down to 1: u = mix(base + G * (i + 1)) >> 32, k = (u * (i + 1)) >> 32 (multiply-high, 0 <= k <= i), swap out[i], out[k].
+ * Nothing is written for n <= 0, p < 0 or out NULL. */
+void scann_shapley_permutation(uint64_t seed, uint64_t key, int32_t p, int32_t n, int32_t* out);
+/* the reduction of scann_shapley on the host, bit for bit: values, perms [n_perm * n_atom] (n_atom = mol_offset[n_struct]) and baseline
+ * [n_struct] in; shapley, stderr_out [n_atom] and full [n_struct] out.  SCANN_ERR_INVALID for a NULL argument, n_perm < 1 or an entry
+ * of perms outside its structure. */
+int scann_shapley_reduce_host(const float* values, const int32_t* perms, const int32_t* mol_offset, int32_t n_struct, int32_t n_perm,
+                              const double* baseline, double* shapley, double* stderr_out, double* full);
+
 /* ---- attention rollout: a prediction traced through the LocalAttention layers ----
  * A GlobalAttention score belongs to an atom's local structure after n_attention rounds of message passing, not to the atom.  Attention
  * rollout (Abnar & Zuidema 2020) composes the layers' attention maps: for one structure of n atoms, packed edges in CSR order, and the

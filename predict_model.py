@@ -168,6 +168,21 @@ def main(args):
                 d["order"] = (np.cumsum(amask[i]) - 1)[d["order"]].astype(np.int32)
                 per.append(d)
         pickle.dump(per, open(os.path.join(args.trained_model, "contributions_{}.pickle".format(target)), "wb"))
+    if args.shapley:
+        print("Shapley values of the atoms for the global pooling: %d permutations, seed %d" % (args.shapley, args.shapley_seed))
+        per, at = [], 0
+        for b in range(len(data)):
+            inputs, _ = data[b]
+            nb = len(np.asarray(inputs["atom_mask"]))
+            # keys: the structure's position in the dataset, so that the batching changes nothing
+            r = scann.atom_shapley(inputs, permutations=args.shapley, seed=args.shapley_seed, keys=np.arange(at, at + nb))
+            at += nb
+            amask = np.asarray(inputs["atom_mask"]).reshape(r["shapley"].shape[:2]) != 0
+            for i in range(len(amask)):  # unpadded: one entry per real atom of the structure
+                d = {k: r[k][i][amask[i]][:, 0] for k in ("shapley", "stderr", "global_attention")}
+                d.update({k: float(r[k][i, 0]) for k in ("y", "baseline", "full")})
+                per.append(d)
+        pickle.dump(per, open(os.path.join(args.trained_model, "shapley_{}.pickle".format(target)), "wb"))
     if args.rollout:
         print("Attention rollout: residual %g, %s" % (args.rollout_residual, "head mean" if args.rollout_head < 0 else "head %d" % args.rollout_head))
         per = []
@@ -296,6 +311,10 @@ def parser():
     p.add_argument("--contributions", type=str, default="", choices=["", "leave_one_out", "deletion", "insertion"],
                    help="also pickle per-atom contributions (the prediction with atoms left out of the global pooling) as "
                         "contributions_<target>.pickle: one dict per structure, unpadded, in the units of the target")
+    p.add_argument("--shapley", type=int, default=0,
+                   help="permutations per structure (0: none) for sampled Shapley values of the atoms for the global pooling: pickles "
+                        "shapley_<target>.pickle, one dict per structure, unpadded, in the units of the target")
+    p.add_argument("--shapley-seed", type=int, default=0, help="seed of the Shapley permutations")
     p.add_argument("--rollout", action="store_true",
                    help="also pickle the attention rollout (the GA scores traced back to the atoms through the local-attention layers) "
                         "as rollout_<target>.pickle: one dict per structure, unpadded (attribution [n], rollout [n, n])")

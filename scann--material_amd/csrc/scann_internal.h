@@ -42,6 +42,27 @@ __host__ __device__ inline unsigned long long mc_mix(unsigned long long z) {  //
 __host__ __device__ inline unsigned long long mc_seed(unsigned long long seed, unsigned t, unsigned long long key) {
   return mc_mix(mc_mix(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)t + 1)) + 0x9E3779B97F4A7C15ull * (key + 1));
 }
+// Shapley sampling (scann_shapley): permutation p of a structure of n atoms with key key_s, a function of (seed, key_s, p, n) only.
+//   base = mc_seed(seed, p, key_s);  out = 0, 1, .., n - 1;
+//   for i = n - 1 down to 1:  u = mc_mix(base + 0x9E3779B97F4A7C15 * (i + 1)) >> 32        (a 32-bit draw per step, counter-based)
+//                             k = (u * (i + 1)) >> 32                                      (multiply-high range reduction: 0 <= k <= i)
+//                             swap out[i], out[k]
+// out[j] = the structure-local atom added at position j of the walk.  (The draw of a step does not depend on the swaps before it, so a
+// kernel may form all draws in parallel and leave the swaps to one thread: shapley_draw is the draw, the swaps are the loop below.)
+__host__ __device__ inline unsigned shapley_draw(unsigned long long base, int i) {  // k of step i
+  const unsigned long long u = mc_mix(base + 0x9E3779B97F4A7C15ull * ((unsigned long long)i + 1)) >> 32;
+  return (unsigned)((u * ((unsigned long long)i + 1)) >> 32);
+}
+__host__ __device__ inline void shapley_permutation(unsigned long long seed, unsigned long long key, int p, int n, int32_t* out) {
+  const unsigned long long base = mc_seed(seed, (unsigned)p, key);
+  for (int i = 0; i < n; ++i) out[i] = i;
+  for (int i = n - 1; i >= 1; --i) {
+    const int k = (int)shapley_draw(base, i);
+    const int32_t t = out[i];
+    out[i] = out[k];
+    out[k] = t;
+  }
+}
 // per atom of an MC batch (launch_mc_rows): the first atom and the first edge of its structure, the structure's key
 struct McRow {
   int32_t a0, e0;
@@ -378,6 +399,32 @@ struct AblateArgs {
 };
 size_t ablate_lds_bytes(int max_atoms, int dg);  // dynamic LDS of a launch whose largest structure has max_atoms atoms
 hipError_t launch_ablate(const AblateArgs& a, bool mfma, hipStream_t s);
+
+// scann_shapley.hip (scann_shapley): Shapley sampling of the pooling game -- the pair matrix of every structure once, the prefix values of
+// n_perm walks per structure, then the fp64 reduction.  LDS of the walk: ablate_lds_bytes (the same layout)
+struct ShapleyArgs {
+  const int32_t* mol_offset;  // [n_struct+1]
+  int32_t n_struct, n_atom, max_atoms, n_perm;
+  const float *gq, *gk;       // [n_atom, dg] of the batch's last forward
+  int32_t dg, dout;           // global_dim, dense_out (128 / 128 on the MFMA kernel)
+  int32_t use_ga_norm, relu_out;
+  const float *Wb, *bb, *wo, *bo;  // bf_property [dg, dout], [dout]; predict_property [dout], [1]
+  unsigned long long seed;
+  const unsigned long long* keys;  // [n_struct] or null (all 0)
+  const int32_t* perms_in;    // [n_perm][n_atom] explicit walks (validated on the host), or null: sampled
+  const int64_t* pair_offset; // [n_struct] first float of each structure's n x n pair matrix
+  float* pair;                // pair[pair_offset[s] + c * n + i] = k_i . q_c, 0 for c == i
+  float* values;              // [n_perm][n_atom] v of the first j + 1 atoms of walk p at p * n_atom + mol_offset[s] + j
+  int32_t* perms;             // [n_perm][n_atom] the walks: structure-local atom by position
+  double *shapley, *stderr_out;  // [n_atom]
+  double *baseline, *full;    // [n_struct]
+};
+constexpr int SHAPLEY_PCHUNK = 4;  // walks per workgroup of shapley_walk_kernel (no result depends on it)
+// ev: null, or four events recorded before the pair kernel, behind it, behind the walks and behind the reduction (scann_shapley_profile)
+hipError_t launch_shapley(const ShapleyArgs& a, bool mfma, hipStream_t s, hipEvent_t* ev = nullptr);
+// fp64 reduction of walks (the host twin of shapley_reduce_kernel; scann_shapley_reduce_host)
+void shapley_reduce_host(const float* values, const int32_t* perms, const int32_t* mol_offset, int n_struct, int n_perm, const double* baseline,
+                         double* shapley, double* stderr_out, double* full);
 
 // scann_rollout.hip (scann_attention_rollout): the first `depth` attention maps of one forward composed per structure
 struct RolloutArgs {

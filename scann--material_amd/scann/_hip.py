@@ -115,6 +115,10 @@ SYMBOLS = [
     ("scann_predict_mc", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     ("scann_mc_drop_scale", C.c_double, [C.c_uint64, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float]),
     ("scann_ablate_pooling", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("scann_shapley", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_shapley_profile", C.c_int, [_P, _P, C.c_int32, C.c_uint64, _P, _P]),
+    ("scann_shapley_permutation", None, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _P]),
+    ("scann_shapley_reduce_host", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("scann_rollout_floats", C.c_int64, [_P, _P]),
     ("scann_attention_rollout", C.c_int, [_P, _P, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("scann_index_create", C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
@@ -524,6 +528,32 @@ def _ptr(a):
     return a.ctypes.data if a is not None else None  # plain address: c_void_p argtypes / fields take ints
 
 
+def shapley_permutation(seed, key, p, n):
+    """Walk p of a structure of n atoms with key ``key`` as scann_shapley samples it (scann_shapley_permutation): int32 [n], the
+    structure-local atom by position."""
+    out = np.empty(max(int(n), 0), np.int32)
+    load_library().scann_shapley_permutation(int(seed) & 0xFFFFFFFFFFFFFFFF, int(key) & 0xFFFFFFFFFFFFFFFF, int(p), int(n), _ptr(out))
+    return out
+
+
+def shapley_reduce_host(values, perms, mol_offset, baseline):
+    """The reduction of scann_shapley on the host, bit for bit (scann_shapley_reduce_host): values, perms [P, n_atom], mol_offset
+    [n_struct + 1], baseline [n_struct] -> (shapley [n_atom], stderr [n_atom], full [n_struct]), float64."""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    perms = np.ascontiguousarray(perms, dtype=np.int32)
+    mol = np.ascontiguousarray(mol_offset, dtype=np.int32)
+    base = np.ascontiguousarray(baseline, dtype=np.float64)
+    B, A = mol.shape[0] - 1, int(mol[-1])
+    if values.ndim != 2 or values.shape != perms.shape or values.shape[1] != A or base.shape != (B,):
+        raise ValueError("values / perms must be [P, %d] and baseline [%d]" % (A, B))
+    sh, se, full = np.empty(A, np.float64), np.empty(A, np.float64), np.empty(B, np.float64)
+    lib = load_library()
+    r = lib.scann_shapley_reduce_host(_ptr(values), _ptr(perms), _ptr(mol), B, values.shape[0], _ptr(base), _ptr(sh), _ptr(se), _ptr(full))
+    if r != 0:
+        raise ScannHipError(r, (lib.scann_last_error(None) or b"").decode())
+    return sh, se, full
+
+
 class PackedBatch:
     """Host-side packed (CSR) batch: the arrays scann_batch_t points at."""
 
@@ -703,13 +733,14 @@ def repad_edges(x, atom_mask, neighbor_mask):
     return out
 
 
-def repad_atoms(x, atom_mask, fill=0):
+def repad_atoms(x, atom_mask, fill=0, dtype=None):
     """Packed per-atom values [n_atom] or rows [n_atom, F] -> [B, M] / [B, M, F] with ``fill`` (default: zero) at padded atoms.
-    THE packed-to-padded routine of per-atom results; integers keep their dtype, everything else comes back as float32."""
+    THE packed-to-padded routine of per-atom results; integers keep their dtype, everything else comes back as float32 (``dtype``:
+    that one instead, e.g. float64 for fp64 reductions)."""
     amask = np.asarray(atom_mask)
     amask = amask.reshape(amask.shape[:2]) != 0
     x = np.asarray(x)
-    out = np.full(amask.shape + x.shape[1:], fill, dtype=x.dtype if x.dtype.kind in "iu" else np.float32)
+    out = np.full(amask.shape + x.shape[1:], fill, dtype=dtype or (x.dtype if x.dtype.kind in "iu" else np.float32))
     out[amask] = x
     return out
 
@@ -1053,6 +1084,44 @@ class Engine:
         self._check(self.lib.scann_ablate_pooling(self._h, rb._h, ABLATE_MODES[mode], _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["ablated"]),
                                                   _ptr(out["order"])))
         return out
+
+    def shapley(self, rb, permutations, seed=0, keys=None, perms=None, want_values=False):
+        """One forward of a resident batch and the sampled Shapley values of its atoms for the global pooling (scann_shapley; raw y):
+        {"y" [n_struct], "ga" [n_atom], "shapley", "stderr" [n_atom] float64, "baseline", "full" [n_struct] float64} and, with
+        ``want_values``, "values" [permutations, n_atom] float32 (the prediction on the first j + 1 atoms of walk p of a structure at
+        [p, atom offset + j]) and "perms" [permutations, n_atom] int32 (the walks: structure-local atom by position).  ``keys``: one
+        uint64 per structure (None: all 0).  ``perms``: explicit walks [permutations, n_atom] instead of sampled ones."""
+        p = rb.packed
+        B, A, P = p.n_struct, p.n_atom, int(permutations)
+        k = None
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys).astype(np.uint64).reshape(-1))
+            if k.shape[0] != B:
+                raise ValueError("keys: %d values for %d structures" % (k.shape[0], B))
+        pin = None
+        if perms is not None:
+            pin = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+            if pin.shape != (max(P, 0), A):
+                raise ValueError("perms: shape %r, expected (%d, %d)" % (pin.shape, P, A))
+        out = {"y": np.empty(B, np.float32), "ga": np.empty(A, np.float32), "shapley": np.empty(A, np.float64),
+               "stderr": np.empty(A, np.float64), "baseline": np.empty(B, np.float64), "full": np.empty(B, np.float64)}
+        if want_values:
+            out["values"] = np.empty((max(P, 0), A), np.float32)
+            out["perms"] = np.empty((max(P, 0), A), np.int32)
+        self._check(self.lib.scann_shapley(self._h, rb._h, P, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(k), _ptr(pin), _ptr(out["y"]), _ptr(out["ga"]),
+                                           _ptr(out["shapley"]), _ptr(out["stderr"]), _ptr(out["baseline"]), _ptr(out["full"]),
+                                           _ptr(out.get("values")), _ptr(out.get("perms"))))
+        return out
+
+    def shapley_profile(self, rb, permutations, seed=0, keys=None):
+        """scann_shapley without outputs, timed between events (scann_shapley_profile): milliseconds of (the pair kernel, the walks, the
+        reduction)."""
+        k = None if keys is None else np.ascontiguousarray(np.asarray(keys).astype(np.uint64).reshape(-1))
+        if k is not None and k.shape[0] != rb.packed.n_struct:
+            raise ValueError("keys: %d values for %d structures" % (k.shape[0], rb.packed.n_struct))
+        ms = np.zeros(3, np.float32)
+        self._check(self.lib.scann_shapley_profile(self._h, rb._h, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(k), _ptr(ms)))
+        return tuple(float(v) for v in ms)
 
     def attention_rollout(self, rb, residual=0.5, head=None, depth=None, matrix=True):
         """One forward of a resident batch and its attention rollout (scann_attention_rollout; raw y): the first ``depth`` layers' attention

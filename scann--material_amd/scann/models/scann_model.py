@@ -256,6 +256,46 @@ class HipModel:
             out["contribution"] = np.where(amask[..., None], y[:, None, :] - out["ablated"], np.float32(0)).astype(np.float32)
         return out
 
+    def atom_shapley(self, inputs, permutations=64, seed=0, keys=None, batch_size=None):
+        """Shapley values of a structure's atoms for the GlobalAttention pooling, sampled on the GPU: the raw prediction split fairly
+        among the atoms.  The game: v(S) is the prediction with the atoms outside S left out of the pooling and everything upstream
+        unchanged (``atom_contributions``' kept sets); an atom's Shapley value is its marginal v(S + i) - v(S) averaged over the orders in
+        which atoms can be added, here over ``permutations`` random orders per structure, all from one forward.  For |S| <= 1, where the
+        reference's use_ga_norm arithmetic is 0 / 0, the game uses that of use_ga_norm = false (the continuous extension: one kept atom
+        pools to its own row, none to 0), so ``baseline`` = v(nothing) is the head on a zero representation.  Efficiency: a structure's
+        values sum to ``full - baseline``, ``full`` being the mean of v(all atoms) over the walks (y in another summation order).
+        ``stderr``: the standard error of each value over the walks (NaN for one walk).  The walks of a structure depend on ``seed``,
+        its key and its atom count only (``keys``: one integer per structure, default its position in ``inputs``), so ``batch_size``
+        changes no bit.  ``inputs``: a padded dict.  Returns float64 {"y": [B, 1], "global_attention": [B, M, 1], "shapley": [B, M, 1],
+        "stderr": [B, M, 1], "baseline": [B, 1], "full": [B, 1]}, 0 at padding.  A one-atom structure under use_ga_norm has y = NaN, and
+        NaN values.  Bad arguments raise ValueError before anything is uploaded."""
+        try:
+            P, sd = int(permutations), int(seed)
+        except (TypeError, ValueError):
+            raise ValueError("permutations and seed must be integers, got %r and %r" % (permutations, seed))
+        if P != permutations or P < 1:
+            raise ValueError("permutations must be an integer >= 1, got %r" % (permutations,))
+        if sd != seed or sd < 0:
+            raise ValueError("seed must be a non-negative integer, got %r" % (seed,))
+        B = int(np.shape(inputs["neighbors"])[0])
+        if keys is None:
+            keys = np.arange(B, dtype=np.uint64)
+        else:
+            keys = np.asarray(keys).reshape(-1)
+            if keys.shape[0] != B:
+                raise ValueError("keys: %d values for %d structures" % (keys.shape[0], B))
+            if not np.issubdtype(keys.dtype, np.integer) or (keys.size and int(keys.min()) < 0):
+                raise ValueError("keys must be non-negative integers")
+            keys = keys.astype(np.uint64)
+        eng = self.engine
+        amask = np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.shapley(rb, P, seed=sd, keys=keys[s0:s1]))
+        cat = {k: np.concatenate([p[k] for p in parts]) for k in ("y", "ga", "shapley", "stderr", "baseline", "full")}
+        out = {k: cat[k].astype(np.float64).reshape(-1, 1) for k in ("y", "baseline", "full")}
+        for name, k in (("global_attention", "ga"), ("shapley", "shapley"), ("stderr", "stderr")):
+            out[name] = _hip.repad_atoms(cat[k], amask, dtype=np.float64)[..., None]
+        return out
+
     def attention_rollout(self, inputs, residual=0.5, head=None, depth=None, matrix=True, batch_size=None):
         """Which atoms a structure's prediction traces back to through the LocalAttention layers: attention rollout (Abnar & Zuidema
         2020).  A GlobalAttention score belongs to an atom's local structure after n_attention rounds of message passing; the rollout
@@ -1020,6 +1060,16 @@ class SCANN:
         out["ablated"] = np.where(real, out["ablated"] * self.std + self.mean, 0).astype(np.float32)
         if "contribution" in out:
             out["contribution"] = out["contribution"] * self.std
+        return out
+
+    def atom_shapley(self, ip, permutations=64, seed=0, keys=None, batch_size=None):
+        """HipModel.atom_shapley in the units of the target: ``shapley`` and ``stderr`` -- differences of predictions -- times std, ``y``,
+        ``baseline`` and ``full`` times std plus mean, as predict_data does."""
+        out = self.model.atom_shapley(ip, permutations=permutations, seed=seed, keys=keys, batch_size=batch_size)
+        for k in ("shapley", "stderr"):
+            out[k] = out[k] * self.std
+        for k in ("y", "baseline", "full"):
+            out[k] = out[k] * self.std + self.mean
         return out
 
     def attention_rollout(self, ip, residual=0.5, head=None, depth=None, matrix=True, batch_size=None):
