@@ -1,5 +1,6 @@
 """Seeded batches on the large side of the launch code's size switches, shared by tests/test_sizes_host.py (which pins that they
-cross what they are meant to cross) and tests/test_gpu_sizes.py (which compares the kernels on them with references).
+cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py and tests/test_gpu_parity.py (which compare
+the kernels on them with references).
 
 The launch code picks a template instantiation, tile height, partial-sum partition or reduction kernel by row count; the
 constants below restate those thresholds, each next to the source line it mirrors.  If a threshold moves, the host test fails
@@ -136,6 +137,47 @@ def giant_data(n_atoms):
     return de3, dn3
 
 
+def hub_structure(rng, n_atoms, degrees):
+    """one structure of `n_atoms` atoms in which atom a has degrees[a] neighbours and every other atom 0 to 8:
+    ([atomic numbers, target], neighbour lists)"""
+    nb = []
+    for a in range(n_atoms):
+        d = degrees.get(a, int(rng.integers(0, 9)))
+        js = rng.choice(np.delete(np.arange(n_atoms), a), d, replace=False)
+        ang = rng.uniform(0.4, 3.5, size=d)
+        nb.append([[6, int(j), float(ang[k]), float(ang[k] / ang.max()), float(rng.uniform(0.9, 4.0))] for k, j in enumerate(js)])
+    return [[int(z) for z in rng.choice([1, 6, 7, 8], n_atoms)], 0.0], nb
+
+
+def flanked(big, flank):
+    """the structure `big` in the middle of the molecules of the dataset `flank`"""
+    de, dn = flank
+    n, mid = len(de), len(de) // 2
+    de2, dn2 = np.empty(n + 1, dtype=object), np.empty(n + 1, dtype=object)
+    for i in range(n):
+        de2[i + (i >= mid)], dn2[i + (i >= mid)] = de[i], dn[i]
+    de2[mid], dn2[mid] = big
+    return de2, dn2
+
+
+CHUNKED_DEGREES = {0: 219, 1: 65, 7: 128, 8: 129, 9: 64, 100: 200, 219: 70}  # six atoms above 64 (chunk tiles), one at 64
+DEG40_DEGREES = {5: 40, 30: EDGE_TILE_32_MAX_DEGREE + 1}                     # nothing above 64: no chunk tiles
+
+
+@functools.lru_cache(maxsize=None)
+def chunked_data():
+    """a 220-atom structure whose atoms 0, 1, 7, 8, 100 and 219 have 65 to 219 neighbours -- chunk tiles, merged by
+    edge_merge_kernel, on 64-row edge tiles -- between two small molecules"""
+    return flanked(hub_structure(np.random.default_rng(11), 220, CHUNKED_DEGREES), so.synth_dataset(2, 3))
+
+
+@functools.lru_cache(maxsize=None)
+def deg40_data():
+    """a 48-atom structure with one atom of 40 neighbours and one of exactly 33 -- more than EDGE_TILE_32_MAX_DEGREE: a few hundred
+    edges on 64-row edge tiles, no chunk tiles -- in the middle of six QM9-like molecules"""
+    return flanked(hub_structure(np.random.default_rng(40), 48, DEG40_DEGREES), so.synth_dataset(6, 3))
+
+
 # ---- batches: (PackedBatch, targets) ----
 
 def padded(data, g_update=True):
@@ -164,6 +206,14 @@ def sparse_atoms(g_update=True):
 
 def giant(n_atoms, g_update=True):
     return packed(giant_data(n_atoms), g_update)
+
+
+def chunked(g_update=True):
+    return packed(chunked_data(), g_update)
+
+
+def deg40(g_update=True):
+    return packed(deg40_data(), g_update)
 
 
 def upload_tile_rows(pk):

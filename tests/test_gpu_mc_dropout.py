@@ -47,6 +47,8 @@ CASES = {
     "cgcnn": dict(feature="cgcnn"),
     "e_b": dict(target="e_b"),
     "64x4": dict(widths=dict(local_dim=64, num_head=4, global_dim=96, dense_out=32), use_drop=True),
+    # embedding rate 0: the MC fused-basis edge kernel reads the first layer from the per-species tables (tests/test_gpu_mc_sizes.py: 64 rows)
+    "tables_attn_only": dict(use_drop=True, p_drop=0.0),
 }
 
 
@@ -54,20 +56,22 @@ CASES = {
 def test_every_sample_matches_the_oracle(hip_lib, monkeypatch, case):
     import torch_ref
 
-    cfg, w, _, pk, model = setup(**CASES[case])
+    kw = dict(CASES[case])
+    p_drop = kw.pop("p_drop", 0.1)
+    cfg, w, _, pk, model = setup(**kw)
     T, seed = 3, 11
     keys = (np.arange(pk.n_struct) * 7 + 1).astype(np.uint64)
     p_attn = 0.05 if cfg["model"].get("use_drop") else 0.0
     rb = model.engine.upload(pk)
-    r = model.engine.predict_mc(rb, T, seed=seed, keys=keys, p_drop=0.1, p_attn=p_attn, want_samples=True)
+    r = model.engine.predict_mc(rb, T, seed=seed, keys=keys, p_drop=p_drop, p_attn=p_attn, want_samples=True)
     rb.free()
     ys = r["y_samples"]
     assert ys.shape == (T, pk.n_struct)
     ga64s = []
     for t in range(T):
-        y64, ga64 = mc_ref.sample_ref(cfg, w, pk, seed, t, keys, 0.1, p_attn, monkeypatch)
+        y64, ga64 = mc_ref.sample_ref(cfg, w, pk, seed, t, keys, p_drop, p_attn, monkeypatch)
         monkeypatch.setattr(torch_ref, "drop_scale_np", mc_ref.local_drop_twin(pk, t, keys, cfg["model"]["local_dim"]))
-        y32 = np.asarray(torch_ref.forward_packed(cfg, w, pk, "float32", drop=(seed, 0.1),
+        y32 = np.asarray(torch_ref.forward_packed(cfg, w, pk, "float32", drop=(seed, p_drop) if p_drop > 0 else None,
                                                   attn_scale=mc_ref.attn_scales(pk, seed, t, keys, cfg["model"]["num_head"],
                                                                                 cfg["model"]["n_attention"], p_attn))[0]).ravel()
         assert rel_err(ys[t], y64) <= max(RTOL, 2 * rel_err(y32, y64)), (t, rel_err(ys[t], y64), rel_err(y32, y64))

@@ -536,24 +536,11 @@ def test_degenerate_batches(hip_lib):
 def test_more_than_64_neighbours(hip_lib, g_update):
     """Atoms with 65 ... 219 neighbours (chunk tiles + softmax merge), between ordinary atoms and next to small molecules,
     on BOTH branches of LocalAttention (one edge-kernel family: attention.py:141-155)."""
+    import size_batches
     from scann import _hip
 
     cfg, w, _, model = make(n=2, model=dict(g_update=g_update))
-    rng = np.random.default_rng(11)
-    A = 220
-    degs = {0: 219, 1: 65, 7: 128, 8: 129, 9: 64, 100: 200, 219: 70}
-    nb = []
-    for a in range(A):
-        d = degs.get(a, int(rng.integers(0, 9)))
-        js = rng.choice(np.delete(np.arange(A), a), d, replace=False)
-        ang = rng.uniform(0.4, 3.5, size=d)
-        nb.append([[6, int(j), float(ang[k]), float(ang[k] / ang.max()), float(rng.uniform(0.9, 4.0))] for k, j in enumerate(js)])
-    de, dn = so.synth_dataset(2, 3)
-    de3, dn3 = np.empty(3, dtype=object), np.empty(3, dtype=object)
-    de3[0], dn3[0] = de[0], dn[0]
-    de3[1], dn3[1] = [[int(z) for z in rng.choice([1, 6, 7, 8], A)], 0.0], nb
-    de3[2], dn3[2] = de[1], dn[1]
-    inputs, _ = so.pad_batch(de3, dn3, g_update)
+    inputs, _ = size_batches.padded(size_batches.chunked_data(), g_update)  # (degrees 219, 65, 128, 129, 64, 200, 70 in 220 atoms)
     y, ga = model.predict(inputs)
     y_ref, ga_ref = so.forward(cfg, w, inputs, np.float32)
     assert rel_err(y, y_ref) <= RTOL and rel_err(ga, ga_ref) <= RTOL

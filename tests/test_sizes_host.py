@@ -65,6 +65,43 @@ def test_size_batches_cross_their_thresholds(hip_lib, name):
         assert sb.wgrad_chunks(pk.n_edge) > 4 and pk.n_edge % (64 * sb.wgrad_chunks(pk.n_edge)) != 0  # the last chunk is partial
 
 
+@pytest.mark.parametrize("g_update", [True, False])
+def test_deg40_is_on_64_row_edge_tiles_by_its_degree_alone(hip_lib, g_update):
+    """few edges, no chunk tiles: only `max_degree > 32` sends it to 64-row tiles -- and each part of it alone is where
+    tests/test_gpu_mc_sizes.py expects it (the flanking molecules on 32 rows, the structure itself on 64)"""
+    from scann.parallel import slice_packed
+
+    pk, targets = sb.deg40(g_update)
+    deg = np.diff(pk.edge_offset)
+    mid = pk.n_struct // 2
+    a0, a1 = int(pk.mol_offset[mid]), int(pk.mol_offset[mid + 1])
+    assert pk.n_struct == 7 and len(targets) == 7 and a1 - a0 == 48
+    assert 0 < pk.n_edge <= 2048 < sb.EDGE_TILE_32_MAX_EDGES and pk.n_atom <= sb.ATOM_TILE_32_MAX
+    assert sorted(deg[a0:a1])[-2:] == [sb.EDGE_TILE_32_MAX_DEGREE + 1, 40] and sorted(deg[a0:a1])[-3] <= 8
+    assert max(deg[:a0].max(), deg[a1:].max()) <= 12
+    assert sb.upload_tile_rows(pk) == (64, 0)
+    assert sb.upload_tile_rows(slice_packed(pk, 0, mid)) == (32, 0) and sb.upload_tile_rows(slice_packed(pk, mid + 1, pk.n_struct)) == (32, 0)
+    assert sb.upload_tile_rows(slice_packed(pk, mid, mid + 1)) == (64, 0)
+
+
+@pytest.mark.parametrize("g_update", [True, False])
+def test_chunked_has_chunk_tiles(hip_lib, g_update):
+    """six atoms above 64 neighbours: chunk tiles (part >= 0) on 64-row tiles, in the batch and in the structure alone"""
+    from scann.parallel import slice_packed
+
+    pk, targets = sb.chunked(g_update)
+    deg = np.diff(pk.edge_offset)
+    a0 = int(pk.mol_offset[1])
+    assert pk.n_struct == 3 and len(targets) == 3 and int(pk.mol_offset[2]) - a0 == 220
+    assert {a: int(deg[a0 + a]) for a in sb.CHUNKED_DEGREES} == sb.CHUNKED_DEGREES
+    assert int((deg > 64).sum()) == 6 and pk.n_edge <= sb.EDGE_TILE_32_MAX_EDGES
+    rows, n_chunk = sb.upload_tile_rows(pk)
+    # 219, 65, 128, 129, 200, 70 neighbours in chunks of at most 64
+    assert rows == 64 and n_chunk == sum((d + 63) // 64 for d in sb.CHUNKED_DEGREES.values() if d > 64) == 17
+    assert sb.upload_tile_rows(slice_packed(pk, 0, 1)) == (32, 0) and sb.upload_tile_rows(slice_packed(pk, 2, 3)) == (32, 0)
+    assert sb.upload_tile_rows(slice_packed(pk, 1, 2)) == (64, n_chunk)
+
+
 @pytest.mark.parametrize("n", [sb.GEN_BWD_MAX_ATOMS, sb.GEN_BWD_MAX_ATOMS + 1, sb.UPLOAD_MAX_ATOMS, sb.UPLOAD_MAX_ATOMS + 1])
 def test_giant_structure_batches(hip_lib, n):
     pk, targets = sb.giant(n)
