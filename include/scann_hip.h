@@ -626,6 +626,60 @@ int scann_project_host(const float* rows, int64_t n, int64_t dim, const float* m
 int scann_sym_eig_host(const double* a, int64_t d, double* w, double* v, int32_t* sweeps);
 int scann_pca_bits(int64_t n);  /* b for n eligible rows, 0 <= n < 2^31; SCANN_ERR_INVALID otherwise */
 
+/* ---- a readout head for another property, fitted on an index: ridge regression with exact leave-one-out residuals ----
+ * The linear probe of transfer learning: K new targets regressed on the frozen rows of an index, the ridge strength chosen by
+ * leave-one-out without a refit (r_i = e_i / (1 - h_i) with the leverage h_i), and the predictive standard deviation
+ * sqrt(sigma^2 (1 + leverage)) of Bayesian linear regression as an uncertainty.  Everything is defined so that it depends on the index
+ * contents and the targets only, bit for bit.
+ * Inputs: a pool of N rows of dim columns and host targets t [N * K] fp32, 1 <= K <= SCANN_HEAD_MAX_TARGETS.  A row counts if and only if
+ * all its dim components and all its K targets are finite -- a NaN target means "unlabelled"; n is the number of rows that count.
+ * Augmented moments (scann_index_fit_moments): exactly the definition of scann_index_moments applied to the N x (dim + K) matrix
+ * [rows | t] -- the same eligibility (over all dim + K columns), column exponents, b = scann_pca_bits(n), int64 sums and fp64 covariance
+ * expression.  Outputs: n_eligible, mean [dim + K], cov [(dim + K)^2] fp64, col_exp [dim + K] (or NULL), bits (or NULL).  Its twin is
+ * scann_moments_host on the augmented matrix.  Fewer than 2 rows that count are SCANN_ERR_INVALID as there (n_eligible is written).
+ * Leave-one-out pass (scann_index_ridge_loo).  Inputs, all fp32 and finite: mean [dim], tmean [K], components V [m * dim] (row c one
+ * vector, 1 <= m <= dim), scales S [L * m], coefficients B [L * K * m], lev0, 1 <= L <= SCANN_HEAD_MAX_LAMBDA, and resid_l [K] with
+ * entries in -1 .. L - 1, or NULL.  For each row p that counts, in fp32, every operation rounded once and none contracted beyond the
+ * stated fmaf:
+ *   y_j  = x_j - mean_j;
+ *   z_c  = the chain of scann_index_project: acc = fmaf(y_j, V[c][j], acc), j ascending from 0;
+ *   t_lc = z_c * S[l][c];   a_l = the chain acc = fmaf(t_lc, t_lc, acc), c ascending from 0 (scann_index_project's md2 with scale S[l]);
+ *   lev_l = lev0 + a_l;
+ *   p_lk = the chain acc = fmaf(z_c, B[l][k][c], acc), c ascending from 0;
+ *   d_k  = t_k - tmean_k;   e_lk = d_k - p_lk;
+ *   r_lk = (float)((double)e_lk / (1.0 - (double)lev_l)) if lev_l < 1, else +inf (a NaN leverage gives +inf).
+ * Sums, fp64: block g is positions 128 g .. 128 g + 127; within a block acc += term with the position ascending, rows that do not count
+ * skipped; then the block sums are added with g ascending.  The block is part of the definition; launch geometry and storage chunks are
+ * not.  sse [L * K]: (double)r * (double)r; sae [L * K]: fabs((double)r); sse_fit [L * K]: (double)e * (double)e; dof [L]: (double)lev_l;
+ * n_used: the rows that counted.  With resid_l, resid [N * K] fp32 holds r_{resid_l[k], k} for the rows that count, NaN for the others
+ * and NaN throughout column k where resid_l[k] = -1.
+ * The call is synchronous, one host wait; it changes nothing in the pool, the handle's weights, training state or selected outputs, runs
+ * no forward and works on inference and training handles at any width.  SCANN_ERR_INVALID before anything is launched, with a message
+ * that names the argument: a null argument, an index of another handle, K, L or m out of range, a non-finite mean, tmean, V, S, B or lev0,
+ * a resid_l entry out of range.  An empty pool returns zeros and n_used = 0.  The twin scann_ridge_loo_host (rows [n * dim], no GPU)
+ * gives the same bits, threaded over the blocks.
+ * Head evaluation (scann_head_batch): one inference forward of a resident batch with the level's output added for that forward only
+ * (y, ga, range guard, exact-fp32 re-run and selection restore exactly as scann_project_batch), and for every row of the level
+ *   pred_k = tmean_k + w_k, w_k the projection chain of y on W[k] (W [K * dim]);
+ *   lev_k  = lev0 + md2 with components V [m * dim] and scale S[k] (S [K * m]: every target has its own ridge strength);
+ * pred, lev [n * K]: the bits of scann_project_batch called with (mean, W) and with (mean, V, S[k]), plus one fp32 add each. */
+#define SCANN_HEAD_MAX_TARGETS 16
+#define SCANN_HEAD_MAX_LAMBDA 32
+int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, int64_t* n_eligible,
+                            float* mean /* [dim + K] */, double* cov /* [(dim + K)^2] */, int32_t* col_exp /* [dim + K] or NULL */,
+                            int32_t* bits /* or NULL */);
+int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, const float* mean,
+                          const float* tmean, const float* components, int32_t m, const float* scale /* [L * m] */,
+                          const float* coef /* [L * K * m] */, int32_t L, float lev0, const int32_t* resid_l /* [K] or NULL */, int64_t* n_used,
+                          double* sse /* [L * K] */, double* sae /* [L * K] */, double* sse_fit /* [L * K] */, double* dof /* [L] */,
+                          float* resid /* [N * K] or NULL */);
+int scann_ridge_loo_host(const float* rows, int64_t n, int64_t dim, const float* targets, int32_t K, const float* mean, const float* tmean,
+                         const float* components, int32_t m, const float* scale, const float* coef, int32_t L, float lev0,
+                         const int32_t* resid_l, int64_t* n_used, double* sse, double* sae, double* sse_fit, double* dof, float* resid);
+int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* tmean,
+                     const float* weights /* [K * dim] */, int32_t K, const float* components /* [m * dim] */, int32_t m,
+                     const float* scale /* [K * m] */, float lev0, float* y, float* ga, float* pred /* [n * K] */, float* lev /* [n * K] */);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -27,6 +27,12 @@ principal components of the model's latent space (mean and covariance on the GPU
 variance, pickles the result -- coordinates, Mahalanobis distance and distance to the mean per row, with the rows' dataset indices and
 atoms -- as ``projection_<target>.pickle`` and, with ``--project-out``, saves the map as a ``LatentProjection`` (.npz) that
 ``SCANN.project`` takes.
+``--fit-head TARGETS.npy [--head-level atom|structure] [--head-out FILE]`` fits a linear readout head for another property on the frozen
+latent space: ``TARGETS.npy`` holds [N] or [N, K] values (K <= 16, NaN: unlabelled), one row per structure of the dataset in dataset
+order, or per atom in packed order.  Ridge regression with the strength chosen by exact leave-one-out on the GPU; prints the
+leave-one-out table, pickles the result with the rows' dataset indices and atoms as ``head_<target>.pickle`` and, with ``--head-out``,
+saves the head as a ``LatentHead`` (.npz).  ``--head FILE`` evaluates a saved head over the dataset instead and pickles one unpadded dict
+per structure (prediction, std, leverage) as ``head_<target>.pickle``.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -103,6 +109,7 @@ def main(args):
         raise SystemExit("--cluster: K must lie in 1 .. 1024, got %d" % args.cluster)
     if args.cluster_iter < 0:
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
+    head_targets = check_head_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -263,6 +270,68 @@ def main(args):
         if args.project_out:
             projection.save(args.project_out)
         pool.free()
+    if head_targets is not None:
+        pool = scann.build_index(data, level=args.head_level, ids=data.indexes)
+        print("Fit a head for %d target(s) on the dataset's %d rows (%s level)" % (head_targets.shape[1], len(pool), args.head_level))
+        try:
+            res, head = scann.fit_head(pool, head_targets)
+        except ValueError as e:  # (the number of rows, too few labelled ones)
+            pool.free()
+            raise SystemExit("--fit-head: %s" % e) from None
+        res["id"], res["atom"] = pool.names()
+        print("n_rows %d" % res["n_rows"])
+        print("%-12s %12s %12s %12s %10s %12s %8s" % ("target", "l2", "loo_rmse", "loo_mae", "loo_r2", "fit_rmse", "dof"))
+        for k, name in enumerate(res["names"]):
+            print("%-12s %12.6g %12.6g %12.6g %10.6f %12.6g %8.2f" % (name, res["l2"][k], res["loo_rmse"][k], res["loo_mae"][k], res["loo_r2"][k],
+                                                                   res["fit_rmse"][k], res["dof"][k]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "head_{}.pickle".format(target)), "wb"))
+        if args.head_out:
+            head.save(args.head_out)
+        pool.free()
+    if args.head:
+        from scann.models import LatentHead
+
+        try:
+            head = LatentHead.load(scann.model, args.head)
+        except ValueError as e:
+            raise SystemExit("--head: %s" % e) from None
+        print("Evaluate the head of %s (%s level, %d targets: %s)" % (args.head, head.level, head.k, ", ".join(head.names)))
+        pickle.dump(head_records(scann, data, head), open(os.path.join(args.trained_model, "head_{}.pickle".format(target)), "wb"))
+
+
+def check_head_flags(args):
+    """--fit-head / --head checked before anything is loaded: the targets as fp32 [N, K], or None without --fit-head"""
+    if args.fit_head and args.head:
+        raise SystemExit("--fit-head and --head: fit a head or evaluate one, not both")
+    if args.head_out and not args.fit_head:
+        raise SystemExit("--head-out: needs --fit-head")
+    if args.head and not os.path.isfile(args.head):
+        raise SystemExit("--head: no such file: %s" % args.head)
+    if not args.fit_head:
+        return None
+    try:
+        t = np.load(args.fit_head, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise SystemExit("--fit-head: cannot read %s: %s" % (args.fit_head, e)) from None
+    if t.dtype.kind not in "fiu" or t.ndim not in (1, 2) or (t.ndim == 2 and not 1 <= t.shape[1] <= 16) or t.shape[0] < 3:
+        raise SystemExit("--fit-head: %s must hold numbers of shape [N] or [N, K], N >= 3, 1 <= K <= 16, got %s %s" % (args.fit_head, t.dtype, t.shape))
+    return np.ascontiguousarray(t.reshape(len(t), -1), dtype=np.float32)
+
+
+def head_records(scann, data, head):
+    """--head: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = head.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = scann.predict_head(inputs, head)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["y"][i, 0])}
+            for key in ("prediction", "std", "leverage"):
+                d[key] = r[key][i][amask[i]] if atom else r[key][i]
+            per.append(d)
+    return per
 
 
 def nearest_records(scann, data, index, k, exclude):
@@ -355,6 +424,14 @@ def parser():
     p.add_argument("--project-level", type=str, default="structure", choices=["atom", "structure"],
                    help="rows to map: one per structure (bf_property) or one per atom (after_Lc)")
     p.add_argument("--project-out", type=str, default="", help="save the map as a LatentProjection (.npz) for SCANN.project")
+    p.add_argument("--fit-head", type=str, default="",
+                   help="TARGETS.npy, [N] or [N, K] values of another property (NaN: unlabelled), one row per structure or atom of the dataset: "
+                        "fit a linear readout head on the latent space (ridge, exact leave-one-out on the GPU) and pickle head_<target>.pickle")
+    p.add_argument("--head-level", type=str, default="structure", choices=["atom", "structure"],
+                   help="rows to regress on: one per structure (bf_property) or one per atom (after_Lc)")
+    p.add_argument("--head-out", type=str, default="", help="save the fitted head as a LatentHead (.npz) for SCANN.predict_head")
+    p.add_argument("--head", type=str, default="",
+                   help="a saved LatentHead (.npz): pickle its prediction, standard deviation and leverage per structure as head_<target>.pickle")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

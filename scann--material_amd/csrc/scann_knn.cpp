@@ -15,21 +15,6 @@
 
 using namespace scann;
 
-struct scann_index {
-  scann_handle* h = nullptr;
-  int device = 0;
-  int32_t dim = 0, stride = 0;  // stride: dim rounded up to a multiple of 4, the rest zero
-  int32_t chunk_rows = 0;       // rows per chunk (a multiple of 64): about 64 MiB of rows
-  int64_t n = 0;
-  std::vector<char*> chunks;    // device blocks of the handle's cache: rows [chunk_rows][stride] fp32, then ids [chunk_rows] int64
-  std::vector<int64_t> ids;     // host copies: what the calls report by position
-  std::vector<int32_t> atoms;
-  std::vector<int32_t> seg_first;  // first position of every segment: a maximal run of consecutive rows with one id (scann_index_match)
-  float* rows_of(size_t c) const { return reinterpret_cast<float*>(chunks[c]); }
-  int64_t* ids_of(size_t c) const { return reinterpret_cast<int64_t*>(chunks[c] + (size_t)chunk_rows * stride * 4); }
-  size_t chunk_bytes() const { return (size_t)chunk_rows * stride * 4 + (size_t)chunk_rows * 8; }
-};
-
 namespace {
 
 constexpr int KNN_QGROUP = 1024;     // queries per pass over the index (bounds the partial lists)

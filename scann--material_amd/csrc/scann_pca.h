@@ -34,6 +34,7 @@ struct PcaArgs {
   unsigned long long* R;     // [stride]
   double* cov;               // [dim][dim]
   int32_t* col_exp;          // [dim] f_j
+  const uint8_t* mask;       // [n_total] or null: a row with mask 0 is not eligible whatever it holds (scann_index_fit_moments: its targets)
 };
 
 // elig, n, colmax; S; mean; cenmax; T and R; cov and col_exp -- six launches on one stream, nothing waits in between

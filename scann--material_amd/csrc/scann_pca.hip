@@ -7,7 +7,8 @@
 //   covariance  fp64, one expression per (i, j) from T, R and n;
 //   projection  z_c = the fp32 chain acc = fmaf(x[j] - mean[j], W[c][j], acc) over the columns ascending, the difference rounded once.
 // The moments are six launches on one stream; the host waits once, behind the last:
-//   pca_prepare_kernel     a row is eligible iff all its components are finite; their count; the column maxima of |x| over the eligible
+//   pca_prepare_kernel     a row is eligible iff all its components are finite (and, with a mask, its mask byte is set: the targets of
+//                          scann_index_fit_moments, scann_head.hip); their count; the column maxima of |x| over the eligible
 //                          rows by integer max on the bit patterns (kmeans_prepare_kernel's pass).
 //   pca_pass_kernel<0>     S_j: a lane owns 4 columns of every R-th row of its workgroup's range and sums q in registers; one LDS add
 //                          and one global 64-bit integer atomic per column and workgroup.
@@ -73,6 +74,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_prepare_kernel(PcaArgs a) {
     const float* row = nullptr;
     if (p < a.n_total) {
       row = pca_row(a.rows, a.chunk_rows, a.stride, p);
+      if (a.mask) bad = !a.mask[p];
       for (int c = 4 * sub; c < a.stride; c += 32) {
         const float4 v = *reinterpret_cast<const float4*>(row + c);
         bad |= !(pca_finite(v.x) && pca_finite(v.y) && pca_finite(v.z) && pca_finite(v.w));

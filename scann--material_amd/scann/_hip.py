@@ -146,6 +146,11 @@ SYMBOLS = [
     ("scann_project_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P]),
     ("scann_sym_eig_host", C.c_int, [_P, C.c_int64, _P, _P, _P]),
     ("scann_pca_bits", C.c_int, [C.c_int64]),
+    ("scann_index_fit_moments", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_index_ridge_loo", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_ridge_loo_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P,
+                                       _P, _P]),
+    ("scann_head_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -169,6 +174,9 @@ KMEANS_MAX_K = 1024
 # scann_index_match: the measures by name (SCANN_MATCH_*) and the most atoms of one query structure (SCANN_MATCH_MAX_ATOMS)
 MATCH_MEASURES = {"chamfer": 0, "hausdorff": 1, "cover": 2}
 MATCH_MAX_ATOMS = 128
+# the readout head on an index: the most targets and ridge strengths of one call (SCANN_HEAD_MAX_TARGETS, SCANN_HEAD_MAX_LAMBDA)
+HEAD_MAX_TARGETS = 16
+HEAD_MAX_LAMBDA = 32
 
 
 def check_knn_k(k):
@@ -404,6 +412,88 @@ def sym_eig(a):
     if rc < 0:
         raise ValueError("sym_eig: invalid arguments (%d)" % rc)
     return w, v, int(sweeps.value)
+
+
+def check_head_targets(targets, n_rows=None):
+    """Targets of a head as the C calls take them: fp32 [N, K] from [N] or [N, K], 1 <= K <= HEAD_MAX_TARGETS (NaN: unlabelled);
+    ValueError otherwise, naming the argument."""
+    try:
+        t = np.asarray(targets, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("targets must be an array of numbers") from None
+    if t.ndim == 1:
+        t = t.reshape(-1, 1)
+    if t.ndim != 2 or not 1 <= t.shape[1] <= HEAD_MAX_TARGETS:
+        raise ValueError("targets must have shape [N] or [N, K], 1 <= K <= %d, got %s" % (HEAD_MAX_TARGETS, np.shape(targets)))
+    if n_rows is not None and t.shape[0] != int(n_rows):
+        raise ValueError("targets hold %d rows, the index %d" % (t.shape[0], int(n_rows)))
+    return np.ascontiguousarray(t)
+
+
+def check_head_args(mean, tmean, components, scale, coef, lev0, resid_l=None, dim=None):
+    """The arguments of a leave-one-out pass as the C calls take them: mean [dim], tmean [K], components [m, dim], scale [L, m], coef
+    [L, K, m], lev0 and resid_l [K] or None -- finite fp32, 1 <= m <= dim, 1 <= K <= HEAD_MAX_TARGETS, 1 <= L <= HEAD_MAX_LAMBDA, resid_l in
+    -1 .. L - 1; ValueError otherwise, naming the argument."""
+    mean, components, _ = check_pca_args(mean, components, None, dim)
+
+    def array(x, name):
+        try:
+            return np.ascontiguousarray(x, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be an array of numbers" % name) from None
+
+    tmean, scale, coef = array(tmean, "tmean"), array(scale, "scale"), array(coef, "coef")
+    m = components.shape[0]
+    if tmean.ndim != 1 or not 1 <= tmean.shape[0] <= HEAD_MAX_TARGETS:
+        raise ValueError("tmean must hold K values, 1 <= K <= %d, got shape %s" % (HEAD_MAX_TARGETS, tmean.shape))
+    K = tmean.shape[0]
+    if scale.ndim != 2 or scale.shape[1] != m or not 1 <= scale.shape[0] <= HEAD_MAX_LAMBDA:
+        raise ValueError("scale must have shape [L, %d], 1 <= L <= %d, got %s" % (m, HEAD_MAX_LAMBDA, scale.shape))
+    L = scale.shape[0]
+    if coef.shape != (L, K, m):
+        raise ValueError("coef must have shape [%d, %d, %d], got %s" % (L, K, m, coef.shape))
+    try:
+        lev0 = float(lev0)
+    except (TypeError, ValueError):
+        raise ValueError("lev0 must be a number, got %r" % (lev0,)) from None
+    for name, a in (("tmean", tmean), ("scale", scale), ("coef", coef), ("lev0", np.float32(lev0))):
+        if not np.isfinite(a).all():
+            raise ValueError("%s holds a non-finite value" % name)
+    if resid_l is not None:
+        r = np.asarray(resid_l)
+        if r.dtype.kind not in "iu" or r.shape != (K,) or (r < -1).any() or (r >= L).any():
+            raise ValueError("resid_l must hold %d integers in -1 .. %d, got %r" % (K, L - 1, resid_l))
+        resid_l = np.ascontiguousarray(r, dtype=np.int32)
+    return mean, tmean, components, scale, coef, lev0, resid_l
+
+
+def _loo_out(L, K, n, resid_l):
+    out = {"sse": np.zeros((L, K)), "sae": np.zeros((L, K)), "sse_fit": np.zeros((L, K)), "dof": np.zeros(L)}
+    if resid_l is not None:
+        out["resid"] = np.full((n, K), np.nan, np.float32)
+    return out
+
+
+def ridge_loo_host(rows, targets, mean, tmean, components, scale, coef, lev0, resid_l=None):
+    """The leave-one-out pass on the host with the kernels' bits (scann_ridge_loo_host, the definition in include/scann_hip.h): {"n",
+    "sse", "sae", "sse_fit" [L, K] fp64, "dof" [L] fp64, with ``resid_l`` "resid" [n, K] fp32}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("ridge_loo_host: rows of shape %s" % (rows.shape,))
+    t = check_head_targets(targets, rows.shape[0])
+    mean, tmean, components, scale, coef, lev0, resid_l = check_head_args(mean, tmean, components, scale, coef, lev0, resid_l, rows.shape[1])
+    if t.shape[1] != tmean.shape[0]:
+        raise ValueError("targets hold %d columns, tmean %d" % (t.shape[1], tmean.shape[0]))
+    L, K, m = coef.shape
+    out = _loo_out(L, K, rows.shape[0], resid_l)
+    n = C.c_int64(0)
+    rc = int(load_library().scann_ridge_loo_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(t), K, _ptr(mean), _ptr(tmean), _ptr(components), m,
+                                                 _ptr(scale), _ptr(coef), L, lev0, _ptr(resid_l), C.byref(n), _ptr(out["sse"]), _ptr(out["sae"]),
+                                                 _ptr(out["sse_fit"]), _ptr(out["dof"]), _ptr(out.get("resid"))))
+    if rc < 0:
+        raise ValueError("ridge_loo_host: invalid arguments (%d)" % rc)
+    out["n"] = int(n.value)
+    return out
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -1339,6 +1429,57 @@ class Engine:
         out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
         self._check(self.lib.scann_project_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(components), _ptr(scale), components.shape[0],
                                                  _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["coords"]), _ptr(out.get("md2")), _ptr(out["dist2"])))
+        return out
+
+    def index_fit_moments(self, ix, targets):
+        """Mean and covariance of [rows | targets] over the rows of ``ix`` whose components and targets are all finite, on the device
+        (scann_index_fit_moments): {"n", "mean" [dim + K] fp32, "cov" [dim + K, dim + K] fp64, "col_exp" [dim + K] int32, "bits"}, bit
+        for bit ``moments_host`` of the augmented matrix."""
+        t = check_head_targets(targets, len(ix))
+        D = ix.dim + t.shape[1]
+        out = {"mean": np.zeros(D, np.float32), "cov": np.zeros((D, D), np.float64), "col_exp": np.zeros(D, np.int32)}
+        ne, bits = C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.scann_index_fit_moments(self._h, ix._h, _ptr(t), t.shape[1], C.byref(ne), _ptr(out["mean"]), _ptr(out["cov"]),
+                                                     _ptr(out["col_exp"]), C.byref(bits)))
+        out["n"], out["bits"] = int(ne.value), int(bits.value)
+        return out
+
+    def index_ridge_loo(self, ix, targets, mean, tmean, components, scale, coef, lev0, resid_l=None):
+        """The exact leave-one-out residuals of every row of ``ix`` at every ridge strength, summed on the device (scann_index_ridge_loo):
+        {"n", "sse", "sae", "sse_fit" [L, K] fp64, "dof" [L] fp64, with ``resid_l`` "resid" [N, K] fp32}, bit for bit ``ridge_loo_host``."""
+        t = check_head_targets(targets, len(ix))
+        mean, tmean, components, scale, coef, lev0, resid_l = check_head_args(mean, tmean, components, scale, coef, lev0, resid_l, ix.dim)
+        if t.shape[1] != tmean.shape[0]:
+            raise ValueError("targets hold %d columns, tmean %d" % (t.shape[1], tmean.shape[0]))
+        L, K, m = coef.shape
+        out = _loo_out(L, K, len(ix), resid_l)
+        n = C.c_int64(0)
+        self._check(self.lib.scann_index_ridge_loo(self._h, ix._h, _ptr(t), K, _ptr(mean), _ptr(tmean), _ptr(components), m, _ptr(scale), _ptr(coef),
+                                                   L, lev0, _ptr(resid_l), C.byref(n), _ptr(out["sse"]), _ptr(out["sae"]), _ptr(out["sse_fit"]),
+                                                   _ptr(out["dof"]), _ptr(out.get("resid"))))
+        out["n"] = int(n.value)
+        return out
+
+    def head_batch(self, rb, level, mean, tmean, weights, components, scale, lev0):
+        """One forward of a resident batch and a head evaluated on each of its ``level`` rows (scann_head_batch; raw y): {"y" [n_struct],
+        "ga" [n_atom], "pred", "lev" [n_struct or n_atom, K]}.  ``weights`` [K, dim], ``components`` [m, dim], ``scale`` [K, m]."""
+        mean, components, _ = check_pca_args(mean, components, None)
+        tmean = np.ascontiguousarray(tmean, dtype=np.float32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        K, m = tmean.shape[0], components.shape[0]
+        if tmean.ndim != 1 or not 1 <= K <= HEAD_MAX_TARGETS or weights.shape != (K, mean.shape[0]) or scale.shape != (K, m):
+            raise ValueError("head_batch: tmean [K], weights [K, %d] and scale [K, %d] are needed, 1 <= K <= %d, got %s, %s and %s" % (
+                mean.shape[0], m, HEAD_MAX_TARGETS, tmean.shape, weights.shape, scale.shape))
+        for name, a in (("tmean", tmean), ("weights", weights), ("scale", scale), ("lev0", np.float32(lev0))):
+            if not np.isfinite(a).all():
+                raise ValueError("%s holds a non-finite value" % name)
+        p = rb.packed
+        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "pred": np.empty((n, K), np.float32),
+               "lev": np.empty((n, K), np.float32)}
+        self._check(self.lib.scann_head_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(tmean), _ptr(weights), K, _ptr(components), m,
+                                              _ptr(scale), float(lev0), _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["pred"]), _ptr(out["lev"])))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

@@ -277,8 +277,193 @@ class LatentIndex:
         r = self.model.engine.index_project(self._ix, projection.mean, projection.components, projection.scale)
         return projection.finish(r)
 
+    def fit_head(self, targets, l2="loo", names=None):
+        """A linear readout head for ``targets`` ([N] or [N, K], K <= 16, one row per row of this index; NaN: unlabelled) on the frozen
+        rows: ridge regression in the principal axes of the rows, the strength chosen per target by exact leave-one-out.  The moments of
+        [rows | targets] (scann_index_fit_moments) and the leave-one-out residuals of every row at every strength
+        (scann_index_ridge_loo) are computed on the GPU and depend on the index contents and the targets only, bit for bit; the X-X
+        covariance is decomposed on the host (``_hip.sym_eig``).  Components at or below the noise floor of the integer moments
+        (``pca``'s) are left out.  ``l2``: "loo" -- the grid max(s_0 10^(-l/2), noise floor), l = 0 .. 16, s_0 the largest eigenvalue --,
+        one number, or a sequence of at most 32.  Per target the strength with the least leave-one-out sum of squares wins, ties to
+        the larger.  Returns ``(result, head)``: {"l2" [K], "loo_rmse", "loo_mae", "loo_r2", "fit_rmse", "dof", "sigma2" [K],
+        "n_rows", "loo_prediction" fp32 [N, K] (t - r; NaN for rows that do not count), "weights" fp32 [K, dim], "names", "path":
+        {"l2" [L], "loo_rmse" [L, K], "dof" [L]}} and the ``LatentHead`` that ``HipModel.predict_head`` takes.  Bad arguments raise
+        ValueError before any device call; so do fewer than 3 usable rows and a covariance without a component above the noise floor."""
+        t = _hip.check_head_targets(targets, len(self))
+        K = t.shape[1]
+        names = ["target_%d" % k for k in range(K)] if names is None else [str(x) for x in names]
+        if len(names) != K:
+            raise ValueError("names: %d for %d targets" % (len(names), K))
+        grid = head_grid(l2)
+        if len(self) < 3:
+            raise ValueError("a head needs at least 3 rows, the index has %d" % len(self))
+        eng, dim = self.model.engine, self.dim
+        try:
+            mo = eng.index_fit_moments(self._ix, t)
+        except _hip.ScannHipError as e:
+            if e.code == -1:
+                raise ValueError(str(e)) from None
+            raise
+        fit = head_closed_form(mo, dim, grid)
+        n = fit["n"]
+        first = eng.index_ridge_loo(self._ix, t, fit["mean"], fit["tmean"], fit["components"], fit["scale"], fit["coef"], fit["lev0"])
+        pick = head_pick(first["sse"], fit["l2"])
+        second = eng.index_ridge_loo(self._ix, t, fit["mean"], fit["tmean"], fit["components"], fit["scale"], fit["coef"], fit["lev0"], pick)
+        return head_result(fit, second, pick, t, names, self.level, dim)
+
     def free(self):
         self._ix.free()
+
+
+def head_grid(l2):
+    """``l2`` of ``fit_head`` checked: "loo" -> None (the default grid, which needs the eigenvalues), else the fp64 values; ValueError
+    for anything else"""
+    if isinstance(l2, str):
+        if l2 != "loo":
+            raise ValueError('l2 must be "loo", a number >= 0 or a sequence of them, got %r' % (l2,))
+        return None
+    try:
+        g = np.atleast_1d(np.asarray(l2, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError('l2 must be "loo", a number >= 0 or a sequence of them, got %r' % (l2,)) from None
+    if isinstance(l2, bool) or g.ndim != 1 or not 1 <= g.shape[0] <= _hip.HEAD_MAX_LAMBDA or not np.isfinite(g).all() or (g < 0).any():
+        raise ValueError("l2 must hold 1 .. %d finite values >= 0, got %r" % (_hip.HEAD_MAX_LAMBDA, l2))
+    return g
+
+
+def head_closed_form(mo, dim, grid=None):
+    """The moments of [rows | targets] ({"n", "mean", "cov", "col_exp", "bits"}) -> what the leave-one-out pass takes, in fp64 and cast
+    to fp32 at the end: the eigen-decomposition of the X-X block (``_hip.sym_eig``), the components above the noise floor, and per
+    strength lambda_l  beta_lkc = g_kc / (s_c + lambda_l), g_k = V c_xy,k;  S_lc = 1 / sqrt((n - 1)(s_c + lambda_l));  lev0 = 1 / n.
+    ValueError for fewer than 3 rows or no component above the floor."""
+    n = int(mo["n"])
+    if n < 3:
+        raise ValueError("a head needs at least 3 rows without a non-finite component or target, got %d" % n)
+    cov = np.asarray(mo["cov"], dtype=np.float64)
+    w, v, _ = _hip.sym_eig(cov[:dim, :dim])
+    noise = float(dim) * 2.0 ** (2 * int(np.asarray(mo["col_exp"])[:dim].max()) - int(mo["bits"]) + 2)
+    m = int((w > noise).sum())
+    if m < 1:
+        raise ValueError("no component of the rows' covariance lies above its noise floor %.3g: nothing to regress on" % noise)
+    s, V = w[:m], v[:m]
+    if grid is None:
+        grid = np.maximum(s[0] * 10.0 ** (-np.arange(17) / 2.0), noise)
+        grid = grid[np.concatenate([[True], grid[1:] != grid[:-1]])]  # (non-increasing: duplicates are neighbours)
+    grid = np.asarray(grid, dtype=np.float64)
+    g = (V @ cov[:dim, dim:]).T  # [K, m]
+    den = s[None, :] + grid[:, None]  # [L, m]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        beta = g[None, :, :] / den[:, None, :]
+        scale = 1.0 / np.sqrt((n - 1.0) * den)
+    out = {"n": n, "m": m, "noise_floor": noise, "variance": s, "l2": grid, "beta": beta, "V": V, "lev0": 1.0 / n,
+           "mean": np.asarray(mo["mean"][:dim], np.float32), "tmean": np.asarray(mo["mean"][dim:], np.float32),
+           "components": V.astype(np.float32), "scale": scale.astype(np.float32), "coef": beta.astype(np.float32),
+           "tvar": np.diag(cov)[dim:].copy()}
+    for name in ("scale", "coef"):
+        if not np.isfinite(out[name]).all():
+            raise ValueError("l2 is too small for this index: %s is not finite in fp32" % name)
+    return out
+
+
+def head_pick(sse, l2):
+    """Per target the strength with the least leave-one-out sum of squares (NaN counts as inf), ties to the larger lambda: int32 [K]"""
+    sse = np.where(np.isnan(sse), np.inf, np.asarray(sse, dtype=np.float64))
+    order = np.lexsort((-np.asarray(l2, dtype=np.float64), ))  # larger lambda first
+    pick = np.zeros(sse.shape[1], np.int32)
+    for k in range(sse.shape[1]):
+        col = sse[order, k]
+        pick[k] = order[int(np.argmin(col))]  # (argmin: the first of equals, i.e. the larger lambda)
+    return pick
+
+
+def head_result(fit, loo, pick, t, names, level, dim):
+    """``fit_head``'s ``(result, head)`` from the closed form, the second leave-one-out pass and the picks"""
+    n, K = fit["n"], len(pick)
+    kk = np.arange(K)
+    sse, sae, sse_fit = loo["sse"][pick, kk], loo["sae"][pick, kk], loo["sse_fit"][pick, kk]
+    W = np.einsum("kc,cj->kj", fit["beta"][pick, kk, :], fit["V"])  # fp64
+    sigma2 = sse / n
+    tss = fit["tvar"] * (n - 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r2 = 1.0 - sse / tss
+    head = LatentHead(fit["mean"], fit["tmean"], W.astype(np.float32), fit["components"], fit["scale"][pick], fit["lev0"], sigma2, fit["l2"][pick],
+                      level, dim, names)
+    result = {"l2": fit["l2"][pick], "loo_rmse": np.sqrt(sse / n), "loo_mae": sae / n, "loo_r2": r2, "fit_rmse": np.sqrt(sse_fit / n),
+              "dof": loo["dof"][pick], "sigma2": sigma2, "n_rows": n, "loo_prediction": (t - loo["resid"]).astype(np.float32),
+              "weights": head.weights, "names": list(names),
+              "path": {"l2": fit["l2"], "loo_rmse": np.sqrt(loo["sse"] / n), "dof": loo["dof"]}}
+    return result, head
+
+
+class LatentHead:
+    """A linear readout head on one level of one model, as ``LatentIndex.fit_head`` fits it: prediction_k = tmean_k + (x - mean) . W_k
+    and leverage_k = lev0 + sum_c ((x - mean) . V_c scale_kc)^2, so that std_k = sqrt(sigma2_k (1 + leverage_k)) is the predictive
+    standard deviation of Bayesian linear regression.  mean [dim], tmean [K], weights [K, dim], components [m, dim], scale [K, m] fp32;
+    sigma2, l2 [K] fp64."""
+
+    def __init__(self, mean, tmean, weights, components, scale, lev0, sigma2, l2, level, dim=None, names=None):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        self.mean, self.components, _ = _hip.check_pca_args(mean, components, None, dim)
+        try:
+            self.tmean = np.ascontiguousarray(tmean, dtype=np.float32)
+            self.weights = np.ascontiguousarray(weights, dtype=np.float32)
+            self.scale = np.ascontiguousarray(scale, dtype=np.float32)
+            self.sigma2 = np.ascontiguousarray(sigma2, dtype=np.float64)
+            self.l2 = np.ascontiguousarray(l2, dtype=np.float64)
+            self.lev0 = float(lev0)
+        except (TypeError, ValueError):
+            raise ValueError("tmean, weights, scale, sigma2 and l2 must be arrays of numbers and lev0 a number") from None
+        K, d, m = self.tmean.shape[0] if self.tmean.ndim == 1 else 0, self.mean.shape[0], self.components.shape[0]
+        if not 1 <= K <= _hip.HEAD_MAX_TARGETS:
+            raise ValueError("tmean must hold 1 .. %d values, got shape %s" % (_hip.HEAD_MAX_TARGETS, self.tmean.shape))
+        for name, a, shape in (("weights", self.weights, (K, d)), ("scale", self.scale, (K, m)), ("sigma2", self.sigma2, (K,)), ("l2", self.l2, (K,))):
+            if a.shape != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
+        for name, a in (("tmean", self.tmean), ("weights", self.weights), ("scale", self.scale), ("lev0", np.float64(self.lev0))):
+            if not np.isfinite(a).all():
+                raise ValueError("%s holds a non-finite value" % name)
+        if np.isnan(self.sigma2).any() or (self.sigma2 < 0).any():
+            raise ValueError("sigma2 must be >= 0")
+        self.level, self.dim = level, int(d)
+        self.names = ["target_%d" % k for k in range(K)] if names is None else [str(x) for x in names]
+        if len(self.names) != K:
+            raise ValueError("names: %d for %d targets" % (len(self.names), K))
+
+    @property
+    def k(self):
+        return int(self.tmean.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the head has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level head of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def finish(self, pred, lev):
+        """the device's pred and lev [n, K] as {"prediction", "std", "leverage"}: the square root taken on the host in fp64"""
+        with np.errstate(invalid="ignore"):
+            std = np.sqrt(self.sigma2[None, :] * (1.0 + lev.astype(np.float64))).astype(np.float32)
+        return {"prediction": pred, "std": std, "leverage": lev}
+
+    def save(self, path):
+        """An ``.npz`` of the head's arrays, level, dim and names (written to exactly ``path``; no pickle)."""
+        with open(path, "wb") as f:
+            np.savez(f, mean=self.mean, tmean=self.tmean, weights=self.weights, components=self.components, scale=self.scale,
+                     lev0=np.array(self.lev0), sigma2=self.sigma2, l2=self.l2, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64),
+                     names=np.array(self.names, dtype=np.str_))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved head; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            args = [z[n] for n in ("mean", "tmean", "weights", "components", "scale")] + [float(z["lev0"]), z["sigma2"], z["l2"]]
+            names = [str(x) for x in z["names"]]
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(*args, level, dim, names)
 
 
 class LatentProjection:

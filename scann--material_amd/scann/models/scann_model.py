@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentClustering, LatentIndex, LatentProjection, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import LatentClustering, LatentHead, LatentIndex, LatentProjection, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -555,6 +555,62 @@ class HipModel:
         out["predict_property"] = cat["y"].reshape(-1, 1)
         if atom and not isinstance(inputs, _hip.PackedBatch):
             for n in ("coordinates", "mahalanobis", "distance_to_mean"):
+                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
+        return out
+
+    def fit_head(self, data, targets, level="structure", l2="loo", ids=None, batch_size=None, names=None):
+        """A linear readout head for another property on the model's frozen latent space (``LatentIndex.fit_head``): ridge regression of
+        ``targets`` on the ``bf_property`` rows (``level`` "structure", one target row per structure) or the ``after_Lc`` rows ("atom",
+        one per real atom: a flat array in packed order or one array per structure), the strength chosen by exact leave-one-out on the
+        GPU.  ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for
+        the call and freed afterwards.  Returns ``(result, head)``; the ``LatentHead`` is what ``predict_head`` takes and can be saved.
+        Bad arguments raise ValueError before anything is uploaded."""
+        lvl = data.level if isinstance(data, LatentIndex) else level
+        level_dim(self.config, lvl)
+        if lvl == "atom" and isinstance(targets, (list, tuple)) and len(targets) and np.ndim(targets[0]) >= 1:
+            try:
+                targets = np.concatenate([np.asarray(x, dtype=np.float32).reshape(len(x), -1) for x in targets])
+            except (TypeError, ValueError):
+                raise ValueError("targets must be a flat array in packed order or one array per structure") from None
+        t = _hip.check_head_targets(targets, len(data) if isinstance(data, LatentIndex) else None)
+        from .latent_index import head_grid
+        head_grid(l2)
+        if names is not None and len(names) != t.shape[1]:
+            raise ValueError("names: %d for %d targets" % (len(names), t.shape[1]))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.fit_head(t, l2=l2, names=names)
+        finally:
+            if own is not None:
+                own.free()
+
+    def predict_head(self, inputs, head, batch_size=None):
+        """New ``inputs`` through a ``LatentHead``, right behind their forward (scann_head_batch): the head's prediction of its K
+        targets, the predictive standard deviation sqrt(sigma2 (1 + leverage)) of Bayesian linear regression -- an uncertainty beside
+        Monte Carlo dropout, ensembles and the latent-space distances -- and the leverage itself.  A padded dict gives {"prediction",
+        "std", "leverage": fp32 [B, K], "y": [B, 1] (the model's own raw prediction)} and at atom level [B, M, K] arrays with 0 at padded
+        atoms; a ``PackedBatch`` gives packed [n_atom, K] arrays.  A head of another width or a bad batch_size raise ValueError before
+        anything is uploaded."""
+        if not isinstance(head, LatentHead):
+            raise ValueError("head must be a LatentHead, got %r" % (type(head).__name__,))
+        head.check_model(self)
+        self._batch_size(batch_size)
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.head_batch(
+            rb, lvl, head.mean, head.tmean, head.weights, head.components, head.scale, head.lev0))
+        K = head.k
+        empty = {"y": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32), "lev": np.zeros((0, K), np.float32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = head.finish(cat["pred"], cat["lev"])
+        out["y"] = cat["y"].reshape(-1, 1)
+        if atom and not isinstance(inputs, _hip.PackedBatch):
+            for n in ("prediction", "std", "leverage"):
                 out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
         return out
 
@@ -1121,6 +1177,17 @@ class SCANN:
         coordinates and the distances live in latent space and stay as they are."""
         out = self.model.project(ip, projection, batch_size=batch_size)
         out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
+
+    def fit_head(self, data, targets, level="structure", l2="loo", ids=None, batch_size=None, names=None):
+        """HipModel.fit_head as it is: ``(result, head)``; the head lives in latent space and in the units of ``targets``."""
+        return self.model.fit_head(data, targets, level=level, l2=l2, ids=ids, batch_size=batch_size, names=names)
+
+    def predict_head(self, ip, head, batch_size=None):
+        """HipModel.predict_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the head's
+        prediction, std and leverage are in the units of the head's targets and stay as they are."""
+        out = self.model.predict_head(ip, head, batch_size=batch_size)
+        out["y"] = out["y"] * self.std + self.mean
         return out
 
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
