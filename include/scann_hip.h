@@ -680,6 +680,48 @@ int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const
                      const float* weights /* [K * dim] */, int32_t K, const float* components /* [m * dim] */, int32_t m,
                      const float* scale /* [K * m] */, float lev0, float* y, float* ga, float* pred /* [n * K] */, float* lev /* [n * K] */);
 
+/* ---- Gaussian landmark features: a nonlinear readout head on an index ----
+ * The second half of a probing study: is a property decodable from the frozen latent space at all, by a nonlinear readout.  The feature
+ * map is the standard one of kernel ridge regression with a fixed basis (Nystroem / sparse Gaussian process):
+ *   phi_c(x) = exp(-|x - z_c|^2 / 2 h^2) = 2^(-dist2(x, z_c) gamma),  gamma = log2(e) / (2 h^2),
+ * to m landmarks z_c.  Ridge regression on the features -- the calls above, unchanged, on an index that holds the features -- is sparse
+ * GP regression with that basis, and sqrt(sigma^2 (1 + leverage)) its predictive standard deviation.
+ * The weight, defined to the bit: scann_rbf_weight(dist2, gamma), no GPU work; the kernel runs the same body.  Every operation is fp32
+ * and rounded once, nothing is contracted beyond the stated fmaf:
+ *   u = dist2 * gamma;   u NaN -> NaN;   u >= 126 (+inf included) -> 0 (no denormal result ever arises);
+ *   i = floorf(u);   g = (u - i) - 0.5f   (g in [-0.5, 0.5));
+ *   p = c7;  p = fmaf(p, g, c_j) for j = 6 .. 0;   result = ldexpf(p, -(int)i);
+ *   c_j = the fp32 rounding of 2^(-1/2) (-ln 2)^j / j!:  0x1.6a09e6p-1, -0x1.f5e466p-2, 0x1.5be298p-3, -0x1.41839ep-5, 0x1.bdb696p-8,
+ *         -0x1.ee4fd2p-11, 0x1.c8d752p-14, -0x1.69e51ep-17.
+ * Consequences: scann_rbf_weight(0, gamma) == 1.0f exactly; for dist2 >= 0 the result lies in [0, 1]; against exp2(-(double)u) with the
+ * same fp32 u the relative error stays below 3 x 2^-24 on [0, 126) (measured 2.02 x 2^-24).  gamma must be finite and > 0 in the calls
+ * below; u < 0 does not arise from a distance (the result is then above 1, +inf from 2^128 on).
+ * Features of an index (scann_index_rbf_features): `out` is an EMPTY index of the same handle with dim == m, 1 <= m <= 1024; landmarks
+ * is host [m * dim], dim the pool's.  The call appends one row per pool row, in position order, with the pool row's id and atom:
+ *   phi[p][c] = scann_rbf_weight(dist2(x_p, z_c), gamma),  dist2 exactly the chain of scann_knn_distsq with the pool row as q.
+ * A pool row with any non-finite component gets NaN in all m features (downstream it does not count, as nowhere else).  Between finite
+ * values a distance may overflow to +inf, which gives the feature 0, never NaN.  The rows never leave the device; the result depends
+ * on the pool contents, the landmarks and gamma only -- not on the chunking, the adds that built the pool or the launch geometry.
+ * SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null argument, an index of another handle,
+ * out not empty or out->dim != m, out == pool, m out of range, a non-finite landmark value (landmark and column are named), gamma not
+ * finite or <= 0.  An empty pool returns SCANN_OK and appends nothing.  Synchronous, one host wait; inference and training handles at
+ * any width; weights, training state and selected outputs are untouched.  scann_rbf_features_host (rows [n * dim], phi [n * m]; no GPU)
+ * is the twin: the same bits.
+ * A kernel head behind a forward (scann_rbf_head_batch): one inference forward of the resident batch with the level's output added for
+ * that forward only (y, ga, range guard, exact-fp32 re-run and selection restore exactly as scann_head_batch), the features of the level's
+ * rows where the forward left them (landmarks [m * dim], dim the level's width), and scann_head_batch's evaluation on the FEATURE rows:
+ * mean [m], weights [K * m], components [mm * m], 1 <= mm <= m, scale [K * mm].  pred, lev [n * K] are the bits of scann_project_host on
+ * phi with (mean, weights) and with (mean, components, scale[k]), plus one fp32 add each; phi [n * m] or NULL receives the features. */
+float scann_rbf_weight(float dist2, float gamma);
+void scann_rbf_weight_array(const float* dist2, int64_t n, float gamma, float* out);  /* out[i] = scann_rbf_weight(dist2[i], gamma) */
+int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float* landmarks /* host [m * dim] */, int32_t m, float gamma,
+                             scann_index_t* out);
+int scann_rbf_features_host(const float* rows, int64_t n, int64_t dim, const float* landmarks, int32_t m, float gamma, float* phi /* [n * m] */);
+int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* landmarks, int32_t m, float gamma,
+                         const float* mean /* [m] */, const float* tmean /* [K] */, const float* weights /* [K * m] */, int32_t K,
+                         const float* components /* [mm * m] */, int32_t mm, const float* scale /* [K * mm] */, float lev0, float* y, float* ga,
+                         float* pred /* [n * K] */, float* lev /* [n * K] */, float* phi /* [n * m] or NULL */);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

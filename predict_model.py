@@ -33,6 +33,12 @@ order, or per atom in packed order.  Ridge regression with the strength chosen b
 leave-one-out table, pickles the result with the rows' dataset indices and atoms as ``head_<target>.pickle`` and, with ``--head-out``,
 saves the head as a ``LatentHead`` (.npz).  ``--head FILE`` evaluates a saved head over the dataset instead and pickles one unpadded dict
 per structure (prediction, std, leverage) as ``head_<target>.pickle``.
+``--fit-kernel-head TARGETS.npy [--landmarks M] [--kernel-head-level atom|structure] [--kernel-head-out FILE]`` fits a nonlinear readout
+head instead: ridge regression on Gaussian features to M landmarks of the latent space (default 256; the most diverse rows), features,
+moments and leave-one-out on the GPU, the bandwidth chosen by leave-one-out.  It prints the bandwidth path and the leave-one-out table,
+pickles the result as ``kernel_head_<target>.pickle`` and, with ``--kernel-head-out``, saves the head as a ``LatentKernelHead`` (.npz).
+``--kernel-head FILE`` evaluates a saved one over the dataset and pickles one unpadded dict per structure (prediction, std, leverage,
+support) as ``kernel_head_<target>.pickle``.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -110,6 +116,7 @@ def main(args):
     if args.cluster_iter < 0:
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
     head_targets = check_head_flags(args)
+    kernel_head_targets = check_kernel_head_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -297,6 +304,58 @@ def main(args):
             raise SystemExit("--head: %s" % e) from None
         print("Evaluate the head of %s (%s level, %d targets: %s)" % (args.head, head.level, head.k, ", ".join(head.names)))
         pickle.dump(head_records(scann, data, head), open(os.path.join(args.trained_model, "head_{}.pickle".format(target)), "wb"))
+    if kernel_head_targets is not None:
+        pool = scann.build_index(data, level=args.kernel_head_level, ids=data.indexes)
+        print("Fit a kernel head for %d target(s) on the dataset's %d rows (%s level, %d landmarks)" % (
+            kernel_head_targets.shape[1], len(pool), args.kernel_head_level, args.landmarks))
+        try:
+            res, head = scann.fit_kernel_head(pool, kernel_head_targets, landmarks=args.landmarks)
+        except ValueError as e:  # (the number of rows, too few labelled ones, fewer usable rows than landmarks)
+            pool.free()
+            raise SystemExit("--fit-kernel-head: %s" % e) from None
+        res["id"], res["atom"] = pool.names()
+        print("n_rows %d, covering radius %.6g, bandwidth %.6g" % (res["n_rows"], res["covering_radius"], res["bandwidth"]))
+        for g, h in enumerate(res["bandwidth_path"]["bandwidth"]):
+            print("bandwidth %12.6g  loo_r2 %s" % (h, " ".join("%10.6f" % x for x in res["bandwidth_path"]["loo_r2"][g])))
+        print("%-12s %12s %12s %12s %10s %12s %8s" % ("target", "l2", "loo_rmse", "loo_mae", "loo_r2", "fit_rmse", "dof"))
+        for k, name in enumerate(res["names"]):
+            print("%-12s %12.6g %12.6g %12.6g %10.6f %12.6g %8.2f" % (name, res["l2"][k], res["loo_rmse"][k], res["loo_mae"][k], res["loo_r2"][k],
+                                                                   res["fit_rmse"][k], res["dof"][k]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "kernel_head_{}.pickle".format(target)), "wb"))
+        if args.kernel_head_out:
+            head.save(args.kernel_head_out)
+        pool.free()
+    if args.kernel_head:
+        from scann.models import LatentKernelHead
+
+        try:
+            head = LatentKernelHead.load(scann.model, args.kernel_head)
+        except ValueError as e:
+            raise SystemExit("--kernel-head: %s" % e) from None
+        print("Evaluate the kernel head of %s (%s level, %d landmarks, %d targets: %s)" % (args.kernel_head, head.level, head.m, head.k, ", ".join(head.names)))
+        pickle.dump(head_records(scann, data, head, kernel=True), open(os.path.join(args.trained_model, "kernel_head_{}.pickle".format(target)), "wb"))
+
+
+def check_kernel_head_flags(args):
+    """--fit-kernel-head / --kernel-head checked before anything is loaded: the targets as fp32 [N, K], or None without --fit-kernel-head"""
+    if args.fit_kernel_head and args.kernel_head:
+        raise SystemExit("--fit-kernel-head and --kernel-head: fit a kernel head or evaluate one, not both")
+    if args.kernel_head_out and not args.fit_kernel_head:
+        raise SystemExit("--kernel-head-out: needs --fit-kernel-head")
+    if args.kernel_head and not os.path.isfile(args.kernel_head):
+        raise SystemExit("--kernel-head: no such file: %s" % args.kernel_head)
+    if not args.fit_kernel_head:
+        return None
+    try:
+        t = np.load(args.fit_kernel_head, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise SystemExit("--fit-kernel-head: cannot read %s: %s" % (args.fit_kernel_head, e)) from None
+    if t.dtype.kind not in "fiu" or t.ndim not in (1, 2) or (t.ndim == 2 and not 1 <= t.shape[1] <= 16) or t.shape[0] < 3:
+        raise SystemExit("--fit-kernel-head: %s must hold numbers of shape [N] or [N, K], N >= 3, 1 <= K <= 16, got %s %s" % (
+            args.fit_kernel_head, t.dtype, t.shape))
+    if not 1 <= args.landmarks <= 1024 or args.landmarks >= t.shape[0]:
+        raise SystemExit("--landmarks: M must lie in 1 .. 1024 and below the %d rows of the targets, got %d" % (t.shape[0], args.landmarks))
+    return np.ascontiguousarray(t.reshape(len(t), -1), dtype=np.float32)
 
 
 def check_head_flags(args):
@@ -318,17 +377,17 @@ def check_head_flags(args):
     return np.ascontiguousarray(t.reshape(len(t), -1), dtype=np.float32)
 
 
-def head_records(scann, data, head):
-    """--head: one unpadded dict per structure of the dataset, in dataset order"""
+def head_records(scann, data, head, kernel=False):
+    """--head / --kernel-head: one unpadded dict per structure of the dataset, in dataset order"""
     per = []
     atom = head.level == "atom"
     for b in range(len(data)):
         inputs, _ = data[b]
-        r = scann.predict_head(inputs, head)
+        r = scann.predict_kernel_head(inputs, head) if kernel else scann.predict_head(inputs, head)
         amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
         for i in range(len(amask)):
             d = {"predict_property": float(r["y"][i, 0])}
-            for key in ("prediction", "std", "leverage"):
+            for key in ("prediction", "std", "leverage") + (("support",) if kernel else ()):
                 d[key] = r[key][i][amask[i]] if atom else r[key][i]
             per.append(d)
     return per
@@ -432,6 +491,16 @@ def parser():
     p.add_argument("--head-out", type=str, default="", help="save the fitted head as a LatentHead (.npz) for SCANN.predict_head")
     p.add_argument("--head", type=str, default="",
                    help="a saved LatentHead (.npz): pickle its prediction, standard deviation and leverage per structure as head_<target>.pickle")
+    p.add_argument("--fit-kernel-head", type=str, default="",
+                   help="TARGETS.npy as --fit-head takes it: fit a nonlinear readout head on Gaussian features to landmarks of the latent space "
+                        "(features, moments and leave-one-out on the GPU) and pickle kernel_head_<target>.pickle")
+    p.add_argument("--landmarks", type=int, default=256, metavar="M", help="landmarks of --fit-kernel-head: the M most diverse rows (1 .. 1024)")
+    p.add_argument("--kernel-head-level", type=str, default="structure", choices=["atom", "structure"],
+                   help="rows to regress on: one per structure (bf_property) or one per atom (after_Lc)")
+    p.add_argument("--kernel-head-out", type=str, default="", help="save the fitted head as a LatentKernelHead (.npz) for SCANN.predict_kernel_head")
+    p.add_argument("--kernel-head", type=str, default="",
+                   help="a saved LatentKernelHead (.npz): pickle its prediction, standard deviation, leverage and support per structure as "
+                        "kernel_head_<target>.pickle")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

@@ -149,6 +149,84 @@ struct Bump {
 
 }  // namespace
 
+namespace scann {
+
+std::string check_head_eval(int dim, const float* mean, const float* tmean, const float* weights, int32_t K, const float* components, int32_t m,
+                            const float* scale, float lev0, const float* pred, const float* lev) {
+  if (K < 1 || K > SCANN_HEAD_MAX_TARGETS) return "K " + std::to_string(K) + " outside 1 .. " + std::to_string(SCANN_HEAD_MAX_TARGETS);
+  if (m < 1 || m > dim) return "m " + std::to_string(m) + " outside 1 .. " + std::to_string(dim);
+  if (!mean) return "mean is null";
+  if (!tmean) return "tmean is null";
+  if (!weights) return "weights is null";
+  if (!components) return "components is null";
+  if (!scale) return "scale is null";
+  if (!pred) return "pred is null";
+  if (!lev) return "lev is null";
+  int64_t at = 0;
+  if (!all_finite(mean, dim, &at)) return "mean holds a non-finite value (column " + std::to_string(at) + ")";
+  if (!all_finite(tmean, K, &at)) return "tmean holds a non-finite value (target " + std::to_string(at) + ")";
+  if (!all_finite(weights, (int64_t)K * dim, &at)) return "weights hold a non-finite value (target " + std::to_string(at / dim) + ")";
+  if (!all_finite(components, (int64_t)m * dim, &at)) return "components hold a non-finite value (component " + std::to_string(at / dim) + ")";
+  if (!all_finite(scale, (int64_t)K * m, &at)) return "scale holds a non-finite value (target " + std::to_string(at / m) + ")";
+  if (!std::isfinite(lev0)) return "lev0 is not finite";
+  return "";
+}
+
+int head_eval_rows(scann_handle* h, hipStream_t s, const float* src, int pitch, int64_t nq, int dim, const float* mean, const float* tmean,
+                   const float* weights, int32_t K, const float* components, int32_t m, const float* scale, float lev0, float* pred, float* lev) {
+  const int stride = (dim + 3) / 4 * 4;
+  Bump b;
+  const size_t oMean = b.take((size_t)stride * 4), oW = b.take((size_t)K * stride * 4), oV = b.take((size_t)m * stride * 4),
+               oPad = b.take(stride != pitch ? (size_t)nq * stride * 4 : 0);
+  const size_t zeroed = b.at;
+  const size_t oTab = b.take(8), oWk = b.take((size_t)nq * K * 4), oZ = b.take((size_t)nq * m * 4), oTmean = b.take((size_t)K * 4),
+               oS = b.take((size_t)K * m * 4), oPred = b.take((size_t)nq * K * 4), oLev = b.take((size_t)nq * K * 4);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, b.at));
+  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
+  if (stride != pitch) {  // rows of the padded width, as an index keeps them
+    if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oPad, (size_t)stride * 4, src, (size_t)pitch * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
+    src = reinterpret_cast<const float*>(ws + oPad);
+  }
+  const void* tab = src;
+  PcaProjArgs pa{};
+  pa.rows = reinterpret_cast<const float* const*>(ws + oTab);
+  pa.first = 0; pa.n = (int32_t)nq; pa.chunk_rows = 0x7fffffff; pa.stride = stride; pa.dim = dim;
+  pa.mean = reinterpret_cast<const float*>(ws + oMean);
+  HeadEvalArgs ea{};
+  ea.n = (int32_t)nq; ea.m = m; ea.K = K; ea.lev0 = lev0;
+  ea.w = reinterpret_cast<const float*>(ws + oWk);
+  ea.z = reinterpret_cast<const float*>(ws + oZ);
+  ea.tmean = reinterpret_cast<const float*>(ws + oTmean);
+  ea.scale = reinterpret_cast<const float*>(ws + oS);
+  ea.pred = reinterpret_cast<float*>(ws + oPred);
+  ea.lev = reinterpret_cast<float*>(ws + oLev);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oW, (size_t)stride * 4, weights, (size_t)dim * 4, (size_t)dim * 4, (size_t)K, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oV, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, &tab, 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTmean, tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + oS, scale, (size_t)K * m * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {  // w: the projection on the K weight rows (the kernel takes any m)
+    pa.comp = reinterpret_cast<const float*>(ws + oW); pa.m = K; pa.coords = reinterpret_cast<float*>(ws + oWk);
+    e = launch_pca_project(pa, s);
+  }
+  if (e == hipSuccess) {
+    pa.comp = reinterpret_cast<const float*>(ws + oV); pa.m = m; pa.coords = reinterpret_cast<float*>(ws + oZ);
+    e = launch_pca_project(pa, s);
+  }
+  if (e == hipSuccess) e = launch_head_eval(ea, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(pred, ea.pred, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(lev, ea.lev, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e_sync = hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  return SCANN_OK;
+}
+
+}  // namespace scann
+
 extern "C" {
 
 int scann_ridge_loo_host(const float* rows, int64_t n, int64_t dim, const float* targets, int32_t K, const float* mean, const float* tmean,
@@ -361,81 +439,17 @@ int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const
   if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: null handle or batch");
   const int dim = head_level_dim(h, level);
   if (!dim) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
-  const std::string w = "scann_head_batch: ";
-  if (K < 1 || K > SCANN_HEAD_MAX_TARGETS) return fail(h, SCANN_ERR_INVALID, w + "K " + std::to_string(K) + " outside 1 .. " + std::to_string(SCANN_HEAD_MAX_TARGETS));
-  if (m < 1 || m > dim) return fail(h, SCANN_ERR_INVALID, w + "m " + std::to_string(m) + " outside 1 .. " + std::to_string(dim));
-  if (!mean) return fail(h, SCANN_ERR_INVALID, w + "mean is null");
-  if (!tmean) return fail(h, SCANN_ERR_INVALID, w + "tmean is null");
-  if (!weights) return fail(h, SCANN_ERR_INVALID, w + "weights is null");
-  if (!components) return fail(h, SCANN_ERR_INVALID, w + "components is null");
-  if (!scale) return fail(h, SCANN_ERR_INVALID, w + "scale is null");
-  if (!pred) return fail(h, SCANN_ERR_INVALID, w + "pred is null");
-  if (!lev) return fail(h, SCANN_ERR_INVALID, w + "lev is null");
-  int64_t at = 0;
-  if (!all_finite(mean, dim, &at)) return fail(h, SCANN_ERR_INVALID, w + "mean holds a non-finite value (column " + std::to_string(at) + ")");
-  if (!all_finite(tmean, K, &at)) return fail(h, SCANN_ERR_INVALID, w + "tmean holds a non-finite value (target " + std::to_string(at) + ")");
-  if (!all_finite(weights, (int64_t)K * dim, &at)) return fail(h, SCANN_ERR_INVALID, w + "weights hold a non-finite value (target " + std::to_string(at / dim) + ")");
-  if (!all_finite(components, (int64_t)m * dim, &at))
-    return fail(h, SCANN_ERR_INVALID, w + "components hold a non-finite value (component " + std::to_string(at / dim) + ")");
-  if (!all_finite(scale, (int64_t)K * m, &at)) return fail(h, SCANN_ERR_INVALID, w + "scale holds a non-finite value (target " + std::to_string(at / m) + ")");
-  if (!std::isfinite(lev0)) return fail(h, SCANN_ERR_INVALID, w + "lev0 is not finite");
+  const std::string bad = check_head_eval(dim, mean, tmean, weights, K, components, m, scale, lev0, pred, lev);
+  if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: " + bad);
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_head_batch: weights not loaded");
   const bool atom = level == SCANN_OUT_AFTER_LC;
   const int64_t nq = atom ? db->n_atom : db->n_struct;
   HIPCHK(h, hipSetDevice(h->device));
   if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
   if (nq <= 0) return SCANN_OK;
-  hipStream_t s = h->streams[db->last_slot];
-  const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
-  const int stride = (dim + 3) / 4 * 4;
-  Bump b;
-  const size_t oMean = b.take((size_t)stride * 4), oW = b.take((size_t)K * stride * 4), oV = b.take((size_t)m * stride * 4),
-               oPad = b.take(stride != dim ? (size_t)nq * stride * 4 : 0);
-  const size_t zeroed = b.at;
-  const size_t oTab = b.take(8), oWk = b.take((size_t)nq * K * 4), oZ = b.take((size_t)nq * m * 4), oTmean = b.take((size_t)K * 4),
-               oS = b.take((size_t)K * m * 4), oPred = b.take((size_t)nq * K * 4), oLev = b.take((size_t)nq * K * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
-  if (stride != dim) {  // rows of the padded width, as an index keeps them
-    if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oPad, (size_t)stride * 4, src, (size_t)dim * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
-    src = reinterpret_cast<const float*>(ws + oPad);
-  }
-  const void* tab = src;
-  PcaProjArgs pa{};
-  pa.rows = reinterpret_cast<const float* const*>(ws + oTab);
-  pa.first = 0; pa.n = (int32_t)nq; pa.chunk_rows = 0x7fffffff; pa.stride = stride; pa.dim = dim;
-  pa.mean = reinterpret_cast<const float*>(ws + oMean);
-  HeadEvalArgs ea{};
-  ea.n = (int32_t)nq; ea.m = m; ea.K = K; ea.lev0 = lev0;
-  ea.w = reinterpret_cast<const float*>(ws + oWk);
-  ea.z = reinterpret_cast<const float*>(ws + oZ);
-  ea.tmean = reinterpret_cast<const float*>(ws + oTmean);
-  ea.scale = reinterpret_cast<const float*>(ws + oS);
-  ea.pred = reinterpret_cast<float*>(ws + oPred);
-  ea.lev = reinterpret_cast<float*>(ws + oLev);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oW, (size_t)stride * 4, weights, (size_t)dim * 4, (size_t)dim * 4, (size_t)K, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oV, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, &tab, 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTmean, tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oS, scale, (size_t)K * m * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {  // w: the projection on the K weight rows (the kernel takes any m)
-    pa.comp = reinterpret_cast<const float*>(ws + oW); pa.m = K; pa.coords = reinterpret_cast<float*>(ws + oWk);
-    e = launch_pca_project(pa, s);
-  }
-  if (e == hipSuccess) {
-    pa.comp = reinterpret_cast<const float*>(ws + oV); pa.m = m; pa.coords = reinterpret_cast<float*>(ws + oZ);
-    e = launch_pca_project(pa, s);
-  }
-  if (e == hipSuccess) e = launch_head_eval(ea, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(pred, ea.pred, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(lev, ea.lev, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
-  const hipError_t e_sync = hipStreamSynchronize(s);
-  cached_free(ws);
-  HIPCHK(h, e);
-  HIPCHK(h, e_sync);
-  return SCANN_OK;
+  // the level's rows where the forward left them
+  return head_eval_rows(h, h->streams[db->last_slot], atom ? db->out_z : db->out_bf, dim, nq, dim, mean, tmean, weights, K, components, m, scale, lev0,
+                        pred, lev);
 }
 
 }  // extern "C"

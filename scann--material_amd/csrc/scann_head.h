@@ -4,7 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "scann_pca.h"
+
+struct scann_handle;
 
 namespace scann {
 
@@ -69,5 +73,13 @@ struct HeadEvalArgs {
   float* lev;          // [n][K]
 };
 hipError_t launch_head_eval(const HeadEvalArgs& a, hipStream_t s);
+
+// The evaluation of scann_head_batch, shared with scann_rbf_head_batch (scann_head.cpp).  check_head_eval: what is wrong with a head's
+// host arguments over rows of `dim` columns, or an empty string.  head_eval_rows: pred / lev [nq * K] of the head on nq device rows,
+// `pitch` floats apart (dim, or the stride dim rounded up to a multiple of 4 with zero padding), enqueued on s, downloaded and waited for.
+std::string check_head_eval(int dim, const float* mean, const float* tmean, const float* weights, int32_t K, const float* components, int32_t m,
+                            const float* scale, float lev0, const float* pred, const float* lev);
+int head_eval_rows(scann_handle* h, hipStream_t s, const float* src, int pitch, int64_t nq, int dim, const float* mean, const float* tmean,
+                   const float* weights, int32_t K, const float* components, int32_t m, const float* scale, float lev0, float* pred, float* lev);
 
 }  // namespace scann

@@ -73,6 +73,30 @@ int check_level(scann_handle* h, const scann_index* ix, int32_t level, const cha
   return SCANN_OK;
 }
 
+}  // namespace
+
+namespace scann {
+
+int index_new_chunk(scann_handle* h, scann_index* ix, hipStream_t s) {
+  char* p = nullptr;
+  HIPCHK(h, cached_malloc((void**)&p, ix->chunk_bytes()));
+  ix->chunks.push_back(p);
+  HIPCHK(h, hipMemsetAsync(p, 0, ix->chunk_bytes(), s));  // the padding columns are zero: fmaf(0, 0, acc) == acc
+  return SCANN_OK;
+}
+
+void index_note_rows(scann_index* ix, int64_t n, const int64_t* ids, const int32_t* atoms) {
+  for (int64_t i = 0; i < n; ++i)
+    if ((i == 0 ? ix->ids.empty() || ix->ids.back() != ids[0] : ids[i] != ids[i - 1])) ix->seg_first.push_back((int32_t)(ix->n + i));
+  ix->ids.insert(ix->ids.end(), ids, ids + n);
+  ix->atoms.insert(ix->atoms.end(), atoms, atoms + n);
+  ix->n += n;
+}
+
+}  // namespace scann
+
+namespace {
+
 // n rows of `dim` floats, `pitch` bytes apart at src (host or device, `kind`), appended behind the index's rows; ids / atoms: host, n each.
 // Rows already stored stay where they are: a chunk that is full is never touched again, a new one comes from the handle's cache.
 int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch, hipMemcpyKind kind, int64_t n, const int64_t* ids,
@@ -84,23 +108,15 @@ int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch,
     const int64_t at = ix->n + done;
     const size_t c = (size_t)(at / ix->chunk_rows);
     const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
-    if (c == ix->chunks.size()) {
-      char* p = nullptr;
-      HIPCHK(h, cached_malloc((void**)&p, ix->chunk_bytes()));
-      ix->chunks.push_back(p);
-      HIPCHK(h, hipMemsetAsync(p, 0, ix->chunk_bytes(), s));  // the padding columns are zero: fmaf(0, 0, acc) == acc
-    }
+    if (c == ix->chunks.size())
+      if (const int r = index_new_chunk(h, ix, s)) return r;
     HIPCHK(h, hipMemcpy2DAsync(ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4, static_cast<const char*>(src) + (size_t)done * pitch,
                                pitch, (size_t)ix->dim * 4, (size_t)m, kind, s));
     HIPCHK(h, hipMemcpyAsync(ix->ids_of(c) + r0, ids + done, (size_t)m * 8, hipMemcpyHostToDevice, s));
     done += m;
   }
   HIPCHK(h, hipStreamSynchronize(s));
-  for (int64_t i = 0; i < n; ++i)
-    if ((i == 0 ? ix->ids.empty() || ix->ids.back() != ids[0] : ids[i] != ids[i - 1])) ix->seg_first.push_back((int32_t)(ix->n + i));
-  ix->ids.insert(ix->ids.end(), ids, ids + n);
-  ix->atoms.insert(ix->atoms.end(), atoms, atoms + n);
-  ix->n += n;
+  index_note_rows(ix, n, ids, atoms);
   return SCANN_OK;
 }
 

@@ -25,6 +25,11 @@ struct scann_index {
 
 namespace scann {
 
+// How an index grows (scann_knn.cpp): one more chunk from the handle's cache behind the last, cleared on stream s; and, once n rows have
+// been written behind the index's rows and their device ids, the host side of the append (ids, atoms, segments, n)
+int index_new_chunk(scann_handle* h, scann_index* ix, hipStream_t s);
+void index_note_rows(scann_index* ix, int64_t n, const int64_t* ids, const int32_t* atoms);
+
 constexpr int KNN_TQ = 128;     // queries per workgroup
 constexpr int KNN_TR = 64;      // index rows per tile
 constexpr int KNN_SLAB = 32;    // columns per LDS slab

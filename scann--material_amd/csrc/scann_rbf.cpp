@@ -1,0 +1,164 @@
+// Gaussian landmark features of a latent-space index, the host half (include/scann_hip.h): scann_rbf_weight, scann_index_rbf_features and
+// scann_rbf_head_batch around the kernel of scann_rbf.hip, and the twin scann_rbf_features_host (the kernel's bits: the distance chain of
+// scann_knn_distsq and the weight chain of scann_rbf.h).  Every floating-point expression here is evaluated as written, each operation
+// rounded to nearest: the file is compiled with floating-point contraction off.
+#pragma clang fp contract(off)
+
+#include <cmath>
+
+#include "scann_head.h"
+#include "scann_knn.h"
+#include "scann_rbf.h"
+#include "scann_runtime.h"
+
+using namespace scann;
+
+namespace {
+
+// what is wrong with the landmarks and gamma, or an empty string
+std::string check_landmarks(const float* landmarks, int32_t m, int64_t dim, float gamma) {
+  if (m < 1 || m > 1024) return "m " + std::to_string(m) + " outside 1 .. 1024";
+  if (!landmarks) return "landmarks is null";
+  for (int64_t i = 0; i < (int64_t)m * dim; ++i)
+    if (!std::isfinite(landmarks[i]))
+      return "landmarks hold a non-finite value (landmark " + std::to_string(i / dim) + ", column " + std::to_string(i % dim) + ")";
+  if (!std::isfinite(gamma) || !(gamma > 0.f)) return "gamma must be finite and > 0";
+  return "";
+}
+
+int level_dim(const scann_handle* h, int32_t level) {
+  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+float scann_rbf_weight(float dist2, float gamma) { return rbf_weight(dist2, gamma); }
+
+void scann_rbf_weight_array(const float* dist2, int64_t n, float gamma, float* out) {
+  for (int64_t i = 0; dist2 && out && i < n; ++i) out[i] = rbf_weight(dist2[i], gamma);
+}
+
+int scann_rbf_features_host(const float* rows, int64_t n, int64_t dim, const float* landmarks, int32_t m, float gamma, float* phi) {
+  if (n < 0 || n > (int64_t)0x7fffffff || dim < 1 || (n > 0 && (!rows || !phi))) return SCANN_ERR_INVALID;
+  if (!check_landmarks(landmarks, m, dim, gamma).empty()) return SCANN_ERR_INVALID;
+  if (n == 0) return SCANN_OK;
+  scann_knn_distsq_matrix(rows, n, landmarks, m, dim, phi);  // the pool row is the chain's first argument
+  const float nan = std::nanf("");
+  for (int64_t p = 0; p < n; ++p) {
+    bool ok = true;
+    for (int64_t j = 0; j < dim; ++j) ok = ok && std::isfinite(rows[p * dim + j]);
+    for (int32_t c = 0; c < m; ++c) phi[p * m + c] = ok ? rbf_weight(phi[p * m + c], gamma) : nan;
+  }
+  return SCANN_OK;
+}
+
+int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float* landmarks, int32_t m, float gamma, scann_index_t* out) {
+  const std::string w = "scann_index_rbf_features: ";
+  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, w + "null handle or pool");
+  if (!out) return fail(h, SCANN_ERR_INVALID, w + "out is null");
+  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, w + "the pool belongs to another handle");
+  if (out->h != h) return fail(h, SCANN_ERR_INVALID, w + "out belongs to another handle");
+  if (out == pool) return fail(h, SCANN_ERR_INVALID, w + "out is the pool itself");
+  const std::string bad = check_landmarks(landmarks, m, pool->dim, gamma);
+  if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, w + bad);
+  if (out->n != 0 || !out->chunks.empty()) return fail(h, SCANN_ERR_INVALID, w + "out is not empty: it holds " + std::to_string(out->n) + " rows");
+  if (out->dim != m) return fail(h, SCANN_ERR_INVALID, w + "out holds rows of " + std::to_string(out->dim) + " columns, m is " + std::to_string(m));
+  const int64_t N = pool->n;
+  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the pool has too many rows");
+  if (N == 0) return SCANN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  const int32_t stride = pool->stride;
+  const int n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows), n_out = (int)((N + out->chunk_rows - 1) / out->chunk_rows);
+  const size_t bL = align_up((size_t)m * stride * 4), bT = align_up((size_t)n_chunk * 8), bO = align_up((size_t)n_out * 8);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bL + bT + bO));
+  int r = SCANN_OK;
+  for (int c = 0; c < n_out && !r; ++c) r = index_new_chunk(h, out, s);  // the chunks an append of N rows would take, cleared
+  hipError_t e = hipSuccess;
+  if (!r) {
+    std::vector<const void*> tab((size_t)n_chunk), otab((size_t)n_out);
+    for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+    for (int c = 0; c < n_out; ++c) otab[(size_t)c] = out->rows_of((size_t)c);
+    RbfArgs a{};
+    a.rows = reinterpret_cast<const float* const*>(ws + bL);
+    a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride;
+    a.lm = reinterpret_cast<const float*>(ws);
+    a.m = m; a.gamma = gamma;
+    a.out = reinterpret_cast<float* const*>(ws + bL + bT);
+    a.out_chunk_rows = out->chunk_rows; a.out_stride = out->stride;
+    e = hipMemsetAsync(ws, 0, bL, s);  // (the landmarks' padding columns are zero)
+    if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)stride * 4, landmarks, (size_t)pool->dim * 4, (size_t)pool->dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ws + bL, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bT, otab.data(), (size_t)n_out * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_rbf_features(a, s);
+    for (int c = 0; c < n_out && e == hipSuccess; ++c) {  // the ids travel with the rows: the pool's host copies
+      const int64_t r0 = (int64_t)c * out->chunk_rows;
+      e = hipMemcpyAsync(out->ids_of((size_t)c), pool->ids.data() + r0, (size_t)std::min<int64_t>(out->chunk_rows, N - r0) * 8, hipMemcpyHostToDevice, s);
+    }
+  }
+  const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
+  cached_free(ws);
+  if (r || e != hipSuccess || e_sync != hipSuccess) {  // nothing stays allocated: out is empty again
+    for (char* p : out->chunks) cached_free(p);
+    out->chunks.clear();
+  }
+  if (r) return r;
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  index_note_rows(out, N, pool->ids.data(), pool->atoms.data());
+  return SCANN_OK;
+}
+
+int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* landmarks, int32_t m, float gamma, const float* mean,
+                         const float* tmean, const float* weights, int32_t K, const float* components, int32_t mm, const float* scale, float lev0,
+                         float* y, float* ga, float* pred, float* lev, float* phi) {
+  const std::string w = "scann_rbf_head_batch: ";
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, w + "null handle or batch");
+  const int dim = level_dim(h, level);
+  if (!dim) return fail(h, SCANN_ERR_INVALID, w + "level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  std::string bad = check_landmarks(landmarks, m, dim, gamma);
+  if (bad.empty()) bad = check_head_eval(m, mean, tmean, weights, K, components, mm, scale, lev0, pred, lev);  // a head over the m features
+  if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, w + bad);
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, w + "weights not loaded");
+  const bool atom = level == SCANN_OUT_AFTER_LC;
+  const int64_t nq = atom ? db->n_atom : db->n_struct;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
+  if (nq <= 0) return SCANN_OK;
+  hipStream_t s = h->streams[db->last_slot];
+  const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
+  const int stride = (dim + 3) / 4 * 4, ms = (m + 3) / 4 * 4;
+  const size_t bL = align_up((size_t)m * stride * 4), bP = align_up(stride != dim ? (size_t)nq * stride * 4 : 0), bF = align_up((size_t)nq * ms * 4);
+  char* ws = nullptr;
+  HIPCHK(h, cached_malloc((void**)&ws, bL + bP + bF + 512));
+  float* feat = reinterpret_cast<float*>(ws + bL + bP);
+  hipError_t e = hipMemsetAsync(ws, 0, bL + bP, s);
+  if (stride != dim) {  // rows of the padded width, as an index keeps them
+    if (e == hipSuccess) e = hipMemcpy2DAsync(ws + bL, (size_t)stride * 4, src, (size_t)dim * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
+    src = reinterpret_cast<const float*>(ws + bL);
+  }
+  const void* tab[2] = {src, feat};
+  RbfArgs a{};
+  a.rows = reinterpret_cast<const float* const*>(ws + bL + bP + bF);
+  a.n_total = (int32_t)nq; a.chunk_rows = 0x7fffffff; a.stride = stride;
+  a.lm = reinterpret_cast<const float*>(ws);
+  a.m = m; a.gamma = gamma;
+  a.out = reinterpret_cast<float* const*>(ws + bL + bP + bF + 256);
+  a.out_chunk_rows = 0x7fffffff; a.out_stride = ms;
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)stride * 4, landmarks, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bP + bF, &tab[0], 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bP + bF + 256, &tab[1], 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_rbf_features(a, s);
+  if (e == hipSuccess && phi) e = hipMemcpy2DAsync(phi, (size_t)m * 4, feat, (size_t)ms * 4, (size_t)m * 4, (size_t)nq, hipMemcpyDeviceToHost, s);
+  int r = SCANN_OK;
+  if (e == hipSuccess) r = head_eval_rows(h, s, feat, ms, nq, m, mean, tmean, weights, K, components, mm, scale, lev0, pred, lev);  // (waits)
+  else (void)hipStreamSynchronize(s);
+  cached_free(ws);
+  HIPCHK(h, e);
+  return r;
+}
+
+}  // extern "C"

@@ -151,6 +151,12 @@ SYMBOLS = [
     ("scann_ridge_loo_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P,
                                        _P, _P]),
     ("scann_head_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P, _P, _P]),
+    ("scann_rbf_weight", C.c_float, [C.c_float, C.c_float]),
+    ("scann_rbf_weight_array", None, [_P, C.c_int64, C.c_float, _P]),
+    ("scann_index_rbf_features", C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P]),
+    ("scann_rbf_features_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_float, _P]),
+    ("scann_rbf_head_batch", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_float, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P, _P,
+                                       _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -177,6 +183,8 @@ MATCH_MAX_ATOMS = 128
 # the readout head on an index: the most targets and ridge strengths of one call (SCANN_HEAD_MAX_TARGETS, SCANN_HEAD_MAX_LAMBDA)
 HEAD_MAX_TARGETS = 16
 HEAD_MAX_LAMBDA = 32
+# Gaussian landmark features: the most landmarks of one call (the width limit of an index)
+RBF_MAX_LANDMARKS = 1024
 
 
 def check_knn_k(k):
@@ -494,6 +502,70 @@ def ridge_loo_host(rows, targets, mean, tmean, components, scale, coef, lev0, re
         raise ValueError("ridge_loo_host: invalid arguments (%d)" % rc)
     out["n"] = int(n.value)
     return out
+
+
+def rbf_gamma(bandwidth):
+    """gamma of the Gaussian landmark features for the bandwidth h, as a head stores it: float32(log2(e) / (2 h^2)), computed in fp64
+    and cast once, so that exp(-d^2 / 2 h^2) = 2^(-d^2 gamma).  ValueError unless h is a positive number whose gamma is finite and > 0."""
+    try:
+        h = float(bandwidth)
+    except (TypeError, ValueError):
+        raise ValueError("bandwidth must be a positive number, got %r" % (bandwidth,)) from None
+    if isinstance(bandwidth, bool) or not (h > 0.0 and np.isfinite(h)):
+        raise ValueError("bandwidth must be a positive number, got %r" % (bandwidth,))
+    with np.errstate(over="ignore", under="ignore"):
+        g = np.float32(np.log2(np.e) / (2.0 * h * h))
+    if not (np.isfinite(g) and g > 0):
+        raise ValueError("bandwidth %r gives gamma = %r in fp32, which must be finite and > 0" % (bandwidth, float(g)))
+    return float(g)
+
+
+def check_rbf_args(landmarks, gamma, dim=None):
+    """(landmarks [m, dim] fp32, gamma) of a feature pass as the C calls take them: 1 <= m <= RBF_MAX_LANDMARKS finite rows, gamma a
+    finite fp32 number > 0; ValueError otherwise, naming the argument."""
+    try:
+        z = np.ascontiguousarray(landmarks, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("landmarks must be an array of numbers") from None
+    if z.ndim != 2 or z.shape[1] < 1 or (dim is not None and z.shape[1] != int(dim)) or not 1 <= z.shape[0] <= RBF_MAX_LANDMARKS:
+        raise ValueError("landmarks must hold m rows%s, 1 <= m <= %d, got shape %s" % (
+            "" if dim is None else " of %d columns" % int(dim), RBF_MAX_LANDMARKS, z.shape))
+    bad = np.argwhere(~np.isfinite(z))
+    if len(bad):
+        raise ValueError("landmarks hold a non-finite value (landmark %d, column %d)" % (bad[0][0], bad[0][1]))
+    try:
+        g = np.float32(gamma)
+    except (TypeError, ValueError):
+        raise ValueError("gamma must be a number, got %r" % (gamma,)) from None
+    if isinstance(gamma, bool) or g.ndim != 0 or not (np.isfinite(g) and g > 0):
+        raise ValueError("gamma must be finite and > 0 in fp32, got %r" % (gamma,))
+    return z, float(g)
+
+
+def rbf_weight(dist2, gamma):
+    """2^(-dist2 gamma) as the feature kernel forms it (scann_rbf_weight, the definition in include/scann_hip.h): a number gives an
+    np.float32, an array an fp32 array of its shape.  No argument is checked: the chain is defined for every fp32 pair."""
+    lib = load_library()
+    if np.ndim(dist2) == 0:
+        return np.float32(lib.scann_rbf_weight(float(np.float32(dist2)), float(np.float32(gamma))))
+    d = np.ascontiguousarray(dist2, dtype=np.float32)
+    out = np.empty(d.shape, np.float32)
+    lib.scann_rbf_weight_array(_ptr(d), d.size, float(np.float32(gamma)), _ptr(out))
+    return out
+
+
+def rbf_features_host(rows, landmarks, gamma):
+    """The Gaussian landmark features on the host with the kernel's bits (scann_rbf_features_host): ``rows`` [n, dim], ``landmarks``
+    [m, dim] -> phi [n, m] fp32; a row with a non-finite component is NaN throughout."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rbf_features_host: rows of shape %s" % (rows.shape,))
+    z, g = check_rbf_args(landmarks, gamma, rows.shape[1])
+    phi = np.empty((rows.shape[0], z.shape[0]), np.float32)
+    rc = int(load_library().scann_rbf_features_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(z), z.shape[0], g, _ptr(phi)))
+    if rc < 0:
+        raise ValueError("rbf_features_host: invalid arguments (%d)" % rc)
+    return phi
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -1480,6 +1552,45 @@ class Engine:
                "lev": np.empty((n, K), np.float32)}
         self._check(self.lib.scann_head_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(tmean), _ptr(weights), K, _ptr(components), m,
                                               _ptr(scale), float(lev0), _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["pred"]), _ptr(out["lev"])))
+        return out
+
+    def index_rbf_features(self, ix, landmarks, gamma):
+        """The Gaussian features of every row of ``ix`` to ``landmarks`` [m, dim], computed on the device into a new index of m columns
+        that carries the rows' ids and atoms (scann_index_rbf_features), bit for bit ``rbf_features_host``.  The caller frees it."""
+        z, g = check_rbf_args(landmarks, gamma, ix.dim)
+        out = self.index_create(z.shape[0])
+        try:
+            self._check(self.lib.scann_index_rbf_features(self._h, ix._h, _ptr(z), z.shape[0], g, out._h))
+        except BaseException:
+            out.free()
+            raise
+        return out
+
+    def rbf_head_batch(self, rb, level, landmarks, gamma, mean, tmean, weights, components, scale, lev0, want_phi=True):
+        """One forward of a resident batch, the Gaussian features of its ``level`` rows and a head evaluated on them
+        (scann_rbf_head_batch; raw y): {"y" [n_struct], "ga" [n_atom], "pred", "lev" [n, K], with ``want_phi`` "phi" [n, m]}.
+        ``landmarks`` [m, dim]; over the m features ``mean`` [m], ``weights`` [K, m], ``components`` [mm, m], ``scale`` [K, mm]."""
+        z, g = check_rbf_args(landmarks, gamma)
+        mean, components, _ = check_pca_args(mean, components, None, z.shape[0])
+        tmean = np.ascontiguousarray(tmean, dtype=np.float32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        K, m, mm = tmean.shape[0] if tmean.ndim == 1 else 0, z.shape[0], components.shape[0]
+        if tmean.ndim != 1 or not 1 <= K <= HEAD_MAX_TARGETS or weights.shape != (K, m) or scale.shape != (K, mm):
+            raise ValueError("rbf_head_batch: tmean [K], weights [K, %d] and scale [K, %d] are needed, 1 <= K <= %d, got %s, %s and %s" % (
+                m, mm, HEAD_MAX_TARGETS, tmean.shape, weights.shape, scale.shape))
+        for name, a in (("tmean", tmean), ("weights", weights), ("scale", scale), ("lev0", np.float32(lev0))):
+            if not np.isfinite(a).all():
+                raise ValueError("%s holds a non-finite value" % name)
+        p = rb.packed
+        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "pred": np.empty((n, K), np.float32),
+               "lev": np.empty((n, K), np.float32)}
+        if want_phi:
+            out["phi"] = np.empty((n, m), np.float32)
+        self._check(self.lib.scann_rbf_head_batch(self._h, rb._h, int(level), _ptr(z), m, g, _ptr(mean), _ptr(tmean), _ptr(weights), K,
+                                                  _ptr(components), mm, _ptr(scale), float(lev0), _ptr(out["y"]), _ptr(out["ga"]),
+                                                  _ptr(out["pred"]), _ptr(out["lev"]), _ptr(out.get("phi"))))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

@@ -311,6 +311,68 @@ class LatentIndex:
         second = eng.index_ridge_loo(self._ix, t, fit["mean"], fit["tmean"], fit["components"], fit["scale"], fit["coef"], fit["lev0"], pick)
         return head_result(fit, second, pick, t, names, self.level, dim)
 
+    def fit_kernel_head(self, targets, landmarks=256, bandwidth="loo", l2="loo", names=None):
+        """A nonlinear readout head for ``targets`` (as ``fit_head`` takes them) on the frozen rows: ridge regression on the Gaussian
+        features phi_c(x) = exp(-|x - z_c|^2 / 2 h^2) to m landmarks -- kernel ridge regression with a fixed basis, i.e. sparse Gaussian
+        process regression --, the features computed on the GPU (scann_index_rbf_features) into a temporary index on which exactly
+        ``fit_head``'s sequence runs.  ``landmarks``: a count m (the first m picks of ``select(m + 1)``; the next pick's radius is their
+        covering radius R) or an integer array of positions in the index (R: the largest distance of a row to them).  ``bandwidth``:
+        "loo" -- h^2 = R^2 {1, 2, 4, 8, 16, 32} --, one positive distance h or a sequence of at most 8.  The bandwidth with the least
+        sum over the targets of leave-one-out sse / total sum of squares wins (targets without variance skipped), ties to the larger
+        h; one bandwidth serves all targets, the ridge strength stays per target (``l2`` as in ``fit_head``).  Returns ``(result,
+        head)``: ``fit_head``'s keys with "weights" [K, m] over the features, "bandwidth", "landmark_position", "landmark_id",
+        "landmark_atom", "covering_radius", "bandwidth_path": {"bandwidth" [G], "loo_rmse", "loo_r2" [G, K]}, and the
+        ``LatentKernelHead`` that ``HipModel.predict_kernel_head`` takes.  Bad arguments raise ValueError before any device call; so
+        do fewer usable rows than landmarks + 1 and a covering radius of 0, before any feature pass."""
+        t = _hip.check_head_targets(targets, len(self))
+        K = t.shape[1]
+        names = ["target_%d" % k for k in range(K)] if names is None else [str(x) for x in names]
+        if len(names) != K:
+            raise ValueError("names: %d for %d targets" % (len(names), K))
+        grid = head_grid(l2)
+        m, positions = kernel_landmarks_arg(landmarks, len(self))
+        kernel_bandwidth_arg(bandwidth)
+        if len(self) < 3:
+            raise ValueError("a head needs at least 3 rows, the index has %d" % len(self))
+        eng = self.model.engine
+        if positions is None:
+            sel = eng.index_select(self._ix, None, m + 1, 0.0)
+            if sel["count"] < m + 1:
+                raise ValueError("a kernel head needs more usable rows than landmarks: %d landmarks, %d rows without a non-finite component" % (
+                    m, sel["count"]))
+            positions, R2 = sel["position"][:m].copy(), float(sel["radius2"][m])
+            Z = np.concatenate([eng.index_read(self._ix, int(p), 1)[0] for p in positions])
+        else:
+            Z = np.concatenate([eng.index_read(self._ix, int(p), 1)[0] for p in positions])
+            _hip.check_rbf_args(Z, 1.0, self.dim)  # (a landmark must be a finite row)
+            ref = eng.index_create(self.dim)
+            try:
+                eng.index_add(ref, Z)
+                sel = eng.index_select(self._ix, ref, 1, 0.0)
+            finally:
+                ref.free()
+            R2 = float(sel["radius2"][0]) if sel["count"] >= 1 else 0.0
+        hs = kernel_bandwidths(bandwidth, R2)
+        ids, atoms = eng.index_names(self._ix)
+
+        def run(gamma):
+            feat = eng.index_rbf_features(self._ix, Z, gamma)
+            try:
+                try:
+                    mo = eng.index_fit_moments(feat, t)
+                except _hip.ScannHipError as e:
+                    if e.code == -1:
+                        raise ValueError(str(e)) from None
+                    raise
+                fit = head_closed_form(mo, m, grid)
+                args = (feat, t, fit["mean"], fit["tmean"], fit["components"], fit["scale"], fit["coef"], fit["lev0"])
+                pick = head_pick(eng.index_ridge_loo(*args)["sse"], fit["l2"])
+                return fit, eng.index_ridge_loo(*args, pick), pick
+            finally:
+                feat.free()
+
+        return kernel_head_result(run, hs, Z, R2, positions, ids, atoms, t, names, self.level, self.dim)
+
     def free(self):
         self._ix.free()
 
@@ -464,6 +526,156 @@ class LatentHead:
             raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
                 path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
         return cls(*args, level, dim, names)
+
+
+KERNEL_BANDWIDTH_FACTORS = (1.0, 2.0, 4.0, 8.0, 16.0, 32.0)  # bandwidth="loo": h^2 over the squared covering radius
+KERNEL_MAX_BANDWIDTHS = 8
+
+
+def kernel_landmarks_arg(landmarks, n_rows):
+    """``landmarks`` of ``fit_kernel_head`` checked: (m, None) for a count, (m, positions int64 [m]) for an integer array of distinct
+    positions in 0 .. n_rows - 1; ValueError otherwise"""
+    top = _hip.RBF_MAX_LANDMARKS
+    if isinstance(landmarks, (int, np.integer)) and not isinstance(landmarks, bool):
+        if not 1 <= int(landmarks) <= top:
+            raise ValueError("landmarks must be a count in 1 .. %d or an array of positions, got %r" % (top, landmarks))
+        return int(landmarks), None
+    a = np.asarray(landmarks)
+    if a.dtype.kind not in "iu" or a.ndim != 1 or not 1 <= a.shape[0] <= top:
+        raise ValueError("landmarks must be a count in 1 .. %d or an array of as many integer positions, got %r" % (top, landmarks))
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= int(n_rows) or len(np.unique(a)) != len(a):
+        raise ValueError("landmarks must name distinct positions in 0 .. %d, got %d of them in %d .. %d" % (int(n_rows) - 1, len(a), a.min(), a.max()))
+    return int(a.shape[0]), a
+
+
+def kernel_bandwidth_arg(bandwidth):
+    """``bandwidth`` of ``fit_kernel_head`` checked: None for "loo", else the fp64 distances [G], 1 <= G <= 8, each with a valid gamma
+    (``_hip.rbf_gamma``); ValueError otherwise"""
+    what = '"loo", a positive distance or a sequence of at most %d' % KERNEL_MAX_BANDWIDTHS
+    if isinstance(bandwidth, str):
+        if bandwidth != "loo":
+            raise ValueError("bandwidth must be %s, got %r" % (what, bandwidth))
+        return None
+    try:
+        h = np.atleast_1d(np.asarray(bandwidth, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("bandwidth must be %s, got %r" % (what, bandwidth)) from None
+    if isinstance(bandwidth, bool) or h.ndim != 1 or not 1 <= h.shape[0] <= KERNEL_MAX_BANDWIDTHS:
+        raise ValueError("bandwidth must be %s, got %r" % (what, bandwidth))
+    for x in h:
+        _hip.rbf_gamma(x)
+    return h
+
+
+def kernel_bandwidths(bandwidth, R2):
+    """The bandwidths to try, fp64 [G]: the caller's, or for "loo" sqrt(R2 f) over KERNEL_BANDWIDTH_FACTORS with R2 the squared
+    covering radius of the landmarks (fp32, as the selection reports it); ValueError for "loo" with an R2 that is 0 or not finite"""
+    h = kernel_bandwidth_arg(bandwidth)
+    if h is not None:
+        return h
+    if not (np.isfinite(R2) and R2 > 0.0):
+        raise ValueError("the landmarks' squared covering radius is %r: every other usable row coincides with a landmark (or lies "
+                         "infinitely far), so there is no scale for a bandwidth" % (R2,))
+    h = np.sqrt(float(R2) * np.asarray(KERNEL_BANDWIDTH_FACTORS, dtype=np.float64))
+    for x in h:
+        _hip.rbf_gamma(x)
+    return h
+
+
+def kernel_head_result(run, hs, Z, R2, positions, ids, atoms, t, names, level, dim):
+    """``fit_kernel_head``'s ``(result, head)``: ``run(gamma)`` -> (closed form, second leave-one-out pass, picks) on the features of
+    one bandwidth, tried for every bandwidth of ``hs``; the score is the fp64 sum over the targets with variance of sse / tss, the
+    least wins, ties to the larger h."""
+    G, K = len(hs), t.shape[1]
+    kk = np.arange(K)
+    path = {"bandwidth": np.asarray(hs, dtype=np.float64).copy(), "loo_rmse": np.zeros((G, K)), "loo_r2": np.zeros((G, K))}
+    best = None
+    for g in np.argsort(-path["bandwidth"], kind="stable"):  # larger h first: a later one must be strictly better
+        gamma = _hip.rbf_gamma(hs[g])
+        fit, loo, pick = run(gamma)
+        n = fit["n"]
+        sse, tss = loo["sse"][pick, kk], fit["tvar"] * (n - 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            path["loo_rmse"][g], path["loo_r2"][g] = np.sqrt(sse / n), 1.0 - sse / tss
+        score = sum(float(sse[k]) / float(tss[k]) for k in range(K) if tss[k] != 0)  # fp64, the targets in order
+        score = np.inf if np.isnan(score) else score
+        if best is None or score < best[0]:
+            best = (score, g, gamma, fit, loo, pick)
+    _, g, gamma, fit, loo, pick = best
+    result, inner = head_result(fit, loo, pick, t, names, level, Z.shape[0])
+    head = LatentKernelHead(Z, gamma, inner, level, dim, names)
+    positions = np.asarray(positions)
+    result.update({"bandwidth": float(hs[g]), "landmark_position": positions.astype(np.int32), "landmark_id": np.asarray(ids)[positions],
+                   "landmark_atom": np.asarray(atoms)[positions], "covering_radius": float(np.sqrt(np.float64(R2))), "bandwidth_path": path})
+    return result, head
+
+
+class LatentKernelHead:
+    """A ridge head on the Gaussian features of one level of one model, as ``LatentIndex.fit_kernel_head`` fits it: phi_c(x) =
+    2^(-|x - z_c|^2 gamma) to the landmarks z [m, dim], and ``head`` -- a ``LatentHead`` over the m features (its ``dim`` is m):
+    prediction_k = tmean_k + (phi - mean) . W_k, leverage_k as there, std_k = sqrt(sigma2_k (1 + leverage_k)), the predictive standard
+    deviation of sparse Gaussian process regression with this basis.  ``gamma`` is the fp32 value log2(e) / (2 h^2) the device uses."""
+
+    def __init__(self, landmarks, gamma, head, level, dim=None, names=None):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        if not isinstance(head, LatentHead):
+            raise ValueError("head must be a LatentHead over the features, got %r" % (type(head).__name__,))
+        self.landmarks, self.gamma = _hip.check_rbf_args(landmarks, gamma, dim)
+        if head.dim != self.landmarks.shape[0]:
+            raise ValueError("the head regresses on %d features, there are %d landmarks" % (head.dim, self.landmarks.shape[0]))
+        self.head, self.level, self.dim = head, level, int(self.landmarks.shape[1])
+        self.names = list(head.names) if names is None else [str(x) for x in names]
+        if len(self.names) != head.k:
+            raise ValueError("names: %d for %d targets" % (len(self.names), head.k))
+
+    @property
+    def k(self):
+        return self.head.k
+
+    @property
+    def m(self):
+        return int(self.landmarks.shape[0])
+
+    @property
+    def bandwidth(self):
+        """h of exp(-d^2 / 2 h^2), from the stored gamma"""
+        return float(np.sqrt(np.log2(np.e) / (2.0 * self.gamma)))
+
+    def check_model(self, model):
+        """ValueError unless the landmarks have the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level kernel head of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def finish(self, pred, lev, phi):
+        """the device's pred, lev [n, K] and phi [n, m] as {"prediction", "std", "leverage", "support"}: support is the largest
+        feature of the row -- how close it lies to its nearest landmark, in [0, 1]"""
+        out = self.head.finish(pred, lev)
+        out["support"] = phi.max(axis=1) if phi.shape[0] else np.zeros(0, np.float32)
+        return out
+
+    def save(self, path):
+        """An ``.npz`` of the landmarks, gamma, the inner head's arrays, level, dim and names (written to exactly ``path``; no pickle)."""
+        h = self.head
+        with open(path, "wb") as f:
+            np.savez(f, landmarks=self.landmarks, gamma=np.array(self.gamma, dtype=np.float32), mean=h.mean, tmean=h.tmean, weights=h.weights,
+                     components=h.components, scale=h.scale, lev0=np.array(h.lev0), sigma2=h.sigma2, l2=h.l2, level=np.array(self.level),
+                     dim=np.array(self.dim, dtype=np.int64), names=np.array(self.names, dtype=np.str_))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved kernel head; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            landmarks, gamma = z["landmarks"], float(z["gamma"])
+            args = [z[n] for n in ("mean", "tmean", "weights", "components", "scale")] + [float(z["lev0"]), z["sigma2"], z["l2"]]
+            names = [str(x) for x in z["names"]]
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level kernel head of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(landmarks, gamma, LatentHead(*args, level, None, names), level, dim, names)
 
 
 class LatentProjection:

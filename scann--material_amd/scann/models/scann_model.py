@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentClustering, LatentHead, LatentIndex, LatentProjection, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import LatentClustering, LatentHead, LatentIndex, LatentKernelHead, LatentProjection, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -614,6 +614,68 @@ class HipModel:
                 out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
         return out
 
+    def fit_kernel_head(self, data, targets, level="structure", landmarks=256, bandwidth="loo", l2="loo", ids=None, batch_size=None, names=None):
+        """A nonlinear readout head for another property on the model's frozen latent space (``LatentIndex.fit_kernel_head``): ridge
+        regression of ``targets`` on Gaussian features to ``landmarks`` of the ``level`` rows, features, moments and leave-one-out all on
+        the GPU -- what tells "the representation lacks the information" from "a linear head is too weak".  ``data`` and ``targets`` as
+        ``fit_head`` takes them.  Returns ``(result, head)``; the ``LatentKernelHead`` is what ``predict_kernel_head`` takes and can be
+        saved.  Bad arguments raise ValueError before anything is uploaded."""
+        from .latent_index import head_grid, kernel_bandwidth_arg, kernel_landmarks_arg
+
+        lvl = data.level if isinstance(data, LatentIndex) else level
+        level_dim(self.config, lvl)
+        if lvl == "atom" and isinstance(targets, (list, tuple)) and len(targets) and np.ndim(targets[0]) >= 1:
+            try:
+                targets = np.concatenate([np.asarray(x, dtype=np.float32).reshape(len(x), -1) for x in targets])
+            except (TypeError, ValueError):
+                raise ValueError("targets must be a flat array in packed order or one array per structure") from None
+        t = _hip.check_head_targets(targets, len(data) if isinstance(data, LatentIndex) else None)
+        head_grid(l2)
+        kernel_landmarks_arg(landmarks, len(data) if isinstance(data, LatentIndex) else len(t))
+        kernel_bandwidth_arg(bandwidth)
+        if names is not None and len(names) != t.shape[1]:
+            raise ValueError("names: %d for %d targets" % (len(names), t.shape[1]))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.fit_kernel_head(t, landmarks=landmarks, bandwidth=bandwidth, l2=l2, names=names)
+        finally:
+            if own is not None:
+                own.free()
+
+    def predict_kernel_head(self, inputs, head, batch_size=None):
+        """New ``inputs`` through a ``LatentKernelHead``, right behind their forward (scann_rbf_head_batch): the head's prediction of its K
+        targets, the predictive standard deviation sqrt(sigma2 (1 + leverage)) of sparse Gaussian process regression -- a nonlinear,
+        distance-aware uncertainty --, the leverage, and ``support``, the largest feature of the row: how close it lies to its nearest
+        landmark, in [0, 1].  A padded dict gives {"prediction", "std", "leverage": fp32 [B, K], "support": [B], "y": [B, 1] (the
+        model's own raw prediction), "ga": [B, M, 1]} and at atom level [B, M, K] / [B, M] arrays with 0 at padded atoms; a
+        ``PackedBatch`` gives packed [n_atom, ...] arrays.  A head of another width or a bad batch_size raise ValueError before anything
+        is uploaded."""
+        if not isinstance(head, LatentKernelHead):
+            raise ValueError("head must be a LatentKernelHead, got %r" % (type(head).__name__,))
+        head.check_model(self)
+        self._batch_size(batch_size)
+        eng, lvl, atom, h = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom", head.head
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.rbf_head_batch(
+            rb, lvl, head.landmarks, head.gamma, h.mean, h.tmean, h.weights, h.components, h.scale, h.lev0))
+        K = head.k
+        empty = {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32),
+                 "lev": np.zeros((0, K), np.float32), "phi": np.zeros((0, head.m), np.float32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = head.finish(cat["pred"], cat["lev"], cat["phi"])
+        out["y"], out["ga"] = cat["y"].reshape(-1, 1), cat["ga"]
+        if not isinstance(inputs, _hip.PackedBatch):
+            out["ga"] = _hip.repad_atoms(out["ga"], inputs["atom_mask"], 0)[..., None]
+            if atom:
+                for n in ("prediction", "std", "leverage", "support"):
+                    out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
+        return out
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -1187,6 +1249,18 @@ class SCANN:
         """HipModel.predict_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the head's
         prediction, std and leverage are in the units of the head's targets and stay as they are."""
         out = self.model.predict_head(ip, head, batch_size=batch_size)
+        out["y"] = out["y"] * self.std + self.mean
+        return out
+
+    def fit_kernel_head(self, data, targets, level="structure", landmarks=256, bandwidth="loo", l2="loo", ids=None, batch_size=None, names=None):
+        """HipModel.fit_kernel_head as it is: ``(result, head)``; the head lives in latent space and in the units of ``targets``."""
+        return self.model.fit_kernel_head(data, targets, level=level, landmarks=landmarks, bandwidth=bandwidth, l2=l2, ids=ids,
+                                          batch_size=batch_size, names=names)
+
+    def predict_kernel_head(self, ip, head, batch_size=None):
+        """HipModel.predict_kernel_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the
+        head's prediction, std, leverage and support stay as they are."""
+        out = self.model.predict_kernel_head(ip, head, batch_size=batch_size)
         out["y"] = out["y"] * self.std + self.mean
         return out
 
