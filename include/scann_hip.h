@@ -722,6 +722,52 @@ int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, c
                          const float* components /* [mm * m] */, int32_t mm, const float* scale /* [K * mm] */, float lev0, float* y, float* ga,
                          float* pred /* [n * K] */, float* lev /* [n * K] */, float* phi /* [n * m] or NULL */);
 
+/* ---- A classification head on an index: multinomial logistic regression ----
+ * The categorical twin of the readout head: is a class label (metal or insulator, crystal system, the kind of local structure an atom
+ * has) decodable from the frozen latent space, with probabilities.  Softmax regression has no closed form, so the fit is iterative; the
+ * split keeps a device result a function of the index contents and the arguments only, bit for bit.  The DEVICE PASS below has a fully
+ * specified definition: given the weights of M models at once it returns each model's log-likelihood gradient and a few score sums over
+ * the rows of the index, in the original coordinates (no projection pass, no N x m scratch).  The OPTIMISER runs on the host in fp64
+ * (LatentIndex.fit_class_head) and needs gradients only, so no logarithm has to be defined to the bit.
+ * The pass (scann_index_logit_pass), defined to the bit.  Every fp32 operation is rounded once, nothing is contracted beyond the stated
+ * fmaf; the host twin and the kernel run the same softmax body (csrc/scann_logit.h).
+ *   Rows that count: row p counts iff all its dim components are finite and 0 <= labels[p] < C; -1 means unlabelled.
+ *   Folds: the fold of row p is p mod F (p the position in the index), F = 0 or 2 .. 16.  Model j with fold[j] = f >= 0 trains on the
+ *     counting rows of the other folds and holds out fold f; with fold[j] = -1 it trains on all counting rows.  F = 0: every entry -1.
+ *   Logits of model j (weights U = weights[j], [C][dim + 1]): y_c = x_c - mean_c;  a_k: acc = U[k][dim] (the intercept), then
+ *     acc = fmaf(y_c, U[k][c], acc) for c ascending.
+ *   Softmax: amax = the fmaxf chain of the a_k, k ascending;  u_k = amax - a_k;  w_k = scann_rbf_weight(u_k, 0x1.715476p+0f) (the
+ *     bit-defined 2^-x above: e^-u_k, exactly 1 at the maximum);  S = the sum of the w_k, k ascending;  p_k = w_k / S, the IEEE correctly
+ *     rounded division.  Non-finite logits are not special-cased: a NaN propagates into that model's sums.
+ *   Per row: r_k = (k == label ? 1.0f : 0.0f) - p_k;  hit: the lowest k that no later logit exceeds (k moves on only for a_k' > a_k)
+ *     equals the label;  brier: b = fmaf(e_k, e_k, b) from 0 with e_k = p_k - onehot_k, k ascending.
+ *   Sums: fp64 over a fixed tree.  Within a block of 128 consecutive positions acc += term in position order; within a span of 32 blocks
+ *     the block sums are added in block order; the span sums are added in span order.  Launch geometry, storage chunks and the grouping
+ *     of models into launches are not part of the definition.
+ *   grad[j][k][c], c < dim: over the training rows of model j, fma((double)r_k, (double)y_c, acc) (the product is exact);  grad[j][k][dim]:
+ *     acc += (double)r_k.  stats[j][0][0 .. 2]: the training rows' count, hits, and brier (acc += (double)brier);  stats[j][1][..]: the
+ *     same over the held-out rows.  n_used: the rows that count.  prob [N * C] or NULL: for a row that counts the p_k under model
+ *     prob_of_fold[p mod max(F, 1)]; NaN where that entry is -1 and for rows that do not count.
+ * SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null argument, an index of another handle, C
+ * outside 2 .. 16, M outside 1 .. 64, F neither 0 nor 2 .. 16, a fold entry outside -1 .. F - 1, a prob_of_fold entry outside -1 .. M - 1, a
+ * non-finite mean or weight, a label outside -1 .. C - 1 (the position is named).  An empty pool returns zeros.  Synchronous, one host
+ * wait; nothing in the pool, the handle's weights, the training state or the output selection changes; inference and training handles
+ * at any width the index accepts.  scann_logit_pass_host (rows [n * dim]; no GPU) is the twin: the same bits.
+ * A classification head behind a forward (scann_logit_head_batch): one inference forward of the resident batch with the level's output
+ * added for that forward only (y, ga, range guard, exact-fp32 re-run and selection restore exactly as scann_head_batch), then the logit
+ * chain and the softmax above on the level's rows where the forward left them: prob [n * C], weights [C * (dim + 1)]. */
+#define SCANN_LOGIT_MAX_CLASSES 16
+#define SCANN_LOGIT_MAX_MODELS  64
+int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* [N] */, int32_t C, const float* mean /* [dim] */,
+                           const float* weights /* [M][C][dim + 1] */, int32_t M, const int32_t* fold /* [M] */, int32_t F,
+                           const int32_t* prob_of_fold /* [max(F,1)] or NULL */, int64_t* n_used, double* grad /* [M][C][dim + 1] */,
+                           double* stats /* [M][2][3] */, float* prob /* [N * C] or NULL */);
+int scann_logit_pass_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const float* mean, const float* weights,
+                          int32_t M, const int32_t* fold, int32_t F, const int32_t* prob_of_fold, int64_t* n_used, double* grad, double* stats,
+                          float* prob);
+int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean /* [dim] */,
+                           const float* weights /* [C][dim + 1] */, int32_t C, float* y, float* ga, float* prob /* [n * C] */);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -39,6 +39,12 @@ moments and leave-one-out on the GPU, the bandwidth chosen by leave-one-out.  It
 pickles the result as ``kernel_head_<target>.pickle`` and, with ``--kernel-head-out``, saves the head as a ``LatentKernelHead`` (.npz).
 ``--kernel-head FILE`` evaluates a saved one over the dataset and pickles one unpadded dict per structure (prediction, std, leverage,
 support) as ``kernel_head_<target>.pickle``.
+``--fit-class-head LABELS.npy [--class-head-level atom|structure] [--class-head-out FILE]`` fits a classification head instead:
+multinomial logistic regression of integer labels (one per structure, or per atom in dataset order; -1: unlabelled) on the frozen latent
+space, the ridge strength chosen by 4-fold cross-validation, every pass over the rows on the GPU.  It prints the cross-validation table,
+pickles the result as ``class_head_<target>.pickle`` and, with ``--class-head-out``, saves the head as a ``LatentClassHead`` (.npz).
+``--class-head FILE`` evaluates a saved one over the dataset and pickles one unpadded dict per structure (probability, label, confidence,
+entropy) as ``class_head_<target>.pickle``.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -117,6 +123,7 @@ def main(args):
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
     head_targets = check_head_flags(args)
     kernel_head_targets = check_kernel_head_flags(args)
+    class_labels = check_class_head_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -334,6 +341,72 @@ def main(args):
             raise SystemExit("--kernel-head: %s" % e) from None
         print("Evaluate the kernel head of %s (%s level, %d landmarks, %d targets: %s)" % (args.kernel_head, head.level, head.m, head.k, ", ".join(head.names)))
         pickle.dump(head_records(scann, data, head, kernel=True), open(os.path.join(args.trained_model, "kernel_head_{}.pickle".format(target)), "wb"))
+    if class_labels is not None:
+        pool = scann.build_index(data, level=args.class_head_level, ids=data.indexes)
+        print("Fit a classification head on the dataset's %d rows (%s level)" % (len(pool), args.class_head_level))
+        try:
+            res, head = scann.fit_class_head(pool, class_labels)
+        except ValueError as e:  # (the number of rows, too few labelled ones, a class without rows)
+            pool.free()
+            raise SystemExit("--fit-class-head: %s" % e) from None
+        res["id"], res["atom"] = pool.names()
+        print("n_rows %d, classes %s, counts %s" % (res["n_rows"], " ".join(str(c) for c in res["classes"]), " ".join(str(c) for c in res["class_count"])))
+        print("%12s %12s %12s %10s" % ("l2", "cv_accuracy", "cv_brier", "converged"))
+        for i, l2 in enumerate(res["path"]["l2"]):
+            print("%12.6g %12.6f %12.6g %10s" % (l2, res["path"]["cv_accuracy"][i], res["path"]["cv_brier"][i], bool(res["path"]["converged"][i])))
+        print("l2 %.6g: cv_accuracy %.6f, cv_brier %.6g, cv_log_loss %.6g, fit_accuracy %.6f, %d iterations, %d passes, %s" % (
+            res["l2"], res["cv_accuracy"], res["cv_brier"], res["cv_log_loss"], res["fit_accuracy"], res["iterations"], res["passes"], res["stopped"]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "class_head_{}.pickle".format(target)), "wb"))
+        if args.class_head_out:
+            head.save(args.class_head_out)
+        pool.free()
+    if args.class_head:
+        from scann.models import LatentClassHead
+
+        try:
+            head = LatentClassHead.load(scann.model, args.class_head)
+        except ValueError as e:
+            raise SystemExit("--class-head: %s" % e) from None
+        print("Evaluate the classification head of %s (%s level, classes %s)" % (args.class_head, head.level, " ".join(str(c) for c in head.classes)))
+        pickle.dump(class_head_records(scann, data, head), open(os.path.join(args.trained_model, "class_head_{}.pickle".format(target)), "wb"))
+
+
+def check_class_head_flags(args):
+    """--fit-class-head / --class-head checked before anything is loaded: the labels as int64 [N], or None without --fit-class-head"""
+    if args.fit_class_head and args.class_head:
+        raise SystemExit("--fit-class-head and --class-head: fit a classification head or evaluate one, not both")
+    if args.class_head_out and not args.fit_class_head:
+        raise SystemExit("--class-head-out: needs --fit-class-head")
+    if args.class_head and not os.path.isfile(args.class_head):
+        raise SystemExit("--class-head: no such file: %s" % args.class_head)
+    if not args.fit_class_head:
+        return None
+    try:
+        t = np.load(args.fit_class_head, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise SystemExit("--fit-class-head: cannot read %s: %s" % (args.fit_class_head, e)) from None
+    if t.dtype.kind not in "iu" or t.ndim != 1 or t.shape[0] < 4:
+        raise SystemExit("--fit-class-head: %s must hold integers of shape [N], N >= 4, got %s %s" % (args.fit_class_head, t.dtype, t.shape))
+    n_classes = len(np.unique(t[t != -1]))
+    if not 2 <= n_classes <= 16:
+        raise SystemExit("--fit-class-head: %s must hold 2 .. 16 distinct labels other than -1, got %d" % (args.fit_class_head, n_classes))
+    return np.ascontiguousarray(t, dtype=np.int64)
+
+
+def class_head_records(scann, data, head):
+    """--class-head: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = head.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = scann.predict_class_head(inputs, head)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["y"][i, 0])}
+            for key in ("probability", "label", "confidence", "entropy"):
+                d[key] = r[key][i][amask[i]] if atom else r[key][i]
+            per.append(d)
+    return per
 
 
 def check_kernel_head_flags(args):
@@ -491,6 +564,16 @@ def parser():
     p.add_argument("--head-out", type=str, default="", help="save the fitted head as a LatentHead (.npz) for SCANN.predict_head")
     p.add_argument("--head", type=str, default="",
                    help="a saved LatentHead (.npz): pickle its prediction, standard deviation and leverage per structure as head_<target>.pickle")
+    p.add_argument("--fit-class-head", type=str, default="",
+                   help="LABELS.npy, integers [N] (one per structure, or per atom in dataset order with --class-head-level atom; -1: unlabelled): "
+                        "fit a classification head on the latent space (softmax regression, cross-validated on the GPU) and pickle "
+                        "class_head_<target>.pickle")
+    p.add_argument("--class-head-level", type=str, default="structure", choices=["atom", "structure"],
+                   help="rows of --fit-class-head: bf_property per structure or after_Lc per atom")
+    p.add_argument("--class-head-out", type=str, default="", help="save the fitted head as a LatentClassHead (.npz) for SCANN.predict_class_head")
+    p.add_argument("--class-head", type=str, default="",
+                   help="a saved LatentClassHead (.npz): pickle its probabilities, label, confidence and entropy per structure as "
+                        "class_head_<target>.pickle")
     p.add_argument("--fit-kernel-head", type=str, default="",
                    help="TARGETS.npy as --fit-head takes it: fit a nonlinear readout head on Gaussian features to landmarks of the latent space "
                         "(features, moments and leave-one-out on the GPU) and pickle kernel_head_<target>.pickle")

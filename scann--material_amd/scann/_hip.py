@@ -157,6 +157,9 @@ SYMBOLS = [
     ("scann_rbf_features_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_float, _P]),
     ("scann_rbf_head_batch", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_float, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_float, _P, _P, _P,
                                        _P, _P]),
+    ("scann_index_logit_pass", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_logit_pass_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_logit_head_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -185,6 +188,10 @@ HEAD_MAX_TARGETS = 16
 HEAD_MAX_LAMBDA = 32
 # Gaussian landmark features: the most landmarks of one call (the width limit of an index)
 RBF_MAX_LANDMARKS = 1024
+# the classification head on an index: the most classes, models of one pass and folds (SCANN_LOGIT_MAX_CLASSES, SCANN_LOGIT_MAX_MODELS)
+LOGIT_MAX_CLASSES = 16
+LOGIT_MAX_MODELS = 64
+LOGIT_MAX_FOLDS = 16
 
 
 def check_knn_k(k):
@@ -500,6 +507,82 @@ def ridge_loo_host(rows, targets, mean, tmean, components, scale, coef, lev0, re
                                                  _ptr(out["sse_fit"]), _ptr(out["dof"]), _ptr(out.get("resid"))))
     if rc < 0:
         raise ValueError("ridge_loo_host: invalid arguments (%d)" % rc)
+    out["n"] = int(n.value)
+    return out
+
+
+def check_class_labels(labels, n_classes, n_rows=None):
+    """Class labels of a classification head as the C calls take them: int32 [N] in -1 .. n_classes - 1 (-1: unlabelled), 2 <= n_classes
+    <= LOGIT_MAX_CLASSES; ValueError otherwise, naming the argument and the first bad position."""
+    if isinstance(n_classes, bool) or not isinstance(n_classes, (int, np.integer)) or not 2 <= int(n_classes) <= LOGIT_MAX_CLASSES:
+        raise ValueError("C must be an integer in 2 .. %d, got %r" % (LOGIT_MAX_CLASSES, n_classes))
+    a = np.asarray(labels)
+    if a.dtype.kind not in "iu" or a.ndim != 1:
+        raise ValueError("labels must be an integer array of shape [N], got %s %s" % (a.dtype, a.shape))
+    if n_rows is not None and a.shape[0] != int(n_rows):
+        raise ValueError("labels hold %d rows, the index %d" % (a.shape[0], int(n_rows)))
+    bad = np.nonzero((a < -1) | (a >= int(n_classes)))[0]
+    if bad.size:
+        raise ValueError("labels[%d] = %d outside -1 .. %d" % (bad[0], int(a[bad[0]]), int(n_classes) - 1))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def check_logit_args(mean, weights, fold, folds, prob_of_fold, dim=None):
+    """The arguments of a classification pass as the C calls take them: mean [dim] and weights [M, C, dim + 1] finite fp32, 2 <= C <=
+    LOGIT_MAX_CLASSES, 1 <= M <= LOGIT_MAX_MODELS; folds F 0 or 2 .. 16; fold [M] int32 in -1 .. F - 1 (None: all -1); prob_of_fold None
+    or [max(F, 1)] int32 in -1 .. M - 1.  ValueError otherwise, naming the argument."""
+    try:
+        mean = np.ascontiguousarray(mean, dtype=np.float32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("mean and weights must be arrays of numbers") from None
+    if mean.ndim != 1 or mean.shape[0] < 1 or (dim is not None and mean.shape[0] != int(dim)):
+        raise ValueError("mean must hold %s values, got shape %s" % ("dim" if dim is None else int(dim), mean.shape))
+    d = mean.shape[0]
+    if weights.ndim != 3 or weights.shape[2] != d + 1 or not 2 <= weights.shape[1] <= LOGIT_MAX_CLASSES or not 1 <= weights.shape[0] <= LOGIT_MAX_MODELS:
+        raise ValueError("weights must have shape [M, C, %d], 1 <= M <= %d, 2 <= C <= %d, got %s" % (
+            d + 1, LOGIT_MAX_MODELS, LOGIT_MAX_CLASSES, weights.shape))
+    for name, a in (("mean", mean), ("weights", weights)):
+        if not np.isfinite(a).all():
+            raise ValueError("%s holds a non-finite value" % name)
+    M = weights.shape[0]
+    if isinstance(folds, bool) or not isinstance(folds, (int, np.integer)) or not (int(folds) == 0 or 2 <= int(folds) <= LOGIT_MAX_FOLDS):
+        raise ValueError("folds must be 0 or an integer in 2 .. %d, got %r" % (LOGIT_MAX_FOLDS, folds))
+    F = int(folds)
+    f = np.full(M, -1, np.int32) if fold is None else np.asarray(fold)
+    if f.dtype.kind not in "iu" or f.shape != (M,) or (f < -1).any() or (f >= F).any():
+        raise ValueError("fold must hold %d integers in -1 .. %d, got %r" % (M, F - 1, fold))
+    if prob_of_fold is not None:
+        q = np.asarray(prob_of_fold)
+        if q.dtype.kind not in "iu" or q.shape != (max(F, 1),) or (q < -1).any() or (q >= M).any():
+            raise ValueError("prob_of_fold must hold %d integers in -1 .. %d, got %r" % (max(F, 1), M - 1, prob_of_fold))
+        prob_of_fold = np.ascontiguousarray(q, dtype=np.int32)
+    return mean, weights, np.ascontiguousarray(f, dtype=np.int32), F, prob_of_fold
+
+
+def _logit_out(M, Cn, d, n, want_prob):
+    out = {"grad": np.zeros((M, Cn, d + 1)), "stats": np.zeros((M, 2, 3))}
+    if want_prob:
+        out["prob"] = np.full((n, Cn), np.nan, np.float32)
+    return out
+
+
+def logit_pass_host(rows, labels, mean, weights, fold=None, folds=0, prob_of_fold=None):
+    """The classification pass on the host with the kernel's bits (scann_logit_pass_host, the definition in include/scann_hip.h): {"n",
+    "grad" [M, C, dim + 1] fp64, "stats" [M, 2, 3] fp64 (training, then held-out rows: count, hits, brier), with ``prob_of_fold`` "prob"
+    [n, C] fp32}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("logit_pass_host: rows of shape %s" % (rows.shape,))
+    mean, weights, fold, F, prob_of_fold = check_logit_args(mean, weights, fold, folds, prob_of_fold, rows.shape[1])
+    M, Cn, _ = weights.shape
+    lab = check_class_labels(labels, Cn, rows.shape[0])
+    out = _logit_out(M, Cn, rows.shape[1], rows.shape[0], prob_of_fold is not None)
+    n = C.c_int64(0)
+    rc = int(load_library().scann_logit_pass_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(lab), Cn, _ptr(mean), _ptr(weights), M, _ptr(fold), F,
+                                                  _ptr(prob_of_fold), C.byref(n), _ptr(out["grad"]), _ptr(out["stats"]), _ptr(out.get("prob"))))
+    if rc < 0:
+        raise ValueError("logit_pass_host: invalid arguments (%d)" % rc)
     out["n"] = int(n.value)
     return out
 
@@ -1591,6 +1674,37 @@ class Engine:
         self._check(self.lib.scann_rbf_head_batch(self._h, rb._h, int(level), _ptr(z), m, g, _ptr(mean), _ptr(tmean), _ptr(weights), K,
                                                   _ptr(components), mm, _ptr(scale), float(lev0), _ptr(out["y"]), _ptr(out["ga"]),
                                                   _ptr(out["pred"]), _ptr(out["lev"]), _ptr(out.get("phi"))))
+        return out
+
+    def index_logit_pass(self, ix, labels, mean, weights, fold=None, folds=0, prob_of_fold=None):
+        """One pass of the classification head over the rows of ``ix`` on the device (scann_index_logit_pass): for every model of
+        ``weights`` [M, C, dim + 1] its log-likelihood gradient and score sums -- {"n", "grad" [M, C, dim + 1] fp64, "stats" [M, 2, 3]
+        fp64, with ``prob_of_fold`` "prob" [N, C] fp32} --, bit for bit ``logit_pass_host``."""
+        mean, weights, fold, F, prob_of_fold = check_logit_args(mean, weights, fold, folds, prob_of_fold, ix.dim)
+        M, Cn, _ = weights.shape
+        lab = check_class_labels(labels, Cn, len(ix))
+        out = _logit_out(M, Cn, ix.dim, len(ix), prob_of_fold is not None)
+        n = C.c_int64(0)
+        self._check(self.lib.scann_index_logit_pass(self._h, ix._h, _ptr(lab), Cn, _ptr(mean), _ptr(weights), M, _ptr(fold), F, _ptr(prob_of_fold),
+                                                    C.byref(n), _ptr(out["grad"]), _ptr(out["stats"]), _ptr(out.get("prob"))))
+        out["n"] = int(n.value)
+        return out
+
+    def logit_head_batch(self, rb, level, mean, weights):
+        """One forward of a resident batch and a classification head evaluated on each of its ``level`` rows (scann_logit_head_batch; raw
+        y): {"y" [n_struct], "ga" [n_atom], "prob" [n_struct or n_atom, C]}.  ``weights`` [C, dim + 1], the intercept last."""
+        try:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be an array of numbers") from None
+        if w.ndim != 2:
+            raise ValueError("logit_head_batch: weights must have shape [C, dim + 1], got %s" % (w.shape,))
+        mean, w3, _, _, _ = check_logit_args(mean, w[None], None, 0, None)
+        p = rb.packed
+        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "prob": np.empty((n, w.shape[0]), np.float32)}
+        self._check(self.lib.scann_logit_head_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(w3), w.shape[0], _ptr(out["y"]), _ptr(out["ga"]),
+                                                    _ptr(out["prob"])))
         return out
 
     def predict_mc(self, rb, samples, seed=0, keys=None, p_drop=None, p_attn=None, want_ga=True, want_samples=False):

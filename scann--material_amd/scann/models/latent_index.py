@@ -373,6 +373,41 @@ class LatentIndex:
 
         return kernel_head_result(run, hs, Z, R2, positions, ids, atoms, t, names, self.level, self.dim)
 
+    def fit_class_head(self, labels, l2="cv", folds=4, max_iter=100, tol=1e-4, classes=None):
+        """A classification head for ``labels`` (integers [N], one per row of this index; -1: unlabelled) on the frozen rows:
+        multinomial logistic regression (softmax, 2 .. 16 classes) in the principal axes of the rows, the ridge strength chosen by
+        ``folds``-fold cross-validation (the fold of a row is its position mod ``folds``).  Every pass over the rows -- for all strengths
+        and folds at once, each model's log-likelihood gradient and score sums (scann_index_logit_pass) -- runs on the GPU and depends
+        on the index contents and the arguments only, bit for bit; the optimiser (``class_head_fit``: L-BFGS in fp64 on the host, which
+        needs gradients only) is deterministic given them.  ``classes``: the label values in the order of the head's classes (None: the
+        distinct labels other than -1, ascending).  ``l2``: "cv" -- the grid max(s_0 10^-l, noise floor), l = 0 .. 5, s_0 the largest
+        eigenvalue --, one number, or a sequence of at most 8; ``folds`` 0 (one ``l2`` value only: no folds are fitted) or 2 .. 16.
+        The strength with the least held-out Brier sum wins, ties to the larger; the head is the all-rows model at that strength.
+        Returns ``(result, head)``: {"l2", "cv_accuracy", "cv_brier", "cv_log_loss" (fp64 on the host from the held-out probability of
+        the true class: this one statistic goes through the host's ``log``), "cv_confusion" [C, C] (true class, predicted class),
+        "fit_accuracy", "class_count" [C], "n_rows", "cv_probability" fp32 [N, C] (held out; NaN for rows that do not count),
+        "weights" fp32 [C, dim], "intercept" fp32 [C], "iterations", "converged", "stopped", "passes", "classes", "path": {"l2",
+        "cv_accuracy", "cv_brier", "converged"}} and the ``LatentClassHead`` that ``HipModel.predict_class_head`` takes.  With
+        ``folds=0`` the cv entries are NaN.  Bad arguments raise ValueError before any device call: fewer than 2 classes present, a
+        class without a labelled row, fewer labelled rows than 2 per fold, bad ``folds``, ``l2``, ``max_iter`` or ``tol``; a class
+        whose rows all have a non-finite component raises it after the first pass."""
+        lab, classes = class_labels_arg(labels, classes, len(self))
+        grid, folds, max_iter, tol = class_fit_args(l2, folds, max_iter, tol)
+        class_count_check(np.bincount(lab[lab >= 0], minlength=len(classes)), classes, folds)
+        eng = self.model.engine
+        try:
+            mo = eng.index_moments(self._ix)
+        except _hip.ScannHipError as e:
+            if e.code == -1:
+                raise ValueError(str(e)) from None
+            raise
+
+        def run_pass(weights, fold, prob_of_fold=None):
+            return eng.index_logit_pass(self._ix, lab, mo["mean"], weights, fold, folds, prob_of_fold)
+
+        fit = class_head_fit(run_pass, mo, lab, len(classes), grid, folds, max_iter, tol)
+        return class_head_result(fit, lab, classes, self.level, self.dim)
+
     def free(self):
         self._ix.free()
 
@@ -526,6 +561,323 @@ class LatentHead:
             raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
                 path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
         return cls(*args, level, dim, names)
+
+
+CLASS_L2_DECADES = 6      # l2="cv": max(s_0 10^-l, noise floor), l = 0 .. 5
+CLASS_MAX_L2 = 8
+CLASS_MEMORY = 8          # curvature pairs L-BFGS keeps
+CLASS_MAX_SHRINKS = 8     # secant shrinks of one line search
+CLASS_SLACK = 1e-6        # a step is accepted when the directional derivative at the new point is <= CLASS_SLACK |the one at the old point|
+
+
+def class_labels_arg(labels, classes, n_rows):
+    """``labels`` and ``classes`` of ``fit_class_head`` checked: (int32 [N] class indices with -1 for unlabelled, int64 [C] class values);
+    ValueError otherwise"""
+    a = np.asarray(labels)
+    if a.dtype.kind not in "iu" or a.ndim != 1:
+        raise ValueError("labels must be an integer array of shape [N], got %s %s" % (a.dtype, a.shape))
+    if a.shape[0] != int(n_rows):
+        raise ValueError("labels hold %d rows, the index %d" % (a.shape[0], int(n_rows)))
+    a = a.astype(np.int64)
+    if classes is None:
+        cl = np.unique(a[a != -1])
+    else:
+        try:
+            cl = np.asarray(classes)
+        except (TypeError, ValueError):
+            raise ValueError("classes must be a sequence of distinct integers other than -1") from None
+        if cl.dtype.kind not in "iu" or cl.ndim != 1 or len(np.unique(cl)) != len(cl) or (cl == -1).any():
+            raise ValueError("classes must be a sequence of distinct integers other than -1, got %r" % (classes,))
+        cl = cl.astype(np.int64)
+    if not 2 <= len(cl) <= _hip.LOGIT_MAX_CLASSES:
+        raise ValueError("a classification head needs 2 .. %d classes, the labels%s hold %d" % (
+            _hip.LOGIT_MAX_CLASSES, "" if classes is None else " and classes", len(cl)))
+    order = np.argsort(cl, kind="stable")
+    at = np.minimum(np.searchsorted(cl[order], a), len(cl) - 1)
+    known = cl[order][at] == a
+    bad = np.nonzero(~known & (a != -1))[0]
+    if bad.size:
+        raise ValueError("labels[%d] = %d is neither -1 nor one of the classes" % (bad[0], int(a[bad[0]])))
+    return np.ascontiguousarray(np.where(known, order[at], -1), dtype=np.int32), cl
+
+
+def class_fit_args(l2, folds, max_iter, tol):
+    """``l2``, ``folds``, ``max_iter`` and ``tol`` of ``fit_class_head`` checked: (None for "cv" or the fp64 strengths, folds, max_iter,
+    tol); ValueError otherwise"""
+    if isinstance(l2, str):
+        if l2 != "cv":
+            raise ValueError('l2 must be "cv", a number >= 0 or a sequence of at most %d, got %r' % (CLASS_MAX_L2, l2))
+        grid = None
+    else:
+        try:
+            grid = np.atleast_1d(np.asarray(l2, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError('l2 must be "cv", a number >= 0 or a sequence of at most %d, got %r' % (CLASS_MAX_L2, l2)) from None
+        if isinstance(l2, bool) or grid.ndim != 1 or not 1 <= grid.shape[0] <= CLASS_MAX_L2 or not np.isfinite(grid).all() or (grid < 0).any():
+            raise ValueError("l2 must hold 1 .. %d finite values >= 0, got %r" % (CLASS_MAX_L2, l2))
+    if isinstance(folds, bool) or not isinstance(folds, (int, np.integer)) or not (int(folds) == 0 or 2 <= int(folds) <= _hip.LOGIT_MAX_FOLDS):
+        raise ValueError("folds must be 0 or an integer in 2 .. %d, got %r" % (_hip.LOGIT_MAX_FOLDS, folds))
+    if int(folds) == 0 and (grid is None or len(grid) != 1):
+        raise ValueError("folds=0 fits no folds, so l2 must be one number, got %r" % (l2,))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or not 1 <= int(max_iter) <= 100000:
+        raise ValueError("max_iter must be an integer in 1 .. 100000, got %r" % (max_iter,))
+    try:
+        tol_f = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError("tol must be a number > 0, got %r" % (tol,)) from None
+    if isinstance(tol, bool) or not (tol_f > 0.0 and np.isfinite(tol_f)):
+        raise ValueError("tol must be a number > 0, got %r" % (tol,))
+    return grid, int(folds), int(max_iter), tol_f
+
+
+def class_count_check(count, classes, folds):
+    """ValueError for a class without a row, or fewer rows than 2 per fold"""
+    for k, c in enumerate(count):
+        if c < 1:
+            raise ValueError("class %d (label %d) has no row that counts" % (k, int(classes[k])))
+    if int(np.sum(count)) < 2 * max(int(folds), 1):
+        raise ValueError("%d folds need at least %d rows that count, got %d" % (folds, 2 * max(int(folds), 1), int(np.sum(count))))
+
+
+def class_head_fit(run_pass, mo, lab, n_classes, grid, folds, max_iter, tol):
+    """The optimiser of ``fit_class_head``, deterministic given the passes' outputs.  ``run_pass(weights fp32 [M, C, dim + 1], fold int32
+    [M], prob_of_fold=None)`` is ``Engine.index_logit_pass`` on the index, or ``_hip.logit_pass_host`` on the same rows: the host route.
+    ``mo``: the rows' moments (``index_moments`` / ``moments_host``); their covariance is decomposed (``_hip.sym_eig``) and components at
+    or below the noise floor are dropped, as ``head_closed_form`` does.  One model per (strength, fold) and one on all rows per
+    strength; model j minimises  sum_i nll_i + (n - 1) l2_j / 2 |W|^2,  W [C, m] in principal-axis coordinates, the intercept
+    unpenalised, n the rows that count.  L-BFGS (memory 8, fp64) per model, all models advancing in lockstep with one pass per round
+    (64 models at most per call).  The initial inverse Hessian is the diagonal 1 / ((n - 1)(s_c / 2 + l2)), 2 / n for the intercept:
+    Boehning's bound, valid for every fold because the all-row Gram matrix dominates every subset's.  Weights go to the device as U = W V
+    cast to fp32, gradients come back as V grad_x.  A step t (first 1) is accepted when the directional derivative at the new point is <=
+    CLASS_SLACK times the size of the one at the old point: the objective is convex, so up to that slack it did not rise along the step,
+    and no loss value is needed.  Otherwise t shrinks by the secant of the two directional derivatives, at most 8 times; then the model
+    stops with stopped="line_search".  Converged: max |grad| / n_train <= tol.  A non-finite gradient raises ValueError."""
+    C = int(n_classes)
+    dim = int(np.asarray(mo["mean"]).shape[0])
+    cov = np.asarray(mo["cov"], dtype=np.float64)
+    w, v, _ = _hip.sym_eig(cov)
+    noise = float(dim) * 2.0 ** (2 * int(np.asarray(mo["col_exp"]).max()) - int(mo["bits"]) + 2)
+    m = int((w > noise).sum())
+    if m < 1:
+        raise ValueError("no component of the rows' covariance lies above its noise floor %.3g: nothing to classify on" % noise)
+    s, V = w[:m], v[:m]
+    if grid is None:
+        grid = np.maximum(s[0] * 10.0 ** (-np.arange(CLASS_L2_DECADES, dtype=np.float64)), noise)
+        grid = grid[np.concatenate([[True], grid[1:] != grid[:-1]])]  # (non-increasing: duplicates are neighbours)
+    grid = np.asarray(grid, dtype=np.float64)
+    L, F = len(grid), int(folds)
+    model_l2 = np.repeat(grid, F + 1)
+    model_fold = np.tile(np.concatenate([np.arange(F), [-1]]), L).astype(np.int32)
+    M = L * (F + 1)
+    mean = np.ascontiguousarray(mo["mean"], dtype=np.float32)
+    passes = 0
+
+    def to_device(X):  # [.., C, m + 1] principal-axis weights and intercept -> U fp32 [.., C, dim + 1]
+        U = np.concatenate([X[..., :m] @ V, X[..., m:]], axis=-1)
+        with np.errstate(over="ignore"):
+            U = U.astype(np.float32)
+        if not np.isfinite(U).all():
+            raise ValueError("the weights left the range of fp32: l2 is too small for this index")
+        return U
+
+    def evaluate(idx, X):  # the passes of models idx at X [len(idx), C, m + 1] -> (log-likelihood gradient in principal axes, stats, n)
+        nonlocal passes
+        g, st, n = np.zeros((len(idx), C, m + 1)), np.zeros((len(idx), 2, 3)), 0
+        for a in range(0, len(idx), _hip.LOGIT_MAX_MODELS):
+            b = min(len(idx), a + _hip.LOGIT_MAX_MODELS)
+            r = run_pass(to_device(X[a:b]), model_fold[idx[a:b]])
+            passes += 1
+            g[a:b, :, :m] = r["grad"][:, :, :dim] @ V.T
+            g[a:b, :, m] = r["grad"][:, :, dim]
+            st[a:b], n = r["stats"], int(r["n"])
+        return g, st, n
+
+    everyone = np.arange(M)
+    X = np.zeros((M, C, m + 1))
+    g_ll, stats, n = evaluate(everyone, X)
+    p0 = float(np.float32(1.0) / np.float32(C))  # every probability at U = 0
+    j_all = F  # the first strength's all-rows model
+    count = np.rint(g_ll[j_all, :, m] + stats[j_all, 0, 0] * p0).astype(np.int64)
+    class_count_check(count, np.arange(C), F)
+    pen = (n - 1.0) * model_l2  # [M]
+    h0 = np.empty((M, C, m + 1))
+    h0[:, :, :m] = 1.0 / ((n - 1.0) * (s[None, None, :] / 2.0 + model_l2[:, None, None]))
+    h0[:, :, m] = 2.0 / n
+
+    def objective_grad(idx, X, g_ll):
+        g = -g_ll
+        g[:, :, :m] += pen[idx, None, None] * X[:, :, :m]
+        if not np.isfinite(g).all():
+            raise ValueError("a gradient is not finite (model %d): l2 is too small for this index, or the logits overflow fp32" % (
+                idx[int(np.nonzero(~np.isfinite(g).all(axis=(1, 2)))[0][0])]))
+        return g
+
+    G = objective_grad(everyone, X, g_ll)
+    n_train = stats[:, 0, 0].copy()
+    state = [{"S": [], "Y": [], "d": None, "t": 1.0, "dd0": 0.0, "it": 0, "shrinks": 0, "stopped": None} for _ in range(M)]
+
+    def direction(j):  # the two-loop recursion with the diagonal h0
+        st, q = state[j], G[j].ravel().copy()
+        al = []
+        for sv, yv in zip(reversed(st["S"]), reversed(st["Y"])):
+            a = float(sv @ q) / float(yv @ sv)
+            al.append(a)
+            q -= a * yv
+        q *= h0[j].ravel()
+        for (sv, yv), a in zip(zip(st["S"], st["Y"]), reversed(al)):
+            q += (a - float(yv @ q) / float(yv @ sv)) * sv
+        d = -q
+        dd = float(G[j].ravel() @ d)
+        if not dd < 0.0:  # (cannot happen with positive curvature pairs; start again from the diagonal)
+            st["S"], st["Y"] = [], []
+            d = -h0[j].ravel() * G[j].ravel()
+            dd = float(G[j].ravel() @ d)
+        st["d"], st["dd0"], st["t"], st["shrinks"] = d, dd, 1.0, 0
+
+    def settle(j):  # after a new point: converged, out of iterations, or the next direction
+        st = state[j]
+        if float(np.abs(G[j]).max()) / max(n_train[j], 1.0) <= tol:
+            st["stopped"] = "converged"
+        elif st["it"] >= max_iter:
+            st["stopped"] = "max_iter"
+        else:
+            direction(j)
+
+    for j in range(M):
+        settle(j)
+    while True:
+        idx = np.array([j for j in range(M) if state[j]["stopped"] is None], dtype=np.int64)
+        if not len(idx):
+            break
+        trial = np.stack([X[j] + (state[j]["t"] * state[j]["d"]).reshape(C, m + 1) for j in idx])
+        g_ll, st_new, _ = evaluate(idx, trial)
+        g_new = objective_grad(idx, trial, g_ll)
+        for a, j in enumerate(idx):
+            st = state[j]
+            dd1 = float(g_new[a].ravel() @ st["d"])
+            if dd1 <= CLASS_SLACK * abs(st["dd0"]):
+                sv, yv = st["t"] * st["d"], (g_new[a] - G[j]).ravel()
+                if float(yv @ sv) > 0.0:
+                    st["S"], st["Y"] = (st["S"] + [sv])[-CLASS_MEMORY:], (st["Y"] + [yv])[-CLASS_MEMORY:]
+                X[j], G[j], stats[j], n_train[j] = trial[a], g_new[a], st_new[a], st_new[a, 0, 0]
+                st["it"] += 1
+                settle(j)
+            elif st["shrinks"] >= CLASS_MAX_SHRINKS:
+                st["stopped"] = "line_search"
+            else:
+                st["shrinks"] += 1
+                st["t"] *= -st["dd0"] / (dd1 - st["dd0"])
+    # selection: the least held-out Brier sum over the folds, ties to the larger strength
+    conv = np.array([st["stopped"] == "converged" for st in state]).reshape(L, F + 1)
+    held = stats[:, 1, :].reshape(L, F + 1, 3)[:, :F, :].sum(axis=1)  # [L, 3]: rows, hits, brier
+    pick = 0
+    if F:
+        brier = np.where(np.isnan(held[:, 2]), np.inf, held[:, 2])
+        order = np.argsort(-grid, kind="stable")
+        pick = int(order[int(np.argmin(brier[order]))])  # (argmin: the first of equals, i.e. the larger strength)
+    sel = np.arange(pick * (F + 1), (pick + 1) * (F + 1))
+    prob = None
+    if F:
+        prob = run_pass(to_device(X[sel]), model_fold[sel], np.arange(F, dtype=np.int32))["prob"]
+        passes += 1
+    head_model = int(sel[-1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        path = {"l2": grid, "cv_accuracy": held[:, 1] / held[:, 0] if F else np.full(L, np.nan),
+                "cv_brier": held[:, 2] / held[:, 0] if F else np.full(L, np.nan), "converged": conv.all(axis=1)}
+    return {"n": n, "m": m, "mean": mean, "U": to_device(X[head_model]), "W": X[head_model].copy(), "V": V, "variance": s,
+            "l2": float(grid[pick]), "pick": pick, "path": path, "stats": stats[head_model].copy(), "prob": prob, "class_count": count,
+            "iterations": int(state[head_model]["it"]), "converged": bool(conv[pick].all()), "stopped": state[head_model]["stopped"],
+            "passes": passes, "folds": F, "noise_floor": noise}
+
+
+def class_head_result(fit, lab, classes, level, dim):
+    """``fit_class_head``'s ``(result, head)`` from the optimiser's output"""
+    C, N, F = len(classes), len(lab), fit["folds"]
+    U = fit["U"]
+    head = LatentClassHead(fit["mean"], U, classes, fit["l2"], level, dim)
+    pick = fit["pick"]
+    prob = fit["prob"] if F else np.full((N, C), np.nan, np.float32)
+    confusion = np.zeros((C, C), np.int64)
+    log_loss = float("nan")
+    if F:
+        ok = ~np.isnan(prob).any(axis=1) & (lab >= 0)
+        pred = np.argmax(prob[ok], axis=1)  # (the first of equals)
+        np.add.at(confusion, (lab[ok], pred), 1)
+        with np.errstate(divide="ignore"):
+            log_loss = float(-np.log(prob[ok, lab[ok]].astype(np.float64)).mean()) if ok.any() else float("nan")
+    st = fit["stats"]
+    result = {"l2": fit["l2"], "cv_accuracy": float(fit["path"]["cv_accuracy"][pick]), "cv_brier": float(fit["path"]["cv_brier"][pick]),
+              "cv_log_loss": log_loss, "cv_confusion": confusion, "fit_accuracy": float(st[0, 1] / st[0, 0]),
+              "class_count": fit["class_count"], "n_rows": fit["n"], "cv_probability": prob, "weights": np.ascontiguousarray(U[:, :dim]),
+              "intercept": np.ascontiguousarray(U[:, dim]), "iterations": fit["iterations"], "converged": fit["converged"],
+              "stopped": fit["stopped"], "passes": fit["passes"], "classes": np.asarray(classes, np.int64), "path": fit["path"]}
+    return result, head
+
+
+class LatentClassHead:
+    """A classification head on one level of one model, as ``LatentIndex.fit_class_head`` fits it: the logits a_k = intercept_k + (x -
+    mean) . W_k and their softmax.  mean [dim], weights [C, dim + 1] fp32 (the intercept in the last column), classes int64 [C] (the label
+    value of every class), l2 the strength it was fitted with."""
+
+    def __init__(self, mean, weights, classes, l2, level, dim=None):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        try:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be an array of numbers") from None
+        if w.ndim != 2:
+            raise ValueError("weights must have shape [C, dim + 1], got %s" % (w.shape,))
+        self.mean, w3, _, _, _ = _hip.check_logit_args(mean, w[None], None, 0, None, dim)
+        self.weights = w3[0]
+        cl = np.asarray(classes)
+        if cl.dtype.kind not in "iu" or cl.shape != (w.shape[0],) or len(np.unique(cl)) != len(cl):
+            raise ValueError("classes must hold %d distinct integers, got %r" % (w.shape[0], classes))
+        self.classes = cl.astype(np.int64)
+        try:
+            self.l2 = float(l2)
+        except (TypeError, ValueError):
+            raise ValueError("l2 must be a number, got %r" % (l2,)) from None
+        self.level, self.dim = level, int(self.mean.shape[0])
+
+    @property
+    def c(self):
+        return int(self.weights.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the head has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level head of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def finish(self, prob):
+        """the device's probabilities [n, C] as {"probability", "label" (the class value of the largest, the first of equals),
+        "confidence" (that probability), "entropy" (nats; fp64 on the host, 0 log 0 = 0)}"""
+        p = prob.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ent = -np.where(p > 0, p * np.log(p), np.where(np.isnan(p), np.nan, 0.0)).sum(axis=1)
+        best = np.argmax(np.where(np.isnan(prob), -np.inf, prob), axis=1) if len(prob) else np.zeros(0, np.int64)
+        return {"probability": prob, "label": self.classes[best], "confidence": prob[np.arange(len(prob)), best].astype(np.float32),
+                "entropy": ent.astype(np.float32)}
+
+    def save(self, path):
+        """An ``.npz`` of the head's arrays, level and dim (written to exactly ``path``; no pickle)."""
+        with open(path, "wb") as f:
+            np.savez(f, mean=self.mean, weights=self.weights, classes=self.classes, l2=np.array(self.l2), level=np.array(self.level),
+                     dim=np.array(self.dim, dtype=np.int64), kind=np.array("class_head"))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved head; ValueError if it is not one, or if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            if "kind" not in z.files or str(z["kind"]) != "class_head":
+                raise ValueError("%s: not a saved LatentClassHead" % path)
+            level, dim = str(z["level"]), int(z["dim"])
+            args = [z["mean"], z["weights"], z["classes"], float(z["l2"])]
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(*args, level, dim)
 
 
 KERNEL_BANDWIDTH_FACTORS = (1.0, 2.0, 4.0, 8.0, 16.0, 32.0)  # bandwidth="loo": h^2 over the squared covering radius

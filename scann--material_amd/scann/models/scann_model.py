@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentClustering, LatentHead, LatentIndex, LatentKernelHead, LatentProjection, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import LatentClassHead, LatentClustering, LatentHead, LatentIndex, LatentKernelHead, LatentProjection, batch_jobs, level_dim, stop_dist2_of
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -676,6 +676,62 @@ class HipModel:
                     out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
         return out
 
+    def fit_class_head(self, data, labels, level="structure", l2="cv", folds=4, max_iter=100, tol=1e-4, classes=None, ids=None, batch_size=None):
+        """A classification head on the model's frozen latent space (``LatentIndex.fit_class_head``): multinomial logistic regression of
+        integer ``labels`` (-1: unlabelled) on the ``bf_property`` rows (``level`` "structure", one label per structure) or the
+        ``after_Lc`` rows ("atom", one per real atom: a flat array in packed order or one array per structure), the ridge strength
+        chosen by cross-validation, every pass over the rows on the GPU.  ``data`` is a ``LatentIndex`` (its level counts, not
+        ``level``) or data as ``build_index`` takes it, which is indexed for the call and freed afterwards.  Returns ``(result,
+        head)``; the ``LatentClassHead`` is what ``predict_class_head`` takes and can be saved.  Bad arguments raise ValueError
+        before anything is uploaded."""
+        from .latent_index import class_count_check, class_fit_args, class_labels_arg
+
+        lvl = data.level if isinstance(data, LatentIndex) else level
+        level_dim(self.config, lvl)
+        if lvl == "atom" and isinstance(labels, (list, tuple)) and len(labels) and np.ndim(labels[0]) >= 1:
+            try:
+                labels = np.concatenate([np.asarray(x).reshape(-1) for x in labels])
+            except (TypeError, ValueError):
+                raise ValueError("labels must be a flat array in packed order or one array per structure") from None
+        labels = np.asarray(labels)
+        lab, cl = class_labels_arg(labels, classes, len(data) if isinstance(data, LatentIndex) else len(labels))
+        _, f, _, _ = class_fit_args(l2, folds, max_iter, tol)
+        class_count_check(np.bincount(lab[lab >= 0], minlength=len(cl)), cl, f)
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.fit_class_head(labels, l2=l2, folds=folds, max_iter=max_iter, tol=tol, classes=classes)
+        finally:
+            if own is not None:
+                own.free()
+
+    def predict_class_head(self, inputs, head, batch_size=None):
+        """New ``inputs`` through a ``LatentClassHead``, right behind their forward (scann_logit_head_batch): the class probabilities,
+        the most probable class, its probability, and the entropy of the probabilities in nats (computed on the host) -- an
+        uncertainty for a categorical prediction.  A padded dict gives {"probability": fp32 [B, C], "label": int64 [B], "confidence",
+        "entropy": fp32 [B], "y": [B, 1] (the model's own raw prediction)} and at atom level [B, M, C] / [B, M] arrays with 0 at
+        padded atoms; a ``PackedBatch`` gives packed [n_atom, ...] arrays.  A head of another width or a bad batch_size raise
+        ValueError before anything is uploaded."""
+        if not isinstance(head, LatentClassHead):
+            raise ValueError("head must be a LatentClassHead, got %r" % (type(head).__name__,))
+        head.check_model(self)
+        self._batch_size(batch_size)
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.logit_head_batch(rb, lvl, head.mean, head.weights))
+        empty = {"y": np.zeros(0, np.float32), "prob": np.zeros((0, head.c), np.float32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = head.finish(cat["prob"])
+        out["y"] = cat["y"].reshape(-1, 1)
+        if atom and not isinstance(inputs, _hip.PackedBatch):
+            for n in ("probability", "label", "confidence", "entropy"):
+                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
+        return out
+
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
         """Monte Carlo dropout: ``samples`` predictions with the graph's Dropout layers active -- Keras' ``model(x, training=True)`` T
@@ -1261,6 +1317,18 @@ class SCANN:
         """HipModel.predict_kernel_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the
         head's prediction, std, leverage and support stay as they are."""
         out = self.model.predict_kernel_head(ip, head, batch_size=batch_size)
+        out["y"] = out["y"] * self.std + self.mean
+        return out
+
+    def fit_class_head(self, data, labels, level="structure", l2="cv", folds=4, max_iter=100, tol=1e-4, classes=None, ids=None, batch_size=None):
+        """HipModel.fit_class_head as it is: ``(result, head)``; the head lives in latent space."""
+        return self.model.fit_class_head(data, labels, level=level, l2=l2, folds=folds, max_iter=max_iter, tol=tol, classes=classes, ids=ids,
+                                         batch_size=batch_size)
+
+    def predict_class_head(self, ip, head, batch_size=None):
+        """HipModel.predict_class_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the
+        probabilities, label, confidence and entropy stay as they are."""
+        out = self.model.predict_class_head(ip, head, batch_size=batch_size)
         out["y"] = out["y"] * self.std + self.mean
         return out
 

@@ -1,0 +1,439 @@
+"""GPU tests of the classification head on a latent index (scann_index_logit_pass / scann_logit_head_batch through
+Engine.index_logit_pass and logit_head_batch; LatentIndex.fit_class_head, HipModel.fit_class_head / predict_class_head).  Every
+comparison of a device result is an equality of bit patterns (a NaN equals a NaN).
+
+1. Engine.index_logit_pass == the twin scann_logit_pass_host: N either side of a block and of a span, dim 1 .. 1,024, C 2, 3, 16, more
+   than 64 logit columns, F 0, 2, 4, planted NaN / inf components and unlabelled rows, prob on and off, a repeat; two storage chunks; one
+   add or many; an empty pool.
+2. Engine.logit_head_batch on the qm9 and mp2018 fixtures at both levels == the twin on the level's downloaded rows; a generic width; an
+   exact-fp32 handle.  3. End to end against the host route, twice, and predict_class_head after a save and load.  4. Non-interference.
+5. Errors name the argument; the CLI."""
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":  # the child process of the exact-fp32 test
+    for p in (os.path.join(ROOT, "scann--material_amd"), os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__file__))):
+        sys.path.insert(0, p)
+
+import logit_ref  # noqa: E402
+import pca_ref  # noqa: E402
+import scann_oracle as so  # noqa: E402
+from test_gpu_knn import _bits, setup  # noqa: E402
+from test_gpu_pca import make_index, random_rows  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def engine(hip_lib):
+    cfg, w, inputs, model = setup(n=4)
+    yield model.engine
+    model.engine.close()
+
+
+def check_pass(engine, ix, args, label):
+    from scann import _hip
+
+    rows, lab, mean, U, fold, F, pof = args
+    want = _hip.logit_pass_host(rows, lab, mean, U, fold, F, pof)
+    got = engine.index_logit_pass(ix, lab, mean, U, fold, F, pof)
+    print("%s: n %d, %d grad values differ" % (label, got["n"], int((got["grad"].view(np.uint64) != want["grad"].view(np.uint64)).sum())))
+    logit_ref.same_pass(got, want, label)
+    logit_ref.same_pass(engine.index_logit_pass(ix, lab, mean, U, fold, F, pof), got, label + ", repeat")
+    plain = engine.index_logit_pass(ix, lab, mean, U, fold, F)
+    assert "prob" not in plain
+    logit_ref.same_pass(plain, {k: v for k, v in want.items() if k != "prob"}, label + ", no prob")
+    return got
+
+
+# (N, dim, C, M, F): the host test's shapes, and a width of 1,024
+CASES = [(1, 1, 2, 1, 0), (127, 3, 3, 2, 2), (129, 130, 16, 5, 4), (4095, 3, 2, 3, 4), (4097, 1, 3, 2, 2), (4097, 130, 3, 4, 0),
+         (9000, 64, 2, 20, 4), (300, 1024, 3, 2, 2), (700, 128, 2, 64, 4)]
+
+
+@pytest.mark.parametrize("case", CASES, ids=["N%d_d%d_C%d_M%d_F%d" % c for c in CASES])
+def test_pass_equals_the_host_twin(engine, case):
+    args = logit_ref.random_pass(*case, seed=case[0])
+    ix = make_index(engine, args[0])
+    try:
+        got = check_pass(engine, ix, args, str(case))
+    finally:
+        ix.free()
+    if case[0] >= 100:
+        assert 0 < got["n"] < case[0] and np.isnan(got["prob"]).any() and np.isfinite(got["prob"]).any()
+
+
+def test_pass_over_two_chunks(engine):
+    """17,000 x 1,024: a storage chunk holds 16,384 rows of 1,024 columns, so block 128 of span 3 ends the first chunk"""
+    N, dim = 17000, 1024
+    rows = random_rows(N, dim)
+    _, lab, _, U, fold, F, pof = logit_ref.random_pass(N, 8, 3, 3, 2, seed=4, planted=False)
+    lab[16383] = -1
+    rows[16384, 1000] = np.nan
+    U = (np.random.default_rng(4).standard_normal((3, 3, dim + 1)) / 32).astype(np.float32)
+    mean = rows[:100].mean(0).astype(np.float32)
+    ix = make_index(engine, rows)
+    try:
+        got = check_pass(engine, ix, (rows, lab, mean, U, fold, F, pof), "two chunks")
+    finally:
+        ix.free()
+    assert got["n"] == int((np.isfinite(rows).all(axis=1) & (lab >= 0)).sum()) < N
+
+
+def test_pass_does_not_depend_on_how_the_index_was_built(engine):
+    args = logit_ref.random_pass(3000, 130, 3, 4, 4, seed=9)
+    rows, lab, mean, U, fold, F, pof = args
+    one, many = engine.index_create(130), engine.index_create(130)
+    try:
+        engine.index_add(one, rows)
+        at = 0
+        for step in [1, 63, 64, 65, 7, 1000, 3, 500, 255, 257]:
+            engine.index_add(many, rows[at:at + step])
+            at += step
+        engine.index_add(many, rows[at:])
+        logit_ref.same_pass(engine.index_logit_pass(many, lab, mean, U, fold, F, pof), engine.index_logit_pass(one, lab, mean, U, fold, F, pof), "many adds")
+    finally:
+        one.free()
+        many.free()
+
+
+def test_pass_of_an_empty_pool_and_of_unlabelled_rows(engine):
+    rows, lab, mean, U, fold, F, pof = logit_ref.random_pass(200, 8, 3, 3, 2, seed=0)
+    ix = engine.index_create(8)
+    try:
+        got = engine.index_logit_pass(ix, np.zeros(0, np.int32), mean, U, fold, F, pof)
+        assert got["n"] == 0 and not got["grad"].any() and not got["stats"].any() and got["grad"].shape == (3, 3, 9) and got["prob"].shape == (0, 3)
+        engine.index_add(ix, rows)
+        got = engine.index_logit_pass(ix, np.full(200, -1, np.int32), mean, U, fold, F, pof)
+        assert got["n"] == 0 and not got["grad"].any() and not got["stats"].any() and np.isnan(got["prob"]).all()
+    finally:
+        ix.free()
+
+
+# ---- 2. the head behind a forward ----
+
+def random_class_head(dim, C, seed):
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal(dim).astype(np.float32), (rng.standard_normal((C, dim + 1)) / np.sqrt(dim)).astype(np.float32)
+
+
+def check_head_batch(model, data, label):
+    """logit_head_batch == the twin on the level's downloaded rows; y and ga those of a plain forward"""
+    from scann import _hip
+
+    eng = model.engine
+    rb = eng.upload(_hip.pack_inputs(data))
+    eng.forward_resident(rb)
+    y, ga = eng.download(rb)
+    for level, C in (("structure", 3), ("atom", 16)):
+        lvl = _hip.KNN_LEVELS[level]
+        dim = model.config["model"]["dense_out" if level == "structure" else "global_dim"]
+        pool = eng.index_create(dim)
+        eng.index_add_batch(pool, rb, lvl)
+        rows = eng.index_read(pool)[0]
+        pool.free()
+        mean, w = random_class_head(dim, C, seed=dim + C)
+        got = eng.logit_head_batch(rb, lvl, mean, w)
+        want = _hip.logit_pass_host(rows, np.zeros(len(rows), np.int32), mean, w[None], None, 0, [0])["prob"]
+        pca_ref.same(got["prob"], want, "%s %s prob" % (label, level))
+        assert got["prob"].shape == (len(rows), C) and np.isfinite(got["prob"]).all() and np.abs(got["prob"].sum(axis=1) - 1).max() < 1e-5
+        pca_ref.same(got["y"], y, "y")
+        pca_ref.same(got["ga"], ga, "ga")
+    rb.free()
+
+
+@pytest.mark.parametrize("kind", ["qm9", "mp2018"])
+def test_head_batch_is_the_twin_on_the_levels_rows(hip_lib, kind):
+    cfg, w, data, model = setup(kind=kind, n=24 if kind == "mp2018" else 40, seed=0)
+    check_head_batch(model, data, kind)
+
+
+def test_head_batch_on_a_generic_width_handle(hip_lib):
+    """rows of 30 and 96 columns, the first no multiple of 4"""
+    cfg, w, data, model = setup(n=9, seed=41, local_dim=64, num_head=4, global_dim=96, dense_out=30)
+    check_head_batch(model, data, "generic")
+
+
+def child_scenario():
+    cfg, w, data, model = setup(n=10, seed=3)
+    check_head_batch(model, data, "child")
+    return model.engine.exact_reruns()
+
+
+def test_head_batch_on_an_exact_fp32_handle(hip_lib):
+    """a handle whose forwards run exact-fp32 (SCANN_EXACT=1): a fresh process"""
+    e = dict(os.environ)
+    e["SCANN_EXACT"] = "1"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---- 3. end to end ----
+
+def labels_for(rows, C, seed=0):
+    """C classes cut along a random direction of the rows, with noise: learnable, not separable"""
+    rng = np.random.default_rng(seed)
+    x = np.nan_to_num(rows.astype(np.float64))
+    x = (x - x.mean(0)) / (x.std(0) + 1e-12)
+    score = x @ rng.standard_normal(rows.shape[1]) / np.sqrt(rows.shape[1]) + 0.3 * rng.standard_normal(len(rows))
+    return (np.searchsorted(np.quantile(score, np.arange(1, C) / C), score) * 5 + 2).astype(np.int64)  # class values 2, 7, 12, ...
+
+
+@pytest.mark.parametrize("level", ["structure", "atom"])
+@pytest.mark.parametrize("kind", ["qm9", "mp2018"])
+def test_fit_class_head_is_the_host_route_on_the_models_rows(hip_lib, kind, level, tmp_path):
+    from scann import _hip
+    from scann.models import LatentClassHead
+
+    n = {"qm9": 64, "mp2018": 24}[kind]
+    cfg, w, data, model = setup(kind=kind, n=n, seed=0)
+    index = model.build_index(data, level=level, batch_size=16, ids=np.arange(n) * 2 + 1)
+    rows = index.rows()[0]
+    lab = labels_for(rows, 3, seed=4)
+    lab[3] = -1
+    kw = dict(folds=4 if level == "atom" else 2, max_iter=30)
+    got, head = model.fit_class_head(index, lab, **kw)
+    want, head_w = logit_ref.host_fit(rows, lab, level=level, **kw)
+    print("%s %s: n_rows %d, l2 %.4g, cv_accuracy %.4f, cv_brier %.4g, cv_log_loss %.4g, fit_accuracy %.4f, iterations %d, passes %d, %s" % (
+        kind, level, got["n_rows"], got["l2"], got["cv_accuracy"], got["cv_brier"], got["cv_log_loss"], got["fit_accuracy"], got["iterations"],
+        got["passes"], got["stopped"]))
+    assert got["n_rows"] == len(rows) - 1 and list(got["classes"]) == [2, 7, 12] and 0.0 <= got["cv_accuracy"] <= 1.0
+    logit_ref.same_fit(got, head, want, head_w, label="%s %s" % (kind, level))
+    again, head_2 = index.fit_class_head(lab, **kw)
+    logit_ref.same_fit(again, head_2, got, head, skip=(), label="twice")
+    # predict_class_head right after, padded and packed: the head on the rows of the index
+    a = model.predict_class_head(data, head, batch_size=16)
+    pk = model.predict_class_head(_hip.pack_inputs(data), head, batch_size=16)
+    y, _ = model.predict(data)
+    assert np.array_equal(_bits(a["y"]), _bits(y)) and np.array_equal(_bits(pk["y"]), _bits(y))
+    prob = _hip.logit_pass_host(rows, np.zeros(len(rows), np.int32), head.mean, head.weights[None], None, 0, [0])["prob"]
+    pca_ref.same(pk["probability"], prob, "probability")
+    assert set(np.unique(pk["label"])) <= {2, 7, 12} and (pk["entropy"] >= 0).all() and (pk["entropy"] <= np.log(3) + 1e-6).all()
+    assert np.array_equal(pk["confidence"], prob.max(axis=1))
+    for key in ("probability", "label", "confidence", "entropy"):
+        pca_ref.same(a[key], pk[key] if level == "structure" else _hip.repad_atoms(pk[key], data["atom_mask"], 0), "padded " + key)
+    # data instead of an index (at atom level one array of labels per structure); save and load
+    if level == "atom":
+        counts = np.asarray(data["atom_mask"]).reshape(np.shape(data["neighbors"])[:2]).astype(bool).sum(1)
+        direct, _ = model.fit_class_head(data, np.split(lab, np.cumsum(counts)[:-1]), level="atom", batch_size=16, **kw)
+    else:
+        direct, _ = model.fit_class_head(data, lab, batch_size=16, **kw)
+    pca_ref.same(direct["cv_probability"], got["cv_probability"], "direct")
+    head.save(str(tmp_path / "ch.npz"))
+    back = LatentClassHead.load(model, str(tmp_path / "ch.npz"))
+    pca_ref.same(model.predict_class_head(data, back, batch_size=16)["probability"], a["probability"], "loaded head")
+    index.free()
+
+
+# ---- 4. state ----
+
+def test_nothing_else_changes(hip_lib):
+    from scann import _hip
+
+    cfg, w, data, model = setup(n=40, seed=2)
+    eng = model.engine
+    names = ["local_attention_1", "after_Lc"]
+    before = model.predict(data, outputs=names)
+    y0, ga0 = model.predict(data)
+    w0 = eng.get_weights()
+    eng.set_outputs([1], after_lc=True)
+    try:
+        rb = eng.upload(_hip.pack_inputs(data))
+        eng.forward_resident(rb)
+        y_first, _ = eng.download(rb)
+        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
+        pool = eng.index_create(128)
+        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
+        p0 = eng.index_read(pool)
+        q0 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
+        N = len(p0[0])
+        _, lab, _, U, fold, F, pof = logit_ref.random_pass(N, 128, 3, 5, 4, seed=7, planted=False)
+        mean = p0[0].mean(0).astype(np.float32)
+        first = eng.index_logit_pass(pool, lab, mean, U, fold, F, pof)
+        logit_ref.same_pass(first, _hip.logit_pass_host(p0[0], lab, mean, U, fold, F, pof), "model rows")
+        free0, _ = eng.device_memory()
+        for rep in range(5):
+            logit_ref.same_pass(eng.index_logit_pass(pool, lab, mean, U, fold, F, pof), first, "repeat")
+        free1, _ = eng.device_memory()
+        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
+        p1 = eng.index_read(pool)
+        for a, b in zip(p0, p1):
+            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        q1 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
+        for key in q0:
+            assert np.array_equal(q0[key].view(np.uint8), q1[key].view(np.uint8)), key
+        # the batch's last y and the selected outputs of its last forward are where they were
+        y_again, _ = eng.download(rb)
+        assert np.array_equal(_bits(y_again), _bits(y_first))
+        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
+        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
+        # logit_head_batch: y is the plain forward's; the selection is put back
+        hm, hw = random_class_head(128, 4, seed=1)
+        r = eng.logit_head_batch(rb, _hip.OUT_BF_PROPERTY, hm, hw)
+        assert np.array_equal(_bits(r["y"]), _bits(y_first))
+        eng.forward_resident(rb)
+        eng.download(rb)
+        with pytest.raises(_hip.ScannHipError):
+            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
+        rb.free()
+        pool.free()
+    finally:
+        eng.set_outputs()
+    w1 = eng.get_weights()
+    for key in w0:
+        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
+    after = model.predict(data, outputs=names)
+    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
+    y1, ga1 = model.predict(data)
+    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+
+
+# ---- 5. errors, the CLI ----
+
+def test_errors_name_what_is_wrong(hip_lib):
+    import ctypes as C
+
+    from scann import _hip
+
+    cfg, w, data, model = setup(n=4, seed=1)
+    eng = model.engine
+    cfg2, w2, _, other = setup(n=4, seed=1)
+    rows, lab, mean, U, fold, F, pof = logit_ref.random_pass(6, 4, 3, 3, 2, seed=0, planted=False)
+    pool, foreign = make_index(eng, rows), make_index(other.engine, rows)
+    P = _hip._ptr
+    grad, stats, prob = np.full((3, 3, 5), 7.0), np.full((3, 2, 3), 7.0), np.full((6, 3), 7, np.float32)
+    n = C.c_int64(-5)
+
+    def run(p=pool, lab=lab, Cn=3, mean=mean, U=U, M=3, fold=fold, F=2, pof=pof, n=n, grad=grad, stats=stats, prob=prob):
+        return eng.lib.scann_index_logit_pass(eng._h, None if p is None else p._h, P(lab), Cn, P(mean), P(U), M, P(fold), F, P(pof),
+                                              None if n is None else C.byref(n), P(grad), P(stats), P(prob))
+
+    def message():
+        return (eng.lib.scann_last_error(eng._h) or b"").decode()
+
+    def with_nan(a, at):
+        b = a.copy()
+        b.reshape(-1)[at] = np.nan
+        return b
+
+    free0, _ = eng.device_memory()
+    bad_lab = lab.copy()
+    bad_lab[4] = 3
+    for kw, word in ((dict(p=None), "null handle or pool"), (dict(p=foreign), "pool belongs to another handle"), (dict(Cn=1), "C 1 outside 2 .. 16"),
+                     (dict(Cn=17), "C 17 outside 2 .. 16"), (dict(M=0), "M 0 outside 1 .. 64"), (dict(M=65), "M 65 outside 1 .. 64"),
+                     (dict(F=1), "F 1 is neither 0 nor in 2 .. 16"), (dict(F=17), "F 17"), (dict(lab=None), "labels is null"),
+                     (dict(mean=None), "mean is null"), (dict(U=None), "weights is null"), (dict(fold=None), "fold is null"),
+                     (dict(n=None), "n_used is null"), (dict(grad=None), "grad is null"), (dict(stats=None), "stats is null"),
+                     (dict(pof=None), "prob needs prob_of_fold"), (dict(fold=np.array([0, 2, -1], np.int32)), "fold[1] = 2 outside -1 .. 1"),
+                     (dict(F=0), "fold[1] = 0 outside -1 .. -1"), (dict(pof=np.array([0, 3], np.int32)), "prob_of_fold[1] = 3 outside -1 .. 2"),
+                     (dict(mean=with_nan(mean, 2)), "mean holds a non-finite value (column 2)"),
+                     (dict(U=with_nan(U, 22)), "weights hold a non-finite value (model 1, class 1)"),
+                     (dict(lab=bad_lab), "labels[4] = 3 outside -1 .. 2")):
+        assert run(**kw) == -1 and word in message(), (word, message())
+    rb = eng.upload(_hip.pack_inputs(data))
+    hm, hw = random_class_head(128, 3, seed=0)
+    hp = np.full((4, 3), 7, np.float32)
+
+    def batch(level=_hip.OUT_BF_PROPERTY, b=rb, Cn=3, mean=hm, wts=hw, prob=hp):
+        return eng.lib.scann_logit_head_batch(eng._h, None if b is None else b._h, level, P(mean), P(wts), Cn, None, None, P(prob))
+
+    for kw, word in ((dict(b=None), "null handle or batch"), (dict(level=9), "got 9"), (dict(Cn=1), "C 1 outside 2 .. 16"), (dict(Cn=17), "C 17 outside"),
+                     (dict(mean=None), "mean is null"), (dict(wts=None), "weights is null"), (dict(prob=None), "prob is null"),
+                     (dict(mean=with_nan(hm, 5)), "mean holds a non-finite value (column 5)"),
+                     (dict(wts=with_nan(hw, 130)), "weights hold a non-finite value (class 1)")):
+        assert batch(**kw) == -1 and word in message(), (word, message())
+    # nothing was written, nothing stays allocated
+    assert np.all(grad == 7) and np.all(stats == 7) and np.all(prob == 7) and np.all(hp == 7) and n.value == -5
+    assert free0 - eng.device_memory()[0] <= 8 << 20
+    assert run() == 0 and n.value == 6 and batch() == 0
+    rb.free()
+    # the Python layers: ValueError before any device call
+    lat = model.build_index(data)
+    for bad in (np.zeros(3, np.int64), np.zeros(4, np.int64), np.arange(4.0), "x"):
+        with pytest.raises(ValueError):
+            lat.fit_class_head(bad)
+    good = np.array([0, 1, 0, 1])
+    for kw in (dict(l2="loo"), dict(folds=1), dict(folds=4), dict(max_iter=0), dict(tol=-1.0), dict(classes=[0, 1, 2])):
+        with pytest.raises(ValueError):
+            lat.fit_class_head(good, **kw)
+    with pytest.raises(ValueError):
+        other.fit_class_head(lat, good, folds=2)  # another model's index
+    with pytest.raises(ValueError):
+        model.predict_class_head(data, "a head")
+    with pytest.raises(ValueError, match="weights"):
+        eng.index_logit_pass(pool, lab, mean, U[:, :, :4], fold, F)
+    with pytest.raises(ValueError, match=r"labels\[4\] = 3"):
+        eng.index_logit_pass(pool, bad_lab, mean, U, fold, F)
+    for ix in (pool, foreign, lat):
+        ix.free()
+
+
+def test_cli_fits_and_applies_a_class_head(hip_lib, tmp_path):
+    """predict_model.py --fit-class-head writes class_head_<target>.pickle and, with --class-head-out, the head; --class-head applies it;
+    the other files' bytes are those of a run without the flags"""
+    import yaml
+
+    from scann.models import SCANN, LatentClassHead
+    from scann.models.scann_model import save_container
+
+    n = 20
+    de, dn = so.synth_dataset(n, 5)
+    full = np.empty(n, dtype=object)
+    for i in range(n):
+        full[i] = {"Atomic": de[i][0], "Properties": {"homo": float(i)}}
+    np.save(tmp_path / "data_energy.npy", full, allow_pickle=True)
+    np.save(tmp_path / "data_nei.npy", dn, allow_pickle=True)
+    cfg = so.default_config("qm9")
+    cfg["model"]["n_attention"] = 2
+    cfg["hyper"].update(batch_size=8, scaler=False, use_ref=False, target="homo", data_energy_path=str(tmp_path / "data_energy.npy"),
+                        data_nei_path=str(tmp_path / "data_nei.npy"), save_path=str(tmp_path / "run"))
+    out = tmp_path / "model"
+    os.makedirs(out / "models")
+    yaml.safe_dump(cfg, open(out / "config.yaml", "w"))
+    save_container(str(out / "models" / "model_homo.h5"), cfg, so.init_weights(cfg, 77, perturb=True))
+    lab = (np.arange(n) % 3).astype(np.int64)
+    lab[5] = -1
+    np.save(tmp_path / "l.npy", lab)
+    cli = [sys.executable, os.path.join(ROOT, "predict_model.py"), str(out)]
+    r = subprocess.run(cli, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    plain = {f: open(out / f, "rb").read() for f in ("ga_scores_homo.pickle", "energy_pre_homo.pickle")}
+    listed = set(os.listdir(out))
+    r = subprocess.run(cli + ["--fit-class-head", str(tmp_path / "l.npy"), "--class-head-out", str(tmp_path / "ch.npz")], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    for f, b in plain.items():
+        assert open(out / f, "rb").read() == b, f
+    assert set(os.listdir(out)) - listed == {"class_head_homo.pickle"}
+    got = pickle.load(open(out / "class_head_homo.pickle", "rb"))
+    scann = SCANN(yaml.safe_load(open(out / "config.yaml")), str(out / "models" / "model_homo.h5"), mode="infer")
+    scann.prepare_dataset(split=False)
+    data = scann.dataIter
+    pool = scann.build_index(data, level="structure", ids=data.indexes)
+    want, head = scann.fit_class_head(pool, lab)
+    assert sorted(got) == sorted(list(want) + ["id", "atom"])
+    for key in ("l2", "cv_accuracy", "cv_brier", "cv_probability", "weights", "intercept", "cv_confusion"):
+        assert np.array_equal(got[key], want[key], equal_nan=True), key
+    assert "cv_accuracy" in r.stdout and "cv_brier" in r.stdout and "n_rows %d" % (n - 1) in r.stdout
+    saved = LatentClassHead.load(scann.model, str(tmp_path / "ch.npz"))
+    for key in ("mean", "weights", "classes"):
+        pca_ref.same(getattr(saved, key), getattr(head, key), key)
+    r = subprocess.run(cli + ["--class-head", str(tmp_path / "ch.npz")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    per = pickle.load(open(out / "class_head_homo.pickle", "rb"))
+    assert len(per) == n and sorted(per[0]) == ["confidence", "entropy", "label", "predict_property", "probability"] and per[0]["probability"].shape == (3,)
+    inputs, _ = data[0]
+    first = scann.predict_class_head(inputs, head)
+    assert np.array_equal(per[0]["probability"], first["probability"][0]) and per[0]["label"] == first["label"][0]
+    pool.free()
+
+
+if __name__ == "__main__":
+    reruns = child_scenario()
+    print("child ok, exact re-runs %d" % reruns)
