@@ -1,6 +1,6 @@
 """Seeded batches on the large side of the launch code's size switches, shared by tests/test_sizes_host.py (which pins that they
-cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py and tests/test_gpu_parity.py (which compare
-the kernels on them with references).
+cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py, tests/test_gpu_output_sizes.py and
+tests/test_gpu_parity.py (which compare the kernels on them with references).
 
 The launch code picks a template instantiation, tile height, partial-sum partition or reduction kernel by row count; the
 constants below restate those thresholds, each next to the source line it mirrors.  If a threshold moves, the host test fails
@@ -52,6 +52,8 @@ LARGE = {
                         tile_rows=64),
     # 64-row edge tiles with every degree <= 16: the unfused attn_bwd16_kernel, 2 atoms per wave
     "qm9_b260": dict(atoms=ATTN_APW16_ATOMS, edges=EDGE_TILE_32_MAX_EDGES, degree=(1, FUSE_ATTN_MAX_DEGREE), tile_rows=64),
+    # the same with ring features (use_ring: the general embedding -- an embed launch, no per-species tables) on 64-row edge tiles
+    "qm9_ring_b260": dict(atoms=ATTN_APW16_ATOMS, edges=EDGE_TILE_32_MAX_EDGES, degree=(1, FUSE_ATTN_MAX_DEGREE), tile_rows=64),
     # rn_bwd_kernel<2>, atom_kernel<.., 2, ..>, 8 atoms per wave, two ln_bwd row groups on the edge rows, gen_ln_chunks > 64 rows
     "sparse_atoms": dict(atoms=max(ATOM_TILE_32_MAX, GEN_LN_64_ROWS_MAX, 7 * ATTN_APW16_ATOMS), edges=LN_BWD_ONE_GROUP_MAX,
                          degree=(1, FUSE_ATTN_MAX_DEGREE), tile_rows=64),
@@ -103,6 +105,13 @@ def mp2018_b128_data():
 def qm9_b260_data():
     """260 QM9-like molecules: 4,779 atoms, 35,837 edges, up to 12 neighbours"""
     return so.synth_dataset(260, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def qm9_ring_b260_data():
+    """260 QM9-like molecules with a ring / aromatic flag per atom (the generator draws them between the molecules, so the graphs are
+    not those of qm9_b260): 4,742 atoms, 35,569 edges, up to 12 neighbours"""
+    return so.synth_dataset(260, 1, use_ring=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -180,15 +189,15 @@ def deg40_data():
 
 # ---- batches: (PackedBatch, targets) ----
 
-def padded(data, g_update=True):
+def padded(data, g_update=True, use_ring=False):
     """the padded Keras input dict and targets of a dataset (so.pad_batch)"""
-    return so.pad_batch(*data, g_update=g_update)
+    return so.pad_batch(*data, g_update=g_update, use_ring=use_ring)
 
 
-def packed(data, g_update=True):
+def packed(data, g_update=True, use_ring=False):
     from scann import _hip
 
-    inputs, targets = padded(data, g_update)
+    inputs, targets = padded(data, g_update, use_ring)
     return _hip.pack_inputs(inputs), np.asarray(targets, np.float32)
 
 
@@ -198,6 +207,10 @@ def mp2018_b128(g_update=True):
 
 def qm9_b260(g_update=True):
     return packed(qm9_b260_data(), g_update)
+
+
+def qm9_ring_b260(g_update=True):
+    return packed(qm9_ring_b260_data(), g_update, use_ring=True)
 
 
 def sparse_atoms(g_update=True):

@@ -37,11 +37,13 @@ def oracle_outputs(cfg, w, inputs, dtype=np.float32):
     return ref
 
 
-def check_against_oracle(cfg, w, inputs, got, names, fp64_bound=False):
+def check_against_oracle(cfg, w, inputs, got, names, fp64_bound=False, refs=None, measured=None):
     """every output against the fp32 oracle (whole padded arrays); fp64_bound: the bound of test_branches, max(RTOL, 2 x the fp32
-    oracle's own error against fp64), for variants that are ill-conditioned in fp32"""
-    ref32 = oracle_outputs(cfg, w, inputs)
-    ref64 = oracle_outputs(cfg, w, inputs, np.float64) if fp64_bound else None
+    oracle's own error against fp64), for variants that are ill-conditioned in fp32.  refs: (oracle_outputs in fp32, in fp64 or None)
+    of these very cfg / w / inputs, computed by the caller once for several calls; measured: a list that receives (name, rel_err,
+    bound) of every output before it is asserted"""
+    ref32 = refs[0] if refs else oracle_outputs(cfg, w, inputs)
+    ref64 = (refs[1] if refs else oracle_outputs(cfg, w, inputs, np.float64)) if fp64_bound else None
     amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
     em = (np.asarray(inputs["neighbor_mask"]) != 0) & amask[:, :, None]
     has = em.any(-1)
@@ -52,6 +54,8 @@ def check_against_oracle(cfg, w, inputs, got, names, fp64_bound=False):
     for n, g in zip(names, got):
         assert g.shape == ref32[n].shape, (n, g.shape, ref32[n].shape)
         assert np.isfinite(g).all(), n
+        if measured is not None:
+            measured.append((n, rel_err(g, ref64[n]), max(RTOL, 2 * rel_err(ref32[n], ref64[n]))) if fp64_bound else (n, rel_err(g, ref32[n]), RTOL))
         if fp64_bound:
             assert rel_err(g, ref64[n]) <= max(RTOL, 2 * rel_err(ref32[n], ref64[n])), (n, rel_err(g, ref64[n]), rel_err(ref32[n], ref64[n]))
         else:

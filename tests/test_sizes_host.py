@@ -47,7 +47,7 @@ def test_wgrad_partition_restatement():
         assert s <= 80 and s * 64 * c >= rows > (s - 1) * 64 * c
 
 
-@pytest.mark.parametrize("name", ["mp2018_b128", "qm9_b260", "sparse_atoms"])
+@pytest.mark.parametrize("name", ["mp2018_b128", "qm9_b260", "qm9_ring_b260", "sparse_atoms"])
 def test_size_batches_cross_their_thresholds(hip_lib, name):
     pk, targets = getattr(sb, name)()
     deg = np.diff(pk.edge_offset)
@@ -58,7 +58,10 @@ def test_size_batches_cross_their_thresholds(hip_lib, name):
     assert not sb.small_side(pk.n_atom, pk.n_edge)
     # the measured sizes (a changed generator shows here first)
     assert (pk.n_struct, pk.n_atom, pk.n_edge, int(deg.max())) == {
-        "mp2018_b128": (128, 3252, 43462, 24), "qm9_b260": (260, 4779, 35837, 12), "sparse_atoms": (1900, 34231, 51255, 3)}[name]
+        "mp2018_b128": (128, 3252, 43462, 24), "qm9_b260": (260, 4779, 35837, 12), "qm9_ring_b260": (260, 4742, 35569, 12),
+        "sparse_atoms": (1900, 34231, 51255, 3)}[name]
+    if name == "qm9_ring_b260":
+        assert pk.ring is not None and np.asarray(pk.ring).shape == (pk.n_atom, 2)
     if name == "sparse_atoms":
         assert (deg == 0).sum() > 1000 and sb.layer_wgrad_bytes(pk.n_atom, pk.n_edge) >= sb.WGRAD_REDUCE4_BYTES
     if name == "mp2018_b128":
