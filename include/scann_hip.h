@@ -768,6 +768,42 @@ int scann_logit_pass_host(const float* rows, int64_t n, int64_t dim, const int32
 int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean /* [dim] */,
                            const float* weights /* [C][dim + 1] */, int32_t C, float* y, float* ga, float* prob /* [n * C] */);
 
+/* ---- A neighbour embedding (t-SNE) of an index: the iterations on the device ----
+ * The two-dimensional map of a latent space that keeps neighbourhoods (van der Maaten & Hinton, JMLR 2008): gradient descent on the
+ * Kullback-Leibler divergence between the neighbour affinities p of the rows and the Student-t affinities of the map, with the exact
+ * O(N^2) pair repulsion -- no Barnes-Hut, no interpolation --, so that a map is a function of the index contents and the arguments only,
+ * bit for bit.  The neighbour graph and the affinities are host work on top of scann_index_query (LatentIndex.embed); the call below runs
+ * n_iter iterations of the descent on a symmetric affinity graph in CSR form: row i's entries e in [row_first[i], row_first[i + 1]) name
+ * the rows col[e] with the weights p[e].
+ * The iteration, defined to the bit.  Every fp32 operation is rounded once, nothing is contracted beyond the stated fmaf, gradual
+ * underflow is part of the definition (no flush to zero), and every row reads the y of the iteration's start.  Every sum starts from +0.
+ *   Pair (i, j): dx = y[i][0] - y[j][0];  dy = y[i][1] - y[j][1];  d = fmaf(dy, dy, dx * dx);  w = 1.0f / (1.0f + d), the IEEE correctly
+ *     rounded division.
+ *   Repulsion of row i: positions j ascending, j = i skipped.  Within a block of 128 consecutive positions (block g: 128 g .. 128 g + 127)
+ *     the fp32 chains  z = z + w;  ww = w * w;  rx = fmaf(ww, dx, rx);  ry = fmaf(ww, dy, ry).  The block sums, converted to fp64, are
+ *     added in block order within a span of 32 blocks; the span sums are added in span order: Z_i, Rx_i, Ry_i.
+ *   Z: the sum of the Z_i over the same fp64 tree over i -- 128-row blocks in position order, 32-block spans, spans in order.
+ *   Attraction of row i: its entries e ascending, j = col[e], the pair as above:  q = p[e] * w;  ax = fmaf(q, dx, ax);  ay = fmaf(q, dy, ay).
+ *   Gradient, fp64, each operation rounded once:  gx = (float)(4.0 * ((double)exaggeration * (double)ax - Rx_i / Z)), and gy alike.
+ *   Update, per coordinate:  gain = ((g > 0) == (u > 0)) ? gain * 0.8f : gain + 0.2f;  gain = fmaxf(gain, 0.01f);  t = (lr * gain) * g;
+ *     u = fmaf(momentum, u, -t);  y' = y + u.
+ *   Centre: mean_c = (float)(S_c / (double)N), S_c the fp64 tree sum of the y'[.][c] over the positions;  y = y' - mean_c.
+ * y, u, gain [N * 2] are read and replaced; z_out is the Z and grad_out [N * 2] (or NULL) the gradient of the last iteration.  With
+ * n_iter = 0 nothing changes and z_out = 0.  Nothing non-finite that arises during the iterations is special-cased.  Launch geometry, the
+ * grouping of spans into workgroups and the work space (24 bytes per row and span: 101 MB at 134 k rows) are not part of the definition.
+ * The call uploads once, runs every iteration on the device, downloads once; synchronous, one host wait.  Nothing in the handle's weights,
+ * training state, output selection or any index changes; inference and training handles.  SCANN_ERR_INVALID before anything is launched,
+ * with a message that names the argument: a null argument, N outside 2 .. SCANN_EMBED_MAX_ROWS, row_first not starting at 0 or
+ * decreasing, a column outside 0 .. N - 1 or equal to its own row, a p that is negative or not finite, a non-finite y, u or gain, n_iter
+ * outside 0 .. 100000, exaggeration or lr not finite and positive, momentum outside [0, 1).  scann_embed_iterate_host (no GPU) is the
+ * twin: the same bits, the repulsion threaded over the rows. */
+#define SCANN_EMBED_MAX_ROWS 262144
+int scann_embed_iterate(scann_handle_t* h, int64_t N, const int64_t* row_first /* [N + 1] */, const int32_t* col /* [E] */,
+                        const float* p /* [E] */, float* y /* [N * 2] in/out */, float* u /* [N * 2] in/out */, float* gain /* [N * 2] in/out */,
+                        int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out /* [N * 2] or NULL */);
+int scann_embed_iterate_host(int64_t N, const int64_t* row_first, const int32_t* col, const float* p, float* y, float* u, float* gain,
+                             int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

@@ -45,6 +45,10 @@ space, the ridge strength chosen by 4-fold cross-validation, every pass over the
 pickles the result as ``class_head_<target>.pickle`` and, with ``--class-head-out``, saves the head as a ``LatentClassHead`` (.npz).
 ``--class-head FILE`` evaluates a saved one over the dataset and pickles one unpadded dict per structure (probability, label, confidence,
 entropy) as ``class_head_<target>.pickle``.
+``--embed [--embed-level atom|structure] [--embed-perplexity P] [--embed-out FILE]`` draws the neighbour embedding (t-SNE) of the
+dataset's rows in two dimensions, the pair repulsion computed exactly on the GPU and the map bit-reproducible.  It prints the divergence
+before and after, pickles the result (coordinates, ids, atoms, neighbour lists) as ``embedding_<target>.pickle`` and, with ``--embed-out``,
+saves the map as a ``LatentEmbedding`` (.npz) for ``SCANN.place``.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -124,6 +128,7 @@ def main(args):
     head_targets = check_head_flags(args)
     kernel_head_targets = check_kernel_head_flags(args)
     class_labels = check_class_head_flags(args)
+    check_embed_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -369,6 +374,29 @@ def main(args):
             raise SystemExit("--class-head: %s" % e) from None
         print("Evaluate the classification head of %s (%s level, classes %s)" % (args.class_head, head.level, " ".join(str(c) for c in head.classes)))
         pickle.dump(class_head_records(scann, data, head), open(os.path.join(args.trained_model, "class_head_{}.pickle".format(target)), "wb"))
+    if args.embed:
+        pool = scann.build_index(data, level=args.embed_level, ids=data.indexes)
+        print("Embed the dataset's %d rows (%s level, perplexity %g)" % (len(pool), args.embed_level, args.embed_perplexity))
+        try:
+            res, emb = scann.fit_embedding(pool, perplexity=args.embed_perplexity)
+        except ValueError as e:  # (too many or too few rows, a row with a non-finite component)
+            pool.free()
+            raise SystemExit("--embed: %s" % e) from None
+        res["id"], res["atom"] = pool.names()
+        print("n_rows %d, %d edges, learning rate %g: kl %.6f -> %.6f, z %.6g" % (
+            len(emb), res["n_edges"], res["learning_rate"], res["kl_init"], res["kl"], res["z"]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "embedding_{}.pickle".format(target)), "wb"))
+        if args.embed_out:
+            emb.save(args.embed_out)
+        pool.free()
+
+
+def check_embed_flags(args):
+    """--embed and its companions checked before anything is loaded"""
+    if args.embed_out and not args.embed:
+        raise SystemExit("--embed-out: needs --embed")
+    if args.embed and not 2 <= args.embed_perplexity <= 15:
+        raise SystemExit("--embed-perplexity: P must lie in 2 .. 15, got %g" % args.embed_perplexity)
 
 
 def check_class_head_flags(args):
@@ -584,6 +612,13 @@ def parser():
     p.add_argument("--kernel-head", type=str, default="",
                    help="a saved LatentKernelHead (.npz): pickle its prediction, standard deviation, leverage and support per structure as "
                         "kernel_head_<target>.pickle")
+    p.add_argument("--embed", action="store_true",
+                   help="draw the neighbour embedding (t-SNE) of the dataset's rows in two dimensions (exact pair repulsion on the GPU, "
+                        "bit-reproducible) and pickle embedding_<target>.pickle")
+    p.add_argument("--embed-level", type=str, default="structure", choices=["atom", "structure"],
+                   help="rows to embed: one per structure (bf_property) or one per atom (after_Lc)")
+    p.add_argument("--embed-perplexity", type=float, default=10.0, metavar="P", help="perplexity of --embed (2 .. 15)")
+    p.add_argument("--embed-out", type=str, default="", help="save the map as a LatentEmbedding (.npz) for SCANN.place")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

@@ -160,6 +160,8 @@ SYMBOLS = [
     ("scann_index_logit_pass", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("scann_logit_pass_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("scann_logit_head_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    ("scann_embed_iterate", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
+    ("scann_embed_iterate_host", C.c_int, [C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -192,6 +194,9 @@ RBF_MAX_LANDMARKS = 1024
 LOGIT_MAX_CLASSES = 16
 LOGIT_MAX_MODELS = 64
 LOGIT_MAX_FOLDS = 16
+# the neighbour embedding: the most rows of one map (SCANN_EMBED_MAX_ROWS) and iterations of one call
+EMBED_MAX_ROWS = 262144
+EMBED_MAX_ITER = 100000
 
 
 def check_knn_k(k):
@@ -584,6 +589,96 @@ def logit_pass_host(rows, labels, mean, weights, fold=None, folds=0, prob_of_fol
     if rc < 0:
         raise ValueError("logit_pass_host: invalid arguments (%d)" % rc)
     out["n"] = int(n.value)
+    return out
+
+
+def check_embed_args(row_first, col, p, y, u, gain, n_iter, exaggeration, momentum, lr):
+    """The arguments of an embedding iteration as the C calls take them -- row_first int64 [N + 1] from 0 and non-decreasing, col int32
+    [E] in 0 .. N - 1 and never its own row, p fp32 [E] finite and >= 0, y, u, gain fp32 [N, 2] finite (copies: the calls work in place),
+    2 <= N <= EMBED_MAX_ROWS, n_iter in 0 .. 100000, exaggeration and lr finite and > 0, momentum in [0, 1) -- ; ValueError otherwise,
+    naming the argument."""
+    out = []
+    for name, a in (("y", y), ("u", u), ("gain", gain)):
+        try:
+            a = np.array(a, dtype=np.float32, order="C")
+        except (TypeError, ValueError):
+            raise ValueError("%s must be an array of numbers [N, 2]" % name) from None
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s must have shape [N, 2], got %s" % (name, a.shape))
+        if not np.isfinite(a).all():
+            raise ValueError("%s holds a non-finite value (row %d)" % (name, int(np.nonzero(~np.isfinite(a).all(axis=1))[0][0])))
+        out.append(a)
+    y, u, gain = out
+    N = y.shape[0]
+    if not 2 <= N <= EMBED_MAX_ROWS:
+        raise ValueError("N = %d rows outside 2 .. %d" % (N, EMBED_MAX_ROWS))
+    if u.shape != y.shape or gain.shape != y.shape:
+        raise ValueError("u %s and gain %s must have y's shape %s" % (u.shape, gain.shape, y.shape))
+    rf = np.asarray(row_first)
+    if rf.dtype.kind not in "iu" or rf.shape != (N + 1,):
+        raise ValueError("row_first must hold %d integers, got %s %s" % (N + 1, rf.dtype, rf.shape))
+    rf = np.ascontiguousarray(rf, dtype=np.int64)
+    if rf[0] != 0:
+        raise ValueError("row_first must start at 0, got %d" % rf[0])
+    if (np.diff(rf) < 0).any():
+        raise ValueError("row_first decreases at row %d" % int(np.nonzero(np.diff(rf) < 0)[0][0]))
+    E = int(rf[-1])
+    c = np.asarray(col)
+    if c.dtype.kind not in "iu" or c.shape != (E,):
+        raise ValueError("col must hold %d integers (row_first[N]), got %s %s" % (E, c.dtype, c.shape))
+    if E and (c.min() < 0 or c.max() >= N):
+        at = int(np.nonzero((c < 0) | (c >= N))[0][0])
+        raise ValueError("col[%d] = %d outside 0 .. %d" % (at, int(c[at]), N - 1))
+    own = np.repeat(np.arange(N), np.diff(rf))
+    if (c == own).any():
+        at = int(np.nonzero(c == own)[0][0])
+        raise ValueError("col[%d] = %d is its own row" % (at, int(c[at])))
+    try:
+        pv = np.ascontiguousarray(p, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("p must be an array of numbers [E]") from None
+    if pv.shape != (E,):
+        raise ValueError("p must hold %d values (row_first[N]), got shape %s" % (E, pv.shape))
+    if E and not (np.isfinite(pv) & (pv >= 0)).all():
+        raise ValueError("p[%d] is negative or not finite" % int(np.nonzero(~(np.isfinite(pv) & (pv >= 0)))[0][0]))
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= int(n_iter) <= EMBED_MAX_ITER:
+        raise ValueError("n_iter must be an integer in 0 .. %d, got %r" % (EMBED_MAX_ITER, n_iter))
+    vals = []
+    for name, v in (("exaggeration", exaggeration), ("momentum", momentum), ("lr", lr)):
+        try:
+            f = float(np.float32(v))
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (name, v)) from None
+        if isinstance(v, bool):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        vals.append(f)
+    if not (np.isfinite(vals[0]) and vals[0] > 0):
+        raise ValueError("exaggeration must be finite and > 0, got %r" % (exaggeration,))
+    if not 0.0 <= vals[1] < 1.0:
+        raise ValueError("momentum must lie in [0, 1), got %r" % (momentum,))
+    if not (np.isfinite(vals[2]) and vals[2] > 0):
+        raise ValueError("lr must be finite and > 0, got %r" % (lr,))
+    return rf, np.ascontiguousarray(c, dtype=np.int32), pv, y, u, gain, int(n_iter), vals[0], vals[1], vals[2]
+
+
+def _embed_call(fn, args, want_grad):
+    rf, col, p, y, u, gain, n_iter, ex, mom, lr = args
+    grad = np.zeros_like(y) if want_grad else None
+    z = C.c_double(0.0)
+    rc = fn(y.shape[0], _ptr(rf), _ptr(col), _ptr(p), _ptr(y), _ptr(u), _ptr(gain), n_iter, ex, mom, lr, C.byref(z), _ptr(grad))
+    out = {"y": y, "u": u, "gain": gain, "z": float(z.value)}
+    if want_grad:
+        out["grad"] = grad
+    return rc, out
+
+
+def embed_iterate_host(row_first, col, p, y, u, gain, n_iter, exaggeration=1.0, momentum=0.8, lr=200.0, want_grad=False):
+    """``n_iter`` iterations of the neighbour embedding on the host with the kernels' bits (scann_embed_iterate_host, the definition in
+    include/scann_hip.h): {"y", "u", "gain" fp32 [N, 2] (new arrays), "z", with ``want_grad`` "grad" fp32 [N, 2] of the last iteration}."""
+    args = check_embed_args(row_first, col, p, y, u, gain, n_iter, exaggeration, momentum, lr)
+    rc, out = _embed_call(load_library().scann_embed_iterate_host, args, want_grad)
+    if rc < 0:
+        raise ValueError("embed_iterate_host: invalid arguments (%d)" % rc)
     return out
 
 
@@ -1688,6 +1783,14 @@ class Engine:
         self._check(self.lib.scann_index_logit_pass(self._h, ix._h, _ptr(lab), Cn, _ptr(mean), _ptr(weights), M, _ptr(fold), F, _ptr(prob_of_fold),
                                                     C.byref(n), _ptr(out["grad"]), _ptr(out["stats"]), _ptr(out.get("prob"))))
         out["n"] = int(n.value)
+        return out
+
+    def embed_iterate(self, row_first, col, p, y, u, gain, n_iter, exaggeration=1.0, momentum=0.8, lr=200.0, want_grad=False):
+        """``n_iter`` iterations of the neighbour embedding on the device (scann_embed_iterate: one upload, one download, nothing copied
+        back in between): ``embed_iterate_host``'s dict, bit for bit."""
+        args = check_embed_args(row_first, col, p, y, u, gain, n_iter, exaggeration, momentum, lr)
+        rc, out = _embed_call(lambda *a: self.lib.scann_embed_iterate(self._h, *a), args, want_grad)
+        self._check(rc)
         return out
 
     def logit_head_batch(self, rb, level, mean, weights):

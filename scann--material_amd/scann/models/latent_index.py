@@ -8,6 +8,7 @@ then position), so a query's answer depends on the query and the index contents 
 from __future__ import annotations
 
 import functools
+import math
 
 import numpy as np
 
@@ -407,6 +408,49 @@ class LatentIndex:
 
         fit = class_head_fit(run_pass, mo, lab, len(classes), grid, folds, max_iter, tol)
         return class_head_result(fit, lab, classes, self.level, self.dim)
+
+    def embed(self, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", route="device"):
+        """The neighbour embedding (t-SNE) of this index's rows in two dimensions: the map that keeps neighbourhoods, where ``pca`` draws
+        the linear one.  The repulsion between all pairs of rows is computed exactly on the GPU (scann_embed_iterate), so the map depends
+        on the index contents and the arguments only, bit for bit.  Each row's 31 nearest other rows come from the index's exact search
+        (``neighbour_graph``), their affinities from ``embed_affinities`` at ``perplexity`` (2 .. 15).  The initial layout is ``pca(2)``'s
+        coordinates scaled so that the first column's standard deviation is 1e-4, with zero velocity and unit gains.  Two calls of the
+        iteration follow: ``iterations[0]`` with ``exaggeration`` and momentum 0.5, then ``iterations[1]`` with exaggeration 1 and
+        momentum 0.8, both with ``learning_rate`` ("auto": max(200, N / 12)).  ``route`` "host" runs the host twin instead of the
+        device: the same bits.  Returns ``(result, embedding)``: {"coords" fp32 [N, 2], "kl_init", "kl" (the Kullback-Leibler divergence
+        over the stored edges, fp64 on the host, of the initial and of the final layout, each with its own Z from one more iteration
+        whose result is dropped), "z", "neighbor_position" int32 [N, K], "neighbor_dist2" fp32 [N, K], "n_edges", "learning_rate"} and
+        the ``LatentEmbedding`` that ``HipModel.place`` takes.  Bad arguments, an index above 262,144 rows, fewer rows than the
+        perplexity needs and rows with a non-finite component raise ValueError; the arguments are checked before any GPU work."""
+        perplexity, iterations, exaggeration, route = embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route)
+        N = len(self)
+        if N > _hip.EMBED_MAX_ROWS:
+            raise ValueError("the index has %d rows, an embedding takes at most %d: thin it first with select(m), or embed the medoids of "
+                             "cluster(k)" % (N, _hip.EMBED_MAX_ROWS))
+        if N - 1 <= perplexity or N < 3:
+            raise ValueError("perplexity %g needs more than %d rows, the index has %d" % (perplexity, int(perplexity) + 1, N))
+        lr = max(200.0, N / 12.0) if isinstance(learning_rate, str) else float(learning_rate)
+        eng = self.model.engine
+        pca, _ = self.pca(2)
+        y0 = embed_initial_layout(pca["coordinates"])
+        pos, d2 = neighbour_graph(self)
+        row_first, col, p = embed_affinities(d2, pos, perplexity)
+        if route == "device":
+            step = functools.partial(eng.embed_iterate, row_first, col, p)
+        else:
+            step = functools.partial(_hip.embed_iterate_host, row_first, col, p)
+        ids, atoms = eng.index_names(self._ix)
+        return embed_run(step, y0, row_first, col, p, iterations, exaggeration, lr, pos, d2, ids, atoms, perplexity, self.level, self.dim)
+
+    def place(self, rows, embedding):
+        """Host ``rows`` [n, dim] on an existing map of this index (``embedding``, as ``embed`` returned it for these rows): each row's
+        31 nearest index rows from the exact search, conditional weights calibrated to the embedding's perplexity
+        (``embed_conditional``), coordinates their weighted mean in fp64.  {"coords" fp32 [n, 2], "nearest_position" int32 [n],
+        "nearest_id" int64 [n], "nearest_atom" int32 [n], "nearest_distance" fp32 [n]}."""
+        embedding.check_index(self)
+        k = min(EMBED_NEIGHBOURS, len(self))
+        r = self.model.engine.index_query(self._ix, rows, k)
+        return embedding.place(r["position"], r["dist2"])
 
     def free(self):
         self._ix.free()
@@ -1141,3 +1185,293 @@ class LatentClustering:
         if self._index is not None:
             self._index.free()
         self._index = None
+
+
+EMBED_NEIGHBOURS = 31       # neighbours of a row in the affinity graph: one search with k = 32 less the row itself
+EMBED_PERPLEXITY = (2, 15)  # the perplexities 31 neighbours carry
+EMBED_BISECTIONS = 64       # steps of the precision search, fixed
+EMBED_BETA_CAP = 2.0 ** 40  # the largest precision, in units of 1 / (the row's mean shifted squared distance)
+
+
+def embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route):
+    """The arguments of ``LatentIndex.embed`` checked: (perplexity, (n_early, n_late), exaggeration, route); ValueError otherwise"""
+    try:
+        perp = float(perplexity)
+    except (TypeError, ValueError):
+        raise ValueError("perplexity must be a number in %d .. %d, got %r" % (EMBED_PERPLEXITY + (perplexity,))) from None
+    if isinstance(perplexity, bool) or not EMBED_PERPLEXITY[0] <= perp <= EMBED_PERPLEXITY[1]:
+        raise ValueError("perplexity must be a number in %d .. %d, got %r" % (EMBED_PERPLEXITY + (perplexity,)))
+    try:
+        its = tuple(iterations)
+    except TypeError:
+        raise ValueError("iterations must be two integers in 0 .. %d, got %r" % (_hip.EMBED_MAX_ITER, iterations)) from None
+    if len(its) != 2 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= _hip.EMBED_MAX_ITER for n in its):
+        raise ValueError("iterations must be two integers in 0 .. %d, got %r" % (_hip.EMBED_MAX_ITER, iterations))
+    try:
+        ex = float(exaggeration)
+    except (TypeError, ValueError):
+        raise ValueError("exaggeration must be a finite number > 0, got %r" % (exaggeration,)) from None
+    if isinstance(exaggeration, bool) or not (math.isfinite(ex) and ex > 0):
+        raise ValueError("exaggeration must be a finite number > 0, got %r" % (exaggeration,))
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise ValueError('learning_rate must be "auto" or a finite number > 0, got %r' % (learning_rate,))
+    else:
+        try:
+            lr = float(learning_rate)
+        except (TypeError, ValueError):
+            raise ValueError('learning_rate must be "auto" or a finite number > 0, got %r' % (learning_rate,)) from None
+        if isinstance(learning_rate, bool) or not (math.isfinite(lr) and lr > 0):
+            raise ValueError('learning_rate must be "auto" or a finite number > 0, got %r' % (learning_rate,))
+    if route not in ("device", "host"):
+        raise ValueError('route must be "device" or "host", got %r' % (route,))
+    return perp, (int(its[0]), int(its[1])), ex, route
+
+
+def neighbour_graph(index, chunk=4096):
+    """For every row of ``index`` its nearest other rows -- 31, or all others in a smaller index --: (position int32 [N, K], dist2 fp32
+    [N, K]), nearest first.  The rows are read back and searched ``chunk`` at a time with k = 32 and no id skipping
+    (``Engine.index_read`` + ``Engine.index_query``): bits and total order are the search's.  From a row's answer its own position is
+    dropped where it appears, otherwise (33 or more coincident rows) the last place.  ValueError for a row with a non-finite component."""
+    eng, ix = index.model.engine, index._ix
+    N = len(index)
+    k = min(EMBED_NEIGHBOURS + 1, N)
+    if k < 2:
+        raise ValueError("a neighbour graph needs at least 2 rows, the index has %d" % N)
+    pos, d2 = np.empty((N, k - 1), np.int32), np.empty((N, k - 1), np.float32)
+    for a in range(0, N, int(chunk)):
+        b = min(N, a + int(chunk))
+        rows, _, _ = eng.index_read(ix, a, b - a)
+        r = eng.index_query(ix, rows, k)
+        own = r["position"] == np.arange(a, b, dtype=np.int32)[:, None]
+        drop = np.where(own.any(axis=1), own.argmax(axis=1), k - 1)
+        keep = np.ones((b - a, k), bool)
+        keep[np.arange(b - a), drop] = False
+        pos[a:b] = r["position"][keep].reshape(b - a, k - 1)
+        d2[a:b] = r["dist2"][keep].reshape(b - a, k - 1)
+    if (pos < 0).any() or not np.isfinite(d2).all():
+        raise ValueError("row %d has no %d neighbours at a finite distance: rows with a non-finite component cannot be embedded" % (
+            int(np.nonzero((pos < 0).any(axis=1) | ~np.isfinite(d2).all(axis=1))[0][0]), k - 1))
+    return pos, d2
+
+
+def neighbour_graph_host(rows, chunk=1024):
+    """``neighbour_graph`` of host rows [N, dim] without a GPU: the search's distances (``_hip.knn_dist2_matrix``) ranked by (distance,
+    position), the search's total order, so the same bits and places."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    N = rows.shape[0]
+    k = min(EMBED_NEIGHBOURS + 1, N)
+    if rows.ndim != 2 or k < 2:
+        raise ValueError("a neighbour graph needs rows [N, dim] with N >= 2, got shape %s" % (rows.shape,))
+    pos, d2 = np.empty((N, k - 1), np.int32), np.empty((N, k - 1), np.float32)
+    for a in range(0, N, int(chunk)):
+        b = min(N, a + int(chunk))
+        d = _hip.knn_dist2_matrix(rows[a:b], rows)
+        order = np.argsort(d, axis=1, kind="stable")[:, :k]  # (stable: equal distances stay in position order)
+        own = order == np.arange(a, b)[:, None]
+        drop = np.where(own.any(axis=1), own.argmax(axis=1), k - 1)
+        keep = np.ones((b - a, k), bool)
+        keep[np.arange(b - a), drop] = False
+        pos[a:b] = order[keep].reshape(b - a, k - 1)
+        d2[a:b] = np.take_along_axis(d, order, axis=1)[keep].reshape(b - a, k - 1)
+    if not np.isfinite(d2).all():
+        raise ValueError("row %d has no %d neighbours at a finite distance: rows with a non-finite component cannot be embedded" % (
+            int(np.nonzero(~np.isfinite(d2).all(axis=1))[0][0]), k - 1))
+    return pos, d2
+
+
+def embed_rows_host(rows, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", ids=None, atoms=None, level="structure"):
+    """``LatentIndex.embed`` of host rows [N, dim] entirely on the host, no GPU: the twins of the moments, the projection, the search's
+    distances and the iteration -- bit for bit what an index holding these rows gives by either route."""
+    perplexity, iterations, exaggeration, _ = embed_fit_args(perplexity, iterations, exaggeration, learning_rate, "host")
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 2:
+        raise ValueError("rows must have shape [N, dim] with dim >= 2, got %s" % (rows.shape,))
+    N, dim = rows.shape
+    if N > _hip.EMBED_MAX_ROWS:
+        raise ValueError("%d rows, an embedding takes at most %d" % (N, _hip.EMBED_MAX_ROWS))
+    if N - 1 <= perplexity or N < 3:
+        raise ValueError("perplexity %g needs more than %d rows, got %d" % (perplexity, int(perplexity) + 1, N))
+    lr = max(200.0, N / 12.0) if isinstance(learning_rate, str) else float(learning_rate)
+    mo = _hip.moments_host(rows)
+    _, v, _ = _hip.sym_eig(mo["cov"])
+    y0 = embed_initial_layout(_hip.project_host(rows, mo["mean"], v[:2].astype(np.float32))["coords"])
+    pos, d2 = neighbour_graph_host(rows)
+    row_first, col, p = embed_affinities(d2, pos, perplexity)
+    ids = np.arange(N, dtype=np.int64) if ids is None else ids
+    atoms = np.full(N, -1, np.int32) if atoms is None else atoms
+    step = functools.partial(_hip.embed_iterate_host, row_first, col, p)
+    return embed_run(step, y0, row_first, col, p, iterations, exaggeration, lr, pos, d2, ids, atoms, perplexity, level, dim)
+
+
+def embed_conditional(dist2, perplexity):
+    """The conditional distribution of every row over its K neighbours, fp64 [n, K]: p_j = exp(-beta d_j) / sum, d_j the squared
+    distance less the row's least one, beta found per row by ``EMBED_BISECTIONS`` = 64 steps -- doubling until the entropy falls below
+    log(perplexity), then halving the bracket -- in units of 1 / (the row's mean d; 1 if that is 0) and capped at ``EMBED_BETA_CAP`` =
+    2^40 of them.  A row whose distances are all equal has the entropy log K at every beta, ends at the cap and stays uniform and
+    finite; so does a row of zeros.  ValueError unless the perplexity lies below K."""
+    d = np.asarray(dist2, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] < 2 or not np.isfinite(d).all():
+        raise ValueError("dist2 must be a finite array [n, K] with K >= 2, got shape %s" % (d.shape,))
+    perp = float(perplexity)
+    if not 1.0 < perp < d.shape[1]:
+        raise ValueError("perplexity %g must lie above 1 and below the %d neighbours" % (perp, d.shape[1]))
+    d = d - d.min(axis=1, keepdims=True)
+    scale = d.mean(axis=1, keepdims=True)
+    d = d / np.where(scale > 0, scale, 1.0)
+    target = math.log(perp)
+    n = d.shape[0]
+    lo, hi, beta = np.zeros((n, 1)), np.full((n, 1), np.inf), np.ones((n, 1))
+    for _ in range(EMBED_BISECTIONS):
+        w = np.exp(-beta * d)
+        s = w.sum(axis=1, keepdims=True)  # >= 1: the nearest neighbour's weight is 1
+        H = np.log(s) + beta * (d * w).sum(axis=1, keepdims=True) / s
+        high = H > target  # too flat: a larger beta
+        lo = np.where(high, beta, lo)
+        hi = np.where(high, hi, beta)
+        beta = np.minimum(np.where(np.isinf(hi), beta * 2.0, (lo + hi) / 2.0), EMBED_BETA_CAP)
+    w = np.exp(-beta * d)
+    return w / w.sum(axis=1, keepdims=True)
+
+
+def embed_affinities(dist2, pos, perplexity):
+    """The symmetric affinities of a neighbour graph (``neighbour_graph``'s position and dist2 [N, K]) as the iteration takes them:
+    ``(row_first int64 [N + 1], col int32 [E], p fp32 [E])``, CSR with columns ascending over the union of the edges i -> j and j -> i,
+    p_ij = (float)((p_j|i + p_i|j) / (2 N)) from ``embed_conditional`` in fp64 (an edge stored one way only has the other term 0)."""
+    pos = np.asarray(pos)
+    if pos.dtype.kind not in "iu" or pos.ndim != 2 or pos.shape != np.shape(dist2):
+        raise ValueError("pos must be an integer array of dist2's shape %s, got %s %s" % (np.shape(dist2), pos.dtype, pos.shape))
+    N, K = pos.shape
+    own = np.arange(N, dtype=np.int64)[:, None]
+    if (pos < 0).any() or (pos >= N).any() or (pos == own).any():
+        raise ValueError("pos must hold positions in 0 .. %d other than the row's own" % (N - 1))
+    P = embed_conditional(dist2, perplexity)
+    i, j = np.broadcast_to(own, (N, K)).ravel(), pos.astype(np.int64).ravel()
+    key = np.concatenate([i * N + j, j * N + i])
+    val = np.concatenate([P.ravel(), P.ravel()])
+    order = np.argsort(key, kind="stable")
+    key, val = key[order], val[order]
+    first = np.concatenate([[True], key[1:] != key[:-1]])
+    start = np.nonzero(first)[0]
+    total = np.add.reduceat(val, start)  # (one or two terms per edge: no order to speak of)
+    edge = key[start]
+    row, col = edge // N, (edge % N).astype(np.int32)
+    row_first = np.zeros(N + 1, np.int64)
+    np.cumsum(np.bincount(row, minlength=N), out=row_first[1:])
+    return row_first, col, (total / (2.0 * N)).astype(np.float32)
+
+
+def embed_initial_layout(coords):
+    """``pca(2)``'s coordinates [N, 2] scaled so that the first column's standard deviation is 1e-4, fp32; mean and variance are exactly
+    rounded sums (``math.fsum``), the scaling one fp64 product per value.  ValueError for a non-finite coordinate or no spread."""
+    c = np.asarray(coords, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError("coords must have shape [N, 2], got %s" % (c.shape,))
+    if not np.isfinite(c).all():
+        raise ValueError("row %d has a non-finite component: it cannot be embedded" % int(np.nonzero(~np.isfinite(c).all(axis=1))[0][0]))
+    mean = math.fsum(c[:, 0]) / len(c)
+    std = math.sqrt(math.fsum((c[:, 0] - mean) ** 2) / len(c))
+    if not std > 0.0:
+        raise ValueError("the rows have no spread along their first principal axis: nothing to embed")
+    return (c * (1e-4 / std)).astype(np.float32)
+
+
+def embed_kl(coords, row_first, col, p, z):
+    """The Kullback-Leibler divergence of a layout over the stored edges, fp64: sum of p log(p / q) with q = 1 / ((1 + |y_i - y_j|^2) z),
+    edges with p = 0 left out."""
+    y = np.asarray(coords, dtype=np.float64)
+    row = np.repeat(np.arange(len(y)), np.diff(row_first))
+    pv = np.asarray(p, dtype=np.float64)
+    live = pv > 0
+    diff = y[row[live]] - y[np.asarray(col)[live]]
+    q = 1.0 / ((1.0 + (diff * diff).sum(axis=1)) * float(z))
+    return float(np.sum(pv[live] * np.log(pv[live] / q)))
+
+
+def embed_run(step, y0, row_first, col, p, iterations, exaggeration, lr, pos, d2, ids, atoms, perplexity, level, dim):
+    """``LatentIndex.embed`` behind the graph: the two phases through ``step(y, u, gain, n_iter, exaggeration, momentum, lr)`` --
+    ``Engine.embed_iterate`` or ``_hip.embed_iterate_host`` with the graph bound -- and the result"""
+    u, gain = np.zeros_like(y0), np.ones_like(y0)
+    z_init = step(y0, u, gain, 1, 1.0, 0.8, lr)["z"]  # (the Z of the layout the call starts from; its step is dropped)
+    st = step(y0, u, gain, iterations[0], exaggeration, 0.5, lr)
+    st = step(st["y"], st["u"], st["gain"], iterations[1], 1.0, 0.8, lr)
+    z = step(st["y"], st["u"], st["gain"], 1, 1.0, 0.8, lr)["z"]
+    coords = st["y"]
+    if not np.isfinite(coords).all():
+        raise ValueError("the embedding left the range of fp32: the learning rate %g is too large for this index" % lr)
+    emb = LatentEmbedding(coords, ids, atoms, perplexity, level, dim)
+    result = {"coords": coords, "kl_init": embed_kl(y0, row_first, col, p, z_init), "kl": embed_kl(coords, row_first, col, p, z), "z": z,
+              "neighbor_position": pos, "neighbor_dist2": d2, "n_edges": int(row_first[-1]), "learning_rate": float(np.float32(lr))}
+    return result, emb
+
+
+class LatentEmbedding:
+    """A neighbour embedding of one level of one model, as ``LatentIndex.embed`` fits it: the map coordinates fp32 [N, 2] of the index's
+    rows in position order, their ids and atoms, and the perplexity new rows are placed with."""
+
+    def __init__(self, coordinates, ids, atoms, perplexity, level, dim):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        try:
+            self.coordinates = np.ascontiguousarray(coordinates, dtype=np.float32)
+            self.ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            self.atoms = np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+            self.perplexity = float(perplexity)
+        except (TypeError, ValueError):
+            raise ValueError("coordinates, ids and atoms must be arrays of numbers and perplexity a number") from None
+        n = self.coordinates.shape[0]
+        if self.coordinates.ndim != 2 or self.coordinates.shape[1] != 2 or n < 2 or not np.isfinite(self.coordinates).all():
+            raise ValueError("coordinates must be a finite array [N, 2] with N >= 2, got shape %s" % (self.coordinates.shape,))
+        if self.ids.shape != (n,) or self.atoms.shape != (n,):
+            raise ValueError("ids %s and atoms %s must hold one entry per row (%d)" % (self.ids.shape, self.atoms.shape, n))
+        if not EMBED_PERPLEXITY[0] <= self.perplexity <= EMBED_PERPLEXITY[1]:
+            raise ValueError("perplexity must lie in %d .. %d, got %r" % (EMBED_PERPLEXITY + (perplexity,)))
+        self.level, self.dim = level, int(dim)
+
+    def __len__(self):
+        return int(self.coordinates.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the embedding has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level embedding of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def check_index(self, index):
+        """ValueError unless ``index`` can be the one the embedding maps: its level, width and number of rows"""
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        if index.level != self.level or index.dim != self.dim or len(index) != len(self):
+            raise ValueError("a %s-level embedding of %d rows of %d columns does not map a %s-level index of %d rows of %d" % (
+                self.level, len(self), self.dim, index.level, len(index), index.dim))
+
+    def place(self, position, dist2):
+        """New rows from their nearest index rows ([n, k] positions and squared distances, nearest first): ``LatentIndex.place``'s dict.
+        With fewer neighbours than the perplexity needs (a tiny index) the weights are uniform."""
+        position, dist2 = np.asarray(position), np.asarray(dist2, dtype=np.float32)
+        n, k = position.shape
+        if (position < 0).any() or not np.isfinite(dist2).all():
+            raise ValueError("row %d has no %d index rows at a finite distance" % (
+                int(np.nonzero((position < 0).any(axis=1) | ~np.isfinite(dist2).all(axis=1))[0][0]), k))
+        w = embed_conditional(dist2, self.perplexity) if n and k > self.perplexity else np.full((n, k), 1.0 / max(k, 1))
+        coords = np.einsum("nk,nkc->nc", w, self.coordinates[position].astype(np.float64)).astype(np.float32)
+        first = position[:, 0]
+        return {"coords": coords, "nearest_position": first.astype(np.int32), "nearest_id": self.ids[first], "nearest_atom": self.atoms[first],
+                "nearest_distance": np.sqrt(dist2[:, 0])}  # (correctly rounded on the host, as nearest reports distances)
+
+    def save(self, path):
+        """An ``.npz`` of coordinates, ids, atoms, perplexity, level and dim (written to exactly ``path``; no pickle)."""
+        with open(path, "wb") as f:
+            np.savez(f, coordinates=self.coordinates, ids=self.ids, atoms=self.atoms, perplexity=np.array(self.perplexity),
+                     level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved embedding; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            args = (z["coordinates"], z["ids"], z["atoms"], float(z["perplexity"]))
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level embedding of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(*args, level, dim)

@@ -15,7 +15,8 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import LatentClassHead, LatentClustering, LatentHead, LatentIndex, LatentKernelHead, LatentProjection, batch_jobs, level_dim, stop_dist2_of
+from .latent_index import (EMBED_NEIGHBOURS, LatentClassHead, LatentClustering, LatentEmbedding, LatentHead, LatentIndex, LatentKernelHead, LatentProjection,
+                           batch_jobs, embed_fit_args, level_dim, stop_dist2_of)
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -533,6 +534,55 @@ class HipModel:
         finally:
             if own is not None:
                 own.free()
+
+    def fit_embedding(self, data, level="structure", perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto",
+                      route="device", ids=None, batch_size=None):
+        """The neighbour embedding (t-SNE) of the model's latent space over ``data`` in two dimensions (``LatentIndex.embed``): the
+        ``bf_property`` rows (``level`` "structure") or the ``after_Lc`` rows ("atom"), the pair repulsion computed exactly on the GPU,
+        the map bit-reproducible.  ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it,
+        which is indexed for the call (``ids``: one per structure, default 0 .. n-1) and freed afterwards -- ``place`` needs the index,
+        so keep one to place new inputs later.  Returns ``(result, embedding)``.  Bad arguments raise ValueError before anything is
+        uploaded."""
+        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route)
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.embed(perplexity=perplexity, iterations=iterations, exaggeration=exaggeration, learning_rate=learning_rate, route=route)
+        finally:
+            if own is not None:
+                own.free()
+
+    def place(self, inputs, embedding, index, batch_size=None):
+        """New ``inputs`` on an existing map, right behind their forward: for every structure (or, at atom level, every atom) its 31
+        nearest rows of ``index`` -- the ``LatentIndex`` that ``embedding`` maps -- from the exact search (scann_index_query_batch),
+        conditional weights calibrated to the embedding's perplexity (``embed_conditional``), coordinates the weighted mean of the
+        neighbours' map rows in fp64.  A padded dict gives {"predict_property": [B, 1], "coords": fp32 [B, 2], "nearest_position": int32
+        [B], "nearest_id": int64 [B], "nearest_atom": int32 [B], "nearest_distance": fp32 [B]} and at atom level [B, M, 2] / [B, M] arrays
+        with 0 / -1 at padded atoms; a ``PackedBatch`` gives packed arrays.  Raw y.  An embedding of another width or index, or a bad
+        batch_size, raise ValueError before anything is uploaded."""
+        if not isinstance(embedding, LatentEmbedding):
+            raise ValueError("embedding must be a LatentEmbedding, got %r" % (type(embedding).__name__,))
+        embedding.check_model(self)
+        embedding.check_index(index)
+        index.check_model(self)
+        self._batch_size(batch_size)
+        k = min(EMBED_NEIGHBOURS, len(index))
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, k))
+        empty = {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "position": np.zeros((0, k), np.int32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = embedding.place(cat["position"], cat["dist2"])
+        out["predict_property"] = cat["y"].reshape(-1, 1)
+        if atom and not isinstance(inputs, _hip.PackedBatch):
+            for n, fill in (("coords", 0), ("nearest_position", -1), ("nearest_id", -1), ("nearest_atom", -1), ("nearest_distance", 0)):
+                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
+        return out
 
     def project(self, inputs, projection, batch_size=None):
         """New ``inputs`` on a ``LatentProjection``'s map, right behind their forward (scann_project_batch): the coordinates, the
@@ -1289,6 +1339,19 @@ class SCANN:
     def fit_projection(self, data, m=2, level="structure", ids=None, batch_size=None):
         """HipModel.fit_projection as it is: ``(result, projection)``; the map lives in latent space."""
         return self.model.fit_projection(data, m=m, level=level, ids=ids, batch_size=batch_size)
+
+    def fit_embedding(self, data, level="structure", perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto",
+                      route="device", ids=None, batch_size=None):
+        """HipModel.fit_embedding as it is: ``(result, embedding)``; the map lives in latent space."""
+        return self.model.fit_embedding(data, level=level, perplexity=perplexity, iterations=iterations, exaggeration=exaggeration,
+                                        learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
+
+    def place(self, ip, embedding, index, batch_size=None):
+        """HipModel.place with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the coordinates
+        and the distances live on the map and in latent space and stay as they are."""
+        out = self.model.place(ip, embedding, index, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
 
     def project(self, ip, projection, batch_size=None):
         """HipModel.project with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
