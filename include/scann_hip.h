@@ -804,6 +804,44 @@ int scann_embed_iterate(scann_handle_t* h, int64_t N, const int64_t* row_first /
 int scann_embed_iterate_host(int64_t N, const int64_t* row_first, const int32_t* col, const float* p, float* y, float* u, float* gain,
                              int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out);
 
+/* ---- Density-peak clustering and kernel density of an index ----
+ * A clustering that needs neither k nor round clusters (Rodriguez & Laio, Science 344, 1492, 2014): a row is a cluster centre if it is
+ * denser than its surroundings and far from anything denser; every other row follows its nearest denser row.  Both passes are exact
+ * O(N^2 dim) self-joins of the index, and the first one, with other rows as queries, is the kernel density of a new structure under the
+ * index: the third applicability-domain score beside the mean k-NN distance and the Mahalanobis distance.  The device part is defined to
+ * the bit; thresholds, labels and the decision graph are host work on top of it (LatentIndex.density_peaks).
+ *   Eligibility: a row is eligible iff all its components are finite (the rule of scann_index_select).
+ *   Weight term of a query x against pool row r:  d = dist2(x, r), exactly the chain of scann_knn_distsq with x as q;
+ *     w = scann_rbf_weight(d, gamma);  t = llrintf(ldexpf(w, 30)), round to nearest even.  So 0 <= t <= 2^30, and t = 2^30 exactly at
+ *     distance 0.  A NaN d contributes nothing (this happens only with a non-finite row).  gamma is finite and > 0.
+ *   Density sum: S(x) = the int64 sum of t over the pool rows that count.  N < 2^31, so no order of the adds can overflow, and the sum is
+ *     the same in any order: no tree is part of the definition.  An ineligible query gets S = -1.
+ *   Density order: row j is ABOVE row i iff S_j > S_i, or S_j == S_i and j < i.
+ *   Parent pass over a pool's own rows (the self-join): S_i is summed over the eligible j != i;  parent_i is the first row, under the
+ *     total order (dist2 ascending, position ascending), among the eligible rows above i, and delta2_i that dist2.  The one eligible row
+ *     with nothing above it (the root) gets parent -1 and delta2 +inf; so does every ineligible row, with S = -1.
+ * Consequences: dist2 is symmetric bit for bit; following parents strictly ascends the density order, so the parents form a tree; the
+ * result does not depend on the chunking, on how many add calls built the index or on the launch geometry.
+ * scann_index_density: nq arbitrary queries (host [nq * dim], dim the pool's) against an index; position skip_pos[i] >= 0 is left out of
+ * query i's sum (skip_pos NULL: nothing is).  An empty pool gives 0 for a finite query.  scann_index_peaks: both passes over the pool's own
+ * rows, device to device -- nothing N x N-sized is ever stored; sums, parent, delta2 [N]; an empty pool returns SCANN_OK.
+ * scann_index_density_batch: one inference forward of the resident batch with the level's output added for that forward only (y
+ * [n_struct] and ga [n_atom] or NULL bitwise, range guard, exact-fp32 re-run and selection restore exactly as scann_index_query_batch;
+ * generic widths, training handles), then the density of the level's rows where the forward left them: sums [n_struct or n_atom].
+ * Synchronous, one host wait per call.  SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null
+ * argument, an index of another handle, gamma not finite or <= 0, a bad level or width, an empty batch.  The calls change nothing in the
+ * pool, the handle's weights, the training state or the selected outputs.  scann_density_host and scann_peaks_host (rows [n * dim]; no
+ * GPU work, threaded over the rows) are the twins: the kernels' bits. */
+int scann_index_density(scann_handle_t* h, scann_index_t* pool, const float* q /* host [nq * dim] */, int64_t nq,
+                        const int32_t* skip_pos /* [nq] or NULL */, float gamma, int64_t* sums /* [nq] */);
+int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64_t* sums /* [N] */, int32_t* parent /* [N] */,
+                      float* delta2 /* [N] */);
+int scann_index_density_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, float gamma, float* y, float* ga,
+                              int64_t* sums);
+int scann_density_host(const float* rows, int64_t n, int64_t dim, const float* q, int64_t nq, const int32_t* skip_pos, float gamma,
+                       int64_t* sums);
+int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int64_t* sums, int32_t* parent, float* delta2);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

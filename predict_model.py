@@ -49,6 +49,11 @@ entropy) as ``class_head_<target>.pickle``.
 dataset's rows in two dimensions, the pair repulsion computed exactly on the GPU and the map bit-reproducible.  It prints the divergence
 before and after, pickles the result (coordinates, ids, atoms, neighbour lists) as ``embedding_<target>.pickle`` and, with ``--embed-out``,
 saves the map as a ``LatentEmbedding`` (.npz) for ``SCANN.place``.
+``--peaks K [--peaks-level atom|structure] [--peaks-bandwidth H] [--peaks-out FILE]`` clusters the dataset's atoms (or structures) by
+density peaks -- no round clusters are assumed; both passes over all pairs run on the GPU, bit-reproducible --, prints the bandwidth, the
+leading decision values and each cluster's size and centre, pickles the result as ``peaks_<target>.pickle`` and, with ``--peaks-out``,
+saves the labels as a ``LatentPeaks`` (.npz).  ``--density FILE [--density-bandwidth H]`` pickles ``density_<target>.pickle``: per structure
+the Gaussian kernel density of its row (or of its atoms' rows) under a saved ``LatentIndex``, for example of the training set.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -129,6 +134,7 @@ def main(args):
     kernel_head_targets = check_kernel_head_flags(args)
     class_labels = check_class_head_flags(args)
     check_embed_flags(args)
+    check_peaks_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -389,6 +395,64 @@ def main(args):
         if args.embed_out:
             emb.save(args.embed_out)
         pool.free()
+    if args.peaks:
+        pool = scann.build_index(data, level=args.peaks_level, ids=data.indexes)
+        print("Density peaks of the dataset's %d rows (%s level), %d clusters" % (len(pool), args.peaks_level, args.peaks))
+        try:
+            res, peaks = scann.density_peaks(pool, k=args.peaks, bandwidth=args.peaks_bandwidth or "auto")
+        except ValueError as e:  # (too few rows, a row with a non-finite component under the automatic bandwidth)
+            pool.free()
+            raise SystemExit("--peaks: %s" % e) from None
+        print("bandwidth %.6g, %d eligible rows; decision values: %s" % (
+            res["bandwidth"], res["n_eligible"], " ".join("%.6g" % g for g in res["decision"][:args.peaks + 3])))
+        for c in range(len(res["size"])):
+            print("cluster %4d: size %8d, centre id %d atom %d" % (c, res["size"][c], res["centre_id"][c], res["centre_atom"][c]))
+        res["id"], res["atom"] = pool.names()
+        pickle.dump(res, open(os.path.join(args.trained_model, "peaks_{}.pickle".format(target)), "wb"))
+        if args.peaks_out:
+            peaks.save(args.peaks_out)
+        pool.free()
+    if args.density:
+        from scann.models import LatentIndex
+
+        try:
+            index = LatentIndex.load(scann.model, args.density)
+        except ValueError as e:
+            raise SystemExit("--density: %s" % e) from None
+        print("Kernel density under %s (%s level, %d rows), bandwidth %g" % (args.density, index.level, len(index), args.density_bandwidth))
+        pickle.dump(density_records(scann, data, index, args.density_bandwidth),
+                    open(os.path.join(args.trained_model, "density_{}.pickle".format(target)), "wb"))
+        index.free()
+
+
+def check_peaks_flags(args):
+    """--peaks / --density and their companions checked before anything is loaded"""
+    if args.peaks < 0:
+        raise SystemExit("--peaks: K must be >= 1, got %d" % args.peaks)
+    if (args.peaks_out or args.peaks_bandwidth) and not args.peaks:
+        raise SystemExit("--peaks-out / --peaks-bandwidth: need --peaks")
+    if args.peaks_bandwidth < 0 or args.peaks_bandwidth != args.peaks_bandwidth:
+        raise SystemExit("--peaks-bandwidth: H must be > 0, got %g" % args.peaks_bandwidth)
+    if args.density_bandwidth and not args.density:
+        raise SystemExit("--density-bandwidth: needs --density")
+    if args.density and not args.density_bandwidth > 0:
+        raise SystemExit("--density: needs --density-bandwidth H > 0 (--peaks prints the one it used)")
+
+
+def density_records(scann, data, index, bandwidth):
+    """--density: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = index.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = scann.density(inputs, index, bandwidth)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["predict_property"][i, 0])}
+            for key in ("density", "sum"):
+                d[key] = r[key][i][amask[i]] if atom else r[key][i]
+            per.append(d)
+    return per
 
 
 def check_embed_flags(args):
@@ -612,6 +676,19 @@ def parser():
     p.add_argument("--kernel-head", type=str, default="",
                    help="a saved LatentKernelHead (.npz): pickle its prediction, standard deviation, leverage and support per structure as "
                         "kernel_head_<target>.pickle")
+    p.add_argument("--peaks", type=int, default=0, metavar="K",
+                   help="also cluster the dataset's rows in latent space into K clusters by density peaks (both passes over all pairs on "
+                        "the GPU, bit-reproducible) and pickle labels, densities, parents, centres and the decision values as "
+                        "peaks_<target>.pickle")
+    p.add_argument("--peaks-level", type=str, default="atom", choices=["atom", "structure"],
+                   help="rows --peaks clusters: one per atom (after_Lc) or one per structure (bf_property)")
+    p.add_argument("--peaks-bandwidth", type=float, default=0.0, metavar="H",
+                   help="kernel width of --peaks (default: automatic, from the 31st-nearest-neighbour distances)")
+    p.add_argument("--peaks-out", type=str, default="", help="save the labels as a LatentPeaks (.npz)")
+    p.add_argument("--density", type=str, default="", metavar="INDEX",
+                   help="also pickle the Gaussian kernel density of every structure (or atom) under a saved LatentIndex (.npz) as "
+                        "density_<target>.pickle")
+    p.add_argument("--density-bandwidth", type=float, default=0.0, metavar="H", help="kernel width of --density")
     p.add_argument("--embed", action="store_true",
                    help="draw the neighbour embedding (t-SNE) of the dataset's rows in two dimensions (exact pair repulsion on the GPU, "
                         "bit-reproducible) and pickle embedding_<target>.pickle")

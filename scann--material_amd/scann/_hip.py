@@ -162,6 +162,11 @@ SYMBOLS = [
     ("scann_logit_head_batch", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     ("scann_embed_iterate", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
     ("scann_embed_iterate_host", C.c_int, [C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
+    ("scann_index_density", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_float, _P]),
+    ("scann_index_peaks", C.c_int, [_P, _P, C.c_float, _P, _P, _P]),
+    ("scann_index_density_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, _P, _P]),
+    ("scann_density_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_float, _P]),
+    ("scann_peaks_host", C.c_int, [_P, C.c_int64, C.c_int64, C.c_float, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -744,6 +749,71 @@ def rbf_features_host(rows, landmarks, gamma):
     if rc < 0:
         raise ValueError("rbf_features_host: invalid arguments (%d)" % rc)
     return phi
+
+
+def check_peaks_gamma(gamma):
+    """gamma of a density pass as the C calls take it: a finite fp32 number > 0; ValueError otherwise, naming the argument."""
+    try:
+        g = np.float32(gamma)
+    except (TypeError, ValueError):
+        raise ValueError("gamma must be a number, got %r" % (gamma,)) from None
+    if isinstance(gamma, bool) or g.ndim != 0 or not (np.isfinite(g) and g > 0):
+        raise ValueError("gamma must be finite and > 0 in fp32, got %r" % (gamma,))
+    return float(g)
+
+
+def check_density_args(q, skip_pos, gamma, dim):
+    """(q [nq, dim] fp32, skip_pos int32 [nq] or None, gamma) of a density pass as the C calls take them; ValueError otherwise, naming the
+    argument."""
+    try:
+        q = np.ascontiguousarray(q, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("q must be an array of numbers") from None
+    if q.ndim != 2 or q.shape[1] != int(dim):
+        raise ValueError("q must hold rows of %d columns, got shape %s" % (int(dim), q.shape))
+    if skip_pos is not None:
+        skip_pos = np.ascontiguousarray(skip_pos)
+        if skip_pos.dtype.kind not in "iu" or skip_pos.shape != (q.shape[0],):
+            raise ValueError("skip_pos must hold one integer position per query (%d), got %s of shape %s" % (
+                q.shape[0], skip_pos.dtype, skip_pos.shape))
+        if len(skip_pos) and (skip_pos.max() > 0x7fffffff or skip_pos.min() < -0x80000000):
+            raise ValueError("skip_pos holds a position outside int32")
+        skip_pos = np.ascontiguousarray(skip_pos, dtype=np.int32)
+    return q, skip_pos, check_peaks_gamma(gamma)
+
+
+def density_host(rows, q, gamma, skip_pos=None):
+    """The density sums of the queries ``q`` [nq, dim] under the pool ``rows`` [n, dim] on the host with the kernel's bits
+    (scann_density_host, the definition in include/scann_hip.h): int64 [nq], -1 for a query with a non-finite component; position
+    ``skip_pos[i]`` >= 0 is left out of query i's sum."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("density_host: rows of shape %s" % (rows.shape,))
+    q, skip_pos, g = check_density_args(q, skip_pos, gamma, rows.shape[1])
+    sums = np.zeros(q.shape[0], np.int64)
+    rc = int(load_library().scann_density_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(q), q.shape[0], _ptr(skip_pos), g, _ptr(sums)))
+    if rc < 0:
+        raise ValueError("density_host: invalid arguments (%d)" % rc)
+    return sums
+
+
+def _peaks_out(n):
+    return {"sum": np.zeros(n, np.int64), "parent": np.full(n, -1, np.int32), "delta2": np.full(n, np.inf, np.float32)}
+
+
+def peaks_host(rows, gamma):
+    """Both passes of the density-peak clustering over ``rows`` [n, dim] on the host with the kernels' bits (scann_peaks_host):
+    {"sum" int64 [n], "parent" int32 [n], "delta2" fp32 [n]}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("peaks_host: rows of shape %s" % (rows.shape,))
+    g = check_peaks_gamma(gamma)
+    out = _peaks_out(rows.shape[0])
+    rc = int(load_library().scann_peaks_host(_ptr(rows), rows.shape[0], rows.shape[1], g, _ptr(out["sum"]), _ptr(out["parent"]),
+                                             _ptr(out["delta2"])))
+    if rc < 0:
+        raise ValueError("peaks_host: invalid arguments (%d)" % rc)
+    return out
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -1791,6 +1861,32 @@ class Engine:
         args = check_embed_args(row_first, col, p, y, u, gain, n_iter, exaggeration, momentum, lr)
         rc, out = _embed_call(lambda *a: self.lib.scann_embed_iterate(self._h, *a), args, want_grad)
         self._check(rc)
+        return out
+
+    def index_density(self, ix, q, gamma, skip_pos=None):
+        """The density sums of the host queries ``q`` [nq, dim] under the rows of ``ix`` (scann_index_density): int64 [nq], bit for bit
+        ``density_host``."""
+        q, skip_pos, g = check_density_args(q, skip_pos, gamma, ix.dim)
+        sums = np.zeros(q.shape[0], np.int64)
+        self._check(self.lib.scann_index_density(self._h, ix._h, _ptr(q), q.shape[0], _ptr(skip_pos), g, _ptr(sums)))
+        return sums
+
+    def index_peaks(self, ix, gamma):
+        """Both passes of the density-peak clustering over the rows of ``ix`` on the device (scann_index_peaks): ``peaks_host``'s dict,
+        bit for bit."""
+        g = check_peaks_gamma(gamma)
+        out = _peaks_out(len(ix))
+        self._check(self.lib.scann_index_peaks(self._h, ix._h, g, _ptr(out["sum"]), _ptr(out["parent"]), _ptr(out["delta2"])))
+        return out
+
+    def density_batch(self, ix, rb, level, gamma):
+        """One forward of a resident batch and the density sums of its ``level`` rows under ``ix`` (scann_index_density_batch; raw y):
+        {"y" [n_struct], "ga" [n_atom], "sum" int64 [n_struct or n_atom]}."""
+        g = check_peaks_gamma(gamma)
+        p = rb.packed
+        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
+        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "sum": np.zeros(n, np.int64)}
+        self._check(self.lib.scann_index_density_batch(self._h, ix._h, rb._h, int(level), g, _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["sum"])))
         return out
 
     def logit_head_batch(self, rb, level, mean, weights):

@@ -442,6 +442,37 @@ class LatentIndex:
         ids, atoms = eng.index_names(self._ix)
         return embed_run(step, y0, row_first, col, p, iterations, exaggeration, lr, pos, d2, ids, atoms, perplexity, self.level, self.dim)
 
+    def density_peaks(self, k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device"):
+        """Density-peak clustering of this index's rows (Rodriguez & Laio 2014): a clustering that needs neither a number of clusters
+        nor round ones.  A row is a cluster centre if it is denser than its surroundings and far from anything denser; every other row
+        follows its nearest denser row.  The Gaussian kernel density of every row and its nearest denser row come from two exact passes
+        over all pairs on the GPU (scann_index_peaks), defined to the bit, so the result depends on the index contents and the arguments
+        only.  ``bandwidth``: the kernel width h, a positive number, or "auto": h^2 is the median over the rows of the squared distance
+        to the ``neighbours``-th nearest other row (1 .. 31, capped at N - 1; ``neighbour_graph``, whose ValueError for a row with a
+        non-finite component it inherits).  Centres: the first ``k`` rows under (density x delta descending, position ascending), or --
+        with ``min_density`` and ``min_delta`` instead of ``k`` -- the rows at or above both thresholds plus the densest row.  Clusters
+        are numbered in density order of their centres (the densest row's is 0); rows with a non-finite component get label -1.
+        ``route`` "host" runs the host twin on the rows read back: the same bits.  Returns ``(result, peaks)``: {"label" int32 [N],
+        "density" fp64 [N] (the mean kernel weight to the other eligible rows; NaN for label -1), "delta" fp64 [N] (the distance to the
+        nearest denser row, inf for the densest), "parent" int32 [N], "sum" int64 [N], "centre_position" int32, "centre_id" int64,
+        "centre_atom" int32, "size" int64 per cluster, "decision" (density x delta sorted descending: the gap in it tells how many
+        clusters there are), "bandwidth", "gamma", "n_eligible"} and the ``LatentPeaks`` that labels the neighbours ``nearest(k=1)``
+        finds.  Bad arguments raise ValueError before any device call."""
+        k, neighbours, min_density, min_delta, route = peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, route)
+        N = len(self)
+        if N < 1:
+            raise ValueError("density peaks need at least 1 row, the index has 0")
+        eng = self.model.engine
+        if isinstance(bandwidth, str):
+            _, d2 = neighbour_graph(self)
+            h = peaks_auto_bandwidth(d2, neighbours)
+        else:
+            h = float(bandwidth)
+        gamma = _hip.rbf_gamma(h)
+        r = eng.index_peaks(self._ix, gamma) if route == "device" else _hip.peaks_host(self.rows()[0], gamma)
+        ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
+        return peaks_result(r, ids, atoms, k, min_density, min_delta, h, gamma, self.level, self.dim)
+
     def place(self, rows, embedding):
         """Host ``rows`` [n, dim] on an existing map of this index (``embedding``, as ``embed`` returned it for these rows): each row's
         31 nearest index rows from the exact search, conditional weights calibrated to the embedding's perplexity
@@ -1473,5 +1504,192 @@ class LatentEmbedding:
             args = (z["coordinates"], z["ids"], z["atoms"], float(z["perplexity"]))
         if level not in LEVELS or level_dim(model.config, level) != dim:
             raise ValueError("%s: a %s-level embedding of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(*args, level, dim)
+
+
+PEAKS_NEIGHBOURS = EMBED_NEIGHBOURS  # the farthest neighbour the automatic bandwidth can look at: what ``neighbour_graph`` returns
+
+
+def peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, route):
+    """The arguments of ``LatentIndex.density_peaks`` checked: (k or None, neighbours, min_density, min_delta, route); ValueError
+    otherwise, naming the argument"""
+    if (k is None) == (min_density is None and min_delta is None):
+        raise ValueError("exactly one of k and the thresholds (min_density, min_delta) must be given")
+    if k is None and (min_density is None or min_delta is None):
+        raise ValueError("min_density and min_delta must be given together")
+    if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1):
+        raise ValueError("k must be an integer >= 1, got %r" % (k,))
+    out = []
+    for name, v in (("min_density", min_density), ("min_delta", min_delta)):
+        if v is None:
+            out.append(None)
+            continue
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number >= 0, got %r" % (name, v)) from None
+        if isinstance(v, bool) or not f >= 0:
+            raise ValueError("%s must be a number >= 0, got %r" % (name, v))
+        out.append(f)
+    if isinstance(bandwidth, str):
+        if bandwidth != "auto":
+            raise ValueError('bandwidth must be "auto" or a positive number, got %r' % (bandwidth,))
+    else:
+        _hip.rbf_gamma(bandwidth)
+    if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= int(neighbours) <= PEAKS_NEIGHBOURS:
+        raise ValueError("neighbours must be an integer in 1 .. %d, got %r" % (PEAKS_NEIGHBOURS, neighbours))
+    if route not in ("device", "host"):
+        raise ValueError('route must be "device" or "host", got %r' % (route,))
+    return None if k is None else int(k), int(neighbours), out[0], out[1], route
+
+
+def peaks_auto_bandwidth(dist2, neighbours):
+    """The automatic kernel width from a neighbour graph's squared distances [N, K], nearest first: h^2 is the median over the rows of
+    the squared distance to the ``neighbours``-th nearest other row (capped at K), in fp64.  ValueError if that median is 0."""
+    d2 = np.asarray(dist2, dtype=np.float64)
+    h2 = float(np.median(d2[:, min(int(neighbours), d2.shape[1]) - 1]))
+    if not (h2 > 0.0 and math.isfinite(h2)):
+        raise ValueError("the automatic bandwidth is %r: more than half of the rows have %d coincident neighbours; give bandwidth a number" % (
+            math.sqrt(h2) if h2 >= 0 else h2, min(int(neighbours), d2.shape[1])))
+    return math.sqrt(h2)
+
+
+def peaks_assemble(S, parent, delta2, k=None, min_density=None, min_delta=None):
+    """The host half of the density-peak clustering, fp64, O(N log N): from the device's sums, parents and squared distances the
+    densities, the decision values, the centres and the labels.  density_i = 2^-30 S_i / n_eligible; delta_i = sqrt(delta2_i); g_i =
+    2^-30 S_i delta_i, +inf outright for the root (the eligible row without a parent) and 0 outright for any other row with S_i = 0 (its
+    delta may be +inf: an overflowed distance).  Centres: the first ``k`` rows under (g
+    descending, position ascending), or the rows with density >= min_density and delta >= min_delta plus the root; clusters numbered in
+    density order (S descending, position ascending) of their centres; rows visited in density order, a non-centre takes its parent's
+    label; ineligible rows (S < 0) get -1.  {"label", "density", "delta", "g", "centre_position", "size", "decision", "n_eligible"}."""
+    S = np.asarray(S, dtype=np.int64)
+    parent = np.asarray(parent, dtype=np.int32)
+    N = S.shape[0]
+    pos = np.arange(N)
+    elig = S >= 0
+    n_el = int(elig.sum())
+    w = np.ldexp(S.astype(np.float64), -30)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        density = np.where(elig, w / max(n_el, 1), np.nan)
+        delta = np.where(elig, np.sqrt(np.asarray(delta2, dtype=np.float64)), np.inf)
+        root = elig & (parent < 0)
+        g = np.where(root, np.inf, np.where(elig, np.where(S == 0, 0.0, w * np.where(root, 0.0, delta)), -np.inf))  # (S = 0: 0, never 0 * inf)
+    if n_el and int(root.sum()) != 1:
+        raise ValueError("the parents do not form a tree: %d eligible rows have none" % int(root.sum()))
+    order = np.lexsort((pos, -S))[:n_el]  # the density order: S descending, position ascending; the ineligible rows (S = -1) come last
+    by_g = np.lexsort((pos, -g))[:n_el]
+    if k is not None:
+        if k > n_el:
+            raise ValueError("k = %d clusters need %d rows without a non-finite component, there are %d" % (k, k, n_el))
+        is_centre = np.zeros(N, bool)
+        is_centre[by_g[:k]] = True
+    else:
+        is_centre = root | (elig & (density >= min_density) & (delta >= min_delta))
+    centres = order[is_centre[order]]  # in density order: the root first
+    number = np.full(N, -1, np.int32)
+    number[centres] = np.arange(len(centres), dtype=np.int32)
+    label = np.full(N, -1, np.int32)
+    for i in order.tolist():
+        label[i] = number[i] if is_centre[i] else label[parent[i]]
+    return {"label": label, "density": density, "delta": delta, "g": g, "centre_position": centres.astype(np.int32),
+            "size": np.bincount(label[label >= 0], minlength=len(centres)).astype(np.int64), "decision": g[by_g], "n_eligible": n_el}
+
+
+def peaks_result(r, ids, atoms, k, min_density, min_delta, h, gamma, level, dim):
+    """``LatentIndex.density_peaks``'s ``(result, peaks)`` from the passes' dict {"sum", "parent", "delta2"}"""
+    a = peaks_assemble(r["sum"], r["parent"], r["delta2"], k, min_density, min_delta)
+    c = a["centre_position"]
+    result = {"label": a["label"], "density": a["density"], "delta": a["delta"], "parent": r["parent"], "sum": r["sum"], "centre_position": c,
+              "centre_id": np.asarray(ids, dtype=np.int64)[c], "centre_atom": np.asarray(atoms, dtype=np.int32)[c], "size": a["size"],
+              "decision": a["decision"], "bandwidth": float(h), "gamma": float(gamma), "n_eligible": a["n_eligible"]}
+    return result, LatentPeaks(a["label"], ids, atoms, c, h, level, dim)
+
+
+def density_peaks_rows_host(rows, k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, ids=None, atoms=None,
+                            level="structure"):
+    """``LatentIndex.density_peaks`` of host rows [N, dim] entirely on the host, no GPU: the twins of the search's distances and of the
+    two passes -- bit for bit what an index holding these rows gives by either route."""
+    k, neighbours, min_density, min_delta, _ = peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, "host")
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("rows must have shape [N, dim] with N >= 1, got %s" % (rows.shape,))
+    N, dim = rows.shape
+    h = peaks_auto_bandwidth(neighbour_graph_host(rows)[1], neighbours) if isinstance(bandwidth, str) else float(bandwidth)
+    gamma = _hip.rbf_gamma(h)
+    ids = np.arange(N, dtype=np.int64) if ids is None else ids
+    atoms = np.full(N, -1, np.int32) if atoms is None else atoms
+    return peaks_result(_hip.peaks_host(rows, gamma), ids, atoms, k, min_density, min_delta, h, gamma, level, dim)
+
+
+def density_of_sums(sums, n_rows):
+    """The kernel density a density sum stands for, fp64: 2^-30 S / n_rows (the mean kernel weight to the index's rows); NaN for S < 0
+    (a query with a non-finite component) and for an empty index."""
+    S = np.asarray(sums, dtype=np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(S >= 0, np.ldexp(S.astype(np.float64), -30) / (n_rows if n_rows > 0 else np.nan), np.nan)
+
+
+class LatentPeaks:
+    """A density-peak clustering of one level of one model, as ``LatentIndex.density_peaks`` fits it: the label of every row of the
+    index in position order, the rows' ids and atoms, the centres' positions and the kernel width.  A new structure takes the label of
+    its nearest index row: ``label_of(position)`` with the positions ``nearest(k=1)`` reports."""
+
+    def __init__(self, label, ids, atoms, centre_position, bandwidth, level, dim):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        try:
+            self.label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+            self.ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            self.atoms = np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+            self.centre_position = np.ascontiguousarray(centre_position, dtype=np.int32).reshape(-1)
+            self.bandwidth = float(bandwidth)
+        except (TypeError, ValueError):
+            raise ValueError("label, ids, atoms and centre_position must be arrays of integers and bandwidth a number") from None
+        n, k = self.label.shape[0], self.centre_position.shape[0]
+        if self.ids.shape != (n,) or self.atoms.shape != (n,):
+            raise ValueError("ids %s and atoms %s must hold one entry per row (%d)" % (self.ids.shape, self.atoms.shape, n))
+        if k and (self.centre_position.min() < 0 or self.centre_position.max() >= n):
+            raise ValueError("centre_position must name rows in 0 .. %d" % (n - 1))
+        if n and (self.label.min() < -1 or self.label.max() >= k):
+            raise ValueError("label must lie in -1 .. %d (one less than the number of centres)" % (k - 1))
+        if not (self.bandwidth > 0 and math.isfinite(self.bandwidth)):
+            raise ValueError("bandwidth must be a positive number, got %r" % (bandwidth,))
+        self.level, self.dim = level, int(dim)
+
+    def __len__(self):
+        return int(self.label.shape[0])
+
+    @property
+    def k(self):
+        return int(self.centre_position.shape[0])
+
+    def check_model(self, model):
+        """ValueError unless the clustering has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level density-peak clustering of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def label_of(self, position):
+        """The labels of index rows by position (any shape, int32): what ``nearest(k=1)``'s positions stand for; -1 for position -1."""
+        p = np.asarray(position)
+        if p.dtype.kind not in "iu" or (p.size and (p.min() < -1 or p.max() >= len(self))):
+            raise ValueError("position must hold integers in -1 .. %d" % (len(self) - 1))
+        return np.where(p >= 0, self.label[np.maximum(p, 0)], -1).astype(np.int32)
+
+    def save(self, path):
+        """An ``.npz`` of label, ids, atoms, centre_position, bandwidth, level and dim (written to exactly ``path``; no pickle)."""
+        with open(path, "wb") as f:
+            np.savez(f, label=self.label, ids=self.ids, atoms=self.atoms, centre_position=self.centre_position,
+                     bandwidth=np.array(self.bandwidth), level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved clustering; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            args = (z["label"], z["ids"], z["atoms"], z["centre_position"], float(z["bandwidth"]))
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level density-peak clustering of %d columns does not fit a model whose %s is %d" % (
                 path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
         return cls(*args, level, dim)

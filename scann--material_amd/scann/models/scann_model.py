@@ -16,7 +16,7 @@ import numpy as np
 
 from .. import _hip
 from .latent_index import (EMBED_NEIGHBOURS, LatentClassHead, LatentClustering, LatentEmbedding, LatentHead, LatentIndex, LatentKernelHead, LatentProjection,
-                           batch_jobs, embed_fit_args, level_dim, stop_dist2_of)
+                           batch_jobs, density_of_sums, embed_fit_args, level_dim, peaks_fit_args, stop_dist2_of)
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -557,6 +557,53 @@ class HipModel:
         finally:
             if own is not None:
                 own.free()
+
+    def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
+                      ids=None, batch_size=None):
+        """Which kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``) the
+        model distinguishes, without a number of clusters and without round clusters: density-peak clustering in its latent space, both
+        passes over all pairs exact on the GPU and bit-reproducible (``LatentIndex.density_peaks``).  ``data`` is a ``LatentIndex`` (its
+        level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for the call (``ids``: one per structure,
+        default 0 .. n-1) and freed afterwards.  Returns ``(result, peaks)``: ``LatentIndex.density_peaks``'s dict and the
+        ``LatentPeaks`` whose ``label_of`` labels the positions ``nearest(k=1)`` reports.  Bad arguments raise ValueError before anything
+        is uploaded."""
+        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, route)
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.density_peaks(k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density, min_delta=min_delta, route=route)
+        finally:
+            if own is not None:
+                own.free()
+
+    def density(self, inputs, index, bandwidth, batch_size=None):
+        """The Gaussian kernel density of every structure (or, for an atom-level index, every atom) of ``inputs`` under the rows of a
+        ``LatentIndex``, summed over all its rows on the GPU right behind the forward (scann_index_density_batch): the third
+        applicability-domain score beside ``nearest``'s distances and ``project``'s Mahalanobis distance.  ``bandwidth``: the kernel
+        width h, a positive number (``density_peaks`` reports the one it used).  A padded dict gives {"predict_property": [B, 1],
+        "density": fp64 [B] -- the mean kernel weight to the index's rows, 2^-30 sum / len(index) --, "sum": int64 [B], the exact
+        fixed-point sum} and at atom level [B, M] arrays with 0 / -1 at padded atoms; a ``PackedBatch`` gives packed [n_atom] arrays.
+        Raw y.  An index of another model or width, a bad bandwidth or batch_size raise ValueError before anything is uploaded."""
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        index.check_model(self)
+        gamma = _hip.rbf_gamma(bandwidth)
+        self._batch_size(batch_size)
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.density_batch(index._ix, rb, lvl, gamma))
+        empty = {"y": np.zeros(0, np.float32), "sum": np.zeros(0, np.int64)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        out = {"predict_property": cat["y"].reshape(-1, 1), "density": density_of_sums(cat["sum"], len(index)), "sum": cat["sum"]}
+        if atom and not isinstance(inputs, _hip.PackedBatch):
+            out["density"] = _hip.repad_atoms(out["density"], inputs["atom_mask"], 0, dtype=np.float64)
+            out["sum"] = _hip.repad_atoms(out["sum"], inputs["atom_mask"], -1)
+        return out
 
     def place(self, inputs, embedding, index, batch_size=None):
         """New ``inputs`` on an existing map, right behind their forward: for every structure (or, at atom level, every atom) its 31
@@ -1345,6 +1392,19 @@ class SCANN:
         """HipModel.fit_embedding as it is: ``(result, embedding)``; the map lives in latent space."""
         return self.model.fit_embedding(data, level=level, perplexity=perplexity, iterations=iterations, exaggeration=exaggeration,
                                         learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
+
+    def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
+                      ids=None, batch_size=None):
+        """HipModel.density_peaks as it is: ``(result, peaks)``; densities and distances live in latent space."""
+        return self.model.density_peaks(data, level=level, k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density,
+                                        min_delta=min_delta, route=route, ids=ids, batch_size=batch_size)
+
+    def density(self, ip, index, bandwidth, batch_size=None):
+        """HipModel.density with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the densities
+        live in latent space and stay as they are."""
+        out = self.model.density(ip, index, bandwidth, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
 
     def place(self, ip, embedding, index, batch_size=None):
         """HipModel.place with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the coordinates
