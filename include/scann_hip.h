@@ -842,6 +842,41 @@ int scann_density_host(const float* rows, int64_t n, int64_t dim, const float* q
                        int64_t* sums);
 int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int64_t* sums, int32_t* parent, float* delta2);
 
+/* ---- Hierarchical clustering of an index: the exact minimum spanning tree ----
+ * Single linkage and density-based hierarchical clustering (HDBSCAN: Campello, Moulavi & Sander, PAKDD 2013) both rest on one object: the
+ * minimum spanning tree of the complete graph over the rows, the second with mutual-reachability weights.  The tree is a series of exact
+ * O(N^2 dim) self-joins of the index -- at most ceil(log2 N) rounds of Boruvka's algorithm -- and, under a total order on the edges, it is
+ * unique: so it is defined to the bit here.  The dendrogram, the cuts, the condensed tree and the stability selection are host work on
+ * the N - 1 edges (LatentIndex.hierarchy, LatentHierarchy).
+ *   Eligibility: a row is eligible iff all its components are finite (the rule of scann_index_select / scann_index_peaks).  Ineligible
+ *     rows are in no edge.
+ *   Weight: for eligible positions i != j,  w(i, j) = max(dist2(i, j), core2[i], core2[j]),  dist2 exactly the chain of
+ *     scann_knn_distsq; the max is exact.  With core2 NULL, w = dist2: plain single linkage.  dist2 of two finite rows may overflow to
+ *     +inf; such an edge is an ordinary edge and ranks last.  A weight is never NaN and never negative.
+ *   Edge order: edges are ordered totally by (w ascending, min(i, j) ascending, max(i, j) ascending).
+ *   Result: the unique minimum spanning tree of the complete graph on the eligible rows under that order;
+ *     n_edges = max(n_eligible - 1, 0); the edges are listed in ascending order of the edge order, with a[e] < b[e].
+ * Consequences: a, b, w and n_edges are a function of the index contents and core2 only, bit for bit -- not of the chunking, of how many
+ * add calls built the pool, of the launch geometry or of a thread count.  For a fixed row q the edge order restricted to the edges at q
+ * is the order (w, r) of the other end r (rows r < q sort before rows r > q either way), which is what the search of a round walks.
+ * rounds (or NULL) receives the number of Boruvka rounds run: at most ceil(log2 n_eligible); it is no part of the definition.
+ * scann_index_mst is synchronous (one 12-byte read-back per round -- the edges, the components and the skipped tiles so far --; no kernel waits on another workgroup, and the host stops with an
+ * internal error if a round did not reduce the components).  core2 is a host array [N], checked before anything is launched: a NaN or
+ * negative entry at any position is SCANN_ERR_INVALID with a message that names it.  An empty pool returns SCANN_OK with 0 edges; a pool
+ * above SCANN_MST_MAX_ROWS is SCANN_ERR_UNSUPPORTED before any launch (as scann_embed_iterate: the bound keeps one synchronous call
+ * short); an index of another handle or a null output is SCANN_ERR_INVALID.  The call changes nothing in the pool, the handle's weights,
+ * the training state or the selected outputs, and works on inference, training, generic-width and exact-fp32 handles.
+ * scann_mst_host (rows [n * dim]; no GPU work, the distances threaded over the rows) is the twin: the same bits.
+ * scann_mst_last_rounds is a measurement aid (tools/mst_rate.py) with no promise of stability, not part of the definition: the record of
+ * the calling thread's last scann_index_mst -- per round (up to cap) the
+ * components before it, the host seconds around it and the tiles whose arithmetic the label rule skipped; *tiles: the tiles of one
+ * round.  Returns the rounds recorded. */
+#define SCANN_MST_MAX_ROWS 262144
+int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2 /* host [N] or NULL */, int64_t* n_edges,
+                    int32_t* a /* [max(N - 1, 0)] */, int32_t* b, float* w, int32_t* rounds /* or NULL */);
+int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2, int64_t* n_edges, int32_t* a, int32_t* b, float* w);
+int scann_mst_last_rounds(int32_t cap, int32_t* components, double* seconds, int64_t* skipped, int64_t* tiles);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

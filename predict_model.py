@@ -54,6 +54,12 @@ density peaks -- no round clusters are assumed; both passes over all pairs run o
 leading decision values and each cluster's size and centre, pickles the result as ``peaks_<target>.pickle`` and, with ``--peaks-out``,
 saves the labels as a ``LatentPeaks`` (.npz).  ``--density FILE [--density-bandwidth H]`` pickles ``density_<target>.pickle``: per structure
 the Gaussian kernel density of its row (or of its atoms' rows) under a saved ``LatentIndex``, for example of the training set.
+``--hierarchy MIN_CLUSTER_SIZE [--hierarchy-level atom|structure] [--hierarchy-min-samples 5] [--hierarchy-out FILE]`` clusters the dataset's
+atoms (or structures) hierarchically (HDBSCAN; single linkage with ``--hierarchy-min-samples 0``) on the exact minimum spanning tree,
+built on the GPU and bit-reproducible: it prints the tree's size and each cluster's size, persistence and exemplar, and how many rows are
+noise, pickles the result as ``hierarchy_<target>.pickle`` and, with ``--hierarchy-out``, saves the tree as a ``LatentHierarchy`` (.npz)
+and the rows it was built on beside it as ``FILE.index.npz``.  ``--attach FILE --attach-min-cluster-size N`` loads both and pickles
+``attach_<target>.pickle``: per structure the label of its row (or of its atoms' rows) under that hierarchy, -1 for noise.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -135,6 +141,7 @@ def main(args):
     class_labels = check_class_head_flags(args)
     check_embed_flags(args)
     check_peaks_flags(args)
+    check_hierarchy_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
         width = int(config["model"]["dense_out" if args.project_level == "structure" else "global_dim"])
@@ -423,6 +430,72 @@ def main(args):
         pickle.dump(density_records(scann, data, index, args.density_bandwidth),
                     open(os.path.join(args.trained_model, "density_{}.pickle".format(target)), "wb"))
         index.free()
+    if args.hierarchy:
+        pool = scann.build_index(data, level=args.hierarchy_level, ids=data.indexes)
+        print("Hierarchy of the dataset's %d rows (%s level), min_samples %d, min_cluster_size %d" % (
+            len(pool), args.hierarchy_level, args.hierarchy_min_samples, args.hierarchy))
+        try:
+            res, tree = scann.hierarchy(pool, min_samples=args.hierarchy_min_samples, min_cluster_size=args.hierarchy)
+        except ValueError as e:  # (too many rows)
+            pool.free()
+            raise SystemExit("--hierarchy: %s" % e) from None
+        print("%d eligible rows, %d edges in %d rounds; %d clusters, %d rows are noise" % (
+            res["n_eligible"], len(res["w"]), res["rounds"], len(res["size"]), int((res["label"] < 0).sum())))
+        for c in range(len(res["size"])):
+            print("cluster %4d: size %8d, persistence %.6g, exemplar id %d atom %d" % (
+                c, res["size"][c], res["persistence"][c], tree.ids[res["exemplar"][c]], tree.atoms[res["exemplar"][c]]))
+        res["id"], res["atom"] = pool.names()
+        pickle.dump(res, open(os.path.join(args.trained_model, "hierarchy_{}.pickle".format(target)), "wb"))
+        if args.hierarchy_out:
+            tree.save(args.hierarchy_out)
+            pool.save(args.hierarchy_out + ".index.npz")
+        pool.free()
+    if args.attach:
+        from scann.models import LatentHierarchy, LatentIndex
+
+        try:
+            tree = LatentHierarchy.load(scann.model, args.attach)
+            index = LatentIndex.load(scann.model, args.attach + ".index.npz")
+        except (ValueError, OSError) as e:
+            raise SystemExit("--attach: %s" % e) from None
+        print("Labels under %s (%s level, %d rows), min_cluster_size %d" % (args.attach, index.level, len(index), args.attach_min_cluster_size))
+        try:
+            records = attach_records(scann, data, tree, index, args.attach_min_cluster_size)
+        except ValueError as e:
+            index.free()
+            raise SystemExit("--attach: %s" % e) from None
+        pickle.dump(records, open(os.path.join(args.trained_model, "attach_{}.pickle".format(target)), "wb"))
+        index.free()
+
+
+def check_hierarchy_flags(args):
+    """--hierarchy / --attach and their companions checked before anything is loaded"""
+    if args.hierarchy and args.hierarchy < 2:
+        raise SystemExit("--hierarchy: MIN_CLUSTER_SIZE must be >= 2, got %d" % args.hierarchy)
+    if args.hierarchy_out and not args.hierarchy:
+        raise SystemExit("--hierarchy-out: needs --hierarchy")
+    if not 0 <= args.hierarchy_min_samples <= 31:
+        raise SystemExit("--hierarchy-min-samples: must lie in 0 .. 31, got %d" % args.hierarchy_min_samples)
+    if args.attach_min_cluster_size and not args.attach:
+        raise SystemExit("--attach-min-cluster-size: needs --attach")
+    if args.attach and args.attach_min_cluster_size < 2:
+        raise SystemExit("--attach: needs --attach-min-cluster-size N >= 2")
+
+
+def attach_records(scann, data, tree, index, min_cluster_size):
+    """--attach: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = index.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = scann.attach(inputs, tree, index, min_cluster_size)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["predict_property"][i, 0])}
+            for key in ("label", "nearest_id", "nearest_atom", "nearest_distance"):
+                d[key] = r[key][i][amask[i]] if atom else r[key][i]
+            per.append(d)
+    return per
 
 
 def check_peaks_flags(args):
@@ -685,6 +758,19 @@ def parser():
     p.add_argument("--peaks-bandwidth", type=float, default=0.0, metavar="H",
                    help="kernel width of --peaks (default: automatic, from the 31st-nearest-neighbour distances)")
     p.add_argument("--peaks-out", type=str, default="", help="save the labels as a LatentPeaks (.npz)")
+    p.add_argument("--hierarchy", type=int, default=0, metavar="MIN_CLUSTER_SIZE",
+                   help="also cluster the dataset's rows in latent space hierarchically (HDBSCAN on the exact minimum spanning tree, built on "
+                        "the GPU, bit-reproducible), keeping clusters of at least MIN_CLUSTER_SIZE rows; the result is pickled as "
+                        "hierarchy_<target>.pickle")
+    p.add_argument("--hierarchy-level", type=str, default="atom", choices=["atom", "structure"],
+                   help="rows --hierarchy clusters: one per atom (after_Lc) or one per structure (bf_property)")
+    p.add_argument("--hierarchy-min-samples", type=int, default=5, metavar="S",
+                   help="the neighbour whose distance is a row's core distance, 1 .. 31; 0: single linkage")
+    p.add_argument("--hierarchy-out", type=str, default="", help="save the tree as a LatentHierarchy (.npz) and its rows as FILE.index.npz")
+    p.add_argument("--attach", type=str, default="", metavar="TREE",
+                   help="also pickle the label of every structure (or atom) under a saved LatentHierarchy (.npz, with TREE.index.npz beside "
+                        "it) as attach_<target>.pickle")
+    p.add_argument("--attach-min-cluster-size", type=int, default=0, metavar="N", help="min_cluster_size of --attach")
     p.add_argument("--density", type=str, default="", metavar="INDEX",
                    help="also pickle the Gaussian kernel density of every structure (or atom) under a saved LatentIndex (.npz) as "
                         "density_<target>.pickle")

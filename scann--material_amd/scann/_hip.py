@@ -167,6 +167,9 @@ SYMBOLS = [
     ("scann_index_density_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, _P, _P]),
     ("scann_density_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_float, _P]),
     ("scann_peaks_host", C.c_int, [_P, C.c_int64, C.c_int64, C.c_float, _P, _P, _P]),
+    ("scann_index_mst", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_mst_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_mst_last_rounds", C.c_int, [C.c_int32, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -814,6 +817,62 @@ def peaks_host(rows, gamma):
     if rc < 0:
         raise ValueError("peaks_host: invalid arguments (%d)" % rc)
     return out
+
+
+MST_MAX_ROWS = 262144  # SCANN_MST_MAX_ROWS
+
+
+def check_mst_core2(core2, n_rows):
+    """core2 of a spanning tree as the C calls take it: None, or fp32 [n_rows] without a NaN or a negative entry; ValueError otherwise,
+    naming the argument and the position."""
+    if core2 is None:
+        return None
+    try:
+        core2 = np.ascontiguousarray(core2, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("core2 must be an array of numbers") from None
+    if core2.shape != (int(n_rows),):
+        raise ValueError("core2 must hold one value per row (%d), got shape %s" % (int(n_rows), core2.shape))
+    bad = np.flatnonzero(~(core2 >= 0))
+    if len(bad):
+        raise ValueError("core2[%d] is %s: core2 must hold no NaN and nothing negative" % (bad[0], "NaN" if np.isnan(core2[bad[0]]) else "negative"))
+    return core2
+
+
+def _mst_out(n):
+    m = max(int(n) - 1, 0)
+    return np.zeros(1, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32)
+
+
+def _mst_result(ne, a, b, w, rounds=None):
+    m = int(ne[0])
+    out = {"a": a[:m].copy(), "b": b[:m].copy(), "w": w[:m].copy()}
+    if rounds is not None:
+        out["rounds"] = int(rounds[0])
+    return out
+
+
+def mst_host(rows, core2=None):
+    """The minimum spanning tree of the complete graph over the eligible rows of ``rows`` [n, dim] on the host with the kernels' bits
+    (scann_mst_host, the definition in include/scann_hip.h): {"a", "b" int32 [n_edges], "w" fp32 [n_edges]}, the edges in the edge
+    order with a < b; w = max(dist2, core2[a], core2[b])."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("mst_host: rows of shape %s" % (rows.shape,))
+    core2 = check_mst_core2(core2, rows.shape[0])
+    ne, a, b, w = _mst_out(rows.shape[0])
+    rc = int(load_library().scann_mst_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(core2), _ptr(ne), _ptr(a), _ptr(b), _ptr(w)))
+    if rc < 0:
+        raise ValueError("mst_host: invalid arguments (%d)" % rc)
+    return _mst_result(ne, a, b, w)
+
+
+def mst_last_rounds():
+    """The record of this thread's last ``Engine.index_mst`` (scann_mst_last_rounds): {"components" int32 [rounds] before each round,
+    "seconds" fp64 [rounds], "skipped" int64 [rounds] tiles left out by the label rule, "tiles" of one round}."""
+    comp, sec, skip, tiles = np.zeros(40, np.int32), np.zeros(40, np.float64), np.zeros(40, np.int64), np.zeros(1, np.int64)
+    n = int(load_library().scann_mst_last_rounds(40, _ptr(comp), _ptr(sec), _ptr(skip), _ptr(tiles)))
+    return {"components": comp[:n].copy(), "seconds": sec[:n].copy(), "skipped": skip[:n].copy(), "tiles": int(tiles[0])}
 
 
 def check_rollout_args(residual, head, depth, num_head, n_attention):
@@ -1878,6 +1937,15 @@ class Engine:
         out = _peaks_out(len(ix))
         self._check(self.lib.scann_index_peaks(self._h, ix._h, g, _ptr(out["sum"]), _ptr(out["parent"]), _ptr(out["delta2"])))
         return out
+
+    def index_mst(self, ix, core2=None):
+        """The minimum spanning tree over the eligible rows of ``ix`` on the device (scann_index_mst): ``mst_host``'s dict, bit for bit,
+        plus "rounds", the Boruvka rounds run."""
+        core2 = check_mst_core2(core2, len(ix))
+        ne, a, b, w = _mst_out(len(ix))
+        rounds = np.zeros(1, np.int32)
+        self._check(self.lib.scann_index_mst(self._h, ix._h, _ptr(core2), _ptr(ne), _ptr(a), _ptr(b), _ptr(w), _ptr(rounds)))
+        return _mst_result(ne, a, b, w, rounds)
 
     def density_batch(self, ix, rb, level, gamma):
         """One forward of a resident batch and the density sums of its ``level`` rows under ``ix`` (scann_index_density_batch; raw y):

@@ -473,6 +473,47 @@ class LatentIndex:
         ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
         return peaks_result(r, ids, atoms, k, min_density, min_delta, h, gamma, self.level, self.dim)
 
+    def hierarchy(self, min_samples=5, route="device"):
+        """The hierarchical clustering of this index's rows: how the kinds nest, and which rows belong to none.  Single linkage
+        (``min_samples`` 0) and density-based hierarchical clustering (HDBSCAN, Campello et al. 2013; ``min_samples`` 1 .. 31) both rest
+        on the minimum spanning tree of the complete graph over the rows, the second with the mutual-reachability weight
+        max(dist2, core2_i, core2_j), core2_i the squared distance to the ``min_samples``-th nearest other row without a non-finite
+        component (``hierarchy_core2`` over ``neighbour_graph``: the exact search's bits).  The tree is built exactly on the GPU by
+        Boruvka rounds of all-pairs passes (scann_index_mst) and is unique under the edge order (w, min, max), so it depends on the index
+        contents and ``min_samples`` only, bit for bit.  ``route`` "host" runs the host twins on the rows read back: the same bits.
+        Returns ``(result, hierarchy)``: {"a", "b" int32 [n_edges], "w" fp32 [n_edges] (the edges in the edge order, a < b),
+        "core2" fp32 [N] (None for ``min_samples`` 0), "rounds" (device route), "n_eligible"} and the ``LatentHierarchy`` with
+        ``linkage()``, ``cut(...)`` and ``clusters(min_cluster_size)``.  Rows with a non-finite component are in no edge and get label
+        -1 everywhere.  Bad arguments and an index above 262,144 rows raise ValueError before any device call."""
+        min_samples, route = hierarchy_fit_args(min_samples, route)
+        N = len(self)
+        if N > _hip.MST_MAX_ROWS:
+            raise ValueError("the index has %d rows, a hierarchy takes at most %d: thin it first with select(m), or cluster the medoids of "
+                             "cluster(k)" % (N, _hip.MST_MAX_ROWS))
+        eng = self.model.engine
+        rows = self.rows()[0] if (min_samples or route == "host") else None
+        core2 = None
+        if min_samples:
+            elig = np.isfinite(rows).all(axis=1)
+            if route == "host":
+                graph = lambda x: neighbour_graph_host(x, strict=False)  # noqa: E731
+            elif elig.all():
+                graph = lambda x: neighbour_graph(self, strict=False)  # noqa: E731
+            else:
+                def graph(x):  # the search over the rows that count, on the device like the rest
+                    sub = LatentIndex(self.model, self.level)
+                    try:
+                        return neighbour_graph(sub.add_rows(x), strict=False)
+                    finally:
+                        sub.free()
+            core2 = hierarchy_core2(rows, min_samples, graph, elig)
+        r = eng.index_mst(self._ix, core2) if route == "device" else _hip.mst_host(rows, core2)
+        ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
+        lone = -1
+        if N and not len(r["a"]):  # no edge: no eligible row, or one -- the rows tell
+            lone = hierarchy_lone_row(self.rows()[0] if rows is None else rows)
+        return hierarchy_result(r, core2, N, ids, atoms, min_samples, self.level, self.dim, lone)
+
     def place(self, rows, embedding):
         """Host ``rows`` [n, dim] on an existing map of this index (``embedding``, as ``embed`` returned it for these rows): each row's
         31 nearest index rows from the exact search, conditional weights calibrated to the embedding's perplexity
@@ -1259,11 +1300,12 @@ def embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route):
     return perp, (int(its[0]), int(its[1])), ex, route
 
 
-def neighbour_graph(index, chunk=4096):
+def neighbour_graph(index, chunk=4096, strict=True):
     """For every row of ``index`` its nearest other rows -- 31, or all others in a smaller index --: (position int32 [N, K], dist2 fp32
     [N, K]), nearest first.  The rows are read back and searched ``chunk`` at a time with k = 32 and no id skipping
     (``Engine.index_read`` + ``Engine.index_query``): bits and total order are the search's.  From a row's answer its own position is
-    dropped where it appears, otherwise (33 or more coincident rows) the last place.  ValueError for a row with a non-finite component."""
+    dropped where it appears, otherwise (33 or more coincident rows) the last place.  ValueError for a row with a non-finite component
+    (``strict`` False: no such check, an overflowed distance stays +inf; ``hierarchy`` passes rows without a non-finite component)."""
     eng, ix = index.model.engine, index._ix
     N = len(index)
     k = min(EMBED_NEIGHBOURS + 1, N)
@@ -1280,13 +1322,13 @@ def neighbour_graph(index, chunk=4096):
         keep[np.arange(b - a), drop] = False
         pos[a:b] = r["position"][keep].reshape(b - a, k - 1)
         d2[a:b] = r["dist2"][keep].reshape(b - a, k - 1)
-    if (pos < 0).any() or not np.isfinite(d2).all():
+    if strict and ((pos < 0).any() or not np.isfinite(d2).all()):
         raise ValueError("row %d has no %d neighbours at a finite distance: rows with a non-finite component cannot be embedded" % (
             int(np.nonzero((pos < 0).any(axis=1) | ~np.isfinite(d2).all(axis=1))[0][0]), k - 1))
     return pos, d2
 
 
-def neighbour_graph_host(rows, chunk=1024):
+def neighbour_graph_host(rows, chunk=1024, strict=True):
     """``neighbour_graph`` of host rows [N, dim] without a GPU: the search's distances (``_hip.knn_dist2_matrix``) ranked by (distance,
     position), the search's total order, so the same bits and places."""
     rows = np.ascontiguousarray(rows, dtype=np.float32)
@@ -1305,7 +1347,7 @@ def neighbour_graph_host(rows, chunk=1024):
         keep[np.arange(b - a), drop] = False
         pos[a:b] = order[keep].reshape(b - a, k - 1)
         d2[a:b] = np.take_along_axis(d, order, axis=1)[keep].reshape(b - a, k - 1)
-    if not np.isfinite(d2).all():
+    if strict and not np.isfinite(d2).all():
         raise ValueError("row %d has no %d neighbours at a finite distance: rows with a non-finite component cannot be embedded" % (
             int(np.nonzero(~np.isfinite(d2).all(axis=1))[0][0]), k - 1))
     return pos, d2
@@ -1693,3 +1735,322 @@ class LatentPeaks:
             raise ValueError("%s: a %s-level density-peak clustering of %d columns does not fit a model whose %s is %d" % (
                 path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
         return cls(*args, level, dim)
+
+
+HIER_MAX_SAMPLES = EMBED_NEIGHBOURS  # the farthest neighbour a core distance can look at: what ``neighbour_graph`` returns
+
+
+def hierarchy_fit_args(min_samples, route):
+    """The arguments of ``LatentIndex.hierarchy`` checked: (min_samples, route); ValueError otherwise, naming the argument"""
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 0 <= int(min_samples) <= HIER_MAX_SAMPLES:
+        raise ValueError("min_samples must be an integer in 0 .. %d, got %r" % (HIER_MAX_SAMPLES, min_samples))
+    if route not in ("device", "host"):
+        raise ValueError('route must be "device" or "host", got %r' % (route,))
+    return int(min_samples), route
+
+
+def check_min_cluster_size(min_cluster_size):
+    if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, np.integer)) or int(min_cluster_size) < 2:
+        raise ValueError("min_cluster_size must be an integer >= 2, got %r" % (min_cluster_size,))
+    return int(min_cluster_size)
+
+
+def hierarchy_core2(rows, min_samples, graph, elig=None):
+    """The squared core distances, fp32 [N]: for a row without a non-finite component the search's dist2 to its ``min_samples``-th
+    nearest OTHER such row -- its farthest one where there are fewer, 0 where it is alone --, and 0 for the other rows (they are in no
+    edge).  ``graph(rows of the eligible) -> (position, dist2 [n, K])`` is ``neighbour_graph`` / ``neighbour_graph_host`` without the
+    finiteness check."""
+    rows = np.asarray(rows, dtype=np.float32)
+    elig = np.isfinite(rows).all(axis=1) if elig is None else elig
+    core2 = np.zeros(rows.shape[0], np.float32)
+    if int(elig.sum()) >= 2:
+        _, d2 = graph(rows if elig.all() else np.ascontiguousarray(rows[elig]))
+        core2[elig] = d2[:, min(int(min_samples), d2.shape[1]) - 1]
+    return core2
+
+
+def hierarchy_lone_row(rows):
+    """the position of the one row without a non-finite component, -1 if there is none or more than one"""
+    elig = np.flatnonzero(np.isfinite(np.asarray(rows, dtype=np.float32)).all(axis=1)) if len(rows) else np.zeros(0, np.int64)
+    return int(elig[0]) if len(elig) == 1 else -1
+
+
+def hierarchy_result(r, core2, n_rows, ids, atoms, min_samples, level, dim, lone_position=-1):
+    """``LatentIndex.hierarchy``'s ``(result, hierarchy)`` from the tree's dict {"a", "b", "w"}; ``lone_position``: the one eligible row
+    of a tree without edges, -1 if there is none"""
+    h = LatentHierarchy(r["a"], r["b"], r["w"], core2, n_rows, ids, atoms, min_samples, level, dim, lone_position)
+    result = {"a": h.a, "b": h.b, "w": h.w, "core2": h.core2 if min_samples else None, "n_eligible": h.n_eligible}
+    if "rounds" in r:
+        result["rounds"] = r["rounds"]
+    return result, h
+
+
+def hierarchy_rows_host(rows, min_samples=5, ids=None, atoms=None, level="structure"):
+    """``LatentIndex.hierarchy`` of host rows [N, dim] entirely on the host, no GPU: the twins of the search's distances and of the
+    tree -- bit for bit what an index holding these rows gives by either route."""
+    min_samples, _ = hierarchy_fit_args(min_samples, "host")
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rows must have shape [N, dim], got %s" % (rows.shape,))
+    N, dim = rows.shape
+    if N > _hip.MST_MAX_ROWS:
+        raise ValueError("%d rows, a hierarchy takes at most %d" % (N, _hip.MST_MAX_ROWS))
+    core2 = hierarchy_core2(rows, min_samples, lambda x: neighbour_graph_host(x, strict=False)) if min_samples else None
+    ids = np.arange(N, dtype=np.int64) if ids is None else ids
+    atoms = np.full(N, -1, np.int32) if atoms is None else atoms
+    r = _hip.mst_host(rows, core2)
+    return hierarchy_result(r, core2, N, ids, atoms, min_samples, level, dim, -1 if len(r["a"]) else hierarchy_lone_row(rows))
+
+
+def _number_by_least_member(raw, n_rows):
+    """raw labels (any integers >= 0, -1: none) renumbered 0, 1, .. in the order of each label's least member position: (label int32
+    [n_rows], the raw label of every new number)"""
+    raw = np.asarray(raw, dtype=np.int64)
+    pos = np.flatnonzero(raw >= 0)
+    label = np.full(n_rows, -1, np.int32)
+    if not len(pos):
+        return label, np.zeros(0, np.int64)
+    uniq, first = np.unique(raw[pos], return_index=True)  # first: the least position among each label's members (pos ascends)
+    order = np.argsort(first, kind="stable")
+    number = np.empty(len(uniq), np.int64)
+    number[order] = np.arange(len(uniq))
+    label[pos] = number[np.searchsorted(uniq, raw[pos])]
+    return label, uniq[order]
+
+
+class LatentHierarchy:
+    """The hierarchical clustering of one level of one model, as ``LatentIndex.hierarchy`` builds it: the N - 1 edges of the minimum
+    spanning tree in the edge order (w ascending, then the positions), the squared core distances, the rows' ids and atoms.  Everything
+    derived from it -- ``linkage``, ``cut``, ``clusters`` -- is deterministic fp64 NumPy on the sorted edges.  The rows that count
+    (the eligible ones: no non-finite component) are the rows the edges name; a tree without edges has none, or the one at
+    ``lone_position``.  The other rows get label -1 everywhere."""
+
+    def __init__(self, a, b, w, core2, n_rows, ids, atoms, min_samples, level, dim, lone_position=-1):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        try:
+            self.a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+            self.b = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+            self.w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+            self.ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            self.atoms = np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+            n = int(n_rows)
+            self.core2 = np.zeros(n, np.float32) if core2 is None else np.ascontiguousarray(core2, dtype=np.float32).reshape(-1)
+            self.min_samples = int(min_samples)
+        except (TypeError, ValueError):
+            raise ValueError("a, b, ids and atoms must be arrays of integers, w and core2 arrays of numbers") from None
+        m = self.a.shape[0]
+        if self.b.shape != (m,) or self.w.shape != (m,):
+            raise ValueError("a %s, b %s and w %s must hold one entry per edge" % (self.a.shape, self.b.shape, self.w.shape))
+        if self.ids.shape != (n,) or self.atoms.shape != (n,) or self.core2.shape != (n,):
+            raise ValueError("ids %s, atoms %s and core2 %s must hold one entry per row (%d)" % (self.ids.shape, self.atoms.shape, self.core2.shape, n))
+        if m and (self.a.min() < 0 or self.b.max() >= n or not (self.a < self.b).all()):
+            raise ValueError("every edge must name rows a < b in 0 .. %d" % (n - 1))
+        if m and (not (self.w >= 0).all() or not (np.diff(self.w) >= 0).all()):
+            raise ValueError("w must be non-negative and ascending")
+        self.level, self.dim, self.n_rows = level, int(dim), n
+        # the rows that count, and the merges: cluster n_eligible + e joins the clusters of a[e] and b[e] (union-find over the edges)
+        in_tree = np.zeros(n, bool)
+        in_tree[self.a], in_tree[self.b] = True, True
+        self.lone_position = int(lone_position)
+        if self.lone_position != -1:
+            if m or not 0 <= self.lone_position < n:
+                raise ValueError("lone_position names the one eligible row of a tree without edges, in 0 .. %d; got %d with %d edges" % (
+                    n - 1, self.lone_position, m))
+            in_tree[self.lone_position] = True
+        self.leaf_position = np.flatnonzero(in_tree).astype(np.int32)
+        ne = self.n_eligible = len(self.leaf_position)
+        if m != max(ne - 1, 0):
+            raise ValueError("%d edges over %d rows are no spanning tree" % (m, ne))
+        leaf = np.full(n, -1, np.int64)
+        leaf[self.leaf_position] = np.arange(ne)
+        top = list(range(ne))  # union-find over leaves; top[root] = the cluster id the set carries
+        up = list(range(ne))
+        size = [1] * ne
+        left, right, count = np.zeros(m, np.int64), np.zeros(m, np.int64), np.zeros(m, np.int64)
+
+        def find(x):
+            r = x
+            while up[r] != r:
+                r = up[r]
+            while up[x] != r:
+                up[x], x = r, up[x]
+            return r
+
+        for e, (x, y) in enumerate(zip(leaf[self.a].tolist(), leaf[self.b].tolist())):
+            rx, ry = find(x), find(y)
+            if rx == ry:
+                raise ValueError("the edges close a cycle at edge %d" % e)
+            cx, cy = top[rx], top[ry]
+            left[e], right[e] = min(cx, cy), max(cx, cy)
+            if size[rx] < size[ry]:
+                rx, ry = ry, rx
+            up[ry] = rx
+            size[rx] += size[ry]
+            top[rx] = ne + e
+            count[e] = size[rx]
+        self._left, self._right, self._count = left, right, count
+
+    def __len__(self):
+        return self.n_rows
+
+    def check_model(self, model):
+        """ValueError unless the hierarchy has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError("a %s-level hierarchy of %d columns does not fit a model whose %s is %d" % (
+                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+
+    def linkage(self):
+        """The dendrogram in SciPy's layout, fp64 [n - 1, 4], n the rows that count: merge e joins the clusters of a[e] and b[e] in edge
+        order at height sqrt(w[e]); columns: the two cluster ids (the smaller first), the height, the rows of the new cluster n + e.
+        Leaf i is the i-th row that count in position order (``leaf_position``; the position itself when all rows count).  Usable with
+        ``scipy.cluster.hierarchy.dendrogram`` as it is."""
+        return np.stack([self._left.astype(np.float64), self._right.astype(np.float64), np.sqrt(self.w.astype(np.float64)),
+                         self._count.astype(np.float64)], axis=1) if len(self.w) else np.zeros((0, 4))
+
+    def cut(self, height=None, k=None):
+        """The flat clustering of a cut through the dendrogram, int32 [N]: with ``height`` the merges at sqrt(w) <= height are made, with
+        ``k`` the first n - k merges (k clusters; 1 <= k <= n).  Clusters are numbered by their least member position; rows that do not
+        count get -1."""
+        if (height is None) == (k is None):
+            raise ValueError("exactly one of height and k must be given")
+        ne, m = self.n_eligible, len(self.w)
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= max(ne, 1):
+                raise ValueError("k must be an integer in 1 .. %d, got %r" % (max(ne, 1), k))
+            n_merge = max(ne - int(k), 0)
+        else:
+            try:
+                hgt = float(height)
+            except (TypeError, ValueError):
+                raise ValueError("height must be a number >= 0, got %r" % (height,)) from None
+            if isinstance(height, bool) or not hgt >= 0:
+                raise ValueError("height must be a number >= 0, got %r" % (height,))
+            n_merge = int(np.searchsorted(np.sqrt(self.w.astype(np.float64)), hgt, side="right"))
+        # the cluster of every leaf after n_merge merges: the nodes ne + e, e < n_merge, top-down
+        owner = np.arange(ne + m, dtype=np.int64)
+        for e in range(n_merge - 1, -1, -1):
+            owner[self._left[e]] = owner[self._right[e]] = owner[ne + e]
+        raw = np.full(self.n_rows, -1, np.int64)
+        raw[self.leaf_position] = owner[:ne]
+        return _number_by_least_member(raw, self.n_rows)[0]
+
+    def clusters(self, min_cluster_size):
+        """HDBSCAN's condensed tree and excess-of-mass selection on the dendrogram.  lambda = 1 / sqrt(w); a zero-weight merge takes the
+        largest lambda of the merges with w > 0, or 1 if there is none, which keeps every stability finite.  Walking down from the root,
+        a split whose two sides both hold >= ``min_cluster_size`` rows makes two new clusters born at the split's lambda; otherwise the
+        rows of a side below ``min_cluster_size`` fall out of the cluster at that lambda and the other side carries it on.
+        stability(c) = the sum over the rows of c of (lambda_leave - lambda_birth), a row that passes into a child cluster leaving at the
+        child's birth.  Bottom-up, a cluster is selected iff its stability >= the sum of its children's selected totals; the root is
+        never selected.  {"label" int32 [N] (-1: noise; clusters numbered by least member position), "probability" fp64 [N]
+        (lambda_leave over the largest lambda_leave of the row's cluster, capped at 1; 0 for noise), "persistence" fp64 per cluster (its
+        stability), "birth2" fp32 per cluster (the squared level w at which it joins its parent), "exemplar" int32 per cluster (the
+        member of largest lambda_leave, least position on ties), "size" int64 per cluster, "lambda" fp64 [N] (lambda_leave; NaN for rows
+        that do not count)}."""
+        mcs = check_min_cluster_size(min_cluster_size)
+        N, ne, m = self.n_rows, self.n_eligible, len(self.w)
+        out = {"label": np.full(N, -1, np.int32), "probability": np.zeros(N), "persistence": np.zeros(0), "birth2": np.zeros(0, np.float32),
+               "exemplar": np.zeros(0, np.int32), "size": np.zeros(0, np.int64), "lambda": np.full(N, np.nan)}
+        if m == 0:
+            return out
+        w64 = self.w.astype(np.float64)
+        with np.errstate(divide="ignore"):
+            lam = 1.0 / np.sqrt(w64)
+        lam[w64 == 0] = lam[w64 > 0].max() if (w64 > 0).any() else 1.0
+        left, right = self._left.tolist(), self._right.tolist()
+        size = [1] * ne + self._count.tolist()
+        lam_l, w_l = lam.tolist(), self.w.tolist()
+        c_parent, c_birth, c_birth2 = [-1], [0.0], [float("inf")]  # cluster 0 is the root
+        c_stab, c_children = [0.0], [[]]
+        p_cluster, p_lambda = [0] * ne, [0.0] * ne
+        stack = [(ne + m - 1, 0)]
+        while stack:
+            node, c = stack.pop()
+            e = node - ne
+            l, r, la = left[e], right[e], lam_l[e]
+            if size[l] >= mcs and size[r] >= mcs:
+                for side in (l, r):
+                    k = len(c_parent)
+                    c_parent.append(c), c_birth.append(la), c_birth2.append(w_l[e]), c_stab.append(0.0), c_children.append([])
+                    c_children[c].append(k)
+                    c_stab[c] += size[side] * (la - c_birth[c])
+                    stack.append((side, k))
+                continue
+            for side in (l, r):
+                if size[side] >= mcs:
+                    stack.append((side, c))
+                    continue
+                c_stab[c] += size[side] * (la - c_birth[c])
+                todo = [side]  # the side's rows fall out of c here
+                while todo:
+                    x = todo.pop()
+                    if x < ne:
+                        p_cluster[x], p_lambda[x] = c, la
+                    else:
+                        todo.append(left[x - ne]), todo.append(right[x - ne])
+        # excess of mass, bottom-up: children carry larger numbers than their parents
+        n_c = len(c_parent)
+        chosen, total = [False] * n_c, [0.0] * n_c
+        for c in range(n_c - 1, 0, -1):
+            below = sum(total[k] for k in c_children[c])
+            if c_stab[c] >= below:
+                chosen[c], total[c] = True, c_stab[c]
+            else:
+                total[c] = below
+        owner = [-1] * n_c  # the selected cluster at or above c that no selected cluster lies above
+        for c in range(1, n_c):
+            owner[c] = owner[c_parent[c]] if owner[c_parent[c]] >= 0 else (c if chosen[c] else -1)
+        raw = np.full(N, -1, np.int64)
+        raw[self.leaf_position] = np.asarray(owner, dtype=np.int64)[np.asarray(p_cluster, dtype=np.int64)]
+        label, which = _number_by_least_member(raw, N)
+        lam_row = np.full(N, np.nan)
+        lam_row[self.leaf_position] = p_lambda
+        k = len(which)
+        top = np.zeros(k)
+        member = label >= 0
+        np.maximum.at(top, label[member], lam_row[member])
+        prob = np.zeros(N)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            prob[member] = np.where(top[label[member]] > 0, np.minimum(lam_row[member] / top[label[member]], 1.0), 1.0)
+        exemplar = np.full(k, -1, np.int32)
+        for i in np.flatnonzero(member)[::-1].tolist():  # descending positions: the least position among the largest stays
+            if lam_row[i] == top[label[i]]:
+                exemplar[label[i]] = i
+        out.update(label=label, probability=prob, persistence=np.asarray(c_stab)[which], birth2=np.asarray(c_birth2, dtype=np.float32)[which],
+                   exemplar=exemplar, size=np.bincount(label[member], minlength=k).astype(np.int64))
+        out["lambda"] = lam_row
+        return out
+
+    def attach_labels(self, position, dist2, clusters):
+        """The labels of new rows from their nearest index row (``position``, ``dist2`` as ``nearest(k=1)`` / scann_index_query_batch
+        report them) under ``clusters`` (what ``clusters(min_cluster_size)`` returned): the label of the nearest row r, or -1 if r is
+        noise, if there is no r, or if max(dist2, core2[r]) >= birth2[label] -- the new row would lie outside the cluster at the level
+        where the cluster is born."""
+        p = np.asarray(position)
+        d = np.asarray(dist2, dtype=np.float32)
+        if p.dtype.kind not in "iu" or p.shape != d.shape or (p.size and (p.min() < -1 or p.max() >= len(self))):
+            raise ValueError("position must hold integers in -1 .. %d and dist2 one distance each" % (len(self) - 1))
+        q = np.maximum(p, 0)
+        lab = np.where(p >= 0, clusters["label"][q], -1).astype(np.int32) if len(self) else np.full(p.shape, -1, np.int32)
+        if len(self) and len(clusters["birth2"]):
+            reach = np.maximum(d, self.core2[q])
+            lab = np.where((lab >= 0) & ~(reach < clusters["birth2"][np.maximum(lab, 0)]), -1, lab).astype(np.int32)
+        return lab
+
+    def save(self, path):
+        """An ``.npz`` of the edges, core2, ids, atoms, min_samples, level and dim (written to exactly ``path``; no pickle)."""
+        with open(path, "wb") as f:
+            np.savez(f, a=self.a, b=self.b, w=self.w, core2=self.core2, ids=self.ids, atoms=self.atoms,
+                     min_samples=np.array(self.min_samples, dtype=np.int64), lone_position=np.array(self.lone_position, dtype=np.int64), level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved hierarchy; ValueError if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            level, dim = str(z["level"]), int(z["dim"])
+            args = (z["a"], z["b"], z["w"], z["core2"], len(z["ids"]), z["ids"], z["atoms"], int(z["min_samples"]))
+            lone = int(z["lone_position"])
+        if level not in LEVELS or level_dim(model.config, level) != dim:
+            raise ValueError("%s: a %s-level hierarchy of %d columns does not fit a model whose %s is %d" % (
+                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
+        return cls(*args, level, dim, lone)

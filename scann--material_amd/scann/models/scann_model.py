@@ -15,8 +15,9 @@ import os
 import numpy as np
 
 from .. import _hip
-from .latent_index import (EMBED_NEIGHBOURS, LatentClassHead, LatentClustering, LatentEmbedding, LatentHead, LatentIndex, LatentKernelHead, LatentProjection,
-                           batch_jobs, density_of_sums, embed_fit_args, level_dim, peaks_fit_args, stop_dist2_of)
+from .latent_index import (EMBED_NEIGHBOURS, LatentClassHead, LatentClustering, LatentEmbedding, LatentHead, LatentHierarchy, LatentIndex, LatentKernelHead,
+                           LatentProjection, batch_jobs, check_min_cluster_size, density_of_sums, embed_fit_args, hierarchy_fit_args, level_dim, peaks_fit_args,
+                           stop_dist2_of)
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
 
@@ -581,6 +582,70 @@ class HipModel:
         finally:
             if own is not None:
                 own.free()
+
+    def hierarchy(self, data, level="atom", min_samples=5, min_cluster_size=None, route="device", ids=None, batch_size=None):
+        """How the kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``)
+        nest, and which rows belong to none: hierarchical clustering in the model's latent space -- single linkage (``min_samples`` 0)
+        or HDBSCAN -- on the exact minimum spanning tree, built on the GPU and bit-reproducible (``LatentIndex.hierarchy``).  ``data``
+        is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for the call
+        (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(result, hierarchy)``:
+        ``LatentIndex.hierarchy``'s dict -- with ``min_cluster_size`` also the entries of ``hierarchy.clusters(min_cluster_size)`` --
+        and the ``LatentHierarchy`` that ``attach`` takes.  Bad arguments raise ValueError before anything is uploaded."""
+        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        hierarchy_fit_args(min_samples, route)
+        if min_cluster_size is not None:
+            check_min_cluster_size(min_cluster_size)
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            result, h = index.hierarchy(min_samples=min_samples, route=route)
+        finally:
+            if own is not None:
+                own.free()
+        if min_cluster_size is not None:
+            result.update(h.clusters(min_cluster_size))
+        return result, h
+
+    def attach(self, inputs, hierarchy, index, min_cluster_size, batch_size=None):
+        """New ``inputs`` under an existing hierarchy, right behind their forward: every structure (or, at atom level, every atom)
+        takes the label its nearest row r of ``index`` -- the ``LatentIndex`` that ``hierarchy`` was built on -- has in
+        ``hierarchy.clusters(min_cluster_size)``, from the exact search (scann_index_query_batch, k = 1); -1 if r is noise or if
+        max(dist2, core2[r]) >= the squared level at which r's cluster is born (``LatentHierarchy.attach_labels``).  A padded dict
+        gives {"predict_property": [B, 1], "global_attention": the scores as ``predict`` returns them, "label": int32 [B],
+        "nearest_position": int32 [B], "nearest_id": int64 [B], "nearest_atom": int32 [B], "nearest_distance": fp32 [B]} and at atom
+        level [B, M] arrays with -1 / 0 at padded atoms; a ``PackedBatch`` gives packed arrays.  Raw y.  A hierarchy of another width
+        or size than the index, or a bad min_cluster_size or batch_size, raise ValueError before anything is uploaded."""
+        if not isinstance(hierarchy, LatentHierarchy):
+            raise ValueError("hierarchy must be a LatentHierarchy, got %r" % (type(hierarchy).__name__,))
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        hierarchy.check_model(self)
+        index.check_model(self)
+        if hierarchy.level != index.level or len(hierarchy) != len(index) or len(index) < 1:
+            raise ValueError("the hierarchy (%s level, %d rows) was not built on this index (%s level, %d rows)" % (
+                hierarchy.level, len(hierarchy), index.level, len(index)))
+        clusters = hierarchy.clusters(min_cluster_size)
+        self._batch_size(batch_size)
+        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
+        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, 1))
+        empty = {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "dist2": np.zeros((0, 1), np.float32),
+                 "position": np.zeros((0, 1), np.int32), "id": np.zeros((0, 1), np.int64), "atom": np.zeros((0, 1), np.int32)}
+        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        pos, d2 = cat["position"][:, 0], cat["dist2"][:, 0]
+        packed = isinstance(inputs, _hip.PackedBatch)
+        out = {"predict_property": cat["y"].reshape(-1, 1),
+               "global_attention": cat["ga"] if packed else _hip.repad_atoms(cat["ga"], inputs["atom_mask"])[..., None],
+               "label": hierarchy.attach_labels(pos, d2, clusters), "nearest_position": pos, "nearest_id": cat["id"][:, 0],
+               "nearest_atom": cat["atom"][:, 0], "nearest_distance": np.sqrt(d2)}
+        if atom and not packed:
+            for n, fill in (("label", -1), ("nearest_position", -1), ("nearest_id", -1), ("nearest_atom", -1), ("nearest_distance", 0)):
+                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
+        return out
 
     def density(self, inputs, index, bandwidth, batch_size=None):
         """The Gaussian kernel density of every structure (or, for an atom-level index, every atom) of ``inputs`` under the rows of a
@@ -1398,6 +1463,18 @@ class SCANN:
         """HipModel.density_peaks as it is: ``(result, peaks)``; densities and distances live in latent space."""
         return self.model.density_peaks(data, level=level, k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density,
                                         min_delta=min_delta, route=route, ids=ids, batch_size=batch_size)
+
+    def hierarchy(self, data, level="atom", min_samples=5, min_cluster_size=None, route="device", ids=None, batch_size=None):
+        """HipModel.hierarchy as it is: ``(result, hierarchy)``; weights and levels live in latent space."""
+        return self.model.hierarchy(data, level=level, min_samples=min_samples, min_cluster_size=min_cluster_size, route=route, ids=ids,
+                                    batch_size=batch_size)
+
+    def attach(self, ip, hierarchy, index, min_cluster_size, batch_size=None):
+        """HipModel.attach with ``predict_property`` in the units of the target (times std plus mean, as predict_data); labels and
+        distances live in latent space and stay as they are."""
+        out = self.model.attach(ip, hierarchy, index, min_cluster_size, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
 
     def density(self, ip, index, bandwidth, batch_size=None):
         """HipModel.density with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the densities
