@@ -877,6 +877,45 @@ int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2 /
 int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2, int64_t* n_edges, int32_t* a, int32_t* b, float* w);
 int scann_mst_last_rounds(int32_t cap, int32_t* components, double* seconds, int64_t* skipped, int64_t* tiles);
 
+/* ---- Silhouette of a labelled index ----
+ * Whether a labelling of the rows -- from scann_index_kmeans, from the density peaks, from a cut of the hierarchy -- is any good, and how
+ * many clusters the rows support (Rousseeuw, J. Comput. Appl. Math. 20, 53, 1987): for row i, a is its mean distance to the other rows
+ * of its own cluster and b the least mean distance to any other cluster; s = (b - a) / max(a, b), formed by the caller.  The pass is an
+ * exact O(N^2 dim) self-join of the index and is defined to the bit; the score, its mean and the choice of k are host work on top of it
+ * (LatentIndex.silhouette, LatentIndex.choose_k).
+ *   Eligibility: a row is eligible iff all its components are finite (the rule of scann_index_select).  A row COUNTS iff it is eligible
+ *     and its label is >= 0; labels are host [N], -1 .. C - 1, -1 for noise or unlabelled.  counts[c] = the counting rows with label c.
+ *   Term of a counting query i (a row of the index, by position) against a counting row j != i (by position):
+ *     d = dist2(row_i, row_j), exactly the chain of scann_knn_distsq with row i as q;  e = d if `squared`, else the correctly rounded fp32
+ *     square root of d;  t = llrintf(ldexpf(e, shift)), round to nearest even.  These are the terms of the call: if any of them has e not
+ *     finite or t > 2^31, the call returns SCANN_ERR_RANGE and its outputs are unspecified (a lower shift is the remedy).  N < 2^31, so
+ *     no order of the adds can overflow int64.
+ *   Sums: S[i][c] = the int64 sum of t over the counting rows j != i with label c.  No tree is part of the definition.
+ *   Finish, in fp64 IEEE operations, each rounded once, nothing contracted, for a counting query i with label ci:
+ *     a_i = ldexp((double)S[i][ci], -shift) / (counts[ci] - 1), or 0 when counts[ci] == 1;
+ *     b_i = the least of ldexp((double)S[i][c], -shift) / counts[c] over c != ci with counts[c] > 0, ties to the lower c, other_i that c;
+ *     with no such c, b_i = NaN and other_i = -1.
+ *     A query that does not count gets a = b = NaN, other = -1, and its row of `sums` is -1.
+ * qpos: host [nq] positions 0 .. N - 1 in any order, repeats allowed, or NULL: all N rows in position order (nq is then ignored).
+ * counts [C], a, b, other [nq], sums [nq * C] or NULL.
+ * Consequences: the result does not depend on the chunking, on how many add calls built the index, on the launch geometry or on a thread
+ * count; a qpos subset gives the rows of the full answer; dist2 is symmetric bit for bit.  The call changes nothing in the pool, the
+ * handle's weights, the training state or the selected outputs; inference, training and generic-width handles.  Synchronous: one small
+ * read-back of the rows' eligibility, then one host wait; the rows never leave the device, and the queries are taken in slices whose
+ * device table [slice][C] stays within 512 MiB.
+ * SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null argument, C outside 1 ..
+ * SCANN_KMEANS_MAX_K, a label outside -1 .. C - 1, a qpos outside 0 .. N - 1 (the entry is named), shift outside -126 .. 126, a pool of
+ * another handle.  An empty pool returns SCANN_OK with zero counts.
+ * scann_silhouette_host (rows [n * dim]; no GPU work) is the twin: the same bits, threaded over the queries -- `threads` > 0 fixes the
+ * thread count, 0 leaves it to the call (at most 16); the result does not depend on it. */
+int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* host [N], -1 .. C-1 */, int32_t C,
+                           const int32_t* qpos /* host [nq] positions, or NULL: all N rows */, int64_t nq, int32_t squared, int32_t shift,
+                           int64_t* counts /* [C] */, double* a /* [nq] */, double* b /* [nq] */, int32_t* other /* [nq] */,
+                           int64_t* sums /* [nq * C] or NULL */);
+int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const int32_t* qpos, int64_t nq,
+                          int32_t squared, int32_t shift, int32_t threads, int64_t* counts, double* a, double* b, int32_t* other,
+                          int64_t* sums);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

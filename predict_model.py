@@ -22,6 +22,11 @@ pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering
 in the model's latent space by k-means on the GPU, prints the sizes, ``n_iter`` / ``converged`` / inertia and each cluster's medoid
 (dataset index and atom), pickles the result as ``clusters_<target>.pickle`` and, with ``--cluster-out``, saves the centres as a
 ``LatentClustering`` (.npz) that ``SCANN.assign`` takes.
+``--cluster-sweep 2,4,8,16,32,64 [--cluster-level atom|structure] [--cluster-sample M] [--cluster-iter N] [--cluster-out FILE]`` chooses
+the number of clusters: k-means for every k of the list, each scored by the silhouette of its labels (every mean distance over all rows,
+exact on the GPU and bit-reproducible; ``--cluster-sample M``: the score is the mean over M sampled rows).  It prints the table -- score,
+inertia, Calinski-Harabasz, Davies-Bouldin, converged per k -- and the best k, pickles the table with the best k's clustering as
+``cluster_sweep_<target>.pickle`` and, with ``--cluster-out``, saves the best k's centres as a ``LatentClustering`` (.npz).
 ``--project M [--project-level atom|structure] [--project-out FILE]`` maps the dataset's structures (or atoms) onto the M leading
 principal components of the model's latent space (mean and covariance on the GPU, bit-reproducible), prints the rank and the explained
 variance, pickles the result -- coordinates, Mahalanobis distance and distance to the mean per row, with the rows' dataset indices and
@@ -136,6 +141,7 @@ def main(args):
         raise SystemExit("--cluster: K must lie in 1 .. 1024, got %d" % args.cluster)
     if args.cluster_iter < 0:
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
+    sweep = check_sweep_flags(args)
     head_targets = check_head_flags(args)
     kernel_head_targets = check_kernel_head_flags(args)
     class_labels = check_class_head_flags(args)
@@ -284,6 +290,24 @@ def main(args):
         for c in range(args.cluster):
             print("cluster %4d: size %8d, medoid id %d atom %d" % (c, res["size"][c], res["medoid_id"][c], res["medoid_atom"][c]))
         pickle.dump(res, open(os.path.join(args.trained_model, "clusters_{}.pickle".format(target)), "wb"))
+        if args.cluster_out:
+            clustering.save(args.cluster_out)
+        clustering.free()
+    if sweep:
+        pool = scann.build_index(data, level=args.cluster_level, ids=data.indexes)
+        print("Choose the number of clusters of the dataset's %d rows (%s level) among %s" % (len(pool), args.cluster_level, sweep))
+        try:
+            table, clustering = scann.choose_k(pool, sweep, sample=args.cluster_sample or None, max_iter=args.cluster_iter)
+        except ValueError as e:
+            raise SystemExit("--cluster-sweep: %s" % e)
+        finally:
+            pool.free()
+        print("     k  silhouette       inertia  Calinski-Harabasz  Davies-Bouldin  converged")
+        for i, k in enumerate(table["k"]):
+            print("%6d  %10.6f  %12.6g  %17.6g  %14.6g  %s" % (k, table["score"][i], table["inertia"][i], table["calinski_harabasz"][i],
+                                                              table["davies_bouldin"][i], bool(table["converged"][i])))
+        print("best k %d, sizes %s" % (table["best_k"], table["best"]["size"].tolist()))
+        pickle.dump(table, open(os.path.join(args.trained_model, "cluster_sweep_{}.pickle".format(target)), "wb"))
         if args.cluster_out:
             clustering.save(args.cluster_out)
         clustering.free()
@@ -480,6 +504,25 @@ def check_hierarchy_flags(args):
         raise SystemExit("--attach-min-cluster-size: needs --attach")
     if args.attach and args.attach_min_cluster_size < 2:
         raise SystemExit("--attach: needs --attach-min-cluster-size N >= 2")
+
+
+def check_sweep_flags(args):
+    """--cluster-sweep's list of k as integers (None without the flag); SystemExit for a bad list or flags that need it"""
+    if not args.cluster_sweep:
+        if args.cluster_sample:
+            raise SystemExit("--cluster-sample: needs --cluster-sweep")
+        return None
+    if args.cluster:
+        raise SystemExit("--cluster-sweep: chooses k itself, drop --cluster")
+    try:
+        ks = [int(x) for x in args.cluster_sweep.split(",")]
+    except ValueError:
+        raise SystemExit("--cluster-sweep: a comma-separated list of integers, got %r" % args.cluster_sweep)
+    if not ks or min(ks) < 1 or max(ks) > 1024:
+        raise SystemExit("--cluster-sweep: every k must lie in 1 .. 1024, got %r" % args.cluster_sweep)
+    if args.cluster_sample < 0:
+        raise SystemExit("--cluster-sample: M must be >= 1, got %d" % args.cluster_sample)
+    return ks
 
 
 def attach_records(scann, data, tree, index, min_cluster_size):
@@ -715,6 +758,12 @@ def parser():
                    help="atom: after_Lc rows, one per atom; structure: bf_property rows, one per structure")
     p.add_argument("--cluster-iter", type=int, default=50, help="at most N updates of the centres")
     p.add_argument("--cluster-out", type=str, default="", help="save the centres as a LatentClustering (.npz) for SCANN.assign")
+    p.add_argument("--cluster-sweep", type=str, default="", metavar="K1,K2,...",
+                   help="choose the number of clusters: k-means for every k of the list, scored by the silhouette of its labels (exact on "
+                        "the GPU, bit-reproducible); prints the table, pickles it as cluster_sweep_<target>.pickle; --cluster-out saves the "
+                        "best k's centres")
+    p.add_argument("--cluster-sample", type=int, default=0, metavar="M",
+                   help="--cluster-sweep scores M sampled rows instead of all (their values are exact: every mean is over all rows)")
     p.add_argument("--project", type=int, default=0,
                    help="also map the dataset's rows onto the M leading principal components of the latent space (moments on the GPU, "
                         "bit-reproducible) and pickle coordinates and distances as projection_<target>.pickle")

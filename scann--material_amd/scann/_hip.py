@@ -170,6 +170,8 @@ SYMBOLS = [
     ("scann_index_mst", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     ("scann_mst_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     ("scann_mst_last_rounds", C.c_int, [C.c_int32, _P, _P, _P, _P]),
+    ("scann_index_silhouette", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_silhouette_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -865,6 +867,98 @@ def mst_host(rows, core2=None):
     if rc < 0:
         raise ValueError("mst_host: invalid arguments (%d)" % rc)
     return _mst_result(ne, a, b, w)
+
+
+# the silhouette: its metrics by name (the C calls' `squared`) and the range of its fixed-point shift
+SILHOUETTE_METRICS = {"euclidean": 0, "sqeuclidean": 1}
+SILHOUETTE_MAX_SHIFT = 126
+
+
+def check_silhouette_args(labels, n_rows, n_clusters, qpos, metric, shift):
+    """(labels int32 [n_rows], C, qpos int32 [nq] or None, squared, shift) of a silhouette pass as the C calls take them; ValueError
+    otherwise, naming the argument.  ``n_clusters`` None: one more than the largest label (at least 1)."""
+    try:
+        labels = np.ascontiguousarray(labels)
+    except (TypeError, ValueError):
+        raise ValueError("labels must be an array of integers") from None
+    if labels.dtype.kind not in "iu" or labels.shape != (int(n_rows),):
+        raise ValueError("labels must hold one integer per row (%d), got %s of shape %s" % (int(n_rows), labels.dtype, labels.shape))
+    top = int(labels.max()) if labels.size else -1
+    if n_clusters is None:
+        n_clusters = max(top + 1, 1)
+    if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= KMEANS_MAX_K:
+        raise ValueError("n_clusters must be an integer in 1 .. %d, got %r: a silhouette takes at most %d clusters" % (
+            KMEANS_MAX_K, n_clusters, KMEANS_MAX_K))
+    C_ = int(n_clusters)
+    if labels.size and (int(labels.min()) < -1 or top >= C_):
+        bad = int(np.flatnonzero((labels < -1) | (labels >= C_))[0])
+        raise ValueError("labels[%d] = %d outside -1 .. %d" % (bad, int(labels[bad]), C_ - 1))
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if qpos is not None:
+        try:
+            qpos = np.ascontiguousarray(qpos)
+        except (TypeError, ValueError):
+            raise ValueError("qpos must be an array of positions") from None
+        if qpos.dtype.kind not in "iu" or qpos.ndim != 1:
+            raise ValueError("qpos must be a one-dimensional array of integer positions, got %s of shape %s" % (qpos.dtype, qpos.shape))
+        if qpos.size and (int(qpos.min()) < 0 or int(qpos.max()) >= int(n_rows)):
+            bad = int(np.flatnonzero((qpos < 0) | (qpos >= int(n_rows)))[0])
+            raise ValueError("qpos[%d] = %d outside 0 .. %d" % (bad, int(qpos[bad]), int(n_rows) - 1))
+        qpos = np.ascontiguousarray(qpos, dtype=np.int32)
+    if not isinstance(metric, str) or metric not in SILHOUETTE_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (", ".join(SILHOUETTE_METRICS), metric))
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not -SILHOUETTE_MAX_SHIFT <= int(shift) <= SILHOUETTE_MAX_SHIFT:
+        raise ValueError("shift must be an integer in -%d .. %d, got %r" % (SILHOUETTE_MAX_SHIFT, SILHOUETTE_MAX_SHIFT, shift))
+    return labels, C_, qpos, SILHOUETTE_METRICS[metric], int(shift)
+
+
+def _silhouette_out(nq, n_clusters, table):
+    out = {"count": np.zeros(n_clusters, np.int64), "a": np.full(nq, np.nan, np.float64), "b": np.full(nq, np.nan, np.float64),
+           "other": np.full(nq, -1, np.int32)}
+    if table:
+        out["sums"] = np.full((nq, n_clusters), -1, np.int64)
+    return out
+
+
+def silhouette_shift(col_exp, variance, metric):
+    """The fixed-point shift of a silhouette pass from the column statistics of the rows (``moments_host`` / ``Engine.index_moments``:
+    ``col_exp`` f_j, ``variance`` the covariance's diagonal): the largest shift for which an upper bound of the largest term is <= 2^30.
+    Column j of two eligible rows differs by less than 2^(f_j + 1) -- by nothing where the column is constant --, so dist2 is below
+    B = sum_j 4^(f_j + 1), its fp32 chain below B (1 + (dim + 3) 2^-23), and the root below sqrt of that times (1 + 2^-24).  ValueError
+    if the bound is not a finite fp32 number: a distance could overflow."""
+    f = np.asarray(col_exp, np.int64)
+    moving = ~((f == 0) & (np.asarray(variance, np.float64) == 0.0))
+    bound = float(np.sum(np.ldexp(1.0, 2 * (f[moving] + 1)))) * (1.0 + (len(f) + 3) * 2.0 ** -23)
+    if not bound < 2.0 ** 128:
+        raise ValueError("the rows' column ranges bound a squared distance by %g, which is not finite in fp32: rescale the rows" % bound)
+    if SILHOUETTE_METRICS[metric] == 0:
+        bound = float(np.sqrt(bound)) * (1.0 + 2.0 ** -24)
+    if bound == 0.0:
+        return SILHOUETTE_MAX_SHIFT
+    ex = int(np.frexp(bound)[1])  # bound <= 2^ex
+    return int(min(max(30 - ex, -SILHOUETTE_MAX_SHIFT), SILHOUETTE_MAX_SHIFT))
+
+
+def silhouette_host(rows, labels, n_clusters=None, qpos=None, metric="euclidean", shift=0, table=False, threads=0):
+    """The silhouette pass over ``rows`` [n, dim] on the host with the kernels' bits (scann_silhouette_host, the definition in
+    include/scann_hip.h): {"count" int64 [C], "a", "b" fp64 [nq], "other" int32 [nq], "sums" int64 [nq, C] with ``table``}; ``qpos``
+    None: every row in position order.  ``threads`` 0: the call's own choice.  A term out of range raises ScannHipError (RANGE)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("silhouette_host: rows of shape %s" % (rows.shape,))
+    labels, C_, qpos, squared, shift = check_silhouette_args(labels, rows.shape[0], n_clusters, qpos, metric, shift)
+    if isinstance(threads, bool) or not isinstance(threads, (int, np.integer)) or not 0 <= int(threads) <= 256:
+        raise ValueError("threads must be an integer in 0 .. 256, got %r" % (threads,))
+    nq = rows.shape[0] if qpos is None else qpos.shape[0]
+    out = _silhouette_out(nq, C_, table)
+    rc = int(load_library().scann_silhouette_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(labels), C_, _ptr(qpos), nq, squared, shift,
+                                                  int(threads), _ptr(out["count"]), _ptr(out["a"]), _ptr(out["b"]), _ptr(out["other"]),
+                                                  _ptr(out.get("sums"))))
+    if rc == -7:
+        raise ScannHipError(rc, "scann_silhouette_host: a term is not finite or above 2^31 at shift %d: lower the shift" % shift)
+    if rc < 0:
+        raise ValueError("silhouette_host: invalid arguments (%d)" % rc)
+    return out
 
 
 def mst_last_rounds():
@@ -1946,6 +2040,15 @@ class Engine:
         rounds = np.zeros(1, np.int32)
         self._check(self.lib.scann_index_mst(self._h, ix._h, _ptr(core2), _ptr(ne), _ptr(a), _ptr(b), _ptr(w), _ptr(rounds)))
         return _mst_result(ne, a, b, w, rounds)
+
+    def index_silhouette(self, ix, labels, n_clusters=None, qpos=None, metric="euclidean", shift=0, table=False):
+        """The silhouette pass over the rows of ``ix`` on the device (scann_index_silhouette): ``silhouette_host``'s dict, bit for bit."""
+        labels, C_, qpos, squared, shift = check_silhouette_args(labels, len(ix), n_clusters, qpos, metric, shift)
+        nq = len(ix) if qpos is None else qpos.shape[0]
+        out = _silhouette_out(nq, C_, table)
+        self._check(self.lib.scann_index_silhouette(self._h, ix._h, _ptr(labels), C_, _ptr(qpos), nq, squared, shift, _ptr(out["count"]),
+                                                    _ptr(out["a"]), _ptr(out["b"]), _ptr(out["other"]), _ptr(out.get("sums"))))
+        return out
 
     def density_batch(self, ix, rb, level, gamma):
         """One forward of a resident batch and the density sums of its ``level`` rows under ``ix`` (scann_index_density_batch; raw y):

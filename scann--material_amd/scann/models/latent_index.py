@@ -216,21 +216,73 @@ class LatentIndex:
                 if init.shape[0] != k:
                     raise ValueError("init holds %d centres, k is %d" % (init.shape[0], k))
         r = eng.index_kmeans(self._ix, init, max_iter, stop_changed)
-        label, d2 = r["label"], r["dist2"]
         ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
-        medoid = np.full(k, -1, np.int32)
-        member = np.nonzero(label >= 0)[0]
-        least = np.full(k, np.inf, np.float32)
-        np.minimum.at(least, label[member], d2[member])
-        nearest = member[d2[member] == least[label[member]]]  # the members at their cluster's least dist2, positions ascending
-        cluster, first = np.unique(label[nearest], return_index=True)
-        medoid[cluster] = nearest[first]  # ... and of those the first position
-        has = medoid >= 0
-        return {"label": label, "distance": np.sqrt(d2),  # (correctly rounded on the host, as nearest reports distances)
-                "centre": r["centre"], "size": r["size"], "n_iter": int(r["n_iter"]), "converged": bool(r["converged"]),
-                "inertia": float(d2[member].astype(np.float64).sum()), "medoid_position": medoid,
-                "medoid_id": np.where(has, ids[np.maximum(medoid, 0)], -1).astype(np.int64),
-                "medoid_atom": np.where(has, atoms[np.maximum(medoid, 0)], -1).astype(np.int32)}
+        return cluster_result(r, ids, atoms, k)
+
+    def silhouette(self, labels, sample=None, seed=0, metric="euclidean", route="device", table=False, n_clusters=None):
+        """How good a labelling of this index's rows is, row by row and as a whole: the silhouette (Rousseeuw 1987).  For a row, ``a`` is
+        its mean distance to the other rows of its own cluster and ``b`` the least mean distance to the rows of any other cluster;
+        s = (b - a) / max(a, b) lies in [-1, 1], near 1 for a row well inside its cluster, near 0 for a row between two, and ``other``
+        names the second one.  Every mean is over all rows of the index, from one exact pass over all pairs on the GPU
+        (scann_index_silhouette), defined to the bit, so the result depends on the index contents and the arguments only.
+        ``labels``: an integer array [N], -1 for noise or unlabelled -- ``cluster(k)["label"]``, ``density_peaks(...)[0]["label"]``, the
+        labels of ``LatentHierarchy.clusters()``; at most 1024 clusters (``n_clusters``: their number, default the largest label + 1).
+        A row counts if it has a label >= 0 and no non-finite component.  ``sample``: None -- every row --, an integer m -- m counting
+        positions drawn without replacement by ``np.random.default_rng(seed)``, then sorted: the sampled rows' values are exact, only
+        the mean is sampled --, or an array of positions.  ``metric``: "euclidean" or "sqeuclidean".  ``route`` "host" runs the host
+        twin on the rows read back: the same bits.  Returns {"position" int32 [n], "silhouette", "a", "b" fp64 [n] (silhouette 0 for the
+        row of a one-row cluster and where a and b are both 0; NaN where the row does not count or there is no other cluster), "other"
+        int32 [n], "size" int64 [C] (the counting rows per cluster), "score" (the fp64 mean of the finite silhouettes, positions
+        ascending; NaN without any), "cluster_score" fp64 [C], "shift" (of the pass's fixed point, chosen from the index's column
+        ranges: ``silhouette_shift``), "metric", and with ``table`` "sums" int64 [n, C]}.  Bad arguments raise ValueError before any
+        device call."""
+        eng = self.model.engine
+        route = silhouette_route(route)
+        if route == "host":
+            return silhouette_rows_host(self.rows()[0], labels, sample=sample, seed=seed, metric=metric, table=table, n_clusters=n_clusters)
+        labels, C_, _, _, _ = _hip.check_silhouette_args(labels, len(self), n_clusters, None, metric, 0)
+        sample = silhouette_sample_arg(sample, seed, len(self))
+
+        def moments():
+            try:
+                return eng.index_moments(self._ix)
+            except _hip.ScannHipError:
+                return None  # fewer than two rows without a non-finite component: no pair, no term
+
+        def counting():
+            labelled = labels >= 0
+            size = eng.index_silhouette(self._ix, labels, C_, np.zeros(0, np.int32), metric, 0)["count"]
+            if int(size.sum()) == int(labelled.sum()):
+                return labelled  # (the usual case: nothing is read back)
+            return labelled & np.isfinite(self.rows()[0]).all(axis=1)
+
+        return silhouette_run(lambda q, shift: eng.index_silhouette(self._ix, labels, C_, q, metric, shift, table), moments, counting,
+                              labels, C_, sample, seed, metric)
+
+    @staticmethod
+    def cluster_scores(result):
+        """``cluster_scores(result)`` of this module: the Calinski-Harabasz and the Davies-Bouldin index of a ``cluster`` result."""
+        return cluster_scores(result)
+
+    def choose_k(self, ks, sample=None, seed=0, metric="euclidean", route="device", **cluster_args):
+        """How many kinds of row the model distinguishes: ``cluster(k, **cluster_args)`` and ``silhouette`` of its labels for every k
+        of ``ks``, and the k with the highest silhouette score, ties to the smaller k.  ``sample``, ``seed``, ``metric``: as
+        ``silhouette`` takes them (an integer sample is drawn anew, with the same seed, among each clustering's counting rows).
+        ``route`` "host" runs the host twins of both on the rows read back: the same bits.  Returns {"k" int64 [n_k] (ascending, each
+        once), "score", "inertia", "calinski_harabasz", "davies_bouldin" fp64 [n_k], "n_iter" int64 [n_k], "converged" bool [n_k],
+        "size" (a list of int64 arrays), "best_k", "best" (the best k's ``cluster`` result) and "silhouette" (its ``silhouette``
+        result)}.  Bad arguments raise ValueError before any device call."""
+        ks = choose_k_arg(ks)
+        route = silhouette_route(route)
+        if route == "host":
+            rows = self.rows()[0]
+            ids, atoms = self.names()
+            return choose_k_run(lambda k: cluster_rows_host(rows, k, ids=ids, atoms=atoms, **cluster_args),
+                                lambda lab, k: silhouette_rows_host(rows, lab, sample=sample, seed=seed, metric=metric, n_clusters=k), ks)
+        _hip.check_silhouette_args(np.zeros(len(self), np.int32), len(self), None, None, metric, 0)
+        silhouette_sample_arg(sample, seed, len(self))
+        return choose_k_run(lambda k: self.cluster(k, **cluster_args),
+                            lambda lab, k: self.silhouette(lab, sample=sample, seed=seed, metric=metric, n_clusters=k), ks)
 
     def pca(self, m=None):
         """The principal-component map of this index's rows, mean and covariance computed on the GPU (scann_index_moments) and
@@ -526,6 +578,216 @@ class LatentIndex:
 
     def free(self):
         self._ix.free()
+
+
+def cluster_result(r, ids, atoms, k):
+    """``LatentIndex.cluster``'s dict from the k-means call's result ``r`` and the rows' names"""
+    label, d2 = r["label"], r["dist2"]
+    medoid = np.full(k, -1, np.int32)
+    member = np.nonzero(label >= 0)[0]
+    least = np.full(k, np.inf, np.float32)
+    np.minimum.at(least, label[member], d2[member])
+    nearest = member[d2[member] == least[label[member]]]  # the members at their cluster's least dist2, positions ascending
+    cluster, first = np.unique(label[nearest], return_index=True)
+    medoid[cluster] = nearest[first]  # ... and of those the first position
+    has = medoid >= 0
+    return {"label": label, "distance": np.sqrt(d2),  # (correctly rounded on the host, as nearest reports distances)
+            "centre": r["centre"], "size": r["size"], "n_iter": int(r["n_iter"]), "converged": bool(r["converged"]),
+            "inertia": float(d2[member].astype(np.float64).sum()), "medoid_position": medoid,
+            "medoid_id": np.where(has, ids[np.maximum(medoid, 0)], -1).astype(np.int64),
+            "medoid_atom": np.where(has, atoms[np.maximum(medoid, 0)], -1).astype(np.int32)}
+
+
+def cluster_rows_host(rows, k, init="kcenter", max_iter=50, stop_changed=0, ids=None, atoms=None):
+    """``LatentIndex.cluster`` without a GPU: the host twins (``_hip.kcenter_host``, ``_hip.kmeans_host``) on ``rows`` [N, dim]; the
+    same dict, bit for bit.  ``ids`` default to the positions, ``atoms`` to -1."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rows must be [N, dim], got shape %s" % (rows.shape,))
+    k, max_iter, stop_changed = _hip.check_kmeans_args(k, max_iter, stop_changed)
+    N, dim = rows.shape
+    if isinstance(init, str):
+        if init != "kcenter":
+            raise ValueError('init must be "kcenter", %d positions or an array [%d, %d], got %r' % (k, k, dim, init))
+        picks = _hip.kcenter_host(rows, None, k, 0.0)
+        if picks["count"] < k:
+            raise ValueError("k = %d clusters need %d rows without a non-finite component, the rows have %d" % (k, k, picks["count"]))
+        init = rows[picks["position"]]
+    else:
+        a = np.asarray(init)
+        if a.dtype.kind in "iu" and a.ndim == 1:
+            if a.shape[0] != k or (k and (a.min() < 0 or a.max() >= N)):
+                raise ValueError("init must name %d positions in 0 .. %d, got %d of them" % (k, N - 1, a.shape[0]))
+            init = rows[a]
+        else:
+            init = _hip.check_kmeans_init(init, dim)
+            if init.shape[0] != k:
+                raise ValueError("init holds %d centres, k is %d" % (init.shape[0], k))
+    ids = np.arange(N, dtype=np.int64) if ids is None else np.asarray(ids, np.int64)
+    atoms = np.full(N, -1, np.int32) if atoms is None else np.asarray(atoms, np.int32)
+    return cluster_result(_hip.kmeans_host(rows, init, max_iter, stop_changed), ids, atoms, k)
+
+
+def silhouette_route(route):
+    if route not in ("device", "host"):
+        raise ValueError('route must be "device" or "host", got %r' % (route,))
+    return route
+
+
+def silhouette_sample_arg(sample, seed, n_rows):
+    """``sample`` of a silhouette checked: None, an integer m >= 1 (returned as int) or int32 positions; ValueError otherwise"""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+        raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
+    if sample is None:
+        return None
+    if isinstance(sample, bool):
+        raise ValueError("sample must be None, an integer >= 1 or an array of positions, got %r" % (sample,))
+    if isinstance(sample, (int, np.integer)):
+        if int(sample) < 1:
+            raise ValueError("sample must be None, an integer >= 1 or an array of positions, got %r" % (sample,))
+        return int(sample)
+    try:
+        pos = np.ascontiguousarray(sample)
+    except (TypeError, ValueError):
+        raise ValueError("sample must be None, an integer >= 1 or an array of positions") from None
+    if pos.dtype.kind not in "iu" or pos.ndim != 1:
+        raise ValueError("sample must be None, an integer >= 1 or a one-dimensional array of integer positions, got %s of shape %s" % (
+            pos.dtype, pos.shape))
+    if pos.size and (int(pos.min()) < 0 or int(pos.max()) >= int(n_rows)):
+        bad = int(np.flatnonzero((pos < 0) | (pos >= int(n_rows)))[0])
+        raise ValueError("sample[%d] = %d outside 0 .. %d" % (bad, int(pos[bad]), int(n_rows) - 1))
+    return pos.astype(np.int32)
+
+
+def silhouette_values(a, b, own_size):
+    """s = (b - a) / max(a, b) in fp64: 0 for the row of a one-row cluster and where max is 0, NaN where a or b is (the row does not
+    count, or there is no other cluster)"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    top = np.maximum(a, b)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = (b - a) / top
+    s = np.where(np.isfinite(top) & ((top == 0.0) | (np.asarray(own_size) == 1)), 0.0, s)
+    return np.where(np.isnan(a) | np.isnan(b), np.nan, s)
+
+
+def silhouette_run(run_pass, moments, counting, labels, n_clusters, sample, seed, metric):
+    """The host work around a silhouette pass, shared by the device and the host route.  ``run_pass(qpos or None, shift)`` is the pass,
+    ``moments()`` the column statistics of the rows (None with fewer than two eligible rows), ``counting()`` the bool mask of the rows
+    that count (asked for only when an integer sample has to be drawn)."""
+    mo = moments()
+    shift = 0 if mo is None else _hip.silhouette_shift(mo["col_exp"], np.diagonal(mo["cov"]), metric)
+    N = len(labels)
+    if sample is None:
+        qpos, position = None, np.arange(N, dtype=np.int32)
+    elif isinstance(sample, int):
+        pool = np.flatnonzero(counting())
+        if sample > len(pool):
+            raise ValueError("sample = %d, but only %d rows count (a label >= 0 and no non-finite component)" % (sample, len(pool)))
+        position = np.sort(np.random.default_rng(seed).choice(pool, sample, replace=False)).astype(np.int32)
+        qpos = position
+    else:
+        qpos = position = sample
+    r = run_pass(qpos, shift)
+    size = r["count"]
+    lab = labels[position]
+    s = silhouette_values(r["a"], r["b"], size[np.maximum(lab, 0)])
+    order = np.argsort(position, kind="stable")
+    fin = np.isfinite(s[order])
+    score = float(np.sum(s[order][fin], dtype=np.float64) / fin.sum()) if fin.any() else float("nan")
+    per = np.full(n_clusters, np.nan, np.float64)
+    for c in np.unique(lab[order][fin]):
+        v = s[order][fin][lab[order][fin] == c]
+        per[c] = float(np.sum(v, dtype=np.float64) / len(v))
+    out = {"position": position, "silhouette": s, "a": r["a"], "b": r["b"], "other": r["other"], "size": size, "score": score,
+           "cluster_score": per, "shift": shift, "metric": metric}
+    if "sums" in r:
+        out["sums"] = r["sums"]
+    return out
+
+
+def silhouette_rows_host(rows, labels, sample=None, seed=0, metric="euclidean", table=False, n_clusters=None):
+    """``LatentIndex.silhouette`` without a GPU: the host twin (``_hip.silhouette_host``) on ``rows`` [N, dim]; the same dict, bit for
+    bit."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rows must be [N, dim], got shape %s" % (rows.shape,))
+    labels, C_, _, _, _ = _hip.check_silhouette_args(labels, len(rows), n_clusters, None, metric, 0)
+    sample = silhouette_sample_arg(sample, seed, len(rows))
+
+    def moments():
+        try:
+            return _hip.moments_host(rows)
+        except ValueError:
+            return None
+
+    return silhouette_run(lambda q, shift: _hip.silhouette_host(rows, labels, C_, q, metric, shift, table), moments,
+                          lambda: (labels >= 0) & np.isfinite(rows).all(axis=1), labels, C_, sample, seed, metric)
+
+
+def cluster_scores(result):
+    """The two cheap companions of the silhouette from a ``cluster`` result, in fp64 NumPy, no device work: {"calinski_harabasz":
+    [B / (k - 1)] / [W / (n - k)] with W the inertia and B the sum over the clusters of size x the squared distance of the centre to the
+    size-weighted mean of the centres (higher is better; 1 where W is 0), "davies_bouldin": the mean over the clusters of the largest
+    (s_c + s_d) / |centre_c - centre_d|, s_c the mean distance of cluster c's rows to its centre (lower is better)}.  Empty clusters
+    are left out; NaN with fewer than two clusters or no more rows than clusters.  It reads "label", "distance", "centre", "size" and
+    "inertia", in whatever precision they come."""
+    size = np.asarray(result["size"], np.float64)
+    centre = np.asarray(result["centre"], np.float64)
+    label = np.asarray(result["label"])
+    dist = np.asarray(result["distance"], np.float64)
+    has = size > 0
+    k, n = int(has.sum()), float(size.sum())
+    if k < 2 or n <= k:
+        return {"calinski_harabasz": float("nan"), "davies_bouldin": float("nan")}
+    mean = (size[has, None] * centre[has]).sum(axis=0) / n
+    between = float((size[has] * ((centre[has] - mean) ** 2).sum(axis=1)).sum())
+    within = float(result["inertia"])
+    ch = 1.0 if within == 0.0 else between * (n - k) / (within * (k - 1.0))
+    member = label >= 0
+    spread = np.bincount(label[member], weights=dist[member], minlength=len(size))[has] / size[has]
+    gap = np.sqrt(((centre[has][:, None, :] - centre[has][None, :, :]) ** 2).sum(axis=2))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = (spread[:, None] + spread[None, :]) / gap
+    ratio[~np.isfinite(ratio)] = 0.0  # coincident centres and the diagonal count for nothing, as in scikit-learn
+    np.fill_diagonal(ratio, 0.0)
+    return {"calinski_harabasz": float(ch), "davies_bouldin": float(ratio.max(axis=1).mean())}
+
+
+def choose_k_arg(ks):
+    """``ks`` of ``choose_k`` checked: the distinct k ascending; ValueError unless they are integers in 1 .. 1024, at least one"""
+    try:
+        arr = np.asarray(list(ks))
+    except TypeError:
+        raise ValueError("ks must be a sequence of integers in 1 .. %d, got %r" % (_hip.KMEANS_MAX_K, ks)) from None
+    if arr.ndim != 1 or not arr.size or arr.dtype.kind not in "iu" or arr.min() < 1 or arr.max() > _hip.KMEANS_MAX_K:
+        raise ValueError("ks must be a sequence of integers in 1 .. %d, at least one, got %r" % (_hip.KMEANS_MAX_K, ks))
+    return [int(k) for k in np.unique(arr)]
+
+
+def choose_k_run(cluster, silhouette, ks):
+    """``choose_k``'s table from ``cluster(k)`` and ``silhouette(labels, k)`` over the ascending ``ks``"""
+    rows, best = [], None
+    for k in ks:
+        res = cluster(k)
+        sil = silhouette(res["label"], k)
+        extra = cluster_scores(res)
+        rows.append((k, sil["score"], res["inertia"], extra["calinski_harabasz"], extra["davies_bouldin"], res["n_iter"], res["converged"],
+                     res["size"]))
+        if best is None or (sil["score"] == sil["score"] and not best[1]["score"] >= sil["score"]):  # ties stay with the smaller k
+            best = (res, sil, k)
+    return {"k": np.array([r[0] for r in rows], np.int64), "score": np.array([r[1] for r in rows], np.float64),
+            "inertia": np.array([r[2] for r in rows], np.float64), "calinski_harabasz": np.array([r[3] for r in rows], np.float64),
+            "davies_bouldin": np.array([r[4] for r in rows], np.float64), "n_iter": np.array([r[5] for r in rows], np.int64),
+            "converged": np.array([r[6] for r in rows], bool), "size": [r[7] for r in rows], "best_k": best[2], "best": best[0],
+            "silhouette": best[1]}
+
+
+def choose_k_rows_host(rows, ks, sample=None, seed=0, metric="euclidean", **cluster_args):
+    """``LatentIndex.choose_k`` without a GPU: the host twins on ``rows`` [N, dim]; the same dict, bit for bit (``cluster_args`` may
+    carry ``ids`` and ``atoms``)."""
+    ks = choose_k_arg(ks)
+    return choose_k_run(lambda k: cluster_rows_host(rows, k, **cluster_args),
+                        lambda lab, k: silhouette_rows_host(rows, lab, sample=sample, seed=seed, metric=metric, n_clusters=k), ks)
 
 
 def head_grid(l2):

@@ -500,6 +500,51 @@ class HipModel:
             if own is not None:
                 own.free()
 
+    def silhouette(self, index, labels, sample=None, seed=0, metric="euclidean", route="device", table=False, n_clusters=None):
+        """How good a labelling of an index's rows is: the silhouette of every row and its mean, every mean distance over all rows of
+        the index from one exact pass over all pairs on the GPU, bit-reproducible (``LatentIndex.silhouette``, whose arguments and dict
+        these are).  ``labels`` come from ``cluster``, ``density_peaks`` or ``hierarchy``.  An index of another model and bad
+        arguments raise ValueError before any device call."""
+        if not isinstance(index, LatentIndex):
+            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        index.check_model(self)
+        return index.silhouette(labels, sample=sample, seed=seed, metric=metric, route=route, table=table, n_clusters=n_clusters)
+
+    def choose_k(self, data, ks, level="atom", sample=None, seed=0, metric="euclidean", init="kcenter", max_iter=50, stop_changed=0,
+                 route="device", ids=None, batch_size=None):
+        """How many kinds of atom environment (``level`` "atom") or of structure ("structure") the model distinguishes: ``cluster`` for
+        every k of ``ks``, each scored by the silhouette of its labels, on the GPU and bit-reproducible (``LatentIndex.choose_k``).
+        ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which is indexed once for
+        the call (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(table, clustering)``:
+        ``LatentIndex.choose_k``'s dict -- per k the score, the inertia, the Calinski-Harabasz and Davies-Bouldin indices, the sizes,
+        ``converged``; "best_k"; the best k's ``cluster`` and ``silhouette`` results -- and the ``LatentClustering`` of the best k's
+        centres, which ``assign`` takes and which can be saved.  Bad arguments raise ValueError before anything is uploaded."""
+        from .latent_index import choose_k_arg, silhouette_route, silhouette_sample_arg
+
+        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        ks = choose_k_arg(ks)
+        silhouette_route(route)
+        if metric not in _hip.SILHOUETTE_METRICS:
+            raise ValueError("metric must be one of %s, got %r" % (", ".join(_hip.SILHOUETTE_METRICS), metric))
+        silhouette_sample_arg(sample if np.ndim(sample) == 0 else None, seed, 0)  # (positions are checked against the index, once it is there)
+        _hip.check_kmeans_args(ks[-1], max_iter, stop_changed)
+        if isinstance(init, str) and init != "kcenter":
+            raise ValueError('init must be "kcenter" for a sweep over k, got %r' % (init,))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            table = index.choose_k(ks, sample=sample, seed=seed, metric=metric, route=route, init=init, max_iter=max_iter,
+                                   stop_changed=stop_changed)
+            return table, LatentClustering(table["best"]["centre"], index.level, index.dim)
+        finally:
+            if own is not None:
+                own.free()
+
     def assign(self, inputs, clustering, batch_size=None):
         """The cluster of every structure (or, for an atom-level clustering, every atom) of new ``inputs``, right behind their forward:
         ``nearest`` with k = 1 against an index that holds the centres in order, so bitwise the assignment of the clustering's
@@ -1440,6 +1485,16 @@ class SCANN:
     def cluster(self, data, k, level="atom", init="kcenter", max_iter=50, stop_changed=0, ids=None, batch_size=None):
         """HipModel.cluster as it is: ``(result, clustering)``; the distances live in latent space."""
         return self.model.cluster(data, k, level=level, init=init, max_iter=max_iter, stop_changed=stop_changed, ids=ids, batch_size=batch_size)
+
+    def silhouette(self, index, labels, sample=None, seed=0, metric="euclidean", route="device", table=False, n_clusters=None):
+        """HipModel.silhouette as it is: the distances live in latent space."""
+        return self.model.silhouette(index, labels, sample=sample, seed=seed, metric=metric, route=route, table=table, n_clusters=n_clusters)
+
+    def choose_k(self, data, ks, level="atom", sample=None, seed=0, metric="euclidean", init="kcenter", max_iter=50, stop_changed=0,
+                 route="device", ids=None, batch_size=None):
+        """HipModel.choose_k as it is: ``(table, clustering)``; the distances live in latent space."""
+        return self.model.choose_k(data, ks, level=level, sample=sample, seed=seed, metric=metric, init=init, max_iter=max_iter,
+                                   stop_changed=stop_changed, route=route, ids=ids, batch_size=batch_size)
 
     def assign(self, ip, clustering, batch_size=None):
         """HipModel.assign with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
