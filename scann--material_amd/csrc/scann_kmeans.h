@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scann_tile.h"
+
 namespace scann {
 
-constexpr int KM_LANES = 256;       // lanes of every workgroup
-constexpr int KM_TP = 128;          // pool rows of a tile of kmeans_assign_kernel
-constexpr int KM_TC = 64;           // centres per block of that kernel: a lane owns 8 rows x 4 centres
-constexpr int KM_SLAB = 32;         // columns per LDS slab
+constexpr int KM_LANES = TILE_LANES;      // lanes of every workgroup
+constexpr int KM_TP = TILE_TQ;      // pool rows of a tile of kmeans_assign_kernel
+constexpr int KM_TC = TILE_TR;      // centres per block of that kernel: a lane owns 8 rows x 4 centres
+constexpr int KM_SLAB = TILE_SLAB;      // columns per LDS slab
 constexpr int KM_MAX_GROUPS = 768;  // workgroups of an assignment at most (three fit a CU at its 138 registers): the tiles are dealt evenly, workgroup g walks tiles g, g + G, ...
 constexpr int KM_ROUNDS = 256;      // rounds whose `changed` counters the state holds: the host enqueues at most this many before it waits
 constexpr int KM_SUM_LDS = 64 << 10;  // bytes of int64 sums a workgroup of kmeans_sum_kernel keeps in LDS: k x cols x 8

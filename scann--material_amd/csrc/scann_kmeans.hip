@@ -12,11 +12,9 @@
 // kmeans_gather_kernel (init_pos only): the initial centres copied from the pool's rows on the device.
 // A round t is three launches on one stream; the host enqueues every round and waits once.  t is a launch argument, everything else
 // (done, changed_t) travels through device memory, and a launch after `done` returns at its first instruction:
-//   kmeans_assign_kernel    the hot path.  A workgroup of 256 lanes takes tiles of 128 pool rows and walks the centres 64 at a time; rows
-//                           and centres go through LDS in slabs of 32 columns, column-major (the next slab is fetched into registers
-//                           meanwhile), and a lane owns an 8 x 4 register block of independent (row, centre) chains, two centres of a
-//                           row per packed fp32 instruction (knn_tile_kernel's block, with the roles exchanged: the rows are the many
-//                           side here).  A chain is never split over lanes.  A lane keeps the first centre under the order for each of
+//   kmeans_assign_kernel    the hot path, on the tile and the slab pipeline of scann_tile.h: a workgroup takes tiles of 128 pool rows
+//                           (the tile's "queries": the rows are the many side here) and walks the centres 64 at a time (its "rows"); a
+//                           lane's block is 8 rows x 4 centres.  A lane keeps the first centre under the order for each of
 //                           its 8 rows over the centres it visits -- ascending, so a strict < keeps the lower index --, and the 16 lanes
 //                           of a row are reduced once per tile by comparisons of (dist2, index).  The distance matrix is never written.
 //                           It writes label / dist2 and counts the rows whose label changed: one integer add per workgroup.
@@ -38,11 +36,7 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int KM_PS = KM_TP, KM_CS = KM_TC;  // floats per staged column of the row / centre slab; column c lies (c / 4) * 4 floats further
-constexpr int KM_SLABS = KM_SLAB * (KM_PS + KM_CS) + 2 * KM_SLAB;  // floats of the two slabs
-constexpr int KM_ASSIGN_SMEM = KM_SLABS + 4 * KM_TP * 2;          // ... then per wave and row the wave's first centre (dist2, index)
+constexpr int KM_ASSIGN_SMEM = TILE_SLABS + 4 * KM_TP * 2;  // floats of the two slabs, then per wave and row the wave's first centre (dist2, index)
 
 __device__ __forceinline__ bool km_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
@@ -126,9 +120,9 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_assign_kernel(KmArgs a, int r
   __shared__ float4 km_smem[KM_ASSIGN_SMEM / 4];
   if (a.st->done) return;  // (uniform)
   float* sm = reinterpret_cast<float*>(km_smem);
-  float* ps = sm;                               // [32][KM_PS] + 32  row slab, column-major
-  float* cs = sm + KM_SLAB * KM_PS + KM_SLAB;   // [32][KM_CS] + 32  centre slab, column-major
-  float* red_d = sm + KM_SLABS;                 // [4][128] the waves' first centres of the tile's rows ...
+  float* ps = sm;                               // the row slab ...
+  float* cs = sm + tile_slab_floats(KM_TP);     // ... and the centre slab (tile_stage)
+  float* red_d = sm + TILE_SLABS;                // [4][128] the waves' first centres of the tile's rows ...
   int32_t* red_l = reinterpret_cast<int32_t*>(red_d + 4 * KM_TP);  // ... and their indices
   const int t = threadIdx.x, pg = t & 15, cg = t >> 4;
   const int k = a.k, stride = a.stride;
@@ -165,38 +159,11 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_assign_kernel(KmArgs a, int r
     fetch(0);
     for (int step = 0; step < n_step; ++step) {
       __syncthreads();  // the previous slab's reads (and the previous tile's reduction) are over
-      // column c of an item at [c * stride + (c / 4) * 4 + item]: the lanes of a wave hold 8 column groups of 8 items, and the shift per
-      // column group spreads their stores over the banks; the 16-byte reads below stay aligned
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int e = t + KM_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = ps + c * KM_PS + c + item;
-        d[0] = gp[i].x; d[KM_PS] = gp[i].y; d[2 * KM_PS] = gp[i].z; d[3 * KM_PS] = gp[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int e = t + KM_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = cs + c * KM_CS + c + item;
-        d[0] = gc[i].x; d[KM_CS] = gc[i].y; d[2 * KM_CS] = gc[i].z; d[3 * KM_CS] = gc[i].w;
-      }
+      tile_stage<KM_LANES, 4, KM_TP>(ps, gp, t);
+      tile_stage<KM_LANES, 2, KM_TC>(cs, gc, t);
       __syncthreads();
       if (step + 1 < n_step) fetch(step + 1);
-#pragma unroll 4
-      for (int c = 0; c < KM_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-        const int sh = c & ~3;
-        const float4 pa = *reinterpret_cast<const float4*>(ps + c * KM_PS + sh + 4 * pg);       // rows 4 pg .. 4 pg + 3
-        const float4 pb = *reinterpret_cast<const float4*>(ps + c * KM_PS + sh + 64 + 4 * pg);  // rows 64 + 4 pg .. 64 + 4 pg + 3
-        const float4 c4 = *reinterpret_cast<const float4*>(cs + c * KM_CS + sh + 4 * cg);       // centres 4 cg .. 4 cg + 3 of the block
-        const f2 c01{c4.x, c4.y}, c23{c4.z, c4.w};
-        const float pv[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const f2 pp{pv[j], pv[j]};
-          const f2 d0 = pp - c01, d1 = pp - c23;  // the row first; rounded once; the explicit fma keeps the square and the sum one operation
-          acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-          acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-        }
-      }
+      tile_slab<TileForm::DIFF>(ps, cs, pg, cg, acc, KM_SLAB);  // the row first
       if (step % n_slab != n_slab - 1) continue;
       // the centre block's last slab: the lane's 4 centres, ascending, against the first so far of each of its 8 rows
       const int c0 = (step / n_slab) * KM_TC + 4 * cg;
@@ -204,7 +171,7 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_assign_kernel(KmArgs a, int r
       for (int j = 0; j < 8; ++j) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float d = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
+          const float d = tile_at(acc, j, i);
           // a NaN distance never qualifies; the first centre that does is taken whatever its distance (+inf is ordered)
           if (c0 + i < k && d == d && (bl[j] < 0 || d < bd[j])) bd[j] = d, bl[j] = c0 + i;
         }
@@ -225,7 +192,7 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_assign_kernel(KmArgs a, int r
       const int w = t >> 6;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int r = (j < 4 ? 0 : 64 - 4) + 4 * pg + j;
+        const int r = tile_query(pg, j);
         red_d[w * KM_TP + r] = bd[j];
         red_l[w * KM_TP + r] = bl[j];
       }

@@ -126,7 +126,7 @@ int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch,
 int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
            int32_t* atoms, int32_t* pos, float* dev_d = nullptr) {
   const int64_t N = ix->n;
-  const int rpr = (int)std::max<int64_t>(KNN_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + KNN_TR - 1) / KNN_TR * KNN_TR);
+  const int rpr = (int)std::max<int64_t>(TILE_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + TILE_TR - 1) / TILE_TR * TILE_TR);
   // one launch over all chunks: every chunk is cut into the same number of ranges (those behind the last row stay empty)
   const int n_chunk = (int)((N + ix->chunk_rows - 1) / ix->chunk_rows);
   const int64_t n_range = (int64_t)n_chunk * ((std::min<int64_t>(N, ix->chunk_rows) + rpr - 1) / rpr);
@@ -257,7 +257,7 @@ int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out) {
   ix->device = h->device;
   ix->dim = dim;
   ix->stride = (dim + 3) / 4 * 4;
-  ix->chunk_rows = (int32_t)std::max<size_t>(4096, ((size_t)64 << 20) / ((size_t)ix->stride * 4) / KNN_TR * KNN_TR);
+  ix->chunk_rows = (int32_t)std::max<size_t>(4096, ((size_t)64 << 20) / ((size_t)ix->stride * 4) / TILE_TR * TILE_TR);
   *out = ix;
   return SCANN_OK;
 }
@@ -889,19 +889,19 @@ int match_search(scann_handle* h, scann_index* ix, const float* dq, const int32_
   if (N == 0) return SCANN_OK;
   const int64_t n_seg = (int64_t)ix->seg_first.size();
   auto seg_end = [&](int64_t g) { return g + 1 < n_seg ? (int64_t)ix->seg_first[(size_t)(g + 1)] : N; };
-  // the tiles: whole structures, at most MT_TQ atoms and MT_SETS structures each
+  // the tiles: whole structures, at most TILE_TQ atoms and MT_SETS structures each
   std::vector<int32_t> tiles;
   int64_t most_sets = 1;
   for (int64_t b = 0; b < n_sets;) {
     int64_t e = b + 1;
-    while (e < n_sets && e - b < MT_SETS && q_first[e + 1] - q_first[b] <= MT_TQ) ++e;
+    while (e < n_sets && e - b < MT_SETS && q_first[e + 1] - q_first[b] <= TILE_TQ) ++e;
     most_sets = std::max(most_sets, e - b);
     tiles.push_back((int32_t)b);
     tiles.push_back((int32_t)e);
     b = e;
   }
   // the ranges: whole segments, closed as soon as they hold about 1 / KNN_RANGES of the rows
-  const int64_t target = std::max<int64_t>(MT_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + MT_TR - 1) / MT_TR * MT_TR);
+  const int64_t target = std::max<int64_t>(TILE_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + TILE_TR - 1) / TILE_TR * TILE_TR);
   std::vector<int32_t> ranges;
   for (int64_t g = 0; g < n_seg;) {
     const int64_t g0 = g, r0 = ix->seg_first[(size_t)g];

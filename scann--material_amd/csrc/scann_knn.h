@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "scann_tile.h"
+
 struct scann_handle;
 
 // A latent-space index (scann_knn.cpp; scann_head.cpp reads it as well)
@@ -29,13 +31,6 @@ namespace scann {
 // been written behind the index's rows and their device ids, the host side of the append (ids, atoms, segments, n)
 int index_new_chunk(scann_handle* h, scann_index* ix, hipStream_t s);
 void index_note_rows(scann_index* ix, int64_t n, const int64_t* ids, const int32_t* atoms);
-
-constexpr int KNN_TQ = 128;     // queries per workgroup
-constexpr int KNN_TR = 64;      // index rows per tile
-constexpr int KNN_SLAB = 32;    // columns per LDS slab
-constexpr int KNN_QS = KNN_TQ, KNN_RS = KNN_TR;  // floats per staged column of the query / row slab; column c lies (c / 4) * 4 floats further
-                                                 // (scann_knn.hip), so a slab takes 32 * stride + 32 floats
-constexpr int KNN_UNION = KNN_TR * KNN_TQ;               // floats the slabs and the distance tile share: max(32 * (128 + 64) + 64, 64 * 128)
 
 // One launch of knn_tile_kernel: `nq` queries against all `n_total` rows of an index, stored in chunks of `chunk_rows` rows.  Workgroup
 // (x, y, z) takes queries [128 y, 128 y + 128) and rows [x * rows_per_range, (x + 1) * rows_per_range) of chunk z and leaves the range's

@@ -2,14 +2,8 @@
 //   dist2(q, r) = acc_D,  acc_0 = 0,  acc_{j+1} = fmaf(q[j] - r[j], q[j] - r[j], acc_j)        (fp32, columns ascending)
 // and the k first rows under the total order (dist2 ascending, position ascending).
 //
-// Why VALU and not the matrix pipe: the product form |q|^2 + |r|^2 - 2 q.r loses exactly the neighbours that matter (near-duplicates) to
-// cancellation, and a pair's chain above has one fixed order, so its bits do not depend on the tiling.
-//
-// knn_tile_kernel (one launch over all storage chunks): a workgroup of 256 lanes takes 128 queries and a contiguous range of index rows.  Rows go through LDS 64 at a time in
-// slabs of 32 columns (the next slab is fetched into registers while this one is computed), stored column-major ([column][item]) so
-// that a lane reads its 8 queries and its 4 rows of one column with three conflict-free 16-byte LDS reads and owns an 8 x 4 register
-// block of independent chains, two rows of one query per packed fp32 instruction.  After
-// the last slab the 128 x 64 distances go to LDS (over the slabs), and lane q < 128 walks query q's 64 distances in position order
+// knn_tile_kernel (one launch over all storage chunks): the tile and the slab pipeline of scann_tile.h, 128 queries against a contiguous
+// range of index rows, 64 at a time.  After the last slab the 128 x 64 distances go to LDS, and lane q < 128 walks query q's 64 distances in position order
 // against its sorted list of the k best so far ([place][query] in LDS: no register array is indexed, nothing spills).  At the end of
 // the range the list is the range's partial result.  knn_merge_kernel: one wave per query pops the least head of the query's partial
 // lists k times.  No atomics; every comparison is of (dist2, position), so the result is the same for any split into ranges.
@@ -21,37 +15,35 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int KT = 256;  // lanes of knn_tile_kernel
+constexpr int KT = TILE_LANES;  // lanes of knn_tile_kernel
 
 __global__ __launch_bounds__(KT) void knn_tile_kernel(KnnArgs a) {
   extern __shared__ float4 knn_smem[];
   float* sm = reinterpret_cast<float*>(knn_smem);
-  float* qs = sm;                             // [32][KNN_QS] + 32  query slab, column-major
-  float* rs = sm + KNN_SLAB * KNN_QS + KNN_SLAB;  // [32][KNN_RS] + 32  row slab, column-major
+  float* qs = sm;                             // the query slab ...
+  float* rs = sm + tile_slab_floats(TILE_TQ);  // ... and the row slab (tile_stage)
   float* tile = sm;                           // [64][128]     distances of the tile, over the slabs
-  float* ld = sm + KNN_UNION;                 // [k][128]      per query: the k least distances so far, ascending ...
-  int32_t* lp = reinterpret_cast<int32_t*>(ld + a.k * KNN_TQ);                   // ... and their positions
-  long long* idt = reinterpret_cast<long long*>(lp + a.k * KNN_TQ);              // [64] ids of the tile's rows (qid only)
+  float* ld = sm + TILE_UNION;                 // [k][128]      per query: the k least distances so far, ascending ...
+  int32_t* lp = reinterpret_cast<int32_t*>(ld + a.k * TILE_TQ);                   // ... and their positions
+  long long* idt = reinterpret_cast<long long*>(lp + a.k * TILE_TQ);              // [64] ids of the tile's rows (qid only)
   const int t = threadIdx.x, qg = t & 15, rg = t >> 4;
-  const int q0 = blockIdx.y * KNN_TQ;
+  const int q0 = blockIdx.y * TILE_TQ;
   const int chunk = blockIdx.z, pos_base = chunk * a.chunk_rows;
   const int n_rows = min(a.chunk_rows, a.n_total - pos_base);  // rows of this chunk
   const float* __restrict__ rows = a.rows[chunk];
   const int r_begin = blockIdx.x * a.rows_per_range, r_end = min(n_rows, r_begin + a.rows_per_range);
   const int k = a.k, stride = a.stride;
-  const bool owner = t < KNN_TQ && q0 + t < a.nq;  // lane t keeps the list of query q0 + t
+  const bool owner = t < TILE_TQ && q0 + t < a.nq;  // lane t keeps the list of query q0 + t
   const bool has_qid = a.qid != nullptr;
   const long long my_id = owner && has_qid ? a.qid[q0 + t] : 0;
   int cnt = 0;
-  const int n_slab = (stride + KNN_SLAB - 1) / KNN_SLAB;
-  const int n_step = ((r_end - r_begin + KNN_TR - 1) / KNN_TR) * n_slab;  // (tile, slab) steps of this range
+  const int n_slab = (stride + TILE_SLAB - 1) / TILE_SLAB;
+  const int n_step = ((r_end - r_begin + TILE_TR - 1) / TILE_TR) * n_slab;  // (tile, slab) steps of this range
   // one step's slab in registers: 128 queries x 8 and 64 rows x 8 float4 (four columns of one item each); items / columns beyond the
   // end are zero.  Step s + 1 is fetched while step s is computed
   float4 gq[4], gr[2];
   auto fetch = [&](int step) {
-    const int tile0 = r_begin + (step / n_slab) * KNN_TR, c0 = (step % n_slab) * KNN_SLAB;
+    const int tile0 = r_begin + (step / n_slab) * TILE_TR, c0 = (step % n_slab) * TILE_SLAB;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = t + KT * i, item = e >> 3, col = c0 + 4 * (e & 7);
@@ -64,74 +56,37 @@ __global__ __launch_bounds__(KT) void knn_tile_kernel(KnnArgs a) {
     }
   };
   f2 acc[8][2];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
+  tile_clear(acc);
   if (n_step > 0) fetch(0);
   for (int step = 0; step < n_step; ++step) {
-    const int tile0 = r_begin + (step / n_slab) * KNN_TR;
+    const int tile0 = r_begin + (step / n_slab) * TILE_TR;
     __syncthreads();  // the previous slab's reads, or the previous tile's walk, are over
-    // column c of an item at [c * stride + (c / 4) * 4 + item]: the lanes of a wave hold 8 column groups of 8 items, and the shift per
-    // column group spreads their stores over the banks; the 16-byte reads below stay aligned
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + KT * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = qs + c * KNN_QS + c + item;
-      d[0] = gq[i].x; d[KNN_QS] = gq[i].y; d[2 * KNN_QS] = gq[i].z; d[3 * KNN_QS] = gq[i].w;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = t + KT * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = rs + c * KNN_RS + c + item;
-      d[0] = gr[i].x; d[KNN_RS] = gr[i].y; d[2 * KNN_RS] = gr[i].z; d[3 * KNN_RS] = gr[i].w;
-    }
+    tile_stage<KT, 4, TILE_TQ>(qs, gq, t);
+    tile_stage<KT, 2, TILE_TR>(rs, gr, t);
     __syncthreads();
     if (step + 1 < n_step) fetch(step + 1);
-#pragma unroll 4
-    for (int c = 0; c < KNN_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-      const int sh = c & ~3;
-      const float4 qa = *reinterpret_cast<const float4*>(qs + c * KNN_QS + sh + 4 * qg);       // queries 4 qg .. 4 qg + 3
-      const float4 qb = *reinterpret_cast<const float4*>(qs + c * KNN_QS + sh + 64 + 4 * qg);  // queries 64 + 4 qg .. 64 + 4 qg + 3
-      const float4 r4 = *reinterpret_cast<const float4*>(rs + c * KNN_RS + sh + 4 * rg);
-      const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f2 qq{qv[j], qv[j]};
-        const f2 d0 = qq - r01, d1 = qq - r23;  // rounded once; the explicit fma below keeps the square and the sum one operation
-        acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-        acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-      }
-    }
+    tile_slab<TileForm::DIFF>(qs, rs, qg, rg, acc, TILE_SLAB);
     if (step % n_slab != n_slab - 1) continue;
     // the tile's last slab: its 128 x 64 distances go to LDS and every query's list is brought up to date
     __syncthreads();  // every lane has read its last slab
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float* dst = tile + (4 * rg + i) * KNN_TQ + 4 * qg;
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
-      *reinterpret_cast<float4*>(dst) = float4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<float4*>(dst + 64) = float4{v[4], v[5], v[6], v[7]};
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
-    if (has_qid && t < KNN_TR) idt[t] = tile0 + t < r_end ? a.ids[chunk][tile0 + t] : 0;
+    tile_write<TILE_TQ>(tile, acc, qg, rg);
+    tile_clear(acc);
+    if (has_qid && t < TILE_TR) idt[t] = tile0 + t < r_end ? a.ids[chunk][tile0 + t] : 0;
     __syncthreads();
     if (owner) {
-      const int n = min(KNN_TR, r_end - tile0);
+      const int n = min(TILE_TR, r_end - tile0);
       for (int r = 0; r < n; ++r) {  // positions ascending: among equal distances the earlier row is already in the list
-        const float d = tile[r * KNN_TQ + t];
+        const float d = tile[r * TILE_TQ + t];
         if (!(d == d)) continue;  // a NaN distance never qualifies
         if (has_qid && idt[r] == my_id) continue;
-        if (cnt == k && !(d < ld[(k - 1) * KNN_TQ + t])) continue;
+        if (cnt == k && !(d < ld[(k - 1) * TILE_TQ + t])) continue;
         int j = cnt < k ? cnt : k - 1;
-        for (; j > 0 && ld[(j - 1) * KNN_TQ + t] > d; --j) {
-          ld[j * KNN_TQ + t] = ld[(j - 1) * KNN_TQ + t];
-          lp[j * KNN_TQ + t] = lp[(j - 1) * KNN_TQ + t];
+        for (; j > 0 && ld[(j - 1) * TILE_TQ + t] > d; --j) {
+          ld[j * TILE_TQ + t] = ld[(j - 1) * TILE_TQ + t];
+          lp[j * TILE_TQ + t] = lp[(j - 1) * TILE_TQ + t];
         }
-        ld[j * KNN_TQ + t] = d;
-        lp[j * KNN_TQ + t] = pos_base + tile0 + r;
+        ld[j * TILE_TQ + t] = d;
+        lp[j * TILE_TQ + t] = pos_base + tile0 + r;
         if (cnt < k) ++cnt;
       }
     }
@@ -139,8 +94,8 @@ __global__ __launch_bounds__(KT) void knn_tile_kernel(KnnArgs a) {
   if (owner) {
     const size_t o = ((size_t)(q0 + t) * a.n_range + (size_t)chunk * gridDim.x + blockIdx.x) * k;
     for (int j = 0; j < k; ++j) {
-      a.part_d[o + j] = j < cnt ? ld[j * KNN_TQ + t] : __builtin_inff();
-      a.part_p[o + j] = j < cnt ? lp[j * KNN_TQ + t] : -1;
+      a.part_d[o + j] = j < cnt ? ld[j * TILE_TQ + t] : __builtin_inff();
+      a.part_p[o + j] = j < cnt ? lp[j * TILE_TQ + t] : -1;
     }
   }
 }
@@ -188,7 +143,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
 
 }  // namespace
 
-size_t knn_lds_bytes(int k) { return (size_t)KNN_UNION * 4 + (size_t)k * KNN_TQ * 8 + KNN_TR * 8; }
+size_t knn_lds_bytes(int k) { return (size_t)TILE_UNION * 4 + (size_t)k * TILE_TQ * 8 + TILE_TR * 8; }
 
 hipError_t launch_knn_tile(const KnnArgs& a, hipStream_t s) {
   if (a.n_total <= 0 || a.nq <= 0) return hipSuccess;
@@ -197,7 +152,7 @@ hipError_t launch_knn_tile(const KnnArgs& a, hipStream_t s) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  const dim3 grid((unsigned)(a.n_range / a.n_chunk), (unsigned)((a.nq + KNN_TQ - 1) / KNN_TQ), (unsigned)a.n_chunk);
+  const dim3 grid((unsigned)(a.n_range / a.n_chunk), (unsigned)((a.nq + TILE_TQ - 1) / TILE_TQ), (unsigned)a.n_chunk);
   hipLaunchKernelGGL(knn_tile_kernel, grid, dim3(KT), lds, s, a);
   return hipGetLastError();
 }

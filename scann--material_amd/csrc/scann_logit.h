@@ -12,12 +12,12 @@ namespace scann {
 
 constexpr int LOGIT_CMAX = 16;     // SCANN_LOGIT_MAX_CLASSES
 constexpr int LOGIT_MMAX = 64;     // SCANN_LOGIT_MAX_MODELS
-constexpr int LOGIT_LANES = 256;   // lanes of logit_pass_kernel
-constexpr int LOGIT_BLOCK = 128;   // positions of a block: the innermost level of the summation tree of the definition
+constexpr int LOGIT_LANES = TILE_LANES; // lanes of logit_pass_kernel
+constexpr int LOGIT_BLOCK = TILE_TQ; // positions of a block: the innermost level of the summation tree of the definition
 constexpr int LOGIT_SPAN = 32;     // blocks of a span, the middle level: one workgroup
-constexpr int LOGIT_COLS = 64;     // logit columns (model x class) of one launch
+constexpr int LOGIT_COLS = TILE_TR; // logit columns (model x class) of one launch
 constexpr int LOGIT_GMAX = 32;     // models of one launch at most (64 columns / 2 classes)
-constexpr int LOGIT_SLAB = 32;     // components per LDS slab of the logit chains
+constexpr int LOGIT_SLAB = TILE_SLAB; // components per LDS slab of the logit chains
 constexpr int LOGIT_CHUNK = 64;    // components per LDS chunk of the gradient accumulation
 constexpr int LOGIT_LD = LOGIT_COLS + 4;  // floats per row of the logit / residual tile and of the component chunk in LDS
 #define SCANN_LOGIT_LOG2E 0x1.715476p+0f  // the fp32 rounding of log2(e): scann_rbf_weight(u, log2 e) = e^-u

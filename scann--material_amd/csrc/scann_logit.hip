@@ -3,8 +3,8 @@
 //
 // logit_pass_kernel: one workgroup of 256 lanes per span of 32 blocks of 128 positions, up to 64 logit columns (model x class) per launch.
 // Per block:
-//   A  the logit chains (fp32 fmaf, components ascending, from the intercept) with the tiling of rbf_feature_kernel: rows (minus the
-//      mean) and weights pass through LDS in slabs of 32 components, a lane owns 8 rows x 4 columns of independent chains;  whether a row
+//   A  the logit chains (fp32 fmaf, components ascending, from the intercept) on the tile and the slab pipeline of scann_tile.h, product
+//      form: rows (minus the mean) are the tile's "queries", the weights its "rows", a lane owns 8 rows x 4 columns;  whether a row
 //      has a non-finite component is found while it is staged.  The 128 x 64 logits go to an LDS tile.
 //   B  one lane per (row, model): logit_softmax (scann_logit.h), the residuals onehot - p written over the logits (0 where the row does
 //      not train the model), brier / hit / membership to LDS, the probabilities of the model that reports the row's fold to global.
@@ -24,13 +24,7 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int PS = LOGIT_BLOCK, LS = LOGIT_COLS;  // floats per staged component of the row / weight slab
 constexpr int TILE = LOGIT_BLOCK * LOGIT_LD;      // floats of the logit tile, and of the area behind it
-
-// 0 where all four are finite, NaN otherwise (x - x is 0 for a finite x only)
-__device__ __forceinline__ float logit_nonfinite(const float4& v) { return ((v.x - v.x) + (v.y - v.y)) + ((v.z - v.z) + (v.w - v.w)); }
 
 __global__ __launch_bounds__(LOGIT_LANES) void logit_pass_kernel(LogitArgs a) {
   __shared__ float4 logit_smem[2 * TILE / 4];
@@ -38,8 +32,8 @@ __global__ __launch_bounds__(LOGIT_LANES) void logit_pass_kernel(LogitArgs a) {
   __shared__ int n_count;
   float* tile = reinterpret_cast<float*>(logit_smem);  // [128][68] logits, then residuals
   float* area = tile + TILE;
-  float* ps = area;                                    // A: [32][128] + 32 row slab, component-major
-  float* ls = area + LOGIT_SLAB * PS + LOGIT_SLAB;     // A: [32][64] + 32  weight slab, component-major
+  float* ps = area;                                    // A: the row slab ...
+  float* ls = area + tile_slab_floats(LOGIT_BLOCK);    // A: ... and the weight slab (tile_stage)
   float* bri = area;                                   // B, D: [128][32] brier of (row, model)
   int* code = reinterpret_cast<int*>(area + LOGIT_BLOCK * LOGIT_GMAX);  // B, D: [128][32] 1 trains, 2 held out, 4 hit
   float* ych = area;                                   // C: [128][68] the chunk's components
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(LOGIT_LANES) void logit_pass_kernel(LogitArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float4 v = prow[i] && col < stride ? *reinterpret_cast<const float4*>(prow[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
-        nf[i] += logit_nonfinite(v);
+        nf[i] += row_nonfinite(v);
         gq[i] = float4{v.x - m4.x, v.y - m4.y, v.z - m4.z, v.w - m4.w};
       }
 #pragma unroll
@@ -99,36 +93,12 @@ __global__ __launch_bounds__(LOGIT_LANES) void logit_pass_kernel(LogitArgs a) {
     fetch(0);
     for (int slab = 0; slab < n_slab; ++slab) {
       __syncthreads();  // the previous slab's reads are over
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int e = t + LOGIT_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = ps + c * PS + c + item;
-        d[0] = gq[i].x; d[PS] = gq[i].y; d[2 * PS] = gq[i].z; d[3 * PS] = gq[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int e = t + LOGIT_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = ls + c * LS + c + item;
-        d[0] = gr[i].x; d[LS] = gr[i].y; d[2 * LS] = gr[i].z; d[3 * LS] = gr[i].w;
-      }
+      tile_stage<LOGIT_LANES, 4, LOGIT_BLOCK>(ps, gq, t);
+      tile_stage<LOGIT_LANES, 2, LOGIT_COLS>(ls, gr, t);
       __syncthreads();
       if (slab + 1 < n_slab) fetch(slab + 1);
       const int nc = min(LOGIT_SLAB, dim - slab * LOGIT_SLAB);  // the components that exist: a chain has no step for the padding
-#pragma unroll 4
-      for (int c = 0; c < nc; ++c) {  // components ascending: every chain in the order of the definition
-        const int sh = c & ~3;
-        const float4 qa = *reinterpret_cast<const float4*>(ps + c * PS + sh + 4 * qg);       // rows 4 qg .. 4 qg + 3
-        const float4 qb = *reinterpret_cast<const float4*>(ps + c * PS + sh + 64 + 4 * qg);  // rows 64 + 4 qg .. 64 + 4 qg + 3
-        const float4 r4 = *reinterpret_cast<const float4*>(ls + c * LS + sh + 4 * rg);       // columns 4 rg .. 4 rg + 3
-        const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-        const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const f2 qq{qv[j], qv[j]};
-          acc[j][0] = __builtin_elementwise_fma(qq, r01, acc[j][0]);
-          acc[j][1] = __builtin_elementwise_fma(qq, r23, acc[j][1]);
-        }
-      }
+      tile_slab<TileForm::PROD>(ps, ls, qg, rg, acc, nc);
     }
     __syncthreads();  // every lane has read its last slab
 #pragma unroll
@@ -136,7 +106,7 @@ __global__ __launch_bounds__(LOGIT_LANES) void logit_pass_kernel(LogitArgs a) {
       if (nf[i] != nf[i]) bad[(t + LOGIT_LANES * i) >> 3] = 1;  // (the eight lanes of an item may all write: the same value)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int row = (j < 4 ? 0 : 60) + 4 * qg + j;
+      const int row = tile_query(qg, j);
       *reinterpret_cast<float4*>(tile + row * LOGIT_LD + 4 * rg) = float4{acc[j][0].x, acc[j][0].y, acc[j][1].x, acc[j][1].y};
     }
     __syncthreads();

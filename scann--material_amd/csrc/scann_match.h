@@ -8,18 +8,17 @@
 
 namespace scann {
 
-constexpr int MT_TQ = KNN_TQ;      // query atoms per tile: a query structure lies in one tile, so this is SCANN_MATCH_MAX_ATOMS
-constexpr int MT_TR = KNN_TR;      // index rows per tile
+// (a tile holds TILE_TQ query atoms, scann_tile.h, and a query structure lies in one tile: that is SCANN_MATCH_MAX_ATOMS)
 constexpr int MT_SETS = 32;        // query structures per tile at most (bounds the per-structure LDS: g values and the k-best lists)
 constexpr int MT_SETS_SMALL = 16;  // ... and what the per-structure LDS is laid out for when no tile holds more: with k <= 8 the workgroup then
                                    // takes under 40 KiB and four of them share a CU's 160 KiB, as with knn_tile_kernel
-constexpr int MT_LD = MT_TQ + 4;   // floats between two rows of the distance tile: 16-byte stores stay aligned, and the lanes that read one
+constexpr int MT_LD = TILE_TQ + 4;  // floats between two rows of the distance tile: 16-byte stores stay aligned, and the lanes that read one
                                    // query's column down the rows (match_tile_kernel, the g pass) spread over 8 banks instead of 1
-constexpr int MT_UNION = MT_TR * MT_LD;  // floats the slabs and the distance tile share: max(32 * (128 + 64) + 64, 64 * 132)
+constexpr int MT_UNION = TILE_TR * MT_LD;  // floats the slabs and the distance tile share: max(32 * (128 + 64) + 64, 64 * 132)
 
 // One launch of match_tile_kernel.  Workgroup (x, y) takes range x of the index rows -- [row_begin, row_end) in positions, beginning and
 // ending on segment boundaries, its first segment's number seg_begin -- and tile y of the query structures: sets [set_begin, set_end),
-// whose atoms are the consecutive query rows q_first[set_begin] .. q_first[set_end] (at most MT_TQ of them, at most MT_SETS sets).  It
+// whose atoms are the consecutive query rows q_first[set_begin] .. q_first[set_end] (at most TILE_TQ of them, at most MT_SETS sets).  It
 // leaves, per set, the range's k best segments under (score, segment) in part_d / part_p [set - set_base][n_range][k]; unused places
 // hold (+inf, -1).
 struct MatchArgs {

@@ -4,10 +4,9 @@
 //   F = (fp64 sum of f_i, i ascending) / n,  G = (fp64 sum of g_j, j ascending) / m,  Fmax = max f_i,  Gmax = max g_j
 // and the score is (float)(F + G), max(Fmax, Gmax) or (float) F.  The k best segments are the first k under (score, segment number).
 //
-// match_tile_kernel: the arithmetic is knn_tile_kernel's -- 256 lanes, 128 query rows x 64 index rows per tile, 32-column slabs through
-// LDS with the next slab prefetched, an 8 x 4 register block of independent difference-form chains per lane (why VALU and why this form:
-// the top of scann_knn.hip).  A workgroup's query rows are whole structures (the host plans the tiles), its index rows a range that
-// begins and ends on segment boundaries (the host plans the ranges from the segment table), each row read from its own storage chunk.
+// match_tile_kernel: the tile and the slab pipeline of scann_tile.h, difference form.  A workgroup's query rows are whole structures
+// (the host plans the tiles), its index rows a range that begins and ends on segment boundaries (the host plans the ranges from the
+// segment table), each row read from its own storage chunk.
 // When a tile's 128 x 64 distances are complete they go to LDS and three short passes reduce them:
 //   g pass  lane (row r, wave w) takes the structures w, w + 4, ... and the min of D[.][r] over each one's atoms        -> gbuf[r][s]
 //   f pass  lane i < 128 walks its query atom's 64 distances in position order with the running f_i of the current segment (a
@@ -30,9 +29,7 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int MT = 256;    // lanes of match_tile_kernel
+constexpr int MT = TILE_LANES;  // lanes of match_tile_kernel
 constexpr int MP = 128;    // lanes of match_pair_kernel: one per query atom
 constexpr int MP_TR = 32;  // segment rows per step of match_pair_kernel
 constexpr int MP_LD = MP + 1;
@@ -44,12 +41,12 @@ __device__ __forceinline__ float match_score(int measure, double F, double G, fl
 __global__ __launch_bounds__(MT) void match_tile_kernel(MatchArgs a) {
   extern __shared__ float4 match_smem[];
   float* sm = reinterpret_cast<float*>(match_smem);
-  float* qs = sm;                                  // [32][KNN_QS] + 32  query slab, column-major (as knn_tile_kernel)
-  float* rs = sm + KNN_SLAB * KNN_QS + KNN_SLAB;   // [32][KNN_RS] + 32  row slab
+  float* qs = sm;                                  // the query slab ...
+  float* rs = sm + tile_slab_floats(TILE_TQ);      // ... and the row slab (tile_stage)
   float* tile = sm;                                // [64][MT_LD]  distances of the tile, over the slabs
   float* gbuf = sm + MT_UNION;                     // [64][SL + 1] g of (row, structure)
   const int SL = a.sets_ld, GLD = SL + 1;          // structures the per-structure arrays have room for (16 or 32: the host's choice)
-  float* ld = gbuf + MT_TR * GLD;                  // [k][SL]      per structure: the k least scores so far, ascending ...
+  float* ld = gbuf + TILE_TR * GLD;                  // [k][SL]      per structure: the k least scores so far, ascending ...
   int32_t* lp = reinterpret_cast<int32_t*>(ld + a.k * SL);          // ... and their segments
   int32_t* qoff = lp + a.k * SL;                   // [SL + 1] first atom of every structure of the tile, relative to the tile's first
   long long* idt = reinterpret_cast<long long*>(qoff + SL + 2);     // [65] ids of the tile's rows and of the one behind them
@@ -68,11 +65,11 @@ __global__ __launch_bounds__(MT) void match_tile_kernel(MatchArgs a) {
   double g_sum = 0.0;                             // s pass: the fp64 sum of g_j, j ascending, ...
   float g_max = -__builtin_inff();                // ... their max ...
   int m_run = 0;                                  // ... and the rows of the current segment so far
-  const int n_slab = (stride + KNN_SLAB - 1) / KNN_SLAB;
-  const int n_step = ((r_end - r_begin + MT_TR - 1) / MT_TR) * n_slab;
+  const int n_slab = (stride + TILE_SLAB - 1) / TILE_SLAB;
+  const int n_step = ((r_end - r_begin + TILE_TR - 1) / TILE_TR) * n_slab;
   float4 gq[4], gr[2];
   auto fetch = [&](int step) {
-    const int tile0 = r_begin + (step / n_slab) * MT_TR, c0 = (step % n_slab) * KNN_SLAB;
+    const int tile0 = r_begin + (step / n_slab) * TILE_TR, c0 = (step % n_slab) * TILE_SLAB;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = t + MT * i, item = e >> 3, col = c0 + 4 * (e & 7);
@@ -82,81 +79,39 @@ __global__ __launch_bounds__(MT) void match_tile_kernel(MatchArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int e = t + MT * i, pos = tile0 + (e >> 3), col = c0 + 4 * (e & 7);
       gr[i] = float4{0.f, 0.f, 0.f, 0.f};
-      if (pos < r_end && col < stride) {  // every row from its own chunk: a range may lie across a chunk boundary
-        const int chunk = pos / chunk_rows;
-        gr[i] = *reinterpret_cast<const float4*>(a.rows[chunk] + (size_t)(pos - chunk * chunk_rows) * stride + col);
-      }
+      // every row from its own chunk: a range may lie across a chunk boundary
+      if (pos < r_end && col < stride) gr[i] = *reinterpret_cast<const float4*>(tile_row(a.rows, pos, chunk_rows, stride) + col);
     }
   };
   f2 acc[8][2];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
+  tile_clear(acc);
   if (n_step > 0) fetch(0);
   for (int step = 0; step < n_step; ++step) {
-    const int tile0 = r_begin + (step / n_slab) * MT_TR;
+    const int tile0 = r_begin + (step / n_slab) * TILE_TR;
     __syncthreads();  // the previous slab's reads, or the previous tile's passes, are over
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + MT * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = qs + c * KNN_QS + c + item;
-      d[0] = gq[i].x; d[KNN_QS] = gq[i].y; d[2 * KNN_QS] = gq[i].z; d[3 * KNN_QS] = gq[i].w;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = t + MT * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = rs + c * KNN_RS + c + item;
-      d[0] = gr[i].x; d[KNN_RS] = gr[i].y; d[2 * KNN_RS] = gr[i].z; d[3 * KNN_RS] = gr[i].w;
-    }
+    tile_stage<MT, 4, TILE_TQ>(qs, gq, t);
+    tile_stage<MT, 2, TILE_TR>(rs, gr, t);
     __syncthreads();
     if (step + 1 < n_step) fetch(step + 1);
-#pragma unroll 4
-    for (int c = 0; c < KNN_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-      const int sh = c & ~3;
-      const float4 qa = *reinterpret_cast<const float4*>(qs + c * KNN_QS + sh + 4 * qg);
-      const float4 qb = *reinterpret_cast<const float4*>(qs + c * KNN_QS + sh + 64 + 4 * qg);
-      const float4 r4 = *reinterpret_cast<const float4*>(rs + c * KNN_RS + sh + 4 * rg);
-      const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f2 qq{qv[j], qv[j]};
-        const f2 d0 = qq - r01, d1 = qq - r23;
-        acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-        acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-      }
-    }
+    tile_slab<TileForm::DIFF>(qs, rs, qg, rg, acc, TILE_SLAB);
     if (step % n_slab != n_slab - 1) continue;
     // the tile's last slab: its 128 x 64 distances go to LDS
     __syncthreads();  // every lane has read its last slab
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float* dst = tile + (4 * rg + i) * MT_LD + 4 * qg;
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
-      *reinterpret_cast<float4*>(dst) = float4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<float4*>(dst + 64) = float4{v[4], v[5], v[6], v[7]};
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
-    const int n = min(MT_TR, r_end - tile0);
+    tile_write<MT_LD>(tile, acc, qg, rg);
+    tile_clear(acc);
+    const int n = min(TILE_TR, r_end - tile0);
     if (t <= n) {  // the ids of the tile's rows and of the row behind them: a row ends its segment if it is the range's last or the next id is another
       const int pos = tile0 + t;
-      long long id = 0;
-      if (pos < r_end) {
-        const int chunk = pos / chunk_rows;
-        id = a.ids[chunk][pos - chunk * chunk_rows];
-      }
-      idt[t] = id;
+      idt[t] = pos < r_end ? *tile_row(a.ids, pos, chunk_rows, 1) : 0;
     }
     __syncthreads();
     // bit r: row r ends its segment (the same 64 bits in every wave)
-    const int lane = t & (MT_TR - 1);
+    const int lane = t & (TILE_TR - 1);
     const unsigned long long ends = __ballot(lane < n && (tile0 + lane + 1 == r_end || idt[lane] != idt[lane + 1]));
     {  // g pass
       const int r = lane;
       if (r < n)
-        for (int s = t >> 6; s < n_set; s += MT / MT_TR) {
+        for (int s = t >> 6; s < n_set; s += MT / TILE_TR) {
           float g = __builtin_inff();
           for (int i = qoff[s]; i < qoff[s + 1]; ++i) {
             const float d = tile[r * MT_LD + i];
@@ -249,8 +204,8 @@ __global__ __launch_bounds__(MP) void match_pair_kernel(MatchPairArgs a) {
     const int nj = min(MP_TR, m - j0);
     if (active)
       for (int jj = 0; jj < nj; ++jj) {
-        const int pos = first + j0 + jj, chunk = pos / chunk_rows;
-        const float* __restrict__ row = a.rows[chunk] + (size_t)(pos - chunk * chunk_rows) * stride;
+        const int pos = first + j0 + jj;
+        const float* __restrict__ row = tile_row(a.rows, pos, chunk_rows, stride);
         float acc = 0.f;
         for (int c = 0; c < stride; c += 4) {  // the chain of the definition, columns ascending (the padding adds fmaf(0, 0, acc) = acc)
           const float4 x = *reinterpret_cast<const float4*>(qrow + c), y = *reinterpret_cast<const float4*>(row + c);
@@ -306,7 +261,7 @@ __global__ __launch_bounds__(MP) void match_pair_kernel(MatchPairArgs a) {
 }  // namespace
 
 size_t match_lds_bytes(int k, int sets_ld) {
-  return (size_t)MT_UNION * 4 + (size_t)MT_TR * (sets_ld + 1) * 4 + (size_t)k * sets_ld * 8 + (sets_ld + 2) * 4 + (MT_TR + 1) * 8;
+  return (size_t)MT_UNION * 4 + (size_t)TILE_TR * (sets_ld + 1) * 4 + (size_t)k * sets_ld * 8 + (sets_ld + 2) * 4 + (TILE_TR + 1) * 8;
 }
 
 hipError_t launch_match_tile(const MatchArgs& a, hipStream_t s) {

@@ -14,16 +14,11 @@
 #include "scann_knn.h"
 #include "scann_mst.h"
 #include "scann_runtime.h"
+#include "scann_twin.h"
 
 using namespace scann;
 
 namespace {
-
-bool finite_row(const float* x, int64_t d) {
-  for (int64_t j = 0; j < d; ++j)
-    if (!std::isfinite(x[j])) return false;
-  return true;
-}
 
 // ceil(log2(n)) for n >= 1
 int ceil_log2(int64_t n) {
@@ -45,38 +40,6 @@ void sort_edges(int64_t n_edges, const int32_t* ea, const int32_t* eb, const flo
   std::iota(order.begin(), order.end(), (int64_t)0);
   std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return mst_before(ew[x], ea[x], eb[x], ew[y], ea[y], eb[y]); });
   for (int64_t e = 0; e < n_edges; ++e) a[e] = ea[order[(size_t)e]], b[e] = eb[order[(size_t)e]], w[e] = ew[order[(size_t)e]];
-}
-
-typedef float v8 __attribute__((vector_size(32)));
-
-// The pool in blocks of eight rows, each block transposed to [dim][8], so that one vector holds column j of eight rows; the rows behind
-// the last repeat it (their results are never read)
-std::vector<float> transpose8(const float* rows, int64_t n, int64_t dim) {
-  std::vector<float> t((size_t)((n + 7) / 8 * 8 * dim));
-  for (int64_t r = 0; r < (n + 7) / 8 * 8; ++r) {
-    const float* src = rows + std::min(r, n - 1) * dim;
-    float* dst = t.data() + (r / 8) * 8 * dim + r % 8;
-    for (int64_t j = 0; j < dim; ++j) dst[8 * j] = src[j];
-  }
-  return t;
-}
-
-// dist2 of eight queries to the eight rows of a transposed block, the chain of scann_knn_distsq with the query first: 64 independent
-// chains, each with its columns ascending; out[u][l] = dist2(x[u], row l of the block)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wpsabi"
-__attribute__((always_inline)) inline void dist2_8x8(const float* const* x, const float* block, int64_t d, v8* out) {
-  v8 a[8];
-  for (int u = 0; u < 8; ++u) a[u] = v8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t j = 0; j < d; ++j) {
-    v8 r;
-    __builtin_memcpy(&r, block + 8 * j, sizeof(r));
-    for (int u = 0; u < 8; ++u) {
-      const v8 t = x[u][j] - r;
-      a[u] = __builtin_elementwise_fma(t, t, a[u]);
-    }
-  }
-  for (int u = 0; u < 8; ++u) out[u] = a[u];
 }
 
 // The twin's search.  A row keeps the first MST_KEEP rows of other components under (w, position), found by one exact pass over the pool.
@@ -150,20 +113,6 @@ __attribute__((always_inline)) inline void twin_groups(const Twin& c, int64_t fi
 // per chain; fmaf is correctly rounded either way, so the bits are the same
 void search_plain(const Twin& c, int64_t first, int64_t step) { twin_groups(c, first, step); }
 __attribute__((target("avx2,fma"))) void search_fma(const Twin& c, int64_t first, int64_t step) { twin_groups(c, first, step); }
-#pragma clang diagnostic pop
-
-// thread k takes the groups of eight rows k, k + nt, ...; every row's list is its own
-void threaded(void (*fn)(const Twin&, int64_t, int64_t), const Twin& c) {
-  if (c.n_todo <= 0) return;
-  const double work = (double)c.n_todo * (double)c.n * (double)c.dim;
-  const int64_t nt = work < 4e6 ? 1 : std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(), (c.n_todo + 7) / 8}));
-  if (nt == 1) return fn(c, 0, 1);
-  std::vector<std::thread> pool;
-  for (int64_t k = 0; k < nt; ++k) pool.emplace_back(fn, std::cref(c), k, nt);
-  for (auto& th : pool) th.join();
-}
-
-bool host_fast() { return __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma"); }
 
 // the record of the calling thread's last scann_index_mst, for scann_mst_last_rounds
 struct RoundLog {
@@ -212,7 +161,7 @@ int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2
       if (hd == cnt[(size_t)i] && cnt[(size_t)i] == MST_KEEP) todo.push_back((int32_t)i);
     }
     c.todo = todo.data(), c.n_todo = (int64_t)todo.size();
-    threaded(host_fast() ? search_fma : search_plain, c);
+    twin_run(host_fast() ? search_fma : search_plain, c, c.n_todo);
     // every component's first edge under (w, min, max); labels are positions of rows
     std::fill(blo.begin(), blo.end(), -1);
     for (int64_t i = 0; i < n; ++i) {
@@ -316,7 +265,7 @@ int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2, 
   const int max_rounds = ceil_log2(std::max<int64_t>(n_comp, 1)) + 1;
   int n_round = 0;
   const char* internal = nullptr;
-  g_log.tiles = (int64_t)((N + PK_TQ - 1) / PK_TQ) * ((N + PK_TR - 1) / PK_TR);
+  g_log.tiles = (int64_t)((N + TILE_TQ - 1) / TILE_TQ) * ((N + TILE_TR - 1) / TILE_TR);
   while (e == hipSuccess && e_sync == hipSuccess && n_comp > 1) {  // at most max_rounds passes: every exit below is reached without a wait in a kernel
     if (n_round >= max_rounds) {
       internal = "more rounds than ceil(log2 n) + 1 would be needed";

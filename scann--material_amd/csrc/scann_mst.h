@@ -35,7 +35,7 @@ __host__ __device__ inline bool mst_before(float w1, int32_t lo1, int32_t hi1, f
 __host__ __device__ inline bool mst_row_before(float w, int32_t r, float bw, int32_t br) { return w < bw || (w == bw && r < br); }
 
 // One round's search: for every row the first row of another component under (w, position).  The tiling is that of peaks_tile_kernel
-// (PK_* of scann_peaks.h): workgroup (x, y) takes queries [128 x, 128 x + 128) and positions [y * rows_per_range, (y + 1) * rows_per_range).
+// (the tile of scann_tile.h): workgroup (x, y) takes queries [128 x, 128 x + 128) and positions [y * rows_per_range, (y + 1) * rows_per_range).
 struct MstArgs {
   const float* const* rows;  // [n_chunk] -> [chunk_rows][stride], columns dim .. stride-1 zero
   int32_t n_total, chunk_rows, stride;

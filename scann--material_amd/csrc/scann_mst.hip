@@ -3,8 +3,8 @@
 // dist2 the difference-form chain of scann_knn_distsq.  The order is total, so the tree is unique (scann_mst.h has the argument and the
 // per-row rule the walk rests on).  A round is
 //   mst_tile_kernel   for every row the first row of ANOTHER component under (w, position): the tiling and the arithmetic of
-//                     peaks_tile_kernel<true> (256 lanes, 128 queries x 64 pool rows, 32-column slabs through LDS, an 8 x 4 block of
-//                     chains per lane, ranges cut by position, each row read from its own storage chunk), with the 64 rows' labels and
+//                     peaks_tile_kernel<true> (the tile and the slab pipeline of scann_tile.h, 128 queries x 64 pool rows, ranges cut
+//                     by position, each row read from its own storage chunk), with the 64 rows' labels and
 //                     core distances beside the distance tile in LDS.  One (w, position) per query and range; knn_merge_kernel (k = 1)
 //                     takes the first over the ranges.  A tile whose 64 rows carry the one label that all 128 queries of the workgroup
 //                     carry holds no qualifying pair: every wave finds that with one compare per lane and a ballot (all waves read the
@@ -25,18 +25,16 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 __global__ __launch_bounds__(PK_LANES) void mst_tile_kernel(MstArgs a) {
-  __shared__ float4 mst_smem[PK_UNION / 4];
-  __shared__ int32_t s_comp[PK_TR];                  // the tile rows' labels ...
-  __shared__ float s_core[PK_TR];                    // ... and core distances
+  __shared__ float4 mst_smem[TILE_UNION / 4];
+  __shared__ int32_t s_comp[TILE_TR];                  // the tile rows' labels ...
+  __shared__ float s_core[TILE_TR];                    // ... and core distances
   float* sm = reinterpret_cast<float*>(mst_smem);
-  float* qs = sm;                                    // [32][PK_QS] + 32  query slab, column-major
-  float* rs = sm + PK_SLAB * PK_QS + PK_SLAB;        // [32][PK_RS] + 32  row slab, column-major
+  float* qs = sm;                                    // the query slab ...
+  float* rs = sm + tile_slab_floats(TILE_TQ);        // ... and the row slab (tile_stage)
   float* tile = sm;                                  // [64][128] distances of the tile, over the slabs
   const int t = threadIdx.x, qg = t & 15, rg = t >> 4;
-  const int q0 = blockIdx.x * PK_TQ, nq = a.n_total;
+  const int q0 = blockIdx.x * TILE_TQ, nq = a.n_total;
   const int stride = a.stride, chunk_rows = a.chunk_rows;
   const long long r_lo = (long long)blockIdx.y * a.rows_per_range, r_hi = r_lo + a.rows_per_range;
   const int r_begin = (int)(r_lo < a.n_total ? r_lo : a.n_total), r_end = (int)(r_hi < a.n_total ? r_hi : a.n_total);
@@ -45,20 +43,16 @@ __global__ __launch_bounds__(PK_LANES) void mst_tile_kernel(MstArgs a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int qi = q0 + ((t + PK_LANES * i) >> 3);
-    qp[i] = nullptr;
-    if (qi < nq) {
-      const int c = qi / chunk_rows;
-      qp[i] = a.rows[c] + (size_t)(qi - c * chunk_rows) * stride;
-    }
+    qp[i] = qi < nq ? tile_row(a.rows, qi, chunk_rows, stride) : nullptr;
   }
-  const bool owner = t < PK_TQ && q0 + t < nq;  // lane t finishes query q0 + t
+  const bool owner = t < TILE_TQ && q0 + t < nq;  // lane t finishes query q0 + t
   const int my_c = owner ? a.comp[q0 + t] : -1;  // negative: not eligible, nothing qualifies
   const float my_core = owner ? a.core2[q0 + t] : 0.f;
   float bw = 0.f;  // the first row of another component so far
   int bp = -1;
   // the skip rule: do all queries of the workgroup carry one label?  (q0 < nq: the grid covers the queries)
   const int q_label = a.comp[q0];
-  const bool q_one = __syncthreads_and(t >= PK_TQ || q0 + t >= nq || a.comp[q0 + t] == q_label) != 0;
+  const bool q_one = __syncthreads_and(t >= TILE_TQ || q0 + t >= nq || a.comp[q0 + t] == q_label) != 0;
   unsigned int n_skipped = 0;
   // the first tile at or behind `from` with work in it (beyond the range: none): every wave looks at the same 64 labels
   auto seek = [&](int from) {
@@ -68,12 +62,12 @@ __global__ __launch_bounds__(PK_LANES) void mst_tile_kernel(MstArgs a) {
       const int pos = tl + (t & 63);
       const bool same = pos >= r_end || a.comp[pos] == q_label;
       if (__ballot(same) != ~0ull) break;
-      tl += PK_TR;
+      tl += TILE_TR;
       ++n_skipped;
     }
     return tl;
   };
-  const int n_slab = (stride + PK_SLAB - 1) / PK_SLAB;
+  const int n_slab = (stride + TILE_SLAB - 1) / TILE_SLAB;
   float4 gq[4], gr[2];
   const float* rp[2] = {nullptr, nullptr};
   int f_slab = 0, f_tile0 = seek(r_begin);  // the step the next fetch belongs to
@@ -84,84 +78,45 @@ __global__ __launch_bounds__(PK_LANES) void mst_tile_kernel(MstArgs a) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int pos = f_tile0 + ((t + PK_LANES * i) >> 3);
-        rp[i] = nullptr;
-        if (pos < r_end) {
-          const int c = pos / chunk_rows;
-          rp[i] = a.rows[c] + (size_t)(pos - c * chunk_rows) * stride;
-        }
+        rp[i] = pos < r_end ? tile_row(a.rows, pos, chunk_rows, stride) : nullptr;
       }
     }
-    const int col = f_slab * PK_SLAB + 4 * (t & 7);
+    const int col = f_slab * TILE_SLAB + 4 * (t & 7);
 #pragma unroll
     for (int i = 0; i < 4; ++i) gq[i] = qp[i] && col < stride ? *reinterpret_cast<const float4*>(qp[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 2; ++i) gr[i] = rp[i] && col < stride ? *reinterpret_cast<const float4*>(rp[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
-    if (++f_slab == n_slab) f_slab = 0, f_tile0 = seek(f_tile0 + PK_TR);
+    if (++f_slab == n_slab) f_slab = 0, f_tile0 = seek(f_tile0 + TILE_TR);
   };
   f2 acc[8][2];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
+  tile_clear(acc);
   int c_slab = 0, tile0 = f_tile0;  // the step being computed
   if (f_tile0 < r_end) fetch();
   while (tile0 < r_end) {
     __syncthreads();  // the previous slab's reads, or the previous tile's walk, are over
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + PK_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = qs + c * PK_QS + c + item;
-      d[0] = gq[i].x; d[PK_QS] = gq[i].y; d[2 * PK_QS] = gq[i].z; d[3 * PK_QS] = gq[i].w;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = t + PK_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = rs + c * PK_RS + c + item;
-      d[0] = gr[i].x; d[PK_RS] = gr[i].y; d[2 * PK_RS] = gr[i].z; d[3 * PK_RS] = gr[i].w;
-    }
+    tile_stage<PK_LANES, 4, TILE_TQ>(qs, gq, t);
+    tile_stage<PK_LANES, 2, TILE_TR>(rs, gr, t);
     __syncthreads();
     if (f_tile0 < r_end) fetch();
-#pragma unroll 4
-    for (int c = 0; c < PK_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-      const int sh = c & ~3;
-      const float4 qa = *reinterpret_cast<const float4*>(qs + c * PK_QS + sh + 4 * qg);       // queries 4 qg .. 4 qg + 3
-      const float4 qb = *reinterpret_cast<const float4*>(qs + c * PK_QS + sh + 64 + 4 * qg);  // queries 64 + 4 qg .. 64 + 4 qg + 3
-      const float4 r4 = *reinterpret_cast<const float4*>(rs + c * PK_RS + sh + 4 * rg);       // rows 4 rg .. 4 rg + 3
-      const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f2 qq{qv[j], qv[j]};
-        const f2 d0 = qq - r01, d1 = qq - r23;  // rounded once; the explicit fma keeps the square and the sum one operation
-        acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-        acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-      }
-    }
+    tile_slab<TileForm::DIFF>(qs, rs, qg, rg, acc, TILE_SLAB);
     if (++c_slab != n_slab) continue;
     c_slab = 0;
     // the tile's last slab
     __syncthreads();  // every lane has read its last slab
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float* dst = tile + (4 * rg + i) * PK_TQ + 4 * qg;
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
-      *reinterpret_cast<float4*>(dst) = float4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<float4*>(dst + 64) = float4{v[4], v[5], v[6], v[7]};
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
-    if (t < PK_TR) {
+    tile_write<TILE_TQ>(tile, acc, qg, rg);
+    tile_clear(acc);
+    if (t < TILE_TR) {
       const bool in = tile0 + t < r_end;
       s_comp[t] = in ? a.comp[tile0 + t] : -1;
       s_core[t] = in ? a.core2[tile0 + t] : 0.f;
     }
     __syncthreads();
     if (owner && my_c >= 0) {
-      const int n = min(PK_TR, r_end - tile0);
+      const int n = min(TILE_TR, r_end - tile0);
       for (int r = 0; r < n; ++r) {  // positions ascending: among equal weights the earlier row stays (the per-row rule)
         const int c = s_comp[r];
         if (c < 0 || c == my_c) continue;
-        const float w = mst_weight(tile[r * PK_TQ + t], my_core, s_core[r]);
+        const float w = mst_weight(tile[r * TILE_TQ + t], my_core, s_core[r]);
         if (bp < 0 || mst_row_before(w, tile0 + r, bw, bp)) bw = w, bp = tile0 + r;
       }
     }
@@ -180,14 +135,7 @@ __global__ __launch_bounds__(PK_LANES) void mst_eligible_kernel(MstArgs a, int32
   const int qi = blockIdx.x * PK_LANES + threadIdx.x;
   bool ok = false;
   if (qi < a.n_total) {
-    const int c = qi / a.chunk_rows;
-    const float* row = a.rows[c] + (size_t)(qi - c * a.chunk_rows) * a.stride;
-    float nf = 0.f;  // NaN once a component was not finite (x - x is 0 for a finite x only; the padding columns are zero)
-    for (int j = 0; j < a.stride; j += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(row + j);
-      nf += ((v.x - v.x) + (v.y - v.y)) + ((v.z - v.z) + (v.w - v.w));
-    }
-    ok = nf == nf;
+    ok = !row_nonfinite(tile_row(a.rows, qi, a.chunk_rows, a.stride), a.stride);
     comp[qi] = ok ? qi : -1;
   }
   const unsigned long long m = __ballot(ok);
@@ -278,7 +226,7 @@ hipError_t launch_mst_eligible(const MstArgs& a, int32_t* comp, int32_t* counter
 
 hipError_t launch_mst_tile(const MstArgs& a, hipStream_t s) {
   if (a.n_total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mst_tile_kernel, dim3((unsigned)((a.n_total + PK_TQ - 1) / PK_TQ), (unsigned)a.n_range), dim3(PK_LANES), 0, s, a);
+  hipLaunchKernelGGL(mst_tile_kernel, dim3((unsigned)((a.n_total + TILE_TQ - 1) / TILE_TQ), (unsigned)a.n_range), dim3(PK_LANES), 0, s, a);
   return hipGetLastError();
 }
 

@@ -4,15 +4,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scann_tile.h"
+
 namespace scann {
 
-constexpr int PCA_LANES = 256;       // lanes of every workgroup
+constexpr int PCA_LANES = TILE_LANES;    // lanes of every workgroup
 constexpr int PCA_BLK = 64;          // columns of a block of pca_scatter_kernel: a workgroup owns one 64 x 64 block of T, a lane 4 x 4 of it
 constexpr int PCA_ROWS = 32;         // rows per LDS slab of that kernel
 constexpr int PCA_GROUPS = 1024;     // about as many workgroups in the sum, maximum and scatter passes
-constexpr int PCA_TP = 128;          // rows of a tile of pca_project_kernel
-constexpr int PCA_TC = 64;           // components per block of that kernel: a lane owns 8 rows x 4 components
-constexpr int PCA_SLAB = 32;         // columns per LDS slab of that kernel
+constexpr int PCA_TP = TILE_TQ;      // rows of a tile of pca_project_kernel
+constexpr int PCA_TC = TILE_TR;      // components per block of that kernel: a lane owns 8 rows x 4 components
+constexpr int PCA_SLAB = TILE_SLAB;    // columns per LDS slab of that kernel
 constexpr int PCA_MAX_GROUPS = 768;  // workgroups of a projection at most: the tiles are dealt evenly
 
 // What the passes of the moments hand to each other, in device memory (zeroed before the first launch)

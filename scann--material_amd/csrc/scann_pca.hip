@@ -20,9 +20,9 @@
 //                          meanwhile; a lane owns a 4 x 4 block of int64 accumulators in registers and adds it to T once, at the end,
 //                          with 64-bit integer atomics.  R_j comes from the diagonal blocks (16 lanes of the first wave).
 //   pca_finalise_kernel    the covariance, one lane per (i, j), i <= j, mirrored; f_j.
-// The projection is kmeans_assign_kernel's 8 x 4 register block of independent chains with the multiply-add changed: a workgroup takes
-// tiles of 128 rows and walks the components 64 at a time through LDS slabs of 32 columns; the centred value is formed once, where the
-// row is fetched.  A chain is never split over lanes.  dist2 (the chain of scann_knn.hip against the mean) rides along in the first
+// The projection runs on the tile and the slab pipeline of scann_tile.h in the product form: a workgroup takes tiles of 128 rows (the
+// tile's "queries") and walks the components 64 at a time (its "rows"); the centred value is formed once, where the row is
+// fetched.  dist2 (the difference-form chain against the mean) rides along in the first
 // component block, in the 16 lanes that own component group 0; pca_md2_kernel is a small pass over the coordinates, one lane per row.
 // No float atomics, no scratch.
 #include "scann_pca.h"
@@ -32,11 +32,6 @@
 namespace scann {
 
 namespace {
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int PCA_PS = PCA_TP, PCA_CS = PCA_TC;  // floats per staged column of the row / component slab; column c lies (c / 4) * 4 floats further
-constexpr int PCA_SLABS = PCA_SLAB * (PCA_PS + PCA_CS) + 2 * PCA_SLAB;  // floats of the two slabs
 
 __device__ __forceinline__ bool pca_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
@@ -297,10 +292,10 @@ __global__ __launch_bounds__(PCA_LANES) void pca_finalise_kernel(PcaArgs a) {
 }
 
 __global__ __launch_bounds__(PCA_LANES) void pca_project_kernel(PcaProjArgs a, int n_tile) {
-  __shared__ float4 pca_smem[PCA_SLABS / 4];
+  __shared__ float4 pca_smem[TILE_SLABS / 4];
   float* sm = reinterpret_cast<float*>(pca_smem);
-  float* ps = sm;                                // [32][PCA_PS] + 32  slab of centred rows, column-major
-  float* cs = sm + PCA_SLAB * PCA_PS + PCA_SLAB;  // [32][PCA_CS] + 32  component slab, column-major
+  float* ps = sm;                             // the slab of centred rows ...
+  float* cs = sm + tile_slab_floats(PCA_TP);  // ... and the component slab (tile_stage)
   const int t = threadIdx.x, pg = t & 15, cg = t >> 4;
   const int m = a.m, stride = a.stride;
   const int n_slab = (stride + PCA_SLAB - 1) / PCA_SLAB;
@@ -353,43 +348,16 @@ __global__ __launch_bounds__(PCA_LANES) void pca_project_kernel(PcaProjArgs a, i
     fetch(0);
     for (int step = 0; step < n_step; ++step) {
       __syncthreads();  // the previous slab's reads are over
-      // column c of an item at [c * stride + (c / 4) * 4 + item] (kmeans_assign_kernel's layout)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int e = t + PCA_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = ps + c * PCA_PS + c + item;
-        d[0] = gp[i].x; d[PCA_PS] = gp[i].y; d[2 * PCA_PS] = gp[i].z; d[3 * PCA_PS] = gp[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int e = t + PCA_LANES * i, item = e >> 3, c = 4 * (e & 7);
-        float* d = cs + c * PCA_CS + c + item;
-        d[0] = gc[i].x; d[PCA_CS] = gc[i].y; d[2 * PCA_CS] = gc[i].z; d[3 * PCA_CS] = gc[i].w;
-      }
+      tile_stage<PCA_LANES, 4, PCA_TP>(ps, gp, t);
+      tile_stage<PCA_LANES, 2, PCA_TC>(cs, gc, t);
       __syncthreads();
       if (step + 1 < n_step) fetch(step + 1);
-#pragma unroll 4
-      for (int c = 0; c < PCA_SLAB; ++c) {  // columns ascending: every chain in the order of the definition
-        const int sh = c & ~3;
-        const float4 pa = *reinterpret_cast<const float4*>(ps + c * PCA_PS + sh + 4 * pg);       // rows 4 pg .. 4 pg + 3
-        const float4 pb = *reinterpret_cast<const float4*>(ps + c * PCA_PS + sh + 64 + 4 * pg);  // rows 64 + 4 pg .. 64 + 4 pg + 3
-        const float4 c4 = *reinterpret_cast<const float4*>(cs + c * PCA_CS + sh + 4 * cg);       // components 4 cg .. 4 cg + 3 of the block
-        const f2 c01{c4.x, c4.y}, c23{c4.z, c4.w};
-        const float pv[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const f2 pp{pv[j], pv[j]};
-          acc[j][0] = __builtin_elementwise_fma(pp, c01, acc[j][0]);
-          acc[j][1] = __builtin_elementwise_fma(pp, c23, acc[j][1]);
-        }
-      }
-      if (want_d2 && step < n_slab) {  // the first component block: the distance to the mean, scann_knn.hip's chain
+      tile_slab<TileForm::PROD>(ps, cs, pg, cg, acc, PCA_SLAB);
+      if (want_d2 && step < n_slab) {  // the first component block: the distance to the mean, the difference-form chain (the rows are centred)
 #pragma unroll 4
         for (int c = 0; c < PCA_SLAB; ++c) {
-          const int sh = c & ~3;
-          const float4 pa = *reinterpret_cast<const float4*>(ps + c * PCA_PS + sh + 4 * pg);
-          const float4 pb = *reinterpret_cast<const float4*>(ps + c * PCA_PS + sh + 64 + 4 * pg);
-          const float pv[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
+          float pv[8];
+          tile_queries(ps, c, pg, pv);
 #pragma unroll
           for (int j = 0; j < 8; ++j) dacc[j] = __builtin_fmaf(pv[j], pv[j], dacc[j]);
         }
@@ -399,12 +367,12 @@ __global__ __launch_bounds__(PCA_LANES) void pca_project_kernel(PcaProjArgs a, i
       const int c0 = (step / n_slab) * PCA_TC + 4 * cg;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int row = (j < 4 ? 0 : 64 - 4) + 4 * pg + j;
+        const int row = tile_query(pg, j);
         if (row < nrow) {
           float* out = a.coords + (size_t)(r0 + row) * m;
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            if (c0 + i < m) out[c0 + i] = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
+            if (c0 + i < m) out[c0 + i] = tile_at(acc, j, i);
           if (want_d2 && step < n_slab) a.dist2[r0 + row] = dacc[j];
         }
         acc[j][0] = acc[j][1] = f2{0.f, 0.f};

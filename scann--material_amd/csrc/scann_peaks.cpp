@@ -11,48 +11,11 @@
 #include "scann_knn.h"
 #include "scann_peaks.h"
 #include "scann_runtime.h"
+#include "scann_twin.h"
 
 using namespace scann;
 
 namespace {
-
-bool finite_row(const float* x, int64_t d) {
-  for (int64_t j = 0; j < d; ++j)
-    if (!std::isfinite(x[j])) return false;
-  return true;
-}
-
-typedef float v8 __attribute__((vector_size(32)));
-
-// The pool in blocks of eight rows, each block transposed to [dim][8], so that one vector holds column j of eight rows; the rows behind
-// the last repeat it (their results are never read)
-std::vector<float> transpose8(const float* rows, int64_t n, int64_t dim) {
-  std::vector<float> t((size_t)((n + 7) / 8 * 8 * dim));
-  for (int64_t r = 0; r < (n + 7) / 8 * 8; ++r) {
-    const float* src = rows + std::min(r, n - 1) * dim;
-    float* dst = t.data() + (r / 8) * 8 * dim + r % 8;
-    for (int64_t j = 0; j < dim; ++j) dst[8 * j] = src[j];
-  }
-  return t;
-}
-
-// dist2 of eight queries to the eight rows of a transposed block, the chain of scann_knn_distsq with the query first: 64 independent
-// chains, each with its columns ascending; out[u][l] = dist2(x[u], row l of the block)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wpsabi"
-__attribute__((always_inline)) inline void dist2_8x8(const float* const* x, const float* block, int64_t d, v8* out) {
-  v8 a[8];
-  for (int u = 0; u < 8; ++u) a[u] = v8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t j = 0; j < d; ++j) {
-    v8 r;
-    __builtin_memcpy(&r, block + 8 * j, sizeof(r));
-    for (int u = 0; u < 8; ++u) {
-      const v8 t = x[u][j] - r;
-      a[u] = __builtin_elementwise_fma(t, t, a[u]);
-    }
-  }
-  for (int u = 0; u < 8; ++u) out[u] = a[u];
-}
 
 struct Twin {
   const float* rows;   // [n][dim] the pool ...
@@ -112,20 +75,6 @@ void density_plain(const Twin& c, int64_t first, int64_t step) { twin_groups<0>(
 __attribute__((target("avx2,fma"))) void density_fma(const Twin& c, int64_t first, int64_t step) { twin_groups<0>(c, first, step); }
 void parent_plain(const Twin& c, int64_t first, int64_t step) { twin_groups<1>(c, first, step); }
 __attribute__((target("avx2,fma"))) void parent_fma(const Twin& c, int64_t first, int64_t step) { twin_groups<1>(c, first, step); }
-#pragma clang diagnostic pop
-
-// a pass over `items` queries: thread k takes the groups of eight queries k, k + nt, ...; every query's result is its own
-void threaded(void (*fn)(const Twin&, int64_t, int64_t), const Twin& c, int64_t items) {
-  if (items <= 0) return;
-  const double work = (double)items * (double)c.n * (double)c.dim;
-  const int64_t nt = work < 4e6 ? 1 : std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(), (items + 7) / 8}));
-  if (nt == 1) return fn(c, 0, 1);
-  std::vector<std::thread> pool;
-  for (int64_t k = 0; k < nt; ++k) pool.emplace_back(fn, std::cref(c), k, nt);
-  for (auto& th : pool) th.join();
-}
-
-bool host_fast() { return __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma"); }
 
 bool bad_gamma(float gamma) { return !std::isfinite(gamma) || !(gamma > 0.f); }
 
@@ -191,7 +140,7 @@ int scann_density_host(const float* rows, int64_t n, int64_t dim, const float* q
   }
   const std::vector<float> rows8 = transpose8(rows, n, dim);
   Twin c{rows, rows8.data(), n, dim, q, nq, skip_pos, false, gamma, sums, nullptr, nullptr};
-  threaded(host_fast() ? density_fma : density_plain, c, nq);
+  twin_run(host_fast() ? density_fma : density_plain, c, nq);
   return SCANN_OK;
 }
 
@@ -200,8 +149,8 @@ int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int
   if (n == 0) return SCANN_OK;
   const std::vector<float> rows8 = transpose8(rows, n, dim);
   Twin c{rows, rows8.data(), n, dim, rows, n, nullptr, true, gamma, sums, parent, delta2};
-  threaded(host_fast() ? density_fma : density_plain, c, n);
-  threaded(host_fast() ? parent_fma : parent_plain, c, n);
+  twin_run(host_fast() ? density_fma : density_plain, c, n);
+  twin_run(host_fast() ? parent_fma : parent_plain, c, n);
   return SCANN_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "scann_rbf.h"
+#include "scann_tile.h"
 
 namespace scann {
 
@@ -20,14 +21,8 @@ __host__ __device__ inline int32_t peaks_term(float dist2, float gamma) {
 // row j with the sum sj is above row i with the sum si (the density order)
 __host__ __device__ inline bool peaks_above(long long sj, int32_t j, long long si, int32_t i) { return sj > si || (sj == si && j < i); }
 
-constexpr int PK_LANES = 256;  // lanes of the two tile kernels
-constexpr int PK_TQ = 128;     // queries per workgroup
-constexpr int PK_TR = 64;      // pool rows per tile
-constexpr int PK_SLAB = 32;    // columns per LDS slab
-constexpr int PK_QS = PK_TQ, PK_RS = PK_TR;  // floats per staged column of the query / row slab; column c lies (c / 4) * 4 floats further
-constexpr int PK_SLABS = PK_SLAB * (PK_QS + PK_RS) + 2 * PK_SLAB;  // floats of the two slabs
-constexpr int PK_UNION = PK_TR * PK_TQ;  // floats the slabs share with the distance tile (parent) or the per-lane sums (density)
-constexpr int PK_BLOCKS = 4096;          // about as many workgroups per launch as this
+constexpr int PK_LANES = TILE_LANES;  // lanes of every kernel of the density, spanning-tree and silhouette passes (the tile: scann_tile.h)
+constexpr int PK_BLOCKS = 4096;       // about as many workgroups per launch as this
 
 // One launch of a tile kernel: nq queries against positions 0 .. n_total - 1 of a pool stored in chunks of `chunk_rows` rows.  Workgroup
 // (x, y) takes queries [128 x, 128 x + 128) and positions [y * rows_per_range, (y + 1) * rows_per_range): ranges are cut by position, so

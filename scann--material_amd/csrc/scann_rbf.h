@@ -6,6 +6,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "scann_tile.h"
+
 namespace scann {
 
 // c_j = the fp32 rounding of 2^(-1/2) (-ln 2)^j / j!, j = 0 .. 7: 2^(-1/2 - g) on g in [-1/2, 1/2)
@@ -38,10 +40,10 @@ __host__ __device__ inline float rbf_weight(float dist2, float gamma) {
   return ldexpf(p, i < -256.f ? 256 : -(int)i);
 }
 
-constexpr int RBF_LANES = 256;  // lanes of rbf_feature_kernel
-constexpr int RBF_TP = 128;     // pool rows per tile
-constexpr int RBF_TL = 64;      // landmarks per tile
-constexpr int RBF_SLAB = 32;    // columns per LDS slab
+constexpr int RBF_LANES = TILE_LANES;  // lanes of rbf_feature_kernel
+constexpr int RBF_TP = TILE_TQ;  // pool rows per tile
+constexpr int RBF_TL = TILE_TR;  // landmarks per tile
+constexpr int RBF_SLAB = TILE_SLAB;  // columns per LDS slab
 constexpr int RBF_LD = RBF_TL + 4;  // floats per row of the feature tile in LDS: 16-byte aligned, rows four banks apart
 // floats the slabs and the feature tile share: max(32 * (128 + 64) + 64, 128 * 68)
 constexpr int RBF_UNION = RBF_TP * RBF_LD;

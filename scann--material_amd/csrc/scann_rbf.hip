@@ -2,10 +2,8 @@
 //   phi[p][c] = scann_rbf_weight(dist2(x_p, z_c), gamma),   dist2 the difference-form chain of scann_knn_distsq (fp32, columns ascending)
 // written device to device as a feature matrix that the moment and leave-one-out kernels of the readout head read like any index.
 //
-// rbf_feature_kernel: the arithmetic and the tiling of knn_tile_kernel (scann_knn.hip).  A workgroup of 256 lanes takes 128 pool rows and
-// 64 landmarks; both pass through LDS in slabs of 32 columns, column-major ([column][item], every group of four columns shifted by four
-// floats), the next slab fetched into registers while this one is computed; a lane owns an 8 x 4 register block of independent chains, two
-// landmarks of one row per packed fp32 instruction.  The landmarks (m x stride x 4 bytes) are re-read per row tile from L2.  Whether a
+// rbf_feature_kernel: the tile and the slab pipeline of scann_tile.h, difference form: 128 pool rows (the tile's "queries") against 64
+// landmarks (its "rows").  The landmarks (m x stride x 4 bytes) are re-read per row tile from L2.  Whether a
 // row has a non-finite component is found while its columns are staged, once per row: such a row is NaN in all its features.  After the
 // last slab the weight chain (scann_rbf.h) runs on the lane's 32 distances and the 128 x 64 features cross LDS (over the slabs) so that
 // 16 lanes store one row's 256 bytes.  Tiles are cut by position, not by storage chunk.  No atomics, no scratch.
@@ -15,18 +13,11 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int PS = RBF_TP, LS = RBF_TL;  // floats per staged column of the row / landmark slab
-
-// 0 where all four are finite, NaN otherwise (x - x is 0 for a finite x only)
-__device__ __forceinline__ float rbf_nonfinite(const float4& v) { return ((v.x - v.x) + (v.y - v.y)) + ((v.z - v.z) + (v.w - v.w)); }
-
 __global__ __launch_bounds__(RBF_LANES) void rbf_feature_kernel(RbfArgs a) {
   __shared__ float4 rbf_smem[(RBF_UNION + RBF_TP) / 4];
   float* sm = reinterpret_cast<float*>(rbf_smem);
-  float* ps = sm;                               // [32][128] + 32  pool-row slab, column-major
-  float* ls = sm + RBF_SLAB * PS + RBF_SLAB;    // [32][64] + 32   landmark slab, column-major
+  float* ps = sm;                               // the pool-row slab ...
+  float* ls = sm + tile_slab_floats(RBF_TP);    // ... and the landmark slab (tile_stage)
   float* tile = sm;                             // [128][68]       features of the tile, over the slabs
   int* bad = reinterpret_cast<int*>(sm + RBF_UNION);  // [128] the row has a non-finite component
   const int t = threadIdx.x, qg = t & 15, rg = t >> 4;
@@ -59,47 +50,21 @@ __global__ __launch_bounds__(RBF_LANES) void rbf_feature_kernel(RbfArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       gq[i] = prow[i] && col < stride ? *reinterpret_cast<const float4*>(prow[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
-      nf[i] += rbf_nonfinite(gq[i]);
+      nf[i] += row_nonfinite(gq[i]);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) gr[i] = lrow[i] && col < stride ? *reinterpret_cast<const float4*>(lrow[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
   };
   f2 acc[8][2];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
+  tile_clear(acc);
   fetch(0);
   for (int slab = 0; slab < n_slab; ++slab) {
     __syncthreads();  // the previous slab's reads are over
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + RBF_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = ps + c * PS + c + item;
-      d[0] = gq[i].x; d[PS] = gq[i].y; d[2 * PS] = gq[i].z; d[3 * PS] = gq[i].w;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = t + RBF_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = ls + c * LS + c + item;
-      d[0] = gr[i].x; d[LS] = gr[i].y; d[2 * LS] = gr[i].z; d[3 * LS] = gr[i].w;
-    }
+    tile_stage<RBF_LANES, 4, RBF_TP>(ps, gq, t);
+    tile_stage<RBF_LANES, 2, RBF_TL>(ls, gr, t);
     __syncthreads();
     if (slab + 1 < n_slab) fetch(slab + 1);
-#pragma unroll 4
-    for (int c = 0; c < RBF_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-      const int sh = c & ~3;
-      const float4 qa = *reinterpret_cast<const float4*>(ps + c * PS + sh + 4 * qg);       // rows 4 qg .. 4 qg + 3
-      const float4 qb = *reinterpret_cast<const float4*>(ps + c * PS + sh + 64 + 4 * qg);  // rows 64 + 4 qg .. 64 + 4 qg + 3
-      const float4 r4 = *reinterpret_cast<const float4*>(ls + c * LS + sh + 4 * rg);       // landmarks 4 rg .. 4 rg + 3
-      const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f2 qq{qv[j], qv[j]};
-        const f2 d0 = qq - r01, d1 = qq - r23;  // rounded once; the explicit fma keeps the square and the sum one operation
-        acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-        acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-      }
-    }
+    tile_slab<TileForm::DIFF>(ps, ls, qg, rg, acc, RBF_SLAB);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -108,7 +73,7 @@ __global__ __launch_bounds__(RBF_LANES) void rbf_feature_kernel(RbfArgs a) {
   const float nan = __builtin_nanf("");
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int row = (j < 4 ? 0 : 60) + 4 * qg + j;
+    const int row = tile_query(qg, j);
     const bool b = bad[row] != 0;
     float4 w;
     w.x = b ? nan : rbf_weight(acc[j][0].x, a.gamma);

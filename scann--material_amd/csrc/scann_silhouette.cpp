@@ -12,47 +12,12 @@
 
 #include "scann_knn.h"
 #include "scann_runtime.h"
+#include "scann_twin.h"
 #include "scann_silhouette.h"
 
 using namespace scann;
 
 namespace {
-
-bool finite_row(const float* x, int64_t d) {
-  for (int64_t j = 0; j < d; ++j)
-    if (!std::isfinite(x[j])) return false;
-  return true;
-}
-
-typedef float v8 __attribute__((vector_size(32)));
-
-// The pool in blocks of eight rows, each block transposed to [dim][8], and the 8 x 8 distance block on it: the scheme of the density
-// twin (scann_peaks.cpp), 64 independent chains of scann_knn_distsq with the query first, columns ascending
-std::vector<float> transpose8(const float* rows, int64_t n, int64_t dim) {
-  std::vector<float> t((size_t)((n + 7) / 8 * 8 * dim));
-  for (int64_t r = 0; r < (n + 7) / 8 * 8; ++r) {
-    const float* src = rows + std::min(r, n - 1) * dim;
-    float* dst = t.data() + (r / 8) * 8 * dim + r % 8;
-    for (int64_t j = 0; j < dim; ++j) dst[8 * j] = src[j];
-  }
-  return t;
-}
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wpsabi"
-__attribute__((always_inline)) inline void dist2_8x8(const float* const* x, const float* block, int64_t d, v8* out) {
-  v8 a[8];
-  for (int u = 0; u < 8; ++u) a[u] = v8{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t j = 0; j < d; ++j) {
-    v8 r;
-    __builtin_memcpy(&r, block + 8 * j, sizeof(r));
-    for (int u = 0; u < 8; ++u) {
-      const v8 t = x[u][j] - r;
-      a[u] = __builtin_elementwise_fma(t, t, a[u]);
-    }
-  }
-  for (int u = 0; u < 8; ++u) out[u] = a[u];
-}
 
 struct Twin {
   const float* rows;    // [n][dim] the pool ...
@@ -135,9 +100,6 @@ __attribute__((always_inline)) inline void twin_groups(const Twin& c, int64_t fi
 // the same loops where the host has AVX2 and a fused multiply-add instruction; fmaf is correctly rounded either way: the same bits
 void groups_plain(const Twin& c, int64_t first, int64_t step) { twin_groups(c, first, step); }
 __attribute__((target("avx2,fma"))) void groups_fma(const Twin& c, int64_t first, int64_t step) { twin_groups(c, first, step); }
-#pragma clang diagnostic pop
-
-bool host_fast() { return __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma"); }
 
 // What both routes check before any work, in the order of the header; empty: fine
 std::string bad_arguments(int64_t n, const int32_t* labels, int32_t C, const int32_t* qpos, int64_t nq, int32_t shift, const int64_t* counts,
@@ -181,18 +143,7 @@ int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32
   const std::vector<float> rows8 = transpose8(rows, n, dim);
   std::atomic<int> bad{0};
   Twin c{rows, rows8.data(), n, dim, labels, cnt.data(), C, qpos, m, squared != 0, shift, std::ldexp(1.0f, shift), counts, a, b, other, sums, &bad};
-  void (*fn)(const Twin&, int64_t, int64_t) = host_fast() ? groups_fma : groups_plain;
-  // thread k takes the groups of eight queries k, k + nt, ...; every query's result is its own
-  const double work = (double)m * (double)n * (double)dim;
-  int64_t nt = threads > 0 ? threads : work < 4e6 ? 1 : std::min<int64_t>(16, (int64_t)std::thread::hardware_concurrency());
-  nt = std::max<int64_t>(1, std::min<int64_t>(nt, (m + 7) / 8));
-  if (nt == 1) {
-    fn(c, 0, 1);
-  } else {
-    std::vector<std::thread> pool;
-    for (int64_t k = 0; k < nt; ++k) pool.emplace_back(fn, std::cref(c), k, nt);
-    for (auto& th : pool) th.join();
-  }
+  twin_run(host_fast() ? groups_fma : groups_plain, c, m, threads);
   return bad.load() ? SCANN_ERR_RANGE : SCANN_OK;
 }
 
@@ -239,16 +190,16 @@ int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t
     if (cnt[(size_t)p]) ++counts_h[(size_t)labels[p]];
   }
   std::vector<int64_t> first((size_t)C + 1, 0);
-  for (int32_t c = 0; c < C; ++c) first[(size_t)c + 1] = first[(size_t)c] + (counts_h[(size_t)c] + PK_TR - 1) / PK_TR * PK_TR;
+  for (int32_t c = 0; c < C; ++c) first[(size_t)c + 1] = first[(size_t)c] + (counts_h[(size_t)c] + TILE_TR - 1) / TILE_TR * TILE_TR;
   const int64_t n_perm = first[(size_t)C];
   if (n_perm > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the padded clusters have too many rows");
-  std::vector<int32_t> perm((size_t)n_perm, -1), tile_label((size_t)(n_perm / PK_TR));
+  std::vector<int32_t> perm((size_t)n_perm, -1), tile_label((size_t)(n_perm / TILE_TR));
   {
     std::vector<int64_t> at(first.begin(), first.end() - 1);
     for (int64_t p = 0; p < N; ++p)
       if (cnt[(size_t)p]) perm[(size_t)at[(size_t)labels[p]]++] = (int32_t)p;
     for (int32_t c = 0; c < C; ++c)
-      for (int64_t tl = first[(size_t)c] / PK_TR; tl < first[(size_t)c + 1] / PK_TR; ++tl) tile_label[(size_t)tl] = c;
+      for (int64_t tl = first[(size_t)c] / TILE_TR; tl < first[(size_t)c + 1] / TILE_TR; ++tl) tile_label[(size_t)tl] = c;
   }
   std::vector<int32_t> qp((size_t)M), ql((size_t)M);
   for (int64_t i = 0; i < M; ++i) {
@@ -257,7 +208,7 @@ int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t
     ql[(size_t)i] = cnt[(size_t)p] ? labels[p] : -1;
   }
   // 3. the queries in slices whose table stays within 512 MiB; everything of the call is enqueued, then one wait
-  const int64_t slice = std::max<int64_t>(PK_TQ, std::min<int64_t>(((int64_t)512 << 20) / (8 * (int64_t)C) / PK_TQ * PK_TQ, (M + PK_TQ - 1) / PK_TQ * PK_TQ));
+  const int64_t slice = std::max<int64_t>(TILE_TQ, std::min<int64_t>(((int64_t)512 << 20) / (8 * (int64_t)C) / TILE_TQ * TILE_TQ, (M + TILE_TQ - 1) / TILE_TQ * TILE_TQ));
   const size_t bT = align_up((size_t)n_chunk * 8), bP = align_up((size_t)std::max<int64_t>(n_perm, 1) * 4), bL = align_up(tile_label.size() * 4 + 4),
                bC = align_up((size_t)C * 8), bQ = align_up((size_t)std::max<int64_t>(M, 1) * 4), bD = align_up((size_t)std::max<int64_t>(M, 1) * 8),
                bS = align_up((size_t)slice * C * 8), bF = 256;

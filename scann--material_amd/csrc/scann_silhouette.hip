@@ -1,11 +1,10 @@
 // Silhouette of a labelled latent-space index (scann_index_silhouette, include/scann_hip.h):
 //   t(i, j) = round-to-nearest-even(2^shift e),  e = dist2(row_i, row_j) or its correctly rounded square root,
 //   S[i][c] = the int64 sum of t over the counting rows j != i with label c,
-// dist2 the difference-form chain of scann_knn_distsq (fp32, columns ascending; why VALU and why this form: the top of scann_knn.hip).
+// dist2 the difference-form chain of scann_knn_distsq (fp32, columns ascending).
 //
-// sil_tile_kernel is peaks_tile_kernel<false> (scann_peaks.hip) with another reduction: 256 lanes, 128 queries x 64 rows per tile,
-// 32-column slabs through LDS, column-major, the next slab fetched into registers while this one is computed, an 8 x 4 register block of
-// independent chains per lane.  A query has C sums, up to 1024, which fit neither registers nor LDS; so the rows come through a
+// sil_tile_kernel is peaks_tile_kernel<false> (scann_peaks.hip) with another reduction, on the tile and the slab pipeline of
+// scann_tile.h, 128 queries x 64 rows per tile.  A query has C sums, up to 1024, which fit neither registers nor LDS; so the rows come through a
 // permutation that the host builds: the counting positions sorted by (label, position), every cluster padded to whole 64-row tiles.  A
 // tile then belongs to one cluster, the lane keeps the eight 64-bit accumulators of the density pass, and they are flushed when the
 // next tile belongs to another cluster and at the end of the range: the 16 lanes that share a query are added through LDS (over the
@@ -22,35 +21,28 @@ namespace scann {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 template <bool SQUARED>
 __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
-  __shared__ float4 sil_smem[PK_UNION / 4];
-  __shared__ int leave_s[PK_TQ];                     // the position each query leaves out; -1: the query gets nothing
-  __shared__ const float* qrow_s[PK_TQ];             // where each query's row lies, null: none
-  __shared__ int perm_s[2][PK_TR];                   // the positions of a tile's rows, this tile's and the next one's
+  __shared__ float4 sil_smem[TILE_UNION / 4];
+  __shared__ int leave_s[TILE_TQ];                     // the position each query leaves out; -1: the query gets nothing
+  __shared__ const float* qrow_s[TILE_TQ];             // where each query's row lies, null: none
+  __shared__ int perm_s[2][TILE_TR];                   // the positions of a tile's rows, this tile's and the next one's
   float* sm = reinterpret_cast<float*>(sil_smem);
-  float* qs = sm;                                    // [32][PK_QS] + 32  query slab, column-major
-  float* rs = sm + PK_SLAB * PK_QS + PK_SLAB;        // [32][PK_RS] + 32  row slab, column-major
+  float* qs = sm;                                    // the query slab ...
+  float* rs = sm + tile_slab_floats(TILE_TQ);        // ... and the row slab (tile_stage)
   unsigned long long* red = reinterpret_cast<unsigned long long*>(sil_smem);  // [16][128] the lanes' sums, over the slabs
   const int t = threadIdx.x, qg = t & 15, rg = t >> 4;
-  const int q0 = blockIdx.x * PK_TQ;
+  const int q0 = blockIdx.x * TILE_TQ;
   const int stride = a.stride, chunk_rows = a.chunk_rows;
   const long long r_lo = (long long)blockIdx.y * a.rows_per_range, r_hi = r_lo + a.rows_per_range;
   const int r_begin = (int)(r_lo < a.n_perm ? r_lo : a.n_perm), r_end = (int)(r_hi < a.n_perm ? r_hi : a.n_perm);  // multiples of 64
   // the lane stages four float4 of queries per slab, always of the same items: their rows are found once, and kept in LDS, not in
   // eight registers (the term stage needs them for the fourth workgroup per CU)
-  const bool owner = t < PK_TQ && q0 + t < a.nq;  // lane t finishes query q0 + t
-  if (t < PK_TQ) {
+  const bool owner = t < TILE_TQ && q0 + t < a.nq;  // lane t finishes query q0 + t
+  if (t < TILE_TQ) {
     const int pos = owner ? a.qpos[q0 + t] : -1;
     leave_s[t] = pos;
-    const float* p = nullptr;
-    if (pos >= 0) {
-      const int c = pos / chunk_rows;
-      p = a.rows[c] + (size_t)(pos - c * chunk_rows) * stride;
-    }
-    qrow_s[t] = p;
+    qrow_s[t] = pos >= 0 ? tile_row(a.rows, pos, chunk_rows, stride) : nullptr;
   }
   __syncthreads();
   unsigned long long s64[8];
@@ -58,8 +50,8 @@ __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
   for (int j = 0; j < 8; ++j) s64[j] = 0;
   uint32_t worst = 0;  // the largest bit pattern among the scaled terms that count
   const float scale = a.scale;
-  const int n_slab = (stride + PK_SLAB - 1) / PK_SLAB;
-  const int n_step = ((r_end - r_begin) / PK_TR) * n_slab;  // (tile, slab) steps of this range
+  const int n_slab = (stride + TILE_SLAB - 1) / TILE_SLAB;
+  const int n_step = ((r_end - r_begin) / TILE_TR) * n_slab;  // (tile, slab) steps of this range
   float4 gq[4], gr[2];
   const float* rp[2] = {nullptr, nullptr};
   int f_slab = 0, f_tile0 = r_begin, f_par = 0;  // the step the next fetch belongs to, and its tile's half of perm_s
@@ -68,16 +60,12 @@ __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int pos = a.perm[f_tile0 + ((t + PK_LANES * i) >> 3)];  // f_tile0 + 63 < n_perm
-        rp[i] = nullptr;
-        if (pos >= 0) {
-          const int c = pos / chunk_rows;
-          rp[i] = a.rows[c] + (size_t)(pos - c * chunk_rows) * stride;
-        }
+        rp[i] = pos >= 0 ? tile_row(a.rows, pos, chunk_rows, stride) : nullptr;
         if ((t & 7) == 0) perm_s[f_par][(t + PK_LANES * i) >> 3] = pos;  // read two barriers later at the earliest
       }
       f_par ^= 1;
     }
-    const int col = f_slab * PK_SLAB + 4 * (t & 7);
+    const int col = f_slab * TILE_SLAB + 4 * (t & 7);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float* qp = qrow_s[(t + PK_LANES * i) >> 3];
@@ -85,45 +73,19 @@ __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) gr[i] = rp[i] && col < stride ? *reinterpret_cast<const float4*>(rp[i] + col) : float4{0.f, 0.f, 0.f, 0.f};
-    if (++f_slab == n_slab) f_slab = 0, f_tile0 += PK_TR;
+    if (++f_slab == n_slab) f_slab = 0, f_tile0 += TILE_TR;
   };
   f2 acc[8][2];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j][0] = acc[j][1] = f2{0.f, 0.f};
+  tile_clear(acc);
   int c_slab = 0, tile0 = r_begin, par = 0;  // the step being computed
   if (n_step > 0) fetch();
   for (int step = 0; step < n_step; ++step) {
     __syncthreads();  // the previous slab's reads, or the previous flush, are over
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + PK_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = qs + c * PK_QS + c + item;
-      d[0] = gq[i].x; d[PK_QS] = gq[i].y; d[2 * PK_QS] = gq[i].z; d[3 * PK_QS] = gq[i].w;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = t + PK_LANES * i, item = e >> 3, c = 4 * (e & 7);
-      float* d = rs + c * PK_RS + c + item;
-      d[0] = gr[i].x; d[PK_RS] = gr[i].y; d[2 * PK_RS] = gr[i].z; d[3 * PK_RS] = gr[i].w;
-    }
+    tile_stage<PK_LANES, 4, TILE_TQ>(qs, gq, t);
+    tile_stage<PK_LANES, 2, TILE_TR>(rs, gr, t);
     __syncthreads();
     if (step + 1 < n_step) fetch();
-#pragma unroll 4
-    for (int c = 0; c < PK_SLAB; ++c) {  // columns ascending: every pair's chain in the order of the definition
-      const int sh = c & ~3;
-      const float4 qa = *reinterpret_cast<const float4*>(qs + c * PK_QS + sh + 4 * qg);       // queries 4 qg .. 4 qg + 3
-      const float4 qb = *reinterpret_cast<const float4*>(qs + c * PK_QS + sh + 64 + 4 * qg);  // queries 64 + 4 qg .. 64 + 4 qg + 3
-      const float4 r4 = *reinterpret_cast<const float4*>(rs + c * PK_RS + sh + 4 * rg);       // rows 4 rg .. 4 rg + 3
-      const f2 r01{r4.x, r4.y}, r23{r4.z, r4.w};
-      const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f2 qq{qv[j], qv[j]};
-        const f2 d0 = qq - r01, d1 = qq - r23;  // rounded once; the explicit fma keeps the square and the sum one operation
-        acc[j][0] = __builtin_elementwise_fma(d0, d0, acc[j][0]);
-        acc[j][1] = __builtin_elementwise_fma(d1, d1, acc[j][1]);
-      }
-    }
+    tile_slab<TileForm::DIFF>(qs, rs, qg, rg, acc, TILE_SLAB);
     if (++c_slab != n_slab) continue;
     c_slab = 0;
     // the tile's last slab: the 32 distances become terms
@@ -132,11 +94,10 @@ __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
     par ^= 1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int leave = leave_s[(j < 4 ? 0 : 60) + 4 * qg + j];
+      const int leave = leave_s[tile_query(qg, j)];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float d = (i & 1) ? acc[j][i >> 1].y : acc[j][i >> 1].x;
-        const float f = sil_scaled(d, SQUARED, scale);
+        const float f = sil_scaled(tile_at(acc, j, i), SQUARED, scale);
         const bool live = leave >= 0 && pp[i] >= 0 && pp[i] != leave;
         s64[j] += live ? sil_round(f) : 0u;
         worst = max(worst, live ? __float_as_uint(f) : 0u);
@@ -144,21 +105,19 @@ __global__ __launch_bounds__(PK_LANES) void sil_tile_kernel(SilArgs a) {
       acc[j][0] = acc[j][1] = f2{0.f, 0.f};
       __builtin_amdgcn_sched_barrier(0);  // one query's four roots at a time: 32 interleaved ones cost the fourth workgroup per CU
     }
-    const int tile = tile0 / PK_TR, label = a.tile_label[tile];
-    tile0 += PK_TR;
+    const int tile = tile0 / TILE_TR, label = a.tile_label[tile];
+    tile0 += TILE_TR;
     if (tile0 < r_end && a.tile_label[tile + 1] == label) continue;  // (the same for every lane)
     // the cluster ends here, or the range does: the sums go to the table
     __syncthreads();  // every lane has read its last slab
+    tile_sums_write(red, s64, qg, rg);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[rg * PK_TQ + (j < 4 ? 0 : 60) + 4 * qg + j] = s64[j];
-      s64[j] = 0;
-    }
+    for (int j = 0; j < 8; ++j) s64[j] = 0;
     __syncthreads();
     if (owner) {
       unsigned long long total = 0;
 #pragma unroll
-      for (int g = 0; g < PK_LANES / 16; ++g) total += red[g * PK_TQ + t];
+      for (int g = 0; g < PK_LANES / 16; ++g) total += red[g * TILE_TQ + t];
       if (total) atomicAdd(a.table + (size_t)(q0 + t) * a.C + label, total);
     }
   }
@@ -201,21 +160,14 @@ __global__ __launch_bounds__(PK_LANES) void sil_finish_kernel(SilArgs a) {
 __global__ __launch_bounds__(PK_LANES) void sil_eligible_kernel(const float* const* rows, int n_total, int chunk_rows, int stride, unsigned char* ok) {
   const int p = blockIdx.x * PK_LANES + threadIdx.x;
   if (p >= n_total) return;
-  const int c = p / chunk_rows;
-  const float* row = rows[c] + (size_t)(p - c * chunk_rows) * stride;
-  float nf = 0.f;  // NaN once a component was not finite (x - x is 0 for a finite x only; the padding columns are zero)
-  for (int k = 0; k < stride; k += 4) {
-    const float4 v = *reinterpret_cast<const float4*>(row + k);
-    nf += ((v.x - v.x) + (v.y - v.y)) + ((v.z - v.z) + (v.w - v.w));
-  }
-  ok[p] = nf != nf ? 0 : 1;
+  ok[p] = row_nonfinite(tile_row(rows, p, chunk_rows, stride), stride) ? 0 : 1;
 }
 
 }  // namespace
 
 hipError_t launch_sil_tiles(const SilArgs& a, hipStream_t s) {
   if (a.n_perm <= 0 || a.nq <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((a.nq + PK_TQ - 1) / PK_TQ), (unsigned)a.n_range);
+  const dim3 grid((unsigned)((a.nq + TILE_TQ - 1) / TILE_TQ), (unsigned)a.n_range);
   if (a.squared)
     hipLaunchKernelGGL(sil_tile_kernel<true>, grid, dim3(PK_LANES), 0, s, a);
   else

@@ -13,7 +13,7 @@ namespace scann {
 hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
 void cached_free(void*) {}
 int fail(scann_handle*, int code, const std::string&) { return code; }
-void peaks_geometry(int64_t, int64_t, int32_t* r, int32_t* n) { *r = PK_TR, *n = 1; }
+void peaks_geometry(int64_t, int64_t, int32_t* r, int32_t* n) { *r = TILE_TR, *n = 1; }
 hipError_t launch_sil_tiles(const SilArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_sil_finish(const SilArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_sil_eligible(const float* const*, int32_t, int32_t, int32_t, unsigned char*, hipStream_t) { return hipErrorNotSupported; }
