@@ -323,7 +323,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
     a.WAh = p.W1h; a.bA = p.bg; a.WBh = p.W3h; a.WCh = p.Wqh; a.bC = p.bq;
     a.oA = W->sp_P1; a.oB = W->sp_P3; a.oC = W->sp_q;
     a.n_member = nm; a.m_w = a.m_x = a.m_o = wst;
-    launch_atom(a, s);
+    launch_atom(a, s, h->n_cu, h->atom_rows);
     HIPCHK(h, hipStreamSynchronize(s));  // once per weight change: forwards on the handle's other streams read the tables too
     W->sp_dirty = false;
     for (int m = 1; m < nm; ++m) o.members[m]->sp_dirty = false;
@@ -401,7 +401,7 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
         a.WDh = reinterpret_cast<const _Float16*>(W->head.Wgkp);
       }
     }
-    if (!(species0 && l == 0)) launch_atom(a, s);
+    if (!(species0 && l == 0)) launch_atom(a, s, h->n_cu, h->atom_rows);
     if (tm) tm->mark(l < L ? 1 : 3);
     if (l == L) break;
     EdgeArgs ea{};

@@ -217,7 +217,8 @@ struct AtomArgs {
   int32_t n_member;
   int64_t m_w, m_x, m_o;
 };
-void launch_atom(const AtomArgs& a, hipStream_t s);
+// n_cu: compute units of the device; force_rows: the handle's SCANN_ATOM_ROWS (0: automatic) -- the tile height is the launch's choice
+void launch_atom(const AtomArgs& a, hipStream_t s, int n_cu, int force_rows);
 
 struct EdgeArgs {
   const EdgeTile* tiles;       // whole atoms per tile: <= TE_MAX edges and <= TQ atoms

@@ -11,6 +11,8 @@
 // Kernels (one launch each per LocalAttention iteration, see scann_runtime.cpp: run_forward):
 //   atom_kernel   : [ResidualNorm of previous layer] -> centres c; P1 = c W1 + bg, P3 = c W3, q = c Wq + bq
 //                   (attention.py:37-40, :160, and the centre/neighbour thirds of filter_geo :142-151)
+//                   (atom_wide_kernel: the same body on 96-row tiles, for the ResidualNorm launches of a plain inference forward whose
+//                   32- / 64-row tiles would leave a CU more than two -- launch_atom picks the height from n_atom and the CU count)
 //   edge_kernel   : per tile of <=64 edges (whole atoms): U = G W2; geom' = LN_g(swish(U+P1[i]+P3[j])+G)
 //                   (:141-153); ang = c[j]*geom' (:136,:157); K = ang Wk + bk (:163);
 //                   per (atom, head) softmax over its edges and ctx = LN(sum attn K + q) (:180-214)
@@ -110,15 +112,78 @@ __global__ __launch_bounds__(256, RT == 2 ? (EX ? 2 : 3) : (MODE == 1 ? 3 : 4)) 
 #undef SCANN_ATOM_BIX
 }
 
-void launch_atom(const AtomArgs& a, hipStream_t s) {
-  if (a.n_atom <= 0) return;
+// Wide tiles (96 rows: RT = 3) of the plain split-fp16 inference launches with a ResidualNorm -- MODE 0 of layers 1 .. L-1 and MODE 2 of
+// the readout's launch.  The body is atom_kernel's, text for text: every weight half a wave loads multiplies three row groups instead
+// of one or two, so a tile streams its five 64 KB images once for 96 rows; a row's values come out of the same instruction sequence at
+// every height (scann_atom_body.inc; tests/test_gpu_atom_rows.py).  Two workgroups per CU: 208-210 VGPRs, 58,880 B of LDS, no scratch (a
+// bound of 3 sends the allocator to occupancy 1 with AGPR spills).  A kernel of its own name: tests/test_host.py holds atom_kernel's
+// instantiations to the three- and four-workgroup register budgets, tests/test_host_atom_wide.py this one's.  Everything else -- exact,
+// training / debug, Monte Carlo, model sets, after_Lc outputs, the base branch's MODE 1 and the first layer's FFN = false launch --
+// stays on atom_kernel (launch_atom).
+// (RT = 4, 128 rows, compiles to 254 VGPRs / 77,312 B without scratch and was measured with this one: it won at no launch size --
+//  atom_tile_rows -- and is not instantiated.)
+template <bool FFN, int MODE, int RT>
+__global__ __launch_bounds__(256, 2) void atom_wide_kernel(AtomArgs a) {
+#pragma clang fp contract(off)  // (as in atom_kernel)
+  static_assert(FFN && (MODE == 0 || MODE == 2) && RT == 3, "the wide tiles exist for the ResidualNorm launches of plain inference forwards");
+  constexpr bool EX = false, KEEP = false, ZOUT = false, MC = false;
+  constexpr int TAR = 32 * RT;
+  __shared__ __attribute__((aligned(16))) unsigned char sTile[2 * TAR * PLANE_STRIDE * 2];
+  __shared__ __attribute__((aligned(16))) float sRed[TAR * 8];
+#define SR_STAT(w, r) (((w) * TAR + (r)) * 2)
+  __shared__ __attribute__((aligned(16))) float sPar[7 * D];
+#define SCANN_ATOM_BIX blockIdx.x
+#include "scann_atom_body.inc"
+#undef SR_STAT
+#undef SCANN_ATOM_BIX
+}
+
+// Rows per tile of the launch `a` on n_cu compute units.  `wide`: a ResidualNorm launch of a plain inference forward, the one kind that
+// has atom_wide_kernel (96 rows) and whose heights were measured.  `force` (env SCANN_ATOM_ROWS, read by scann_create): 32 / 64 / 96
+// where the launch has that instantiation, anything else is the automatic choice.
+static int atom_tile_rows(const AtomArgs& a, int n_cu, bool wide, int force) {
+  if (force == 32 || force == 64 || (wide && force == 96)) return force;
   // 32-row tiles (<= 128 VGPRs, 22 KB of LDS: four workgroups per CU = 1,024 slots) while they all fit ONE round of workgroups: the
   // launch is then the latency chain of a tile, and a 32-row tile's chain is shorter (one batch per launch: 490 k -> 568 k
   // molecules/s, training step 1.14 -> 1.09 ms).  Beyond that 64-row tiles (half the weight traffic per row).
   // (re-measured in round 5 at the driver's 10-batch shape, 23 k atoms: 64-row tiles -- half the weight traffic, 360 tiles -- 0.159-0.170 ms
   //  of atom launches per forward against 0.152-0.157 ms for the 720 32-row tiles: the threshold stays)
   const int rows = a.n_atom <= 32 * 1024 ? 32 : 64;
-  if (a.n_member > 0) {  // model set: the plain inference kernels (scann_forward_models), the same row height as one member's launch
+  if (!wide || n_cu <= 0) return rows;
+  // The plain inference launches, measured at every height (ms of atom launches per forward, bench.py --no-extras --group G, QM9 L = 7:
+  // seven launches; one 256-CU device; G >= 8: mean of four passes that lie within 3 % of each other; profiles/atom_rows_notes.md):
+  //   G   atoms     32 rows   64 rows   96 rows   128 rows
+  //   1    2.3 k    0.0711    0.0953    0.1175    0.1441      a lone tile's chain: 10.2 / 13.6 / 16.8 / 20.6 us per launch
+  //   2    4.6 k    0.0808    0.1016    0.1256    0.1490
+  //   8   18.4 k    0.1377    0.1444    0.1358    0.1569
+  //  10   23.0 k    0.1433    0.1509    0.1486    0.1667      720 / 360 / 240 / 180 tiles
+  //  12   27.6 k    0.1800    0.1576    0.1903    0.1751      864 / 432 / 288 / 216 tiles
+  //  14   32.2 k    0.1869    0.1654    0.1927    0.1824
+  //  16   36.8 k    0.2170    0.2086    0.1998    0.2453      1,150 / 575 / 384 / 288 tiles
+  // A launch is not the weight stream of its busiest CU: a third of the L1 -> L2 read requests (96 rows at G = 10) buys nothing, because
+  // with one workgroup on a CU each SIMD holds ONE wave and every epilogue, barrier and weight wait of its chain lies open -- a lone
+  // 96-row tile lives 16.8 us against 10.2.  What pays is two or three waves per SIMD from tiles as high as that allows:
+  //   32 rows up to three tiles per CU (G <= 10); 64 rows up to two per CU (G = 12, 14: -12 %); 96 rows up to two per CU (G = 16: -4 %);
+  //   beyond that (unmeasured) 64 rows as before.  128 rows wins nowhere.
+  if ((a.n_atom + 31) / 32 <= 3 * n_cu) return 32;
+  if ((a.n_atom + 63) / 64 <= 2 * n_cu) return 64;
+  if ((a.n_atom + 95) / 96 <= 2 * n_cu) return 96;
+  return 64;
+}
+
+void launch_atom(const AtomArgs& a, hipStream_t s, int n_cu, int force_rows) {
+  if (a.n_atom <= 0) return;
+  const bool keep = !a.exact && (a.drop_p > 0.f || a.keep_pre1 || a.keep_T2 || a.keep_preA);  // training forward
+  const bool wide = a.ffn && (a.mode == 0 || a.mode == 2) && !a.exact && !keep && a.n_member <= 0 && !(a.mc_rows && a.drop_p > 0.f) &&
+                    !(a.mode == 2 && a.out_z);  // atom_wide_kernel's launches
+  const int rows = atom_tile_rows(a, n_cu, wide, force_rows);
+  if (rows == 96) {
+    const dim3 grid((a.n_atom + rows - 1) / rows), block(256);
+    if (a.mode == 0) hipLaunchKernelGGL((atom_wide_kernel<true, 0, 3>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((atom_wide_kernel<true, 2, 3>), grid, block, 0, s, a);
+    return;
+  }
+  if (a.n_member > 0) {  // model set: the plain inference kernels (scann_forward_models), 32- or 64-row tiles by one member's rows
     const dim3 grid(((a.n_atom + rows - 1) / rows) * a.n_member), block(256);
 #define SCANN_ATOM_SET(F, M)                                                                                          \
   do {                                                                                                                \
@@ -156,7 +221,6 @@ void launch_atom(const AtomArgs& a, hipStream_t s) {
 #undef SCANN_ATOM_MC
     return;
   }
-  const bool keep = !a.exact && (a.drop_p > 0.f || a.keep_pre1 || a.keep_T2 || a.keep_preA);  // training forward
   if (a.mode == 2 && a.out_z) {  // inference forward that returns after_Lc (never a training forward: run_forward)
 #define SCANN_ATOM_Z(F)                                                                                        \
   do {                                                                                                         \
