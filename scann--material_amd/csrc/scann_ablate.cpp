@@ -1,6 +1,7 @@
 // scann_ablate_pooling (include/scann_hip.h): one forward of the resident batch, then every ablated pooling of one mode from the readout's
 // operands gq / gk that the forward left on the device (scann_ablate.hip).  The forward and its download are forward_and_download
 // (scann_batch.cpp): y, the GlobalAttention scores, the range guard and the exact re-run behave as in scann_batch_download.
+#include "scann_call.h"
 #include "scann_runtime.h"
 
 using namespace scann;
@@ -20,10 +21,10 @@ int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, fl
   const int A = db->n_atom, B = db->n_struct;
   if (const int r = forward_and_download(h, db, 0, 0, y, ga)) return r;
   hipStream_t s = h->streams[db->last_slot];
-  const size_t bY = align_up((size_t)std::max(A, 1) * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, 2 * bY));
   AblateArgs a{};
+  CallWs ws;
+  ws.take(a.y_abl, (size_t)std::max(A, 1)); ws.take(a.order, (size_t)std::max(A, 1));
+  HIPCHK(h, ws.alloc());
   a.mol_offset = db->mol_offset; a.n_struct = B; a.max_atoms = db->max_atoms;
   a.dg = c.global_dim; a.dout = c.dense_out; a.use_ga_norm = c.use_ga_norm; a.relu_out = c.relu_out; a.mode = mode;
   if (h->generic) {
@@ -35,13 +36,11 @@ int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, fl
     a.Wb = h->head.Wb; a.bb = h->head.bb; a.wo = h->head.wo; a.bo = h->head.bo;
   }
   a.ga_attn = db->ga;
-  a.y_abl = reinterpret_cast<float*>(ws);
-  a.order = reinterpret_cast<int32_t*>(ws + bY);
   hipError_t e = A > 0 ? launch_ablate(a, !h->generic, s) : hipSuccess;
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e == hipSuccess && A > 0 && y_abl) e = hipMemcpy(y_abl, a.y_abl, (size_t)A * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess && A > 0 && order) e = hipMemcpy(order, a.order, (size_t)A * 4, hipMemcpyDeviceToHost);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   return SCANN_OK;
 }

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_embed.h"
 #include "scann_runtime.h"
 
@@ -150,15 +151,6 @@ double iterate_host(int64_t N, const int64_t* row_first, const int32_t* col, con
   return Z;
 }
 
-struct Bump {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at += align_up(bytes);
-    return o;
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -187,44 +179,32 @@ int scann_embed_iterate(scann_handle_t* h, int64_t N, const int64_t* row_first, 
   const int64_t E = row_first[N], n_block = (N + EMBED_BLOCK - 1) / EMBED_BLOCK, n_span = (N + EMBED_SPAN_ROWS - 1) / EMBED_SPAN_ROWS;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->streams[0];
-  Bump b;
-  const size_t oFirst = b.take((size_t)(N + 1) * 8), oCol = b.take((size_t)E * 4), oP = b.take((size_t)E * 4), oY0 = b.take((size_t)N * 8),
-               oY1 = b.take((size_t)N * 8), oU = b.take((size_t)N * 8), oGain = b.take((size_t)N * 8), oGrad = b.take((size_t)N * 8),
-               oPart = b.take((size_t)n_span * 3 * N * 8), oRs = b.take((size_t)3 * N * 8), oBs = b.take((size_t)3 * n_block * 8), oZ = b.take(8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
   TsneArgs a{};
   a.N = (int32_t)N; a.n_span = (int32_t)n_span;
-  a.row_first = reinterpret_cast<const int64_t*>(ws + oFirst);
-  a.col = reinterpret_cast<const int32_t*>(ws + oCol);
-  a.p = reinterpret_cast<const float*>(ws + oP);
-  a.y[0] = reinterpret_cast<float2*>(ws + oY0); a.y[1] = reinterpret_cast<float2*>(ws + oY1);
-  a.u = reinterpret_cast<float2*>(ws + oU);
-  a.gain = reinterpret_cast<float2*>(ws + oGain);
-  a.grad = reinterpret_cast<float2*>(ws + oGrad);
-  a.part = reinterpret_cast<double*>(ws + oPart);
-  a.rsum = reinterpret_cast<double*>(ws + oRs);
-  a.bsum = reinterpret_cast<double*>(ws + oBs);
-  a.z_out = reinterpret_cast<double*>(ws + oZ);
   a.exaggeration = exaggeration; a.momentum = momentum; a.lr = lr;
-  hipError_t e = hipMemcpyAsync(ws + oFirst, row_first, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && E > 0) e = hipMemcpyAsync(ws + oCol, col, (size_t)E * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && E > 0) e = hipMemcpyAsync(ws + oP, p, (size_t)E * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oY0, y, (size_t)N * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oU, u, (size_t)N * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oGain, gain, (size_t)N * 8, hipMemcpyHostToDevice, s);
+  CallWs ws;
+  ws.take(a.row_first, (size_t)N + 1); ws.take(a.col, (size_t)E); ws.take(a.p, (size_t)E); ws.take(a.y[0], (size_t)N); ws.take(a.y[1], (size_t)N);
+  ws.take(a.u, (size_t)N); ws.take(a.gain, (size_t)N); ws.take(a.grad, (size_t)N); ws.take(a.part, (size_t)n_span * 3 * N); ws.take(a.rsum, (size_t)3 * N);
+  ws.take(a.bsum, (size_t)3 * n_block); ws.take(a.z_out, 1);
+  HIPCHK(h, ws.alloc());
+  hipError_t e = hipMemcpyAsync(writable(a.row_first), row_first, (size_t)(N + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && E > 0) e = hipMemcpyAsync(writable(a.col), col, (size_t)E * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && E > 0) e = hipMemcpyAsync(writable(a.p), p, (size_t)E * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.y[0], y, (size_t)N * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.u, u, (size_t)N * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(a.gain, gain, (size_t)N * 8, hipMemcpyHostToDevice, s);
   int cur = 0;
   for (int32_t it = 0; it < n_iter && e == hipSuccess; ++it, cur ^= 1) e = launch_embed_iteration(a, cur, s);
   std::vector<float> grad(grad_out ? (size_t)(2 * N) : 0);  // (the outputs change only if the call succeeds)
   std::vector<float> yo((size_t)(2 * N)), uo((size_t)(2 * N)), go((size_t)(2 * N));
   double z = 0.0;
-  if (e == hipSuccess) e = hipMemcpyAsync(yo.data(), cur ? ws + oY1 : ws + oY0, (size_t)N * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(uo.data(), ws + oU, (size_t)N * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(go.data(), ws + oGain, (size_t)N * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && grad_out) e = hipMemcpyAsync(grad.data(), ws + oGrad, (size_t)N * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&z, ws + oZ, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(yo.data(), a.y[cur], (size_t)N * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(uo.data(), a.u, (size_t)N * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(go.data(), a.gain, (size_t)N * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && grad_out) e = hipMemcpyAsync(grad.data(), a.grad, (size_t)N * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&z, a.z_out, 8, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   std::copy(yo.begin(), yo.end(), y);

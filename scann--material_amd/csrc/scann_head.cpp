@@ -7,6 +7,7 @@
 #include <cmath>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_head.h"
 #include "scann_knn.h"
 #include "scann_runtime.h"
@@ -133,20 +134,6 @@ void loo_outputs(const double* q, int32_t L, int32_t K, int64_t* n_used, double*
   *n_used = (int64_t)q[3 * LK + L];
 }
 
-int head_level_dim(const scann_handle* h, int32_t level) {
-  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
-}
-
-// a workspace laid out piece by piece
-struct Bump {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at += align_up(bytes);
-    return o;
-  }
-};
-
 }  // namespace
 
 namespace scann {
@@ -175,51 +162,41 @@ std::string check_head_eval(int dim, const float* mean, const float* tmean, cons
 int head_eval_rows(scann_handle* h, hipStream_t s, const float* src, int pitch, int64_t nq, int dim, const float* mean, const float* tmean,
                    const float* weights, int32_t K, const float* components, int32_t m, const float* scale, float lev0, float* pred, float* lev) {
   const int stride = (dim + 3) / 4 * 4;
-  Bump b;
-  const size_t oMean = b.take((size_t)stride * 4), oW = b.take((size_t)K * stride * 4), oV = b.take((size_t)m * stride * 4),
-               oPad = b.take(stride != pitch ? (size_t)nq * stride * 4 : 0);
-  const size_t zeroed = b.at;
-  const size_t oTab = b.take(8), oWk = b.take((size_t)nq * K * 4), oZ = b.take((size_t)nq * m * 4), oTmean = b.take((size_t)K * 4),
-               oS = b.take((size_t)K * m * 4), oPred = b.take((size_t)nq * K * 4), oLev = b.take((size_t)nq * K * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
-  if (stride != pitch) {  // rows of the padded width, as an index keeps them
-    if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oPad, (size_t)stride * 4, src, (size_t)pitch * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
-    src = reinterpret_cast<const float*>(ws + oPad);
-  }
-  const void* tab = src;
   PcaProjArgs pa{};
-  pa.rows = reinterpret_cast<const float* const*>(ws + oTab);
   pa.first = 0; pa.n = (int32_t)nq; pa.chunk_rows = 0x7fffffff; pa.stride = stride; pa.dim = dim;
-  pa.mean = reinterpret_cast<const float*>(ws + oMean);
   HeadEvalArgs ea{};
   ea.n = (int32_t)nq; ea.m = m; ea.K = K; ea.lev0 = lev0;
-  ea.w = reinterpret_cast<const float*>(ws + oWk);
-  ea.z = reinterpret_cast<const float*>(ws + oZ);
-  ea.tmean = reinterpret_cast<const float*>(ws + oTmean);
-  ea.scale = reinterpret_cast<const float*>(ws + oS);
-  ea.pred = reinterpret_cast<float*>(ws + oPred);
-  ea.lev = reinterpret_cast<float*>(ws + oLev);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oW, (size_t)stride * 4, weights, (size_t)dim * 4, (size_t)dim * 4, (size_t)K, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oV, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, &tab, 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTmean, tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oS, scale, (size_t)K * m * 4, hipMemcpyHostToDevice, s);
+  CallWs ws;
+  RowStage st;  // rows of the padded width, as an index keeps them
+  float *d_W, *d_V;
+  ws.take(pa.mean, (size_t)stride); ws.take(d_W, (size_t)K * stride); ws.take(d_V, (size_t)m * stride);
+  st.take(ws, nq, dim, pitch, stride, hipMemcpyDeviceToDevice);
+  const size_t zeroed = ws.bytes();
+  ws.take(pa.rows, 1); ws.take(ea.w, (size_t)nq * K); ws.take(ea.z, (size_t)nq * m); ws.take(ea.tmean, (size_t)K); ws.take(ea.scale, (size_t)K * m);
+  ws.take(ea.pred, (size_t)nq * K); ws.take(ea.lev, (size_t)nq * K);
+  HIPCHK(h, ws.alloc());
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = st.stage_rows(src, s, false);
+  const void* tab = st.rows(src);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(pa.mean), mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d_W, (size_t)stride * 4, weights, (size_t)dim * 4, (size_t)dim * 4, (size_t)K, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d_V, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(pa.rows), &tab, 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(ea.tmean), tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(ea.scale), scale, (size_t)K * m * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {  // w: the projection on the K weight rows (the kernel takes any m)
-    pa.comp = reinterpret_cast<const float*>(ws + oW); pa.m = K; pa.coords = reinterpret_cast<float*>(ws + oWk);
+    pa.comp = d_W; pa.m = K; pa.coords = writable(ea.w);
     e = launch_pca_project(pa, s);
   }
   if (e == hipSuccess) {
-    pa.comp = reinterpret_cast<const float*>(ws + oV); pa.m = m; pa.coords = reinterpret_cast<float*>(ws + oZ);
+    pa.comp = d_V; pa.m = m; pa.coords = writable(ea.z);
     e = launch_pca_project(pa, s);
   }
   if (e == hipSuccess) e = launch_head_eval(ea, s);
   if (e == hipSuccess) e = hipMemcpyAsync(pred, ea.pred, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(lev, ea.lev, (size_t)nq * K * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   return SCANN_OK;
@@ -258,8 +235,7 @@ int scann_ridge_loo_host(const float* rows, int64_t n, int64_t dim, const float*
 
 int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float* targets, int32_t K, int64_t* n_eligible, float* mean, double* cov,
                             int32_t* col_exp, int32_t* bits) {
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_fit_moments")) return r;
   if (K < 1 || K > SCANN_HEAD_MAX_TARGETS)
     return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: K " + std::to_string(K) + " outside 1 .. " + std::to_string(SCANN_HEAD_MAX_TARGETS));
   if (!n_eligible) return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: n_eligible is null");
@@ -267,7 +243,7 @@ int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float*
   if (!cov) return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: cov is null");
   const int64_t N = pool->n;
   const int32_t dim = pool->dim, stride = pool->stride, D = dim + K;
-  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_fit_moments: the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_fit_moments", (int64_t)0x7fffffff - 1024)) return r;
   if (N == 0) {
     *n_eligible = 0;
     return fail(h, SCANN_ERR_INVALID, "scann_index_fit_moments: a covariance needs at least 2 rows, the pool has 0");
@@ -281,49 +257,23 @@ int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float*
   a.n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
   m.K = K;
   // one workspace for the call; what the memset clears comes first
-  Bump b;
-  const size_t oSt = b.take(sizeof(PcaState)), oColmax = b.take((size_t)stride * 4), oCenmax = b.take((size_t)stride * 4),
-               oSums = b.take((size_t)stride * 8), oR = b.take((size_t)stride * 8), oT = b.take((size_t)stride * stride * 8),
-               oTmax = b.take(HEAD_KMAX * 4), oTcen = b.take(HEAD_KMAX * 4), oTsum = b.take(HEAD_KMAX * 8), oRt = b.take(HEAD_KMAX * 8),
-               oTtt = b.take(HEAD_KMAX * HEAD_KMAX * 8), oTxt = b.take((size_t)stride * HEAD_KMAX * 8);
-  const size_t zeroed = b.at;
-  const size_t oMean = b.take((size_t)stride * 4), oExp = b.take((size_t)stride * 4), oCov = b.take((size_t)dim * dim * 8),
-               oTab = b.take((size_t)a.n_chunk * 8), oElig = b.take((size_t)N), oMask = b.take((size_t)N), oTg = b.take((size_t)N * K * 4),
-               oTmean = b.take(HEAD_KMAX * 4), oTexp = b.take(HEAD_KMAX * 4), oCross = b.take((size_t)D * K * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  a.st = reinterpret_cast<PcaState*>(ws + oSt);
-  a.colmax = reinterpret_cast<uint32_t*>(ws + oColmax);
-  a.cenmax = reinterpret_cast<uint32_t*>(ws + oCenmax);
-  a.sums = reinterpret_cast<unsigned long long*>(ws + oSums);
-  a.R = reinterpret_cast<unsigned long long*>(ws + oR);
-  a.T = reinterpret_cast<unsigned long long*>(ws + oT);
-  a.mean = reinterpret_cast<float*>(ws + oMean);
-  a.col_exp = reinterpret_cast<int32_t*>(ws + oExp);
-  a.cov = reinterpret_cast<double*>(ws + oCov);
-  a.rows = reinterpret_cast<const float* const*>(ws + oTab);
-  a.elig = reinterpret_cast<uint8_t*>(ws + oElig);
-  a.mask = reinterpret_cast<const uint8_t*>(ws + oMask);
-  m.t = reinterpret_cast<const float*>(ws + oTg);
-  m.tmax = reinterpret_cast<uint32_t*>(ws + oTmax);
-  m.tcen = reinterpret_cast<uint32_t*>(ws + oTcen);
-  m.tsum = reinterpret_cast<unsigned long long*>(ws + oTsum);
-  m.Rt = reinterpret_cast<unsigned long long*>(ws + oRt);
-  m.Ttt = reinterpret_cast<unsigned long long*>(ws + oTtt);
-  m.Txt = reinterpret_cast<unsigned long long*>(ws + oTxt);
-  m.tmean = reinterpret_cast<float*>(ws + oTmean);
-  m.texp = reinterpret_cast<int32_t*>(ws + oTexp);
-  m.cross = reinterpret_cast<double*>(ws + oCross);
-  std::vector<const void*> tab((size_t)a.n_chunk);
-  for (int c = 0; c < a.n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  CallWs ws;
+  ws.take(a.st, 1); ws.take(a.colmax, (size_t)stride); ws.take(a.cenmax, (size_t)stride); ws.take(a.sums, (size_t)stride); ws.take(a.R, (size_t)stride);
+  ws.take(a.T, (size_t)stride * stride); ws.take(m.tmax, HEAD_KMAX); ws.take(m.tcen, HEAD_KMAX); ws.take(m.tsum, HEAD_KMAX); ws.take(m.Rt, HEAD_KMAX);
+  ws.take(m.Ttt, HEAD_KMAX * HEAD_KMAX); ws.take(m.Txt, (size_t)stride * HEAD_KMAX);
+  const size_t zeroed = ws.bytes();
+  ws.take(a.mean, (size_t)stride); ws.take(a.col_exp, (size_t)stride); ws.take(a.cov, (size_t)dim * dim); ws.take(a.rows, (size_t)a.n_chunk);
+  ws.take(a.elig, (size_t)N); ws.take(a.mask, (size_t)N); ws.take(m.t, (size_t)N * K); ws.take(m.tmean, HEAD_KMAX); ws.take(m.texp, HEAD_KMAX);
+  ws.take(m.cross, (size_t)D * K);
+  HIPCHK(h, ws.alloc());
   PcaState st{};
   std::vector<float> mean_h((size_t)dim), tmean_h(HEAD_KMAX);
   std::vector<double> cov_h((size_t)dim * dim), cross_h((size_t)D * K);
   std::vector<int32_t> exp_h((size_t)dim), texp_h(HEAD_KMAX);
-  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, tab.data(), (size_t)a.n_chunk * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTg, targets, (size_t)N * K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = launch_head_mask(nullptr, 0, 0, a.n_total, m.t, K, reinterpret_cast<uint8_t*>(ws + oMask), s);
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = ws.upload_rows(pool, a.n_chunk, a.rows, nullptr, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(m.t), targets, (size_t)N * K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_head_mask(nullptr, 0, 0, a.n_total, m.t, K, writable(a.mask), s);
   if (e == hipSuccess) e = launch_pca_moments(a, s);
   if (e == hipSuccess) e = launch_head_moments(a, m, s);
   if (e == hipSuccess) e = hipMemcpyAsync(&st, a.st, sizeof(PcaState), hipMemcpyDeviceToHost, s);
@@ -334,7 +284,7 @@ int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float*
   if (e == hipSuccess) e = hipMemcpyAsync(texp_h.data(), m.texp, HEAD_KMAX * 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(cross_h.data(), m.cross, (size_t)D * K * 8, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   *n_eligible = st.n;
@@ -358,14 +308,13 @@ int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float*
 int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* targets, int32_t K, const float* mean, const float* tmean,
                           const float* components, int32_t m, const float* scale, const float* coef, int32_t L, float lev0, const int32_t* resid_l,
                           int64_t* n_used, double* sse, double* sae, double* sse_fit, double* dof, float* resid) {
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, "scann_index_ridge_loo: null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, "scann_index_ridge_loo: the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_ridge_loo")) return r;
   const int64_t N = pool->n;
   const int32_t dim = pool->dim, stride = pool->stride;
   const std::string bad = check_loo(dim, K, targets || N == 0, mean, tmean, components, m, scale, coef, L, lev0, resid_l, n_used, sse, sae,
                                     sse_fit, dof, resid);
   if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, "scann_index_ridge_loo: " + bad);
-  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_ridge_loo: the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_ridge_loo", (int64_t)0x7fffffff - 1024)) return r;
   const int64_t LK = (int64_t)L * K, Q = 3 * LK + L + 1, n_tile = (N + HEAD_TILE - 1) / HEAD_TILE;
   std::vector<double> q((size_t)Q, 0.0);
   if (N == 0) {
@@ -377,45 +326,31 @@ int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* t
   const int n_chunk = (int)pool->chunks.size();
   // the coordinates pass through a device block of at most 256 MiB, a group of whole tiles at a time
   const int64_t g = std::min<int64_t>(n_tile * HEAD_TILE, std::max<int64_t>(HEAD_TILE, (((int64_t)256 << 20) / ((int64_t)m * 4)) / HEAD_TILE * HEAD_TILE));
-  Bump b;
-  const size_t oMean = b.take((size_t)stride * 4), oComp = b.take((size_t)m * stride * 4);
-  const size_t zeroed = b.at;  // (the padding columns of the mean and of the components are zero)
-  const size_t oTab = b.take((size_t)n_chunk * 8), oZ = b.take((size_t)g * m * 4), oTg = b.take((size_t)N * K * 4), oTmean = b.take((size_t)K * 4),
-               oS = b.take((size_t)L * m * 4), oB = b.take((size_t)LK * m * 4), oElig = b.take((size_t)N), oRl = b.take((size_t)K * 4),
-               oRes = b.take(resid_l ? (size_t)N * K * 4 : 0), oPart = b.take((size_t)n_tile * Q * 8), oOut = b.take((size_t)Q * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  std::vector<const void*> tab((size_t)n_chunk);
-  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
   PcaProjArgs pa{};
-  pa.rows = reinterpret_cast<const float* const*>(ws + oTab);
   pa.chunk_rows = pool->chunk_rows; pa.stride = stride; pa.dim = dim; pa.m = m;
-  pa.mean = reinterpret_cast<const float*>(ws + oMean);
-  pa.comp = reinterpret_cast<const float*>(ws + oComp);
-  pa.coords = reinterpret_cast<float*>(ws + oZ);
   HeadLooArgs la{};
   la.m = m; la.L = L; la.K = K; la.lev0 = lev0;
+  double* d_out;
+  CallWs ws;
+  ws.take(pa.mean, (size_t)stride); ws.take(pa.comp, (size_t)m * stride);
+  const size_t zeroed = ws.bytes();  // (the padding columns of the mean and of the components are zero)
+  ws.take(pa.rows, (size_t)n_chunk); ws.take(pa.coords, (size_t)g * m); ws.take(la.t, (size_t)N * K); ws.take(la.tmean, (size_t)K);
+  ws.take(la.scale, (size_t)L * m); ws.take(la.coef, (size_t)LK * m); ws.take(la.elig, (size_t)N); ws.take(la.resid_l, (size_t)K);
+  ws.take(la.resid, resid_l ? (size_t)N * K : 0); ws.take(la.part, (size_t)n_tile * Q); ws.take(d_out, (size_t)Q);
+  HIPCHK(h, ws.alloc());
   la.z = pa.coords;
-  la.t = reinterpret_cast<const float*>(ws + oTg);
-  la.tmean = reinterpret_cast<const float*>(ws + oTmean);
-  la.scale = reinterpret_cast<const float*>(ws + oS);
-  la.coef = reinterpret_cast<const float*>(ws + oB);
-  la.elig = reinterpret_cast<const uint8_t*>(ws + oElig);
-  la.resid_l = resid_l ? reinterpret_cast<const int32_t*>(ws + oRl) : nullptr;
-  la.resid = resid_l ? reinterpret_cast<float*>(ws + oRes) : nullptr;
-  la.part = reinterpret_cast<double*>(ws + oPart);
-  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oComp, (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTg, targets, (size_t)N * K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTmean, tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oS, scale, (size_t)L * m * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oB, coef, (size_t)LK * m * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && resid_l) e = hipMemcpyAsync(ws + oRl, resid_l, (size_t)K * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && resid_l) e = hipMemsetAsync(ws + oRes, 0xff, (size_t)N * K * 4, s);  // NaN wherever the kernel writes nothing
-  if (e == hipSuccess)
-    e = launch_head_mask(pa.rows, pool->chunk_rows, stride, (int32_t)N, la.t, K, reinterpret_cast<uint8_t*>(ws + oElig), s);
+  if (!resid_l) la.resid_l = nullptr, la.resid = nullptr;
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(pa.mean), mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(writable(pa.comp), (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = ws.upload_rows(pool, n_chunk, pa.rows, nullptr, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(la.t), targets, (size_t)N * K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(la.tmean), tmean, (size_t)K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(la.scale), scale, (size_t)L * m * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(la.coef), coef, (size_t)LK * m * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && resid_l) e = hipMemcpyAsync(writable(la.resid_l), resid_l, (size_t)K * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && resid_l) e = hipMemsetAsync(la.resid, 0xff, (size_t)N * K * 4, s);  // NaN wherever the kernel writes nothing
+  if (e == hipSuccess) e = launch_head_mask(pa.rows, pool->chunk_rows, stride, (int32_t)N, la.t, K, writable(la.elig), s);
   for (int64_t r0 = 0; r0 < N && e == hipSuccess; r0 += g) {
     const int64_t cnt = std::min<int64_t>(g, N - r0);
     pa.first = (int32_t)r0; pa.n = (int32_t)cnt;
@@ -423,11 +358,11 @@ int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* t
     e = launch_pca_project(pa, s);
     if (e == hipSuccess) e = launch_head_loo(la, s);  // (the stream orders the next group's projection behind this group's tiles)
   }
-  if (e == hipSuccess) e = launch_head_sum(la.part, (int32_t)n_tile, (int32_t)Q, reinterpret_cast<double*>(ws + oOut), s);
-  if (e == hipSuccess) e = hipMemcpyAsync(q.data(), ws + oOut, (size_t)Q * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && resid_l) e = hipMemcpyAsync(resid, ws + oRes, (size_t)N * K * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = launch_head_sum(la.part, (int32_t)n_tile, (int32_t)Q, d_out, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(q.data(), d_out, (size_t)Q * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && resid_l) e = hipMemcpyAsync(resid, la.resid, (size_t)N * K * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   loo_outputs(q.data(), L, K, n_used, sse, sae, sse_fit, dof);
@@ -437,8 +372,8 @@ int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* t
 int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* tmean, const float* weights, int32_t K,
                      const float* components, int32_t m, const float* scale, float lev0, float* y, float* ga, float* pred, float* lev) {
   if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: null handle or batch");
-  const int dim = head_level_dim(h, level);
-  if (!dim) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  const int dim = level_dim(h, level);
+  if (!dim) return bad_level(h, level, "scann_head_batch");
   const std::string bad = check_head_eval(dim, mean, tmean, weights, K, components, m, scale, lev0, pred, lev);
   if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, "scann_head_batch: " + bad);
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_head_batch: weights not loaded");

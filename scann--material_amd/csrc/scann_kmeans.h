@@ -1,4 +1,4 @@
-// Internal declarations of the k-means clustering over a latent-space index (scann_kmeans.hip; the host half is in scann_knn.cpp); the
+// Internal declarations of the k-means clustering over a latent-space index (scann_kmeans.hip; the host half is in scann_kmeans.cpp); the
 // C ABI is include/scann_hip.h: scann_index_kmeans.
 #pragma once
 #include <hip/hip_runtime.h>

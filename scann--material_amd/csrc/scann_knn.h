@@ -32,6 +32,17 @@ namespace scann {
 int index_new_chunk(scann_handle* h, scann_index* ix, hipStream_t s);
 void index_note_rows(scann_index* ix, int64_t n, const int64_t* ids, const int32_t* atoms);
 
+// What the analyses over an index (scann_select.cpp, scann_kmeans.cpp, scann_match.cpp) use of scann_knn.cpp.  The opening checks of a
+// search ("<who>: null argument", ...; 0: fine); search: nq queries on the device ([nq][stride], padded like the rows; dqid: device [nq] or
+// null) against the whole index, synchronous -- dev_d non-null: the distances [nq][k] stay there, on the device, and nothing comes back to
+// the host; dist2_to_rows: the host twin's distance chain of one vector to n rows
+constexpr int KNN_RANGES = 1024;  // about as many row ranges, i.e. workgroups per 128 queries, as this
+int check_index(scann_handle* h, const scann_index* ix, const char* who);
+int check_k(scann_handle* h, int32_t k, const char* who);
+int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
+           int32_t* atoms, int32_t* pos, float* dev_d = nullptr);
+void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out);
+
 // One launch of knn_tile_kernel: `nq` queries against all `n_total` rows of an index, stored in chunks of `chunk_rows` rows.  Workgroup
 // (x, y, z) takes queries [128 y, 128 y + 128) and rows [x * rows_per_range, (x + 1) * rows_per_range) of chunk z and leaves the range's
 // k best under the order (dist2, position) in part_d / part_p [query][n_range][k], range = z * gridDim.x + x; unused places (and the

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_knn.h"
 #include "scann_logit.h"
 #include "scann_runtime.h"
@@ -127,19 +128,6 @@ std::string check_pass(int64_t n, int64_t dim, const int32_t* labels, int32_t C,
   return "";
 }
 
-int level_dim(const scann_handle* h, int32_t level) {
-  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
-}
-
-struct Bump {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at += align_up(bytes);
-    return o;
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -179,13 +167,12 @@ int scann_logit_pass_host(const float* rows, int64_t n, int64_t dim, const int32
 int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t* labels, int32_t C, const float* mean, const float* weights, int32_t M,
                            const int32_t* fold, int32_t F, const int32_t* prob_of_fold, int64_t* n_used, double* grad, double* stats, float* prob) {
   const std::string w = "scann_index_logit_pass: ";
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, w + "null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, w + "the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_logit_pass")) return r;
   const int64_t N = pool->n;
   const int32_t dim = pool->dim, stride = pool->stride;
   const std::string bad = check_pass(N, dim, labels, C, mean, weights, M, fold, F, prob_of_fold, n_used, grad, stats, prob);
   if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, w + bad);
-  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_logit_pass", (int64_t)0x7fffffff - 1024)) return r;
   const int64_t D1 = (int64_t)dim + 1, G = (int64_t)M * C * D1, S = (int64_t)M * 6, n_span = (N + SPAN_ROWS - 1) / SPAN_ROWS;
   std::fill(grad, grad + G, 0.0);
   std::fill(stats, stats + S, 0.0);
@@ -196,41 +183,34 @@ int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t
   const int n_chunk = (int)pool->chunks.size();
   const int per = LOGIT_COLS / C;  // models of one launch
   const int gcol = std::min(M, per) * C;
-  Bump b;
-  const size_t oMean = b.take((size_t)stride * 4), oU = b.take((size_t)M * C * stride * 4);
-  const size_t zeroed = b.at;  // (the padding columns of the mean and of the weights are zero)
-  const size_t oU0 = b.take((size_t)M * C * 4), oTab = b.take((size_t)n_chunk * 8), oLab = b.take((size_t)N * 4),
-               oGp = b.take((size_t)n_span * gcol * D1 * 8), oSp = b.take((size_t)n_span * LOGIT_GMAX * 6 * 8), oG = b.take((size_t)G * 8),
-               oS = b.take((size_t)S * 8), oUsed = b.take((size_t)n_span * 8), oProb = b.take(prob ? (size_t)N * C * 4 : 0);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  std::vector<const void*> tab((size_t)n_chunk);
-  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  LogitArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride; a.dim = dim;
+  a.C = C; a.F = F;
+  float *d_u, *d_u0;
+  double *d_grad, *d_stats;
+  CallWs ws;
+  ws.take(a.mean, (size_t)stride); ws.take(d_u, (size_t)M * C * stride);
+  const size_t zeroed = ws.bytes();  // (the padding columns of the mean and of the weights are zero)
+  ws.take(d_u0, (size_t)M * C); ws.take(a.rows, (size_t)n_chunk); ws.take(a.labels, (size_t)N); ws.take(a.gpart, (size_t)n_span * gcol * D1);
+  ws.take(a.spart, (size_t)n_span * LOGIT_GMAX * 6); ws.take(d_grad, (size_t)G); ws.take(d_stats, (size_t)S); ws.take(a.n_used, (size_t)n_span);
+  ws.take(a.prob, prob ? (size_t)N * C : 0);
+  HIPCHK(h, ws.alloc());
+  if (!prob) a.prob = nullptr;
   std::vector<float> u0((size_t)M * C);
   for (int64_t i = 0; i < (int64_t)M * C; ++i) u0[(size_t)i] = weights[i * D1 + dim];
   std::vector<int64_t> used((size_t)n_span, 0);
-  LogitArgs a{};
-  a.rows = reinterpret_cast<const float* const*>(ws + oTab);
-  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride; a.dim = dim;
-  a.labels = reinterpret_cast<const int32_t*>(ws + oLab);
-  a.mean = reinterpret_cast<const float*>(ws + oMean);
-  a.C = C; a.F = F;
-  a.gpart = reinterpret_cast<double*>(ws + oGp);
-  a.spart = reinterpret_cast<double*>(ws + oSp);
-  a.prob = prob ? reinterpret_cast<float*>(ws + oProb) : nullptr;
-  a.n_used = reinterpret_cast<int64_t*>(ws + oUsed);
-  hipError_t e = hipMemsetAsync(ws, 0, zeroed, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + oU, (size_t)stride * 4, weights, (size_t)D1 * 4, (size_t)dim * 4, (size_t)M * C, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oU0, u0.data(), (size_t)M * C * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oTab, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oLab, labels, (size_t)N * 4, hipMemcpyHostToDevice, s);
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.mean), mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d_u, (size_t)stride * 4, weights, (size_t)D1 * 4, (size_t)dim * 4, (size_t)M * C, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_u0, u0.data(), (size_t)M * C * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = ws.upload_rows(pool, n_chunk, a.rows, nullptr, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.labels), labels, (size_t)N * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && prob) e = launch_logit_fill_nan(a.prob, N * C, s);  // NaN wherever the kernel writes nothing
   for (int j0 = 0; j0 < M && e == hipSuccess; j0 += per) {  // the stream orders a group's launch behind the sums of the one before
     const int nm = std::min(per, M - j0);
     a.n_model = nm; a.ncol = nm * C;
-    a.u = reinterpret_cast<const float*>(ws + oU) + (size_t)j0 * C * stride;
-    a.u0 = reinterpret_cast<const float*>(ws + oU0) + (size_t)j0 * C;
+    a.u = d_u + (size_t)j0 * C * stride;
+    a.u0 = d_u0 + (size_t)j0 * C;
     for (int j = 0; j < LOGIT_GMAX; ++j) a.fold[j] = j < nm ? fold[j0 + j] : -1;
     for (int f = 0; f < LOGIT_CMAX; ++f) {
       const int m = prob && f < std::max(F, 1) ? prob_of_fold[f] : -1;
@@ -239,15 +219,15 @@ int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t
     e = hipMemsetAsync(a.gpart, 0, (size_t)n_span * a.ncol * D1 * 8, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.spart, 0, (size_t)n_span * nm * 6 * 8, s);
     if (e == hipSuccess) e = launch_logit_pass(a, s);
-    if (e == hipSuccess) e = launch_logit_sum(a.gpart, (int32_t)n_span, (int32_t)(a.ncol * D1), reinterpret_cast<double*>(ws + oG) + (size_t)j0 * C * D1, s);
-    if (e == hipSuccess) e = launch_logit_sum(a.spart, (int32_t)n_span, nm * 6, reinterpret_cast<double*>(ws + oS) + (size_t)j0 * 6, s);
+    if (e == hipSuccess) e = launch_logit_sum(a.gpart, (int32_t)n_span, (int32_t)(a.ncol * D1), d_grad + (size_t)j0 * C * D1, s);
+    if (e == hipSuccess) e = launch_logit_sum(a.spart, (int32_t)n_span, nm * 6, d_stats + (size_t)j0 * 6, s);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(grad, ws + oG, (size_t)G * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(stats, ws + oS, (size_t)S * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(used.data(), ws + oUsed, (size_t)n_span * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && prob) e = hipMemcpyAsync(prob, ws + oProb, (size_t)N * C * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(grad, d_grad, (size_t)G * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, (size_t)S * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(used.data(), a.n_used, (size_t)n_span * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && prob) e = hipMemcpyAsync(prob, a.prob, (size_t)N * C * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   for (int64_t i = 0; i < n_span; ++i) *n_used += used[(size_t)i];
@@ -259,7 +239,7 @@ int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level,
   const std::string w = "scann_logit_head_batch: ";
   if (!h || !db) return fail(h, SCANN_ERR_INVALID, w + "null handle or batch");
   const int dim = level_dim(h, level);
-  if (!dim) return fail(h, SCANN_ERR_INVALID, w + "level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  if (!dim) return bad_level(h, level, "scann_logit_head_batch");
   if (C < 2 || C > SCANN_LOGIT_MAX_CLASSES)
     return fail(h, SCANN_ERR_INVALID, w + "C " + std::to_string(C) + " outside 2 .. " + std::to_string(SCANN_LOGIT_MAX_CLASSES));
   if (!mean) return fail(h, SCANN_ERR_INVALID, w + "mean is null");
@@ -277,18 +257,16 @@ int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level,
   if (nq <= 0) return SCANN_OK;
   hipStream_t s = h->streams[db->last_slot];
   const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
-  Bump b;
-  const size_t oMean = b.take((size_t)dim * 4), oU = b.take((size_t)C * (dim + 1) * 4), oP = b.take((size_t)nq * C * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, b.at));
-  hipError_t e = hipMemcpyAsync(ws + oMean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + oU, weights, (size_t)C * (dim + 1) * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess)
-    e = launch_logit_eval(src, dim, (int32_t)nq, dim, reinterpret_cast<const float*>(ws + oMean), reinterpret_cast<const float*>(ws + oU), C,
-                          reinterpret_cast<float*>(ws + oP), s);
-  if (e == hipSuccess) e = hipMemcpyAsync(prob, ws + oP, (size_t)nq * C * 4, hipMemcpyDeviceToHost, s);
+  float *d_mean, *d_u, *d_prob;
+  CallWs ws;
+  ws.take(d_mean, (size_t)dim); ws.take(d_u, (size_t)C * (dim + 1)); ws.take(d_prob, (size_t)nq * C);
+  HIPCHK(h, ws.alloc());
+  hipError_t e = hipMemcpyAsync(d_mean, mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_u, weights, (size_t)C * (dim + 1) * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_logit_eval(src, dim, (int32_t)nq, dim, d_mean, d_u, C, d_prob, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(prob, d_prob, (size_t)nq * C * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   return SCANN_OK;

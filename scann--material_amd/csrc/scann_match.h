@@ -1,4 +1,4 @@
-// Internal declarations of the structure matching over a latent-space index (scann_match.hip, host side in scann_knn.cpp); the C ABI and
+// Internal declarations of the structure matching over a latent-space index (scann_match.hip, host side in scann_match.cpp); the C ABI and
 // the definition are in include/scann_hip.h (scann_index_match).
 #pragma once
 #include <hip/hip_runtime.h>

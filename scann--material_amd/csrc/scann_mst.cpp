@@ -11,6 +11,7 @@
 #include <numeric>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_knn.h"
 #include "scann_mst.h"
 #include "scann_runtime.h"
@@ -202,8 +203,7 @@ int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2
 
 int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2, int64_t* n_edges, int32_t* a, int32_t* b, float* w, int32_t* rounds) {
   const std::string who = "scann_index_mst: ";
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, who + "null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, who + "the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_mst")) return r;
   if (!n_edges) return fail(h, SCANN_ERR_INVALID, who + "n_edges is null");
   const int64_t N = pool->n;
   if (N > SCANN_MST_MAX_ROWS)
@@ -226,36 +226,22 @@ int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2, 
   t.n_total = (int32_t)N; t.chunk_rows = pool->chunk_rows; t.stride = pool->stride;
   peaks_geometry(N, N, &t.rows_per_range, &t.n_range);
   // one workspace for the call
-  const size_t b4 = align_up((size_t)N * 4), b8 = align_up((size_t)N * 8), bP = align_up((size_t)N * t.n_range * 4), bT = align_up((size_t)n_chunk * 8);
-  //   comp, core2, out_w, out_p, hi, ptr0, ptr1, edge_a, edge_b, edge_w: 10 x b4; key: b8; part_w, part_p: 2 x bP; the chunk table; counters
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, 10 * b4 + b8 + 2 * bP + bT + 256));
-  char* p = ws;
-  auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
-  int32_t* d_comp = reinterpret_cast<int32_t*>(take(b4));
-  float* d_core = reinterpret_cast<float*>(take(b4));
-  float* out_w = reinterpret_cast<float*>(take(b4));
-  int32_t* out_p = reinterpret_cast<int32_t*>(take(b4));
   MstStep c{};
-  c.n = (int32_t)N; c.comp = d_comp; c.best_w = out_w; c.best_p = out_p;
-  c.hi = reinterpret_cast<int32_t*>(take(b4));
-  c.ptr[0] = reinterpret_cast<int32_t*>(take(b4));
-  c.ptr[1] = reinterpret_cast<int32_t*>(take(b4));
-  c.edge_a = reinterpret_cast<int32_t*>(take(b4));
-  c.edge_b = reinterpret_cast<int32_t*>(take(b4));
-  c.edge_w = reinterpret_cast<float*>(take(b4));
-  c.key = reinterpret_cast<unsigned long long*>(take(b8));
-  t.part_w = reinterpret_cast<float*>(take(bP));
-  t.part_p = reinterpret_cast<int32_t*>(take(bP));
-  char* d_tab = take(bT);
-  t.rows = reinterpret_cast<const float* const*>(d_tab);
-  c.counters = reinterpret_cast<int32_t*>(take(256));  // [0] edges, [1] components, [2] tiles skipped
+  c.n = (int32_t)N;
+  float *d_core, *out_w;
+  int32_t* out_p;
+  CallWs ws;
+  ws.take(c.comp, (size_t)N); ws.take(d_core, (size_t)N); ws.take(out_w, (size_t)N); ws.take(out_p, (size_t)N); ws.take(c.hi, (size_t)N);
+  ws.take(c.ptr[0], (size_t)N); ws.take(c.ptr[1], (size_t)N); ws.take(c.edge_a, (size_t)N); ws.take(c.edge_b, (size_t)N); ws.take(c.edge_w, (size_t)N);
+  ws.take(c.key, (size_t)N); ws.take(t.part_w, (size_t)N * t.n_range); ws.take(t.part_p, (size_t)N * t.n_range); ws.take(t.rows, (size_t)n_chunk);
+  ws.take(c.counters, 64);  // [0] edges, [1] components, [2] tiles skipped
+  HIPCHK(h, ws.alloc());
+  int32_t* const d_comp = c.comp;
+  c.best_w = out_w; c.best_p = out_p;
   t.comp = d_comp; t.core2 = d_core;
   t.skipped = reinterpret_cast<unsigned int*>(c.counters + 2);
-  std::vector<const void*> tab((size_t)n_chunk);
-  for (int k = 0; k < n_chunk; ++k) tab[(size_t)k] = pool->rows_of((size_t)k);
   int32_t counters[3] = {0, 0, 0};
-  hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
+  hipError_t e = ws.upload_rows(pool, n_chunk, t.rows, nullptr, s);
   if (e == hipSuccess) e = hipMemsetAsync(c.counters, 0, 256, s);
   if (e == hipSuccess) e = core2 ? hipMemcpyAsync(d_core, core2, (size_t)N * 4, hipMemcpyHostToDevice, s) : hipMemsetAsync(d_core, 0, (size_t)N * 4, s);
   if (e == hipSuccess) e = launch_mst_eligible(t, d_comp, c.counters, s);
@@ -298,7 +284,7 @@ int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2, 
     if (e == hipSuccess) e = hipMemcpyAsync(ew.data(), c.edge_w, (size_t)m * 4, hipMemcpyDeviceToHost, s);
     e_sync = hipStreamSynchronize(s);
   }
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   if (internal) return fail(h, SCANN_ERR_UNSUPPORTED, who + "internal error: " + internal);

@@ -2,7 +2,8 @@
 // the projection (scann_moments_host, scann_project_host: the kernels' bits, scann_pca.hip) and the symmetric eigen-decomposition
 // (scann_sym_eig_host: cyclic Jacobi in fp64, the one function both the product and the tests call).  Every floating-point expression
 // here is evaluated as written, each operation rounded to nearest: the file is compiled with floating-point contraction off.  The calls
-// that touch an index or run a forward are in scann_knn.cpp, beside the index.
+// that touch an index or run a forward (scann_index_moments, scann_index_project, scann_project_batch around the kernels of scann_pca.hip)
+// are at the end of the file; the forward of scann_project_batch is forward_and_download (scann_batch.cpp), as for the index's own batch calls.
 #pragma clang fp contract(off)
 
 #include <algorithm>
@@ -13,6 +14,9 @@
 #include <vector>
 
 #include "../../include/scann_hip.h"
+#include "scann_call.h"
+#include "scann_pca.h"
+#include "scann_runtime.h"
 
 namespace {
 
@@ -219,6 +223,171 @@ int scann_sym_eig_host(const double* a, int64_t d, double* w, double* v, int32_t
     for (int64_t j = 0; j < d; ++j) v[k * d + j] = flip ? -src[j] : src[j];
   }
   return SCANN_OK;
+}
+
+}  // extern "C"
+
+// ---- the calls that touch an index or run a forward (scann_pca.hip) ----
+
+extern "C" {
+
+int scann_index_moments(scann_handle_t* h, scann_index_t* pool, int64_t* n_eligible, float* mean, double* cov, int32_t* col_exp, int32_t* bits) {
+  if (const int r = check_pool(h, pool, "scann_index_moments")) return r;
+  if (!n_eligible) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: n_eligible is null");
+  if (!mean) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: mean is null");
+  if (!cov) return fail(h, SCANN_ERR_INVALID, "scann_index_moments: cov is null");
+  const int64_t N = pool->n;
+  const int32_t dim = pool->dim, stride = pool->stride;
+  if (const int r = check_pool_rows(h, pool, "scann_index_moments", (int64_t)0x7fffffff - 1024)) return r;
+  if (N == 0) {
+    *n_eligible = 0;
+    return fail(h, SCANN_ERR_INVALID, "scann_index_moments: a covariance needs at least 2 rows, the pool has 0");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->streams[0];
+  PcaArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride; a.dim = dim;
+  a.n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
+  // one workspace for the call.  First what the memset clears: the state, the two column maxima, S, R and T; then the mean, the
+  // covariance, f, the chunk table and the eligibility bytes
+  CallWs ws;
+  ws.take(a.st, 1); ws.take(a.colmax, (size_t)stride); ws.take(a.cenmax, (size_t)stride); ws.take(a.sums, (size_t)stride); ws.take(a.R, (size_t)stride);
+  ws.take(a.T, (size_t)stride * stride);
+  const size_t zeroed = ws.bytes();
+  ws.take(a.mean, (size_t)stride); ws.take(a.col_exp, (size_t)stride); ws.take(a.cov, (size_t)dim * dim); ws.take(a.rows, (size_t)a.n_chunk);
+  ws.take(a.elig, (size_t)N);
+  HIPCHK(h, ws.alloc());
+  PcaState st{};
+  std::vector<float> mean_h((size_t)dim);
+  std::vector<double> cov_h((size_t)dim * dim);
+  std::vector<int32_t> exp_h((size_t)dim);
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = ws.upload_rows(pool, a.n_chunk, a.rows, nullptr, s);
+  if (e == hipSuccess) e = launch_pca_moments(a, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&st, a.st, sizeof(PcaState), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(mean_h.data(), a.mean, (size_t)dim * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(cov_h.data(), a.cov, (size_t)dim * dim * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(exp_h.data(), a.col_exp, (size_t)dim * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
+  ws.release();
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  *n_eligible = st.n;
+  if (st.n < 2)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_moments: a covariance needs at least 2 rows without a non-finite component, the pool has " +
+                                          std::to_string(st.n) + " among its " + std::to_string(N));
+  std::copy(mean_h.begin(), mean_h.end(), mean);
+  std::copy(cov_h.begin(), cov_h.end(), cov);
+  if (col_exp) std::copy(exp_h.begin(), exp_h.end(), col_exp);
+  if (bits) *bits = scann_pca_bits(st.n);
+  return SCANN_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the arguments of a projection onto rows of `dim` columns
+int check_projection(scann_handle* h, const char* who, int64_t dim, const float* mean, const float* components, const float* scale, int32_t m,
+                     const float* coords, const float* md2) {
+  const std::string w(who);
+  if (m < 1 || m > dim) return fail(h, SCANN_ERR_INVALID, w + ": m " + std::to_string(m) + " outside 1 .. " + std::to_string(dim));
+  if (!mean) return fail(h, SCANN_ERR_INVALID, w + ": mean is null");
+  if (!components) return fail(h, SCANN_ERR_INVALID, w + ": components is null");
+  if (!coords) return fail(h, SCANN_ERR_INVALID, w + ": coords is null");
+  if (md2 && !scale) return fail(h, SCANN_ERR_INVALID, w + ": md2 needs scale, which is null");
+  for (int64_t j = 0; j < dim; ++j)
+    if (!std::isfinite(mean[j])) return fail(h, SCANN_ERR_INVALID, w + ": mean holds a non-finite value (column " + std::to_string(j) + ")");
+  for (int64_t i = 0; i < (int64_t)m * dim; ++i)
+    if (!std::isfinite(components[i]))
+      return fail(h, SCANN_ERR_INVALID, w + ": components hold a non-finite value (component " + std::to_string(i / dim) + ", column " +
+                                            std::to_string(i % dim) + ")");
+  for (int32_t c = 0; scale && c < m; ++c)
+    if (!std::isfinite(scale[c])) return fail(h, SCANN_ERR_INVALID, w + ": scale holds a non-finite value (component " + std::to_string(c) + ")");
+  return SCANN_OK;
+}
+
+// rows [first, first + n) of the chunks in `tab` ([chunk_rows][stride] each, the padding zero) projected; the outputs are host arrays.
+// The coordinates pass through a device block of at most 256 MiB, a group of rows at a time
+int project_rows(scann_handle* h, const std::vector<const void*>& tab, int32_t chunk_rows, int32_t stride, int32_t dim, int64_t first, int64_t n,
+                 const float* mean, const float* components, const float* scale, int32_t m, float* coords, float* md2, float* dist2, hipStream_t s) {
+  if (n <= 0) return SCANN_OK;
+  const int64_t g = std::min<int64_t>(n, std::max<int64_t>(PCA_TP, (((int64_t)256 << 20) / ((int64_t)m * 4)) / PCA_TP * PCA_TP));
+  PcaProjArgs a{};
+  a.chunk_rows = chunk_rows; a.stride = stride; a.dim = dim; a.m = m;
+  CallWs ws;
+  ws.take(a.mean, (size_t)stride); ws.take(a.comp, (size_t)m * stride); ws.take(a.scale, (size_t)m);
+  const size_t zeroed = ws.bytes();  // (the padding columns of the mean and of the components are zero)
+  ws.take(a.rows, tab.size()); ws.take(a.coords, (size_t)g * m); ws.take(a.md2, (size_t)g); ws.take(a.dist2, (size_t)g);
+  HIPCHK(h, ws.alloc());
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.mean), mean, (size_t)dim * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(writable(a.comp), (size_t)stride * 4, components, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && scale) e = hipMemcpyAsync(writable(a.scale), scale, (size_t)m * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.rows), tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s);
+  if (!md2) a.md2 = nullptr;  // (the kernel writes what it is given)
+  if (!dist2) a.dist2 = nullptr;
+  for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += g) {
+    const int64_t cnt = std::min<int64_t>(g, n - r0);
+    a.first = (int32_t)(first + r0); a.n = (int32_t)cnt;
+    e = launch_pca_project(a, s);  // (the stream orders a group behind the copies of the one before)
+    if (e == hipSuccess) e = hipMemcpyAsync(coords + (size_t)r0 * m, a.coords, (size_t)cnt * m * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && md2) e = hipMemcpyAsync(md2 + r0, a.md2, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && dist2) e = hipMemcpyAsync(dist2 + r0, a.dist2, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t e_sync = hipStreamSynchronize(s);
+  ws.release();
+  HIPCHK(h, e);
+  HIPCHK(h, e_sync);
+  return SCANN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int scann_index_project(scann_handle_t* h, scann_index_t* pool, int64_t first, int64_t n, const float* mean, const float* components,
+                        const float* scale, int32_t m, float* coords, float* md2, float* dist2) {
+  if (const int r = check_pool(h, pool, "scann_index_project")) return r;
+  if (first < 0 || n < 0 || first + n > pool->n)
+    return fail(h, SCANN_ERR_INVALID, "scann_index_project: rows " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " + std::to_string(pool->n));
+  if (const int r = check_projection(h, "scann_index_project", pool->dim, mean, components, scale, m, coords, md2)) return r;
+  if (n == 0) return SCANN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<const void*> tab(pool->chunks.size());
+  for (size_t c = 0; c < tab.size(); ++c) tab[c] = pool->rows_of(c);
+  return project_rows(h, tab, pool->chunk_rows, pool->stride, pool->dim, first, n, mean, components, scale, m, coords, md2, dist2, h->streams[0]);
+}
+
+int scann_project_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* components, const float* scale,
+                        int32_t m, float* y, float* ga, float* coords, float* md2, float* dist2) {
+  if (!h || !db) return fail(h, SCANN_ERR_INVALID, "scann_project_batch: null handle or batch");
+  const int dim = level_dim(h, level);
+  if (!dim) return bad_level(h, level, "scann_project_batch");
+  if (const int r = check_projection(h, "scann_project_batch", dim, mean, components, scale, m, coords, md2)) return r;
+  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_project_batch: weights not loaded");
+  const bool atom = level == SCANN_OUT_AFTER_LC;
+  const int64_t nq = atom ? db->n_atom : db->n_struct;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
+  if (nq <= 0) return SCANN_OK;
+  hipStream_t s = h->streams[db->last_slot];
+  const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
+  const int stride = (dim + 3) / 4 * 4;
+  CallWs ws;  // rows of the padded width, as an index keeps them
+  RowStage st;
+  st.take(ws, nq, dim, dim, stride, hipMemcpyDeviceToDevice);
+  HIPCHK(h, ws.alloc());
+  const hipError_t e = st.stage_rows(src, s);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    ws.release();
+    HIPCHK(h, e);
+  }
+  const std::vector<const void*> tab(1, st.rows(src));
+  const int r = project_rows(h, tab, 0x7fffffff, stride, dim, 0, nq, mean, components, scale, m, coords, md2, dist2, s);
+  ws.release();
+  return r;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_knn.h"
 #include "scann_peaks.h"
 #include "scann_runtime.h"
@@ -78,10 +79,6 @@ __attribute__((target("avx2,fma"))) void parent_fma(const Twin& c, int64_t first
 
 bool bad_gamma(float gamma) { return !std::isfinite(gamma) || !(gamma > 0.f); }
 
-int level_dim(const scann_handle* h, int32_t level) {
-  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
-}
-
 // Enqueued on s: the sums of nq queries -- dq, device rows of the pool's stride, or null: the pool's own rows -- against the pool, left in
 // d_sums [nq]; tab: the device copy of the pool's chunk table
 hipError_t enqueue_density(const scann_index* pool, const float* const* tab, const float* dq, const int32_t* dskip, int64_t nq, float gamma,
@@ -102,24 +99,21 @@ hipError_t enqueue_density(const scann_index* pool, const float* const* tab, con
 int density_staged(scann_handle* h, scann_index* pool, const float* q, hipMemcpyKind kind, const int32_t* skip, int64_t nq, float gamma, hipStream_t s,
                    int64_t* sums) {
   const int n_chunk = (int)((pool->n + pool->chunk_rows - 1) / pool->chunk_rows);
-  const bool pad = pool->stride != pool->dim, copy = pad || kind == hipMemcpyHostToDevice;
-  const size_t bQ = copy ? align_up((size_t)nq * pool->stride * 4) : 0, bK = align_up((size_t)nq * 4), bS = align_up((size_t)nq * 8),
-               bT = align_up((size_t)std::max(n_chunk, 1) * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bQ + bK + bS + bT));
-  std::vector<const void*> tab((size_t)std::max(n_chunk, 1), nullptr);
-  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
-  hipError_t e = pad ? hipMemsetAsync(ws, 0, bQ, s) : hipSuccess;
-  if (e == hipSuccess && copy) e = hipMemcpy2DAsync(ws, (size_t)pool->stride * 4, q, (size_t)pool->dim * 4, (size_t)pool->dim * 4, (size_t)nq, kind, s);
-  if (e == hipSuccess && skip) e = hipMemcpyAsync(ws + bQ, skip, (size_t)nq * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + bQ + bK + bS, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s);
-  unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(ws + bQ + bK);
-  if (e == hipSuccess)
-    e = enqueue_density(pool, reinterpret_cast<const float* const*>(ws + bQ + bK + bS), copy ? reinterpret_cast<const float*>(ws) : q,
-                        skip ? reinterpret_cast<const int32_t*>(ws + bQ) : nullptr, nq, gamma, d_sums, s);
+  CallWs ws;
+  RowStage st;
+  int32_t* d_skip;
+  unsigned long long* d_sums;
+  const float* const* d_rows;
+  st.take(ws, nq, pool->dim, pool->dim, pool->stride, kind);
+  ws.take(d_skip, (size_t)nq); ws.take(d_sums, (size_t)nq); ws.take(d_rows, (size_t)std::max(n_chunk, 1));
+  HIPCHK(h, ws.alloc());
+  hipError_t e = st.stage_rows(q, s);
+  if (e == hipSuccess && skip) e = hipMemcpyAsync(d_skip, skip, (size_t)nq * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = ws.upload_rows(pool, n_chunk, d_rows, nullptr, s);
+  if (e == hipSuccess) e = enqueue_density(pool, d_rows, st.rows(q), skip ? d_skip : nullptr, nq, gamma, d_sums, s);
   if (e == hipSuccess) e = hipMemcpyAsync(sums, d_sums, (size_t)nq * 8, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   return SCANN_OK;
@@ -156,13 +150,12 @@ int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int
 
 int scann_index_density(scann_handle_t* h, scann_index_t* pool, const float* q, int64_t nq, const int32_t* skip_pos, float gamma, int64_t* sums) {
   const std::string w = "scann_index_density: ";
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, w + "null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, w + "the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_density")) return r;
   if (nq < 0 || nq > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_INVALID, w + "nq " + std::to_string(nq) + " outside 0 .. 2^31 - 1025");
   if (nq > 0 && !q) return fail(h, SCANN_ERR_INVALID, w + "q is null");
   if (nq > 0 && !sums) return fail(h, SCANN_ERR_INVALID, w + "sums is null");
   if (bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
-  if (pool->n > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_density", (int64_t)0x7fffffff - 1024)) return r;
   if (nq == 0) return SCANN_OK;
   if (pool->n == 0) {
     for (int64_t i = 0; i < nq; ++i) sums[i] = finite_row(q + i * pool->dim, pool->dim) ? 0 : -1;
@@ -174,11 +167,10 @@ int scann_index_density(scann_handle_t* h, scann_index_t* pool, const float* q, 
 
 int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64_t* sums, int32_t* parent, float* delta2) {
   const std::string w = "scann_index_peaks: ";
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, w + "null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, w + "the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_peaks")) return r;
   if (bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
   const int64_t N = pool->n;
-  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_peaks", (int64_t)0x7fffffff - 1024)) return r;
   if (N > 0 && !sums) return fail(h, SCANN_ERR_INVALID, w + "sums is null");
   if (N > 0 && !parent) return fail(h, SCANN_ERR_INVALID, w + "parent is null");
   if (N > 0 && !delta2) return fail(h, SCANN_ERR_INVALID, w + "delta2 is null");
@@ -191,21 +183,16 @@ int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64
   a.nq = (int32_t)N; a.gamma = gamma;
   peaks_geometry(N, N, &a.rows_per_range, &a.n_range);
   // one workspace for the call: the sums, the ranges' partial results, the merged results, the chunk table
-  const size_t bS = align_up((size_t)N * 8), bP = align_up((size_t)N * a.n_range * 4), bO = align_up((size_t)N * 4), bT = align_up((size_t)n_chunk * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bS + 2 * bP + 2 * bO + bT));
-  a.sums = reinterpret_cast<unsigned long long*>(ws);
-  a.part_d = reinterpret_cast<float*>(ws + bS);
-  a.part_p = reinterpret_cast<int32_t*>(ws + bS + bP);
-  float* out_d = reinterpret_cast<float*>(ws + bS + 2 * bP);
-  int32_t* out_p = reinterpret_cast<int32_t*>(ws + bS + 2 * bP + bO);
-  a.rows = reinterpret_cast<const float* const*>(ws + bS + 2 * bP + 2 * bO);
-  std::vector<const void*> tab((size_t)n_chunk);
-  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
+  CallWs ws;
+  float* out_d;
+  int32_t* out_p;
+  ws.take(a.sums, (size_t)N); ws.take(a.part_d, (size_t)N * a.n_range); ws.take(a.part_p, (size_t)N * a.n_range); ws.take(out_d, (size_t)N);
+  ws.take(out_p, (size_t)N); ws.take(a.rows, (size_t)n_chunk);
+  HIPCHK(h, ws.alloc());
   std::vector<int64_t> sums_h((size_t)N);  // (the outputs change only if the call succeeds)
   std::vector<int32_t> parent_h((size_t)N);
   std::vector<float> delta_h((size_t)N);
-  hipError_t e = hipMemcpyAsync(ws + bS + 2 * bP + 2 * bO, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
+  hipError_t e = ws.upload_rows(pool, n_chunk, a.rows, nullptr, s);
   if (e == hipSuccess) e = enqueue_density(pool, a.rows, nullptr, nullptr, N, gamma, a.sums, s);
   if (e == hipSuccess) e = launch_peaks_parent(a, s);
   if (e == hipSuccess) e = launch_knn_merge(a.part_d, a.part_p, (int)N, a.n_range, 1, out_d, out_p, s);  // the first under (dist2, position)
@@ -213,7 +200,7 @@ int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64
   if (e == hipSuccess) e = hipMemcpyAsync(parent_h.data(), out_p, (size_t)N * 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(delta_h.data(), out_d, (size_t)N * 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   std::copy(sums_h.begin(), sums_h.end(), sums);
@@ -226,11 +213,7 @@ int scann_index_density_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatc
   const std::string w = "scann_index_density_batch: ";
   if (!h || !idx || !db) return fail(h, SCANN_ERR_INVALID, w + "null argument");
   if (idx->h != h) return fail(h, SCANN_ERR_INVALID, w + "the index belongs to another handle");
-  const int d = level_dim(h, level);
-  if (!d) return fail(h, SCANN_ERR_INVALID, w + "level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
-  if (d != idx->dim)
-    return fail(h, SCANN_ERR_INVALID, w + "the index holds rows of " + std::to_string(idx->dim) + " columns, the model's " +
-                                          (level == SCANN_OUT_BF_PROPERTY ? "dense_out" : "global_dim") + " is " + std::to_string(d));
+  if (const int r = check_level(h, idx, level, "scann_index_density_batch")) return r;
   if (bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
   const bool atom = level == SCANN_OUT_AFTER_LC;
   const int64_t nq = atom ? db->n_atom : db->n_struct;

@@ -6,6 +6,7 @@
 
 #include <cmath>
 
+#include "scann_call.h"
 #include "scann_head.h"
 #include "scann_knn.h"
 #include "scann_rbf.h"
@@ -24,10 +25,6 @@ std::string check_landmarks(const float* landmarks, int32_t m, int64_t dim, floa
       return "landmarks hold a non-finite value (landmark " + std::to_string(i / dim) + ", column " + std::to_string(i % dim) + ")";
   if (!std::isfinite(gamma) || !(gamma > 0.f)) return "gamma must be finite and > 0";
   return "";
-}
-
-int level_dim(const scann_handle* h, int32_t level) {
-  return level == SCANN_OUT_BF_PROPERTY ? h->cfg.dense_out : level == SCANN_OUT_AFTER_LC ? h->cfg.global_dim : 0;
 }
 
 }  // namespace
@@ -72,27 +69,23 @@ int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float
   hipStream_t s = h->streams[0];
   const int32_t stride = pool->stride;
   const int n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows), n_out = (int)((N + out->chunk_rows - 1) / out->chunk_rows);
-  const size_t bL = align_up((size_t)m * stride * 4), bT = align_up((size_t)n_chunk * 8), bO = align_up((size_t)n_out * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bL + bT + bO));
+  RbfArgs a{};
+  a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride;
+  a.m = m; a.gamma = gamma;
+  a.out_chunk_rows = out->chunk_rows; a.out_stride = out->stride;
+  CallWs ws;
+  ws.take(a.lm, (size_t)m * stride);
+  const size_t zeroed = ws.bytes();  // (the landmarks' padding columns are zero)
+  ws.take(a.rows, (size_t)n_chunk); ws.take(a.out, (size_t)n_out);
+  HIPCHK(h, ws.alloc());
   int r = SCANN_OK;
   for (int c = 0; c < n_out && !r; ++c) r = index_new_chunk(h, out, s);  // the chunks an append of N rows would take, cleared
   hipError_t e = hipSuccess;
   if (!r) {
-    std::vector<const void*> tab((size_t)n_chunk), otab((size_t)n_out);
-    for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
-    for (int c = 0; c < n_out; ++c) otab[(size_t)c] = out->rows_of((size_t)c);
-    RbfArgs a{};
-    a.rows = reinterpret_cast<const float* const*>(ws + bL);
-    a.n_total = (int32_t)N; a.chunk_rows = pool->chunk_rows; a.stride = stride;
-    a.lm = reinterpret_cast<const float*>(ws);
-    a.m = m; a.gamma = gamma;
-    a.out = reinterpret_cast<float* const*>(ws + bL + bT);
-    a.out_chunk_rows = out->chunk_rows; a.out_stride = out->stride;
-    e = hipMemsetAsync(ws, 0, bL, s);  // (the landmarks' padding columns are zero)
-    if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)stride * 4, landmarks, (size_t)pool->dim * 4, (size_t)pool->dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ws + bL, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bT, otab.data(), (size_t)n_out * 8, hipMemcpyHostToDevice, s);
+    e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(writable(a.lm), (size_t)stride * 4, landmarks, (size_t)pool->dim * 4, (size_t)pool->dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = ws.upload_rows(pool, n_chunk, a.rows, nullptr, s);
+    if (e == hipSuccess) e = ws.upload_rows(out, n_out, a.out, nullptr, s);
     if (e == hipSuccess) e = launch_rbf_features(a, s);
     for (int c = 0; c < n_out && e == hipSuccess; ++c) {  // the ids travel with the rows: the pool's host copies
       const int64_t r0 = (int64_t)c * out->chunk_rows;
@@ -100,7 +93,7 @@ int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float
     }
   }
   const hipError_t e_sync = hipStreamSynchronize(s);  // the call's one wait
-  cached_free(ws);
+  ws.release();
   if (r || e != hipSuccess || e_sync != hipSuccess) {  // nothing stays allocated: out is empty again
     for (char* p : out->chunks) cached_free(p);
     out->chunks.clear();
@@ -118,7 +111,7 @@ int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, c
   const std::string w = "scann_rbf_head_batch: ";
   if (!h || !db) return fail(h, SCANN_ERR_INVALID, w + "null handle or batch");
   const int dim = level_dim(h, level);
-  if (!dim) return fail(h, SCANN_ERR_INVALID, w + "level must be SCANN_OUT_BF_PROPERTY or SCANN_OUT_AFTER_LC, got " + std::to_string(level));
+  if (!dim) return bad_level(h, level, "scann_rbf_head_batch");
   std::string bad = check_landmarks(landmarks, m, dim, gamma);
   if (bad.empty()) bad = check_head_eval(m, mean, tmean, weights, K, components, mm, scale, lev0, pred, lev);  // a head over the m features
   if (!bad.empty()) return fail(h, SCANN_ERR_INVALID, w + bad);
@@ -131,32 +124,30 @@ int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, c
   hipStream_t s = h->streams[db->last_slot];
   const float* src = atom ? db->out_z : db->out_bf;  // the level's rows where the forward left them
   const int stride = (dim + 3) / 4 * 4, ms = (m + 3) / 4 * 4;
-  const size_t bL = align_up((size_t)m * stride * 4), bP = align_up(stride != dim ? (size_t)nq * stride * 4 : 0), bF = align_up((size_t)nq * ms * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bL + bP + bF + 512));
-  float* feat = reinterpret_cast<float*>(ws + bL + bP);
-  hipError_t e = hipMemsetAsync(ws, 0, bL + bP, s);
-  if (stride != dim) {  // rows of the padded width, as an index keeps them
-    if (e == hipSuccess) e = hipMemcpy2DAsync(ws + bL, (size_t)stride * 4, src, (size_t)dim * 4, (size_t)dim * 4, (size_t)nq, hipMemcpyDeviceToDevice, s);
-    src = reinterpret_cast<const float*>(ws + bL);
-  }
-  const void* tab[2] = {src, feat};
   RbfArgs a{};
-  a.rows = reinterpret_cast<const float* const*>(ws + bL + bP + bF);
   a.n_total = (int32_t)nq; a.chunk_rows = 0x7fffffff; a.stride = stride;
-  a.lm = reinterpret_cast<const float*>(ws);
   a.m = m; a.gamma = gamma;
-  a.out = reinterpret_cast<float* const*>(ws + bL + bP + bF + 256);
   a.out_chunk_rows = 0x7fffffff; a.out_stride = ms;
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ws, (size_t)stride * 4, landmarks, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bP + bF, &tab[0], 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ws + bL + bP + bF + 256, &tab[1], 8, hipMemcpyHostToDevice, s);
+  float* feat;
+  CallWs ws;
+  RowStage st;  // rows of the padded width, as an index keeps them
+  ws.take(a.lm, (size_t)m * stride);
+  st.take(ws, nq, dim, dim, stride, hipMemcpyDeviceToDevice);
+  const size_t zeroed = ws.bytes();
+  ws.take(feat, (size_t)nq * ms); ws.take(a.rows, 1); ws.take(a.out, 1);
+  HIPCHK(h, ws.alloc());
+  hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
+  if (e == hipSuccess) e = st.stage_rows(src, s, false);
+  const void* tab[2] = {st.rows(src), feat};
+  if (e == hipSuccess) e = hipMemcpy2DAsync(writable(a.lm), (size_t)stride * 4, landmarks, (size_t)dim * 4, (size_t)dim * 4, (size_t)m, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.rows), &tab[0], 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(a.out), &tab[1], 8, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = launch_rbf_features(a, s);
   if (e == hipSuccess && phi) e = hipMemcpy2DAsync(phi, (size_t)m * 4, feat, (size_t)ms * 4, (size_t)m * 4, (size_t)nq, hipMemcpyDeviceToHost, s);
   int r = SCANN_OK;
   if (e == hipSuccess) r = head_eval_rows(h, s, feat, ms, nq, m, mean, tmean, weights, K, components, mm, scale, lev0, pred, lev);  // (waits)
   else (void)hipStreamSynchronize(s);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   return r;
 }

@@ -2,6 +2,7 @@
 // the handle's selected outputs -- its own options say so, the handle is not written -- then the maps composed per structure where the
 // forward left them (scann_rollout.hip).  The forward and its download are forward_and_download (scann_batch.cpp): y, the GlobalAttention
 // scores, the range guard and the exact re-run behave as in scann_batch_download.
+#include "scann_call.h"
 #include "scann_runtime.h"
 
 using namespace scann;
@@ -53,27 +54,24 @@ int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residua
       total += (int64_t)(mol[b + 1] - mol[b]) * (mol[b + 1] - mol[b]);
     }
   }
-  const size_t bAb = align_up((size_t)depth * std::max(E, 1) * 4), bAt = align_up((size_t)std::max(A, 1) * 4),
-               bOf = align_up((size_t)std::max(B, 1) * 8), bR = align_up((size_t)std::max<int64_t>(total, 1) * 4);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bAb + bAt + bOf + bR));
   RolloutArgs a{};
   a.mol_offset = db->mol_offset; a.edge_offset = db->edge_offset; a.edge_col = db->edge_col;
   a.n_struct = B; a.n_edge = E; a.max_atoms = db->max_atoms;
   a.num_head = c.num_head; a.head = head; a.depth = depth; a.residual = residual;
   a.attn = E > 0 ? db->out_attn : nullptr;
   a.ga = db->ga;
-  a.abar = reinterpret_cast<float*>(ws);
-  a.attribution = reinterpret_cast<float*>(ws + bAb);
-  a.roll_offset = reinterpret_cast<const int64_t*>(ws + bAb + bAt);
-  a.rollout = rollout ? reinterpret_cast<float*>(ws + bAb + bAt + bOf) : nullptr;
+  CallWs ws;
+  ws.take(a.abar, (size_t)depth * std::max(E, 1)); ws.take(a.attribution, (size_t)std::max(A, 1)); ws.take(a.roll_offset, (size_t)std::max(B, 1));
+  ws.take(a.rollout, (size_t)std::max<int64_t>(total, 1));
+  HIPCHK(h, ws.alloc());
+  if (!rollout) a.rollout = nullptr;
   hipError_t e = hipSuccess;
-  if (rollout && B > 0) e = hipMemcpyAsync(ws + bAb + bAt, off.data(), (size_t)B * 8, hipMemcpyHostToDevice, s);
+  if (rollout && B > 0) e = hipMemcpyAsync(writable(a.roll_offset), off.data(), (size_t)B * 8, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && A > 0) e = launch_rollout(a, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e == hipSuccess && A > 0 && attribution) e = hipMemcpy(attribution, a.attribution, (size_t)A * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess && total > 0) e = hipMemcpy(rollout, a.rollout, (size_t)total * 4, hipMemcpyDeviceToHost);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   return SCANN_OK;
 }

@@ -1,4 +1,4 @@
-// Internal declarations of the greedy k-center selection over a latent-space index (scann_select.hip; the host half is in scann_knn.cpp);
+// Internal declarations of the greedy k-center selection over a latent-space index (scann_select.hip; the host half is in scann_select.cpp);
 // the C ABI is include/scann_hip.h: scann_index_select.
 #pragma once
 #include <hip/hip_runtime.h>

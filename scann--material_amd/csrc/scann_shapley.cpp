@@ -1,6 +1,7 @@
 // scann_shapley (include/scann_hip.h): one forward of the resident batch, then Shapley sampling of the pooling game from the readout's
 // operands gq / gk that the forward left on the device (scann_shapley.hip).  The forward and its download are forward_and_download
 // (scann_batch.cpp), as in scann_ablate_pooling.  Every refusal comes before anything is launched.
+#include "scann_call.h"
 #include "scann_runtime.h"
 
 using namespace scann;
@@ -81,10 +82,6 @@ static int run_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, ui
   }
   if (const int r = forward_and_download(h, db, 0, 0, y, ga)) return r;
   hipStream_t st = h->streams[db->last_slot];
-  const size_t bV = align_up((size_t)P * std::max(A, 1) * 4), bG = align_up((size_t)std::max<int64_t>(total, 1) * 4),
-               bB = align_up((size_t)std::max(B, 1) * 8), bA = align_up((size_t)std::max(A, 1) * 8);
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, (perms_in ? 3 : 2) * bV + bG + 4 * bB + 2 * bA));
   ShapleyArgs a{};
   a.mol_offset = db->mol_offset; a.n_struct = B; a.n_atom = A; a.max_atoms = db->max_atoms; a.n_perm = P;
   a.dg = c.global_dim; a.dout = c.dense_out; a.use_ga_norm = c.use_ga_norm; a.relu_out = c.relu_out;
@@ -97,17 +94,14 @@ static int run_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, ui
     a.Wb = h->head.Wb; a.bb = h->head.bb; a.wo = h->head.wo; a.bo = h->head.bo;
   }
   a.seed = seed;
-  char* at = ws;
-  a.values = reinterpret_cast<float*>(at); at += bV;
-  a.perms = reinterpret_cast<int32_t*>(at); at += bV;
-  int32_t* d_in = reinterpret_cast<int32_t*>(at); at += perms_in ? bV : 0;
-  a.pair = reinterpret_cast<float*>(at); at += bG;
-  int64_t* d_off = reinterpret_cast<int64_t*>(at); at += bB;
-  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(at); at += bB;
-  a.baseline = reinterpret_cast<double*>(at); at += bB;
-  a.full = reinterpret_cast<double*>(at); at += bB;
-  a.shapley = reinterpret_cast<double*>(at); at += bA;
-  a.stderr_out = reinterpret_cast<double*>(at);
+  const size_t nV = (size_t)P * std::max(A, 1), nB = (size_t)std::max(B, 1), nA = (size_t)std::max(A, 1);
+  int32_t* d_in;
+  int64_t* d_off;
+  unsigned long long* d_keys;
+  CallWs ws;
+  ws.take(a.values, nV); ws.take(a.perms, nV); ws.take(d_in, perms_in ? nV : 0); ws.take(a.pair, (size_t)std::max<int64_t>(total, 1));
+  ws.take(d_off, nB); ws.take(d_keys, nB); ws.take(a.baseline, nB); ws.take(a.full, nB); ws.take(a.shapley, nA); ws.take(a.stderr_out, nA);
+  HIPCHK(h, ws.alloc());
   a.pair_offset = d_off;
   a.keys = keys ? d_keys : nullptr;
   a.perms_in = perms_in ? d_in : nullptr;
@@ -131,7 +125,7 @@ static int run_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, ui
   if (e == hipSuccess && A > 0 && stderr_out) e = hipMemcpy(stderr_out, a.stderr_out, (size_t)A * 8, hipMemcpyDeviceToHost);
   if (e == hipSuccess && A > 0 && values) e = hipMemcpy(values, a.values, (size_t)P * A * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess && A > 0 && perms_out) e = hipMemcpy(perms_out, a.perms, (size_t)P * A * 4, hipMemcpyDeviceToHost);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   return SCANN_OK;
 }

@@ -10,6 +10,7 @@
 #include <limits>
 #include <thread>
 
+#include "scann_call.h"
 #include "scann_knn.h"
 #include "scann_runtime.h"
 #include "scann_twin.h"
@@ -150,10 +151,9 @@ int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32
 int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t* labels, int32_t C, const int32_t* qpos, int64_t nq,
                            int32_t squared, int32_t shift, int64_t* counts, double* a, double* b, int32_t* other, int64_t* sums) {
   const std::string w = "scann_index_silhouette: ";
-  if (!h || !pool) return fail(h, SCANN_ERR_INVALID, w + "null handle or pool");
-  if (pool->h != h) return fail(h, SCANN_ERR_INVALID, w + "the pool belongs to another handle");
+  if (const int r = check_pool(h, pool, "scann_index_silhouette")) return r;
   const int64_t N = pool->n;
-  if (N > (int64_t)0x7fffffff - 1024) return fail(h, SCANN_ERR_UNSUPPORTED, w + "the pool has too many rows");
+  if (const int r = check_pool_rows(h, pool, "scann_index_silhouette", (int64_t)0x7fffffff - 1024)) return r;
   const std::string why = bad_arguments(N, labels, C, qpos, nq, shift, counts, a, b, other);
   if (!why.empty()) return fail(h, SCANN_ERR_INVALID, w + why);
   const int64_t M = qpos ? nq : N;
@@ -164,22 +164,20 @@ int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->streams[0];
   const int n_chunk = (int)((N + pool->chunk_rows - 1) / pool->chunk_rows);
-  std::vector<const void*> tab((size_t)n_chunk);
-  for (int c = 0; c < n_chunk; ++c) tab[(size_t)c] = pool->rows_of((size_t)c);
 
   // 1. which rows are eligible: the rows stay on the device, one byte per row comes back
   std::vector<unsigned char> cnt((size_t)N);
   {
-    const size_t bT = align_up((size_t)n_chunk * 8), bE = align_up((size_t)N);
-    char* ws = nullptr;
-    HIPCHK(h, cached_malloc((void**)&ws, bT + bE));
-    hipError_t e = hipMemcpyAsync(ws, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-      e = launch_sil_eligible(reinterpret_cast<const float* const*>(ws), (int32_t)N, pool->chunk_rows, pool->stride,
-                              reinterpret_cast<unsigned char*>(ws + bT), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), ws + bT, (size_t)N, hipMemcpyDeviceToHost, s);
+    const float* const* d_rows;
+    unsigned char* d_elig;
+    CallWs ws;
+    ws.take(d_rows, (size_t)n_chunk); ws.take(d_elig, (size_t)N);
+    HIPCHK(h, ws.alloc());
+    hipError_t e = ws.upload_rows(pool, n_chunk, d_rows, nullptr, s);
+    if (e == hipSuccess) e = launch_sil_eligible(d_rows, (int32_t)N, pool->chunk_rows, pool->stride, d_elig, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_elig, (size_t)N, hipMemcpyDeviceToHost, s);
     const hipError_t e_sync = hipStreamSynchronize(s);
-    cached_free(ws);
+    ws.release();
     HIPCHK(h, e);
     HIPCHK(h, e_sync);
   }
@@ -209,49 +207,43 @@ int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t
   }
   // 3. the queries in slices whose table stays within 512 MiB; everything of the call is enqueued, then one wait
   const int64_t slice = std::max<int64_t>(TILE_TQ, std::min<int64_t>(((int64_t)512 << 20) / (8 * (int64_t)C) / TILE_TQ * TILE_TQ, (M + TILE_TQ - 1) / TILE_TQ * TILE_TQ));
-  const size_t bT = align_up((size_t)n_chunk * 8), bP = align_up((size_t)std::max<int64_t>(n_perm, 1) * 4), bL = align_up(tile_label.size() * 4 + 4),
-               bC = align_up((size_t)C * 8), bQ = align_up((size_t)std::max<int64_t>(M, 1) * 4), bD = align_up((size_t)std::max<int64_t>(M, 1) * 8),
-               bS = align_up((size_t)slice * C * 8), bF = 256;
-  char* ws = nullptr;
-  HIPCHK(h, cached_malloc((void**)&ws, bT + bP + bL + bC + 3 * bQ + 2 * bD + bS + bF));
-  char* at = ws;
-  auto take = [&](size_t bytes) { char* p = at; at += bytes; return p; };
-  char *d_tab = take(bT), *d_perm = take(bP), *d_tl = take(bL), *d_counts = take(bC), *d_qp = take(bQ), *d_ql = take(bQ), *d_other = take(bQ),
-       *d_a = take(bD), *d_b = take(bD), *d_table = take(bS), *d_flag = take(bF);
+  SilArgs all{};  // the regions of the whole call; a slice's arguments start from a copy
+  all.chunk_rows = pool->chunk_rows; all.stride = pool->stride; all.n_perm = (int32_t)n_perm;
+  all.squared = squared != 0; all.shift = shift; all.C = C; all.scale = std::ldexp(1.0f, shift);
+  const size_t n_q = (size_t)std::max<int64_t>(M, 1);
+  CallWs ws;
+  ws.take(all.rows, (size_t)n_chunk); ws.take(all.perm, (size_t)std::max<int64_t>(n_perm, 1)); ws.take(all.tile_label, tile_label.size() + 1);
+  ws.take(all.counts, (size_t)C); ws.take(all.qpos, n_q); ws.take(all.qlabel, n_q); ws.take(all.other, n_q); ws.take(all.a, n_q); ws.take(all.b, n_q);
+  ws.take(all.table, (size_t)slice * C); ws.take(all.flag, 64);
+  HIPCHK(h, ws.alloc());
+  unsigned long long* const d_table = all.table;
   std::vector<double> a_h((size_t)M), b_h((size_t)M);  // (the outputs change only if the call succeeds)
   std::vector<int32_t> other_h((size_t)M);
   unsigned int flag_h = 0;
-  hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (size_t)n_chunk * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && n_perm) e = hipMemcpyAsync(d_perm, perm.data(), (size_t)n_perm * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && n_perm) e = hipMemcpyAsync(d_tl, tile_label.data(), tile_label.size() * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_counts, counts_h.data(), (size_t)C * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(d_qp, qp.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(d_ql, ql.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, s);
+  hipError_t e = ws.upload_rows(pool, n_chunk, all.rows, nullptr, s);
+  if (e == hipSuccess && n_perm) e = hipMemcpyAsync(writable(all.perm), perm.data(), (size_t)n_perm * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && n_perm) e = hipMemcpyAsync(writable(all.tile_label), tile_label.data(), tile_label.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(writable(all.counts), counts_h.data(), (size_t)C * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && M) e = hipMemcpyAsync(writable(all.qpos), qp.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && M) e = hipMemcpyAsync(writable(all.qlabel), ql.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(all.flag, 0, 4, s);
   for (int64_t q0 = 0; q0 < M && e == hipSuccess; q0 += slice) {
     const int64_t m = std::min(slice, M - q0);
-    SilArgs k{};
-    k.rows = reinterpret_cast<const float* const*>(d_tab);
-    k.chunk_rows = pool->chunk_rows; k.stride = pool->stride;
-    k.perm = reinterpret_cast<const int32_t*>(d_perm); k.tile_label = reinterpret_cast<const int32_t*>(d_tl); k.n_perm = (int32_t)n_perm;
-    k.qpos = reinterpret_cast<const int32_t*>(d_qp) + q0; k.qlabel = reinterpret_cast<const int32_t*>(d_ql) + q0;
+    SilArgs k = all;
+    k.qpos += q0; k.qlabel += q0; k.a += q0; k.b += q0; k.other += q0;
     k.nq = (int32_t)m;
     peaks_geometry(n_perm, m, &k.rows_per_range, &k.n_range);
-    k.squared = squared != 0; k.shift = shift; k.C = C; k.scale = std::ldexp(1.0f, shift);
-    k.table = reinterpret_cast<unsigned long long*>(d_table); k.counts = reinterpret_cast<const long long*>(d_counts);
-    k.flag = reinterpret_cast<unsigned int*>(d_flag);
-    k.a = reinterpret_cast<double*>(d_a) + q0; k.b = reinterpret_cast<double*>(d_b) + q0; k.other = reinterpret_cast<int32_t*>(d_other) + q0;
     e = hipMemsetAsync(d_table, 0, (size_t)m * C * 8, s);
     if (e == hipSuccess) e = launch_sil_tiles(k, s);
     if (e == hipSuccess) e = launch_sil_finish(k, s);
     if (e == hipSuccess && sums) e = hipMemcpyAsync(sums + q0 * C, d_table, (size_t)m * C * 8, hipMemcpyDeviceToHost, s);
   }
-  if (e == hipSuccess && M) e = hipMemcpyAsync(a_h.data(), d_a, (size_t)M * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(b_h.data(), d_b, (size_t)M * 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && M) e = hipMemcpyAsync(other_h.data(), d_other, (size_t)M * 4, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&flag_h, d_flag, 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && M) e = hipMemcpyAsync(a_h.data(), all.a, (size_t)M * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && M) e = hipMemcpyAsync(b_h.data(), all.b, (size_t)M * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && M) e = hipMemcpyAsync(other_h.data(), all.other, (size_t)M * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&flag_h, all.flag, 4, hipMemcpyDeviceToHost, s);
   const hipError_t e_sync = hipStreamSynchronize(s);
-  cached_free(ws);
+  ws.release();
   HIPCHK(h, e);
   HIPCHK(h, e_sync);
   if (flag_h)
