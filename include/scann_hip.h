@@ -998,6 +998,20 @@ int scann_host_copy(void* dst, const void* src, int64_t bytes);
  * edge_end.  Returns the planned edge rows per tile (32 | 64) or a negative status (text: scann_pack_last_error). */
 int scann_plan_tiles(const scann_batch_t* batch, int32_t tile_rows, int32_t tile_atoms, int32_t allow_chunks, int32_t cap,
                      int32_t* tiles_out, int32_t* part_out, int32_t* n_tiles, int32_t* n_slots);
+/* The FILLED edge-tile plan of the inference edge kernels (host only, for the same reason): a tile's atoms need not be a contiguous
+ * range of the batch.  atom_row_out[n_atom] = the caller's row of the k-th atom in TILE ORDER, a permutation that never leaves a
+ * structure (inside a structure: the remaining atom of the largest degree that still fits the open tile, the lowest row among
+ * equals; the open tile carries over into the next structure); tile_offset_out[n_atom + 1] = the CSR offsets of the atoms in that
+ * order (an atom's edges stay contiguous and in their order); tiles_out[cap][4] = atom_begin, atom_end, edge_begin, edge_end in
+ * tile-order numbering.  When that does not take FEWER tiles than scann_plan_tiles (same tile_rows, tile_atoms, chunks allowed), or
+ * the batch has an atom of more than tile_rows neighbours, the result is the identity order and the contiguous tiles.
+ * Returns 1 (filled), 0 (identity) or a negative status (text: scann_pack_last_error). */
+int scann_plan_tiles_filled(const scann_batch_t* batch, int32_t tile_rows, int32_t tile_atoms, int32_t cap, int32_t* atom_row_out,
+                            int32_t* tile_offset_out, int32_t* tiles_out, int32_t* n_tiles);
+/* Which plan the piece-major inference edge kernels run a resident batch on: out2[0] = 1 when it is the filled plan (made when the
+ * batch is forwarded a second time, unless SCANN_TILE_FILL=0 was set when the handle was created, an atom is chunked, or best fit
+ * saves no tile), out2[1] = its tiles.  scann_batch_info goes on reporting the contiguous plan. */
+int scann_batch_tile_plan(scann_handle_t* h, const scann_dbatch_t* batch, int32_t* out2);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,11 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     }
   }
   const int32_t n_big = (int32_t)big_tab.size() / 3;
+  // The piece-major inference edge kernels find a tile's atoms through per-tile slot tables (EdgeArgs::tile_atom), built behind the copy
+  // (launch_tile_order): here for the contiguous plan.  The filled plan, in which a tile's atoms need not be a contiguous range, costs
+  // the host more than one forward gains from it: it is made when the batch is forwarded AGAIN (ensure_tile_fill).
+  const bool tile_side = h->cfg.g_update && !h->generic && E > 0;
+  const size_t n_ftile = tiles.size();
   HIPCHK(h, hipSetDevice(h->device));
   scann_dbatch* db = nullptr;
   if (scratch) {
@@ -86,6 +91,7 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     cached_free(db->dbg_c);
     cached_free(db->dbg_g);
     cached_free(db->dbg_ctx);
+    cached_free(db->fill_block);
     if (db->stamps) (void)hipFree(db->stamps);
     char* const gen_ws = db->gen_ws;  // (the generic-width forward's workspace is kept across calls, like the arena below)
     const size_t gen_ws_bytes = db->gen_ws_bytes;
@@ -128,6 +134,8 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
   const size_t o_gq = take(rowA), o_gk = take(rowA), o_ga = take((size_t)A * 4), o_y = take((size_t)B * 4);
   const size_t o_pflag = take(pad ? 4 : 0);  // right behind y: fetched with the results in one copy
   const size_t o_pbuf = take((size_t)n_slot * 3 * D * 4);
+  const size_t slot_bytes = tile_side ? n_ftile * TQ * 4 : 0;
+  const size_t o_tatom = take(slot_bytes), o_te0 = take(slot_bytes), o_tsp = take(h->cfg.feature_cgcnn ? 0 : slot_bytes);
   hipError_t e = hipSuccess;
   scann_handle::Stage* stage = nullptr;
   char* img_ptr = nullptr;
@@ -222,15 +230,24 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
     pa.out_dist = (float*)(a0 + o_dist); pa.out_weight = (float*)(a0 + o_wgt);
     pa.flag = (int32_t*)(a0 + o_pflag);
   }
+  TileOrderArgs ta{};
+  if (tile_side) {
+    char* a0 = db->arena;
+    ta.tiles = (const EdgeTile*)(a0 + o_tiles); ta.n_tile = (int32_t)n_ftile; ta.n_atom = A;
+    ta.edge_offset = d_eoff; ta.atomic = h->cfg.feature_cgcnn ? nullptr : (const int32_t*)(a0 + o_atomic);
+    ta.tile_atom = (int32_t*)(a0 + o_tatom); ta.tile_edge0 = (int32_t*)(a0 + o_te0); ta.tile_species = (int32_t*)(a0 + o_tsp);
+  }
   // (the pack kernel's flag word is zeroed by edge_row_kernel, launched BEFORE it: no memset command of its own)
   if (scratch) {
     if (e == hipSuccess) e = hipMemcpyAsync(db->arena, img.data(), in_bytes, hipMemcpyHostToDevice, h->streams[0]);
     if (e == hipSuccess && (E > 0 || pad)) launch_edge_row(d_eoff, E > 0 ? A : 0, d_erow, h->streams[0], pad ? pa.flag : nullptr);
     if (e == hipSuccess && pad) launch_pack_padded(pa, h->streams[0]);
+    if (e == hipSuccess && tile_side) launch_tile_order(ta, h->streams[0]);
   } else {
     if (e == hipSuccess) e = hipMemcpyAsync(db->arena, img.data(), in_bytes, hipMemcpyHostToDevice, h->copy_stream);
     if (e == hipSuccess && (E > 0 || pad)) launch_edge_row(d_eoff, E > 0 ? A : 0, d_erow, h->copy_stream, pad ? pa.flag : nullptr);
     if (e == hipSuccess && pad) launch_pack_padded(pa, h->copy_stream);
+    if (e == hipSuccess && tile_side) launch_tile_order(ta, h->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(stage->ev, h->copy_stream);
     if (e == hipSuccess) stage->used = true;
     // a default (system-fenced) event: it orders a DMA engine's write into a REUSED arena (cached_malloc) before kernels on another
@@ -253,6 +270,13 @@ static int upload_impl(scann_handle_t* h, const scann_batch_t* b, scann_dbatch_t
   db->dist = (float*)(a0 + o_dist); db->weight = (float*)(a0 + o_wgt); db->tiles = (EdgeTile*)(a0 + o_tiles);
   db->in_off = (int32_t*)(a0 + o_inoff); db->in_edge = (int32_t*)(a0 + o_inedge);
   db->has_rev = want_rev;
+  db->n_ftile = (int32_t)n_ftile;
+  db->f_tiles = db->tiles; db->t_offset = db->edge_offset; db->t_col = db->edge_col; db->t_row = db->edge_row;
+  db->t_dist = db->dist; db->t_weight = db->weight;
+  if (tile_side) {
+    db->tile_atom = (int32_t*)(a0 + o_tatom); db->tile_edge0 = (int32_t*)(a0 + o_te0);
+    db->tile_species = h->cfg.feature_cgcnn ? nullptr : (int32_t*)(a0 + o_tsp);
+  }
   db->ring = (float*)(a0 + o_ring); db->cgcnn = (float*)(a0 + o_cg); db->c0 = (float*)(a0 + o_c0);
   db->geom = (float*)(a0 + o_geom); db->gd = (float*)(a0 + o_gd);
   db->c = (float*)(a0 + o_c); db->ctx = (float*)(a0 + o_ctx); db->P1 = (float*)(a0 + o_P1); db->P3 = (float*)(a0 + o_P3);
@@ -309,6 +333,7 @@ void free_batch(scann_dbatch* db) {
   cached_free(db->dbg_c);
   cached_free(db->dbg_g);
   cached_free(db->dbg_ctx);
+  cached_free(db->fill_block);
   if (db->stamps) (void)hipFree(db->stamps);
   if (db->upload_ev) (void)hipEventDestroy(db->upload_ev);
   delete db;
@@ -324,6 +349,63 @@ int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who) {
   HIPCHK(h, hipMemcpy(&bad, db->pack_flag, 4, hipMemcpyDeviceToHost));
   if (bad & 1) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": an unmasked neighbour slot points at a padded atom (or outside the structure)");
   if (bad & 2) return fail(h, SCANN_ERR_INVALID, std::string(who) + ": atomic number outside the embedding table (n_atoms)");
+  return SCANN_OK;
+}
+
+// The filled plan of a batch that is forwarded again (run_forward): the host plans it from the offsets read back, one block of the
+// device cache takes the plan, the tile-order copies of the edges and the slot tables, and launch_tile_order fills it on `s`, which is
+// waited for -- once per batch; the forwards that follow, on whatever stream, find the block complete.  A one-shot batch (the streamed
+// and padded calls, a dataset pass) never comes here: planning costs the host about what the plan saves the device in thirty forwards.
+int ensure_tile_fill(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s) {
+  if (db->fill_tried) return SCANN_OK;
+  db->fill_tried = true;
+  if (!h->tile_fill || !db->tile_atom || db->n_big > 0 || db->n_tile <= 1) return SCANN_OK;
+  const int32_t B = db->n_struct, A = db->n_atom, E = db->n_edge;
+  std::vector<int32_t> mol((size_t)B + 1), eoff((size_t)A + 1), atom_row, tile_offset;
+  std::vector<EdgeTile> ftiles;
+  if (db->upload_ev && !db->upload_done) HIPCHK(h, hipEventSynchronize(db->upload_ev));
+  else if (!db->upload_ev) HIPCHK(h, hipStreamSynchronize(h->streams[0]));
+  HIPCHK(h, hipMemcpy(mol.data(), db->mol_offset, mol.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(eoff.data(), db->edge_offset, eoff.size() * 4, hipMemcpyDeviceToHost));
+  const std::vector<EdgeTile> contiguous((size_t)db->n_tile);  // (its size is what the filled plan has to beat)
+  if (!plan_tiles_filled(mol.data(), B, eoff.data(), A, db->tile_rows, db->tile_atoms, contiguous, db->n_big, atom_row, tile_offset, ftiles))
+    return SCANN_OK;
+  const size_t nt = ftiles.size();
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes); return o; };
+  const size_t o_arow = take((size_t)A * 4), o_toff = take((size_t)(A + 1) * 4), o_ftiles = take(nt * sizeof(EdgeTile));
+  const size_t in_bytes = off;
+  const size_t o_tcol = take((size_t)E * 4), o_trow = take((size_t)E * 4), o_tdist = take((size_t)E * 4), o_twgt = take((size_t)E * 4);
+  const size_t o_tatom = take(nt * TQ * 4), o_te0 = take(nt * TQ * 4), o_tsp = take(db->tile_species ? nt * TQ * 4 : 0);
+  std::vector<char> img(in_bytes);
+  memcpy(img.data() + o_arow, atom_row.data(), (size_t)A * 4);
+  memcpy(img.data() + o_toff, tile_offset.data(), (size_t)(A + 1) * 4);
+  memcpy(img.data() + o_ftiles, ftiles.data(), nt * sizeof(EdgeTile));
+  char* blk = nullptr;
+  if (cached_malloc((void**)&blk, off) != hipSuccess) return SCANN_OK;  // (no room for it: the contiguous plan goes on)
+  hipError_t e = hipMemcpy(blk, img.data(), in_bytes, hipMemcpyHostToDevice);
+  TileOrderArgs ta{};
+  ta.tiles = (const EdgeTile*)(blk + o_ftiles); ta.n_tile = (int32_t)nt; ta.n_atom = A;
+  ta.atom_row = (const int32_t*)(blk + o_arow); ta.tile_offset = (const int32_t*)(blk + o_toff);
+  ta.edge_offset = db->edge_offset; ta.atomic = db->tile_species ? db->atomic : nullptr;
+  ta.col = db->edge_col; ta.dist = db->dist; ta.weight = db->weight;
+  ta.tile_atom = (int32_t*)(blk + o_tatom); ta.tile_edge0 = (int32_t*)(blk + o_te0); ta.tile_species = (int32_t*)(blk + o_tsp);
+  ta.out_col = (int32_t*)(blk + o_tcol); ta.out_row = (int32_t*)(blk + o_trow);
+  ta.out_dist = (float*)(blk + o_tdist); ta.out_weight = (float*)(blk + o_twgt);
+  if (e == hipSuccess) {
+    launch_tile_order(ta, s);
+    e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    cached_free(blk);
+    return fail(h, SCANN_ERR_HIP, std::string("filled tile plan: ") + hipGetErrorString(e));
+  }
+  db->fill_block = blk;
+  db->filled = true; db->n_ftile = (int32_t)nt;
+  db->f_tiles = (EdgeTile*)(blk + o_ftiles); db->t_offset = (int32_t*)(blk + o_toff);
+  db->t_col = ta.out_col; db->t_row = ta.out_row; db->t_dist = ta.out_dist; db->t_weight = ta.out_weight;
+  db->tile_atom = ta.tile_atom; db->tile_edge0 = ta.tile_edge0;
+  if (db->tile_species) db->tile_species = ta.tile_species;
   return SCANN_OK;
 }
 
@@ -431,6 +513,13 @@ int scann_batch_info(scann_handle_t* h, const scann_dbatch_t* db, int32_t* out8)
   if (!h || !db || !out8) return fail(h, SCANN_ERR_INVALID, "scann_batch_info: null argument");
   out8[0] = db->n_struct; out8[1] = db->n_atom; out8[2] = db->n_edge; out8[3] = db->n_big;
   out8[4] = db->n_slot; out8[5] = db->max_degree; out8[6] = db->n_tile; out8[7] = db->tile_rows;
+  return SCANN_OK;
+}
+
+int scann_batch_tile_plan(scann_handle_t* h, const scann_dbatch_t* db, int32_t* out2) {
+  if (!h || !db || !out2) return fail(h, SCANN_ERR_INVALID, "scann_batch_tile_plan: null argument");
+  out2[0] = db->filled ? 1 : 0;
+  out2[1] = db->tile_atom ? db->n_ftile : db->n_tile;
   return SCANN_OK;
 }
 

@@ -4,7 +4,8 @@
 // dropout exist), DEAD (geom' is not stored), ATTN (inference outputs: the attention weights are stored), MC (Monte Carlo dropout on the
 // attention weights with structure-local masks, scann_predict_mc), BLK (piece-major geometry
 // tiles), TEK; `a` (EdgeArgs); LDS sTile [2 TEK PLANE_STRIDE halfs],
-// sQ [TQ LDS_STRIDE], sE [NHEAD (TEK + 1)] with the index maps SE_STAT(wave, row) / SE_LOGIT(row, head), sPar [5 D], sOff [TQ + 1];
+// sQ [TQ LDS_STRIDE], sE [NHEAD (TEK + 1)] with the index maps SE_STAT(wave, row) / SE_LOGIT(row, head), sPar [5 D], sOff [TQ + 1],
+// sRow / sCen / sE0 [TQ] (BLK: the tile's slots of EdgeArgs::tile_atom / tile_cen / tile_edge0);
 // SCANN_EDGE_TIX = the edge tile of this workgroup.
   _Float16* const sH = reinterpret_cast<_Float16*>(sTile);
   _Float16* const sL = sH + TEK * PLANE_STRIDE;
@@ -73,6 +74,16 @@
     }
   }
   const int voff = ld1i(a.edge_offset, (unsigned)(tile.atom_begin + min(tid, natom)) * 4u);
+  // BLK: the tile's atoms need not be a contiguous range of the batch (the filled plan, EdgeArgs::tile_atom): slot tid of the tile's
+  // tables, parked in LDS (sRow, sCen, sE0) for the query loads, the context store and the caller's edge numbers.  Addressed by the
+  // tile's number: these loads, and the P1 rows' below, do not wait for the descriptor
+  const unsigned slot4 = ((unsigned)tix * TQ + min(tid, TQ - 1)) * 4u;
+  int trow = 0, tcen = 0, te0 = 0;
+  if constexpr (BLK) {
+    trow = ld1i(a.tile_atom, slot4);
+    if (FB) tcen = ld1i(a.tile_cen, slot4);
+    if (ATTN || MC) te0 = ld1i(a.tile_edge0, slot4);
+  }
   STAMP_IF(a.stamps, 10, threadIdx.x == 0 && nboff[0] != 0xfffffff1u);  // (diagnostic build) the neighbour indices have arrived
   const float bkc = a.p.bk[tid & (D - 1)];
   const float par0 = GUPD ? (tid < D ? a.p.lng_g : a.p.lng_b)[tid & (D - 1)] : a.p.bfg[tid & (D - 1)];
@@ -85,8 +96,11 @@
       float4 p1reg[3];  // centre thirds P1 = c_i W1 + bg of the tile's atoms
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const int idx = tid + 256 * i, la = min(idx >> 5, natom - 1), c4 = idx & 31;
-        const int arow = FB && a.species ? a.species[tile.atom_begin + la] : tile.atom_begin + la;
+        const int idx = tid + 256 * i, c4 = idx & 31;
+        [[maybe_unused]] const int la = min(idx >> 5, natom - 1);
+        int arow;
+        if constexpr (BLK) arow = ld1i(a.tile_cen, ((unsigned)tix * TQ + (idx >> 5)) * 4u);  // (idx >> 5 < TQ; slots >= natom repeat the last atom)
+        else arow = FB && a.species ? a.species[tile.atom_begin + la] : tile.atom_begin + la;
         p1reg[i] = ld4(a.P1, ((unsigned)arow * 32 + c4) * 16);
       }
       // geometry rows G of the tile's edges in the ACCUMULATOR layout, straight into registers: they stay there, exact fp32,
@@ -209,6 +223,13 @@
   }
   STAMP_IF(a.stamps, 11, threadIdx.x == 0 && (!GUPD || __float_as_uint(greg[RT - 1][3].w) != 0x7fc12345u));  // (diagnostic build) rows arrived, split, staged
   if (tid <= natom) sOff[tid] = part >= 0 ? (tid == 0 ? 0 : ne) : voff - eb;  // a chunk tile holds edges [0, ne) of its single atom
+  if constexpr (BLK) {
+    if (tid < TQ) {
+      sRow[tid] = trow;
+      if (FB) sCen[tid] = tcen;
+      if (ATTN || MC) sE0[tid] = te0;
+    }
+  }
   sPar[tid] = par0;            // g_update: gamma | beta of layer_norm_g; base: filter bias (both halves)
   sPar[2 * D + tid] = par1;    // gamma | beta of layer_norm
   if (tid < D) sPar[4 * D + tid] = bkc;
@@ -239,7 +260,8 @@
   const unsigned qoff = (tid & 31) * 16;
   // byte offset of the row of tile-local atom la (clamped by the caller) in an [n_atom,128] tensor / the per-species table
   const auto arow_off = [&](int la) __attribute__((always_inline)) {
-    return qoff + (unsigned)(FB && a.species ? a.species[tile.atom_begin + la] : tile.atom_begin + la) * (D * 4);
+    if constexpr (BLK) return qoff + (unsigned)(FB ? sCen : sRow)[la] * (D * 4);
+    else return qoff + (unsigned)(FB && a.species ? a.species[tile.atom_begin + la] : tile.atom_begin + la) * (D * 4);
   };
   float4 q0, q1, q2;
   float4 cn[RT][4];
@@ -445,10 +467,14 @@
       const int e0 = sOff[la], e1 = sOff[la + 1];
       unsigned long long mcs = 0;  // MC: the atom's structure seed, and its first edge's structure-local index minus the tile's first edge
       size_t mce = 0;
+      // the caller's number of the tile's edge n is ce + n: the attention maps and the Monte Carlo masks are keyed by it, whatever
+      // order the plan puts the atoms in (a chunk tile's plan is the identity: eb is the chunk's first edge, sE0 the atom's)
+      [[maybe_unused]] int ce = eb;
+      if constexpr (BLK && (ATTN || MC)) ce = part >= 0 ? eb : sE0[la] - e0;
       if constexpr (MC) {
-        const McRow mr = a.mc_rows[tile.atom_begin + la];
+        const McRow mr = a.mc_rows[BLK ? sRow[la] : tile.atom_begin + la];
         mcs = mc_seed(a.attn_drop_seed, a.mc_t, mr.key);
-        mce = (size_t)(eb - mr.e0);
+        mce = (size_t)(long long)(ce - mr.e0);  // (ce + n >= mr.e0 for the atom's own edges n >= e0: the sums below do not wrap)
       }
       // row maximum first (logits only), then one exp per edge: no running-maximum rescaling in the accumulation loop
       float m = -INFINITY;
@@ -483,7 +509,7 @@
                    // the head's four lanes take every fourth edge: one writer per (edge, head), 4 edges x 8 heads = 128 contiguous bytes
                    // per 32 lanes.  A chunk tile knows its own chunk's maximum and sum only: exp(e - m_chunk), finished by attn_merge_kernel
         const float rn = part >= 0 ? 1.f : __builtin_amdgcn_rcpf(ssum);
-        for (int n = e0 + (c4 & 3); n < e1; n += 4) a.attn_out[(size_t)(eb + n) * NHEAD + h] = fast_exp(sE[SE_LOGIT(n, h)] - m) * rn;
+        for (int n = e0 + (c4 & 3); n < e1; n += 4) a.attn_out[(size_t)(ce + n) * NHEAD + h] = fast_exp(sE[SE_LOGIT(n, h)] - m) * rn;
       }
       if (part >= 0) {  // chunk tile: leave the softmax state of this chunk for edge_merge_kernel
         float* pb = a.part_buf + (size_t)part * 3 * D + 4 * c4;
@@ -529,7 +555,7 @@
         const float4 be = *reinterpret_cast<const float4*>(&sPar[3 * D + 4 * c4]);
         const float4 y = make_float4(ln_apply(t[i].x, rstd, nmr, g.x, be.x), ln_apply(t[i].y, rstd, nmr, g.y, be.y),
                                      ln_apply(t[i].z, rstd, nmr, g.z, be.z), ln_apply(t[i].w, rstd, nmr, g.w, be.w));
-        st4(a.ctx, ((unsigned)(tile.atom_begin + rr) * 32 + c4) * 16, y);
+        st4(a.ctx, ((unsigned)(BLK ? sRow[rr] : tile.atom_begin + rr) * 32 + c4) * 16, y);
       }
     }
   }

@@ -230,6 +230,14 @@ struct EdgeArgs {
   const int32_t* tile_part;
   float* part_buf;
   int32_t g_update;
+  // The piece-major inference kernels (BLK: g_update, neither exact nor keep) run on the batch's TILE-ORDER side (scann_dbatch::f_tiles,
+  // scann_batch_upload): tiles, edge_offset, edge_col, edge_row, dist and edge_weight are then numbered in the order the filled plan
+  // puts the atoms in -- edge_col still holds the caller's atom rows, edge_row the tile-order index of the centre -- and every
+  // [n_atom,128] tensor, species, mc_rows and attn_out stay in the caller's order: a tile finds the caller's row of its atom in slot s
+  // in tile_atom[tile][s] (slots past its last atom repeat it), the row of the tensors c, P1, P3, q of THIS launch in tile_cen (=
+  // tile_atom, or the atomic numbers when species is set) and the atom's first edge in the caller's numbering in tile_edge0.  The tables
+  // are addressed by the tile's number alone: their loads do not wait for the tile descriptor.  Null for every other family
+  const int32_t *tile_atom, *tile_cen, *tile_edge0;  // [n_tile][TQ]
   const int32_t* edge_offset;  // [n_atom+1]
   const int32_t* edge_col;     // [n_edge]
   const int32_t* edge_row;     // [n_edge] centre atom of each edge
@@ -451,6 +459,31 @@ int plan_tiles(const int32_t* mol_offset, int32_t B, const int32_t* edge_offset,
                int tile_rows_req, int tile_atoms, bool allow_chunks, std::vector<EdgeTile>& tiles, std::vector<int32_t>& tile_part,
                std::vector<int32_t>& big_tab, std::vector<int32_t>& edge_row, int* tile_rows_out, int32_t* max_degree,
                int32_t* n_slot, std::string& err, bool fill_edge_row = true);
+// The filled plan (scann_plan_tiles_filled, include/scann_hip.h) behind `contiguous`, plan_tiles' result at `rows` edges per tile, of
+// which n_big atoms are chunked: atom_row [A], tile_offset [A + 1], tiles.  Returns whether the plan is filled (false: the identity
+// order, the offsets as they came and `contiguous`).
+bool plan_tiles_filled(const int32_t* mol_offset, int32_t B, const int32_t* edge_offset, int32_t A, int rows, int tile_atoms,
+                       const std::vector<EdgeTile>& contiguous, int32_t n_big, std::vector<int32_t>& atom_row,
+                       std::vector<int32_t>& tile_offset, std::vector<EdgeTile>& tiles);
+// The tile-order side of a batch for the piece-major inference edge kernels (scann_batch_upload, behind the input copy and the device
+// packing).  Always: the per-tile slot tables tile_atom [n_tile][TQ] = the caller's atom row of the tile's atom in slot s (slots past
+// the tile's last atom repeat it), tile_edge0 = that atom's first edge in the caller's numbering, tile_species = its atomic number
+// (with `atomic`).  With atom_row (a filled plan): the tile-order copies of the edges -- col (still the caller's atom rows), dist,
+// weight, and row = the tile-order index of the centre atom.
+struct TileOrderArgs {
+  const EdgeTile* tiles;
+  int32_t n_tile, n_atom;
+  const int32_t* atom_row;      // [n_atom] or null (identity)
+  const int32_t* tile_offset;   // [n_atom+1] offsets in tile order (with atom_row)
+  const int32_t* edge_offset;   // [n_atom+1] the caller's
+  const int32_t* atomic;        // [n_atom] or null
+  const int32_t* col;
+  const float *dist, *weight;   // [n_edge] the caller's order
+  int32_t *tile_atom, *tile_edge0, *tile_species;  // [n_tile][TQ]
+  int32_t *out_col, *out_row;
+  float *out_dist, *out_weight; // [n_edge] tile order (with atom_row)
+};
+void launch_tile_order(const TileOrderArgs& a, hipStream_t s);
 // edge_row[e] = centre atom of edge e from the CSR offsets, on the device (scann_batch_upload: behind the input copy)
 void launch_edge_row(const int32_t* edge_offset, int n_atom, int32_t* edge_row, hipStream_t s, int32_t* zero_word = nullptr);
 

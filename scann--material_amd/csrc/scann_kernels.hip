@@ -326,6 +326,8 @@ __global__ __launch_bounds__(256, RT == 2 ? 3 : 4) void edge_kernel(EdgeArgs a) 
 #endif
   __shared__ __attribute__((aligned(16))) float sPar[5 * D];          // layer_norm_g gamma/beta (base: filter bias), layer_norm gamma/beta, key bias
   __shared__ int sOff[TQ + 1];
+  // BLK: the tile's slots of the per-tile tables (EdgeArgs::tile_atom, tile_cen with FB, tile_edge0 with ATTN / MC), see the body
+  __shared__ int sRow[TQ], sCen[TQ], sE0[TQ];
 #ifdef SCANN_DIAG_OCC2  // diagnostic: two workgroups per CU instead of three (how much of the time is latency hidden by occupancy?)
   __shared__ float sDummy[7 * 1024];
   if (a.n_tile < 0) sDummy[threadIdx.x] = 1.f;
@@ -483,6 +485,35 @@ __global__ __launch_bounds__(256) void pack_padded_kernel(PackPaddedArgs a) {
 void launch_pack_padded(const PackPaddedArgs& a, hipStream_t s) {
   const int n = a.B * a.M;
   if (n > 0) hipLaunchKernelGGL(pack_padded_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+}
+
+// The tile-order side of a batch (TileOrderArgs): thread i < n_tile TQ fills slot i of the per-tile tables, thread i < n_atom (a filled
+// plan only) copies the edges of the i-th atom in tile order behind its tile-order offset.
+__global__ __launch_bounds__(256) void tile_order_kernel(TileOrderArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.n_tile * TQ) {
+    const int t = i / TQ, s = i - t * TQ;
+    const EdgeTile tile = a.tiles[t];
+    const int k = min(tile.atom_begin + s, tile.atom_end - 1);
+    const int r = a.atom_row ? a.atom_row[k] : k;
+    a.tile_atom[i] = r;
+    a.tile_edge0[i] = a.edge_offset[r];
+    if (a.atomic) a.tile_species[i] = a.atomic[r];
+  }
+  if (a.atom_row && i < a.n_atom) {
+    const int r = a.atom_row[i];
+    const int src = a.edge_offset[r], dst = a.tile_offset[i], deg = a.tile_offset[i + 1] - dst;
+    for (int n = 0; n < deg; ++n) {
+      a.out_col[dst + n] = a.col[src + n];
+      a.out_dist[dst + n] = a.dist[src + n];
+      a.out_weight[dst + n] = a.weight[src + n];
+      a.out_row[dst + n] = i;
+    }
+  }
+}
+void launch_tile_order(const TileOrderArgs& a, hipStream_t s) {
+  const int n = std::max(a.n_tile * TQ, a.atom_row ? a.n_atom : 0);
+  if (n > 0) hipLaunchKernelGGL(tile_order_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
 }
 
 void launch_edge(const EdgeArgs& a, hipStream_t s) {

@@ -284,6 +284,7 @@ int scann_create(const scann_config_t* cfg, int device_id, scann_handle_t** out)
   if (const char* xr = getenv("SCANN_XCD_REMAP")) h->xcd_remap = atoi(xr) != 0;
   if (const char* ar = getenv("SCANN_ATOM_ROWS")) h->atom_rows = atoi(ar);
   if (const char* fb = getenv("SCANN_FUSE_BASIS")) h->fuse_basis = atoi(fb) != 0;
+  if (const char* tf = getenv("SCANN_TILE_FILL")) h->tile_fill = atoi(tf) != 0;
   if (const char* st = getenv("SCANN_SPECIES_TABLES")) h->species_tables = atoi(st) != 0;
   if (const char* sg = getenv("SCANN_STRICT_RANGE")) h->strict_range = atoi(sg) != 0;
   if (const char* fe = getenv("SCANN_EXACT")) h->force_exact = atoi(fe) != 0;

@@ -125,6 +125,7 @@ struct scann_handle {
   int xcd_remap = 1;   // env SCANN_XCD_REMAP=0 disables the XCD-contiguous tile order
   int atom_rows = 0;   // env SCANN_ATOM_ROWS=32 / 64 / 96: atom tile height where the launch has that instantiation (0, anything else: launch_atom chooses)
   int fuse_basis = 1;  // env SCANN_FUSE_BASIS=0: basis_kernel writes geom0 and layer 0 reads it, as in training (A/B switch)
+  int tile_fill = 1;   // env SCANN_TILE_FILL=0: the inference edge kernels run on the contiguous tile plan (the identity order; A/B switch)
   int species_tables = 1;  // env SCANN_SPECIES_TABLES=0: the first layer's atom rows come from an atom launch, not from per-species tables
   bool generic = false;        // widths other than 128 / 8: the plain-fp32 kernels of scann_generic.hip / scann_generic_train.hip
   float* g_weights = nullptr;  // generic: the flat fp32 parameter vector on the device (spec order, spec_off offsets)
@@ -222,6 +223,18 @@ struct scann_dbatch {
   int32_t *atomic = nullptr, *mol_offset = nullptr, *edge_offset = nullptr, *edge_col = nullptr, *edge_row = nullptr;
   float *dist = nullptr, *weight = nullptr, *ring = nullptr, *cgcnn = nullptr, *c0 = nullptr;
   EdgeTile* tiles = nullptr;
+  // the tile-order side, read by the piece-major inference edge kernels alone (scann_batch_upload, launch_tile_order): their tile plan,
+  // the CSR arrays in that plan's atom order -- the arrays above when the plan is the identity (filled false) -- and the per-tile slot
+  // tables [n_ftile][TQ].  Null for a batch that never runs those kernels (base branch, generic widths, no edges)
+  bool filled = false;      // the tile-order side is the filled plan's (ensure_tile_fill: made when the batch is forwarded again)
+  bool fill_tried = false;  // ... or it has been decided that it stays the contiguous plan's
+  int64_t n_fused = 0;      // forwards of the piece-major family enqueued on the batch so far
+  char* fill_block = nullptr;  // the filled plan's arrays (one block of the device cache, freed with the batch)
+  int32_t n_ftile = 0;
+  EdgeTile* f_tiles = nullptr;
+  int32_t *t_offset = nullptr, *t_col = nullptr, *t_row = nullptr;
+  float *t_dist = nullptr, *t_weight = nullptr;
+  int32_t *tile_atom = nullptr, *tile_edge0 = nullptr, *tile_species = nullptr;
   float *keep_q = nullptr, *keep_V = nullptr, *keep_T = nullptr, *keep_ang = nullptr, *keep_K = nullptr;  // [L][rows,128], training forward (owned by the train workspace)
   float *keep_pre1 = nullptr, *keep_H1 = nullptr, *keep_T2 = nullptr;  // ResidualNorm intermediates, [L][n_atom,128]
   float *keep_preA = nullptr, *keep_z = nullptr;  // after_Lc pre-activation / output [n_atom,128]
@@ -367,6 +380,8 @@ int check_pack_flag(scann_handle_t* h, scann_dbatch_t* db, const char* who);
 // after the batch's stream has been synchronised: the forward's range guard fired -> run it again on the exact-fp32 instantiations,
 // writing the outputs the batch recorded for it (*rerun = true), unless SCANN_STRICT_RANGE asks for the error (check_range reports it)
 int rerun_if_out_of_range(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s, bool* rerun);
+// the filled tile plan of a batch that is forwarded again (scann_batch.cpp); a no-op once it has been made or decided against
+int ensure_tile_fill(scann_handle_t* h, scann_dbatch_t* db, hipStream_t s);
 // One inference forward of a resident batch on its last_slot stream, writing `layers` / `flags` besides the handle's selected outputs,
 // and its results fetched as scann_batch_download fetches them (pack flag, range guard, exact re-run, db->idle); y / ga: host, or null
 int forward_and_download(scann_handle_t* h, scann_dbatch_t* db, uint64_t layers, int32_t flags, float* y, float* ga);

@@ -101,6 +101,8 @@ SYMBOLS = [
     ("scann_slice_count", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("scann_slice_batch", C.c_int, [_P] * 8 + [C.c_int32, C.c_int64] + [_P] * 7),
     ("scann_plan_tiles", C.c_int, [C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("scann_plan_tiles_filled", C.c_int, [C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
+    ("scann_batch_tile_plan", C.c_int, [_P, _P, _P]),
     ("scann_exact_reruns", C.c_int64, [_P]),
     ("scann_device_memory", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("scann_batch_info", C.c_int, [_P, _P, _P]),
@@ -1062,6 +1064,8 @@ def load_library(path=None):
     _check_runtime_env()
     lib = C.CDLL(p)
     for name, res, args in SYMBOLS:
+        if name in ("scann_plan_tiles_filled", "scann_batch_tile_plan") and os.environ.get("SCANN_HIP_LIB") and not hasattr(lib, name):
+            continue  # (an earlier commit's library, named for an A/B run -- tools/ab_bits.py, tools/ab_libs.sh: it has no filled plan)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1241,6 +1245,23 @@ def plan_tiles(packed, tile_rows=64, tile_atoms=24, allow_chunks=True):
     if rc < 0:
         raise ScannHipError(rc, (lib.scann_pack_last_error() or b"").decode())
     return rc, tiles[:nt.value].copy(), part[:nt.value].copy(), ns.value
+
+
+def plan_tiles_filled(packed, tile_rows=64, tile_atoms=24):
+    """The filled edge-tile plan of the inference edge kernels for `packed` (host only, scann_plan_tiles_filled):
+    (filled, atom_row[n_atom], tile_offset[n_atom + 1], tiles[n,4]) -- atom_row[k] = the caller's row of the k-th atom in tile order,
+    tile_offset the CSR offsets in that order, the tiles in tile-order numbering; filled False: the identity order and the tiles of
+    plan_tiles."""
+    lib = load_library()
+    cap = packed.n_atom + packed.n_edge // 32 + 2
+    atom_row, tile_offset = np.empty(packed.n_atom, np.int32), np.empty(packed.n_atom + 1, np.int32)
+    tiles = np.empty((cap, 4), np.int32)
+    nt = C.c_int32(0)
+    st = packed.as_struct()
+    rc = lib.scann_plan_tiles_filled(C.byref(st), tile_rows, tile_atoms, cap, _ptr(atom_row), _ptr(tile_offset), _ptr(tiles), C.byref(nt))
+    if rc < 0:
+        raise ScannHipError(rc, (lib.scann_pack_last_error() or b"").decode())
+    return bool(rc), atom_row, tile_offset, tiles[:nt.value].copy()
 
 
 def slice_dataset(ds_mol_offset, ds_edge_offset, ds_atomic, ds_ring, ds_edge_local, ds_edge_dist, ds_edge_weight, sel):
@@ -1609,6 +1630,13 @@ class Engine:
         self._check(self.lib.scann_batch_info(self._h, rb._h, _ptr(out)))
         keys = ("structs", "atoms", "edges", "big_atoms", "merge_slots", "max_degree", "tiles", "tile_rows")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def tile_plan(self, rb):
+        """(filled, tiles) of the plan the inference edge kernels run the resident batch on (scann_batch_tile_plan): the filled plan
+        is made when a batch is forwarded a second time"""
+        out = np.zeros(2, dtype=np.int32)
+        self._check(self.lib.scann_batch_tile_plan(self._h, rb._h, _ptr(out)))
+        return bool(out[0]), int(out[1])
 
     def num_streams(self):
         return self.lib.scann_num_streams(self._h)
