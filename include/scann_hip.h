@@ -916,6 +916,45 @@ int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32
                           int32_t squared, int32_t shift, int32_t threads, int64_t* counts, double* a, double* b, int32_t* other,
                           int64_t* sums);
 
+/* ---- Exact neighbour ranks of an index ----
+ * Whether a map of the rows -- the principal-component map, the neighbour embedding -- can be believed is a question about ranks
+ * (trustworthiness and continuity: Venna & Kaski, ICANN 2001; the co-ranking framework: Lee & Verleysen, Neurocomputing 72, 1431, 2009):
+ * how far down row i's ranking in one space do its neighbours in the other space sit.  The one primitive all these scores need is the
+ * rank of row j among all rows, seen from row i: an exact O(N^2 dim) self-join of the index, and a count of integers, so it is defined to
+ * the bit without any summation order.  The scores themselves are host work on top of it (LatentIndex.map_quality,
+ * LatentIndex.choose_perplexity).
+ *   Eligibility: a row is eligible iff all its components are finite (the rule of scann_index_select, scann_index_peaks and
+ *     scann_index_silhouette).
+ *   Key: for an eligible query i (a row of the pool, by position) and an eligible row l != i,  d(i, l) = dist2(row_i, row_l), exactly
+ *     the chain of scann_knn_distsq with row i as q.  Two finite rows never give NaN; +inf is an ordinary value.  The key of l seen from i
+ *     is (d(i, l), l) under the search's total order: dist2 ascending, then position ascending.
+ *   Rank: for a probe j = probe[i * m + p] that is eligible and != i,  rank[i * m + p] = the number of eligible rows l != i whose key is
+ *     strictly less than j's key -- the nearest other row has rank 0 -- and dist2[i * m + p] = d(i, j).
+ *   No rank: a probe that is -1, equals i, is ineligible or belongs to an ineligible query gets rank -1 and dist2 +inf.
+ *   Probe lists may repeat a position and need no order; equal probes get equal ranks.
+ * qpos: host [nq] positions 0 .. N - 1 in any order, repeats allowed, or NULL: all N rows in position order (nq is then ignored).
+ * probe: host [nq * m], 1 <= m <= SCANN_RANKS_MAX_PROBES.  rank [nq * m]; dist2 [nq * m] or NULL.
+ * Consequences: the result is a function of the pool's contents and the arguments only -- it does not depend on the chunking, on how
+ * many add calls built the index, on the launch geometry, on the query slicing or on a thread count; a qpos subset gives the rows of the
+ * full answer; the row at place p of query i's leave-self-out answer from scann_index_query has rank p; probing all other rows of an
+ * eligible query yields a permutation of 0 .. n_eligible - 2.
+ * The call is synchronous with one host wait, the rows never leave the device, and the queries are taken in slices of
+ * SCANN_RANKS_SLICE; it changes nothing in the pool, the handle's weights, the training state or the selected outputs and works on
+ * inference, training, generic-width and exact-fp32 handles and on an index of any dim 1 .. 1024 (a 2-column index of map coordinates
+ * is a first-class use).  SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null argument, m
+ * outside 1 .. SCANN_RANKS_MAX_PROBES, a qpos outside 0 .. N - 1 or a probe outside -1 .. N - 1 (the entry is named), a pool of another
+ * handle.  An empty pool returns SCANN_OK.
+ * scann_ranks_host (rows [n * dim]; no GPU work) is the twin: the same bits, threaded over the queries -- `threads` > 0 fixes the
+ * thread count, 0 leaves it to the call (at most 16); the result does not depend on it. */
+#define SCANN_RANKS_MAX_PROBES 32
+#define SCANN_RANKS_SLICE 262144
+int scann_index_ranks(scann_handle_t* h, scann_index_t* pool,
+                      const int32_t* qpos /* host [nq] positions, or NULL: all N rows, nq ignored */, int64_t nq,
+                      const int32_t* probe /* host [nq * m] positions, -1: unused */, int32_t m,
+                      int32_t* rank /* [nq * m] */, float* dist2 /* [nq * m] or NULL */);
+int scann_ranks_host(const float* rows, int64_t n, int64_t dim, const int32_t* qpos, int64_t nq, const int32_t* probe, int32_t m,
+                     int32_t threads, int32_t* rank, float* dist2);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

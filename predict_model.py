@@ -54,6 +54,10 @@ entropy) as ``class_head_<target>.pickle``.
 dataset's rows in two dimensions, the pair repulsion computed exactly on the GPU and the map bit-reproducible.  It prints the divergence
 before and after, pickles the result (coordinates, ids, atoms, neighbour lists) as ``embedding_<target>.pickle`` and, with ``--embed-out``,
 saves the map as a ``LatentEmbedding`` (.npz) for ``SCANN.place``.
+``--map-quality K`` adds to what ``--embed`` or ``--project 2`` prints and pickles whether the map can be believed: trustworthiness,
+continuity and the neighbourhood overlap at K neighbours, from exact neighbour ranks computed on the GPU (key "quality" of the pickle).
+``--embed-sweep 5,10,15`` draws the map at every perplexity of the list, scores each and the linear map beside them, prints the table,
+pickles it as ``embed_sweep_<target>.pickle`` and, with ``--embed-out``, saves the map with the greatest neighbourhood overlap.
 ``--peaks K [--peaks-level atom|structure] [--peaks-bandwidth H] [--peaks-out FILE]`` clusters the dataset's atoms (or structures) by
 density peaks -- no round clusters are assumed; both passes over all pairs run on the GPU, bit-reproducible --, prints the bandwidth, the
 leading decision values and each cluster's size and centre, pickles the result as ``peaks_<target>.pickle`` and, with ``--peaks-out``,
@@ -145,7 +149,7 @@ def main(args):
     head_targets = check_head_flags(args)
     kernel_head_targets = check_kernel_head_flags(args)
     class_labels = check_class_head_flags(args)
-    check_embed_flags(args)
+    embed_sweep = check_embed_flags(args)
     check_peaks_flags(args)
     check_hierarchy_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
@@ -322,6 +326,8 @@ def main(args):
         res["id"], res["atom"] = pool.names()
         print("n_rows %d, rank %d, total variance %.6g, explained variance ratio %s" % (
             res["n_rows"], res["rank"], res["total_variance"], " ".join("%.4f" % r for r in res["explained_variance_ratio"])))
+        if args.map_quality and args.project == 2:
+            res["quality"] = print_map_quality(scann, pool, res["coordinates"], args.map_quality, "--project")
         pickle.dump(res, open(os.path.join(args.trained_model, "projection_{}.pickle".format(target)), "wb"))
         if args.project_out:
             projection.save(args.project_out)
@@ -422,10 +428,30 @@ def main(args):
         res["id"], res["atom"] = pool.names()
         print("n_rows %d, %d edges, learning rate %g: kl %.6f -> %.6f, z %.6g" % (
             len(emb), res["n_edges"], res["learning_rate"], res["kl_init"], res["kl"], res["z"]))
+        if args.map_quality:
+            res["quality"] = print_map_quality(scann, pool, res, args.map_quality, "--embed")
         pickle.dump(res, open(os.path.join(args.trained_model, "embedding_{}.pickle".format(target)), "wb"))
         if args.embed_out:
             emb.save(args.embed_out)
         pool.free()
+    if embed_sweep:
+        pool = scann.build_index(data, level=args.embed_level, ids=data.indexes)
+        print("Choose the perplexity of the map of the dataset's %d rows (%s level) among %s" % (len(pool), args.embed_level, embed_sweep))
+        try:
+            table, emb = scann.choose_perplexity(pool, embed_sweep, k=args.map_quality or 15)
+        except ValueError as e:
+            raise SystemExit("--embed-sweep: %s" % e) from None
+        finally:
+            pool.free()
+        print("perplexity  neighbour overlap  trustworthiness  continuity      LCMC  R_NX area        kl")
+        for i, p in enumerate(table["perplexity"]):
+            print("%10s  %17.6f  %15.6f  %10.6f  %8.6f  %9.6f  %8.6f" % (p if isinstance(p, str) else "%g" % p, table["neighbour_overlap"][i],
+                                                                        table["trustworthiness"][i], table["continuity"][i], table["lcmc"][i],
+                                                                        table["rnx_auc"][i], table["kl"][i]))
+        print("best perplexity %g" % table["best_perplexity"])
+        pickle.dump(table, open(os.path.join(args.trained_model, "embed_sweep_{}.pickle".format(target)), "wb"))
+        if args.embed_out:
+            emb.save(args.embed_out)
     if args.peaks:
         pool = scann.build_index(data, level=args.peaks_level, ids=data.indexes)
         print("Density peaks of the dataset's %d rows (%s level), %d clusters" % (len(pool), args.peaks_level, args.peaks))
@@ -571,12 +597,40 @@ def density_records(scann, data, index, bandwidth):
     return per
 
 
+def print_map_quality(scann, pool, coords, k, flag):
+    """--map-quality: the scores of a map of ``pool``'s rows, printed; the dict that goes into the pickle"""
+    graph = (coords["neighbor_position"], coords["neighbor_dist2"]) if isinstance(coords, dict) else None  # (--embed has searched already)
+    try:
+        q = scann.map_quality(pool, coords, k=k, graph=graph)
+    except ValueError as e:
+        pool.free()
+        raise SystemExit("--map-quality (%s): %s" % (flag, e)) from None
+    print("map quality at k = %d: trustworthiness %.6f, continuity %.6f, neighbour overlap %.6f, LCMC %.6f, R_NX area %.6f" % (
+        q["k"], q["trustworthiness"], q["continuity"], q["neighbour_overlap"], q["lcmc"], q["rnx_auc"]))
+    return q
+
+
 def check_embed_flags(args):
-    """--embed and its companions checked before anything is loaded"""
-    if args.embed_out and not args.embed:
+    """--embed and its companions checked before anything is loaded; the perplexities of --embed-sweep, or None"""
+    if args.embed_out and not (args.embed or args.embed_sweep):
         raise SystemExit("--embed-out: needs --embed")
     if args.embed and not 2 <= args.embed_perplexity <= 15:
         raise SystemExit("--embed-perplexity: P must lie in 2 .. 15, got %g" % args.embed_perplexity)
+    if args.map_quality and not 1 <= args.map_quality <= 31:
+        raise SystemExit("--map-quality: K must lie in 1 .. 31, got %d" % args.map_quality)
+    if args.map_quality and not (args.embed or args.embed_sweep or args.project == 2):
+        raise SystemExit("--map-quality: needs --embed, --embed-sweep or --project 2")
+    if args.embed and args.embed_sweep:
+        raise SystemExit("--embed-sweep: draws its own maps, leave --embed out")
+    if not args.embed_sweep:
+        return None
+    try:
+        ps = [float(p) for p in args.embed_sweep.split(",")]
+    except ValueError:
+        raise SystemExit("--embed-sweep: a comma-separated list of perplexities, got %r" % args.embed_sweep) from None
+    if any(not 2 <= p <= 15 for p in ps) or any(b <= a for a, b in zip(ps, ps[1:])):
+        raise SystemExit("--embed-sweep: ascending distinct perplexities in 2 .. 15, got %r" % args.embed_sweep)
+    return ps
 
 
 def check_class_head_flags(args):
@@ -831,6 +885,12 @@ def parser():
                    help="rows to embed: one per structure (bf_property) or one per atom (after_Lc)")
     p.add_argument("--embed-perplexity", type=float, default=10.0, metavar="P", help="perplexity of --embed (2 .. 15)")
     p.add_argument("--embed-out", type=str, default="", help="save the map as a LatentEmbedding (.npz) for SCANN.place")
+    p.add_argument("--map-quality", type=int, default=0, metavar="K",
+                   help="score the map of --embed, --embed-sweep or --project 2 at K neighbours (1 .. 31): trustworthiness, continuity and "
+                        "neighbourhood overlap from exact neighbour ranks on the GPU")
+    p.add_argument("--embed-sweep", type=str, default="", metavar="P1,P2,...",
+                   help="choose the perplexity: draw the map at every perplexity of the list, score each (at --map-quality K, default 15) "
+                        "and the linear map, pickle embed_sweep_<target>.pickle")
     p.add_argument("--with", dest="with_models", type=str, default="",
                    help="comma-separated trained model folders of the same architecture, run in one model set with this one")
     return p

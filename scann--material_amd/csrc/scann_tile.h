@@ -1,7 +1,7 @@
 // The slab pipeline of the tiled passes over a latent-space index, once: the tile constants, the LDS layout of a staged slab, the inner
 // column loop on a lane's register block and the ways a finished block leaves the registers.  The kernels that are built from it
 // (knn_tile_kernel, match_tile_kernel, kmeans_assign_kernel, rbf_feature_kernel, logit_pass_kernel, pca_project_kernel,
-// peaks_tile_kernel, mst_tile_kernel, sil_tile_kernel) keep what is their own: what they fetch and by which rule, the step loop with
+// peaks_tile_kernel, mst_tile_kernel, sil_tile_kernel, ranks_tile_kernel) keep what is their own: what they fetch and by which rule, the step loop with
 // its barriers, and the epilogue.
 //
 // The chain.  Every result of these passes is defined to the bit (include/scann_hip.h) by one fp32 chain per pair, columns ascending:

@@ -174,6 +174,8 @@ SYMBOLS = [
     ("scann_mst_last_rounds", C.c_int, [C.c_int32, _P, _P, _P, _P]),
     ("scann_index_silhouette", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("scann_silhouette_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("scann_index_ranks", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
+    ("scann_ranks_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -960,6 +962,67 @@ def silhouette_host(rows, labels, n_clusters=None, qpos=None, metric="euclidean"
         raise ScannHipError(rc, "scann_silhouette_host: a term is not finite or above 2^31 at shift %d: lower the shift" % shift)
     if rc < 0:
         raise ValueError("silhouette_host: invalid arguments (%d)" % rc)
+    return out
+
+
+# the neighbour ranks: probes per query (SCANN_RANKS_MAX_PROBES) and queries per slice of the device call (SCANN_RANKS_SLICE)
+RANKS_MAX_PROBES = 32
+RANKS_SLICE = 262144
+
+
+def check_ranks_args(probe, n_rows, qpos):
+    """(probe int32 [nq, m], qpos int32 [nq] or None) of a rank pass as the C calls take them; ValueError otherwise, naming the
+    argument.  ``probe`` holds positions, -1 for an unused place; ``qpos`` None: every row in position order."""
+    n_rows = int(n_rows)
+    if qpos is not None:
+        try:
+            qpos = np.ascontiguousarray(qpos)
+        except (TypeError, ValueError):
+            raise ValueError("qpos must be an array of positions") from None
+        if qpos.dtype.kind not in "iu" or qpos.ndim != 1:
+            raise ValueError("qpos must be a one-dimensional array of integer positions, got %s of shape %s" % (qpos.dtype, qpos.shape))
+        if qpos.size and (int(qpos.min()) < 0 or int(qpos.max()) >= n_rows):
+            bad = int(np.flatnonzero((qpos < 0) | (qpos >= n_rows))[0])
+            raise ValueError("qpos[%d] = %d outside 0 .. %d" % (bad, int(qpos[bad]), n_rows - 1))
+        qpos = np.ascontiguousarray(qpos, dtype=np.int32)
+    nq = n_rows if qpos is None else qpos.shape[0]
+    try:
+        probe = np.ascontiguousarray(probe)
+    except (TypeError, ValueError):
+        raise ValueError("probe must be an array of positions") from None
+    if probe.dtype.kind not in "iu" or probe.ndim != 2 or probe.shape[0] != nq:
+        raise ValueError("probe must hold integer positions of shape [%d, m], got %s of shape %s" % (nq, probe.dtype, probe.shape))
+    if not 1 <= probe.shape[1] <= RANKS_MAX_PROBES:
+        raise ValueError("m %d outside 1 .. %d: probe has shape %s" % (probe.shape[1], RANKS_MAX_PROBES, probe.shape))
+    if probe.size and (int(probe.min()) < -1 or int(probe.max()) >= n_rows):
+        flat = probe.reshape(-1)
+        bad = int(np.flatnonzero((flat < -1) | (flat >= n_rows))[0])
+        raise ValueError("probe[%d] = %d outside -1 .. %d" % (bad, int(flat[bad]), n_rows - 1))
+    return np.ascontiguousarray(probe, dtype=np.int32), qpos
+
+
+def _ranks_out(shape, dist2):
+    out = {"rank": np.full(shape, -1, np.int32)}
+    if dist2:
+        out["dist2"] = np.full(shape, np.inf, np.float32)
+    return out
+
+
+def ranks_host(rows, probe, qpos=None, threads=0, dist2=False):
+    """The exact neighbour ranks over ``rows`` [n, dim] on the host with the kernels' bits (scann_ranks_host, the definition in
+    include/scann_hip.h): {"rank" int32 [nq, m], with ``dist2`` "dist2" fp32 [nq, m]}; rank -1 and dist2 +inf where a probe has no
+    rank.  ``qpos`` None: every row in position order.  ``threads`` 0: the call's own choice."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("ranks_host: rows of shape %s" % (rows.shape,))
+    probe, qpos = check_ranks_args(probe, rows.shape[0], qpos)
+    if isinstance(threads, bool) or not isinstance(threads, (int, np.integer)) or not 0 <= int(threads) <= 256:
+        raise ValueError("threads must be an integer in 0 .. 256, got %r" % (threads,))
+    out = _ranks_out(probe.shape, dist2)
+    rc = int(load_library().scann_ranks_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(qpos), probe.shape[0], _ptr(probe), probe.shape[1],
+                                             int(threads), _ptr(out["rank"]), _ptr(out.get("dist2"))))
+    if rc < 0:
+        raise ValueError("ranks_host: invalid arguments (%d)" % rc)
     return out
 
 
@@ -2076,6 +2139,14 @@ class Engine:
         out = _silhouette_out(nq, C_, table)
         self._check(self.lib.scann_index_silhouette(self._h, ix._h, _ptr(labels), C_, _ptr(qpos), nq, squared, shift, _ptr(out["count"]),
                                                     _ptr(out["a"]), _ptr(out["b"]), _ptr(out["other"]), _ptr(out.get("sums"))))
+        return out
+
+    def index_ranks(self, ix, probe, qpos=None, dist2=False):
+        """The exact neighbour ranks over the rows of ``ix`` on the device (scann_index_ranks): ``ranks_host``'s dict, bit for bit."""
+        probe, qpos = check_ranks_args(probe, len(ix), qpos)
+        out = _ranks_out(probe.shape, dist2)
+        self._check(self.lib.scann_index_ranks(self._h, ix._h, _ptr(qpos), probe.shape[0], _ptr(probe), probe.shape[1], _ptr(out["rank"]),
+                                               _ptr(out.get("dist2"))))
         return out
 
     def density_batch(self, ix, rb, level, gamma):

@@ -461,7 +461,7 @@ class LatentIndex:
         fit = class_head_fit(run_pass, mo, lab, len(classes), grid, folds, max_iter, tol)
         return class_head_result(fit, lab, classes, self.level, self.dim)
 
-    def embed(self, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", route="device"):
+    def embed(self, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", route="device", graph=None):
         """The neighbour embedding (t-SNE) of this index's rows in two dimensions: the map that keeps neighbourhoods, where ``pca`` draws
         the linear one.  The repulsion between all pairs of rows is computed exactly on the GPU (scann_embed_iterate), so the map depends
         on the index contents and the arguments only, bit for bit.  Each row's 31 nearest other rows come from the index's exact search
@@ -473,7 +473,9 @@ class LatentIndex:
         over the stored edges, fp64 on the host, of the initial and of the final layout, each with its own Z from one more iteration
         whose result is dropped), "z", "neighbor_position" int32 [N, K], "neighbor_dist2" fp32 [N, K], "n_edges", "learning_rate"} and
         the ``LatentEmbedding`` that ``HipModel.place`` takes.  Bad arguments, an index above 262,144 rows, fewer rows than the
-        perplexity needs and rows with a non-finite component raise ValueError; the arguments are checked before any GPU work."""
+        perplexity needs and rows with a non-finite component raise ValueError; the arguments are checked before any GPU work.
+        ``graph``: the ``(position, dist2)`` of ``neighbour_graph`` for these rows where the caller has it already (``choose_perplexity``
+        computes it once for all its maps)."""
         perplexity, iterations, exaggeration, route = embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route)
         N = len(self)
         if N > _hip.EMBED_MAX_ROWS:
@@ -485,7 +487,7 @@ class LatentIndex:
         eng = self.model.engine
         pca, _ = self.pca(2)
         y0 = embed_initial_layout(pca["coordinates"])
-        pos, d2 = neighbour_graph(self)
+        pos, d2 = neighbour_graph(self) if graph is None else graph
         row_first, col, p = embed_affinities(d2, pos, perplexity)
         if route == "device":
             step = functools.partial(eng.embed_iterate, row_first, col, p)
@@ -565,6 +567,55 @@ class LatentIndex:
         if N and not len(r["a"]):  # no edge: no eligible row, or one -- the rows tell
             lone = hierarchy_lone_row(self.rows()[0] if rows is None else rows)
         return hierarchy_result(r, core2, N, ids, atoms, min_samples, self.level, self.dim, lone)
+
+    def map_quality(self, coords, k=15, sample=None, seed=0, route="device", graph=None):
+        """Whether a map of this index's rows can be believed: the rank-based scores of ``coords`` -- fp32 [N, c] in position order, a
+        ``LatentEmbedding`` of this index, or the result of ``embed`` / ``pca`` -- against the rows themselves (Venna & Kaski 2001; Lee
+        & Verleysen 2009).  Each row's 31 nearest other rows in latent space (``neighbour_graph``, or the ``graph`` = (position, dist2)
+        that ``embed`` returned) and on the map (the same search on a temporary index of the coordinates) are ranked in the OTHER
+        space by one exact pass over all pairs on the GPU each (scann_index_ranks), defined to the bit; the scores are fp64 NumPy on
+        those integers.  With rho the 0-based rank, K = min(31, N - 2) and the first k places of a row's lists:
+          row_trustworthiness = 1 - 2 / (k (2N - 3k - 1)) * the sum over its map-neighbours of max(0, rho_latent + 1 - k),
+          row_continuity likewise over its latent-neighbours with rho_map,  row_overlap = #(map-neighbours with rho_latent < k) / k,
+        "trustworthiness", "continuity" and "neighbour_overlap" their means over the scored rows (formed from the integer totals);
+        "ks" 1 .. K with "trustworthiness_curve", "continuity_curve" (NaN where 2N - 3k' - 1 <= 0) and "qnx_curve" the same at every
+        k'; "lcmc" = neighbour_overlap - k / (N - 1); "rnx_auc" the 1/k'-weighted mean of ((N - 1) Q_NX(k') - k') / (N - 1 - k');
+        "false_neighbours" / "missed_neighbours" int32 per row: its map-neighbours that are no latent-neighbours, and the reverse;
+        "rank_latent" / "rank_map" int32 [n, K] the ranks themselves; "position" the scored rows, "k", "n_rows".
+        ``sample``: None, m rows drawn with ``seed`` or positions (the silhouette's rule): those rows are scored exactly against all
+        rows.  ``route`` "host" runs the twins on the rows read back: the same bytes.  ValueError for k outside 1 .. K, 2N - 3k - 1
+        <= 0, coordinates of the wrong length or not finite -- before any GPU work -- and for rows with a non-finite component."""
+        route = silhouette_route(route)
+        coords = map_coords_arg(coords, self)
+        if route == "host":
+            return map_quality_rows_host(self.rows()[0], coords, k=k, sample=sample, seed=seed, graph=graph)
+        N = len(self)
+        k = map_quality_k_arg(k, N)
+        sample = silhouette_sample_arg(sample, seed, N)
+        eng = self.model.engine
+        low = _CoordIndex(self.model, coords)
+        try:
+            return map_quality_run(lambda: neighbour_graph(self) if graph is None else graph, lambda: neighbour_graph(low),
+                                   lambda probe, q: eng.index_ranks(self._ix, probe, q)["rank"],
+                                   lambda probe, q: eng.index_ranks(low._ix, probe, q)["rank"], N, k, sample, seed)
+        finally:
+            low.free()
+
+    def choose_perplexity(self, perplexities, k=15, sample=None, seed=0, **embed_args):
+        """Which perplexity draws the most faithful map: ``embed`` at every perplexity of ``perplexities`` (ascending, distinct), each
+        map scored by ``map_quality`` at ``k``, and ``pca(2)`` scored as the row "linear".  The latent neighbour graph is computed once
+        and shared by the maps and the scores.  Returns ``(table, embedding)``: {"perplexity" (a list, "linear" last),
+        "neighbour_overlap", "trustworthiness", "continuity", "lcmc", "rnx_auc", "kl" fp64 arrays (kl NaN for "linear"),
+        "best_perplexity", "best" (the best map's ``embed`` result) and "quality" (its ``map_quality``)} and the ``LatentEmbedding``
+        with the greatest neighbour_overlap, ties to the lower perplexity.  ``embed_args``: ``embed``'s other arguments."""
+        perplexities = choose_perplexity_arg(perplexities)
+        map_quality_k_arg(k, len(self))
+        silhouette_sample_arg(sample, seed, len(self))
+        graph = neighbour_graph(self)
+        return choose_perplexity_run(lambda p: self.embed(perplexity=p, graph=graph, **embed_args),
+                                     lambda c: self.map_quality(c, k=k, sample=sample, seed=seed, graph=graph,
+                                                                route=embed_args.get("route", "device")),
+                                     lambda: self.pca(2)[0]["coordinates"], perplexities)
 
     def place(self, rows, embedding):
         """Host ``rows`` [n, dim] on an existing map of this index (``embedding``, as ``embed`` returned it for these rows): each row's
@@ -1615,7 +1666,8 @@ def neighbour_graph_host(rows, chunk=1024, strict=True):
     return pos, d2
 
 
-def embed_rows_host(rows, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", ids=None, atoms=None, level="structure"):
+def embed_rows_host(rows, perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto", ids=None, atoms=None, level="structure",
+                    graph=None):
     """``LatentIndex.embed`` of host rows [N, dim] entirely on the host, no GPU: the twins of the moments, the projection, the search's
     distances and the iteration -- bit for bit what an index holding these rows gives by either route."""
     perplexity, iterations, exaggeration, _ = embed_fit_args(perplexity, iterations, exaggeration, learning_rate, "host")
@@ -1631,7 +1683,7 @@ def embed_rows_host(rows, perplexity=10, iterations=(250, 500), exaggeration=12.
     mo = _hip.moments_host(rows)
     _, v, _ = _hip.sym_eig(mo["cov"])
     y0 = embed_initial_layout(_hip.project_host(rows, mo["mean"], v[:2].astype(np.float32))["coords"])
-    pos, d2 = neighbour_graph_host(rows)
+    pos, d2 = neighbour_graph_host(rows) if graph is None else graph
     row_first, col, p = embed_affinities(d2, pos, perplexity)
     ids = np.arange(N, dtype=np.int64) if ids is None else ids
     atoms = np.full(N, -1, np.int32) if atoms is None else atoms
@@ -1813,6 +1865,194 @@ class LatentEmbedding:
 
 
 PEAKS_NEIGHBOURS = EMBED_NEIGHBOURS  # the farthest neighbour the automatic bandwidth can look at: what ``neighbour_graph`` returns
+
+
+class _CoordIndex:
+    """Map coordinates [N, c] as a temporary index on ``model``'s GPU handle, with what ``neighbour_graph`` asks of an index"""
+
+    def __init__(self, model, coords):
+        self.model = model
+        self._ix = model.engine.index_create(coords.shape[1])
+        try:
+            model.engine.index_add(self._ix, coords)
+        except Exception:
+            self._ix.free()
+            raise
+
+    def __len__(self):
+        return len(self._ix)
+
+    def free(self):
+        self._ix.free()
+
+
+def map_coords_arg(coords, index=None, n_rows=None):
+    """The coordinates of a map as fp32 [N, c]: an array, a ``LatentEmbedding`` (checked against ``index``), the result dict of
+    ``embed`` ("coords") or ``pca`` ("coordinates"), or the pair either returns; ValueError unless they are finite and one per row"""
+    if isinstance(coords, tuple) and len(coords) == 2 and isinstance(coords[0], dict):
+        coords = coords[0]
+    if isinstance(coords, LatentEmbedding):
+        if index is not None:
+            coords.check_index(index)
+        coords = coords.coordinates
+    elif isinstance(coords, dict):
+        if "coords" not in coords and "coordinates" not in coords:
+            raise ValueError('a result dict must hold "coords" (embed) or "coordinates" (pca)')
+        coords = coords["coords"] if "coords" in coords else coords["coordinates"]
+    try:
+        c = np.ascontiguousarray(coords, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("coords must be an array of numbers [N, c]") from None
+    n = len(index) if index is not None else n_rows
+    if c.ndim != 2 or c.shape[1] < 1 or c.shape[1] > 1024 or (n is not None and c.shape[0] != int(n)):
+        raise ValueError("coords must have shape [%s, c] with c in 1 .. 1024, one row per row of the index, got %s" % (
+            "N" if n is None else int(n), c.shape))
+    if not np.isfinite(c).all():
+        raise ValueError("coords: row %d has a non-finite component" % int(np.nonzero(~np.isfinite(c).all(axis=1))[0][0]))
+    return c
+
+
+def map_quality_k_arg(k, n_rows):
+    """``k`` of ``map_quality`` checked against the number of rows: 1 .. K = min(31, N - 2) with 2N - 3k - 1 > 0; ValueError otherwise"""
+    K = min(EMBED_NEIGHBOURS, int(n_rows) - 2)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= K:
+        raise ValueError("k must be an integer in 1 .. %d (min(%d, N - 2) with N = %d rows), got %r" % (K, EMBED_NEIGHBOURS, int(n_rows), k))
+    if 2 * int(n_rows) - 3 * int(k) - 1 <= 0:
+        raise ValueError("k = %d is too large for %d rows: the scores need 2N - 3k - 1 > 0" % (int(k), int(n_rows)))
+    return int(k)
+
+
+def map_quality_scores(rank_latent, rank_map, n_rows, k):
+    """The scores of ``map_quality`` from the ranks, fp64 NumPy on integers: ``rank_latent`` int [n, K] the latent-space ranks of every
+    scored row's map-neighbours, nearest first, ``rank_map`` the map ranks of its latent-neighbours"""
+    rl, rm = np.asarray(rank_latent, np.int64), np.asarray(rank_map, np.int64)
+    n, K = rl.shape
+    N = int(n_rows)
+
+    def at(r, kk):  # the integer penalties and hits of every row at kk
+        head = r[:, :kk]
+        return np.maximum(head + 1 - kk, 0).sum(axis=1), (head < kk).sum(axis=1)
+
+    def coef(kk):
+        return 2.0 / (kk * (2.0 * N - 3.0 * kk - 1.0)) if 2 * N - 3 * kk - 1 > 0 else float("nan")
+
+    ks = np.arange(1, K + 1, dtype=np.int64)
+    t_curve, c_curve, q_curve = np.empty(K), np.empty(K), np.empty(K)
+    for kk in range(1, K + 1):
+        pen_l, hit_l = at(rl, kk)
+        pen_m, _ = at(rm, kk)
+        t_curve[kk - 1] = 1.0 - coef(kk) * (float(int(pen_l.sum())) / n)
+        c_curve[kk - 1] = 1.0 - coef(kk) * (float(int(pen_m.sum())) / n)
+        q_curve[kk - 1] = float(int(hit_l.sum())) / (n * kk)
+    pen_l, hit_l = at(rl, k)
+    pen_m, hit_m = at(rm, k)
+    kf = ks.astype(np.float64)
+    rnx = ((N - 1) * q_curve - kf) / (N - 1 - kf)
+    return {"k": int(k), "n_rows": N, "ks": ks,
+            "row_trustworthiness": 1.0 - coef(k) * pen_l.astype(np.float64), "row_continuity": 1.0 - coef(k) * pen_m.astype(np.float64),
+            "row_overlap": hit_l.astype(np.float64) / k,
+            "trustworthiness": float(t_curve[k - 1]), "continuity": float(c_curve[k - 1]), "neighbour_overlap": float(q_curve[k - 1]),
+            "trustworthiness_curve": t_curve, "continuity_curve": c_curve, "qnx_curve": q_curve,
+            "lcmc": float(q_curve[k - 1] - k / (N - 1.0)), "rnx_auc": float(np.sum(rnx / kf) / np.sum(1.0 / kf)),
+            "false_neighbours": (k - hit_l).astype(np.int32), "missed_neighbours": (k - hit_m).astype(np.int32),
+            "rank_latent": rl.astype(np.int32), "rank_map": rm.astype(np.int32)}
+
+
+def map_quality_run(graph_latent, graph_map, ranks_latent, ranks_map, n_rows, k, sample, seed):
+    """The host work around the two rank passes of ``map_quality``, shared by the device and the host route.  ``graph_latent()`` and
+    ``graph_map()`` give the neighbour graphs (position [N, >= K], dist2) of the two spaces, ``ranks_latent(probe, qpos or None)`` and
+    ``ranks_map`` the ranks of ``probe`` [n, K] in each."""
+    N = int(n_rows)
+    K = min(EMBED_NEIGHBOURS, N - 2)
+    if sample is None:
+        qpos, position = None, np.arange(N, dtype=np.int32)
+    elif isinstance(sample, int):
+        if sample > N:
+            raise ValueError("sample = %d, but there are only %d rows" % (sample, N))
+        qpos = position = np.sort(np.random.default_rng(seed).choice(N, sample, replace=False)).astype(np.int32)
+    else:
+        qpos = position = sample
+    pos_latent = np.ascontiguousarray(np.asarray(graph_latent()[0])[position, :K], dtype=np.int32)
+    pos_map = np.ascontiguousarray(np.asarray(graph_map()[0])[position, :K], dtype=np.int32)
+    if pos_latent.shape != (len(position), K):
+        raise ValueError("graph must hold the positions [%d, >= %d] of neighbour_graph, got %s" % (N, K, np.shape(graph_latent()[0])))
+    rank_latent, rank_map = ranks_latent(pos_map, qpos), ranks_map(pos_latent, qpos)
+    if (rank_latent < 0).any() or (rank_map < 0).any():
+        raise ValueError("row %d has a non-finite component: the map of such rows cannot be scored" % int(
+            position[np.nonzero((rank_latent < 0).any(axis=1) | (rank_map < 0).any(axis=1))[0][0]]))
+    out = map_quality_scores(rank_latent, rank_map, N, k)
+    out["position"] = position
+    return out
+
+
+def map_quality_rows_host(rows, coords, k=15, sample=None, seed=0, graph=None):
+    """``LatentIndex.map_quality`` without a GPU: the host twins (``neighbour_graph_host``, ``_hip.ranks_host``) on ``rows`` [N, dim]
+    and ``coords`` [N, c]; the same dict, bit for bit."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rows must be [N, dim], got shape %s" % (rows.shape,))
+    coords = map_coords_arg(coords, n_rows=len(rows))
+    k = map_quality_k_arg(k, len(rows))
+    sample = silhouette_sample_arg(sample, seed, len(rows))
+    return map_quality_run(lambda: neighbour_graph_host(rows) if graph is None else graph, lambda: neighbour_graph_host(coords),
+                           lambda probe, q: _hip.ranks_host(rows, probe, q)["rank"],
+                           lambda probe, q: _hip.ranks_host(coords, probe, q)["rank"], len(rows), k, sample, seed)
+
+
+def choose_perplexity_arg(perplexities):
+    """``perplexities`` of ``choose_perplexity`` checked: a non-empty ascending list of distinct perplexities (each as ``embed`` takes it)"""
+    try:
+        ps = [float(p) for p in perplexities]
+    except (TypeError, ValueError):
+        raise ValueError("perplexities must be a list of numbers in %d .. %d, got %r" % (EMBED_PERPLEXITY + (perplexities,))) from None
+    if not ps or any(isinstance(p, bool) for p in perplexities) or any(not EMBED_PERPLEXITY[0] <= p <= EMBED_PERPLEXITY[1] for p in ps) or any(
+            b <= a for a, b in zip(ps, ps[1:])):
+        raise ValueError("perplexities must be an ascending list of distinct numbers in %d .. %d, got %r" % (EMBED_PERPLEXITY + (perplexities,)))
+    return ps
+
+
+MAP_QUALITY_COLUMNS = ("neighbour_overlap", "trustworthiness", "continuity", "lcmc", "rnx_auc")
+
+
+def choose_perplexity_run(embed, quality, linear, perplexities):
+    """``choose_perplexity``'s table from ``embed(perplexity)``, ``quality(coords)`` and ``linear()`` (the coordinates of ``pca(2)``)
+    over the ascending ``perplexities``"""
+    table = {name: [] for name in MAP_QUALITY_COLUMNS + ("kl",)}
+    best = None
+    for p in perplexities:
+        res, emb = embed(p)
+        q = quality(res["coords"])
+        for name in MAP_QUALITY_COLUMNS:
+            table[name].append(q[name])
+        table["kl"].append(res["kl"])
+        if best is None or q["neighbour_overlap"] > best[2]["neighbour_overlap"]:  # (ascending: among equal scores the lower stays)
+            best = (p, res, q, emb)
+    q = quality(linear())
+    for name in MAP_QUALITY_COLUMNS:
+        table[name].append(q[name])
+    table["kl"].append(float("nan"))
+    out = {name: np.asarray(v, np.float64) for name, v in table.items()}
+    out.update({"perplexity": list(perplexities) + ["linear"], "best_perplexity": best[0], "best": best[1], "quality": best[2]})
+    return out, best[3]
+
+
+def choose_perplexity_rows_host(rows, perplexities, k=15, sample=None, seed=0, **embed_args):
+    """``LatentIndex.choose_perplexity`` of host rows [N, dim] entirely on the host, no GPU: the same table and embedding, bit for bit"""
+    perplexities = choose_perplexity_arg(perplexities)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 2:
+        raise ValueError("rows must have shape [N, dim] with dim >= 2, got %s" % (rows.shape,))
+    map_quality_k_arg(k, len(rows))
+    silhouette_sample_arg(sample, seed, len(rows))
+    graph = neighbour_graph_host(rows)
+
+    def linear():
+        mo = _hip.moments_host(rows)
+        _, v, _ = _hip.sym_eig(mo["cov"])
+        return _hip.project_host(rows, mo["mean"], v[:2].astype(np.float32))["coords"]
+
+    return choose_perplexity_run(lambda p: embed_rows_host(rows, perplexity=p, graph=graph, **embed_args),
+                                 lambda c: map_quality_rows_host(rows, c, k=k, sample=sample, seed=seed, graph=graph), linear, perplexities)
 
 
 def peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, route):

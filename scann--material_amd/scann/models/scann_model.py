@@ -604,6 +604,65 @@ class HipModel:
             if own is not None:
                 own.free()
 
+    def map_quality(self, data_or_index, coords, level="structure", k=15, sample=None, seed=0, route="device", graph=None, ids=None,
+                    batch_size=None):
+        """Whether a map of the model's latent space can be believed: trustworthiness, continuity and neighbourhood overlap of
+        ``coords`` -- an array [N, c], a ``LatentEmbedding`` or the result of ``fit_embedding`` / ``fit_projection`` -- against the
+        latent rows themselves, from exact neighbour ranks computed on the GPU, bit-reproducible (``LatentIndex.map_quality``, whose
+        arguments and dict these are).  ``data_or_index`` is the ``LatentIndex`` the map was drawn from (its level counts, not
+        ``level``) or data as ``build_index`` takes it, which is indexed for the call (``ids``: one per structure, default 0 .. n-1)
+        and freed afterwards.  An index of another model and bad arguments raise ValueError before any device call."""
+        from .latent_index import silhouette_route, silhouette_sample_arg
+
+        level_dim(self.config, data_or_index.level if isinstance(data_or_index, LatentIndex) else level)
+        silhouette_route(route)
+        silhouette_sample_arg(sample if np.ndim(sample) == 0 else None, seed, 0)  # (positions are checked against the index, once it is there)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31:
+            raise ValueError("k must be an integer in 1 .. 31, got %r" % (k,))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data_or_index, LatentIndex):
+                data_or_index.check_model(self)
+                index = data_or_index
+            else:
+                index = own = self.build_index(data_or_index, level=level, ids=ids, batch_size=batch_size)
+            return index.map_quality(coords, k=k, sample=sample, seed=seed, route=route, graph=graph)
+        finally:
+            if own is not None:
+                own.free()
+
+    def choose_perplexity(self, data, perplexities, level="structure", k=15, sample=None, seed=0, iterations=(250, 500), exaggeration=12.0,
+                          learning_rate="auto", route="device", ids=None, batch_size=None):
+        """Which perplexity draws the most faithful map of the model's latent space over ``data``: ``fit_embedding`` for every
+        perplexity of ``perplexities``, each map scored by ``map_quality`` at ``k``, the linear map of ``fit_projection(m=2)`` scored
+        beside them (``LatentIndex.choose_perplexity``).  ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as
+        ``build_index`` takes it, which is indexed once for the call and freed afterwards.  Returns ``(table, embedding)``: per
+        perplexity and for "linear" the neighbour overlap, trustworthiness, continuity, LCMC and the R_NX area, "best_perplexity", the
+        best map's ``embed`` and ``map_quality`` results -- and its ``LatentEmbedding``.  Bad arguments raise ValueError before
+        anything is uploaded."""
+        from .latent_index import choose_perplexity_arg, silhouette_sample_arg
+
+        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        perplexities = choose_perplexity_arg(perplexities)
+        embed_fit_args(perplexities[0], iterations, exaggeration, learning_rate, route)
+        silhouette_sample_arg(sample if np.ndim(sample) == 0 else None, seed, 0)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31:
+            raise ValueError("k must be an integer in 1 .. 31, got %r" % (k,))
+        self._batch_size(batch_size)
+        own = None
+        try:
+            if isinstance(data, LatentIndex):
+                data.check_model(self)
+                index = data
+            else:
+                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            return index.choose_perplexity(perplexities, k=k, sample=sample, seed=seed, iterations=iterations, exaggeration=exaggeration,
+                                           learning_rate=learning_rate, route=route)
+        finally:
+            if own is not None:
+                own.free()
+
     def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
                       ids=None, batch_size=None):
         """Which kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``) the
@@ -1512,6 +1571,18 @@ class SCANN:
         """HipModel.fit_embedding as it is: ``(result, embedding)``; the map lives in latent space."""
         return self.model.fit_embedding(data, level=level, perplexity=perplexity, iterations=iterations, exaggeration=exaggeration,
                                         learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
+
+    def map_quality(self, data_or_index, coords, level="structure", k=15, sample=None, seed=0, route="device", graph=None, ids=None,
+                    batch_size=None):
+        """HipModel.map_quality as it is: the ranks live in latent space and on the map."""
+        return self.model.map_quality(data_or_index, coords, level=level, k=k, sample=sample, seed=seed, route=route, graph=graph, ids=ids,
+                                      batch_size=batch_size)
+
+    def choose_perplexity(self, data, perplexities, level="structure", k=15, sample=None, seed=0, iterations=(250, 500), exaggeration=12.0,
+                          learning_rate="auto", route="device", ids=None, batch_size=None):
+        """HipModel.choose_perplexity as it is: ``(table, embedding)``; the maps live in latent space."""
+        return self.model.choose_perplexity(data, perplexities, level=level, k=k, sample=sample, seed=seed, iterations=iterations,
+                                            exaggeration=exaggeration, learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
 
     def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
                       ids=None, batch_size=None):
