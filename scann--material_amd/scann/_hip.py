@@ -410,6 +410,29 @@ def check_pca_args(mean, components, scale, dim=None):
     return mean, components, scale
 
 
+def _batch_out(packed, level):
+    """(n, out) of a call behind a forward: n, the ``level`` rows of the batch (its atoms for OUT_AFTER_LC, else its structures), and
+    the dict with the buffers every such call fills, "y" [n_struct] and "ga" [n_atom]"""
+    n = packed.n_atom if int(level) == OUT_AFTER_LC else packed.n_struct
+    return n, {"y": np.empty(packed.n_struct, np.float32), "ga": np.empty(packed.n_atom, np.float32)}
+
+
+def _check_head_weights(call, tmean, weights, scale, lev0, dim, m):
+    """(tmean [K], weights [K, dim], scale [K, m]) of a head evaluated behind a forward as the C calls take them, 1 <= K <=
+    HEAD_MAX_TARGETS, all finite and ``lev0`` too; ValueError otherwise, in the name of ``call``"""
+    tmean = np.ascontiguousarray(tmean, dtype=np.float32)
+    weights = np.ascontiguousarray(weights, dtype=np.float32)
+    scale = np.ascontiguousarray(scale, dtype=np.float32)
+    K = tmean.shape[0] if tmean.ndim == 1 else 0
+    if tmean.ndim != 1 or not 1 <= K <= HEAD_MAX_TARGETS or weights.shape != (K, dim) or scale.shape != (K, m):
+        raise ValueError("%s: tmean [K], weights [K, %d] and scale [K, %d] are needed, 1 <= K <= %d, got %s, %s and %s" % (
+            call, dim, m, HEAD_MAX_TARGETS, tmean.shape, weights.shape, scale.shape))
+    for name, a in (("tmean", tmean), ("weights", weights), ("scale", scale), ("lev0", np.float32(lev0))):
+        if not np.isfinite(a).all():
+            raise ValueError("%s holds a non-finite value" % name)
+    return tmean, weights, scale
+
+
 def _project_out(n, m, scale):
     out = {"coords": np.empty((n, m), np.float32), "dist2": np.empty(n, np.float32)}
     if scale is not None:
@@ -1859,8 +1882,8 @@ class Engine:
         qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
         if qid is not None and qid.shape[0] != p.n_struct:
             raise ValueError("index_query_batch: %d structures need %d query ids" % (p.n_struct, p.n_struct))
-        out = self._knn_out(p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct, k)
-        out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
+        n, out = _batch_out(p, level)
+        out.update(self._knn_out(n, k))
         self._check(self.lib.scann_index_query_batch(self._h, ix._h, rb._h, int(level), _ptr(qid), k, _ptr(out["y"]), _ptr(out["ga"]),
                                                      _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["position"])))
         return out
@@ -1988,9 +2011,8 @@ class Engine:
         """One forward of a resident batch and the projection of each of its ``level`` rows (scann_project_batch; raw y): {"y"
         [n_struct], "ga" [n_atom], "coords" [n_struct or n_atom, m], "dist2", with ``scale`` "md2"}."""
         mean, components, scale = check_pca_args(mean, components, scale)
-        p = rb.packed
-        out = _project_out(p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct, components.shape[0], scale)
-        out["y"], out["ga"] = np.empty(p.n_struct, np.float32), np.empty(p.n_atom, np.float32)
+        n, out = _batch_out(rb.packed, level)
+        out.update(_project_out(n, components.shape[0], scale))
         self._check(self.lib.scann_project_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(components), _ptr(scale), components.shape[0],
                                                  _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["coords"]), _ptr(out.get("md2")), _ptr(out["dist2"])))
         return out
@@ -2028,20 +2050,11 @@ class Engine:
         """One forward of a resident batch and a head evaluated on each of its ``level`` rows (scann_head_batch; raw y): {"y" [n_struct],
         "ga" [n_atom], "pred", "lev" [n_struct or n_atom, K]}.  ``weights`` [K, dim], ``components`` [m, dim], ``scale`` [K, m]."""
         mean, components, _ = check_pca_args(mean, components, None)
-        tmean = np.ascontiguousarray(tmean, dtype=np.float32)
-        weights = np.ascontiguousarray(weights, dtype=np.float32)
-        scale = np.ascontiguousarray(scale, dtype=np.float32)
-        K, m = tmean.shape[0], components.shape[0]
-        if tmean.ndim != 1 or not 1 <= K <= HEAD_MAX_TARGETS or weights.shape != (K, mean.shape[0]) or scale.shape != (K, m):
-            raise ValueError("head_batch: tmean [K], weights [K, %d] and scale [K, %d] are needed, 1 <= K <= %d, got %s, %s and %s" % (
-                mean.shape[0], m, HEAD_MAX_TARGETS, tmean.shape, weights.shape, scale.shape))
-        for name, a in (("tmean", tmean), ("weights", weights), ("scale", scale), ("lev0", np.float32(lev0))):
-            if not np.isfinite(a).all():
-                raise ValueError("%s holds a non-finite value" % name)
-        p = rb.packed
-        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
-        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "pred": np.empty((n, K), np.float32),
-               "lev": np.empty((n, K), np.float32)}
+        m = components.shape[0]
+        tmean, weights, scale = _check_head_weights("head_batch", tmean, weights, scale, lev0, mean.shape[0], m)
+        K = tmean.shape[0]
+        n, out = _batch_out(rb.packed, level)
+        out["pred"], out["lev"] = np.empty((n, K), np.float32), np.empty((n, K), np.float32)
         self._check(self.lib.scann_head_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(tmean), _ptr(weights), K, _ptr(components), m,
                                               _ptr(scale), float(lev0), _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["pred"]), _ptr(out["lev"])))
         return out
@@ -2064,20 +2077,11 @@ class Engine:
         ``landmarks`` [m, dim]; over the m features ``mean`` [m], ``weights`` [K, m], ``components`` [mm, m], ``scale`` [K, mm]."""
         z, g = check_rbf_args(landmarks, gamma)
         mean, components, _ = check_pca_args(mean, components, None, z.shape[0])
-        tmean = np.ascontiguousarray(tmean, dtype=np.float32)
-        weights = np.ascontiguousarray(weights, dtype=np.float32)
-        scale = np.ascontiguousarray(scale, dtype=np.float32)
-        K, m, mm = tmean.shape[0] if tmean.ndim == 1 else 0, z.shape[0], components.shape[0]
-        if tmean.ndim != 1 or not 1 <= K <= HEAD_MAX_TARGETS or weights.shape != (K, m) or scale.shape != (K, mm):
-            raise ValueError("rbf_head_batch: tmean [K], weights [K, %d] and scale [K, %d] are needed, 1 <= K <= %d, got %s, %s and %s" % (
-                m, mm, HEAD_MAX_TARGETS, tmean.shape, weights.shape, scale.shape))
-        for name, a in (("tmean", tmean), ("weights", weights), ("scale", scale), ("lev0", np.float32(lev0))):
-            if not np.isfinite(a).all():
-                raise ValueError("%s holds a non-finite value" % name)
-        p = rb.packed
-        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
-        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "pred": np.empty((n, K), np.float32),
-               "lev": np.empty((n, K), np.float32)}
+        m, mm = z.shape[0], components.shape[0]
+        tmean, weights, scale = _check_head_weights("rbf_head_batch", tmean, weights, scale, lev0, m, mm)
+        K = tmean.shape[0]
+        n, out = _batch_out(rb.packed, level)
+        out["pred"], out["lev"] = np.empty((n, K), np.float32), np.empty((n, K), np.float32)
         if want_phi:
             out["phi"] = np.empty((n, m), np.float32)
         self._check(self.lib.scann_rbf_head_batch(self._h, rb._h, int(level), _ptr(z), m, g, _ptr(mean), _ptr(tmean), _ptr(weights), K,
@@ -2153,9 +2157,8 @@ class Engine:
         """One forward of a resident batch and the density sums of its ``level`` rows under ``ix`` (scann_index_density_batch; raw y):
         {"y" [n_struct], "ga" [n_atom], "sum" int64 [n_struct or n_atom]}."""
         g = check_peaks_gamma(gamma)
-        p = rb.packed
-        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
-        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "sum": np.zeros(n, np.int64)}
+        n, out = _batch_out(rb.packed, level)
+        out["sum"] = np.zeros(n, np.int64)
         self._check(self.lib.scann_index_density_batch(self._h, ix._h, rb._h, int(level), g, _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["sum"])))
         return out
 
@@ -2169,9 +2172,8 @@ class Engine:
         if w.ndim != 2:
             raise ValueError("logit_head_batch: weights must have shape [C, dim + 1], got %s" % (w.shape,))
         mean, w3, _, _, _ = check_logit_args(mean, w[None], None, 0, None)
-        p = rb.packed
-        n = p.n_atom if int(level) == OUT_AFTER_LC else p.n_struct
-        out = {"y": np.empty(p.n_struct, np.float32), "ga": np.empty(p.n_atom, np.float32), "prob": np.empty((n, w.shape[0]), np.float32)}
+        n, out = _batch_out(rb.packed, level)
+        out["prob"] = np.empty((n, w.shape[0]), np.float32)
         self._check(self.lib.scann_logit_head_batch(self._h, rb._h, int(level), _ptr(mean), _ptr(w3), w.shape[0], _ptr(out["y"]), _ptr(out["ga"]),
                                                     _ptr(out["prob"])))
         return out

@@ -88,6 +88,72 @@ def explained_ratio(w):
     return w / (total * (1.0 + (len(w) + 2) * 2.0 ** -52))
 
 
+def width_mismatch(noun, level, dim, config, path=None):
+    """THE message for rows of ``level`` and ``dim`` columns that are not ``config``'s, ``path``: in front for a file"""
+    return "%sa %s-level %s of %d columns does not fit a model whose %s is %d" % (
+        "" if path is None else "%s: " % (path,), level, noun, dim, "dense_out" if level == "structure" else "global_dim",
+        level_dim(config, level) if level in LEVELS else -1)
+
+
+# how a scalar field of a saved result is boxed for np.savez and unboxed for the constructor
+AS_FLOAT = (np.array, float)
+AS_FLOAT32 = (lambda v: np.array(v, dtype=np.float32), float)
+AS_INT = (lambda v: np.array(v, dtype=np.int64), int)
+AS_NAMES = (lambda v: np.array(v, dtype=np.str_), lambda a: [str(x) for x in a])
+
+
+def saved_fields(*fields, of=""):
+    """A saved result's FIELDS from a declaration: "key" for an array attribute saved as it is, ("key", AS_...) for a scalar;
+    ``of``: the attribute that holds them ("head." for an inner head's).  -> ((key, attribute path, box, unbox), ...)"""
+    return tuple((f, of + f, None, None) if isinstance(f, str) else (f[0], of + f[0]) + f[1] for f in fields)
+
+
+class SavedResult:
+    """What the results a fit leaves behind share: they belong to one ``level`` of a model and to rows of ``dim`` columns, fit every
+    model whose level has that width, and are saved as one ``.npz`` without pickle.  A subclass declares ``NOUN`` (what the mismatch
+    message calls it), ``FIELDS`` (``saved_fields``, in the order of its constructor's arguments; ``level`` and ``dim`` follow them),
+    and where it differs: ``KIND`` (a tag the file carries and ``load`` demands), ``saved_fits`` (a further check of a loaded file
+    against ``dim``) and ``from_saved`` (a constructor that takes the fields in another order)."""
+    NOUN, FIELDS, KIND = None, (), None
+
+    def check_model(self, model):
+        """ValueError unless the result has the width of ``model``'s level"""
+        if level_dim(model.config, self.level) != self.dim:
+            raise ValueError(width_mismatch(self.NOUN, self.level, self.dim, model.config))
+
+    def save(self, path):
+        """An ``.npz`` of the fields, level and dim (written to exactly ``path``; no pickle)."""
+        out = {}
+        for key, attr, box, _ in self.FIELDS:
+            v = functools.reduce(getattr, attr.split("."), self)
+            out[key] = v if box is None else box(v)
+        out.update(level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+        if self.KIND is not None:
+            out["kind"] = np.array(self.KIND)
+        with open(path, "wb") as f:
+            np.savez(f, **out)
+
+    @classmethod
+    def load(cls, model, path):
+        """The saved result; ValueError if the file is of another kind, or if its level's width is not this model's."""
+        with np.load(path, allow_pickle=False) as z:
+            if cls.KIND is not None and ("kind" not in z.files or str(z["kind"]) != cls.KIND):
+                raise ValueError("%s: not a saved %s" % (path, cls.__name__))
+            level, dim = str(z["level"]), int(z["dim"])
+            v = {key: z[key] if unbox is None else unbox(z[key]) for key, _, _, unbox in cls.FIELDS}
+        if level not in LEVELS or level_dim(model.config, level) != dim or not cls.saved_fits(v, dim):
+            raise ValueError(width_mismatch(cls.NOUN, level, dim, model.config, path))
+        return cls.from_saved(v, level, dim)
+
+    @classmethod
+    def saved_fits(cls, v, dim):
+        return True
+
+    @classmethod
+    def from_saved(cls, v, level, dim):
+        return cls(*v.values(), level, dim)
+
+
 class LatentIndex:
     """Rows of one level of one model on its GPU.  ``level``: "structure" (one ``bf_property`` row per structure) or "atom" (one
     ``after_Lc`` row per real atom).  Every row carries the id of its structure and, at atom level, the atom's index within it."""
@@ -154,8 +220,7 @@ class LatentIndex:
             level, dim = str(z["level"]), int(z["dim"])
             rows, ids, atoms = z["rows"], z["ids"], z["atoms"]
         if level_dim(model.config, level) != dim or rows.ndim != 2 or rows.shape[1] != dim:
-            raise ValueError("%s: a %s-level index of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level)))
+            raise ValueError(width_mismatch("index", level, dim, model.config, path))
         ix = cls(model, level)
         if len(rows):
             ix.add_rows(rows, ids, atoms)
@@ -921,11 +986,13 @@ def head_result(fit, loo, pick, t, names, level, dim):
     return result, head
 
 
-class LatentHead:
+class LatentHead(SavedResult):
     """A linear readout head on one level of one model, as ``LatentIndex.fit_head`` fits it: prediction_k = tmean_k + (x - mean) . W_k
     and leverage_k = lev0 + sum_c ((x - mean) . V_c scale_kc)^2, so that std_k = sqrt(sigma2_k (1 + leverage_k)) is the predictive
     standard deviation of Bayesian linear regression.  mean [dim], tmean [K], weights [K, dim], components [m, dim], scale [K, m] fp32;
     sigma2, l2 [K] fp64."""
+    NOUN = "head"
+    FIELDS = saved_fields("mean", "tmean", "weights", "components", "scale", ("lev0", AS_FLOAT), "sigma2", "l2", ("names", AS_NAMES))
 
     def __init__(self, mean, tmean, weights, components, scale, lev0, sigma2, l2, level, dim=None, names=None):
         if level not in LEVELS:
@@ -960,36 +1027,16 @@ class LatentHead:
     def k(self):
         return int(self.tmean.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the head has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level head of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+    @classmethod
+    def from_saved(cls, v, level, dim):
+        names = v.pop("names")  # (the constructor takes them last)
+        return cls(*v.values(), level, dim, names)
 
     def finish(self, pred, lev):
         """the device's pred and lev [n, K] as {"prediction", "std", "leverage"}: the square root taken on the host in fp64"""
         with np.errstate(invalid="ignore"):
             std = np.sqrt(self.sigma2[None, :] * (1.0 + lev.astype(np.float64))).astype(np.float32)
         return {"prediction": pred, "std": std, "leverage": lev}
-
-    def save(self, path):
-        """An ``.npz`` of the head's arrays, level, dim and names (written to exactly ``path``; no pickle)."""
-        with open(path, "wb") as f:
-            np.savez(f, mean=self.mean, tmean=self.tmean, weights=self.weights, components=self.components, scale=self.scale,
-                     lev0=np.array(self.lev0), sigma2=self.sigma2, l2=self.l2, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64),
-                     names=np.array(self.names, dtype=np.str_))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved head; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            args = [z[n] for n in ("mean", "tmean", "weights", "components", "scale")] + [float(z["lev0"]), z["sigma2"], z["l2"]]
-            names = [str(x) for x in z["names"]]
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(*args, level, dim, names)
 
 
 CLASS_L2_DECADES = 6      # l2="cv": max(s_0 10^-l, noise floor), l = 0 .. 5
@@ -1243,10 +1290,12 @@ def class_head_result(fit, lab, classes, level, dim):
     return result, head
 
 
-class LatentClassHead:
+class LatentClassHead(SavedResult):
     """A classification head on one level of one model, as ``LatentIndex.fit_class_head`` fits it: the logits a_k = intercept_k + (x -
     mean) . W_k and their softmax.  mean [dim], weights [C, dim + 1] fp32 (the intercept in the last column), classes int64 [C] (the label
     value of every class), l2 the strength it was fitted with."""
+    NOUN, KIND = "head", "class_head"  # (the tag tells its file from a LatentHead's, whose keys it shares in part)
+    FIELDS = saved_fields("mean", "weights", "classes", ("l2", AS_FLOAT))
 
     def __init__(self, mean, weights, classes, l2, level, dim=None):
         if level not in LEVELS:
@@ -1273,12 +1322,6 @@ class LatentClassHead:
     def c(self):
         return int(self.weights.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the head has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level head of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
-
     def finish(self, prob):
         """the device's probabilities [n, C] as {"probability", "label" (the class value of the largest, the first of equals),
         "confidence" (that probability), "entropy" (nats; fp64 on the host, 0 log 0 = 0)}"""
@@ -1288,25 +1331,6 @@ class LatentClassHead:
         best = np.argmax(np.where(np.isnan(prob), -np.inf, prob), axis=1) if len(prob) else np.zeros(0, np.int64)
         return {"probability": prob, "label": self.classes[best], "confidence": prob[np.arange(len(prob)), best].astype(np.float32),
                 "entropy": ent.astype(np.float32)}
-
-    def save(self, path):
-        """An ``.npz`` of the head's arrays, level and dim (written to exactly ``path``; no pickle)."""
-        with open(path, "wb") as f:
-            np.savez(f, mean=self.mean, weights=self.weights, classes=self.classes, l2=np.array(self.l2), level=np.array(self.level),
-                     dim=np.array(self.dim, dtype=np.int64), kind=np.array("class_head"))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved head; ValueError if it is not one, or if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            if "kind" not in z.files or str(z["kind"]) != "class_head":
-                raise ValueError("%s: not a saved LatentClassHead" % path)
-            level, dim = str(z["level"]), int(z["dim"])
-            args = [z["mean"], z["weights"], z["classes"], float(z["l2"])]
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level head of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(*args, level, dim)
 
 
 KERNEL_BANDWIDTH_FACTORS = (1.0, 2.0, 4.0, 8.0, 16.0, 32.0)  # bandwidth="loo": h^2 over the squared covering radius
@@ -1392,11 +1416,15 @@ def kernel_head_result(run, hs, Z, R2, positions, ids, atoms, t, names, level, d
     return result, head
 
 
-class LatentKernelHead:
+class LatentKernelHead(SavedResult):
     """A ridge head on the Gaussian features of one level of one model, as ``LatentIndex.fit_kernel_head`` fits it: phi_c(x) =
     2^(-|x - z_c|^2 gamma) to the landmarks z [m, dim], and ``head`` -- a ``LatentHead`` over the m features (its ``dim`` is m):
     prediction_k = tmean_k + (phi - mean) . W_k, leverage_k as there, std_k = sqrt(sigma2_k (1 + leverage_k)), the predictive standard
     deviation of sparse Gaussian process regression with this basis.  ``gamma`` is the fp32 value log2(e) / (2 h^2) the device uses."""
+    NOUN = "kernel head"
+    # one flat file: the inner head's fields (all but its names) at top level beside the landmarks
+    FIELDS = saved_fields("landmarks", ("gamma", AS_FLOAT32)) + saved_fields(
+        "mean", "tmean", "weights", "components", "scale", ("lev0", AS_FLOAT), "sigma2", "l2", of="head.") + saved_fields(("names", AS_NAMES))
 
     def __init__(self, landmarks, gamma, head, level, dim=None, names=None):
         if level not in LEVELS:
@@ -1424,11 +1452,10 @@ class LatentKernelHead:
         """h of exp(-d^2 / 2 h^2), from the stored gamma"""
         return float(np.sqrt(np.log2(np.e) / (2.0 * self.gamma)))
 
-    def check_model(self, model):
-        """ValueError unless the landmarks have the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level kernel head of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+    @classmethod
+    def from_saved(cls, v, level, dim):
+        landmarks, gamma, names = v.pop("landmarks"), v.pop("gamma"), v.pop("names")
+        return cls(landmarks, gamma, LatentHead(*v.values(), level, None, names), level, dim, names)
 
     def finish(self, pred, lev, phi):
         """the device's pred, lev [n, K] and phi [n, m] as {"prediction", "std", "leverage", "support"}: support is the largest
@@ -1437,32 +1464,13 @@ class LatentKernelHead:
         out["support"] = phi.max(axis=1) if phi.shape[0] else np.zeros(0, np.float32)
         return out
 
-    def save(self, path):
-        """An ``.npz`` of the landmarks, gamma, the inner head's arrays, level, dim and names (written to exactly ``path``; no pickle)."""
-        h = self.head
-        with open(path, "wb") as f:
-            np.savez(f, landmarks=self.landmarks, gamma=np.array(self.gamma, dtype=np.float32), mean=h.mean, tmean=h.tmean, weights=h.weights,
-                     components=h.components, scale=h.scale, lev0=np.array(h.lev0), sigma2=h.sigma2, l2=h.l2, level=np.array(self.level),
-                     dim=np.array(self.dim, dtype=np.int64), names=np.array(self.names, dtype=np.str_))
 
-    @classmethod
-    def load(cls, model, path):
-        """The saved kernel head; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            landmarks, gamma = z["landmarks"], float(z["gamma"])
-            args = [z[n] for n in ("mean", "tmean", "weights", "components", "scale")] + [float(z["lev0"]), z["sigma2"], z["l2"]]
-            names = [str(x) for x in z["names"]]
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level kernel head of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(landmarks, gamma, LatentHead(*args, level, None, names), level, dim, names)
-
-
-class LatentProjection:
+class LatentProjection(SavedResult):
     """A principal-component map of one level of one model: mean [dim], components [m, dim] (fp32, rows), their variances (fp64) and the
     noise floor below which a variance cannot be told from 0.  ``scale`` [m] fp32 is 1 / sqrt(variance) above the floor and 0 at or
     below it, so such a component adds nothing to the Mahalanobis distance; ``rank`` counts the components above it."""
+    NOUN = "projection"
+    FIELDS = saved_fields("mean", "components", "variance", ("noise_floor", AS_FLOAT))
 
     def __init__(self, mean, components, variance, noise_floor, level, dim=None):
         if level not in LEVELS:
@@ -1486,12 +1494,6 @@ class LatentProjection:
     def m(self):
         return int(self.components.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the projection has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level projection of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
-
     def finish(self, r):
         """the device's {"coords", "md2", "dist2"} as the rows the callers report: square roots taken on the host (correctly rounded, as
         ``nearest`` reports distances), NaN where the distance to the mean is not finite"""
@@ -1500,26 +1502,11 @@ class LatentProjection:
         coords[bad], md[bad], dist[bad] = np.nan, np.nan, np.nan
         return {"coordinates": coords, "mahalanobis": md, "distance_to_mean": dist}
 
-    def save(self, path):
-        """An ``.npz`` of mean, components, variance, noise_floor, level and dim (written to exactly ``path``)."""
-        with open(path, "wb") as f:
-            np.savez(f, mean=self.mean, components=self.components, variance=self.variance, noise_floor=np.array(self.noise_floor),
-                     level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
 
-    @classmethod
-    def load(cls, model, path):
-        """The saved projection; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            mean, components, variance, noise = z["mean"], z["components"], z["variance"], float(z["noise_floor"])
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level projection of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(mean, components, variance, noise, level, dim)
-
-
-class LatentClustering:
+class LatentClustering(SavedResult):
     """The centres of a clustering of one level of one model: what ``HipModel.assign`` assigns new inputs to."""
+    NOUN = "clustering"
+    FIELDS = saved_fields("centres")
 
     def __init__(self, centres, level, dim=None):
         centres = np.ascontiguousarray(centres, dtype=np.float32)
@@ -1537,11 +1524,9 @@ class LatentClustering:
     def k(self):
         return int(self.centres.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the centres have the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level clustering of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+    @classmethod
+    def saved_fits(cls, v, dim):
+        return v["centres"].ndim == 2 and v["centres"].shape[1] == dim
 
     def index_on(self, model):
         """The centres as a ``LatentIndex`` on ``model``'s GPU, centre c at position c with id c (built once per model and kept)."""
@@ -1550,21 +1535,6 @@ class LatentClustering:
             self.free()
             self._index = LatentIndex(model, self.level).add_rows(self.centres)
         return self._index
-
-    def save(self, path):
-        """An ``.npz`` of centres, level and dim (written to exactly ``path``)."""
-        with open(path, "wb") as f:
-            np.savez(f, centres=self.centres, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved clustering; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim, centres = str(z["level"]), int(z["dim"]), z["centres"]
-        if level not in LEVELS or level_dim(model.config, level) != dim or centres.ndim != 2 or centres.shape[1] != dim:
-            raise ValueError("%s: a %s-level clustering of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(centres, level, dim)
 
     def free(self):
         if self._index is not None:
@@ -1792,9 +1762,11 @@ def embed_run(step, y0, row_first, col, p, iterations, exaggeration, lr, pos, d2
     return result, emb
 
 
-class LatentEmbedding:
+class LatentEmbedding(SavedResult):
     """A neighbour embedding of one level of one model, as ``LatentIndex.embed`` fits it: the map coordinates fp32 [N, 2] of the index's
     rows in position order, their ids and atoms, and the perplexity new rows are placed with."""
+    NOUN = "embedding"
+    FIELDS = saved_fields("coordinates", "ids", "atoms", ("perplexity", AS_FLOAT))
 
     def __init__(self, coordinates, ids, atoms, perplexity, level, dim):
         if level not in LEVELS:
@@ -1818,12 +1790,6 @@ class LatentEmbedding:
     def __len__(self):
         return int(self.coordinates.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the embedding has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level embedding of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
-
     def check_index(self, index):
         """ValueError unless ``index`` can be the one the embedding maps: its level, width and number of rows"""
         if not isinstance(index, LatentIndex):
@@ -1845,23 +1811,6 @@ class LatentEmbedding:
         first = position[:, 0]
         return {"coords": coords, "nearest_position": first.astype(np.int32), "nearest_id": self.ids[first], "nearest_atom": self.atoms[first],
                 "nearest_distance": np.sqrt(dist2[:, 0])}  # (correctly rounded on the host, as nearest reports distances)
-
-    def save(self, path):
-        """An ``.npz`` of coordinates, ids, atoms, perplexity, level and dim (written to exactly ``path``; no pickle)."""
-        with open(path, "wb") as f:
-            np.savez(f, coordinates=self.coordinates, ids=self.ids, atoms=self.atoms, perplexity=np.array(self.perplexity),
-                     level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved embedding; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            args = (z["coordinates"], z["ids"], z["atoms"], float(z["perplexity"]))
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level embedding of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(*args, level, dim)
 
 
 PEAKS_NEIGHBOURS = EMBED_NEIGHBOURS  # the farthest neighbour the automatic bandwidth can look at: what ``neighbour_graph`` returns
@@ -2174,10 +2123,12 @@ def density_of_sums(sums, n_rows):
         return np.where(S >= 0, np.ldexp(S.astype(np.float64), -30) / (n_rows if n_rows > 0 else np.nan), np.nan)
 
 
-class LatentPeaks:
+class LatentPeaks(SavedResult):
     """A density-peak clustering of one level of one model, as ``LatentIndex.density_peaks`` fits it: the label of every row of the
     index in position order, the rows' ids and atoms, the centres' positions and the kernel width.  A new structure takes the label of
     its nearest index row: ``label_of(position)`` with the positions ``nearest(k=1)`` reports."""
+    NOUN = "density-peak clustering"
+    FIELDS = saved_fields("label", "ids", "atoms", "centre_position", ("bandwidth", AS_FLOAT))
 
     def __init__(self, label, ids, atoms, centre_position, bandwidth, level, dim):
         if level not in LEVELS:
@@ -2208,35 +2159,12 @@ class LatentPeaks:
     def k(self):
         return int(self.centre_position.shape[0])
 
-    def check_model(self, model):
-        """ValueError unless the clustering has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level density-peak clustering of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
-
     def label_of(self, position):
         """The labels of index rows by position (any shape, int32): what ``nearest(k=1)``'s positions stand for; -1 for position -1."""
         p = np.asarray(position)
         if p.dtype.kind not in "iu" or (p.size and (p.min() < -1 or p.max() >= len(self))):
             raise ValueError("position must hold integers in -1 .. %d" % (len(self) - 1))
         return np.where(p >= 0, self.label[np.maximum(p, 0)], -1).astype(np.int32)
-
-    def save(self, path):
-        """An ``.npz`` of label, ids, atoms, centre_position, bandwidth, level and dim (written to exactly ``path``; no pickle)."""
-        with open(path, "wb") as f:
-            np.savez(f, label=self.label, ids=self.ids, atoms=self.atoms, centre_position=self.centre_position,
-                     bandwidth=np.array(self.bandwidth), level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved clustering; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            args = (z["label"], z["ids"], z["atoms"], z["centre_position"], float(z["bandwidth"]))
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level density-peak clustering of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(*args, level, dim)
 
 
 HIER_MAX_SAMPLES = EMBED_NEIGHBOURS  # the farthest neighbour a core distance can look at: what ``neighbour_graph`` returns
@@ -2320,12 +2248,14 @@ def _number_by_least_member(raw, n_rows):
     return label, uniq[order]
 
 
-class LatentHierarchy:
+class LatentHierarchy(SavedResult):
     """The hierarchical clustering of one level of one model, as ``LatentIndex.hierarchy`` builds it: the N - 1 edges of the minimum
     spanning tree in the edge order (w ascending, then the positions), the squared core distances, the rows' ids and atoms.  Everything
     derived from it -- ``linkage``, ``cut``, ``clusters`` -- is deterministic fp64 NumPy on the sorted edges.  The rows that count
     (the eligible ones: no non-finite component) are the rows the edges name; a tree without edges has none, or the one at
     ``lone_position``.  The other rows get label -1 everywhere."""
+    NOUN = "hierarchy"
+    FIELDS = saved_fields("a", "b", "w", "core2", "ids", "atoms", ("min_samples", AS_INT), ("lone_position", AS_INT))
 
     def __init__(self, a, b, w, core2, n_rows, ids, atoms, min_samples, level, dim, lone_position=-1):
         if level not in LEVELS:
@@ -2396,11 +2326,9 @@ class LatentHierarchy:
     def __len__(self):
         return self.n_rows
 
-    def check_model(self, model):
-        """ValueError unless the hierarchy has the width of ``model``'s level"""
-        if level_dim(model.config, self.level) != self.dim:
-            raise ValueError("a %s-level hierarchy of %d columns does not fit a model whose %s is %d" % (
-                self.level, self.dim, "dense_out" if self.level == "structure" else "global_dim", level_dim(model.config, self.level)))
+    @classmethod
+    def from_saved(cls, v, level, dim):
+        return cls(v["a"], v["b"], v["w"], v["core2"], len(v["ids"]), v["ids"], v["atoms"], v["min_samples"], level, dim, v["lone_position"])
 
     def linkage(self):
         """The dendrogram in SciPy's layout, fp64 [n - 1, 4], n the rows that count: merge e joins the clusters of a[e] and b[e] in edge
@@ -2538,21 +2466,3 @@ class LatentHierarchy:
             reach = np.maximum(d, self.core2[q])
             lab = np.where((lab >= 0) & ~(reach < clusters["birth2"][np.maximum(lab, 0)]), -1, lab).astype(np.int32)
         return lab
-
-    def save(self, path):
-        """An ``.npz`` of the edges, core2, ids, atoms, min_samples, level and dim (written to exactly ``path``; no pickle)."""
-        with open(path, "wb") as f:
-            np.savez(f, a=self.a, b=self.b, w=self.w, core2=self.core2, ids=self.ids, atoms=self.atoms,
-                     min_samples=np.array(self.min_samples, dtype=np.int64), lone_position=np.array(self.lone_position, dtype=np.int64), level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
-
-    @classmethod
-    def load(cls, model, path):
-        """The saved hierarchy; ValueError if its level's width is not this model's."""
-        with np.load(path, allow_pickle=False) as z:
-            level, dim = str(z["level"]), int(z["dim"])
-            args = (z["a"], z["b"], z["w"], z["core2"], len(z["ids"]), z["ids"], z["atoms"], int(z["min_samples"]))
-            lone = int(z["lone_position"])
-        if level not in LEVELS or level_dim(model.config, level) != dim:
-            raise ValueError("%s: a %s-level hierarchy of %d columns does not fit a model whose %s is %d" % (
-                path, level, dim, "dense_out" if level == "structure" else "global_dim", level_dim(model.config, level) if level in LEVELS else -1))
-        return cls(*args, level, dim, lone)

@@ -7,6 +7,7 @@ pretrained, mode)``, ``.model.predict(inputs)``, ``.prepare_dataset``, ``.evalua
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import io
 import json
@@ -16,7 +17,7 @@ import numpy as np
 
 from .. import _hip
 from .latent_index import (EMBED_NEIGHBOURS, LatentClassHead, LatentClustering, LatentEmbedding, LatentHead, LatentHierarchy, LatentIndex, LatentKernelHead,
-                           LatentProjection, batch_jobs, check_min_cluster_size, density_of_sums, embed_fit_args, hierarchy_fit_args, level_dim, peaks_fit_args,
+                           LatentProjection, batch_jobs, check_min_cluster_size, count_structures, density_of_sums, embed_fit_args, hierarchy_fit_args, level_dim, peaks_fit_args,
                            stop_dist2_of)
 
 INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_weight", "neighbor_distance"]
@@ -120,6 +121,53 @@ def _output_selection(names, n_attention):
         elif n not in OUTPUT_NAMES:
             raise ValueError("unknown output %r (known: %s, local_attention_<k>)" % (n, ", ".join(OUTPUT_NAMES)))
     return names, sorted(set(layers)), "after_Lc" in names, "bf_property" in names
+
+
+# -- the steps the analysis methods of HipModel share: a new analysis uses these rather than a neighbour's lines --
+
+def _expect(value, cls, noun):
+    """ValueError unless ``value`` is the artefact a method takes"""
+    if not isinstance(value, cls):
+        raise ValueError("%s must be a %s, got %r" % (noun, cls.__name__, type(value).__name__))
+
+
+def _level_of(data, level):
+    """The level in force: a ``LatentIndex``'s own, ``level`` for data that is yet to be indexed"""
+    return data.level if isinstance(data, LatentIndex) else level
+
+
+def _flat_per_structure(values, level, noun, dtype=None):
+    """Atom-level targets or labels given as one array per structure -> one array in packed order (anything else: as it is).  With a
+    ``dtype`` every structure's array is rows [n, ...] of that type, without one a vector."""
+    if level == "atom" and isinstance(values, (list, tuple)) and len(values) and np.ndim(values[0]) >= 1:
+        try:
+            if dtype is None:
+                return np.concatenate([np.asarray(x).reshape(-1) for x in values])
+            return np.concatenate([np.asarray(x, dtype=dtype).reshape(len(x), -1) for x in values])
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a flat array in packed order or one array per structure" % noun) from None
+    return values
+
+
+def _exclude_ids_arg(inputs, exclude_ids):
+    """``exclude_ids`` as int64 [B], one per structure of ``inputs`` (None stays None); ValueError for another count"""
+    if exclude_ids is None:
+        return None
+    B = count_structures(inputs)
+    qid = np.ascontiguousarray(exclude_ids, dtype=np.int64).reshape(-1)
+    if qid.shape[0] != B:
+        raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
+    return qid
+
+
+def _repad(out, inputs, level, fills, dtypes=None):
+    """The per-atom entries of ``out`` -- ``fills``: {name: value at padded atoms} -- from packed [n_atom, ...] to [B, M, ...] when the
+    rows are atoms and ``inputs`` is a padded dict; a ``PackedBatch`` keeps them packed.  ``dtypes``: {name: dtype} for entries that
+    are not to come back as fp32 (``_hip.repad_atoms``).  Returns ``out``."""
+    if level == "atom" and not isinstance(inputs, _hip.PackedBatch):
+        for n, fill in fills.items():
+            out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill, dtype=(dtypes or {}).get(n))
+    return out
 
 
 
@@ -358,34 +406,22 @@ class HipModel:
         hyper.batch_size).  A k outside 1 .. 32, an index of another model or width, or a bad batch_size raise ValueError before anything
         is uploaded."""
         k = _hip.check_knn_k(k)
-        if not isinstance(index, LatentIndex):
-            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        _expect(index, LatentIndex, "index")
         index.check_model(self)
-        is_packed = isinstance(inputs, _hip.PackedBatch)
-        B = inputs.n_struct if is_packed else int(np.shape(inputs["neighbors"])[0])
-        qid = None
-        if exclude_ids is not None:
-            qid = np.ascontiguousarray(exclude_ids, dtype=np.int64).reshape(-1)
-            if qid.shape[0] != B:
-                raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(
-            index._ix, rb, lvl, k, None if qid is None else qid[s0:s1]))
-        empty = {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
-                 "atom": np.zeros((0, k), np.int32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        qid = _exclude_ids_arg(inputs, exclude_ids)
+        eng, lvl = self.engine, _hip.KNN_LEVELS[index.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(
+            index._ix, rb, lvl, k, None if qid is None else qid[s0:s1]),
+            {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64), "atom": np.zeros((0, k), np.int32)})
         dist = np.sqrt(cat["dist2"])  # correctly rounded on the host: no device square root enters the definition
         mean = np.zeros(dist.shape[0], dtype=np.float32)
         for j in range(k):  # fp32, places in order
             mean = mean + dist[:, j]
         mean = (mean / np.float32(k)).astype(np.float32)[:, None]
         out = {"predict_property": cat["y"].reshape(-1, 1), "distance": dist, "neighbor_id": cat["id"], "latent_distance": mean}
-        if atom:
+        if index.level == "atom":
             out["neighbor_atom"] = cat["atom"]
-            if not is_packed:
-                for n, fill in (("distance", 0), ("latent_distance", 0), ("neighbor_id", -1), ("neighbor_atom", -1)):
-                    out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
-        return out
+        return _repad(out, inputs, index.level, {"distance": 0, "latent_distance": 0, "neighbor_id": -1, "neighbor_atom": -1})
 
     def match_structures(self, inputs, index, k=5, measure="chamfer", exclude_ids=None, batch_size=None):
         """The ``k`` structures of an atom-level ``LatentIndex`` that are made of the same local structures as each structure of
@@ -403,41 +439,31 @@ class HipModel:
         batch_size or exclude_ids length, or a structure of more than _hip.MATCH_MAX_ATOMS atoms raise ValueError before anything is
         uploaded."""
         k, ms = _hip.check_knn_k(k), _hip.check_match_measure(measure)
-        if not isinstance(index, LatentIndex):
-            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        _expect(index, LatentIndex, "index")
         index.check_model(self)
         if index.level != "atom":
             raise ValueError("match_structures compares structures atom by atom: it needs an atom-level index, got a %s-level one" % index.level)
         self._batch_size(batch_size)
         is_packed = isinstance(inputs, _hip.PackedBatch)
-        B = inputs.n_struct if is_packed else int(np.shape(inputs["neighbors"])[0])
-        n_at = np.diff(inputs.mol_offset) if is_packed else (np.asarray(inputs["atom_mask"]).reshape(B, -1) != 0).sum(1)
+        n_at = np.diff(inputs.mol_offset) if is_packed else (np.asarray(inputs["atom_mask"]).reshape(count_structures(inputs), -1) != 0).sum(1)
         big = np.nonzero(n_at > _hip.MATCH_MAX_ATOMS)[0]
         if big.size:
             raise ValueError("structure %d has %d atoms, more than the %d a query structure may have" % (
                 big[0], int(n_at[big[0]]), _hip.MATCH_MAX_ATOMS))
-        qid = None
-        if exclude_ids is not None:
-            qid = np.ascontiguousarray(exclude_ids, dtype=np.int64).reshape(-1)
-            if qid.shape[0] != B:
-                raise ValueError("exclude_ids: %d structures need %d ids, got %d" % (B, B, qid.shape[0]))
+        qid = _exclude_ids_arg(inputs, exclude_ids)
         eng = self.engine
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_match_batch(
-            index._ix, rb, k, ms, None if qid is None else qid[s0:s1]))
-        empty = {"y": np.zeros(0, np.float32), "score": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
-                 "size": np.zeros((0, k), np.int32), "parts": np.zeros((0, k, 4), np.float32),
-                 "match_position": np.zeros((0, k), np.int32), "match_dist2": np.zeros((0, k), np.float32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_match_batch(
+            index._ix, rb, k, ms, None if qid is None else qid[s0:s1]),
+            {"y": np.zeros(0, np.float32), "score": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
+             "size": np.zeros((0, k), np.int32), "parts": np.zeros((0, k, 4), np.float32),
+             "match_position": np.zeros((0, k), np.int32), "match_dist2": np.zeros((0, k), np.float32)})
         _, atoms = eng.index_names(index._ix)  # (host copies: the rows stay on the device)
         pos = cat["match_position"]
         matched = np.where(pos >= 0, atoms[np.maximum(pos, 0)] if len(atoms) else -1, -1).astype(np.int32)
         out = {"predict_property": cat["y"].reshape(-1, 1), "distance": np.sqrt(cat["score"]),  # (correctly rounded on the host, as nearest)
                "neighbor_id": cat["id"], "neighbor_size": cat["size"], "parts": cat["parts"], "matched_atom": matched,
                "matched_distance": np.sqrt(cat["match_dist2"])}
-        if not is_packed:
-            out["matched_atom"] = _hip.repad_atoms(out["matched_atom"], inputs["atom_mask"], -1)
-            out["matched_distance"] = _hip.repad_atoms(out["matched_distance"], inputs["atom_mask"], 0)
-        return out
+        return _repad(out, inputs, "atom", {"matched_atom": -1, "matched_distance": 0})
 
     def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
         """Which ``m`` structures (or atoms, ``level`` "atom") of ``pool`` to label next: greedy k-center selection in the model's latent
@@ -459,18 +485,11 @@ class HipModel:
             level = pool.level
         if isinstance(reference, LatentIndex) and reference.level != level:
             raise ValueError("the reference is a %s-level index, the pool's level is %s" % (reference.level, level))
-        own = []
-        try:
-            if not isinstance(pool, LatentIndex):
-                pool = self.build_index(pool, level=level, batch_size=batch_size)
-                own.append(pool)
-            if reference is not None and not isinstance(reference, LatentIndex):
-                reference = self.build_index(reference, level=level, batch_size=batch_size)
-                own.append(reference)
+        with contextlib.ExitStack() as scope:
+            pool = scope.enter_context(self._indexed(pool, level, batch_size=batch_size))
+            if reference is not None:
+                reference = scope.enter_context(self._indexed(reference, level, batch_size=batch_size))
             return pool.select(m, reference=reference, stop_distance=stop_distance)
-        finally:
-            for ix in own:
-                ix.free()
 
     def cluster(self, data, k, level="atom", init="kcenter", max_iter=50, stop_changed=0, ids=None, batch_size=None):
         """Which kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``) the
@@ -486,27 +505,17 @@ class HipModel:
             if init != "kcenter":
                 raise ValueError('init must be "kcenter", %d positions or an array of %d centres, got %r' % (k, k, init))
         elif np.asarray(init).dtype.kind not in "iu":
-            _hip.check_kmeans_init(init, level_dim(self.config, data.level if isinstance(data, LatentIndex) else level))
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+            _hip.check_kmeans_init(init, level_dim(self.config, _level_of(data, level)))
+        with self._indexed(data, level, ids, batch_size) as index:
             result = index.cluster(k, init=init, max_iter=max_iter, stop_changed=stop_changed)
             return result, LatentClustering(result["centre"], index.level, index.dim)
-        finally:
-            if own is not None:
-                own.free()
 
     def silhouette(self, index, labels, sample=None, seed=0, metric="euclidean", route="device", table=False, n_clusters=None):
         """How good a labelling of an index's rows is: the silhouette of every row and its mean, every mean distance over all rows of
         the index from one exact pass over all pairs on the GPU, bit-reproducible (``LatentIndex.silhouette``, whose arguments and dict
         these are).  ``labels`` come from ``cluster``, ``density_peaks`` or ``hierarchy``.  An index of another model and bad
         arguments raise ValueError before any device call."""
-        if not isinstance(index, LatentIndex):
-            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        _expect(index, LatentIndex, "index")
         index.check_model(self)
         return index.silhouette(labels, sample=sample, seed=seed, metric=metric, route=route, table=table, n_clusters=n_clusters)
 
@@ -521,7 +530,7 @@ class HipModel:
         centres, which ``assign`` takes and which can be saved.  Bad arguments raise ValueError before anything is uploaded."""
         from .latent_index import choose_k_arg, silhouette_route, silhouette_sample_arg
 
-        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        level_dim(self.config, _level_of(data, level))
         ks = choose_k_arg(ks)
         silhouette_route(route)
         if metric not in _hip.SILHOUETTE_METRICS:
@@ -531,19 +540,10 @@ class HipModel:
         if isinstance(init, str) and init != "kcenter":
             raise ValueError('init must be "kcenter" for a sweep over k, got %r' % (init,))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             table = index.choose_k(ks, sample=sample, seed=seed, metric=metric, route=route, init=init, max_iter=max_iter,
                                    stop_changed=stop_changed)
             return table, LatentClustering(table["best"]["centre"], index.level, index.dim)
-        finally:
-            if own is not None:
-                own.free()
 
     def assign(self, inputs, clustering, batch_size=None):
         """The cluster of every structure (or, for an atom-level clustering, every atom) of new ``inputs``, right behind their forward:
@@ -551,8 +551,7 @@ class HipModel:
         definition (first centre under (distance, index)).  A padded dict gives {"predict_property": [B, 1], "cluster": int32 [B],
         "distance": fp32 [B]} and at atom level [B, M] arrays with -1 / 0 at padded atoms; a ``PackedBatch`` gives packed [n_atom]
         arrays.  Raw y.  A clustering of another width or a bad batch_size raise ValueError before anything is uploaded."""
-        if not isinstance(clustering, LatentClustering):
-            raise ValueError("clustering must be a LatentClustering, got %r" % (type(clustering).__name__,))
+        _expect(clustering, LatentClustering, "clustering")
         clustering.check_model(self)
         self._batch_size(batch_size)
         r = self.nearest(inputs, clustering.index_on(self), k=1, batch_size=batch_size)
@@ -565,21 +564,12 @@ class HipModel:
         is indexed for the call (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(result, projection)``:
         ``LatentIndex.pca``'s dict -- the map of ``data`` itself -- and the ``LatentProjection`` that ``project`` takes and that can be
         saved.  Bad arguments raise ValueError before anything is uploaded."""
-        dim = level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        dim = level_dim(self.config, _level_of(data, level))
         if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= dim:
             raise ValueError("m must be an integer in 1 .. %d, got %r" % (dim, m))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.pca(int(m))
-        finally:
-            if own is not None:
-                own.free()
 
     def fit_embedding(self, data, level="structure", perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto",
                       route="device", ids=None, batch_size=None):
@@ -589,20 +579,11 @@ class HipModel:
         which is indexed for the call (``ids``: one per structure, default 0 .. n-1) and freed afterwards -- ``place`` needs the index,
         so keep one to place new inputs later.  Returns ``(result, embedding)``.  Bad arguments raise ValueError before anything is
         uploaded."""
-        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        level_dim(self.config, _level_of(data, level))
         embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route)
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.embed(perplexity=perplexity, iterations=iterations, exaggeration=exaggeration, learning_rate=learning_rate, route=route)
-        finally:
-            if own is not None:
-                own.free()
 
     def map_quality(self, data_or_index, coords, level="structure", k=15, sample=None, seed=0, route="device", graph=None, ids=None,
                     batch_size=None):
@@ -614,23 +595,14 @@ class HipModel:
         and freed afterwards.  An index of another model and bad arguments raise ValueError before any device call."""
         from .latent_index import silhouette_route, silhouette_sample_arg
 
-        level_dim(self.config, data_or_index.level if isinstance(data_or_index, LatentIndex) else level)
+        level_dim(self.config, _level_of(data_or_index, level))
         silhouette_route(route)
         silhouette_sample_arg(sample if np.ndim(sample) == 0 else None, seed, 0)  # (positions are checked against the index, once it is there)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31:
             raise ValueError("k must be an integer in 1 .. 31, got %r" % (k,))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data_or_index, LatentIndex):
-                data_or_index.check_model(self)
-                index = data_or_index
-            else:
-                index = own = self.build_index(data_or_index, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data_or_index, level, ids, batch_size) as index:
             return index.map_quality(coords, k=k, sample=sample, seed=seed, route=route, graph=graph)
-        finally:
-            if own is not None:
-                own.free()
 
     def choose_perplexity(self, data, perplexities, level="structure", k=15, sample=None, seed=0, iterations=(250, 500), exaggeration=12.0,
                           learning_rate="auto", route="device", ids=None, batch_size=None):
@@ -643,25 +615,16 @@ class HipModel:
         anything is uploaded."""
         from .latent_index import choose_perplexity_arg, silhouette_sample_arg
 
-        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        level_dim(self.config, _level_of(data, level))
         perplexities = choose_perplexity_arg(perplexities)
         embed_fit_args(perplexities[0], iterations, exaggeration, learning_rate, route)
         silhouette_sample_arg(sample if np.ndim(sample) == 0 else None, seed, 0)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 31:
             raise ValueError("k must be an integer in 1 .. 31, got %r" % (k,))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.choose_perplexity(perplexities, k=k, sample=sample, seed=seed, iterations=iterations, exaggeration=exaggeration,
                                            learning_rate=learning_rate, route=route)
-        finally:
-            if own is not None:
-                own.free()
 
     def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
                       ids=None, batch_size=None):
@@ -672,20 +635,11 @@ class HipModel:
         default 0 .. n-1) and freed afterwards.  Returns ``(result, peaks)``: ``LatentIndex.density_peaks``'s dict and the
         ``LatentPeaks`` whose ``label_of`` labels the positions ``nearest(k=1)`` reports.  Bad arguments raise ValueError before anything
         is uploaded."""
-        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        level_dim(self.config, _level_of(data, level))
         peaks_fit_args(k, bandwidth, neighbours, min_density, min_delta, route)
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.density_peaks(k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density, min_delta=min_delta, route=route)
-        finally:
-            if own is not None:
-                own.free()
 
     def hierarchy(self, data, level="atom", min_samples=5, min_cluster_size=None, route="device", ids=None, batch_size=None):
         """How the kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``)
@@ -695,22 +649,13 @@ class HipModel:
         (``ids``: one per structure, default 0 .. n-1) and freed afterwards.  Returns ``(result, hierarchy)``:
         ``LatentIndex.hierarchy``'s dict -- with ``min_cluster_size`` also the entries of ``hierarchy.clusters(min_cluster_size)`` --
         and the ``LatentHierarchy`` that ``attach`` takes.  Bad arguments raise ValueError before anything is uploaded."""
-        level_dim(self.config, data.level if isinstance(data, LatentIndex) else level)
+        level_dim(self.config, _level_of(data, level))
         hierarchy_fit_args(min_samples, route)
         if min_cluster_size is not None:
             check_min_cluster_size(min_cluster_size)
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             result, h = index.hierarchy(min_samples=min_samples, route=route)
-        finally:
-            if own is not None:
-                own.free()
         if min_cluster_size is not None:
             result.update(h.clusters(min_cluster_size))
         return result, h
@@ -724,10 +669,8 @@ class HipModel:
         "nearest_position": int32 [B], "nearest_id": int64 [B], "nearest_atom": int32 [B], "nearest_distance": fp32 [B]} and at atom
         level [B, M] arrays with -1 / 0 at padded atoms; a ``PackedBatch`` gives packed arrays.  Raw y.  A hierarchy of another width
         or size than the index, or a bad min_cluster_size or batch_size, raise ValueError before anything is uploaded."""
-        if not isinstance(hierarchy, LatentHierarchy):
-            raise ValueError("hierarchy must be a LatentHierarchy, got %r" % (type(hierarchy).__name__,))
-        if not isinstance(index, LatentIndex):
-            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        _expect(hierarchy, LatentHierarchy, "hierarchy")
+        _expect(index, LatentIndex, "index")
         hierarchy.check_model(self)
         index.check_model(self)
         if hierarchy.level != index.level or len(hierarchy) != len(index) or len(index) < 1:
@@ -735,21 +678,16 @@ class HipModel:
                 hierarchy.level, len(hierarchy), index.level, len(index)))
         clusters = hierarchy.clusters(min_cluster_size)
         self._batch_size(batch_size)
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, 1))
-        empty = {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "dist2": np.zeros((0, 1), np.float32),
-                 "position": np.zeros((0, 1), np.int32), "id": np.zeros((0, 1), np.int64), "atom": np.zeros((0, 1), np.int32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl = self.engine, _hip.KNN_LEVELS[index.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, 1),
+                            {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "dist2": np.zeros((0, 1), np.float32),
+                             "position": np.zeros((0, 1), np.int32), "id": np.zeros((0, 1), np.int64), "atom": np.zeros((0, 1), np.int32)})
         pos, d2 = cat["position"][:, 0], cat["dist2"][:, 0]
-        packed = isinstance(inputs, _hip.PackedBatch)
         out = {"predict_property": cat["y"].reshape(-1, 1),
-               "global_attention": cat["ga"] if packed else _hip.repad_atoms(cat["ga"], inputs["atom_mask"])[..., None],
+               "global_attention": cat["ga"] if isinstance(inputs, _hip.PackedBatch) else _hip.repad_atoms(cat["ga"], inputs["atom_mask"])[..., None],
                "label": hierarchy.attach_labels(pos, d2, clusters), "nearest_position": pos, "nearest_id": cat["id"][:, 0],
                "nearest_atom": cat["atom"][:, 0], "nearest_distance": np.sqrt(d2)}
-        if atom and not packed:
-            for n, fill in (("label", -1), ("nearest_position", -1), ("nearest_id", -1), ("nearest_atom", -1), ("nearest_distance", 0)):
-                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
-        return out
+        return _repad(out, inputs, index.level, {"label": -1, "nearest_position": -1, "nearest_id": -1, "nearest_atom": -1, "nearest_distance": 0})
 
     def density(self, inputs, index, bandwidth, batch_size=None):
         """The Gaussian kernel density of every structure (or, for an atom-level index, every atom) of ``inputs`` under the rows of a
@@ -759,20 +697,15 @@ class HipModel:
         "density": fp64 [B] -- the mean kernel weight to the index's rows, 2^-30 sum / len(index) --, "sum": int64 [B], the exact
         fixed-point sum} and at atom level [B, M] arrays with 0 / -1 at padded atoms; a ``PackedBatch`` gives packed [n_atom] arrays.
         Raw y.  An index of another model or width, a bad bandwidth or batch_size raise ValueError before anything is uploaded."""
-        if not isinstance(index, LatentIndex):
-            raise ValueError("index must be a LatentIndex, got %r" % (type(index).__name__,))
+        _expect(index, LatentIndex, "index")
         index.check_model(self)
         gamma = _hip.rbf_gamma(bandwidth)
         self._batch_size(batch_size)
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.density_batch(index._ix, rb, lvl, gamma))
-        empty = {"y": np.zeros(0, np.float32), "sum": np.zeros(0, np.int64)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl = self.engine, _hip.KNN_LEVELS[index.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.density_batch(index._ix, rb, lvl, gamma),
+                            {"y": np.zeros(0, np.float32), "sum": np.zeros(0, np.int64)})
         out = {"predict_property": cat["y"].reshape(-1, 1), "density": density_of_sums(cat["sum"], len(index)), "sum": cat["sum"]}
-        if atom and not isinstance(inputs, _hip.PackedBatch):
-            out["density"] = _hip.repad_atoms(out["density"], inputs["atom_mask"], 0, dtype=np.float64)
-            out["sum"] = _hip.repad_atoms(out["sum"], inputs["atom_mask"], -1)
-        return out
+        return _repad(out, inputs, index.level, {"density": 0, "sum": -1}, dtypes={"density": np.float64})
 
     def place(self, inputs, embedding, index, batch_size=None):
         """New ``inputs`` on an existing map, right behind their forward: for every structure (or, at atom level, every atom) its 31
@@ -782,23 +715,18 @@ class HipModel:
         [B], "nearest_id": int64 [B], "nearest_atom": int32 [B], "nearest_distance": fp32 [B]} and at atom level [B, M, 2] / [B, M] arrays
         with 0 / -1 at padded atoms; a ``PackedBatch`` gives packed arrays.  Raw y.  An embedding of another width or index, or a bad
         batch_size, raise ValueError before anything is uploaded."""
-        if not isinstance(embedding, LatentEmbedding):
-            raise ValueError("embedding must be a LatentEmbedding, got %r" % (type(embedding).__name__,))
+        _expect(embedding, LatentEmbedding, "embedding")
         embedding.check_model(self)
         embedding.check_index(index)
         index.check_model(self)
         self._batch_size(batch_size)
         k = min(EMBED_NEIGHBOURS, len(index))
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[index.level], index.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, k))
-        empty = {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "position": np.zeros((0, k), np.int32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl = self.engine, _hip.KNN_LEVELS[index.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, k),
+                            {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, k), np.float32), "position": np.zeros((0, k), np.int32)})
         out = embedding.place(cat["position"], cat["dist2"])
         out["predict_property"] = cat["y"].reshape(-1, 1)
-        if atom and not isinstance(inputs, _hip.PackedBatch):
-            for n, fill in (("coords", 0), ("nearest_position", -1), ("nearest_id", -1), ("nearest_atom", -1), ("nearest_distance", 0)):
-                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], fill)
-        return out
+        return _repad(out, inputs, index.level, {"coords": 0, "nearest_position": -1, "nearest_id": -1, "nearest_atom": -1, "nearest_distance": 0})
 
     def project(self, inputs, projection, batch_size=None):
         """New ``inputs`` on a ``LatentProjection``'s map, right behind their forward (scann_project_batch): the coordinates, the
@@ -807,22 +735,16 @@ class HipModel:
         "mahalanobis": [B], "distance_to_mean": [B]} and at atom level [B, M, m] / [B, M] arrays with 0 at padded atoms; a
         ``PackedBatch`` gives packed [n_atom, m] / [n_atom] arrays.  Raw y.  A projection of another width or a bad batch_size raise
         ValueError before anything is uploaded."""
-        if not isinstance(projection, LatentProjection):
-            raise ValueError("projection must be a LatentProjection, got %r" % (type(projection).__name__,))
+        _expect(projection, LatentProjection, "projection")
         projection.check_model(self)
         self._batch_size(batch_size)
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[projection.level], projection.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.project_batch(
-            rb, lvl, projection.mean, projection.components, projection.scale))
-        m = projection.m
-        empty = {"y": np.zeros(0, np.float32), "coords": np.zeros((0, m), np.float32), "md2": np.zeros(0, np.float32), "dist2": np.zeros(0, np.float32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl = self.engine, _hip.KNN_LEVELS[projection.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.project_batch(
+            rb, lvl, projection.mean, projection.components, projection.scale),
+            {"y": np.zeros(0, np.float32), "coords": np.zeros((0, projection.m), np.float32), "md2": np.zeros(0, np.float32), "dist2": np.zeros(0, np.float32)})
         out = projection.finish(cat)
         out["predict_property"] = cat["y"].reshape(-1, 1)
-        if atom and not isinstance(inputs, _hip.PackedBatch):
-            for n in ("coordinates", "mahalanobis", "distance_to_mean"):
-                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
-        return out
+        return _repad(out, inputs, projection.level, {"coordinates": 0, "mahalanobis": 0, "distance_to_mean": 0})
 
     def fit_head(self, data, targets, level="structure", l2="loo", ids=None, batch_size=None, names=None):
         """A linear readout head for another property on the model's frozen latent space (``LatentIndex.fit_head``): ridge regression of
@@ -831,30 +753,17 @@ class HipModel:
         GPU.  ``data`` is a ``LatentIndex`` (its level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for
         the call and freed afterwards.  Returns ``(result, head)``; the ``LatentHead`` is what ``predict_head`` takes and can be saved.
         Bad arguments raise ValueError before anything is uploaded."""
-        lvl = data.level if isinstance(data, LatentIndex) else level
-        level_dim(self.config, lvl)
-        if lvl == "atom" and isinstance(targets, (list, tuple)) and len(targets) and np.ndim(targets[0]) >= 1:
-            try:
-                targets = np.concatenate([np.asarray(x, dtype=np.float32).reshape(len(x), -1) for x in targets])
-            except (TypeError, ValueError):
-                raise ValueError("targets must be a flat array in packed order or one array per structure") from None
-        t = _hip.check_head_targets(targets, len(data) if isinstance(data, LatentIndex) else None)
         from .latent_index import head_grid
+
+        lvl = _level_of(data, level)
+        level_dim(self.config, lvl)
+        t = _hip.check_head_targets(_flat_per_structure(targets, lvl, "targets", np.float32), len(data) if isinstance(data, LatentIndex) else None)
         head_grid(l2)
         if names is not None and len(names) != t.shape[1]:
             raise ValueError("names: %d for %d targets" % (len(names), t.shape[1]))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.fit_head(t, l2=l2, names=names)
-        finally:
-            if own is not None:
-                own.free()
 
     def predict_head(self, inputs, head, batch_size=None):
         """New ``inputs`` through a ``LatentHead``, right behind their forward (scann_head_batch): the head's prediction of its K
@@ -863,22 +772,16 @@ class HipModel:
         "std", "leverage": fp32 [B, K], "y": [B, 1] (the model's own raw prediction)} and at atom level [B, M, K] arrays with 0 at padded
         atoms; a ``PackedBatch`` gives packed [n_atom, K] arrays.  A head of another width or a bad batch_size raise ValueError before
         anything is uploaded."""
-        if not isinstance(head, LatentHead):
-            raise ValueError("head must be a LatentHead, got %r" % (type(head).__name__,))
+        _expect(head, LatentHead, "head")
         head.check_model(self)
         self._batch_size(batch_size)
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.head_batch(
-            rb, lvl, head.mean, head.tmean, head.weights, head.components, head.scale, head.lev0))
-        K = head.k
-        empty = {"y": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32), "lev": np.zeros((0, K), np.float32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl, K = self.engine, _hip.KNN_LEVELS[head.level], head.k
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.head_batch(
+            rb, lvl, head.mean, head.tmean, head.weights, head.components, head.scale, head.lev0),
+            {"y": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32), "lev": np.zeros((0, K), np.float32)})
         out = head.finish(cat["pred"], cat["lev"])
         out["y"] = cat["y"].reshape(-1, 1)
-        if atom and not isinstance(inputs, _hip.PackedBatch):
-            for n in ("prediction", "std", "leverage"):
-                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
-        return out
+        return _repad(out, inputs, head.level, {"prediction": 0, "std": 0, "leverage": 0})
 
     def fit_kernel_head(self, data, targets, level="structure", landmarks=256, bandwidth="loo", l2="loo", ids=None, batch_size=None, names=None):
         """A nonlinear readout head for another property on the model's frozen latent space (``LatentIndex.fit_kernel_head``): ridge
@@ -888,31 +791,17 @@ class HipModel:
         saved.  Bad arguments raise ValueError before anything is uploaded."""
         from .latent_index import head_grid, kernel_bandwidth_arg, kernel_landmarks_arg
 
-        lvl = data.level if isinstance(data, LatentIndex) else level
+        lvl = _level_of(data, level)
         level_dim(self.config, lvl)
-        if lvl == "atom" and isinstance(targets, (list, tuple)) and len(targets) and np.ndim(targets[0]) >= 1:
-            try:
-                targets = np.concatenate([np.asarray(x, dtype=np.float32).reshape(len(x), -1) for x in targets])
-            except (TypeError, ValueError):
-                raise ValueError("targets must be a flat array in packed order or one array per structure") from None
-        t = _hip.check_head_targets(targets, len(data) if isinstance(data, LatentIndex) else None)
+        t = _hip.check_head_targets(_flat_per_structure(targets, lvl, "targets", np.float32), len(data) if isinstance(data, LatentIndex) else None)
         head_grid(l2)
         kernel_landmarks_arg(landmarks, len(data) if isinstance(data, LatentIndex) else len(t))
         kernel_bandwidth_arg(bandwidth)
         if names is not None and len(names) != t.shape[1]:
             raise ValueError("names: %d for %d targets" % (len(names), t.shape[1]))
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.fit_kernel_head(t, landmarks=landmarks, bandwidth=bandwidth, l2=l2, names=names)
-        finally:
-            if own is not None:
-                own.free()
 
     def predict_kernel_head(self, inputs, head, batch_size=None):
         """New ``inputs`` through a ``LatentKernelHead``, right behind their forward (scann_rbf_head_batch): the head's prediction of its K
@@ -922,25 +811,19 @@ class HipModel:
         model's own raw prediction), "ga": [B, M, 1]} and at atom level [B, M, K] / [B, M] arrays with 0 at padded atoms; a
         ``PackedBatch`` gives packed [n_atom, ...] arrays.  A head of another width or a bad batch_size raise ValueError before anything
         is uploaded."""
-        if not isinstance(head, LatentKernelHead):
-            raise ValueError("head must be a LatentKernelHead, got %r" % (type(head).__name__,))
+        _expect(head, LatentKernelHead, "head")
         head.check_model(self)
         self._batch_size(batch_size)
-        eng, lvl, atom, h = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom", head.head
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.rbf_head_batch(
-            rb, lvl, head.landmarks, head.gamma, h.mean, h.tmean, h.weights, h.components, h.scale, h.lev0))
-        K = head.k
-        empty = {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32),
-                 "lev": np.zeros((0, K), np.float32), "phi": np.zeros((0, head.m), np.float32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl, h, K = self.engine, _hip.KNN_LEVELS[head.level], head.head, head.k
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.rbf_head_batch(
+            rb, lvl, head.landmarks, head.gamma, h.mean, h.tmean, h.weights, h.components, h.scale, h.lev0),
+            {"y": np.zeros(0, np.float32), "ga": np.zeros(0, np.float32), "pred": np.zeros((0, K), np.float32),
+             "lev": np.zeros((0, K), np.float32), "phi": np.zeros((0, head.m), np.float32)})
         out = head.finish(cat["pred"], cat["lev"], cat["phi"])
         out["y"], out["ga"] = cat["y"].reshape(-1, 1), cat["ga"]
         if not isinstance(inputs, _hip.PackedBatch):
             out["ga"] = _hip.repad_atoms(out["ga"], inputs["atom_mask"], 0)[..., None]
-            if atom:
-                for n in ("prediction", "std", "leverage", "support"):
-                    out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
-        return out
+        return _repad(out, inputs, head.level, {"prediction": 0, "std": 0, "leverage": 0, "support": 0})
 
     def fit_class_head(self, data, labels, level="structure", l2="cv", folds=4, max_iter=100, tol=1e-4, classes=None, ids=None, batch_size=None):
         """A classification head on the model's frozen latent space (``LatentIndex.fit_class_head``): multinomial logistic regression of
@@ -952,29 +835,15 @@ class HipModel:
         before anything is uploaded."""
         from .latent_index import class_count_check, class_fit_args, class_labels_arg
 
-        lvl = data.level if isinstance(data, LatentIndex) else level
+        lvl = _level_of(data, level)
         level_dim(self.config, lvl)
-        if lvl == "atom" and isinstance(labels, (list, tuple)) and len(labels) and np.ndim(labels[0]) >= 1:
-            try:
-                labels = np.concatenate([np.asarray(x).reshape(-1) for x in labels])
-            except (TypeError, ValueError):
-                raise ValueError("labels must be a flat array in packed order or one array per structure") from None
-        labels = np.asarray(labels)
+        labels = np.asarray(_flat_per_structure(labels, lvl, "labels"))
         lab, cl = class_labels_arg(labels, classes, len(data) if isinstance(data, LatentIndex) else len(labels))
         _, f, _, _ = class_fit_args(l2, folds, max_iter, tol)
         class_count_check(np.bincount(lab[lab >= 0], minlength=len(cl)), cl, f)
         self._batch_size(batch_size)
-        own = None
-        try:
-            if isinstance(data, LatentIndex):
-                data.check_model(self)
-                index = data
-            else:
-                index = own = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
             return index.fit_class_head(labels, l2=l2, folds=folds, max_iter=max_iter, tol=tol, classes=classes)
-        finally:
-            if own is not None:
-                own.free()
 
     def predict_class_head(self, inputs, head, batch_size=None):
         """New ``inputs`` through a ``LatentClassHead``, right behind their forward (scann_logit_head_batch): the class probabilities,
@@ -983,20 +852,15 @@ class HipModel:
         "entropy": fp32 [B], "y": [B, 1] (the model's own raw prediction)} and at atom level [B, M, C] / [B, M] arrays with 0 at
         padded atoms; a ``PackedBatch`` gives packed [n_atom, ...] arrays.  A head of another width or a bad batch_size raise
         ValueError before anything is uploaded."""
-        if not isinstance(head, LatentClassHead):
-            raise ValueError("head must be a LatentClassHead, got %r" % (type(head).__name__,))
+        _expect(head, LatentClassHead, "head")
         head.check_model(self)
         self._batch_size(batch_size)
-        eng, lvl, atom = self.engine, _hip.KNN_LEVELS[head.level], head.level == "atom"
-        parts = self._run_chunks(inputs, batch_size, lambda rb, s0, s1: eng.logit_head_batch(rb, lvl, head.mean, head.weights))
-        empty = {"y": np.zeros(0, np.float32), "prob": np.zeros((0, head.c), np.float32)}
-        cat = {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+        eng, lvl = self.engine, _hip.KNN_LEVELS[head.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.logit_head_batch(rb, lvl, head.mean, head.weights),
+                            {"y": np.zeros(0, np.float32), "prob": np.zeros((0, head.c), np.float32)})
         out = head.finish(cat["prob"])
         out["y"] = cat["y"].reshape(-1, 1)
-        if atom and not isinstance(inputs, _hip.PackedBatch):
-            for n in ("probability", "label", "confidence", "entropy"):
-                out[n] = _hip.repad_atoms(out[n], inputs["atom_mask"], 0)
-        return out
+        return _repad(out, inputs, head.level, {"probability": 0, "label": 0, "confidence": 0, "entropy": 0})
 
     def predict_uncertainty(self, inputs, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None,
                             return_samples=False):
@@ -1110,6 +974,26 @@ class HipModel:
         upload = (lambda chunk: eng.upload(_hip.pack_inputs(chunk))) if host_pack else None
         self._pipeline(batch_jobs(self, data, self._batch_size(batch_size), upload), finish, launch=lambda rb, slot: None)
         return parts
+
+    def _run_cat(self, inputs, batch_size, call, empty):
+        """``_run_chunks`` for a call that returns a dict of arrays per chunk: the entries ``empty`` names, concatenated in chunk order;
+        ``empty`` itself -- the prototype, {name: array of no rows} -- for inputs without a structure."""
+        parts = self._run_chunks(inputs, batch_size, call)
+        return {n: np.concatenate([p[n] for p in parts]) if parts else empty[n] for n in empty}
+
+    @contextlib.contextmanager
+    def _indexed(self, data, level, ids=None, batch_size=None):
+        """The ``LatentIndex`` an analysis runs on: ``data`` itself if it is one of this model (ValueError otherwise), else ``data``
+        indexed at ``level`` for the length of the ``with`` block and freed on the way out, also on an error."""
+        if isinstance(data, LatentIndex):
+            data.check_model(self)
+            yield data
+            return
+        index = self.build_index(data, level=level, ids=ids, batch_size=batch_size)
+        try:
+            yield index
+        finally:
+            index.free()
 
     def _upload_padded(self, inputs):
         """A padded input dict (or row views of one) -> resident batch: feature = "atomic" without ring on an inference handle is
@@ -1512,152 +1396,6 @@ class SCANN:
             out[k] = out[k] * self.std + self.mean
         return out
 
-    def attention_rollout(self, ip, residual=0.5, head=None, depth=None, matrix=True, batch_size=None):
-        """HipModel.attention_rollout with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
-        scores, the attribution and the rollout are unitless shares and stay as they are."""
-        out = self.model.attention_rollout(ip, residual=residual, head=head, depth=depth, matrix=matrix, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def build_index(self, data, level="structure", ids=None, batch_size=None):
-        """HipModel.build_index: a ``LatentIndex`` of ``data`` on the model's GPU."""
-        return self.model.build_index(data, level=level, ids=ids, batch_size=batch_size)
-
-    def nearest(self, ip, index, k=5, exclude_ids=None, batch_size=None):
-        """HipModel.nearest with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
-        live in latent space and stay as they are."""
-        out = self.model.nearest(ip, index, k=k, exclude_ids=exclude_ids, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def match_structures(self, ip, index, k=5, measure="chamfer", exclude_ids=None, batch_size=None):
-        """HipModel.match_structures with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
-        distances live in latent space and stay as they are."""
-        out = self.model.match_structures(ip, index, k=k, measure=measure, exclude_ids=exclude_ids, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
-        """HipModel.select_diverse as it is: the distances live in latent space."""
-        return self.model.select_diverse(pool, m, reference=reference, level=level, stop_distance=stop_distance, batch_size=batch_size)
-
-    def cluster(self, data, k, level="atom", init="kcenter", max_iter=50, stop_changed=0, ids=None, batch_size=None):
-        """HipModel.cluster as it is: ``(result, clustering)``; the distances live in latent space."""
-        return self.model.cluster(data, k, level=level, init=init, max_iter=max_iter, stop_changed=stop_changed, ids=ids, batch_size=batch_size)
-
-    def silhouette(self, index, labels, sample=None, seed=0, metric="euclidean", route="device", table=False, n_clusters=None):
-        """HipModel.silhouette as it is: the distances live in latent space."""
-        return self.model.silhouette(index, labels, sample=sample, seed=seed, metric=metric, route=route, table=table, n_clusters=n_clusters)
-
-    def choose_k(self, data, ks, level="atom", sample=None, seed=0, metric="euclidean", init="kcenter", max_iter=50, stop_changed=0,
-                 route="device", ids=None, batch_size=None):
-        """HipModel.choose_k as it is: ``(table, clustering)``; the distances live in latent space."""
-        return self.model.choose_k(data, ks, level=level, sample=sample, seed=seed, metric=metric, init=init, max_iter=max_iter,
-                                   stop_changed=stop_changed, route=route, ids=ids, batch_size=batch_size)
-
-    def assign(self, ip, clustering, batch_size=None):
-        """HipModel.assign with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the distances
-        live in latent space and stay as they are."""
-        out = self.model.assign(ip, clustering, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def fit_projection(self, data, m=2, level="structure", ids=None, batch_size=None):
-        """HipModel.fit_projection as it is: ``(result, projection)``; the map lives in latent space."""
-        return self.model.fit_projection(data, m=m, level=level, ids=ids, batch_size=batch_size)
-
-    def fit_embedding(self, data, level="structure", perplexity=10, iterations=(250, 500), exaggeration=12.0, learning_rate="auto",
-                      route="device", ids=None, batch_size=None):
-        """HipModel.fit_embedding as it is: ``(result, embedding)``; the map lives in latent space."""
-        return self.model.fit_embedding(data, level=level, perplexity=perplexity, iterations=iterations, exaggeration=exaggeration,
-                                        learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
-
-    def map_quality(self, data_or_index, coords, level="structure", k=15, sample=None, seed=0, route="device", graph=None, ids=None,
-                    batch_size=None):
-        """HipModel.map_quality as it is: the ranks live in latent space and on the map."""
-        return self.model.map_quality(data_or_index, coords, level=level, k=k, sample=sample, seed=seed, route=route, graph=graph, ids=ids,
-                                      batch_size=batch_size)
-
-    def choose_perplexity(self, data, perplexities, level="structure", k=15, sample=None, seed=0, iterations=(250, 500), exaggeration=12.0,
-                          learning_rate="auto", route="device", ids=None, batch_size=None):
-        """HipModel.choose_perplexity as it is: ``(table, embedding)``; the maps live in latent space."""
-        return self.model.choose_perplexity(data, perplexities, level=level, k=k, sample=sample, seed=seed, iterations=iterations,
-                                            exaggeration=exaggeration, learning_rate=learning_rate, route=route, ids=ids, batch_size=batch_size)
-
-    def density_peaks(self, data, level="atom", k=None, bandwidth="auto", neighbours=31, min_density=None, min_delta=None, route="device",
-                      ids=None, batch_size=None):
-        """HipModel.density_peaks as it is: ``(result, peaks)``; densities and distances live in latent space."""
-        return self.model.density_peaks(data, level=level, k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density,
-                                        min_delta=min_delta, route=route, ids=ids, batch_size=batch_size)
-
-    def hierarchy(self, data, level="atom", min_samples=5, min_cluster_size=None, route="device", ids=None, batch_size=None):
-        """HipModel.hierarchy as it is: ``(result, hierarchy)``; weights and levels live in latent space."""
-        return self.model.hierarchy(data, level=level, min_samples=min_samples, min_cluster_size=min_cluster_size, route=route, ids=ids,
-                                    batch_size=batch_size)
-
-    def attach(self, ip, hierarchy, index, min_cluster_size, batch_size=None):
-        """HipModel.attach with ``predict_property`` in the units of the target (times std plus mean, as predict_data); labels and
-        distances live in latent space and stay as they are."""
-        out = self.model.attach(ip, hierarchy, index, min_cluster_size, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def density(self, ip, index, bandwidth, batch_size=None):
-        """HipModel.density with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the densities
-        live in latent space and stay as they are."""
-        out = self.model.density(ip, index, bandwidth, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def place(self, ip, embedding, index, batch_size=None):
-        """HipModel.place with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the coordinates
-        and the distances live on the map and in latent space and stay as they are."""
-        out = self.model.place(ip, embedding, index, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def project(self, ip, projection, batch_size=None):
-        """HipModel.project with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
-        coordinates and the distances live in latent space and stay as they are."""
-        out = self.model.project(ip, projection, batch_size=batch_size)
-        out["predict_property"] = out["predict_property"] * self.std + self.mean
-        return out
-
-    def fit_head(self, data, targets, level="structure", l2="loo", ids=None, batch_size=None, names=None):
-        """HipModel.fit_head as it is: ``(result, head)``; the head lives in latent space and in the units of ``targets``."""
-        return self.model.fit_head(data, targets, level=level, l2=l2, ids=ids, batch_size=batch_size, names=names)
-
-    def predict_head(self, ip, head, batch_size=None):
-        """HipModel.predict_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the head's
-        prediction, std and leverage are in the units of the head's targets and stay as they are."""
-        out = self.model.predict_head(ip, head, batch_size=batch_size)
-        out["y"] = out["y"] * self.std + self.mean
-        return out
-
-    def fit_kernel_head(self, data, targets, level="structure", landmarks=256, bandwidth="loo", l2="loo", ids=None, batch_size=None, names=None):
-        """HipModel.fit_kernel_head as it is: ``(result, head)``; the head lives in latent space and in the units of ``targets``."""
-        return self.model.fit_kernel_head(data, targets, level=level, landmarks=landmarks, bandwidth=bandwidth, l2=l2, ids=ids,
-                                          batch_size=batch_size, names=names)
-
-    def predict_kernel_head(self, ip, head, batch_size=None):
-        """HipModel.predict_kernel_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the
-        head's prediction, std, leverage and support stay as they are."""
-        out = self.model.predict_kernel_head(ip, head, batch_size=batch_size)
-        out["y"] = out["y"] * self.std + self.mean
-        return out
-
-    def fit_class_head(self, data, labels, level="structure", l2="cv", folds=4, max_iter=100, tol=1e-4, classes=None, ids=None, batch_size=None):
-        """HipModel.fit_class_head as it is: ``(result, head)``; the head lives in latent space."""
-        return self.model.fit_class_head(data, labels, level=level, l2=l2, folds=folds, max_iter=max_iter, tol=tol, classes=classes, ids=ids,
-                                         batch_size=batch_size)
-
-    def predict_class_head(self, ip, head, batch_size=None):
-        """HipModel.predict_class_head with ``y`` in the units of the model's own target (times std plus mean, as predict_data); the
-        probabilities, label, confidence and entropy stay as they are."""
-        out = self.model.predict_class_head(ip, head, batch_size=batch_size)
-        out["y"] = out["y"] * self.std + self.mean
-        return out
-
     def predict_uncertainty(self, ip, samples=30, seed=0, keys=None, rate=None, attention_rate=None, batch_size=None, return_samples=False):
         """HipModel.predict_uncertainty in the units of the target, as predict_data de-normalises: the mean times std plus mean, the
         standard deviation and the samples times |std|; the GlobalAttention scores as they are."""
@@ -1683,3 +1421,34 @@ class SCANN:
         if isinstance(out, list):  # infer mode (the reference tests len(out) == 2, scann_model.py:317)
             return out[0] * self.std + self.mean, out[1]
         return out * self.std + self.mean
+
+
+# The rest of the facade: HipModel's analysis methods under the same names.  (name, the one entry of the result that is a prediction of
+# the model's own target and is de-normalised as predict_data does -- None: the result passes through as it is; everything else lives in
+# latent space, on a map or in the units of a head's own targets).  Signature and defaults are HipModel's: they exist once.
+FACADE = (("attention_rollout", "predict_property"), ("build_index", None), ("nearest", "predict_property"),
+          ("match_structures", "predict_property"), ("select_diverse", None), ("cluster", None), ("silhouette", None), ("choose_k", None),
+          ("assign", "predict_property"), ("fit_projection", None), ("fit_embedding", None), ("map_quality", None), ("choose_perplexity", None),
+          ("density_peaks", None), ("hierarchy", None), ("attach", "predict_property"), ("density", "predict_property"),
+          ("place", "predict_property"), ("project", "predict_property"), ("fit_head", None), ("predict_head", "y"), ("fit_kernel_head", None),
+          ("predict_kernel_head", "y"), ("fit_class_head", None), ("predict_class_head", "y"))
+
+
+def _facade(name, key):
+    inner = getattr(HipModel, name)
+
+    @functools.wraps(inner)
+    def method(self, *args, **kwargs):
+        out = getattr(self.model, name)(*args, **kwargs)
+        if key is not None:
+            out[key] = out[key] * self.std + self.mean
+        return out
+
+    method.__qualname__ = "SCANN." + name
+    method.__doc__ = ("HipModel.%s as it is.\n\n" % name if key is None else
+                      "HipModel.%s with ``%s`` in the units of the target (times std plus mean, as predict_data).\n\n" % (name, key)) + inner.__doc__
+    return method
+
+
+for _name, _key in FACADE:
+    setattr(SCANN, _name, _facade(_name, _key))

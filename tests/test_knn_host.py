@@ -82,14 +82,16 @@ def test_selection_ties_exclusion_and_short_lists():
 # ---- the Python layer against a stand-in engine ----
 
 class _Ix:
-    def __init__(self, dim):
+    def __init__(self, dim, engine=None):
         self.dim, self.rows, self.ids, self.atoms = dim, np.zeros((0, dim), np.float32), np.zeros(0, np.int64), np.zeros(0, np.int32)
+        self.engine = engine  # the stand-in that counts this index's free
 
     def __len__(self):
         return len(self.rows)
 
     def free(self):
-        pass
+        if self.engine is not None:
+            self.engine.freed += 1
 
 
 class _StandIn:
@@ -99,7 +101,7 @@ class _StandIn:
 
     def __init__(self, cfg):
         self.cfg = types.SimpleNamespace(dense_out=int(cfg["model"]["dense_out"]), global_dim=int(cfg["model"]["global_dim"]))
-        self.uploads, self.calls, self.seen, self.created = 0, [], 0, 0
+        self.uploads, self.calls, self.seen, self.created, self.freed = 0, [], 0, 0, 0
 
     def num_streams(self):
         return 2
@@ -110,7 +112,7 @@ class _StandIn:
 
     def index_create(self, dim):
         self.created += 1
-        return _Ix(dim)
+        return _Ix(dim, self)
 
     def index_add(self, ix, rows, ids=None, atoms=None):
         rows = np.asarray(rows, np.float32)
