@@ -490,6 +490,72 @@ int scann_index_match_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_
 int scann_match_parts_host(const float* q, const int32_t* q_first, int64_t n_sets, const float* rows, const int32_t* seg_first, int64_t n_seg,
                            int64_t dim, float* parts /* [n_sets * n_seg * 4] */);
 
+/* ---- pairing: one-to-one atom maps between a query structure and a segment, the exact assignment on the device ----
+ * The measures of scann_index_match are best-match reductions: every atom picks its nearest partner on its own, so the correspondence is
+ * many-to-one and the score cannot count (rows {3 x a, 3 x b} against {5 x a, 1 x b}: chamfer 0).  The pairing solves the linear
+ * assignment problem over the matrix of squared distances (the best-match structural kernel of De et al., PCCP 2016) and returns a
+ * true atom map.  "assign" means cluster assignment in this library; this is called pairing everywhere.
+ *
+ * Definition, for a query structure A = a_0 .. a_{n-1} and a segment B = b_0 .. b_{m-1}, 1 <= n, m <= SCANN_PAIRING_MAX_ATOMS:
+ *  1. Distances.  D[i][j] = dist2(a_i, b_j), exactly the fp32 chain of scann_knn_distsq with the query atom as q.
+ *  2. Not comparable.  If any D[i][j] is NaN or +inf, or m > SCANN_PAIRING_MAX_ATOMS: score = +inf, total = -1, shift = 0, every
+ *     partner -1 and every partner distance +inf.
+ *  3. Per-pair fixed point.  Dmax = max D (exact).  shift = 30 - ilogbf(Dmax) for Dmax > 0 (the true exponent, subnormals included),
+ *     0 for Dmax = 0.  t[i][j] = llrint(ldexp((double) D[i][j], shift)): the scaling is exact, then one rounding to nearest even.  So
+ *     0 <= t <= 2^31 and the largest entry keeps 30 bits; shift lies in -97 .. 179.  No caller-chosen shift, no range error.
+ *  4. Square cost matrix.  Q = max(n, m); rows are the query side, columns the segment side.  C[i][j] = t[i][j] for i < n, j < m.  For
+ *     n < m the dummy rows i >= n have C[i][j] = min_{i' < n} t[i'][j]: a surplus atom of the segment is charged its nearest partner.
+ *     For m < n the dummy columns j >= m have C[i][j] = min_{j' < m} t[i][j'], likewise.
+ *  5. Optimum.  total = min over permutations pi of sum_i C[i][pi(i)], an int64 below 2^38: an integer minimum, so it has no summation
+ *     order and depends on no algorithm, launch geometry or thread count.  score = (float)(ldexp((double) total, -shift) / (double) Q),
+ *     the division in fp64 and rounded once.  It is symmetric in (A, B) bit for bit: D transposes exactly, Dmax and shift are the
+ *     same, C transposes.
+ *  6. The map is not unique under ties, so the procedure is part of the definition: the shortest-augmenting-path method with
+ *     potentials in exact int64 arithmetic.  State: u[Q] = v[Q] = 0, p[j] = -1.  For each row i = 0 .. Q-1 ascending: minv[j] = INF,
+ *     used[j] = false, way[j] = -1, j0 = -1 (the virtual column that holds row i).  Repeat until the break:
+ *       if j0 >= 0 mark j0 used;  i0 = j0 < 0 ? i : p[j0];  delta = INF;
+ *       over the unused j ascending: cur = C[i0][j] - u[i0] - v[j]; if cur < minv[j] then minv[j] = cur, way[j] = j0; if minv[j] < delta
+ *         then delta = minv[j], j1 = j (strict: the least column index wins a tie);
+ *       u[i] += delta;  for used j: u[p[j]] += delta, v[j] -= delta;  for the others: minv[j] -= delta;
+ *       j0 = j1;  break when p[j0] == -1.
+ *     Then walk way back from j0: p[j0] = (way[j0] == -1) ? i : p[way[j0]], j0 = way[j0], until j0 == -1.  pi(p[j]) = j.
+ *     Reduced costs never go negative and stay below 2^39, so a parallel argmin over (minv, j) reproduces the sequential scan.
+ *     Per query atom i: its partner is segment atom pi(i) if pi(i) < m, with partner_dist2 = D[i][pi(i)]; otherwise the atom is
+ *     surplus: partner -1 and partner_dist2 = f_i = min_j D[i][j], what it was charged.
+ *
+ * scann_index_pairing pairs explicit (query set, segment number) pairs -- any order, repeats allowed, n_pairs = 0 is fine -- of host
+ * query rows q [q_first[n_sets] * dim] with segments of the index, one workgroup per pair.  Outputs: score, total, shift [n_pairs];
+ * partner_pos (the partner's POSITION in the index, -1 for a surplus atom) and partner_dist2 in pair order, pair e owning
+ * n(pair_set[e]) places; all but score may be NULL.  scann_index_pairing_batch runs one inference forward of the resident batch with
+ * after_Lc added for that forward only (y, ga, the handle's selection, training state, generic widths and SCANN_EXACT exactly as for
+ * scann_index_match_batch), takes each structure's shortlist -- the answer of scann_index_match with k = shortlist under `measure`, query
+ * ids applied there, k <= shortlist <= SCANN_KNN_MAX_K -- pairs the structure with every shortlisted segment and answers the first k of
+ * them under the TOTAL order (pairing score ascending, then segment number ascending); pairs that are not comparable rank last, by
+ * segment number.  Outputs: score, segment, ids, sizes, total, shift, short_score (the segment's score under `measure`), short_place
+ * (its place in the shortlist) [n_struct * k]; partner_pos, partner_dist2 [n_atom * k] at [(atom) * k + place]; all but score may be
+ * NULL.  Places without a segment hold score +inf, segment -1, id -1, size 0, total -1, shift 0, short_score +inf, short_place -1,
+ * partner -1, partner_dist2 +inf.  The result is a function of the query, the index and (k, shortlist, measure) only.
+ * SCANN_ERR_INVALID before anything is launched, the message naming the argument: a null argument, k or shortlist out of range or
+ * shortlist < k, a bad measure, an index of another handle or width, a pair index out of range, an empty query.  A query structure of
+ * more than SCANN_PAIRING_MAX_ATOMS atoms is SCANN_ERR_UNSUPPORTED; a SEGMENT above it is no error: that pair is not comparable.
+ * Synchronous.
+ * The twins do no GPU work.  scann_pairing_host is the definition for one pair, a [n * dim] against b [m * dim]: score, total, shift,
+ * partner [n] (the index within b, -1: surplus), partner_dist2 [n], any NULL; n above the limit is SCANN_ERR_UNSUPPORTED.
+ * scann_pairing_solve_host is step 6 alone on any cost matrix [Q * Q] (row-major, rows first) with entries <= 2^31, 1 <= Q <=
+ * SCANN_PAIRING_SOLVE_MAX: col_of_row [Q] = pi, total. */
+#define SCANN_PAIRING_MAX_ATOMS 128 /* a side: lane l of the solving wave owns columns l and l + 64 of the cost matrix, 66 KiB of LDS */
+#define SCANN_PAIRING_SOLVE_MAX 4096
+int scann_index_pairing(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets,
+                        const int32_t* pair_set, const int32_t* pair_segment, int64_t n_pairs, float* score, int64_t* total, int32_t* shift,
+                        int32_t* partner_pos, float* partner_dist2);
+int scann_index_pairing_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure,
+                              int32_t shortlist, int32_t k, float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes,
+                              int64_t* total, int32_t* shift, float* short_score, int32_t* short_place, int32_t* partner_pos,
+                              float* partner_dist2);
+int scann_pairing_host(const float* a, int64_t n, const float* b, int64_t m, int64_t dim, float* score, int64_t* total, int32_t* shift,
+                       int32_t* partner, float* partner_dist2);
+int scann_pairing_solve_host(const uint32_t* cost, int32_t Q, int32_t* col_of_row, int64_t* total);
+
 /* ---- greedy k-center selection: the most diverse rows of an index, picked on the device ----
  * Which m candidates should be labelled next, given what is labelled already?  Farthest-point selection in latent space (the core-set
  * rule of Sener & Savarese, ICLR 2018): repeatedly take the candidate whose distance to everything labelled or already taken is

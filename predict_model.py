@@ -14,6 +14,9 @@ out; ``distance``; ``latent_distance``: their mean, an uncertainty measure), or 
 as well).  With ``--nearest-index FILE`` a saved ``LatentIndex``, for example of the training set, is searched and nothing is left out.
 ``--match K [--match-measure chamfer|hausdorff|cover] [--match-index FILE]`` pickles ``match_<target>.pickle``: per structure the K
 structures of the dataset (or of a saved atom-level index) made of the most similar local structures, and which atom matches which.
+``--pair K [--pair-shortlist S] [--pair-measure chamfer|hausdorff|cover] [--pair-index FILE]`` pickles ``pair_<target>.pickle``: the same
+question answered one to one -- the S candidates of ``--match`` reranked by the exact pairing of their atoms with the structure's, and
+per neighbour a true atom map.
 ``--select M [--select-level atom] [--select-reference FILE]`` also pickles ``selected_<target>.pickle``: one dict with the M most
 diverse structures of the dataset (or atoms, at ``--select-level atom``) by greedy k-center selection in the model's latent space, in
 pick order (``neighbor_id``: dataset indices; ``atom``; ``radius``: the covering radius at each pick; ``position``; ``count``).  With
@@ -139,6 +142,10 @@ def main(args):
         raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
     if args.match and not 1 <= args.match <= 32:
         raise SystemExit("--match: K must lie in 1 .. 32, got %d" % args.match)
+    if args.pair and not 1 <= args.pair <= 32:
+        raise SystemExit("--pair: K must lie in 1 .. 32, got %d" % args.pair)
+    if args.pair and not args.pair <= args.pair_shortlist <= 32:
+        raise SystemExit("--pair-shortlist: S must lie in K = %d .. 32, got %d" % (args.pair, args.pair_shortlist))
     if args.select < 0:
         raise SystemExit("--select: M must be >= 1, got %d" % args.select)
     if args.cluster and not 1 <= args.cluster <= 1024:
@@ -272,6 +279,26 @@ def main(args):
             raise SystemExit("--match: %s" % e) from None
         index.free()
         pickle.dump(per, open(os.path.join(args.trained_model, "match_{}.pickle".format(target)), "wb"))
+    if args.pair:
+        from scann.models import LatentIndex
+
+        if args.pair_index:
+            index = LatentIndex.load(scann.model, args.pair_index)
+            if index.level != "atom":
+                raise SystemExit("--pair-index: %s is a %s-level index, pairing needs an atom-level one" % (args.pair_index, index.level))
+            print("Pair: %d of the %d nearest structures of %s (%d atom rows), %s" % (args.pair, args.pair_shortlist, args.pair_index, len(index),
+                                                                                      args.pair_measure))
+        else:  # the dataset itself, every structure queried with its own dataset index left out
+            index = scann.build_index(data, level="atom", ids=data.indexes)
+            print("Pair: %d of the %d nearest of the dataset's own structures (%d atom rows), %s, leave-one-out" % (
+                args.pair, args.pair_shortlist, len(index), args.pair_measure))
+        try:
+            per = pair_records(scann, data, index, args.pair, args.pair_shortlist, args.pair_measure, exclude=not args.pair_index)
+        except ValueError as e:  # (a structure above the atom limit)
+            index.free()
+            raise SystemExit("--pair: %s" % e) from None
+        index.free()
+        pickle.dump(per, open(os.path.join(args.trained_model, "pair_{}.pickle".format(target)), "wb"))
     if args.select:
         from scann.models import LatentIndex
 
@@ -763,6 +790,22 @@ def match_records(scann, data, index, k, measure, exclude):
     return per
 
 
+def pair_records(scann, data, index, k, shortlist, measure, exclude):
+    """--pair: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        sel = data.indexes[b * data.batch_size:(b + 1) * data.batch_size]
+        r = scann.pair_structures(inputs, index, k=k, shortlist=shortlist, measure=measure, exclude_ids=sel if exclude else None)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):  # paired_*: the structure's own atoms
+            d = {n: r[n][i] for n in ("distance", "neighbor_id", "neighbor_size", "shortlist_distance", "shortlist_place", "surplus")}
+            d.update(predict_property=float(r["predict_property"][i, 0]), paired_atom=r["paired_atom"][i][amask[i]],
+                     paired_distance=r["paired_distance"][i][amask[i]])
+            per.append(d)
+    return per
+
+
 def parser():
     p = argparse.ArgumentParser()
     p.add_argument("trained_model", type=str, help="Target trained model path for loading")
@@ -798,6 +841,16 @@ def parser():
                    help="chamfer: mean nearest-atom distance both ways; hausdorff: the worst one; cover: the query's atoms only")
     p.add_argument("--match-index", type=str, default="",
                    help="a saved atom-level LatentIndex (.npz) to match against instead of the dataset itself; nothing is left out")
+    p.add_argument("--pair", type=int, default=0,
+                   help="also pickle the K (1 .. 32) structures of the dataset nearest under the one-to-one pairing of their atoms with the "
+                        "structure's (the exact assignment over the after_Lc rows, solved on the GPU), leave-one-out, with the atom map, as "
+                        "pair_<target>.pickle: one dict per structure, unpadded, ids = dataset indices")
+    p.add_argument("--pair-shortlist", type=int, default=32,
+                   help="the candidates that are paired: the S (K .. 32) nearest structures under --pair-measure")
+    p.add_argument("--pair-measure", type=str, default="chamfer", choices=["chamfer", "hausdorff", "cover"],
+                   help="the measure that shortlists the candidates, as --match-measure")
+    p.add_argument("--pair-index", type=str, default="",
+                   help="a saved atom-level LatentIndex (.npz) to pair against instead of the dataset itself; nothing is left out")
     p.add_argument("--select", type=int, default=0,
                    help="also pickle the M most diverse structures of the dataset (greedy k-center selection in latent space) as "
                         "selected_<target>.pickle: one dict with ids (dataset indices), atoms and radii in pick order")

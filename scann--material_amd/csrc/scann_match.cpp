@@ -192,8 +192,10 @@ int match_search(scann_handle* h, scann_index* ix, const float* dq, const int32_
   return SCANN_OK;
 }
 
-// as search_staged: host or device query rows of the index's width staged at the padded width, then matched
-int match_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int32_t* q_first, int64_t n_sets, const int64_t* qid,
+}  // namespace
+
+// as search_staged: host or device query rows of the index's width staged at the padded width, then matched (scann_match.h)
+int scann::match_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int32_t* q_first, int64_t n_sets, const int64_t* qid,
                  int measure, int k, hipStream_t s, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos,
                  float* match_d) {
   const int64_t nq = q_first[n_sets];
@@ -211,8 +213,6 @@ int match_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind
   HIPCHK(h, e);
   return r;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -56,4 +56,10 @@ struct MatchPairArgs {
 };
 hipError_t launch_match_pair(const MatchPairArgs& a, hipStream_t s);
 
+// scann_match.cpp, for scann_pairing.cpp's shortlist: scann_index_match on checked arguments -- host or device query rows q of the index's
+// width (kind), staged at the padded width and matched on stream s; synchronous.  Outputs as scann_index_match's, all but score may be null
+int match_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int32_t* q_first, int64_t n_sets, const int64_t* qid,
+                 int measure, int k, hipStream_t s, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos,
+                 float* match_d);
+
 }  // namespace scann

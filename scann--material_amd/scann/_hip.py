@@ -137,6 +137,10 @@ SYMBOLS = [
     ("scann_index_match", C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("scann_index_match_batch", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("scann_match_parts_host", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P]),
+    ("scann_index_pairing", C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_index_pairing_batch", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32] + [_P] * 12),
+    ("scann_pairing_host", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    ("scann_pairing_solve_host", C.c_int, [_P, C.c_int32, _P, _P]),
     ("scann_index_select", C.c_int64, [_P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
     ("scann_kcenter_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P]),
     ("scann_index_kmeans", C.c_int64, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
@@ -199,6 +203,9 @@ KMEANS_MAX_K = 1024
 # scann_index_match: the measures by name (SCANN_MATCH_*) and the most atoms of one query structure (SCANN_MATCH_MAX_ATOMS)
 MATCH_MEASURES = {"chamfer": 0, "hausdorff": 1, "cover": 2}
 MATCH_MAX_ATOMS = 128
+# scann_index_pairing: the most atoms on either side of a pair (SCANN_PAIRING_MAX_ATOMS) and the solver twin's largest matrix
+PAIRING_MAX_ATOMS = 128
+PAIRING_SOLVE_MAX = 4096
 # the readout head on an index: the most targets and ridge strengths of one call (SCANN_HEAD_MAX_TARGETS, SCANN_HEAD_MAX_LAMBDA)
 HEAD_MAX_TARGETS = 16
 HEAD_MAX_LAMBDA = 32
@@ -274,6 +281,49 @@ def match_parts_host(q, q_first, rows, seg_first):
     if r != 0:
         raise ValueError("match_parts_host: bad arguments")
     return out
+
+
+def check_pairing_shortlist(shortlist, k):
+    """shortlist of a pairing rerank as the C calls take it: an integer in k .. KNN_MAX_K; ValueError otherwise."""
+    if isinstance(shortlist, bool) or not isinstance(shortlist, (int, np.integer)) or not k <= int(shortlist) <= KNN_MAX_K:
+        raise ValueError("shortlist must be an integer in k = %d .. %d, got %r" % (k, KNN_MAX_K, shortlist))
+    return int(shortlist)
+
+
+def pairing_host(a, b):
+    """The one-to-one pairing of the rows ``a`` [n, dim] with the rows ``b`` [m, dim] on the host with the kernel's bits
+    (scann_pairing_host, the definition in include/scann_hip.h): {"score" fp32, "total" int, "shift" int, "partner" [n] int32 -- the
+    index within ``b``, -1 for a surplus row --, "partner_dist2" [n] fp32}.  A pair that is not comparable (a NaN or infinite distance,
+    more than PAIRING_MAX_ATOMS rows in ``b``) answers score inf, total -1, partners -1."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or a.shape[1] < 1 or a.shape[0] < 1 or b.shape[0] < 1:
+        raise ValueError("pairing_host: shapes %s and %s" % (a.shape, b.shape))
+    if a.shape[0] > PAIRING_MAX_ATOMS:
+        raise ValueError("pairing_host: %d query rows, more than %d" % (a.shape[0], PAIRING_MAX_ATOMS))
+    score, total, shift = np.zeros(1, np.float32), np.zeros(1, np.int64), np.zeros(1, np.int32)
+    partner, pd = np.zeros(a.shape[0], np.int32), np.zeros(a.shape[0], np.float32)
+    r = load_library().scann_pairing_host(_ptr(a), a.shape[0], _ptr(b), b.shape[0], a.shape[1], _ptr(score), _ptr(total), _ptr(shift),
+                                          _ptr(partner), _ptr(pd))
+    if r != 0:
+        raise ValueError("pairing_host: bad arguments")
+    return {"score": score[0], "total": int(total[0]), "shift": int(shift[0]), "partner": partner, "partner_dist2": pd}
+
+
+def pairing_solve_host(cost):
+    """The assignment procedure of the definition alone (scann_pairing_solve_host) on a square matrix of integers 0 .. 2^31:
+    (col_of_row [Q] int32, total int)."""
+    c = np.asarray(cost)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or not 1 <= c.shape[0] <= PAIRING_SOLVE_MAX or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("pairing_solve_host: a square integer matrix of 1 .. %d rows, got %s %s" % (PAIRING_SOLVE_MAX, c.dtype, c.shape))
+    if c.min() < 0 or c.max() > 2 ** 31:
+        raise ValueError("pairing_solve_host: entries must lie in 0 .. 2^31")
+    c = np.ascontiguousarray(c, dtype=np.uint32)
+    col, total = np.zeros(c.shape[0], np.int32), np.zeros(1, np.int64)
+    r = load_library().scann_pairing_solve_host(_ptr(c), c.shape[0], _ptr(col), _ptr(total))
+    if r != 0:
+        raise ValueError("pairing_solve_host: bad arguments")
+    return col, int(total[0])
 
 
 def check_select_args(m, stop_dist2):
@@ -1942,6 +1992,62 @@ class Engine:
         self._check(self.lib.scann_index_match_batch(self._h, ix._h, rb._h, _ptr(qid), measure, k, _ptr(out["y"]), _ptr(out["ga"]),
                                                      _ptr(out["score"]), _ptr(out["segment"]), _ptr(out["id"]), _ptr(out["size"]),
                                                      _ptr(out["parts"]), _ptr(out["match_position"]), _ptr(out["match_dist2"])))
+        return out
+
+    def index_pairing(self, ix, q, q_first, pair_set, pair_segment):
+        """The one-to-one pairing of explicit (query set, segment) pairs (scann_index_pairing): ``q`` [nq, dim] cut by ``q_first``
+        [n_sets + 1]; ``pair_set``, ``pair_segment`` [n_pairs] in any order, repeats allowed.  {"score" fp32, "total" int64, "shift" int32
+        [n_pairs], "partner_position" int32 -- the partner's position in the index, -1 for a surplus atom --, "partner_dist2" fp32
+        [sum of n over the pairs] in pair order, "offset" [n_pairs + 1]: pair e owns offset[e] .. offset[e + 1] - 1}."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise ValueError("index_pairing: queries of shape %s for an index of %d columns" % (q.shape, ix.dim))
+        if q.shape[0] < 1:
+            raise ValueError("index_pairing: an empty query")
+        q_first = check_match_sets(q_first, q.shape[0])
+        n_sets, n_at = q_first.shape[0] - 1, np.diff(q_first)
+        big = np.nonzero(n_at > PAIRING_MAX_ATOMS)[0]
+        if big.size:
+            raise ValueError("index_pairing: query structure %d has %d atoms, more than %d" % (big[0], int(n_at[big[0]]), PAIRING_MAX_ATOMS))
+        ps = np.ascontiguousarray(pair_set, dtype=np.int64).reshape(-1)
+        pg = np.ascontiguousarray(pair_segment, dtype=np.int64).reshape(-1)
+        if ps.shape != pg.shape:
+            raise ValueError("index_pairing: %d pair sets and %d pair segments" % (ps.shape[0], pg.shape[0]))
+        n_seg = int(self.lib.scann_index_segments(ix._h, None, None, None))
+        if ps.size and (ps.min() < 0 or ps.max() >= n_sets):
+            raise ValueError("index_pairing: pair_set outside the %d query structures" % n_sets)
+        if pg.size and (pg.min() < 0 or pg.max() >= n_seg):
+            raise ValueError("index_pairing: pair_segment outside the %d segments of the index" % n_seg)
+        ps, pg = ps.astype(np.int32), pg.astype(np.int32)
+        offset = np.concatenate([[0], np.cumsum(n_at[ps], dtype=np.int64)]).astype(np.int64)
+        n_pairs, n_out = ps.shape[0], int(offset[-1])
+        out = {"score": np.empty(n_pairs, np.float32), "total": np.empty(n_pairs, np.int64), "shift": np.empty(n_pairs, np.int32),
+               "partner_position": np.empty(n_out, np.int32), "partner_dist2": np.empty(n_out, np.float32), "offset": offset}
+        self._check(self.lib.scann_index_pairing(self._h, ix._h, _ptr(q), _ptr(q_first), n_sets, _ptr(ps), _ptr(pg), n_pairs, _ptr(out["score"]),
+                                                 _ptr(out["total"]), _ptr(out["shift"]), _ptr(out["partner_position"]), _ptr(out["partner_dist2"])))
+        return out
+
+    def index_pairing_batch(self, ix, rb, k, shortlist, measure="chamfer", query_ids=None):
+        """One forward of a resident batch, each structure's ``shortlist`` nearest segments of ``ix`` under ``measure`` (index_match_batch),
+        the one-to-one pairing with each of them and the first ``k`` under (pairing score, segment) (scann_index_pairing_batch; raw y):
+        {"y" [n_struct], "ga" [n_atom], "score", "segment", "id", "size", "total", "shift", "short_score", "short_place" [n_struct, k],
+        "partner_position", "partner_dist2" [n_atom, k]}."""
+        k, measure = check_knn_k(k), check_match_measure(measure)
+        shortlist = check_pairing_shortlist(shortlist, k)
+        p = rb.packed
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != p.n_struct:
+            raise ValueError("index_pairing_batch: %d structures need %d query ids" % (p.n_struct, p.n_struct))
+        B, A = p.n_struct, p.n_atom
+        out = {"y": np.empty(B, np.float32), "ga": np.empty(A, np.float32), "score": np.empty((B, k), np.float32),
+               "segment": np.empty((B, k), np.int32), "id": np.empty((B, k), np.int64), "size": np.empty((B, k), np.int32),
+               "total": np.empty((B, k), np.int64), "shift": np.empty((B, k), np.int32), "short_score": np.empty((B, k), np.float32),
+               "short_place": np.empty((B, k), np.int32), "partner_position": np.empty((A, k), np.int32),
+               "partner_dist2": np.empty((A, k), np.float32)}
+        self._check(self.lib.scann_index_pairing_batch(
+            self._h, ix._h, rb._h, _ptr(qid), measure, shortlist, k, _ptr(out["y"]), _ptr(out["ga"]), _ptr(out["score"]), _ptr(out["segment"]),
+            _ptr(out["id"]), _ptr(out["size"]), _ptr(out["total"]), _ptr(out["shift"]), _ptr(out["short_score"]), _ptr(out["short_place"]),
+            _ptr(out["partner_position"]), _ptr(out["partner_dist2"])))
         return out
 
     def index_select(self, pool_ix, ref_ix, m, stop_dist2=0.0):

@@ -439,17 +439,7 @@ class HipModel:
         batch_size or exclude_ids length, or a structure of more than _hip.MATCH_MAX_ATOMS atoms raise ValueError before anything is
         uploaded."""
         k, ms = _hip.check_knn_k(k), _hip.check_match_measure(measure)
-        _expect(index, LatentIndex, "index")
-        index.check_model(self)
-        if index.level != "atom":
-            raise ValueError("match_structures compares structures atom by atom: it needs an atom-level index, got a %s-level one" % index.level)
-        self._batch_size(batch_size)
-        is_packed = isinstance(inputs, _hip.PackedBatch)
-        n_at = np.diff(inputs.mol_offset) if is_packed else (np.asarray(inputs["atom_mask"]).reshape(count_structures(inputs), -1) != 0).sum(1)
-        big = np.nonzero(n_at > _hip.MATCH_MAX_ATOMS)[0]
-        if big.size:
-            raise ValueError("structure %d has %d atoms, more than the %d a query structure may have" % (
-                big[0], int(n_at[big[0]]), _hip.MATCH_MAX_ATOMS))
+        self._atom_query(inputs, index, "match_structures", _hip.MATCH_MAX_ATOMS, batch_size)
         qid = _exclude_ids_arg(inputs, exclude_ids)
         eng = self.engine
         cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_match_batch(
@@ -464,6 +454,94 @@ class HipModel:
                "neighbor_id": cat["id"], "neighbor_size": cat["size"], "parts": cat["parts"], "matched_atom": matched,
                "matched_distance": np.sqrt(cat["match_dist2"])}
         return _repad(out, inputs, "atom", {"matched_atom": -1, "matched_distance": 0})
+
+    def _atom_query(self, inputs, index, who, most_atoms, batch_size):
+        """What the atom-by-atom comparisons refuse before anything is uploaded: an ``index`` that is no atom-level ``LatentIndex`` of
+        this model, a bad batch_size, a structure of more than ``most_atoms`` atoms.  Returns the atoms per structure."""
+        _expect(index, LatentIndex, "index")
+        index.check_model(self)
+        if index.level != "atom":
+            raise ValueError("%s compares structures atom by atom: it needs an atom-level index, got a %s-level one" % (who, index.level))
+        self._batch_size(batch_size)
+        return self._atoms_per_structure(inputs, most_atoms)
+
+    @staticmethod
+    def _atoms_per_structure(inputs, most_atoms):
+        """Atoms of every structure of ``inputs``; ValueError naming the first with more than ``most_atoms``"""
+        is_packed = isinstance(inputs, _hip.PackedBatch)
+        n_at = np.diff(inputs.mol_offset) if is_packed else (np.asarray(inputs["atom_mask"]).reshape(count_structures(inputs), -1) != 0).sum(1)
+        big = np.nonzero(n_at > most_atoms)[0]
+        if big.size:
+            raise ValueError("structure %d has %d atoms, more than the %d a query structure may have" % (big[0], int(n_at[big[0]]), most_atoms))
+        return n_at
+
+    def pair_structures(self, inputs, index, k=5, shortlist=32, measure="chamfer", exclude_ids=None, batch_size=None):
+        """``match_structures`` with a true atom map: the ``k`` structures of an atom-level ``LatentIndex`` nearest to each structure of
+        ``inputs`` under the one-to-one pairing of their atoms -- the linear assignment problem over the squared distances of the
+        ``after_Lc`` rows, solved exactly on the GPU right behind the forward (scann_index_pairing_batch; the definition is in
+        include/scann_hip.h).  Every query atom gets its own atom of the neighbour, so the map lines two structures up atom by atom and
+        the score counts: structures made of the same local structures in different numbers are not at distance 0.  The candidates are
+        the ``shortlist`` nearest structures under ``measure`` (``match_structures``' measures; ``exclude_ids`` applies there), reranked
+        by (pairing score, position in the index); the result depends on the query, the index and (k, shortlist, measure) only.
+        Returns {"predict_property": [B, 1], "distance": [B, k] fp32 -- the square root of the pairing score, the mean squared distance
+        over max(n, m) pairs with a surplus atom charged its nearest partner --, "neighbor_id": [B, k] int64, "neighbor_size": [B, k],
+        "shortlist_distance": [B, k] (the neighbour's distance under ``measure``), "shortlist_place": [B, k] (its place in the
+        shortlist), "paired_atom": [B, M, k] int32 -- the atom's partner, its index within the neighbour, -1 where the atom is surplus
+        or at padding --, "paired_distance": [B, M, k] fp32 (for a surplus atom: to its nearest atom), "surplus": [B, k] = n - m (0
+        without a neighbour)}; a ``PackedBatch`` gives packed [n_atom, k] arrays.  A neighbour of more than _hip.PAIRING_MAX_ATOMS
+        atoms is not comparable: distance inf, ranked last.  Places without a neighbour hold distance inf, id -1, size 0, place -1,
+        paired_atom -1.  Raw y.  It refuses what ``match_structures`` refuses, and a shortlist outside k .. 32."""
+        k, ms = _hip.check_knn_k(k), _hip.check_match_measure(measure)
+        sl = _hip.check_pairing_shortlist(shortlist, k)
+        n_at = self._atom_query(inputs, index, "pair_structures", _hip.PAIRING_MAX_ATOMS, batch_size)
+        qid = _exclude_ids_arg(inputs, exclude_ids)
+        eng = self.engine
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_pairing_batch(
+            index._ix, rb, k, sl, ms, None if qid is None else qid[s0:s1]),
+            {"y": np.zeros(0, np.float32), "score": np.zeros((0, k), np.float32), "id": np.zeros((0, k), np.int64),
+             "size": np.zeros((0, k), np.int32), "short_score": np.zeros((0, k), np.float32), "short_place": np.zeros((0, k), np.int32),
+             "partner_position": np.zeros((0, k), np.int32), "partner_dist2": np.zeros((0, k), np.float32)})
+        _, atoms = eng.index_names(index._ix)  # (host copies: the rows stay on the device)
+        pos = cat["partner_position"]
+        paired = np.where(pos >= 0, atoms[np.maximum(pos, 0)] if len(atoms) else -1, -1).astype(np.int32)
+        surplus = np.where(cat["size"] > 0, np.asarray(n_at, np.int32).reshape(-1, 1) - cat["size"], 0).astype(np.int32)
+        out = {"predict_property": cat["y"].reshape(-1, 1), "distance": np.sqrt(cat["score"]),  # (correctly rounded on the host, as nearest)
+               "neighbor_id": cat["id"], "neighbor_size": cat["size"], "shortlist_distance": np.sqrt(cat["short_score"]),
+               "shortlist_place": cat["short_place"], "paired_atom": paired, "paired_distance": np.sqrt(cat["partner_dist2"]), "surplus": surplus}
+        return _repad(out, inputs, "atom", {"paired_atom": -1, "paired_distance": 0})
+
+    def align_structures(self, inputs_a, inputs_b, batch_size=None):
+        """The e-th structure of ``inputs_a`` mapped onto the e-th of ``inputs_b`` atom by atom, with no index in sight: two polymorphs,
+        a structure before and after relaxation, a substitution series.  ``inputs_b`` is indexed at atom level for the call; the pairs
+        (e, e) go through the one-to-one pairing of ``pair_structures`` (scann_index_pairing) on the ``after_Lc`` rows.  Returns
+        {"distance": [B] fp32, "atom_map": [B, M_a] int32 -- the atom of b that atom i of a is paired with, -1 where it is surplus or at
+        padding --, "atom_distance": [B, M_a] fp32, "surplus": [B] = n_a - n_b, "predict_property": [B, 1] of a and
+        "predict_property_b": [B, 1] of b}; ``PackedBatch`` inputs give packed [n_atom] arrays.  A structure of b above
+        _hip.PAIRING_MAX_ATOMS atoms is not comparable (distance inf, map -1); one of a, another number of structures or a bad batch_size
+        raise ValueError before anything is uploaded.  Raw y."""
+        B = count_structures(inputs_a)
+        if count_structures(inputs_b) != B:
+            raise ValueError("align_structures: %d structures against %d" % (B, count_structures(inputs_b)))
+        self._batch_size(batch_size)
+        n_a = self._atoms_per_structure(inputs_a, _hip.PAIRING_MAX_ATOMS)
+        n_b = self._atoms_per_structure(inputs_b, np.iinfo(np.int32).max)
+        if B == 0:
+            raise ValueError("align_structures: no structure")
+        eng = self.engine
+        packed_a = isinstance(inputs_a, _hip.PackedBatch)
+        ya, rows = self.predict(inputs_a, outputs=["predict_property", "after_Lc"])
+        if not packed_a:
+            rows = rows[np.asarray(inputs_a["atom_mask"]).reshape(B, -1) != 0]
+        yb = self.predict(inputs_b, outputs=["predict_property"])[0]
+        with self._indexed(inputs_b, "atom", batch_size=batch_size) as ix:
+            pairs = np.arange(B)
+            r = eng.index_pairing(ix._ix, rows, np.concatenate([[0], np.cumsum(n_a)]), pairs, pairs)
+            _, atoms = eng.index_names(ix._ix)
+        pos = r["partner_position"]
+        out = {"distance": np.sqrt(r["score"]), "atom_map": np.where(pos >= 0, atoms[np.maximum(pos, 0)], -1).astype(np.int32),
+               "atom_distance": np.sqrt(r["partner_dist2"]), "surplus": (np.asarray(n_a) - np.asarray(n_b)).astype(np.int32),
+               "predict_property": ya.reshape(-1, 1), "predict_property_b": yb.reshape(-1, 1)}
+        return _repad(out, inputs_a, "atom", {"atom_map": -1, "atom_distance": 0})
 
     def select_diverse(self, pool, m, reference=None, level="structure", stop_distance=None, batch_size=None):
         """Which ``m`` structures (or atoms, ``level`` "atom") of ``pool`` to label next: greedy k-center selection in the model's latent
@@ -1374,6 +1452,20 @@ class SCANN:
         res = {k: v * self.std for k, v in out.items()}
         res["predict_property"] = y * self.std + self.mean
         return res
+
+    def pair_structures(self, ip, index, k=5, shortlist=32, measure="chamfer", exclude_ids=None, batch_size=None):
+        """HipModel.pair_structures with ``predict_property`` in the units of the target (times std plus mean, as predict_data); the
+        distances, the atom maps and the counts live in latent space and pass through as they are."""
+        out = self.model.pair_structures(ip, index, k=k, shortlist=shortlist, measure=measure, exclude_ids=exclude_ids, batch_size=batch_size)
+        out["predict_property"] = out["predict_property"] * self.std + self.mean
+        return out
+
+    def align_structures(self, ip_a, ip_b, batch_size=None):
+        """HipModel.align_structures with both predictions, ``predict_property`` and ``predict_property_b``, in the units of the target."""
+        out = self.model.align_structures(ip_a, ip_b, batch_size=batch_size)
+        for k in ("predict_property", "predict_property_b"):
+            out[k] = out[k] * self.std + self.mean
+        return out
 
     def atom_contributions(self, ip, mode="leave_one_out", batch_size=None):
         """HipModel.atom_contributions in the units of the target: ``y`` and ``ablated`` de-normalised as predict_data does (times std
