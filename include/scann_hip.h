@@ -1021,6 +1021,80 @@ int scann_index_ranks(scann_handle_t* h, scann_index_t* pool,
 int scann_ranks_host(const float* rows, int64_t n, int64_t dim, const int32_t* qpos, int64_t nq, const int32_t* probe, int32_t m,
                      int32_t threads, int32_t* rank, float* dist2);
 
+/* ---- A partition of an index into cells: the exact nearest-row search that skips cells out of reach ----
+ * scann_index_query and everything built on the same search (scann_index_query_batch, the reference pass of scann_index_select, the
+ * neighbour graph) compare each query with every row.  Latent rows fall into kinds; a search that knows the kinds can leave most rows
+ * unread and still give the brute-force answer IN EVERY BYTE.  A partition is a cell-ordered COPY of the rows attached to the index:
+ * it doubles the index's device memory.  The original rows never move and positions keep their meaning.
+ * Definition of scann_index_partition(h, idx, cells, max_iter, info), 1 <= cells <= SCANN_KMEANS_MAX_K (cells = 0 drops the partition):
+ *   Centres.  The first C = min(cells, eligible rows) picks of scann_index_select(idx, no reference, no threshold), refined by
+ *     scann_index_kmeans(init_pos = picks, max_iter, stop_changed = 0); its labels, its dist2 (row to its final centre) and its centres
+ *     are used as they come.
+ *   Order.  The rows sorted by (label, dist2 to the centre ascending, position ascending); rows with label -1 (a non-finite component)
+ *     form a final LOOSE segment in position order.  Every cell, and the loose segment, is padded to whole tiles of 64 entries with pad
+ *     entries of position -1; an empty cell has no tile.  A tile therefore belongs to one cell and one shell of distances round its centre.
+ *   Per tile.  lo_t / hi_t = the least / greatest dist2 to the centre among the tile's real rows, in the bits scann_index_kmeans returned;
+ *     a loose tile has lo = 0, hi = +inf.
+ *   Storage.  The copy holds rows, ids and original positions in blocks of the handle's cache, chunked like the index.
+ *   Lifetime.  scann_index_add / scann_index_add_batch of one row or more drop the partition (the index then behaves as without one);
+ *     scann_index_free frees it.
+ *   info [4] (may be NULL): cells in use C, tiles, pad entries, rows of the largest cell.
+ * scann_index_cells_read returns info, centres [C * dim], perm [64 * tiles] (original position per entry of the cell order, read back
+ * from the device copy; -1: a pad entry), first_tile [C + 2] (first tile of cell c; [C]: first loose tile; [C + 1]: tiles), lo and hi
+ * [tiles]; every output may be NULL, so a first call with only info sizes the second; without a partition info is all zero.
+ * scann_cells_host(rows [n * dim], ...) is the twin composed of scann_kcenter_host and scann_kmeans_host, the same bytes, no GPU work;
+ * its arrays are sized by scann_cells_capacity(n, cells) tiles (perm: 64 times as many entries; centres cells * dim; first_tile cells + 2).
+ *
+ * The bound.  scann_cell_bound(D, lo, hi), with D = dist2(q, z_c) the chain of scann_knn_distsq with the query first, a = sqrt(D),
+ * r_lo = sqrt(lo), r_hi = sqrt(hi), eps = 2^-12, everything in fp64:
+ *     g  = max((1 - eps) a - (1 + eps) r_hi,  (1 - eps) r_lo - (1 + eps) a) - 2^-64
+ *     lb = g > 0 ? (1 - eps) g^2 : 0,      and lb = 0 whenever D or hi is not finite.
+ *   Claim: for every real row x of tile t, the chain value dist2(q, x) >= lb (a NaN chain value never qualifies and is not claimed).
+ *   Proof.  Write d(.,.) for the exact Euclidean distance of two fp32 vectors and c(.,.) for the chain.  A finite chain value obeys
+ *     c = d^2 (1 + th) + et,  |th| <= gam = (dim + 3) 2^-24 <= 1027 * 2^-24 < 2^-13 = eps / 2  (one rounding of the difference squared,
+ *     one per fused step),  |et| <= u = 1024 * 2^-149 = 2^-139  (products that underflow; w = sqrt(u) < 2^-69).
+ *     Hence for any pair  (1 - eps/2)(sqrt(c) - w) <= d <= (1 + eps/2)(sqrt(c) + w).  The fp64 square roots and the few fp64 operations
+ *     of g are off by relative 2^-52 each, of the larger operand at worst: against the margin between eps and eps/2, i.e. 2^-13 of that
+ *     operand, this is nothing, so  d(q, z) >= (1 - eps) a - w,  d(q, z) <= (1 + eps) a + w,  and for a real row x of the tile, whose
+ *     c(x, z) lies in [lo, hi]:  d(x, z) <= (1 + eps) r_hi + w,  d(x, z) >= (1 - eps) r_lo - w.  By the triangle inequality on the exact
+ *     distances  d(q, x) >= max(d(q, z) - d(x, z), d(x, z) - d(q, z)) >= g + (2^-64 - 2 w) > g + 2^-65.  For g > 0 therefore
+ *     d(q, x)^2 > g^2 + 2^-130, and  c(q, x) >= (1 - gam) d(q, x)^2 - u > (1 - gam) g^2 + (1 - gam) 2^-130 - 2^-139 > (1 - eps) g^2 = lb;
+ *     a c(q, x) that overflowed is +inf >= lb.  eps carries a four-fold margin over gam at dim 1024 and 2^-64 covers more than three w.
+ *     (Checked on the CPU as well: tests/test_cells_host.py walks dim 1 .. 1024 and magnitudes 1e-22 .. 3e18 and finds no violation.)
+ *
+ * The search.  With a partition, scann_index_query, scann_index_query_batch, scann_index_query_rows and the reference pass of
+ * scann_index_select take the pruned route.  Per group of 128 queries (the queries of a pass of up to 1,024 are ordered by their
+ * nearest centres, so that a group looks at few cells) a tile may be skipped only if, for EVERY query q of the group, q already holds k qualifying rows with exact chain distances, tau_q
+ * being the k-th of them, and scann_cell_bound(D(q, c(t)), lo_t, hi_t) > tau_q, strictly.  Loose tiles are always visited.  Qualifying
+ * rows are those of scann_index_query: a NaN distance never qualifies, rows whose id equals the query's id are skipped, +inf is an
+ * ordinary value; the order is (dist2, original position).  A skipped row has dist2 >= lb > tau_q, so it is behind k rows that were
+ * seen: the output -- dist2, position, id, atom and the +inf / -1 tail -- is scann_index_query's without a partition in every byte.
+ * The other analyses over an index (match, kmeans, density, mst, silhouette, ranks, ...) never read the copy.
+ * Fall-back.  A pass whose plan keeps more than 1/2 of its (group, tile) pairs -- seeds and survivors over groups x tiles of the copy --
+ * is answered by the full kernel if k <= 3, or k <= 7 where the copy has at least 16,384 tiles: there the pruned route measured slower
+ * (profiles/cells_rate.txt); at larger k it wins even where it visits every tile, because its second pass drops a distance above tau_q
+ * after one compare.  The answer is the same either way.
+ * The stats then count, for that pass, its seeds plus every pair of the full search as visited (visited = total + seeds).
+ * scann_index_search_stats(idx, out[4]): for the last search on idx the (128-query group, 64-row tile) pairs a full search visits,
+ * the pairs visited as seeds, the pairs visited in all, and the groups; without a partition visited == total and seeds == 0.
+ * scann_index_partition_args: the (cells, max_iter) the partition was asked for, (0, 0) without one.
+ * scann_index_query_rows(h, idx, first, n, k, ...): the queries are rows first .. first + n - 1 of the index itself, read where they
+ * lie on the device; the answer is that of scann_index_read followed by scann_index_query (no query ids) in every byte.
+ * SCANN_ERR_INVALID before anything is launched: a null argument, an index of another handle, cells outside 0 .. SCANN_KMEANS_MAX_K,
+ * max_iter < 0, rows outside the index, k outside 1 .. SCANN_KNN_MAX_K.  All calls are synchronous and change neither weights, training
+ * state nor selected outputs. */
+int scann_index_partition(scann_handle_t* h, scann_index_t* idx, int32_t cells, int32_t max_iter, int64_t* info /* [4] or NULL */);
+int scann_index_partition_args(const scann_index_t* idx, int32_t* cells, int32_t* max_iter);
+int scann_index_cells_read(scann_handle_t* h, scann_index_t* idx, int64_t* info /* [4] */, float* centres, int32_t* perm, int32_t* first_tile,
+                           float* lo, float* hi);
+int scann_index_search_stats(const scann_index_t* idx, int64_t* out /* [4] */);
+int scann_index_query_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t k, float* dist2, int64_t* ids,
+                           int32_t* atoms, int32_t* pos);
+int64_t scann_cells_capacity(int64_t n, int32_t cells);
+int scann_cells_host(const float* rows, int64_t n, int64_t dim, int32_t cells, int32_t max_iter, int64_t* info, float* centres, int32_t* perm,
+                     int32_t* first_tile, float* lo, float* hi);
+double scann_cell_bound(float D, float lo, float hi);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

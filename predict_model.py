@@ -140,6 +140,8 @@ def main(args):
         return main_with(args)
     if args.nearest and not 1 <= args.nearest <= 32:
         raise SystemExit("--nearest: K must lie in 1 .. 32, got %d" % args.nearest)
+    if not 0 <= args.nearest_cells <= 1024:
+        raise SystemExit("--nearest-cells: C must lie in 0 .. 1024 (0: no partition), got %d" % args.nearest_cells)
     if args.match and not 1 <= args.match <= 32:
         raise SystemExit("--match: K must lie in 1 .. 32, got %d" % args.match)
     if args.pair and not 1 <= args.pair <= 32:
@@ -254,11 +256,16 @@ def main(args):
 
         if args.nearest_index:
             index = LatentIndex.load(scann.model, args.nearest_index)
+            if args.nearest_cells and len(index):
+                index.partition(args.nearest_cells)
             print("Nearest %d rows of %s (%s level, %d rows)" % (args.nearest, args.nearest_index, index.level, len(index)))
         else:  # the dataset itself, every structure queried with its own dataset index left out
-            index = scann.build_index(data, level=args.nearest_level, ids=data.indexes)
+            index = scann.build_index(data, level=args.nearest_level, ids=data.indexes, cells=args.nearest_cells or None)
             print("Nearest %d of the dataset's own %d rows (%s level), leave-one-out" % (args.nearest, len(index), index.level))
         per = nearest_records(scann, data, index, args.nearest, exclude=not args.nearest_index)
+        if index.partition_args():  # (of the last batch's search)
+            print("Nearest: %d cells, %.1f %% of the (query group, row tile) pairs visited" % (
+                index.partition_args()[0], 100.0 * index.search_stats()["visited_share"]))
         index.free()
         pickle.dump(per, open(os.path.join(args.trained_model, "nearest_{}.pickle".format(target)), "wb"))
     if args.match:
@@ -833,6 +840,9 @@ def parser():
                    help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
     p.add_argument("--nearest-index", type=str, default="",
                    help="a saved LatentIndex (.npz) to search instead of the dataset itself; nothing is left out")
+    p.add_argument("--nearest-cells", type=int, default=0,
+                   help="partition the searched index into C (1 .. 1024) cells, so that --nearest skips the cells out of reach; the "
+                        "answers are the same in every byte (default 0: compare every row)")
     p.add_argument("--match", type=int, default=0,
                    help="also pickle the K (1 .. 32) structures of the dataset made of the most similar local structures (sets of after_Lc "
                         "rows compared on the GPU), leave-one-out, with the atom-to-atom correspondence, as match_<target>.pickle: one dict "

@@ -6,6 +6,7 @@
 // the level's output flag in that one forward's options: y, the scores, the range guard and the exact re-run behave as in
 // scann_batch_download, and the handle is not written.
 #include "scann_call.h"
+#include "scann_cells.h"
 #include "scann_knn.h"
 #include "scann_runtime.h"
 
@@ -68,6 +69,7 @@ int index_new_chunk(scann_handle* h, scann_index* ix, hipStream_t s) {
 }
 
 void index_note_rows(scann_index* ix, int64_t n, const int64_t* ids, const int32_t* atoms) {
+  if (n > 0) cells_drop(ix);  // a partition describes the rows it was built from (the appends are synchronous: nothing reads it now)
   for (int64_t i = 0; i < n; ++i)
     if ((i == 0 ? ix->ids.empty() || ix->ids.back() != ids[0] : ids[i] != ids[i - 1])) ix->seg_first.push_back((int32_t)(ix->n + i));
   ix->ids.insert(ix->ids.end(), ids, ids + n);
@@ -109,6 +111,13 @@ int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch,
 // reference, k = 1)
 int scann::search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
                   int32_t* atoms, int32_t* pos, float* dev_d) {
+  return ix->part ? cells_search(h, ix, dq, dqid, nq, k, s, dist2, ids, atoms, pos, dev_d)
+                  : search_full(h, ix, dq, dqid, nq, k, s, dist2, ids, atoms, pos, dev_d);
+}
+
+// the search that compares every query with every row (what search() is without a partition, and what cells_search falls back to)
+int scann::search_full(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2,
+                       int64_t* ids, int32_t* atoms, int32_t* pos, float* dev_d) {
   const int64_t N = ix->n;
   const int rpr = (int)std::max<int64_t>(TILE_TR, ((N + KNN_RANGES - 1) / KNN_RANGES + TILE_TR - 1) / TILE_TR * TILE_TR);
   // one launch over all chunks: every chunk is cut into the same number of ranges (those behind the last row stay empty)
@@ -145,6 +154,12 @@ int scann::search(scann_handle* h, scann_index* ix, const float* dq, const int64
   else if (e != hipSuccess) (void)hipStreamSynchronize(s);
   ws.release();
   HIPCHK(h, e);
+  {  // what scann_index_search_stats reports: every (128-query group, 64-row tile) pair was visited
+    int64_t groups = 0, tiles = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += g) groups += (std::min<int64_t>(g, nq - q0) + TILE_TQ - 1) / TILE_TQ;
+    for (int64_t r = 0; r < N; r += ix->chunk_rows) tiles += (std::min<int64_t>(ix->chunk_rows, N - r) + TILE_TR - 1) / TILE_TR;
+    ix->stats[0] = ix->stats[2] = groups * tiles; ix->stats[1] = 0; ix->stats[3] = groups;
+  }
   for (size_t i = 0; i < pos_h.size(); ++i) {
     const int32_t p = pos_h[i];
     if (pos) pos[i] = p;
@@ -237,6 +252,7 @@ void scann_index_free(scann_handle_t* h, scann_index_t* ix) {
   if (!ix) return;
   (void)h;  // (the chunks go back to the device's block cache, which outlives the handle)
   if (hipSetDevice(ix->device) == hipSuccess) (void)hipDeviceSynchronize();
+  cells_drop(ix);
   for (char* p : ix->chunks) cached_free(p);
   delete ix;
 }

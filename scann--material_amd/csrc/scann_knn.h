@@ -8,6 +8,9 @@
 #include "scann_tile.h"
 
 struct scann_handle;
+namespace scann {
+struct CellPart;  // scann_cells.h
+}
 
 // A latent-space index (scann_knn.cpp; scann_head.cpp reads it as well)
 struct scann_index {
@@ -20,6 +23,8 @@ struct scann_index {
   std::vector<int64_t> ids;     // host copies: what the calls report by position
   std::vector<int32_t> atoms;
   std::vector<int32_t> seg_first;  // first position of every segment: a maximal run of consecutive rows with one id (scann_index_match)
+  scann::CellPart* part = nullptr;  // the partition into cells (scann_index_partition), or none: only search() reads it
+  int64_t stats[4] = {0, 0, 0, 0};  // the last search (scann_index_search_stats)
   float* rows_of(size_t c) const { return reinterpret_cast<float*>(chunks[c]); }
   int64_t* ids_of(size_t c) const { return reinterpret_cast<int64_t*>(chunks[c] + (size_t)chunk_rows * stride * 4); }
   size_t chunk_bytes() const { return (size_t)chunk_rows * stride * 4 + (size_t)chunk_rows * 8; }
@@ -41,6 +46,8 @@ int check_index(scann_handle* h, const scann_index* ix, const char* who);
 int check_k(scann_handle* h, int32_t k, const char* who);
 int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
            int32_t* atoms, int32_t* pos, float* dev_d = nullptr);
+int search_full(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
+                int32_t* atoms, int32_t* pos, float* dev_d = nullptr);  // search() of an index without a partition, whether it has one or not
 void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out);
 
 // One launch of knn_tile_kernel: `nq` queries against all `n_total` rows of an index, stored in chunks of `chunk_rows` rows.  Workgroup

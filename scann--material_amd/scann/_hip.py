@@ -180,6 +180,14 @@ SYMBOLS = [
     ("scann_silhouette_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("scann_index_ranks", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
     ("scann_ranks_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("scann_index_partition", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    ("scann_index_partition_args", C.c_int, [_P, _P, _P]),
+    ("scann_index_cells_read", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_search_stats", C.c_int, [_P, _P]),
+    ("scann_index_query_rows", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    ("scann_cells_capacity", C.c_int64, [C.c_int64, C.c_int32]),
+    ("scann_cells_host", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("scann_cell_bound", C.c_double, [C.c_float, C.c_float, C.c_float]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -407,6 +415,50 @@ def kmeans_host(rows, init, max_iter, stop_changed=0):
         raise ValueError("kmeans_host: invalid arguments (%d)" % n_iter)
     out["n_iter"], out["converged"] = n_iter, bool(conv.value)
     return out
+
+
+CELLS_INFO = ("cells", "tiles", "pad", "largest")
+
+
+def _cells_out(info, centre, perm, first, lo, hi):
+    """What scann_cells_host / scann_index_cells_read filled, cut to the partition's size."""
+    c, t = int(info[0]), int(info[1])
+    out = dict(zip(CELLS_INFO, (int(v) for v in info)))
+    out.update({"centre": centre[:c].copy(), "perm": perm[: 64 * t].copy(), "first_tile": first[: c + 2].copy(), "lo": lo[:t].copy(), "hi": hi[:t].copy()})
+    return out
+
+
+def check_cells_args(cells, max_iter, lowest=1):
+    if isinstance(cells, bool) or not isinstance(cells, (int, np.integer)) or not lowest <= int(cells) <= KMEANS_MAX_K:
+        raise ValueError("cells must be an integer in %d .. %d, got %r" % (lowest, KMEANS_MAX_K, cells))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 0:
+        raise ValueError("max_iter must be an integer >= 0, got %r" % (max_iter,))
+    return int(cells), int(max_iter)
+
+
+def cells_host(rows, cells, max_iter=8):
+    """The partition of host rows [n, dim] into ``cells`` cells as scann_index_partition lays it out (scann_cells_host, the definition in
+    include/scann_hip.h), without a GPU: {"cells", "tiles", "pad", "largest", "centre" [C, dim], "perm" [64 tiles] (original position, -1:
+    a pad entry), "first_tile" [C + 2], "lo", "hi" [tiles]}."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("cells_host: rows of shape %s" % (rows.shape,))
+    cells, max_iter = check_cells_args(cells, max_iter)
+    lib = load_library()
+    cap = int(lib.scann_cells_capacity(rows.shape[0], cells))
+    info = np.zeros(4, np.int64)
+    centre, perm, first = np.zeros((cells, rows.shape[1]), np.float32), np.full(64 * cap, -1, np.int32), np.zeros(cells + 2, np.int32)
+    lo, hi = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    r = lib.scann_cells_host(_ptr(rows), rows.shape[0], rows.shape[1], cells, max_iter, _ptr(info), _ptr(centre), _ptr(perm), _ptr(first), _ptr(lo), _ptr(hi))
+    if r < 0:
+        raise ValueError("cells_host: invalid arguments (%d)" % r)
+    return _cells_out(info, centre, perm, first, lo, hi)
+
+
+def cell_bound(D, lo, hi):
+    """The least chain distance a query at dist2 ``D`` from a cell's centre can have to a row of a tile whose rows lie at dist2 ``lo`` ..
+    ``hi`` from that centre (scann_cell_bound): a float, 0 where nothing can be said."""
+    return float(load_library().scann_cell_bound(C.c_float(float(D)), C.c_float(float(lo)), C.c_float(float(hi))))
 
 
 def pca_bits(n):
@@ -1916,6 +1968,47 @@ class Engine:
         self._check(self.lib.scann_index_query(self._h, ix._h, _ptr(q), q.shape[0], _ptr(qid), k, _ptr(out["dist2"]), _ptr(out["id"]),
                                                _ptr(out["atom"]), _ptr(out["position"])))
         return out
+
+    def index_query_rows(self, ix, first, n, k):
+        """``index_query`` of rows first .. first + n - 1 of the index itself, staged device to device (scann_index_query_rows): the bits of
+        ``index_read`` followed by ``index_query``."""
+        k = check_knn_k(k)
+        out = self._knn_out(max(int(n), 0), k)
+        self._check(self.lib.scann_index_query_rows(self._h, ix._h, int(first), int(n), k, _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]),
+                                                    _ptr(out["position"])))
+        return out
+
+    def index_partition(self, ix, cells, max_iter=8):
+        """Partition the index into ``cells`` cells (scann_index_partition; 0 drops the partition): searches then skip cells out of reach and
+        answer the same bytes.  {"cells", "tiles", "pad", "largest"}."""
+        cells, max_iter = check_cells_args(cells, max_iter, lowest=0)
+        info = np.zeros(4, np.int64)
+        self._check(self.lib.scann_index_partition(self._h, ix._h, cells, max_iter, _ptr(info)))
+        return dict(zip(CELLS_INFO, (int(v) for v in info)))
+
+    def index_partition_args(self, ix):
+        """(cells, max_iter) the index's partition was asked for, (0, 0) without one."""
+        c, m = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.scann_index_partition_args(ix._h, C.byref(c), C.byref(m)))
+        return int(c.value), int(m.value)
+
+    def index_cells_read(self, ix):
+        """The index's partition as ``cells_host`` reports one (scann_index_cells_read); "cells" 0 and empty arrays without one."""
+        info = np.zeros(4, np.int64)
+        self._check(self.lib.scann_index_cells_read(self._h, ix._h, _ptr(info), None, None, None, None, None))
+        c, t = int(info[0]), int(info[1])
+        centre, perm, first = np.zeros((c, ix.dim), np.float32), np.full(64 * t, -1, np.int32), np.zeros(c + 2, np.int32)
+        lo, hi = np.zeros(t, np.float32), np.zeros(t, np.float32)
+        if t:
+            self._check(self.lib.scann_index_cells_read(self._h, ix._h, _ptr(info), _ptr(centre), _ptr(perm), _ptr(first), _ptr(lo), _ptr(hi)))
+        return _cells_out(info, centre, perm, first, lo, hi)
+
+    def index_search_stats(self, ix):
+        """The last search on the index (scann_index_search_stats): {"total": (128-query group, 64-row tile) pairs a full search visits,
+        "seeds": pairs visited as seeds, "visited": pairs visited in all, "groups"}."""
+        out = np.zeros(4, np.int64)
+        self._check(self.lib.scann_index_search_stats(ix._h, _ptr(out)))
+        return {"total": int(out[0]), "seeds": int(out[1]), "visited": int(out[2]), "groups": int(out[3])}
 
     def index_add_batch(self, ix, rb, level, ids=None):
         """One forward of a resident batch; its ``level`` rows (OUT_BF_PROPERTY / OUT_AFTER_LC) are appended device to device."""

@@ -154,6 +154,12 @@ class SavedResult:
         return cls(*v.values(), level, dim)
 
 
+def auto_cells(n_rows):
+    """The cells ``LatentIndex.partition(cells="auto")`` asks for: one per 2,048 rows, at most 1,024 -- about 32 tiles to a cell, so that
+    the centre distances (cells / rows of a full search) and the pad entries (at most one tile per cell) both stay near 1/2048 of the index."""
+    return min(_hip.KMEANS_MAX_K, max(1, int(n_rows) // 2048))
+
+
 class LatentIndex:
     """Rows of one level of one model on its GPU.  ``level``: "structure" (one ``bf_property`` row per structure) or "atom" (one
     ``after_Lc`` row per real atom).  Every row carries the id of its structure and, at atom level, the atom's index within it."""
@@ -207,11 +213,50 @@ class LatentIndex:
         structures of an atom-level index, numbered in position order -- from the host copies the index keeps."""
         return self.model.engine.index_segments(self._ix)
 
+    def partition(self, cells="auto", max_iter=8):
+        """Partition the index into cells so that every nearest-row search over it -- ``nearest``, ``place``, ``attach``, the reference
+        pass of ``select``, the neighbour graph under ``embed``, ``density_peaks``, ``hierarchy`` and ``map_quality`` -- skips the cells
+        out of reach (scann_index_partition).  The answers stay the brute-force answers in every byte; the cell-ordered copy doubles the
+        index's device memory, and adding rows drops it.  ``cells``: 1 .. _hip.KMEANS_MAX_K, or "auto" = ``auto_cells(len(self))``;
+        ``max_iter``: Lloyd rounds that refine the farthest-point centres.  Returns {"cells": cells in use, "tiles": 64-row tiles of the
+        copy, "pad": its pad entries, "largest": rows of the largest cell, "pad_share": pad / (64 tiles)}."""
+        if isinstance(cells, str):
+            if cells != "auto":
+                raise ValueError('cells must be "auto" or an integer in 1 .. %d, got %r' % (_hip.KMEANS_MAX_K, cells))
+            cells = auto_cells(len(self))
+        cells, max_iter = _hip.check_cells_args(cells, max_iter)
+        info = self.model.engine.index_partition(self._ix, cells, max_iter)
+        info["pad_share"] = info["pad"] / (64.0 * info["tiles"]) if info["tiles"] else 0.0
+        return info
+
+    def drop_partition(self):
+        """Free the partition, if there is one: searches compare every row again.  Returns self."""
+        self.model.engine.index_partition(self._ix, 0, 0)
+        return self
+
+    def partition_args(self):
+        """(cells, max_iter) the partition was built with, or None without one, as the index itself knows them
+        (scann_index_partition_args).  An engine that has no such call -- the CPU stand-ins of the tests, never ``Engine`` -- has no
+        partitions."""
+        ask = getattr(self.model.engine, "index_partition_args", None)
+        cells, max_iter = ask(self._ix) if ask else (0, 0)
+        return (cells, max_iter) if cells else None
+
+    def search_stats(self):
+        """The last search over this index: {"total": (128-query group, 64-row tile) pairs a full search visits, "seeds", "visited",
+        "groups", "visited_share": visited / total}; without a partition visited == total."""
+        st = self.model.engine.index_search_stats(self._ix)
+        st["visited_share"] = st["visited"] / st["total"] if st["total"] else 1.0
+        return st
+
     def save(self, path):
-        """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``)."""
+        """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``), and of the partition's arguments if the index
+        has one: the build is deterministic, so ``load`` rebuilds the same layout."""
         rows, ids, atoms = self.rows()
+        part = self.partition_args()
+        extra = {"partition": np.array(part, dtype=np.int64)} if part else {}
         with open(path, "wb") as f:
-            np.savez(f, rows=rows, ids=ids, atoms=atoms, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64))
+            np.savez(f, rows=rows, ids=ids, atoms=atoms, level=np.array(self.level), dim=np.array(self.dim, dtype=np.int64), **extra)
 
     @classmethod
     def load(cls, model, path):
@@ -219,12 +264,15 @@ class LatentIndex:
         with np.load(path, allow_pickle=False) as z:
             level, dim = str(z["level"]), int(z["dim"])
             rows, ids, atoms = z["rows"], z["ids"], z["atoms"]
+            part = tuple(int(v) for v in z["partition"]) if "partition" in z.files else (0, 0)
         if level_dim(model.config, level) != dim or rows.ndim != 2 or rows.shape[1] != dim:
             raise ValueError(width_mismatch("index", level, dim, model.config, path))
         ix = cls(model, level)
         if len(rows):
             ix.add_rows(rows, ids, atoms)
         ix._n_struct = int(ids.max()) + 1 if len(ids) else 0  # default ids of later adds do not collide
+        if part[0] and len(rows):
+            ix.partition(part[0], part[1])
         return ix
 
     def select(self, m, reference=None, stop_distance=None):
@@ -1585,8 +1633,9 @@ def embed_fit_args(perplexity, iterations, exaggeration, learning_rate, route):
 
 def neighbour_graph(index, chunk=4096, strict=True):
     """For every row of ``index`` its nearest other rows -- 31, or all others in a smaller index --: (position int32 [N, K], dist2 fp32
-    [N, K]), nearest first.  The rows are read back and searched ``chunk`` at a time with k = 32 and no id skipping
-    (``Engine.index_read`` + ``Engine.index_query``): bits and total order are the search's.  From a row's answer its own position is
+    [N, K]), nearest first.  The rows are searched ``chunk`` at a time, where they lie on the device, with k = 32 and no id skipping
+    (``Engine.index_query_rows``, the bits of ``Engine.index_read`` + ``Engine.index_query``, which is what an engine without that call
+    is asked for: the CPU stand-ins of the tests only, the route is never taken with ``Engine``): bits and total order are the search's.  From a row's answer its own position is
     dropped where it appears, otherwise (33 or more coincident rows) the last place.  ValueError for a row with a non-finite component
     (``strict`` False: no such check, an overflowed distance stays +inf; ``hierarchy`` passes rows without a non-finite component)."""
     eng, ix = index.model.engine, index._ix
@@ -1597,8 +1646,7 @@ def neighbour_graph(index, chunk=4096, strict=True):
     pos, d2 = np.empty((N, k - 1), np.int32), np.empty((N, k - 1), np.float32)
     for a in range(0, N, int(chunk)):
         b = min(N, a + int(chunk))
-        rows, _, _ = eng.index_read(ix, a, b - a)
-        r = eng.index_query(ix, rows, k)
+        r = eng.index_query_rows(ix, a, b - a, k) if hasattr(eng, "index_query_rows") else eng.index_query(ix, eng.index_read(ix, a, b - a)[0], k)
         own = r["position"] == np.arange(a, b, dtype=np.int32)[:, None]
         drop = np.where(own.any(axis=1), own.argmax(axis=1), k - 1)
         keep = np.ones((b - a, k), bool)

@@ -386,14 +386,21 @@ class HipModel:
             out["rollout"] = R
         return out
 
-    def build_index(self, data, level="structure", ids=None, batch_size=None):
+    def build_index(self, data, level="structure", ids=None, batch_size=None, cells=None):
         """A ``LatentIndex`` of ``data`` on this model's GPU: one ``bf_property`` row per structure (``level`` "structure") or one
         ``after_Lc`` row per real atom ("atom"), computed batch by batch and kept on the device.  ``data``: a padded dict, a
         ``PackedBatch`` or a dataset as ``predict_dataset`` takes it; ``ids``: one per structure (default 0 .. n-1 in input order).  A bad
-        level or batch_size raises ValueError before anything is uploaded."""
+        level or batch_size raises ValueError before anything is uploaded.  ``cells`` ("auto" or 1 .. 1024; default None: none): partition the
+        finished index (``LatentIndex.partition``), so that ``nearest``, ``place``, ``attach`` and ``select_diverse`` skip cells out of
+        reach; their answers do not change."""
         level_dim(self.config, level)
         self._batch_size(batch_size)
-        return LatentIndex(self, level).add(data, ids=ids, batch_size=batch_size)
+        if cells is not None and cells != "auto":
+            _hip.check_cells_args(cells, 0)
+        index = LatentIndex(self, level).add(data, ids=ids, batch_size=batch_size)
+        if cells is not None and len(index):
+            index.partition(cells)
+        return index
 
     def nearest(self, inputs, index, k=5, exclude_ids=None, batch_size=None):
         """The ``k`` nearest rows of a ``LatentIndex`` for every structure (or, for an atom-level index, every atom) of ``inputs``, by

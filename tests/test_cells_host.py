@@ -1,0 +1,250 @@
+"""CPU tests of an index's partition into cells and of the search that skips cells out of reach (include/scann_hip.h:
+scann_index_partition): no GPU is needed.
+
+1. The bound (scann_cell_bound) is sound: on a grid of dimensions 1 .. 1024, magnitudes 1e-22 .. 3e18 and spreads 1e-4 .. 30 round a
+   centre, with a query equal to a row, equal to the centre and exactly on a shell, no chain distance of the host twin
+   (scann_knn_distsq_matrix) lies below it -- and it is not vacuous.
+2. The host twin scann_cells_host equals the NumPy restatement of the definition (tests/cells_ref.py) in every byte.
+3. The pruned search, written in NumPy over the host partition, returns the total-order selection of the full distance matrix
+   (tests/knn_ref.py), also where most distances tie; on well-separated blobs it visits at most half of the (group, tile) pairs.
+4. The ABI, the Python layer's argument checks, and the stand-alone program under the sanitizers (make asan-cells)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cells_ref
+import kmeans_ref
+import knn_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "scann--material_amd", "csrc")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- 1. the bound ----
+
+def test_bound_is_the_header_formula(hip_lib):
+    from scann import _hip
+
+    rng = np.random.default_rng(0)
+    D = (rng.standard_normal(400) ** 2 * 10.0 ** rng.integers(-30, 30, 400)).astype(np.float32)
+    lo = (D * rng.uniform(0, 2, 400)).astype(np.float32)
+    hi = (lo * rng.uniform(1, 3, 400)).astype(np.float32)
+    want = cells_ref.bound(D, lo, hi)
+    got = np.array([_hip.cell_bound(a, b, c) for a, b, c in zip(D, lo, hi)])
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)) and (got > 0).sum() > 50
+    assert _hip.cell_bound(np.inf, 0, 1) == 0 and _hip.cell_bound(np.nan, 0, 1) == 0 and _hip.cell_bound(4, 0, np.inf) == 0
+    assert _hip.cell_bound(4, np.nan, np.nan) == 0 and _hip.cell_bound(1, 1, 1) == 0 and _hip.cell_bound(0, 0, 0) == 0
+    assert 80 < _hip.cell_bound(100, 0, 1) < 81 and 99 < _hip.cell_bound(0, 100, 121) < 100
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3, 33, 128, 1024])
+def test_bound_never_exceeds_a_chain_distance(hip_lib, dim):
+    from scann import _hip
+
+    rng = np.random.default_rng(dim)
+    pairs = positive = violations = 0
+    n, tile = 48, 16
+    for mag in (1e-22, 1e-12, 1e-3, 1.0, 1e6, 3e18):
+        for spread in (1e-4, 1e-2, 1.0, 30.0):
+            z = (rng.standard_normal((1, dim)) * mag).astype(np.float32)
+            x = (z + rng.standard_normal((n, dim)) * (mag * spread)).astype(np.float32)
+            with np.errstate(all="ignore"):
+                dz = _hip.knn_dist2_matrix(x, z)[:, 0]  # the row first, as scann_index_kmeans forms it
+            x = x[np.argsort(dz, kind="stable")]
+            dz = np.sort(dz, kind="stable")
+            qs = [z + rng.standard_normal((6, dim)) * (mag * s) for s in (1e-4, 1e-2, 1.0, 30.0)]
+            qs += [x[:1], x[-1:], z, z + (x[tile - 1:tile] - z)[:, ::-1]]  # a row, the centre, a point on the first shell (dim > 1: elsewhere on it)
+            q = np.concatenate(qs).astype(np.float32)
+            with np.errstate(all="ignore"):
+                D = _hip.knn_dist2_matrix(q, z)[:, 0]
+                d = _hip.knn_dist2_matrix(q, x)
+            for t0 in range(0, n, tile):
+                lb = np.array([_hip.cell_bound(a, dz[t0], dz[t0 + tile - 1]) for a in D])  # the exported function itself ...
+                assert np.array_equal(lb.view(np.uint64), cells_ref.bound(D, dz[t0], dz[t0 + tile - 1]).view(np.uint64))  # ... = the restatement
+                below = d[:, t0:t0 + tile].astype(np.float64) < lb[:, None]  # (a NaN distance never qualifies and is not claimed)
+                violations += int(below.sum())
+                positive += int((lb > 0).sum())
+                pairs += below.size
+    print("dim %d: %d pairs, %d positive bounds, %d violations" % (dim, pairs, positive, violations))
+    assert violations == 0
+    assert positive > 0
+
+
+# ---- 2. the twin against the definition ----
+
+def _case_rows(name, n, dim, rng):
+    rows = rng.standard_normal((n, dim)).astype(np.float32)
+    if name == "blobs":
+        rows += (rng.integers(0, 3, n)[:, None] * 20).astype(np.float32)
+    elif name == "identical":
+        rows[:] = np.float32(1.5)
+    elif name == "nonfinite" and n >= 3:
+        rows[0, 0], rows[n // 2, dim - 1], rows[n - 1, 0] = np.nan, np.inf, -np.inf
+    elif name == "grid":
+        rows = rng.integers(0, 4, (n, dim)).astype(np.float32)
+    return rows
+
+
+TWIN_CASES = [(n, dim, cells, name) for n in (1, 63, 64, 65, 1000) for dim, cells, name in
+              ((3, 1, "random"), (33, 7, "blobs"), (2, 64, "random"), (3, 4, "identical"), (5, 5, "nonfinite"), (2, 9, "grid"))]
+
+
+@pytest.mark.parametrize("n,dim,cells,name", TWIN_CASES, ids=["N%d_d%d_c%d_%s" % c for c in TWIN_CASES])
+def test_twin_equals_the_definition(hip_lib, n, dim, cells, name):
+    from scann import _hip
+
+    rows = _case_rows(name, n, dim, np.random.default_rng(n * 31 + cells))
+    got = _hip.cells_host(rows, cells, 4)
+    want = cells_ref.partition(rows, cells, 4, _hip.knn_dist2_matrix)
+    cells_ref.same(got, want, name)
+    real = got["perm"][got["perm"] >= 0]
+    assert np.array_equal(np.sort(real), np.arange(n)) and got["tiles"] * 64 == len(got["perm"]) and got["pad"] == len(got["perm"]) - n
+    if name == "identical" and n > 1:  # every centre is the same point: all rows go to cell 0, the other cells are empty
+        assert got["cells"] == min(cells, n) and got["largest"] == n and np.all(np.diff(got["first_tile"][1:]) == 0)
+    if name == "nonfinite" and n >= 3:
+        loose = got["perm"][64 * got["first_tile"][got["cells"]]:]
+        assert np.array_equal(loose[loose >= 0], [0, n // 2, n - 1]) and got["lo"][-1] == 0 and np.isinf(got["hi"][-1])
+
+
+def test_twin_in_numpy_alone_and_special_layouts(hip_lib):
+    from scann import _hip
+
+    rng = np.random.default_rng(3)
+    rows = rng.standard_normal((90, 3)).astype(np.float32)
+    cells_ref.same(_hip.cells_host(rows, 5, 3), cells_ref.partition(rows, 5, 3, kmeans_ref.fma_dist2), "numpy chain")
+    # a cell of exactly 64 rows beside one of 5: two tiles, one full, no pad in the first
+    rows = rng.standard_normal((69, 2)).astype(np.float32)
+    rows[64:, 0] += 1000
+    got = _hip.cells_host(rows, 2, 8)
+    assert got["cells"] == 2 and got["tiles"] == 2 and got["pad"] == 59 and got["largest"] == 64 and sorted(np.diff(got["first_tile"])[:2]) == [1, 1]
+    cells_ref.same(got, cells_ref.partition(rows, 2, 8, _hip.knn_dist2_matrix), "a cell of 64")
+    # cells > N: one cell per row at most; no eligible row: no cell, everything loose
+    got = _hip.cells_host(rows[:5], 64, 2)
+    assert got["cells"] == 5 and got["tiles"] == 5 and np.array_equal(got["lo"], np.zeros(5, np.float32))
+    got = _hip.cells_host(np.full((3, 2), np.nan, np.float32), 4, 2)
+    assert got["cells"] == 0 and got["tiles"] == 1 and np.array_equal(got["perm"][:3], [0, 1, 2]) and np.isinf(got["hi"][0])
+    for bad in (lambda: _hip.cells_host(rows, 0), lambda: _hip.cells_host(rows, 1025), lambda: _hip.cells_host(rows, 2, -1),
+                lambda: _hip.cells_host(rows[:0], 2), lambda: _hip.cells_host(rows, True), lambda: _hip.cells_host(rows, 2.5)):
+        with pytest.raises(ValueError):
+            bad()
+
+
+# ---- 3. the pruned search on the host ----
+
+def _check_pruned(rows, q, k, cells, label, ids=None, query_ids=None):
+    from scann import _hip
+
+    part = _hip.cells_host(rows, cells, 4)
+    with np.errstate(all="ignore"):
+        d = _hip.knn_dist2_matrix(q, rows)
+    want_d, want_p, _, _ = knn_ref.select(d, k, ids=ids, query_ids=query_ids)
+    got_d, got_p, st = cells_ref.pruned_search(rows, part, q, k, _hip.knn_dist2_matrix, ids=ids, query_ids=query_ids)
+    print("%s: N %d, Q %d, k %d, cells %d: visited %d of %d pairs (%d seeds)" % (label, len(rows), len(q), k, part["cells"], st["visited"],
+                                                                               st["total"], st["seeds"]))
+    assert np.array_equal(got_p, want_p), label
+    assert np.array_equal(_bits(got_d), _bits(want_d)), label
+    return st
+
+
+def blobs(seed=11):
+    """8 blobs of 512 rows in 32 columns, centres at 1000 e_b, unit variance, shuffled; 256 queries, 128 round blob 0 and 128 round blob 5,
+    interleaved"""
+    rng = np.random.default_rng(seed)
+    rows = rng.standard_normal((8 * 512, 32)).astype(np.float32)
+    for b in range(8):
+        rows[b * 512:(b + 1) * 512, b] += 1000
+    rows = rows[rng.permutation(len(rows))]
+    q = rng.standard_normal((256, 32)).astype(np.float32)
+    q[0::2, 0] += 1000
+    q[1::2, 5] += 1000
+    return rows, q
+
+
+def test_pruned_search_is_the_full_selection_on_the_host(hip_lib):
+    rng = np.random.default_rng(7)
+    for n, dim, cells, k, nq in ((1, 3, 1, 1, 1), (63, 2, 2, 5, 7), (65, 33, 7, 32, 129), (130, 3, 64, 5, 7), (300, 2, 200, 32, 20), (700, 8, 7, 5, 140)):
+        rows = (rng.standard_normal((n, dim)) + rng.integers(0, 3, (n, 1)) * 6).astype(np.float32)
+        q = (rng.standard_normal((nq, dim)) + rng.integers(0, 3, (nq, 1)) * 6).astype(np.float32)
+        _check_pruned(rows, q, k, cells, "random")
+    # most distances tie: the integer grid {0..3}^2, and {0, 1}^8 in wider rows; queries on the grid as well
+    grid = rng.integers(0, 4, (600, 2)).astype(np.float32)
+    _check_pruned(grid, rng.integers(0, 4, (129, 2)).astype(np.float32), 32, 7, "grid")
+    cube = np.zeros((500, 16), np.float32)
+    cube[:, :8] = rng.integers(0, 2, (500, 8))
+    qc = np.zeros((40, 16), np.float32)
+    qc[:, :8] = rng.integers(0, 2, (40, 8))
+    _check_pruned(cube, qc, 32, 9, "cube")
+    # query ids that exclude a whole id, and every row; non-finite rows and a query with a NaN
+    rows = (rng.standard_normal((200, 4)) + rng.integers(0, 2, (200, 1)) * 9).astype(np.float32)
+    ids = (np.arange(200) // 50).astype(np.int64)
+    q = rows[rng.integers(0, 200, 30)].copy()
+    _check_pruned(rows, q, 5, 4, "exclude a segment", ids=ids, query_ids=np.full(30, 2, np.int64))
+    _check_pruned(rows, q, 5, 4, "exclude every row", ids=np.zeros(200, np.int64), query_ids=np.zeros(30, np.int64))
+    rows[3], rows[77, 1], rows[150] = np.nan, np.inf, 3e19
+    q[4, 0] = np.nan
+    _check_pruned(rows, q, 32, 4, "non-finite")
+
+
+def test_pruned_search_skips_on_blobs_on_the_host(hip_lib):
+    rows, q = blobs()
+    st = _check_pruned(rows, q, 5, 8, "blobs")
+    assert st["groups"] == 2 and 2 * st["visited"] <= st["total"], st
+
+
+# ---- 4. the ABI, the Python layer, the sanitizers ----
+
+def test_header_and_python_agree(hip_lib):
+    from scann import _hip
+
+    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
+    for text in ("int scann_index_partition(scann_handle_t* h, scann_index_t* idx, int32_t cells, int32_t max_iter, int64_t* info /* [4] or NULL */);",
+                 "int scann_index_cells_read(scann_handle_t* h, scann_index_t* idx, int64_t* info /* [4] */, float* centres, int32_t* perm, "
+                 "int32_t* first_tile, float* lo, float* hi);",
+                 "int scann_index_search_stats(const scann_index_t* idx, int64_t* out /* [4] */);",
+                 "int scann_index_query_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t k, float* dist2, int64_t* ids, "
+                 "int32_t* atoms, int32_t* pos);",
+                 "int scann_cells_host(const float* rows, int64_t n, int64_t dim, int32_t cells, int32_t max_iter, int64_t* info, float* centres, "
+                 "int32_t* perm, int32_t* first_tile, float* lo, float* hi);",
+                 "double scann_cell_bound(float D, float lo, float hi);", "it doubles the index's device memory",
+                 "g = max((1 - eps) a - (1 + eps) r_hi, (1 - eps) r_lo - (1 + eps) a) - 2^-64", "lb = 0 whenever D or hi is not finite",
+                 "the chain value dist2(q, x) >= lb", "Loose tiles are always visited", "> tau_q, strictly"):
+        assert text in flat, text
+    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    P = C.c_void_p
+    assert sig["scann_index_partition"] == (C.c_int, [P, P, C.c_int32, C.c_int32, P])
+    assert sig["scann_index_cells_read"] == (C.c_int, [P] * 8)
+    assert sig["scann_index_search_stats"] == (C.c_int, [P, P])
+    assert sig["scann_index_query_rows"] == (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P])
+    assert sig["scann_cells_host"] == (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P, P])
+    assert sig["scann_cell_bound"] == (C.c_double, [C.c_float, C.c_float, C.c_float])
+    for name in ("scann_index_partition", "scann_index_partition_args", "scann_index_cells_read", "scann_index_search_stats", "scann_index_query_rows",
+                 "scann_cells_capacity", "scann_cells_host", "scann_cell_bound"):
+        assert hasattr(hip_lib, name), name
+    # null arguments are refused without a device
+    assert hip_lib.scann_index_partition(None, None, 4, 1, None) == -1 and hip_lib.scann_index_cells_read(None, None, None, None, None, None, None, None) == -1
+    assert hip_lib.scann_index_search_stats(None, None) == -1 and hip_lib.scann_index_query_rows(None, None, 0, 1, 1, None, None, None, None) == -1
+    assert hip_lib.scann_cells_capacity(1000, 7) == 1000 // 64 + 8
+
+
+def test_python_layer_checks_its_arguments():
+    from scann import _hip
+    from scann.models import latent_index
+
+    assert [latent_index.auto_cells(n) for n in (0, 1, 2047, 2048, 131072, 2400000, 10 ** 8)] == [1, 1, 1, 1, 64, 1024, 1024]
+    for cells, it in ((0, 1), (1025, 1), (True, 1), (2.0, 1), ("7", 1), (3, -1), (3, 1.5)):
+        with pytest.raises(ValueError):
+            _hip.check_cells_args(cells, it)
+    assert _hip.check_cells_args(np.int64(5), np.int32(0)) == (5, 0) and _hip.check_cells_args(0, 2, lowest=0) == (0, 2)
+
+
+def test_twin_under_the_sanitizers():
+    """make asan-cells: the stand-alone program drives scann_cells_host and scann_cell_bound under AddressSanitizer + UBSan"""
+    r = subprocess.run(["make", "-C", CSRC, "asan-cells"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "scann_cells_check: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
