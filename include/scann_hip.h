@@ -166,6 +166,13 @@ int scann_device_memory(scann_handle_t* h, int64_t* free_bytes, int64_t* total_b
  * reference's fp32 Dense layers, attention.py:95-113) instead of returning SCANN_ERR_RANGE; this counts them.  Env
  * SCANN_STRICT_RANGE=1 turns the re-run off (the error is returned).  Training entry points always return the error. */
 int64_t scann_exact_reruns(const scann_handle_t* h);
+/* 1 if every inference forward of the handle runs on the exact-fp32 kernels because of its checkpoint: a 128x128 kernel with
+ * |w| >= 255.9, or an operand of a split-fp16 projection that stays below the scheme's low end -- a kernel column below 2^-16
+ * throughout, or operand rows whose largest element the loaded tensors keep below 2^-8: LayerNorm outputs, the first layer's centres
+ * and geometry, the key projection's centres x geometry product, the swish rows of the ResidualNorm and of after_Lc (there a hi + lo
+ * pair has an absolute quantum of 2^-25, not 22 significant bits).  Decided by scann_load_weights, not repeated after optimiser steps.  Such a handle refuses to train, to sample MC
+ * dropout, to return input gradients or per-layer intermediates, with an error that names the tensor.  0 otherwise. */
+int scann_weights_exact(const scann_handle_t* h);
 int scann_num_streams(const scann_handle_t* h);
 
 /* ---- outputs beyond y and the GlobalAttention scores (what a user of the reference reads through a Keras sub-model, as

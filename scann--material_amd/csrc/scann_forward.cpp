@@ -250,11 +250,14 @@ int run_forward(scann_handle* h, scann_dbatch* db, hipStream_t s, const FwdOpts&
   const bool exact = o.exact || ((h->force_exact || W->weights_exact) && !debug && !tr);
   const int nm = o.n_member;
   const int64_t wst = o.m_w, ast = o.m_a;  // byte strides between members' weight images / workspaces (0: not a set launch)
+  if (!W->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
+  if (W->small_operands && !exact && !h->generic)  // a debug or a training forward: only the split-fp16 kernels keep what those read
+    return fail(h, SCANN_ERR_UNSUPPORTED, "forward: " + W->exact_reason + "; per-layer intermediates (scann_set_debug) and the training forward exist on "
+                                          "the split-fp16 kernels only (inference of such a checkpoint runs on the exact-fp32 kernels)");
   if (!o.of_set) {
     db->idle = false;  // work is being enqueued on the batch (scann_batch_release)
     db->fwd_pending = true;
   }
-  if (!W->loaded) return fail(h, SCANN_ERR_WEIGHTS, "forward: weights not loaded");
   const scann_config_t& c = h->cfg;
   const int L = c.n_attention;
   const bool outs = o.out_flags != FWD_OUT_UNTOUCHED;  // this forward writes the batch's output block and db->out_* record what
@@ -609,6 +612,7 @@ int scann_debug_read(scann_handle_t* h, scann_dbatch_t* db, int what, int layer,
 }
 
 int64_t scann_exact_reruns(const scann_handle_t* h) { return h ? h->exact_reruns : -1; }
+int scann_weights_exact(const scann_handle_t* h) { return h ? (int)h->weights_exact : -1; }
 
 int scann_set_outputs(scann_handle_t* h, uint64_t attn_layers, int32_t flags) {
   if (!h) return SCANN_ERR_INVALID;
@@ -668,8 +672,8 @@ int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, u
   if (!(p_drop < 1.f) || !(p_attn < 1.f)) return fail(h, SCANN_ERR_INVALID, "scann_predict_mc: dropout rates must lie in [0, 1)");
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_predict_mc: weights not loaded");
   if (!h->generic && (h->weights_exact || h->force_exact))
-    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_predict_mc: this handle's forwards run on the exact-fp32 kernels (a 128x128 kernel with |w| >= 255.9, "
-                                          "or SCANN_EXACT=1), which have no dropout instantiations");
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_predict_mc: this handle's forwards run on the exact-fp32 kernels (" +
+                                              (h->weights_exact ? h->exact_reason : std::string("SCANN_EXACT=1")) + "), which have no dropout instantiations");
   HIPCHK(h, hipSetDevice(h->device));
   const int T = n_samples, A = db->n_atom, B = db->n_struct;
   const int slot = db->last_slot;  // behind whatever was last enqueued on the batch

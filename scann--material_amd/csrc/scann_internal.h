@@ -98,7 +98,10 @@ __device__ __forceinline__ double gen_pool_score(const float* __restrict__ gq, c
 // kernels therefore test every LayerNorm variance (and the one activation that no LayerNorm follows) for finiteness and, on
 // failure, store (site << 8 | layer + 1) in a host-pinned word that the entry points returning results check after their
 // synchronisation (SCANN_ERR_RANGE).  Sites: 1 layer_norm_g, 2 layer_norm (context), 3 ResidualNorm, 4 after_Lc activation,
-// 5 a weight after an optimiser step.
+// 5 a weight after an optimiser step.  The guard watches the TOP of the range only.  The bottom -- operand rows or kernel columns so
+// small that their lo parts are fp16 subnormals and the pair keeps fewer than 22 bits -- costs precision, not finiteness, and no
+// statistic downstream shows it; it is decided per checkpoint when the weights are loaded (scann_runtime.cpp: small_operand_reason;
+// scann_weights_exact), at no cost per launch.
 __device__ __forceinline__ void flag_range(int32_t* flag, int site, int layer) {
   if (flag && *reinterpret_cast<volatile int32_t*>(flag) == 0)  // the first report stands: kernels run in layer order on their stream
     *flag = (site << 8) | (layer + 1);

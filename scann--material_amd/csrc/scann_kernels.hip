@@ -278,8 +278,17 @@ void launch_atom(const AtomArgs& a, hipStream_t s, int n_cu, int force_rows) {
 // once at load time (pack_weight_f16: pre-scaled by 2^8 so that their lo parts stay normal numbers; the exact inverse is
 // applied to the accumulators), activations when a tile is written to LDS -- the tile buffer holds a hi plane and a lo plane
 // of 64 x 128 fp16 instead of 64 x 128 fp32: same bytes, same b128 fragment reads.
-// Range: |activation| and |weight * 256| must stay below 65504 (scann_load_weights refuses larger weights; activations here
-// are LayerNorm / swish outputs of O(1..10)).
+// Range, top: |activation| and |weight * 256| must stay below 65504 (a 128x128 kernel beyond that sends the handle to the EX
+// kernels at load time, an activation beyond it trips flag_range and the forward is re-run on them).
+// Range, bottom: hi + lo has 22 significant bits only while lo is a normal fp16 number; below that the pair has an absolute quantum
+// (error <= 2^-25), so a row of operands whose LARGEST element is m is carried to about 2^-25 / m of that element.  Nothing in
+// these kernels scales a row (the fused backward does: row_scale, scann_train_fused.hip).  Instead scann_load_weights classifies
+// the checkpoint (scann_runtime.cpp: small_operand_reason, which lists every operand): LayerNorm outputs, whose size gamma and beta
+// fix; the first layer's centres (the embedding table through dense_embed) and geometry (the K = 20 filters over their scalar input);
+// ang = c[j] * geom', the PRODUCT of two such rows; the swish of one Dense layer of a LayerNorm output; and the kernels' own columns --
+// where one of them stays below 2^-8 (a column of a kernel times 2^8: the same) the handle runs on the EX kernels from the start,
+// like one with |w| >= 255.9.  Not covered: rows that are small for reasons of the DATA alone under ordinary weights, cgcnn feature
+// rows beyond an upper bound, and weights that training makes small after the load.
 
 //
 // FB (g_update, 64-row tiles, first layer of an inference forward): the geometry rows come out of basis_kernel's arithmetic, done

@@ -240,6 +240,172 @@ void pack_weight_f16(const float* W, int ld, int k_real, int ks, uint16_t* out) 
         }
 }
 
+// The low end of the split-fp16 range.  A pair hi + lo holds 22 significant bits only while lo is a normal fp16 number; below that it
+// has an absolute quantum (rounding error <= 2^-25), so an operand row whose LARGEST element is m carries a relative error of about
+// 2^-25 / m, and so does a column of a kernel (times 2^8) whose largest element is m.  Below m = SMALL_OPERAND = 2^-8 that is more than
+// 2^-17 = 7.6e-6 per operand -- a decade above fp32's own 2^-24 and within a factor 13 of the 1e-4 the forward promises, which two
+// attention layers and the readout easily spend -- and the checkpoint runs on the exact-fp32 kernels instead, like one with |w| >= 255.9.
+// What the projections will see is known at load time, operand by operand:
+//   the columns of the seven kernels per layer and the three of the readout;
+//   the rows a LayerNorm hands on (centres and geometry from the second layer on, every context): x = gamma n + beta with n of zero mean
+//     and unit variance, component c of size sqrt(gamma_c^2 + beta_c^2);
+//   the first layer's centres, swish(dense_embed(embedding)): one row per table entry, computed here (first_centres);
+//   the first layer's geometry, swish(neighbor_d(.)) * swish(neighbor_w(.)): a K = 20 filter is a function of ONE scalar, so each
+//     component's largest value over the distances / angles is computed here (filter_size) -- a row can only be smaller;
+//   the key projection's operand, which is a PRODUCT, component by component: centres x the layer's new geometry (base branch: x the
+//     filtered Gaussians, times a neighbour weight that is 1 for an atom's widest neighbour) -- two factors of 2^-6 are a row of 2^-12;
+//   the two swish rows behind a Dense layer of a LayerNorm output -- the ResidualNorm's hidden row and after_Lc's output, z = x . W + b,
+//     of root mean square sqrt(sum_k gamma_k^2 W_kj^2 + (sum_k beta_k W_kj + b_j)^2) in column j, and swish(z) ~ z / 2 where it matters.
+// A row's size is the largest of its components' sizes.  Not classified: cgcnn features enter the first centres as an upper bound only
+// (features in [0, 1]: a row that is certainly small is found, another may not be); rows that are small for the DATA's sake under
+// ordinary weights (a structure whose after_Lc or ResidualNorm hidden rows happen to be tiny); and a checkpoint that becomes small
+// under training -- the rule runs in scann_load_weights, not after an optimiser step (site 5 of flag_range watches |w| >= 255.9 only).  Exact zeros are representable and never count: a kernel column or a LayerNorm that is zero
+// throughout is skipped, and a row's largest element decides, not its smallest.  Returns the cause, naming the tensor, or "".
+// (tests/split_ref.py restates the rule in NumPy: the suite's emulation of the scheme shows what it lets through.)
+constexpr double SMALL_OPERAND = 1.0 / 256.0;
+static std::string small_operand_reason(const scann_config_t& c, std::map<std::string, const float*>& src) {
+  const int L = c.n_attention;
+  auto col_small = [&](const std::string& name, int row0) {
+    const float* W = src[name] + (size_t)row0 * D;
+    double least = INFINITY;
+    for (int j = 0; j < D; ++j) {
+      double m = 0.0;
+      for (int k = 0; k < D; ++k) m = std::max(m, (double)std::fabs(W[(size_t)k * D + j]));
+      if (m > 0.0) least = std::min(least, m);
+    }
+    return least * (double)WSCALE < SMALL_OPERAND;
+  };
+  typedef std::vector<double> Row;  // one size per component
+  auto top = [](const Row& r) { return *std::max_element(r.begin(), r.end()); };
+  auto small = [&](const Row& r) { return top(r) > 0.0 && top(r) < SMALL_OPERAND; };
+  auto swish = [](double z) { return z / (1.0 + std::exp(-z)); };
+  auto ln_size = [&](const std::string& prefix) {  // the rows a LayerNorm hands on: sqrt(gamma_c^2 + beta_c^2)
+    const float *g = src[prefix + "/gamma"], *b = src[prefix + "/beta"];
+    Row r(D);
+    for (int k = 0; k < D; ++k) r[k] = std::sqrt((double)g[k] * g[k] + (double)b[k] * b[k]);
+    return r;
+  };
+  auto ln_small = [&](const std::string& prefix) { return small(ln_size(prefix)); };
+  // a K = 20 filter is a function of one scalar: the largest |swish(gaussians(x) . W + b)| of each component over x = 0 .. top in 64 steps
+  auto filter_size = [&](const std::string& prefix, double x_top) {
+    const float *W = src[prefix + "/kernel"], *b = src[prefix + "/bias"];
+    Row r(D, 0.0);
+    for (int i = 0; i <= 64; ++i) {
+      double g[NG];
+      for (int k = 0; k < NG; ++k) {
+        const double d = i * (x_top / 64.0) - k * (x_top / (NG - 1));
+        g[k] = std::exp(-d * d / 0.25);
+      }
+      for (int j = 0; j < D; ++j) {
+        double z = b[j];
+        for (int k = 0; k < NG; ++k) z += g[k] * W[(size_t)k * D + j];
+        r[j] = std::max(r[j], std::fabs(swish(z)));
+      }
+    }
+    return r;
+  };
+  // The first layer's centres, swish(dense_embed(.)): no LayerNorm precedes them, but the loaded tensors fix them.  Exact for the atomic
+  // embedding -- one row per table row from 1 on (row 0 is the padding index), with use_ring times the four ring-feature combinations;
+  // for cgcnn features an upper bound of every row, taking the features in [0, 1]: only rows that are CERTAINLY small are classified.
+  // Returns the size of each component (largest over the rows); *least = the smallest of the rows' largest elements that is not 0.
+  auto first_centres = [&](double* least) {
+    const int E = c.embedding_dim, cin = E + (c.use_ring ? 10 : 0);
+    const float *We = src["dense_embed/kernel"], *be = src["dense_embed/bias"];
+    std::vector<Row> in;
+    const bool bound = c.feature_cgcnn != 0;
+    if (bound) {
+      Row e(cin, 0.0);
+      const float *Wc = src["embed_atom/kernel"], *bc = src["embed_atom/bias"];
+      for (int k = 0; k < E; ++k) {
+        e[k] = std::fabs(bc[k]);
+        for (int f = 0; f < 92; ++f) e[k] += std::fabs(Wc[(size_t)f * E + k]);
+      }
+      if (c.use_ring)
+        for (int k = 0; k < 10; ++k) e[E + k] = std::fabs(src["extra_embed/bias"][k]) + std::fabs(src["extra_embed/kernel"][k]) + std::fabs(src["extra_embed/kernel"][10 + k]);
+      in.push_back(e);
+    } else {
+      const float* T = src["embed_atom/embeddings"];
+      for (int s = 1; s < c.n_atoms; ++s)
+        for (int rc = 0; rc < (c.use_ring ? 4 : 1); ++rc) {
+          Row e(cin);
+          for (int k = 0; k < E; ++k) e[k] = T[(size_t)s * E + k];
+          if (c.use_ring)
+            for (int k = 0; k < 10; ++k) e[E + k] = (rc >> 1) * (double)src["extra_embed/kernel"][k] + (rc & 1) * (double)src["extra_embed/kernel"][10 + k] + src["extra_embed/bias"][k];
+          in.push_back(e);
+        }
+    }
+    Row size(D, 0.0);
+    *least = INFINITY;
+    for (const Row& e : in) {
+      double m = 0.0;
+      for (int j = 0; j < D; ++j) {
+        double z = bound ? std::fabs(be[j]) : be[j];
+        for (int k = 0; k < cin; ++k) z += e[k] * (bound ? std::fabs(We[(size_t)k * D + j]) : We[(size_t)k * D + j]);
+        const double v = bound ? z : std::fabs(swish(z));  // |swish(z)| <= |z|
+        size[j] = std::max(size[j], v);
+        m = std::max(m, v);
+      }
+      if (m > 0.0) *least = std::min(*least, m);
+    }
+    return size;
+  };
+  auto swish_small = [&](const std::string& ln, const std::string& dense) {
+    const float *g = src[ln + "/gamma"], *b = src[ln + "/beta"], *W = src[dense + "/kernel"], *bias = src[dense + "/bias"];
+    double r = 0.0;
+    for (int j = 0; j < D; ++j) {
+      double var = 0.0, mean = bias[j];
+      for (int k = 0; k < D; ++k) {
+        const double w = W[(size_t)k * D + j];
+        var += (double)g[k] * g[k] * w * w;
+        mean += (double)b[k] * w;
+      }
+      r = std::max(r, std::sqrt(var + mean * mean));
+    }
+    return r > 0.0 && 0.5 * r < SMALL_OPERAND;
+  };
+  const std::string column = ": a column of the kernel is below 2^-16 throughout (its split-fp16 image keeps too few bits)";
+  const std::string few = " stay below 2^-8, where a split-fp16 operand keeps too few bits";
+  double least = 0.0;
+  Row cen = first_centres(&least);
+  if (least < SMALL_OPERAND) return "dense_embed: its swish output rows (the first layer's centres)" + few;
+  if (c.g_update && L > 0) {
+    Row g = filter_size("neighbor_d", (double)c.gaussian_d);
+    const Row gw = filter_size("neighbor_w", 2.0 * M_PI);
+    for (int k = 0; k < D; ++k) g[k] *= gw[k];
+    if (small(g)) return "neighbor_d, neighbor_w: the products of their swish outputs (the first layer's geometry)" + few;
+  }
+  for (int i = 0; i < L; ++i) {
+    const std::string p = "local_attention_" + std::to_string(i) + "/", r = "residual_norm_" + std::to_string(i) + "/";
+    {  // the key projection's operand is a PRODUCT, component by component: centres x this layer's new geometry (base branch: x the filtered
+       // Gaussians at their largest over the distances, times a neighbour weight that is 1 for an atom's widest neighbour)
+      Row ang = c.g_update ? ln_size(p + "layer_norm_g") : filter_size(p + "filter_geo", (double)c.gaussian_d);
+      for (int k = 0; k < D; ++k) ang[k] *= cen[k];
+      if (small(ang)) return p + "key: its operand rows (centres x geometry, component by component)" + few;
+      cen = ln_size((c.use_attn_norm ? r : p) + "layer_norm");
+    }
+    std::vector<std::string> names = {p + "query/kernel", p + "key/kernel"};
+    if (c.use_attn_norm) names.insert(names.end(), {r + "dense_1/kernel", r + "dense_2/kernel"});
+    for (const std::string& n : names)
+      if (col_small(n, 0)) return n + column;
+    if (c.g_update) {
+      for (int j = 0; j < 3; ++j)
+        if (col_small(p + "filter_geo/kernel", j * D)) return p + "filter_geo/kernel, rows " + std::to_string(j * D) + ".." + std::to_string(j * D + D - 1) + column;
+      if (ln_small(p + "layer_norm_g")) return p + "layer_norm_g: its output rows (the geometry) stay below 2^-8, where a split-fp16 operand keeps too few bits";
+    }
+    if (ln_small(p + "layer_norm")) return p + "layer_norm: its output rows (the context) stay below 2^-8, where a split-fp16 operand keeps too few bits";
+    if (c.use_attn_norm) {
+      if (ln_small(r + "layer_norm")) return r + "layer_norm: its output rows (the centres) stay below 2^-8, where a split-fp16 operand keeps too few bits";
+      if (swish_small(p + "layer_norm", r + "dense_1"))
+        return r + "dense_1: its swish output rows (the operand of dense_2) stay below 2^-8, where a split-fp16 operand keeps too few bits";
+    }
+  }
+  for (const char* n : {"after_Lc/kernel", "global_attention/query/kernel", "global_attention/key/kernel"})
+    if (col_small(n, 0)) return n + column;
+  if (L > 0 && swish_small((c.use_attn_norm ? "residual_norm_" : "local_attention_") + std::to_string(L - 1) + "/layer_norm", "after_Lc"))
+    return "after_Lc: its swish output rows (the operand of global_attention/query and key) stay below 2^-8, where a split-fp16 operand keeps too few bits";
+  return "";
+}
+
 }  // namespace scann
 
 extern "C" {
@@ -502,6 +668,15 @@ int load_weights(scann_handle* h, const float* blob, const scann_tensor_desc_t* 
           break;  // an fp32-only tensor (embedding, dense_embed, bf_property, head): any finite value
         }
     }
+  h->small_operands = false;
+  h->exact_reason = h->weights_exact ? "a 128x128 kernel has |w| >= 255.9" : "";
+  if (!h->weights_exact) {
+    const std::string why = small_operand_reason(c, src);
+    if (!why.empty()) {
+      h->weights_exact = h->small_operands = true;
+      h->exact_reason = why;
+    }
+  }
   struct LTOff { size_t W1T, W2T, W3T, WqT, WkT, Wf1T, Wf2T, W1Th, W2Th, W3Th, WqTh, WkTh, Wf1Th, Wf2Th; };
   std::vector<LTOff> lto(L);
   struct LOff {

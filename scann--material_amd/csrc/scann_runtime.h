@@ -137,7 +137,10 @@ struct scann_handle {
   std::map<std::string, int64_t> gt_off;  // "<tensor name>#<block>" -> offset in g_WT
   float* g_WT = nullptr;
   int gt_max = 0;                         // elements of the largest block
-  bool weights_exact = false;  // a loaded 128x128 kernel has |w| >= 255.9: the split-fp16 images cannot hold it, inference runs exact
+  bool weights_exact = false;  // a loaded 128x128 kernel has |w| >= 255.9 (the split-fp16 images cannot hold it), or an operand of a projection
+                               // stays below the scheme's low end (small_operands; scann_runtime.cpp: small_operand_reason): inference runs exact
+  bool small_operands = false;
+  std::string exact_reason;    // why weights_exact is set, naming the tensor (the text of the errors that refuse such a handle)
   bool force_exact = false;    // env SCANN_EXACT=1: every inference forward on the exact-fp32 kernels (test / diagnosis switch)
   bool strict_range = false;   // env SCANN_STRICT_RANGE=1: SCANN_ERR_RANGE instead of the exact-fp32 re-run of an inference forward
   int64_t exact_reruns = 0;    // forwards re-run on the exact-fp32 kernels so far (scann_exact_reruns)

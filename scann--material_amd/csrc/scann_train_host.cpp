@@ -785,7 +785,7 @@ int scann_train_begin(scann_handle_t* h) {
   if (!h) return SCANN_ERR_INVALID;
   if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_train_begin: weights not loaded");
   if (h->weights_exact)
-    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_train_begin: a 128x128 kernel has |w| >= 255.9; the training kernels multiply in split-fp16 "
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_train_begin: " + h->exact_reason + "; the training kernels multiply in split-fp16 "
                                           "form only (inference of such a checkpoint runs on the exact-fp32 kernels)");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t n = h->host_master.size();
@@ -1010,7 +1010,7 @@ int scann_input_grads(scann_handle_t* h, scann_dbatch_t* db, float* y, float* d_
   if (d_ring && !c.use_ring) return fail(h, SCANN_ERR_INVALID, "scann_input_grads: the model has no ring_aromatic input (use_ring off)");
   if (d_cgcnn && !c.feature_cgcnn) return fail(h, SCANN_ERR_INVALID, "scann_input_grads: the model has no cgcnn input (feature is not cgcnn)");
   if (h->weights_exact)
-    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_input_grads: a 128x128 kernel has |w| >= 255.9; the backward kernels multiply in split-fp16 "
+    return fail(h, SCANN_ERR_UNSUPPORTED, "scann_input_grads: " + h->exact_reason + "; the backward kernels multiply in split-fp16 "
                                           "form only (inference of such a checkpoint runs on the exact-fp32 kernels)");
   HIPCHK(h, hipSetDevice(h->device));
   if (h->generic && !h->g_WT)

@@ -104,6 +104,7 @@ SYMBOLS = [
     ("scann_plan_tiles_filled", C.c_int, [C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("scann_batch_tile_plan", C.c_int, [_P, _P, _P]),
     ("scann_exact_reruns", C.c_int64, [_P]),
+    ("scann_weights_exact", C.c_int, [_P]),
     ("scann_device_memory", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("scann_batch_info", C.c_int, [_P, _P, _P]),
     ("scann_count_padded", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -1252,8 +1253,8 @@ def load_library(path=None):
     _check_runtime_env()
     lib = C.CDLL(p)
     for name, res, args in SYMBOLS:
-        if name in ("scann_plan_tiles_filled", "scann_batch_tile_plan") and os.environ.get("SCANN_HIP_LIB") and not hasattr(lib, name):
-            continue  # (an earlier commit's library, named for an A/B run -- tools/ab_bits.py, tools/ab_libs.sh: it has no filled plan)
+        if name in ("scann_plan_tiles_filled", "scann_batch_tile_plan", "scann_weights_exact") and os.environ.get("SCANN_HIP_LIB") and not hasattr(lib, name):
+            continue  # (an earlier commit's library, named for an A/B run -- tools/ab_bits.py, tools/ab_libs.sh: it has no filled plan, no low-range rule)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1806,6 +1807,13 @@ class Engine:
     def exact_reruns(self):
         """forwards this handle has re-run on the exact-fp32 kernels because an activation left the split-fp16 range"""
         return int(self.lib.scann_exact_reruns(self._h))
+
+    def weights_exact(self):
+        """True if the loaded checkpoint sends every inference forward to the exact-fp32 kernels: a 128x128 kernel with |w| >= 255.9,
+        or an operand of a split-fp16 projection below the scheme's low end (scann_weights_exact, include/scann_hip.h)"""
+        if not hasattr(self.lib, "scann_weights_exact"):  # an earlier commit's library named through SCANN_HIP_LIB (load_library)
+            return False
+        return bool(self.lib.scann_weights_exact(self._h))
 
     def device_memory(self):
         """(free, total) bytes of the handle's device (hipMemGetInfo)"""
