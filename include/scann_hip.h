@@ -1102,6 +1102,60 @@ int scann_cells_host(const float* rows, int64_t n, int64_t dim, int32_t cells, i
                      int32_t* first_tile, float* lo, float* hi);
 double scann_cell_bound(float D, float lo, float hi);
 
+/* ---- Radius search: the rows within a distance of a query, exact, and near-duplicate pairs ----
+ * scann_index_query answers "which are the k nearest rows"; these calls answer "which rows lie within r".  The number of answers per
+ * query is unknown beforehand and may be zero, so the calls follow a size-then-fill protocol.
+ * Definition.  For a query q, a threshold radius2 and an index, the HITS of q are the rows with dist2(q, row) <= radius2, where
+ *   radius2 is fp32, >= 0, and +inf is allowed;
+ *   dist2 is exactly the chain of scann_knn_distsq with the query first;
+ *   the compare is an fp32 <=, inclusive; a NaN distance never qualifies; +inf is an ordinary value, so it qualifies only at
+ *     radius2 = +inf;
+ *   with query ids, rows whose id equals the query's are skipped, as in scann_index_query.
+ * A query's hits are listed in the total order (dist2 ascending, position ascending).  The first k hits of a query are therefore
+ * scann_index_query's first k places wherever those places qualify (tests/test_within_host.py, tests/test_gpu_within.py).
+ * The answer is a function of the queries, the index contents and radius2 only, in every byte: the kernel appends hits in the order
+ * they arrive, and the order above is established afterwards, by a sort of each query's segment whose keys (dist2, position) are unique.
+ * Counts and total.  counts[i] (the hits of query i) and *total (their sum) are always written and always exact; they are integers
+ *   added without an order, and a result in their own right: the ball count.
+ * Size-then-fill.  If *total <= cap, the hits of query i occupy places [F_i, F_i + counts[i]) of dist2 / pos / ids / atoms, F being the
+ *   exclusive prefix sum of counts; any of the four may be NULL.  Otherwise the entry arrays are NOT TOUCHED and the call still returns
+ *   SCANN_OK: the caller compares *total with cap and calls again.  cap = 0 with all four arrays NULL is the count-only call; an entry
+ *   array given with cap = 0 is SCANN_ERR_INVALID.  0 <= cap <= SCANN_WITHIN_MAX_CAP = 2^30.  The device staging is 12 bytes per entry
+ *   of cap; staging that does not fit is SCANN_ERR_OOM before any kernel runs.
+ * scann_index_within takes host queries q [nq * dim].  scann_index_within_rows takes rows first .. first + n - 1 of the index itself as
+ * the queries, read where they lie (as scann_index_query_rows); the query's own position never qualifies, and upper = 1 keeps only
+ * positions greater than the query's.  dist2 is symmetric bit for bit (the difference is negated exactly, its square is the same), so
+ * a self-join with upper = 1 lists every unordered pair exactly once.  scann_index_within_batch runs one inference forward of the
+ * resident batch with the level's output added for that forward only -- y [n_struct], ga [n_atom] or NULL, the range guard, the
+ * exact-fp32 re-run, the selection restore, generic widths and training handles exactly as scann_index_query_batch -- and then searches
+ * the level's rows where the forward left them; query_ids [n_struct] or NULL name the structures.
+ * With a partition (scann_index_partition) all three take a pruned route: the queries of a pass of up to 1,024 are ordered by their
+ * nearest centres as for scann_index_query, and a (group of 128 queries, tile) pair is skipped iff
+ *   scann_cell_bound(D(q, c(t)), lo_t, hi_t) > radius2, strictly, for EVERY query q of the group.
+ * The claim proved above gives dist2 >= lb > radius2 for every real row of a skipped tile, so no hit is lost.  The threshold is known
+ * before the first tile: there are no seeds.  Loose tiles are always visited; pad entries never qualify; positions are the original
+ * positions.  The result is that of the index without a partition in every byte.  scann_index_search_stats reports the pass like a
+ * search, with seeds = 0 (without a partition and upper = 1 the tiles that lie wholly at or below a group's least query position are
+ * not launched, so there visited < total).
+ * scann_within_host is the twin: rows [n * dim] with row_ids [n] (NULL: the position), queries q [nq * dim] with query_ids [nq] or NULL
+ * and query_pos [nq] (NULL, or the position each query holds in rows: that position never qualifies, and upper = 1, which needs
+ * query_pos, keeps only greater positions); counts, total, dist2 and pos are the device's bytes, no GPU work, at most 16 threads.
+ * SCANN_ERR_INVALID before anything is launched, with a message that names the argument: a null handle, index, counts or total, an
+ * index of another handle, an empty query or batch, rows outside the index, upper not 0 or 1, radius2 NaN or negative, cap negative
+ * or above the bound, an entry array with cap = 0, a bad level or width.  An empty index gives zeros.  The calls are synchronous and
+ * change nothing in the index, the weights, the training state or the selected outputs. */
+#define SCANN_WITHIN_MAX_CAP ((int64_t)1 << 30)
+int scann_index_within(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, float radius2, int64_t cap,
+                       int64_t* counts /* [nq] */, int64_t* total, float* dist2, int32_t* pos, int64_t* ids, int32_t* atoms /* [cap], any may be NULL */);
+int scann_index_within_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t upper, float radius2, int64_t cap,
+                            int64_t* counts, int64_t* total, float* dist2, int32_t* pos, int64_t* ids, int32_t* atoms);
+int scann_index_within_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, float radius2,
+                             int64_t cap, float* y, float* ga, int64_t* counts, int64_t* total, float* dist2, int32_t* pos, int64_t* ids,
+                             int32_t* atoms);
+int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* row_ids, const float* q, int64_t nq, const int64_t* query_ids,
+                      const int32_t* query_pos, int32_t upper, float radius2, int64_t cap, int64_t* counts, int64_t* total, float* dist2,
+                      int32_t* pos);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

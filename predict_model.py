@@ -72,6 +72,12 @@ built on the GPU and bit-reproducible: it prints the tree's size and each cluste
 noise, pickles the result as ``hierarchy_<target>.pickle`` and, with ``--hierarchy-out``, saves the tree as a ``LatentHierarchy`` (.npz)
 and the rows it was built on beside it as ``FILE.index.npz``.  ``--attach FILE --attach-min-cluster-size N`` loads both and pickles
 ``attach_<target>.pickle``: per structure the label of its row (or of its atoms' rows) under that hierarchy, -1 for noise.
+``--duplicates RADIUS [--duplicates-level atom] [--duplicates-out FILE]`` finds the dataset's near-duplicate groups: the structures (or
+atoms) whose rows lie within RADIUS of each other in the model's latent space, by the exact radius search on the GPU.  It prints the
+number of groups and of redundant rows and pickles the groups (pairs, distances, group per row, the dedup mask ``keep``, and the rows'
+dataset indices and atoms) as ``duplicates_<target>.pickle``, or as FILE.  ``--within RADIUS --within-index FILE`` is the leakage report:
+it prints how many of the dataset's structures have a row of the saved ``LatentIndex`` FILE, for example of the training set, within
+RADIUS, and pickles one dict per structure (count, neighbor_id, distance, position) as ``within_<target>.pickle``.
 ``--with <dir2>,<dir3>`` runs those trained models (one architecture) in one model set with ``<trained_model>`` over its dataset: each
 writes the energy_pre_<target>.pickle / ga_scores_<target>.pickle it would write alone, into its own folder, and when all targets agree
 ``ensemble_<target>.pickle`` (next to ``<trained_model>``) holds the mean and standard deviation (ddof 1) of the de-normalised predictions."""
@@ -154,6 +160,7 @@ def main(args):
         raise SystemExit("--cluster: K must lie in 1 .. 1024, got %d" % args.cluster)
     if args.cluster_iter < 0:
         raise SystemExit("--cluster-iter: N must be >= 0, got %d" % args.cluster_iter)
+    check_within_flags(args)
     sweep = check_sweep_flags(args)
     head_targets = check_head_flags(args)
     kernel_head_targets = check_kernel_head_flags(args)
@@ -306,6 +313,29 @@ def main(args):
             raise SystemExit("--pair: %s" % e) from None
         index.free()
         pickle.dump(per, open(os.path.join(args.trained_model, "pair_{}.pickle".format(target)), "wb"))
+    if args.duplicates is not None:
+        pool = scann.build_index(data, level=args.duplicates_level, ids=data.indexes)
+        dup = pool.duplicates(args.duplicates)
+        dup["id"], dup["atom"] = pool.names()
+        pool.free()
+        print("Duplicates within %g (%s level): %d rows, %d pairs, %d groups, %d redundant rows" % (
+            args.duplicates, args.duplicates_level, len(dup["group"]), len(dup["pairs"]), dup["n_groups"], len(dup["group"]) - dup["n_groups"]))
+        pickle.dump(dup, open(args.duplicates_out or os.path.join(args.trained_model, "duplicates_{}.pickle".format(target)), "wb"))
+    if args.within is not None:
+        from scann.models import LatentIndex
+
+        index = LatentIndex.load(scann.model, args.within_index)
+        if index.level != "structure":
+            raise SystemExit("--within-index: %s is a %s-level index, the leakage report needs a structure-level one" % (args.within_index, index.level))
+        r = scann.within(data, index, args.within)
+        print("Within %g of %s (%d rows): %d of %d structures have an indexed row within the radius" % (
+            args.within, args.within_index, len(index), int((r["count"] > 0).sum()), len(r["count"])))
+        index.free()
+        first = r["first"]
+        per = [{"predict_property": float(r["predict_property"][i, 0]), "count": int(r["count"][i])} for i in range(len(r["count"]))]
+        for i, d in enumerate(per):
+            d.update({n: r[n][first[i]:first[i + 1]] for n in ("neighbor_id", "distance", "position")})
+        pickle.dump(per, open(os.path.join(args.trained_model, "within_{}.pickle".format(target)), "wb"))
     if args.select:
         from scann.models import LatentIndex
 
@@ -762,6 +792,17 @@ def head_records(scann, data, head, kernel=False):
     return per
 
 
+def check_within_flags(args):
+    """--duplicates / --within: a radius >= 0 each, and --within needs the index it searches"""
+    for flag, value in (("--duplicates", args.duplicates), ("--within", args.within)):
+        if value is not None and not value >= 0:
+            raise SystemExit("%s: RADIUS must be >= 0, got %r" % (flag, value))
+    if args.within is not None and not args.within_index:
+        raise SystemExit("--within: needs --within-index FILE, the saved LatentIndex to search")
+    if args.within is None and args.within_index:
+        raise SystemExit("--within-index: needs --within RADIUS")
+
+
 def nearest_records(scann, data, index, k, exclude):
     """--nearest: one unpadded dict per structure of the dataset, in dataset order"""
     per = []
@@ -861,6 +902,16 @@ def parser():
                    help="the measure that shortlists the candidates, as --match-measure")
     p.add_argument("--pair-index", type=str, default="",
                    help="a saved atom-level LatentIndex (.npz) to pair against instead of the dataset itself; nothing is left out")
+    p.add_argument("--duplicates", type=float, default=None, metavar="RADIUS",
+                   help="find the dataset's near-duplicate groups: rows within RADIUS of each other in latent space (the exact radius "
+                        "search on the GPU); prints the groups and the redundant rows, pickles duplicates_<target>.pickle")
+    p.add_argument("--duplicates-level", type=str, default="structure", choices=["structure", "atom"],
+                   help="structure: bf_property rows, one per structure; atom: after_Lc rows, one per atom")
+    p.add_argument("--duplicates-out", type=str, default="", help="write the groups to FILE instead")
+    p.add_argument("--within", type=float, default=None, metavar="RADIUS",
+                   help="the leakage report: how many of the dataset's structures have a row of --within-index within RADIUS; pickles "
+                        "within_<target>.pickle, one dict per structure")
+    p.add_argument("--within-index", type=str, default="", help="the saved structure-level LatentIndex (.npz) that --within searches")
     p.add_argument("--select", type=int, default=0,
                    help="also pickle the M most diverse structures of the dataset (greedy k-center selection in latent space) as "
                         "selected_<target>.pickle: one dict with ids (dataset indices), atoms and radii in pick order")

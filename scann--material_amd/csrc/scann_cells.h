@@ -126,13 +126,14 @@ struct CellSearchArgs {
   int32_t* list;         // [2][n_group][n_tile]: the seeds, then the survivors
   int32_t* count;        // [2][n_group]
   const float* tau;      // [nq][k] the seed pass's merged lists (tau = the last place)
+  float radius2;         // plan pass 2 (a radius search): the threshold of every query
   float* part_d;         // [nq][2 * n_list][k]
   int32_t* part_p;
   int32_t n_list;
 };
 size_t cells_list_lds_bytes(int k);
 hipError_t launch_cells_centre(const CellSearchArgs& a, hipStream_t s);   // D, key_cell, key_d
-hipError_t launch_cells_plan(const CellSearchArgs& a, int pass, hipStream_t s);  // pass 0: seeds; 1: survivors
+hipError_t launch_cells_plan(const CellSearchArgs& a, int pass, hipStream_t s);  // pass 0: seeds; 1: survivors; 2: a radius search's survivors
 hipError_t launch_cells_list(const CellSearchArgs& a, int pass, hipStream_t s);
 
 }  // namespace scann

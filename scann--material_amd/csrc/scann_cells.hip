@@ -102,6 +102,8 @@ __global__ __launch_bounds__(256) void cells_centre_kernel(CellSearchArgs a) {
 }
 
 // One workgroup per group of 128 queries.  Flags of the group's tiles, then their ordered compaction into the pass's list.
+// pass 2 is the plan of a radius search (scann_within.cpp): pass 1's survivors with every tau_q = a.radius2 and no seeds; its list and
+// its count take the places of pass 0's.
 __global__ __launch_bounds__(256) void cells_plan_kernel(CellSearchArgs a, int pass) {
   __shared__ float dmin[CELLS_MAX], dmax[CELLS_MAX];  // per cell over the group's queries: least and greatest D (pass 1)
   __shared__ unsigned char wild[CELLS_MAX];                 // a query of the group has a D that is not finite
@@ -111,11 +113,13 @@ __global__ __launch_bounds__(256) void cells_plan_kernel(CellSearchArgs a, int p
   __shared__ int32_t base;
   __shared__ float tau_max;
   const int t = threadIdx.x, g = blockIdx.x, T = a.n_tile, C = a.C;
-  unsigned char* flag = a.seed_flag + (size_t)g * T;
+  const bool radius = pass == 2;
+  const int slot = radius ? 0 : pass;  // where the pass's list and count lie
+  unsigned char* flag = radius ? nullptr : a.seed_flag + (size_t)g * T;
   if (t < TILE_TQ) {
     const int q = a.qperm[g * TILE_TQ + t];
     ql[t] = q;
-    tau[t] = pass == 1 && q >= 0 ? a.tau[(size_t)q * a.k + a.k - 1] : __builtin_inff();
+    tau[t] = q < 0 || pass == 0 ? __builtin_inff() : radius ? a.radius2 : a.tau[(size_t)q * a.k + a.k - 1];
   }
   if (t == 0) base = 0;
   __syncthreads();
@@ -158,13 +162,13 @@ __global__ __launch_bounds__(256) void cells_plan_kernel(CellSearchArgs a, int p
   }
   __syncthreads();
   // the tiles in order, 256 at a time: this pass's flag of each, and the flagged ones appended to the list
-  int32_t* list = a.list + ((size_t)pass * a.n_group + g) * T;
+  int32_t* list = a.list + ((size_t)slot * a.n_group + g) * T;
   for (int t0 = 0; t0 < T; t0 += 256) {
     const int tt = t0 + t;
     int f = 0;
     if (tt < T) {
       if (pass == 0) f = flag[tt];
-      else if (flag[tt]) f = 0;            // a seed: visited already
+      else if (!radius && flag[tt]) f = 0;  // a seed: visited already
       else if (tt >= a.n_cell_tile) f = 1;  // a loose tile is always visited
       else {
         const int c = a.tile_cell[tt];
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256) void cells_plan_kernel(CellSearchArgs a, int p
     if (t == 255) base += scan[255];
     __syncthreads();
   }
-  if (t == 0) a.count[pass * a.n_group + g] = base;
+  if (t == 0) a.count[slot * a.n_group + g] = base;
 }
 
 // knn_tile_kernel's tile body over a list of tiles of the cell-ordered copy: workgroup (x, g) takes the x-th share of group g's list

@@ -200,9 +200,11 @@ int search_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKin
   return r;
 }
 
+}  // namespace
+
 // The rows a batch has at a level -- one per structure, or (atom) one per atom in packed order -- named: id_v = the structure's id
 // (ids[b]; ids null: first + b), at_v (if asked for) = the atom's index in its structure, -1 for a structure row
-int expand_ids(scann_handle* h, const scann_dbatch* db, bool atom, const int64_t* ids, int64_t first, std::vector<int64_t>& id_v,
+int scann::expand_ids(scann_handle* h, const scann_dbatch* db, bool atom, const int64_t* ids, int64_t first, std::vector<int64_t>& id_v,
                std::vector<int32_t>* at_v) {
   const int B = db->n_struct;
   id_v.assign((size_t)(atom ? db->n_atom : B), 0);
@@ -221,8 +223,6 @@ int expand_ids(scann_handle* h, const scann_dbatch* db, bool atom, const int64_t
   }
   return SCANN_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -8,6 +8,7 @@
 #include "scann_tile.h"
 
 struct scann_handle;
+struct scann_dbatch;
 namespace scann {
 struct CellPart;  // scann_cells.h
 }
@@ -49,6 +50,10 @@ int search(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqi
 int search_full(scann_handle* h, scann_index* ix, const float* dq, const int64_t* dqid, int64_t nq, int k, hipStream_t s, float* dist2, int64_t* ids,
                 int32_t* atoms, int32_t* pos, float* dev_d = nullptr);  // search() of an index without a partition, whether it has one or not
 void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out);
+// the rows a batch has at a level (one per structure, or with `atom` one per atom in packed order) named: id_v = the structure's id
+// (ids[b]; ids null: first + b), at_v (if asked for) = the atom's index in its structure, -1 for a structure row
+int expand_ids(scann_handle* h, const scann_dbatch* db, bool atom, const int64_t* ids, int64_t first, std::vector<int64_t>& id_v,
+               std::vector<int32_t>* at_v);
 
 // One launch of knn_tile_kernel: `nq` queries against all `n_total` rows of an index, stored in chunks of `chunk_rows` rows.  Workgroup
 // (x, y, z) takes queries [128 y, 128 y + 128) and rows [x * rows_per_range, (x + 1) * rows_per_range) of chunk z and leaves the range's

@@ -188,6 +188,10 @@ SYMBOLS = [
     ("scann_index_query_rows", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     ("scann_cells_capacity", C.c_int64, [C.c_int64, C.c_int32]),
     ("scann_cells_host", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_within", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_float, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_within_rows", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_within_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_float, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_within_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_float, C.c_int64, _P, _P, _P, _P]),
     ("scann_cell_bound", C.c_double, [C.c_float, C.c_float, C.c_float]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
@@ -511,6 +515,80 @@ def check_pca_args(mean, components, scale, dim=None):
         if a is not None and not np.isfinite(a).all():
             raise ValueError("%s holds a non-finite value" % name)
     return mean, components, scale
+
+
+# scann_index_within: the most entries one call returns (SCANN_WITHIN_MAX_CAP)
+WITHIN_MAX_CAP = 1 << 30
+
+
+def check_within_args(radius2, max_pairs, upper=0):
+    """(radius2, max_pairs, upper) of a radius search as the C calls take them: radius2 a number >= 0 (inf allowed, NaN not), max_pairs an
+    integer in 0 .. WITHIN_MAX_CAP, upper 0 or 1; ValueError otherwise."""
+    try:
+        r2 = float(radius2)
+    except (TypeError, ValueError):
+        raise ValueError("radius2 must be a number >= 0, got %r" % (radius2,)) from None
+    if isinstance(radius2, bool) or not r2 >= 0.0:
+        raise ValueError("radius2 must be a number >= 0, got %r" % (radius2,))
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 0 <= int(max_pairs) <= WITHIN_MAX_CAP:
+        raise ValueError("max_pairs must be an integer in 0 .. %d, got %r" % (WITHIN_MAX_CAP, max_pairs))
+    if isinstance(upper, bool):
+        upper = int(upper)
+    if not isinstance(upper, (int, np.integer)) or int(upper) not in (0, 1):
+        raise ValueError("upper must be 0 or 1, got %r" % (upper,))
+    return float(np.float32(r2)), int(max_pairs), int(upper)
+
+
+def _within_run(call, nq, max_pairs, count_only, who, extra=None):
+    """The size-then-fill protocol of a radius search: ``call(cap, counts, total, dist2, pos, ids, atoms)`` -- buffers as addresses, None
+    for the count-only call -- runs with a modest cap first (max(4096, 16 nq), never above ``max_pairs``) and once more with cap = total
+    if the hits did not fit.  ValueError that names both numbers if total > max_pairs.  Returns {"count" int64 [nq], "first" int64
+    [nq + 1], "total"} and, unless ``count_only``, "dist2", "position", "id", "atom" [total]; ``extra``: entries every call refills."""
+    counts, total = np.zeros(nq, np.int64), np.zeros(1, np.int64)
+    out = dict(extra or {})
+    cap = 0 if count_only else min(max(4096, 16 * nq), max_pairs)
+    while True:
+        ent = None if cap == 0 else (np.empty(cap, np.float32), np.empty(cap, np.int32), np.empty(cap, np.int64), np.empty(cap, np.int32))
+        call(cap, _ptr(counts), _ptr(total), *((None,) * 4 if ent is None else [_ptr(a) for a in ent]))
+        t = int(total[0])
+        if count_only or t <= cap:
+            break
+        if t > max_pairs:
+            raise ValueError("%s: %d rows lie within the radius, max_pairs is %d" % (who, t, max_pairs))
+        cap = t
+    out.update({"count": counts, "first": np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), "total": t})
+    if not count_only:
+        ent = ent or (np.empty(0, np.float32), np.empty(0, np.int32), np.empty(0, np.int64), np.empty(0, np.int32))
+        out.update({"dist2": ent[0][:t], "position": ent[1][:t], "id": ent[2][:t], "atom": ent[3][:t]})
+    return out
+
+
+def within_host(rows, q, radius2, row_ids=None, query_ids=None, query_pos=None, upper=0, max_pairs=1 << 24, count_only=False):
+    """The rows of ``rows`` [n, dim] within ``radius2`` (squared, fp32) of every query of ``q`` [nq, dim] as scann_index_within lists them
+    (scann_within_host, the definition in include/scann_hip.h), without a GPU: {"count", "first", "total", "dist2", "position"}.
+    ``query_pos`` [nq]: the position each query holds in ``rows`` -- it never qualifies, and ``upper`` = 1 keeps only greater ones."""
+    rows, q = np.ascontiguousarray(rows, dtype=np.float32), np.ascontiguousarray(q, dtype=np.float32)
+    if rows.ndim != 2 or q.ndim != 2 or rows.shape[1] != q.shape[1] or rows.shape[1] < 1 or q.shape[0] < 1:
+        raise ValueError("within_host: rows of shape %s, queries of shape %s" % (rows.shape, q.shape))
+    r2, max_pairs, upper = check_within_args(radius2, max_pairs, upper)
+    n, nq = rows.shape[0], q.shape[0]
+    rid = None if row_ids is None else np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+    qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+    qpos = None if query_pos is None else np.ascontiguousarray(query_pos, dtype=np.int32).reshape(-1)
+    if (rid is not None and rid.shape[0] != n) or (qid is not None and qid.shape[0] != nq) or (qpos is not None and qpos.shape[0] != nq):
+        raise ValueError("within_host: %d rows and %d queries need as many row ids, query ids and query positions" % (n, nq))
+    if upper and qpos is None:
+        raise ValueError("within_host: upper needs query_pos")
+    lib = load_library()
+
+    def call(cap, counts, total, dist2, pos, ids, atoms):
+        r = lib.scann_within_host(_ptr(rows), n, rows.shape[1], _ptr(rid), _ptr(q), nq, _ptr(qid), _ptr(qpos), upper, r2, cap, counts, total, dist2, pos)
+        if r != 0:
+            raise ValueError("within_host: invalid arguments (%d)" % r)
+
+    out = _within_run(call, nq, max_pairs, count_only, "within_host")
+    out.pop("id", None), out.pop("atom", None)
+    return out
 
 
 def _batch_out(packed, level):
@@ -1985,6 +2063,44 @@ class Engine:
         self._check(self.lib.scann_index_query_rows(self._h, ix._h, int(first), int(n), k, _ptr(out["dist2"]), _ptr(out["id"]), _ptr(out["atom"]),
                                                     _ptr(out["position"])))
         return out
+
+    def index_within(self, ix, q, radius2, query_ids=None, max_pairs=1 << 24, count_only=False):
+        """The rows of the index within ``radius2`` (squared, fp32) of every host query vector (scann_index_within), by the size-then-fill
+        protocol: {"count" int64 [nq], "first" int64 [nq + 1], "total"} and, unless ``count_only``, "dist2", "position", "id", "atom"
+        [total], query i's hits at first[i] .. first[i + 1] - 1 in the order (dist2, position).  ValueError if more than ``max_pairs``."""
+        r2, max_pairs, _ = check_within_args(radius2, max_pairs)
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise ValueError("index_within: queries of shape %s for an index of %d columns" % (q.shape, ix.dim))
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != q.shape[0]:
+            raise ValueError("index_within: %d queries need %d query ids" % (q.shape[0], q.shape[0]))
+        return _within_run(lambda cap, counts, total, d, p, i, a: self._check(self.lib.scann_index_within(
+            self._h, ix._h, _ptr(q), q.shape[0], _ptr(qid), r2, cap, counts, total, d, p, i, a)), q.shape[0], max_pairs, count_only, "index_within")
+
+    def index_within_rows(self, ix, first, n, radius2, upper=0, max_pairs=1 << 24, count_only=False):
+        """``index_within`` with rows first .. first + n - 1 of the index itself as the queries, read where they lie
+        (scann_index_within_rows): a query's own position never qualifies, ``upper`` = 1 keeps only greater positions."""
+        r2, max_pairs, upper = check_within_args(radius2, max_pairs, upper)
+        return _within_run(lambda cap, counts, total, d, p, i, a: self._check(self.lib.scann_index_within_rows(
+            self._h, ix._h, int(first), int(n), upper, r2, cap, counts, total, d, p, i, a)), max(int(n), 0), max_pairs, count_only, "index_within_rows")
+
+    def index_within_batch(self, ix, rb, level, radius2, query_ids=None, max_pairs=1 << 24, count_only=False):
+        """One forward of a resident batch and the rows of the index within ``radius2`` of each of its ``level`` rows
+        (scann_index_within_batch; raw y): ``index_within``'s dict plus "y" [n_struct] and "ga" [n_atom]."""
+        r2, max_pairs, _ = check_within_args(radius2, max_pairs)
+        p = rb.packed
+        qid = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int64).reshape(-1)
+        if qid is not None and qid.shape[0] != p.n_struct:
+            raise ValueError("index_within_batch: %d structures need %d query ids" % (p.n_struct, p.n_struct))
+        n, out = _batch_out(p, level)
+        return _within_run(lambda cap, counts, total, d, pos, i, a: self._check(self.lib.scann_index_within_batch(
+            self._h, ix._h, rb._h, int(level), _ptr(qid), r2, cap, _ptr(out["y"]), _ptr(out["ga"]), counts, total, d, pos, i, a)),
+            n, max_pairs, count_only, "index_within_batch", extra=out)
+
+    def within_host(self, rows, q, radius2, **kw):
+        """``_hip.within_host``: the twin of ``index_within``, no GPU work."""
+        return within_host(rows, q, radius2, **kw)
 
     def index_partition(self, ix, cells, max_iter=8):
         """Partition the index into ``cells`` cells (scann_index_partition; 0 drops the partition): searches then skip cells out of reach and

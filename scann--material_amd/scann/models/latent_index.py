@@ -75,6 +75,56 @@ def stop_dist2_of(stop_distance):
     return float(np.float32(stop) * np.float32(stop))
 
 
+def radius2_of(radius):
+    """``radius`` of a radius search as the squared fp32 threshold the C calls take, squared in fp32 the way ``stop_dist2_of`` does it
+    (inf stays inf); ValueError for a negative or NaN one or for no number."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError("radius must be a number >= 0, got %r" % (radius,)) from None
+    if isinstance(radius, bool) or not r >= 0.0:
+        raise ValueError("radius must be a number >= 0, got %r" % (radius,))
+    return float(np.float32(r) * np.float32(r))
+
+
+def within_result(r, count_only):
+    """What ``LatentIndex.within`` returns, from the engine's dict of a radius search"""
+    out = {"count": r["count"], "first": r["first"]}
+    if not count_only:
+        out.update({"position": r["position"], "id": r["id"], "atom": r["atom"], "dist2": r["dist2"],
+                    "distance": np.sqrt(r["dist2"])})  # (correctly rounded on the host, as nearest reports distances)
+    return out
+
+
+def duplicates_chunk_arg(chunk):
+    """``chunk`` of ``LatentIndex.duplicates``: the rows of one self-join call, an integer >= 1; ValueError otherwise"""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+        raise ValueError("chunk must be an integer >= 1, got %r" % (chunk,))
+    return int(chunk)
+
+
+def duplicate_groups(i, j, dist2, n_rows):
+    """``LatentIndex.duplicates``' dict from the pairs (i < j) of a self-join over ``n_rows`` rows.  The components come from a union-find
+    written with arrays: every pair hooks the greater of its two roots to the lesser, then every row's pointer is shortened to its
+    root, until no pair joins two roots; a root is therefore always its component's least position."""
+    i, j = np.asarray(i, np.int64), np.asarray(j, np.int64)
+    group = np.arange(n_rows, dtype=np.int64)
+    while len(i):
+        gi, gj = group[i], group[j]
+        if np.array_equal(gi, gj):
+            break
+        np.minimum.at(group, np.maximum(gi, gj), np.minimum(gi, gj))
+        while True:
+            up = group[group]
+            if np.array_equal(up, group):
+                break
+            group = up
+    roots, sizes = np.unique(group, return_counts=True)
+    return {"pairs": np.stack([i, j], axis=1).astype(np.int32).reshape(-1, 2), "distance": np.sqrt(np.asarray(dist2, np.float32)),
+            "group": group.astype(np.int32), "n_groups": int(len(roots)), "sizes": sizes.astype(np.int64),
+            "keep": group == np.arange(n_rows)}
+
+
 def explained_ratio(w):
     """The share of every eigenvalue in the total variance, fp64: negative eigenvalues (rounding noise of a rank-deficient covariance)
     count as 0, and the divisor is the fp64 sum of the others times 1 + (d + 2) * 2^-52 = 1 + (2 d + 4) * 2^-53.  The d - 1 adds of that
@@ -248,6 +298,50 @@ class LatentIndex:
         st = self.model.engine.index_search_stats(self._ix)
         st["visited_share"] = st["visited"] / st["total"] if st["total"] else 1.0
         return st
+
+    def within(self, rows, radius, exclude_ids=None, max_pairs=1 << 24, count_only=False):
+        """Which rows of this index lie within Euclidean distance ``radius`` of every host query vector of ``rows`` [nq, dim]: the exact
+        radius search on the GPU (scann_index_within).  Where ``nearest`` always answers k rows, this answers as many as there are,
+        possibly none: the ball count of a prediction, or whether a test structure has a training twin.  ``radius`` is squared in fp32
+        and compared with the fp32 distance chain, inclusively; ``np.inf`` is allowed.  ``exclude_ids`` [nq]: rows whose id equals the
+        query's are skipped.  Returns {"count" int64 [nq], "first" int64 [nq + 1], "position" int32, "id" int64, "atom" int32, "dist2",
+        "distance" fp32 [total]}: query i's hits are entries first[i] .. first[i + 1] - 1, in the order (distance, position), so the
+        result depends on the queries, the index and the radius only, in every byte.  ``count_only``: counts and "first" alone, nothing
+        else is allocated.  More than ``max_pairs`` hits in all, or bad arguments, raise ValueError."""
+        r2 = radius2_of(radius)
+        _hip.check_within_args(r2, max_pairs)
+        r = self.model.engine.index_within(self._ix, rows, r2, query_ids=exclude_ids, max_pairs=max_pairs, count_only=count_only)
+        return within_result(r, count_only)
+
+    def duplicates(self, radius, max_pairs=1 << 24, chunk=65536, route="device"):
+        """The near-duplicate groups of this index: every unordered pair of rows within Euclidean distance ``radius`` (the self-join of
+        scann_index_within_rows with ``upper`` = 1, ``chunk`` rows at a time, each pair listed once) and the connected components of
+        those pairs, by a union-find on the host.  Returns {"pairs" int32 [P, 2] (i < j, ordered by i, then distance, then j),
+        "distance" fp32 [P], "group" int32 [N] -- the least position of the row's component; a row without a partner is its own group --,
+        "n_groups", "sizes" int64 [n_groups] (by ascending group), "keep" bool [N] -- true at each group's least position: the dedup
+        mask}.  ``route`` "host" runs the host twin on the rows read back: the same bytes.  More than ``max_pairs`` pairs, or bad
+        arguments, raise ValueError."""
+        r2 = radius2_of(radius)
+        _, max_pairs, _ = _hip.check_within_args(r2, max_pairs)
+        chunk = duplicates_chunk_arg(chunk)
+        if route not in ("device", "host"):
+            raise ValueError('route must be "device" or "host", got %r' % (route,))
+        eng, N = self.model.engine, len(self)
+        host_rows = self.rows()[0] if route == "host" and N else None
+        pi, pj, pd, found = [], [], [], 0
+        for first in range(0, N, chunk):
+            n = min(chunk, N - first)
+            if route == "host":
+                r = _hip.within_host(host_rows, host_rows[first:first + n], r2, query_pos=np.arange(first, first + n, dtype=np.int32), upper=1,
+                                     max_pairs=max_pairs - found)
+            else:
+                r = eng.index_within_rows(self._ix, first, n, r2, upper=1, max_pairs=max_pairs - found)
+            found += r["total"]
+            pi.append(np.repeat(np.arange(first, first + n, dtype=np.int32), r["count"]))
+            pj.append(r["position"])
+            pd.append(r["dist2"])
+        return duplicate_groups(np.concatenate(pi) if pi else np.zeros(0, np.int32), np.concatenate(pj) if pj else np.zeros(0, np.int32),
+                                np.concatenate(pd) if pd else np.zeros(0, np.float32), N)
 
     def save(self, path):
         """An ``.npz`` of rows, ids, atoms, level and dim (written to exactly ``path``), and of the partition's arguments if the index

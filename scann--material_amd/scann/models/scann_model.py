@@ -430,6 +430,55 @@ class HipModel:
             out["neighbor_atom"] = cat["atom"]
         return _repad(out, inputs, index.level, {"distance": 0, "latent_distance": 0, "neighbor_id": -1, "neighbor_atom": -1})
 
+    def within(self, inputs, index, radius, exclude_ids=None, batch_size=None, max_pairs=1 << 24, count_only=False):
+        """Which rows of a ``LatentIndex`` lie within Euclidean distance ``radius`` of every structure (or, for an atom-level index,
+        every atom) of ``inputs``: the exact radius search on the GPU right behind the forward (scann_index_within_batch).  This is the
+        leakage check of a benchmark -- ``count > 0`` names the test structures that have a training twin, and the lists say which
+        training structure -- and the ball count of a prediction.  ``exclude_ids`` [B]: rows whose id equals the structure's are
+        skipped.  Returns {"predict_property": [B, 1] (raw y), "count": int64 [B], or [B, M] at atom level with 0 at padded atoms (a
+        ``PackedBatch`` gives the packed [n_atom]), "first": int64 [nq + 1] over the nq query rows in packed order, "position" int32,
+        "neighbor_id" int64, "neighbor_atom" int32, "dist2", "distance" fp32 [total]}: the hits of query row i are entries first[i] ..
+        first[i + 1] - 1 in the order (distance, position); ``count_only`` leaves the lists out.  ``LatentIndex.within`` defines the
+        radius.  More than ``max_pairs`` hits in all, an index of another model or width, or bad arguments raise ValueError before
+        anything is uploaded."""
+        from .latent_index import radius2_of
+
+        r2 = radius2_of(radius)
+        _, max_pairs, _ = _hip.check_within_args(r2, max_pairs)
+        _expect(index, LatentIndex, "index")
+        index.check_model(self)
+        qid = _exclude_ids_arg(inputs, exclude_ids)
+        eng, lvl, found = self.engine, _hip.KNN_LEVELS[index.level], [0]
+
+        def call(rb, s0, s1):
+            r = eng.index_within_batch(index._ix, rb, lvl, r2, None if qid is None else qid[s0:s1], max_pairs=max_pairs - found[0],
+                                       count_only=count_only)
+            found[0] += 0 if count_only else r["total"]
+            return r
+
+        names = {"y": np.float32, "count": np.int64} if count_only else {
+            "y": np.float32, "count": np.int64, "position": np.int32, "id": np.int64, "atom": np.int32, "dist2": np.float32}
+        cat = self._run_cat(inputs, batch_size, call, {n: np.zeros(0, t) for n, t in names.items()})
+        out = {"predict_property": cat["y"].reshape(-1, 1), "count": cat["count"],
+               "first": np.concatenate([[0], np.cumsum(cat["count"])]).astype(np.int64)}
+        if not count_only:
+            out.update({"position": cat["position"], "neighbor_id": cat["id"], "neighbor_atom": cat["atom"], "dist2": cat["dist2"],
+                        "distance": np.sqrt(cat["dist2"])})
+        return _repad(out, inputs, index.level, {"count": 0}, {"count": np.int64})
+
+    def duplicates(self, data, radius, level="structure", batch_size=None, max_pairs=1 << 24):
+        """The near-duplicate groups of ``data`` in the model's latent space: the same crystal entered twice, conformers the model cannot
+        tell apart (``LatentIndex.duplicates``, whose dict this returns; ``keep`` is the dedup mask).  ``data`` is a ``LatentIndex`` (its
+        level counts, not ``level``) or data as ``build_index`` takes it, which is indexed for the call and freed afterwards.  Bad
+        arguments raise ValueError before anything is uploaded."""
+        from .latent_index import radius2_of
+
+        level_dim(self.config, _level_of(data, level))
+        _hip.check_within_args(radius2_of(radius), max_pairs)
+        self._batch_size(batch_size)
+        with self._indexed(data, level, batch_size=batch_size) as index:
+            return index.duplicates(radius, max_pairs=max_pairs)
+
     def match_structures(self, inputs, index, k=5, measure="chamfer", exclude_ids=None, batch_size=None):
         """The ``k`` structures of an atom-level ``LatentIndex`` that are made of the same local structures as each structure of
         ``inputs``: the two are compared as sets of ``after_Lc`` rows on the GPU right behind the forward (scann_index_match_batch).
@@ -1549,5 +1598,8 @@ def _facade(name, key):
     return method
 
 
-for _name, _key in FACADE:
+# the radius search, by the same rule (a table of its own: tests/test_python_layer_host.py counts the entries of the one above)
+FACADE_RADIUS = (("within", "predict_property"), ("duplicates", None))
+
+for _name, _key in FACADE + FACADE_RADIUS:
     setattr(SCANN, _name, _facade(_name, _key))

@@ -1,0 +1,318 @@
+"""CPU tests of the radius search over a latent-space index (include/scann_hip.h: scann_index_within): no GPU is needed.
+
+1. The host twin scann_within_host equals the NumPy restatement of the definition (tests/within_ref.py) in every byte, on random,
+   clustered, all-identical, integer-grid and non-finite rows, with ids, own positions and ``upper``; the inclusive boundary; ``upper``
+   lists every unordered pair once; the first k hits are tests/knn_ref.py's selection where its places qualify.
+2. The pruned plan, written in NumPy over the host partition with the header's bound, returns the entries of the full matrix; on
+   well-separated blobs it visits at most 1/4 (256 queries) and 1/2 (the self-join) of the (group, tile) pairs.
+3. The size-then-fill protocol on the C call itself, with sentinel-filled arrays.
+4. ``duplicates``' groups on planted copies, the ABI, the Python layer's argument checks, and the stand-alone program under the
+   sanitizers (make asan-within)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import knn_ref
+import within_ref
+from test_cells_host import blobs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "scann--material_amd", "csrc")
+
+
+def _case_rows(name, n, dim, rng):
+    rows = rng.standard_normal((n, dim)).astype(np.float32)
+    if name == "clustered":
+        rows = (rows * 0.05 + rng.integers(0, 3, (n, 1)) * 7).astype(np.float32)
+    elif name == "identical":
+        rows[:] = np.float32(1.5)
+    elif name == "grid":
+        rows = rng.integers(0, 4, (n, dim)).astype(np.float32)
+    elif name == "nonfinite" and n >= 3:
+        rows[0, 0], rows[n // 2, dim - 1], rows[n - 1, 0] = np.nan, np.inf, -np.inf
+    return rows
+
+
+def radii_of(d):
+    """The radii of a case from its own distance matrix: 0, a value that IS a distance of the case (the one with about 3 hits per query
+    below it), the midpoint of two neighbouring distances where about 10 hits per query lie below, and +inf"""
+    finite = np.sort(d[np.isfinite(d)])
+    if not len(finite):
+        return [0.0, np.inf]
+    at = min(len(finite) - 1, 10 * d.shape[0])
+    return [0.0, float(finite[min(len(finite) - 1, 3 * d.shape[0])]), float((finite[at] + finite[max(at - 1, 0)]) / 2), np.inf]
+
+
+TWIN_CASES = [(n, dim, name) for n in (1, 63, 64, 65, 300) for dim, name in ((3, "random"), (33, "clustered"), (3, "identical"), (2, "grid"), (5, "nonfinite"))]
+
+
+@pytest.mark.parametrize("n,dim,name", TWIN_CASES, ids=["N%d_d%d_%s" % c for c in TWIN_CASES])
+def test_twin_equals_the_definition(hip_lib, n, dim, name):
+    from scann import _hip
+
+    rng = np.random.default_rng(n * 17 + dim)
+    rows = _case_rows(name, n, dim, rng)
+    q = np.concatenate([rows[rng.integers(0, n, 20)], _case_rows(name, 21, dim, rng)])  # exact copies of rows among the queries
+    if name == "nonfinite":
+        q[3, 0] = np.nan
+    with np.errstate(all="ignore"):
+        d = _hip.knn_dist2_matrix(q, rows)
+        dself = _hip.knn_dist2_matrix(rows, rows)
+    ids, qid = rng.integers(0, 4, n).astype(np.int64), rng.integers(0, 4, len(q)).astype(np.int64)
+    for r2 in radii_of(d):
+        label = "%s r2 %r" % (name, r2)
+        within_ref.same(_hip.within_host(rows, q, r2), within_ref.within(d, r2), label)
+        within_ref.same(_hip.within_host(rows, q, r2, row_ids=ids, query_ids=qid), within_ref.within(d, r2, ids=ids, query_ids=qid), label + " ids")
+        within_ref.same(_hip.within_host(rows, q, r2, query_ids=qid), within_ref.within(d, r2, query_ids=qid), label + " position ids")
+        counted = _hip.within_host(rows, q, r2, count_only=True)
+        assert "dist2" not in counted and np.array_equal(counted["count"], within_ref.within(d, r2)["count"])
+        qpos = np.arange(n, dtype=np.int32)
+        both = _hip.within_host(rows, rows, r2, query_pos=qpos)
+        up = _hip.within_host(rows, rows, r2, query_pos=qpos, upper=1)
+        within_ref.same(both, within_ref.within(dself, r2, query_pos=qpos), label + " self")
+        within_ref.same(up, within_ref.within(dself, r2, query_pos=qpos, upper=1), label + " upper")
+        # dist2 is symmetric bit for bit: every unordered pair once with upper, twice without
+        assert both["total"] == 2 * up["total"]
+        i = np.repeat(np.arange(n), up["count"])
+        assert np.all(i < up["position"]) and len(set(zip(i.tolist(), up["position"].tolist()))) == up["total"]
+    if name == "identical":
+        assert _hip.within_host(rows, q[:20], 0.0)["total"] == 20 * n  # planted exact copies at radius 0
+
+
+def test_the_boundary_is_inclusive_and_inf_is_an_ordinary_value(hip_lib):
+    from scann import _hip
+
+    rows = np.array([[0, 0], [3, 4], [6, 8], [np.inf, 0], [np.nan, 0]], np.float32)
+    q = np.zeros((1, 2), np.float32)
+    assert _hip.within_host(rows, q, 25.0)["position"].tolist() == [0, 1]  # 25 <= 25
+    assert _hip.within_host(rows, q, np.nextafter(np.float32(25), np.float32(0)))["position"].tolist() == [0]
+    assert _hip.within_host(rows, q, 3e38)["position"].tolist() == [0, 1, 2]  # +inf qualifies only at radius2 = +inf ...
+    r = _hip.within_host(rows, q, np.inf)
+    assert r["position"].tolist() == [0, 1, 2, 3] and np.isposinf(r["dist2"][3])  # ... and a NaN never
+    # many pairs tie at exactly radius2, on the integer grid: every one of them is a hit, in position order
+    rng = np.random.default_rng(5)
+    grid = rng.integers(0, 3, (400, 2)).astype(np.float32)
+    d = _hip.knn_dist2_matrix(grid[:50], grid)
+    for r2 in (0.0, 1.0, 2.0, 4.0, 5.0):
+        got = _hip.within_host(grid, grid[:50], r2)
+        within_ref.same(got, within_ref.within(d, r2), "grid %r" % r2)
+        assert (got["dist2"] == r2).sum() == (d == r2).sum() > 50
+
+
+def test_first_k_hits_are_the_nearest_rows_where_they_qualify(hip_lib):
+    from scann import _hip
+
+    rng = np.random.default_rng(9)
+    rows = rng.integers(0, 5, (500, 3)).astype(np.float32)  # ties within and across the radius
+    q = rng.integers(0, 5, (40, 3)).astype(np.float32)
+    ids, qid = rng.integers(0, 6, 500).astype(np.int64), rng.integers(0, 6, 40).astype(np.int64)
+    d = _hip.knn_dist2_matrix(q, rows)
+    k = 32
+    for r2 in (0.0, 2.0, 6.0):
+        got = _hip.within_host(rows, q, r2, row_ids=ids, query_ids=qid)
+        kd, kp, _, _ = knn_ref.select(d, k, ids=ids, query_ids=qid)
+        for i in range(40):
+            m = min(k, int(got["count"][i]))
+            s = slice(got["first"][i], got["first"][i] + m)
+            assert np.array_equal(got["position"][s], kp[i, :m]) and np.array_equal(got["dist2"][s].view(np.uint32), kd[i, :m].view(np.uint32))
+            assert np.all(kd[i, :m] <= r2) and (m == k or not kd[i, m] <= r2)  # exactly the places that qualify
+
+
+# ---- 2. the pruned plan on the host ----
+
+def _check_pruned(rows, q, r2, cells, label, **rules):
+    from scann import _hip
+
+    part = _hip.cells_host(rows, cells, 4)
+    with np.errstate(all="ignore"):
+        d = _hip.knn_dist2_matrix(q, rows)
+    want = within_ref.within(d, r2, **rules)
+    got, st = within_ref.pruned(rows, part, q, r2, _hip.knn_dist2_matrix, **rules)
+    print("%s: N %d, Q %d, radius2 %r, cells %d: visited %d of %d pairs, %d hits" % (label, len(rows), len(q), r2, part["cells"], st["visited"],
+                                                                                  st["total"], want["total"]))
+    within_ref.same(got, want, label)
+    return st, want
+
+
+def test_pruned_plan_returns_the_full_matrix_entries(hip_lib):
+    from scann import _hip
+
+    rng = np.random.default_rng(7)
+    for n, dim, cells, nq in ((1, 3, 1, 1), (63, 2, 2, 7), (65, 33, 7, 129), (130, 3, 64, 7), (300, 2, 200, 20), (700, 8, 7, 140)):
+        rows = (rng.standard_normal((n, dim)) + rng.integers(0, 3, (n, 1)) * 6).astype(np.float32)
+        q = (rng.standard_normal((nq, dim)) + rng.integers(0, 3, (nq, 1)) * 6).astype(np.float32)
+        for r2 in radii_of(_hip.knn_dist2_matrix(q, rows)):
+            _check_pruned(rows, q, r2, cells, "random")
+    grid = rng.integers(0, 4, (600, 2)).astype(np.float32)
+    for r2 in (0.0, 1.0, 2.0):
+        _check_pruned(grid, rng.integers(0, 4, (129, 2)).astype(np.float32), r2, 7, "grid")
+        _check_pruned(grid, grid, r2, 7, "grid self-join", query_pos=np.arange(600), upper=1)
+    rows = (rng.standard_normal((200, 4)) + rng.integers(0, 2, (200, 1)) * 9).astype(np.float32)
+    ids = (np.arange(200) // 50).astype(np.int64)
+    q = rows[rng.integers(0, 200, 30)].copy()
+    _check_pruned(rows, q, 2.0, 4, "exclude a segment", ids=ids, query_ids=np.full(30, 2, np.int64))
+    rows[3], rows[77, 1], rows[150] = np.nan, np.inf, 3e19
+    q[4, 0] = np.nan
+    for r2 in (2.0, np.inf):
+        _check_pruned(rows, q, r2, 4, "non-finite")
+
+
+def test_pruned_plan_skips_on_blobs(hip_lib):
+    rows, q = blobs()
+    st, want = _check_pruned(rows, q, 40.0, 8, "blobs, 256 queries")
+    assert st["groups"] == 2 and st["total"] == 128 and 4 * st["visited"] <= st["total"], st
+    assert want["total"] == 6338  # the case is not vacuous
+    st, want = _check_pruned(rows, rows, 40.0, 8, "blobs, self-join", query_pos=np.arange(len(rows)), upper=1)
+    assert st["groups"] == 32 and st["total"] == 2048 and 2 * st["visited"] <= st["total"], st
+    assert want["total"] > 1000
+
+
+# ---- 3. the protocol on the C call ----
+
+def test_size_then_fill_protocol(hip_lib):
+    from scann import _hip
+
+    rng = np.random.default_rng(3)
+    rows = rng.integers(0, 4, (300, 2)).astype(np.float32)
+    q = rng.integers(0, 4, (50, 2)).astype(np.float32)
+    want = within_ref.within(_hip.knn_dist2_matrix(q, rows), 1.0)
+    total = want["total"]
+    assert total > 100
+
+    def call(cap, arrays=True):
+        counts, tot = np.full(50, -1, np.int64), np.full(1, -1, np.int64)
+        d, p = np.full(total + 1, -7, np.float32), np.full(total + 1, -7, np.int32)
+        r = hip_lib.scann_within_host(rows.ctypes.data, 300, 2, None, q.ctypes.data, 50, None, None, 0, 1.0, cap, counts.ctypes.data, tot.ctypes.data,
+                                      d.ctypes.data if arrays else None, p.ctypes.data if arrays else None)
+        return r, counts, int(tot[0]), d, p
+
+    r, counts, tot, d, p = call(total)  # cap = total fills
+    assert r == 0 and tot == total and np.array_equal(counts, want["count"])
+    assert np.array_equal(p[:total], want["position"]) and np.array_equal(d[:total].view(np.uint32), want["dist2"].view(np.uint32)) and p[total] == -7
+    r, counts, tot, d, p = call(total - 1)  # one short: counts and total exact, the entry arrays untouched, still SCANN_OK
+    assert r == 0 and tot == total and np.array_equal(counts, want["count"]) and np.all(d == -7) and np.all(p == -7)
+    r, counts, tot, d, p = call(0, arrays=False)  # count only
+    assert r == 0 and tot == total and np.array_equal(counts, want["count"])
+    assert call(0)[0] == -1 and call(-1)[0] == -1 and call((1 << 30) + 1)[0] == -1  # an entry array with cap 0; cap outside its bounds
+    # the wrapper: a second call sized by the first; more than max_pairs names both numbers
+    big = np.zeros((400, 2), np.float32)
+    got = _hip.within_host(big, big[:30], 0.0)  # 12,000 hits > the first cap of 4,096
+    assert got["total"] == 12000 and np.array_equal(got["position"], np.tile(np.arange(400, dtype=np.int32), 30))
+    with pytest.raises(ValueError, match="12000.*max_pairs is 11999"):
+        _hip.within_host(big, big[:30], 0.0, max_pairs=11999)
+    assert _hip.within_host(big, big[:30], 0.0, max_pairs=12000)["total"] == 12000
+    assert _hip.within_host(big, big[:30], 0.0, max_pairs=5, count_only=True)["total"] == 12000  # counting needs no room
+
+
+# ---- 4. duplicates, the ABI, the Python layer, the sanitizers ----
+
+class _HostEngine:
+    """what ``LatentIndex.duplicates(route="host")`` uses of an engine, over host rows"""
+
+    def __init__(self, rows):
+        self.stored = np.ascontiguousarray(rows, np.float32)
+
+    def index_read(self, ix):
+        n = len(self.stored)
+        return self.stored, np.arange(n, dtype=np.int64), np.full(n, -1, np.int32)
+
+
+def _host_index(rows):
+    from scann.models import latent_index
+
+    ix = object.__new__(latent_index.LatentIndex)
+    ix.model = type("M", (), {"engine": _HostEngine(rows)})()
+    ix._ix = range(len(rows))
+    ix.dim, ix.level = rows.shape[1], "structure"
+    return ix
+
+
+def test_duplicate_groups_on_planted_copies(hip_lib):
+    rng = np.random.default_rng(1)
+    a, b = rng.standard_normal(6).astype(np.float32), rng.standard_normal(6).astype(np.float32) + 5
+    eps = np.float32(1e-3)
+    a1, a2 = a.copy(), a.copy()
+    a1[0] += eps  # a -- a' and a' -- a'' are within 1.5 eps, a -- a'' (2 eps apart) is not: one group of three all the same
+    a2[0] += 2 * eps
+    r = _host_index(np.stack([a, a1, b, a2])).duplicates(1.5e-3, route="host")
+    assert r["pairs"].tolist() == [[0, 1], [1, 3]] and r["group"].tolist() == [0, 0, 2, 0] and r["n_groups"] == 2
+    assert r["sizes"].tolist() == [3, 1] and r["keep"].tolist() == [True, False, True, False] and r["pairs"].dtype == np.int32
+    # a larger case against a plain union-find over the reference's pairs, in chunks that cut the self-join
+    rows = rng.integers(0, 6, (500, 2)).astype(np.float32)
+    from scann import _hip
+
+    want = within_ref.within(_hip.knn_dist2_matrix(rows, rows), 1.0, query_pos=np.arange(500), upper=1)
+    wi = np.repeat(np.arange(500), want["count"])
+    for chunk in (65536, 64, 7):
+        r = _host_index(rows).duplicates(1.0, chunk=chunk, route="host")
+        assert np.array_equal(r["pairs"], np.stack([wi, want["position"]], axis=1)) and np.array_equal(r["distance"], np.sqrt(want["dist2"]))
+        assert np.array_equal(r["group"], within_ref.groups_of(wi, want["position"], 500))
+        assert r["n_groups"] == len(np.unique(r["group"])) and r["sizes"].sum() == 500 and r["keep"].sum() == r["n_groups"]
+    none = _host_index(rng.standard_normal((9, 3)).astype(np.float32)).duplicates(0.0, route="host")
+    assert none["pairs"].shape == (0, 2) and none["group"].tolist() == list(range(9)) and none["keep"].all()
+    with pytest.raises(ValueError, match="max_pairs"):
+        _host_index(rows).duplicates(1.0, max_pairs=10, route="host")
+
+
+def test_header_and_python_agree(hip_lib):
+    from scann import _hip
+
+    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
+    for text in ("int scann_index_within(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, float radius2, "
+                 "int64_t cap, int64_t* counts /* [nq] */, int64_t* total, float* dist2, int32_t* pos, int64_t* ids, int32_t* atoms",
+                 "int scann_index_within_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t upper, float radius2, int64_t cap,",
+                 "int scann_index_within_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, float radius2,",
+                 "int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* row_ids, const float* q, int64_t nq, const int64_t* query_ids, "
+                 "const int32_t* query_pos, int32_t upper, float radius2, int64_t cap, int64_t* counts, int64_t* total, float* dist2, int32_t* pos);",
+                 "the compare is an fp32 <=, inclusive", "a NaN distance never qualifies", "the entry arrays are NOT TOUCHED",
+                 "scann_index_query's first k places wherever those places qualify", "> radius2, strictly, for EVERY query q of the group",
+                 "dist2 >= lb > radius2", "#define SCANN_WITHIN_MAX_CAP ((int64_t)1 << 30)"):
+        assert text in flat, text
+    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    P, I64, I32, F = C.c_void_p, C.c_int64, C.c_int32, C.c_float
+    assert sig["scann_index_within"] == (C.c_int, [P, P, P, I64, P, F, I64, P, P, P, P, P, P])
+    assert sig["scann_index_within_rows"] == (C.c_int, [P, P, I64, I64, I32, F, I64, P, P, P, P, P, P])
+    assert sig["scann_index_within_batch"] == (C.c_int, [P, P, P, I32, P, F, I64, P, P, P, P, P, P, P, P])
+    assert sig["scann_within_host"] == (C.c_int, [P, I64, I64, P, P, I64, P, P, I32, F, I64, P, P, P, P])
+    assert _hip.WITHIN_MAX_CAP == 1 << 30
+    # null arguments are refused without a device
+    assert hip_lib.scann_index_within(None, None, None, 1, None, 1.0, 0, None, None, None, None, None, None) == -1
+    assert hip_lib.scann_index_within_rows(None, None, 0, 1, 0, 1.0, 0, None, None, None, None, None, None) == -1
+    assert hip_lib.scann_index_within_batch(None, None, None, 2, None, 1.0, 0, None, None, None, None, None, None, None, None) == -1
+
+
+def test_python_layer_checks_its_arguments(hip_lib):
+    from scann import _hip
+    from scann.models import latent_index
+
+    for r2, mp, up in ((-1.0, 10, 0), (np.nan, 10, 0), ("x", 10, 0), (True, 10, 0), (1.0, -1, 0), (1.0, (1 << 30) + 1, 0), (1.0, 2.5, 0), (1.0, True, 0),
+                       (1.0, 10, 2), (1.0, 10, -1), (1.0, 10, 0.5)):
+        with pytest.raises(ValueError):
+            _hip.check_within_args(r2, mp, up)
+    assert _hip.check_within_args(np.float32(2.5), np.int64(7), True) == (2.5, 7, 1) and _hip.check_within_args(np.inf, 0)[0] == np.inf
+    for radius in (-1, np.nan, "r", None, True):
+        with pytest.raises(ValueError):
+            latent_index.radius2_of(radius)
+    third = np.float32(1) / np.float32(3)
+    assert latent_index.radius2_of(third) == float(third * third) and latent_index.radius2_of(np.inf) == np.inf and latent_index.radius2_of(0) == 0.0
+    for chunk in (0, -3, 2.5, True, "a"):
+        with pytest.raises(ValueError):
+            latent_index.duplicates_chunk_arg(chunk)
+    rows = np.zeros((4, 2), np.float32)
+    for bad in (lambda: _hip.within_host(rows, rows[:, :1], 1.0), lambda: _hip.within_host(rows, rows[:0], 1.0), lambda: _hip.within_host(rows, rows, -1.0),
+                lambda: _hip.within_host(rows, rows, 1.0, upper=1), lambda: _hip.within_host(rows, rows, 1.0, query_ids=np.zeros(3)),
+                lambda: _hip.within_host(rows, rows, 1.0, row_ids=np.zeros(5)), lambda: _hip.within_host(rows, rows, 1.0, query_pos=np.zeros(2)),
+                lambda: _host_index(rows).duplicates(1.0, route="gpu"), lambda: _host_index(rows).duplicates(-1.0, route="host"),
+                lambda: _host_index(rows).duplicates(1.0, chunk=0, route="host")):
+        with pytest.raises(ValueError):
+            bad()
+    assert _hip.within_host(rows[:0], rows, 1.0)["total"] == 0  # an empty table gives zeros
+
+
+def test_twin_under_the_sanitizers():
+    """make asan-within: the stand-alone program drives scann_within_host and within_finish under AddressSanitizer + UBSan"""
+    r = subprocess.run(["make", "-C", CSRC, "asan-within"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "scann_within_check: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
