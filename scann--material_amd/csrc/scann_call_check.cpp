@@ -2,12 +2,10 @@
 // AddressSanitizer + UBSan (host code only, no device is touched) and runs it.  The device-block cache is stubbed with host malloc and a
 // count of live blocks, so the program sees every offset, every pointer alloc() fills in, and how often a block is freed.  No HIP call is
 // made: of the chunk table it checks the host copy (host_table), which is what the workspace has to keep alive.
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 
-#include "scann_call.h"
+#define SCANN_CHECK_OWN_CACHE
+#include "scann_check.h"
 
 namespace {
 int g_live = 0, g_allocs = 0, g_frees = 0;
@@ -29,16 +27,11 @@ void cached_free(void* p) {
   std::free(p);
   --g_live, ++g_frees;
 }
-int fail(scann_handle*, int code, const std::string&) { return code; }
 }  // namespace scann
 
 namespace {
 
-int bad = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) ++bad, std::printf("line %d: %s\n", __LINE__, #cond); \
-  } while (0)
+#define CHECK(cond) EXPECT(cond)
 
 struct Args {
   const float* const* rows;
@@ -134,6 +127,5 @@ int main() {
     ws.release();  // (a table freed before this, or not at all, is a sanitizer report)
   }
   CHECK(g_live == 0 && g_allocs == g_frees);
-  std::printf(bad ? "scann_call_check: %d FAILED\n" : "scann_call_check: ok\n", bad);
-  return bad ? 1 : 0;
+  return finish("scann_call_check");
 }

@@ -10,6 +10,7 @@
 
 #include "scann_call.h"
 #include "scann_runtime.h"
+#include "scann_search.h"
 
 using namespace scann;
 
@@ -21,12 +22,7 @@ void cells_layout(const int32_t* labels, const float* dist2, int64_t n, int32_t 
   std::vector<int32_t> order((size_t)n);
   std::iota(order.begin(), order.end(), 0);
   auto cell_of = [&](int32_t p) { return labels[p] < 0 ? C : labels[p]; };
-  std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-    const int32_t cx = cell_of(x), cy = cell_of(y);
-    if (cx != cy) return cx < cy;
-    if (cx < C && dist2[x] != dist2[y]) return dist2[x] < dist2[y];
-    return x < y;
-  });
+  sort_by_cell(order.data(), order.data() + n, C, cell_of, dist2);
   out.C = C;
   out.perm.clear(); out.lo.clear(); out.hi.clear();
   out.first_tile.assign((size_t)C + 2, 0);
@@ -120,12 +116,8 @@ int scann::cells_search(scann_handle* h, scann_index* ix, const float* dq, const
   const int64_t g = std::min<int64_t>(nq, 1024);
   const int G = (int)((g + TILE_TQ - 1) / TILE_TQ);
   const int W = std::max(1, std::min(CELL_LISTS, T));
-  int64_t full_tiles = 0;  // tiles a full search of the index's own chunks visits
-  for (int64_t r = 0; r < ix->n; r += ix->chunk_rows) full_tiles += (std::min<int64_t>(ix->chunk_rows, ix->n - r) + TILE_TR - 1) / TILE_TR;
-  CellSearchArgs a{};
-  a.rows = P.d_rows; a.ids = P.d_ids; a.pos = P.d_pos; a.centres = P.d_centres; a.tile_cell = P.d_tile_cell; a.first_tile = P.d_first_tile;
-  a.rlo = P.d_rlo; a.rhi = P.d_rhi; a.full = P.d_full;
-  a.C = C; a.n_tile = T; a.n_cell_tile = P.n_cell_tile; a.chunk_rows = P.chunk_rows; a.stride = P.stride;
+  const int64_t full_tiles = SearchStats::full_tiles(ix);
+  CellSearchArgs a = cells_args(P);
   a.k = k; a.n_list = W;
   CallWs ws;
   float *out_d, *tau_d;
@@ -136,30 +128,15 @@ int scann::cells_search(scann_handle* h, scann_index* ix, const float* dq, const
   ws.take(a.part_d, (size_t)g * 2 * W * k); ws.take(a.part_p, (size_t)g * 2 * W * k);
   HIPCHK(h, ws.alloc());
   a.qperm = d_qperm; a.tau = tau_d;
-  std::vector<int32_t> pos_h(dev_d ? 0 : (size_t)g * k), key_c((size_t)g), qperm((size_t)G * TILE_TQ), count((size_t)2 * G);
-  std::vector<float> key_d((size_t)g);
-  int64_t st[4] = {0, 0, 0, 0};
+  std::vector<int32_t> pos_h(dev_d ? 0 : (size_t)g * k), count((size_t)2 * G);
+  PassOrder order;
+  SearchStats st;
   const double share = fallback_share(k, T);
   hipError_t e = hipSuccess;
   for (int64_t q0 = 0; q0 < nq && e == hipSuccess; q0 += g) {
     const int m = (int)std::min<int64_t>(g, nq - q0), n_group = (m + TILE_TQ - 1) / TILE_TQ;
     a.q = dq + (size_t)q0 * P.stride; a.qid = dqid ? dqid + q0 : nullptr; a.nq = m; a.n_group = n_group;
-    e = launch_cells_centre(a, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(key_c.data(), a.key_cell, (size_t)m * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(key_d.data(), a.key_d, (size_t)m * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) break;
-    // the queries by (place of the nearest cell on the walk through the centres, distance to its centre, place): a group of 128 then
-    // looks at the same cells
-    std::fill(qperm.begin(), qperm.end(), -1);
-    std::iota(qperm.begin(), qperm.begin() + m, 0);
-    std::sort(qperm.begin(), qperm.begin() + m, [&](int32_t x, int32_t y) {
-      const int32_t cx = key_c[(size_t)x] < 0 ? C : P.cell_rank[(size_t)key_c[(size_t)x]], cy = key_c[(size_t)y] < 0 ? C : P.cell_rank[(size_t)key_c[(size_t)y]];
-      if (cx != cy) return cx < cy;
-      if (cx < C && key_d[(size_t)x] != key_d[(size_t)y]) return key_d[(size_t)x] < key_d[(size_t)y];
-      return x < y;
-    });
-    e = hipMemcpyAsync(d_qperm, qperm.data(), (size_t)n_group * TILE_TQ * 4, hipMemcpyHostToDevice, s);
+    e = cells_pass_order(a, P.cell_rank, order, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.seed_flag, 0, (size_t)n_group * T, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.part_p, 0xff, (size_t)m * 2 * W * k * 4, s);  // position -1: a list that has ended
     if (e == hipSuccess) e = launch_cells_plan(a, 0, s);
@@ -171,9 +148,6 @@ int scann::cells_search(scann_handle* h, scann_index* ix, const float* dq, const
     if (e != hipSuccess) break;
     int64_t seeds = 0, kept = 0;
     for (int i = 0; i < n_group; ++i) seeds += count[(size_t)i], kept += count[(size_t)i] + count[(size_t)n_group + i];
-    st[0] += (int64_t)n_group * full_tiles;
-    st[1] += seeds;
-    st[3] += n_group;
     if ((double)kept > share * (double)n_group * (double)T) {
       // the plan keeps too much: the full kernel answers this pass (its seeds were visited, and count as that)
       const size_t o = (size_t)q0 * k;
@@ -182,28 +156,23 @@ int scann::cells_search(scann_handle* h, scann_index* ix, const float* dq, const
         ws.release();
         return r;
       }
-      st[2] += seeds + (int64_t)n_group * full_tiles;
+      st.pass(n_group, full_tiles, seeds, seeds + (int64_t)n_group * full_tiles);
       continue;
     }
-    st[2] += kept;
+    st.pass(n_group, full_tiles, seeds, kept);
     e = launch_cells_list(a, 1, s);
     if (e == hipSuccess) e = launch_knn_merge(a.part_d, a.part_p, m, 2 * W, k, dev_d ? dev_d + (size_t)q0 * k : out_d, out_p, s);
     if (e == hipSuccess && !dev_d) e = hipMemcpyAsync(dist2 + (size_t)q0 * k, out_d, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && !dev_d) e = hipMemcpyAsync(pos_h.data(), out_p, (size_t)m * k * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) break;
-    for (size_t i = 0; !dev_d && i < (size_t)m * k; ++i) {
-      const int32_t p = pos_h[i];
-      const size_t o = (size_t)q0 * k + i;
-      if (pos) pos[o] = p;
-      if (ids) ids[o] = p < 0 ? -1 : ix->ids[(size_t)p];
-      if (atoms) atoms[o] = p < 0 ? -1 : ix->atoms[(size_t)p];
-    }
+    const size_t o = (size_t)q0 * k;
+    if (!dev_d) name_positions(ix, pos_h.data(), (size_t)m * k, pos ? pos + o : nullptr, ids ? ids + o : nullptr, atoms ? atoms + o : nullptr);
   }
   if (e != hipSuccess) (void)hipStreamSynchronize(s);
   ws.release();
   HIPCHK(h, e);
-  std::copy(st, st + 4, ix->stats);
+  st.write(ix);
   return SCANN_OK;
 }
 
@@ -373,18 +342,16 @@ int scann_index_query_rows(scann_handle_t* h, scann_index_t* ix, int64_t first, 
   if (n > (int64_t)0x7fffffff / SCANN_KNN_MAX_K) return fail(h, SCANN_ERR_INVALID, "scann_index_query_rows: too many queries in one call");
   if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query_rows: dist2 is null");
   HIPCHK(h, hipSetDevice(h->device));
-  int64_t st[4] = {0, 0, 0, 0};
-  for (int64_t done = 0; done < n;) {  // the queries where they lie, chunk by chunk: rows of the index are padded as queries are
-    const int64_t at = first + done;
-    const size_t c = (size_t)(at / ix->chunk_rows);
-    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
-    if (const int r = search(h, ix, ix->rows_of(c) + (size_t)r0 * ix->stride, nullptr, m, k, h->streams[0], dist2 + (size_t)done * k,
-                             ids ? ids + (size_t)done * k : nullptr, atoms ? atoms + (size_t)done * k : nullptr, pos ? pos + (size_t)done * k : nullptr))
-      return r;
-    for (int i = 0; i < 4; ++i) st[i] += ix->stats[i];
-    done += m;
-  }
-  std::copy(st, st + 4, ix->stats);
+  SearchStats st;
+  // the queries where they lie, chunk by chunk: rows of the index are padded as queries are
+  if (const int r = row_runs(ix, first, n, [&](size_t c, int64_t r0, int64_t m, int64_t done) {
+        const int r = search(h, ix, ix->rows_of(c) + (size_t)r0 * ix->stride, nullptr, m, k, h->streams[0], dist2 + (size_t)done * k,
+                             ids ? ids + (size_t)done * k : nullptr, atoms ? atoms + (size_t)done * k : nullptr, pos ? pos + (size_t)done * k : nullptr);
+        st.add(ix->stats);
+        return r;
+      }))
+    return r;
+  st.write(ix);
   return SCANN_OK;
 }
 

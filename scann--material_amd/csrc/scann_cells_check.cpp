@@ -3,37 +3,20 @@
 // AddressSanitizer + UBSan (host code only, no device is touched) and runs it.  It walks N = 1, 63, 64, 65 and 1000, a cell of exactly
 // 64 rows, cells > N, identical rows, non-finite rows and the refusals, checks the layout's invariants -- every position once, whole
 // tiles, shells ascending within a cell, lo / hi the bits of the tile's first and last real row -- and the bound against the chain.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
+// It also drives the pure pieces the searches share (scann_search.h): the order of a pass's queries, and the walk over a window of rows.
 #include "scann_cells.cpp"
 #include "scann_kmeans.cpp"
 #include "scann_select.cpp"
 
-// what the device halves refer to; none of it is called here (dist2_to_rows is the twins' chain: the plain loop of scann_knn.cpp)
+#include "scann_check.h"
+
+// the stubs of its own
 namespace scann {
-hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
-void cached_free(void*) {}
-int fail(scann_handle*, int code, const std::string&) { return code; }
-int check_index(scann_handle*, const scann_index*, const char*) { return SCANN_ERR_INVALID; }
-int check_k(scann_handle*, int32_t, const char*) { return SCANN_ERR_INVALID; }
 int search(scann_handle*, scann_index*, const float*, const int64_t*, int64_t, int, hipStream_t, float*, int64_t*, int32_t*, int32_t*, float*) {
   return SCANN_ERR_INVALID;
 }
 int search_full(scann_handle*, scann_index*, const float*, const int64_t*, int64_t, int, hipStream_t, float*, int64_t*, int32_t*, int32_t*, float*) {
   return SCANN_ERR_INVALID;
-}
-void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out) {
-  for (int64_t r = 0; r < n; ++r) {
-    float acc = 0.f;
-    for (int64_t j = 0; j < d; ++j) {
-      const float t = q[j] - rows[r * d + j];
-      acc = fmaf(t, t, acc);
-    }
-    out[r] = acc;
-  }
 }
 hipError_t launch_kcenter_prepare(const KcArgs&, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_kcenter_step(const KcArgs&, int, hipStream_t) { return hipErrorNotSupported; }
@@ -43,26 +26,16 @@ hipError_t launch_kmeans_round(const KmArgs&, int, hipStream_t) { return hipErro
 hipError_t launch_knn_merge(const float*, const int32_t*, int, int, int, float*, int32_t*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cells_gather(const CellGatherArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cells_roots(const float*, const float*, double*, double*, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cells_centre(const CellSearchArgs&, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cells_plan(const CellSearchArgs&, int, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cells_list(const CellSearchArgs&, int, hipStream_t) { return hipErrorNotSupported; }
 }  // namespace scann
 
 namespace {
-
-int bad = 0;
-unsigned state = 2025u;
-unsigned draw() { state = state * 1664525u + 1013904223u; return (state >> 8) & 0xffffff; }
-
-#define EXPECT(c) do { if (!(c)) ++bad, std::printf("line %d: %s\n", __LINE__, #c); } while (0)
 
 float scann_knn_distsq_local(const float* q, const float* r, int64_t d) {  // one pair of the chain
   float out;
   scann::dist2_to_rows(q, r, 1, d, &out);
   return out;
 }
-
-uint32_t bits_of(float x) { uint32_t b; std::memcpy(&b, &x, 4); return b; }
 
 void check_partition(const std::vector<float>& rows, int64_t n, int64_t dim, int32_t cells, int32_t max_iter) {
   const int64_t cap = scann_cells_capacity(n, cells);
@@ -99,6 +72,66 @@ void check_partition(const std::vector<float>& rows, int64_t n, int64_t dim, int
   for (int64_t p = 0; p < n; ++p) EXPECT(seen[(size_t)p]);
 }
 
+// query_order (scann_search.h): a permutation of the pass's queries, ascending under (rank of the nearest cell, distance to its centre
+// unless there is none, place), queries without a cell last in place order, then -1 to the end of the last group of 128 and no further
+void check_query_order() {
+  const int32_t C = 5;
+  const std::vector<int32_t> ident = {0, 1, 2, 3, 4}, walk = {3, 0, 4, 1, 2};
+  for (const std::vector<int32_t>& rank : {ident, walk})
+    for (int32_t m : {1, 127, 128, 129}) {
+      std::vector<int32_t> cell((size_t)m);
+      std::vector<float> d((size_t)m);
+      for (int32_t i = 0; i < m; ++i) cell[(size_t)i] = (int32_t)(draw() % (C + 1)) - 1, d[(size_t)i] = (float)(draw() % 3);  // many ties
+      const size_t padded = (size_t)(m + 127) / 128 * 128;
+      std::vector<int32_t> qperm(padded + 1, -7);
+      scann::query_order(cell.data(), d.data(), rank.data(), C, m, qperm.data());
+      std::vector<char> seen((size_t)m, 0);
+      auto key = [&](int32_t x) { return cell[(size_t)x] < 0 ? C : rank[(size_t)cell[(size_t)x]]; };
+      for (int32_t i = 0; i < m; ++i) {
+        const int32_t y = qperm[(size_t)i];
+        EXPECT(y >= 0 && y < m && !seen[(size_t)y]);
+        if (y < 0 || y >= m) return;
+        seen[(size_t)y] = 1;
+        if (i == 0) continue;
+        const int32_t x = qperm[(size_t)i - 1];
+        if (key(x) != key(y)) EXPECT(key(x) < key(y));
+        else if (key(x) < C && d[(size_t)x] != d[(size_t)y]) EXPECT(d[(size_t)x] < d[(size_t)y]);
+        else EXPECT(x < y);
+      }
+      for (size_t i = (size_t)m; i < padded; ++i) EXPECT(qperm[i] == -1);
+      EXPECT(qperm[padded] == -7);
+    }
+  // written out: cell 1 comes first on the walk {1, 0}; equal (cell, distance) by place; no cell: last, by place whatever the distance
+  const int32_t cell[6] = {1, -1, 0, 1, -1, 0}, by_walk[2] = {1, 0}, by_number[2] = {0, 1};
+  const float d[6] = {2.f, 9.f, 1.f, 2.f, 0.f, 1.f};
+  std::vector<int32_t> qperm(128);
+  scann::query_order(cell, d, by_walk, 2, 6, qperm.data());
+  EXPECT((std::vector<int32_t>(qperm.begin(), qperm.begin() + 7) == std::vector<int32_t>{0, 3, 2, 5, 1, 4, -1}) && qperm[127] == -1);
+  scann::query_order(cell, d, by_number, 2, 6, qperm.data());
+  EXPECT((std::vector<int32_t>(qperm.begin(), qperm.begin() + 7) == std::vector<int32_t>{2, 5, 0, 3, 1, 4, -1}));
+}
+
+// row_runs (scann_search.h): the window cut at the chunk boundaries and nowhere else, every row once and in order
+void check_row_runs() {
+  scann_index ix;
+  ix.chunk_rows = 64;
+  struct Window { int64_t first, n; int runs; };
+  // no boundary; starts on one; ends on one; spans one; spans three; a whole chunk; empty
+  for (const Window& w : {Window{3, 10, 1}, Window{64, 10, 1}, Window{54, 10, 1}, Window{60, 10, 2}, Window{60, 140, 4}, Window{128, 64, 1}, Window{70, 0, 0}}) {
+    int runs = 0;
+    int64_t rows = 0;
+    EXPECT(scann::row_runs(&ix, w.first, w.n, [&](size_t c, int64_t r0, int64_t m, int64_t done) {
+             EXPECT(done == rows && (int64_t)c * 64 + r0 == w.first + done && m >= 1 && r0 >= 0 && r0 + m <= 64);
+             EXPECT(runs == 0 ? true : r0 == 0);  // only the first run starts inside a chunk
+             ++runs, rows += m;
+             return 0;
+           }) == 0);
+    EXPECT(runs == w.runs && rows == w.n);
+  }
+  int runs = 0;  // a status that is not 0 ends the walk and is what the walk returns
+  EXPECT(scann::row_runs(&ix, 60, 140, [&](size_t, int64_t, int64_t, int64_t) { return ++runs == 2 ? 7 : 0; }) == 7 && runs == 2);
+}
+
 std::vector<float> rows_of(int64_t n, int64_t dim, float scale) {
   std::vector<float> x((size_t)(n * dim));
   for (auto& v : x) v = ((float)(draw() % 20001) / 10000.f - 1.f) * scale;
@@ -108,6 +141,7 @@ std::vector<float> rows_of(int64_t n, int64_t dim, float scale) {
 }  // namespace
 
 int main() {
+  state = 2025u;
   for (int64_t n : {1, 63, 64, 65, 1000})
     for (int64_t dim : {1, 3, 33})
       for (int32_t cells : {1, 2, 7, 64, 1024}) check_partition(rows_of(n, dim, 1.f), n, dim, cells, 3);
@@ -151,6 +185,7 @@ int main() {
   EXPECT(positive > 0);
   EXPECT(scann_cell_bound(INFINITY, 0.f, 1.f) == 0.0 && scann_cell_bound(NAN, 0.f, 1.f) == 0.0 && scann_cell_bound(4.f, 0.f, INFINITY) == 0.0);
   EXPECT(scann_cell_bound(100.f, 0.f, 1.f) > 80.0 && scann_cell_bound(0.f, 100.f, 121.f) > 99.0 && scann_cell_bound(1.f, 1.f, 1.f) == 0.0);
-  std::printf(bad ? "scann_cells_check: %d FAILED\n" : "scann_cells_check: ok\n", bad);
-  return bad ? 1 : 0;
+  check_query_order();
+  check_row_runs();
+  return finish("scann_cells_check");
 }

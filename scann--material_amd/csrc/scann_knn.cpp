@@ -9,6 +9,7 @@
 #include "scann_cells.h"
 #include "scann_knn.h"
 #include "scann_runtime.h"
+#include "scann_search.h"
 
 using namespace scann;
 
@@ -87,18 +88,15 @@ int append_rows(scann_handle* h, scann_index* ix, const void* src, size_t pitch,
                 const int32_t* atoms, hipStream_t s) {
   if (n <= 0) return SCANN_OK;
   if (ix->n + n > (int64_t)0x7fffffff) return fail(h, SCANN_ERR_UNSUPPORTED, "scann_index_add: an index holds fewer than 2^31 rows");
-  int64_t done = 0;
-  while (done < n) {
-    const int64_t at = ix->n + done;
-    const size_t c = (size_t)(at / ix->chunk_rows);
-    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
+  const int r = row_runs(ix, ix->n, n, [&](size_t c, int64_t r0, int64_t m, int64_t done) {
     if (c == ix->chunks.size())
       if (const int r = index_new_chunk(h, ix, s)) return r;
     HIPCHK(h, hipMemcpy2DAsync(ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4, static_cast<const char*>(src) + (size_t)done * pitch,
                                pitch, (size_t)ix->dim * 4, (size_t)m, kind, s));
     HIPCHK(h, hipMemcpyAsync(ix->ids_of(c) + r0, ids + done, (size_t)m * 8, hipMemcpyHostToDevice, s));
-    done += m;
-  }
+    return (int)SCANN_OK;
+  });
+  if (r) return r;
   HIPCHK(h, hipStreamSynchronize(s));
   index_note_rows(ix, n, ids, atoms);
   return SCANN_OK;
@@ -135,9 +133,11 @@ int scann::search_full(scann_handle* h, scann_index* ix, const float* dq, const 
   ws.take(d_rows, n_tab); ws.take(d_ids, n_tab);
   HIPCHK(h, ws.alloc());
   std::vector<int32_t> pos_h(dev_d ? 0 : (size_t)nq * k);
+  SearchStats st;  // every (128-query group, 64-row tile) pair is visited
   hipError_t e = ws.upload_rows(ix, n_chunk, d_rows, d_ids, s);  // the chunks' rows, and their ids
   for (int64_t q0 = 0; q0 < nq && e == hipSuccess; q0 += g) {
     const int m = (int)std::min<int64_t>(g, nq - q0);
+    st.pass(SearchStats::groups(m), SearchStats::full_tiles(ix), 0, SearchStats::groups(m) * SearchStats::full_tiles(ix));
     KnnArgs a{};
     a.rows = d_rows; a.ids = d_ids;
     a.n_total = (int32_t)N; a.chunk_rows = ix->chunk_rows; a.n_chunk = n_chunk;
@@ -154,18 +154,8 @@ int scann::search_full(scann_handle* h, scann_index* ix, const float* dq, const 
   else if (e != hipSuccess) (void)hipStreamSynchronize(s);
   ws.release();
   HIPCHK(h, e);
-  {  // what scann_index_search_stats reports: every (128-query group, 64-row tile) pair was visited
-    int64_t groups = 0, tiles = 0;
-    for (int64_t q0 = 0; q0 < nq; q0 += g) groups += (std::min<int64_t>(g, nq - q0) + TILE_TQ - 1) / TILE_TQ;
-    for (int64_t r = 0; r < N; r += ix->chunk_rows) tiles += (std::min<int64_t>(ix->chunk_rows, N - r) + TILE_TR - 1) / TILE_TR;
-    ix->stats[0] = ix->stats[2] = groups * tiles; ix->stats[1] = 0; ix->stats[3] = groups;
-  }
-  for (size_t i = 0; i < pos_h.size(); ++i) {
-    const int32_t p = pos_h[i];
-    if (pos) pos[i] = p;
-    if (ids) ids[i] = p < 0 ? -1 : ix->ids[(size_t)p];
-    if (atoms) atoms[i] = p < 0 ? -1 : ix->atoms[(size_t)p];
-  }
+  st.write(ix);
+  name_positions(ix, pos_h.data(), pos_h.size(), pos, ids, atoms);
   return SCANN_OK;
 }
 
@@ -174,33 +164,6 @@ void scann::dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t 
   if (__builtin_cpu_supports("fma")) dist2_matrix_fma(q, 1, rows, n, d, out);
   else dist2_matrix_plain(q, 1, rows, n, d, out);
 }
-
-namespace {
-
-// nq queries of the index's width at q -- host rows (kind = hipMemcpyHostToDevice) or device rows -- and their ids (host [nq], or null) staged
-// in one block of the cache and searched: the rows padded to the stride, then the ids.  Device rows whose width is the stride are searched
-// where they lie.
-int search_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int64_t* qid, int64_t nq, int k, hipStream_t s,
-                  float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos) {
-  CallWs ws;
-  RowStage st;
-  int64_t* d_qid;
-  st.take(ws, nq, ix->dim, ix->dim, ix->stride, kind);
-  ws.take(d_qid, (size_t)nq);
-  HIPCHK(h, ws.alloc());
-  hipError_t e = st.stage_rows(q, s);
-  if (e == hipSuccess && qid) e = hipMemcpyAsync(d_qid, qid, (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  int r = SCANN_OK;
-  if (e == hipSuccess)
-    r = search(h, ix, st.rows(q), qid ? d_qid : nullptr, nq, k, s, dist2, ids, atoms, pos);
-  else
-    (void)hipStreamSynchronize(s);
-  ws.release();
-  HIPCHK(h, e);
-  return r;
-}
-
-}  // namespace
 
 // The rows a batch has at a level -- one per structure, or (atom) one per atom in packed order -- named: id_v = the structure's id
 // (ids[b]; ids null: first + b), at_v (if asked for) = the atom's index in its structure, -1 for a structure row
@@ -243,6 +206,7 @@ int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out) {
   ix->device = h->device;
   ix->dim = dim;
   ix->stride = (dim + 3) / 4 * 4;
+  static_assert(4096 % TILE_TR == 0, "a chunk holds whole tiles (SearchStats::full_tiles)");
   ix->chunk_rows = (int32_t)std::max<size_t>(4096, ((size_t)64 << 20) / ((size_t)ix->stride * 4) / TILE_TR * TILE_TR);
   *out = ix;
   return SCANN_OK;
@@ -276,14 +240,13 @@ int scann_index_read(scann_handle_t* h, scann_index_t* ix, int64_t first, int64_
   if (first < 0 || n < 0 || first + n > ix->n)
     return fail(h, SCANN_ERR_INVALID, "scann_index_read: rows " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " + std::to_string(ix->n));
   HIPCHK(h, hipSetDevice(h->device));
-  for (int64_t done = 0; rows && done < n;) {
-    const int64_t at = first + done;
-    const size_t c = (size_t)(at / ix->chunk_rows);
-    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
-    HIPCHK(h, hipMemcpy2D(rows + (size_t)done * ix->dim, (size_t)ix->dim * 4, ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4,
-                          (size_t)ix->dim * 4, (size_t)m, hipMemcpyDeviceToHost));
-    done += m;
-  }
+  if (rows)
+    if (const int r = row_runs(ix, first, n, [&](size_t c, int64_t r0, int64_t m, int64_t done) {
+          HIPCHK(h, hipMemcpy2D(rows + (size_t)done * ix->dim, (size_t)ix->dim * 4, ix->rows_of(c) + (size_t)r0 * ix->stride, (size_t)ix->stride * 4,
+                                (size_t)ix->dim * 4, (size_t)m, hipMemcpyDeviceToHost));
+          return (int)SCANN_OK;
+        }))
+      return r;
   if (ids) std::copy(ix->ids.begin() + first, ix->ids.begin() + first + n, ids);
   if (atoms) std::copy(ix->atoms.begin() + first, ix->atoms.begin() + first + n, atoms);
   return SCANN_OK;
@@ -297,7 +260,10 @@ int scann_index_query(scann_handle_t* h, scann_index_t* ix, const float* q, int6
   if (nq > (int64_t)0x7fffffff / SCANN_KNN_MAX_K) return fail(h, SCANN_ERR_INVALID, "scann_index_query: too many queries in one call");
   if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query: dist2 is null");
   HIPCHK(h, hipSetDevice(h->device));
-  return search_staged(h, ix, q, hipMemcpyHostToDevice, query_ids, nq, k, h->streams[0], dist2, ids, atoms, pos);
+  hipStream_t s = h->streams[0];
+  return staged_queries(h, ix, q, hipMemcpyHostToDevice, query_ids, nq, s, [&](const float* dq, const int64_t* dqid) {
+    return search(h, ix, dq, dqid, nq, k, s, dist2, ids, atoms, pos);
+  });
 }
 
 int scann_index_add_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t* db, int32_t level, const int64_t* ids) {
@@ -321,20 +287,12 @@ int scann_index_query_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_t
   if (!db) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: null argument");
   if (const int r = check_k(h, k, "scann_index_query_batch")) return r;
   if (const int r = check_level(h, ix, level, "scann_index_query_batch")) return r;
-  const bool atom = level == SCANN_OUT_AFTER_LC;
-  const int B = db->n_struct, A = db->n_atom;
-  const int64_t nq = atom ? A : B;
+  const int64_t nq = level == SCANN_OUT_AFTER_LC ? db->n_atom : db->n_struct;
   if (nq <= 0) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: an empty query");
   if (!dist2) return fail(h, SCANN_ERR_INVALID, "scann_index_query_batch: dist2 is null");
-  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_query_batch: weights not loaded");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
-  std::vector<int64_t> qid;
-  if (query_ids)
-    if (const int r = expand_ids(h, db, atom, query_ids, 0, qid, nullptr)) return r;
-  // the level's rows are the queries where the forward left them
-  return search_staged(h, ix, atom ? db->out_z : db->out_bf, hipMemcpyDeviceToDevice, query_ids ? qid.data() : nullptr, nq, k, h->streams[db->last_slot],
-                       dist2, ids, atoms, pos);
+  return staged_batch_queries(h, ix, db, level, query_ids, y, ga, "scann_index_query_batch", [&](const float* dq, const int64_t* dqid) {
+    return search(h, ix, dq, dqid, nq, k, h->streams[db->last_slot], dist2, ids, atoms, pos);
+  });
 }
 
 }  // extern "C"

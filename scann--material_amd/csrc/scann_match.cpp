@@ -194,7 +194,7 @@ int match_search(scann_handle* h, scann_index* ix, const float* dq, const int32_
 
 }  // namespace
 
-// as search_staged: host or device query rows of the index's width staged at the padded width, then matched (scann_match.h)
+// as staged_queries (scann_search.h): host or device query rows of the index's width staged at the padded width, then matched (scann_match.h)
 int scann::match_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int32_t* q_first, int64_t n_sets, const int64_t* qid,
                  int measure, int k, hipStream_t s, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos,
                  float* match_d) {

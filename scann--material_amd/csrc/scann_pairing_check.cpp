@@ -4,21 +4,12 @@
 // 1 and 128, dim 1, 3 and 130, a permuted copy, the counting example of the header, Dmax = 0, subnormal and huge distances, overflow,
 // a NaN row, a segment above the limit, the refusals -- and checks the symmetry of the score bit for bit and the integer exponent
 // against ilogbf.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "scann_pairing.cpp"
 
-// what the device half of scann_pairing.cpp refers to; none of it is called here
+#include "scann_check.h"
+
+// the stubs of its own
 namespace scann {
-hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
-void cached_free(void*) {}
-int fail(scann_handle*, int code, const std::string&) { return code; }
-int check_index(scann_handle*, const scann_index*, const char*) { return SCANN_ERR_INVALID; }
-int check_k(scann_handle*, int32_t, const char*) { return SCANN_ERR_INVALID; }
-int forward_and_download(scann_handle_t*, scann_dbatch_t*, uint64_t, int32_t, float*, float*) { return SCANN_ERR_INVALID; }
 int read_mol_offset(scann_handle_t*, const scann_dbatch_t*, std::vector<int32_t>&) { return SCANN_ERR_INVALID; }
 int match_staged(scann_handle*, scann_index*, const float*, hipMemcpyKind, const int32_t*, int64_t, const int64_t*, int, int, hipStream_t, float*,
                  int32_t*, int64_t*, int32_t*, float*, int32_t*, float*) { return SCANN_ERR_INVALID; }
@@ -27,14 +18,6 @@ hipError_t launch_pairing(const PairingArgs&, const int32_t*, hipStream_t) { ret
 }  // namespace scann
 
 namespace {
-
-int bad = 0;
-unsigned state = 2024u;
-unsigned draw() { state = state * 1664525u + 1013904223u; return (state >> 8) & 0xffffff; }
-
-#define EXPECT(c) do { if (!(c)) ++bad, std::printf("line %d: %s\n", __LINE__, #c); } while (0)
-
-uint32_t bits_of(float x) { uint32_t b; std::memcpy(&b, &x, 4); return b; }
 
 // the least sum over all permutations
 long long brute(const std::vector<uint32_t>& C, int Q) {
@@ -92,6 +75,7 @@ std::vector<float> rows_of(int64_t n, int64_t dim, float scale, bool integer) {
 }  // namespace
 
 int main() {
+  state = 2024u;
   // the integer exponent against ilogbf
   for (float x : {1.f, 1.5f, 2.f, 0.75f, 1e-38f, 1e-40f, 1.4e-45f, 3e38f, 1.17549435e-38f, 5.877e-39f}) EXPECT(pairing_ilogb(bits_of(x)) == std::ilogb(x));
   EXPECT(pairing_shift(bits_of(0.f)) == 0 && pairing_shift(bits_of(1.f)) == 30 && pairing_shift(bits_of(1.4e-45f)) == 179 && pairing_shift(bits_of(3.4e38f)) == -97);
@@ -179,6 +163,5 @@ int main() {
     EXPECT(scann_pairing_host(nullptr, 1, b.data(), 1, 3, nullptr, nullptr, nullptr, nullptr, nullptr) == SCANN_ERR_INVALID);
     EXPECT(scann_pairing_host(b.data(), 2, b.data(), 2, 3, nullptr, nullptr, nullptr, nullptr, nullptr) == SCANN_OK);
   }
-  std::printf(bad ? "scann_pairing_check: %d FAILED\n" : "scann_pairing_check: ok\n", bad);
-  return bad ? 1 : 0;
+  return finish("scann_pairing_check");
 }

@@ -3,19 +3,12 @@
 // subset, with and without dist2, m = 1, 31 and 32, probes that are -1, the query itself, repeated or ineligible, coincident rows, one
 // and several threads, a pool that is no multiple of the 8-row block, the refusals -- and checks the twin against a count written out
 // in the definition's words, and that the thread count does not enter the bytes.
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "scann_ranks.cpp"
 
-// what the device half of scann_ranks.cpp refers to; none of it is called here
+#include "scann_check.h"
+
+// the stubs of its own
 namespace scann {
-hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
-void cached_free(void*) {}
-int fail(scann_handle*, int code, const std::string&) { return code; }
-void peaks_geometry(int64_t, int64_t, int32_t* r, int32_t* n) { *r = TILE_TR, *n = 1; }
-hipError_t launch_sil_eligible(const float* const*, int32_t, int32_t, int32_t, unsigned char*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_ranks_prepare(const RanksArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_ranks_tiles(const RanksArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_ranks_finish(const RanksArgs&, hipStream_t) { return hipErrorNotSupported; }
@@ -39,9 +32,8 @@ int32_t rank_by_count(const std::vector<float>& rows, int64_t n, int64_t dim, in
 }  // namespace
 
 int main() {
-  int bad = 0;
-  unsigned state = 12345u;
-  auto draw = [&]() { state = state * 1664525u + 1013904223u; return (state >> 8) & 0xffff; };
+  state = 12345u;
+  auto draw = [] { return ::draw() & 0xffff; };
   for (int64_t n : {1, 2, 7, 8, 9, 203}) {
     for (int64_t dim : {1, 3, 130}) {
       std::vector<float> rows((size_t)(n * dim));
@@ -79,6 +71,5 @@ int main() {
   if (scann_ranks_host(rows.data(), 4, 3, nullptr, 0, probe.data(), 2, 0, rank.data(), nullptr) != SCANN_ERR_INVALID) ++bad;   // a probe outside
   if (scann_ranks_host(rows.data(), 4, 3, nullptr, 0, nullptr, 2, 0, rank.data(), nullptr) != SCANN_ERR_INVALID) ++bad;        // a null argument
   if (scann_ranks_host(rows.data(), 0, 3, nullptr, 0, nullptr, 2, 0, nullptr, nullptr) != SCANN_OK) ++bad;                     // an empty pool
-  std::printf(bad ? "scann_ranks_check: %d FAILED\n" : "scann_ranks_check: ok\n", bad);
-  return bad ? 1 : 0;
+  return finish("scann_ranks_check");
 }

@@ -2,21 +2,14 @@
 // scann_silhouette.cpp under AddressSanitizer + UBSan (host code only, no device is touched) and runs it.  It walks the twin's paths --
 // all rows and a qpos subset, both metrics, the table, non-finite and unlabelled rows, one and several threads, a pool that is no
 // multiple of the 8-row block, the refusals -- and checks that the thread count does not enter the bytes.
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "scann_silhouette.cpp"
 
-// what the device half of scann_silhouette.cpp refers to; none of it is called here
+#include "scann_check.h"
+
+// the stubs of its own
 namespace scann {
-hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
-void cached_free(void*) {}
-int fail(scann_handle*, int code, const std::string&) { return code; }
-void peaks_geometry(int64_t, int64_t, int32_t* r, int32_t* n) { *r = TILE_TR, *n = 1; }
 hipError_t launch_sil_tiles(const SilArgs&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_sil_finish(const SilArgs&, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_sil_eligible(const float* const*, int32_t, int32_t, int32_t, unsigned char*, hipStream_t) { return hipErrorNotSupported; }
 }  // namespace scann
 
 namespace {
@@ -42,9 +35,8 @@ int run(const std::vector<float>& rows, int64_t n, int64_t dim, const std::vecto
 }  // namespace
 
 int main() {
-  int bad = 0;
-  unsigned state = 12345u;
-  auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)((state >> 8) & 0xffff) / 65536.f - 0.5f; };
+  state = 12345u;
+  auto next = [] { return (float)(draw() & 0xffff) / 65536.f - 0.5f; };
   for (int64_t n : {1, 2, 7, 8, 9, 203}) {
     for (int64_t dim : {1, 3, 130}) {
       std::vector<float> rows((size_t)(n * dim));
@@ -76,6 +68,5 @@ int main() {
   if (run(rows, 4, 3, lab, 3, &q, 0, 0, 0, &o) != SCANN_ERR_INVALID) ++bad;                                   // a position outside
   if (run(rows, 4, 3, lab, 3, nullptr, 0, 127, 0, &o) != SCANN_ERR_INVALID) ++bad;                            // a shift outside
   if (run(rows, 0, 3, lab, 3, nullptr, 0, 0, 0, &o) != SCANN_OK || o.counts != std::vector<int64_t>{0, 0, 0}) ++bad;  // an empty pool
-  std::printf(bad ? "scann_silhouette_check: %d FAILED\n" : "scann_silhouette_check: ok\n", bad);
-  return bad ? 1 : 0;
+  return finish("scann_silhouette_check");
 }

@@ -14,6 +14,7 @@
 
 #include "scann_call.h"
 #include "scann_runtime.h"
+#include "scann_search.h"
 
 using namespace scann;
 
@@ -82,23 +83,24 @@ int within_core(scann_handle* h, scann_index* ix, const std::vector<Seg>& segs, 
                 hipStream_t s, const Out& o) {
   std::fill(o.counts, o.counts + nq, 0);
   *o.total = 0;
-  std::fill(ix->stats, ix->stats + 4, 0);
+  SearchStats st;
+  st.write(ix);
   const int64_t N = ix->n;
   if (N == 0) return SCANN_OK;
   const CellPart* P = ix->part;
   const int stride = ix->stride;
   const int n_chunk = (int)((N + ix->chunk_rows - 1) / ix->chunk_rows);
-  const int T_full = (int)((N + TILE_TR - 1) / TILE_TR), T = P ? P->n_tile : T_full, C = P ? P->lay.C : 0;
+  const int T_full = (int)SearchStats::full_tiles(ix), T = P ? P->n_tile : T_full, C = P ? P->lay.C : 0;
   const int64_t pass = P ? 1024 : WITHIN_PASS;
   int64_t seg_max = 0, n_groups = 0;
   for (const Seg& sg : segs) {
     seg_max = std::max(seg_max, sg.m);
-    for (int64_t q0 = 0; q0 < sg.m; q0 += pass) n_groups += (std::min(pass, sg.m - q0) + TILE_TQ - 1) / TILE_TQ;
+    for (int64_t q0 = 0; q0 < sg.m; q0 += pass) n_groups += SearchStats::groups(std::min(pass, sg.m - q0));
   }
   const int64_t g = std::min(seg_max, pass);
-  const int G = (int)((g + TILE_TQ - 1) / TILE_TQ);
+  const int G = (int)SearchStats::groups(g);
   WithinArgs a{};
-  CellSearchArgs ca{};
+  CellSearchArgs ca = P ? cells_args(*P) : CellSearchArgs{};
   CallWs ws;
   const float* const* d_rows;
   const int64_t* const* d_ids;
@@ -114,49 +116,34 @@ int within_core(scann_handle* h, scann_index* ix, const std::vector<Seg>& segs, 
   if (P) {
     a.rows = P->d_rows; a.ids = P->d_ids; a.pos = P->d_pos; a.n_entries = T * TILE_TR; a.chunk_rows = P->chunk_rows;
     a.qperm = d_qperm; a.list = ca.list; a.count = ca.count; a.n_tile = T;
-    ca.rows = P->d_rows; ca.ids = P->d_ids; ca.pos = P->d_pos; ca.centres = P->d_centres; ca.tile_cell = P->d_tile_cell; ca.first_tile = P->d_first_tile;
-    ca.rlo = P->d_rlo; ca.rhi = P->d_rhi; ca.full = P->d_full;
-    ca.C = C; ca.n_tile = T; ca.n_cell_tile = P->n_cell_tile; ca.chunk_rows = P->chunk_rows; ca.stride = stride;
     ca.k = 1; ca.qperm = d_qperm; ca.radius2 = radius2;
   } else {
     a.rows = d_rows; a.ids = d_ids; a.n_entries = (int32_t)N; a.chunk_rows = ix->chunk_rows;
   }
-  std::vector<int32_t> key_c((size_t)(P ? g : 0)), qperm((size_t)(P ? G * TILE_TQ : 0)), plan_count((size_t)(P ? n_groups : 0));
-  std::vector<float> key_d((size_t)(P ? g : 0));
-  int64_t visited = 0, groups_done = 0, q_off = 0;
+  std::vector<int32_t> plan_count((size_t)(P ? n_groups : 0));
+  PassOrder order;
+  int64_t groups_done = 0, q_off = 0;
   hipError_t e = hipMemsetAsync(ws.base(), 0, zeroed, s);
   if (e == hipSuccess && !P) e = ws.upload_rows(ix, n_chunk, d_rows, d_ids, s);
   for (const Seg& sg : segs) {
     for (int64_t q0 = 0; q0 < sg.m && e == hipSuccess; q0 += pass) {
-      const int m = (int)std::min(pass, sg.m - q0), n_group = (m + TILE_TQ - 1) / TILE_TQ;
+      const int m = (int)std::min(pass, sg.m - q0), n_group = (int)SearchStats::groups(m);
       a.q = sg.dq + (size_t)q0 * stride; a.qid = dqid ? dqid + q_off + q0 : nullptr; a.nq = m; a.n_group = n_group;
       a.q_base = (int32_t)(q_off + q0); a.self_first = sg.self_first >= 0 ? (int32_t)(sg.self_first + q0) : -1;
       if (!P) {
         e = launch_within_tile(a, std::min(WITHIN_RANGES, T), s);
+        int64_t visited = 0;
         for (int i = 0; i < n_group; ++i) visited += T - (upper ? std::min<int64_t>(T, (a.self_first + (int64_t)i * TILE_TQ + 1) / TILE_TR) : 0);
-        groups_done += n_group;
+        st.pass(n_group, T_full, 0, visited);
         continue;
       }
       ca.q = a.q; ca.qid = a.qid; ca.nq = m; ca.n_group = n_group;
-      e = launch_cells_centre(ca, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(key_c.data(), ca.key_cell, (size_t)m * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(key_d.data(), ca.key_d, (size_t)m * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the pass's one wait; the plan counts of the pass before have arrived too)
-      if (e != hipSuccess) break;
-      // the queries by (place of the nearest cell on the walk through the centres, distance to its centre, place), as cells_search orders them
-      std::fill(qperm.begin(), qperm.end(), -1);
-      std::iota(qperm.begin(), qperm.begin() + m, 0);
-      std::sort(qperm.begin(), qperm.begin() + m, [&](int32_t x, int32_t y) {
-        const int32_t cx = key_c[(size_t)x] < 0 ? C : P->cell_rank[(size_t)key_c[(size_t)x]], cy = key_c[(size_t)y] < 0 ? C : P->cell_rank[(size_t)key_c[(size_t)y]];
-        if (cx != cy) return cx < cy;
-        if (cx < C && key_d[(size_t)x] != key_d[(size_t)y]) return key_d[(size_t)x] < key_d[(size_t)y];
-        return x < y;
-      });
-      e = hipMemcpyAsync(d_qperm, qperm.data(), (size_t)n_group * TILE_TQ * 4, hipMemcpyHostToDevice, s);
+      e = cells_pass_order(ca, P->cell_rank, order, s);  // (the pass's one wait; the plan counts of the pass before have arrived too)
       if (e == hipSuccess) e = launch_cells_plan(ca, 2, s);
       if (e == hipSuccess) e = launch_within_tile(a, std::max(1, std::min(CELL_LISTS, T)), s);
       if (e == hipSuccess) e = hipMemcpyAsync(plan_count.data() + groups_done, ca.count, (size_t)n_group * 4, hipMemcpyDeviceToHost, s);
       groups_done += n_group;
+      st.pass(n_group, T_full, 0, 0);  // (what it visited: the plan's counts, once they have arrived)
     }
     q_off += sg.m;
     if (e != hipSuccess) break;
@@ -185,36 +172,14 @@ int within_core(scann_handle* h, scann_index* ix, const std::vector<Seg>& segs, 
   HIPCHK(h, e_rec);
   for (int64_t i = 0; i < nq; ++i) o.counts[i] = cnt[(size_t)i];
   *o.total = total;
-  for (int32_t c : plan_count) visited += c;
-  ix->stats[0] = groups_done * (int64_t)T_full; ix->stats[1] = 0; ix->stats[2] = visited; ix->stats[3] = groups_done;
+  for (int32_t c : plan_count) st.pass(0, 0, 0, c);
+  st.write(ix);
   if (total == 0 || total > o.cap) return SCANN_OK;  // nothing to fill, or the caller sizes a second call by *total
   std::vector<int32_t> pos_h(o.pos ? 0 : (size_t)total);
   int32_t* pos = o.pos ? o.pos : pos_h.data();
   within_finish(first.data(), nq, rq.data(), rp.data(), rd.data(), total, o.dist2, pos);
-  for (int64_t i = 0; i < total && (o.ids || o.atoms); ++i) {
-    if (o.ids) o.ids[i] = ix->ids[(size_t)pos[i]];
-    if (o.atoms) o.atoms[i] = ix->atoms[(size_t)pos[i]];
-  }
+  name_positions(ix, pos, (size_t)total, nullptr, o.ids, o.atoms);
   return SCANN_OK;
-}
-
-// host or device query rows staged at the index's padded width with their ids, then within_core (search_staged's plan)
-int within_staged(scann_handle* h, scann_index* ix, const float* q, hipMemcpyKind kind, const int64_t* qid, int64_t nq, float radius2, hipStream_t s,
-                  const Out& o) {
-  CallWs ws;
-  RowStage st;
-  int64_t* d_qid;
-  st.take(ws, nq, ix->dim, ix->dim, ix->stride, kind);
-  ws.take(d_qid, qid ? (size_t)nq : 0);
-  HIPCHK(h, ws.alloc());
-  hipError_t e = st.stage_rows(q, s);
-  if (e == hipSuccess && qid) e = hipMemcpyAsync(d_qid, qid, (size_t)nq * 8, hipMemcpyHostToDevice, s);
-  int r = SCANN_OK;
-  if (e == hipSuccess) r = within_core(h, ix, {Seg{st.rows(q), nq, -1}}, qid ? d_qid : nullptr, nq, 0, radius2, s, o);
-  else (void)hipStreamSynchronize(s);
-  ws.release();
-  HIPCHK(h, e);
-  return r;
 }
 
 }  // namespace
@@ -229,7 +194,10 @@ int scann_index_within(scann_handle_t* h, scann_index_t* ix, const float* q, int
   const Out o{cap, counts, total, dist2, pos, ids, atoms};
   if (const int r = check_out(h, "scann_index_within", radius2, o)) return r;
   HIPCHK(h, hipSetDevice(h->device));
-  return within_staged(h, ix, q, hipMemcpyHostToDevice, query_ids, nq, radius2, h->streams[0], o);
+  hipStream_t s = h->streams[0];
+  return staged_queries(h, ix, q, hipMemcpyHostToDevice, query_ids, nq, s, [&](const float* dq, const int64_t* dqid) {
+    return within_core(h, ix, {Seg{dq, nq, -1}}, dqid, nq, 0, radius2, s, o);
+  });
 }
 
 int scann_index_within_rows(scann_handle_t* h, scann_index_t* ix, int64_t first, int64_t n, int32_t upper, float radius2, int64_t cap,
@@ -242,13 +210,10 @@ int scann_index_within_rows(scann_handle_t* h, scann_index_t* ix, int64_t first,
   if (const int r = check_out(h, "scann_index_within_rows", radius2, o)) return r;
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<Seg> segs;  // the queries where they lie, chunk by chunk: rows of the index are padded as queries are
-  for (int64_t done = 0; done < n;) {
-    const int64_t at = first + done;
-    const size_t c = (size_t)(at / ix->chunk_rows);
-    const int64_t r0 = at % ix->chunk_rows, m = std::min<int64_t>(n - done, ix->chunk_rows - r0);
-    segs.push_back(Seg{ix->rows_of(c) + (size_t)r0 * ix->stride, m, at});
-    done += m;
-  }
+  row_runs(ix, first, n, [&](size_t c, int64_t r0, int64_t m, int64_t done) {
+    segs.push_back(Seg{ix->rows_of(c) + (size_t)r0 * ix->stride, m, first + done});
+    return (int)SCANN_OK;
+  });
   return within_core(h, ix, segs, nullptr, n, upper, radius2, h->streams[0], o);
 }
 
@@ -258,20 +223,13 @@ int scann_index_within_batch(scann_handle_t* h, scann_index_t* ix, scann_dbatch_
   if (const int r = check_index(h, ix, "scann_index_within_batch")) return r;
   if (!db) return fail(h, SCANN_ERR_INVALID, "scann_index_within_batch: null argument");
   if (const int r = check_level(h, ix, level, "scann_index_within_batch")) return r;
-  const bool atom = level == SCANN_OUT_AFTER_LC;
-  const int64_t nq = atom ? db->n_atom : db->n_struct;
+  const int64_t nq = level == SCANN_OUT_AFTER_LC ? db->n_atom : db->n_struct;
   if (nq <= 0) return fail(h, SCANN_ERR_INVALID, "scann_index_within_batch: an empty query");
   const Out o{cap, counts, total, dist2, pos, ids, atoms};
   if (const int r = check_out(h, "scann_index_within_batch", radius2, o)) return r;
-  if (!h->loaded) return fail(h, SCANN_ERR_WEIGHTS, "scann_index_within_batch: weights not loaded");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (const int r = forward_and_download(h, db, 0, level, y, ga)) return r;
-  std::vector<int64_t> qid;
-  if (query_ids)
-    if (const int r = expand_ids(h, db, atom, query_ids, 0, qid, nullptr)) return r;
-  // the level's rows are the queries where the forward left them
-  return within_staged(h, ix, atom ? db->out_z : db->out_bf, hipMemcpyDeviceToDevice, query_ids ? qid.data() : nullptr, nq, radius2,
-                       h->streams[db->last_slot], o);
+  return staged_batch_queries(h, ix, db, level, query_ids, y, ga, "scann_index_within_batch", [&](const float* dq, const int64_t* dqid) {
+    return within_core(h, ix, {Seg{dq, nq, -1}}, dqid, nq, 0, radius2, h->streams[db->last_slot], o);
+  });
 }
 
 int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* row_ids, const float* q, int64_t nq, const int64_t* query_ids,

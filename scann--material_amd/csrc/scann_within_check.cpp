@@ -3,43 +3,17 @@
 // code only, no device is touched) and runs it.  Planted cases: exact copies at radius 0, the inclusive boundary, `upper`, query ids,
 // non-finite rows, an empty table, the cap protocol with sentinel-filled arrays, records handed to within_finish in a scrambled order,
 // and the refusals.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "scann_within.cpp"
 
-// what the device half refers to; none of it is called here (dist2_to_rows is the twin's chain: the plain loop of scann_knn.cpp)
+#include "scann_check.h"
+
+// the stubs of its own
 namespace scann {
-hipError_t cached_malloc(void**, size_t) { return hipErrorNotSupported; }
-void cached_free(void*) {}
-int fail(scann_handle*, int code, const std::string&) { return code; }
-int check_index(scann_handle*, const scann_index*, const char*) { return SCANN_ERR_INVALID; }
 int expand_ids(scann_handle*, const scann_dbatch*, bool, const int64_t*, int64_t, std::vector<int64_t>&, std::vector<int32_t>*) { return SCANN_ERR_INVALID; }
-int forward_and_download(scann_handle_t*, scann_dbatch_t*, uint64_t, int32_t, float*, float*) { return SCANN_ERR_INVALID; }
-void dist2_to_rows(const float* q, const float* rows, int64_t n, int64_t d, float* out) {
-  for (int64_t r = 0; r < n; ++r) {
-    float acc = 0.f;
-    for (int64_t j = 0; j < d; ++j) {
-      const float t = q[j] - rows[r * d + j];
-      acc = fmaf(t, t, acc);
-    }
-    out[r] = acc;
-  }
-}
-hipError_t launch_cells_centre(const CellSearchArgs&, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cells_plan(const CellSearchArgs&, int, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_within_tile(const WithinArgs&, int, hipStream_t) { return hipErrorNotSupported; }
 }  // namespace scann
 
 namespace {
-
-int bad = 0;
-unsigned state = 2026u;
-unsigned draw() { state = state * 1664525u + 1013904223u; return (state >> 8) & 0xffffff; }
-
-#define EXPECT(c) do { if (!(c)) ++bad, std::printf("line %d: %s\n", __LINE__, #c); } while (0)
 
 std::vector<float> rows_of(int64_t n, int64_t dim, int levels) {
   std::vector<float> x((size_t)(n * dim));
@@ -103,6 +77,7 @@ Result run(const std::vector<float>& rows, int64_t n, int64_t dim, const std::ve
 }  // namespace
 
 int main() {
+  state = 2026u;
   for (int64_t n : {1, 63, 64, 65, 300})
     for (int64_t dim : {1, 2, 33}) {
       const std::vector<float> rows = rows_of(n, dim, 3), q = rows_of(70, dim, 3);
@@ -174,6 +149,5 @@ int main() {
   EXPECT(scann_within_host(r.data(), 10, 2, nullptr, r.data(), 0, nullptr, nullptr, 0, 1.f, 0, c, &tot, nullptr, nullptr) == SCANN_ERR_INVALID);
   EXPECT(scann_within_host(r.data(), 10, 2, nullptr, r.data(), 10, nullptr, nullptr, 0, 1.f, 0, nullptr, &tot, nullptr, nullptr) == SCANN_ERR_INVALID);
   EXPECT(scann_within_host(r.data(), 10, 2, nullptr, r.data(), 10, nullptr, p, 1, 0.f, 0, c, &tot, nullptr, nullptr) == SCANN_OK);
-  std::printf(bad ? "scann_within_check: %d FAILED\n" : "scann_within_check: ok\n", bad);
-  return bad ? 1 : 0;
+  return finish("scann_within_check");
 }

@@ -245,6 +245,7 @@ def test_python_layer_checks_its_arguments():
 
 
 def test_twin_under_the_sanitizers():
-    """make asan-cells: the stand-alone program drives scann_cells_host and scann_cell_bound under AddressSanitizer + UBSan"""
+    """make asan-cells: the stand-alone program drives scann_cells_host, scann_cell_bound and the searches' shared host pieces
+    (csrc/scann_search.h: query_order, row_runs) under AddressSanitizer + UBSan"""
     r = subprocess.run(["make", "-C", CSRC, "asan-cells"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "scann_cells_check: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
