@@ -1,6 +1,7 @@
 """Seeded batches on the large side of the launch code's size switches, shared by tests/test_sizes_host.py (which pins that they
 cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py, tests/test_gpu_output_sizes.py and
-tests/test_gpu_parity.py (which compare the kernels on them with references).
+tests/test_gpu_parity.py (which compare the kernels on them with references); and batches past 2^31 bytes per tensor, up to the upload
+limit, for tests/test_gpu_large_rows.py.
 
 The launch code picks a template instantiation, tile height, partial-sum partition or reduction kernel by row count; the
 constants below restate those thresholds, each next to the source line it mirrors.  If a threshold moves, the host test fails
@@ -25,6 +26,8 @@ LN_BWD_ONE_GROUP_MAX = 32 * 1536      # scann_train.hip ln_bwd_groups: one 32-ro
 GEN_LN_64_ROWS_MAX = 512 * 64         # scann_generic_train.hip gen_ln_chunks: <= 64 rows per chunk up to this, more above
 UPLOAD_MAX_ATOMS = 60000 // (5 * 4)   # scann_batch.cpp upload_impl: 5 floats of LDS per atom of the largest structure (3,000)
 GEN_BWD_MAX_ATOMS = (65536 // 8 - 4) // 3  # scann_train_host.cpp gen_backward: (3 n + 4) doubles <= 64 KiB (2,729)
+UPLOAD_MAX_ROWS = (1 << 32) // (128 * 4) - 1   # scann_batch.cpp upload_impl: max(atoms, edges) * 128 * 4 < 2^32 (8,388,607 rows)
+SIGNED_OFFSET_ROWS = (1 << 31) // (128 * 4)    # above this many rows a [rows, 128] fp32 tensor passes 2^31 bytes (4,194,304)
 
 
 def wgrad_chunks(rows):
@@ -238,3 +241,58 @@ def upload_tile_rows(pk):
     if small and int(np.diff(pk.edge_offset).max()) > EDGE_TILE_32_MAX_DEGREE:
         rows, _, part, _ = _hip.plan_tiles(pk, 64)
     return rows, int((part >= 0).sum())
+
+
+# ---- batches whose [rows, 128] tensors pass 2^31 bytes, up to the upload limit (tests/test_gpu_large_rows.py) ----
+# Each is a seeded batch above tiled with _hip.concat_packed (NumPy only): (PackedBatch, replicas, the small batch it is made of).
+# A replica's rows in the large batch are the small batch's rows shifted by r * n_atom / r * n_edge, so every per-replica result of
+# the large batch reshapes to [replicas, ...] against the small batch forwarded alone.
+
+LIMIT_FILLER_ATOMS, LIMIT_REPLICAS = 230, 234  # qm9_at_limit: 234 x 35,837 = 8,385,858 edges, the filler brings the other 2,749
+
+
+def replicated(small, n):
+    from scann import _hip
+
+    return _hip.concat_packed([small] * n)
+
+
+def qm9_x118(g_update=True):
+    """qm9_b260 118 times: 563,922 atoms, 4,228,766 edges -- the edge tensors pass 2^31 bytes, the atom tensors do not"""
+    small, _ = qm9_b260(g_update)
+    return replicated(small, 118), 118, small
+
+
+def sparse_x123(g_update=True):
+    """sparse_atoms 123 times: 4,210,413 atoms (isolated ones among them), 6,304,365 edges -- atom and edge tensors pass 2^31 bytes"""
+    small, _ = sparse_atoms(g_update)
+    return replicated(small, 123), 123, small
+
+
+@functools.lru_cache(maxsize=None)
+def limit_filler_data(extra=0):
+    """one structure of 230 atoms: 229 with 12 neighbours each and one with 1 + `extra` -- 2,749 + `extra` edges, every degree given"""
+    degrees = {a: 12 for a in range(LIMIT_FILLER_ATOMS - 1)}
+    degrees[LIMIT_FILLER_ATOMS - 1] = 1 + extra
+    de, dn = np.empty(1, dtype=object), np.empty(1, dtype=object)
+    de[0], dn[0] = hub_structure(np.random.default_rng(2749), LIMIT_FILLER_ATOMS, degrees)
+    return de, dn
+
+
+def limit_filler(g_update=True, extra=0):
+    """the filler structure alone: PackedBatch"""
+    return packed(limit_filler_data(extra), g_update)[0]
+
+
+def qm9_at_limit(g_update=True, extra=0):
+    """qm9_b260 234 times, then the filler structure: n_edge is exactly UPLOAD_MAX_ROWS (+ `extra`).  The filler is last: its edge rows
+    are the last rows below 2^32 bytes, and the spare row behind them ends 4 bytes below 2^32"""
+    from scann import _hip
+
+    small, _ = qm9_b260(g_update)
+    return _hip.concat_packed([small] * LIMIT_REPLICAS + [limit_filler(g_update, extra)]), LIMIT_REPLICAS, small
+
+
+def qm9_over_limit(g_update=True):
+    """qm9_at_limit with one more edge in the filler: the first batch scann_batch_upload refuses"""
+    return qm9_at_limit(g_update, extra=1)

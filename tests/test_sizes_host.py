@@ -26,6 +26,10 @@ def test_thresholds_match_the_launch_code():
     assert "const bool small = E > 0 && E <= 32 * 1024;" in batch and "if (small && max_degree > 32) {" in batch
     assert "if ((size_t)max_atoms * 5 * sizeof(float) > 60000)" in batch
     assert sb.UPLOAD_MAX_ATOMS == 3000 and 3000 * 5 * 4 <= 60000 < 3001 * 5 * 4
+    assert "if ((uint64_t)std::max(A, E) * D * 4 >= (1ull << 32))" in batch and "constexpr int D = 128;" in src("scann_internal.h")
+    assert "scann_batch_upload: more than 8,388,607 atoms or edges in one batch; split it" in batch
+    assert sb.UPLOAD_MAX_ROWS == 8388607 and sb.UPLOAD_MAX_ROWS * 128 * 4 < 1 << 32 <= (sb.UPLOAD_MAX_ROWS + 1) * 128 * 4
+    assert sb.SIGNED_OFFSET_ROWS == 4194304 and sb.SIGNED_OFFSET_ROWS * 128 * 4 == 1 << 31
     assert "db->tile_rows == 32 && db->n_big == 0 && db->max_degree <= 16" in src("scann_train_host.cpp")
     assert "((size_t)3 * db->max_atoms + 4) * sizeof(double) > 65536" in src("scann_train_host.cpp")
     assert sb.GEN_BWD_MAX_ATOMS == 2729 and (3 * 2729 + 4) * 8 <= 65536 < (3 * 2730 + 4) * 8
@@ -130,3 +134,64 @@ def test_sub_batches_of_the_split_sum_are_small(hip_lib):
             sub = slice_packed(pk, lo, hi)
             assert sb.small_side(sub.n_atom, sub.n_edge) and sb.upload_tile_rows(sub) == (32, 0), (name, lo, hi)
             assert _hip.plan_tiles(sub, 32)[0] == 32
+
+
+def _is_replicated(big, n, small, a0=0, e0=0):
+    """structures / atoms / edges of `big` from atom a0 / edge e0 on are `small` n times over, each replica's indices shifted by its rows"""
+    A, E, B = small.n_atom, small.n_edge, small.n_struct
+    a_shift = (a0 + A * np.arange(n, dtype=np.int64))[:, None]
+    e_shift = (e0 + E * np.arange(n, dtype=np.int64))[:, None]
+    s0 = int(np.searchsorted(big.mol_offset, a0))
+    ok = np.array_equal(big.mol_offset[s0 + 1:s0 + 1 + n * B].reshape(n, B), small.mol_offset[1:][None] + a_shift)
+    ok = ok and np.array_equal(big.edge_offset[a0 + 1:a0 + 1 + n * A].reshape(n, A), small.edge_offset[1:][None] + e_shift)
+    ok = ok and np.array_equal(big.edge_col[e0:e0 + n * E].reshape(n, E), small.edge_col[None] + a_shift)
+    ok = ok and np.array_equal(big.atomic[a0:a0 + n * A].reshape(n, A), np.broadcast_to(small.atomic, (n, A)))
+    for name in ("edge_dist", "edge_weight"):
+        ok = ok and np.array_equal(getattr(big, name)[e0:e0 + n * E].reshape(n, E), np.broadcast_to(getattr(small, name), (n, E)))
+    return bool(ok)
+
+
+@pytest.mark.parametrize("g_update", [True, False])
+def test_replicated_batches_pass_two_to_the_31_bytes(hip_lib, g_update):
+    """qm9_x118: only the edge tensors pass 2^31 bytes; sparse_x123: atom and edge tensors both; neither reaches the upload limit; both
+    stay on 64-row tiles without chunk tiles, and every replica is the small batch with its rows shifted"""
+    from scann import _hip
+
+    big, n, small = sb.qm9_x118(g_update)
+    assert n == 118 and (small.n_struct, small.n_atom, small.n_edge) == (260, 4779, 35837)
+    assert (big.n_struct, big.n_atom, big.n_edge) == (118 * 260, 563922, 4228766)
+    assert big.n_atom < sb.SIGNED_OFFSET_ROWS < big.n_edge <= sb.UPLOAD_MAX_ROWS
+    assert big.n_edge * 128 * 4 > 1 << 31 and big.n_edge * 256 * 4 > 1 << 32  # (the 256-wide case: past 2^32 bytes)
+    assert _is_replicated(big, n, small) and sb.upload_tile_rows(big) == (64, 0)
+    assert _hip.plan_tiles_filled(big, 64, 24)[0]  # (best fit saves tiles: a second forward runs on the filled plan)
+    big, n, small = sb.sparse_x123(g_update)
+    assert n == 123 and (small.n_struct, small.n_atom, small.n_edge) == (1900, 34231, 51255)
+    assert (big.n_struct, big.n_atom, big.n_edge) == (123 * 1900, 4210413, 6304365)
+    assert sb.SIGNED_OFFSET_ROWS < big.n_atom < big.n_edge <= sb.UPLOAD_MAX_ROWS
+    assert int((np.diff(big.edge_offset) == 0).sum()) > 123 * 1000
+    assert _is_replicated(big, n, small) and sb.upload_tile_rows(big) == (64, 0)
+    assert not _hip.plan_tiles_filled(big, 64, 24)[0]  # (degrees 0 .. 3: the atom limit closes the tiles of either plan)
+
+
+@pytest.mark.parametrize("g_update", [True, False])
+def test_limit_batches_sit_on_either_side_of_the_upload_limit(hip_lib, g_update):
+    """qm9_at_limit: exactly UPLOAD_MAX_ROWS edges, the filler structure (229 atoms of 12 neighbours, one of 1) last, so that its rows are
+    the last below 2^32 bytes and the spare row behind them ends 4 bytes short of 2^32; qm9_over_limit: one edge more"""
+    from scann import _hip
+    from scann.parallel import slice_packed
+
+    big, n, small = sb.qm9_at_limit(g_update)
+    assert n == 234 and n * small.n_edge == 8385858
+    assert big.n_struct == 234 * 260 + 1 and big.n_atom == 234 * 4779 + 230 and big.n_edge == sb.UPLOAD_MAX_ROWS
+    assert (big.n_edge + 1) * 128 * 4 == 1 << 32  # (the spare row: bytes [2^32 - 512, 2^32))
+    assert big.n_edge * 64 * 4 == (1 << 31) - 256  # (the 64-wide case: the last row of an [E, 64] tensor is the last below 2^31 bytes)
+    assert _is_replicated(big, n, small) and sb.upload_tile_rows(big) == (64, 0) and _hip.plan_tiles_filled(big, 64, 24)[0]
+    filler, last = sb.limit_filler(g_update), slice_packed(big, big.n_struct - 1, big.n_struct)
+    deg = np.diff(filler.edge_offset)
+    assert filler.n_struct == 1 and filler.n_atom == 230 and filler.n_edge == 2749
+    assert (deg[:229] == 12).all() and deg[229] == 1
+    assert _is_replicated(last, 1, filler)
+    over, n2, _ = sb.qm9_over_limit(g_update)
+    assert n2 == 234 and over.n_edge == sb.UPLOAD_MAX_ROWS + 1 and over.n_atom == big.n_atom and over.n_struct == big.n_struct
+    assert np.diff(over.edge_offset)[-1] == 2 and _is_replicated(over, n2, small)
+    assert np.array_equal(over.edge_offset[:-1], big.edge_offset[:-1])
