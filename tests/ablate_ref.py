@@ -7,6 +7,7 @@ with structure s at mol_offset[s]:mol_offset[s + 1].  Test-only."""
 import numpy as np
 
 import scann_oracle as so
+from analysis_checks import rel_err
 
 MODES = ("leave_one_out", "deletion", "insertion")
 
@@ -70,14 +71,6 @@ def ablate(config, weights, z, mol_offset, mode, order, dtype, entries=None):
             keep = np.stack([kept_set(mode, n, np.asarray(order[o0:o1]), e) for e in es])
             out[o0 + np.asarray(es)] = pooled(config, w, zs, keep, dt)
     return out, y
-
-
-def rel_err(got, ref):
-    """tests/test_gpu_outputs.py's"""
-    ref = np.asarray(ref, dtype=np.float64)
-    got = np.asarray(got, dtype=np.float64)
-    scale = max(float(np.sqrt(np.mean(ref * ref))), 1e-30)
-    return float(np.max(np.abs(got - ref) / np.maximum(np.abs(ref), scale)))
 
 
 def check_order(order, ga, mol_offset):

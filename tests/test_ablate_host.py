@@ -10,6 +10,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import ablate_ref
 import scann_oracle as so
 
@@ -102,13 +103,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn()
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, lambda config: _StandIn())
 
 
 def _batch(n=5):
@@ -175,15 +170,14 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
+    h = abi_checks.header()
     assert ("int scann_ablate_pooling(scann_handle_t* h, scann_dbatch_t* db, int32_t mode, float* y, float* ga, float* y_abl, "
             "int32_t* order);") in h
     assert "#define SCANN_ABI_VERSION 1" in h
     for name, v in (("LEAVE_ONE_OUT", 0), ("DELETION", 1), ("INSERTION", 2), ("MAX_ATOMS", _hip.ABLATE_MAX_ATOMS)):
         assert "#define SCANN_ABLATE_%s %d" % (name, v) in h
     assert _hip.ABLATE_MODES == {"leave_one_out": 0, "deletion": 1, "insertion": 2}
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}["scann_ablate_pooling"]
-    assert sig == (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    abi_checks.signatures({"scann_ablate_pooling": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])})
     assert hasattr(hip_lib, "scann_ablate_pooling")
 
 
@@ -194,9 +188,8 @@ def test_null_handle_is_an_error_not_a_crash(hip_lib):
 def test_ablate_kernel_uses_no_scratch(hip_lib):
     """the MFMA kernel of csrc/scann_ablate.hip (and its plain-fp32 twin) spill nothing, read from the built library's kernel descriptors"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "ablate_kernel" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "ablate_kernel" in n}
     assert len(kern) == 2, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import cells_ref
 import kmeans_ref
 import knn_ref
@@ -203,27 +204,25 @@ def test_pruned_search_skips_on_blobs_on_the_host(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for text in ("int scann_index_partition(scann_handle_t* h, scann_index_t* idx, int32_t cells, int32_t max_iter, int64_t* info /* [4] or NULL */);",
-                 "int scann_index_cells_read(scann_handle_t* h, scann_index_t* idx, int64_t* info /* [4] */, float* centres, int32_t* perm, "
-                 "int32_t* first_tile, float* lo, float* hi);",
-                 "int scann_index_search_stats(const scann_index_t* idx, int64_t* out /* [4] */);",
-                 "int scann_index_query_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t k, float* dist2, int64_t* ids, "
-                 "int32_t* atoms, int32_t* pos);",
-                 "int scann_cells_host(const float* rows, int64_t n, int64_t dim, int32_t cells, int32_t max_iter, int64_t* info, float* centres, "
-                 "int32_t* perm, int32_t* first_tile, float* lo, float* hi);",
-                 "double scann_cell_bound(float D, float lo, float hi);", "it doubles the index's device memory",
-                 "g = max((1 - eps) a - (1 + eps) r_hi, (1 - eps) r_lo - (1 + eps) a) - 2^-64", "lb = 0 whenever D or hi is not finite",
-                 "the chain value dist2(q, x) >= lb", "Loose tiles are always visited", "> tau_q, strictly"):
-        assert text in flat, text
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    abi_checks.declared("int scann_index_partition(scann_handle_t* h, scann_index_t* idx, int32_t cells, int32_t max_iter, int64_t* info /* [4] or NULL */);",
+                        "int scann_index_cells_read(scann_handle_t* h, scann_index_t* idx, int64_t* info /* [4] */, float* centres, int32_t* perm, "
+                        "int32_t* first_tile, float* lo, float* hi);",
+                        "int scann_index_search_stats(const scann_index_t* idx, int64_t* out /* [4] */);",
+                        "int scann_index_query_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t k, float* dist2, int64_t* ids, "
+                        "int32_t* atoms, int32_t* pos);",
+                        "int scann_cells_host(const float* rows, int64_t n, int64_t dim, int32_t cells, int32_t max_iter, int64_t* info, float* centres, "
+                        "int32_t* perm, int32_t* first_tile, float* lo, float* hi);",
+                        "double scann_cell_bound(float D, float lo, float hi);", "it doubles the index's device memory",
+                        "g = max((1 - eps) a - (1 + eps) r_hi, (1 - eps) r_lo - (1 + eps) a) - 2^-64", "lb = 0 whenever D or hi is not finite",
+                        "the chain value dist2(q, x) >= lb", "Loose tiles are always visited", "> tau_q, strictly")
     P = C.c_void_p
-    assert sig["scann_index_partition"] == (C.c_int, [P, P, C.c_int32, C.c_int32, P])
-    assert sig["scann_index_cells_read"] == (C.c_int, [P] * 8)
-    assert sig["scann_index_search_stats"] == (C.c_int, [P, P])
-    assert sig["scann_index_query_rows"] == (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P])
-    assert sig["scann_cells_host"] == (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P, P])
-    assert sig["scann_cell_bound"] == (C.c_double, [C.c_float, C.c_float, C.c_float])
+    sig = abi_checks.signatures({
+        "scann_index_partition": (C.c_int, [P, P, C.c_int32, C.c_int32, P]),
+        "scann_index_cells_read": (C.c_int, [P] * 8),
+        "scann_index_search_stats": (C.c_int, [P, P]),
+        "scann_index_query_rows": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P]),
+        "scann_cells_host": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P, P]),
+        "scann_cell_bound": (C.c_double, [C.c_float, C.c_float, C.c_float])})
     for name in ("scann_index_partition", "scann_index_partition_args", "scann_index_cells_read", "scann_index_search_stats", "scann_index_query_rows",
                  "scann_cells_capacity", "scann_cells_host", "scann_cell_bound"):
         assert hasattr(hip_lib, name), name

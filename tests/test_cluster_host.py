@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import kmeans_ref
 import scann_oracle as so
 
@@ -226,22 +227,20 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, const float* init /* [k * dim] or NULL */, "
-                 "const int32_t* init_pos /* [k] positions in pool, or NULL */, int32_t max_iter, int64_t stop_changed, "
-                 "int32_t* labels /* [N] */, float* dist2 /* [N] or NULL */, float* centres /* [k * dim] */, "
-                 "int64_t* sizes /* [k] or NULL */, int32_t* converged /* or NULL */);",
-                 "int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, "
-                 "int64_t stop_changed, int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged);",
-                 "#define SCANN_KMEANS_MAX_K 1024"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int64_t scann_index_kmeans(scann_handle_t* h, scann_index_t* pool, int32_t k, const float* init /* [k * dim] or NULL */, "
+                        "const int32_t* init_pos /* [k] positions in pool, or NULL */, int32_t max_iter, int64_t stop_changed, "
+                        "int32_t* labels /* [N] */, float* dist2 /* [N] or NULL */, float* centres /* [k * dim] */, "
+                        "int64_t* sizes /* [k] or NULL */, int32_t* converged /* or NULL */);",
+                        "int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, "
+                        "int64_t stop_changed, int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged);",
+                        "#define SCANN_KMEANS_MAX_K 1024")
     assert "#define SCANN_ABI_VERSION 1" in h and hip_lib.scann_abi_version() == 1
     assert _hip.KMEANS_MAX_K == 1024
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_kmeans"] == (C.c_int64, [P, P, C.c_int32, P, P, C.c_int32, C.c_int64, P, P, P, P, P])
-    assert sig["scann_kmeans_host"] == (C.c_int64, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int32, C.c_int64, P, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_kmeans": (C.c_int64, [P, P, C.c_int32, P, P, C.c_int32, C.c_int64, P, P, P, P, P]),
+        "scann_kmeans_host": (C.c_int64, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int32, C.c_int64, P, P, P, P, P])})
     assert hasattr(hip_lib, "scann_index_kmeans") and hasattr(hip_lib, "scann_kmeans_host")
 
 
@@ -287,9 +286,8 @@ def test_kmeans_kernels_use_no_scratch_and_keep_their_names_apart(hip_lib):
     """the kernels of csrc/scann_kmeans.hip spill nothing, read from the built library's kernel descriptors; their names stay out of
     the name census the other host tests take"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "kmeans_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "kmeans_" in n}
     for want in ("kmeans_prepare_kernel", "kmeans_gather_kernel", "kmeans_assign_kernel", "kmeans_sum_kernel", "kmeans_finalise_kernel"):
         assert sum(want in n for n in kern) == 1, (want, sorted(kern))
     assert len(kern) == 5, sorted(kern)

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import abi_checks
 import embed_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,19 +141,17 @@ def test_the_c_call_refuses_bad_arguments_itself(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for decl in ("int scann_embed_iterate(scann_handle_t* h, int64_t N, const int64_t* row_first /* [N + 1] */, const int32_t* col /* [E] */, "
-                 "const float* p /* [E] */, float* y /* [N * 2] in/out */, float* u /* [N * 2] in/out */, float* gain /* [N * 2] in/out */, "
-                 "int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out /* [N * 2] or NULL */);",
-                 "int scann_embed_iterate_host(int64_t N, const int64_t* row_first, const int32_t* col, const float* p, float* y, float* u, "
-                 "float* gain, int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out);",
-                 "#define SCANN_EMBED_MAX_ROWS 262144", "#define SCANN_ABI_VERSION 1"):
-        assert decl in flat, decl
+    abi_checks.declared("int scann_embed_iterate(scann_handle_t* h, int64_t N, const int64_t* row_first /* [N + 1] */, const int32_t* col /* [E] */, "
+                        "const float* p /* [E] */, float* y /* [N * 2] in/out */, float* u /* [N * 2] in/out */, float* gain /* [N * 2] in/out */, "
+                        "int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out /* [N * 2] or NULL */);",
+                        "int scann_embed_iterate_host(int64_t N, const int64_t* row_first, const int32_t* col, const float* p, float* y, float* u, "
+                        "float* gain, int32_t n_iter, float exaggeration, float momentum, float lr, double* z_out, float* grad_out);",
+                        "#define SCANN_EMBED_MAX_ROWS 262144", "#define SCANN_ABI_VERSION 1")
     assert _hip.EMBED_MAX_ROWS == 262144 and hip_lib.scann_abi_version() == 1
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L, F, D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.POINTER(C.c_double)
-    assert sig["scann_embed_iterate"] == (C.c_int, [P, L, P, P, P, P, P, P, I, F, F, F, D, P])
-    assert sig["scann_embed_iterate_host"] == (C.c_int, [L, P, P, P, P, P, P, I, F, F, F, D, P])
+    sig = abi_checks.signatures({
+        "scann_embed_iterate": (C.c_int, [P, L, P, P, P, P, P, P, I, F, F, F, D, P]),
+        "scann_embed_iterate_host": (C.c_int, [L, P, P, P, P, P, P, I, F, F, F, D, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
 

@@ -25,6 +25,7 @@ if __name__ == "__main__":  # the child process of the environment-switch tests
 import ablate_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
 from ablate_ref import MODES, rel_err  # noqa: E402
+from analysis_checks import training_twin  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -212,35 +213,18 @@ def test_bitwise_repeat_permutation_and_alone(hip_lib, case):
 def test_training_handle(hip_lib):
     """after two training steps: the result is an inference handle's with the same weights, and weights, gradients and the following
     (deterministic) step are those of a twin that never made the call"""
-    from scann.models.scann_model import HipModel
-
     cfg, w, inputs, pk, _ = setup(kind="qm9", n=8, L=2)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            got = {m: eng.ablate_pooling(rb, m) for m in MODES}
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True)
-            for m in MODES:
-                ref = run(inf, pk, m)
-                assert np.array_equal(got[m]["order"], ref["order"]), m
-                for k in ("y", "ablated", "ga"):  # (the training handle's forward reads the same fp32 master weights' images)
-                    assert np.array_equal(got[m][k].view(np.uint32), ref[k].view(np.uint32)), (m, k)
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for k in ga:
-        assert np.array_equal(ga[k].view(np.uint32), gb[k].view(np.uint32)), k
-        assert np.array_equal(wa[k].view(np.uint32), wb[k].view(np.uint32)), k
-        assert np.array_equal(wa2[k].view(np.uint32), wb2[k].view(np.uint32)), k
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        got = {m: train_model.engine.ablate_pooling(rb, m) for m in MODES}
+        inf, _ = inference()
+        for m in MODES:
+            ref = run(inf, pk, m)
+            assert np.array_equal(got[m]["order"], ref["order"]), m
+            for k in ("y", "ablated", "ga"):  # (the training handle's forward reads the same fp32 master weights' images)
+                assert np.array_equal(got[m][k].view(np.uint32), ref[k].view(np.uint32)), (m, k)
+
+    training_twin(cfg, w, pk, calls)
 
 
 def test_unknown_mode_and_selected_outputs(hip_lib):

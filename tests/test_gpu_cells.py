@@ -23,13 +23,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 import cells_ref  # noqa: E402
 import knn_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
+from analysis_checks import _bits  # noqa: E402
 from test_cells_host import blobs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _bytes_equal(a, b):

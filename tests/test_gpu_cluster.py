@@ -21,7 +21,7 @@ import pytest
 
 import kmeans_ref
 import scann_oracle as so
-from test_gpu_knn import _bits, padded, setup
+from analysis_checks import _bits, make_index, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,13 +33,6 @@ def engine(hip_lib):
     cfg, w, inputs, model = setup(n=4)
     yield model.engine
     model.engine.close()
-
-
-def make_index(eng, rows, ids=None, atoms=None):
-    ix = eng.index_create(rows.shape[1])
-    if len(rows):
-        eng.index_add(ix, rows, ids, atoms)
-    return ix
 
 
 def check_exact(eng, rows, init, max_iter, stop=0, label="", want=None, ix=None):
@@ -224,85 +217,33 @@ def test_cluster_is_the_host_clustering_of_the_models_rows(hip_lib, kind, level)
 # ---- state, errors ----
 
 def test_nothing_else_changes(hip_lib):
-    from scann import _hip
-
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
+    with untouched(model, data) as u:
+        eng, pool = u.eng, u.pool
         first = eng.index_kmeans(pool, np.arange(7) * 3, 6)
-        free0, _ = eng.device_memory()
-        for rep in range(10):
+
+        def call():
             r = eng.index_kmeans(pool, np.arange(7) * 3, 6)
-            kmeans_ref.same(r, first, "repeat")
-            eng.index_kmeans(pool, p0[0][:3], 0)
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+            eng.index_kmeans(pool, u.rows[0][:3], 0)
+            return r
+
+        u.repeat(call, lambda r: kmeans_ref.same(r, first, "repeat"), 10, 16 << 20)
 
 
 def test_training_handle(hip_lib):
     """after two training steps a clustering on the training handle equals the host twin's, and weights, gradients and the following
     (deterministic) step are those of a twin that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows, pos = random_case(900, 128, 11)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            check_exact(eng, rows, pos, 5, label="training handle")
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key  # (the Adam state entered this step)
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        check_exact(eng, rows, pos, 5, label="training handle")
+
+    training_twin(cfg, w, pk, calls)
 
 
 def test_generic_width_handle(hip_lib):

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import embed_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
+from analysis_checks import _bits, setup, training_twin, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -196,54 +196,16 @@ def test_qm9_atom_rows_by_both_routes(hip_lib):
 
 # ---- state ----
 
-def check_nothing_changes(model, data):
+def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        p0 = eng.index_read(pool)
-        st = embed_ref.random_state(len(p0[0]), seed=7)
+    cfg, w, data, model = setup(n=40, seed=2)
+    with untouched(model, data) as u:
+        eng = u.eng
+        st = embed_ref.random_state(len(u.rows[0]), seed=7)
         first = eng.embed_iterate(*st, 3, 12.0, 0.5, 200.0, want_grad=True)
         embed_ref.same_state(first, _hip.embed_iterate_host(*st, 3, 12.0, 0.5, 200.0, want_grad=True), "beside a model's index")
-        free0, _ = eng.device_memory()
-        for rep in range(5):
-            embed_ref.same_state(eng.embed_iterate(*st, 3, 12.0, 0.5, 200.0, want_grad=True), first, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
-
-
-def test_nothing_else_changes(hip_lib):
-    cfg, w, data, model = setup(n=40, seed=2)
-    check_nothing_changes(model, data)
+        u.repeat(lambda: eng.embed_iterate(*st, 3, 12.0, 0.5, 200.0, want_grad=True), lambda r: embed_ref.same_state(r, first, "repeat"), 5, 16 << 20)
     # a whole fit beside an existing index: its rows and the predictions stay
     y0, _ = model.predict(data)
     index = model.build_index(data, level="atom", batch_size=16)
@@ -259,32 +221,17 @@ def test_training_handle(hip_lib):
     """after two training steps the iterations on the training handle equal the host twin's, and weights, gradients and the following
     (deterministic) step are those of a twin that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     st = embed_ref.random_state(900, seed=2)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            embed_ref.same_state(eng.embed_iterate(*st, 3, 12.0, 0.5, 200.0, want_grad=True),
-                                 _hip.embed_iterate_host(*st, 3, 12.0, 0.5, 200.0, want_grad=True), "training handle")
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key  # (the Adam state entered this step)
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        embed_ref.same_state(eng.embed_iterate(*st, 3, 12.0, 0.5, 200.0, want_grad=True),
+                             _hip.embed_iterate_host(*st, 3, 12.0, 0.5, 200.0, want_grad=True), "training handle")
+
+    training_twin(cfg, w, pk, calls)
 
 
 # ---- errors, the CLI ----

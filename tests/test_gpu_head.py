@@ -25,8 +25,7 @@ if __name__ == "__main__":  # the child process of the exact-fp32 test
 import head_ref  # noqa: E402
 import pca_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
+from analysis_checks import _bits, make_index, random_rows, setup, training_twin, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -356,108 +355,52 @@ def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
-        q0 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        t = targets_for(p0[0], 2, seed=7)
+    with untouched(model, data) as u:
+        eng, pool, rb, rows = u.eng, u.pool, u.rb, u.rows[0]
+        t = targets_for(rows, 2, seed=7)
         _, _, _, _, V, S, B, lev0 = head_ref.random_head(8, 128, 6, 4, 2, seed=7)
-        mean, tmean = p0[0].mean(0).astype(np.float32), t.mean(0).astype(np.float32)
+        mean, tmean = rows.mean(0).astype(np.float32), t.mean(0).astype(np.float32)
         first_m = eng.index_fit_moments(pool, t)
         first_l = eng.index_ridge_loo(pool, t, mean, tmean, V, S, B, lev0, np.array([1, 3], np.int32))
-        free0, _ = eng.device_memory()
-        for rep in range(5):
-            pca_ref.same_moments(eng.index_fit_moments(pool, t), first_m, "repeat")
-            head_ref.same_loo(eng.index_ridge_loo(pool, t, mean, tmean, V, S, B, lev0, np.array([1, 3], np.int32)), first_l, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        q1 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        for key in q0:
-            assert np.array_equal(q0[key].view(np.uint8), q1[key].view(np.uint8)), key
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
+
+        def same(r):
+            pca_ref.same_moments(r[0], first_m, "repeat")
+            head_ref.same_loo(r[1], first_l, "repeat")
+
+        u.repeat(lambda: (eng.index_fit_moments(pool, t), eng.index_ridge_loo(pool, t, mean, tmean, V, S, B, lev0, np.array([1, 3], np.int32))),
+                 same, 5, 16 << 20)
+        u.check()
         # head_batch: y is the plain forward's; the selection is put back
         h = random_eval_head(128, 2, 4, seed=1)
         r = eng.head_batch(rb, _hip.OUT_BF_PROPERTY, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"])
-        assert np.array_equal(_bits(r["y"]), _bits(y_first))
-        eng.forward_resident(rb)
-        eng.download(rb)
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        assert np.array_equal(_bits(r["y"]), _bits(u.y_first))
+        u.reforward()
 
 
 def test_training_handle(hip_lib):
     """after two training steps the calls on the training handle equal the host twins', and weights, gradients and the following
     (deterministic) step -- the Adam state entered it -- are those of a twin that never made the calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     args = list(head_ref.random_head(900, 128, 20, 4, 2, seed=8))
     h = random_eval_head(128, 2, 4, seed=2)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, args[0])
-            pca_ref.same_moments(eng.index_fit_moments(ix, args[1]), _hip.moments_host(head_ref.augmented(args[0], args[1])), "training handle")
-            check_loo(eng, ix, args, np.array([0, 3], np.int32), "training handle")
-            ix.free()
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            rb2 = inf.upload(pk)
-            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
-                hb = [e.head_batch(b, level, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"]) for e, b in ((eng, rb), (inf, rb2))]
-                for key in hb[0]:
-                    pca_ref.same(hb[0][key], hb[1][key], "training against inference handle, " + key)
-            rb2.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, args[0])
+        pca_ref.same_moments(eng.index_fit_moments(ix, args[1]), _hip.moments_host(head_ref.augmented(args[0], args[1])), "training handle")
+        check_loo(eng, ix, args, np.array([0, 3], np.int32), "training handle")
+        ix.free()
+        inf_model, rb2 = inference()
+        inf = inf_model.engine
+        for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
+            hb = [e.head_batch(b, level, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"]) for e, b in ((eng, rb), (inf, rb2))]
+            for key in hb[0]:
+                pca_ref.same(hb[0][key], hb[1][key], "training against inference handle, " + key)
+
+    training_twin(cfg, w, pk, calls)
 
 
 # ---- 6. errors, the CLI ----

@@ -20,8 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import hier_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
+from analysis_checks import _bits, make_index, random_rows, same_arrays, setup, training_twin, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -365,58 +364,12 @@ def test_generic_width_handle(hip_lib):
 
 
 def test_nothing_else_changes(hip_lib):
-    from scann import _hip
-
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
-        q0 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        core = core2_of(eng, pool, p0[0], 4)
+    with untouched(model, data) as u:
+        eng, pool = u.eng, u.pool
+        core = core2_of(eng, pool, u.rows[0], 4)
         first = eng.index_mst(pool, core)
-        free0, _ = eng.device_memory()
-        for rep in range(5):
-            same_tree(eng.index_mst(pool, core), first, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        q1 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        for key in q0:
-            assert np.array_equal(q0[key].view(np.uint8), q1[key].view(np.uint8)), key
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
-        assert free0 - eng.device_memory()[0] <= 16 << 20  # nothing was taken from the device that did not come back
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        u.repeat(lambda: eng.index_mst(pool, core), lambda r: same_tree(r, first, "repeat"), 5, 16 << 20)
 
 
 def test_training_handle(hip_lib):
@@ -424,65 +377,44 @@ def test_training_handle(hip_lib):
     weights, gradients and the following (deterministic) step -- the Adam state entered it -- are those of a handle that never made the
     calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows = random_rows(900, 128, seed=8)
-    res = []
-    for i in range(2):
-        train_model = HipModel(cfg, w, device=0, deterministic=True)
-        eng = train_model.engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, rows)
-            core = core2_of(eng, ix, rows, 5)
-            want = _hip.mst_host(rows, core)
-            same_tree(eng.index_mst(ix, core), want, "training handle")
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            ix2 = make_index(inf, rows)
-            same_tree(inf.index_mst(ix2, core), want, "inference handle")
-            rb2 = inf.upload(pk)
-            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):  # attach's device call, k = 1
-                db = [e.index_query_batch(x, b, level, 1) for e, x, b in ((eng, ix, rb), (inf, ix2, rb2))]
-                for key in db[0]:
-                    assert np.array_equal(db[0][key].view(np.uint8), db[1][key].view(np.uint8)), "training against inference handle, " + key
-            rb2.free()
-            ix.free()
-            ix2.free()
-            # HipModel.attach itself on the training handle: the inference model's answer, and the rule's labels
-            from scann.models import LatentIndex
-            from scann.models import latent_index as li
 
-            inf_model = HipModel(cfg, eng.get_weights(), device=0, infer=True)
-            _, _, level_rows = level_rows_of(inf_model.engine, rb3 := inf_model.engine.upload(pk))
-            rb3.free()
-            pool_rows = np.concatenate([level_rows["atom"][::2], rows[:200]])
-            _, h = li.hierarchy_rows_host(pool_rows, min_samples=3, level="atom")
-            att = []
-            for m_ in (train_model, inf_model):
-                lat = LatentIndex(m_, "atom").add_rows(pool_rows)
-                att.append(m_.attach(pk, h, lat, 4))
-                lat.free()
-            for key in att[0]:
-                assert np.array_equal(att[0][key].view(np.uint8), att[1][key].view(np.uint8)), "attach on the training handle, " + key
-            want_label, want_pos, _ = attach_rule(level_rows["atom"], pool_rows, h, h.clusters(4))
-            assert np.array_equal(att[0]["label"], want_label) and np.array_equal(att[0]["nearest_position"], want_pos)
-            assert (att[0]["nearest_distance"][::2] == 0).all()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, rows)
+        core = core2_of(eng, ix, rows, 5)
+        want = _hip.mst_host(rows, core)
+        same_tree(eng.index_mst(ix, core), want, "training handle")
+        inf_model, rb2 = inference()
+        inf = inf_model.engine
+        ix2 = make_index(inf, rows)
+        same_tree(inf.index_mst(ix2, core), want, "inference handle")
+        for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):  # attach's device call, k = 1
+            db = [e.index_query_batch(x, b, level, 1) for e, x, b in ((eng, ix, rb), (inf, ix2, rb2))]
+            same_arrays(db[0], db[1], "training against inference handle")
+        ix.free()
+        ix2.free()
+        # HipModel.attach itself on the training handle: the inference model's answer, and the rule's labels
+        from scann.models import LatentIndex
+        from scann.models import latent_index as li
+
+        _, _, level_rows = level_rows_of(inf, rb2)
+        pool_rows = np.concatenate([level_rows["atom"][::2], rows[:200]])
+        _, h = li.hierarchy_rows_host(pool_rows, min_samples=3, level="atom")
+        att = []
+        for m_ in (train_model, inf_model):
+            lat = LatentIndex(m_, "atom").add_rows(pool_rows)
+            att.append(m_.attach(pk, h, lat, 4))
+            lat.free()
+        same_arrays(att[0], att[1], "attach on the training handle")
+        want_label, want_pos, _ = attach_rule(level_rows["atom"], pool_rows, h, h.clusters(4))
+        assert np.array_equal(att[0]["label"], want_label) and np.array_equal(att[0]["nearest_position"], want_pos)
+        assert (att[0]["nearest_distance"][::2] == 0).all()
+
+    training_twin(cfg, w, pk, calls)
 
 
 # ---- 5. errors, the CLI, the crescents ----

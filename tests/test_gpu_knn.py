@@ -23,27 +23,9 @@ if __name__ == "__main__":  # the child process of the environment-switch tests
 
 import knn_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
+from analysis_checks import _bits, amask_of, padded, setup, steady_memory, training_twin  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def padded(kind, n, seed, cfg):
-    inputs, _ = so.pad_batch(*so.synth_dataset(n, seed, kind=kind), g_update=cfg["model"]["g_update"])
-    return {k: np.array(v) for k, v in inputs.items()}
-
-
-def setup(kind="qm9", n=24, seed=0, infer=True, **over):
-    """as tests/test_gpu_rollout.py::setup builds its model and batch"""
-    from scann.models.scann_model import HipModel
-
-    cfg = so.default_config(kind)
-    cfg["model"].update(over)
-    w = so.init_weights(cfg, 1234, perturb=True)
-    return cfg, w, padded(kind, n, seed, cfg), HipModel(cfg, w, device=0, infer=infer)
 
 
 @pytest.fixture(scope="module")
@@ -51,10 +33,6 @@ def engine(hip_lib):
     cfg, w, inputs, model = setup(n=4)
     yield model.engine
     model.engine.close()
-
-
-def amask_of(inputs):
-    return np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
 
 
 def check_exact(eng, ix, rows, ids, atoms, q, k, label, query_ids=None):
@@ -458,43 +436,25 @@ def test_training_handle(hip_lib):
     """after two training steps: the index and the neighbours are an inference handle's with the same weights, and weights, gradients
     and the following (deterministic) step are those of a twin that never made the calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
-    pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            rb2 = inf.upload(pk)
-            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
-                a, b = eng.index_create(128), inf.index_create(128)
-                eng.index_add_batch(a, rb, level, np.arange(8))
-                inf.index_add_batch(b, rb2, level, np.arange(8))
-                ra, rb_ = eng.index_read(a), inf.index_read(b)
-                assert np.array_equal(_bits(ra[0]), _bits(rb_[0])) and np.array_equal(ra[1], rb_[1]) and np.array_equal(ra[2], rb_[2])
-                qa, qb = eng.index_query_batch(a, rb, level, 3, np.arange(8)), inf.index_query_batch(b, rb2, level, 3, np.arange(8))
-                for key in qa:
-                    assert np.array_equal(qa[key], qb[key]) and qa[key].dtype == qb[key].dtype, key
-                a.free()
-                b.free()
-            rb2.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng, (inf_model, rb2) = train_model.engine, inference()
+        inf = inf_model.engine
+        for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
+            a, b = eng.index_create(128), inf.index_create(128)
+            eng.index_add_batch(a, rb, level, np.arange(8))
+            inf.index_add_batch(b, rb2, level, np.arange(8))
+            ra, rb_ = eng.index_read(a), inf.index_read(b)
+            assert np.array_equal(_bits(ra[0]), _bits(rb_[0])) and np.array_equal(ra[1], rb_[1]) and np.array_equal(ra[2], rb_[2])
+            qa, qb = eng.index_query_batch(a, rb, level, 3, np.arange(8)), inf.index_query_batch(b, rb2, level, 3, np.arange(8))
+            for key in qa:
+                assert np.array_equal(qa[key], qb[key]) and qa[key].dtype == qb[key].dtype, key
+            a.free()
+            b.free()
+
+    training_twin(cfg, w, _hip.pack_inputs(data), calls)
 
 
 def test_repeated_calls_do_not_eat_device_memory(hip_lib):
@@ -506,17 +466,17 @@ def test_repeated_calls_do_not_eat_device_memory(hip_lib):
     ix = eng.index_create(128)
     eng.index_add_batch(ix, rb, _hip.OUT_AFTER_LC)
     first = eng.index_query_batch(ix, rb, _hip.OUT_AFTER_LC, 5)
-    free0, _ = eng.device_memory()
-    for rep in range(30):
+
+    def call(rep):
         r = eng.index_query_batch(ix, rb, _hip.OUT_AFTER_LC, 5)
         assert np.array_equal(r["position"], first["position"])
         tmp = eng.index_create(128)
         eng.index_add_batch(tmp, rb, _hip.OUT_BF_PROPERTY)
         tmp.free()
-    free1, _ = eng.device_memory()
+
+    steady_memory(eng, call, 30, 96 << 20)  # (one 64 MiB chunk of the temporary index may rest in the block cache)
     rb.free()
     ix.free()
-    assert free0 - free1 <= 96 << 20, (free0, free1)  # (one 64 MiB chunk of the temporary index may rest in the block cache)
 
 
 def test_save_and_load_on_the_device(hip_lib, tmp_path):

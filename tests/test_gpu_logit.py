@@ -24,8 +24,7 @@ if __name__ == "__main__":  # the child process of the exact-fp32 test
 import logit_ref  # noqa: E402
 import pca_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
+from analysis_checks import _bits, make_index, random_rows, setup, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -237,61 +236,19 @@ def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        p0 = eng.index_read(pool)
-        q0 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        N = len(p0[0])
-        _, lab, _, U, fold, F, pof = logit_ref.random_pass(N, 128, 3, 5, 4, seed=7, planted=False)
-        mean = p0[0].mean(0).astype(np.float32)
+    with untouched(model, data) as u:
+        eng, pool, rb, rows = u.eng, u.pool, u.rb, u.rows[0]
+        _, lab, _, U, fold, F, pof = logit_ref.random_pass(len(rows), 128, 3, 5, 4, seed=7, planted=False)
+        mean = rows.mean(0).astype(np.float32)
         first = eng.index_logit_pass(pool, lab, mean, U, fold, F, pof)
-        logit_ref.same_pass(first, _hip.logit_pass_host(p0[0], lab, mean, U, fold, F, pof), "model rows")
-        free0, _ = eng.device_memory()
-        for rep in range(5):
-            logit_ref.same_pass(eng.index_logit_pass(pool, lab, mean, U, fold, F, pof), first, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        q1 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        for key in q0:
-            assert np.array_equal(q0[key].view(np.uint8), q1[key].view(np.uint8)), key
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
+        logit_ref.same_pass(first, _hip.logit_pass_host(rows, lab, mean, U, fold, F, pof), "model rows")
+        u.repeat(lambda: eng.index_logit_pass(pool, lab, mean, U, fold, F, pof), lambda r: logit_ref.same_pass(r, first, "repeat"), 5, 16 << 20)
+        u.check()
         # logit_head_batch: y is the plain forward's; the selection is put back
         hm, hw = random_class_head(128, 4, seed=1)
         r = eng.logit_head_batch(rb, _hip.OUT_BF_PROPERTY, hm, hw)
-        assert np.array_equal(_bits(r["y"]), _bits(y_first))
-        eng.forward_resident(rb)
-        eng.download(rb)
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        assert np.array_equal(_bits(r["y"]), _bits(u.y_first))
+        u.reforward()
 
 
 # ---- 5. errors, the CLI ----

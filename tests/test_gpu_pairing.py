@@ -27,7 +27,8 @@ if __name__ == "__main__":  # the child process of the environment-switch tests
 import pairing_ref  # noqa: E402
 import rank_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_match import amask_of, atom_rows, firsts, ids_of, padded, setup  # noqa: E402
+from analysis_checks import amask_of, padded, setup, training_twin  # noqa: E402
+from test_gpu_match import atom_rows, firsts, ids_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -537,29 +538,25 @@ def test_under_an_environment_switch(hip_lib, switch):
 
 
 def test_training_handle(hip_lib):
-    """after a training step the pairings are an inference handle's with the same weights, and the weights are untouched"""
+    """after two training steps the pairings are an inference handle's with the same weights, and weights, gradients and the following
+    (deterministic) step are those of a twin that never made the calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
-    pk = _hip.pack_inputs(data)
-    eng = HipModel(cfg, w, device=0, deterministic=True).engine
-    eng.train_begin()
-    rb = eng.upload(pk)
-    eng.train_step(rb, np.linspace(-1, 1, pk.n_struct).astype(np.float32), 1e-3, dropout=0.1, seed=3)
-    w1 = {k: v.copy() for k, v in eng.get_weights().items()}
-    inf = HipModel(cfg, w1, device=0, infer=True).engine
-    rb2 = inf.upload(pk)
-    a, b = eng.index_create(128), inf.index_create(128)
-    eng.index_add_batch(a, rb, _hip.OUT_AFTER_LC, np.arange(8))
-    inf.index_add_batch(b, rb2, _hip.OUT_AFTER_LC, np.arange(8))
-    qa, qb = eng.index_pairing_batch(a, rb, 3, 6, "chamfer", np.arange(8)), inf.index_pairing_batch(b, rb2, 3, 6, "chamfer", np.arange(8))
-    for key in qa:
-        assert qa[key].tobytes() == qb[key].tobytes() and qa[key].dtype == qb[key].dtype, key
-    for k, v in eng.get_weights().items():
-        assert v.tobytes() == w1[k].tobytes(), k
-    for h in (a, b, rb, rb2):
-        h.free()
+
+    def calls(train_model, rb, inference):
+        eng, (inf_model, rb2) = train_model.engine, inference()
+        inf = inf_model.engine
+        a, b = eng.index_create(128), inf.index_create(128)
+        eng.index_add_batch(a, rb, _hip.OUT_AFTER_LC, np.arange(8))
+        inf.index_add_batch(b, rb2, _hip.OUT_AFTER_LC, np.arange(8))
+        qa, qb = eng.index_pairing_batch(a, rb, 3, 6, "chamfer", np.arange(8)), inf.index_pairing_batch(b, rb2, 3, 6, "chamfer", np.arange(8))
+        for key in qa:
+            assert qa[key].tobytes() == qb[key].tobytes() and qa[key].dtype == qb[key].dtype, key
+        a.free()
+        b.free()
+
+    training_twin(cfg, w, _hip.pack_inputs(data), calls)
 
 
 def test_cli_writes_the_pairs(hip_lib, tmp_path):

@@ -18,7 +18,7 @@ import pytest
 
 import pca_ref
 import scann_oracle as so
-from test_gpu_knn import _bits, setup
+from analysis_checks import _bits, make_index, random_rows, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,22 +30,6 @@ def engine(hip_lib):
     cfg, w, inputs, model = setup(n=4)
     yield model.engine
     model.engine.close()
-
-
-def make_index(eng, rows):
-    ix = eng.index_create(rows.shape[1])
-    if len(rows):
-        eng.index_add(ix, rows)
-    return ix
-
-
-def random_rows(N, dim, seed=None):
-    """columns of very different scale and offset, a few duplicated rows"""
-    rng = np.random.default_rng(N * 7 + dim * 3 if seed is None else seed)
-    rows = (rng.standard_normal((N, dim)) * rng.uniform(0.01, 30, dim) + rng.standard_normal(dim) * 5).astype(np.float32)
-    if N >= 100:
-        rows[N // 2:N // 2 + 4] = rows[3]
-    return rows
 
 
 def random_projection(dim, m, seed=0):
@@ -286,60 +270,23 @@ def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
     mean, comp, scale = random_projection(128, 5)
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
+    with untouched(model, data) as u:
+        eng, pool, rb = u.eng, u.pool, u.rb
         first = eng.index_moments(pool)
         first_p = eng.index_project(pool, mean, comp, scale)
-        free0, _ = eng.device_memory()
-        for rep in range(10):
-            pca_ref.same_moments(eng.index_moments(pool), first, "repeat")
-            pca_ref.same_projection(eng.index_project(pool, mean, comp, scale), first_p, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
+
+        def same(r):
+            pca_ref.same_moments(r[0], first, "repeat")
+            pca_ref.same_projection(r[1], first_p, "repeat")
+
+        u.repeat(lambda: (eng.index_moments(pool), eng.index_project(pool, mean, comp, scale)), same, 10, 16 << 20)
+        u.check()
         # project_batch: y and ga are those of a plain forward, the rows those of the pool; the selection is put back
         r = eng.project_batch(rb, _hip.OUT_AFTER_LC, mean, comp, scale)
-        assert np.array_equal(_bits(r["y"]), _bits(y_first))
+        assert np.array_equal(_bits(r["y"]), _bits(u.y_first))
         pca_ref.same_projection({k: r[k] for k in first_p}, first_p, "project_batch")
-        eng.forward_resident(rb)
-        eng.download(rb)
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        u.reforward()
 
 
 def test_device_memory_after_free(hip_lib):
@@ -372,54 +319,38 @@ def test_training_handle(hip_lib):
     """after two training steps the moments and a projection on the training handle equal the host twins', and weights, gradients and
     the following (deterministic) step are those of a twin that never made the calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows = random_rows(900, 128)
     mean, comp, scale = random_projection(128, 4)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, rows)
-            pca_ref.same_moments(eng.index_moments(ix), _hip.moments_host(rows), "training handle")
-            pca_ref.same_projection(eng.index_project(ix, mean, comp, scale), _hip.project_host(rows, mean, comp, scale), "training handle")
-            ix.free()
-            # project_batch: what an inference handle with the same weights gives, y and ga those of its forward + download, and the
-            # projection of the level's rows as add_batch stores them
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            rb2 = inf.upload(pk)
-            inf.forward_resident(rb2)
-            y_inf, ga_inf = inf.download(rb2)
-            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
-                r, r_inf = eng.project_batch(rb, level, mean, comp, scale), inf.project_batch(rb2, level, mean, comp, scale)
-                for key in r:
-                    pca_ref.same(r[key], r_inf[key], "training against inference handle, " + key)
-                pca_ref.same(r["y"], y_inf, "y")
-                pca_ref.same(r["ga"], ga_inf, "ga")
-                tmp = eng.index_create(128)
-                eng.index_add_batch(tmp, rb, level)
-                level_rows = eng.index_read(tmp)[0]
-                tmp.free()
-                assert len(level_rows) == (pk.n_atom if level == _hip.OUT_AFTER_LC else pk.n_struct)
-                pca_ref.same_projection({k: r[k] for k in ("coords", "md2", "dist2")}, _hip.project_host(level_rows, mean, comp, scale), "project_batch")
-            rb2.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key  # (the Adam state entered this step)
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, rows)
+        pca_ref.same_moments(eng.index_moments(ix), _hip.moments_host(rows), "training handle")
+        pca_ref.same_projection(eng.index_project(ix, mean, comp, scale), _hip.project_host(rows, mean, comp, scale), "training handle")
+        ix.free()
+        # project_batch: what an inference handle with the same weights gives, y and ga those of its forward + download, and the
+        # projection of the level's rows as add_batch stores them
+        inf_model, rb2 = inference()
+        inf = inf_model.engine
+        inf.forward_resident(rb2)
+        y_inf, ga_inf = inf.download(rb2)
+        for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
+            r, r_inf = eng.project_batch(rb, level, mean, comp, scale), inf.project_batch(rb2, level, mean, comp, scale)
+            for key in r:
+                pca_ref.same(r[key], r_inf[key], "training against inference handle, " + key)
+            pca_ref.same(r["y"], y_inf, "y")
+            pca_ref.same(r["ga"], ga_inf, "ga")
+            tmp = eng.index_create(128)
+            eng.index_add_batch(tmp, rb, level)
+            level_rows = eng.index_read(tmp)[0]
+            tmp.free()
+            assert len(level_rows) == (pk.n_atom if level == _hip.OUT_AFTER_LC else pk.n_struct)
+            pca_ref.same_projection({k: r[k] for k in ("coords", "md2", "dist2")}, _hip.project_host(level_rows, mean, comp, scale), "project_batch")
+
+    training_twin(cfg, w, pk, calls)
 
 
 def test_generic_width_handle(hip_lib):

@@ -18,8 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import rank_ref as rr  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
+from analysis_checks import make_index, random_rows, setup, training_twin, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -210,82 +209,30 @@ def test_the_search_places_have_their_ranks(engine):
 # ---- 6. state ----
 
 def test_nothing_else_changes(hip_lib):
-    from scann import _hip
-
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        p0 = eng.index_read(pool)
+    with untouched(model, data) as u:
+        eng, pool = u.eng, u.pool
         probe = rr.probe_lists(len(pool), len(pool), 31, seed=9)
-        first = check_pool(eng, pool, p0[0], probe, label="the model's rows")
-        free0, _ = eng.device_memory()
-        for rep in range(4):
-            rr.same(eng.index_ranks(pool, probe, dist2=True), first, "repeat %d" % rep)
-        assert free0 - eng.device_memory()[0] <= 16 << 20  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for x, y_ in zip(p0, p1):
-            assert x.dtype == y_.dtype and np.array_equal(x.view(np.uint8), y_.view(np.uint8))
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        first = check_pool(eng, pool, u.rows[0], probe, label="the model's rows")
+        u.repeat(lambda: eng.index_ranks(pool, probe, dist2=True), lambda r: rr.same(r, first, "repeat"), 4, 16 << 20)
 
 
 def test_training_handle(hip_lib):
     """after two training steps the call on the training handle equals the twin, and weights, gradients and the following
     (deterministic) step are those of a twin handle that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows = rr.pathological_pool(700, 128, seed=3)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, rows)
-            check_pool(eng, ix, rows, rr.probe_lists(700, 700, 31, seed=4), label="training handle")
-            ix.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, rows)
+        check_pool(eng, ix, rows, rr.probe_lists(700, 700, 31, seed=4), label="training handle")
+        ix.free()
+
+    training_twin(cfg, w, pk, calls)
 
 
 def test_generic_width_handle(hip_lib):

@@ -26,9 +26,8 @@ import head_ref  # noqa: E402
 import pca_ref  # noqa: E402
 import rbf_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
+from analysis_checks import _bits, make_index, random_rows, setup, training_twin, untouched  # noqa: E402
 from test_gpu_head import random_eval_head, targets_for  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -348,107 +347,46 @@ def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
-        q0 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        Z, gamma = landmarks_for(p0[0], 70)
+    with untouched(model, data) as u:
+        eng, pool, rb = u.eng, u.pool, u.rb
+        Z, gamma = landmarks_for(u.rows[0], 70)
         first = features(eng, pool, Z, gamma)[0]
-        free0, _ = eng.device_memory()
-        for rep in range(5):
-            pca_ref.same(features(eng, pool, Z, gamma)[0], first, "repeat")
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their chunks and workspace from the block cache
-        p1 = eng.index_read(pool)
-        for a, b in zip(p0, p1):
-            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        q1 = eng.index_query(pool, p0[0][:9] + np.float32(0.01), 3)
-        for key in q0:
-            assert np.array_equal(q0[key].view(np.uint8), q1[key].view(np.uint8)), key
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
+        u.repeat(lambda: features(eng, pool, Z, gamma)[0], lambda r: pca_ref.same(r, first, "repeat"), 5, 16 << 20)
+        u.check()
         # rbf_head_batch: y is the plain forward's; the selection is put back
         h = random_eval_head(6, 2, 4, seed=1)
         Zs = np.random.default_rng(0).standard_normal((6, 128)).astype(np.float32)
         r = eng.rbf_head_batch(rb, _hip.OUT_BF_PROPERTY, Zs, 0.01, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"])
-        assert np.array_equal(_bits(r["y"]), _bits(y_first))
-        eng.forward_resident(rb)
-        eng.download(rb)
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+        assert np.array_equal(_bits(r["y"]), _bits(u.y_first))
+        u.reforward()
 
 
 def test_training_handle(hip_lib):
     """after two training steps the calls on the training handle equal the host twin's and an inference handle's, and weights, gradients
     and the following (deterministic) step -- the Adam state entered it -- are those of a twin that never made the calls"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows = random_rows(900, 128, seed=8)
     Z, gamma = landmarks_for(rows, 40)
     h = random_eval_head(5, 2, 4, seed=2)
     Zs = np.random.default_rng(1).standard_normal((5, 128)).astype(np.float32)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, rows)
-            pca_ref.same(features(eng, ix, Z, gamma)[0], _hip.rbf_features_host(rows, Z, gamma), "training handle")
-            ix.free()
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            rb2 = inf.upload(pk)
-            for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
-                hb = [e.rbf_head_batch(b, level, Zs, 0.01, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"])
-                      for e, b in ((eng, rb), (inf, rb2))]
-                for key in hb[0]:
-                    pca_ref.same(hb[0][key], hb[1][key], "training against inference handle, " + key)
-            rb2.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, rows)
+        pca_ref.same(features(eng, ix, Z, gamma)[0], _hip.rbf_features_host(rows, Z, gamma), "training handle")
+        ix.free()
+        inf_model, rb2 = inference()
+        inf = inf_model.engine
+        for level in (_hip.OUT_BF_PROPERTY, _hip.OUT_AFTER_LC):
+            hb = [e.rbf_head_batch(b, level, Zs, 0.01, h["mean"], h["tmean"], h["weights"], h["components"], h["scale"], h["lev0"])
+                  for e, b in ((eng, rb), (inf, rb2))]
+            for key in hb[0]:
+                pca_ref.same(hb[0][key], hb[1][key], "training against inference handle, " + key)
+
+    training_twin(cfg, w, pk, calls)
 
 
 # ---- 5. errors, the CLI ----

@@ -23,17 +23,11 @@ if __name__ == "__main__":  # the child process of the environment-switch test
 
 import rollout_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
+from analysis_checks import _bits, rel_err, steady_memory, training_twin  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -24
-
-
-def rel_err(got, ref):  # tests/test_gpu_outputs.py
-    ref = np.asarray(ref, dtype=np.float64)
-    got = np.asarray(got, dtype=np.float64)
-    scale = max(float(np.sqrt(np.mean(ref * ref))), 1e-30)
-    return float(np.max(np.abs(got - ref) / np.maximum(np.abs(ref), scale)))
 
 
 def big220_data():
@@ -185,10 +179,6 @@ def test_y_and_ga_are_the_forwards_and_rows_sum_to_one(hip_lib, mk):
         assert np.max(np.abs(s - ga.astype(np.float64)[..., 0].sum(1))) <= bnd + (amask.sum(1).max() + 1) * EPS
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.mark.parametrize("mk", [dict(n=8), dict(n=8, seed=41, local_dim=64, num_head=4, global_dim=96, dense_out=32), dict(data="big220")],
                          ids=["qm9", "generic", "big220"])
 def test_bitwise_repeat_alone_permuted_matrix_and_packed(hip_lib, mk):
@@ -282,49 +272,30 @@ def test_repeated_calls_do_not_eat_device_memory(hip_lib):
     eng = model.engine
     rb = eng.upload(_hip.pack_inputs(inputs))
     first = eng.attention_rollout(rb)
-    free0, _ = eng.device_memory()
-    for rep in range(50):
+
+    def call(rep):
         r = eng.attention_rollout(rb, matrix=rep % 2 == 0)
         assert np.array_equal(_bits(r["attribution"]), _bits(first["attribution"]))
-    free1, _ = eng.device_memory()
+
+    steady_memory(eng, call, 50, 32 << 20)  # (the slack of test_repeated_predicts_with_outputs_do_not_eat_device_memory)
     rb.free()
-    assert free0 - free1 <= 32 << 20, (free0, free1)  # (the slack of test_repeated_predicts_with_outputs_do_not_eat_device_memory)
 
 
 def test_training_handle(hip_lib):
     """after two training steps: the result is an inference handle's with the same weights, and weights, gradients and the following
     (deterministic) step are those of a twin that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, inputs, _ = setup(n=8, seed=5, L=2)
-    pk = _hip.pack_inputs(inputs)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            got = eng.attention_rollout(rb)
-            inf = HipModel(cfg, eng.get_weights(), device=0, infer=True).engine
-            rb2 = inf.upload(pk)
-            ref = inf.attention_rollout(rb2)
-            rb2.free()
-            for k in ("y", "ga", "attribution", "rollout"):
-                assert np.array_equal(_bits(got[k]), _bits(ref[k])), k
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for k in ga:
-        assert np.array_equal(_bits(ga[k]), _bits(gb[k])), k
-        assert np.array_equal(_bits(wa[k]), _bits(wb[k])), k
-        assert np.array_equal(_bits(wa2[k]), _bits(wb2[k])), k
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        got = train_model.engine.attention_rollout(rb)
+        inf_model, rb2 = inference()
+        ref = inf_model.engine.attention_rollout(rb2)
+        for k in ("y", "ga", "attribution", "rollout"):
+            assert np.array_equal(_bits(got[k]), _bits(ref[k])), k
+
+    training_twin(cfg, w, _hip.pack_inputs(inputs), calls)
 
 
 def test_limit_on_atoms_per_structure(hip_lib):

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_knn import setup  # noqa: E402
+from analysis_checks import setup  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -19,7 +19,7 @@ import pytest
 
 import kcenter_ref
 import scann_oracle as so
-from test_gpu_knn import _bits, padded, setup
+from analysis_checks import _bits, make_index, padded, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,13 +31,6 @@ def engine(hip_lib):
     cfg, w, inputs, model = setup(n=4)
     yield model.engine
     model.engine.close()
-
-
-def make_index(eng, rows, ids=None, atoms=None):
-    ix = eng.index_create(rows.shape[1])
-    if len(rows):
-        eng.index_add(ix, rows, ids, atoms)
-    return ix
 
 
 def check_exact(eng, rows, ref, m, stop=0.0, ids=None, atoms=None, label=""):
@@ -258,91 +251,45 @@ def test_select_diverse_is_the_host_selection_on_the_models_rows(hip_lib, kind, 
 # ---- state, errors ----
 
 def test_nothing_else_changes(hip_lib):
-    from scann import _hip
-
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool, ref = eng.index_create(128), eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.index_add(ref, eng.index_read(pool)[0][:50] + np.float32(0.125))
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0, r0 = eng.index_read(pool), eng.index_read(ref)
+    with untouched(model, data) as u:
+        eng, pool = u.eng, u.pool
+        ref = make_index(eng, u.rows[0][:50] + np.float32(0.125))
+        r0 = eng.index_read(ref)
         first = eng.index_select(pool, ref, 64)
-        free0, _ = eng.device_memory()
-        for rep in range(20):
+
+        def call():
             r = eng.index_select(pool, ref, 64)
-            assert np.array_equal(r["position"], first["position"]) and np.array_equal(_bits(r["radius2"]), _bits(first["radius2"]))
             eng.index_select(pool, None, 3, 0.5)
-        free1, _ = eng.device_memory()
-        assert free0 - free1 <= 16 << 20, (free0, free1)  # repeated calls take their workspace from the block cache
-        p1, r1 = eng.index_read(pool), eng.index_read(ref)
-        for a, b in zip(p0 + r0, p1 + r1):
+            return r
+
+        def same(r):
+            assert np.array_equal(r["position"], first["position"]) and np.array_equal(_bits(r["radius2"]), _bits(first["radius2"]))
+
+        u.repeat(call, same, 20, 16 << 20)
+        for a, b in zip(r0, eng.index_read(ref)):  # the reference index as well
             assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-        assert len(pool) == len(p0[0]) and len(ref) == 50
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
+        assert len(ref) == 50
         ref.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
 
 
 def test_training_handle(hip_lib):
     """after two training steps a selection on the training handle equals the host twin's, and weights, gradients and the following
     (deterministic) step are those of a twin that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rng = np.random.default_rng(2)
     rows = rng.standard_normal((900, 128)).astype(np.float32)
     ref = rng.standard_normal((60, 128)).astype(np.float32)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            check_exact(eng, rows, ref, 50, label="training handle")
-            check_exact(eng, rows, None, 50, stop=100.0, label="training handle, stop")
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key  # (the Adam state entered this step)
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        check_exact(eng, rows, ref, 50, label="training handle")
+        check_exact(eng, rows, None, 50, stop=100.0, label="training handle, stop")
+
+    training_twin(cfg, w, pk, calls)
 
 
 def test_generic_width_handle(hip_lib):

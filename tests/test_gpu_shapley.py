@@ -24,6 +24,7 @@ if __name__ == "__main__":  # the child process of the environment-switch test
 
 import ablate_ref  # noqa: E402
 import shapley_ref as sr  # noqa: E402
+from analysis_checks import training_twin  # noqa: E402
 from shapley_ref import CASES, P_TEST, rel_err  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -310,24 +311,18 @@ def test_python_layer_denormalises_and_leaves_the_model_as_it_was(hip_lib):
 
 
 def test_training_handle(hip_lib):
-    """after a training step: the result is an inference handle's with the same weights"""
-    from scann.models.scann_model import HipModel
-
+    """after two training steps: the result is an inference handle's with the same weights, and weights, gradients and the following
+    (deterministic) step are those of a twin that never made the call"""
     d = case_data("qm9")
-    pk = d["pk"]
-    eng = HipModel(d["cfg"], d["w"], device=0, deterministic=True).engine
-    eng.train_begin()
-    rb = eng.upload(pk)
-    eng.train_step(rb, np.linspace(-1, 1, pk.n_struct).astype(np.float32), 1e-3, dropout=0.1, seed=3)
-    got = eng.shapley(rb, 4, seed=2, want_values=True)
-    w1 = eng.get_weights()
-    rb.free()
-    inf = HipModel(d["cfg"], w1, device=0, infer=True).engine
-    rb = inf.upload(pk)
-    ref = inf.shapley(rb, 4, seed=2, want_values=True)
-    rb.free()
-    for k in got:
-        assert np.array_equal(_bits(got[k]), _bits(ref[k])), k
+
+    def calls(train_model, rb, inference):
+        got = train_model.engine.shapley(rb, 4, seed=2, want_values=True)
+        inf_model, rb2 = inference()
+        ref = inf_model.engine.shapley(rb2, 4, seed=2, want_values=True)
+        for k in got:
+            assert np.array_equal(_bits(got[k]), _bits(ref[k])), k
+
+    training_twin(d["cfg"], d["w"], d["pk"], calls)
 
 
 # ---- 8. the MFMA body against the plain one ----

@@ -18,8 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import scann_oracle as so  # noqa: E402
 import silhouette_ref as sr  # noqa: E402
-from test_gpu_knn import _bits, setup  # noqa: E402
-from test_gpu_pca import make_index, random_rows  # noqa: E402
+from analysis_checks import make_index, random_rows, setup, training_twin, untouched  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 METRICS = ("euclidean", "sqeuclidean")
@@ -298,85 +297,35 @@ def test_nothing_else_changes(hip_lib):
     from scann import _hip
 
     cfg, w, data, model = setup(n=40, seed=2)
-    eng = model.engine
-    names = ["local_attention_1", "after_Lc"]
-    before = model.predict(data, outputs=names)
-    y0, ga0 = model.predict(data)
-    w0 = eng.get_weights()
-    eng.set_outputs([1], after_lc=True)
-    try:
-        rb = eng.upload(_hip.pack_inputs(data))
-        eng.forward_resident(rb)
-        y_first, _ = eng.download(rb)
-        sel0 = [eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1), eng.read_output(rb, _hip.OUT_AFTER_LC)]
-        pool = eng.index_create(128)
-        eng.index_add_batch(pool, rb, _hip.OUT_AFTER_LC)
-        eng.forward_resident(rb)
-        eng.download(rb)
-        p0 = eng.index_read(pool)
+    with untouched(model, data) as u:
+        eng, pool, rows = u.eng, u.pool, u.rows[0]
         lab = (np.arange(len(pool)) % 4 - (np.arange(len(pool)) % 9 == 0)).astype(np.int32)
-        shift = sr.shift_for(p0[0], "euclidean")
+        shift = sr.shift_for(rows, "euclidean")
         first = eng.index_silhouette(pool, lab, 4, None, "euclidean", shift, table=True)
-        sr.same(first, _hip.silhouette_host(p0[0], lab, 4, None, "euclidean", shift, table=True), "the model's rows")
-        free0, _ = eng.device_memory()
-        for rep in range(4):
-            again = eng.index_silhouette(pool, lab, 4, None, "euclidean", shift, table=True)
+        sr.same(first, _hip.silhouette_host(rows, lab, 4, None, "euclidean", shift, table=True), "the model's rows")
+
+        def same(again):
             assert all(again[k].tobytes() == first[k].tobytes() for k in first)
-        assert free0 - eng.device_memory()[0] <= 16 << 20  # repeated calls take their workspace from the block cache
-        p1 = eng.index_read(pool)
-        for x, y_ in zip(p0, p1):
-            assert x.dtype == y_.dtype and np.array_equal(x.view(np.uint8), y_.view(np.uint8))
-        # the batch's last y and the selected outputs of its last forward are where they were
-        y_again, _ = eng.download(rb)
-        assert np.array_equal(_bits(y_again), _bits(y_first))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_LOCAL_ATTENTION, 1)), _bits(sel0[0]))
-        assert np.array_equal(_bits(eng.read_output(rb, _hip.OUT_AFTER_LC)), _bits(sel0[1]))
-        with pytest.raises(_hip.ScannHipError):
-            eng.read_output(rb, _hip.OUT_BF_PROPERTY)  # still not selected
-        rb.free()
-        pool.free()
-    finally:
-        eng.set_outputs()
-    w1 = eng.get_weights()
-    for key in w0:
-        assert np.array_equal(_bits(w0[key]), _bits(w1[key])), key
-    after = model.predict(data, outputs=names)
-    assert all(np.array_equal(_bits(x), _bits(y_)) for x, y_ in zip(before, after))
-    y1, ga1 = model.predict(data)
-    assert np.array_equal(_bits(y0), _bits(y1)) and np.array_equal(_bits(ga0), _bits(ga1))
+
+        u.repeat(lambda: eng.index_silhouette(pool, lab, 4, None, "euclidean", shift, table=True), same, 4, 16 << 20)
 
 
 def test_training_handle(hip_lib):
     """after two training steps the call on the training handle equals the twin, and weights, gradients and the following
     (deterministic) step are those of a twin handle that never made the call"""
     from scann import _hip
-    from scann.models.scann_model import HipModel
 
     cfg, w, data, _ = setup(n=8, seed=5, n_attention=2)
     pk = _hip.pack_inputs(data)
-    targets = np.linspace(-1, 1, pk.n_struct).astype(np.float32)
     rows, lab = sr.pathological_case(700, 128, seed=3)
-    res = []
-    for i in range(2):
-        eng = HipModel(cfg, w, device=0, deterministic=True).engine
-        eng.train_begin()
-        rb = eng.upload(pk)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=3)
-        eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=4)
-        if i == 0:
-            ix = make_index(eng, rows)
-            check_pool(eng, ix, rows, lab, 5, "euclidean", label="training handle")
-            ix.free()
-        grads, weights = eng.get_grads(), eng.get_weights()
-        step = eng.train_step(rb, targets, 1e-3, dropout=0.1, seed=5)
-        res.append((grads, weights, step, eng.get_weights()))
-        rb.free()
-    (ga, wa, sa, wa2), (gb, wb, sb_, wb2) = res
-    for key in ga:
-        assert np.array_equal(_bits(ga[key]), _bits(gb[key])), key
-        assert np.array_equal(_bits(wa[key]), _bits(wb[key])), key
-        assert np.array_equal(_bits(wa2[key]), _bits(wb2[key])), key
-    assert sa == sb_
+
+    def calls(train_model, rb, inference):
+        eng = train_model.engine
+        ix = make_index(eng, rows)
+        check_pool(eng, ix, rows, lab, 5, "euclidean", label="training handle")
+        ix.free()
+
+    training_twin(cfg, w, pk, calls)
 
 
 def same_table(got, want, label):

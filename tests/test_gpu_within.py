@@ -21,9 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import scann_oracle as so  # noqa: E402
 import within_ref  # noqa: E402
+from analysis_checks import _bits, amask_of, padded, setup, steady_memory  # noqa: E402
 from test_cells_host import blobs  # noqa: E402
 from test_gpu_cells import clustered  # noqa: E402
-from test_gpu_knn import _bits, amask_of, padded, reps_of, setup  # noqa: E402
+from test_gpu_knn import reps_of  # noqa: E402
 from test_within_host import radii_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -529,15 +530,15 @@ def test_repeated_calls_do_not_eat_device_memory(hip_lib):
         eng.index_partition(ix, 4, 2)
         first = eng.index_within_batch(ix, rb, _hip.OUT_AFTER_LC, 0.3)
         eng.index_within_rows(ix, 0, len(ix), 0.3, upper=1)
-        free0, _ = eng.device_memory()
-        for rep in range(30):
+
+        def call(rep):
             r = eng.index_within_batch(ix, rb, _hip.OUT_AFTER_LC, 0.3) if rep % 2 else eng.index_within_rows(ix, 0, len(ix), 0.3, upper=1)
             if rep % 2:
                 assert r["position"].tobytes() == first["position"].tobytes()
-        free1, _ = eng.device_memory()
+
+        steady_memory(eng, call, 30, 32 << 20)
         rb.free()
         ix.free()
-        assert free0 - free1 <= 32 << 20, (free0, free1)
     finally:
         eng.close()
 

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import head_ref
 import pca_ref
 import scann_oracle as so
@@ -286,31 +287,28 @@ def test_header_and_python_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, "
-                 "int64_t* n_eligible, float* mean /* [dim + K] */, double* cov /* [(dim + K)^2] */, int32_t* col_exp /* [dim + K] or NULL */, "
-                 "int32_t* bits /* or NULL */);",
-                 "int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, "
-                 "const float* mean, const float* tmean, const float* components, int32_t m, const float* scale /* [L * m] */, "
-                 "const float* coef /* [L * K * m] */, int32_t L, float lev0, const int32_t* resid_l /* [K] or NULL */, int64_t* n_used, "
-                 "double* sse /* [L * K] */, double* sae /* [L * K] */, double* sse_fit /* [L * K] */, double* dof /* [L] */, "
-                 "float* resid /* [N * K] or NULL */);",
-                 "int scann_ridge_loo_host(const float* rows, int64_t n, int64_t dim, const float* targets, int32_t K, const float* mean, "
-                 "const float* tmean, const float* components, int32_t m, const float* scale, const float* coef, int32_t L, float lev0, "
-                 "const int32_t* resid_l, int64_t* n_used, double* sse, double* sae, double* sse_fit, double* dof, float* resid);",
-                 "int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* tmean, "
-                 "const float* weights /* [K * dim] */, int32_t K, const float* components /* [m * dim] */, int32_t m, "
-                 "const float* scale /* [K * m] */, float lev0, float* y, float* ga, float* pred /* [n * K] */, float* lev /* [n * K] */);",
-                 "#define SCANN_HEAD_MAX_TARGETS 16", "#define SCANN_HEAD_MAX_LAMBDA 32"):
-        assert decl in flat, decl
+    abi_checks.declared("int scann_index_fit_moments(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, "
+                        "int64_t* n_eligible, float* mean /* [dim + K] */, double* cov /* [(dim + K)^2] */, int32_t* col_exp /* [dim + K] or NULL */, "
+                        "int32_t* bits /* or NULL */);",
+                        "int scann_index_ridge_loo(scann_handle_t* h, scann_index_t* pool, const float* targets /* [N * K] */, int32_t K, "
+                        "const float* mean, const float* tmean, const float* components, int32_t m, const float* scale /* [L * m] */, "
+                        "const float* coef /* [L * K * m] */, int32_t L, float lev0, const int32_t* resid_l /* [K] or NULL */, int64_t* n_used, "
+                        "double* sse /* [L * K] */, double* sae /* [L * K] */, double* sse_fit /* [L * K] */, double* dof /* [L] */, "
+                        "float* resid /* [N * K] or NULL */);",
+                        "int scann_ridge_loo_host(const float* rows, int64_t n, int64_t dim, const float* targets, int32_t K, const float* mean, "
+                        "const float* tmean, const float* components, int32_t m, const float* scale, const float* coef, int32_t L, float lev0, "
+                        "const int32_t* resid_l, int64_t* n_used, double* sse, double* sae, double* sse_fit, double* dof, float* resid);",
+                        "int scann_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* tmean, "
+                        "const float* weights /* [K * dim] */, int32_t K, const float* components /* [m * dim] */, int32_t m, "
+                        "const float* scale /* [K * m] */, float lev0, float* y, float* ga, float* pred /* [n * K] */, float* lev /* [n * K] */);",
+                        "#define SCANN_HEAD_MAX_TARGETS 16", "#define SCANN_HEAD_MAX_LAMBDA 32")
     assert _hip.HEAD_MAX_TARGETS == 16 and _hip.HEAD_MAX_LAMBDA == 32
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    assert sig["scann_index_fit_moments"] == (C.c_int, [P, P, P, I, P, P, P, P, P])
-    assert sig["scann_index_ridge_loo"] == (C.c_int, [P, P, P, I, P, P, P, I, P, P, I, F, P, P, P, P, P, P, P])
-    assert sig["scann_ridge_loo_host"] == (C.c_int, [P, L, L, P, I, P, P, P, I, P, P, I, F, P, P, P, P, P, P, P])
-    assert sig["scann_head_batch"] == (C.c_int, [P, P, I, P, P, P, I, P, I, P, F, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_fit_moments": (C.c_int, [P, P, P, I, P, P, P, P, P]),
+        "scann_index_ridge_loo": (C.c_int, [P, P, P, I, P, P, P, I, P, P, I, F, P, P, P, P, P, P, P]),
+        "scann_ridge_loo_host": (C.c_int, [P, L, L, P, I, P, P, P, I, P, P, I, F, P, P, P, P, P, P, P]),
+        "scann_head_batch": (C.c_int, [P, P, I, P, P, P, I, P, I, P, F, P, P, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
 
@@ -365,9 +363,8 @@ def test_head_kernels_use_no_scratch_and_keep_their_names_apart(hip_lib):
     """the kernels of csrc/scann_head.hip spill nothing, read from the built library's kernel descriptors; their names stay out of the
     name census the other host tests take"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "head_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "head_" in n}
     for want, count in (("head_mask_kernel", 1), ("head_tstat_kernel", 3), ("head_tmean_kernel", 1), ("head_cross_kernel", 1),
                         ("head_cross_finalise_kernel", 1), ("head_loo_kernel", 1), ("head_sum_kernel", 1), ("head_eval_kernel", 1)):
         assert sum(want in n for n in kern) == count, (want, sorted(kern))

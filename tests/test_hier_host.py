@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import abi_checks
 import hier_cpu
 import hier_ref
 import kcenter_ref
@@ -406,21 +407,19 @@ def test_argument_errors_name_the_argument(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for decl in ("int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2 /* host [N] or NULL */, int64_t* n_edges, "
-                 "int32_t* a /* [max(N - 1, 0)] */, int32_t* b, float* w, int32_t* rounds /* or NULL */);",
-                 "int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2, int64_t* n_edges, int32_t* a, int32_t* b, float* w);",
-                 "int scann_mst_last_rounds(int32_t cap, int32_t* components, double* seconds, int64_t* skipped, int64_t* tiles);",
-                 "#define SCANN_MST_MAX_ROWS 262144", "w(i, j) = max(dist2(i, j), core2[i], core2[j])",
-                 "(w ascending, min(i, j) ascending, max(i, j) ascending)", "n_edges = max(n_eligible - 1, 0)", "at most ceil(log2 n_eligible)",
-                 "#define SCANN_ABI_VERSION 1"):
-        assert decl in flat, decl
+    abi_checks.declared("int scann_index_mst(scann_handle_t* h, scann_index_t* pool, const float* core2 /* host [N] or NULL */, int64_t* n_edges, "
+                        "int32_t* a /* [max(N - 1, 0)] */, int32_t* b, float* w, int32_t* rounds /* or NULL */);",
+                        "int scann_mst_host(const float* rows, int64_t n, int64_t dim, const float* core2, int64_t* n_edges, int32_t* a, int32_t* b, float* w);",
+                        "int scann_mst_last_rounds(int32_t cap, int32_t* components, double* seconds, int64_t* skipped, int64_t* tiles);",
+                        "#define SCANN_MST_MAX_ROWS 262144", "w(i, j) = max(dist2(i, j), core2[i], core2[j])",
+                        "(w ascending, min(i, j) ascending, max(i, j) ascending)", "n_edges = max(n_eligible - 1, 0)", "at most ceil(log2 n_eligible)",
+                        "#define SCANN_ABI_VERSION 1")
     assert _hip.MST_MAX_ROWS == 262144
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L = C.c_void_p, C.c_int32, C.c_int64
-    assert sig["scann_index_mst"] == (C.c_int, [P, P, P, P, P, P, P, P])
-    assert sig["scann_mst_host"] == (C.c_int, [P, L, L, P, P, P, P, P])
-    assert sig["scann_mst_last_rounds"] == (C.c_int, [I, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_mst": (C.c_int, [P, P, P, P, P, P, P, P]),
+        "scann_mst_host": (C.c_int, [P, L, L, P, P, P, P, P]),
+        "scann_mst_last_rounds": (C.c_int, [I, P, P, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
     shared = open(os.path.join(ROOT, "scann--material_amd", "csrc", "scann_mst.h")).read()

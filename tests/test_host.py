@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import scann_oracle as so
+from abi_checks import device_kernels as _device_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -659,46 +660,6 @@ def test_pack_padded_threads_give_the_single_thread_arrays(hip_lib, monkeypatch)
     bad["neighbors"][b, 0, 0] = M - 1  # a padded atom of that structure
     with pytest.raises(ValueError, match="padded atom"):
         _hip.pack_inputs(bad)
-
-
-def _device_kernels(so_path):
-    """{mangled kernel name: (scratch bytes per lane, VGPRs)} of every gfx950 code object inside a shared library: the .hip_fatbin
-    section holds one clang offload bundle per .hip source file; their ELF notes carry the kernel descriptors' metadata."""
-    import shutil
-    import tempfile
-
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not all(os.path.exists(t) for t in tools):
-        pytest.skip("ROCm LLVM binutils not found")
-    tmp = tempfile.mkdtemp(prefix="scann_co_")
-    try:
-        fat = os.path.join(tmp, "fatbin")
-        subprocess.check_call([tools[0], "--dump-section", ".hip_fatbin=" + fat, so_path])
-        blob = open(fat, "rb").read()
-        magic = b"__CLANG_OFFLOAD_BUNDLE__"
-        starts, i = [], blob.find(magic)
-        while i >= 0:
-            starts.append(i)
-            i = blob.find(magic, i + 1)
-        out = {}
-        for k, a in enumerate(starts):
-            part, co = os.path.join(tmp, "b%d" % k), os.path.join(tmp, "c%d.co" % k)
-            open(part, "wb").write(blob[a:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-            subprocess.check_call([tools[1], "--unbundle", "--type=o", "--input=" + part, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-            name = scratch = None
-            for line in subprocess.check_output([tools[2], "--notes", co], text=True).splitlines():
-                line = line.strip()
-                if line.startswith(".name:"):
-                    name = line.split()[-1]
-                elif line.startswith(".private_segment_fixed_size:"):
-                    scratch = int(line.split()[-1])
-                elif line.startswith(".vgpr_count:") and name is not None:
-                    out[name] = (scratch, int(line.split()[-1]))
-                    name = scratch = None
-        return out
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def test_default_forward_kernels_use_no_scratch(hip_lib):

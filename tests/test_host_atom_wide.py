@@ -4,7 +4,8 @@ descriptors, as tests/test_host.py reads atom_kernel's.  And the launch code's h
 import os
 import re
 
-from test_host import _device_kernels
+import abi_checks
+
 
 WIDE = re.compile(r"_ZN5scann16atom_wide_kernelILb(\d)ELi(\d)ELi(\d)EEEv")
 
@@ -14,7 +15,7 @@ def test_wide_atom_kernels_use_no_scratch(hip_lib):
     FFN = true, MODE 0 (layers 1 .. L-1) and MODE 2 (after_Lc, gq, gk), RT = 3 (128 rows won at no launch size and is not shipped)"""
     from scann import _hip
 
-    kern = _device_kernels(_hip.LIB_PATH)
+    kern = abi_checks.device_kernels(_hip.LIB_PATH)
     seen = set()
     for name, (scratch, vgpr) in kern.items():
         if "atom_wide_kernel" not in name:

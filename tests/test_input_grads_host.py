@@ -6,6 +6,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import scann_oracle as so
 
 pytest.importorskip("torch")
@@ -116,13 +117,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn()
-    m.input_names = list(INPUT_NAMES) + (["ring_aromatic"] if m.config["model"]["use_ring"] else [])
-    return m
+    return abi_checks.stand_in_model(cfg, lambda config: _StandIn(), ring=True)
 
 
 @pytest.mark.parametrize("wrt,over", [(("neighbor_distanc",), {}), (("ring_aromatic",), {}), (("atomic",), {}),
@@ -200,9 +195,8 @@ def test_input_gradient_kernels_use_no_scratch(hip_lib):
     """The three leaves of the data-gradient backward (csrc/scann_input_grad.hip) spill nothing, read from the built library's
     kernel descriptors."""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "input_grad_kernel" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "input_grad_kernel" in n}
     assert len(kern) == 3, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)

@@ -10,6 +10,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import knn_ref
 import scann_oracle as so
 
@@ -163,13 +164,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn(m.config)
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, _StandIn)
 
 
 def _batch(n=5, seed=2):
@@ -332,35 +327,33 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out);",
-                 "void scann_index_free(scann_handle_t* h, scann_index_t* idx);",
-                 "int64_t scann_index_size(const scann_index_t* idx);",
-                 "int scann_index_add(scann_handle_t* h, scann_index_t* idx, const float* rows, int64_t n, const int64_t* ids, const int32_t* atoms);",
-                 "int scann_index_read(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, float* rows, int64_t* ids, int32_t* atoms);",
-                 "int scann_index_query(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, int32_t k, "
-                 "float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos);",
-                 "int scann_index_add_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* ids);",
-                 "int scann_index_query_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, "
-                 "int32_t k, float* y, float* ga, float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos);",
-                 "float scann_knn_distsq(const float* q, const float* r, int64_t d);",
-                 "void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int scann_index_create(scann_handle_t* h, int32_t dim, scann_index_t** out);",
+                        "void scann_index_free(scann_handle_t* h, scann_index_t* idx);",
+                        "int64_t scann_index_size(const scann_index_t* idx);",
+                        "int scann_index_add(scann_handle_t* h, scann_index_t* idx, const float* rows, int64_t n, const int64_t* ids, const int32_t* atoms);",
+                        "int scann_index_read(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, float* rows, int64_t* ids, int32_t* atoms);",
+                        "int scann_index_query(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, int32_t k, "
+                        "float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos);",
+                        "int scann_index_add_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* ids);",
+                        "int scann_index_query_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, "
+                        "int32_t k, float* y, float* ga, float* dist2, int64_t* ids, int32_t* atoms, int32_t* pos);",
+                        "float scann_knn_distsq(const float* q, const float* r, int64_t d);",
+                        "void scann_knn_distsq_matrix(const float* q, int64_t nq, const float* rows, int64_t n, int64_t d, float* out);")
     assert "#define SCANN_ABI_VERSION 1" in h
     assert "#define SCANN_KNN_MAX_K %d" % _hip.KNN_MAX_K in h and _hip.KNN_MAX_K == 32
     assert _hip.KNN_LEVELS == {"structure": _hip.OUT_BF_PROPERTY, "atom": _hip.OUT_AFTER_LC}
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_create"] == (C.c_int, [P, C.c_int32, C.POINTER(P)])
-    assert sig["scann_index_free"] == (None, [P, P]) and sig["scann_index_size"] == (C.c_int64, [P])
-    assert sig["scann_index_add"] == (C.c_int, [P, P, P, C.c_int64, P, P])
-    assert sig["scann_index_read"] == (C.c_int, [P, P, C.c_int64, C.c_int64, P, P, P])
-    assert sig["scann_index_query"] == (C.c_int, [P, P, P, C.c_int64, P, C.c_int32, P, P, P, P])
-    assert sig["scann_index_add_batch"] == (C.c_int, [P, P, P, C.c_int32, P])
-    assert sig["scann_index_query_batch"] == (C.c_int, [P, P, P, C.c_int32, P, C.c_int32] + [P] * 6)
-    assert sig["scann_knn_distsq"] == (C.c_float, [P, P, C.c_int64])
-    assert sig["scann_knn_distsq_matrix"] == (None, [P, C.c_int64, P, C.c_int64, C.c_int64, P])
+    sig = abi_checks.signatures({
+        "scann_index_create": (C.c_int, [P, C.c_int32, C.POINTER(P)]),
+        "scann_index_free": (None, [P, P]), "scann_index_size": (C.c_int64, [P]),
+        "scann_index_add": (C.c_int, [P, P, P, C.c_int64, P, P]),
+        "scann_index_read": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P, P]),
+        "scann_index_query": (C.c_int, [P, P, P, C.c_int64, P, C.c_int32, P, P, P, P]),
+        "scann_index_add_batch": (C.c_int, [P, P, P, C.c_int32, P]),
+        "scann_index_query_batch": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32] + [P] * 6),
+        "scann_knn_distsq": (C.c_float, [P, P, C.c_int64]),
+        "scann_knn_distsq_matrix": (None, [P, C.c_int64, P, C.c_int64, C.c_int64, P])})
     for n in sig:
         assert hasattr(hip_lib, n), n
 
@@ -381,9 +374,8 @@ def test_null_arguments_are_errors_not_crashes(hip_lib):
 def test_knn_kernels_use_no_scratch(hip_lib):
     """the tile kernel and the merge of csrc/scann_knn.hip spill nothing, read from the built library's kernel descriptors"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "knn_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "knn_" in n}
     assert len(kern) == 2 and sum("knn_tile_kernel" in n for n in kern) == 1 and sum("knn_merge_kernel" in n for n in kern) == 1, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)

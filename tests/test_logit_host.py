@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import logit_ref
 import pca_ref
 
@@ -94,24 +95,22 @@ def test_header_and_python_agree(hip_lib):
 
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for decl in ("int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* [N] */, int32_t C, "
-                 "const float* mean /* [dim] */, const float* weights /* [M][C][dim + 1] */, int32_t M, const int32_t* fold /* [M] */, int32_t F, "
-                 "const int32_t* prob_of_fold /* [max(F,1)] or NULL */, int64_t* n_used, double* grad /* [M][C][dim + 1] */, "
-                 "double* stats /* [M][2][3] */, float* prob /* [N * C] or NULL */);",
-                 "int scann_logit_pass_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const float* mean, "
-                 "const float* weights, int32_t M, const int32_t* fold, int32_t F, const int32_t* prob_of_fold, int64_t* n_used, double* grad, "
-                 "double* stats, float* prob);",
-                 "int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean /* [dim] */, "
-                 "const float* weights /* [C][dim + 1] */, int32_t C, float* y, float* ga, float* prob /* [n * C] */);",
-                 "#define SCANN_LOGIT_MAX_CLASSES 16", "#define SCANN_LOGIT_MAX_MODELS 64"):
-        assert decl in flat, decl
+    abi_checks.declared("int scann_index_logit_pass(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* [N] */, int32_t C, "
+                        "const float* mean /* [dim] */, const float* weights /* [M][C][dim + 1] */, int32_t M, const int32_t* fold /* [M] */, int32_t F, "
+                        "const int32_t* prob_of_fold /* [max(F,1)] or NULL */, int64_t* n_used, double* grad /* [M][C][dim + 1] */, "
+                        "double* stats /* [M][2][3] */, float* prob /* [N * C] or NULL */);",
+                        "int scann_logit_pass_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const float* mean, "
+                        "const float* weights, int32_t M, const int32_t* fold, int32_t F, const int32_t* prob_of_fold, int64_t* n_used, double* grad, "
+                        "double* stats, float* prob);",
+                        "int scann_logit_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean /* [dim] */, "
+                        "const float* weights /* [C][dim + 1] */, int32_t C, float* y, float* ga, float* prob /* [n * C] */);",
+                        "#define SCANN_LOGIT_MAX_CLASSES 16", "#define SCANN_LOGIT_MAX_MODELS 64")
     assert _hip.LOGIT_MAX_CLASSES == 16 and _hip.LOGIT_MAX_MODELS == 64
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L = C.c_void_p, C.c_int32, C.c_int64
-    assert sig["scann_index_logit_pass"] == (C.c_int, [P, P, P, I, P, P, I, P, I, P, P, P, P, P])
-    assert sig["scann_logit_pass_host"] == (C.c_int, [P, L, L, P, I, P, P, I, P, I, P, P, P, P, P])
-    assert sig["scann_logit_head_batch"] == (C.c_int, [P, P, I, P, P, I, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_logit_pass": (C.c_int, [P, P, P, I, P, P, I, P, I, P, P, P, P, P]),
+        "scann_logit_pass_host": (C.c_int, [P, L, L, P, I, P, P, I, P, I, P, P, P, P, P]),
+        "scann_logit_head_batch": (C.c_int, [P, P, I, P, P, I, P, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
 

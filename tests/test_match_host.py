@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import match_ref
 import scann_oracle as so
 from test_knn_host import _StandIn
@@ -168,25 +169,23 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int64_t scann_index_segments(const scann_index_t* idx, int64_t* first, int32_t* count, int64_t* id);",
-                 "int scann_index_match(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets, "
-                 "const int64_t* query_ids, int32_t measure, int32_t k, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, "
-                 "int32_t* match_pos, float* match_dist2);",
-                 "int scann_index_match_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure, "
-                 "int32_t k, float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos, "
-                 "float* match_dist2);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int64_t scann_index_segments(const scann_index_t* idx, int64_t* first, int32_t* count, int64_t* id);",
+                        "int scann_index_match(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets, "
+                        "const int64_t* query_ids, int32_t measure, int32_t k, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, "
+                        "int32_t* match_pos, float* match_dist2);",
+                        "int scann_index_match_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure, "
+                        "int32_t k, float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, float* parts, int32_t* match_pos, "
+                        "float* match_dist2);")
     for name, v in _hip.MATCH_MEASURES.items():
         assert "#define SCANN_MATCH_%s %d" % (name.upper(), v) in h
     assert "#define SCANN_MATCH_MAX_ATOMS %d" % _hip.MATCH_MAX_ATOMS in h and _hip.MATCH_MAX_ATOMS >= 128
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_segments"] == (C.c_int64, [P, P, P, P])
-    assert sig["scann_index_match"] == (C.c_int, [P, P, P, P, C.c_int64, P, C.c_int32, C.c_int32] + [P] * 7)
-    assert sig["scann_index_match_batch"] == (C.c_int, [P, P, P, P, C.c_int32, C.c_int32] + [P] * 9)
-    assert sig["scann_match_parts_host"] == (C.c_int, [P, P, C.c_int64, P, P, C.c_int64, C.c_int64, P])
+    sig = abi_checks.signatures({
+        "scann_index_segments": (C.c_int64, [P, P, P, P]),
+        "scann_index_match": (C.c_int, [P, P, P, P, C.c_int64, P, C.c_int32, C.c_int32] + [P] * 7),
+        "scann_index_match_batch": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32] + [P] * 9),
+        "scann_match_parts_host": (C.c_int, [P, P, C.c_int64, P, P, C.c_int64, C.c_int64, P])})
     for n in ("scann_index_segments", "scann_index_match", "scann_index_match_batch", "scann_match_parts_host"):
         assert hasattr(hip_lib, n), n
 
@@ -194,9 +193,8 @@ def test_header_ctypes_and_library_agree(hip_lib):
 def test_match_kernels_use_no_scratch(hip_lib):
     """the tile kernel and the pair kernel of csrc/scann_match.hip spill nothing, read from the built library's kernel descriptors"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "match_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "match_" in n}
     assert len(kern) == 2 and sum("match_tile_kernel" in n for n in kern) == 1 and sum("match_pair_kernel" in n for n in kern) == 1, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)
@@ -227,13 +225,7 @@ class _MatchStandIn(_StandIn):
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _MatchStandIn(m.config)
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, _MatchStandIn)
 
 
 def _batch(n=5, seed=2):

@@ -8,6 +8,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import mc_ref
 import scann_oracle as so
 
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_declares_the_entry_points():
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
+    h = abi_checks.header()
     assert "int scann_predict_mc(scann_handle_t* h, scann_dbatch_t* db, int32_t n_samples, uint64_t seed," in h
     assert "double scann_mc_drop_scale(uint64_t seed, int32_t t, uint64_t key, uint32_t tag, uint64_t idx, float p);" in h
 
@@ -72,13 +73,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn()
-    m.input_names = list(INPUT_NAMES) + (["ring_aromatic"] if m.config["model"]["use_ring"] else [])
-    return m
+    return abi_checks.stand_in_model(cfg, lambda config: _StandIn(), ring=True)
 
 
 def _batch(n=5):

@@ -8,8 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+import abi_checks
 import scann_oracle as so
-from test_host import _device_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = ("scann_models_load", "scann_models_count", "scann_forward_models", "scann_models_download")
@@ -30,7 +30,7 @@ def test_set_instantiations_use_no_scratch(hip_lib):
     the merge and readout set kernels: no scratch, within the VGPR budgets of test_default_forward_kernels_use_no_scratch"""
     from scann import _hip
 
-    kern = _device_kernels(_hip.LIB_PATH)
+    kern = abi_checks.device_kernels(_hip.LIB_PATH)
     atoms = {n: v for n, v in kern.items() if re.match(r"_ZN5scann11atom_kernelILb\dELi\dELi\dELb0ELb0ELb0ELb0ELb1EEEvNS_8AtomArgsE$", n)}
     edges = {n: v for n, v in kern.items() if re.match(r"_ZN5scann11edge_kernelILb\dELi\dELb\dELb0ELb0ELb\dELb0ELb0ELb1EEEvNS_8EdgeArgsE$", n)}
     assert len(atoms) == 12 and len(edges) == 8, (sorted(atoms), sorted(edges))

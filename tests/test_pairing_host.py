@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import match_ref
 import pairing_ref
 import scann_oracle as so
@@ -160,27 +161,25 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int scann_index_pairing(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets, "
-                 "const int32_t* pair_set, const int32_t* pair_segment, int64_t n_pairs, float* score, int64_t* total, int32_t* shift, "
-                 "int32_t* partner_pos, float* partner_dist2);",
-                 "int scann_index_pairing_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure, "
-                 "int32_t shortlist, int32_t k, float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, int64_t* total, "
-                 "int32_t* shift, float* short_score, int32_t* short_place, int32_t* partner_pos, float* partner_dist2);",
-                 "int scann_pairing_host(const float* a, int64_t n, const float* b, int64_t m, int64_t dim, float* score, int64_t* total, int32_t* shift, "
-                 "int32_t* partner, float* partner_dist2);",
-                 "int scann_pairing_solve_host(const uint32_t* cost, int32_t Q, int32_t* col_of_row, int64_t* total);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int scann_index_pairing(scann_handle_t* h, scann_index_t* idx, const float* q, const int32_t* q_first /* [n_sets + 1] */, int64_t n_sets, "
+                        "const int32_t* pair_set, const int32_t* pair_segment, int64_t n_pairs, float* score, int64_t* total, int32_t* shift, "
+                        "int32_t* partner_pos, float* partner_dist2);",
+                        "int scann_index_pairing_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, const int64_t* query_ids, int32_t measure, "
+                        "int32_t shortlist, int32_t k, float* y, float* ga, float* score, int32_t* segment, int64_t* ids, int32_t* sizes, int64_t* total, "
+                        "int32_t* shift, float* short_score, int32_t* short_place, int32_t* partner_pos, float* partner_dist2);",
+                        "int scann_pairing_host(const float* a, int64_t n, const float* b, int64_t m, int64_t dim, float* score, int64_t* total, int32_t* shift, "
+                        "int32_t* partner, float* partner_dist2);",
+                        "int scann_pairing_solve_host(const uint32_t* cost, int32_t Q, int32_t* col_of_row, int64_t* total);")
     assert "#define SCANN_PAIRING_MAX_ATOMS %d" % _hip.PAIRING_MAX_ATOMS in h and _hip.PAIRING_MAX_ATOMS == pairing_ref.MAX_ATOMS == 128
     assert "#define SCANN_PAIRING_SOLVE_MAX %d" % _hip.PAIRING_SOLVE_MAX in h
     assert _hip.MATCH_MEASURES == {"chamfer": 0, "hausdorff": 1, "cover": 2}  # the pairing is no fourth measure
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_pairing"] == (C.c_int, [P, P, P, P, C.c_int64, P, P, C.c_int64] + [P] * 5)
-    assert sig["scann_index_pairing_batch"] == (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, C.c_int32] + [P] * 12)
-    assert sig["scann_pairing_host"] == (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64] + [P] * 5)
-    assert sig["scann_pairing_solve_host"] == (C.c_int, [P, C.c_int32, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_pairing": (C.c_int, [P, P, P, P, C.c_int64, P, P, C.c_int64] + [P] * 5),
+        "scann_index_pairing_batch": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, C.c_int32] + [P] * 12),
+        "scann_pairing_host": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64] + [P] * 5),
+        "scann_pairing_solve_host": (C.c_int, [P, C.c_int32, P, P])})
     for n in ("scann_index_pairing", "scann_index_pairing_batch", "scann_pairing_host", "scann_pairing_solve_host"):
         assert hasattr(hip_lib, n), n
     # the error returns that need no handle
@@ -200,9 +199,8 @@ def test_header_ctypes_and_library_agree(hip_lib):
 def test_pairing_kernel_uses_no_scratch(hip_lib):
     """the three size classes of pairing_kernel (csrc/scann_pairing.hip) spill nothing, read from the built library's kernel descriptors"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "pairing_kernel" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "pairing_kernel" in n}
     assert len(kern) == 3, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)
@@ -254,13 +252,7 @@ class _PairStandIn(_MatchStandIn):
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _PairStandIn(m.config)
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, _PairStandIn)
 
 
 def _batch(n=5, seed=2):

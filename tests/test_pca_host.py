@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import pca_ref
 import scann_oracle as so
 
@@ -239,32 +240,30 @@ def test_header_and_python_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int scann_index_moments(scann_handle_t* h, scann_index_t* pool, int64_t* n_eligible, float* mean /* [dim] */, "
-                 "double* cov /* [dim * dim] */, int32_t* col_exp /* [dim] or NULL */, int32_t* bits /* or NULL */);",
-                 "int scann_index_project(scann_handle_t* h, scann_index_t* pool, int64_t first, int64_t n, const float* mean, "
-                 "const float* components, const float* scale, int32_t m, float* coords /* [n * m] */, float* md2 /* [n] or NULL */, "
-                 "float* dist2 /* [n] or NULL */);",
-                 "int scann_project_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* components, "
-                 "const float* scale, int32_t m, float* y, float* ga, float* coords, float* md2, float* dist2);",
-                 "int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eligible, float* mean, double* cov, "
-                 "int32_t* col_exp, int32_t* bits);",
-                 "int scann_project_host(const float* rows, int64_t n, int64_t dim, const float* mean, const float* components, "
-                 "const float* scale, int32_t m, float* coords, float* md2, float* dist2);",
-                 "int scann_sym_eig_host(const double* a, int64_t d, double* w, double* v, int32_t* sweeps);",
-                 "int scann_pca_bits(int64_t n);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int scann_index_moments(scann_handle_t* h, scann_index_t* pool, int64_t* n_eligible, float* mean /* [dim] */, "
+                        "double* cov /* [dim * dim] */, int32_t* col_exp /* [dim] or NULL */, int32_t* bits /* or NULL */);",
+                        "int scann_index_project(scann_handle_t* h, scann_index_t* pool, int64_t first, int64_t n, const float* mean, "
+                        "const float* components, const float* scale, int32_t m, float* coords /* [n * m] */, float* md2 /* [n] or NULL */, "
+                        "float* dist2 /* [n] or NULL */);",
+                        "int scann_project_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* mean, const float* components, "
+                        "const float* scale, int32_t m, float* y, float* ga, float* coords, float* md2, float* dist2);",
+                        "int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eligible, float* mean, double* cov, "
+                        "int32_t* col_exp, int32_t* bits);",
+                        "int scann_project_host(const float* rows, int64_t n, int64_t dim, const float* mean, const float* components, "
+                        "const float* scale, int32_t m, float* coords, float* md2, float* dist2);",
+                        "int scann_sym_eig_host(const double* a, int64_t d, double* w, double* v, int32_t* sweeps);",
+                        "int scann_pca_bits(int64_t n);")
     assert "#define SCANN_ABI_VERSION 1" in h and hip_lib.scann_abi_version() == 1
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_moments"] == (C.c_int, [P] * 7)
-    assert sig["scann_index_project"] == (C.c_int, [P, P, C.c_int64, C.c_int64, P, P, P, C.c_int32, P, P, P])
-    assert sig["scann_project_batch"] == (C.c_int, [P, P, C.c_int32, P, P, P, C.c_int32, P, P, P, P, P])
-    assert sig["scann_moments_host"] == (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P, P])
-    assert sig["scann_project_host"] == (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, C.c_int32, P, P, P])
-    assert sig["scann_sym_eig_host"] == (C.c_int, [P, C.c_int64, P, P, P])
-    assert sig["scann_pca_bits"] == (C.c_int, [C.c_int64])
+    sig = abi_checks.signatures({
+        "scann_index_moments": (C.c_int, [P] * 7),
+        "scann_index_project": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P, P, C.c_int32, P, P, P]),
+        "scann_project_batch": (C.c_int, [P, P, C.c_int32, P, P, P, C.c_int32, P, P, P, P, P]),
+        "scann_moments_host": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P, P]),
+        "scann_project_host": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, C.c_int32, P, P, P]),
+        "scann_sym_eig_host": (C.c_int, [P, C.c_int64, P, P, P]),
+        "scann_pca_bits": (C.c_int, [C.c_int64])})
     for name in sig:
         assert hasattr(hip_lib, name), name
 
@@ -330,9 +329,8 @@ def test_pca_kernels_use_no_scratch_and_keep_their_names_apart(hip_lib):
     """the kernels of csrc/scann_pca.hip spill nothing, read from the built library's kernel descriptors; their names stay out of the
     name census the other host tests take"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "pca_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "pca_" in n}
     for want, count in (("pca_prepare_kernel", 1), ("pca_pass_kernel", 2), ("pca_mean_kernel", 1), ("pca_scatter_kernel", 1),
                         ("pca_finalise_kernel", 1), ("pca_project_kernel", 1), ("pca_md2_kernel", 1)):
         assert sum(want in n for n in kern) == count, (want, sorted(kern))

@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import abi_checks
 import kcenter_ref
 import peaks_cpu
 import peaks_ref
@@ -305,27 +306,25 @@ def test_the_c_twins_refuse_bad_arguments_themselves(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for decl in ("int scann_index_density(scann_handle_t* h, scann_index_t* pool, const float* q /* host [nq * dim] */, int64_t nq, "
-                 "const int32_t* skip_pos /* [nq] or NULL */, float gamma, int64_t* sums /* [nq] */);",
-                 "int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64_t* sums /* [N] */, int32_t* parent /* [N] */, "
-                 "float* delta2 /* [N] */);",
-                 "int scann_index_density_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, float gamma, float* y, "
-                 "float* ga, int64_t* sums);",
-                 "int scann_density_host(const float* rows, int64_t n, int64_t dim, const float* q, int64_t nq, const int32_t* skip_pos, "
-                 "float gamma, int64_t* sums);",
-                 "int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int64_t* sums, int32_t* parent, float* delta2);",
-                 "t = llrintf(ldexpf(w, 30)), round to nearest even", "row j is ABOVE row i iff S_j > S_i, or S_j == S_i and j < i",
-                 "(dist2 ascending, position ascending)", "An ineligible query gets S = -1", "the parents form a tree", "#define SCANN_ABI_VERSION 1"):
-        assert decl in flat, decl
+    abi_checks.declared("int scann_index_density(scann_handle_t* h, scann_index_t* pool, const float* q /* host [nq * dim] */, int64_t nq, "
+                        "const int32_t* skip_pos /* [nq] or NULL */, float gamma, int64_t* sums /* [nq] */);",
+                        "int scann_index_peaks(scann_handle_t* h, scann_index_t* pool, float gamma, int64_t* sums /* [N] */, int32_t* parent /* [N] */, "
+                        "float* delta2 /* [N] */);",
+                        "int scann_index_density_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, float gamma, float* y, "
+                        "float* ga, int64_t* sums);",
+                        "int scann_density_host(const float* rows, int64_t n, int64_t dim, const float* q, int64_t nq, const int32_t* skip_pos, "
+                        "float gamma, int64_t* sums);",
+                        "int scann_peaks_host(const float* rows, int64_t n, int64_t dim, float gamma, int64_t* sums, int32_t* parent, float* delta2);",
+                        "t = llrintf(ldexpf(w, 30)), round to nearest even", "row j is ABOVE row i iff S_j > S_i, or S_j == S_i and j < i",
+                        "(dist2 ascending, position ascending)", "An ineligible query gets S = -1", "the parents form a tree", "#define SCANN_ABI_VERSION 1")
     assert hip_lib.scann_abi_version() == 1
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    assert sig["scann_index_density"] == (C.c_int, [P, P, P, L, P, F, P])
-    assert sig["scann_index_peaks"] == (C.c_int, [P, P, F, P, P, P])
-    assert sig["scann_index_density_batch"] == (C.c_int, [P, P, P, I, F, P, P, P])
-    assert sig["scann_density_host"] == (C.c_int, [P, L, L, P, L, P, F, P])
-    assert sig["scann_peaks_host"] == (C.c_int, [P, L, L, F, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_density": (C.c_int, [P, P, P, L, P, F, P]),
+        "scann_index_peaks": (C.c_int, [P, P, F, P, P, P]),
+        "scann_index_density_batch": (C.c_int, [P, P, P, I, F, P, P, P]),
+        "scann_density_host": (C.c_int, [P, L, L, P, L, P, F, P]),
+        "scann_peaks_host": (C.c_int, [P, L, L, F, P, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
 

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import rank_ref as rr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -229,23 +230,21 @@ def test_argument_errors_name_the_argument(hip_lib, tie_free):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for text in ("int scann_index_ranks(scann_handle_t* h, scann_index_t* pool, const int32_t* qpos /* host [nq] positions, or NULL: all N rows, nq "
-                 "ignored */, int64_t nq, const int32_t* probe /* host [nq * m] positions, -1: unused */, int32_t m, int32_t* rank /* [nq * m] */, "
-                 "float* dist2 /* [nq * m] or NULL */);",
-                 "int scann_ranks_host(const float* rows, int64_t n, int64_t dim, const int32_t* qpos, int64_t nq, const int32_t* probe, int32_t m, "
-                 "int32_t threads, int32_t* rank, float* dist2);",
-                 "a row is eligible iff all its components are finite", "exactly the chain of scann_knn_distsq with row i as q",
-                 "dist2 ascending, then position ascending", "strictly less than j's key", "the nearest other row has rank 0",
-                 "gets rank -1 and dist2 +inf", "equal probes get equal ranks", "a qpos subset gives the rows of the full answer",
-                 "leave-self-out answer from scann_index_query has rank p", "a permutation of 0 .. n_eligible - 2",
-                 "on the query slicing or on a thread count", "#define SCANN_RANKS_MAX_PROBES 32", "#define SCANN_RANKS_SLICE 262144",
-                 "#define SCANN_ABI_VERSION 1"):
-        assert text in flat, text
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    abi_checks.declared("int scann_index_ranks(scann_handle_t* h, scann_index_t* pool, const int32_t* qpos /* host [nq] positions, or NULL: all N rows, nq "
+                        "ignored */, int64_t nq, const int32_t* probe /* host [nq * m] positions, -1: unused */, int32_t m, int32_t* rank /* [nq * m] */, "
+                        "float* dist2 /* [nq * m] or NULL */);",
+                        "int scann_ranks_host(const float* rows, int64_t n, int64_t dim, const int32_t* qpos, int64_t nq, const int32_t* probe, int32_t m, "
+                        "int32_t threads, int32_t* rank, float* dist2);",
+                        "a row is eligible iff all its components are finite", "exactly the chain of scann_knn_distsq with row i as q",
+                        "dist2 ascending, then position ascending", "strictly less than j's key", "the nearest other row has rank 0",
+                        "gets rank -1 and dist2 +inf", "equal probes get equal ranks", "a qpos subset gives the rows of the full answer",
+                        "leave-self-out answer from scann_index_query has rank p", "a permutation of 0 .. n_eligible - 2",
+                        "on the query slicing or on a thread count", "#define SCANN_RANKS_MAX_PROBES 32", "#define SCANN_RANKS_SLICE 262144",
+                        "#define SCANN_ABI_VERSION 1")
     P, I, L = C.c_void_p, C.c_int32, C.c_int64
-    assert sig["scann_index_ranks"] == (C.c_int, [P, P, P, L, P, I, P, P])
-    assert sig["scann_ranks_host"] == (C.c_int, [P, L, L, P, L, P, I, I, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_ranks": (C.c_int, [P, P, P, L, P, I, P, P]),
+        "scann_ranks_host": (C.c_int, [P, L, L, P, L, P, I, I, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
     assert _hip.RANKS_MAX_PROBES == 32 and _hip.RANKS_SLICE == 262144

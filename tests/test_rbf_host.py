@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import head_ref
 import pca_ref
 import rbf_ref
@@ -140,23 +141,19 @@ def test_header_and_python_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("float scann_rbf_weight(float dist2, float gamma);",
-                 "int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float* landmarks /* host [m * dim] */, int32_t m, "
-                 "float gamma, scann_index_t* out);",
-                 "int scann_rbf_features_host(const float* rows, int64_t n, int64_t dim, const float* landmarks, int32_t m, float gamma, "
-                 "float* phi /* [n * m] */);",
-                 "int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* landmarks, int32_t m, float gamma, "
-                 "const float* mean /* [m] */, const float* tmean /* [K] */, const float* weights /* [K * m] */, int32_t K, "
-                 "const float* components /* [mm * m] */, int32_t mm, const float* scale /* [K * mm] */, float lev0, float* y, float* ga, "
-                 "float* pred /* [n * K] */, float* lev /* [n * K] */, float* phi /* [n * m] or NULL */);",
-                 "#define SCANN_ABI_VERSION 1"):
-        assert decl in flat, decl
-    for text in ("scann_rbf_weight(0, gamma) == 1.0f exactly", "lies in [0, 1]", "3 x 2^-24", "u >= 126", "NaN in all m features",
-                 "0x1.6a09e6p-1,", "-0x1.f5e466p-2,", "0x1.5be298p-3,", "-0x1.41839ep-5,", "0x1.bdb696p-8,", "-0x1.ee4fd2p-11,", "0x1.c8d752p-14,",
-                 "-0x1.69e51ep-17."):
-        assert text in flat, text
+    abi_checks.declared("float scann_rbf_weight(float dist2, float gamma);",
+                        "int scann_index_rbf_features(scann_handle_t* h, scann_index_t* pool, const float* landmarks /* host [m * dim] */, int32_t m, "
+                        "float gamma, scann_index_t* out);",
+                        "int scann_rbf_features_host(const float* rows, int64_t n, int64_t dim, const float* landmarks, int32_t m, float gamma, "
+                        "float* phi /* [n * m] */);",
+                        "int scann_rbf_head_batch(scann_handle_t* h, scann_dbatch_t* db, int32_t level, const float* landmarks, int32_t m, float gamma, "
+                        "const float* mean /* [m] */, const float* tmean /* [K] */, const float* weights /* [K * m] */, int32_t K, "
+                        "const float* components /* [mm * m] */, int32_t mm, const float* scale /* [K * mm] */, float lev0, float* y, float* ga, "
+                        "float* pred /* [n * K] */, float* lev /* [n * K] */, float* phi /* [n * m] or NULL */);",
+                        "#define SCANN_ABI_VERSION 1")
+    abi_checks.declared("scann_rbf_weight(0, gamma) == 1.0f exactly", "lies in [0, 1]", "3 x 2^-24", "u >= 126", "NaN in all m features",
+                        "0x1.6a09e6p-1,", "-0x1.f5e466p-2,", "0x1.5be298p-3,", "-0x1.41839ep-5,", "0x1.bdb696p-8,", "-0x1.ee4fd2p-11,", "0x1.c8d752p-14,",
+                        "-0x1.69e51ep-17.")
     # the coefficients live in one place that the host and the device code include
     csrc = os.path.join(ROOT, "scann--material_amd", "csrc")
     holders = [f for f in sorted(os.listdir(csrc)) if "0x1.6a09e6p-1" in open(os.path.join(csrc, f), errors="replace").read()]
@@ -165,22 +162,21 @@ def test_header_and_python_agree(hip_lib):
         assert '#include "scann_rbf.h"' in open(os.path.join(csrc, f)).read()
     want = [2.0 ** -0.5 * (-np.log(2.0)) ** j / float(np.prod(np.arange(1, j + 1))) for j in range(8)]
     assert [np.float32(c) for c in want] == [np.float32(c) for c in rbf_ref.COEF] and all(float(np.float32(c)) == c for c in rbf_ref.COEF)
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P, I, L, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    assert sig["scann_rbf_weight"] == (F, [F, F])
-    assert sig["scann_rbf_weight_array"] == (None, [P, L, F, P])
-    assert sig["scann_index_rbf_features"] == (C.c_int, [P, P, P, I, F, P])
-    assert sig["scann_rbf_features_host"] == (C.c_int, [P, L, L, P, I, F, P])
-    assert sig["scann_rbf_head_batch"] == (C.c_int, [P, P, I, P, I, F, P, P, P, I, P, I, P, F, P, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_rbf_weight": (F, [F, F]),
+        "scann_rbf_weight_array": (None, [P, L, F, P]),
+        "scann_index_rbf_features": (C.c_int, [P, P, P, I, F, P]),
+        "scann_rbf_features_host": (C.c_int, [P, L, L, P, I, F, P]),
+        "scann_rbf_head_batch": (C.c_int, [P, P, I, P, I, F, P, P, P, I, P, I, P, F, P, P, P, P, P])})
     lib = _hip.load_library()
     assert all(hasattr(lib, n) for n in sig) and lib.scann_abi_version() == 1
 
 
 def test_feature_kernel_uses_no_scratch(hip_lib):
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "rbf_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "rbf_" in n}
     assert len(kern) == 1 and "rbf_feature_kernel" in next(iter(kern)), sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0 and vgpr <= 128, (name, scratch, vgpr)  # two workgroups per SIMD row, four per CU with 35 KB of LDS each

@@ -10,6 +10,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import rollout_ref
 import scann_oracle as so
 
@@ -184,13 +185,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn()
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, lambda config: _StandIn())
 
 
 def _batch(n=5):
@@ -276,16 +271,15 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
+    h = flat = abi_checks.header()
     assert "int64_t scann_rollout_floats(scann_handle_t* h, const scann_dbatch_t* db);" in flat
     assert ("int scann_attention_rollout(scann_handle_t* h, scann_dbatch_t* db, float residual, int32_t head, int32_t depth, float* y, "
             "float* ga, float* attribution, float* rollout);") in flat
     assert "#define SCANN_ABI_VERSION 1" in h
     assert "#define SCANN_ROLLOUT_MAX_ATOMS %d" % _hip.ROLLOUT_MAX_ATOMS in h and _hip.ROLLOUT_MAX_ATOMS == _hip.ABLATE_MAX_ATOMS == 960
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
-    assert sig["scann_rollout_floats"] == (C.c_int64, [C.c_void_p, C.c_void_p])
-    assert sig["scann_attention_rollout"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 4)
+    sig = abi_checks.signatures({
+        "scann_rollout_floats": (C.c_int64, [C.c_void_p, C.c_void_p]),
+        "scann_attention_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 4)})
     assert hasattr(hip_lib, "scann_rollout_floats") and hasattr(hip_lib, "scann_attention_rollout")
 
 
@@ -298,9 +292,8 @@ def test_rollout_kernels_use_no_scratch(hip_lib):
     """the three column-slab instantiations of csrc/scann_rollout.hip and its edge-weight pre-pass spill nothing, read from the built
     library's kernel descriptors"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "rollout_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "rollout_" in n}
     assert len(kern) == 4 and sum("rollout_kernel" in n for n in kern) == 3, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)

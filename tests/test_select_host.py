@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import kcenter_ref
 import scann_oracle as so
 
@@ -167,18 +168,16 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t* reference /* or NULL */, int64_t m, "
-                 "float stop_dist2, int32_t* pos, int64_t* ids, int32_t* atoms, float* radius2);",
-                 "int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, "
-                 "float stop_dist2, int32_t* pos, float* radius2);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int64_t scann_index_select(scann_handle_t* h, scann_index_t* pool, scann_index_t* reference /* or NULL */, int64_t m, "
+                        "float stop_dist2, int32_t* pos, int64_t* ids, int32_t* atoms, float* radius2);",
+                        "int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64_t nr, int64_t dim, int64_t m, "
+                        "float stop_dist2, int32_t* pos, float* radius2);")
     assert "#define SCANN_ABI_VERSION 1" in h and hip_lib.scann_abi_version() == 1
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_index_select"] == (C.c_int64, [P, P, P, C.c_int64, C.c_float, P, P, P, P])
-    assert sig["scann_kcenter_host"] == (C.c_int64, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64, C.c_float, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_select": (C.c_int64, [P, P, P, C.c_int64, C.c_float, P, P, P, P]),
+        "scann_kcenter_host": (C.c_int64, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64, C.c_float, P, P])})
     assert hasattr(hip_lib, "scann_index_select") and hasattr(hip_lib, "scann_kcenter_host")
 
 
@@ -211,9 +210,8 @@ def test_kcenter_kernels_use_no_scratch_and_keep_their_names_apart(hip_lib):
     """the kernels of csrc/scann_select.hip spill nothing, read from the built library's kernel descriptors; their names stay out of
     the name census the other host tests take"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "kcenter_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "kcenter_" in n}
     assert len(kern) == 2 and sum("kcenter_step_kernel" in n for n in kern) == 1 and sum("kcenter_prepare_kernel" in n for n in kern) == 1, sorted(kern)
     for name, (scratch, vgpr) in kern.items():
         assert scratch == 0, (name, scratch, vgpr)

@@ -12,6 +12,7 @@ import types
 import numpy as np
 import pytest
 
+import abi_checks
 import ablate_ref
 import shapley_ref as sr
 
@@ -183,23 +184,21 @@ def test_header_ctypes_and_library_agree(hip_lib):
 
     from scann import _hip
 
-    h = open(os.path.join(ROOT, "include", "scann_hip.h")).read()
-    flat = " ".join(h.split())
-    for decl in ("int scann_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, "
-                 "const int32_t* perms_in, float* y, float* ga, double* shapley, double* stderr_out, double* baseline, double* full, "
-                 "float* values, int32_t* perms_out);",
-                 "int scann_shapley_profile(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, float* ms);",
-                 "void scann_shapley_permutation(uint64_t seed, uint64_t key, int32_t p, int32_t n, int32_t* out);",
-                 "int scann_shapley_reduce_host(const float* values, const int32_t* perms, const int32_t* mol_offset, int32_t n_struct, "
-                 "int32_t n_perm, const double* baseline, double* shapley, double* stderr_out, double* full);"):
-        assert decl in flat, decl
+    h = abi_checks.header()
+    abi_checks.declared("int scann_shapley(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, "
+                        "const int32_t* perms_in, float* y, float* ga, double* shapley, double* stderr_out, double* baseline, double* full, "
+                        "float* values, int32_t* perms_out);",
+                        "int scann_shapley_profile(scann_handle_t* h, scann_dbatch_t* db, int32_t n_perm, uint64_t seed, const uint64_t* keys, float* ms);",
+                        "void scann_shapley_permutation(uint64_t seed, uint64_t key, int32_t p, int32_t n, int32_t* out);",
+                        "int scann_shapley_reduce_host(const float* values, const int32_t* perms, const int32_t* mol_offset, int32_t n_struct, "
+                        "int32_t n_perm, const double* baseline, double* shapley, double* stderr_out, double* full);")
     assert "#define SCANN_ABI_VERSION 1" in h and hip_lib.scann_abi_version() == 1
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
     P = C.c_void_p
-    assert sig["scann_shapley"] == (C.c_int, [P, P, C.c_int32, C.c_uint64, P, P, P, P, P, P, P, P, P, P])
-    assert sig["scann_shapley_profile"] == (C.c_int, [P, P, C.c_int32, C.c_uint64, P, P])
-    assert sig["scann_shapley_permutation"] == (None, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, P])
-    assert sig["scann_shapley_reduce_host"] == (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_shapley": (C.c_int, [P, P, C.c_int32, C.c_uint64, P, P, P, P, P, P, P, P, P, P]),
+        "scann_shapley_profile": (C.c_int, [P, P, C.c_int32, C.c_uint64, P, P]),
+        "scann_shapley_permutation": (None, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, P]),
+        "scann_shapley_reduce_host": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P, P, P])})
     for n in ("scann_shapley", "scann_shapley_profile", "scann_shapley_permutation", "scann_shapley_reduce_host"):
         assert hasattr(hip_lib, n), n
 
@@ -238,9 +237,8 @@ def test_shapley_kernels_use_no_scratch_and_keep_their_names_apart(hip_lib):
     """the kernels of csrc/scann_shapley.hip spill nothing, read from the built library's kernel descriptors; their names stay out of the
     name census the other host tests take"""
     from scann import _hip
-    from test_host import _device_kernels
 
-    kern = {n: v for n, v in _device_kernels(_hip.LIB_PATH).items() if "shapley_" in n}
+    kern = {n: v for n, v in abi_checks.device_kernels(_hip.LIB_PATH).items() if "shapley_" in n}
     assert len(kern) == 4, sorted(kern)
     assert sum("shapley_walk_kernel" in n for n in kern) == 2 and sum("gen_shapley_walk_kernel" in n for n in kern) == 1
     assert sum("shapley_pair_kernel" in n for n in kern) == 1 and sum("shapley_reduce_kernel" in n for n in kern) == 1
@@ -280,13 +278,7 @@ class _StandIn:
 
 
 def _model(cfg):
-    from scann.models.scann_model import INPUT_NAMES, HipModel, normalize_config
-
-    m = HipModel.__new__(HipModel)
-    m.config = normalize_config(cfg)
-    m.engine = _StandIn()
-    m.input_names = list(INPUT_NAMES)
-    return m
+    return abi_checks.stand_in_model(cfg, lambda config: _StandIn())
 
 
 def _batch(n=5):

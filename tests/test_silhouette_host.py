@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import abi_checks
 import silhouette_ref as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -234,20 +235,19 @@ def test_the_c_twin_refuses_bad_arguments_itself(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for decl in ("int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* host [N], -1 .. C-1 */, int32_t C, "
-                 "const int32_t* qpos /* host [nq] positions, or NULL: all N rows */, int64_t nq, int32_t squared, int32_t shift, "
-                 "int64_t* counts /* [C] */, double* a /* [nq] */, double* b /* [nq] */, int32_t* other /* [nq] */, "
-                 "int64_t* sums /* [nq * C] or NULL */);",
-                 "int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const int32_t* qpos, "
-                 "int64_t nq, int32_t squared, int32_t shift, int32_t threads, int64_t* counts, double* a, double* b, int32_t* other, int64_t* sums);",
-                 "t = llrintf(ldexpf(e, shift)), round to nearest even", "ties to the lower c", "a qpos subset gives the rows of the full answer",
-                 "No tree is part of the definition", "#define SCANN_ABI_VERSION 1"):
-        assert decl in flat, decl
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    flat = abi_checks.header()
+    abi_checks.declared("int scann_index_silhouette(scann_handle_t* h, scann_index_t* pool, const int32_t* labels /* host [N], -1 .. C-1 */, int32_t C, "
+                        "const int32_t* qpos /* host [nq] positions, or NULL: all N rows */, int64_t nq, int32_t squared, int32_t shift, "
+                        "int64_t* counts /* [C] */, double* a /* [nq] */, double* b /* [nq] */, int32_t* other /* [nq] */, "
+                        "int64_t* sums /* [nq * C] or NULL */);",
+                        "int scann_silhouette_host(const float* rows, int64_t n, int64_t dim, const int32_t* labels, int32_t C, const int32_t* qpos, "
+                        "int64_t nq, int32_t squared, int32_t shift, int32_t threads, int64_t* counts, double* a, double* b, int32_t* other, int64_t* sums);",
+                        "t = llrintf(ldexpf(e, shift)), round to nearest even", "ties to the lower c", "a qpos subset gives the rows of the full answer",
+                        "No tree is part of the definition", "#define SCANN_ABI_VERSION 1")
     P, I, L = C.c_void_p, C.c_int32, C.c_int64
-    assert sig["scann_index_silhouette"] == (C.c_int, [P, P, P, I, P, L, I, I, P, P, P, P, P])
-    assert sig["scann_silhouette_host"] == (C.c_int, [P, L, L, P, I, P, L, I, I, I, P, P, P, P, P])
+    sig = abi_checks.signatures({
+        "scann_index_silhouette": (C.c_int, [P, P, P, I, P, L, I, I, P, P, P, P, P]),
+        "scann_silhouette_host": (C.c_int, [P, L, L, P, I, P, L, I, I, I, P, P, P, P, P])})
     for name in sig:
         assert hasattr(hip_lib, name), name
     assert _hip.KMEANS_MAX_K == 1024 and "#define SCANN_KMEANS_MAX_K 1024" in flat

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_checks
 import knn_ref
 import within_ref
 from test_cells_host import blobs
@@ -260,23 +261,21 @@ def test_duplicate_groups_on_planted_copies(hip_lib):
 def test_header_and_python_agree(hip_lib):
     from scann import _hip
 
-    flat = " ".join(open(os.path.join(ROOT, "include", "scann_hip.h")).read().split())
-    for text in ("int scann_index_within(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, float radius2, "
-                 "int64_t cap, int64_t* counts /* [nq] */, int64_t* total, float* dist2, int32_t* pos, int64_t* ids, int32_t* atoms",
-                 "int scann_index_within_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t upper, float radius2, int64_t cap,",
-                 "int scann_index_within_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, float radius2,",
-                 "int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* row_ids, const float* q, int64_t nq, const int64_t* query_ids, "
-                 "const int32_t* query_pos, int32_t upper, float radius2, int64_t cap, int64_t* counts, int64_t* total, float* dist2, int32_t* pos);",
-                 "the compare is an fp32 <=, inclusive", "a NaN distance never qualifies", "the entry arrays are NOT TOUCHED",
-                 "scann_index_query's first k places wherever those places qualify", "> radius2, strictly, for EVERY query q of the group",
-                 "dist2 >= lb > radius2", "#define SCANN_WITHIN_MAX_CAP ((int64_t)1 << 30)"):
-        assert text in flat, text
-    sig = {n: (r, a) for n, r, a in _hip.SYMBOLS}
+    abi_checks.declared("int scann_index_within(scann_handle_t* h, scann_index_t* idx, const float* q, int64_t nq, const int64_t* query_ids, float radius2, "
+                        "int64_t cap, int64_t* counts /* [nq] */, int64_t* total, float* dist2, int32_t* pos, int64_t* ids, int32_t* atoms",
+                        "int scann_index_within_rows(scann_handle_t* h, scann_index_t* idx, int64_t first, int64_t n, int32_t upper, float radius2, int64_t cap,",
+                        "int scann_index_within_batch(scann_handle_t* h, scann_index_t* idx, scann_dbatch_t* db, int32_t level, const int64_t* query_ids, float radius2,",
+                        "int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* row_ids, const float* q, int64_t nq, const int64_t* query_ids, "
+                        "const int32_t* query_pos, int32_t upper, float radius2, int64_t cap, int64_t* counts, int64_t* total, float* dist2, int32_t* pos);",
+                        "the compare is an fp32 <=, inclusive", "a NaN distance never qualifies", "the entry arrays are NOT TOUCHED",
+                        "scann_index_query's first k places wherever those places qualify", "> radius2, strictly, for EVERY query q of the group",
+                        "dist2 >= lb > radius2", "#define SCANN_WITHIN_MAX_CAP ((int64_t)1 << 30)")
     P, I64, I32, F = C.c_void_p, C.c_int64, C.c_int32, C.c_float
-    assert sig["scann_index_within"] == (C.c_int, [P, P, P, I64, P, F, I64, P, P, P, P, P, P])
-    assert sig["scann_index_within_rows"] == (C.c_int, [P, P, I64, I64, I32, F, I64, P, P, P, P, P, P])
-    assert sig["scann_index_within_batch"] == (C.c_int, [P, P, P, I32, P, F, I64, P, P, P, P, P, P, P, P])
-    assert sig["scann_within_host"] == (C.c_int, [P, I64, I64, P, P, I64, P, P, I32, F, I64, P, P, P, P])
+    abi_checks.signatures({
+        "scann_index_within": (C.c_int, [P, P, P, I64, P, F, I64, P, P, P, P, P, P]),
+        "scann_index_within_rows": (C.c_int, [P, P, I64, I64, I32, F, I64, P, P, P, P, P, P]),
+        "scann_index_within_batch": (C.c_int, [P, P, P, I32, P, F, I64, P, P, P, P, P, P, P, P]),
+        "scann_within_host": (C.c_int, [P, I64, I64, P, P, I64, P, P, I32, F, I64, P, P, P, P])})
     assert _hip.WITHIN_MAX_CAP == 1 << 30
     # null arguments are refused without a device
     assert hip_lib.scann_index_within(None, None, None, 1, None, 1.0, 0, None, None, None, None, None, None) == -1
