@@ -922,18 +922,20 @@ def test_first_layer_computes_its_geometry_rows_itself(hip_lib, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["qm9", "worst", "mp2018", "corners"])
+@pytest.mark.parametrize("case", ["qm9", "worst", "mp2018", "corners", "lattices", "cells_small"])
 def test_device_packing_gives_the_host_packers_arrays(hip_lib, case):
     """Padded -> CSR on the DEVICE (scann_upload_padded: the host reads the masks, pack_padded_kernel compacts the payload arrays that
     crossed the bus as they were) against the native host packer (scann_pack_padded, i.e. what DataIterator.__getitem__ + gather_shape
     amount to: datagenerator.py:69-135, custom_layers.py:18-28): every CSR array byte for byte -- QM9-shaped, worst-case 29 x 12,
     MP2018-shaped crystals (hundreds of atoms, up to 24 neighbours), and the corners: an atom without neighbours, a one-atom structure,
-    garbage in masked slots, float32 masks.  Then the forward on the device-packed batch: the bytes of the host-packed one."""
+    garbage in masked slots, float32 masks; and the crystal batches of tests/crystal_batches.py, whose lists repeat a neighbour and name
+    the atom itself (lattices: one-atom cells among them).  Then the forward on the device-packed batch: the bytes of the host-packed one."""
+    import crystal_batches as cb
     from scann import _hip
     from scann.models.scann_model import HipModel
 
     rng = np.random.default_rng(11)
-    name = "mp2018" if case == "mp2018" else "qm9"
+    name = "mp2018" if case == "mp2018" or case in cb.DATA else "qm9"
     cfg = so.default_config(name)
     w = so.init_weights(cfg, 1234, perturb=True)
     if case == "corners":
@@ -941,6 +943,8 @@ def test_device_packing_gives_the_host_packers_arrays(hip_lib, case):
         de[2] = [[6], 0.5]
         dn[2] = [[]]           # a one-atom structure (no neighbour at all)
         dn[5][1] = []           # an atom without neighbours inside an ordinary molecule
+    elif case in cb.DATA:
+        de, dn = cb.DATA[case]()
     else:
         de, dn = so.synth_dataset({"qm9": 300, "worst": 64, "mp2018": 24}[case], 7, kind=case)
     inputs, _ = so.pad_batch(de, dn, True)

@@ -144,15 +144,22 @@ def test_gradients_at_size_equal_the_sum_over_small_sub_batches(hip_lib, monkeyp
     heavy-tailed basis-filter gradients by up to ~1.8e-5 of their rms (as far as each side sits from fp64 autograd), so they are held
     to GRAD_FLOOR under grad_errors' normalisation, the measure check_grads applies to every tensor."""
     from scann.models.scann_model import HipModel
-    from scann.parallel import slice_packed
 
     cfg, w = config(name)
     pk, targets = cache(("batch", name), BATCHES[name])
     monkeypatch.setenv("SCANN_TRAIN_FUSED", fused)
     eng = HipModel(cfg, w, device=0).engine
     eng.train_begin()
+    check_sum_over_small_sub_batches(eng, pk, targets, lambda rb: assert_side(eng, rb, name), "%s fused=%s" % (name, fused))
+
+
+def check_sum_over_small_sub_batches(eng, pk, targets, expect, label):
+    """the rule of test_gradients_at_size_equal_the_sum_over_small_sub_batches for the training handle `eng` and one batch; `expect(rb)`
+    asserts from the uploaded batch that it is on the large side"""
+    from scann.parallel import slice_packed
+
     rb = eng.upload(pk)
-    assert_side(eng, rb, name)
+    expect(rb)
     sse = eng.train_forward(rb, targets)
     eng.zero_grads()
     eng.train_backward(rb, sse, pk.n_struct)
@@ -180,14 +187,15 @@ def test_gradients_at_size_equal_the_sum_over_small_sub_batches(hip_lib, monkeyp
     for k, ref in g_big.items():
         if k.startswith(FLOAT_ATOMIC):
             err = atomic_err[k]
-            assert err <= tg.GRAD_FLOOR, (name, len(cuts), k, err)
+            assert err <= tg.GRAD_FLOOR, (label, len(cuts), k, err)
         else:
             scale = max(float(np.sqrt(np.mean(ref.astype(np.float64) ** 2))), 1e-12)
             err = float(np.max(np.abs(g_sum[k].astype(np.float64) - ref))) / scale
-            assert err <= 2e-5, (name, len(cuts), k, err)
+            assert err <= 2e-5, (label, len(cuts), k, err)
         worst[k.startswith(FLOAT_ATOMIC)] = max(worst[k.startswith(FLOAT_ATOMIC)], (err, k))
-    print("%s fused=%s: %d sub-batches, worst |sum - whole| / rms %.2e (%s; bound 2e-5), float-atomic tensors %.2e (%s; bound %.0e)" % (
-        name, fused, len(cuts), worst[False][0], worst[False][1], worst[True][0], worst[True][1], tg.GRAD_FLOOR))
+    print("%s: %d sub-batches, worst |sum - whole| / rms %.2e (%s; bound 2e-5), float-atomic tensors %.2e (%s; bound %.0e)" % (
+        label, len(cuts), worst[False][0], worst[False][1], worst[True][0], worst[True][1], tg.GRAD_FLOOR))
+    return len(cuts), worst
 
 
 # ---- 3. the plain-fp32 training kernels at size ----
