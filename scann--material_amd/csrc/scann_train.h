@@ -1,6 +1,7 @@
 // Declarations of the training-path kernels (scann_train.hip).  Internal.
 #pragma once
 #include "scann_internal.h"
+#include "scann_train_slots.h"
 
 #include <vector>
 
@@ -26,32 +27,7 @@ struct RepackDesc {
                       // -1: split-fp16 image of a [128,128] kernel, -2: of a [20,128] kernel padded to K = 32 (pack_weight_f16)
 };
 
-// Weight gradients are bit-reproducible: every launch_wgrad* stores per-slab partial sums into slots of `ctx.arena` (bump
-// allocated, never reused within a step) and records (destination, slots); wgrad_flush adds them in slab order (one launch per
-// WGRAD_REDUCE_MAX tensors; the backward pass flushes once per layer, on the side stream).  wgrad_slabs(rows) slots of 128*128 (+128 with a bias) floats per gradient.
-struct WgradReduceEntry {
-  float* dst;
-  const float* part;
-  int32_t n_slab, numel;
-};
-constexpr int WGRAD_MAX_JOBS = 8;
-constexpr int WGRAD_REDUCE_MAX = 32;  // gradient tensors per reduce launch (a layer has <= 19; the last layer + the readout 29)
-struct WgradCtx {
-  struct Job {
-    const float *X, *dY;
-    float *part, *bpart;
-    int32_t rows, chunks;
-    const int32_t* nb = nullptr;  // gated operand: row r of the X operand is X[nb[r]] * X2[r] (ang = c[j] * G', attention.py:157,
-    const float* X2 = nullptr;    // which the training forward then does not have to keep)
-  };
-  std::vector<Job> jobs;                  // queued by wgrad_add, launched together by wgrad_launch
-  float* arena = nullptr;                 // partial slots (device)
-  size_t off = 0;                         // floats used
-  std::vector<WgradReduceEntry> entries;  // one per gradient tensor since the last wgrad_flush
-};
-int wgrad_slabs(int rows);
-void wgrad_add(WgradCtx& ctx, const float* X, const float* dY, float* dW, float* db, int rows, const int32_t* nb = nullptr,
-               const float* X2 = nullptr);
+// WgradCtx, its one capped bump (reserve_slots / reserve_vec / wgrad_add) and the partitions behind every slot count: scann_train_slots.h
 void wgrad_launch(WgradCtx& ctx, hipStream_t s);
 void wgrad_flush(WgradCtx& ctx, hipStream_t s);
 
@@ -63,8 +39,6 @@ void launch_linear_sum(const float* X0, const float* W0, const float* X1, const 
                        int rows, int accumulate, hipStream_t s, const float* swish_pre = nullptr);
 void launch_swish_bwd(const float* pre, const float* dout, float* dpre, size_t n, hipStream_t s);
 void launch_dropout(float* x, size_t n, unsigned long long seed, unsigned tag, float p, hipStream_t s);
-int ln_bwd_slots(int rows);
-int attn_bwd_slots(int n_atom, int max_degree);
 void launch_ln_bwd(WgradCtx& ctx, const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int rows,
                    int accumulate, hipStream_t s);
 // dcn[e] = dang[e] * g[e] (per edge; summed per neighbour atom with launch_gather_sum), dg_tot = dang * c[nb] (+ dg_in)
@@ -83,8 +57,6 @@ void launch_attn_bwd(WgradCtx& ctx, const float* q, const float* K, const int* e
                      float* dK, float* dgamma, float* dbeta, int n_atom, int max_degree, float drop_p, unsigned drop_tag,
                      unsigned long long drop_seed, hipStream_t s);
 // ---- fused backward chains (scann_train_fused.hip) ----
-float* reserve_vec(WgradCtx& ctx, float* dst, int n_slot);  // records (dst, slots) of a gradient vector a kernel stores per workgroup
-int tile_slots(int rows);                                   // workgroups (= gamma / beta slots) of a fused kernel over `rows`
 struct RnBwdArgs {
   const float *dC, *T2, *pre1, *gamma;          // [n_atom,128] x3 (dC may be null: zeros), layer_norm gamma
   const _Float16 *Wf2Th, *Wf1Th;                // split-fp16 images of dense_2^T, dense_1^T
@@ -143,12 +115,8 @@ void launch_embed_bwd(const float* dc0, const int* atomic, int n_atom, const flo
                       unsigned drop_tag, float drop_p, hipStream_t s, WgradCtx* det = nullptr);
 void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb, float* dWe, float* dbe, float* dWr, float* dbr,
                               float* dWde, float* dbde, hipStream_t s, WgradCtx* det = nullptr, int n_species = 0);
-float* reserve_slots(WgradCtx& ctx, float* dst, int n_slot, int numel);  // records (dst, n_slot slots of numel floats)
 void det_flush(WgradCtx& ctx, hipStream_t s);                            // adds every recorded slot set in slot order
 void launch_scalar_sum(const float* x, int n, float* dst, hipStream_t s);  // *dst += x[0] + ... + x[n - 1], fixed order
-// floats of det slots one backward over this batch shape reserves at most
-size_t det_slot_floats(int n_atom, int n_edge, int n_layer, int n_species, int emb_dim, bool g_update, bool general, bool cgcnn,
-                       bool ring);
 void launch_sse(const float* y, const float* t, int n, double* out, float* t_dev, float* dy, double* host_stat, hipStream_t s);
 void launch_dy(const float* y, const float* t, int n, float scale, const double* stat, float* dy, hipStream_t s);
 void launch_adam(float* w, float* g, float* m, float* v, const float* l2mask, size_t n, float lr_hat, float b1, float b2,

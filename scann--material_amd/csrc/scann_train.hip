@@ -423,18 +423,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(WgradReduceSet set) 
   }
 }
 
-int wgrad_chunks(int rows) {
-  // slab per workgroup: at least 4 chunks of 64 rows and <= 80 slabs per gradient (a layer's launch is ~7 gradients: a few hundred
-  // workgroups), so that the partial slots (64 KB each) the reduce re-reads stay small whatever the batch size.  Measured at batch
-  // 128 (profiles/r02_notes.md): 1 -> 4 chunks for the atom-row gradients, 36 -> 9 slabs each, -20 us per step.
-  const int tiles = (rows + 63) / 64;
-  return std::max(std::min(4, tiles), (tiles + 79) / 80);
-}
-int wgrad_slabs(int rows) {
-  const int chunks = wgrad_chunks(rows);
-  return (rows + 64 * chunks - 1) / (64 * chunks);
-}
-
 // the 128-wide gradient vectors (biases, LayerNorm gamma / beta): one workgroup of 1,024 threads per vector, eight groups of 128
 // walking the slots k = group, group + 8, ... (four loads in flight each), then the eight group sums added in group order --
 // the slot count of these is the WORKGROUP count of the producing kernel (hundreds), far more than the <= 80 slabs of a matrix
@@ -508,6 +496,7 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_all_kernel(WgradReduceSet s
 }
 
 void wgrad_flush(WgradCtx& ctx, hipStream_t s) {
+  if (ctx.overrun) return;
   // the (destination, slots) records travel as kernel arguments: no table copy, so a flush can follow each layer's gradient
   // launch on the side stream
   std::vector<WgradReduceEntry> mats, vecs;
@@ -550,25 +539,9 @@ void wgrad_flush(WgradCtx& ctx, hipStream_t s) {
   ctx.entries.clear();
 }
 
-// queue one gradient dW += X^T dY (db += column sums of dY when db) for the next wgrad_launch
-void wgrad_add(WgradCtx& ctx, const float* X, const float* dY, float* dW, float* db, int rows, const int32_t* nb, const float* X2) {
-  if (rows <= 0) return;
-  WgradCtx::Job j{};
-  j.X = X; j.dY = dY; j.rows = rows; j.chunks = wgrad_chunks(rows);
-  j.nb = nb; j.X2 = X2;
-  const int n_slab = wgrad_slabs(rows);
-  j.part = ctx.arena + ctx.off;
-  ctx.entries.push_back(WgradReduceEntry{dW, j.part, n_slab, D * D});
-  ctx.off += (size_t)n_slab * D * D;
-  if (db) {
-    j.bpart = ctx.arena + ctx.off;
-    ctx.entries.push_back(WgradReduceEntry{db, j.bpart, n_slab, D});
-    ctx.off += (size_t)n_slab * D;
-  }
-  ctx.jobs.push_back(j);
-}
-// one launch (per WGRAD_MAX_JOBS) for everything queued
+// one launch (per WGRAD_MAX_JOBS) for everything queued (wgrad_add, scann_train_slots.h)
 void wgrad_launch(WgradCtx& ctx, hipStream_t s) {
+  if (ctx.overrun) return;
   for (size_t j0 = 0; j0 < ctx.jobs.size(); j0 += WGRAD_MAX_JOBS) {
     const int n = (int)std::min<size_t>(WGRAD_MAX_JOBS, ctx.jobs.size() - j0);
     WgradSet set{};
@@ -723,36 +696,24 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
   for (int rr = 0; rr < 32; ++rr) tot += sred[which][rr][col];
   (which ? dbeta : dgamma)[(size_t)blockIdx.x * D + col] = tot;  // this workgroup's slot (summed in slot order by wgrad_reduce_kernel)
 }
-void wgrad_flush(WgradCtx& ctx, hipStream_t s);
-// row groups of 32 per workgroup: with per-workgroup partial slots instead of atomics the launch no longer has to stay small
-// (round 1 capped it at ~160 workgroups); about 1,500 workgroups fill the chip several times over
-static int ln_bwd_groups(int rows) { return std::min(32, std::max(1, (rows + 32 * 1536 - 1) / (32 * 1536))); }
-int ln_bwd_slots(int rows) {
-  const int groups = ln_bwd_groups(rows);
-  return (rows + 32 * groups - 1) / (32 * groups);
-}
-// records (dst, slots) of one parameter-gradient vector whose per-workgroup partial sums a kernel is about to store
-float* reserve_vec(WgradCtx& ctx, float* dst, int n_slot) {
-  float* part = ctx.arena + ctx.off;
-  ctx.entries.push_back(WgradReduceEntry{dst, part, n_slot, D});
-  ctx.off += (size_t)n_slot * D;
-  return part;
-}
+// (row groups of 32 per workgroup: ln_bwd_split, scann_train_slots.h)
 void launch_ln_bwd(WgradCtx& ctx, const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int rows,
                    int accumulate, hipStream_t s) {
   if (rows <= 0) return;
-  const int groups = ln_bwd_groups(rows), n_wg = ln_bwd_slots(rows);
+  const int groups = ln_bwd_groups(rows), n_wg = ln_bwd_split(rows).n;
   float* gp = reserve_vec(ctx, dgamma, n_wg);
   float* bp = reserve_vec(ctx, dbeta, n_wg);
+  if (ctx.overrun) return;
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(n_wg), dim3(256), 0, s, x, gamma, dy, dx, gp, bp, rows, groups, accumulate, LnBwdFuse{});
 }
 // LayerNorm_g backward of LocalAttention with its neighbours fused: dy = dang * c[nb] (+ dg_in) in, dx = dT and dV = dT * swish'(V) out
 void launch_ln_bwd_edge(WgradCtx& ctx, const float* T, const float* gamma, const float* dang, const float* c, const int* nb,
                         const float* dg_in, const float* V, float* dT, float* dV, float* dgamma, float* dbeta, int rows, hipStream_t s) {
   if (rows <= 0) return;
-  const int groups = ln_bwd_groups(rows), n_wg = ln_bwd_slots(rows);
+  const int groups = ln_bwd_groups(rows), n_wg = ln_bwd_split(rows).n;
   float* gp = reserve_vec(ctx, dgamma, n_wg);
   float* bp = reserve_vec(ctx, dbeta, n_wg);
+  if (ctx.overrun) return;
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(n_wg), dim3(256), 0, s, T, gamma, (const float*)nullptr, dT, gp, bp, rows, groups, 0,
                      LnBwdFuse{dang, c, nb, dg_in, V, dV});
 }
@@ -1054,16 +1015,7 @@ __global__ __launch_bounds__(256) void attn_bwd16_kernel(const float* __restrict
   (which < 2 ? dgamma : dbeta)[(size_t)blockIdx.x * D + 2 * ln + (which & 1)] = tot;  // this workgroup's slot
 }
 
-// atoms per wave of attn_bwd16_kernel: the wave walks its atoms one after the other (each a chain of loads and lane reductions), so
-// as few as fill the chip a few times over (~1,000 workgroups); the per-workgroup gamma / beta slots are tiny
-static int attn_apw16(int n_atom) { return std::min(8, std::max(1, (n_atom + 4095) / 4096)); }
-int attn_bwd_slots(int n_atom, int max_degree) {
-  if (max_degree <= 16) {
-    const int apw16 = attn_apw16(n_atom);
-    return (n_atom + 4 * apw16 - 1) / (4 * apw16);  // one slot per workgroup
-  }
-  return 4 * ((n_atom + 4 * 2 - 1) / (4 * 2));      // one slot per wave
-}
+// (atoms per wave, workgroups and slots: attn_bwd_split / attn_bwd_slots, scann_train_slots.h)
 void launch_attn_bwd(WgradCtx& ctx, const float* q, const float* K, const int* edge_offset, const float* dctx, const float* gamma, float* dq,
                      float* dK, float* dgamma, float* dbeta, int n_atom, int max_degree, float drop_p, unsigned drop_tag,
                      unsigned long long drop_seed, hipStream_t s) {
@@ -1071,15 +1023,14 @@ void launch_attn_bwd(WgradCtx& ctx, const float* q, const float* K, const int* e
   const int n_slot = attn_bwd_slots(n_atom, max_degree);
   float* gp = reserve_vec(ctx, dgamma, n_slot);
   float* bp = reserve_vec(ctx, dbeta, n_slot);
-  if (max_degree <= 16) {
-    const int apw16 = attn_apw16(n_atom);
-    hipLaunchKernelGGL(attn_bwd16_kernel, dim3((n_atom + 4 * apw16 - 1) / (4 * apw16)), dim3(256), 0, s, q, K, edge_offset, dctx,
-                       gamma, dq, dK, gp, bp, n_atom, apw16, drop_p, drop_tag, drop_seed);
-    return;
-  }
-  const int apw = 2;
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3((n_atom + 4 * apw - 1) / (4 * apw)), dim3(256), 0, s, q, K, edge_offset, dctx,
-                     gamma, dq, dK, gp, bp, n_atom, apw, drop_p, drop_tag, drop_seed);
+  if (ctx.overrun) return;
+  const int apw = attn_bwd_apw(n_atom, max_degree), n_wg = attn_bwd_split(n_atom, max_degree).n;
+  if (max_degree <= 16)
+    hipLaunchKernelGGL(attn_bwd16_kernel, dim3(n_wg), dim3(256), 0, s, q, K, edge_offset, dctx, gamma, dq, dK, gp, bp, n_atom, apw,
+                       drop_p, drop_tag, drop_seed);
+  else
+    hipLaunchKernelGGL(attn_bwd_kernel, dim3(n_wg), dim3(256), 0, s, q, K, edge_offset, dctx, gamma, dq, dK, gp, bp, n_atom, apw,
+                       drop_p, drop_tag, drop_seed);
 }
 
 // ---- readout backward: one workgroup per structure ------------------------------------------------------------------
@@ -1319,8 +1270,8 @@ void launch_basis_bwd(const BasisParams& p, const float* dist, const float* weig
                       float* dbd, float* dWw, float* dbw, hipStream_t s, WgradCtx* det) {
   if (n_edge > 0)
   {
-    const int chunks = n_edge >= (1 << 20) ? 4 : 1;  // the per-edge arithmetic, not the final atomics, bounds this kernel: 4 x fewer workgroups measured 105 vs 37 us at 18 k edges
-    const int n_wg = (n_edge + 32 * chunks - 1) / (32 * chunks);
+    const Split sp = basis_split(n_edge);
+    const int chunks = sp.per / 32, n_wg = sp.n;
     if (det) {  // the same partition (a function of n_edge only), one slot per workgroup and gradient row, summed in workgroup order
       float* part = nullptr;
       for (int k = 0; k < NG; ++k) {
@@ -1330,6 +1281,7 @@ void launch_basis_bwd(const BasisParams& p, const float* dist, const float* weig
       for (int k = 0; k < NG; ++k) reserve_vec(*det, dWw + k * D, n_wg);
       reserve_vec(*det, dbd, n_wg);
       reserve_vec(*det, dbw, n_wg);
+      if (det->overrun) return;
       hipLaunchKernelGGL(basis_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, p, dist, weight, dgeom, n_edge, chunks, part);
       det_flush(*det, s);
       return;
@@ -1394,11 +1346,12 @@ __global__ __launch_bounds__(128) void base_geom_bwd_det_kernel(const float* __r
 void launch_base_geom_bwd(const float* gd, const float* Wf, const float* bf, const float* wgt, const float* dgeomL, int n_edge,
                           float* dWf, float* dbf, hipStream_t s, WgradCtx* det) {
   if (n_edge <= 0) return;
-  const int n_wg = (n_edge + 31) / 32;
+  const int n_wg = base_geom_split(n_edge).n;
   if (det) {
     float* part = reserve_vec(*det, dWf, n_wg);
     for (int k = 1; k < NG; ++k) reserve_vec(*det, dWf + k * D, n_wg);
     reserve_vec(*det, dbf, n_wg);
+    if (det->overrun) return;
     hipLaunchKernelGGL(base_geom_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, gd, Wf, bf, wgt, dgeomL, n_edge, part);
     det_flush(*det, s);
     return;
@@ -1533,17 +1486,19 @@ void launch_embed_bwd(const float* dc0, const int* atomic, int n_atom, const flo
                       float* dlut, int n_species, int emb_dim, float* dEmb, float* dW, float* db, unsigned long long drop_seed,
                       unsigned drop_tag, float drop_p, hipStream_t s, WgradCtx* det) {
   if (n_atom <= 0) return;
-  const int run = std::max(32, (n_atom + 127) / 128);  // <= 128 workgroups
-  const int n_wg = (n_atom + run - 1) / run;
+  const Split sp = embed_table_split(n_atom);  // <= 128 workgroups
+  const int run = sp.per, n_wg = sp.n;
   if (det) {
     // the species table: one slot per workgroup of the same partition (a function of n_atom), added into dlut in workgroup order
     // before the per-species launch reads it; then that launch's kernel / bias terms, one slot per species, in species order
     float* tab = reserve_slots(*det, dlut, n_wg, n_species * D);
+    if (det->overrun) return;
     hipLaunchKernelGGL(embed_scatter_det_kernel, dim3(n_wg), dim3(128), (size_t)n_species * D * sizeof(float), s, dc0, atomic, tab,
                        n_atom, run, n_species, drop_seed, drop_tag, drop_p);
     det_flush(*det, s);
     float* part = reserve_slots(*det, dW, n_species, emb_dim * D);
     reserve_vec(*det, db, n_species);
+    if (det->overrun) return;
     hipLaunchKernelGGL(embed_bwd_det_kernel, dim3(n_species), dim3(128), D * sizeof(float), s, emb, W, b, dlut, n_species, emb_dim,
                        dEmb, part);
     det_flush(*det, s);
@@ -1729,12 +1684,12 @@ __global__ __launch_bounds__(128) void embed_general_bwd_det_kernel(EmbedArgs a,
     }
   }
 }
-int embed_general_det_run(int n_atom) { return std::max(32, ((n_atom + 127) / 128 + 7) / 8 * 8); }  // <= 128 workgroups
 void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb, float* dWe, float* dbe, float* dWr, float* dbr,
                               float* dWde, float* dbde, hipStream_t s, WgradCtx* det, int n_species) {
   if (a.n_atom <= 0) return;
   if (det) {
-    const int run = embed_general_det_run(a.n_atom), n_wg = (a.n_atom + run - 1) / run;
+    const Split sp = embed_general_split(a.n_atom);  // <= 128 workgroups
+    const int run = sp.per, n_wg = sp.n;
     const int cin = a.emb_dim + (a.ring ? 10 : 0);
     EmbedDetSlots o{};
     o.run = run;
@@ -1754,6 +1709,7 @@ void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb,
       o.br = reserve_slots(*det, dbr, n_wg, 10);
       o.Wr = reserve_slots(*det, dWr, n_wg, 20);
     }
+    if (det->overrun) return;
     hipLaunchKernelGGL(embed_general_bwd_det_kernel, dim3(n_wg), dim3(128), 0, s, a, dc0, o);
     det_flush(*det, s);
     return;
@@ -1762,13 +1718,8 @@ void launch_embed_general_bwd(const EmbedArgs& a, const float* dc0, float* dEmb,
 }
 
 // ---- deterministic mode: slot records and their fixed-order sums --------------------------------------------------------------
-float* reserve_slots(WgradCtx& ctx, float* dst, int n_slot, int numel) {
-  float* part = ctx.arena + ctx.off;
-  ctx.entries.push_back(WgradReduceEntry{dst, part, n_slot, numel});
-  ctx.off += (size_t)n_slot * numel;
-  return part;
-}
 void det_flush(WgradCtx& ctx, hipStream_t s) {
+  if (ctx.overrun) return;
   // 128-wide rows: vec_reduce_kernel (eight groups of slots per column, group sums in group order); other sizes: wgrad_reduce_kernel
   // (a thread per element, the slots in order) -- the same sums as wgrad_flush's, with the grid sized to the largest record
   std::vector<WgradReduceEntry> mats, vecs;
@@ -1808,28 +1759,6 @@ __global__ __launch_bounds__(256) void scalar_sum_kernel(const float* __restrict
 void launch_scalar_sum(const float* x, int n, float* dst, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(scalar_sum_kernel, dim3(1), dim3(256), 0, s, x, n, dst);
 }
-size_t det_slot_floats(int n_atom, int n_edge, int n_layer, int n_species, int emb_dim, bool g_update, bool general, bool cgcnn,
-                       bool ring) {
-  // upper bound of what one backward's det launches reserve (bump allocated, never reused within the step)
-  size_t f = 0;
-  if (n_edge > 0) {
-    const int chunks = n_edge >= (1 << 20) ? 4 : 1;
-    if (g_update) f += (size_t)(2 * NG + 2) * D * ((n_edge + 32 * chunks - 1) / (32 * chunks));
-    else f += (size_t)n_layer * (NG + 1) * D * ((n_edge + 31) / 32);
-  }
-  if (n_atom > 0) {
-    if (general) {
-      const int run = embed_general_det_run(n_atom), n_wg = (n_atom + run - 1) / run;
-      const int cin = emb_dim + (ring ? 10 : 0);
-      f += (size_t)n_wg * ((size_t)(1 + cin) * D + (cgcnn ? (size_t)93 * emb_dim : (size_t)n_species * emb_dim) + (ring ? 30 : 0));
-    } else {
-      const int run = std::max(32, (n_atom + 127) / 128), n_wg = (n_atom + run - 1) / run;
-      f += (size_t)n_wg * n_species * D + (size_t)n_species * (emb_dim + 1) * D;
-    }
-  }
-  return f;
-}
-
 // ---- loss ------------------------------------------------------------------------------------------------------------------
 // out = {sum (y - t)^2, n, sum |y - t|}.  Optional extras of scann_train_step (null otherwise): t may be pinned host memory, copied to t_dev on the
 // way; host_stat (pinned) receives the pair without a copy operation; dy = d rmse / d y for a single-rank step (the batch IS the

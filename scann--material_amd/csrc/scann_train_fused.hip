@@ -583,37 +583,37 @@ __global__ __launch_bounds__(256) void atom_gather3_kernel(const float4* __restr
   dP1[i] = u;
 }
 
-// 32-row tiles while the launch fits one round of workgroups (three per CU): it is then the latency chain of a tile, and a 32-row
-// tile's chain is shorter (same choice as launch_atom / the edge-tile plan); 64-row tiles beyond
-static int fused_tile_rows(int rows) { return rows <= 32 * 768 ? 32 : 64; }
-int tile_slots(int rows) { return (rows + fused_tile_rows(rows) - 1) / fused_tile_rows(rows); }
-
+// (32- or 64-row tiles, one gamma / beta slot per tile: fused_split, scann_train_slots.h)
 void launch_rn_bwd(WgradCtx& ctx, RnBwdArgs a, float* dgamma, float* dbeta, hipStream_t s) {
   if (a.n_atom <= 0) return;
-  const int n = tile_slots(a.n_atom);
-  a.dgamma = reserve_vec(ctx, dgamma, n);
-  a.dbeta = reserve_vec(ctx, dbeta, n);
-  if (fused_tile_rows(a.n_atom) == 32) hipLaunchKernelGGL(rn_bwd_kernel<1>, dim3(n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(rn_bwd_kernel<2>, dim3(n), dim3(256), 0, s, a);
+  const Split sp = fused_split(a.n_atom);
+  a.dgamma = reserve_vec(ctx, dgamma, sp.n);
+  a.dbeta = reserve_vec(ctx, dbeta, sp.n);
+  if (ctx.overrun) return;
+  if (sp.per == 32) hipLaunchKernelGGL(rn_bwd_kernel<1>, dim3(sp.n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(rn_bwd_kernel<2>, dim3(sp.n), dim3(256), 0, s, a);
 }
 void launch_edge_bwd(WgradCtx& ctx, EdgeBwdArgs a, float* dgamma, float* dbeta, hipStream_t s) {
   if (a.n_edge <= 0) return;
-  const int n = tile_slots(a.n_edge);
-  a.dgamma = reserve_vec(ctx, dgamma, n);
-  a.dbeta = reserve_vec(ctx, dbeta, n);
-  if (fused_tile_rows(a.n_edge) == 32) hipLaunchKernelGGL((edge_bwd_kernel<1, false>), dim3(n), dim3(256), 0, s, a, AttnPart{});
-  else hipLaunchKernelGGL((edge_bwd_kernel<2, false>), dim3(n), dim3(256), 0, s, a, AttnPart{});
+  const Split sp = fused_split(a.n_edge);
+  a.dgamma = reserve_vec(ctx, dgamma, sp.n);
+  a.dbeta = reserve_vec(ctx, dbeta, sp.n);
+  if (ctx.overrun) return;
+  if (sp.per == 32) hipLaunchKernelGGL((edge_bwd_kernel<1, false>), dim3(sp.n), dim3(256), 0, s, a, AttnPart{});
+  else hipLaunchKernelGGL((edge_bwd_kernel<2, false>), dim3(sp.n), dim3(256), 0, s, a, AttnPart{});
 }
 void launch_attn_edge_bwd(WgradCtx& ctx, EdgeBwdArgs a, AttnPart b, int n_tile, float* dgamma_g, float* dbeta_g, float* dgamma_ln,
                           float* dbeta_ln, hipStream_t s, hipEvent_t done) {
-  if (a.n_edge <= 0 || n_tile <= 0) {
+  if (a.n_edge > 0 && n_tile > 0) {
+    a.dgamma = reserve_vec(ctx, dgamma_g, n_tile);
+    a.dbeta = reserve_vec(ctx, dbeta_g, n_tile);
+    b.dgamma = reserve_vec(ctx, dgamma_ln, n_tile);
+    b.dbeta = reserve_vec(ctx, dbeta_ln, n_tile);
+  }
+  if (a.n_edge <= 0 || n_tile <= 0 || ctx.overrun) {  // no kernel to signal `done`: a marker in its place
     if (done) (void)hipEventRecord(done, s);
     return;
   }
-  a.dgamma = reserve_vec(ctx, dgamma_g, n_tile);
-  a.dbeta = reserve_vec(ctx, dbeta_g, n_tile);
-  b.dgamma = reserve_vec(ctx, dgamma_ln, n_tile);
-  b.dbeta = reserve_vec(ctx, dbeta_ln, n_tile);
   // `done` (or null): recorded by the kernel's OWN completion signal (hipExtLaunchKernelGGL's stop event) -- a side stream can wait for
   // it without a marker packet behind the kernel on this stream: 4.0 instead of 6.7 us per fork (tools/fork_probe.hip, mode 3 vs 0)
   if (done) hipExtLaunchKernelGGL((edge_bwd_kernel<1, true>), dim3(n_tile), dim3(256), 0, s, nullptr, done, 0, a, b);

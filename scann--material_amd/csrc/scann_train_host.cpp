@@ -22,18 +22,8 @@ int ensure_train_ws(scann_handle* h, scann_dbatch* db, scann_train_ws** out) {
   // per-layer tensors kept by the training forward (edge_kernel_lean on 64-edge tiles): q [A,128]; V, T, ang, K [E,128]
   // (base branch: geomL in the V slices, T unused)
   const size_t Lk = (size_t)h->cfg.n_attention;
-  // weight-gradient partial slots: per layer <= 2 gradients over the edge rows (key, filter_geo geometry third; base: key) and
-  // <= 5 over the atom rows (filter_geo centre / neighbour thirds, query, ResidualNorm dense_1 / dense_2), readout 3 over atoms
-  // and 1 over structures; each with a bias row per slab
   const size_t Lc = (size_t)h->cfg.n_attention;
-  w.wpart_floats = (size_t)(D * D + D) * (Lc * (2 * (size_t)wgrad_slabs(std::max(db->n_edge, 1)) + 5 * (size_t)wgrad_slabs(db->n_atom)) +
-                                           3 * (size_t)wgrad_slabs(db->n_atom) + (size_t)wgrad_slabs(db->n_struct)) +
-                   // LayerNorm gamma / beta partials: per layer ln_bwd over edges and atoms, attention backward over atoms
-                   (size_t)2 * D * Lc * ((size_t)std::max(ln_bwd_slots(std::max(db->n_edge, 1)), tile_slots(std::max(db->n_edge, 1))) +
-                                         (size_t)std::max(ln_bwd_slots(db->n_atom), tile_slots(db->n_atom)) +
-                                         (size_t)attn_bwd_slots(db->n_atom, db->max_degree)) +
-                   (size_t)D * db->n_struct +  // predict_property/kernel: one slot per structure (readout_bwd_kernel)
-                   (size_t)4 * D * Lc * (size_t)db->n_tile;  // attention + edge backward in one launch: four vectors, one slot per tile
+  w.wpart_floats = wpart_slot_floats(db->n_atom, db->n_edge, db->n_struct, h->cfg.n_attention, db->max_degree, db->n_tile);
   // the operands of a layer's weight gradients live until the end of the step (sets of their own per layer): the gradient launches on
   // the side stream never have to be waited for before a buffer is reused
   // the modular backward (SCANN_TRAIN_FUSED=0) reads T and ang as tensors; the fused chains form them again
@@ -393,6 +383,431 @@ static int gen_backward(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w
   return SCANN_OK;
 }
 
+// ---- the 128-wide backward: a stream plan, a context, stages; backward_impl below them reads as the order of stages and hand-offs ----
+
+namespace {
+
+// The streams of one backward and every hand-off between them: the only code of the backward that records an event or makes a stream
+// wait for one (a launch_* given a `done` event records it by the kernel's own completion signal).
+// Weight-gradient GEMMs are off the critical path (only the final reduce needs them): with the kept-activation forward their operands
+// are never overwritten inside a layer, so they run on a side stream beside the data-gradient chain, which alone does not fill the
+// chip at batch 128; the second side stream takes the layers' reductions and the basis leaf.
+// One stream (the data-gradient mode, or a handle without side streams) is ONE state: side and side2 are null, every hand-off returns
+// the main stream, next_ev() null, and nothing is recorded or waited for.
+struct BwdStreams {
+  hipStream_t main, side = nullptr, side2 = nullptr;
+
+  BwdStreams(const scann_handle* h, bool single) : main(h->streams[0]), ring(h->train_ev) {
+    if (!single && h->train_aux) side = h->train_aux, side2 = h->train_aux2;
+  }
+  // the next event of the ring: for a producer launched with it as its own completion signal (launch_atom_gather3 /
+  // launch_attn_edge_bwd, `done`), so that after_event() needs no marker packet behind the producer on its stream -- 4.0 instead of
+  // 6.7 us per hand-off (tools/fork_probe.hip, mode 3 vs 0)
+  hipEvent_t next_ev() { return side ? ring[ev_i++ % ring.size()] : nullptr; }
+  // `to` waits for everything on `from` so far; returns where to launch: `to`, or `from` where there is no `to`.  From the main stream
+  // this costs it ~7 us (tools/fork_probe.hip)
+  hipStream_t after(hipStream_t from, hipStream_t to) {
+    if (!side) return main;
+    if (!to) return from;
+    wait_all(from, to);
+    side2_given = side2_given || to == side2;
+    return to;
+  }
+  // `to` waits for the completion event `e` of one launch
+  hipStream_t after_event(hipEvent_t e, hipStream_t to) {
+    if (!side || !to) return main;
+    (void)hipStreamWaitEvent(to, e, 0);
+    return to;
+  }
+  // the stream of the basis leaf: the second side stream behind `produced`, the completion event of the kernel that wrote the leaf's
+  // input (null: behind everything on the main stream so far); leaf_done() marks the leaf's end there for the closing join
+  hipStream_t leaf(hipEvent_t produced) {
+    if (!side2) return main;
+    if (produced) return after_event(produced, side2);
+    wait_all(main, side2);
+    return side2;
+  }
+  void leaf_done(hipStream_t ls) {
+    if (ls == main) return;
+    leaf_ev = next_ev();
+    (void)hipEventRecord(leaf_ev, ls);
+  }
+  // the closing join: the main stream waits for the side stream, and for the second one by what it was given -- everything after()
+  // handed it (the leaf, earlier on that stream, included), or else the leaf alone
+  void join_all() {
+    if (!side) return;
+    wait_all(side, main);
+    if (side2_given) wait_all(side2, main);
+    else if (leaf_ev) (void)hipStreamWaitEvent(main, leaf_ev, 0);
+  }
+
+ private:
+  void wait_all(hipStream_t from, hipStream_t to) {
+    hipEvent_t e = next_ev();
+    (void)hipEventRecord(e, from);
+    (void)hipStreamWaitEvent(to, e, 0);
+  }
+  const std::vector<hipEvent_t>& ring;  // fork / join events of the handle
+  size_t ev_i = 0;
+  bool side2_given = false;
+  hipEvent_t leaf_ev = nullptr;
+};
+
+// projections of layer l + 1 that still have to be added to dC (d loss / d centres_{l+1}): folded into the next rn_bwd_kernel, or
+// launched by flush() where nobody folds them in
+struct Pend {
+  int n = 0;
+  const float* X[3];
+  const _Float16* Wh[3];
+  const float* W[3];
+  bool fresh = false;  // dC holds nothing yet: the terms ARE d loss / d centres (first use: dpreA.Wa^T of the readout)
+  void add(const float* x, const _Float16* wh, const float* w) {
+    X[n] = x; Wh[n] = wh; W[n] = w;
+    ++n;
+  }
+  void fold_into(RnBwdArgs& ra, const float* dC) {
+    ra.dC = fresh ? nullptr : dC;
+    ra.n_pre = n;
+    for (int t = 0; t < n; ++t) { ra.X[t] = X[t]; ra.Wh[t] = Wh[t]; }
+    n = 0;
+    fresh = false;
+  }
+  void flush(float* dC, int rows, hipStream_t s) {
+    if (n)
+      launch_linear_sum(X[0], W[0], n > 1 ? X[1] : nullptr, n > 1 ? W[1] : nullptr, n > 2 ? X[2] : nullptr, n > 2 ? W[2] : nullptr, dC, rows,
+                        fresh ? 0 : 1, s);
+    n = 0;
+    fresh = false;
+  }
+};
+
+// The operands of a layer's weight gradients exist once per layer (set L = the readout): the gradient launch of layer l runs on the
+// side stream beside the data-gradient chains of the layers below and nothing it reads is overwritten before the end of the step.
+struct BwdOperands {
+  float *t3, *t4, *dQ, *dP1, *dP3;  // [A,128]
+  float *edK, *eU;                  // [E,128]
+};
+
+// What the stages of one backward share.  ig non-null: the data-gradient mode (InGrad).
+struct Bwd {
+  scann_handle_t* const h;
+  scann_dbatch_t* const db;
+  scann_train_ws& w;
+  const InGrad* const ig;
+  const scann_config_t& c;
+  const int L, A, E, B;
+  const size_t nA, nE;
+  float* const G;   // the gradient vector the parameter gradients go to
+  const bool fused;  // fused chains (scann_train_fused.hip); SCANN_TRAIN_FUSED=0 selects the modular one-kernel-per-operation backward
+  // On the forward's 32-row tile plan (whole atoms per tile, every degree <= 16) the softmax / LayerNorm backward of a tile's atoms
+  // runs at the head of the tile's edge_bwd workgroup: one launch less per layer.
+  const bool fuse_attn;
+  BwdStreams st;
+  WgradCtx wg;             // weight-gradient jobs and partial slots (w.wpart)
+  WgradCtx dct;            // deterministic mode: slots of the six reductions that otherwise end in float atomics (scann_train.h)
+  WgradCtx* det = nullptr;
+  // named temporaries
+  float *dC, *dCtx;                  // [A,128] d loss / d centres leaving / d context of the layer at hand
+  float *edAng, *eT, *edGa, *edGb;   // [E,128]
+  Pend pend;
+  const float* dG_in = nullptr;  // gradient w.r.t. the geometry leaving layer l (none for the last layer)
+  hipStream_t tail_s;            // where the embedding chain goes
+  bool basis_done = false;
+
+  Bwd(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, const InGrad* ig)
+      : h(h), db(db), w(w), ig(ig), c(h->cfg), L(c.n_attention), A(db->n_atom), E(db->n_edge), B(db->n_struct),
+        nA((size_t)A * D), nE((size_t)E * D), G(ig ? h->ig_grad : h->t_grad), fused(h->train_fused),
+        fuse_attn(fused && c.g_update && db->tile_rows == 32 && db->n_big == 0 && db->max_degree <= 16 && E > 0),
+        st(h, ig != nullptr), dC(w.tA[0]), dCtx(w.tA[1]), edAng(w.tE[0]), eT(w.tE[1]), edGa(w.tE[2]), edGb(w.tE[3]),
+        tail_s(st.main) {
+    wg.arena = w.wpart;
+    wg.cap = w.wpart_floats;
+  }
+  float* g(const std::string& name) const { return G + spec_offset(h, name); }
+  template <class... T>
+  void wadd(T... a) {  // a weight gradient's GEMM job (none in the data-gradient mode)
+    if (!ig) wgrad_add(wg, a...);
+  }
+  BwdOperands operands(int l) const {
+    float* const* a = &w.tA[5 + 5 * (size_t)l];
+    float* const* e = &w.tE[4 + 2 * (size_t)l];
+    return BwdOperands{a[0], a[1], a[2], a[3], a[4], e[0], e[1]};
+  }
+};
+
+// layer l: its parameters, its operand set and the tensors the training forward kept (nothing is recomputed)
+struct BwdLayer : BwdOperands {
+  const int l;
+  const LayerParams& p;
+  const scann_handle::LayerT& pt;
+  const std::string la, rn;
+  const float *c_in, *ctx;      // centres entering LocalAttention l; its output (after layer_norm)
+  const float *Gin, *Gout;      // geometry entering / leaving layer l (= layer_norm_g output); null on the base branch
+  const float *qL, *KL, *VL;    // q [A,128]; K, V (base branch: geomL) [E,128]
+  const float *angL, *TL;       // [E,128]; null: formed again from c[j] and G' / from V and G
+  BwdLayer(const Bwd& b, int l_)
+      : BwdOperands(b.operands(l_)), l(l_), p(b.h->layers[l_]), pt(b.h->layersT[l_]), la("local_attention_" + std::to_string(l_) + "/"),
+        rn("residual_norm_" + std::to_string(l_) + "/"), c_in(b.db->dbg_c + (size_t)l_ * b.nA), ctx(b.db->dbg_ctx + (size_t)l_ * b.nA),
+        Gin(b.c.g_update ? b.db->dbg_g + (size_t)l_ * b.nE : nullptr), Gout(b.c.g_update ? b.db->dbg_g + (size_t)(l_ + 1) * b.nE : nullptr),
+        qL(b.db->keep_q + (size_t)l_ * b.nA), KL(b.db->keep_K + (size_t)l_ * b.nE), VL(b.db->keep_V + (size_t)l_ * b.nE),
+        angL(b.db->keep_ang ? b.db->keep_ang + (size_t)l_ * b.nE : nullptr), TL(b.db->keep_T ? b.db->keep_T + (size_t)l_ * b.nE : nullptr) {}
+};
+
+// deterministic mode: the slots are allocated with the batch's workspace on the first such backward and sized from the batch shape alone
+int bwd_det_arena(Bwd& b) {
+  if (!b.h->deterministic || b.ig) return SCANN_OK;
+  scann_handle_t* h = b.h;
+  scann_train_ws& w = b.w;
+  const scann_config_t& c = b.c;
+  const bool general = c.use_ring || c.feature_cgcnn;
+  const size_t need = det_slot_floats(b.A, b.E, b.L, c.n_atoms, c.embedding_dim, c.g_update, general, c.feature_cgcnn, c.use_ring);
+  if (need > w.det_floats) {
+    // (the slots of a previous step on this batch may still be read by its reductions: the stream order of the main stream
+    //  alone does not cover the side streams, so wait for the device before the block goes back to the cache)
+    if (w.det_part) {
+      HIPCHK(h, hipDeviceSynchronize());
+      cached_free(w.det_part);
+      w.det_part = nullptr;
+      w.det_floats = 0;
+    }
+    HIPCHK(h, cached_malloc((void**)&w.det_part, need * 4));
+    w.det_floats = need;
+  }
+  b.dct.arena = w.det_part;
+  b.dct.cap = w.det_floats;
+  b.det = &b.dct;
+  return SCANN_OK;
+}
+
+// ---- readout (scann_model.py:424-447, attention.py:267-318): "layer L" of the operand-set scheme ----
+void bwd_readout(Bwd& b) {
+  scann_handle_t* h = b.h;
+  scann_dbatch_t* db = b.db;
+  hipStream_t s = b.st.main;
+  const BwdOperands o = b.operands(b.L);
+  float *const dgq = b.w.tA[4], *const dgk = o.t3, *const dpreA = o.dQ;
+  // the training forward kept preA = cL.Wa + ba and z = swish(preA); gq, gk, ga, y are still in the batch workspace
+  const float *preA = db->keep_preA, *z = db->keep_z;
+  const float* cL = db->dbg_c + (size_t)b.L * b.nA;  // centres entering after_Lc
+  ReadoutBwdArgs ra{};
+  ra.mol_offset = db->mol_offset; ra.n_struct = b.B; ra.max_atoms = db->max_atoms; ra.use_ga_norm = b.c.use_ga_norm;
+  ra.gq = db->gq; ra.gk = db->gk; ra.ga = db->ga; ra.dy = b.w.dy;
+  ra.Wb = h->head.Wb; ra.bb = h->head.bb; ra.wo = h->head.wo;
+  ra.dgq = dgq; ra.dgk = dgk; ra.rep_out = b.w.rep; ra.dpre_out = b.w.dpre;
+  // (one slot per structure, summed in structure order with the layer's other vectors: 128 workgroups adding to the same 128
+  // addresses was a queue of 16 k atomics)
+  ra.dwo = reserve_vec(b.wg, b.g("predict_property/kernel"), b.B); ra.dbo = b.g("predict_property/bias");
+  if (!b.wg.overrun) launch_readout_bwd(ra, s, b.det != nullptr);
+  // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z, dgq,
+  // dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no hand-off of their own,
+  // each of which costs the main stream ~7 us (tools/fork_probe.hip)
+  b.wadd(b.w.rep, b.w.dpre, b.g("bf_property/kernel"), b.g("bf_property/bias"), b.B);
+  b.wadd(z, dgq, b.g("global_attention/query/kernel"), b.g("global_attention/query/bias"), b.A);
+  b.wadd(z, dgk, b.g("global_attention/key/kernel"), b.g("global_attention/key/bias"), b.A);
+  launch_linear_sum(dgq, h->WgqT, dgk, h->WgkT, nullptr, nullptr, dpreA, b.A, 0, s, preA);  // dpreA = (dgq.Wgq^T + dgk.Wgk^T) * swish'(preA)
+  b.wadd(cL, dpreA, b.g("after_Lc/kernel"), b.g("after_Lc/bias"), b.A);
+  // d loss / d centres_L = dpreA.Wa^T: folded into the first rn_bwd_kernel (or launched by Pend::flush)
+  b.pend.add(dpreA, h->WaTh, h->WaT);
+  b.pend.fresh = true;
+}
+
+// ---- ResidualNorm backward (attention.py:37-40): c_{l+1} = LN(x + drop(W2 swish(W1 x + b1) + b2)), x = ctx ----
+int bwd_residual_norm(Bwd& b, const BwdLayer& y) {
+  scann_handle_t* h = b.h;
+  hipStream_t s = b.st.main;
+  if (!(b.fused && b.c.use_attn_norm)) b.pend.flush(b.dC, b.A, s);  // nobody below folds the projections of the layer above in
+  if (!b.c.use_attn_norm) {
+    HIPCHK(h, hipMemcpyAsync(b.dCtx, b.dC, b.nA * 4, hipMemcpyDeviceToDevice, s));
+    return SCANN_OK;
+  }
+  const float* pre1 = b.db->keep_pre1 + (size_t)y.l * b.nA;
+  const float* H1 = b.db->keep_H1 + (size_t)y.l * b.nA;
+  const float* T2 = b.db->keep_T2 + (size_t)y.l * b.nA;
+  if (b.fused) {
+    // one kernel: [dC += the projections of the layer above] -> LayerNorm backward -> Dropout mask -> dense_2^T, swish' -> dense_1^T
+    RnBwdArgs ra{};
+    b.pend.fold_into(ra, b.dC);
+    ra.T2 = T2; ra.pre1 = pre1; ra.gamma = y.p.lnr_g; ra.Wf2Th = y.pt.Wf2Th; ra.Wf1Th = y.pt.Wf1Th;
+    ra.dY = y.t3; ra.dpre1 = y.t4; ra.dCtx = b.dCtx; ra.n_atom = b.A;
+    ra.drop_p = b.w.drop_p; ra.drop_seed = b.w.seed; ra.drop_tag = (unsigned)y.l;
+    launch_rn_bwd(b.wg, ra, b.g(y.rn + "layer_norm/gamma"), b.g(y.rn + "layer_norm/beta"), s);
+  } else {
+    launch_ln_bwd(b.wg, T2, y.p.lnr_g, b.dC, b.dCtx, b.g(y.rn + "layer_norm/gamma"), b.g(y.rn + "layer_norm/beta"), b.A, 0, s);  // dT2 -> dCtx
+    // gradient of the Dense_2 output = dT2 through the Dropout mask, in a buffer of its own: dT2 (dCtx) is the residual path and
+    // is accumulated into below, while the queued weight gradient reads its operand at the end of the layer
+    if (b.w.drop_p > 0.f) launch_dropout_copy(y.t3, b.dCtx, b.nA, b.w.seed, (unsigned)y.l, b.w.drop_p, s);
+    else HIPCHK(h, hipMemcpyAsync(y.t3, b.dCtx, b.nA * 4, hipMemcpyDeviceToDevice, s));
+    launch_linear(y.t3, y.pt.Wf2T, nullptr, y.t4, const_cast<float*>(pre1), b.A, 4, s);  // dpre1 = (dY.W2^T) * swish'(pre1)
+    launch_linear(y.t4, y.pt.Wf1T, nullptr, b.dCtx, nullptr, b.A, 1, s);                 // dctx = dT2 + dpre1.W1^T
+  }
+  b.wadd(H1, y.t3, b.g(y.rn + "dense_2/kernel"), b.g(y.rn + "dense_2/bias"), b.A);
+  b.wadd(y.ctx, y.t4, b.g(y.rn + "dense_1/kernel"), b.g(y.rn + "dense_1/bias"), b.A);
+  return SCANN_OK;
+}
+
+// ---- LocalAttention backward (attention.py:118-216): softmax / LayerNorm backward per atom (unless it rides in the edge launch of
+// bwd_geometry), and the key / query weight-gradient jobs ----
+void bwd_attention(Bwd& b, const BwdLayer& y) {
+  if (!b.fuse_attn)
+    launch_attn_bwd(b.wg, y.qL, y.KL, b.db->edge_offset, b.dCtx, y.p.ln_g, y.dQ, y.edK, b.g(y.la + "layer_norm/gamma"),
+                    b.g(y.la + "layer_norm/beta"), b.A, b.db->max_degree, b.w.attn_p, DROP_TAG_ATTN + (unsigned)y.l, b.w.seed, b.st.main);
+  if (y.angL) b.wadd(y.angL, y.edK, b.g(y.la + "key/kernel"), b.g(y.la + "key/bias"), b.E);
+  else b.wadd(y.c_in, y.edK, b.g(y.la + "key/kernel"), b.g(y.la + "key/bias"), b.E, b.db->edge_col, y.Gout);  // ang = c[j] * G'
+  b.wadd(y.c_in, y.dQ, b.g(y.la + "query/kernel"), b.g(y.la + "query/bias"), b.A);
+}
+
+// The fixed-order sums of a layer's partial slots (and of its LayerNorm gamma / beta slots) behind its gradient launch on `ws`.
+// The side stream's chain per layer is a gradient launch (~32 us) and two reductions of its partial slots (~34 us): as long as the
+// main stream's chain per layer (~70 us), so the step ended when the SIDE stream did, ~65 us after the main one.  The reductions go
+// to the second side stream (idle but for the basis leaf): gradient launch of layer l - 1 beside the reductions of layer l.
+// (the LAST layer's reductions stay behind their gradient launch: the second side stream is busy with the basis leaf, 46 us, by then)
+void bwd_reduce(Bwd& b, hipStream_t ws, bool last) { wgrad_flush(b.wg, last ? ws : b.st.after(ws, b.st.side2)); }
+
+// ---- LocalAttention, base branch (attention.py:155): geomL = swish(gd.Wf + bf) * weight from the raw basis (kept in the V slices),
+// no geometry threading; its leaf is filter_geo ----
+void bwd_base_branch(Bwd& b, const BwdLayer& y) {
+  scann_dbatch_t* db = b.db;
+  hipStream_t s = b.st.main;
+  launch_linear(y.edK, y.pt.WkT, nullptr, b.edAng, nullptr, b.E, 0, s);            // dang
+  launch_edge_dang(y.c_in, db->edge_col, y.VL, b.edAng, nullptr, b.eT, y.eU, b.E, s);  // eT = dang * geomL ; eU = dgeomL = dang * c[j]
+  launch_gather_sum(b.eT, db->in_off, db->in_edge, b.dC, b.A, 0, s);               // dC[j] = sum over the edges that point at j
+  if (b.ig) {
+    launch_base_input_grad(db->dist, db->weight, y.eU, y.p.Wfg, y.p.bfg, b.h->cd, b.E, D, b.ig->d_dist, b.ig->d_weight, s);
+  } else {
+    // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
+    hipStream_t ws = b.st.after(s, b.st.side);
+    wgrad_launch(b.wg, ws);
+    bwd_reduce(b, ws, y.l == 0);
+    launch_base_geom_bwd(db->gd, y.p.Wfg, y.p.bfg, db->weight, y.eU, b.E, b.g(y.la + "filter_geo/kernel"), b.g(y.la + "filter_geo/bias"), ws,
+                         b.det);
+  }
+  b.pend.add(y.dQ, y.pt.WqTh, y.pt.WqT);  // dC += dq.Wq^T: folded into the next rn_bwd_kernel (or launched by Pend::flush)
+}
+
+// ---- basis MLP (scann_model.py:378-389): a leaf (parameter gradients, or d y / d (dist, weight)) on a stream of its own, started as
+// soon as the geometry gradient entering layer 0 exists -- at 45 us it is the longest thing between there and the optimiser ----
+void bwd_basis_leaf(Bwd& b, const float* dG, hipEvent_t produced) {  // `produced`: completion event of the kernel that wrote dG, or null
+  scann_handle_t* h = b.h;
+  scann_dbatch_t* db = b.db;
+  hipStream_t bs = b.st.leaf(produced);
+  if (b.ig)
+    launch_basis_input_grad(db->dist, db->weight, dG, h->basis.Wd, h->basis.bd, h->basis.Ww, h->basis.bw, h->basis.cd, h->basis.cw, b.E, D,
+                            b.ig->d_dist, b.ig->d_weight, bs);
+  else
+    launch_basis_bwd(h->basis, db->dist, db->weight, dG, b.E, b.g("neighbor_d/kernel"), b.g("neighbor_d/bias"), b.g("neighbor_w/kernel"),
+                     b.g("neighbor_w/bias"), bs, b.det);
+  b.st.leaf_done(bs);
+  b.basis_done = true;
+}
+
+// ---- LocalAttention with geometry update: G' = LN_g(swish(V) + G), V = G.W2 + P1[i] + P3[j]; gate ang = c[j] * G' ----
+// Returns the completion event of the launch that wrote the last operands of the layer's weight gradients (null: none was made).
+hipEvent_t bwd_geometry(Bwd& b, const BwdLayer& y) {
+  scann_dbatch_t* db = b.db;
+  hipStream_t s = b.st.main;
+  float* dGnext = (b.dG_in == b.edGa) ? b.edGb : b.edGa;  // d loss / d geometry entering layer l
+  hipEvent_t ev_sums = nullptr;
+  if (b.fused) {
+    // one kernel: dang = dK.Wk^T -> dG'tot = dang * c[j] + dG'(next layer) -> LayerNorm_g backward -> dV = dT * swish'(V) -> dG = dT + dV.W2^T
+    EdgeBwdArgs ea{};
+    ea.dK = y.edK; ea.c = y.c_in; ea.dG_in = b.dG_in; ea.T = y.TL; ea.G = y.Gin; ea.V = y.VL; ea.gamma = y.p.lng_g; ea.nb = db->edge_col;
+    ea.WkTh = y.pt.WkTh; ea.W2Th = y.pt.W2Th; ea.dang = b.edAng; ea.dV = y.eU; ea.dG = dGnext; ea.n_edge = b.E;
+    hipEvent_t ev_dg = nullptr;  // layer 0: the basis leaf waits for the geometry gradient this launch leaves
+    if (b.fuse_attn) {
+      AttnPart ab{};
+      ab.q = y.qL; ab.K = y.KL; ab.dctx = b.dCtx; ab.gamma = y.p.ln_g; ab.edge_offset = db->edge_offset; ab.tiles = db->tiles;
+      ab.dq = y.dQ; ab.dK = y.edK; ab.drop_p = b.w.attn_p; ab.drop_tag = DROP_TAG_ATTN + (unsigned)y.l; ab.drop_seed = b.w.seed;
+      if (y.l == 0 && b.st.side2) ev_dg = b.st.next_ev();
+      launch_attn_edge_bwd(b.wg, ea, ab, db->n_tile, b.g(y.la + "layer_norm_g/gamma"), b.g(y.la + "layer_norm_g/beta"),
+                           b.g(y.la + "layer_norm/gamma"), b.g(y.la + "layer_norm/beta"), s, ev_dg);
+    } else {
+      launch_edge_bwd(b.wg, ea, b.g(y.la + "layer_norm_g/gamma"), b.g(y.la + "layer_norm_g/beta"), s);
+    }
+    if (y.l == 0) bwd_basis_leaf(b, dGnext, ev_dg);  // (before the atom sums below: they do not touch the geometry gradient)
+    // dC[j] = sum over the edges that point at j of dang * G' (gate), dP3[j] = the same sum of dV, dP1[i] = sum of dV over i's own edges
+    ev_sums = b.st.next_ev();  // ... and this launch's completion is what the layer's weight-gradient launch on the side stream waits for
+    launch_atom_gather3(b.edAng, y.Gout, y.eU, db->edge_offset, db->in_off, db->in_edge, b.dC, y.dP1, y.dP3, b.A, s, ev_sums);
+  } else {
+    launch_linear(y.edK, y.pt.WkT, nullptr, b.edAng, nullptr, b.E, 0, s);  // dang
+    launch_gather_prod_sum(b.edAng, y.Gout, db->in_off, db->in_edge, b.dC, b.A, 0, s);
+    // LayerNorm_g backward with its neighbours fused: in  dG'tot = dang * c[j] + dG'(next layer), out  dT (residual path, -> dGnext)
+    // and dV = dT * swish'(V) (-> eU)
+    launch_ln_bwd_edge(b.wg, y.TL, y.p.lng_g, b.edAng, y.c_in, db->edge_col, b.dG_in, y.VL, dGnext, y.eU, b.g(y.la + "layer_norm_g/gamma"),
+                       b.g(y.la + "layer_norm_g/beta"), b.E, s);
+    launch_atom_sums(y.eU, db->edge_offset, db->in_off, db->in_edge, y.dP1, y.dP3, b.A, s);  // dP1[i]: the atom's own edges; dP3[j]: the edges that point at j
+    launch_linear(y.eU, y.pt.W2T, nullptr, dGnext, nullptr, b.E, 1, s);                      // dG += dV.W2^T
+  }
+  float* fgk = b.g(y.la + "filter_geo/kernel");
+  b.wadd(y.Gin, y.eU, fgk + (size_t)D * D, nullptr, b.E);  // dW2
+  b.wadd(y.c_in, y.dP1, fgk, b.g(y.la + "filter_geo/bias"), b.A);
+  b.wadd(y.c_in, y.dP3, fgk + (size_t)2 * D * D, nullptr, b.A);
+  // dC += dP1.W1^T + dP3.W3^T + dq.Wq^T: folded into the next layer's rn_bwd_kernel (or launched by Pend::flush)
+  b.pend.add(y.dP1, y.pt.W1Th, y.pt.W1T);
+  b.pend.add(y.dP3, y.pt.W3Th, y.pt.W3T);
+  b.pend.add(y.dQ, y.pt.WqTh, y.pt.WqT);
+  b.dG_in = dGnext;
+  return ev_sums;
+}
+
+// ---- every weight gradient of the layer (ResidualNorm 2, key, query, filter_geo 3) in ONE launch, then the fixed-order sum of its
+// partial slots: both beside the chains of the layers below.  `ev_sums`: bwd_geometry's ----
+// (a hand-off per layer: 2 / 3 / 4 / 7 layers sharing one measured slower, profiles/r04_notes.md)
+void bwd_layer_wgrad(Bwd& b, int l, hipEvent_t ev_sums) {
+  if (b.ig) return;  // (no weight gradients)
+  if (l == 0 && ev_sums) {
+    // The FIRST layer's gradient launch and its reductions are the longest thing left (the main stream only has the embedding chain,
+    // ~40 us): they stay on the main stream, with no hand-over in front of them, and the embedding chain goes to the side stream
+    // instead (0.830 -> 0.819 ms per step, eight alternations on one box: profiles/r05_notes.md)
+    wgrad_launch(b.wg, b.st.main);
+    wgrad_flush(b.wg, b.st.main);
+    b.tail_s = b.st.after_event(ev_sums, b.st.side);
+    return;
+  }
+  hipStream_t ws = ev_sums ? b.st.after_event(ev_sums, b.st.side) : b.st.after(b.st.main, b.st.side);
+  wgrad_launch(b.wg, ws);
+  bwd_reduce(b, ws, l == 0);
+}
+
+// ---- embedding (scann_model.py:362-374): the weight gradients of the table / dense_embed (general: ring, cgcnn), or in the
+// data-gradient mode d y / d (ring, cgcnn) from d y / d centres after dense_embed (no Dropout: inference semantics) ----
+void bwd_embed_leaf(Bwd& b) {
+  scann_handle_t* h = b.h;
+  scann_dbatch_t* db = b.db;
+  const scann_config_t& c = b.c;
+  hipStream_t s = b.tail_s;
+  if (b.ig) {
+    if (!b.ig->d_ring && !b.ig->d_cgcnn) return;
+    InputGradEmbed e{};
+    const EmbedArgs& ea = h->embed;
+    e.width = D; e.emb_dim = c.embedding_dim; e.dC = b.dC; e.atomic = db->atomic;
+    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+    e.ring = c.use_ring ? db->ring : nullptr;
+    e.emb = ea.emb; e.We = ea.We; e.be = ea.be; e.Wr = ea.Wr; e.br = ea.br; e.Wde = ea.Wde; e.bde = ea.bde;
+    e.d_ring = b.ig->d_ring; e.d_cgcnn = b.ig->d_cgcnn;
+    launch_embed_input_grad(e, b.A, s);
+    return;
+  }
+  // deterministic mode: the readout's bias gradient = the sum of d loss / d y, in structure order, beside the embedding chain
+  if (b.det) launch_scalar_sum(b.w.dy, b.B, b.g("predict_property/bias"), s);
+  if (c.use_ring || c.feature_cgcnn) {
+    launch_dropout(b.dC, b.nA, b.w.seed, DROP_TAG_EMBED, b.w.drop_p, s);
+    EmbedArgs e = h->embed;
+    e.n_atom = b.A; e.atomic = db->atomic; e.c0 = db->c0;
+    e.ring = c.use_ring ? db->ring : nullptr;
+    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
+    launch_embed_general_bwd(e, b.dC, c.feature_cgcnn ? nullptr : b.g("embed_atom/embeddings"),
+                             c.feature_cgcnn ? b.g("embed_atom/kernel") : nullptr, c.feature_cgcnn ? b.g("embed_atom/bias") : nullptr,
+                             c.use_ring ? b.g("extra_embed/kernel") : nullptr, c.use_ring ? b.g("extra_embed/bias") : nullptr,
+                             b.g("dense_embed/kernel"), b.g("dense_embed/bias"), s, b.det, c.n_atoms);
+  } else {
+    launch_embed_bwd(b.dC, db->atomic, b.A, h->d_weights + h->o_emb, h->d_weights + h->o_Wde, h->d_weights + h->o_bde, b.w.dlut,
+                     c.n_atoms, c.embedding_dim, b.g("embed_atom/embeddings"), b.g("dense_embed/kernel"), b.g("dense_embed/bias"), b.w.seed,
+                     DROP_TAG_EMBED, b.w.drop_p, s, b.det);
+  }
+}
+
+}  // namespace
+
 // d_stat (device, {global sse, global count}) non-null: the loss scale is formed on the device (scann_train_step: no host round trip)
 // ig non-null: the data-gradient mode (InGrad; scann_input_grads): one stream, no weight-gradient launch or reduction, no deterministic
 // slots; what the fused kernels store per workgroup for the LayerNorm gradients stays in the partial arena, the readout's bias
@@ -401,359 +816,34 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
                          const InGrad* ig = nullptr) {
   if (const int r = ensure_reverse(h, db)) return r;
   if (h->generic) return gen_backward(h, db, w, scale, d_stat, dy_done, ig);
-  hipStream_t s = h->streams[0];
-  const scann_config_t& c = h->cfg;
-  const int L = c.n_attention, A = db->n_atom, E = db->n_edge, B = db->n_struct;
-  const size_t nA = (size_t)A * D, nE = (size_t)E * D;
-  float* const G = ig ? h->ig_grad : h->t_grad;
-  auto g = [&](const std::string& name) { return G + spec_offset(h, name); };
-  if (!dy_done) launch_dy(db->y, w.targets, B, scale, d_stat, w.dy, s);
-  // Weight-gradient GEMMs are off the critical path (only the final reduce needs them): with the kept-activation forward
-  // their operands are never overwritten inside a layer, so they run on a side stream beside the data-gradient chain, which
-  // alone does not fill the chip at batch 128.  fork(): side stream waits for everything enqueued so far; join(): main waits
-  // for the side stream (start of every layer: the previous layer's temporaries are about to be overwritten).
-  hipStream_t aux = h->train_aux;
-  const bool side = aux != nullptr && !ig;
-  size_t ev_i = 0;
-  auto fork = [&]() -> hipStream_t {
-    if (!side) return s;
-    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
-    (void)hipEventRecord(e, s);
-    (void)hipStreamWaitEvent(aux, e, 0);
-    return aux;
-  };
-  // a fork whose producer was launched with the event as its own completion signal (launch_atom_gather3 / launch_attn_edge_bwd, `done`):
-  // the side stream only has to wait -- no marker packet on the main stream (4.0 instead of 6.7 us per fork, tools/fork_probe.hip)
-  auto next_ev = [&]() -> hipEvent_t { return side ? h->train_ev[ev_i++ % h->train_ev.size()] : nullptr; };
-  auto fork_after = [&](hipEvent_t e) -> hipStream_t {
-    if (!side) return s;
-    (void)hipStreamWaitEvent(aux, e, 0);
-    return aux;
-  };
-  auto join = [&]() {
-    if (!side) return;
-    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
-    (void)hipEventRecord(e, aux);
-    (void)hipStreamWaitEvent(s, e, 0);
-  };
-  // The side stream's chain per layer is a gradient launch (~32 us) and two reductions of its partial slots (~34 us): as long as the
-  // main stream's chain per layer (~70 us), so the step ended when the SIDE stream did, ~65 us after the main one.  The reductions
-  // go to the second side stream (idle but for the basis leaf): gradient launch of layer l - 1 beside the reductions of layer l.
-  bool aux2_used = false;
-  auto flush_side = [&](hipStream_t ws, WgradCtx& ctx, bool last) {
-    if (!side) return;
-    hipStream_t fs = ws;
-    // (the LAST layer's reductions stay behind their gradient launch: the second side stream is busy with the basis leaf, 46 us, by then)
-    if (h->train_aux2 && !last) {
-      hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
-      (void)hipEventRecord(e, ws);
-      (void)hipStreamWaitEvent(h->train_aux2, e, 0);
-      fs = h->train_aux2;
-      aux2_used = true;
-    }
-    wgrad_flush(ctx, fs);
-  };
-  WgradCtx wg;
-  wg.arena = w.wpart;
-  auto wadd = [&](auto&&... a) {  // a weight gradient's GEMM job (none in the data-gradient mode)
-    if (!ig) wgrad_add(wg, a...);
-  };
-  // deterministic mode: slots of the six reductions that otherwise end in float atomics (scann_train.h), allocated with the batch's
-  // workspace on the first such backward and sized from the batch shape alone
-  WgradCtx dct;
-  WgradCtx* const det = h->deterministic && !ig ? &dct : nullptr;
-  if (det) {
-    const bool general = c.use_ring || c.feature_cgcnn;
-    const size_t need = det_slot_floats(A, E, L, c.n_atoms, c.embedding_dim, c.g_update, general, c.feature_cgcnn, c.use_ring);
-    if (need > w.det_floats) {
-      // (the slots of a previous step on this batch may still be read by its reductions: the stream order of the main stream
-      //  alone does not cover the side streams, so wait for the device before the block goes back to the cache)
-      if (w.det_part) {
-        HIPCHK(h, hipDeviceSynchronize());
-        cached_free(w.det_part);
-        w.det_part = nullptr;
-        w.det_floats = 0;
-      }
-      HIPCHK(h, cached_malloc((void**)&w.det_part, need * 4));
-      w.det_floats = need;
-    }
-    dct.arena = w.det_part;
-  }
-  // a fork costs the main stream ~7 us (tools/fork_probe.hip): the layers' gradient launches may share one (their operand sets live
-  // to the end of the step)
-  const int fork_every = 1;  // (2 / 3 / 4 / 7 layers per fork measured slower: profiles/r04_notes.md)
-
-  // named temporaries
-  float *dC = w.tA[0], *dCtx = w.tA[1], *t0 = w.tA[2], *t1 = w.tA[3], *t2 = w.tA[4];
-  float *edAng = w.tE[0], *eT = w.tE[1], *edGa = w.tE[2], *edGb = w.tE[3];
-  // The operands of a layer's weight gradients (t3, t4, dQ, dP1, dP3, edK, eU) exist once per layer (set L = the readout): the
-  // gradient launch of layer l runs on the side stream beside the data-gradient chains of the layers below and nothing it reads
-  // is overwritten before the end of the step.
-  auto setA = [&](int l, int k) { return w.tA[5 + 5 * (size_t)l + k]; };
-  auto setE = [&](int l, int k) { return w.tE[4 + 2 * (size_t)l + k]; };
-  float *t3 = setA(L, 0), *t4 = setA(L, 1), *dQ = setA(L, 2), *dP1 = setA(L, 3), *dP3 = setA(L, 4), *edK = setE(L, 0), *eU = setE(L, 1);
-  const float* cL = db->dbg_c + (size_t)L * nA;  // centres entering after_Lc
-
-  // ---- readout (scann_model.py:424-447, attention.py:267-318) ----
-  float* const rdgk = t3;  // the readout is "layer L" of the operand-set scheme
-  // the training forward kept preA = cL.Wa + ba and z = swish(preA); gq, gk, ga, y are still in the batch workspace
-  t0 = db->keep_preA;
-  t1 = db->keep_z;
-  ReadoutBwdArgs ra{};
-  ra.mol_offset = db->mol_offset; ra.n_struct = B; ra.max_atoms = db->max_atoms; ra.use_ga_norm = c.use_ga_norm;
-  ra.gq = db->gq; ra.gk = db->gk; ra.ga = db->ga; ra.dy = w.dy;
-  ra.Wb = h->head.Wb; ra.bb = h->head.bb; ra.wo = h->head.wo;
-  ra.dgq = t2; ra.dgk = rdgk; ra.rep_out = w.rep; ra.dpre_out = w.dpre;
-  // (one slot per structure, summed in structure order with the layer's other vectors: 128 workgroups adding to the same 128
-  // addresses was a queue of 16 k atomics)
-  ra.dwo = reserve_vec(wg, g("predict_property/kernel"), B); ra.dbo = g("predict_property/bias");
-  launch_readout_bwd(ra, s, det != nullptr);
-  // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z = t1,
-  // dgq = t2, dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no fork of their own,
-  // each of which costs the main stream ~7 us (tools/fork_probe.hip)
-  wadd(w.rep, w.dpre, g("bf_property/kernel"), g("bf_property/bias"), B);
-  wadd(t1, t2, g("global_attention/query/kernel"), g("global_attention/query/bias"), A);
-  wadd(t1, rdgk, g("global_attention/key/kernel"), g("global_attention/key/bias"), A);
-  float* const dpreA = dQ;
-  launch_linear_sum(t2, h->WgqT, rdgk, h->WgkT, nullptr, nullptr, dpreA, A, 0, s, t0);  // dpreA = (dgq.Wgq^T + dgk.Wgk^T) * swish'(preA)
-  wadd(cL, dpreA, g("after_Lc/kernel"), g("after_Lc/bias"), A);
-
-  const float* dG_in = nullptr;  // gradient w.r.t. the geometry leaving layer l (none for the last layer)
-  // fused chains (scann_train_fused.hip); SCANN_TRAIN_FUSED=0 selects the modular one-kernel-per-operation backward
-  const bool fused = h->train_fused;
-  struct Pend {  // projections of layer l + 1 that still have to be added to dC (d loss / d centres_{l+1})
-    int n = 0;
-    const float* X[3];
-    const _Float16* Wh[3];
-    const float* W[3];
-    bool fresh = false;  // dC holds nothing yet: the terms ARE d loss / d centres (first use: dpreA.Wa^T of the readout)
-  } pend;
-  hipStream_t tail_s = s;  // where the embedding chain goes (below)
-  auto flush_pend = [&]() {
-    if (pend.n)
-      launch_linear_sum(pend.X[0], pend.W[0], pend.n > 1 ? pend.X[1] : nullptr, pend.n > 1 ? pend.W[1] : nullptr,
-                        pend.n > 2 ? pend.X[2] : nullptr, pend.n > 2 ? pend.W[2] : nullptr, dC, A, pend.fresh ? 0 : 1, tail_s);
-    pend.n = 0;
-    pend.fresh = false;
-  };
-  // d loss / d centres_L = dpreA.Wa^T: folded into the first rn_bwd_kernel (or launched by flush_pend)
-  pend.n = 1;
-  pend.X[0] = dpreA; pend.Wh[0] = h->WaTh; pend.W[0] = h->WaT;
-  pend.fresh = true;
-  // basis MLP (scann_model.py:378-389): a leaf (parameter gradients only) on a stream of its own, started as soon as the geometry
-  // gradient entering layer 0 exists -- at 45 us it is the longest thing between there and the optimiser
-  hipEvent_t ev_basis = nullptr;
-  bool basis_done = false;
-  auto basis_leaf = [&](const float* dG, hipEvent_t produced) {  // `produced`: completion event of the kernel that wrote dG, or null
-    hipStream_t bs = s;
-    if (side && h->train_aux2) {
-      hipEvent_t e = produced;
-      if (!e) {
-        e = h->train_ev[ev_i++ % h->train_ev.size()];
-        (void)hipEventRecord(e, s);
-      }
-      (void)hipStreamWaitEvent(h->train_aux2, e, 0);
-      bs = h->train_aux2;
-    }
-    if (ig)
-      launch_basis_input_grad(db->dist, db->weight, dG, h->basis.Wd, h->basis.bd, h->basis.Ww, h->basis.bw, h->basis.cd, h->basis.cw, E, D,
-                              ig->d_dist, ig->d_weight, bs);
-    else
-      launch_basis_bwd(h->basis, db->dist, db->weight, dG, E, g("neighbor_d/kernel"), g("neighbor_d/bias"),
-                       g("neighbor_w/kernel"), g("neighbor_w/bias"), bs, det);
-    if (bs != s) {
-      ev_basis = h->train_ev[ev_i++ % h->train_ev.size()];
-      (void)hipEventRecord(ev_basis, bs);
-    }
-    basis_done = true;
-  };
-  for (int l = L - 1; l >= 0; --l) {
-    t3 = setA(l, 0); t4 = setA(l, 1); dQ = setA(l, 2); dP1 = setA(l, 3); dP3 = setA(l, 4);
-    edK = setE(l, 0); eU = setE(l, 1);
-    const LayerParams& p = h->layers[l];
-    const scann_handle::LayerT& pt = h->layersT[l];
-    const std::string la = "local_attention_" + std::to_string(l) + "/", rn = "residual_norm_" + std::to_string(l) + "/";
-    const float* c_in = db->dbg_c + (size_t)l * nA;        // centres entering LocalAttention l
-    const float* ctx = db->dbg_ctx + (size_t)l * nA;       // LocalAttention output (after layer_norm)
-    const float* Gin = c.g_update ? db->dbg_g + (size_t)l * nE : nullptr;         // geometry entering layer l
-    const float* Gout = c.g_update ? db->dbg_g + (size_t)(l + 1) * nE : nullptr;  // geometry leaving layer l (= layer_norm_g output)
-    // tensors the training forward kept (nothing is recomputed): q [A,128]; K, ang, V (base branch: geomL), T [E,128]
-    const float* qL = db->keep_q + (size_t)l * nA;
-    const float* angL = db->keep_ang ? db->keep_ang + (size_t)l * nE : nullptr;  // null: formed again from c[j] and G
-    const float* KL = db->keep_K + (size_t)l * nE;
-    const float* VL = db->keep_V + (size_t)l * nE;
-    const float* TL = db->keep_T ? db->keep_T + (size_t)l * nE : nullptr;        // null: formed again from V and G
-
-    if (pend.n && !(fused && c.use_attn_norm)) flush_pend();  // nobody below folds the projections of the layer above in
-    // ---- ResidualNorm backward (attention.py:37-40): c_{l+1} = LN(x + drop(W2 swish(W1 x + b1) + b2)), x = ctx ----
-    if (c.use_attn_norm) {
-      const float* pre1 = db->keep_pre1 + (size_t)l * nA;
-      const float* H1 = db->keep_H1 + (size_t)l * nA;
-      const float* T2 = db->keep_T2 + (size_t)l * nA;
-      if (fused) {
-        // one kernel: [dC += the projections of the layer above] -> LayerNorm backward -> Dropout mask -> dense_2^T, swish' -> dense_1^T
-        RnBwdArgs ra{};
-        ra.dC = pend.fresh ? nullptr : dC; ra.T2 = T2; ra.pre1 = pre1; ra.gamma = p.lnr_g; ra.Wf2Th = pt.Wf2Th; ra.Wf1Th = pt.Wf1Th;
-        ra.dY = t3; ra.dpre1 = t4; ra.dCtx = dCtx; ra.n_atom = A;
-        ra.drop_p = w.drop_p; ra.drop_seed = w.seed; ra.drop_tag = (unsigned)l;
-        ra.n_pre = pend.n;
-        for (int t = 0; t < pend.n; ++t) { ra.X[t] = pend.X[t]; ra.Wh[t] = pend.Wh[t]; }
-        pend.n = 0;
-        pend.fresh = false;
-        launch_rn_bwd(wg, ra, g(rn + "layer_norm/gamma"), g(rn + "layer_norm/beta"), s);
-      } else {
-        launch_ln_bwd(wg, T2, p.lnr_g, dC, dCtx, g(rn + "layer_norm/gamma"), g(rn + "layer_norm/beta"), A, 0, s);  // dT2 -> dCtx
-        // gradient of the Dense_2 output = dT2 through the Dropout mask, in a buffer of its own: dT2 (dCtx) is the residual path and
-        // is accumulated into below, while the queued weight gradient reads its operand at the end of the layer
-        if (w.drop_p > 0.f) launch_dropout_copy(t3, dCtx, nA, w.seed, (unsigned)l, w.drop_p, s);
-        else HIPCHK(h, hipMemcpyAsync(t3, dCtx, nA * 4, hipMemcpyDeviceToDevice, s));
-        launch_linear(t3, pt.Wf2T, nullptr, t4, const_cast<float*>(pre1), A, 4, s);  // dpre1 = (dY.W2^T) * swish'(pre1)
-        launch_linear(t4, pt.Wf1T, nullptr, dCtx, nullptr, A, 1, s);                 // dctx = dT2 + dpre1.W1^T
-      }
-      wadd(H1, t3, g(rn + "dense_2/kernel"), g(rn + "dense_2/bias"), A);
-      wadd(ctx, t4, g(rn + "dense_1/kernel"), g(rn + "dense_1/bias"), A);
-    } else {
-      HIPCHK(h, hipMemcpyAsync(dCtx, dC, nA * 4, hipMemcpyDeviceToDevice, s));
-    }
-
-    // ---- LocalAttention backward (attention.py:118-216) ----
-    // On the forward's 32-row tile plan (whole atoms per tile, every degree <= 16) the softmax / LayerNorm backward of a tile's atoms
-    // runs at the head of the tile's edge_bwd workgroup: one launch less per layer.
-    const bool fuse_attn = fused && c.g_update && db->tile_rows == 32 && db->n_big == 0 && db->max_degree <= 16 && E > 0;
-    if (!fuse_attn)
-      launch_attn_bwd(wg, qL, KL, db->edge_offset, dCtx, p.ln_g, dQ, edK, g(la + "layer_norm/gamma"), g(la + "layer_norm/beta"), A,
-                      db->max_degree, w.attn_p, DROP_TAG_ATTN + (unsigned)l, w.seed, s);
-    if (angL) wadd(angL, edK, g(la + "key/kernel"), g(la + "key/bias"), E);
-    else wadd(c_in, edK, g(la + "key/kernel"), g(la + "key/bias"), E, db->edge_col, Gout);  // ang = c[j] * G'
-    wadd(c_in, dQ, g(la + "query/kernel"), g(la + "query/bias"), A);
-    if (!c.g_update) {
-      // base SCANN (attention.py:155): geomL = swish(gd.Wf + bf) * weight from the raw basis (kept in the V slices), no geometry threading
-      launch_linear(edK, pt.WkT, nullptr, edAng, nullptr, E, 0, s);            // dang
-      launch_edge_dang(c_in, db->edge_col, VL, edAng, nullptr, eT, eU, E, s);  // eT = dang * geomL ; eU = dgeomL = dang * c[j]
-      launch_gather_sum(eT, db->in_off, db->in_edge, dC, A, 0, s);             // dC[j] = sum over the edges that point at j
-      if (ig) {
-        launch_base_input_grad(db->dist, db->weight, eU, p.Wfg, p.bfg, h->cd, E, D, ig->d_dist, ig->d_weight, s);
-      } else {
-        // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
-        hipStream_t ws = fork();
-        wgrad_launch(wg, ws);
-        flush_side(ws, wg, l == 0);
-        launch_base_geom_bwd(db->gd, p.Wfg, p.bfg, db->weight, eU, E, g(la + "filter_geo/kernel"), g(la + "filter_geo/bias"), ws, det);
-      }
-      pend.n = 1;  // dC += dq.Wq^T: folded into the next rn_bwd_kernel (or launched by flush_pend)
-      pend.X[0] = dQ; pend.Wh[0] = pt.WqTh; pend.W[0] = pt.WqT;
+  Bwd b(h, db, w, ig);
+  hipStream_t s = b.st.main;
+  if (!dy_done) launch_dy(db->y, w.targets, b.B, scale, d_stat, w.dy, s);
+  if (const int r = bwd_det_arena(b)) return r;
+  bwd_readout(b);  // its weight gradients ride with the first layer's launch
+  for (int l = b.L - 1; l >= 0; --l) {
+    const BwdLayer y(b, l);
+    if (const int r = bwd_residual_norm(b, y)) return r;
+    bwd_attention(b, y);
+    if (!b.c.g_update) {
+      bwd_base_branch(b, y);  // with its gradient launch, reductions and filter_geo leaf on the side streams
       continue;
     }
-    // geometry update: G' = LN_g(swish(V) + G), V = G.W2 + P1[i] + P3[j]; gate ang = c[j] * G'
-    float* dGnext = (dG_in == edGa) ? edGb : edGa;  // d loss / d geometry entering layer l
-    hipEvent_t ev_sums = nullptr;
-    if (fused) {
-      // one kernel: dang = dK.Wk^T -> dG'tot = dang * c[j] + dG'(next layer) -> LayerNorm_g backward -> dV = dT * swish'(V) -> dG = dT + dV.W2^T
-      EdgeBwdArgs ea{};
-      ea.dK = edK; ea.c = c_in; ea.dG_in = dG_in; ea.T = TL; ea.G = Gin; ea.V = VL; ea.gamma = p.lng_g; ea.nb = db->edge_col;
-      ea.WkTh = pt.WkTh; ea.W2Th = pt.W2Th; ea.dang = edAng; ea.dV = eU; ea.dG = dGnext; ea.n_edge = E;
-      hipEvent_t ev_dg = nullptr;  // layer 0: the basis leaf waits for the geometry gradient this launch leaves
-      if (fuse_attn) {
-        AttnPart ab{};
-        ab.q = qL; ab.K = KL; ab.dctx = dCtx; ab.gamma = p.ln_g; ab.edge_offset = db->edge_offset; ab.tiles = db->tiles;
-        ab.dq = dQ; ab.dK = edK; ab.drop_p = w.attn_p; ab.drop_tag = DROP_TAG_ATTN + (unsigned)l; ab.drop_seed = w.seed;
-        if (l == 0 && h->train_aux2) ev_dg = next_ev();
-        launch_attn_edge_bwd(wg, ea, ab, db->n_tile, g(la + "layer_norm_g/gamma"), g(la + "layer_norm_g/beta"), g(la + "layer_norm/gamma"),
-                             g(la + "layer_norm/beta"), s, ev_dg);
-      } else {
-        launch_edge_bwd(wg, ea, g(la + "layer_norm_g/gamma"), g(la + "layer_norm_g/beta"), s);
-      }
-      if (l == 0) basis_leaf(dGnext, ev_dg);  // (before the atom sums below: they do not touch the geometry gradient)
-      // dC[j] = sum over the edges that point at j of dang * G' (gate), dP3[j] = the same sum of dV, dP1[i] = sum of dV over i's own edges
-      ev_sums = next_ev();  // ... and this launch's completion is what the layer's weight-gradient launch on the side stream waits for
-      launch_atom_gather3(edAng, Gout, eU, db->edge_offset, db->in_off, db->in_edge, dC, dP1, dP3, A, s, ev_sums);
-    } else {
-      launch_linear(edK, pt.WkT, nullptr, edAng, nullptr, E, 0, s);  // dang
-      launch_gather_prod_sum(edAng, Gout, db->in_off, db->in_edge, dC, A, 0, s);
-      // LayerNorm_g backward with its neighbours fused: in  dG'tot = dang * c[j] + dG'(next layer), out  dT (residual path, -> dGnext)
-      // and dV = dT * swish'(V) (-> eU)
-      launch_ln_bwd_edge(wg, TL, p.lng_g, edAng, c_in, db->edge_col, dG_in, VL, dGnext, eU, g(la + "layer_norm_g/gamma"),
-                         g(la + "layer_norm_g/beta"), E, s);
-      launch_atom_sums(eU, db->edge_offset, db->in_off, db->in_edge, dP1, dP3, A, s);  // dP1[i]: the atom's own edges; dP3[j]: the edges that point at j
-      launch_linear(eU, pt.W2T, nullptr, dGnext, nullptr, E, 1, s);                    // dG += dV.W2^T
-    }
-    float* fgk = g(la + "filter_geo/kernel");
-    wadd(Gin, eU, fgk + (size_t)D * D, nullptr, E);  // dW2
-    wadd(c_in, dP1, fgk, g(la + "filter_geo/bias"), A);
-    wadd(c_in, dP3, fgk + (size_t)2 * D * D, nullptr, A);
-    if (ig) {
-      // (no weight gradients)
-    } else if (l == 0 && side && ev_sums) {
-      // The FIRST layer's gradient launch and its reductions are the longest thing left (the main stream only has the embedding chain,
-      // ~40 us): they stay on the main stream, with no hand-over in front of them, and the embedding chain goes to the side stream
-      // instead (0.830 -> 0.819 ms per step, eight alternations on one box: profiles/r05_notes.md)
-      wgrad_launch(wg, s);
-      wgrad_flush(wg, s);
-      tail_s = fork_after(ev_sums);
-    } else if ((L - 1 - l) % fork_every == fork_every - 1 || l == 0) {
-      // every weight gradient of this layer (ResidualNorm 2, key, query, filter_geo 3) in ONE launch, then the fixed-order sum of its
-      // partial slots (and of the layer's LayerNorm gamma / beta slots): both beside the chains of the layers below
-      hipStream_t ws = ev_sums ? fork_after(ev_sums) : fork();
-      wgrad_launch(wg, ws);
-      flush_side(ws, wg, l == 0);
-    }
-    // dC += dP1.W1^T + dP3.W3^T + dq.Wq^T: folded into the next layer's rn_bwd_kernel (or launched by flush_pend)
-    pend.n = 3;
-    pend.X[0] = dP1; pend.X[1] = dP3; pend.X[2] = dQ;
-    pend.Wh[0] = pt.W1Th; pend.Wh[1] = pt.W3Th; pend.Wh[2] = pt.WqTh;
-    pend.W[0] = pt.W1T; pend.W[1] = pt.W3T; pend.W[2] = pt.WqT;
-    dG_in = dGnext;
+    const hipEvent_t ev_sums = bwd_geometry(b, y);  // (layer 0, fused: the basis leaf goes to the second side stream from in here)
+    bwd_layer_wgrad(b, l, ev_sums);                 // side stream; layer 0: main stream, and the embedding chain to the side stream
   }
-  // ---- basis MLP and embedding (scann_model.py:362-389) ----
-  // (the basis leaf first: it needs only the geometry gradient the last edge_bwd_kernel left, and at 43 us on its own stream it is
+  // (the basis leaf first: it needs only the geometry gradient the last edge backward left, and at 43 us on its own stream it is
   // the longest thing between here and the optimiser -- started behind the embedding chain it ended 30 us after it)
-  if (dG_in && !basis_done) basis_leaf(dG_in, nullptr);
-  flush_pend();
-  if (ig) {  // d y / d (ring, cgcnn) from d y / d centres after dense_embed (no Dropout: inference semantics)
-    if (ig->d_ring || ig->d_cgcnn) {
-      InputGradEmbed e{};
-      const EmbedArgs& ea = h->embed;
-      e.width = D; e.emb_dim = c.embedding_dim; e.dC = dC; e.atomic = db->atomic;
-      e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
-      e.ring = c.use_ring ? db->ring : nullptr;
-      e.emb = ea.emb; e.We = ea.We; e.be = ea.be; e.Wr = ea.Wr; e.br = ea.br; e.Wde = ea.Wde; e.bde = ea.bde;
-      e.d_ring = ig->d_ring; e.d_cgcnn = ig->d_cgcnn;
-      launch_embed_input_grad(e, A, s);
-    }
-    HIPCHK(h, hipGetLastError());
-    return SCANN_OK;
+  if (b.dG_in && !b.basis_done) bwd_basis_leaf(b, b.dG_in, nullptr);
+  b.pend.flush(b.dC, b.A, b.tail_s);
+  bwd_embed_leaf(b);
+  if (b.det && b.dct.overrun) return fail(h, SCANN_ERR_HIP, "scann_train_backward: deterministic partial arena overrun");
+  if (b.wg.overrun) return fail(h, SCANN_ERR_HIP, "scann_train_backward: weight-gradient partial arena overrun");
+  if (!ig) {
+    if (!b.wg.jobs.empty()) wgrad_launch(b.wg, s);  // a model without LocalAttention layers: the readout's gradients were never launched
+    b.st.join_all();
+    wgrad_flush(b.wg, s);  // ONE launch adds the per-slab partials of every weight gradient, in slab order
   }
-  // deterministic mode: the readout's bias gradient = the sum of d loss / d y, in structure order, beside the embedding chain
-  if (det) launch_scalar_sum(w.dy, B, g("predict_property/bias"), tail_s);
-  if (c.use_ring || c.feature_cgcnn) {
-    launch_dropout(dC, nA, w.seed, DROP_TAG_EMBED, w.drop_p, tail_s);
-    EmbedArgs e = h->embed;
-    e.n_atom = A; e.atomic = db->atomic; e.c0 = db->c0;
-    e.ring = c.use_ring ? db->ring : nullptr;
-    e.cgcnn = c.feature_cgcnn ? db->cgcnn : nullptr;
-    launch_embed_general_bwd(e, dC, c.feature_cgcnn ? nullptr : g("embed_atom/embeddings"),
-                             c.feature_cgcnn ? g("embed_atom/kernel") : nullptr, c.feature_cgcnn ? g("embed_atom/bias") : nullptr,
-                             c.use_ring ? g("extra_embed/kernel") : nullptr, c.use_ring ? g("extra_embed/bias") : nullptr,
-                             g("dense_embed/kernel"), g("dense_embed/bias"), tail_s, det, c.n_atoms);
-  } else {
-    launch_embed_bwd(dC, db->atomic, A, h->d_weights + h->o_emb, h->d_weights + h->o_Wde, h->d_weights + h->o_bde, w.dlut,
-                     c.n_atoms, c.embedding_dim, g("embed_atom/embeddings"), g("dense_embed/kernel"), g("dense_embed/bias"), w.seed,
-                     DROP_TAG_EMBED, w.drop_p, tail_s, det);
-  }
-  if (det && dct.off > w.det_floats)
-    return fail(h, SCANN_ERR_HIP, "scann_train_backward: deterministic partial arena overrun");
-  if (wg.off > w.wpart_floats)
-    return fail(h, SCANN_ERR_HIP, "scann_train_backward: weight-gradient partial arena overrun");
-  if (!wg.jobs.empty()) wgrad_launch(wg, s);  // a model without LocalAttention layers: the readout's gradients were never launched
-  join();
-  if (aux2_used) {  // everything the second side stream was given (the basis leaf included)
-    hipEvent_t e = h->train_ev[ev_i++ % h->train_ev.size()];
-    (void)hipEventRecord(e, h->train_aux2);
-    (void)hipStreamWaitEvent(s, e, 0);
-  } else if (ev_basis) {
-    (void)hipStreamWaitEvent(s, ev_basis, 0);
-  }
-  wgrad_flush(wg, s);  // ONE launch adds the per-slab partials of every weight gradient, in slab order
   HIPCHK(h, hipGetLastError());
   return SCANN_OK;
 }

@@ -13,16 +13,16 @@ import numpy as np
 import scann_oracle as so
 
 # ---- thresholds (csrc/) ----
-FUSED_TILE_ROWS_32_MAX = 32 * 768     # scann_train_fused.hip fused_tile_rows: rn_bwd_kernel<2> / edge_bwd_kernel<2,..> above (rows)
+FUSED_TILE_ROWS_32_MAX = 32 * 768     # scann_train_slots.h fused_split: rn_bwd_kernel<2> / edge_bwd_kernel<2,..> above (rows)
 EDGE_TILE_32_MAX_EDGES = 32 * 1024    # scann_batch.cpp upload_impl `small`: 32-row edge tiles only while E <= this ...
 EDGE_TILE_32_MAX_DEGREE = 32          # ... and no atom has more neighbours (else planned again at 64 rows)
-FUSE_ATTN_MAX_DEGREE = 16             # scann_train_host.cpp backward_impl fuse_attn (also needs 32-row tiles); attn_bwd16_kernel up to this
+FUSE_ATTN_MAX_DEGREE = 16             # scann_train_host.cpp Bwd::fuse_attn (also needs 32-row tiles); attn_bwd16_kernel up to this
 ATOM_TILE_32_MAX = 32 * 1024          # scann_kernels.hip launch_atom: atom_kernel<.., 2, ..> (64-row tiles) above (atoms)
-ATTN_APW16_ATOMS = 4096               # scann_train.hip attn_apw16: one atom per wave up to this many atoms, 2 to 8 above
-WGRAD_FOUR_CHUNKS_MAX = 4 * 64 * 80   # scann_train.hip wgrad_chunks: 4 chunks of 64 rows per slab up to this, more above
+ATTN_APW16_ATOMS = 4096               # scann_train_slots.h attn_apw16: one atom per wave up to this many atoms, 2 to 8 above
+WGRAD_FOUR_CHUNKS_MAX = 4 * 64 * 80   # scann_train_slots.h wgrad_chunks: 4 chunks of 64 rows per slab up to this, more above
 WGRAD_REDUCE4_BYTES = 24 << 20        # scann_train.hip wgrad_flush: wgrad_reduce4_kernel at >= this many bytes of partial slots
 WGRAD_SLOT_BYTES = 128 * 128 * 4      # one partial slot of a 128 x 128 weight gradient
-LN_BWD_ONE_GROUP_MAX = 32 * 1536      # scann_train.hip ln_bwd_groups: one 32-row group per workgroup up to this, >= 2 above (rows)
+LN_BWD_ONE_GROUP_MAX = 32 * 1536      # scann_train_slots.h ln_bwd_groups: one 32-row group per workgroup up to this, >= 2 above (rows)
 GEN_LN_64_ROWS_MAX = 512 * 64         # scann_generic_train.hip gen_ln_chunks: <= 64 rows per chunk up to this, more above
 UPLOAD_MAX_ATOMS = 60000 // (5 * 4)   # scann_batch.cpp upload_impl: 5 floats of LDS per atom of the largest structure (3,000)
 GEN_BWD_MAX_ATOMS = (65536 // 8 - 4) // 3  # scann_train_host.cpp gen_backward: (3 n + 4) doubles <= 64 KiB (2,729)
@@ -31,13 +31,13 @@ SIGNED_OFFSET_ROWS = (1 << 31) // (128 * 4)    # above this many rows a [rows, 1
 
 
 def wgrad_chunks(rows):
-    """scann_train.hip wgrad_chunks"""
+    """scann_train_slots.h wgrad_chunks"""
     tiles = (rows + 63) // 64
     return max(min(4, tiles), (tiles + 79) // 80)
 
 
 def wgrad_slabs(rows):
-    """scann_train.hip wgrad_slabs"""
+    """scann_train_slots.h wgrad_slabs"""
     c = wgrad_chunks(rows)
     return (rows + 64 * c - 1) // (64 * c)
 

@@ -20,7 +20,9 @@ def src(name):
 
 def test_thresholds_match_the_launch_code():
     """each constant against the expression of the line it mirrors"""
-    assert "static int fused_tile_rows(int rows) { return rows <= 32 * 768 ? 32 : 64; }" in src("scann_train_fused.hip")
+    slots = src("scann_train_slots.h")  # the training backward's partitions, stated once for launcher and bound
+    assert "inline Split fused_split(int rows) { return split(rows, rows <= 32 * 768 ? 32 : 64); }" in slots
+    assert "fused_split(a.n_atom)" in src("scann_train_fused.hip") and "fused_split(a.n_edge)" in src("scann_train_fused.hip")
     assert sb.FUSED_TILE_ROWS_32_MAX == 32 * 768
     batch = src("scann_batch.cpp")
     assert "const bool small = E > 0 && E <= 32 * 1024;" in batch and "if (small && max_degree > 32) {" in batch
@@ -35,10 +37,10 @@ def test_thresholds_match_the_launch_code():
     assert sb.GEN_BWD_MAX_ATOMS == 2729 and (3 * 2729 + 4) * 8 <= 65536 < (3 * 2730 + 4) * 8
     assert "const int rows = a.n_atom <= 32 * 1024 ? 32 : 64;" in src("scann_kernels.hip")
     train = src("scann_train.hip")
-    assert "return std::min(8, std::max(1, (n_atom + 4095) / 4096));" in train
-    assert "return std::max(std::min(4, tiles), (tiles + 79) / 80);" in train
+    assert "return std::min(8, std::max(1, (n_atom + 4095) / 4096));" in slots and "attn_bwd_apw(n_atom, max_degree)" in train
+    assert "return std::max(std::min(4, tiles), (tiles + 79) / 80);" in slots and "wgrad_chunks(" not in train
     assert len(re.findall(r"bytes >= \(\(size_t\)24 << 20\)", train)) == 1 and "bytes < ((size_t)24 << 20)" in train
-    assert "return std::min(32, std::max(1, (rows + 32 * 1536 - 1) / (32 * 1536)));" in train
+    assert "return std::min(32, std::max(1, (rows + 32 * 1536 - 1) / (32 * 1536)));" in slots and "ln_bwd_groups(rows)" in train
     assert "int gen_ln_chunks(int rows) { return std::max(1, std::min(512, (rows + 63) / 64)); }" in src("scann_generic_train.hip")
     # the training forward of the plain-fp32 path refuses what its backward cannot run
     assert "if (kp && ((size_t)3 * db->max_atoms + 4) * sizeof(double) > 65536)" in src("scann_forward.cpp")
