@@ -1156,6 +1156,48 @@ int scann_within_host(const float* rows, int64_t n, int64_t dim, const int64_t* 
                       const int32_t* query_pos, int32_t upper, float radius2, int64_t cap, int64_t* counts, int64_t* total, float* dist2,
                       int32_t* pos);
 
+/* ---- Prototypes and criticisms of an index: MMD-critic, the greedy loops on the device ----
+ * The few rows that stand for all of an index, and the rows those do not stand for (Kim, Khanna & Koyejo, NeurIPS 2016): prototypes are
+ * picked greedily so that the kernel mean of the picked set matches the kernel mean of the pool, criticisms are the rows where the two
+ * still differ most.  Every quantity is an integer, so the picks are defined to the bit; weights, the witness function and the MMD
+ * curve are host work on the calls' integers (LatentIndex.prototypes).
+ *   Terms.  Pool P of N rows of dim columns; gamma finite and > 0; a row is eligible iff all its components are finite (the rule of
+ *     scann_index_select), n = the number of eligible rows.  t(i, j) = the weight term of scann_index_peaks at dist2(P[i], P[j]), so
+ *     0 <= t <= 2^30, t is symmetric bit for bit and t(i, i) = 2^30.  A_i = the int64 sum of t(i, j) over all eligible j, j = i included:
+ *     the self-join sum of scann_index_peaks + 2^30.  An ineligible row gets A = -1 and B = 0 and is never picked.
+ *   Prototypes.  B_i (int64) starts at 0.  Pick s = 0, 1, .., m-1 is the first row, among the eligible rows not picked yet, under the total
+ *     order (score descending, position ascending), score_i = (s + 1) A_i - n B_i, an exact int64.  The call reports the pick's position,
+ *     its score and b_at_pick = B_pick; then B_i += t(i, pick) for every eligible i.  The last pick's column is folded as well, so the
+ *     returned B is the sum over all picks.  Selection ends after m picks or when no eligible unpicked row is left.
+ *   Why this score.  With |S| = s the greedy MMD-critic objective is J(S) = 2/(n s) sum_{l in S} A_l - 1/s^2 sum_{l,l' in S} t(l, l').
+ *     J(S + c) differs among the candidates c only through (s + 1) A_c - n B_c, t(c, c) being the same constant for all of them: the
+ *     integer score is the exact argmax of J; no summation order and no rounding enter.
+ *   Range.  |score| <= N m 2^30.  The calls require N m <= 2^32 (1,024 prototypes of 2.4 M rows, 32,768 of 131,072) and refuse anything
+ *     above with SCANN_ERR_INVALID and a message that names both numbers, before anything is launched.  No 128-bit arithmetic.
+ *   Criticisms, a weighted greedy selection with kernel suppression.  weight [N] int64, each in 0 .. 2^31 (checked on the host before
+ *     anything is launched); a row is live iff it is eligible, not among the excluded positions, and has weight > 0.  Cmax_i (int32)
+ *     starts at 0.  Each pick is the first live unpicked row under (score descending, position ascending), score_i = weight_i (2^30 -
+ *     Cmax_i) <= 2^61; the selection ends after c picks or when no live row has score > 0.  After a pick Cmax_i = max(Cmax_i, t(i, pick)).
+ * Consequences: the first prototype is the densest row, ties to the lowest position; an exact duplicate of a pick falls behind it by
+ * n 2^30 and an exact duplicate of a criticism scores 0; the result depends on the pool's contents, gamma and m only, not on the
+ * chunking, the number of add calls or the launch geometry.
+ * scann_index_prototypes returns the number of picks m' (pos, ids, atoms, score, b_at_pick [m]; behind m': position -1, id -1, atom -1,
+ * score 0, b 0; ids, atoms, score, b_at_pick, A [N], B [N] may be NULL); scann_index_criticisms likewise (exclude [n_exclude], positions
+ * of the pool).  Synchronous, every launch on one stream, one host wait; an empty pool returns 0.  SCANN_ERR_INVALID before anything is
+ * launched, with a message that names the argument: a null handle, pool or pos, a pool of another handle, m or c < 1, gamma not finite or
+ * <= 0, N m above 2^32, a weight outside 0 .. 2^31, an excluded position outside the pool.  The calls change nothing in the pool, the
+ * weights, the training state or the selected outputs; inference and training handles, any width.  scann_prototypes_host and
+ * scann_criticisms_host (rows [n * dim]; no GPU work, threaded over the rows -- the sums are integers, so the thread count cannot enter
+ * the result) are the twins: the kernels' bits. */
+int64_t scann_index_prototypes(scann_handle_t* h, scann_index_t* pool, int64_t m, float gamma, int32_t* pos, int64_t* ids, int32_t* atoms,
+                               int64_t* score, int64_t* b_at_pick /* [m] */, int64_t* A /* [N] or NULL */, int64_t* B /* [N] or NULL */);
+int64_t scann_index_criticisms(scann_handle_t* h, scann_index_t* pool, const int64_t* weight /* [N] */, const int32_t* exclude,
+                               int64_t n_exclude, int64_t c, float gamma, int32_t* pos, int64_t* ids, int32_t* atoms, int64_t* score /* [c] */);
+int64_t scann_prototypes_host(const float* rows, int64_t n, int64_t dim, int64_t m, float gamma, int32_t* pos, int64_t* score,
+                              int64_t* b_at_pick, int64_t* A, int64_t* B);
+int64_t scann_criticisms_host(const float* rows, int64_t n, int64_t dim, const int64_t* weight, const int32_t* exclude, int64_t n_exclude,
+                              int64_t c, float gamma, int32_t* pos, int64_t* score);
+
 int scann_comm_unique_id(char* out128);                       /* ncclGetUniqueId on rank 0; broadcast by the caller */
 int scann_comm_init(scann_handle_t* h, const char* id128, int rank, int world);
 /* ranks of the handle's RCCL communicator as RCCL reports them (ncclCommCount); 0 without a communicator (single rank, or the

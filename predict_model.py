@@ -66,6 +66,11 @@ density peaks -- no round clusters are assumed; both passes over all pairs run o
 leading decision values and each cluster's size and centre, pickles the result as ``peaks_<target>.pickle`` and, with ``--peaks-out``,
 saves the labels as a ``LatentPeaks`` (.npz).  ``--density FILE [--density-bandwidth H]`` pickles ``density_<target>.pickle``: per structure
 the Gaussian kernel density of its row (or of its atoms' rows) under a saved ``LatentIndex``, for example of the training set.
+``--prototypes M [--criticisms C] [--prototypes-level atom|structure] [--prototypes-bandwidth H] [--prototypes-out FILE]`` picks the M atoms
+(or structures) that stand for the whole dataset in latent space and the C that those do not stand for (MMD-critic; both greedy loops run
+on the GPU in exact integers, bit-reproducible), prints them with the MMD curve, pickles the result as ``prototypes_<target>.pickle`` and,
+with ``--prototypes-out``, saves the picked rows as a ``LatentPrototypes`` (.npz).  ``--nearest-prototype FILE`` loads such a file and
+pickles ``nearest_prototype_<target>.pickle``: per structure its (or its atoms') nearest prototype and the distance to it.
 ``--hierarchy MIN_CLUSTER_SIZE [--hierarchy-level atom|structure] [--hierarchy-min-samples 5] [--hierarchy-out FILE]`` clusters the dataset's
 atoms (or structures) hierarchically (HDBSCAN; single linkage with ``--hierarchy-min-samples 0``) on the exact minimum spanning tree,
 built on the GPU and bit-reproducible: it prints the tree's size and each cluster's size, persistence and exemplar, and how many rows are
@@ -167,6 +172,7 @@ def main(args):
     class_labels = check_class_head_flags(args)
     embed_sweep = check_embed_flags(args)
     check_peaks_flags(args)
+    check_prototypes_flags(args)
     check_hierarchy_flags(args)
     config = yaml.safe_load(open(os.path.join(args.trained_model, "config.yaml")))
     if args.project:  # (0: the flag was not given)
@@ -533,6 +539,36 @@ def main(args):
         if args.peaks_out:
             peaks.save(args.peaks_out)
         pool.free()
+    if args.prototypes:
+        pool = scann.build_index(data, level=args.prototypes_level, ids=data.indexes)
+        print("Prototypes of the dataset's %d rows (%s level): %d prototypes, %d criticisms" % (
+            len(pool), args.prototypes_level, args.prototypes, args.criticisms))
+        try:
+            res, protos = scann.prototypes(pool, args.prototypes, criticisms=args.criticisms, bandwidth=args.prototypes_bandwidth or "auto")
+        except ValueError as e:  # (too many rows for M, a row with a non-finite component under the automatic bandwidth)
+            pool.free()
+            raise SystemExit("--prototypes: %s" % e) from None
+        print("bandwidth %.6g, %d eligible rows" % (res["bandwidth"], res["n_eligible"]))
+        for s in range(res["count"]):
+            print("prototype %4d: id %d atom %d, mmd2 %.6g%s" % (s, res["id"][s], res["atom"][s], res["mmd2"][s],
+                                                                ", stands for %d rows" % res["size"][s] if "size" in res else ""))
+        for s in range(len(res["criticism_position"])):
+            print("criticism %4d: id %d atom %d, witness %.6g" % (s, res["criticism_id"][s], res["criticism_atom"][s], res["criticism_witness"][s]))
+        pickle.dump(res, open(os.path.join(args.trained_model, "prototypes_{}.pickle".format(target)), "wb"))
+        if args.prototypes_out and protos is not None:
+            protos.save(args.prototypes_out)
+        pool.free()
+    if args.nearest_prototype:
+        from scann.models import LatentPrototypes
+
+        try:
+            protos = LatentPrototypes.load(scann.model, args.nearest_prototype)
+        except ValueError as e:
+            raise SystemExit("--nearest-prototype: %s" % e) from None
+        print("Nearest of the %d prototypes of %s (%s level)" % (protos.m, args.nearest_prototype, protos.level))
+        pickle.dump(nearest_prototype_records(scann, data, protos),
+                    open(os.path.join(args.trained_model, "nearest_prototype_{}.pickle".format(target)), "wb"))
+        protos.free()
     if args.density:
         from scann.models import LatentIndex
 
@@ -643,6 +679,34 @@ def check_peaks_flags(args):
         raise SystemExit("--density-bandwidth: needs --density")
     if args.density and not args.density_bandwidth > 0:
         raise SystemExit("--density: needs --density-bandwidth H > 0 (--peaks prints the one it used)")
+
+
+def check_prototypes_flags(args):
+    """--prototypes and its companions checked before anything is loaded"""
+    if args.prototypes < 0:
+        raise SystemExit("--prototypes: M must be >= 1, got %d" % args.prototypes)
+    if (args.criticisms or args.prototypes_out or args.prototypes_bandwidth) and not args.prototypes:
+        raise SystemExit("--criticisms / --prototypes-out / --prototypes-bandwidth: need --prototypes")
+    if args.criticisms < 0:
+        raise SystemExit("--criticisms: C must be >= 0, got %d" % args.criticisms)
+    if args.prototypes_bandwidth < 0 or args.prototypes_bandwidth != args.prototypes_bandwidth:
+        raise SystemExit("--prototypes-bandwidth: H must be > 0, got %g" % args.prototypes_bandwidth)
+
+
+def nearest_prototype_records(scann, data, protos):
+    """--nearest-prototype: one unpadded dict per structure of the dataset, in dataset order"""
+    per = []
+    atom = protos.level == "atom"
+    for b in range(len(data)):
+        inputs, _ = data[b]
+        r = scann.nearest_prototype(inputs, protos)
+        amask = np.asarray(inputs["atom_mask"]).reshape(np.shape(inputs["neighbors"])[:2]) != 0
+        for i in range(len(amask)):
+            d = {"predict_property": float(r["predict_property"][i, 0])}
+            for key in ("prototype", "prototype_id", "distance") + (("prototype_atom",) if atom else ()):
+                d[key] = r[key][i][amask[i]] if atom else r[key][i]
+            per.append(d)
+    return per
 
 
 def density_records(scann, data, index, bandwidth):
@@ -975,6 +1039,17 @@ def parser():
     p.add_argument("--peaks-bandwidth", type=float, default=0.0, metavar="H",
                    help="kernel width of --peaks (default: automatic, from the 31st-nearest-neighbour distances)")
     p.add_argument("--peaks-out", type=str, default="", help="save the labels as a LatentPeaks (.npz)")
+    p.add_argument("--prototypes", type=int, default=0, metavar="M",
+                   help="also pick the M rows of the dataset that stand for all of it in latent space (MMD-critic, the greedy loop on the GPU in "
+                        "exact integers): prototypes_<target>.pickle")
+    p.add_argument("--criticisms", type=int, default=0, metavar="C", help="with --prototypes: also the C rows the prototypes do not stand for")
+    p.add_argument("--prototypes-level", type=str, default="atom", choices=["atom", "structure"],
+                   help="rows --prototypes picks from: one per atom (after_Lc) or one per structure (bf_property)")
+    p.add_argument("--prototypes-bandwidth", type=float, default=0.0, metavar="H",
+                   help="kernel width of --prototypes (default: automatic, from the 31st-nearest-neighbour distances)")
+    p.add_argument("--prototypes-out", type=str, default="", help="save the picked rows as a LatentPrototypes (.npz)")
+    p.add_argument("--nearest-prototype", type=str, default="", metavar="FILE",
+                   help="a saved LatentPrototypes: pickle every structure's (or atom's) nearest prototype as nearest_prototype_<target>.pickle")
     p.add_argument("--hierarchy", type=int, default=0, metavar="MIN_CLUSTER_SIZE",
                    help="also cluster the dataset's rows in latent space hierarchically (HDBSCAN on the exact minimum spanning tree, built on "
                         "the GPU, bit-reproducible), keeping clusters of at least MIN_CLUSTER_SIZE rows; the result is pickled as "

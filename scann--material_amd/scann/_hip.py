@@ -193,6 +193,10 @@ SYMBOLS = [
     ("scann_index_within_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_float, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("scann_within_host", C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_float, C.c_int64, _P, _P, _P, _P]),
     ("scann_cell_bound", C.c_double, [C.c_float, C.c_float, C.c_float]),
+    ("scann_index_prototypes", C.c_int64, [_P, _P, C.c_int64, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    ("scann_index_criticisms", C.c_int64, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, _P, _P, _P, _P]),
+    ("scann_prototypes_host", C.c_int64, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, _P, _P, _P, _P]),
+    ("scann_criticisms_host", C.c_int64, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_float, _P, _P]),
     ("scann_models_load", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("scann_models_count", C.c_int, [_P]),
     ("scann_forward_models", C.c_int, [_P, _P, C.c_int]),
@@ -1026,6 +1030,87 @@ def peaks_host(rows, gamma):
                                              _ptr(out["delta2"])))
     if rc < 0:
         raise ValueError("peaks_host: invalid arguments (%d)" % rc)
+    return out
+
+
+# prototypes of an index: rows x m may not pass it (the score stays within int64), and a criticism weight's largest value
+PROTO_RANGE = 1 << 32
+PROTO_MAX_WEIGHT = 1 << 31
+
+
+def check_prototypes_args(m, gamma, n_rows):
+    """(m, gamma) of a prototype selection over ``n_rows`` rows as the C calls take them; ValueError for an m that is no integer >= 1, a
+    bad gamma, and for n_rows * m above 2^32, naming both numbers."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+        raise ValueError("m must be an integer >= 1, got %r" % (m,))
+    g = check_peaks_gamma(gamma)
+    if int(n_rows) * int(m) > PROTO_RANGE:
+        raise ValueError("%d rows times m = %d pass 2^32: a prototype score would leave int64" % (n_rows, m))
+    return int(m), g
+
+
+def check_criticisms_args(weight, exclude, c, gamma, n_rows):
+    """(weight int64 [n_rows], exclude int32 [n_exclude], c, gamma) of a criticism selection as the C calls take them; ValueError
+    otherwise, naming the argument."""
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or int(c) < 1:
+        raise ValueError("c must be an integer >= 1, got %r" % (c,))
+    w = np.asarray(weight)
+    if w.dtype.kind not in "iu" or w.shape != (n_rows,):
+        raise ValueError("weight must hold one integer per row (%d), got %s of shape %s" % (n_rows, w.dtype, w.shape))
+    if w.size and (int(w.min()) < 0 or int(w.max()) > PROTO_MAX_WEIGHT):
+        raise ValueError("weight must lie in 0 .. 2^31, got %d .. %d" % (int(w.min()), int(w.max())))
+    e = np.zeros(0, np.int64) if exclude is None else np.asarray(exclude)
+    if e.dtype.kind not in "iu" or e.ndim != 1:
+        raise ValueError("exclude must be a list of integer positions, got %s of shape %s" % (e.dtype, e.shape))
+    if e.size and (int(e.min()) < 0 or int(e.max()) >= n_rows):
+        raise ValueError("exclude holds a position outside the %d rows" % n_rows)
+    return np.ascontiguousarray(w, dtype=np.int64), np.ascontiguousarray(e, dtype=np.int32), int(c), check_peaks_gamma(gamma)
+
+
+def _prototypes_out(m, n, named):
+    out = {"position": np.full(m, -1, np.int32), "score": np.zeros(m, np.int64), "b_at_pick": np.zeros(m, np.int64),
+           "A": np.zeros(n, np.int64), "B": np.zeros(n, np.int64)}
+    if named:
+        out.update(id=np.full(m, -1, np.int64), atom=np.full(m, -1, np.int32))
+    return out
+
+
+def _criticisms_out(c, named):
+    out = {"position": np.full(c, -1, np.int32), "score": np.zeros(c, np.int64)}
+    if named:
+        out.update(id=np.full(c, -1, np.int64), atom=np.full(c, -1, np.int32))
+    return out
+
+
+def prototypes_host(rows, m, gamma):
+    """The greedy MMD-critic prototypes of ``rows`` [n, dim] on the host with the kernel's bits (scann_prototypes_host, the definition in
+    include/scann_hip.h): {"position" int32, "score", "b_at_pick" int64 [m], "A", "B" int64 [n], "count"}; behind ``count``: -1 / 0."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("prototypes_host: rows of shape %s" % (rows.shape,))
+    m, g = check_prototypes_args(m, gamma, rows.shape[0])
+    out = _prototypes_out(m, rows.shape[0], False)
+    cnt = int(load_library().scann_prototypes_host(_ptr(rows), rows.shape[0], rows.shape[1], m, g, _ptr(out["position"]), _ptr(out["score"]),
+                                                   _ptr(out["b_at_pick"]), _ptr(out["A"]), _ptr(out["B"])))
+    if cnt < 0:
+        raise ValueError("prototypes_host: invalid arguments (%d)" % cnt)
+    out["count"] = cnt
+    return out
+
+
+def criticisms_host(rows, weight, exclude, c, gamma):
+    """The criticisms of ``rows`` [n, dim] under the integer ``weight`` [n], the positions ``exclude`` left out, on the host with the
+    kernel's bits (scann_criticisms_host): {"position" int32, "score" int64 [c], "count"}; behind ``count``: -1 / 0."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("criticisms_host: rows of shape %s" % (rows.shape,))
+    w, e, c, g = check_criticisms_args(weight, exclude, c, gamma, rows.shape[0])
+    out = _criticisms_out(c, False)
+    cnt = int(load_library().scann_criticisms_host(_ptr(rows), rows.shape[0], rows.shape[1], _ptr(w), _ptr(e), e.shape[0], c, g,
+                                                   _ptr(out["position"]), _ptr(out["score"])))
+    if cnt < 0:
+        raise ValueError("criticisms_host: invalid arguments (%d)" % cnt)
+    out["count"] = cnt
     return out
 
 
@@ -2448,6 +2533,30 @@ class Engine:
         g = check_peaks_gamma(gamma)
         out = _peaks_out(len(ix))
         self._check(self.lib.scann_index_peaks(self._h, ix._h, g, _ptr(out["sum"]), _ptr(out["parent"]), _ptr(out["delta2"])))
+        return out
+
+    def index_prototypes(self, ix, m, gamma):
+        """The greedy MMD-critic prototypes of the rows of ``ix`` on the device (scann_index_prototypes): ``prototypes_host``'s dict, bit
+        for bit, plus "id" and "atom" [m]."""
+        m, g = check_prototypes_args(m, gamma, len(ix))
+        out = _prototypes_out(m, len(ix), True)
+        cnt = int(self.lib.scann_index_prototypes(self._h, ix._h, m, g, _ptr(out["position"]), _ptr(out["id"]), _ptr(out["atom"]), _ptr(out["score"]),
+                                                  _ptr(out["b_at_pick"]), _ptr(out["A"]), _ptr(out["B"])))
+        if cnt < 0:
+            self._check(cnt)
+        out["count"] = cnt
+        return out
+
+    def index_criticisms(self, ix, weight, exclude, c, gamma):
+        """The criticisms of the rows of ``ix`` under the integer ``weight`` [N], the positions ``exclude`` left out, on the device
+        (scann_index_criticisms): ``criticisms_host``'s dict, bit for bit, plus "id" and "atom" [c]."""
+        w, e, c, g = check_criticisms_args(weight, exclude, c, gamma, len(ix))
+        out = _criticisms_out(c, True)
+        cnt = int(self.lib.scann_index_criticisms(self._h, ix._h, _ptr(w), _ptr(e), e.shape[0], c, g, _ptr(out["position"]), _ptr(out["id"]),
+                                                  _ptr(out["atom"]), _ptr(out["score"])))
+        if cnt < 0:
+            self._check(cnt)
+        out["count"] = cnt
         return out
 
     def index_mst(self, ix, core2=None):

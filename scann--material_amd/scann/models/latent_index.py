@@ -734,6 +734,63 @@ class LatentIndex:
         ids, atoms = eng.index_names(self._ix)  # (host copies: the rows stay on the device)
         return peaks_result(r, ids, atoms, k, min_density, min_delta, h, gamma, self.level, self.dim)
 
+    def prototypes(self, m, criticisms=0, bandwidth="auto", neighbours=31, witness="under", assign=True, route="device"):
+        """The ``m`` rows that stand for all of this index, and the rows those do not stand for: MMD-critic (Kim, Khanna & Koyejo 2016).
+        Prototypes are picked greedily so that the Gaussian kernel mean of the picked set matches the kernel mean of the index; the
+        greedy loop runs on the GPU in exact integers (scann_index_prototypes), so the picks depend on the index contents, the bandwidth
+        and ``m`` only, bit for bit, and the first pick is the densest row.  ``criticisms``: that many rows where the two kernel means
+        still differ most, picked greedily with kernel suppression so that they do not repeat each other (scann_index_criticisms);
+        ``witness`` "under" weighs a row by how far the prototypes under-represent it, "both" by the absolute difference (the paper's
+        rule).  ``bandwidth``: the kernel width h, a positive number, or "auto" as in ``density_peaks``.  ``route`` "host" runs the host
+        twins on the rows read back: the same bits.  Returns ``(result, prototypes)``: {"position" int32, "id" int64, "atom" int32,
+        "score", "b_at_pick" int64 [m'], "mmd2" fp64 [m'] (the squared MMD between the index and the first 1 .. m' prototypes),
+        "witness" fp64 [N] (mean kernel weight to the index less that to the prototypes; NaN for a row with a non-finite component),
+        "A", "B" int64 [N], "count", "n_eligible", "criticism_position", "criticism_id", "criticism_atom", "criticism_score",
+        "criticism_witness", "bandwidth", "gamma", and with ``assign`` and m' <= 1024 "nearest_prototype" int32 [N] and "size" int64
+        [m']} and the ``LatentPrototypes`` that holds the picked rows.  Bad arguments raise ValueError before any device call."""
+        m, criticisms, neighbours, witness, assign, route = prototypes_fit_args(m, criticisms, bandwidth, neighbours, witness, assign, route)
+        N = len(self)
+        if N < 1:
+            raise ValueError("prototypes need at least 1 row, the index has 0")
+        _hip.check_prototypes_args(m, 1.0, N)
+        eng, ix = self.model.engine, self._ix
+        h = peaks_auto_bandwidth(neighbour_graph(self)[1], neighbours) if isinstance(bandwidth, str) else float(bandwidth)
+
+        def rows_at(pos):
+            return np.concatenate([eng.index_read(ix, int(p), 1)[0] for p in pos] + [np.zeros((0, self.dim), np.float32)])
+
+        if route == "device":
+            proto, crit = functools.partial(eng.index_prototypes, ix), functools.partial(eng.index_criticisms, ix)
+            assign_to = (lambda pos: eng.index_kmeans(ix, pos, 0, 0)) if assign else None
+        else:
+            rows = self.rows()[0]
+            proto, crit = functools.partial(_hip.prototypes_host, rows), functools.partial(_hip.criticisms_host, rows)
+            assign_to = (lambda pos: _hip.kmeans_host(rows, rows[pos], 0, 0)) if assign else None
+        return prototypes_run(proto, crit, assign_to, lambda: eng.index_names(ix), rows_at, m, criticisms, h, witness, self.level, self.dim)
+
+    def mmd(self, other, bandwidth, chunk=65536):
+        """The squared maximum mean discrepancy between this index and ``other`` (a ``LatentIndex`` of the same model, level and
+        width) under the Gaussian kernel of width ``bandwidth``: dataset shift in one number.  mmd2 = mean k(a, a') + mean k(b, b') -
+        2 mean k(a, b), every mean over all pairs of rows without a non-finite component, the row itself included.  The self terms come
+        from the two self-joins, the cross term from the density of ``other``'s rows under this index (``chunk`` host queries at a
+        time): integer sums, so the value is exact and order-free.  Returns {"mmd2", "witness" fp64 [len(other)] (mean kernel weight of
+        each row of ``other`` to this index less that to ``other``), "numerator", "denominator" (Python integers), "bandwidth"}."""
+        if not isinstance(other, LatentIndex) or other.model is not self.model or other.level != self.level or other.dim != self.dim:
+            raise ValueError("other must be a %s-level LatentIndex of %d columns of the same model" % (self.level, self.dim))
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+            raise ValueError("chunk must be an integer >= 1, got %r" % (chunk,))
+        gamma = _hip.rbf_gamma(bandwidth)
+        eng = self.model.engine
+
+        def self_sums(index):  # the row itself counts: + 2^30 on the eligible rows
+            S = eng.index_peaks(index._ix, gamma)["sum"] if len(index) else np.zeros(0, np.int64)
+            return np.where(S >= 0, S + PROTO_ONE, -1)
+
+        q = other.rows()[0]
+        cross = [eng.index_density(self._ix, q[i:i + int(chunk)], gamma) for i in range(0, len(q), int(chunk))]
+        mmd2, wit, num, den = mmd_of_sums(self_sums(self), self_sums(other), np.concatenate(cross + [np.zeros(0, np.int64)]))
+        return {"mmd2": mmd2, "witness": wit, "numerator": num, "denominator": den, "bandwidth": float(bandwidth)}
+
     def hierarchy(self, min_samples=5, route="device"):
         """The hierarchical clustering of this index's rows: how the kinds nest, and which rows belong to none.  Single linkage
         (``min_samples`` 0) and density-based hierarchical clustering (HDBSCAN, Campello et al. 2013; ``min_samples`` 1 .. 31) both rest
@@ -2307,6 +2364,185 @@ class LatentPeaks(SavedResult):
         if p.dtype.kind not in "iu" or (p.size and (p.min() < -1 or p.max() >= len(self))):
             raise ValueError("position must hold integers in -1 .. %d" % (len(self) - 1))
         return np.where(p >= 0, self.label[np.maximum(p, 0)], -1).astype(np.int32)
+
+
+PROTO_ONE = 1 << 30  # the fixed-point weight term of two coincident rows
+
+
+def prototypes_fit_args(m, criticisms, bandwidth, neighbours, witness, assign, route):
+    """The arguments of ``LatentIndex.prototypes`` checked: (m, criticisms, neighbours, witness, assign, route); ValueError otherwise,
+    naming the argument"""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+        raise ValueError("m must be an integer >= 1, got %r" % (m,))
+    if isinstance(criticisms, bool) or not isinstance(criticisms, (int, np.integer)) or int(criticisms) < 0:
+        raise ValueError("criticisms must be an integer >= 0, got %r" % (criticisms,))
+    if isinstance(bandwidth, str):
+        if bandwidth != "auto":
+            raise ValueError('bandwidth must be "auto" or a positive number, got %r' % (bandwidth,))
+    else:
+        _hip.rbf_gamma(bandwidth)
+    if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= int(neighbours) <= PEAKS_NEIGHBOURS:
+        raise ValueError("neighbours must be an integer in 1 .. %d, got %r" % (PEAKS_NEIGHBOURS, neighbours))
+    if witness not in ("under", "both"):
+        raise ValueError('witness must be "under" or "both", got %r' % (witness,))
+    if not isinstance(assign, (bool, np.bool_)):
+        raise ValueError("assign must be True or False, got %r" % (assign,))
+    if route not in ("device", "host"):
+        raise ValueError('route must be "device" or "host", got %r' % (route,))
+    return int(m), int(criticisms), int(neighbours), witness, bool(assign), route
+
+
+def prototypes_weights(A, B, n_picks, witness="under"):
+    """The host half between the two selections, in exact integers: from the prototype call's A and B [N] and its number of picks m'
+    the witness numerators W_i = m' A_i - n B_i (|W| < 2^63: the range cap), the witness function W_i / (n m' 2^30) in fp64 (NaN for
+    an ineligible row) and the criticism weights: max(W, 0) ("under": the rows the prototypes under-represent) or |W| ("both", the
+    paper's rule), shifted right until the largest has 31 bits; an ineligible row weighs 0.  -> (W int64, witness fp64, weight int64)"""
+    A, B = np.asarray(A, dtype=np.int64), np.asarray(B, dtype=np.int64)
+    elig = A >= 0
+    n = int(elig.sum())
+    W = np.where(elig, int(n_picks) * A - n * B, 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        wit = np.where(elig, W.astype(np.float64) / float(max(n * int(n_picks), 1) * PROTO_ONE), np.nan)
+    aw = np.maximum(W, 0) if witness == "under" else np.abs(W)
+    top = int(aw.max()) if aw.size else 0
+    return W, wit, aw >> max(0, top.bit_length() - 31)
+
+
+def prototypes_mmd2(A, position, b_at_pick):
+    """The squared MMD between the pool and the first s prototypes, s = 1 .. m', from the prototype call's integers: T = sum A_i over
+    the eligible rows, SA_s = sum of A over the first s picks, K_s = K_{s-1} + 2 b_at_pick_s + 2^30;
+    mmd2[s] = (s^2 T - 2 n s SA_s + n^2 K_s) / (n^2 s^2 2^30), numerator and denominator Python integers, one true division."""
+    A = np.asarray(A, dtype=np.int64)
+    elig = A >= 0
+    n, T = int(elig.sum()), sum(int(x) for x in A[elig])
+    out, SA, K = [], 0, 0
+    for s, (p, b) in enumerate(zip(np.asarray(position).tolist(), np.asarray(b_at_pick).tolist()), 1):
+        SA += int(A[p])
+        K += 2 * int(b) + PROTO_ONE
+        out.append((s * s * T - 2 * n * s * SA + n * n * K) / (n * n * s * s * PROTO_ONE))
+    return np.array(out, dtype=np.float64)
+
+
+def prototypes_run(proto, crit, assign_to, names, rows_at, m, criticisms, h, witness, level, dim):
+    """``LatentIndex.prototypes``'s ``(result, prototypes)``: ``proto(m, gamma)`` and ``crit(weight, exclude, c, gamma)`` are the two
+    selections (the device calls or their twins), ``assign_to(positions)`` the labelling pass or None, ``names()`` the rows' (ids, atoms),
+    ``rows_at(positions)`` their rows"""
+    gamma = _hip.rbf_gamma(h)
+    r = proto(m, gamma)
+    mp = int(r["count"])
+    pos = r["position"][:mp]
+    ids, atoms = names()
+    ids, atoms = np.asarray(ids, dtype=np.int64), np.asarray(atoms, dtype=np.int32)
+    W, wit, weight = prototypes_weights(r["A"], r["B"], max(mp, 1), witness)
+    result = {"position": pos, "id": ids[pos], "atom": atoms[pos], "score": r["score"][:mp], "b_at_pick": r["b_at_pick"][:mp],
+              "mmd2": prototypes_mmd2(r["A"], pos, r["b_at_pick"][:mp]), "witness": wit, "A": r["A"], "B": r["B"], "count": mp,
+              "n_eligible": int((r["A"] >= 0).sum()), "bandwidth": float(h), "gamma": float(gamma)}
+    cpos = np.zeros(0, np.int32)
+    if criticisms and mp:
+        c = crit(weight, pos, criticisms, gamma)
+        cpos = c["position"][:int(c["count"])]
+        result["criticism_score"] = c["score"][:len(cpos)]
+    else:
+        result["criticism_score"] = np.zeros(0, np.int64)
+    result.update(criticism_position=cpos, criticism_id=ids[cpos], criticism_atom=atoms[cpos], criticism_witness=wit[cpos])
+    if assign_to is not None and 1 <= mp <= _hip.KMEANS_MAX_K:
+        a = assign_to(pos)
+        result.update(nearest_prototype=a["label"], size=a["size"])
+    protos = LatentPrototypes(rows_at(pos), ids[pos], atoms[pos], rows_at(cpos), ids[cpos], atoms[cpos], h, level, dim) if mp else None
+    return result, protos
+
+
+def prototypes_rows_host(rows, m, criticisms=0, bandwidth="auto", neighbours=31, witness="under", assign=True, ids=None, atoms=None,
+                         level="structure"):
+    """``LatentIndex.prototypes`` of host rows [N, dim] entirely on the host, no GPU: the twins of the search's distances, of the two
+    selections and of the labelling pass -- bit for bit what an index holding these rows gives by either route."""
+    m, criticisms, neighbours, witness, assign, _ = prototypes_fit_args(m, criticisms, bandwidth, neighbours, witness, assign, "host")
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("rows must have shape [N, dim] with N >= 1, got %s" % (rows.shape,))
+    N, dim = rows.shape
+    _hip.check_prototypes_args(m, 1.0, N)
+    h = peaks_auto_bandwidth(neighbour_graph_host(rows)[1], neighbours) if isinstance(bandwidth, str) else float(bandwidth)
+    ids = np.arange(N, dtype=np.int64) if ids is None else ids
+    atoms = np.full(N, -1, np.int32) if atoms is None else atoms
+    return prototypes_run(functools.partial(_hip.prototypes_host, rows), functools.partial(_hip.criticisms_host, rows),
+                          (lambda pos: _hip.kmeans_host(rows, rows[pos], 0, 0)) if assign else None, lambda: (ids, atoms),
+                          lambda pos: rows[pos], m, criticisms, h, witness, level, dim)
+
+
+def mmd_of_sums(Sa, Sb, cross):
+    """The squared MMD between two samples a and b and b's witness from integer density sums: Sa [na] the sums of a's rows under a (the
+    row itself included), Sb [nb] of b's under b, cross [nb] of b's under a; -1 marks a row with a non-finite component, left out.
+    mmd2 = Ta / na^2 + Tb / nb^2 - 2 X / (na nb), all over 2^30: one true division of Python integers.  witness_j = mean k(b_j, a) -
+    mean k(b_j, b) in fp64, NaN for a row left out.  -> (mmd2, witness [nb], numerator, denominator)"""
+    Sa, Sb, X = (np.asarray(v, dtype=np.int64) for v in (Sa, Sb, cross))
+    ea, eb = Sa >= 0, Sb >= 0
+    na, nb = int(ea.sum()), int(eb.sum())
+    if na < 1 or nb < 1:
+        raise ValueError("the MMD needs a row without a non-finite component on either side, there are %d and %d" % (na, nb))
+    Ta, Tb, Tx = (sum(int(x) for x in v) for v in (Sa[ea], Sb[eb], X[eb]))
+    num, den = Ta * nb * nb + Tb * na * na - 2 * Tx * na * nb, na * na * nb * nb * PROTO_ONE
+    with np.errstate(invalid="ignore"):
+        wit = np.where(eb, X.astype(np.float64) / (na * float(PROTO_ONE)) - Sb.astype(np.float64) / (nb * float(PROTO_ONE)), np.nan)
+    return num / den, wit, num, den
+
+
+class LatentPrototypes(SavedResult):
+    """The prototypes and criticisms of one level of one model, as ``LatentIndex.prototypes`` picks them: their rows, ids and atoms and
+    the kernel width.  ``index_on(model)`` holds the prototype rows as an index, prototype p at position p: a prediction is explained
+    by the nearest of them (``HipModel.nearest_prototype``)."""
+    NOUN = "prototype set"
+    KIND = "prototypes"
+    FIELDS = saved_fields("rows", "ids", "atoms", "criticism_rows", "criticism_ids", "criticism_atoms", ("bandwidth", AS_FLOAT))
+
+    def __init__(self, rows, ids, atoms, criticism_rows, criticism_ids, criticism_atoms, bandwidth, level, dim=None):
+        if level not in LEVELS:
+            raise ValueError("level must be one of %s, got %r" % (", ".join(LEVELS), level))
+        try:
+            self.rows = np.ascontiguousarray(rows, dtype=np.float32)
+            self.ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            self.atoms = np.ascontiguousarray(atoms, dtype=np.int32).reshape(-1)
+            self.criticism_ids = np.ascontiguousarray(criticism_ids, dtype=np.int64).reshape(-1)
+            self.criticism_atoms = np.ascontiguousarray(criticism_atoms, dtype=np.int32).reshape(-1)
+            self.bandwidth = float(bandwidth)
+            width = self.rows.shape[1] if self.rows.ndim == 2 else -1
+            self.criticism_rows = np.ascontiguousarray(criticism_rows, dtype=np.float32).reshape(len(self.criticism_ids), max(width, 1))
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("rows and criticism_rows must be arrays of numbers of one width with one id and one atom per row, and "
+                             "bandwidth a number") from None
+        m = self.rows.shape[0]
+        if self.rows.ndim != 2 or m < 1 or width < 1 or (dim is not None and width != int(dim)):
+            raise ValueError("rows must be an array of at least 1 row%s, got shape %s" % ("" if dim is None else " of %d columns" % int(dim), self.rows.shape))
+        if self.ids.shape != (m,) or self.atoms.shape != (m,) or self.criticism_atoms.shape != self.criticism_ids.shape:
+            raise ValueError("ids and atoms must hold one entry per row")
+        if not np.isfinite(self.rows).all() or not np.isfinite(self.criticism_rows).all():
+            raise ValueError("rows hold a non-finite value")
+        if not (self.bandwidth > 0 and math.isfinite(self.bandwidth)):
+            raise ValueError("bandwidth must be a positive number, got %r" % (bandwidth,))
+        self.level, self.dim = level, int(width)
+        self._index = None  # the prototype rows as an index on a model's GPU (index_on)
+
+    @property
+    def m(self):
+        return int(self.rows.shape[0])
+
+    @classmethod
+    def saved_fits(cls, v, dim):
+        return v["rows"].ndim == 2 and v["rows"].shape[1] == dim
+
+    def index_on(self, model):
+        """The prototype rows as a ``LatentIndex`` on ``model``'s GPU, prototype p at position p under its id and atom (built once per
+        model and kept)."""
+        self.check_model(model)
+        if self._index is None or self._index.model is not model:
+            self.free()
+            self._index = LatentIndex(model, self.level).add_rows(self.rows, self.ids, self.atoms if self.level == "atom" else None)
+        return self._index
+
+    def free(self):
+        if self._index is not None:
+            self._index.free()
+        self._index = None
 
 
 HIER_MAX_SAMPLES = EMBED_NEIGHBOURS  # the farthest neighbour a core distance can look at: what ``neighbour_graph`` returns

@@ -775,6 +775,45 @@ class HipModel:
         with self._indexed(data, level, ids, batch_size) as index:
             return index.density_peaks(k=k, bandwidth=bandwidth, neighbours=neighbours, min_density=min_density, min_delta=min_delta, route=route)
 
+    def prototypes(self, data, m, level="atom", criticisms=0, bandwidth="auto", neighbours=31, witness="under", assign=True, route="device",
+                   ids=None, batch_size=None):
+        """The ``m`` atom environments (``level`` "atom", the ``after_Lc`` rows) or structures ("structure", ``bf_property``) that stand
+        for all of ``data`` in the model's latent space, and the ``criticisms`` that those do not stand for: MMD-critic, both greedy
+        loops exact on the GPU and bit-reproducible (``LatentIndex.prototypes``).  ``data`` is a ``LatentIndex`` (its level counts, not
+        ``level``) or data as ``build_index`` takes it, which is indexed for the call (``ids``: one per structure, default 0 .. n-1) and
+        freed afterwards.  Returns ``(result, prototypes)``: ``LatentIndex.prototypes``'s dict and the ``LatentPrototypes`` that
+        ``nearest_prototype`` takes and that can be saved.  Bad arguments raise ValueError before anything is uploaded."""
+        from .latent_index import prototypes_fit_args
+
+        level_dim(self.config, _level_of(data, level))
+        prototypes_fit_args(m, criticisms, bandwidth, neighbours, witness, assign, route)
+        self._batch_size(batch_size)
+        with self._indexed(data, level, ids, batch_size) as index:
+            return index.prototypes(m, criticisms=criticisms, bandwidth=bandwidth, neighbours=neighbours, witness=witness, assign=assign, route=route)
+
+    def nearest_prototype(self, inputs, prototypes, batch_size=None):
+        """The nearest prototype of every structure (or, for atom-level prototypes, every atom) of new ``inputs`` and its distance,
+        right behind their forward: a prediction explained by an example.  ``nearest`` with k = 1 against an index that holds the
+        prototype rows in order.  A padded dict gives {"predict_property": [B, 1], "prototype": int32 [B] (its place among the
+        prototypes), "prototype_id": int64 [B], "distance": fp32 [B]} and at atom level [B, M] arrays plus "prototype_atom", with -1 / 0
+        at padded atoms; a ``PackedBatch`` gives packed [n_atom] arrays.  Raw y.  Prototypes of another width or a bad batch_size raise
+        ValueError before anything is uploaded."""
+        from .latent_index import LatentPrototypes
+
+        _expect(prototypes, LatentPrototypes, "prototypes")
+        prototypes.check_model(self)
+        self._batch_size(batch_size)
+        index = prototypes.index_on(self)
+        eng, lvl = self.engine, _hip.KNN_LEVELS[index.level]
+        cat = self._run_cat(inputs, batch_size, lambda rb, s0, s1: eng.index_query_batch(index._ix, rb, lvl, 1, None),
+                            {"y": np.zeros(0, np.float32), "dist2": np.zeros((0, 1), np.float32), "id": np.zeros((0, 1), np.int64),
+                             "atom": np.zeros((0, 1), np.int32), "position": np.zeros((0, 1), np.int32)})
+        out = {"predict_property": cat["y"].reshape(-1, 1), "prototype": cat["position"][:, 0], "prototype_id": cat["id"][:, 0],
+               "distance": np.sqrt(cat["dist2"][:, 0])}
+        if index.level == "atom":
+            out["prototype_atom"] = cat["atom"][:, 0]
+        return _repad(out, inputs, index.level, {"distance": 0, "prototype": -1, "prototype_id": -1, "prototype_atom": -1})
+
     def hierarchy(self, data, level="atom", min_samples=5, min_cluster_size=None, route="device", ids=None, batch_size=None):
         """How the kinds of atom environment (``level`` "atom", the ``after_Lc`` rows) or of structure ("structure", ``bf_property``)
         nest, and which rows belong to none: hierarchical clustering in the model's latent space -- single linkage (``min_samples`` 0)
@@ -1600,6 +1639,8 @@ def _facade(name, key):
 
 # the radius search, by the same rule (a table of its own: tests/test_python_layer_host.py counts the entries of the one above)
 FACADE_RADIUS = (("within", "predict_property"), ("duplicates", None))
+# ... and the prototypes
+FACADE_PROTO = (("prototypes", None), ("nearest_prototype", "predict_property"))
 
-for _name, _key in FACADE + FACADE_RADIUS:
+for _name, _key in FACADE + FACADE_RADIUS + FACADE_PROTO:
     setattr(SCANN, _name, _facade(_name, _key))
