@@ -1,7 +1,8 @@
 """Seeded batches on the large side of the launch code's size switches, shared by tests/test_sizes_host.py (which pins that they
-cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py, tests/test_gpu_output_sizes.py and
-tests/test_gpu_parity.py (which compare the kernels on them with references); and batches past 2^31 bytes per tensor, up to the upload
-limit, for tests/test_gpu_large_rows.py.
+cross what they are meant to cross) and tests/test_gpu_sizes.py, tests/test_gpu_mc_sizes.py, tests/test_gpu_output_sizes.py,
+tests/test_gpu_parity.py and tests/test_gpu_input_grad_sizes.py (which compare the kernels on them with references; the last one also
+takes the ring / cgcnn variants below, pinned by tests/test_input_grad_sizes_host.py); and batches past 2^31 bytes per tensor, up to the
+upload limit, for tests/test_gpu_large_rows.py.
 
 The launch code picks a template instantiation, tile height, partial-sum partition or reduction kernel by row count; the
 constants below restate those thresholds, each next to the source line it mirrors.  If a threshold moves, the host test fails
@@ -230,6 +231,50 @@ def chunked(g_update=True):
 
 def deg40(g_update=True):
     return packed(deg40_data(), g_update)
+
+
+# ---- the general embedding's inputs on these batches (tests/test_gpu_input_grad_sizes.py) ----
+
+CHUNKED_RING_SEED = 23
+
+
+def with_cgcnn(pk):
+    """`pk` with 92 seeded 0 / 1 features per atom in place of its atomic numbers (feature cgcnn): rng(5), as
+    test_gpu_input_grads.setup seeds its table"""
+    from scann import _hip
+
+    feat = np.random.default_rng(5).integers(0, 2, size=(pk.n_atom, 92)).astype(np.float32)
+    return _hip.PackedBatch(None, pk.mol_offset, pk.edge_offset, pk.edge_col, pk.edge_dist, pk.edge_weight, ring=pk.ring, cgcnn=feat)
+
+
+def with_ring(pk, seed):
+    """`pk` with a seeded ring / aromatic flag pair per atom (use_ring), for structures whose generator draws none"""
+    from scann import _hip
+
+    ring = np.random.default_rng(seed).integers(0, 2, size=(pk.n_atom, 2)).astype(np.float32)
+    return _hip.PackedBatch(pk.atomic, pk.mol_offset, pk.edge_offset, pk.edge_col, pk.edge_dist, pk.edge_weight, ring=ring, cgcnn=pk.cgcnn)
+
+
+def qm9_b260_cgcnn(g_update=True):
+    pk, targets = qm9_b260(g_update)
+    return with_cgcnn(pk), targets
+
+
+def chunked_ring(g_update=True):
+    """`chunked` with ring flags: chunk tiles under the general embedding"""
+    pk, targets = chunked(g_update)
+    return with_ring(pk, CHUNKED_RING_SEED), targets
+
+
+def small_general(g_update=True):
+    """8 QM9-like molecules with ring flags and cgcnn features (use_ring + feature cgcnn): the batch test_gpu_input_grads.setup(n=8,
+    use_ring=True, feature="cgcnn") builds, on 32-row tiles"""
+    from scann import _hip
+
+    de, dn = so.synth_dataset(8, 1, use_ring=True)
+    inputs, targets = so.pad_batch(de, dn, g_update, use_ring=True)
+    inputs["atomic"] = np.random.default_rng(5).integers(0, 2, size=(101, 92)).astype("float32")[inputs["atomic"]]
+    return _hip.pack_inputs(inputs), np.asarray(targets, np.float32)
 
 
 def upload_tile_rows(pk):

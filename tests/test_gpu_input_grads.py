@@ -43,11 +43,39 @@ def errors(got, ref):
     return out
 
 
-def check(got, cfg, w, pk, refs=None):
+EDGE_LEAVES = ("neighbor_distance", "neighbor_weight")  # [n_edge]; every other leaf has one row per atom
+
+
+def structure_errors(got, ref, pk):
+    """errors() per structure: {leaf: [n_struct]}, each structure's worst entry over ITS OWN max |ref| (errors()' normalisation; the
+    max dominates the rms), so that a structure with small gradients is not measured against the batch's largest.  A structure
+    without entries in a leaf (no edges) counts as equal"""
+    mol = pk.mol_offset.astype(np.int64)
+    bounds = {True: pk.edge_offset.astype(np.int64)[mol], False: mol}
+
+    def seg_max(x, b):
+        out, full = np.zeros(len(b) - 1), b[1:] > b[:-1]
+        if full.any():
+            out[full] = np.maximum.reduceat(x, b[:-1][full])  # (the empty segments between two full ones have no rows to skip)
+        return out
+
+    out = {}
+    for k, r in ref.items():
+        r = np.asarray(r, np.float64)
+        d = np.abs(np.asarray(got[k], np.float64) - r).reshape(r.shape[0], -1).max(1)
+        b = bounds[k in EDGE_LEAVES]
+        assert b[-1] == r.shape[0], (k, r.shape)
+        out[k] = seg_max(d, b) / np.maximum(seg_max(np.abs(r).reshape(r.shape[0], -1).max(1), b), 1e-12)
+    return out
+
+
+def check(got, cfg, w, pk, refs=None, g32=None):
+    """`g32`: the torch-fp32 graph's gradients where the caller has them already (the same call, made once)"""
     import input_grad_ref
 
     y64, ref = refs if refs is not None else input_grad_ref.input_grads(cfg, w, pk)
-    _, g32 = input_grad_ref.input_grads(cfg, w, pk, dtype="float32")
+    if g32 is None:
+        _, g32 = input_grad_ref.input_grads(cfg, w, pk, dtype="float32")
     e_gpu, e_32 = errors(got, ref), errors(g32, ref)
     bad = {k: (e_gpu[k], e_32[k]) for k in ref if not e_gpu[k] <= min(GRAD_CAP, max(GRAD_FLOOR, GRAD_SLACK * e_32[k]))}
     assert not bad, bad
