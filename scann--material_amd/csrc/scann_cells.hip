@@ -44,9 +44,6 @@ __global__ __launch_bounds__(256) void cells_roots_kernel(const float* __restric
   rhi[i] = sqrt((double)hi[i]);  // (+inf stays +inf: a loose tile)
 }
 
-// (d, p) before (e, q) in the total order
-__device__ __forceinline__ bool cell_before(float d, int32_t p, float e, int32_t q) { return d < e || (d == e && p < q); }
-
 // 8 queries per workgroup in LDS, lane t takes centres t, t + 256, ...: one chain per (query, centre), columns ascending, query first
 constexpr int CQ = 8;
 __global__ __launch_bounds__(256) void cells_centre_kernel(CellSearchArgs a) {
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(256) void cells_centre_kernel(CellSearchArgs a) {
 #pragma unroll
     for (int i = 0; i < CQ; ++i) {
       if (q0 + i < a.nq) a.D[(size_t)(q0 + i) * a.C + c] = acc[i];
-      if (acc[i] == acc[i] && cell_before(acc[i], c, best_d[i], best_c[i])) best_d[i] = acc[i], best_c[i] = c;  // a NaN distance never qualifies
+      if (acc[i] == acc[i] && dist_before(acc[i], c, best_d[i], best_c[i])) best_d[i] = acc[i], best_c[i] = c;  // a NaN distance never qualifies
     }
   }
 #pragma unroll
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(256) void cells_centre_kernel(CellSearchArgs a) {
     float d = __builtin_inff();
     int32_t c = 0x7fffffff;
     for (int l = 0; l < 256; ++l)
-      if (cell_before(bd[t * 256 + l], bc[t * 256 + l], d, c)) d = bd[t * 256 + l], c = bc[t * 256 + l];
+      if (dist_before(bd[t * 256 + l], bc[t * 256 + l], d, c)) d = bd[t * 256 + l], c = bc[t * 256 + l];
     a.key_cell[q0 + t] = c == 0x7fffffff ? -1 : c;
     a.key_d[q0 + t] = d;
   }
@@ -282,9 +279,9 @@ __global__ __launch_bounds__(KT) void cells_list_kernel(CellSearchArgs a, int pa
         if (!(d == d)) continue;  // a NaN distance never qualifies
         if (has_qid && idt[r] == my_id) continue;
         if (d > my_tau) continue;  // k rows at most this far are known already; an equal distance stays
-        if (cnt == k && !cell_before(d, p, ld[(k - 1) * TILE_TQ + t], lp[(k - 1) * TILE_TQ + t])) continue;
+        if (cnt == k && !dist_before(d, p, ld[(k - 1) * TILE_TQ + t], lp[(k - 1) * TILE_TQ + t])) continue;
         int j = cnt < k ? cnt : k - 1;
-        for (; j > 0 && cell_before(d, p, ld[(j - 1) * TILE_TQ + t], lp[(j - 1) * TILE_TQ + t]); --j) {
+        for (; j > 0 && dist_before(d, p, ld[(j - 1) * TILE_TQ + t], lp[(j - 1) * TILE_TQ + t]); --j) {
           ld[j * TILE_TQ + t] = ld[(j - 1) * TILE_TQ + t];
           lp[j * TILE_TQ + t] = lp[(j - 1) * TILE_TQ + t];
         }

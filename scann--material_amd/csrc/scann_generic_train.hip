@@ -23,16 +23,6 @@ namespace scann {
 
 namespace {
 
-__device__ __forceinline__ float gen_dswish(float x) {  // d/dx x sigmoid(x) = s (1 + x (1 - s))
-  const float s = 1.0f / (1.0f + expf(-x));
-  return s * (1.0f + x * (1.0f - s));
-}
-__device__ __forceinline__ float gt_wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // sum of p[0], p[stride], ... p[(n - 1) * stride] in that order; eight loads in flight (the additions keep their order)
 __device__ __forceinline__ float gt_ordered_sum(const float* __restrict__ p, int n, size_t stride) {
   float s = 0.f;
@@ -65,7 +55,7 @@ __global__ void gen_act_bwd_kernel(const float* __restrict__ dY, const float* __
   float v = dY[i];
   if (row_scale) v = v * row_scale[i / (size_t)N];
   if (drop_p > 0.f) v = v * drop_scale(drop_seed, drop_tag, i, drop_p);
-  if (pre) v = v * gen_dswish(pre[i]);
+  if (pre) v = v * dswish_exact(pre[i]);
   out[i] = v;
 }
 
@@ -185,20 +175,20 @@ __global__ __launch_bounds__(256) void gen_layernorm_bwd_kernel(const float* __r
   const float* dy = dY + (size_t)r * N;
   float s = 0.f;
   for (int k = lane; k < N; k += 64) s += q ? x[k] + q[k] : x[k];
-  const float mean = gt_wave_sum64(s) / (float)N;
+  const float mean = shfl_sum64(s) / (float)N;
   float v = 0.f;
   for (int k = lane; k < N; k += 64) {
     const float d = (q ? x[k] + q[k] : x[k]) - mean;
     v += d * d;
   }
-  const float rstd = 1.0f / sqrtf(gt_wave_sum64(v) / (float)N + 1e-6f);
+  const float rstd = 1.0f / sqrtf(shfl_sum64(v) / (float)N + 1e-6f);
   float sg = 0.f, sgx = 0.f;
   for (int k = lane; k < N; k += 64) {
     const float xh = ((q ? x[k] + q[k] : x[k]) - mean) * rstd, g = dy[k] * gamma[k];
     sg += g;
     sgx += g * xh;
   }
-  const float mg = gt_wave_sum64(sg) / (float)N, mgx = gt_wave_sum64(sgx) / (float)N;
+  const float mg = shfl_sum64(sg) / (float)N, mgx = shfl_sum64(sgx) / (float)N;
   for (int k = lane; k < N; k += 64) {
     const float xh = ((q ? x[k] + q[k] : x[k]) - mean) * rstd, g = dy[k] * gamma[k];
     dX[(size_t)r * N + k] = rstd * (g - mg - xh * mgx);

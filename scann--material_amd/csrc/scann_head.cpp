@@ -25,9 +25,7 @@ inline void loo_block(const float* rows, int64_t n, int64_t dim, const float* t,
   std::vector<float> y((size_t)dim), z((size_t)m), lev((size_t)L);
   const float nan = std::nanf("");
   for (int64_t p = g * HEAD_TILE; p < std::min<int64_t>(n, (g + 1) * HEAD_TILE); ++p) {
-    bool ok = true;
-    for (int64_t j = 0; j < dim; ++j) ok = ok && std::isfinite(rows[p * dim + j]);
-    for (int32_t k = 0; k < K; ++k) ok = ok && std::isfinite(t[p * K + k]);
+    const bool ok = finite_row(rows + p * dim, dim) && finite_row(t + p * K, K);
     if (resid)
       for (int32_t k = 0; k < K; ++k) resid[p * K + k] = nan;
     if (!ok) continue;

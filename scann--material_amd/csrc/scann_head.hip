@@ -32,49 +32,17 @@ constexpr int HEAD_ZS = HEAD_TILE + 1;           // floats per staged component 
 constexpr int HEAD_CS = HEAD_COLS + 4;           // floats per staged component of the coefficient slab
 constexpr int HEAD_UNION = HEAD_COLS * HEAD_ZS;  // the slabs and the tile of residuals share this: 64 * 129 >= 32 * 129 + 32 * 68
 
-__device__ __forceinline__ bool head_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// frexp's exponent of the float whose bits are b (an absolute value): 0 for zero (pca_exponent)
-__device__ __forceinline__ int head_exponent(uint32_t b) {
-  if (b == 0) return 0;
-  const int ef = (int)(b >> 23);
-  if (ef) return ef - 126;
-  return (31 - __builtin_clz(b)) - 148;
-}
-
-__device__ __forceinline__ int head_bits(uint32_t n) {
-  const int L = n ? 32 - __builtin_clz(n) : 0;
-  return min(24, (62 - L) / 2);
-}
-
-__device__ __forceinline__ const float* head_row(const float* const* rows, int32_t chunk_rows, int32_t stride, int64_t p) {
-  const uint32_t ch = (uint32_t)p / (uint32_t)chunk_rows, r = (uint32_t)p - ch * (uint32_t)chunk_rows;
-  return rows[ch] + (size_t)r * stride;
-}
-
-// 8 lanes per row, 32 rows per workgroup and pass
+// the eligibility scan (scann_prim.h) over the rows, where there are any, and the K targets of a row, its 8 lanes taking one in turn
 __global__ __launch_bounds__(HEAD_LANES) void head_mask_kernel(const float* const* rows, int chunk_rows, int stride, int n_total, const float* t, int K,
                                                                uint8_t* mask) {
-  const int tid = threadIdx.x, sub = tid & 7;
-  const int n_pass = (n_total + 31) / 32;
-  for (int g = blockIdx.x; g < n_pass; g += gridDim.x) {
-    const int p = g * 32 + (tid >> 3);
-    int bad = 0;
-    if (p < n_total) {
-      for (int k = sub; k < K; k += 8) bad |= !head_finite(t[(size_t)p * K + k]);
-      if (rows) {
-        const float* row = head_row(rows, chunk_rows, stride, p);
-        for (int c = 4 * sub; c < stride; c += 32) {
-          const float4 v = *reinterpret_cast<const float4*>(row + c);
-          bad |= !(head_finite(v.x) && head_finite(v.y) && head_finite(v.z) && head_finite(v.w));
-        }
-      }
-    }
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    bad |= __shfl_xor(bad, 4);
-    if (p < n_total && sub == 0) mask[p] = bad ? 0 : 1;
-  }
+  eligible_scan(
+      rows, chunk_rows, stride, n_total,
+      [&](int p, int sub) {
+        int bad = 0;
+        for (int k = sub; k < K; k += 8) bad |= !f32_finite(t[(size_t)p * K + k]);
+        return bad;
+      },
+      [&](int p, int bad) { mask[p] = bad ? 0 : 1; });
 }
 
 // MODE 0: tmax_k = max |t|; MODE 1: S_k += q(t, k); MODE 2: tcen_k = max |t - mean_k|; over the eligible rows, a lane one row at a time
@@ -91,7 +59,7 @@ __global__ __launch_bounds__(HEAD_LANES) void head_tstat_kernel(PcaArgs a, HeadM
 #pragma unroll
   for (int k = 0; k < HEAD_KMAX; ++k) {
     s[k] = 0, mx[k] = 0;
-    sh[k] = MODE == 1 && k < K ? 30 - head_exponent(m.tmax[k]) : 0;
+    sh[k] = MODE == 1 && k < K ? 30 - f32_exponent(m.tmax[k]) : 0;
     mean[k] = MODE == 2 && k < K ? m.tmean[k] : 0.f;
   }
   for (int64_t p = (int64_t)blockIdx.x * HEAD_LANES + tid; p < a.n_total; p += (int64_t)gridDim.x * HEAD_LANES) {
@@ -133,7 +101,7 @@ __global__ __launch_bounds__(HEAD_LANES) void head_tmean_kernel(PcaArgs a, HeadM
   float mu = 0.f;
   if (n > 0) {
     const double q = (double)(long long)m.tsum[k] / (double)n;
-    mu = (float)__builtin_ldexp(q, head_exponent(m.tmax[k]) - 30);
+    mu = (float)__builtin_ldexp(q, f32_exponent(m.tmax[k]) - 30);
   }
   m.tmean[k] = mu;
 }
@@ -145,16 +113,16 @@ __global__ __launch_bounds__(HEAD_LANES) void head_cross_kernel(PcaArgs a, HeadM
   int* vs = reinterpret_cast<int*>(vs4);
   const uint32_t n = a.st->n;
   if (n < 2) return;  // (uniform)
-  const int bits = head_bits(n);
+  const int bits = sum_bits(n);
   const int tid = threadIdx.x, K = m.K;
   const int j = blockIdx.y * HEAD_LANES + tid;
   const bool inj = j < a.stride;
   const float meanj = inj ? a.mean[j] : 0.f;
-  const int shj = bits - (inj ? head_exponent(a.cenmax[j]) : 0);
+  const int shj = bits - (inj ? f32_exponent(a.cenmax[j]) : 0);
   // staging: the lane quantises target tid & 15 of rows (tid >> 4) + 16 i of a slab
   const int sk = tid & 15, sr = tid >> 4;
   const float meant = sk < K ? m.tmean[sk] : 0.f;
-  const int sht = bits - (sk < K ? head_exponent(m.tcen[sk]) : 0);
+  const int sht = bits - (sk < K ? f32_exponent(m.tcen[sk]) : 0);
   const bool first = blockIdx.y == 0;  // these workgroups also sum the K x K block (lane = (k1, k2)) and R of the targets
   long long acc[HEAD_KMAX], tt = 0, rt = 0;
 #pragma unroll
@@ -179,7 +147,7 @@ __global__ __launch_bounds__(HEAD_LANES) void head_cross_kernel(PcaArgs a, HeadM
     for (int r = 0; r < nr; ++r) {
       if (!els[r]) continue;  // (uniform)
       int u = 0;
-      if (inj) u = (int)__builtin_rint(__builtin_ldexp((double)(head_row(a.rows, a.chunk_rows, a.stride, p0 + r)[j] - meanj), shj));
+      if (inj) u = (int)__builtin_rint(__builtin_ldexp((double)(tile_row(a.rows, (uint32_t)(p0 + r), (uint32_t)a.chunk_rows, a.stride)[j] - meanj), shj));
       const int4 v0 = vs4[r * 4], v1 = vs4[r * 4 + 1], v2 = vs4[r * 4 + 2], v3 = vs4[r * 4 + 3];
       const int v[HEAD_KMAX] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
 #pragma unroll
@@ -210,9 +178,9 @@ __global__ __launch_bounds__(HEAD_LANES) void head_cross_finalise_kernel(PcaArgs
   const int64_t e = (int64_t)blockIdx.x * HEAD_LANES + threadIdx.x;
   const int i = (int)(e / K), k = (int)(e % K);
   if (i >= D) return;
-  const int bits = head_bits(n);
+  const int bits = sum_bits(n);
   const bool x = i < a.dim;
-  const int fi = head_exponent(x ? a.cenmax[i] : m.tcen[i - a.dim]), fk = head_exponent(m.tcen[k]);
+  const int fi = f32_exponent(x ? a.cenmax[i] : m.tcen[i - a.dim]), fk = f32_exponent(m.tcen[k]);
   const double T = (double)(long long)(x ? m.Txt[(size_t)i * HEAD_KMAX + k] : m.Ttt[(i - a.dim) * HEAD_KMAX + k]);
   const double Ri = (double)(long long)(x ? a.R[i] : m.Rt[i - a.dim]), Rk = (double)(long long)m.Rt[k];
   const double prod = Ri * Rk;

@@ -3,31 +3,18 @@
 // (local_dim) is a run-time argument, so the same kernels serve the 128 / 8 MFMA handles and the plain-fp32 generic-width ones; the
 // weights are read as row-major Keras tensors [in, out] (the 128-wide handles keep raw copies of exactly these in their arena).
 #include "scann_train.h"
+#include "scann_mma.h"
 
 namespace scann {
 
 namespace {
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float swish_f(float x) { return x * sigm(x); }
-__device__ __forceinline__ float dswish_f(float x) {  // d/dx x * sigmoid(x)
-  const float s = sigm(x);
-  return s * (1.0f + x * (1.0f - s));
-}
-
-// sum over the 64 lanes of a wave, the same butterfly order in every call
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // Gaussian expansion exp(-(x - c_k)^2 / 0.25) (custom_layers.py:63-65, width 0.5 squared) and its derivative in x
 __device__ __forceinline__ void gauss20(float x, const float* __restrict__ cen, float* g, float* dg) {
 #pragma unroll
   for (int k = 0; k < NG; ++k) {
     const float d = x - cen[k];
-    g[k] = expf(-(d * d) / 0.25f);
+    g[k] = gauss(x, cen[k]);
     dg[k] = -8.0f * d * g[k];
   }
 }
@@ -61,11 +48,11 @@ __global__ __launch_bounds__(256) void basis_input_grad_kernel(const float* __re
       tw = fmaf(dgw[k], wwk, tw);
     }
     const float g = dg[c];
-    sd = fmaf(g * swish_f(aw) * dswish_f(ad), td, sd);
-    sw = fmaf(g * swish_f(ad) * dswish_f(aw), tw, sw);
+    sd = fmaf(g * swish_exact(aw) * dswish_exact(ad), td, sd);
+    sw = fmaf(g * swish_exact(ad) * dswish_exact(aw), tw, sw);
   }
-  sd = wave_sum(sd);
-  sw = wave_sum(sw);
+  sd = shfl_sum64(sd);
+  sw = shfl_sum64(sw);
   if (lane == 0) {
     if (d_dist) d_dist[e] = sd;
     if (d_weight) d_weight[e] = sw;
@@ -97,11 +84,11 @@ __global__ __launch_bounds__(256) void base_input_grad_kernel(const float* __res
       t = fmaf(dgd[k], wk, t);
     }
     const float g = dg[c];
-    sw = fmaf(g, swish_f(pre), sw);
-    sd = fmaf(g * w * dswish_f(pre), t, sd);
+    sw = fmaf(g, swish_exact(pre), sw);
+    sd = fmaf(g * w * dswish_exact(pre), t, sd);
   }
-  sd = wave_sum(sd);
-  sw = wave_sum(sw);
+  sd = shfl_sum64(sd);
+  sw = shfl_sum64(sw);
   if (lane == 0) {
     if (d_dist) d_dist[e] += sd;
     if (d_weight) d_weight[e] += sw;
@@ -138,13 +125,13 @@ __global__ __launch_bounds__(256) void embed_input_grad_kernel(InputGradEmbed a)
   for (int c = tid; c < W; c += blockDim.x) {
     float pre = a.bde[c];
     for (int k = 0; k < cin; ++k) pre = fmaf(v[k], a.Wde[(size_t)k * W + c], pre);
-    dpre[c] = a.dC[(size_t)atom * W + c] * dswish_f(pre);
+    dpre[c] = a.dC[(size_t)atom * W + c] * dswish_exact(pre);
   }
   __syncthreads();
   for (int k = wave; k < cin; k += (int)(blockDim.x >> 6)) {  // row k of Wde against dpre: one wave, lanes over the columns
     float s = 0.f;
     for (int c = lane; c < W; c += 64) s = fmaf(dpre[c], a.Wde[(size_t)k * W + c], s);
-    s = wave_sum(s);
+    s = shfl_sum64(s);
     if (lane == 0) dv[k] = s;
   }
   __syncthreads();

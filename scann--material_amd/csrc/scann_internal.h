@@ -91,6 +91,13 @@ __device__ __forceinline__ double gen_pool_score(const float* __restrict__ gq, c
   }
   return agg;
 }
+// Sum over the 64 lanes of a wave by the xor butterfly 32 down to 1, every lane getting it: the one order of the plain-fp32 kernels
+// (scann_generic.hip, scann_generic_train.hip, scann_input_grad.hip), which keep their summation order whatever scann_mma.h does
+__device__ __forceinline__ float shfl_sum64(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 #endif
 
 // Range guard of the split-fp16 projections (|activation| and |weight| * 2^8 must stay below 65504, the largest fp16): an operand

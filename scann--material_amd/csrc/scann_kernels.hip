@@ -733,10 +733,8 @@ void launch_embed(const EmbedArgs& a, hipStream_t s) {
 
 // ---- readout kernel ----------------------------------------------------------------------------------
 
-// (DPP / lane-swap forms of the xor butterflies: the same additions and maxima without six LDS round trips each -- in the readout
-//  they sit one behind the other: norm -> maximum -> sum of the exponentials -> head)
-__device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
-__device__ __forceinline__ float wave_max(float v) { return wave_max64(v); }
+// (wave_sum64 / wave_max64, scann_mma.h: DPP / lane-swap forms of the xor butterflies, the same additions and maxima without six LDS
+//  round trips each -- in the readout they sit one behind the other: norm -> maximum -> sum of the exponentials -> head)
 
 // One workgroup per structure.  GlobalAttention.call (attention.py:267-318) on the real atoms only (the
 // multiplicative atom mask zeroes every padded term).  The pair energies E[i][j] = k_i . q_j (:279) are 32x32 MFMA
@@ -815,7 +813,7 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
     if (a.use_ga_norm) {
       float ss = 0.f;
       for (int i = lane; i < n; i += 64) ss += sAgg[i] * sAgg[i];
-      nrm = sqrtf(wave_sum(ss));  // tf.linalg.normalize: no epsilon (n == 1 -> 0/0 = NaN as in the reference)
+      nrm = sqrtf(wave_sum64(ss));  // tf.linalg.normalize: no epsilon (n == 1 -> 0/0 = NaN as in the reference)
     }
     float m = -INFINITY;
     for (int i = lane; i < n; i += 64) {
@@ -823,14 +821,14 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
       sAgg[i] = v;
       m = fmaxf(m, v);
     }
-    m = wave_max(m);
+    m = wave_max64(m);
     float ss = 0.f;
     for (int i = lane; i < n; i += 64) {
       const float e = expf(sAgg[i] - m);
       sAgg[i] = e;
       ss += e;
     }
-    ss = wave_sum(ss);
+    ss = wave_sum64(ss);
     for (int i = lane; i < n; i += 64) {
       const float at = sAgg[i] / ss;
       sAgg[i] = at;
@@ -890,7 +888,7 @@ __global__ __launch_bounds__(256) void readout_kernel(ReadoutArgs a) {
       part = hb * a.p.wo[f];
     }
   }
-  part = wave_sum(part);
+  part = wave_sum64(part);
   if (lane == 0) sRed[wave] = part;
   __syncthreads();
   if (tid == 0) {

@@ -9,13 +9,6 @@ using namespace scann;
 
 extern "C" {
 
-// frexp's exponent of a column's largest |x| (0 for a column of zeros): the scale of the update's integer sums
-static int kmeans_exponent(float m) {
-  int e = 0;
-  if (m > 0.f) (void)std::frexp(m, &e);
-  return e;
-}
-
 int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, const float* init, int32_t max_iter, int64_t stop_changed,
                           int32_t* labels, float* dist2, float* centres, int64_t* sizes, int32_t* converged) {
   if (n < 0 || n > (int64_t)0x7fffffff || dim < 1 || k < 1 || k > SCANN_KMEANS_MAX_K || !init || max_iter < 0 || stop_changed < 0 || !centres ||
@@ -29,11 +22,10 @@ int64_t scann_kmeans_host(const float* rows, int64_t n, int64_t dim, int32_t k, 
   {
     std::vector<float> mx((size_t)dim, 0.f);
     for (int64_t p = 0; p < n; ++p) {
-      for (int64_t j = 0; j < dim; ++j)
-        if (!std::isfinite(rows[p * dim + j])) elig[(size_t)p] = 0;
+      elig[(size_t)p] = finite_row(rows + p * dim, dim);
       for (int64_t j = 0; j < dim && elig[(size_t)p]; ++j) mx[(size_t)j] = std::max(mx[(size_t)j], std::fabs(rows[p * dim + j]));
     }
-    for (int64_t j = 0; j < dim; ++j) ex[(size_t)j] = kmeans_exponent(mx[(size_t)j]);
+    for (int64_t j = 0; j < dim; ++j) ex[(size_t)j] = frexp_exponent(mx[(size_t)j]);  // the scale of the update's integer sums
   }
   std::vector<int32_t> lab((size_t)n, -1);
   std::vector<float> d2((size_t)n, __builtin_inff()), tmp((size_t)k);

@@ -38,61 +38,19 @@ namespace {
 
 constexpr int KM_ASSIGN_SMEM = TILE_SLABS + 4 * KM_TP * 2;  // floats of the two slabs, then per wave and row the wave's first centre (dist2, index)
 
-__device__ __forceinline__ bool km_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// frexp's exponent of the float whose bits are b (b >= 0: an absolute value): b < 2^e; 0 for zero
-__device__ __forceinline__ int km_exponent(uint32_t b) {
-  if (b == 0) return 0;
-  const int ef = (int)(b >> 23);
-  if (ef) return ef - 126;
-  return (31 - __builtin_clz(b)) - 148;  // subnormal: b * 2^-149
-}
-
 __device__ __forceinline__ int km_slot(int t) { return t & (KM_ROUNDS - 1); }
 // the loop ends with round t's assignment
 __device__ __forceinline__ bool km_last_round(const KmArgs& a, int t, uint32_t changed) {
   return (int64_t)changed <= a.stop_changed || t >= a.max_iter;
 }
 
-// 8 lanes per row, 32 rows per workgroup and pass
+// the eligibility scan with the column maxima (scann_prim.h)
 __global__ __launch_bounds__(KM_LANES) void kmeans_prepare_kernel(KmArgs a) {
-  __shared__ uint32_t cmax[1024];
-  const int t = threadIdx.x, sub = t & 7;
-  for (int j = t; j < a.stride; j += KM_LANES) cmax[j] = 0;
-  __syncthreads();
-  const int n_pass = (a.n_total + 31) / 32;
-  for (int g = blockIdx.x; g < n_pass; g += gridDim.x) {
-    const int p = g * 32 + (t >> 3);
-    int bad = 0;
-    const float* row = nullptr;
-    if (p < a.n_total) {
-      row = a.rows[p / a.chunk_rows] + (size_t)(p % a.chunk_rows) * a.stride;
-      for (int c = 4 * sub; c < a.stride; c += 32) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        bad |= !(km_finite(v.x) && km_finite(v.y) && km_finite(v.z) && km_finite(v.w));
-      }
-    }
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    bad |= __shfl_xor(bad, 4);
-    if (p >= a.n_total) continue;
-    if (sub == 0) {
-      a.elig[p] = bad ? 0 : 1;
-      a.labels[p] = -1;
-      a.dist2[p] = __builtin_inff();
-    }
-    if (bad) continue;
-    for (int c = 4 * sub; c < a.stride; c += 32) {  // (the row is in the cache)
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      atomicMax(&cmax[c], __float_as_uint(v.x) & 0x7fffffffu);
-      atomicMax(&cmax[c + 1], __float_as_uint(v.y) & 0x7fffffffu);
-      atomicMax(&cmax[c + 2], __float_as_uint(v.z) & 0x7fffffffu);
-      atomicMax(&cmax[c + 3], __float_as_uint(v.w) & 0x7fffffffu);
-    }
-  }
-  __syncthreads();
-  for (int j = t; j < a.stride; j += KM_LANES)
-    if (cmax[j]) atomicMax(&a.colmax[j], cmax[j]);
+  eligible_scan_colmax<KM_LANES>(a.rows, a.chunk_rows, a.stride, a.n_total, a.colmax, NoExtra{}, [&](int p, int bad) {
+    a.elig[p] = bad ? 0 : 1;
+    a.labels[p] = -1;
+    a.dist2[p] = __builtin_inff();
+  });
 }
 
 // one workgroup per centre
@@ -105,11 +63,13 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_gather_kernel(KmArgs a) {
     }
     return;
   }
-  const float* row = a.rows[p / a.chunk_rows] + (size_t)(p % a.chunk_rows) * a.stride;
+  const float* row = tile_row(a.rows, p, a.chunk_rows, a.stride);
   for (int j = threadIdx.x; j < a.stride; j += KM_LANES) a.centres[(size_t)c * a.stride + j] = row[j];
 }
 
-// (d, l) before (e, m) in the total order; l < 0: no centre yet, behind every other
+// (d, l) before (e, m) in the total order; l < 0: no centre yet, behind every other.  The last line is dist_before (scann_prim.h)
+// written out: behind the call hipcc compiles kmeans_assign_kernel's reduction to branches on the exec mask in place of selects, and at
+// k = 256 a call of five rounds over 2.4 M rows then takes 1 % longer (profiles/primitives_refactor.txt, section 5)
 __device__ __forceinline__ bool km_before(float d, int32_t l, float e, int32_t m) {
   if (l < 0) return false;
   if (m < 0) return true;
@@ -236,7 +196,7 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_sum_kernel(KmArgs a, int roun
   const bool in_col = col < a.stride, counts = blockIdx.y == 0 && lc == 0;
   int sh[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) sh[j] = 30 - (in_col ? km_exponent(a.colmax[col + j]) : 0);
+  for (int j = 0; j < 4; ++j) sh[j] = 30 - (in_col ? f32_exponent(a.colmax[col + j]) : 0);
   const int64_t p_end = min((int64_t)a.n_total, ((int64_t)blockIdx.x + 1) * rows_per_group);
   for (int64_t p0 = (int64_t)blockIdx.x * rows_per_group + rsub; p0 < p_end; p0 += 8 * R) {
     int32_t l[8];
@@ -251,8 +211,7 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_sum_kernel(KmArgs a, int roun
       const int64_t p = p0 + (int64_t)i * R;
       x[i] = float4{0.f, 0.f, 0.f, 0.f};
       if (l[i] >= 0 && in_col) {
-        const uint32_t ch = (uint32_t)p / (uint32_t)a.chunk_rows, r = (uint32_t)p - ch * (uint32_t)a.chunk_rows;
-        x[i] = *reinterpret_cast<const float4*>(a.rows[ch] + (size_t)r * a.stride + col);
+        x[i] = *reinterpret_cast<const float4*>(tile_row(a.rows, (uint32_t)p, (uint32_t)a.chunk_rows, a.stride) + col);
       }
     }
 #pragma unroll
@@ -300,7 +259,7 @@ __global__ __launch_bounds__(KM_LANES) void kmeans_finalise_kernel(KmArgs a, int
     const size_t o = (size_t)c * a.stride + j;
     if (n > 0 && j < a.dim) {
       const double mean = (double)(long long)a.sums[o] / (double)n;  // both conversions and the division round to nearest
-      a.centres[o] = (float)__builtin_ldexp(mean, km_exponent(a.colmax[j]) - 30);
+      a.centres[o] = (float)__builtin_ldexp(mean, f32_exponent(a.colmax[j]) - 30);
     }
     a.sums[o] = 0;
   }

@@ -100,9 +100,6 @@ __global__ __launch_bounds__(KT) void knn_tile_kernel(KnnArgs a) {
   }
 }
 
-// (d, p) before (e, q) in the total order
-__device__ __forceinline__ bool knn_before(float d, int32_t p, float e, int32_t q) { return d < e || (d == e && p < q); }
-
 __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_p, int n_range, int k,
                                                        float* __restrict__ out_d, int32_t* __restrict__ out_p) {
   extern __shared__ float4 knn_smem[];
@@ -122,7 +119,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
       const int32_t p = part_p[e];
       if (p < 0) continue;  // the list has ended
       const float d = part_d[e];
-      if (knn_before(d, p, bd, bp)) bd = d, bp = p, bl = l;
+      if (dist_before(d, p, bd, bp)) bd = d, bp = p, bl = l;
     }
     float wd = bd;
     int32_t wp = bp;
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
     for (int off = 32; off > 0; off >>= 1) {
       const float od = __shfl_xor(wd, off);
       const int32_t op = __shfl_xor(wp, off);
-      if (knn_before(od, op, wd, wp)) wd = od, wp = op;
+      if (dist_before(od, op, wd, wp)) wd = od, wp = op;
     }
     if (wp != NONE && bp == wp) ++head[bl];  // positions are unique: one lane advances one list
     if (lane == 0) {

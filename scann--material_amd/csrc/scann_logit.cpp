@@ -50,9 +50,7 @@ inline void span_sums(const PassCall& c, int64_t s) {
     for (int64_t p = p0; p < std::min<int64_t>(c.n, p0 + LOGIT_BLOCK); ++p) {
       const float* x = c.rows + p * c.dim;
       const int32_t label = c.labels[p];
-      bool ok = label >= 0 && label < c.C;
-      for (int64_t j = 0; ok && j < c.dim; ++j) ok = std::isfinite(x[j]);
-      if (!ok) continue;
+      if (label < 0 || label >= c.C || !finite_row(x, c.dim)) continue;
       ++used;
       for (int64_t j = 0; j < c.dim; ++j) y[(size_t)j] = x[j] - c.mean[j];
       const int32_t fp = c.F > 0 ? (int32_t)(p % c.F) : 0;

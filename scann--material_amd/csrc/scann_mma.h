@@ -181,6 +181,13 @@ __device__ __forceinline__ float sum8(float v) {
   v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
   return v;
 }
+// Sum over the whole wave in the order of the attention backward (attn_bwd16_kernel and its fused form): sum8, then the other half of
+// the row of 16, then the two lane swaps.  Not wave_sum64: the fourth step there is row_mirror, and a gradient's bits follow the steps.
+__device__ __forceinline__ float red64(float v) {
+  v = sum8(v);
+  v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x128, 0xF, 0xF, true));  // row_ror:8
+  return xor32(xor16(v));
+}
 // LayerNormalization(epsilon = 1e-6) in the forward kernels (attention.py:35,111,113; Keras' non-fused form is x inv + (beta - mean inv),
 // inv = rsqrt(var + eps) gamma: four roundings per element).  Here 1 / sqrt(var + eps) is ONE v_rsq_f32 (1 ulp; the correctly rounded
 // sqrt + division it replaces are ~28 instructions per row) and an element is two fused multiply-adds, ((x rstd - mean rstd) gamma +
@@ -217,7 +224,14 @@ __device__ __forceinline__ float4 f4swish_plus(float4 v, float4 g) {
   return make_float4(swish_plus(v.x, g.x), swish_plus(v.y, g.y), swish_plus(v.z, g.z), swish_plus(v.w, g.w));
 }
 
-__device__ __forceinline__ float swish_exact(float x) { return x * (1.0f / (1.0f + expf(-x))); }
+// the exact forms (expf and a division) of the training path, the plain-fp32 path and the explanations: sigmoid, swish = x sigmoid(x)
+// and swish' = s (1 + x (1 - s))
+__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float swish_exact(float x) { return x * sigmoid_exact(x); }
+__device__ __forceinline__ float dswish_exact(float x) {
+  const float s = sigmoid_exact(x);
+  return s * (1.0f + x * (1.0f - s));
+}
 
 // e^x through v_exp_f32 (2^x, 1 ulp); used where the argument is <= 0 (softmax numerators).
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }

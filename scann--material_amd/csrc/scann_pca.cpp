@@ -20,13 +20,6 @@
 
 namespace {
 
-// frexp's exponent of a column's largest absolute value (0 for a column of zeros)
-int top_exponent(float m) {
-  int e = 0;
-  if (m > 0.f) (void)std::frexp(m, &e);
-  return e;
-}
-
 // T[i][j] += sum over the rows of u[p][i] * u[p][j] for i = first, first + step, ... and j >= i: integer sums, so any split over threads gives the same
 void scatter_rows(const int32_t* u, int64_t n, int64_t dim, int64_t first, int64_t step, int64_t* T) {
   for (int64_t p = 0; p < n; ++p) {
@@ -88,9 +81,7 @@ int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eli
   std::vector<int64_t> live;
   std::vector<float> mx((size_t)dim, 0.f);
   for (int64_t p = 0; p < n; ++p) {
-    bool ok = true;
-    for (int64_t j = 0; j < dim; ++j) ok = ok && std::isfinite(rows[p * dim + j]);
-    if (!ok) continue;
+    if (!scann::finite_row(rows + p * dim, dim)) continue;
     live.push_back(p);
     for (int64_t j = 0; j < dim; ++j) mx[(size_t)j] = std::max(mx[(size_t)j], std::fabs(rows[p * dim + j]));
   }
@@ -101,7 +92,7 @@ int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eli
   if (bits) *bits = b;
   std::vector<int64_t> S((size_t)dim, 0);
   for (int64_t j = 0; j < dim; ++j) {
-    const int e = top_exponent(mx[(size_t)j]);
+    const int e = scann::frexp_exponent(mx[(size_t)j]);
     for (int64_t p : live) S[(size_t)j] += std::llrint(std::ldexp((double)rows[p * dim + j], 30 - e));
     mean[j] = (float)std::ldexp((double)S[(size_t)j] / (double)ne, e - 30);
   }
@@ -109,7 +100,7 @@ int scann_moments_host(const float* rows, int64_t n, int64_t dim, int64_t* n_eli
   for (int64_t j = 0; j < dim; ++j) {
     float m = 0.f;
     for (int64_t p : live) m = std::max(m, std::fabs(rows[p * dim + j] - mean[j]));
-    f[(size_t)j] = top_exponent(m);
+    f[(size_t)j] = scann::frexp_exponent(m);
     if (col_exp) col_exp[j] = f[(size_t)j];
   }
   std::vector<int32_t> u((size_t)ne * dim);

@@ -33,69 +33,17 @@ namespace scann {
 
 namespace {
 
-__device__ __forceinline__ bool pca_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// frexp's exponent of the float whose bits are b (b >= 0: an absolute value): b < 2^e; 0 for zero
-__device__ __forceinline__ int pca_exponent(uint32_t b) {
-  if (b == 0) return 0;
-  const int ef = (int)(b >> 23);
-  if (ef) return ef - 126;
-  return (31 - __builtin_clz(b)) - 148;  // subnormal: b * 2^-149
-}
-
-// b of the definition: n < 2^L
-__device__ __forceinline__ int pca_bits(uint32_t n) {
-  const int L = n ? 32 - __builtin_clz(n) : 0;
-  return min(24, (62 - L) / 2);
-}
-
-__device__ __forceinline__ const float* pca_row(const float* const* rows, int32_t chunk_rows, int32_t stride, int64_t p) {
-  const uint32_t ch = (uint32_t)p / (uint32_t)chunk_rows, r = (uint32_t)p - ch * (uint32_t)chunk_rows;
-  return rows[ch] + (size_t)r * stride;
-}
-
-// 8 lanes per row, 32 rows per workgroup and pass
+// the eligibility scan with the column maxima (scann_prim.h); the barriers of eligible_scan_colmax also order the count
 __global__ __launch_bounds__(PCA_LANES) void pca_prepare_kernel(PcaArgs a) {
-  __shared__ uint32_t cmax[1024];
   __shared__ uint32_t cnt;
-  const int t = threadIdx.x, sub = t & 7;
-  for (int j = t; j < a.stride; j += PCA_LANES) cmax[j] = 0;
-  if (t == 0) cnt = 0;
-  __syncthreads();
-  const int n_pass = (a.n_total + 31) / 32;
-  for (int g = blockIdx.x; g < n_pass; g += gridDim.x) {
-    const int p = g * 32 + (t >> 3);
-    int bad = 0;
-    const float* row = nullptr;
-    if (p < a.n_total) {
-      row = pca_row(a.rows, a.chunk_rows, a.stride, p);
-      if (a.mask) bad = !a.mask[p];
-      for (int c = 4 * sub; c < a.stride; c += 32) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        bad |= !(pca_finite(v.x) && pca_finite(v.y) && pca_finite(v.z) && pca_finite(v.w));
-      }
-    }
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    bad |= __shfl_xor(bad, 4);
-    if (p >= a.n_total) continue;
-    if (sub == 0) {
-      a.elig[p] = bad ? 0 : 1;
-      if (!bad) atomicAdd(&cnt, 1u);
-    }
-    if (bad) continue;
-    for (int c = 4 * sub; c < a.stride; c += 32) {  // (the row is in the cache)
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      atomicMax(&cmax[c], __float_as_uint(v.x) & 0x7fffffffu);
-      atomicMax(&cmax[c + 1], __float_as_uint(v.y) & 0x7fffffffu);
-      atomicMax(&cmax[c + 2], __float_as_uint(v.z) & 0x7fffffffu);
-      atomicMax(&cmax[c + 3], __float_as_uint(v.w) & 0x7fffffffu);
-    }
-  }
-  __syncthreads();
-  for (int j = t; j < a.stride; j += PCA_LANES)
-    if (cmax[j]) atomicMax(&a.colmax[j], cmax[j]);
-  if (t == 0 && cnt) atomicAdd(&a.st->n, cnt);
+  if (threadIdx.x == 0) cnt = 0;
+  eligible_scan_colmax<PCA_LANES>(
+      a.rows, a.chunk_rows, a.stride, a.n_total, a.colmax, [&](int p, int) { return a.mask ? !a.mask[p] : 0; },
+      [&](int p, int bad) {
+        a.elig[p] = bad ? 0 : 1;
+        if (!bad) atomicAdd(&cnt, 1u);
+      });
+  if (threadIdx.x == 0 && cnt) atomicAdd(&a.st->n, cnt);
 }
 
 // MODE 0: S_j += q(x, j); MODE 1: cenmax_j = max |x - mean_j|.  Workgroup x: rows [x * rows_per_group, + rows_per_group); lane t:
@@ -112,7 +60,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_pass_kernel(PcaArgs a, int rows
   float mean[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    sh[j] = 30 - pca_exponent(a.colmax[col + j]);
+    sh[j] = 30 - f32_exponent(a.colmax[col + j]);
     mean[j] = MODE == 1 ? a.mean[col + j] : 0.f;
   }
   const int64_t p_end = min((int64_t)a.n_total, ((int64_t)blockIdx.x + 1) * rows_per_group);
@@ -128,7 +76,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_pass_kernel(PcaArgs a, int rows
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         x[i] = float4{0.f, 0.f, 0.f, 0.f};
-        if (el[i]) x[i] = *reinterpret_cast<const float4*>(pca_row(a.rows, a.chunk_rows, a.stride, p0 + (int64_t)i * R) + col);
+        if (el[i]) x[i] = *reinterpret_cast<const float4*>(tile_row(a.rows, (uint32_t)(p0 + (int64_t)i * R), (uint32_t)a.chunk_rows, a.stride) + col);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -167,7 +115,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_mean_kernel(PcaArgs a) {
     float m = 0.f;
     if (n > 0) {
       const double q = (double)(long long)a.sums[j] / (double)n;  // both conversions and the division round to nearest
-      m = (float)__builtin_ldexp(q, pca_exponent(a.colmax[j]) - 30);
+      m = (float)__builtin_ldexp(q, f32_exponent(a.colmax[j]) - 30);
     }
     a.mean[j] = m;
   }
@@ -178,7 +126,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_scatter_kernel(PcaArgs a, int r
   __shared__ int4 sa[PCA_ROWS * (PCA_BLK / 4)], sb[PCA_ROWS * (PCA_BLK / 4)];
   const uint32_t n = a.st->n;
   if (n < 2) return;  // (uniform)
-  const int bits = pca_bits(n);
+  const int bits = sum_bits(n);
   const int t = threadIdx.x, ti = t & 15, tj = t >> 4;
   const int stride = a.stride, nb = (stride + PCA_BLK - 1) / PCA_BLK;
   int I = 0, rem = blockIdx.y;
@@ -193,9 +141,9 @@ __global__ __launch_bounds__(PCA_LANES) void pca_scatter_kernel(PcaArgs a, int r
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     meanA[j] = inA ? a.mean[colA + j] : 0.f;
-    shA[j] = bits - (inA ? pca_exponent(a.cenmax[colA + j]) : 0);
+    shA[j] = bits - (inA ? f32_exponent(a.cenmax[colA + j]) : 0);
     meanB[j] = inB ? a.mean[colB + j] : 0.f;
-    shB[j] = bits - (inB ? pca_exponent(a.cenmax[colB + j]) : 0);
+    shB[j] = bits - (inB ? f32_exponent(a.cenmax[colB + j]) : 0);
   }
   const int64_t p_begin = (int64_t)blockIdx.x * rows_per_group;
   const int64_t p_end = min((int64_t)a.n_total, p_begin + rows_per_group);
@@ -209,7 +157,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_scatter_kernel(PcaArgs a, int r
       el[i] = p < p_end ? a.elig[p] : 0;
       gA[i] = gB[i] = float4{0.f, 0.f, 0.f, 0.f};
       if (el[i]) {
-        const float* row = pca_row(a.rows, a.chunk_rows, stride, p);
+        const float* row = tile_row(a.rows, (uint32_t)p, (uint32_t)a.chunk_rows, stride);
         if (inA) gA[i] = *reinterpret_cast<const float4*>(row + colA);
         if (inB) gB[i] = *reinterpret_cast<const float4*>(row + colB);
       }
@@ -278,8 +226,8 @@ __global__ __launch_bounds__(PCA_LANES) void pca_finalise_kernel(PcaArgs a) {
   const int64_t e = (int64_t)blockIdx.x * PCA_LANES + threadIdx.x;
   const int i = (int)(e / a.dim), j = (int)(e % a.dim);
   if (i >= a.dim || i > j) return;
-  const int bits = pca_bits(n);
-  const int fi = pca_exponent(a.cenmax[i]), fj = pca_exponent(a.cenmax[j]);
+  const int bits = sum_bits(n);
+  const int fi = f32_exponent(a.cenmax[i]), fj = f32_exponent(a.cenmax[j]);
   const double T = (double)(long long)a.T[(size_t)i * a.stride + j];
   const double Ri = (double)(long long)a.R[i], Rj = (double)(long long)a.R[j];
   const double prod = Ri * Rj;
@@ -310,7 +258,7 @@ __global__ __launch_bounds__(PCA_LANES) void pca_project_kernel(PcaProjArgs a, i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int item = (t >> 3) + 32 * i;
-      rp[i] = item < nrow ? pca_row(a.rows, a.chunk_rows, stride, (int64_t)a.first + r0 + item) : nullptr;
+      rp[i] = item < nrow ? tile_row(a.rows, (uint32_t)((int64_t)a.first + r0 + item), (uint32_t)a.chunk_rows, stride) : nullptr;
     }
     // one step's slab in registers: 128 rows x 8 and 64 components x 8 float4 (four columns of one item each); items / columns beyond the
     // end are zero.  The rows are centred here: x - mean in fp32, rounded once.  Step s + 1 is fetched while step s is computed

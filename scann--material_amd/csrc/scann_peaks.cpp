@@ -77,8 +77,6 @@ __attribute__((target("avx2,fma"))) void density_fma(const Twin& c, int64_t firs
 void parent_plain(const Twin& c, int64_t first, int64_t step) { twin_groups<1>(c, first, step); }
 __attribute__((target("avx2,fma"))) void parent_fma(const Twin& c, int64_t first, int64_t step) { twin_groups<1>(c, first, step); }
 
-bool bad_gamma(float gamma) { return !std::isfinite(gamma) || !(gamma > 0.f); }
-
 // Enqueued on s: the sums of nq queries -- dq, device rows of the pool's stride, or null: the pool's own rows -- against the pool, left in
 // d_sums [nq]; tab: the device copy of the pool's chunk table
 hipError_t enqueue_density(const scann_index* pool, const float* const* tab, const float* dq, const int32_t* dskip, int64_t nq, float gamma,

@@ -14,8 +14,6 @@ using namespace scann;
 
 namespace {
 
-bool proto_bad_gamma(float gamma) { return !std::isfinite(gamma) || !(gamma > 0.f); }
-
 // fn(lo, hi) over the rows [0, n) cut into one range per thread; every row's result is its own
 template <class F>
 void over_rows(int64_t n, int64_t dim, const F& fn) {
@@ -71,7 +69,7 @@ extern "C" {
 
 int64_t scann_prototypes_host(const float* rows, int64_t n, int64_t dim, int64_t m, float gamma, int32_t* pos, int64_t* score, int64_t* b_at_pick,
                               int64_t* A, int64_t* B) {
-  if (n < 0 || n > (int64_t)0x7fffffff - 1024 || dim < 1 || m < 1 || proto_bad_gamma(gamma) || !pos || (n > 0 && !rows)) return SCANN_ERR_INVALID;
+  if (n < 0 || n > (int64_t)0x7fffffff - 1024 || dim < 1 || m < 1 || bad_gamma(gamma) || !pos || (n > 0 && !rows)) return SCANN_ERR_INVALID;
   if ((__int128)n * m > PT_RANGE) return SCANN_ERR_INVALID;
   proto_tail(0, m, pos, nullptr, nullptr, score, b_at_pick);
   if (n == 0) return 0;
@@ -107,7 +105,7 @@ int64_t scann_prototypes_host(const float* rows, int64_t n, int64_t dim, int64_t
 
 int64_t scann_criticisms_host(const float* rows, int64_t n, int64_t dim, const int64_t* weight, const int32_t* exclude, int64_t n_exclude, int64_t c,
                               float gamma, int32_t* pos, int64_t* score) {
-  if (n < 0 || n > (int64_t)0x7fffffff - 1024 || dim < 1 || c < 1 || proto_bad_gamma(gamma) || !pos || (n > 0 && (!rows || !weight)) || n_exclude < 0 ||
+  if (n < 0 || n > (int64_t)0x7fffffff - 1024 || dim < 1 || c < 1 || bad_gamma(gamma) || !pos || (n > 0 && (!rows || !weight)) || n_exclude < 0 ||
       (n_exclude > 0 && !exclude))
     return SCANN_ERR_INVALID;
   if (bad_weight(weight, n) >= 0) return SCANN_ERR_INVALID;
@@ -144,7 +142,7 @@ int64_t scann_index_prototypes(scann_handle_t* h, scann_index_t* pool, int64_t m
   const std::string w = "scann_index_prototypes: ";
   if (const int r = check_pool(h, pool, "scann_index_prototypes")) return r;
   if (m < 1) return fail(h, SCANN_ERR_INVALID, w + "m " + std::to_string(m) + " is not >= 1");
-  if (proto_bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
+  if (bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
   if (!pos) return fail(h, SCANN_ERR_INVALID, w + "pos is null");
   const int64_t N = pool->n;
   if (const int r = check_pool_rows(h, pool, "scann_index_prototypes", (int64_t)0x7fffffff - 1024)) return r;
@@ -209,7 +207,7 @@ int64_t scann_index_criticisms(scann_handle_t* h, scann_index_t* pool, const int
   const std::string w = "scann_index_criticisms: ";
   if (const int r = check_pool(h, pool, "scann_index_criticisms")) return r;
   if (c < 1) return fail(h, SCANN_ERR_INVALID, w + "c " + std::to_string(c) + " is not >= 1");
-  if (proto_bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
+  if (bad_gamma(gamma)) return fail(h, SCANN_ERR_INVALID, w + "gamma must be finite and > 0");
   if (!pos) return fail(h, SCANN_ERR_INVALID, w + "pos is null");
   const int64_t N = pool->n;
   if (const int r = check_pool_rows(h, pool, "scann_index_criticisms", (int64_t)0x7fffffff - 1024)) return r;

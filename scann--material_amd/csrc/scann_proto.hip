@@ -45,8 +45,6 @@ __device__ __forceinline__ void pt_wave_first(long long& v, int32_t& p) {
   }
 }
 
-__device__ __forceinline__ bool pt_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 // one lane per row: the self-join left S_i (the sum over j != i, -1 for an ineligible row) in A
 __global__ __launch_bounds__(PT_LANES) void proto_prepare_kernel(ProtoArgs a) {
   const int p = blockIdx.x * PT_LANES + threadIdx.x;
@@ -61,25 +59,9 @@ __global__ __launch_bounds__(PT_LANES) void proto_prepare_kernel(ProtoArgs a) {
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(reinterpret_cast<unsigned long long*>(&a.st->n), c);
 }
 
-// 8 lanes per row, 32 rows per workgroup and pass
+// the eligibility scan (scann_prim.h)
 __global__ __launch_bounds__(PT_LANES) void crit_prepare_kernel(ProtoArgs a) {
-  const int t = threadIdx.x, sub = t & 7;
-  const int n_pass = (a.n_total + 31) / 32;
-  for (int g = blockIdx.x; g < n_pass; g += gridDim.x) {
-    const int p = g * 32 + (t >> 3);
-    int bad = 0;
-    if (p < a.n_total) {
-      const float* row = a.rows[p / a.chunk_rows] + (size_t)(p % a.chunk_rows) * a.stride;
-      for (int c = 4 * sub; c < a.stride; c += 32) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        bad |= !(pt_finite(v.x) && pt_finite(v.y) && pt_finite(v.z) && pt_finite(v.w));
-      }
-    }
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    bad |= __shfl_xor(bad, 4);
-    if (sub == 0 && p < a.n_total) a.live[p] = !bad && a.A[p] > 0 ? PT_LIVE : PT_OUT;
-  }
+  eligible_scan(a.rows, a.chunk_rows, a.stride, a.n_total, NoExtra{}, [&](int p, int bad) { a.live[p] = !bad && a.A[p] > 0 ? PT_LIVE : PT_OUT; });
 }
 
 __global__ __launch_bounds__(PT_LANES) void crit_exclude_kernel(ProtoArgs a, const int32_t* ex, int32_t n_ex) {
@@ -107,7 +89,7 @@ __global__ __launch_bounds__(PT_LANES) void proto_step_kernel(ProtoArgs a) {
   const int G = gridDim.x;
   const int n_my = (a.n_tile - (int)blockIdx.x + G - 1) / G;  // tiles blockIdx.x, blockIdx.x + G, ...
   if (cur >= 0) {
-    const float* c = a.rows[cur / a.chunk_rows] + (size_t)(cur % a.chunk_rows) * stride;
+    const float* c = tile_row(a.rows, cur, a.chunk_rows, stride);
     for (int j = t; j < n_slab * PT_SLAB; j += PT_LANES) centre[j] = j < stride ? c[j] : 0.f;
   }
   // tile k of this workgroup: its chunk, its first row there and how many rows it holds (<= 0: a tile behind the chunk's last row)

@@ -23,7 +23,7 @@ std::string check_landmarks(const float* landmarks, int32_t m, int64_t dim, floa
   for (int64_t i = 0; i < (int64_t)m * dim; ++i)
     if (!std::isfinite(landmarks[i]))
       return "landmarks hold a non-finite value (landmark " + std::to_string(i / dim) + ", column " + std::to_string(i % dim) + ")";
-  if (!std::isfinite(gamma) || !(gamma > 0.f)) return "gamma must be finite and > 0";
+  if (bad_gamma(gamma)) return "gamma must be finite and > 0";
   return "";
 }
 
@@ -44,8 +44,7 @@ int scann_rbf_features_host(const float* rows, int64_t n, int64_t dim, const flo
   scann_knn_distsq_matrix(rows, n, landmarks, m, dim, phi);  // the pool row is the chain's first argument
   const float nan = std::nanf("");
   for (int64_t p = 0; p < n; ++p) {
-    bool ok = true;
-    for (int64_t j = 0; j < dim; ++j) ok = ok && std::isfinite(rows[p * dim + j]);
+    const bool ok = finite_row(rows + p * dim, dim);
     for (int32_t c = 0; c < m; ++c) phi[p * m + c] = ok ? rbf_weight(phi[p * m + c], gamma) : nan;
   }
   return SCANN_OK;

@@ -30,10 +30,8 @@ int64_t scann_kcenter_host(const float* rows, int64_t n, const float* ref, int64
   select_tail(0, m, pos, nullptr, nullptr, radius2);
   if (n == 0) return 0;
   std::vector<float> mind((size_t)n, __builtin_inff()), tmp((size_t)std::max(n, nr));
-  std::vector<char> live((size_t)n, 1);
-  for (int64_t p = 0; p < n; ++p)
-    for (int64_t j = 0; j < dim; ++j)
-      if (!std::isfinite(rows[p * dim + j])) live[(size_t)p] = 0;
+  std::vector<char> live((size_t)n);
+  for (int64_t p = 0; p < n; ++p) live[(size_t)p] = finite_row(rows + p * dim, dim);
   for (int64_t p = 0; p < n && nr > 0; ++p) {
     if (!live[(size_t)p]) continue;
     dist2_to_rows(rows + p * dim, ref, nr, dim, tmp.data());

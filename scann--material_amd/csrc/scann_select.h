@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scann_prim.h"
+
 namespace scann {
 
 constexpr int KC_LANES = 256;        // lanes of a workgroup = pool rows of a tile: one lane owns one row's chain

@@ -50,30 +50,12 @@ __device__ __forceinline__ unsigned long long kc_wave_first(unsigned long long k
   return key;
 }
 
-__device__ __forceinline__ bool kc_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// 8 lanes per row, 32 rows per workgroup and pass
+// the eligibility scan (scann_prim.h)
 __global__ __launch_bounds__(KC_LANES) void kcenter_prepare_kernel(KcArgs a, int has_init) {
-  const int t = threadIdx.x, sub = t & 7;
-  const int n_pass = (a.n_total + 31) / 32;
-  for (int g = blockIdx.x; g < n_pass; g += gridDim.x) {
-    const int p = g * 32 + (t >> 3);
-    int bad = 0;
-    if (p < a.n_total) {
-      const float* row = a.rows[p / a.chunk_rows] + (size_t)(p % a.chunk_rows) * a.stride;
-      for (int c = 4 * sub; c < a.stride; c += 32) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        bad |= !(kc_finite(v.x) && kc_finite(v.y) && kc_finite(v.z) && kc_finite(v.w));
-      }
-    }
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    bad |= __shfl_xor(bad, 4);
-    if (sub == 0 && p < a.n_total) {
-      a.live[p] = bad ? 0 : 1;
-      if (!has_init) a.mind[p] = __builtin_inff();
-    }
-  }
+  eligible_scan(a.rows, a.chunk_rows, a.stride, a.n_total, NoExtra{}, [&](int p, int bad) {
+    a.live[p] = bad ? 0 : 1;
+    if (!has_init) a.mind[p] = __builtin_inff();
+  });
 }
 
 __global__ __launch_bounds__(KC_LANES) void kcenter_step_kernel(KcArgs a) {
@@ -90,7 +72,7 @@ __global__ __launch_bounds__(KC_LANES) void kcenter_step_kernel(KcArgs a) {
   const int G = gridDim.x;
   const int n_my = (a.n_tile - (int)blockIdx.x + G - 1) / G;  // tiles blockIdx.x, blockIdx.x + G, ...
   if (cur >= 0) {
-    const float* c = a.rows[cur / a.chunk_rows] + (size_t)(cur % a.chunk_rows) * stride;
+    const float* c = tile_row(a.rows, cur, a.chunk_rows, stride);
     for (int j = t; j < n_slab * KC_SLAB; j += KC_LANES) centre[j] = j < stride ? c[j] : 0.f;
   }
   // tile k of this workgroup: its chunk, its first row there and how many rows it holds (<= 0: a tile behind the chunk's last row)

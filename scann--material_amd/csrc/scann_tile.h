@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scann_prim.h"
+
 namespace scann {
 
 constexpr int TILE_LANES = 256;  // lanes of a workgroup
@@ -109,13 +111,6 @@ __device__ __forceinline__ void tile_write(float* tile, const f2 (&acc)[8][2], i
 __device__ __forceinline__ void tile_sums_write(unsigned long long* red, const unsigned long long (&s64)[8], int qg, int rg) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) red[rg * TILE_TQ + tile_query(qg, j)] = s64[j];
-}
-
-// where position pos lies in a table stored in chunks of chunk_rows rows, `stride` elements to a row
-template <class T>
-__device__ __forceinline__ const T* tile_row(const T* const* rows, int pos, int chunk_rows, int stride) {
-  const int c = pos / chunk_rows;
-  return rows[c] + (size_t)(pos - c * chunk_rows) * stride;
 }
 
 // 0 where all four are finite, NaN otherwise (x - x is 0 for a finite x only)

@@ -15,15 +15,6 @@
 
 namespace scann {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float swish_(float x) { return x * sigmoidf_(x); }
-// d/dx [x * sigmoid(x)] = s * (1 + x * (1 - s))
-__device__ __forceinline__ float dswish_(float x) {
-  const float s = sigmoidf_(x);
-  return s * (1.0f + x * (1.0f - s));
-}
-__device__ __forceinline__ int acc_row_(int i, int lane) { return (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5); }
-
 // ---- linear: Y = act(X . W + b) on 64-row tiles (same MFMA fragment scheme as the forward kernels) -----------------
 // flags: bit0 accumulate into Y, bit1 swish, bit2 multiply by swish'(P) (P is then an INPUT: the fused swish backward).
 // Otherwise P (optional) receives the pre-activation X.W + b.
@@ -110,11 +101,11 @@ __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ X
         float4 v = make_float4(acc[rt][4 * j] + bv[j].x, acc[rt][4 * j + 1] + bv[j].y, acc[rt][4 * j + 2] + bv[j].z, acc[rt][4 * j + 3] + bv[j].w);
         if (flags & 4) {  // P is an input here: the pre-activation whose swish this product is the gradient of
           const float4 pr = preact[rt][j];
-          v = make_float4(v.x * dswish_(pr.x), v.y * dswish_(pr.y), v.z * dswish_(pr.z), v.w * dswish_(pr.w));
+          v = make_float4(v.x * dswish_exact(pr.x), v.y * dswish_exact(pr.y), v.z * dswish_exact(pr.z), v.w * dswish_exact(pr.w));
         } else if (P) {
           *reinterpret_cast<float4*>(P + o) = v;
         }
-        if (flags & 2) v = make_float4(swish_(v.x), swish_(v.y), swish_(v.z), swish_(v.w));
+        if (flags & 2) v = make_float4(swish_exact(v.x), swish_exact(v.y), swish_exact(v.z), swish_exact(v.w));
         if (flags & 1) v = make_float4(v.x + yold[rt][j].x, v.y + yold[rt][j].y, v.z + yold[rt][j].z, v.w + yold[rt][j].w);
         *reinterpret_cast<float4*>(Y + o) = v;
       }
@@ -188,7 +179,7 @@ __global__ __launch_bounds__(256) void linear_sum_kernel(LinearSumArgs a, float*
       float4 v = make_float4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
       if (P) {  // fused swish backward: the sum is d loss / d swish(P)
         const float4 pr = *reinterpret_cast<const float4*>(P + o);
-        v = make_float4(v.x * dswish_(pr.x), v.y * dswish_(pr.y), v.z * dswish_(pr.z), v.w * dswish_(pr.w));
+        v = make_float4(v.x * dswish_exact(pr.x), v.y * dswish_exact(pr.y), v.z * dswish_exact(pr.z), v.w * dswish_exact(pr.w));
       }
       *reinterpret_cast<float4*>(Y + o) = make_float4(v.x + yold[j].x, v.y + yold[j].y, v.z + yold[j].z, v.w + yold[j].w);
     }
@@ -362,7 +353,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradSet set) {
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) part[(size_t)(32 * m + acc_row_(i, lane)) * D + col] = acc[m][i] * inv;
+    for (int i = 0; i < 16; ++i) part[(size_t)(32 * m + acc_row(i, lane)) * D + col] = acc[m][i] * inv;
   bsum = xor32(bsum);
   if (bpart && kh == 0) bpart[(size_t)blockIdx.x * D + col] = bsum;
 }
@@ -561,7 +552,7 @@ void wgrad_launch(WgradCtx& ctx, hipStream_t s) {
 __global__ void swish_bwd_kernel(const float* __restrict__ pre, const float* __restrict__ dout,
                                  float* __restrict__ dpre, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dpre[i] = dout[i] * dswish_(pre[i]);
+  if (i < n) dpre[i] = dout[i] * dswish_exact(pre[i]);
 }
 void launch_swish_bwd(const float* pre, const float* dout, float* dpre, size_t n, hipStream_t s) {
   if (n) hipLaunchKernelGGL(swish_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pre, dout, dpre, n);
@@ -675,7 +666,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
         if (f.V) {
           const float4 vv = reinterpret_cast<const float4*>(f.V)[(size_t)r * 32 + sub + 8 * i];
           reinterpret_cast<float4*>(f.dV)[(size_t)r * 32 + sub + 8 * i] =
-              make_float4(dxv.x * dswish_(vv.x), dxv.y * dswish_(vv.y), dxv.z * dswish_(vv.z), dxv.w * dswish_(vv.w));
+              make_float4(dxv.x * dswish_exact(vv.x), dxv.y * dswish_exact(vv.y), dxv.z * dswish_exact(vv.z), dxv.w * dswish_exact(vv.w));
         }
         dg[i].x += dv[i].x * xv[i].x; dg[i].y += dv[i].y * xv[i].y; dg[i].z += dv[i].z * xv[i].z; dg[i].w += dv[i].w * xv[i].w;
         dbt[i].x += dv[i].x; dbt[i].y += dv[i].y; dbt[i].z += dv[i].z; dbt[i].w += dv[i].w;
@@ -908,21 +899,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
 // Fast path when no atom of the batch has more than 16 neighbours (QM9: <= 12): the atom's key rows, logits and
 // attention gradients live in registers, so K is read once and the 8-lane dot-product reductions run once per edge.
 // Lane reductions of the attention backward through DPP (no LDS round trips): the wave-per-atom kernels are chains of such
-// sums, so their latency is the kernel time.  red8: sum over each aligned group of 8 lanes (one head), in every lane of it.
-#define SCANN_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), 0xF, 0xF, true))
-__device__ __forceinline__ float red8(float v) {
-  v += SCANN_DPP(v, 0xB1);   // quad_perm [1,0,3,2]: lane ^ 1
-  v += SCANN_DPP(v, 0x4E);   // quad_perm [2,3,0,1]: lane ^ 2
-  v += SCANN_DPP(v, 0x141);  // row_half_mirror: the other quad of the group of 8
-  return v;
-}
-__device__ __forceinline__ float red64(float v) {
-  v = red8(v);
-  v += SCANN_DPP(v, 0x128);  // row_ror:8 -- the other half of the row of 16
-  v = xor16(v);  // (lane swaps: no LDS round trip, same additions)
-  v = xor32(v);
-  return v;
-}
+// sums, so their latency is the kernel time.  sum8 (scann_mma.h): the sum over each aligned group of 8 lanes (one head), in every lane
+// of it; red64: over the wave.
 
 __global__ __launch_bounds__(256) void attn_bwd16_kernel(const float* __restrict__ q, const float* __restrict__ K,
                                                          const int* __restrict__ edge_offset,
@@ -955,7 +933,7 @@ __global__ __launch_bounds__(256) void attn_bwd16_kernel(const float* __restrict
     for (int n = 0; n < 16; ++n) {
       if (n >= deg) k2[n] = make_float2(0.f, 0.f);
       float e = qx * k2[n].x + qy * k2[n].y;
-      e = red8(e);
+      e = sum8(e);
       ev[n] = n < deg ? e : -INFINITY;
       m = fmaxf(m, ev[n]);
     }
@@ -990,7 +968,7 @@ __global__ __launch_bounds__(256) void attn_bwd16_kernel(const float* __restrict
 #pragma unroll
     for (int n = 0; n < 16; ++n) {
       float d = dpx * k2[n].x + dpy * k2[n].y;
-      d = red8(d);
+      d = sum8(d);
       da[n] = d * keep[n];
       dot += ev[n] * da[n];
     }
@@ -1083,9 +1061,9 @@ __device__ __forceinline__ void readout_bwd_body(const ReadoutBwdArgs& a) {
 #pragma unroll
     for (int u = 0; u < 16; ++u) pre += sRep[k0 + u] * w[u];
   }
-  const float hj = swish_(pre);
+  const float hj = swish_exact(pre);
   const float dh = dy * a.wo[tid];
-  const float dpre = dh * dswish_(pre);
+  const float dpre = dh * dswish_exact(pre);
   a.dwo[(size_t)mol * D + tid] = dy * hj;  // this structure's slot (vec_reduce_kernel adds the slots in order)
   if (!DET && tid == 0) atomicAdd(a.dbo, dy);
   a.rep_out[(size_t)mol * D + tid] = rep;
@@ -1183,10 +1161,6 @@ void launch_readout_bwd(const ReadoutBwdArgs& a, hipStream_t s, bool det) {
 }
 
 // ---- basis backward: geom0 = swish(gd.Wd + bd) * swish(gw.Ww + bw)  (scann_model.py:378-389) ---------------------------
-__device__ __forceinline__ float gauss_(float x, float c) {
-  const float d = x - c;
-  return expf(-(d * d) / 0.25f);
-}
 // DET: the workgroup's sums go to slot blockIdx.x of each of the 2 NG + 2 gradient rows (row r's slots at part + r * gridDim.x * 128)
 template <bool DET>
 __device__ __forceinline__ void basis_bwd_body(const BasisParams& p, const float* __restrict__ dist, const float* __restrict__ weight,
@@ -1214,7 +1188,7 @@ __device__ __forceinline__ void basis_bwd_body(const BasisParams& p, const float
   for (int i = tid; i < 32 * 2 * NG; i += 128) {
     const int e = i / (2 * NG), k = i % (2 * NG);
     float v = 0.f;
-    if (e < ne) v = k < NG ? gauss_(dist[e0 + e], p.cd[k]) : gauss_(weight[e0 + e], p.cw[k - NG]);
+    if (e < ne) v = k < NG ? gauss(dist[e0 + e], p.cd[k]) : gauss(weight[e0 + e], p.cw[k - NG]);
     sG[e][k] = v;
   }
   __syncthreads();
@@ -1227,7 +1201,7 @@ __device__ __forceinline__ void basis_bwd_body(const BasisParams& p, const float
     }
     ad += bd; aw += bw;
     const float dg = dgeom[(size_t)(e0 + e) * D + tid];
-    const float dpd = dg * swish_(aw) * dswish_(ad), dpw = dg * swish_(ad) * dswish_(aw);
+    const float dpd = dg * swish_exact(aw) * dswish_exact(ad), dpw = dg * swish_exact(ad) * dswish_exact(aw);
     gbd += dpd; gbw += dpw;
 #pragma unroll
     for (int k = 0; k < NG; ++k) {
@@ -1316,7 +1290,7 @@ __device__ __forceinline__ void base_geom_bwd_body(const float* __restrict__ gd,
     float pre = b;
 #pragma unroll
     for (int k = 0; k < NG; ++k) pre += sG[e][k] * w[k];
-    const float dp = dgeomL[(size_t)(e0 + e) * D + tid] * wgt[e0 + e] * dswish_(pre);
+    const float dp = dgeomL[(size_t)(e0 + e) * D + tid] * wgt[e0 + e] * dswish_exact(pre);
     gb += dp;
 #pragma unroll
     for (int k = 0; k < NG; ++k) gw[k] += sG[e][k] * dp;
@@ -1445,7 +1419,7 @@ __device__ __forceinline__ void embed_bwd_body(const float* __restrict__ emb, co
     for (int u = 0; u < 16; ++u)
       if (k0 + u < emb_dim) pre += e[u] * w[u];
   }
-  const float dpre = dl * dswish_(pre);
+  const float dpre = dl * dswish_exact(pre);
   sdp[col] = dpre;
   if (DET) {
     *pB = dpre;
@@ -1542,7 +1516,7 @@ __global__ __launch_bounds__(128) void embed_general_bwd_kernel(EmbedArgs a, con
   for (int la = 0; la < na; ++la) {  // thread = output column
     float pre = a.bde[tid];
     for (int k = 0; k < cin; ++k) pre += sV[la][k] * a.Wde[k * D + tid];
-    const float dp = dc0[(size_t)(a0 + la) * D + tid] * dswish_(pre);
+    const float dp = dc0[(size_t)(a0 + la) * D + tid] * dswish_exact(pre);
     sDp[la][tid] = dp;
     gb += dp;
   }
@@ -1632,7 +1606,7 @@ __global__ __launch_bounds__(128) void embed_general_bwd_det_kernel(EmbedArgs a,
     for (int la = 0; la < na; ++la) {  // thread = output column
       float pre = a.bde[tid];
       for (int k = 0; k < cin; ++k) pre += sV[la][k] * a.Wde[k * D + tid];
-      const float dp = dc0[(size_t)(a0 + la) * D + tid] * dswish_(pre);
+      const float dp = dc0[(size_t)(a0 + la) * D + tid] * dswish_exact(pre);
       sDp[la][tid] = dp;
       gb += dp;
     }

@@ -21,15 +21,6 @@ namespace scann {
 
 namespace {
 
-__device__ __forceinline__ float sigm_(float x) { return 1.0f / (1.0f + expf(-x)); }
-// d/dx [x * sigmoid(x)] = s * (1 + x * (1 - s))
-__device__ __forceinline__ float dsw_(float x) {
-  const float s = sigm_(x);
-  return s * (1.0f + x * (1.0f - s));
-}
-
-__device__ __forceinline__ float f4sum_(float4 a) { return (a.x + a.y) + (a.z + a.w); }
-
 constexpr float WINV = 1.0f / WSCALE;
 constexpr int STAGE_STRIDE = D + 4;  // floats per row of the gamma / beta staging (aliases the plane buffer)
 
@@ -78,7 +69,7 @@ __device__ __forceinline__ void put_stats(float* __restrict__ sRed, const float4
   for (int rt = 0; rt < RT; ++rt) {
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s += f4sum_(x[rt][j]);
+    for (int j = 0; j < 4; ++j) s += f4sum(x[rt][j]);
     const float mean32 = xor32(s) * (1.0f / 32.0f);
     float v2 = 0.f;
 #pragma unroll
@@ -125,7 +116,7 @@ __device__ __forceinline__ void ln_bwd_head(float4 (&x)[RT][4], float4 (&dy)[RT]
         dbt[j] = make_float4(dbt[j].x + d.x, dbt[j].y + d.y, dbt[j].z + d.z, dbt[j].w + d.w);
       }
       const float4 ax = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
-      p1 += f4sum_(ax);
+      p1 += f4sum(ax);
       p2 += (ax.x * xh.x + ax.y * xh.y) + (ax.z * xh.z + ax.w * xh.w);
       x[rt][j] = xh;
       dy[rt][j] = ax;
@@ -290,8 +281,8 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void rn_bwd_kernel(RnBwdArgs 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float4 p = dy[rt][j];
-      dy[rt][j] = make_float4(acc[rt][4 * j] * post[rt] * dsw_(p.x), acc[rt][4 * j + 1] * post[rt] * dsw_(p.y),
-                              acc[rt][4 * j + 2] * post[rt] * dsw_(p.z), acc[rt][4 * j + 3] * post[rt] * dsw_(p.w));  // dpre1
+      dy[rt][j] = make_float4(acc[rt][4 * j] * post[rt] * dswish_exact(p.x), acc[rt][4 * j + 1] * post[rt] * dswish_exact(p.y),
+                              acc[rt][4 * j + 2] * post[rt] * dswish_exact(p.z), acc[rt][4 * j + 3] * post[rt] * dswish_exact(p.w));  // dpre1
     }
   put_rowmax<RT>(sMax[2], dy, lrow, lh, wave);
   __syncthreads();  // every wave is done reading the dY planes
@@ -323,21 +314,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void rn_bwd_kernel(RnBwdArgs 
 // ATT (32-row tiles of the forward's plan: whole atoms, every degree <= 16): the tile's dK rows do not come from memory -- the waves
 // first run attn_bwd16_kernel's arithmetic on the tile's atoms (softmax / LayerNorm backward per atom, one atom per wave at a time),
 // leaving dq and dK in memory for the weight gradients and dK in a staging buffer for the chain below.  One launch less per layer.
-#define SCANN_DPP_(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), 0xF, 0xF, true))
-__device__ __forceinline__ float red8_(float v) {
-  v += SCANN_DPP_(v, 0xB1);   // lane ^ 1
-  v += SCANN_DPP_(v, 0x4E);   // lane ^ 2
-  v += SCANN_DPP_(v, 0x141);  // the other quad of the group of 8
-  return v;
-}
-__device__ __forceinline__ float red64_(float v) {
-  v = red8_(v);
-  v += SCANN_DPP_(v, 0x128);
-  v = xor16(v);  // (v_permlane16_swap / v_permlane32_swap: no LDS round trip, same additions)
-  v = xor32(v);
-  return v;
-}
-
+// (its lane reductions: sum8 and red64 of scann_mma.h)
 template <int RT, bool ATT = false>
 __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void edge_bwd_kernel(EdgeBwdArgs a, AttnPart b) {
   static_assert(!ATT || RT == 1, "the fused attention backward runs on the 32-row tile plan");
@@ -377,7 +354,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void edge_bwd_kernel(EdgeBwdA
       for (int n = 0; n < 16; ++n) {
         if (n >= deg) k2[n] = make_float2(0.f, 0.f);
         float e = qx * k2[n].x + qy * k2[n].y;
-        e = red8_(e);
+        e = sum8(e);
         ev[n] = n < deg ? e : -INFINITY;
         m = fmaxf(m, ev[n]);
       }
@@ -397,14 +374,14 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void edge_bwd_kernel(EdgeBwdA
         px += ev[n] * keep[n] * k2[n].x;
         py += ev[n] * keep[n] * k2[n].y;
       }
-      const float sm = red64_(px + py);
+      const float sm = red64(px + py);
       const float mean = sm * (1.0f / D);
       const float cx = px - mean, cy = py - mean;
-      const float v = red64_(cx * cx + cy * cy);
+      const float v = red64(cx * cx + cy * cy);
       const float rstd = 1.0f / sqrtf(v * (1.0f / D) + 1e-6f);
       const float hx = cx * rstd, hy = cy * rstd;
       const float ax = dyv.x * g.x, ay = dyv.y * g.y;
-      const float m1 = red64_(ax + ay) * (1.0f / D), m2 = red64_(ax * hx + ay * hy) * (1.0f / D);
+      const float m1 = red64(ax + ay) * (1.0f / D), m2 = red64(ax * hx + ay * hy) * (1.0f / D);
       const float dpx = rstd * (ax - m1 - hx * m2), dpy = rstd * (ay - m1 - hy * m2);
       dg.x += dyv.x * hx; dg.y += dyv.y * hy; dbt.x += dyv.x; dbt.y += dyv.y;
       float da[16];
@@ -412,7 +389,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void edge_bwd_kernel(EdgeBwdA
 #pragma unroll
       for (int n = 0; n < 16; ++n) {
         float d = dpx * k2[n].x + dpy * k2[n].y;
-        d = red8_(d);
+        d = sum8(d);
         da[n] = d * keep[n];
         dot += ev[n] * da[n];
       }
@@ -504,7 +481,7 @@ __global__ __launch_bounds__(256, RT == 2 ? 2 : 3) void edge_bwd_kernel(EdgeBwdA
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float4 v = ld4(a.V, off[rt] + 32 * j), t = x[rt][j];
-      dy[rt][j] = make_float4(t.x * dsw_(v.x), t.y * dsw_(v.y), t.z * dsw_(v.z), t.w * dsw_(v.w));  // dV
+      dy[rt][j] = make_float4(t.x * dswish_exact(v.x), t.y * dswish_exact(v.y), t.z * dswish_exact(v.z), t.w * dswish_exact(v.w));  // dV
     }
   put_rowmax<RT>(sMax[1], dy, lrow, lh, wave);
   __syncthreads();  // row maxima visible; every thread is done with the staging buffer

@@ -9,13 +9,9 @@
 #include <thread>
 #include <vector>
 
-namespace scann {
+#include "scann_prim.h"
 
-inline bool finite_row(const float* x, int64_t d) {
-  for (int64_t j = 0; j < d; ++j)
-    if (!std::isfinite(x[j])) return false;
-  return true;
-}
+namespace scann {
 
 typedef float v8 __attribute__((vector_size(32)));
 

@@ -56,6 +56,34 @@ def random_rows(N, dim, seed=None):
     return rows
 
 
+SUBNORMAL = np.float32(2.0 ** -149)  # the smallest fp32 above zero
+
+
+def subnormal_column(rng, n):
+    """n values k * 2^-149, 1 <= k < 400: frexp's exponent of the largest takes the subnormal branch, and no mean of them is zero"""
+    return rng.integers(1, 400, n).astype(np.float32) * SUBNORMAL
+
+
+def scan_edge_rows():
+    """The smallest indexes that reach every edge of the eligibility scan the prepare kernels share (csrc/scann_prim.h: 8 lanes per row, 32
+    rows per pass, 32 columns per trip of a lane): 1, 31, 32 and 33 rows -- the pass boundary from both sides --; widths 1 and 5 -- strides 4
+    and 8, lanes without a column -- and 32 and 36 -- the last lane's columns, and a second trip.  From 31 rows on, +inf stands in column
+    0 of row 0 and NaN in the last column of the last row; from width 5 on, -inf in the last column of row 1 (a NaN distance never
+    qualifies whatever the scan said, an infinite one does), and column 1 holds subnormals only.  Yields (label, rows)."""
+    for n in (1, 31, 32, 33):
+        for dim in (1, 5, 32, 36):
+            rng = np.random.default_rng(100 * n + dim)
+            rows = (rng.standard_normal((n, dim)) * 3).astype(np.float32)
+            if dim >= 5:
+                rows[:, 1] = subnormal_column(rng, n)
+            if n >= 31:
+                rows[0, 0] = np.inf
+                rows[n - 1, dim - 1] = np.nan
+                if dim >= 5:
+                    rows[1, dim - 1] = -np.inf
+            yield "scan edges, N %d dim %d" % (n, dim), rows
+
+
 def rel_err(got, ref):
     """tests/test_gpu_outputs.py's"""
     ref = np.asarray(ref, dtype=np.float64)

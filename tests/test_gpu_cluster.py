@@ -21,7 +21,7 @@ import pytest
 
 import kmeans_ref
 import scann_oracle as so
-from analysis_checks import _bits, make_index, setup, training_twin, untouched
+from analysis_checks import SUBNORMAL, _bits, make_index, scan_edge_rows, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -130,6 +130,16 @@ def test_planted_cases_on_the_device(engine):
     wide[699, 0] = -np.inf
     got = check_exact(engine, wide, wide[[1, 50, 400]], 5, label="planted, wide")
     assert np.all(got["label"][[13, 300, 699]] == -1) and np.all(np.isposinf(got["dist2"][[13, 300, 699]])) and got["size"].sum() == 697
+
+
+def test_edges_of_the_eligibility_scan(engine):
+    """labels and dist2 say which rows the scan found eligible; the centres of the subnormal column carry frexp's exponent of its maximum"""
+    for label, rows in scan_edge_rows():
+        ok = np.isfinite(rows).all(axis=1)
+        got = check_exact(engine, rows, rows[ok][:2], 3, label=label)
+        assert np.array_equal(got["label"] >= 0, ok) and np.array_equal(np.isposinf(got["dist2"]), ~ok), label
+        if rows.shape[1] >= 5:
+            assert got["centre"][:, 1].all() and (np.abs(got["centre"][:, 1]) < 400 * SUBNORMAL).all(), label
 
 
 def test_invariance_of_how_the_index_was_built(engine):

@@ -25,7 +25,8 @@ if __name__ == "__main__":  # the child process of the exact-fp32 test
 import head_ref  # noqa: E402
 import pca_ref  # noqa: E402
 import scann_oracle as so  # noqa: E402
-from analysis_checks import _bits, make_index, random_rows, setup, training_twin, untouched  # noqa: E402
+from analysis_checks import (SUBNORMAL, _bits, make_index, random_rows, scan_edge_rows, setup, subnormal_column, training_twin,  # noqa: E402
+                             untouched)
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +101,32 @@ def test_fit_moments_of_planted_rows(engine):
     pca_ref.same_moments(got, _hip.moments_host(aug), "planted")
     pca_ref.same_moments(got, pca_ref.moments(aug), "planted, NumPy")
     assert got["n"] == 695 and not got["cov"][131].any() and got["mean"][131] == -7.25
+
+
+def test_fit_moments_at_the_edges_of_the_eligibility_scan(engine):
+    """the rows' edges, and the targets' own: six targets, so that lanes 4 and 5 of a row's eight hold one each; NaN in the last of them, a
+    column of subnormals among them"""
+    from scann import _hip
+
+    for label, rows in scan_edge_rows():
+        N, dim = rows.shape
+        t = targets_for(rows, 6, seed=3)
+        t[:, 2] = subnormal_column(np.random.default_rng(N), N)
+        ix = make_index(engine, rows)
+        try:
+            if N < 2:  # a covariance needs two rows: the twin refuses the index, and the device does once its scan has counted the one
+                with pytest.raises(ValueError, match="at least 2 rows"):
+                    _hip.moments_host(head_ref.augmented(rows, t))
+                with pytest.raises(_hip.ScannHipError, match="has 1 among its 1"):
+                    engine.index_fit_moments(ix, t)
+                continue
+            t[2, 5] = np.nan
+            got = engine.index_fit_moments(ix, t)
+        finally:
+            ix.free()
+        pca_ref.same_moments(got, _hip.moments_host(head_ref.augmented(rows, t)), label)
+        assert got["n"] == np.isfinite(rows).all(axis=1).sum() - 1, label
+        assert 0 < got["mean"][dim + 2] < 400 * SUBNORMAL and got["col_exp"][dim + 2] < -125, label
 
 
 def test_fit_moments_over_two_chunks(engine, two_chunks):

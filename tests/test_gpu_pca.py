@@ -18,7 +18,7 @@ import pytest
 
 import pca_ref
 import scann_oracle as so
-from analysis_checks import _bits, make_index, random_rows, setup, training_twin, untouched
+from analysis_checks import SUBNORMAL, _bits, make_index, random_rows, scan_edge_rows, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -105,6 +105,28 @@ def test_moments_of_planted_rows(engine):
     finally:
         ix.free()
     assert not got["cov"].any() and np.array_equal(_bits(got["mean"]), _bits(same_rows[0]))
+
+
+def test_moments_at_the_edges_of_the_eligibility_scan(engine):
+    """n says which rows the scan found eligible; mean and col_exp of the subnormal column carry frexp's exponent of its maximum"""
+    from scann import _hip
+
+    for label, rows in scan_edge_rows():
+        ix = make_index(engine, rows)
+        try:
+            if len(rows) < 2:  # a covariance needs two rows: the twin refuses the index, and the device does once its scan has counted the one
+                with pytest.raises(ValueError, match="at least 2 rows"):
+                    _hip.moments_host(rows)
+                with pytest.raises(_hip.ScannHipError, match="has 1 among its 1"):
+                    engine.index_moments(ix)
+                continue
+            got = engine.index_moments(ix)
+        finally:
+            ix.free()
+        pca_ref.same_moments(got, _hip.moments_host(rows), label)
+        assert got["n"] == np.isfinite(rows).all(axis=1).sum(), label
+        if rows.shape[1] >= 5:
+            assert 0 < got["mean"][1] < 400 * SUBNORMAL and got["col_exp"][1] < -125, label
 
 
 def test_moments_do_not_depend_on_how_the_index_was_built(engine):

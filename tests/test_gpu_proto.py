@@ -15,7 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 import proto_ref  # noqa: E402
-from analysis_checks import _bits, make_index, random_rows, same_arrays, setup, training_twin, untouched  # noqa: E402
+from analysis_checks import _bits, make_index, random_rows, same_arrays, scan_edge_rows, setup, training_twin, untouched  # noqa: E402
 from test_gpu_peaks import gamma_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +105,25 @@ def test_kernels_equal_the_host_twins(engine, N, dim, crit):
         at = {int(p): s for s, p in enumerate(got["position"][:got["count"]])}
         assert [at[d] for d in dup] == sorted(at[d] for d in dup)
         assert len({int(got["A"][d]) for d in dup}) == 1 and len({int(got["B"][d]) for d in dup}) == 1
+
+
+def test_criticisms_at_the_edges_of_the_eligibility_scan(engine):
+    """every row weighs 1, so that the scan alone decides which rows live; with c beyond N the picks go on until no live row has a score
+    left, and none of them is a row with a non-finite component"""
+    from scann import _hip
+
+    for label, rows in scan_edge_rows():
+        N = len(rows)
+        ok = np.isfinite(rows).all(axis=1)
+        ids, atoms = names_for(N)
+        weight = np.ones(N, np.int64)
+        ix = make_index(engine, rows, ids, atoms)
+        try:
+            got = engine.index_criticisms(ix, weight, None, N + 2, 0.05)
+        finally:
+            ix.free()
+        same_criticisms(got, _hip.criticisms_host(rows, weight, None, N + 2, 0.05), ids, atoms, label)
+        assert got["count"] > 0 and ok[got["position"][:got["count"]]].all(), label
 
 
 def test_duplicates_and_coincident_rows(engine):

@@ -19,7 +19,7 @@ import pytest
 
 import kcenter_ref
 import scann_oracle as so
-from analysis_checks import _bits, make_index, padded, setup, training_twin, untouched
+from analysis_checks import _bits, make_index, padded, scan_edge_rows, setup, training_twin, untouched
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -96,6 +96,14 @@ def test_kernel_exact_on_small_integers(engine):
         got = check_exact(engine, rows, r, 400, label="integers")
         pos, rad, cnt = kcenter_ref.select(rows, r, 400, 0.0, kcenter_ref.exact_dist2)
         assert got["count"] == cnt and np.array_equal(got["position"], pos) and np.array_equal(_bits(got["radius2"]), _bits(rad))
+
+
+def test_edges_of_the_eligibility_scan(engine):
+    """with m beyond N every eligible row is picked, and no other"""
+    for label, rows in scan_edge_rows():
+        ok = np.isfinite(rows).all(axis=1)
+        got = check_exact(engine, rows, None, len(rows) + 2, label=label)
+        assert sorted(got["position"][:got["count"]].tolist()) == np.flatnonzero(ok).tolist(), label
 
 
 def test_planted_cases_on_the_device(engine):
