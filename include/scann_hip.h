@@ -275,6 +275,39 @@ int scann_train_step_end(scann_handle_t* h, double* sse_out, int64_t* count_out,
 int scann_get_grads(scann_handle_t* h, float* out);           /* [scann_param_count] */
 int scann_get_weights(scann_handle_t* h, float* out);         /* current master parameters, same order */
 
+/* ---- fine-tuning: frozen tensors, per-tensor learning rates and a backward that stops at the floor ----
+ * Stage of a tensor, with L = n_attention:
+ *   0              the leaves: embed_atom, extra_embed, dense_embed, neighbor_d, neighbor_w
+ *   l + 1          local_attention_<l> and residual_norm_<l>, l = 0 .. L-1 (the base branch's per-layer filter_geo belongs to its layer)
+ *   L + 1          after_Lc, global_attention
+ *   L + 2          bf_property, predict_property
+ * scann_tensor_stage is pure host code and needs no handle; a name that is no tensor of such a model returns -1.
+ * Learning-rate scale: one fp32 factor s per tensor in scann_weight_name() order, finite and >= 0; NULL restores "all 1" and the
+ * unscaled optimiser kernel.  It may be set before or after scann_train_begin (it survives that call) and takes effect from the next
+ * scann_train_backward, scann_train_step[_begin] and scann_adam_step.  SCANN_ERR_INVALID, with a message that names the argument: a
+ * null handle, a negative or non-finite entry, every entry 0 (nothing to train), a call between scann_train_step_begin and its _end.
+ * Optimiser: an element of a tensor with s == 0 is frozen (Keras trainable = False) -- its weight and both Adam moments keep their
+ * bytes and the l2 regulariser term is not applied; its gradient entry is still zeroed where the step zeroes gradients.  For s > 0 the
+ * update is scann_adam_step's with lr_hat replaced by lr_hat * s (one fp32 product), through the same device function as the unscaled
+ * kernel: s == 1 gives its bytes.  The step counter advances as before.  With no scale set the launch is the unscaled kernel itself.
+ * Floor: the lowest stage that holds a tensor with s > 0.  A training backward launches nothing whose only consumers lie below the
+ * floor: no ResidualNorm / attention / geometry / base-branch backward, weight-gradient launch or reduction for the layers
+ * l < floor - 1; above stage 0 no basis leaf, no embedding leaf and no projection into them; at floor L + 2 the readout launches only
+ * what bf_property and predict_property need.  Inside the stages that run, the weight-gradient jobs of frozen tensors are not queued
+ * (a job that writes a kernel and its bias stays while either is trained); partial sums a fused kernel stores anyway stay.
+ * Gradient vector: entries of tensors in stages below the floor are not written by the backward (zero after scann_zero_grads);
+ * entries of frozen tensors in stages that ran are unspecified and never applied; trained tensors get the bytes of the whole
+ * backward.  The flat all-reduce is unchanged.
+ * scann_train_stages: bit k of *ran = stage k was entered by the last training backward enqueued on the handle (set by the stages
+ * themselves, not derived from the scale).
+ * The training forward is unchanged (Dropout stays active in frozen layers, as in Keras).  scann_input_grads, inference, model sets
+ * and every analysis call ignore scale and floor.  Plain-fp32 handles (widths other than 128 / 8): the optimiser rule holds; their
+ * backward is NOT cut at the floor, and scann_train_stages reports every stage. */
+int scann_tensor_stage(const char* name, int n_attention);
+int scann_set_lr_scale(scann_handle_t* h, const float* scale /* [scann_weight_count] or NULL */);
+int scann_get_lr_scale(const scann_handle_t* h, float* out /* [scann_weight_count]; all 1 when none is set */);
+int scann_train_stages(const scann_handle_t* h, uint64_t* ran);
+
 /* ---- gradients of the prediction with respect to the inputs (inference semantics) ----
  * d y_s / d input for every structure of a resident batch (inference semantics, dy_s = 1 per structure); synchronous.
  * y is the raw output (predict_property, before any target de-normalisation); mrelu (target e_b) passes the gradient through as the

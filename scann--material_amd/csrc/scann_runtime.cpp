@@ -497,7 +497,7 @@ void scann_destroy(scann_handle_t* h) {
     if (st.ev) (void)hipEventDestroy(st.ev);
   }
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  for (void* q : {(void*)h->t_master, (void*)h->t_grad, (void*)h->t_m, (void*)h->t_v, (void*)h->t_l2, (void*)h->t_descs, (void*)h->ig_grad})
+  for (void* q : {(void*)h->t_master, (void*)h->t_grad, (void*)h->t_m, (void*)h->t_v, (void*)h->t_l2, (void*)h->t_lrs, (void*)h->t_descs, (void*)h->ig_grad})
     if (q) (void)hipFree(q);
   if (h->comm) ncclCommDestroy(h->comm);
   if (h->train_aux && !h->train_aux_borrowed) (void)hipStreamDestroy(h->train_aux);

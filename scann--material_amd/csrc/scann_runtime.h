@@ -4,6 +4,7 @@
 #include "../../include/scann_hip.h"
 #include "scann_internal.h"
 #include "scann_train.h"
+#include "scann_train_plan.h"
 
 #include <rccl/rccl.h>
 
@@ -173,6 +174,12 @@ struct scann_handle {
   // scann_input_grads: where its backward's parameter-gradient side products go (never the training state above), allocated by its first call
   float* ig_grad = nullptr;
   int64_t t_step = 0;
+  // scann_set_lr_scale: one factor per tensor (empty: none set -- the unscaled adam_kernel, the whole backward), its per-element image
+  // for the scaled Adam kernel (built where the scale is set, and by scann_train_begin), and the backward's plan under it
+  std::vector<float> lr_scale;
+  float* t_lrs = nullptr;
+  scann::TrainPlan plan;
+  uint64_t stages_ran = 0;             // scann_train_stages: a bit per stage the last training backward entered
   float attn_drop_p = 0.f;             // use_drop: Dropout(0.05) on attention weights (scann_set_attention_dropout)
   bool deterministic = false;          // scann_set_deterministic: the backward's small reductions in a fixed order, no float atomics
   ncclComm_t comm = nullptr;

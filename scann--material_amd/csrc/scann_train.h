@@ -121,6 +121,9 @@ void launch_sse(const float* y, const float* t, int n, double* out, float* t_dev
 void launch_dy(const float* y, const float* t, int n, float scale, const double* stat, float* dy, hipStream_t s);
 void launch_adam(float* w, float* g, float* m, float* v, const float* l2mask, size_t n, float lr_hat, float b1, float b2,
                  float eps, float l2, int zero_g, hipStream_t s);
+// the same update under a per-element learning-rate factor (scann_set_lr_scale): lr_i = lr_hat * lrs[i]; lrs[i] == 0 leaves w, m, v alone
+void launch_adam_scaled(float* w, float* g, float* m, float* v, const float* l2mask, const float* lrs, size_t n, float lr_hat, float b1,
+                        float b2, float eps, float l2, int zero_g, hipStream_t s);
 void launch_repack(const RepackDesc* descs, int n, const float* master, float* arena, int32_t* range_flag, hipStream_t s);
 
 // ---- leaves of the data-gradient backward (scann_input_grad.hip; scann_input_grads) ----

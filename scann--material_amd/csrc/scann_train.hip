@@ -1795,22 +1795,48 @@ void launch_dy(const float* y, const float* t, int n, float scale, const double*
 // ---- Adam (tf.keras.optimizers.Adam, epsilon 1e-7) + l2 regulariser gradient ------------------------------------------------
 // g += 2*l2*w on regularised kernels; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; w -= lr_hat * m / (sqrt(v) + eps)
 // with lr_hat = lr_t * sqrt(1 - b2^t) / (1 - b1^t) computed by the caller.
-__global__ void adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            const float* __restrict__ l2mask, size_t n, float lr_hat, float b1, float b2, float eps,
-                            float l2, int zero_g) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// The arithmetic of one element, stated once for both kernels below: they cannot be contracted or rounded differently.
+__device__ __forceinline__ void adam_element(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                             const float* __restrict__ l2mask, size_t i, float lr_i, float b1, float b2, float eps, float l2,
+                                             int zero_g) {
   const float gi = g[i] + 2.0f * l2 * l2mask[i] * w[i];
   if (zero_g) g[i] = 0.f;  // scann_train_step: the next step starts from a zeroed gradient vector without a memset
   const float mi = b1 * m[i] + (1.0f - b1) * gi;
   const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
   m[i] = mi;
   v[i] = vi;
-  w[i] -= lr_hat * mi / (sqrtf(vi) + eps);
+  w[i] -= lr_i * mi / (sqrtf(vi) + eps);
+}
+__global__ void adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            const float* __restrict__ l2mask, size_t n, float lr_hat, float b1, float b2, float eps,
+                            float l2, int zero_g) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  adam_element(w, g, m, v, l2mask, i, lr_hat, b1, b2, eps, l2, zero_g);
 }
 void launch_adam(float* w, float* g, float* m, float* v, const float* l2mask, size_t n, float lr_hat, float b1, float b2,
                  float eps, float l2, int zero_g, hipStream_t s) {
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, g, m, v, l2mask, n, lr_hat, b1, b2, eps, l2, zero_g);
+}
+// scann_set_lr_scale: lrs[i] is the factor of the element's tensor.  0: the element is frozen (Keras trainable = False) -- w, m and v
+// keep their bytes, no regulariser term, and only the gradient is zeroed where the step zeroes gradients.  Otherwise lr_i = lr_hat * s,
+// one fp32 product (s == 1: lr_hat itself, the unscaled kernel's bytes).
+__global__ void adam_scaled_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                   const float* __restrict__ l2mask, const float* __restrict__ lrs, size_t n, float lr_hat, float b1,
+                                   float b2, float eps, float l2, int zero_g) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float sc = lrs[i];
+  if (sc == 0.f) {
+    if (zero_g) g[i] = 0.f;
+    return;
+  }
+  adam_element(w, g, m, v, l2mask, i, __fmul_rn(lr_hat, sc), b1, b2, eps, l2, zero_g);
+}
+void launch_adam_scaled(float* w, float* g, float* m, float* v, const float* l2mask, const float* lrs, size_t n, float lr_hat, float b1,
+                        float b2, float eps, float l2, int zero_g, hipStream_t s) {
+  hipLaunchKernelGGL(adam_scaled_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, g, m, v, l2mask, lrs, n, lr_hat, b1, b2, eps,
+                     l2, zero_g);
 }
 
 // ---- master weights -> MFMA fragment order (after every optimiser step) --------------------------------------------------------

@@ -108,6 +108,17 @@ int build_gen_transposes(scann_handle* h) {
   return SCANN_OK;
 }
 
+// scann_set_lr_scale: the per-element image of the per-tensor factors, as t_l2 is of the regulariser mask
+int upload_lr_scale(scann_handle* h) {
+  const size_t n = h->host_master.size();
+  std::vector<float> e(n, 1.0f);
+  for (size_t i = 0; i < h->specs.size(); ++i)
+    std::fill(e.begin() + h->spec_off[i], e.begin() + h->spec_off[i] + h->specs[i].numel(), h->lr_scale[i]);
+  if (!h->t_lrs) HIPCHK(h, hipMalloc((void**)&h->t_lrs, n * 4));
+  HIPCHK(h, hipMemcpy(h->t_lrs, e.data(), n * 4, hipMemcpyHostToDevice));
+  return SCANN_OK;
+}
+
 int64_t spec_offset(const scann_handle* h, const std::string& name) {
   for (size_t i = 0; i < h->specs.size(); ++i)
     if (h->specs[i].name == name) return h->spec_off[i];
@@ -513,20 +524,33 @@ struct Bwd {
   const float* dG_in = nullptr;  // gradient w.r.t. the geometry leaving layer l (none for the last layer)
   hipStream_t tail_s;            // where the embedding chain goes
   bool basis_done = false;
+  // which stages run and which jobs are queued (scann_train_plan.h): the handle's under scann_set_lr_scale; the data-gradient mode
+  // ignores the scale and runs everything
+  const TrainPlan plan;
 
   Bwd(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, const InGrad* ig)
       : h(h), db(db), w(w), ig(ig), c(h->cfg), L(c.n_attention), A(db->n_atom), E(db->n_edge), B(db->n_struct),
         nA((size_t)A * D), nE((size_t)E * D), G(ig ? h->ig_grad : h->t_grad), fused(h->train_fused),
         fuse_attn(fused && c.g_update && db->tile_rows == 32 && db->n_big == 0 && db->max_degree <= 16 && E > 0),
         st(h, ig != nullptr), dC(w.tA[0]), dCtx(w.tA[1]), edAng(w.tE[0]), eT(w.tE[1]), edGa(w.tE[2]), edGb(w.tE[3]),
-        tail_s(st.main) {
+        tail_s(st.main), plan(ig || h->lr_scale.empty() ? train_plan(c.n_attention, {}, nullptr) : h->plan) {
     wg.arena = w.wpart;
     wg.cap = w.wpart_floats;
   }
   float* g(const std::string& name) const { return G + spec_offset(h, name); }
-  template <class... T>
-  void wadd(T... a) {  // a weight gradient's GEMM job (none in the data-gradient mode)
-    if (!ig) wgrad_add(wg, a...);
+  // the stage functions mark the stage they enter (scann_train_stages); the data-gradient mode leaves the training state alone
+  void enter(int stage) const {
+    if (!ig && stage >= 0 && stage < 64) h->stages_ran |= (uint64_t)1 << stage;
+  }
+  int tensor_at(const float* p) const {  // the tensor a gradient pointer lies in (spec_off ascends)
+    const int64_t off = p - G;
+    return (int)(std::upper_bound(h->spec_off.begin(), h->spec_off.end(), off) - h->spec_off.begin()) - 1;
+  }
+  // a weight gradient's GEMM job (none in the data-gradient mode, none whose kernel and bias are both frozen)
+  void wadd(const float* X, const float* dY, float* dW, float* db, int rows, const int32_t* nb = nullptr, const float* X2 = nullptr) {
+    if (ig) return;
+    if (!plan.live.empty() && !plan.keep_job(tensor_at(dW), db ? tensor_at(db) : -1)) return;
+    wgrad_add(wg, X, dY, dW, db, rows, nb, X2);
   }
   BwdOperands operands(int l) const {
     float* const* a = &w.tA[5 + 5 * (size_t)l];
@@ -597,7 +621,13 @@ void bwd_readout(Bwd& b) {
   // (one slot per structure, summed in structure order with the layer's other vectors: 128 workgroups adding to the same 128
   // addresses was a queue of 16 k atomics)
   ra.dwo = reserve_vec(b.wg, b.g("predict_property/kernel"), b.B); ra.dbo = b.g("predict_property/bias");
+  b.enter(b.L + 2);
   if (!b.wg.overrun) launch_readout_bwd(ra, s, b.det != nullptr);
+  if (!b.plan.readout_body()) {  // floor at the property head: what bf_property and predict_property need, and no more
+    b.wadd(b.w.rep, b.w.dpre, b.g("bf_property/kernel"), b.g("bf_property/bias"), b.B);
+    return;
+  }
+  b.enter(b.L + 1);
   // the readout's four weight gradients ride with the first layer's launch on the side stream (their operands -- rep, dpre, z, dgq,
   // dgk and dpreA in the readout's operand set -- are not written again before the end of the step): no hand-off of their own,
   // each of which costs the main stream ~7 us (tools/fork_probe.hip)
@@ -615,6 +645,7 @@ void bwd_readout(Bwd& b) {
 int bwd_residual_norm(Bwd& b, const BwdLayer& y) {
   scann_handle_t* h = b.h;
   hipStream_t s = b.st.main;
+  b.enter(y.l + 1);
   if (!(b.fused && b.c.use_attn_norm)) b.pend.flush(b.dC, b.A, s);  // nobody below folds the projections of the layer above in
   if (!b.c.use_attn_norm) {
     HIPCHK(h, hipMemcpyAsync(b.dCtx, b.dC, b.nA * 4, hipMemcpyDeviceToDevice, s));
@@ -648,6 +679,7 @@ int bwd_residual_norm(Bwd& b, const BwdLayer& y) {
 // ---- LocalAttention backward (attention.py:118-216): softmax / LayerNorm backward per atom (unless it rides in the edge launch of
 // bwd_geometry), and the key / query weight-gradient jobs ----
 void bwd_attention(Bwd& b, const BwdLayer& y) {
+  b.enter(y.l + 1);
   if (!b.fuse_attn)
     launch_attn_bwd(b.wg, y.qL, y.KL, b.db->edge_offset, b.dCtx, y.p.ln_g, y.dQ, y.edK, b.g(y.la + "layer_norm/gamma"),
                     b.g(y.la + "layer_norm/beta"), b.A, b.db->max_degree, b.w.attn_p, DROP_TAG_ATTN + (unsigned)y.l, b.w.seed, b.st.main);
@@ -668,16 +700,18 @@ void bwd_reduce(Bwd& b, hipStream_t ws, bool last) { wgrad_flush(b.wg, last ? ws
 void bwd_base_branch(Bwd& b, const BwdLayer& y) {
   scann_dbatch_t* db = b.db;
   hipStream_t s = b.st.main;
+  b.enter(y.l + 1);
   launch_linear(y.edK, y.pt.WkT, nullptr, b.edAng, nullptr, b.E, 0, s);            // dang
   launch_edge_dang(y.c_in, db->edge_col, y.VL, b.edAng, nullptr, b.eT, y.eU, b.E, s);  // eT = dang * geomL ; eU = dgeomL = dang * c[j]
-  launch_gather_sum(b.eT, db->in_off, db->in_edge, b.dC, b.A, 0, s);               // dC[j] = sum over the edges that point at j
+  // dC[j] = sum over the edges that point at j (at the floor nothing below reads it)
+  if (b.plan.feeds_below(y.l)) launch_gather_sum(b.eT, db->in_off, db->in_edge, b.dC, b.A, 0, s);
   if (b.ig) {
     launch_base_input_grad(db->dist, db->weight, y.eU, y.p.Wfg, y.p.bfg, b.h->cd, b.E, D, b.ig->d_dist, b.ig->d_weight, s);
   } else {
     // the layer's weight gradients, their reduction and the filter_geo leaf beside the chain of the layers below
     hipStream_t ws = b.st.after(s, b.st.side);
     wgrad_launch(b.wg, ws);
-    bwd_reduce(b, ws, y.l == 0);
+    bwd_reduce(b, ws, y.l == b.plan.lowest_layer());
     launch_base_geom_bwd(db->gd, y.p.Wfg, y.p.bfg, db->weight, y.eU, b.E, b.g(y.la + "filter_geo/kernel"), b.g(y.la + "filter_geo/bias"), ws,
                          b.det);
   }
@@ -690,6 +724,7 @@ void bwd_basis_leaf(Bwd& b, const float* dG, hipEvent_t produced) {  // `produce
   scann_handle_t* h = b.h;
   scann_dbatch_t* db = b.db;
   hipStream_t bs = b.st.leaf(produced);
+  b.enter(0);
   if (b.ig)
     launch_basis_input_grad(db->dist, db->weight, dG, h->basis.Wd, h->basis.bd, h->basis.Ww, h->basis.bw, h->basis.cd, h->basis.cw, b.E, D,
                             b.ig->d_dist, b.ig->d_weight, bs);
@@ -707,6 +742,8 @@ hipEvent_t bwd_geometry(Bwd& b, const BwdLayer& y) {
   hipStream_t s = b.st.main;
   float* dGnext = (b.dG_in == b.edGa) ? b.edGb : b.edGa;  // d loss / d geometry entering layer l
   hipEvent_t ev_sums = nullptr;
+  const bool leaf = y.l == 0 && b.plan.leaves();  // the basis leaf is started from in here
+  b.enter(y.l + 1);
   if (b.fused) {
     // one kernel: dang = dK.Wk^T -> dG'tot = dang * c[j] + dG'(next layer) -> LayerNorm_g backward -> dV = dT * swish'(V) -> dG = dT + dV.W2^T
     EdgeBwdArgs ea{};
@@ -717,25 +754,25 @@ hipEvent_t bwd_geometry(Bwd& b, const BwdLayer& y) {
       AttnPart ab{};
       ab.q = y.qL; ab.K = y.KL; ab.dctx = b.dCtx; ab.gamma = y.p.ln_g; ab.edge_offset = db->edge_offset; ab.tiles = db->tiles;
       ab.dq = y.dQ; ab.dK = y.edK; ab.drop_p = b.w.attn_p; ab.drop_tag = DROP_TAG_ATTN + (unsigned)y.l; ab.drop_seed = b.w.seed;
-      if (y.l == 0 && b.st.side2) ev_dg = b.st.next_ev();
+      if (leaf && b.st.side2) ev_dg = b.st.next_ev();
       launch_attn_edge_bwd(b.wg, ea, ab, db->n_tile, b.g(y.la + "layer_norm_g/gamma"), b.g(y.la + "layer_norm_g/beta"),
                            b.g(y.la + "layer_norm/gamma"), b.g(y.la + "layer_norm/beta"), s, ev_dg);
     } else {
       launch_edge_bwd(b.wg, ea, b.g(y.la + "layer_norm_g/gamma"), b.g(y.la + "layer_norm_g/beta"), s);
     }
-    if (y.l == 0) bwd_basis_leaf(b, dGnext, ev_dg);  // (before the atom sums below: they do not touch the geometry gradient)
+    if (leaf) bwd_basis_leaf(b, dGnext, ev_dg);  // (before the atom sums below: they do not touch the geometry gradient)
     // dC[j] = sum over the edges that point at j of dang * G' (gate), dP3[j] = the same sum of dV, dP1[i] = sum of dV over i's own edges
     ev_sums = b.st.next_ev();  // ... and this launch's completion is what the layer's weight-gradient launch on the side stream waits for
     launch_atom_gather3(b.edAng, y.Gout, y.eU, db->edge_offset, db->in_off, db->in_edge, b.dC, y.dP1, y.dP3, b.A, s, ev_sums);
   } else {
     launch_linear(y.edK, y.pt.WkT, nullptr, b.edAng, nullptr, b.E, 0, s);  // dang
-    launch_gather_prod_sum(b.edAng, y.Gout, db->in_off, db->in_edge, b.dC, b.A, 0, s);
+    if (b.plan.feeds_below(y.l)) launch_gather_prod_sum(b.edAng, y.Gout, db->in_off, db->in_edge, b.dC, b.A, 0, s);  // (at the floor nothing reads dC)
     // LayerNorm_g backward with its neighbours fused: in  dG'tot = dang * c[j] + dG'(next layer), out  dT (residual path, -> dGnext)
     // and dV = dT * swish'(V) (-> eU)
     launch_ln_bwd_edge(b.wg, y.TL, y.p.lng_g, b.edAng, y.c_in, db->edge_col, b.dG_in, y.VL, dGnext, y.eU, b.g(y.la + "layer_norm_g/gamma"),
                        b.g(y.la + "layer_norm_g/beta"), b.E, s);
     launch_atom_sums(y.eU, db->edge_offset, db->in_off, db->in_edge, y.dP1, y.dP3, b.A, s);  // dP1[i]: the atom's own edges; dP3[j]: the edges that point at j
-    launch_linear(y.eU, y.pt.W2T, nullptr, dGnext, nullptr, b.E, 1, s);                      // dG += dV.W2^T
+    if (b.plan.feeds_below(y.l)) launch_linear(y.eU, y.pt.W2T, nullptr, dGnext, nullptr, b.E, 1, s);  // dG += dV.W2^T
   }
   float* fgk = b.g(y.la + "filter_geo/kernel");
   b.wadd(y.Gin, y.eU, fgk + (size_t)D * D, nullptr, b.E);  // dW2
@@ -765,7 +802,7 @@ void bwd_layer_wgrad(Bwd& b, int l, hipEvent_t ev_sums) {
   }
   hipStream_t ws = ev_sums ? b.st.after_event(ev_sums, b.st.side) : b.st.after(b.st.main, b.st.side);
   wgrad_launch(b.wg, ws);
-  bwd_reduce(b, ws, l == 0);
+  bwd_reduce(b, ws, l == b.plan.lowest_layer());
 }
 
 // ---- embedding (scann_model.py:362-374): the weight gradients of the table / dense_embed (general: ring, cgcnn), or in the
@@ -775,6 +812,7 @@ void bwd_embed_leaf(Bwd& b) {
   scann_dbatch_t* db = b.db;
   const scann_config_t& c = b.c;
   hipStream_t s = b.tail_s;
+  b.enter(0);
   if (b.ig) {
     if (!b.ig->d_ring && !b.ig->d_cgcnn) return;
     InputGradEmbed e{};
@@ -815,13 +853,17 @@ void bwd_embed_leaf(Bwd& b) {
 static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& w, float scale, const double* d_stat, bool dy_done,
                          const InGrad* ig = nullptr) {
   if (const int r = ensure_reverse(h, db)) return r;
-  if (h->generic) return gen_backward(h, db, w, scale, d_stat, dy_done, ig);
+  if (h->generic) {  // the plain-fp32 backward is not cut at the floor: it enters every stage, and says so
+    if (!ig) h->stages_ran = train_plan(h->cfg.n_attention, {}, nullptr).stage_bits();
+    return gen_backward(h, db, w, scale, d_stat, dy_done, ig);
+  }
   Bwd b(h, db, w, ig);
   hipStream_t s = b.st.main;
+  if (!ig) h->stages_ran = 0;
   if (!dy_done) launch_dy(db->y, w.targets, b.B, scale, d_stat, w.dy, s);
   if (const int r = bwd_det_arena(b)) return r;
   bwd_readout(b);  // its weight gradients ride with the first layer's launch
-  for (int l = b.L - 1; l >= 0; --l) {
+  for (int l = b.L - 1; l >= b.plan.lowest_layer(); --l) {  // the layers at and above the floor
     const BwdLayer y(b, l);
     if (const int r = bwd_residual_norm(b, y)) return r;
     bwd_attention(b, y);
@@ -834,13 +876,19 @@ static int backward_impl(scann_handle_t* h, scann_dbatch_t* db, scann_train_ws& 
   }
   // (the basis leaf first: it needs only the geometry gradient the last edge backward left, and at 43 us on its own stream it is
   // the longest thing between here and the optimiser -- started behind the embedding chain it ended 30 us after it)
-  if (b.dG_in && !b.basis_done) bwd_basis_leaf(b, b.dG_in, nullptr);
-  b.pend.flush(b.dC, b.A, b.tail_s);
-  bwd_embed_leaf(b);
+  if (b.plan.leaves()) {
+    if (b.dG_in && !b.basis_done) bwd_basis_leaf(b, b.dG_in, nullptr);
+    b.pend.flush(b.dC, b.A, b.tail_s);
+    bwd_embed_leaf(b);
+  } else if (b.det) {
+    // (deterministic mode sums the readout's bias gradient beside the embedding chain: without that chain, here)
+    launch_scalar_sum(b.w.dy, b.B, b.g("predict_property/bias"), s);
+  }
   if (b.det && b.dct.overrun) return fail(h, SCANN_ERR_HIP, "scann_train_backward: deterministic partial arena overrun");
   if (b.wg.overrun) return fail(h, SCANN_ERR_HIP, "scann_train_backward: weight-gradient partial arena overrun");
   if (!ig) {
-    if (!b.wg.jobs.empty()) wgrad_launch(b.wg, s);  // a model without LocalAttention layers: the readout's gradients were never launched
+    // a model without LocalAttention layers, or a floor above them: the readout's gradients were never launched
+    if (!b.wg.jobs.empty()) wgrad_launch(b.wg, s);
     b.st.join_all();
     wgrad_flush(b.wg, s);  // ONE launch adds the per-slab partials of every weight gradient, in slab order
   }
@@ -855,7 +903,8 @@ static int adam_impl(scann_handle_t* h, float lr_t, float beta1, float beta2, fl
   const float lr_hat = (float)((double)lr_t * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
   const size_t n = h->host_master.size();
   // t_l2 holds a 0/1 mask; fold the coefficient in by scaling through the kernel argument
-  launch_adam(h->t_master, h->t_grad, h->t_m, h->t_v, h->t_l2, n, lr_hat, beta1, beta2, eps, l2, zero_g, s);
+  if (h->lr_scale.empty()) launch_adam(h->t_master, h->t_grad, h->t_m, h->t_v, h->t_l2, n, lr_hat, beta1, beta2, eps, l2, zero_g, s);
+  else launch_adam_scaled(h->t_master, h->t_grad, h->t_m, h->t_v, h->t_l2, h->t_lrs, n, lr_hat, beta1, beta2, eps, l2, zero_g, s);
   if (h->generic) {  // the plain kernels read the Keras tensors as they are: the forward's copy is the master vector
     HIPCHK(h, hipMemcpyAsync(h->g_weights, h->t_master, n * 4, hipMemcpyDeviceToDevice, s));
     return SCANN_OK;
@@ -903,6 +952,8 @@ int scann_train_begin(scann_handle_t* h) {
     if (reg) std::fill(l2.begin() + h->spec_off[i], l2.begin() + h->spec_off[i] + h->specs[i].numel(), 1.0f);
   }
   HIPCHK(h, hipMemcpy(h->t_l2, l2.data(), n * 4, hipMemcpyHostToDevice));
+  if (!h->lr_scale.empty())  // a scale set before this call survives it
+    if (const int r = upload_lr_scale(h)) return r;
   if (h->generic) {
     if (const int r = build_gen_transposes(h)) return r;
   } else if (!h->train_aux) {
@@ -943,6 +994,56 @@ int scann_set_attention_dropout(scann_handle_t* h, float p) {
 int scann_set_deterministic(scann_handle_t* h, int on) {
   if (!h) return SCANN_ERR_INVALID;
   h->deterministic = on != 0;  // read by each backward as it is enqueued (plain-fp32 handles: every sum is fixed-order already)
+  return SCANN_OK;
+}
+
+int scann_tensor_stage(const char* name, int n_attention) { return tensor_stage(name, n_attention); }
+
+int scann_set_lr_scale(scann_handle_t* h, const float* scale) {
+  if (!h) return fail(h, SCANN_ERR_INVALID, "scann_set_lr_scale: h is null");
+  if (h->step_begun != h->step_ended)
+    return fail(h, SCANN_ERR_INVALID, "scann_set_lr_scale: a step is in flight (between scann_train_step_begin and its _end)");
+  if (!scale) {  // all 1: the unscaled kernel and the whole backward
+    h->lr_scale.clear();
+    h->plan = TrainPlan{};
+    return SCANN_OK;
+  }
+  const size_t nt = h->specs.size();
+  bool any = false;
+  for (size_t i = 0; i < nt; ++i) {
+    if (!(scale[i] >= 0.f) || !std::isfinite(scale[i]))
+      return fail(h, SCANN_ERR_INVALID, "scann_set_lr_scale: scale[" + std::to_string(i) + "] (" + h->specs[i].name + ") is negative or not finite");
+    any = any || scale[i] > 0.f;
+  }
+  if (!any) return fail(h, SCANN_ERR_INVALID, "scann_set_lr_scale: every entry of scale is 0: nothing to train");
+  std::vector<float> keep(scale, scale + nt);
+  if (h->t_master) {  // in training mode: the per-element image now (scann_train_begin builds it otherwise)
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->streams[0]));  // an optimiser step enqueued earlier may still read the image
+    h->lr_scale.swap(keep);
+    const int r = upload_lr_scale(h);
+    if (r) {
+      h->lr_scale.swap(keep);
+      return r;
+    }
+  } else {
+    h->lr_scale.swap(keep);
+  }
+  std::vector<std::string> names;
+  for (const WeightSpec& sp : h->specs) names.push_back(sp.name);
+  h->plan = train_plan(h->cfg.n_attention, names, h->lr_scale.data());
+  return SCANN_OK;
+}
+
+int scann_get_lr_scale(const scann_handle_t* h, float* out) {
+  if (!h || !out) return fail(const_cast<scann_handle_t*>(h), SCANN_ERR_INVALID, h ? "scann_get_lr_scale: out is null" : "scann_get_lr_scale: h is null");
+  for (size_t i = 0; i < h->specs.size(); ++i) out[i] = h->lr_scale.empty() ? 1.0f : h->lr_scale[i];
+  return SCANN_OK;
+}
+
+int scann_train_stages(const scann_handle_t* h, uint64_t* ran) {
+  if (!h || !ran) return fail(const_cast<scann_handle_t*>(h), SCANN_ERR_INVALID, h ? "scann_train_stages: ran is null" : "scann_train_stages: h is null");
+  *ran = h->stages_ran;
   return SCANN_OK;
 }
 

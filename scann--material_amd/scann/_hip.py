@@ -92,6 +92,10 @@ SYMBOLS = [
     ("scann_train_step_end", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     ("scann_get_grads", C.c_int, [_P, _P]),
     ("scann_get_weights", C.c_int, [_P, _P]),
+    ("scann_tensor_stage", C.c_int, [C.c_char_p, C.c_int]),
+    ("scann_set_lr_scale", C.c_int, [_P, _P]),
+    ("scann_get_lr_scale", C.c_int, [_P, _P]),
+    ("scann_train_stages", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("scann_comm_unique_id", C.c_int, [C.c_char_p]),
     ("scann_comm_init", C.c_int, [_P, C.c_char_p, C.c_int, C.c_int]),
     ("scann_comm_ranks", C.c_int, [_P]),
@@ -2701,10 +2705,54 @@ class Engine:
         self._check(self.lib.scann_train_step_end(self._h, C.byref(sse), C.byref(cnt), C.byref(sabs)))
         return sse.value, cnt.value, sabs.value
 
-    def get_grads(self):
+    def get_grads(self, masked=True):
+        """The gradient vector as a dict.  Under a learning-rate scale (set_lr_scale) the entries of frozen tensors are unspecified
+        where their stage ran; masked=True (the default) returns zeros for every frozen tensor, masked=False the raw entries."""
         flat = np.empty(self.param_count(), dtype=np.float32)
         self._check(self.lib.scann_get_grads(self._h, _ptr(flat)))
-        return self._unflatten(flat)
+        out = self._unflatten(flat)
+        if masked:
+            for name, s in self.lr_scale().items():
+                if s == 0.0:
+                    out[name] = np.zeros_like(out[name])
+        return out
+
+    def set_lr_scale(self, scale):
+        """Per-tensor learning-rate factors (scann_set_lr_scale): a mapping tensor name -> factor (finite, >= 0; tensors it does not
+        name keep 1), a sequence in weight_specs() order, or None for "all 1" and the unscaled optimiser.  A tensor with factor 0 is
+        frozen, and the training backward stops above the lowest stage that still holds a trained tensor."""
+        if scale is None:
+            self._check(self.lib.scann_set_lr_scale(self._h, None))
+            return
+        names = [n for n, _ in self.weight_specs()]
+        if hasattr(scale, "items"):
+            unknown = sorted(set(scale) - set(names))
+            if unknown:
+                raise ValueError("set_lr_scale: no tensor named " + ", ".join(unknown))
+            vec = np.array([float(scale.get(n, 1.0)) for n in names], dtype=np.float32)
+        else:
+            vec = np.ascontiguousarray(scale, dtype=np.float32).ravel()
+            if vec.size != len(names):
+                raise ValueError("set_lr_scale: %d factors for %d tensors" % (vec.size, len(names)))
+        self._check(self.lib.scann_set_lr_scale(self._h, _ptr(vec)))
+
+    def lr_scale(self):
+        """{tensor name: factor} as the handle holds it (scann_get_lr_scale); all 1.0 when none is set"""
+        names = [n for n, _ in self.weight_specs()]
+        vec = np.empty(len(names), dtype=np.float32)
+        self._check(self.lib.scann_get_lr_scale(self._h, _ptr(vec)))
+        return {n: float(v) for n, v in zip(names, vec)}
+
+    def train_stages(self):
+        """The stages the last training backward entered (scann_train_stages), ascending: 0 the leaves, l + 1 layer l,
+        n_attention + 1 after_Lc / GlobalAttention, n_attention + 2 the property head."""
+        ran = C.c_uint64()
+        self._check(self.lib.scann_train_stages(self._h, C.byref(ran)))
+        return [k for k in range(64) if (ran.value >> k) & 1]
+
+    def tensor_stage(self, name):
+        """Stage of a tensor name for this model's layer count (scann_tensor_stage); -1 for an unknown name"""
+        return int(self.lib.scann_tensor_stage(name.encode(), int(self.cfg.n_attention)))
 
     def get_weights(self):
         flat = np.empty(self.param_count(), dtype=np.float32)

@@ -26,7 +26,10 @@ INPUT_NAMES = ["atomic", "atom_mask", "neighbors", "neighbor_mask", "neighbor_we
 _MODEL_DEFAULTS = dict(feature="atomic", use_ring=False, use_drop=False, g_update=False, gaussian_d=4.0,
                        use_attn_norm=True, use_ga_norm=True)
 # deterministic (extension, train.py --deterministic): bit-reproducible training steps and initial weights drawn from hyper.seed
-_HYPER_DEFAULTS = dict(scaler=False, scheduler="cosine", use_ref=False, target="", pretrained="", deterministic=False)
+# freeze / lr_scale / reset (extension, train.py --freeze / --lr-scale / --reset; scann/models/finetune.py): fine-tuning -- patterns over
+# tensor names that freeze tensors, scale their learning rate, or draw them afresh after a pretrained checkpoint is loaded; None: absent
+_HYPER_DEFAULTS = dict(scaler=False, scheduler="cosine", use_ref=False, target="", pretrained="", deterministic=False,
+                       freeze=None, lr_scale=None, reset=None)
 
 
 def normalize_config(config):
@@ -1415,6 +1418,15 @@ class SCANN:
                 print("load pretrained model from ", pretrained, "\n")
                 self.model = create_model_pretrained(pretrained)
                 self.config["hyper"]["pretrained"] = pretrained
+                if mode == "train" and self.config["hyper"]["reset"]:
+                    # the head for a new target: the matched tensors from the model's own initialisers (under --deterministic the
+                    # draw comes from hyper.seed, like a fresh model's)
+                    from .finetune import reset_weights
+
+                    seed = int(self.config["hyper"].get("seed", 0)) if self.config["hyper"]["deterministic"] else None
+                    w, done = reset_weights(self.model.get_weights(), self.model.engine.weight_specs(), self.config["hyper"]["reset"], seed)
+                    self.model.set_weights(w)
+                    print("re-initialised %d tensors: %s\n" % (len(done), ", ".join(done)))
             elif self.config["hyper"]["deterministic"]:
                 # reproducible run: the initial weights come from hyper.seed as well, not from fresh OS entropy
                 self.model = create_model(self.config, seed=int(self.config["hyper"].get("seed", 0)))

@@ -195,6 +195,16 @@ def fit(scann, epochs=1000, dropout=0.1, verbose=True):
     model = scann.model
     eng = model.engine
     eng.train_begin()
+    # fine-tuning (hyper.freeze / hyper.lr_scale, scann/models/finetune.py): every rank reads the same configuration, so every rank
+    # freezes the same tensors and cuts its backward at the same stage; applied before the first step
+    # (a run without either key asks the engine for nothing new: the optimiser and the backward are the unscaled ones)
+    from .finetune import lr_scale_of_config, trainable_counts
+
+    specs, scale = None, None
+    if hy.get("freeze") or hy.get("lr_scale"):
+        specs = eng.weight_specs()
+        scale = lr_scale_of_config(cfg, [n for n, _ in specs])
+        eng.set_lr_scale(scale)
     attn_drop = 0.05 if cfg["model"].get("use_drop") else 0.0  # attention.py:115-116
     comm = Communicator(eng)
     train_it, valid_it = scann.trainIter, scann.validIter
@@ -210,6 +220,11 @@ def fit(scann, epochs=1000, dropout=0.1, verbose=True):
     hist = {k: [] for k in ("loss", "mae", "r2_square", "val_loss", "val_mae", "val_r2_square", "lr")}
     best, wait, it = float("inf"), 0, 0
     l2 = 1e-4
+    if verbose and comm.rank == 0:
+        if specs is None:
+            specs = [(k, np.shape(v)) for k, v in eng.get_weights().items()]
+        n_train, n_total = trainable_counts(specs, scale)
+        print("Trainable params: {:,} / {:,}".format(n_train, n_total))
 
     def run_epoch(iterator, training, epoch_lr):
         nonlocal it

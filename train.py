@@ -5,7 +5,10 @@ kept because downstream scripts grep them.
 
 Extensions: ``--epochs`` (the reference hard-codes 1000, train.py:53), ``--packed`` (flat-CSR ``PackedDataset`` iterators instead
 of the nested-list ``DataIterator``), ``--gpus N`` (test-set prediction spread over N devices), ``--seed``, ``--deterministic``
-(bit-reproducible training: fixed-order gradient sums on the GPU and initial weights drawn from ``--seed``).
+(bit-reproducible training: fixed-order gradient sums on the GPU and initial weights drawn from ``--seed``), and the fine-tuning flags
+``--freeze PATTERNS`` / ``--lr-scale PATTERN=S,...`` / ``--reset PATTERNS`` (``fnmatch`` patterns over tensor names, comma-separated;
+``hyper.freeze`` / ``hyper.lr_scale`` / ``hyper.reset``, scann/models/finetune.py): with ``--pretrained``, freeze the body, scale the
+learning rate of some tensors, draw the head afresh for a new target.
 
 Data-parallel training is one process per GPU: ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 train.py ...`` or ``scann.parallel.spawn_ranks(["train.py", ...], N)``; every rank runs this file, rank 0 reports."""
@@ -20,6 +23,7 @@ import yaml
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "scann--material_amd"))
 from scann.models import SCANN  # noqa: E402
+from scann.models.finetune import parse_pattern_list, parse_scale_list  # noqa: E402
 
 # command-line flag -> (config section, key): what the reference's main() copies into the yaml dict before building the model
 OVERRIDES = {
@@ -59,6 +63,13 @@ def configured(args):
     if args.deterministic:
         config["hyper"]["deterministic"] = True
         config["hyper"]["seed"] = args.seed
+    # fine-tuning: a flag that is given replaces the yaml's key; the rules are checked against the model's tensors when training starts
+    if parse_pattern_list(args.freeze) is not None:
+        config["hyper"]["freeze"] = parse_pattern_list(args.freeze)
+    if parse_scale_list(args.lr_scale) is not None:
+        config["hyper"]["lr_scale"] = parse_scale_list(args.lr_scale)
+    if parse_pattern_list(args.reset) is not None:
+        config["hyper"]["reset"] = parse_pattern_list(args.reset)
     return config
 
 
@@ -90,6 +101,12 @@ def parser():
     p.add_argument("--packed", action="store_true", help="PackedDataset iterators (flat CSR, native slicing)")
     p.add_argument("--gpus", type=int, default=0, help="devices for the test-set prediction of evaluate()")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--freeze", type=str, default=None, help="fine-tuning: comma-separated patterns of tensors to freeze, e.g. "
+                   "'embed_atom/*,local_attention_[0-4]/*'")
+    p.add_argument("--lr-scale", dest="lr_scale", type=str, default=None, help="fine-tuning: PATTERN=S,... learning-rate factors, "
+                   "e.g. 'local_attention_*=0.1'; applied after --freeze, the last match wins")
+    p.add_argument("--reset", type=str, default=None, help="fine-tuning: comma-separated patterns of tensors to draw afresh after "
+                   "--pretrained is loaded, e.g. 'bf_property/*,predict_property/*'")
     return p
 
 
